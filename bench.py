@@ -8,7 +8,12 @@ overlap-save, F = 512 @ 48 kHz); at N GPUs the job is 8192*N sources (configs[3]
 weak scaling, one process per GPU, partial mixes sum-reduced to rank 0 over RCCL.  `--workload`
 selects the other configs for ad-hoc runs.
 
-Prints ONE JSON line on rank 0 (contract in the task statement).  How the numbers are taken:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run measures the headline and nothing else:
+set-up, warm-up, the --steps timed callbacks, the line.  `--full` adds every other figure below (the marked roofline pass,
+the `ordered` / `exact_peaks` / `latency` / ... passes, `max_sources_under_10ms`, `cpu_baseline`), each still switched
+off by its own --no-* option.  `--dump-outputs DIR` writes what the last timed callback returned to its caller (the mix
+and the peaks the caller reads, float32 .npy) so that two builds can be compared output for output: with the same arguments
+the inputs are the same in every run.  How the numbers are taken:
 
 * `value` / `ms_per_step`: EXACTLY --steps callbacks, queued back to back after --warmup untimed ones,
   bracketed by barrier + torch.cuda.synchronize() on both sides; the time is the span between ONE pair of
@@ -51,6 +56,20 @@ WORKLOADS = {
 HBM_PEAK = 8.0e12  # MI355X_MICROARCH.md: 8 TB/s spec
 N_SRC_BUFFERS_BYTES = int(os.environ.get("GAS_BENCH_SRC_BYTES", 320 << 20))  # rotate source buffers over > 256 MiB so the Infinity Cache cannot hold them (the override is a cache experiment, never the headline)
 CONDITION_STEPS = 64  # untimed callbacks in front of the --warmup ones: clocks and caches settle independently of --warmup
+DUMP_BYTES = 64 * 10**6  # --dump-outputs writes at most this much in all
+
+
+def dump_outputs(path, arrays):
+    """Writes each named array as <path>/<name>.npy in float32.  An array larger than its equal share of DUMP_BYTES is cut
+    to a fixed, seeded sample of its rows: the same rows in every run with the same arguments."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // len(arrays)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if a.nbytes > share:
+            keep = np.sort(np.random.default_rng(0).choice(len(a), share // a[0].nbytes, replace=False))
+            a = a[keep]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def lib_sha16():
@@ -221,10 +240,12 @@ class Runner:
             self.ctx.hrtf_load(env["hrir"])
         self.slots = self.ctx.source_alloc_many(n_local, kind, chain)
         self.n_draining = 0
+        self.draining_rows = np.arange(0)  # positions in the callback's source list
         if kind == 2 and args.draining_every > 0:
             for s_ in self.slots[:: args.draining_every]:
                 self.ctx.source_set_draining(int(s_), True)
                 self.n_draining += 1
+            self.draining_rows = np.arange(0, n_local, args.draining_every)
         # two physics ticks of parameters, device-resident, alternated every 2 callbacks
         prng = np.random.default_rng(1234 + 7919 * env["rank"])
         self.psets = []
@@ -343,6 +364,19 @@ class Runner:
         self.fence()
         dt_wall = time.perf_counter() - t0
         return ev0.elapsed_time(ev1), dt_wall * 1e3, t_enq * 1e3
+
+    def outputs(self, k):
+        """What callback k of the last pass handed its caller: its mix (on rank 0 the sum over ranks) and the peaks the
+        caller reads.  Under GAS_FLAG_PEAKS_DRAINING_ONLY those are the draining sources' (none: no peaks); every other
+        source's peak is +inf there, "not measured" (gas_amd.h).  Valid right after that pass, before the next one
+        reuses the buckets."""
+        out = {"mix": self.buckets[(k // self.B) % 2][k % self.B].cpu().numpy()}
+        peaks = self.peaks.cpu().numpy()
+        if self.flags & self.gas.capi.FLAG_PEAKS_DRAINING_ONLY:
+            peaks = peaks[self.draining_rows]
+        if len(peaks):
+            out["peaks"] = peaks
+        return out
 
     def marked(self, callbacks):
         """Dominant-kernel time from HIP events recorded inside the library around every callback's main launch."""
@@ -474,7 +508,13 @@ def main():
     ap.add_argument("--draining-every", type=int, default=64, help="1 source in N has ended its stream (exact peak needed, audio_spatializer.cpp:464-469); 0 = none")
     ap.add_argument("--exact-peaks", action="store_true", help="headline with the exact peak of every source")
     ap.add_argument("--in-process", action="store_true", help="ONE process drives --gpus N devices through gas_multi_* (all-to-one peer writes of the 4 KiB partial mixes, one ordered sum on device 0, every callback: the real-time arrangement); launch WITHOUT torchrun.  With fewer visible GPUs than N the shards share the devices there are (one GPU: the per-callback cost of the gather + root sum)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the marked roofline pass, the extras, the max-sources probe and the CPU baseline (each still subject to its --no-* / --marked-callbacks option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed callback's mix and the peaks its caller reads (the draining sources' unless --exact-peaks) to DIR/mix.npy, DIR/peaks.npy (float32; rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.in_process and args.dump_outputs:
+        ap.error("--dump-outputs is not implemented for --in-process")
 
     import torch
     import torch.distributed as dist
@@ -536,14 +576,17 @@ def main():
     # ---- headline pass: exactly --steps callbacks, no markers inside -----------------------------------------------
     run = Runner(env, head_flags, n_local, args.reduce_bucket)
     gpu_ms, wall_ms, enq_ms = run.timed(args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, run.outputs(args.steps - 1))
     if world > 1:
         tmax = torch.tensor([gpu_ms, wall_ms], device="cuda" if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         gpu_ms, wall_ms = float(tmax[0].item()), float(tmax[1].item())
     ms_per_step = gpu_ms / args.steps
     value = n_total * frames * args.steps / (gpu_ms * 1e-3)
-    # ---- marked pass: the dominant kernel's span, events inside the library ----------------------------------------
-    prof = run.marked(args.marked_callbacks) if args.marked_callbacks > 0 else {"launches": 0, "kernel_ms": 0.0, "bytes_per_launch": 0, "kernel": ""}
+    # ---- marked pass (--full): the dominant kernel's span, events inside the library --------------------------------
+    if args.full:
+        prof = run.marked(args.marked_callbacks) if args.marked_callbacks > 0 else {"launches": 0, "kernel_ms": 0.0, "bytes_per_launch": 0, "kernel": ""}
     n_draining = run.n_draining
 
     result = None
@@ -585,13 +628,14 @@ def main():
                 "reduce_bucket": run.B,
                 "realtime_budget_ms": frames / 48000.0 * 1e3,
             },
-            "roofline": roofline_entry(prof, n_local, desc, peaks_desc, not args.no_pipelined_mix, experiment),
         }
+        if args.full:
+            result["roofline"] = roofline_entry(prof, n_local, desc, peaks_desc, not args.no_pipelined_mix, experiment)
+            achieved = result["roofline"]["achieved"] * 1e9
         result["config"]["lib_sha16"] = lib_sha16()
-        achieved = result["roofline"]["achieved"] * 1e9
 
-    # ---- extras on one GPU ------------------------------------------------------------------------------------------
-    extras = rank == 0 and world == 1 and not args.no_extras
+    # ---- extras on one GPU (--full) ---------------------------------------------------------------------------------
+    extras = args.full and rank == 0 and world == 1 and not args.no_extras
     if extras:
         try:
             # same-run copy-bandwidth ceiling over the dominant launch's algorithmic bytes (reads: frames + history +
@@ -736,7 +780,7 @@ def main():
             result["extras_error"] = repr(e)
     env["srcs"].clear()
     torch.cuda.empty_cache()
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         if not args.no_max_sources and args.workload.startswith("hrtf") and not args.no_extras:
             try:
                 result["max_sources_under_10ms"] = probe_max_sources(gas, synth, torch, kind, chain, frames, hrir, args.dirs)

@@ -24,6 +24,40 @@ FX_LOWPASS, FX_HIGHPASS, FX_BANDPASS, FX_NOTCH, FX_LOWSHELF, FX_AMPLIFY = 4, 5, 
 MAX_EFFECTS = 4
 # gas_fx_settings: settings of the engine-effect kinds by chain position (64 bytes)
 FX_SETTINGS_DTYPE = np.dtype([("filter_cutoff_hz", np.float32, (MAX_EFFECTS,)), ("filter_resonance", np.float32, (MAX_EFFECTS,)), ("filter_gain", np.float32, (MAX_EFFECTS,)), ("amplify_volume_db", np.float32, (MAX_EFFECTS,))])
+# the engine's nonlinear / dynamics kinds (10 is not assigned); settings: gas_fx_dyn_settings by chain position
+FX_DISTORTION, FX_COMPRESSOR = 11, 12
+DISTORTION_CLIP, DISTORTION_ATAN, DISTORTION_LOFI, DISTORTION_OVERDRIVE, DISTORTION_WAVESHAPE = 0, 1, 2, 3, 4
+FX_DYN_SETTINGS_DTYPE = np.dtype(
+    [
+        ("distortion_mode", np.int32, (MAX_EFFECTS,)),
+        ("distortion_pre_gain_db", np.float32, (MAX_EFFECTS,)),
+        ("distortion_keep_hf_hz", np.float32, (MAX_EFFECTS,)),
+        ("distortion_drive", np.float32, (MAX_EFFECTS,)),
+        ("distortion_post_gain_db", np.float32, (MAX_EFFECTS,)),
+        ("compressor_threshold_db", np.float32, (MAX_EFFECTS,)),
+        ("compressor_ratio", np.float32, (MAX_EFFECTS,)),
+        ("compressor_gain_db", np.float32, (MAX_EFFECTS,)),
+        ("compressor_attack_us", np.float32, (MAX_EFFECTS,)),
+        ("compressor_release_ms", np.float32, (MAX_EFFECTS,)),
+        ("compressor_mix", np.float32, (MAX_EFFECTS,)),
+        ("reserved", np.uint32, (MAX_EFFECTS,)),
+    ]
+)
+assert FX_DYN_SETTINGS_DTYPE.itemsize == 192
+
+
+def fx_dyn_settings_defaults(n):
+    """[ENGINE] AudioEffectDistortion / AudioEffectCompressor resource defaults, n rows."""
+    d = np.zeros(n, FX_DYN_SETTINGS_DTYPE)
+    d["distortion_mode"] = DISTORTION_CLIP
+    d["distortion_keep_hf_hz"] = 16000.0
+    d["compressor_ratio"] = 4.0
+    d["compressor_attack_us"] = 20.0
+    d["compressor_release_ms"] = 250.0
+    d["compressor_mix"] = 1.0
+    return d
+
+
 MEM_HOST = 0
 MEM_DEVICE = 1
 FLAG_PEAKS_DRAINING_ONLY = 1
@@ -164,6 +198,7 @@ EXPORTS = [
     "gas_source_set_draining",
     "gas_params_publish",
     "gas_fx_settings_publish",
+    "gas_fx_dyn_settings_publish",
     "gas_params_publish_batch",
     "gas_hrtf_load",
     "gas_hrtf_load_positions",
@@ -245,6 +280,7 @@ def load_library():
     L.gas_source_set_draining.argtypes = [vp, u32, i32]
     L.gas_params_publish.argtypes = [vp, u32, vp]
     L.gas_fx_settings_publish.argtypes = [vp, vp, vp, u32]
+    L.gas_fx_dyn_settings_publish.argtypes = [vp, vp, vp, u32]
     L.gas_params_publish_batch.argtypes = [vp, vp, vp, u32, i32]
     L.gas_hrtf_load.argtypes = [vp, vp, u32, u32]
     L.gas_hrtf_load_positions.argtypes = [vp, vp, vp, u32, u32, u32, u32, i32, vp]
@@ -353,6 +389,16 @@ class SpatializerContext:
         f = np.ascontiguousarray(settings, dtype=FX_SETTINGS_DTYPE)
         assert s.shape == f.shape
         self._check(self.lib.gas_fx_settings_publish(self.h, _np_ptr(s), _np_ptr(f), len(s)), "gas_fx_settings_publish")
+
+    @staticmethod
+    def fx_dyn_settings_defaults(n):
+        return fx_dyn_settings_defaults(n)
+
+    def fx_dyn_settings_publish(self, slots, settings):
+        s = np.ascontiguousarray(slots, dtype=np.uint32)
+        f = np.ascontiguousarray(settings, dtype=FX_DYN_SETTINGS_DTYPE)
+        assert s.shape == f.shape
+        self._check(self.lib.gas_fx_dyn_settings_publish(self.h, _np_ptr(s), _np_ptr(f), len(s)), "gas_fx_dyn_settings_publish")
 
     def params_publish_batch(self, slots, params):
         s = np.ascontiguousarray(slots, dtype=np.uint32)
@@ -551,6 +597,7 @@ class BatchedSpatializerHost:
         L.gas_host_get_playback_position.argtypes = [vp, u32, C.POINTER(C.c_uint64)]
         L.gas_host_get_mixed_frames.argtypes = [vp, i32, vp, i32]
         L.gas_host_set_effect_settings.argtypes = [vp, u32, vp]
+        L.gas_host_set_effect_settings_dyn.argtypes = [vp, u32, vp]
         L.gas_host_set_release_fn.argtypes = [vp, vp, vp]
         L.gas_host_collect_released.argtypes = [vp]
         L.gas_host_set_process_effects_fn.argtypes = [vp, vp, vp]
@@ -632,6 +679,10 @@ class BatchedSpatializerHost:
     def set_effect_settings(self, pid, settings):
         f = np.ascontiguousarray(settings, dtype=FX_SETTINGS_DTYPE).reshape(1)
         return self.lib.gas_host_set_effect_settings(self.h, pid, _np_ptr(f))
+
+    def set_effect_dyn_settings(self, pid, settings):
+        f = np.ascontiguousarray(settings, dtype=FX_DYN_SETTINGS_DTYPE).reshape(1)
+        return self.lib.gas_host_set_effect_settings_dyn(self.h, pid, _np_ptr(f))
 
     def is_playback_active(self, pid):
         return bool(self.lib.gas_host_is_playback_active(self.h, pid))

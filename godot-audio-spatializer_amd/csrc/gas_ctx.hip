@@ -121,6 +121,13 @@ struct gas_ctx {
 	std::vector<uint8_t> fx_dirty_flag;
 	std::vector<uint32_t> fx_dirty_list;
 	gas_fx_settings *h_fx_upload = nullptr; // pinned, [max_sources], allocated by the first flush that needs it
+	// gas_fx_dyn_settings (GAS_FX_DISTORTION / GAS_FX_COMPRESSOR): host mirror, latest wins (params_mu); uploaded as ONE
+	// copy of [m settings][m slots] out of a pinned staging buffer, then scattered on the device (k_scatter_dyn)
+	std::vector<gas_fx_dyn_settings> h_dyn;
+	std::vector<uint8_t> dyn_dirty_flag;
+	std::vector<uint32_t> dyn_dirty_list;
+	unsigned char *h_dyn_upload = nullptr; // pinned, [max_sources] settings then [max_sources] slots
+	unsigned char *d_dyn_upload = nullptr;
 
 	// plain [HRTF] group of the cached list (k_hrtf_uni): which entries need their exact peak
 	uint32_t *h_peak_bits = nullptr, *d_peak_bits = nullptr; // two halves of (max_sources + 31) / 32 words: bit k = entry k of the plain-[HRTF] group / of the staged group
@@ -272,7 +279,7 @@ int group_of(int kind, const int32_t *fx, uint32_t n_fx) {
 	// reflection ring and one HRTF history per playback
 	int n_er = 0, n_hrtf = 0;
 	for (uint32_t j = 0; j < n_fx; j++) {
-		if (fx[j] < GAS_FX_HIGHSHELF || fx[j] > GAS_FX_AMPLIFY) {
+		if ((fx[j] < GAS_FX_HIGHSHELF || fx[j] > GAS_FX_AMPLIFY) && fx[j] != GAS_FX_DISTORTION && fx[j] != GAS_FX_COMPRESSOR) {
 			return -1;
 		}
 		n_er += fx[j] == GAS_FX_EARLY_REFLECTIONS;
@@ -304,6 +311,35 @@ gas_fx_settings fx_settings_defaults() {
 		d.amplify_volume_db[j] = 0.0f;
 	}
 	return d;
+}
+
+// [ENGINE] AudioEffectDistortion / AudioEffectCompressor resource defaults
+gas_fx_dyn_settings fx_dyn_settings_defaults() {
+	gas_fx_dyn_settings d;
+	for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
+		d.distortion_mode[j] = GAS_DISTORTION_CLIP;
+		d.distortion_pre_gain_db[j] = 0.0f;
+		d.distortion_keep_hf_hz[j] = 16000.0f;
+		d.distortion_drive[j] = 0.0f;
+		d.distortion_post_gain_db[j] = 0.0f;
+		d.compressor_threshold_db[j] = 0.0f;
+		d.compressor_ratio[j] = 4.0f;
+		d.compressor_gain_db[j] = 0.0f;
+		d.compressor_attack_us[j] = 20.0f;
+		d.compressor_release_ms[j] = 250.0f;
+		d.compressor_mix[j] = 1.0f;
+		d.reserved[j] = 0;
+	}
+	return d;
+}
+
+bool fx_dyn_settings_valid(const gas_fx_dyn_settings &d) {
+	for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
+		if (d.distortion_mode[j] < GAS_DISTORTION_CLIP || d.distortion_mode[j] > GAS_DISTORTION_WAVESHAPE || !(d.compressor_ratio[j] > 0.0f) || !(d.compressor_attack_us[j] > 0.0f) || !(d.compressor_release_ms[j] > 0.0f)) {
+			return false;
+		}
+	}
+	return true;
 }
 
 uint16_t chain_signature(const int32_t *fx, uint32_t n_fx) {
@@ -753,6 +789,8 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 							e = gas_launch_biquad_mix(c->stream, kind == GAS_FX_AMPLIFY ? GAS_MODE_FX_AMPLIFY : GAS_MODE_FX_FILTER, in, c->st, F, (uint32_t)j, 1, c->cfg.mix_rate, parts, 0, c->partial_rows, reinterpret_cast<float *>(outb), gas_bus_args(), kind);
 						} else if (kind == GAS_FX_EARLY_REFLECTIONS) {
 							e = gas_launch_er_only(c->stream, in, c->st, F, c->cfg.er_ring_frames, parts, 0, c->partial_rows, outb);
+						} else if (kind == GAS_FX_DISTORTION || kind == GAS_FX_COMPRESSOR) { // k_fx_dyn.hip, settings and state by chain position
+							e = gas_launch_fx_dyn(c->stream, kind, in, c->st, F, (uint32_t)j, c->cfg.mix_rate, outb);
 						} else {
 							e = gas_launch_hrtf_rows(c->stream, (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) != 0, in, c->st, c->tab, c->d_tw, F, outb);
 						}
@@ -1017,6 +1055,32 @@ int flush_fx_settings(gas_ctx *c) {
 	return GAS_OK;
 }
 
+// gas_fx_dyn_settings_publish's rows -> the slot-indexed device table: one copy of [m settings][m slots], one scatter.
+int flush_fx_dyn_settings(gas_ctx *c) {
+	uint32_t m = 0;
+	{
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		m = (uint32_t)c->dyn_dirty_list.size();
+		if (m == 0) {
+			return GAS_OK;
+		}
+		gas_fx_dyn_settings *hs = reinterpret_cast<gas_fx_dyn_settings *>(c->h_dyn_upload);
+		uint32_t *hslots = reinterpret_cast<uint32_t *>(c->h_dyn_upload + (size_t)m * sizeof(gas_fx_dyn_settings));
+		for (uint32_t i = 0; i < m; i++) {
+			const uint32_t s = c->dyn_dirty_list[i];
+			hs[i] = c->h_dyn[s];
+			hslots[i] = s;
+			c->dyn_dirty_flag[s] = 0;
+		}
+		c->dyn_dirty_list.clear();
+	}
+	const size_t bytes = (size_t)m * (sizeof(gas_fx_dyn_settings) + sizeof(uint32_t));
+	GAS_HIP(c, hipMemcpyAsync(c->d_dyn_upload, c->h_dyn_upload, bytes, hipMemcpyHostToDevice, c->stream));
+	GAS_HIP(c, gas_launch_scatter_dyn(c->stream, c->st.dyn, reinterpret_cast<const gas_fx_dyn_settings *>(c->d_dyn_upload), reinterpret_cast<const uint32_t *>(c->d_dyn_upload + (size_t)m * sizeof(gas_fx_dyn_settings)), m));
+	GAS_HIP(c, hipStreamSynchronize(c->stream)); // the pinned staging buffer is reused by the next flush
+	return GAS_OK;
+}
+
 int flush_params(gas_ctx *c) {
 	uint32_t m = 0;
 	{
@@ -1037,7 +1101,8 @@ int flush_params(gas_ctx *c) {
 		GAS_HIP(c, gas_launch_scatter_params(c->stream, c->st.params, c->d_upload, c->d_upload_slots, m));
 		GAS_HIP(c, hipStreamSynchronize(c->stream));
 	}
-	return flush_fx_settings(c);
+	const int rc = flush_fx_settings(c);
+	return rc != GAS_OK ? rc : flush_fx_dyn_settings(c);
 }
 
 void stream_rows_sync_back(gas_ctx *c);
@@ -1300,6 +1365,11 @@ void gas_ctx_destroy(gas_ctx *c) {
 	(void)hipFree(c->d_upload_slots);
 	(void)hipFree(c->st.fxs);
 	(void)hipHostFree(c->h_fx_upload);
+	(void)hipFree(c->st.dyn);
+	(void)hipFree(c->st.dist_h);
+	(void)hipFree(c->st.comp_rundb);
+	(void)hipFree(c->d_dyn_upload);
+	(void)hipHostFree(c->h_dyn_upload);
 	(void)hipFree(c->d_slots);
 	(void)hipFree(c->d_rows);
 	(void)hipFree(c->d_slots_rows);
@@ -1399,6 +1469,14 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 		GAS_HIP(c, hipMalloc(&c->st.params, sizeof(gas_params) * N));
 		GAS_HIP(c, hipMemsetAsync(c->st.params, 0, sizeof(gas_params) * N, c->stream));
 		GAS_HIP(c, hipMalloc(&c->st.fxs, sizeof(gas_fx_settings) * N));
+		c->st.dyn_stride = (uint32_t)N;
+		GAS_HIP(c, hipMalloc(&c->st.dyn, sizeof(gas_fx_dyn_settings) * N));
+		GAS_HIP(c, hipMalloc(&c->st.dist_h, sizeof(float) * GAS_MAX_EFFECTS * 2 * N));
+		GAS_HIP(c, hipMemsetAsync(c->st.dist_h, 0, sizeof(float) * GAS_MAX_EFFECTS * 2 * N, c->stream));
+		GAS_HIP(c, hipMalloc(&c->st.comp_rundb, sizeof(float) * GAS_MAX_EFFECTS * N));
+		GAS_HIP(c, hipMemsetAsync(c->st.comp_rundb, 0, sizeof(float) * GAS_MAX_EFFECTS * N, c->stream));
+		GAS_HIP(c, hipMalloc(&c->d_dyn_upload, (sizeof(gas_fx_dyn_settings) + sizeof(uint32_t)) * N));
+		GAS_HIP(c, hipHostMalloc(&c->h_dyn_upload, (sizeof(gas_fx_dyn_settings) + sizeof(uint32_t)) * N, hipHostMallocDefault));
 		GAS_HIP(c, hipMalloc(&c->d_upload, sizeof(gas_params) * N));
 		GAS_HIP(c, hipMalloc(&c->d_upload_slots, sizeof(uint32_t) * N));
 		GAS_HIP(c, hipMalloc(&c->d_slots, sizeof(uint32_t) * N));
@@ -1456,8 +1534,13 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 	c->dirty_flag.assign(N, 0);
 	c->h_fxs.assign(N, fx_settings_defaults());
 	c->fx_dirty_flag.assign(N, 0);
+	c->h_dyn.assign(N, fx_dyn_settings_defaults());
+	c->dyn_dirty_flag.assign(N, 0);
 	{ // every slot starts from the engine's resource defaults
-		const hipError_t e = hipMemcpy(c->st.fxs, c->h_fxs.data(), sizeof(gas_fx_settings) * N, hipMemcpyHostToDevice);
+		hipError_t e = hipMemcpy(c->st.fxs, c->h_fxs.data(), sizeof(gas_fx_settings) * N, hipMemcpyHostToDevice);
+		if (e == hipSuccess) {
+			e = hipMemcpy(c->st.dyn, c->h_dyn.data(), sizeof(gas_fx_dyn_settings) * N, hipMemcpyHostToDevice);
+		}
 		if (e != hipSuccess) {
 			gas_ctx_destroy(c);
 			return GAS_ERR_DEVICE;
@@ -1597,6 +1680,17 @@ int gas_source_alloc(gas_ctx *c, int kind, const int32_t *effects, uint32_t n_ef
 			break;
 		}
 	}
+	for (uint32_t j = 0; j < n_effects; j++) {
+		if (effects[j] == GAS_FX_DISTORTION || effects[j] == GAS_FX_COMPRESSOR) { // likewise for gas_fx_dyn_settings
+			std::lock_guard<std::mutex> lk(c->params_mu);
+			c->h_dyn[s] = fx_dyn_settings_defaults();
+			if (!c->dyn_dirty_flag[s]) {
+				c->dyn_dirty_flag[s] = 1;
+				c->dyn_dirty_list.push_back(s);
+			}
+			break;
+		}
+	}
 	return GAS_OK;
 }
 
@@ -1681,6 +1775,30 @@ int gas_fx_settings_publish(gas_ctx *c, const uint32_t *slots, const gas_fx_sett
 		if (!c->fx_dirty_flag[s]) {
 			c->fx_dirty_flag[s] = 1;
 			c->fx_dirty_list.push_back(s);
+		}
+	}
+	return GAS_OK;
+}
+
+int gas_fx_dyn_settings_publish(gas_ctx *c, const uint32_t *slots, const gas_fx_dyn_settings *settings, uint32_t n) {
+	if (!c || (n > 0 && (!slots || !settings))) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	for (uint32_t i = 0; i < n; i++) {
+		if (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used) {
+			return GAS_ERR_BAD_SLOT;
+		}
+		if (!fx_dyn_settings_valid(settings[i])) {
+			return GAS_ERR_INVALID_ARGUMENT;
+		}
+	}
+	std::lock_guard<std::mutex> lk(c->params_mu);
+	for (uint32_t i = 0; i < n; i++) {
+		const uint32_t s = slots[i];
+		c->h_dyn[s] = settings[i];
+		if (!c->dyn_dirty_flag[s]) {
+			c->dyn_dirty_flag[s] = 1;
+			c->dyn_dirty_list.push_back(s);
 		}
 	}
 	return GAS_OK;

@@ -12,6 +12,7 @@
 
 static_assert(sizeof(gas_params) == 128, "gas_params is a 128-byte POD");
 static_assert(sizeof(gas_audio_frame) == 8, "AudioFrame is 2 x f32");
+static_assert(sizeof(gas_fx_dyn_settings) == 12 * 4 * GAS_MAX_EFFECTS, "gas_fx_dyn_settings is 12 arrays by chain position");
 
 // ---------------------------------------------------------------------------
 // Device-resident SpatializerPlaybackData (audio_spatializer_3d.h:85-99,
@@ -33,6 +34,11 @@ struct gas_dev_state {
 	gas_params *params; // [max_sources]
 	gas_fx_settings *fxs; // [max_sources] settings of the engine-effect kinds (GAS_FX_LOWPASS .. GAS_FX_AMPLIFY), by chain position
 	uint8_t *was_further; // [max_sources] was_further_than_max_distance_last_frame (audio_spatializer_3d.h:118)
+	// GAS_FX_DISTORTION / GAS_FX_COMPRESSOR (k_fx_dyn.hip): settings and the state that reaches the output
+	gas_fx_dyn_settings *dyn; // [max_sources], by chain position
+	float *dist_h; // [GAS_MAX_EFFECTS][2 ears][max_sources] the distortion's one-pole state h
+	float *comp_rundb; // [GAS_MAX_EFFECTS][max_sources] the compressor's smoothed over-threshold level
+	uint32_t dyn_stride; // max_sources
 };
 
 // Device-resident playback cursor: what SpatialPlaybackListNode + the engine's sampler hold.
@@ -175,6 +181,10 @@ hipError_t gas_launch_hrtf_regrid(hipStream_t stream, const float *d_positions, 
 void gas_make_twiddles(float2 *host_tw /* [64][16] */);
 
 hipError_t gas_launch_mix_reduce(hipStream_t stream, const float *partials, uint32_t p_count, uint32_t p_stride, uint32_t channels, uint32_t frames, gas_audio_frame *out);
+// k_fx_dyn.hip: a GAS_FX_DISTORTION / GAS_FX_COMPRESSOR stage of a staged chain (rows in -> dense rows out), settings
+// and state of chain position chain_pos; and the scatter of published gas_fx_dyn_settings rows into the slot table
+hipError_t gas_launch_fx_dyn(hipStream_t stream, int kind, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t chain_pos, float mix_rate, gas_audio_frame *rows_out);
+hipError_t gas_launch_scatter_dyn(hipStream_t stream, gas_fx_dyn_settings *table, const gas_fx_dyn_settings *upload, const uint32_t *slots, uint32_t n);
 hipError_t gas_launch_scatter_params(hipStream_t stream, gas_params *table, const gas_params *upload, const uint32_t *slots, uint32_t n);
 hipError_t gas_launch_calc_spatialization(hipStream_t stream, const gas_spatializer3d_config *cfgs, const uint32_t *cfg_index, const gas_source_pose *poses, const gas_listener *listeners, uint32_t n_listeners, const uint32_t *slots, uint32_t n, gas_params *table, uint8_t *was_further, gas_params *out_params, const gas_area_send *areas = nullptr, const float *listener_area_pos = nullptr, gas_audio_frame *out_reverb = nullptr);
 hipError_t gas_launch_sample_sources(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc /* 16.16 step per row for resampled playbacks, or nullptr */);

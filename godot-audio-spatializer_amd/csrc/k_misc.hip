@@ -105,6 +105,11 @@ __global__ void k_zero_slot(gas_dev_state st, uint32_t slot, uint32_t hist_len, 
 		if (st.er_pos) {
 			st.er_pos[slot] = 0;
 		}
+		for (int j = 0; j < GAS_MAX_EFFECTS; j++) { // GAS_FX_DISTORTION / GAS_FX_COMPRESSOR state of every chain position
+			st.dist_h[((size_t)j * 2 + 0) * st.dyn_stride + slot] = 0.0f;
+			st.dist_h[((size_t)j * 2 + 1) * st.dyn_stride + slot] = 0.0f;
+			st.comp_rundb[(size_t)j * st.dyn_stride + slot] = 0.0f;
+		}
 	}
 	if (st.er_ring) {
 		for (uint32_t i = t; i < er_ring_frames; i += gridDim.x * blockDim.x) {

@@ -22,6 +22,10 @@
 
 #include "../../include/gas_amd_host.h"
 
+// A weak reference: the host layer is also built for the CPU against a stand-in of the library's entries (the
+// ThreadSanitizer build) that does not define this one; in libgas_amd.so it is always there.
+#pragma weak gas_fx_dyn_settings_publish
+
 namespace {
 
 constexpr int TAIL = GAS_LOOKAHEAD_BUFFER_SIZE; // frames a playback runs ahead of what the DSP sees (audio_spatializer.h:49)
@@ -77,11 +81,12 @@ struct Playback {
 };
 
 struct Command {
-	enum Kind { START, PARAMS, FX_SETTINGS } kind = START;
+	enum Kind { START, PARAMS, FX_SETTINGS, FX_DYN_SETTINGS } kind = START;
 	uint32_t id = 0;
 	std::unique_ptr<Playback> playback; // START
 	gas_params params{}; // PARAMS
 	gas_fx_settings fx_settings{}; // FX_SETTINGS
+	gas_fx_dyn_settings fx_dyn_settings{}; // FX_DYN_SETTINGS
 };
 
 // [ENGINE] Math::db_to_linear
@@ -223,6 +228,11 @@ struct gas_host {
 				auto it = by_id.find(c.id);
 				if (it != by_id.end()) {
 					gas_fx_settings_publish(ctx, &it->second->slot, &c.fx_settings, 1); // snapshotted with the parameters (:328)
+				}
+			} else if (c.kind == Command::FX_DYN_SETTINGS) {
+				auto it = by_id.find(c.id);
+				if (it != by_id.end() && gas_fx_dyn_settings_publish) {
+					gas_fx_dyn_settings_publish(ctx, &it->second->slot, &c.fx_dyn_settings, 1); // (validated when queued)
 				}
 			} else {
 				auto it = by_id.find(c.id);
@@ -522,6 +532,27 @@ int gas_host_set_effect_settings(gas_host *h, uint32_t id, const gas_fx_settings
 	c.kind = Command::FX_SETTINGS;
 	c.id = id;
 	c.fx_settings = *settings;
+	std::lock_guard<std::mutex> lk(h->inbox_mu);
+	h->inbox.push_back(std::move(c));
+	return GAS_OK;
+}
+
+int gas_host_set_effect_settings_dyn(gas_host *h, uint32_t id, const gas_fx_dyn_settings *settings) {
+	if (!h || !h->lookup(id)) {
+		return GAS_ERR_BAD_SLOT;
+	}
+	if (!settings) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	for (int j = 0; j < GAS_MAX_EFFECTS; j++) { // gas_fx_dyn_settings_publish's rule, checked here: the audio thread cannot report it
+		if (settings->distortion_mode[j] < GAS_DISTORTION_CLIP || settings->distortion_mode[j] > GAS_DISTORTION_WAVESHAPE || !(settings->compressor_ratio[j] > 0.0f) || !(settings->compressor_attack_us[j] > 0.0f) || !(settings->compressor_release_ms[j] > 0.0f)) {
+			return GAS_ERR_INVALID_ARGUMENT;
+		}
+	}
+	Command c;
+	c.kind = Command::FX_DYN_SETTINGS;
+	c.id = id;
+	c.fx_dyn_settings = *settings;
 	std::lock_guard<std::mutex> lk(h->inbox_mu);
 	h->inbox.push_back(std::move(c));
 	return GAS_OK;

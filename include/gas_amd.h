@@ -85,7 +85,18 @@ typedef enum gas_effect_kind {
 	GAS_FX_NOTCH = 7, /* [ENGINE] AudioEffectNotchFilter */
 	GAS_FX_LOWSHELF = 8, /* [ENGINE] AudioEffectLowShelfFilter */
 	GAS_FX_AMPLIFY = 9, /* [ENGINE] AudioEffectAmplify: volume ramp previous -> current volume_db across the block */
+	/* The engine's first nonlinear and dynamics kinds; settings per playback and chain position: gas_fx_dyn_settings.
+	 * (10 is not assigned: an effect kind the library does not know is GAS_ERR_INVALID_ARGUMENT / _UNSUPPORTED_CHAIN.) */
+	GAS_FX_DISTORTION = 11, /* [ENGINE] AudioEffectDistortion: per-ear one-pole split, the low band shaped by `mode` */
+	GAS_FX_COMPRESSOR = 12, /* [ENGINE] AudioEffectCompressor without sidechain: stereo-linked detector, one gain per frame */
 } gas_effect_kind;
+
+/* [ENGINE] AudioEffectDistortion::Mode */
+#define GAS_DISTORTION_CLIP 0
+#define GAS_DISTORTION_ATAN 1
+#define GAS_DISTORTION_LOFI 2
+#define GAS_DISTORTION_OVERDRIVE 3
+#define GAS_DISTORTION_WAVESHAPE 4
 
 typedef enum gas_mem {
 	GAS_MEM_HOST = 0, /* host pointers; the call copies in/out and returns when the result is in *out */
@@ -196,6 +207,25 @@ typedef struct gas_fx_settings {
 	float amplify_volume_db[GAS_MAX_EFFECTS]; /* [ENGINE] AudioEffectAmplify::volume_db */
 } gas_fx_settings;
 
+/* Settings of the GAS_FX_DISTORTION / GAS_FX_COMPRESSOR effects of one playback, by chain position like gas_fx_settings:
+ * position j is read only when effect j of the playback's chain is one of those kinds.  Read once per block (no ramps).
+ * A slot that never got settings has the engine's resource defaults, given per field.  The compressor's `sidechain`
+ * bus is not supported: a playback whose compressor uses one stays on the engine's own path. */
+typedef struct gas_fx_dyn_settings {
+	int32_t distortion_mode[GAS_MAX_EFFECTS]; /* GAS_DISTORTION_*, default CLIP */
+	float distortion_pre_gain_db[GAS_MAX_EFFECTS]; /* default 0 */
+	float distortion_keep_hf_hz[GAS_MAX_EFFECTS]; /* default 16000 */
+	float distortion_drive[GAS_MAX_EFFECTS]; /* 0 .. 1, default 0 */
+	float distortion_post_gain_db[GAS_MAX_EFFECTS]; /* default 0 */
+	float compressor_threshold_db[GAS_MAX_EFFECTS]; /* default 0 */
+	float compressor_ratio[GAS_MAX_EFFECTS]; /* > 0, default 4 */
+	float compressor_gain_db[GAS_MAX_EFFECTS]; /* makeup gain, default 0 */
+	float compressor_attack_us[GAS_MAX_EFFECTS]; /* > 0, default 20 */
+	float compressor_release_ms[GAS_MAX_EFFECTS]; /* > 0, default 250 */
+	float compressor_mix[GAS_MAX_EFFECTS]; /* default 1 */
+	uint32_t reserved[GAS_MAX_EFFECTS];
+} gas_fx_dyn_settings;
+
 /* Per-kernel device timing collected with HIP events on the context stream. */
 typedef struct gas_profile {
 	uint64_t launches; /* timed launches of the dominant kernel since the last reset */
@@ -250,6 +280,10 @@ int gas_params_publish_batch(gas_ctx *ctx, const uint32_t *slots, const gas_para
 /* Settings of the engine-effect kinds, host arrays; latest wins, snapshotted with the parameters at the start of the
  * next gas_process_block.  Physics thread, like gas_params_publish. */
 int gas_fx_settings_publish(gas_ctx *ctx, const uint32_t *slots, const gas_fx_settings *settings, uint32_t n);
+/* The same for gas_fx_dyn_settings: latest wins, snapshotted at the start of the next gas_process_block, physics thread.
+ * A distortion_mode outside 0..4 or a compressor ratio, attack or release that is not > 0 (at any position) is
+ * GAS_ERR_INVALID_ARGUMENT, and nothing of the call is taken. */
+int gas_fx_dyn_settings_publish(gas_ctx *ctx, const uint32_t *slots, const gas_fx_dyn_settings *settings, uint32_t n);
 
 /* ---- NEW AudioSpatializerHRTF resource: hrir is [dirs][2 ears][taps] f32, taps <= 256 */
 int gas_hrtf_load(gas_ctx *ctx, const float *hrir, uint32_t dirs, uint32_t taps);

@@ -58,6 +58,67 @@ def fx_dyn_settings_defaults(n):
     return d
 
 
+# the engine's delay and reverb (one "line" of delay memory per instance, gas_ctx_reserve_fx_lines); settings:
+# gas_fx_line_settings by chain position
+FX_DELAY, FX_REVERB = 13, 14
+FX_LINE_SETTINGS_DTYPE = np.dtype(
+    [
+        ("delay_dry", np.float32, (MAX_EFFECTS,)),
+        ("delay_tap1_active", np.int32, (MAX_EFFECTS,)),
+        ("delay_tap1_ms", np.float32, (MAX_EFFECTS,)),
+        ("delay_tap1_level_db", np.float32, (MAX_EFFECTS,)),
+        ("delay_tap1_pan", np.float32, (MAX_EFFECTS,)),
+        ("delay_tap2_active", np.int32, (MAX_EFFECTS,)),
+        ("delay_tap2_ms", np.float32, (MAX_EFFECTS,)),
+        ("delay_tap2_level_db", np.float32, (MAX_EFFECTS,)),
+        ("delay_tap2_pan", np.float32, (MAX_EFFECTS,)),
+        ("delay_feedback_active", np.int32, (MAX_EFFECTS,)),
+        ("delay_feedback_ms", np.float32, (MAX_EFFECTS,)),
+        ("delay_feedback_level_db", np.float32, (MAX_EFFECTS,)),
+        ("delay_feedback_lowpass_hz", np.float32, (MAX_EFFECTS,)),
+        ("reverb_predelay_ms", np.float32, (MAX_EFFECTS,)),
+        ("reverb_predelay_feedback", np.float32, (MAX_EFFECTS,)),
+        ("reverb_room_size", np.float32, (MAX_EFFECTS,)),
+        ("reverb_damping", np.float32, (MAX_EFFECTS,)),
+        ("reverb_spread", np.float32, (MAX_EFFECTS,)),
+        ("reverb_hipass", np.float32, (MAX_EFFECTS,)),
+        ("reverb_dry", np.float32, (MAX_EFFECTS,)),
+        ("reverb_wet", np.float32, (MAX_EFFECTS,)),
+    ]
+)
+assert FX_LINE_SETTINGS_DTYPE.itemsize == 336
+
+
+def fx_line_settings_defaults(n):
+    """[ENGINE] AudioEffectDelay / AudioEffectReverb resource defaults, n rows."""
+    d = np.zeros(n, FX_LINE_SETTINGS_DTYPE)
+    for name, v in (
+        ("delay_dry", 1.0),
+        ("delay_tap1_active", 1),
+        ("delay_tap1_ms", 250.0),
+        ("delay_tap1_level_db", -6.0),
+        ("delay_tap1_pan", 0.2),
+        ("delay_tap2_active", 1),
+        ("delay_tap2_ms", 500.0),
+        ("delay_tap2_level_db", -12.0),
+        ("delay_tap2_pan", -0.4),
+        ("delay_feedback_active", 0),
+        ("delay_feedback_ms", 340.0),
+        ("delay_feedback_level_db", -6.0),
+        ("delay_feedback_lowpass_hz", 16000.0),
+        ("reverb_predelay_ms", 150.0),
+        ("reverb_predelay_feedback", 0.4),
+        ("reverb_room_size", 0.8),
+        ("reverb_damping", 0.5),
+        ("reverb_spread", 1.0),
+        ("reverb_hipass", 0.0),
+        ("reverb_dry", 1.0),
+        ("reverb_wet", 0.5),
+    ):
+        d[name] = v
+    return d
+
+
 MEM_HOST = 0
 MEM_DEVICE = 1
 FLAG_PEAKS_DRAINING_ONLY = 1
@@ -199,6 +260,8 @@ EXPORTS = [
     "gas_params_publish",
     "gas_fx_settings_publish",
     "gas_fx_dyn_settings_publish",
+    "gas_fx_line_settings_publish",
+    "gas_ctx_reserve_fx_lines",
     "gas_params_publish_batch",
     "gas_hrtf_load",
     "gas_hrtf_load_positions",
@@ -281,6 +344,8 @@ def load_library():
     L.gas_params_publish.argtypes = [vp, u32, vp]
     L.gas_fx_settings_publish.argtypes = [vp, vp, vp, u32]
     L.gas_fx_dyn_settings_publish.argtypes = [vp, vp, vp, u32]
+    L.gas_fx_line_settings_publish.argtypes = [vp, vp, vp, u32]
+    L.gas_ctx_reserve_fx_lines.argtypes = [vp, u32, u32]
     L.gas_params_publish_batch.argtypes = [vp, vp, vp, u32, i32]
     L.gas_hrtf_load.argtypes = [vp, vp, u32, u32]
     L.gas_hrtf_load_positions.argtypes = [vp, vp, vp, u32, u32, u32, u32, i32, vp]
@@ -399,6 +464,20 @@ class SpatializerContext:
         f = np.ascontiguousarray(settings, dtype=FX_DYN_SETTINGS_DTYPE)
         assert s.shape == f.shape
         self._check(self.lib.gas_fx_dyn_settings_publish(self.h, _np_ptr(s), _np_ptr(f), len(s)), "gas_fx_dyn_settings_publish")
+
+    @staticmethod
+    def fx_line_settings_defaults(n):
+        return fx_line_settings_defaults(n)
+
+    def fx_line_settings_publish(self, slots, settings):
+        s = np.ascontiguousarray(slots, dtype=np.uint32)
+        f = np.ascontiguousarray(settings, dtype=FX_LINE_SETTINGS_DTYPE)
+        assert s.shape == f.shape
+        self._check(self.lib.gas_fx_line_settings_publish(self.h, _np_ptr(s), _np_ptr(f), len(s)), "gas_fx_line_settings_publish")
+
+    def reserve_fx_lines(self, delay_lines, reverb_lines):
+        """Size the GAS_FX_DELAY / GAS_FX_REVERB line pools (main thread, not during a callback); (0, 0) releases them."""
+        self._check(self.lib.gas_ctx_reserve_fx_lines(self.h, int(delay_lines), int(reverb_lines)), "gas_ctx_reserve_fx_lines")
 
     def params_publish_batch(self, slots, params):
         s = np.ascontiguousarray(slots, dtype=np.uint32)
@@ -598,6 +677,7 @@ class BatchedSpatializerHost:
         L.gas_host_get_mixed_frames.argtypes = [vp, i32, vp, i32]
         L.gas_host_set_effect_settings.argtypes = [vp, u32, vp]
         L.gas_host_set_effect_settings_dyn.argtypes = [vp, u32, vp]
+        L.gas_host_set_effect_settings_line.argtypes = [vp, u32, vp]
         L.gas_host_set_release_fn.argtypes = [vp, vp, vp]
         L.gas_host_collect_released.argtypes = [vp]
         L.gas_host_set_process_effects_fn.argtypes = [vp, vp, vp]
@@ -683,6 +763,10 @@ class BatchedSpatializerHost:
     def set_effect_dyn_settings(self, pid, settings):
         f = np.ascontiguousarray(settings, dtype=FX_DYN_SETTINGS_DTYPE).reshape(1)
         return self.lib.gas_host_set_effect_settings_dyn(self.h, pid, _np_ptr(f))
+
+    def set_effect_line_settings(self, pid, settings):
+        f = np.ascontiguousarray(settings, dtype=FX_LINE_SETTINGS_DTYPE).reshape(1)
+        return self.lib.gas_host_set_effect_settings_line(self.h, pid, _np_ptr(f))
 
     def is_playback_active(self, pid):
         return bool(self.lib.gas_host_is_playback_active(self.h, pid))

@@ -5,11 +5,14 @@
 // There is NO CPU fallback: every entry needs a HIP device and fails with GAS_ERR_NO_DEVICE /
 // GAS_ERR_DEVICE otherwise.
 #include <algorithm>
+#include <array>
+#include <cmath>
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <new>
 
+#include "gas_fx_line_check.h"
 #include "gas_internal.h"
 
 namespace {
@@ -128,6 +131,19 @@ struct gas_ctx {
 	std::vector<uint32_t> dyn_dirty_list;
 	unsigned char *h_dyn_upload = nullptr; // pinned, [max_sources] settings then [max_sources] slots
 	unsigned char *d_dyn_upload = nullptr;
+	// GAS_FX_DELAY / GAS_FX_REVERB lines (gas_ctx_reserve_fx_lines): pool sizes and free lines (alloc_mu), each slot's
+	// lines by chain position (written under alloc_mu and params_mu), settings mirror and what the next flush uploads
+	// (params_mu): [m settings][m {slot, line[4]}][z {kind, line}] through one pinned staging buffer
+	gas_line_geo line_geo{};
+	uint32_t line_cap[2] = { 0, 0 }; // delay, reverb
+	std::vector<uint32_t> line_free[2];
+	std::vector<std::array<int32_t, GAS_MAX_EFFECTS>> h_line_of;
+	std::vector<gas_fx_line_settings> h_line;
+	std::vector<uint8_t> line_dirty_flag;
+	std::vector<uint32_t> line_dirty_list;
+	std::vector<uint32_t> line_zero_list; // {kind, line} pairs, each line at most once (line_zero_pending)
+	std::vector<uint8_t> line_zero_pending[2]; // [pool][line]: queued in line_zero_list
+	unsigned char *h_line_upload = nullptr, *d_line_upload = nullptr;
 
 	// plain [HRTF] group of the cached list (k_hrtf_uni): which entries need their exact peak
 	uint32_t *h_peak_bits = nullptr, *d_peak_bits = nullptr; // two halves of (max_sources + 31) / 32 words: bit k = entry k of the plain-[HRTF] group / of the staged group
@@ -279,7 +295,7 @@ int group_of(int kind, const int32_t *fx, uint32_t n_fx) {
 	// reflection ring and one HRTF history per playback
 	int n_er = 0, n_hrtf = 0;
 	for (uint32_t j = 0; j < n_fx; j++) {
-		if ((fx[j] < GAS_FX_HIGHSHELF || fx[j] > GAS_FX_AMPLIFY) && fx[j] != GAS_FX_DISTORTION && fx[j] != GAS_FX_COMPRESSOR) {
+		if ((fx[j] < GAS_FX_HIGHSHELF || fx[j] > GAS_FX_AMPLIFY) && (fx[j] < GAS_FX_DISTORTION || fx[j] > GAS_FX_REVERB)) {
 			return -1;
 		}
 		n_er += fx[j] == GAS_FX_EARLY_REFLECTIONS;
@@ -340,6 +356,78 @@ bool fx_dyn_settings_valid(const gas_fx_dyn_settings &d) {
 		}
 	}
 	return true;
+}
+
+// [ENGINE] AudioEffectDelay / AudioEffectReverb resource defaults
+gas_fx_line_settings fx_line_settings_defaults() {
+	gas_fx_line_settings d;
+	for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
+		d.delay_dry[j] = 1.0f;
+		d.delay_tap1_active[j] = 1;
+		d.delay_tap1_ms[j] = 250.0f;
+		d.delay_tap1_level_db[j] = -6.0f;
+		d.delay_tap1_pan[j] = 0.2f;
+		d.delay_tap2_active[j] = 1;
+		d.delay_tap2_ms[j] = 500.0f;
+		d.delay_tap2_level_db[j] = -12.0f;
+		d.delay_tap2_pan[j] = -0.4f;
+		d.delay_feedback_active[j] = 0;
+		d.delay_feedback_ms[j] = 340.0f;
+		d.delay_feedback_level_db[j] = -6.0f;
+		d.delay_feedback_lowpass_hz[j] = 16000.0f;
+		d.reverb_predelay_ms[j] = 150.0f;
+		d.reverb_predelay_feedback[j] = 0.4f;
+		d.reverb_room_size[j] = 0.8f;
+		d.reverb_damping[j] = 0.5f;
+		d.reverb_spread[j] = 1.0f;
+		d.reverb_hipass[j] = 0.0f;
+		d.reverb_dry[j] = 1.0f;
+		d.reverb_wet[j] = 0.5f;
+	}
+	return d;
+}
+
+// Line geometry at a mix rate: the engine's Freeverb tunings in seconds, the two ears' extra spread.
+gas_line_geo make_line_geo(float mix_rate) {
+	static const double ct[8] = { 0.025306122448979593, 0.026938775510204082, 0.028956916099773241, 0.03074829931972789, 0.032244897959183672, 0.03380952380952381, 0.035306122448979592, 0.036666666666666667 };
+	static const double at[4] = { 0.0051020408163265302, 0.007732426303854875, 0.01, 0.012607709750566893 };
+	static const double spread_base[2] = { 0.0, 0.000521 };
+	const double sr = (double)mix_rate;
+	gas_line_geo g{};
+	const uint32_t fb = (uint32_t)(int)(1.5 * sr) + 1;
+	uint32_t ring = 1;
+	while (ring < fb + 512) { // longer than the longest tap by more than a block (k_fx_line.hip)
+		ring *= 2;
+	}
+	g.ring_mask = ring - 1;
+	g.fb_frames = fb;
+	g.delay_floats = ((GAS_LINE_HEADER + 2 * (size_t)ring + 2 * (size_t)fb) + 63) / 64 * 64;
+	g.echo_size = (uint32_t)(int)(0.5 * sr + 1.0);
+	size_t off = GAS_LINE_HEADER;
+	for (int e = 0; e < 2; e++) {
+		g.xs[e] = (uint32_t)lrint(spread_base[e] * sr);
+		g.echo_off[e] = (uint32_t)off;
+		off += g.echo_size;
+		for (int k = 0; k < 8; k++) {
+			g.comb_size[e][k] = (uint32_t)lrint(ct[k] * sr) + g.xs[e];
+			g.comb_off[e][k] = (uint32_t)off;
+			off += g.comb_size[e][k];
+		}
+		for (int k = 0; k < 4; k++) {
+			g.ap_size[e][k] = (uint32_t)lrint(at[k] * sr) + g.xs[e];
+			g.ap_off[e][k] = (uint32_t)off;
+			off += g.ap_size[e][k];
+		}
+	}
+	for (int k = 0; k < 4; k++) {
+		g.ap_base[k] = (uint32_t)lrint(at[k] * sr);
+	}
+	g.reverb_floats = (off + 63) / 64 * 64;
+	return g;
+}
+
+inline int line_pool_of(int kind) { // 0 delay, 1 reverb, -1 no line
+	return kind == GAS_FX_DELAY ? 0 : (kind == GAS_FX_REVERB ? 1 : -1);
 }
 
 uint16_t chain_signature(const int32_t *fx, uint32_t n_fx) {
@@ -791,6 +879,8 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 							e = gas_launch_er_only(c->stream, in, c->st, F, c->cfg.er_ring_frames, parts, 0, c->partial_rows, outb);
 						} else if (kind == GAS_FX_DISTORTION || kind == GAS_FX_COMPRESSOR) { // k_fx_dyn.hip, settings and state by chain position
 							e = gas_launch_fx_dyn(c->stream, kind, in, c->st, F, (uint32_t)j, c->cfg.mix_rate, outb);
+						} else if (kind == GAS_FX_DELAY || kind == GAS_FX_REVERB) { // k_fx_line.hip, state in the slot's line of chain position j
+							e = gas_launch_fx_line(c->stream, kind, in, c->st, c->line_geo, F, (uint32_t)j, c->cfg.mix_rate, outb);
 						} else {
 							e = gas_launch_hrtf_rows(c->stream, (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) != 0, in, c->st, c->tab, c->d_tw, F, outb);
 						}
@@ -1081,6 +1171,92 @@ int flush_fx_dyn_settings(gas_ctx *c) {
 	return GAS_OK;
 }
 
+// gas_fx_line_settings_publish's rows, new slot -> line entries and lines to zero: one copy of
+// [m settings][m {slot, line[4]}][z {kind, line}], one scatter, one zeroing launch.
+int flush_fx_lines(gas_ctx *c) {
+	if (!c->h_line_upload) {
+		return GAS_OK;
+	}
+	uint32_t m = 0, z = 0;
+	{
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		m = (uint32_t)c->line_dirty_list.size();
+		z = (uint32_t)(c->line_zero_list.size() / 2);
+		if (m == 0 && z == 0) {
+			return GAS_OK;
+		}
+		gas_fx_line_settings *hs = reinterpret_cast<gas_fx_line_settings *>(c->h_line_upload);
+		uint32_t *hsl = reinterpret_cast<uint32_t *>(c->h_line_upload + (size_t)m * sizeof(gas_fx_line_settings));
+		for (uint32_t i = 0; i < m; i++) {
+			const uint32_t s = c->line_dirty_list[i];
+			hs[i] = c->h_line[s];
+			hsl[i * (1 + GAS_MAX_EFFECTS)] = s;
+			for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
+				hsl[i * (1 + GAS_MAX_EFFECTS) + 1 + j] = (uint32_t)c->h_line_of[s][j];
+			}
+			c->line_dirty_flag[s] = 0;
+		}
+		std::memcpy(hsl + (size_t)m * (1 + GAS_MAX_EFFECTS), c->line_zero_list.data(), (size_t)z * 2 * sizeof(uint32_t));
+		for (uint32_t i = 0; i < z; i++) {
+			c->line_zero_pending[line_pool_of((int)c->line_zero_list[2 * i])][c->line_zero_list[2 * i + 1]] = 0;
+		}
+		c->line_dirty_list.clear();
+		c->line_zero_list.clear();
+	}
+	const size_t zoff = (size_t)m * (sizeof(gas_fx_line_settings) + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t));
+	GAS_HIP(c, hipMemcpyAsync(c->d_line_upload, c->h_line_upload, zoff + (size_t)z * 2 * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	GAS_HIP(c, gas_launch_scatter_line(c->stream, c->st, reinterpret_cast<const gas_fx_line_settings *>(c->d_line_upload), reinterpret_cast<const uint32_t *>(c->d_line_upload + (size_t)m * sizeof(gas_fx_line_settings)), m));
+	GAS_HIP(c, gas_launch_zero_lines(c->stream, c->st, c->line_geo, reinterpret_cast<const uint32_t *>(c->d_line_upload + zoff), z));
+	GAS_HIP(c, hipStreamSynchronize(c->stream)); // the pinned staging buffer is reused by the next flush
+	return GAS_OK;
+}
+
+// Marks slot s's settings row (and its line table row) for the next flush; params_mu held.
+void line_mark_dirty(gas_ctx *c, uint32_t s) {
+	if (!c->line_dirty_flag[s]) {
+		c->line_dirty_flag[s] = 1;
+		c->line_dirty_list.push_back(s);
+	}
+}
+
+// Queues the zeroing of slot s's lines (chain signature sig), each line at most once until the next flush, so the
+// queue never holds more pairs than the pools have lines (the upload buffer's zero section); params_mu held.
+void line_queue_zero(gas_ctx *c, uint32_t s, uint16_t sig) {
+	for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
+		const int kind = (sig >> (4 * j)) & 0xf;
+		const int pool = line_pool_of(kind);
+		const int32_t line = c->h_line_of[s][j];
+		if (pool >= 0 && line >= 0 && !c->line_zero_pending[pool][line]) {
+			c->line_zero_pending[pool][line] = 1;
+			c->line_zero_list.push_back((uint32_t)kind);
+			c->line_zero_list.push_back((uint32_t)line);
+		}
+	}
+}
+
+void release_fx_lines(gas_ctx *c) {
+	(void)hipFree(c->st.delay_pool);
+	(void)hipFree(c->st.reverb_pool);
+	(void)hipFree(c->st.line_of);
+	(void)hipFree(c->st.line_settings);
+	(void)hipFree(c->d_line_upload);
+	(void)hipHostFree(c->h_line_upload);
+	c->st.delay_pool = c->st.reverb_pool = nullptr;
+	c->st.line_of = nullptr;
+	c->st.line_settings = nullptr;
+	c->d_line_upload = c->h_line_upload = nullptr;
+	c->line_cap[0] = c->line_cap[1] = 0;
+	c->line_free[0].clear();
+	c->line_free[1].clear();
+	c->h_line_of.clear();
+	c->h_line.clear();
+	c->line_dirty_flag.clear();
+	c->line_dirty_list.clear();
+	c->line_zero_list.clear();
+	c->line_zero_pending[0].clear();
+	c->line_zero_pending[1].clear();
+}
+
 int flush_params(gas_ctx *c) {
 	uint32_t m = 0;
 	{
@@ -1101,8 +1277,9 @@ int flush_params(gas_ctx *c) {
 		GAS_HIP(c, gas_launch_scatter_params(c->stream, c->st.params, c->d_upload, c->d_upload_slots, m));
 		GAS_HIP(c, hipStreamSynchronize(c->stream));
 	}
-	const int rc = flush_fx_settings(c);
-	return rc != GAS_OK ? rc : flush_fx_dyn_settings(c);
+	int rc = flush_fx_settings(c);
+	rc = rc != GAS_OK ? rc : flush_fx_dyn_settings(c);
+	return rc != GAS_OK ? rc : flush_fx_lines(c);
 }
 
 void stream_rows_sync_back(gas_ctx *c);
@@ -1132,6 +1309,16 @@ int apply_pending_frees(gas_ctx *c) {
 	std::lock_guard<std::mutex> alloc_lk(c->alloc_mu);
 	for (uint32_t s : c->pending_free) {
 		SlotInfo &si = c->slots[s];
+		if (!c->h_line_of.empty()) { // its lines go back to the pools (zeroed when they are handed out again)
+			std::lock_guard<std::mutex> lk(c->params_mu); // (h_line_of is read by the flush under params_mu)
+			for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
+				const int pool = line_pool_of((si.chain_sig >> (4 * j)) & 0xf);
+				if (pool >= 0 && c->h_line_of[s][j] >= 0) {
+					c->line_free[pool].push_back((uint32_t)c->h_line_of[s][j]);
+					c->h_line_of[s][j] = -1;
+				}
+			}
+		}
 		si = SlotInfo{};
 		si.dirty_state = 1;
 		c->free_list.push_back(s);
@@ -1370,6 +1557,7 @@ void gas_ctx_destroy(gas_ctx *c) {
 	(void)hipFree(c->st.comp_rundb);
 	(void)hipFree(c->d_dyn_upload);
 	(void)hipHostFree(c->h_dyn_upload);
+	release_fx_lines(c);
 	(void)hipFree(c->d_slots);
 	(void)hipFree(c->d_rows);
 	(void)hipFree(c->d_slots_rows);
@@ -1652,8 +1840,18 @@ int gas_source_alloc(gas_ctx *c, int kind, const int32_t *effects, uint32_t n_ef
 	if ((g == G_FX_ER || g == G_FX_ER_HRTF || (g == G_FX_GENERIC && chain_has(sig, GAS_FX_EARLY_REFLECTIONS))) && c->cfg.er_ring_frames == 0) {
 		return GAS_ERR_UNSUPPORTED_CHAIN;
 	}
+	uint32_t need[2] = { 0, 0 }; // delay / reverb lines of the chain
+	for (uint32_t j = 0; j < n_effects; j++) {
+		const int pool = line_pool_of(effects[j]);
+		if (pool >= 0) {
+			need[pool]++;
+		}
+	}
 	std::lock_guard<std::mutex> alloc_lk(c->alloc_mu); // any thread (instantiate_playback_data runs on the physics thread, audio_spatializer.cpp:69)
-	if (c->free_list.empty()) {
+	if (need[0] + need[1] > 0 && c->line_cap[0] == 0 && c->line_cap[1] == 0) {
+		return GAS_ERR_UNSUPPORTED_CHAIN; // no pool reserved (gas_ctx_reserve_fx_lines)
+	}
+	if (c->free_list.empty() || c->line_free[0].size() < need[0] || c->line_free[1].size() < need[1]) {
 		return GAS_ERR_OUT_OF_SLOTS;
 	}
 	const uint32_t s = c->free_list.back();
@@ -1690,6 +1888,21 @@ int gas_source_alloc(gas_ctx *c, int kind, const int32_t *effects, uint32_t n_ef
 			}
 			break;
 		}
+	}
+	if (need[0] + need[1] > 0) { // one line per delay / reverb, zeroed and entered in the table at the next flush
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		for (uint32_t j = 0; j < GAS_MAX_EFFECTS; j++) {
+			const int pool = j < n_effects ? line_pool_of(effects[j]) : -1;
+			if (pool >= 0) {
+				c->h_line_of[s][j] = (int32_t)c->line_free[pool].back();
+				c->line_free[pool].pop_back();
+			} else {
+				c->h_line_of[s][j] = -1;
+			}
+		}
+		c->h_line[s] = fx_line_settings_defaults();
+		line_mark_dirty(c, s);
+		line_queue_zero(c, s, sig);
 	}
 	return GAS_OK;
 }
@@ -1737,6 +1950,14 @@ int gas_source_reset(gas_ctx *c, uint32_t slot) {
 	}
 	GAS_HIP(c, hipSetDevice(c->cfg.device));
 	GAS_HIP(c, gas_launch_zero_slot(c->stream, c->st, slot, c->hist_len, c->cfg.er_ring_frames));
+	{ // its delay / reverb lines: zeroed by the next flush, before the next block (alloc_mu: the audio thread may be
+	  // returning a freed slot's lines; the same lock order as gas_source_alloc)
+		std::lock_guard<std::mutex> alloc_lk(c->alloc_mu);
+		if (!c->h_line_of.empty() && c->slots[slot].used) {
+			std::lock_guard<std::mutex> lk(c->params_mu);
+			line_queue_zero(c, slot, c->slots[slot].chain_sig);
+		}
+	}
 	return GAS_OK;
 }
 
@@ -1801,6 +2022,105 @@ int gas_fx_dyn_settings_publish(gas_ctx *c, const uint32_t *slots, const gas_fx_
 			c->dyn_dirty_list.push_back(s);
 		}
 	}
+	return GAS_OK;
+}
+
+int gas_fx_line_settings_publish(gas_ctx *c, const uint32_t *slots, const gas_fx_line_settings *settings, uint32_t n) {
+	if (!c || (n > 0 && (!slots || !settings))) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	for (uint32_t i = 0; i < n; i++) {
+		if (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used) {
+			return GAS_ERR_BAD_SLOT;
+		}
+		if (!gas_fx_line_settings_valid(settings[i])) {
+			return GAS_ERR_INVALID_ARGUMENT;
+		}
+	}
+	std::lock_guard<std::mutex> lk(c->params_mu);
+	if (c->h_line.empty()) { // no pool reserved: no slot has a delay or reverb the settings could reach
+		return GAS_OK;
+	}
+	for (uint32_t i = 0; i < n; i++) {
+		c->h_line[slots[i]] = settings[i];
+		line_mark_dirty(c, slots[i]);
+	}
+	return GAS_OK;
+}
+
+int gas_ctx_reserve_fx_lines(gas_ctx *c, uint32_t delay_lines, uint32_t reverb_lines) {
+	if (!c) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	const uint32_t F = c->cfg.frames;
+	const double sr = (double)c->cfg.mix_rate;
+	if (reverb_lines > 0 && (lrint(0.02 * sr) < (long)F || lrint(0.025306122 * sr) < (long)F)) {
+		return GAS_ERR_INVALID_ARGUMENT; // the reverb kernel's predelay and comb reads must not reach the block's own writes
+	}
+	std::lock_guard<std::mutex> alloc_lk(c->alloc_mu);
+	for (int p = 0; p < 2; p++) {
+		if (c->line_free[p].size() != c->line_cap[p]) {
+			return GAS_ERR_INVALID_ARGUMENT; // lines are held
+		}
+	}
+	GAS_HIP(c, hipSetDevice(c->cfg.device));
+	GAS_HIP(c, hipStreamSynchronize(c->stream));
+	{
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		release_fx_lines(c);
+	}
+	if (delay_lines == 0 && reverb_lines == 0) {
+		return GAS_OK;
+	}
+	const size_t N = c->cfg.max_sources;
+	const gas_line_geo geo = make_line_geo(c->cfg.mix_rate);
+	// [<= N settings rows][<= N {slot, line[4]}][<= every line once {kind, line}] (line_mark_dirty / line_queue_zero)
+	const size_t upload = N * (sizeof(gas_fx_line_settings) + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t)) + ((size_t)delay_lines + reverb_lines) * 2 * sizeof(uint32_t);
+	std::vector<gas_fx_line_settings> defaults(N, fx_line_settings_defaults());
+	hipError_t e = hipSuccess;
+	auto step = [&e](hipError_t r) {
+		if (e == hipSuccess) {
+			e = r;
+		}
+	};
+	if (delay_lines) {
+		step(hipMalloc(&c->st.delay_pool, geo.delay_floats * sizeof(float) * delay_lines));
+		step(e == hipSuccess ? hipMemsetAsync(c->st.delay_pool, 0, geo.delay_floats * sizeof(float) * delay_lines, c->stream) : e);
+	}
+	if (reverb_lines) {
+		step(hipMalloc(&c->st.reverb_pool, geo.reverb_floats * sizeof(float) * reverb_lines));
+		step(e == hipSuccess ? hipMemsetAsync(c->st.reverb_pool, 0, geo.reverb_floats * sizeof(float) * reverb_lines, c->stream) : e);
+	}
+	step(hipMalloc(&c->st.line_of, sizeof(int32_t) * GAS_MAX_EFFECTS * N));
+	step(e == hipSuccess ? hipMemsetAsync(c->st.line_of, 0xff, sizeof(int32_t) * GAS_MAX_EFFECTS * N, c->stream) : e);
+	step(hipMalloc(&c->st.line_settings, sizeof(gas_fx_line_settings) * N));
+	step(e == hipSuccess ? hipMemcpy(c->st.line_settings, defaults.data(), sizeof(gas_fx_line_settings) * N, hipMemcpyHostToDevice) : e);
+	step(hipMalloc(&c->d_line_upload, upload));
+	step(hipHostMalloc(&c->h_line_upload, upload, hipHostMallocDefault));
+	step(e == hipSuccess ? hipStreamSynchronize(c->stream) : e);
+	if (e != hipSuccess) {
+		c->last_err = std::string("gas_ctx_reserve_fx_lines: ") + hipGetErrorString(e);
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		release_fx_lines(c);
+		return e == hipErrorOutOfMemory ? GAS_ERR_OUT_OF_MEMORY : GAS_ERR_DEVICE;
+	}
+	std::lock_guard<std::mutex> lk(c->params_mu);
+	c->line_geo = geo;
+	c->line_cap[0] = delay_lines;
+	c->line_cap[1] = reverb_lines;
+	for (int p = 0; p < 2; p++) { // handed out from line 0 up
+		const uint32_t n = p == 0 ? delay_lines : reverb_lines;
+		c->line_zero_pending[p].assign(n, 0);
+		c->line_free[p].resize(n);
+		for (uint32_t i = 0; i < n; i++) {
+			c->line_free[p][i] = n - 1 - i;
+		}
+	}
+	std::array<int32_t, GAS_MAX_EFFECTS> none;
+	none.fill(-1);
+	c->h_line_of.assign(N, none);
+	c->h_line = std::move(defaults);
+	c->line_dirty_flag.assign(N, 0);
 	return GAS_OK;
 }
 

@@ -13,6 +13,24 @@
 static_assert(sizeof(gas_params) == 128, "gas_params is a 128-byte POD");
 static_assert(sizeof(gas_audio_frame) == 8, "AudioFrame is 2 x f32");
 static_assert(sizeof(gas_fx_dyn_settings) == 12 * 4 * GAS_MAX_EFFECTS, "gas_fx_dyn_settings is 12 arrays by chain position");
+static_assert(sizeof(gas_fx_line_settings) == 21 * 4 * GAS_MAX_EFFECTS, "gas_fx_line_settings is 21 arrays by chain position");
+
+// GAS_FX_DELAY / GAS_FX_REVERB line geometry, fixed per context by the mix rate (gas_ctx_reserve_fx_lines).
+// Every line starts with GAS_LINE_HEADER floats of state; offsets below are in floats from the line's start.
+#define GAS_LINE_HEADER 64
+struct gas_line_geo {
+	// delay line: header {P, q, h[2]}, ring [ring_mask + 1][2 ears], feedback buffer [fb_frames][2 ears]
+	uint32_t ring_mask, fb_frames;
+	size_t delay_floats;
+	// reverb line: header {per ear e at 32 e: epos, h1, h2, comb pos[8], comb dh[8], allpass pos[4]}, then per ear
+	// the echo buffer, the 8 combs and the 4 allpasses
+	uint32_t echo_size;
+	uint32_t xs[2]; // extra spread frames per ear
+	uint32_t comb_size[2][8], ap_size[2][4];
+	uint32_t echo_off[2], comb_off[2][8], ap_off[2][4];
+	uint32_t ap_base[4]; // lrint(at[k] sr): the shortest limit allpass k can have
+	size_t reverb_floats;
+};
 
 // ---------------------------------------------------------------------------
 // Device-resident SpatializerPlaybackData (audio_spatializer_3d.h:85-99,
@@ -39,6 +57,12 @@ struct gas_dev_state {
 	float *dist_h; // [GAS_MAX_EFFECTS][2 ears][max_sources] the distortion's one-pole state h
 	float *comp_rundb; // [GAS_MAX_EFFECTS][max_sources] the compressor's smoothed over-threshold level
 	uint32_t dyn_stride; // max_sources
+	// GAS_FX_DELAY / GAS_FX_REVERB (k_fx_line.hip): settings, slot -> line table, the two line pools (nullptr until
+	// gas_ctx_reserve_fx_lines)
+	gas_fx_line_settings *line_settings; // [max_sources], by chain position
+	int32_t *line_of; // [GAS_MAX_EFFECTS][max_sources] line of chain position j in its kind's pool
+	float *delay_pool; // [delay lines][geo.delay_floats]
+	float *reverb_pool; // [reverb lines][geo.reverb_floats]
 };
 
 // Device-resident playback cursor: what SpatialPlaybackListNode + the engine's sampler hold.
@@ -184,6 +208,11 @@ hipError_t gas_launch_mix_reduce(hipStream_t stream, const float *partials, uint
 // k_fx_dyn.hip: a GAS_FX_DISTORTION / GAS_FX_COMPRESSOR stage of a staged chain (rows in -> dense rows out), settings
 // and state of chain position chain_pos; and the scatter of published gas_fx_dyn_settings rows into the slot table
 hipError_t gas_launch_fx_dyn(hipStream_t stream, int kind, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t chain_pos, float mix_rate, gas_audio_frame *rows_out);
+// k_fx_line.hip: a GAS_FX_DELAY / GAS_FX_REVERB stage (rows in -> dense rows out); the scatter of published settings
+// records ([m] gas_fx_line_settings, then [m] {slot, line[GAS_MAX_EFFECTS]}) and the zeroing of ([z] {kind, line}) lines
+hipError_t gas_launch_fx_line(hipStream_t stream, int kind, const gas_group_args &g, const gas_dev_state &st, const gas_line_geo &geo, uint32_t frames, uint32_t chain_pos, float mix_rate, gas_audio_frame *rows_out);
+hipError_t gas_launch_scatter_line(hipStream_t stream, const gas_dev_state &st, const gas_fx_line_settings *upload, const uint32_t *slot_lines, uint32_t n);
+hipError_t gas_launch_zero_lines(hipStream_t stream, const gas_dev_state &st, const gas_line_geo &geo, const uint32_t *kind_line, uint32_t n);
 hipError_t gas_launch_scatter_dyn(hipStream_t stream, gas_fx_dyn_settings *table, const gas_fx_dyn_settings *upload, const uint32_t *slots, uint32_t n);
 hipError_t gas_launch_scatter_params(hipStream_t stream, gas_params *table, const gas_params *upload, const uint32_t *slots, uint32_t n);
 hipError_t gas_launch_calc_spatialization(hipStream_t stream, const gas_spatializer3d_config *cfgs, const uint32_t *cfg_index, const gas_source_pose *poses, const gas_listener *listeners, uint32_t n_listeners, const uint32_t *slots, uint32_t n, gas_params *table, uint8_t *was_further, gas_params *out_params, const gas_area_send *areas = nullptr, const float *listener_area_pos = nullptr, gas_audio_frame *out_reverb = nullptr);

@@ -89,6 +89,10 @@ typedef enum gas_effect_kind {
 	 * (10 is not assigned: an effect kind the library does not know is GAS_ERR_INVALID_ARGUMENT / _UNSUPPORTED_CHAIN.) */
 	GAS_FX_DISTORTION = 11, /* [ENGINE] AudioEffectDistortion: per-ear one-pole split, the low band shaped by `mode` */
 	GAS_FX_COMPRESSOR = 12, /* [ENGINE] AudioEffectCompressor without sidechain: stereo-linked detector, one gain per frame */
+	/* The engine's time-domain kinds with long per-instance memory ("lines", reserved with gas_ctx_reserve_fx_lines);
+	 * settings per playback and chain position: gas_fx_line_settings. */
+	GAS_FX_DELAY = 13, /* [ENGINE] AudioEffectDelay: two panned taps and a low-passed feedback echo, ears independent */
+	GAS_FX_REVERB = 14, /* [ENGINE] AudioEffectReverb: predelay echo, 8 combs, 4 allpasses per ear (Freeverb tunings) */
 } gas_effect_kind;
 
 /* [ENGINE] AudioEffectDistortion::Mode */
@@ -226,6 +230,36 @@ typedef struct gas_fx_dyn_settings {
 	uint32_t reserved[GAS_MAX_EFFECTS];
 } gas_fx_dyn_settings;
 
+/* Settings of the GAS_FX_DELAY / GAS_FX_REVERB effects of one playback, by chain position like gas_fx_dyn_settings:
+ * position j is read only when effect j of the playback's chain is one of those kinds.  Read once per block.  A slot's
+ * settings start at the engine's resource defaults, given per field, when the slot is allocated.  Ranges (the engine's
+ * property ranges; gas_fx_line_settings_publish refuses anything outside them at any position): tap and feedback
+ * delays 0 .. 1500 ms, pans -1 .. 1, lowpass 1 .. 16000 Hz, predelay 20 .. 500 ms, predelay feedback 0 .. 0.98, the
+ * other reverb fields and delay_dry 0 .. 1, levels finite.  The *_active fields are on when not 0. */
+typedef struct gas_fx_line_settings {
+	float delay_dry[GAS_MAX_EFFECTS]; /* default 1 */
+	int32_t delay_tap1_active[GAS_MAX_EFFECTS]; /* default 1 */
+	float delay_tap1_ms[GAS_MAX_EFFECTS]; /* default 250 */
+	float delay_tap1_level_db[GAS_MAX_EFFECTS]; /* default -6 */
+	float delay_tap1_pan[GAS_MAX_EFFECTS]; /* default 0.2 */
+	int32_t delay_tap2_active[GAS_MAX_EFFECTS]; /* default 1 */
+	float delay_tap2_ms[GAS_MAX_EFFECTS]; /* default 500 */
+	float delay_tap2_level_db[GAS_MAX_EFFECTS]; /* default -12 */
+	float delay_tap2_pan[GAS_MAX_EFFECTS]; /* default -0.4 */
+	int32_t delay_feedback_active[GAS_MAX_EFFECTS]; /* default 0 */
+	float delay_feedback_ms[GAS_MAX_EFFECTS]; /* default 340 */
+	float delay_feedback_level_db[GAS_MAX_EFFECTS]; /* default -6 */
+	float delay_feedback_lowpass_hz[GAS_MAX_EFFECTS]; /* default 16000 */
+	float reverb_predelay_ms[GAS_MAX_EFFECTS]; /* default 150 */
+	float reverb_predelay_feedback[GAS_MAX_EFFECTS]; /* default 0.4 */
+	float reverb_room_size[GAS_MAX_EFFECTS]; /* default 0.8 */
+	float reverb_damping[GAS_MAX_EFFECTS]; /* default 0.5 */
+	float reverb_spread[GAS_MAX_EFFECTS]; /* default 1 */
+	float reverb_hipass[GAS_MAX_EFFECTS]; /* default 0 */
+	float reverb_dry[GAS_MAX_EFFECTS]; /* default 1 */
+	float reverb_wet[GAS_MAX_EFFECTS]; /* default 0.5 */
+} gas_fx_line_settings;
+
 /* Per-kernel device timing collected with HIP events on the context stream. */
 typedef struct gas_profile {
 	uint64_t launches; /* timed launches of the dominant kernel since the last reset */
@@ -284,6 +318,29 @@ int gas_fx_settings_publish(gas_ctx *ctx, const uint32_t *slots, const gas_fx_se
  * A distortion_mode outside 0..4 or a compressor ratio, attack or release that is not > 0 (at any position) is
  * GAS_ERR_INVALID_ARGUMENT, and nothing of the call is taken. */
 int gas_fx_dyn_settings_publish(gas_ctx *ctx, const uint32_t *slots, const gas_fx_dyn_settings *settings, uint32_t n);
+/* The same for gas_fx_line_settings: latest wins, snapshotted at the start of the next gas_process_block, physics
+ * thread.  A value outside the ranges given at gas_fx_line_settings (at any position) is GAS_ERR_INVALID_ARGUMENT, and
+ * nothing of the call is taken. */
+int gas_fx_line_settings_publish(gas_ctx *ctx, const uint32_t *slots, const gas_fx_line_settings *settings, uint32_t n);
+
+/* ---- delay memory of the GAS_FX_DELAY / GAS_FX_REVERB instances ("lines") ---------------------------------------
+ * Every GAS_FX_DELAY of a chain holds one delay line, every GAS_FX_REVERB one reverb line, from two device pools the
+ * caller sizes here.  Main thread, never concurrently with gas_process_block (like gas_hrtf_load).  The call allocates
+ * the pools, the slot -> line table, the device settings table and a pinned upload buffer; nothing is allocated on the
+ * audio thread.  (0, 0) releases everything.  While any line is held (by an allocated slot, or a freed one before the
+ * next block boundary) the call is GAS_ERR_INVALID_ARGUMENT.  reverb_lines > 0 needs lrint(0.02 mix_rate) >= frames and
+ * lrint(0.025306122 mix_rate) >= frames (about 25.6 kHz at 512 frames), else GAS_ERR_INVALID_ARGUMENT.  With sr the
+ * mix rate (f64), the bytes per line are:
+ *   delay:  256 + 8 R + 8 ((int)(1.5 sr) + 1), R = the smallest power of two >= (int)(1.5 sr) + 513
+ *           (about 1.5 MiB at 48 kHz);
+ *   reverb: 256 + 4 sum over the two ears e of (echo + sum_k comb_k(e) + sum_k allpass_k(e)),
+ *           echo = (int)(0.5 sr + 1), comb_k(e) = lrint(ct_k sr) + xs(e), allpass_k(e) = lrint(at_k sr) + xs(e),
+ *           xs(0) = 0, xs(1) = lrint(0.000521 sr), ct / at the Freeverb tunings of DESIGN.md 3.5e (about 300 KiB);
+ * each rounded up to a multiple of 256.  gas_source_alloc takes one line per such effect of the chain: with no pool
+ * reserved it is GAS_ERR_UNSUPPORTED_CHAIN, with too few free lines GAS_ERR_OUT_OF_SLOTS (nothing taken).  Lines go
+ * back with the slot at the next block boundary after gas_source_free; they are zeroed whenever they change hands and
+ * by gas_source_reset.  A gas_multi caller reserves per shard (gas_multi_shard). */
+int gas_ctx_reserve_fx_lines(gas_ctx *ctx, uint32_t delay_lines, uint32_t reverb_lines);
 
 /* ---- NEW AudioSpatializerHRTF resource: hrir is [dirs][2 ears][taps] f32, taps <= 256 */
 int gas_hrtf_load(gas_ctx *ctx, const float *hrir, uint32_t dirs, uint32_t taps);

@@ -119,6 +119,20 @@ def fx_line_settings_defaults(n):
     return d
 
 
+# the engine's graphic equalisers (one "bank" of state per instance, gas_ctx_reserve_fx_eq); settings:
+# gas_fx_eq_settings, band gains in dB by chain position, then band
+FX_EQ6, FX_EQ10, FX_EQ21 = 16, 17, 18
+EQ_MAX_BANDS = 21
+EQ_BANDS = {FX_EQ6: 6, FX_EQ10: 10, FX_EQ21: 21}
+FX_EQ_SETTINGS_DTYPE = np.dtype([("band_gain_db", np.float32, (MAX_EFFECTS, EQ_MAX_BANDS))])
+assert FX_EQ_SETTINGS_DTYPE.itemsize == 336
+
+
+def fx_eq_settings_defaults(n):
+    """0 dB at every position and band, n rows (what a slot starts with)."""
+    return np.zeros(n, FX_EQ_SETTINGS_DTYPE)
+
+
 MEM_HOST = 0
 MEM_DEVICE = 1
 FLAG_PEAKS_DRAINING_ONLY = 1
@@ -262,6 +276,8 @@ EXPORTS = [
     "gas_fx_dyn_settings_publish",
     "gas_fx_line_settings_publish",
     "gas_ctx_reserve_fx_lines",
+    "gas_fx_eq_settings_publish",
+    "gas_ctx_reserve_fx_eq",
     "gas_params_publish_batch",
     "gas_hrtf_load",
     "gas_hrtf_load_positions",
@@ -346,6 +362,8 @@ def load_library():
     L.gas_fx_dyn_settings_publish.argtypes = [vp, vp, vp, u32]
     L.gas_fx_line_settings_publish.argtypes = [vp, vp, vp, u32]
     L.gas_ctx_reserve_fx_lines.argtypes = [vp, u32, u32]
+    L.gas_fx_eq_settings_publish.argtypes = [vp, vp, vp, u32]
+    L.gas_ctx_reserve_fx_eq.argtypes = [vp, u32]
     L.gas_params_publish_batch.argtypes = [vp, vp, vp, u32, i32]
     L.gas_hrtf_load.argtypes = [vp, vp, u32, u32]
     L.gas_hrtf_load_positions.argtypes = [vp, vp, vp, u32, u32, u32, u32, i32, vp]
@@ -478,6 +496,20 @@ class SpatializerContext:
     def reserve_fx_lines(self, delay_lines, reverb_lines):
         """Size the GAS_FX_DELAY / GAS_FX_REVERB line pools (main thread, not during a callback); (0, 0) releases them."""
         self._check(self.lib.gas_ctx_reserve_fx_lines(self.h, int(delay_lines), int(reverb_lines)), "gas_ctx_reserve_fx_lines")
+
+    @staticmethod
+    def fx_eq_settings_defaults(n):
+        return fx_eq_settings_defaults(n)
+
+    def fx_eq_settings_publish(self, slots, settings):
+        s = np.ascontiguousarray(slots, dtype=np.uint32)
+        f = np.ascontiguousarray(settings, dtype=FX_EQ_SETTINGS_DTYPE)
+        assert s.shape == f.shape
+        self._check(self.lib.gas_fx_eq_settings_publish(self.h, _np_ptr(s), _np_ptr(f), len(s)), "gas_fx_eq_settings_publish")
+
+    def reserve_fx_eq(self, eq_banks):
+        """Size the GAS_FX_EQ6 / _EQ10 / _EQ21 bank pool (main thread, not during a callback); 0 releases it."""
+        self._check(self.lib.gas_ctx_reserve_fx_eq(self.h, int(eq_banks)), "gas_ctx_reserve_fx_eq")
 
     def params_publish_batch(self, slots, params):
         s = np.ascontiguousarray(slots, dtype=np.uint32)
@@ -678,6 +710,7 @@ class BatchedSpatializerHost:
         L.gas_host_set_effect_settings.argtypes = [vp, u32, vp]
         L.gas_host_set_effect_settings_dyn.argtypes = [vp, u32, vp]
         L.gas_host_set_effect_settings_line.argtypes = [vp, u32, vp]
+        L.gas_host_set_effect_settings_eq.argtypes = [vp, u32, vp]
         L.gas_host_set_release_fn.argtypes = [vp, vp, vp]
         L.gas_host_collect_released.argtypes = [vp]
         L.gas_host_set_process_effects_fn.argtypes = [vp, vp, vp]
@@ -767,6 +800,10 @@ class BatchedSpatializerHost:
     def set_effect_line_settings(self, pid, settings):
         f = np.ascontiguousarray(settings, dtype=FX_LINE_SETTINGS_DTYPE).reshape(1)
         return self.lib.gas_host_set_effect_settings_line(self.h, pid, _np_ptr(f))
+
+    def set_effect_settings_eq(self, pid, settings):
+        f = np.ascontiguousarray(settings, dtype=FX_EQ_SETTINGS_DTYPE).reshape(1)
+        return self.lib.gas_host_set_effect_settings_eq(self.h, pid, _np_ptr(f))
 
     def is_playback_active(self, pid):
         return bool(self.lib.gas_host_is_playback_active(self.h, pid))

@@ -12,6 +12,7 @@
 #include <cstring>
 #include <new>
 
+#include "gas_fx_eq_check.h"
 #include "gas_fx_line_check.h"
 #include "gas_internal.h"
 
@@ -44,7 +45,7 @@ struct SlotInfo {
 	uint8_t has_params = 0;
 	uint8_t pending_free = 0;
 	uint8_t dirty_state = 0; // state must be zeroed before reuse
-	uint16_t chain_sig = 0; // G_FX_GENERIC: effect kinds, 4 bits each, first effect in the low nibble
+	uint32_t chain_sig = 0; // G_FX_GENERIC: effect kinds, 8 bits each, first effect in the low byte
 	uint8_t draining = 0; // stream ended: the host's silence gate needs this source's peak (audio_spatializer.cpp:464)
 };
 
@@ -56,7 +57,7 @@ struct Group {
 
 // One run of G_FX_GENERIC entries that share a chain.
 struct ChainRange {
-	uint16_t sig = 0;
+	uint32_t sig = 0;
 	uint32_t offset = 0, count = 0; // relative to the group's offset
 	bool peak_all = true, peak_any = true; // which of its sources report their exact peak (GAS_FLAG_PEAKS_DRAINING_ONLY; read by a last stage that is k_hrtf_uni)
 };
@@ -144,6 +145,19 @@ struct gas_ctx {
 	std::vector<uint32_t> line_zero_list; // {kind, line} pairs, each line at most once (line_zero_pending)
 	std::vector<uint8_t> line_zero_pending[2]; // [pool][line]: queued in line_zero_list
 	unsigned char *h_line_upload = nullptr, *d_line_upload = nullptr;
+	// GAS_FX_EQ6 / _EQ10 / _EQ21 banks (gas_ctx_reserve_fx_eq), kept like the lines: pool size and free banks (alloc_mu),
+	// each slot's banks by chain position (written under alloc_mu and params_mu), settings mirror and what the next flush
+	// uploads (params_mu): [m settings][m {slot, bank[4]}][z bank] through one pinned staging buffer
+	uint32_t eq_cap = 0;
+	std::vector<uint32_t> eq_free;
+	std::vector<std::array<int32_t, GAS_MAX_EFFECTS>> h_eq_of;
+	std::vector<gas_fx_eq_settings> h_eq;
+	std::vector<uint8_t> eq_dirty_flag;
+	std::vector<uint32_t> eq_dirty_list;
+	std::vector<uint32_t> eq_zero_list; // banks, each at most once (eq_zero_pending)
+	std::vector<uint8_t> eq_zero_pending; // [bank]: queued in eq_zero_list
+	unsigned char *h_eq_upload = nullptr, *d_eq_upload = nullptr;
+	gas_eq_coefs eq_coefs[3] = {}; // EQ6, EQ10, EQ21 at the mix rate (make_eq_coefs)
 
 	// plain [HRTF] group of the cached list (k_hrtf_uni): which entries need their exact peak
 	uint32_t *h_peak_bits = nullptr, *d_peak_bits = nullptr; // two halves of (max_sources + 31) / 32 words: bit k = entry k of the plain-[HRTF] group / of the staged group
@@ -295,7 +309,7 @@ int group_of(int kind, const int32_t *fx, uint32_t n_fx) {
 	// reflection ring and one HRTF history per playback
 	int n_er = 0, n_hrtf = 0;
 	for (uint32_t j = 0; j < n_fx; j++) {
-		if ((fx[j] < GAS_FX_HIGHSHELF || fx[j] > GAS_FX_AMPLIFY) && (fx[j] < GAS_FX_DISTORTION || fx[j] > GAS_FX_REVERB)) {
+		if ((fx[j] < GAS_FX_HIGHSHELF || fx[j] > GAS_FX_AMPLIFY) && (fx[j] < GAS_FX_DISTORTION || fx[j] > GAS_FX_REVERB) && (fx[j] < GAS_FX_EQ6 || fx[j] > GAS_FX_EQ21)) {
 			return -1;
 		}
 		n_er += fx[j] == GAS_FX_EARLY_REFLECTIONS;
@@ -430,17 +444,63 @@ inline int line_pool_of(int kind) { // 0 delay, 1 reverb, -1 no line
 	return kind == GAS_FX_DELAY ? 0 : (kind == GAS_FX_REVERB ? 1 : -1);
 }
 
-uint16_t chain_signature(const int32_t *fx, uint32_t n_fx) {
-	uint16_t sig = 0;
+// Effect kinds by chain position, 8 bits each, first effect in the low byte.  The digits keep their order, so sorting by
+// signature orders chains of the kinds below 16 exactly as the earlier 4-bit digits did.
+// [ENGINE] the EQ6 / EQ10 / EQ21 presets' band centres (Hz)
+const double k_eq_freqs6[6] = { 32, 100, 320, 1000, 3200, 10000 };
+const double k_eq_freqs10[10] = { 31.25, 62.5, 125, 250, 500, 1000, 2000, 4000, 8000, 16000 };
+const double k_eq_freqs21[21] = { 22, 32, 44, 63, 90, 125, 175, 250, 350, 500, 700, 1000, 1400, 2000, 2800, 4000, 5600, 8000, 11000, 16000, 22000 };
+
+// [ENGINE] EQ::recalculate_band_coefficients in f64, rounded to f32.  A band whose formula has no real
+// root (a == 0 or a negative discriminant: the engine skips it and leaves its coefficients unset) gets c1 = c2 = c3 = 0.
+gas_eq_coefs make_eq_coefs(int kind, float mix_rate) {
+	const int B = gas_eq_bands(kind);
+	const double *f = kind == GAS_FX_EQ6 ? k_eq_freqs6 : (kind == GAS_FX_EQ10 ? k_eq_freqs10 : k_eq_freqs21);
+	const double sr = (double)mix_rate;
+	gas_eq_coefs q{};
+	for (int i = 0; i < B; i++) {
+		double octave_size;
+		if (i == 0) {
+			octave_size = log2(f[1]) - log2(f[0]);
+		} else if (i == B - 1) {
+			octave_size = log2(f[i]) - log2(f[i - 1]);
+		} else {
+			octave_size = ((log2(f[i]) - log2(f[i - 1])) + (log2(f[i + 1]) - log2(f[i]))) * 0.5;
+		}
+		const double frq_l = round(f[i] / pow(2.0, octave_size / 2.0));
+		const double s = 0.5; // sqrt(1/2) squared
+		const double th = 2.0 * M_PI * f[i] / sr, th_l = 2.0 * M_PI * frq_l / sr;
+		const double ct = cos(th), ctl = cos(th_l), stl = sin(th_l);
+		const double a = s * ct * ct - 2.0 * s * ctl * ct + s - stl * stl;
+		const double b = 2.0 * s * ctl * ctl + s * ct * ct - 2.0 * s * ctl * ct - s + stl * stl;
+		const double c = 0.25 * s * ct * ct - 0.5 * s * ctl * ct + 0.25 * s - 0.25 * stl * stl;
+		const double disc = b * b - 4.0 * a * c;
+		if (a == 0.0 || disc < 0.0) {
+			continue;
+		}
+		const double r1 = (-b + sqrt(disc)) / (2.0 * a);
+		q.c1[i] = (float)(2.0 * (0.5 - r1) / 2.0);
+		q.c2[i] = (float)(2.0 * r1);
+		q.c3[i] = (float)(2.0 * (0.5 + r1) * ct);
+	}
+	return q;
+}
+
+inline bool is_eq(int kind) {
+	return kind >= GAS_FX_EQ6 && kind <= GAS_FX_EQ21;
+}
+
+uint32_t chain_signature(const int32_t *fx, uint32_t n_fx) {
+	uint32_t sig = 0;
 	for (uint32_t j = 0; j < n_fx; j++) {
-		sig |= (uint16_t)(fx[j] & 0xf) << (4 * j);
+		sig |= (uint32_t)(fx[j] & 0xff) << (8 * j);
 	}
 	return sig;
 }
 
-bool chain_has(uint16_t sig, int kind) {
+bool chain_has(uint32_t sig, int kind) {
 	for (int j = 0; j < 4; j++) {
-		if (((sig >> (4 * j)) & 0xf) == kind) {
+		if (((sig >> (8 * j)) & 0xff) == kind) {
 			return true;
 		}
 	}
@@ -454,7 +514,7 @@ bool chain_has(uint16_t sig, int kind) {
 inline bool range_ends_in_uni(const ChainRange &r, bool staged_uni) {
 	int last = 0, n_fx = 0;
 	for (int j = 0; j < 4; j++) {
-		const int kind = (r.sig >> (4 * j)) & 0xf;
+		const int kind = (r.sig >> (8 * j)) & 0xff;
 		if (kind) {
 			last = kind;
 			n_fx++;
@@ -842,8 +902,8 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 					const uint32_t *peak_rows = in.rows;
 					const bool last_is_uni = range_ends_in_uni(r, staged_uni);
 					const bool own = groups == c->groups; // the context's own list: GAS_FLAG_PEAKS_DRAINING_ONLY's bits exist
-					const int k0 = r.sig & 0xf;
-					if (last_is_uni && c->uni_flt_enabled && (r.sig >> 4) == GAS_FX_HRTF && (k0 == GAS_FX_HIGHSHELF || (k0 >= GAS_FX_LOWPASS && k0 <= GAS_FX_LOWSHELF)) && gas_shelf_scan_applies(k0 == GAS_FX_HIGHSHELF ? GAS_MODE_FX_HIGHSHELF : GAS_MODE_FX_FILTER, r.count, F)) {
+					const int k0 = r.sig & 0xff;
+					if (last_is_uni && c->uni_flt_enabled && (r.sig >> 8) == GAS_FX_HRTF && (k0 == GAS_FX_HIGHSHELF || (k0 >= GAS_FX_LOWPASS && k0 <= GAS_FX_LOWSHELF)) && gas_shelf_scan_applies(k0 == GAS_FX_HIGHSHELF ? GAS_MODE_FX_HIGHSHELF : GAS_MODE_FX_FILTER, r.count, F)) {
 						// [one-biquad filter, HRTF]: one launch (k_hrtf_uni<FLT>), no rows in between.  The filter there is the
 						// scan form, so it is taken exactly where the two-launch road would take k_shelf_scan (same bits either
 						// way; small callbacks and GAS_SHELF_SCAN=0 keep the engine's serial order)
@@ -852,11 +912,11 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 						continue;
 					}
 					for (int j = 0; j < 4 && e == hipSuccess; j++) {
-						const int kind = (r.sig >> (4 * j)) & 0xf;
+						const int kind = (r.sig >> (8 * j)) & 0xff;
 						if (!kind) {
 							break;
 						}
-						if (last_is_uni && c->uni_er_enabled && kind == GAS_FX_EARLY_REFLECTIONS && j < 3 && ((r.sig >> (4 * (j + 1))) & 0xf) == GAS_FX_HRTF) {
+						if (last_is_uni && c->uni_er_enabled && kind == GAS_FX_EARLY_REFLECTIONS && j < 3 && ((r.sig >> (8 * (j + 1))) & 0xff) == GAS_FX_HRTF) {
 							// ... [ER, HRTF] at the end of a longer chain: both in the last launch (k_hrtf_uni<ER>), no rows in between
 							gas_group_args gu = in;
 							gu.peak_rows = peak_rows;
@@ -881,6 +941,8 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 							e = gas_launch_fx_dyn(c->stream, kind, in, c->st, F, (uint32_t)j, c->cfg.mix_rate, outb);
 						} else if (kind == GAS_FX_DELAY || kind == GAS_FX_REVERB) { // k_fx_line.hip, state in the slot's line of chain position j
 							e = gas_launch_fx_line(c->stream, kind, in, c->st, c->line_geo, F, (uint32_t)j, c->cfg.mix_rate, outb);
+						} else if (is_eq(kind)) { // k_fx_eq.hip, state in the slot's bank of chain position j
+							e = gas_launch_fx_eq(c->stream, kind, in, c->st, c->eq_coefs[kind - GAS_FX_EQ6], F, (uint32_t)j, outb);
 						} else {
 							e = gas_launch_hrtf_rows(c->stream, (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) != 0, in, c->st, c->tab, c->d_tw, F, outb);
 						}
@@ -1221,9 +1283,9 @@ void line_mark_dirty(gas_ctx *c, uint32_t s) {
 
 // Queues the zeroing of slot s's lines (chain signature sig), each line at most once until the next flush, so the
 // queue never holds more pairs than the pools have lines (the upload buffer's zero section); params_mu held.
-void line_queue_zero(gas_ctx *c, uint32_t s, uint16_t sig) {
+void line_queue_zero(gas_ctx *c, uint32_t s, uint32_t sig) {
 	for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
-		const int kind = (sig >> (4 * j)) & 0xf;
+		const int kind = (sig >> (8 * j)) & 0xff;
 		const int pool = line_pool_of(kind);
 		const int32_t line = c->h_line_of[s][j];
 		if (pool >= 0 && line >= 0 && !c->line_zero_pending[pool][line]) {
@@ -1257,6 +1319,86 @@ void release_fx_lines(gas_ctx *c) {
 	c->line_zero_pending[1].clear();
 }
 
+// gas_fx_eq_settings_publish's rows, new slot -> bank entries and banks to zero: one copy of
+// [m settings][m {slot, bank[4]}][z bank], one scatter, one zeroing launch.
+int flush_fx_eq(gas_ctx *c) {
+	if (!c->h_eq_upload) {
+		return GAS_OK;
+	}
+	uint32_t m = 0, z = 0;
+	{
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		m = (uint32_t)c->eq_dirty_list.size();
+		z = (uint32_t)c->eq_zero_list.size();
+		if (m == 0 && z == 0) {
+			return GAS_OK;
+		}
+		gas_fx_eq_settings *hs = reinterpret_cast<gas_fx_eq_settings *>(c->h_eq_upload);
+		uint32_t *hsb = reinterpret_cast<uint32_t *>(c->h_eq_upload + (size_t)m * sizeof(gas_fx_eq_settings));
+		for (uint32_t i = 0; i < m; i++) {
+			const uint32_t s = c->eq_dirty_list[i];
+			hs[i] = c->h_eq[s];
+			hsb[i * (1 + GAS_MAX_EFFECTS)] = s;
+			for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
+				hsb[i * (1 + GAS_MAX_EFFECTS) + 1 + j] = (uint32_t)c->h_eq_of[s][j];
+			}
+			c->eq_dirty_flag[s] = 0;
+		}
+		std::memcpy(hsb + (size_t)m * (1 + GAS_MAX_EFFECTS), c->eq_zero_list.data(), (size_t)z * sizeof(uint32_t));
+		for (uint32_t i = 0; i < z; i++) {
+			c->eq_zero_pending[c->eq_zero_list[i]] = 0;
+		}
+		c->eq_dirty_list.clear();
+		c->eq_zero_list.clear();
+	}
+	const size_t zoff = (size_t)m * (sizeof(gas_fx_eq_settings) + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t));
+	GAS_HIP(c, hipMemcpyAsync(c->d_eq_upload, c->h_eq_upload, zoff + (size_t)z * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	GAS_HIP(c, gas_launch_scatter_eq(c->stream, c->st, reinterpret_cast<const gas_fx_eq_settings *>(c->d_eq_upload), reinterpret_cast<const uint32_t *>(c->d_eq_upload + (size_t)m * sizeof(gas_fx_eq_settings)), m));
+	GAS_HIP(c, gas_launch_zero_banks(c->stream, c->st, reinterpret_cast<const uint32_t *>(c->d_eq_upload + zoff), z));
+	GAS_HIP(c, hipStreamSynchronize(c->stream)); // the pinned staging buffer is reused by the next flush
+	return GAS_OK;
+}
+
+// Marks slot s's EQ settings row (and its bank table row) for the next flush; params_mu held.
+void eq_mark_dirty(gas_ctx *c, uint32_t s) {
+	if (!c->eq_dirty_flag[s]) {
+		c->eq_dirty_flag[s] = 1;
+		c->eq_dirty_list.push_back(s);
+	}
+}
+
+// Queues the zeroing of slot s's banks (chain signature sig), each bank at most once until the next flush, so the queue
+// never holds more entries than the pool has banks (the upload buffer's zero section); params_mu held.
+void eq_queue_zero(gas_ctx *c, uint32_t s, uint32_t sig) {
+	for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
+		const int32_t bank = c->h_eq_of[s][j];
+		if (is_eq((sig >> (8 * j)) & 0xff) && bank >= 0 && !c->eq_zero_pending[bank]) {
+			c->eq_zero_pending[bank] = 1;
+			c->eq_zero_list.push_back((uint32_t)bank);
+		}
+	}
+}
+
+void release_fx_eq(gas_ctx *c) {
+	(void)hipFree(c->st.eq_pool);
+	(void)hipFree(c->st.eq_of);
+	(void)hipFree(c->st.eq_settings);
+	(void)hipFree(c->d_eq_upload);
+	(void)hipHostFree(c->h_eq_upload);
+	c->st.eq_pool = nullptr;
+	c->st.eq_of = nullptr;
+	c->st.eq_settings = nullptr;
+	c->d_eq_upload = c->h_eq_upload = nullptr;
+	c->eq_cap = 0;
+	c->eq_free.clear();
+	c->h_eq_of.clear();
+	c->h_eq.clear();
+	c->eq_dirty_flag.clear();
+	c->eq_dirty_list.clear();
+	c->eq_zero_list.clear();
+	c->eq_zero_pending.clear();
+}
+
 int flush_params(gas_ctx *c) {
 	uint32_t m = 0;
 	{
@@ -1279,7 +1421,8 @@ int flush_params(gas_ctx *c) {
 	}
 	int rc = flush_fx_settings(c);
 	rc = rc != GAS_OK ? rc : flush_fx_dyn_settings(c);
-	return rc != GAS_OK ? rc : flush_fx_lines(c);
+	rc = rc != GAS_OK ? rc : flush_fx_lines(c);
+	return rc != GAS_OK ? rc : flush_fx_eq(c);
 }
 
 void stream_rows_sync_back(gas_ctx *c);
@@ -1312,10 +1455,19 @@ int apply_pending_frees(gas_ctx *c) {
 		if (!c->h_line_of.empty()) { // its lines go back to the pools (zeroed when they are handed out again)
 			std::lock_guard<std::mutex> lk(c->params_mu); // (h_line_of is read by the flush under params_mu)
 			for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
-				const int pool = line_pool_of((si.chain_sig >> (4 * j)) & 0xf);
+				const int pool = line_pool_of((si.chain_sig >> (8 * j)) & 0xff);
 				if (pool >= 0 && c->h_line_of[s][j] >= 0) {
 					c->line_free[pool].push_back((uint32_t)c->h_line_of[s][j]);
 					c->h_line_of[s][j] = -1;
+				}
+			}
+		}
+		if (!c->h_eq_of.empty()) { // its banks go back to the pool (zeroed when they are handed out again)
+			std::lock_guard<std::mutex> lk(c->params_mu);
+			for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
+				if (is_eq((si.chain_sig >> (8 * j)) & 0xff) && c->h_eq_of[s][j] >= 0) {
+					c->eq_free.push_back((uint32_t)c->h_eq_of[s][j]);
+					c->h_eq_of[s][j] = -1;
 				}
 			}
 		}
@@ -1401,7 +1553,7 @@ int build_groups(gas_ctx *c, const uint32_t *slots, uint32_t n) {
 		for (uint32_t k = 0; k < gg.count; k++) {
 			hs[gg.offset + k] = ts[k];
 			hr[gg.offset + k] = tr[k];
-			const uint16_t sig = c->slots[ts[k]].chain_sig;
+			const uint32_t sig = c->slots[ts[k]].chain_sig;
 			if (c->chain_ranges.empty() || c->chain_ranges.back().sig != sig) {
 				ChainRange r;
 				r.sig = sig;
@@ -1558,6 +1710,7 @@ void gas_ctx_destroy(gas_ctx *c) {
 	(void)hipFree(c->d_dyn_upload);
 	(void)hipHostFree(c->h_dyn_upload);
 	release_fx_lines(c);
+	release_fx_eq(c);
 	(void)hipFree(c->d_slots);
 	(void)hipFree(c->d_rows);
 	(void)hipFree(c->d_slots_rows);
@@ -1836,22 +1989,27 @@ int gas_source_alloc(gas_ctx *c, int kind, const int32_t *effects, uint32_t n_ef
 	if (g == -2) {
 		return GAS_ERR_UNSUPPORTED_CHAIN;
 	}
-	const uint16_t sig = (g == G_FX_GENERIC || (kind == GAS_KIND_EFFECT && n_effects > 0)) ? chain_signature(effects, n_effects) : 0; // fused chains keep theirs too: a bus callback runs them staged
+	const uint32_t sig = (g == G_FX_GENERIC || (kind == GAS_KIND_EFFECT && n_effects > 0)) ? chain_signature(effects, n_effects) : 0; // fused chains keep theirs too: a bus callback runs them staged
 	if ((g == G_FX_ER || g == G_FX_ER_HRTF || (g == G_FX_GENERIC && chain_has(sig, GAS_FX_EARLY_REFLECTIONS))) && c->cfg.er_ring_frames == 0) {
 		return GAS_ERR_UNSUPPORTED_CHAIN;
 	}
 	uint32_t need[2] = { 0, 0 }; // delay / reverb lines of the chain
+	uint32_t need_eq = 0; // EQ banks of the chain
 	for (uint32_t j = 0; j < n_effects; j++) {
 		const int pool = line_pool_of(effects[j]);
 		if (pool >= 0) {
 			need[pool]++;
 		}
+		need_eq += is_eq(effects[j]);
 	}
 	std::lock_guard<std::mutex> alloc_lk(c->alloc_mu); // any thread (instantiate_playback_data runs on the physics thread, audio_spatializer.cpp:69)
 	if (need[0] + need[1] > 0 && c->line_cap[0] == 0 && c->line_cap[1] == 0) {
 		return GAS_ERR_UNSUPPORTED_CHAIN; // no pool reserved (gas_ctx_reserve_fx_lines)
 	}
-	if (c->free_list.empty() || c->line_free[0].size() < need[0] || c->line_free[1].size() < need[1]) {
+	if (need_eq > 0 && c->eq_cap == 0) {
+		return GAS_ERR_UNSUPPORTED_CHAIN; // no bank pool reserved (gas_ctx_reserve_fx_eq)
+	}
+	if (c->free_list.empty() || c->line_free[0].size() < need[0] || c->line_free[1].size() < need[1] || c->eq_free.size() < need_eq) { // all or nothing
 		return GAS_ERR_OUT_OF_SLOTS;
 	}
 	const uint32_t s = c->free_list.back();
@@ -1903,6 +2061,20 @@ int gas_source_alloc(gas_ctx *c, int kind, const int32_t *effects, uint32_t n_ef
 		c->h_line[s] = fx_line_settings_defaults();
 		line_mark_dirty(c, s);
 		line_queue_zero(c, s, sig);
+	}
+	if (need_eq > 0) { // one bank per equaliser, zeroed and entered in the table at the next flush
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		for (uint32_t j = 0; j < GAS_MAX_EFFECTS; j++) {
+			if (j < n_effects && is_eq(effects[j])) {
+				c->h_eq_of[s][j] = (int32_t)c->eq_free.back();
+				c->eq_free.pop_back();
+			} else {
+				c->h_eq_of[s][j] = -1;
+			}
+		}
+		c->h_eq[s] = gas_fx_eq_settings{}; // 0 dB everywhere
+		eq_mark_dirty(c, s);
+		eq_queue_zero(c, s, sig);
 	}
 	return GAS_OK;
 }
@@ -1956,6 +2128,10 @@ int gas_source_reset(gas_ctx *c, uint32_t slot) {
 		if (!c->h_line_of.empty() && c->slots[slot].used) {
 			std::lock_guard<std::mutex> lk(c->params_mu);
 			line_queue_zero(c, slot, c->slots[slot].chain_sig);
+		}
+		if (!c->h_eq_of.empty() && c->slots[slot].used) { // and its EQ banks
+			std::lock_guard<std::mutex> lk(c->params_mu);
+			eq_queue_zero(c, slot, c->slots[slot].chain_sig);
 		}
 	}
 	return GAS_OK;
@@ -2121,6 +2297,89 @@ int gas_ctx_reserve_fx_lines(gas_ctx *c, uint32_t delay_lines, uint32_t reverb_l
 	c->h_line_of.assign(N, none);
 	c->h_line = std::move(defaults);
 	c->line_dirty_flag.assign(N, 0);
+	return GAS_OK;
+}
+
+int gas_fx_eq_settings_publish(gas_ctx *c, const uint32_t *slots, const gas_fx_eq_settings *settings, uint32_t n) {
+	if (!c || (n > 0 && (!slots || !settings))) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	for (uint32_t i = 0; i < n; i++) {
+		if (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used) {
+			return GAS_ERR_BAD_SLOT;
+		}
+		if (!gas_fx_eq_settings_valid(settings[i])) {
+			return GAS_ERR_INVALID_ARGUMENT;
+		}
+	}
+	std::lock_guard<std::mutex> lk(c->params_mu);
+	if (c->h_eq.empty()) { // no pool reserved: no slot has an equaliser the settings could reach
+		return GAS_OK;
+	}
+	for (uint32_t i = 0; i < n; i++) {
+		c->h_eq[slots[i]] = settings[i];
+		eq_mark_dirty(c, slots[i]);
+	}
+	return GAS_OK;
+}
+
+int gas_ctx_reserve_fx_eq(gas_ctx *c, uint32_t eq_banks) {
+	if (!c) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	std::lock_guard<std::mutex> alloc_lk(c->alloc_mu);
+	if (c->eq_free.size() != c->eq_cap) {
+		return GAS_ERR_INVALID_ARGUMENT; // banks are held
+	}
+	GAS_HIP(c, hipSetDevice(c->cfg.device));
+	GAS_HIP(c, hipStreamSynchronize(c->stream));
+	{
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		release_fx_eq(c);
+	}
+	if (eq_banks == 0) {
+		return GAS_OK;
+	}
+	const size_t N = c->cfg.max_sources;
+	// [<= N settings rows][<= N {slot, bank[4]}][<= every bank once] (eq_mark_dirty / eq_queue_zero)
+	const size_t upload = N * (sizeof(gas_fx_eq_settings) + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t)) + (size_t)eq_banks * sizeof(uint32_t);
+	std::vector<gas_fx_eq_settings> defaults(N, gas_fx_eq_settings{});
+	hipError_t e = hipSuccess;
+	auto step = [&e](hipError_t r) {
+		if (e == hipSuccess) {
+			e = r;
+		}
+	};
+	step(hipMalloc(&c->st.eq_pool, sizeof(float) * GAS_EQ_BANK_FLOATS * eq_banks));
+	step(e == hipSuccess ? hipMemsetAsync(c->st.eq_pool, 0, sizeof(float) * GAS_EQ_BANK_FLOATS * eq_banks, c->stream) : e);
+	step(hipMalloc(&c->st.eq_of, sizeof(int32_t) * GAS_MAX_EFFECTS * N));
+	step(e == hipSuccess ? hipMemsetAsync(c->st.eq_of, 0xff, sizeof(int32_t) * GAS_MAX_EFFECTS * N, c->stream) : e);
+	step(hipMalloc(&c->st.eq_settings, sizeof(gas_fx_eq_settings) * N));
+	step(e == hipSuccess ? hipMemsetAsync(c->st.eq_settings, 0, sizeof(gas_fx_eq_settings) * N, c->stream) : e);
+	step(hipMalloc(&c->d_eq_upload, upload));
+	step(hipHostMalloc(&c->h_eq_upload, upload, hipHostMallocDefault));
+	step(e == hipSuccess ? hipStreamSynchronize(c->stream) : e);
+	if (e != hipSuccess) {
+		c->last_err = std::string("gas_ctx_reserve_fx_eq: ") + hipGetErrorString(e);
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		release_fx_eq(c);
+		return e == hipErrorOutOfMemory ? GAS_ERR_OUT_OF_MEMORY : GAS_ERR_DEVICE;
+	}
+	std::lock_guard<std::mutex> lk(c->params_mu);
+	for (int k = 0; k < 3; k++) {
+		c->eq_coefs[k] = make_eq_coefs(GAS_FX_EQ6 + k, c->cfg.mix_rate);
+	}
+	c->eq_cap = eq_banks;
+	c->eq_zero_pending.assign(eq_banks, 0);
+	c->eq_free.resize(eq_banks);
+	for (uint32_t i = 0; i < eq_banks; i++) { // handed out from bank 0 up
+		c->eq_free[i] = eq_banks - 1 - i;
+	}
+	std::array<int32_t, GAS_MAX_EFFECTS> none;
+	none.fill(-1);
+	c->h_eq_of.assign(N, none);
+	c->h_eq = std::move(defaults);
+	c->eq_dirty_flag.assign(N, 0);
 	return GAS_OK;
 }
 

@@ -14,6 +14,15 @@ static_assert(sizeof(gas_params) == 128, "gas_params is a 128-byte POD");
 static_assert(sizeof(gas_audio_frame) == 8, "AudioFrame is 2 x f32");
 static_assert(sizeof(gas_fx_dyn_settings) == 12 * 4 * GAS_MAX_EFFECTS, "gas_fx_dyn_settings is 12 arrays by chain position");
 static_assert(sizeof(gas_fx_line_settings) == 21 * 4 * GAS_MAX_EFFECTS, "gas_fx_line_settings is 21 arrays by chain position");
+static_assert(sizeof(gas_fx_eq_settings) == 336, "gas_fx_eq_settings is [GAS_MAX_EFFECTS][21] f32");
+
+// GAS_FX_EQ6 / _EQ10 / _EQ21 (k_fx_eq.hip): one bank of state per instance, [21 bands][a2, a3, b2, b3]
+// [2 ears] floats (the engine's BandProcess history per band and ear), and the per-band coefficients of one preset at
+// the context's mix rate (computed in f64, rounded to f32; 0 for a band whose formula has no real root)
+#define GAS_EQ_BANK_FLOATS (GAS_EQ_MAX_BANDS * 8)
+struct gas_eq_coefs {
+	float c1[GAS_EQ_MAX_BANDS], c2[GAS_EQ_MAX_BANDS], c3[GAS_EQ_MAX_BANDS];
+};
 
 // GAS_FX_DELAY / GAS_FX_REVERB line geometry, fixed per context by the mix rate (gas_ctx_reserve_fx_lines).
 // Every line starts with GAS_LINE_HEADER floats of state; offsets below are in floats from the line's start.
@@ -63,6 +72,11 @@ struct gas_dev_state {
 	int32_t *line_of; // [GAS_MAX_EFFECTS][max_sources] line of chain position j in its kind's pool
 	float *delay_pool; // [delay lines][geo.delay_floats]
 	float *reverb_pool; // [reverb lines][geo.reverb_floats]
+	// GAS_FX_EQ6 / _EQ10 / _EQ21 (k_fx_eq.hip): settings, slot -> bank table, the bank pool (nullptr until
+	// gas_ctx_reserve_fx_eq)
+	gas_fx_eq_settings *eq_settings; // [max_sources], by chain position
+	int32_t *eq_of; // [GAS_MAX_EFFECTS][max_sources] bank of chain position j
+	float *eq_pool; // [banks][GAS_EQ_BANK_FLOATS]
 };
 
 // Device-resident playback cursor: what SpatialPlaybackListNode + the engine's sampler hold.
@@ -212,6 +226,13 @@ hipError_t gas_launch_fx_dyn(hipStream_t stream, int kind, const gas_group_args 
 // records ([m] gas_fx_line_settings, then [m] {slot, line[GAS_MAX_EFFECTS]}) and the zeroing of ([z] {kind, line}) lines
 hipError_t gas_launch_fx_line(hipStream_t stream, int kind, const gas_group_args &g, const gas_dev_state &st, const gas_line_geo &geo, uint32_t frames, uint32_t chain_pos, float mix_rate, gas_audio_frame *rows_out);
 hipError_t gas_launch_scatter_line(hipStream_t stream, const gas_dev_state &st, const gas_fx_line_settings *upload, const uint32_t *slot_lines, uint32_t n);
+// k_fx_eq.hip: a GAS_FX_EQ6 / _EQ10 / _EQ21 stage (rows in -> dense rows out) with the preset's coefficients; the
+// scatter of published settings records ([m] gas_fx_eq_settings, then [m] {slot, bank[GAS_MAX_EFFECTS]}) and the
+// zeroing of ([z] bank) banks
+hipError_t gas_launch_fx_eq(hipStream_t stream, int kind, const gas_group_args &g, const gas_dev_state &st, const gas_eq_coefs &coefs, uint32_t frames, uint32_t chain_pos, gas_audio_frame *rows_out);
+hipError_t gas_launch_scatter_eq(hipStream_t stream, const gas_dev_state &st, const gas_fx_eq_settings *upload, const uint32_t *slot_banks, uint32_t n);
+hipError_t gas_launch_zero_banks(hipStream_t stream, const gas_dev_state &st, const uint32_t *banks, uint32_t n);
+int gas_eq_bands(int kind); // 6, 10, 21; 0 for any other kind
 hipError_t gas_launch_zero_lines(hipStream_t stream, const gas_dev_state &st, const gas_line_geo &geo, const uint32_t *kind_line, uint32_t n);
 hipError_t gas_launch_scatter_dyn(hipStream_t stream, gas_fx_dyn_settings *table, const gas_fx_dyn_settings *upload, const uint32_t *slots, uint32_t n);
 hipError_t gas_launch_scatter_params(hipStream_t stream, gas_params *table, const gas_params *upload, const uint32_t *slots, uint32_t n);

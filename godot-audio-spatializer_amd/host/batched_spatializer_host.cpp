@@ -21,12 +21,14 @@
 #include <vector>
 
 #include "../../include/gas_amd_host.h"
+#include "../csrc/gas_fx_eq_check.h"
 #include "../csrc/gas_fx_line_check.h"
 
 // A weak reference: the host layer is also built for the CPU against a stand-in of the library's entries (the
 // ThreadSanitizer build) that does not define this one; in libgas_amd.so it is always there.
 #pragma weak gas_fx_dyn_settings_publish
 #pragma weak gas_fx_line_settings_publish
+#pragma weak gas_fx_eq_settings_publish
 
 namespace {
 
@@ -83,13 +85,14 @@ struct Playback {
 };
 
 struct Command {
-	enum Kind { START, PARAMS, FX_SETTINGS, FX_DYN_SETTINGS, FX_LINE_SETTINGS } kind = START;
+	enum Kind { START, PARAMS, FX_SETTINGS, FX_DYN_SETTINGS, FX_LINE_SETTINGS, FX_EQ_SETTINGS } kind = START;
 	uint32_t id = 0;
 	std::unique_ptr<Playback> playback; // START
 	gas_params params{}; // PARAMS
 	gas_fx_settings fx_settings{}; // FX_SETTINGS
 	gas_fx_dyn_settings fx_dyn_settings{}; // FX_DYN_SETTINGS
 	gas_fx_line_settings fx_line_settings{}; // FX_LINE_SETTINGS
+	gas_fx_eq_settings fx_eq_settings{}; // FX_EQ_SETTINGS
 };
 
 // [ENGINE] Math::db_to_linear
@@ -241,6 +244,11 @@ struct gas_host {
 				auto it = by_id.find(c.id);
 				if (it != by_id.end() && gas_fx_line_settings_publish) {
 					gas_fx_line_settings_publish(ctx, &it->second->slot, &c.fx_line_settings, 1); // (validated when queued)
+				}
+			} else if (c.kind == Command::FX_EQ_SETTINGS) {
+				auto it = by_id.find(c.id);
+				if (it != by_id.end() && gas_fx_eq_settings_publish) {
+					gas_fx_eq_settings_publish(ctx, &it->second->slot, &c.fx_eq_settings, 1); // (validated when queued)
 				}
 			} else {
 				auto it = by_id.find(c.id);
@@ -580,6 +588,25 @@ int gas_host_set_effect_settings_line(gas_host *h, uint32_t id, const gas_fx_lin
 	c.kind = Command::FX_LINE_SETTINGS;
 	c.id = id;
 	c.fx_line_settings = *settings;
+	std::lock_guard<std::mutex> lk(h->inbox_mu);
+	h->inbox.push_back(std::move(c));
+	return GAS_OK;
+}
+
+int gas_host_set_effect_settings_eq(gas_host *h, uint32_t id, const gas_fx_eq_settings *settings) {
+	if (!h || !h->lookup(id)) {
+		return GAS_ERR_BAD_SLOT;
+	}
+	if (!settings) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (!gas_fx_eq_settings_valid(*settings)) { // gas_fx_eq_settings_publish's rule, checked here: the audio thread cannot report it
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	Command c;
+	c.kind = Command::FX_EQ_SETTINGS;
+	c.id = id;
+	c.fx_eq_settings = *settings;
 	std::lock_guard<std::mutex> lk(h->inbox_mu);
 	h->inbox.push_back(std::move(c));
 	return GAS_OK;

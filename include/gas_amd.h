@@ -93,6 +93,12 @@ typedef enum gas_effect_kind {
 	 * settings per playback and chain position: gas_fx_line_settings. */
 	GAS_FX_DELAY = 13, /* [ENGINE] AudioEffectDelay: two panned taps and a low-passed feedback echo, ears independent */
 	GAS_FX_REVERB = 14, /* [ENGINE] AudioEffectReverb: predelay echo, 8 combs, 4 allpasses per ear (Freeverb tunings) */
+	/* The engine's graphic equalisers: one unity-peak resonator per band and ear, summed with a gain per band (state in
+	 * "banks", reserved with gas_ctx_reserve_fx_eq); settings per playback and chain position: gas_fx_eq_settings.
+	 * (15 is not assigned.) */
+	GAS_FX_EQ6 = 16, /* [ENGINE] AudioEffectEQ6: bands at 32, 100, 320, 1000, 3200, 10000 Hz */
+	GAS_FX_EQ10 = 17, /* [ENGINE] AudioEffectEQ10: bands at 31.25 Hz and every octave up to 16 kHz */
+	GAS_FX_EQ21 = 18, /* [ENGINE] AudioEffectEQ21: bands at 22 Hz to 22 kHz, half an octave apart */
 } gas_effect_kind;
 
 /* [ENGINE] AudioEffectDistortion::Mode */
@@ -260,6 +266,16 @@ typedef struct gas_fx_line_settings {
 	float reverb_wet[GAS_MAX_EFFECTS]; /* default 0.5 */
 } gas_fx_line_settings;
 
+/* Settings of the GAS_FX_EQ6 / GAS_FX_EQ10 / GAS_FX_EQ21 effects of one playback, by chain position, then band: position
+ * j is read only when effect j of the playback's chain is one of those kinds; EQ6 reads bands 0..5, EQ10 bands 0..9.
+ * Read once per block (no ramp).  A slot's settings start at 0 dB everywhere when it is allocated.  Range (the engine's
+ * property range; gas_fx_eq_settings_publish refuses anything outside it or not finite, at any position and band, used
+ * or not): -60 .. 24 dB. */
+#define GAS_EQ_MAX_BANDS 21
+typedef struct gas_fx_eq_settings {
+	float band_gain_db[GAS_MAX_EFFECTS][GAS_EQ_MAX_BANDS];
+} gas_fx_eq_settings;
+
 /* Per-kernel device timing collected with HIP events on the context stream. */
 typedef struct gas_profile {
 	uint64_t launches; /* timed launches of the dominant kernel since the last reset */
@@ -322,6 +338,10 @@ int gas_fx_dyn_settings_publish(gas_ctx *ctx, const uint32_t *slots, const gas_f
  * thread.  A value outside the ranges given at gas_fx_line_settings (at any position) is GAS_ERR_INVALID_ARGUMENT, and
  * nothing of the call is taken. */
 int gas_fx_line_settings_publish(gas_ctx *ctx, const uint32_t *slots, const gas_fx_line_settings *settings, uint32_t n);
+/* The same for gas_fx_eq_settings: latest wins, snapshotted at the start of the next gas_process_block, physics thread.
+ * A gain outside -60 .. 24 dB or not finite (at any position and band) is GAS_ERR_INVALID_ARGUMENT, and nothing of the
+ * call is taken. */
+int gas_fx_eq_settings_publish(gas_ctx *ctx, const uint32_t *slots, const gas_fx_eq_settings *settings, uint32_t n);
 
 /* ---- delay memory of the GAS_FX_DELAY / GAS_FX_REVERB instances ("lines") ---------------------------------------
  * Every GAS_FX_DELAY of a chain holds one delay line, every GAS_FX_REVERB one reverb line, from two device pools the
@@ -341,6 +361,18 @@ int gas_fx_line_settings_publish(gas_ctx *ctx, const uint32_t *slots, const gas_
  * back with the slot at the next block boundary after gas_source_free; they are zeroed whenever they change hands and
  * by gas_source_reset.  A gas_multi caller reserves per shard (gas_multi_shard). */
 int gas_ctx_reserve_fx_lines(gas_ctx *ctx, uint32_t delay_lines, uint32_t reverb_lines);
+
+/* ---- state of the GAS_FX_EQ6 / _EQ10 / _EQ21 instances ("banks") -----------------------------------------------
+ * Every equaliser of a chain holds one bank (2 ears x 21 bands x 4 floats, 672 bytes) from a device pool the caller
+ * sizes here, with the same contract as gas_ctx_reserve_fx_lines: main thread, never concurrently with
+ * gas_process_block; the pool, the slot -> bank table, the device settings table and a pinned upload buffer are
+ * allocated here and nothing on the audio thread; 0 releases everything; while any bank is held the call is
+ * GAS_ERR_INVALID_ARGUMENT.  gas_source_alloc takes one bank per equaliser of the chain: with no pool reserved it is
+ * GAS_ERR_UNSUPPORTED_CHAIN, with too few free banks (or lines, for a chain that also holds a delay or reverb)
+ * GAS_ERR_OUT_OF_SLOTS, and nothing is taken.  Banks go back with the slot at the next block boundary after
+ * gas_source_free; they are zeroed whenever they change hands and by gas_source_reset.  The two reservations are
+ * independent: neither call touches the other's pool.  A gas_multi caller reserves per shard (gas_multi_shard). */
+int gas_ctx_reserve_fx_eq(gas_ctx *ctx, uint32_t eq_banks);
 
 /* ---- NEW AudioSpatializerHRTF resource: hrir is [dirs][2 ears][taps] f32, taps <= 256 */
 int gas_hrtf_load(gas_ctx *ctx, const float *hrir, uint32_t dirs, uint32_t taps);

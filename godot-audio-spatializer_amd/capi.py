@@ -133,6 +133,51 @@ def fx_eq_settings_defaults(n):
     return np.zeros(n, FX_EQ_SETTINGS_DTYPE)
 
 
+# the engine's chorus and phaser (one chorus "line" / phaser "bank" per instance, gas_ctx_reserve_fx_mod); settings:
+# gas_fx_mod_settings by chain position (then voice for the chorus's per-voice arrays)
+FX_CHORUS, FX_PHASER = 19, 20
+CHORUS_MAX_VOICES = 4
+_PV = (MAX_EFFECTS, CHORUS_MAX_VOICES)
+FX_MOD_SETTINGS_DTYPE = np.dtype(
+    [
+        ("chorus_voice_count", np.int32, (MAX_EFFECTS,)),
+        ("chorus_dry", np.float32, (MAX_EFFECTS,)),
+        ("chorus_wet", np.float32, (MAX_EFFECTS,)),
+        ("chorus_delay_ms", np.float32, _PV),
+        ("chorus_rate_hz", np.float32, _PV),
+        ("chorus_depth_ms", np.float32, _PV),
+        ("chorus_level_db", np.float32, _PV),
+        ("chorus_cutoff_hz", np.float32, _PV),
+        ("chorus_pan", np.float32, _PV),
+        ("phaser_range_min_hz", np.float32, (MAX_EFFECTS,)),
+        ("phaser_range_max_hz", np.float32, (MAX_EFFECTS,)),
+        ("phaser_rate_hz", np.float32, (MAX_EFFECTS,)),
+        ("phaser_feedback", np.float32, (MAX_EFFECTS,)),
+        ("phaser_depth", np.float32, (MAX_EFFECTS,)),
+    ]
+)
+assert FX_MOD_SETTINGS_DTYPE.itemsize == 512
+
+
+def fx_mod_settings_defaults(n):
+    """The engine's AudioEffectChorus / AudioEffectPhaser defaults at every position, n rows (what a slot starts with)."""
+    d = np.zeros(n, FX_MOD_SETTINGS_DTYPE)
+    d["chorus_voice_count"] = 2
+    d["chorus_dry"] = 1.0
+    d["chorus_wet"] = 0.5
+    d["chorus_delay_ms"] = (15.0, 20.0, 12.0, 12.0)
+    d["chorus_rate_hz"] = (0.8, 1.2, 1.0, 1.0)
+    d["chorus_depth_ms"] = (2.0, 3.0, 0.0, 0.0)
+    d["chorus_cutoff_hz"] = (8000.0, 8000.0, 16000.0, 16000.0)
+    d["chorus_pan"] = (-0.5, 0.5, 0.0, 0.0)
+    d["phaser_range_min_hz"] = 440.0
+    d["phaser_range_max_hz"] = 1600.0
+    d["phaser_rate_hz"] = 0.5
+    d["phaser_feedback"] = 0.7
+    d["phaser_depth"] = 1.0
+    return d
+
+
 MEM_HOST = 0
 MEM_DEVICE = 1
 FLAG_PEAKS_DRAINING_ONLY = 1
@@ -278,6 +323,8 @@ EXPORTS = [
     "gas_ctx_reserve_fx_lines",
     "gas_fx_eq_settings_publish",
     "gas_ctx_reserve_fx_eq",
+    "gas_fx_mod_settings_publish",
+    "gas_ctx_reserve_fx_mod",
     "gas_params_publish_batch",
     "gas_hrtf_load",
     "gas_hrtf_load_positions",
@@ -364,6 +411,8 @@ def load_library():
     L.gas_ctx_reserve_fx_lines.argtypes = [vp, u32, u32]
     L.gas_fx_eq_settings_publish.argtypes = [vp, vp, vp, u32]
     L.gas_ctx_reserve_fx_eq.argtypes = [vp, u32]
+    L.gas_fx_mod_settings_publish.argtypes = [vp, vp, vp, u32]
+    L.gas_ctx_reserve_fx_mod.argtypes = [vp, u32, u32]
     L.gas_params_publish_batch.argtypes = [vp, vp, vp, u32, i32]
     L.gas_hrtf_load.argtypes = [vp, vp, u32, u32]
     L.gas_hrtf_load_positions.argtypes = [vp, vp, vp, u32, u32, u32, u32, i32, vp]
@@ -510,6 +559,20 @@ class SpatializerContext:
     def reserve_fx_eq(self, eq_banks):
         """Size the GAS_FX_EQ6 / _EQ10 / _EQ21 bank pool (main thread, not during a callback); 0 releases it."""
         self._check(self.lib.gas_ctx_reserve_fx_eq(self.h, int(eq_banks)), "gas_ctx_reserve_fx_eq")
+
+    @staticmethod
+    def fx_mod_settings_defaults(n):
+        return fx_mod_settings_defaults(n)
+
+    def fx_mod_settings_publish(self, slots, settings):
+        s = np.ascontiguousarray(slots, dtype=np.uint32)
+        f = np.ascontiguousarray(settings, dtype=FX_MOD_SETTINGS_DTYPE)
+        assert s.shape == f.shape
+        self._check(self.lib.gas_fx_mod_settings_publish(self.h, _np_ptr(s), _np_ptr(f), len(s)), "gas_fx_mod_settings_publish")
+
+    def reserve_fx_mod(self, chorus_lines, phaser_banks):
+        """Size the GAS_FX_CHORUS line and GAS_FX_PHASER bank pools (main thread, not during a callback); (0, 0) releases them."""
+        self._check(self.lib.gas_ctx_reserve_fx_mod(self.h, int(chorus_lines), int(phaser_banks)), "gas_ctx_reserve_fx_mod")
 
     def params_publish_batch(self, slots, params):
         s = np.ascontiguousarray(slots, dtype=np.uint32)
@@ -711,6 +774,7 @@ class BatchedSpatializerHost:
         L.gas_host_set_effect_settings_dyn.argtypes = [vp, u32, vp]
         L.gas_host_set_effect_settings_line.argtypes = [vp, u32, vp]
         L.gas_host_set_effect_settings_eq.argtypes = [vp, u32, vp]
+        L.gas_host_set_effect_settings_mod.argtypes = [vp, u32, vp]
         L.gas_host_set_release_fn.argtypes = [vp, vp, vp]
         L.gas_host_collect_released.argtypes = [vp]
         L.gas_host_set_process_effects_fn.argtypes = [vp, vp, vp]
@@ -804,6 +868,10 @@ class BatchedSpatializerHost:
     def set_effect_settings_eq(self, pid, settings):
         f = np.ascontiguousarray(settings, dtype=FX_EQ_SETTINGS_DTYPE).reshape(1)
         return self.lib.gas_host_set_effect_settings_eq(self.h, pid, _np_ptr(f))
+
+    def set_effect_settings_mod(self, pid, settings):
+        f = np.ascontiguousarray(settings, dtype=FX_MOD_SETTINGS_DTYPE).reshape(1)
+        return self.lib.gas_host_set_effect_settings_mod(self.h, pid, _np_ptr(f))
 
     def is_playback_active(self, pid):
         return bool(self.lib.gas_host_is_playback_active(self.h, pid))

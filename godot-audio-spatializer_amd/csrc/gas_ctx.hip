@@ -14,6 +14,7 @@
 
 #include "gas_fx_eq_check.h"
 #include "gas_fx_line_check.h"
+#include "gas_fx_mod_check.h"
 #include "gas_internal.h"
 
 namespace {
@@ -158,6 +159,19 @@ struct gas_ctx {
 	std::vector<uint8_t> eq_zero_pending; // [bank]: queued in eq_zero_list
 	unsigned char *h_eq_upload = nullptr, *d_eq_upload = nullptr;
 	gas_eq_coefs eq_coefs[3] = {}; // EQ6, EQ10, EQ21 at the mix rate (make_eq_coefs)
+	// GAS_FX_CHORUS lines and GAS_FX_PHASER banks (gas_ctx_reserve_fx_mod), kept like the delay and reverb lines: pool
+	// sizes and free entries (alloc_mu), each slot's entries by chain position (written under alloc_mu and params_mu),
+	// settings mirror and what the next flush uploads (params_mu): [m settings][m {slot, index[4]}][z {kind, index}]
+	// through one pinned staging buffer
+	uint32_t mod_cap[2] = { 0, 0 }; // chorus lines, phaser banks
+	std::vector<uint32_t> mod_free[2];
+	std::vector<std::array<int32_t, GAS_MAX_EFFECTS>> h_mod_of;
+	std::vector<gas_fx_mod_settings> h_mod;
+	std::vector<uint8_t> mod_dirty_flag;
+	std::vector<uint32_t> mod_dirty_list;
+	std::vector<uint32_t> mod_zero_list; // {kind, index} pairs, each entry at most once (mod_zero_pending)
+	std::vector<uint8_t> mod_zero_pending[2]; // [pool][index]: queued in mod_zero_list
+	unsigned char *h_mod_upload = nullptr, *d_mod_upload = nullptr;
 
 	// plain [HRTF] group of the cached list (k_hrtf_uni): which entries need their exact peak
 	uint32_t *h_peak_bits = nullptr, *d_peak_bits = nullptr; // two halves of (max_sources + 31) / 32 words: bit k = entry k of the plain-[HRTF] group / of the staged group
@@ -309,7 +323,7 @@ int group_of(int kind, const int32_t *fx, uint32_t n_fx) {
 	// reflection ring and one HRTF history per playback
 	int n_er = 0, n_hrtf = 0;
 	for (uint32_t j = 0; j < n_fx; j++) {
-		if ((fx[j] < GAS_FX_HIGHSHELF || fx[j] > GAS_FX_AMPLIFY) && (fx[j] < GAS_FX_DISTORTION || fx[j] > GAS_FX_REVERB) && (fx[j] < GAS_FX_EQ6 || fx[j] > GAS_FX_EQ21)) {
+		if ((fx[j] < GAS_FX_HIGHSHELF || fx[j] > GAS_FX_AMPLIFY) && (fx[j] < GAS_FX_DISTORTION || fx[j] > GAS_FX_REVERB) && (fx[j] < GAS_FX_EQ6 || fx[j] > GAS_FX_EQ21) && (fx[j] < GAS_FX_CHORUS || fx[j] > GAS_FX_PHASER)) {
 			return -1;
 		}
 		n_er += fx[j] == GAS_FX_EARLY_REFLECTIONS;
@@ -488,6 +502,10 @@ gas_eq_coefs make_eq_coefs(int kind, float mix_rate) {
 
 inline bool is_eq(int kind) {
 	return kind >= GAS_FX_EQ6 && kind <= GAS_FX_EQ21;
+}
+
+inline int mod_pool_of(int kind) { // 0 chorus line, 1 phaser bank, -1 neither
+	return kind == GAS_FX_CHORUS ? 0 : (kind == GAS_FX_PHASER ? 1 : -1);
 }
 
 uint32_t chain_signature(const int32_t *fx, uint32_t n_fx) {
@@ -943,6 +961,8 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 							e = gas_launch_fx_line(c->stream, kind, in, c->st, c->line_geo, F, (uint32_t)j, c->cfg.mix_rate, outb);
 						} else if (is_eq(kind)) { // k_fx_eq.hip, state in the slot's bank of chain position j
 							e = gas_launch_fx_eq(c->stream, kind, in, c->st, c->eq_coefs[kind - GAS_FX_EQ6], F, (uint32_t)j, outb);
+						} else if (mod_pool_of(kind) >= 0) { // k_fx_mod.hip, state in the slot's chorus line / phaser bank of chain position j
+							e = gas_launch_fx_mod(c->stream, kind, in, c->st, F, (uint32_t)j, c->cfg.mix_rate, outb);
 						} else {
 							e = gas_launch_hrtf_rows(c->stream, (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) != 0, in, c->st, c->tab, c->d_tw, F, outb);
 						}
@@ -1399,6 +1419,94 @@ void release_fx_eq(gas_ctx *c) {
 	c->eq_zero_pending.clear();
 }
 
+// gas_fx_mod_settings_publish's rows, new slot -> line / bank entries and entries to zero: one copy of
+// [m settings][m {slot, index[4]}][z {kind, index}], one scatter, one zeroing launch.
+int flush_fx_mod(gas_ctx *c) {
+	if (!c->h_mod_upload) {
+		return GAS_OK;
+	}
+	uint32_t m = 0, z = 0;
+	{
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		m = (uint32_t)c->mod_dirty_list.size();
+		z = (uint32_t)c->mod_zero_list.size() / 2;
+		if (m == 0 && z == 0) {
+			return GAS_OK;
+		}
+		gas_fx_mod_settings *hs = reinterpret_cast<gas_fx_mod_settings *>(c->h_mod_upload);
+		uint32_t *hsi = reinterpret_cast<uint32_t *>(c->h_mod_upload + (size_t)m * sizeof(gas_fx_mod_settings));
+		for (uint32_t i = 0; i < m; i++) {
+			const uint32_t s = c->mod_dirty_list[i];
+			hs[i] = c->h_mod[s];
+			hsi[i * (1 + GAS_MAX_EFFECTS)] = s;
+			for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
+				hsi[i * (1 + GAS_MAX_EFFECTS) + 1 + j] = (uint32_t)c->h_mod_of[s][j];
+			}
+			c->mod_dirty_flag[s] = 0;
+		}
+		std::memcpy(hsi + (size_t)m * (1 + GAS_MAX_EFFECTS), c->mod_zero_list.data(), (size_t)z * 2 * sizeof(uint32_t));
+		for (uint32_t i = 0; i < z; i++) {
+			c->mod_zero_pending[mod_pool_of((int)c->mod_zero_list[2 * i])][c->mod_zero_list[2 * i + 1]] = 0;
+		}
+		c->mod_dirty_list.clear();
+		c->mod_zero_list.clear();
+	}
+	const size_t zoff = (size_t)m * (sizeof(gas_fx_mod_settings) + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t));
+	GAS_HIP(c, hipMemcpyAsync(c->d_mod_upload, c->h_mod_upload, zoff + (size_t)z * 2 * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	GAS_HIP(c, gas_launch_scatter_mod(c->stream, c->st, reinterpret_cast<const gas_fx_mod_settings *>(c->d_mod_upload), reinterpret_cast<const uint32_t *>(c->d_mod_upload + (size_t)m * sizeof(gas_fx_mod_settings)), m));
+	GAS_HIP(c, gas_launch_zero_mod(c->stream, c->st, reinterpret_cast<const uint32_t *>(c->d_mod_upload + zoff), z));
+	GAS_HIP(c, hipStreamSynchronize(c->stream)); // the pinned staging buffer is reused by the next flush
+	return GAS_OK;
+}
+
+// Marks slot s's chorus / phaser settings row (and its table row) for the next flush; params_mu held.
+void mod_mark_dirty(gas_ctx *c, uint32_t s) {
+	if (!c->mod_dirty_flag[s]) {
+		c->mod_dirty_flag[s] = 1;
+		c->mod_dirty_list.push_back(s);
+	}
+}
+
+// Queues the zeroing of slot s's chorus lines and phaser banks (chain signature sig), each at most once until the next
+// flush, so the queue never holds more pairs than the pools have entries (the upload buffer's zero section);
+// params_mu held.
+void mod_queue_zero(gas_ctx *c, uint32_t s, uint32_t sig) {
+	for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
+		const int kind = (sig >> (8 * j)) & 0xff;
+		const int pool = mod_pool_of(kind);
+		const int32_t idx = c->h_mod_of[s][j];
+		if (pool >= 0 && idx >= 0 && !c->mod_zero_pending[pool][idx]) {
+			c->mod_zero_pending[pool][idx] = 1;
+			c->mod_zero_list.push_back((uint32_t)kind);
+			c->mod_zero_list.push_back((uint32_t)idx);
+		}
+	}
+}
+
+void release_fx_mod(gas_ctx *c) {
+	(void)hipFree(c->st.chorus_pool);
+	(void)hipFree(c->st.phaser_pool);
+	(void)hipFree(c->st.mod_of);
+	(void)hipFree(c->st.mod_settings);
+	(void)hipFree(c->d_mod_upload);
+	(void)hipHostFree(c->h_mod_upload);
+	c->st.chorus_pool = c->st.phaser_pool = nullptr;
+	c->st.mod_of = nullptr;
+	c->st.mod_settings = nullptr;
+	c->st.chorus_mask = 0;
+	c->d_mod_upload = c->h_mod_upload = nullptr;
+	for (int p = 0; p < 2; p++) {
+		c->mod_cap[p] = 0;
+		c->mod_free[p].clear();
+		c->mod_zero_pending[p].clear();
+	}
+	c->h_mod_of.clear();
+	c->h_mod.clear();
+	c->mod_dirty_flag.clear();
+	c->mod_dirty_list.clear();
+	c->mod_zero_list.clear();
+}
+
 int flush_params(gas_ctx *c) {
 	uint32_t m = 0;
 	{
@@ -1422,7 +1530,8 @@ int flush_params(gas_ctx *c) {
 	int rc = flush_fx_settings(c);
 	rc = rc != GAS_OK ? rc : flush_fx_dyn_settings(c);
 	rc = rc != GAS_OK ? rc : flush_fx_lines(c);
-	return rc != GAS_OK ? rc : flush_fx_eq(c);
+	rc = rc != GAS_OK ? rc : flush_fx_eq(c);
+	return rc != GAS_OK ? rc : flush_fx_mod(c);
 }
 
 void stream_rows_sync_back(gas_ctx *c);
@@ -1468,6 +1577,16 @@ int apply_pending_frees(gas_ctx *c) {
 				if (is_eq((si.chain_sig >> (8 * j)) & 0xff) && c->h_eq_of[s][j] >= 0) {
 					c->eq_free.push_back((uint32_t)c->h_eq_of[s][j]);
 					c->h_eq_of[s][j] = -1;
+				}
+			}
+		}
+		if (!c->h_mod_of.empty()) { // its chorus lines and phaser banks go back to the pools (zeroed when handed out again)
+			std::lock_guard<std::mutex> lk(c->params_mu);
+			for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
+				const int pool = mod_pool_of((si.chain_sig >> (8 * j)) & 0xff);
+				if (pool >= 0 && c->h_mod_of[s][j] >= 0) {
+					c->mod_free[pool].push_back((uint32_t)c->h_mod_of[s][j]);
+					c->h_mod_of[s][j] = -1;
 				}
 			}
 		}
@@ -1711,6 +1830,7 @@ void gas_ctx_destroy(gas_ctx *c) {
 	(void)hipHostFree(c->h_dyn_upload);
 	release_fx_lines(c);
 	release_fx_eq(c);
+	release_fx_mod(c);
 	(void)hipFree(c->d_slots);
 	(void)hipFree(c->d_rows);
 	(void)hipFree(c->d_slots_rows);
@@ -1995,12 +2115,17 @@ int gas_source_alloc(gas_ctx *c, int kind, const int32_t *effects, uint32_t n_ef
 	}
 	uint32_t need[2] = { 0, 0 }; // delay / reverb lines of the chain
 	uint32_t need_eq = 0; // EQ banks of the chain
+	uint32_t need_mod[2] = { 0, 0 }; // chorus lines / phaser banks of the chain
 	for (uint32_t j = 0; j < n_effects; j++) {
 		const int pool = line_pool_of(effects[j]);
 		if (pool >= 0) {
 			need[pool]++;
 		}
 		need_eq += is_eq(effects[j]);
+		const int mpool = mod_pool_of(effects[j]);
+		if (mpool >= 0) {
+			need_mod[mpool]++;
+		}
 	}
 	std::lock_guard<std::mutex> alloc_lk(c->alloc_mu); // any thread (instantiate_playback_data runs on the physics thread, audio_spatializer.cpp:69)
 	if (need[0] + need[1] > 0 && c->line_cap[0] == 0 && c->line_cap[1] == 0) {
@@ -2009,7 +2134,10 @@ int gas_source_alloc(gas_ctx *c, int kind, const int32_t *effects, uint32_t n_ef
 	if (need_eq > 0 && c->eq_cap == 0) {
 		return GAS_ERR_UNSUPPORTED_CHAIN; // no bank pool reserved (gas_ctx_reserve_fx_eq)
 	}
-	if (c->free_list.empty() || c->line_free[0].size() < need[0] || c->line_free[1].size() < need[1] || c->eq_free.size() < need_eq) { // all or nothing
+	if (need_mod[0] + need_mod[1] > 0 && c->mod_cap[0] == 0 && c->mod_cap[1] == 0) {
+		return GAS_ERR_UNSUPPORTED_CHAIN; // no chorus / phaser pool reserved (gas_ctx_reserve_fx_mod)
+	}
+	if (c->free_list.empty() || c->line_free[0].size() < need[0] || c->line_free[1].size() < need[1] || c->eq_free.size() < need_eq || c->mod_free[0].size() < need_mod[0] || c->mod_free[1].size() < need_mod[1]) { // all or nothing
 		return GAS_ERR_OUT_OF_SLOTS;
 	}
 	const uint32_t s = c->free_list.back();
@@ -2076,6 +2204,21 @@ int gas_source_alloc(gas_ctx *c, int kind, const int32_t *effects, uint32_t n_ef
 		eq_mark_dirty(c, s);
 		eq_queue_zero(c, s, sig);
 	}
+	if (need_mod[0] + need_mod[1] > 0) { // one line or bank per chorus / phaser, zeroed and entered in the table at the next flush
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		for (uint32_t j = 0; j < GAS_MAX_EFFECTS; j++) {
+			const int pool = j < n_effects ? mod_pool_of(effects[j]) : -1;
+			if (pool >= 0) {
+				c->h_mod_of[s][j] = (int32_t)c->mod_free[pool].back();
+				c->mod_free[pool].pop_back();
+			} else {
+				c->h_mod_of[s][j] = -1;
+			}
+		}
+		c->h_mod[s] = gas_fx_mod_settings_defaults();
+		mod_mark_dirty(c, s);
+		mod_queue_zero(c, s, sig);
+	}
 	return GAS_OK;
 }
 
@@ -2132,6 +2275,10 @@ int gas_source_reset(gas_ctx *c, uint32_t slot) {
 		if (!c->h_eq_of.empty() && c->slots[slot].used) { // and its EQ banks
 			std::lock_guard<std::mutex> lk(c->params_mu);
 			eq_queue_zero(c, slot, c->slots[slot].chain_sig);
+		}
+		if (!c->h_mod_of.empty() && c->slots[slot].used) { // and its chorus lines and phaser banks
+			std::lock_guard<std::mutex> lk(c->params_mu);
+			mod_queue_zero(c, slot, c->slots[slot].chain_sig);
 		}
 	}
 	return GAS_OK;
@@ -2380,6 +2527,115 @@ int gas_ctx_reserve_fx_eq(gas_ctx *c, uint32_t eq_banks) {
 	c->h_eq_of.assign(N, none);
 	c->h_eq = std::move(defaults);
 	c->eq_dirty_flag.assign(N, 0);
+	return GAS_OK;
+}
+
+int gas_fx_mod_settings_publish(gas_ctx *c, const uint32_t *slots, const gas_fx_mod_settings *settings, uint32_t n) {
+	if (!c || (n > 0 && (!slots || !settings))) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	for (uint32_t i = 0; i < n; i++) {
+		if (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used) {
+			return GAS_ERR_BAD_SLOT;
+		}
+		if (!gas_fx_mod_settings_valid(settings[i])) {
+			return GAS_ERR_INVALID_ARGUMENT;
+		}
+	}
+	std::lock_guard<std::mutex> lk(c->params_mu);
+	if (c->h_mod.empty()) { // no pool reserved: no slot has a chorus or phaser the settings could reach
+		return GAS_OK;
+	}
+	for (uint32_t i = 0; i < n; i++) {
+		c->h_mod[slots[i]] = settings[i];
+		mod_mark_dirty(c, slots[i]);
+	}
+	return GAS_OK;
+}
+
+// [ENGINE] AudioEffectChorus's ring: 1 << bitlength((int)(0.24 sr)) frames
+uint32_t chorus_ring_frames(double sr) {
+	const uint32_t n = (uint32_t)(int)(0.24 * sr);
+	uint32_t bits = 0;
+	while (bits < 31 && (n >> bits) != 0) {
+		bits++;
+	}
+	return 1u << bits;
+}
+
+int gas_ctx_reserve_fx_mod(gas_ctx *c, uint32_t chorus_lines, uint32_t phaser_banks) {
+	if (!c) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	const double sr = (double)c->cfg.mix_rate;
+	const uint32_t R = chorus_ring_frames(sr);
+	if (chorus_lines > 0 && (long)R < lrint(0.05 * sr) + 2L * (int)(0.02 * sr) + 12 + (long)c->cfg.frames) {
+		return GAS_ERR_INVALID_ARGUMENT; // one block's ring writes could overtake its own oldest read
+	}
+	std::lock_guard<std::mutex> alloc_lk(c->alloc_mu);
+	for (int p = 0; p < 2; p++) {
+		if (c->mod_free[p].size() != c->mod_cap[p]) {
+			return GAS_ERR_INVALID_ARGUMENT; // lines or banks are held
+		}
+	}
+	GAS_HIP(c, hipSetDevice(c->cfg.device));
+	GAS_HIP(c, hipStreamSynchronize(c->stream));
+	{
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		release_fx_mod(c);
+	}
+	if (chorus_lines == 0 && phaser_banks == 0) {
+		return GAS_OK;
+	}
+	const size_t N = c->cfg.max_sources;
+	const size_t line_floats = GAS_CHORUS_HEADER + 2 * (size_t)R;
+	// [<= N settings rows][<= N {slot, index[4]}][<= every line and bank once {kind, index}] (mod_mark_dirty / mod_queue_zero)
+	const size_t upload = N * (sizeof(gas_fx_mod_settings) + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t)) + ((size_t)chorus_lines + phaser_banks) * 2 * sizeof(uint32_t);
+	std::vector<gas_fx_mod_settings> defaults(N, gas_fx_mod_settings_defaults());
+	hipError_t e = hipSuccess;
+	auto step = [&e](hipError_t r) {
+		if (e == hipSuccess) {
+			e = r;
+		}
+	};
+	if (chorus_lines) {
+		step(hipMalloc(&c->st.chorus_pool, line_floats * sizeof(float) * chorus_lines));
+		step(e == hipSuccess ? hipMemsetAsync(c->st.chorus_pool, 0, line_floats * sizeof(float) * chorus_lines, c->stream) : e);
+	}
+	if (phaser_banks) {
+		step(hipMalloc(&c->st.phaser_pool, sizeof(float) * GAS_PHASER_BANK_FLOATS * phaser_banks));
+		step(e == hipSuccess ? hipMemsetAsync(c->st.phaser_pool, 0, sizeof(float) * GAS_PHASER_BANK_FLOATS * phaser_banks, c->stream) : e);
+	}
+	step(hipMalloc(&c->st.mod_of, sizeof(int32_t) * GAS_MAX_EFFECTS * N));
+	step(e == hipSuccess ? hipMemsetAsync(c->st.mod_of, 0xff, sizeof(int32_t) * GAS_MAX_EFFECTS * N, c->stream) : e);
+	step(hipMalloc(&c->st.mod_settings, sizeof(gas_fx_mod_settings) * N));
+	step(e == hipSuccess ? hipMemcpy(c->st.mod_settings, defaults.data(), sizeof(gas_fx_mod_settings) * N, hipMemcpyHostToDevice) : e);
+	step(hipMalloc(&c->d_mod_upload, upload));
+	step(hipHostMalloc(&c->h_mod_upload, upload, hipHostMallocDefault));
+	step(e == hipSuccess ? hipStreamSynchronize(c->stream) : e);
+	if (e != hipSuccess) {
+		c->last_err = std::string("gas_ctx_reserve_fx_mod: ") + hipGetErrorString(e);
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		release_fx_mod(c);
+		return e == hipErrorOutOfMemory ? GAS_ERR_OUT_OF_MEMORY : GAS_ERR_DEVICE;
+	}
+	std::lock_guard<std::mutex> lk(c->params_mu);
+	c->st.chorus_mask = R - 1;
+	c->mod_cap[0] = chorus_lines;
+	c->mod_cap[1] = phaser_banks;
+	for (int p = 0; p < 2; p++) { // handed out from entry 0 up
+		const uint32_t n = p == 0 ? chorus_lines : phaser_banks;
+		c->mod_zero_pending[p].assign(n, 0);
+		c->mod_free[p].resize(n);
+		for (uint32_t i = 0; i < n; i++) {
+			c->mod_free[p][i] = n - 1 - i;
+		}
+	}
+	std::array<int32_t, GAS_MAX_EFFECTS> none;
+	none.fill(-1);
+	c->h_mod_of.assign(N, none);
+	c->h_mod = std::move(defaults);
+	c->mod_dirty_flag.assign(N, 0);
 	return GAS_OK;
 }
 

@@ -15,6 +15,7 @@ static_assert(sizeof(gas_audio_frame) == 8, "AudioFrame is 2 x f32");
 static_assert(sizeof(gas_fx_dyn_settings) == 12 * 4 * GAS_MAX_EFFECTS, "gas_fx_dyn_settings is 12 arrays by chain position");
 static_assert(sizeof(gas_fx_line_settings) == 21 * 4 * GAS_MAX_EFFECTS, "gas_fx_line_settings is 21 arrays by chain position");
 static_assert(sizeof(gas_fx_eq_settings) == 336, "gas_fx_eq_settings is [GAS_MAX_EFFECTS][21] f32");
+static_assert(sizeof(gas_fx_mod_settings) == 512, "gas_fx_mod_settings is 5 arrays by chain position, 6 by position and voice, 5 by position");
 
 // GAS_FX_EQ6 / _EQ10 / _EQ21 (k_fx_eq.hip): one bank of state per instance, [21 bands][a2, a3, b2, b3]
 // [2 ears] floats (the engine's BandProcess history per band and ear), and the per-band coefficients of one preset at
@@ -23,6 +24,13 @@ static_assert(sizeof(gas_fx_eq_settings) == 336, "gas_fx_eq_settings is [GAS_MAX
 struct gas_eq_coefs {
 	float c1[GAS_EQ_MAX_BANDS], c2[GAS_EQ_MAX_BANDS], c3[GAS_EQ_MAX_BANDS];
 };
+
+// GAS_FX_CHORUS / GAS_FX_PHASER (k_fx_mod.hip).  A chorus line is GAS_CHORUS_HEADER floats of state
+// {pos u32, -, cycles[4] u64, -, h[4 voices][2 ears] at GAS_CHORUS_H}, then a ring of chorus_mask + 1 stereo frames; a
+// phaser bank is GAS_PHASER_BANK_FLOATS floats {phase, -, h[2 ears], zm1[6 stages][2 ears]}.
+#define GAS_CHORUS_HEADER 64
+#define GAS_CHORUS_H 16
+#define GAS_PHASER_BANK_FLOATS 16
 
 // GAS_FX_DELAY / GAS_FX_REVERB line geometry, fixed per context by the mix rate (gas_ctx_reserve_fx_lines).
 // Every line starts with GAS_LINE_HEADER floats of state; offsets below are in floats from the line's start.
@@ -77,6 +85,13 @@ struct gas_dev_state {
 	gas_fx_eq_settings *eq_settings; // [max_sources], by chain position
 	int32_t *eq_of; // [GAS_MAX_EFFECTS][max_sources] bank of chain position j
 	float *eq_pool; // [banks][GAS_EQ_BANK_FLOATS]
+	// GAS_FX_CHORUS / GAS_FX_PHASER (k_fx_mod.hip): settings, slot -> line / bank table, the two pools (nullptr until
+	// gas_ctx_reserve_fx_mod)
+	gas_fx_mod_settings *mod_settings; // [max_sources], by chain position
+	int32_t *mod_of; // [GAS_MAX_EFFECTS][max_sources] chorus line or phaser bank of chain position j
+	float *chorus_pool; // [chorus lines][GAS_CHORUS_HEADER + 2 (chorus_mask + 1)]
+	float *phaser_pool; // [phaser banks][GAS_PHASER_BANK_FLOATS]
+	uint32_t chorus_mask; // ring frames - 1
 };
 
 // Device-resident playback cursor: what SpatialPlaybackListNode + the engine's sampler hold.
@@ -233,6 +248,12 @@ hipError_t gas_launch_fx_eq(hipStream_t stream, int kind, const gas_group_args &
 hipError_t gas_launch_scatter_eq(hipStream_t stream, const gas_dev_state &st, const gas_fx_eq_settings *upload, const uint32_t *slot_banks, uint32_t n);
 hipError_t gas_launch_zero_banks(hipStream_t stream, const gas_dev_state &st, const uint32_t *banks, uint32_t n);
 int gas_eq_bands(int kind); // 6, 10, 21; 0 for any other kind
+// k_fx_mod.hip: a GAS_FX_CHORUS / GAS_FX_PHASER stage (rows in -> dense rows out); the scatter of published settings
+// records ([m] gas_fx_mod_settings, then [m] {slot, line or bank[GAS_MAX_EFFECTS]}) and the zeroing of ([z] {kind, index})
+// chorus lines and phaser banks
+hipError_t gas_launch_fx_mod(hipStream_t stream, int kind, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t chain_pos, float mix_rate, gas_audio_frame *rows_out);
+hipError_t gas_launch_scatter_mod(hipStream_t stream, const gas_dev_state &st, const gas_fx_mod_settings *upload, const uint32_t *slot_idx, uint32_t n);
+hipError_t gas_launch_zero_mod(hipStream_t stream, const gas_dev_state &st, const uint32_t *kind_idx, uint32_t n);
 hipError_t gas_launch_zero_lines(hipStream_t stream, const gas_dev_state &st, const gas_line_geo &geo, const uint32_t *kind_line, uint32_t n);
 hipError_t gas_launch_scatter_dyn(hipStream_t stream, gas_fx_dyn_settings *table, const gas_fx_dyn_settings *upload, const uint32_t *slots, uint32_t n);
 hipError_t gas_launch_scatter_params(hipStream_t stream, gas_params *table, const gas_params *upload, const uint32_t *slots, uint32_t n);

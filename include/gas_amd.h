@@ -99,6 +99,10 @@ typedef enum gas_effect_kind {
 	GAS_FX_EQ6 = 16, /* [ENGINE] AudioEffectEQ6: bands at 32, 100, 320, 1000, 3200, 10000 Hz */
 	GAS_FX_EQ10 = 17, /* [ENGINE] AudioEffectEQ10: bands at 31.25 Hz and every octave up to 16 kHz */
 	GAS_FX_EQ21 = 18, /* [ENGINE] AudioEffectEQ21: bands at 22 Hz to 22 kHz, half an octave apart */
+	/* The engine's modulation kinds (state in "lines" and "banks", reserved with gas_ctx_reserve_fx_mod); settings per
+	 * playback and chain position: gas_fx_mod_settings. */
+	GAS_FX_CHORUS = 19, /* [ENGINE] AudioEffectChorus: up to 4 LFO-modulated taps of a stereo ring, each low-passed and panned */
+	GAS_FX_PHASER = 20, /* [ENGINE] AudioEffectPhaser: six first-order allpasses per ear with feedback, swept by one LFO */
 } gas_effect_kind;
 
 /* [ENGINE] AudioEffectDistortion::Mode */
@@ -276,6 +280,29 @@ typedef struct gas_fx_eq_settings {
 	float band_gain_db[GAS_MAX_EFFECTS][GAS_EQ_MAX_BANDS];
 } gas_fx_eq_settings;
 
+/* Settings of the GAS_FX_CHORUS / GAS_FX_PHASER effects of one playback, by chain position (then voice for the
+ * chorus's [GAS_MAX_EFFECTS][GAS_CHORUS_MAX_VOICES] arrays): position j is read only when effect j of the playback's
+ * chain is one of those kinds.  Read once per block (no ramp).  A slot's settings start at the defaults below when it is
+ * allocated.  Ranges (the engine's property ranges; gas_fx_mod_settings_publish refuses anything outside them or not
+ * finite, at any position and voice, used or not) and defaults by voice 0, 1, 2, 3: */
+#define GAS_CHORUS_MAX_VOICES 4
+typedef struct gas_fx_mod_settings {
+	int32_t chorus_voice_count[GAS_MAX_EFFECTS]; /* 1 .. 4, default 2 */
+	float chorus_dry[GAS_MAX_EFFECTS]; /* 0 .. 1, default 1 */
+	float chorus_wet[GAS_MAX_EFFECTS]; /* 0 .. 1, default 0.5 */
+	float chorus_delay_ms[GAS_MAX_EFFECTS][GAS_CHORUS_MAX_VOICES]; /* 0 .. 50, default 15, 20, 12, 12 */
+	float chorus_rate_hz[GAS_MAX_EFFECTS][GAS_CHORUS_MAX_VOICES]; /* 0.1 .. 20, default 0.8, 1.2, 1, 1 */
+	float chorus_depth_ms[GAS_MAX_EFFECTS][GAS_CHORUS_MAX_VOICES]; /* 0 .. 20, default 2, 3, 0, 0 */
+	float chorus_level_db[GAS_MAX_EFFECTS][GAS_CHORUS_MAX_VOICES]; /* -60 .. 24, default 0 */
+	float chorus_cutoff_hz[GAS_MAX_EFFECTS][GAS_CHORUS_MAX_VOICES]; /* 1 .. 20500, default 8000, 8000, 16000, 16000; >= 16000: no low-pass */
+	float chorus_pan[GAS_MAX_EFFECTS][GAS_CHORUS_MAX_VOICES]; /* -1 .. 1, default -0.5, 0.5, 0, 0 */
+	float phaser_range_min_hz[GAS_MAX_EFFECTS]; /* 10 .. 10000, default 440 (min > max is legal) */
+	float phaser_range_max_hz[GAS_MAX_EFFECTS]; /* 10 .. 10000, default 1600 */
+	float phaser_rate_hz[GAS_MAX_EFFECTS]; /* 0.01 .. 20, default 0.5 */
+	float phaser_feedback[GAS_MAX_EFFECTS]; /* 0.1 .. 0.9, default 0.7 */
+	float phaser_depth[GAS_MAX_EFFECTS]; /* 0.1 .. 4, default 1 */
+} gas_fx_mod_settings;
+
 /* Per-kernel device timing collected with HIP events on the context stream. */
 typedef struct gas_profile {
 	uint64_t launches; /* timed launches of the dominant kernel since the last reset */
@@ -342,6 +369,10 @@ int gas_fx_line_settings_publish(gas_ctx *ctx, const uint32_t *slots, const gas_
  * A gain outside -60 .. 24 dB or not finite (at any position and band) is GAS_ERR_INVALID_ARGUMENT, and nothing of the
  * call is taken. */
 int gas_fx_eq_settings_publish(gas_ctx *ctx, const uint32_t *slots, const gas_fx_eq_settings *settings, uint32_t n);
+/* The same for gas_fx_mod_settings: latest wins, snapshotted at the start of the next gas_process_block, physics
+ * thread.  A value outside the ranges given at gas_fx_mod_settings or not finite (at any position and voice) is
+ * GAS_ERR_INVALID_ARGUMENT, and nothing of the call is taken. */
+int gas_fx_mod_settings_publish(gas_ctx *ctx, const uint32_t *slots, const gas_fx_mod_settings *settings, uint32_t n);
 
 /* ---- delay memory of the GAS_FX_DELAY / GAS_FX_REVERB instances ("lines") ---------------------------------------
  * Every GAS_FX_DELAY of a chain holds one delay line, every GAS_FX_REVERB one reverb line, from two device pools the
@@ -373,6 +404,23 @@ int gas_ctx_reserve_fx_lines(gas_ctx *ctx, uint32_t delay_lines, uint32_t reverb
  * gas_source_free; they are zeroed whenever they change hands and by gas_source_reset.  The two reservations are
  * independent: neither call touches the other's pool.  A gas_multi caller reserves per shard (gas_multi_shard). */
 int gas_ctx_reserve_fx_eq(gas_ctx *ctx, uint32_t eq_banks);
+
+/* ---- state of the GAS_FX_CHORUS / GAS_FX_PHASER instances (chorus "lines", phaser "banks") ------------------------
+ * Every chorus of a chain holds one chorus line, every phaser one phaser bank, from two device pools the caller sizes
+ * here, with the same contract as gas_ctx_reserve_fx_lines: main thread, never concurrently with gas_process_block; the
+ * pools, the slot -> line / bank table, the device settings table and a pinned upload buffer are allocated here and
+ * nothing on the audio thread; (0, 0) releases everything; while any line or bank is held the call is
+ * GAS_ERR_INVALID_ARGUMENT.  Bytes per instance, with sr the mix rate:
+ *   chorus: 256 + 8 R, R = 1 << bitlength((int)(0.24 sr)) ring frames (16384 at 44.1 and 48 kHz, 32768 at 96 kHz);
+ *   phaser: 64.
+ * chorus_lines > 0 needs R >= lrint(0.05 sr) + 2 (int)(0.02 sr) + 12 + frames (the longest read plus one block), else
+ * GAS_ERR_INVALID_ARGUMENT.  gas_source_alloc takes one line or bank per such effect of the chain: with neither pool
+ * reserved it is GAS_ERR_UNSUPPORTED_CHAIN, with too few free lines or banks in any pool (these, the delay and reverb
+ * lines, the EQ banks) GAS_ERR_OUT_OF_SLOTS, and nothing is taken.  Lines and banks go back with the slot at the next
+ * block boundary after gas_source_free; they are zeroed whenever they change hands and by gas_source_reset.  The
+ * reservation is independent of gas_ctx_reserve_fx_lines and gas_ctx_reserve_fx_eq: no call touches another's pools.
+ * A gas_multi caller reserves per shard (gas_multi_shard). */
+int gas_ctx_reserve_fx_mod(gas_ctx *ctx, uint32_t chorus_lines, uint32_t phaser_banks);
 
 /* ---- NEW AudioSpatializerHRTF resource: hrir is [dirs][2 ears][taps] f32, taps <= 256 */
 int gas_hrtf_load(gas_ctx *ctx, const float *hrir, uint32_t dirs, uint32_t taps);

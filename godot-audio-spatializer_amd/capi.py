@@ -178,6 +178,34 @@ def fx_mod_settings_defaults(n):
     return d
 
 
+# the engine's panner, stereo enhance and limiter (no recurrence over frames; one mono "ring" per stereo enhance,
+# gas_ctx_reserve_fx_stereo; panner and limiter hold no state); settings: gas_fx_stereo_settings by chain position
+FX_PANNER, FX_STEREO_ENHANCE, FX_LIMITER = 21, 22, 23
+FX_STEREO_SETTINGS_DTYPE = np.dtype(
+    [
+        ("panner_pan", np.float32, (MAX_EFFECTS,)),
+        ("enhance_pan_pullout", np.float32, (MAX_EFFECTS,)),
+        ("enhance_time_pullout_ms", np.float32, (MAX_EFFECTS,)),
+        ("enhance_surround", np.float32, (MAX_EFFECTS,)),
+        ("limiter_ceiling_db", np.float32, (MAX_EFFECTS,)),
+        ("limiter_threshold_db", np.float32, (MAX_EFFECTS,)),
+        ("limiter_soft_clip_db", np.float32, (MAX_EFFECTS,)),
+        ("limiter_soft_clip_ratio", np.float32, (MAX_EFFECTS,)),
+    ]
+)
+assert FX_STEREO_SETTINGS_DTYPE.itemsize == 128
+
+
+def fx_stereo_settings_defaults(n):
+    """The engine's AudioEffectPanner / StereoEnhance / Limiter defaults at every position, n rows (what a slot starts with)."""
+    d = np.zeros(n, FX_STEREO_SETTINGS_DTYPE)
+    d["enhance_pan_pullout"] = 1.0
+    d["limiter_ceiling_db"] = -0.1
+    d["limiter_soft_clip_db"] = 2.0
+    d["limiter_soft_clip_ratio"] = 10.0
+    return d
+
+
 MEM_HOST = 0
 MEM_DEVICE = 1
 FLAG_PEAKS_DRAINING_ONLY = 1
@@ -325,6 +353,8 @@ EXPORTS = [
     "gas_ctx_reserve_fx_eq",
     "gas_fx_mod_settings_publish",
     "gas_ctx_reserve_fx_mod",
+    "gas_fx_stereo_settings_publish",
+    "gas_ctx_reserve_fx_stereo",
     "gas_params_publish_batch",
     "gas_hrtf_load",
     "gas_hrtf_load_positions",
@@ -413,6 +443,8 @@ def load_library():
     L.gas_ctx_reserve_fx_eq.argtypes = [vp, u32]
     L.gas_fx_mod_settings_publish.argtypes = [vp, vp, vp, u32]
     L.gas_ctx_reserve_fx_mod.argtypes = [vp, u32, u32]
+    L.gas_fx_stereo_settings_publish.argtypes = [vp, vp, vp, u32]
+    L.gas_ctx_reserve_fx_stereo.argtypes = [vp, u32]
     L.gas_params_publish_batch.argtypes = [vp, vp, vp, u32, i32]
     L.gas_hrtf_load.argtypes = [vp, vp, u32, u32]
     L.gas_hrtf_load_positions.argtypes = [vp, vp, vp, u32, u32, u32, u32, i32, vp]
@@ -573,6 +605,20 @@ class SpatializerContext:
     def reserve_fx_mod(self, chorus_lines, phaser_banks):
         """Size the GAS_FX_CHORUS line and GAS_FX_PHASER bank pools (main thread, not during a callback); (0, 0) releases them."""
         self._check(self.lib.gas_ctx_reserve_fx_mod(self.h, int(chorus_lines), int(phaser_banks)), "gas_ctx_reserve_fx_mod")
+
+    @staticmethod
+    def fx_stereo_settings_defaults(n):
+        return fx_stereo_settings_defaults(n)
+
+    def fx_stereo_settings_publish(self, slots, settings):
+        s = np.ascontiguousarray(slots, dtype=np.uint32)
+        f = np.ascontiguousarray(settings, dtype=FX_STEREO_SETTINGS_DTYPE)
+        assert s.shape == f.shape
+        self._check(self.lib.gas_fx_stereo_settings_publish(self.h, _np_ptr(s), _np_ptr(f), len(s)), "gas_fx_stereo_settings_publish")
+
+    def reserve_fx_stereo(self, enhance_rings):
+        """Size the GAS_FX_STEREO_ENHANCE ring pool (main thread, not during a callback); 0 releases it."""
+        self._check(self.lib.gas_ctx_reserve_fx_stereo(self.h, int(enhance_rings)), "gas_ctx_reserve_fx_stereo")
 
     def params_publish_batch(self, slots, params):
         s = np.ascontiguousarray(slots, dtype=np.uint32)
@@ -775,6 +821,7 @@ class BatchedSpatializerHost:
         L.gas_host_set_effect_settings_line.argtypes = [vp, u32, vp]
         L.gas_host_set_effect_settings_eq.argtypes = [vp, u32, vp]
         L.gas_host_set_effect_settings_mod.argtypes = [vp, u32, vp]
+        L.gas_host_set_effect_settings_stereo.argtypes = [vp, u32, vp]
         L.gas_host_set_release_fn.argtypes = [vp, vp, vp]
         L.gas_host_collect_released.argtypes = [vp]
         L.gas_host_set_process_effects_fn.argtypes = [vp, vp, vp]
@@ -872,6 +919,10 @@ class BatchedSpatializerHost:
     def set_effect_settings_mod(self, pid, settings):
         f = np.ascontiguousarray(settings, dtype=FX_MOD_SETTINGS_DTYPE).reshape(1)
         return self.lib.gas_host_set_effect_settings_mod(self.h, pid, _np_ptr(f))
+
+    def set_effect_settings_stereo(self, pid, settings):
+        f = np.ascontiguousarray(settings, dtype=FX_STEREO_SETTINGS_DTYPE).reshape(1)
+        return self.lib.gas_host_set_effect_settings_stereo(self.h, pid, _np_ptr(f))
 
     def is_playback_active(self, pid):
         return bool(self.lib.gas_host_is_playback_active(self.h, pid))

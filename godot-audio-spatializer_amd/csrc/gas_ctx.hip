@@ -15,6 +15,7 @@
 #include "gas_fx_eq_check.h"
 #include "gas_fx_line_check.h"
 #include "gas_fx_mod_check.h"
+#include "gas_fx_stereo_check.h"
 #include "gas_internal.h"
 
 namespace {
@@ -172,6 +173,19 @@ struct gas_ctx {
 	std::vector<uint32_t> mod_zero_list; // {kind, index} pairs, each entry at most once (mod_zero_pending)
 	std::vector<uint8_t> mod_zero_pending[2]; // [pool][index]: queued in mod_zero_list
 	unsigned char *h_mod_upload = nullptr, *d_mod_upload = nullptr;
+	// GAS_FX_PANNER / _STEREO_ENHANCE / _LIMITER settings and the stereo-enhance rings (gas_ctx_reserve_fx_stereo), kept
+	// like the chorus lines; the settings mirror, the slot -> ring table and the staging buffer exist from gas_ctx_create
+	// on (panner and limiter need no reservation), the pool and the staging buffer's [z ring] section from the
+	// reservation: [m settings][m {slot, ring[4]}][z ring]
+	uint32_t ring_cap = 0;
+	std::vector<uint32_t> ring_free;
+	std::vector<std::array<int32_t, GAS_MAX_EFFECTS>> h_stereo_of;
+	std::vector<gas_fx_stereo_settings> h_stereo;
+	std::vector<uint8_t> stereo_dirty_flag;
+	std::vector<uint32_t> stereo_dirty_list;
+	std::vector<uint32_t> ring_zero_list; // each ring at most once (ring_zero_pending)
+	std::vector<uint8_t> ring_zero_pending; // [ring]: queued in ring_zero_list
+	unsigned char *h_stereo_upload = nullptr, *d_stereo_upload = nullptr;
 
 	// plain [HRTF] group of the cached list (k_hrtf_uni): which entries need their exact peak
 	uint32_t *h_peak_bits = nullptr, *d_peak_bits = nullptr; // two halves of (max_sources + 31) / 32 words: bit k = entry k of the plain-[HRTF] group / of the staged group
@@ -323,7 +337,7 @@ int group_of(int kind, const int32_t *fx, uint32_t n_fx) {
 	// reflection ring and one HRTF history per playback
 	int n_er = 0, n_hrtf = 0;
 	for (uint32_t j = 0; j < n_fx; j++) {
-		if ((fx[j] < GAS_FX_HIGHSHELF || fx[j] > GAS_FX_AMPLIFY) && (fx[j] < GAS_FX_DISTORTION || fx[j] > GAS_FX_REVERB) && (fx[j] < GAS_FX_EQ6 || fx[j] > GAS_FX_EQ21) && (fx[j] < GAS_FX_CHORUS || fx[j] > GAS_FX_PHASER)) {
+		if ((fx[j] < GAS_FX_HIGHSHELF || fx[j] > GAS_FX_AMPLIFY) && (fx[j] < GAS_FX_DISTORTION || fx[j] > GAS_FX_REVERB) && (fx[j] < GAS_FX_EQ6 || fx[j] > GAS_FX_EQ21) && (fx[j] < GAS_FX_CHORUS || fx[j] > GAS_FX_LIMITER)) {
 			return -1;
 		}
 		n_er += fx[j] == GAS_FX_EARLY_REFLECTIONS;
@@ -506,6 +520,10 @@ inline bool is_eq(int kind) {
 
 inline int mod_pool_of(int kind) { // 0 chorus line, 1 phaser bank, -1 neither
 	return kind == GAS_FX_CHORUS ? 0 : (kind == GAS_FX_PHASER ? 1 : -1);
+}
+
+inline bool is_stereo(int kind) { // k_fx_stereo.hip's kinds
+	return kind >= GAS_FX_PANNER && kind <= GAS_FX_LIMITER;
 }
 
 uint32_t chain_signature(const int32_t *fx, uint32_t n_fx) {
@@ -963,6 +981,8 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 							e = gas_launch_fx_eq(c->stream, kind, in, c->st, c->eq_coefs[kind - GAS_FX_EQ6], F, (uint32_t)j, outb);
 						} else if (mod_pool_of(kind) >= 0) { // k_fx_mod.hip, state in the slot's chorus line / phaser bank of chain position j
 							e = gas_launch_fx_mod(c->stream, kind, in, c->st, F, (uint32_t)j, c->cfg.mix_rate, outb);
+						} else if (is_stereo(kind)) { // k_fx_stereo.hip, settings by chain position; a stereo enhance's state in the slot's ring of chain position j
+							e = gas_launch_fx_stereo(c->stream, kind, in, c->st, F, (uint32_t)j, c->cfg.mix_rate, outb);
 						} else {
 							e = gas_launch_hrtf_rows(c->stream, (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) != 0, in, c->st, c->tab, c->d_tw, F, outb);
 						}
@@ -1507,6 +1527,88 @@ void release_fx_mod(gas_ctx *c) {
 	c->mod_zero_list.clear();
 }
 
+// gas_fx_stereo_settings_publish's rows, new slot -> ring entries and rings to zero: one copy of
+// [m settings][m {slot, ring[4]}][z ring], one scatter, one zeroing launch.
+int flush_fx_stereo(gas_ctx *c) {
+	uint32_t m = 0, z = 0;
+	{
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		m = (uint32_t)c->stereo_dirty_list.size();
+		z = (uint32_t)c->ring_zero_list.size();
+		if (m == 0 && z == 0) {
+			return GAS_OK;
+		}
+		if (!c->h_stereo_upload || !c->d_stereo_upload) { // a failed gas_ctx_reserve_fx_stereo could not restore it
+			return GAS_ERR_OUT_OF_MEMORY;
+		}
+		gas_fx_stereo_settings *hs = reinterpret_cast<gas_fx_stereo_settings *>(c->h_stereo_upload);
+		uint32_t *hsi = reinterpret_cast<uint32_t *>(c->h_stereo_upload + (size_t)m * sizeof(gas_fx_stereo_settings));
+		for (uint32_t i = 0; i < m; i++) {
+			const uint32_t s = c->stereo_dirty_list[i];
+			hs[i] = c->h_stereo[s];
+			hsi[i * (1 + GAS_MAX_EFFECTS)] = s;
+			for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
+				hsi[i * (1 + GAS_MAX_EFFECTS) + 1 + j] = (uint32_t)c->h_stereo_of[s][j];
+			}
+			c->stereo_dirty_flag[s] = 0;
+		}
+		std::memcpy(hsi + (size_t)m * (1 + GAS_MAX_EFFECTS), c->ring_zero_list.data(), (size_t)z * sizeof(uint32_t));
+		for (uint32_t i = 0; i < z; i++) {
+			c->ring_zero_pending[c->ring_zero_list[i]] = 0;
+		}
+		c->stereo_dirty_list.clear();
+		c->ring_zero_list.clear();
+	}
+	const size_t zoff = (size_t)m * (sizeof(gas_fx_stereo_settings) + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t));
+	GAS_HIP(c, hipMemcpyAsync(c->d_stereo_upload, c->h_stereo_upload, zoff + (size_t)z * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	GAS_HIP(c, gas_launch_scatter_stereo(c->stream, c->st, reinterpret_cast<const gas_fx_stereo_settings *>(c->d_stereo_upload), reinterpret_cast<const uint32_t *>(c->d_stereo_upload + (size_t)m * sizeof(gas_fx_stereo_settings)), m));
+	GAS_HIP(c, gas_launch_zero_rings(c->stream, c->st, reinterpret_cast<const uint32_t *>(c->d_stereo_upload + zoff), z));
+	GAS_HIP(c, hipStreamSynchronize(c->stream)); // the pinned staging buffer is reused by the next flush
+	return GAS_OK;
+}
+
+// Marks slot s's panner / stereo enhance / limiter settings row (and its table row) for the next flush; params_mu held.
+void stereo_mark_dirty(gas_ctx *c, uint32_t s) {
+	if (!c->stereo_dirty_flag[s]) {
+		c->stereo_dirty_flag[s] = 1;
+		c->stereo_dirty_list.push_back(s);
+	}
+}
+
+// Queues the zeroing of slot s's stereo-enhance rings (chain signature sig), each at most once until the next flush,
+// so the queue never holds more entries than the pool has rings (the upload buffer's zero section); params_mu held.
+void ring_queue_zero(gas_ctx *c, uint32_t s, uint32_t sig) {
+	for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
+		const int32_t idx = c->h_stereo_of[s][j];
+		if (((sig >> (8 * j)) & 0xff) == GAS_FX_STEREO_ENHANCE && idx >= 0 && !c->ring_zero_pending[idx]) {
+			c->ring_zero_pending[idx] = 1;
+			c->ring_zero_list.push_back((uint32_t)idx);
+		}
+	}
+}
+
+// The staging buffer of flush_fx_stereo with room for `rings` entries in its zero section; main thread, stream idle.
+hipError_t alloc_stereo_upload(gas_ctx *c, uint32_t rings) {
+	(void)hipFree(c->d_stereo_upload);
+	(void)hipHostFree(c->h_stereo_upload);
+	c->d_stereo_upload = c->h_stereo_upload = nullptr;
+	// [<= N settings rows][<= N {slot, ring[4]}][<= every ring once] (stereo_mark_dirty / ring_queue_zero)
+	const size_t upload = (size_t)c->cfg.max_sources * (sizeof(gas_fx_stereo_settings) + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t)) + (size_t)rings * sizeof(uint32_t);
+	hipError_t e = hipMalloc(&c->d_stereo_upload, upload);
+	return e != hipSuccess ? e : hipHostMalloc(&c->h_stereo_upload, upload, hipHostMallocDefault);
+}
+
+// The ring pool only: the settings, the table and the staging buffer stay (gas_ctx_destroy frees those).
+void release_fx_stereo_pool(gas_ctx *c) {
+	(void)hipFree(c->st.enhance_pool);
+	c->st.enhance_pool = nullptr;
+	c->st.enhance_mask = 0;
+	c->ring_cap = 0;
+	c->ring_free.clear();
+	c->ring_zero_pending.clear();
+	c->ring_zero_list.clear();
+}
+
 int flush_params(gas_ctx *c) {
 	uint32_t m = 0;
 	{
@@ -1531,7 +1633,8 @@ int flush_params(gas_ctx *c) {
 	rc = rc != GAS_OK ? rc : flush_fx_dyn_settings(c);
 	rc = rc != GAS_OK ? rc : flush_fx_lines(c);
 	rc = rc != GAS_OK ? rc : flush_fx_eq(c);
-	return rc != GAS_OK ? rc : flush_fx_mod(c);
+	rc = rc != GAS_OK ? rc : flush_fx_mod(c);
+	return rc != GAS_OK ? rc : flush_fx_stereo(c);
 }
 
 void stream_rows_sync_back(gas_ctx *c);
@@ -1587,6 +1690,15 @@ int apply_pending_frees(gas_ctx *c) {
 				if (pool >= 0 && c->h_mod_of[s][j] >= 0) {
 					c->mod_free[pool].push_back((uint32_t)c->h_mod_of[s][j]);
 					c->h_mod_of[s][j] = -1;
+				}
+			}
+		}
+		if (c->ring_cap > 0) { // its stereo-enhance rings go back to the pool (zeroed when handed out again)
+			std::lock_guard<std::mutex> lk(c->params_mu);
+			for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
+				if (((si.chain_sig >> (8 * j)) & 0xff) == GAS_FX_STEREO_ENHANCE && c->h_stereo_of[s][j] >= 0) {
+					c->ring_free.push_back((uint32_t)c->h_stereo_of[s][j]);
+					c->h_stereo_of[s][j] = -1;
 				}
 			}
 		}
@@ -1831,6 +1943,11 @@ void gas_ctx_destroy(gas_ctx *c) {
 	release_fx_lines(c);
 	release_fx_eq(c);
 	release_fx_mod(c);
+	release_fx_stereo_pool(c);
+	(void)hipFree(c->st.stereo_settings);
+	(void)hipFree(c->st.stereo_of);
+	(void)hipFree(c->d_stereo_upload);
+	(void)hipHostFree(c->h_stereo_upload);
 	(void)hipFree(c->d_slots);
 	(void)hipFree(c->d_rows);
 	(void)hipFree(c->d_slots_rows);
@@ -1938,6 +2055,10 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 		GAS_HIP(c, hipMemsetAsync(c->st.comp_rundb, 0, sizeof(float) * GAS_MAX_EFFECTS * N, c->stream));
 		GAS_HIP(c, hipMalloc(&c->d_dyn_upload, (sizeof(gas_fx_dyn_settings) + sizeof(uint32_t)) * N));
 		GAS_HIP(c, hipHostMalloc(&c->h_dyn_upload, (sizeof(gas_fx_dyn_settings) + sizeof(uint32_t)) * N, hipHostMallocDefault));
+		GAS_HIP(c, hipMalloc(&c->st.stereo_settings, sizeof(gas_fx_stereo_settings) * N));
+		GAS_HIP(c, hipMalloc(&c->st.stereo_of, sizeof(int32_t) * GAS_MAX_EFFECTS * N));
+		GAS_HIP(c, hipMemsetAsync(c->st.stereo_of, 0xff, sizeof(int32_t) * GAS_MAX_EFFECTS * N, c->stream));
+		GAS_HIP(c, alloc_stereo_upload(c, 0));
 		GAS_HIP(c, hipMalloc(&c->d_upload, sizeof(gas_params) * N));
 		GAS_HIP(c, hipMalloc(&c->d_upload_slots, sizeof(uint32_t) * N));
 		GAS_HIP(c, hipMalloc(&c->d_slots, sizeof(uint32_t) * N));
@@ -1997,10 +2118,20 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 	c->fx_dirty_flag.assign(N, 0);
 	c->h_dyn.assign(N, fx_dyn_settings_defaults());
 	c->dyn_dirty_flag.assign(N, 0);
+	c->h_stereo.assign(N, gas_fx_stereo_settings_defaults());
+	c->stereo_dirty_flag.assign(N, 0);
+	{
+		std::array<int32_t, GAS_MAX_EFFECTS> none;
+		none.fill(-1);
+		c->h_stereo_of.assign(N, none);
+	}
 	{ // every slot starts from the engine's resource defaults
 		hipError_t e = hipMemcpy(c->st.fxs, c->h_fxs.data(), sizeof(gas_fx_settings) * N, hipMemcpyHostToDevice);
 		if (e == hipSuccess) {
 			e = hipMemcpy(c->st.dyn, c->h_dyn.data(), sizeof(gas_fx_dyn_settings) * N, hipMemcpyHostToDevice);
+		}
+		if (e == hipSuccess) {
+			e = hipMemcpy(c->st.stereo_settings, c->h_stereo.data(), sizeof(gas_fx_stereo_settings) * N, hipMemcpyHostToDevice);
 		}
 		if (e != hipSuccess) {
 			gas_ctx_destroy(c);
@@ -2116,6 +2247,8 @@ int gas_source_alloc(gas_ctx *c, int kind, const int32_t *effects, uint32_t n_ef
 	uint32_t need[2] = { 0, 0 }; // delay / reverb lines of the chain
 	uint32_t need_eq = 0; // EQ banks of the chain
 	uint32_t need_mod[2] = { 0, 0 }; // chorus lines / phaser banks of the chain
+	uint32_t need_rings = 0; // stereo-enhance rings of the chain
+	bool any_stereo = false;
 	for (uint32_t j = 0; j < n_effects; j++) {
 		const int pool = line_pool_of(effects[j]);
 		if (pool >= 0) {
@@ -2126,6 +2259,8 @@ int gas_source_alloc(gas_ctx *c, int kind, const int32_t *effects, uint32_t n_ef
 		if (mpool >= 0) {
 			need_mod[mpool]++;
 		}
+		need_rings += effects[j] == GAS_FX_STEREO_ENHANCE;
+		any_stereo = any_stereo || is_stereo(effects[j]);
 	}
 	std::lock_guard<std::mutex> alloc_lk(c->alloc_mu); // any thread (instantiate_playback_data runs on the physics thread, audio_spatializer.cpp:69)
 	if (need[0] + need[1] > 0 && c->line_cap[0] == 0 && c->line_cap[1] == 0) {
@@ -2137,7 +2272,10 @@ int gas_source_alloc(gas_ctx *c, int kind, const int32_t *effects, uint32_t n_ef
 	if (need_mod[0] + need_mod[1] > 0 && c->mod_cap[0] == 0 && c->mod_cap[1] == 0) {
 		return GAS_ERR_UNSUPPORTED_CHAIN; // no chorus / phaser pool reserved (gas_ctx_reserve_fx_mod)
 	}
-	if (c->free_list.empty() || c->line_free[0].size() < need[0] || c->line_free[1].size() < need[1] || c->eq_free.size() < need_eq || c->mod_free[0].size() < need_mod[0] || c->mod_free[1].size() < need_mod[1]) { // all or nothing
+	if (need_rings > 0 && c->ring_cap == 0) {
+		return GAS_ERR_UNSUPPORTED_CHAIN; // no ring pool reserved (gas_ctx_reserve_fx_stereo)
+	}
+	if (c->free_list.empty() || c->line_free[0].size() < need[0] || c->line_free[1].size() < need[1] || c->eq_free.size() < need_eq || c->mod_free[0].size() < need_mod[0] || c->mod_free[1].size() < need_mod[1] || c->ring_free.size() < need_rings) { // all or nothing
 		return GAS_ERR_OUT_OF_SLOTS;
 	}
 	const uint32_t s = c->free_list.back();
@@ -2219,6 +2357,20 @@ int gas_source_alloc(gas_ctx *c, int kind, const int32_t *effects, uint32_t n_ef
 		mod_mark_dirty(c, s);
 		mod_queue_zero(c, s, sig);
 	}
+	if (any_stereo) { // settings from the resource defaults; one ring per stereo enhance, zeroed and entered in the table at the next flush
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		for (uint32_t j = 0; j < GAS_MAX_EFFECTS; j++) {
+			if (j < n_effects && effects[j] == GAS_FX_STEREO_ENHANCE) {
+				c->h_stereo_of[s][j] = (int32_t)c->ring_free.back();
+				c->ring_free.pop_back();
+			} else {
+				c->h_stereo_of[s][j] = -1;
+			}
+		}
+		c->h_stereo[s] = gas_fx_stereo_settings_defaults();
+		stereo_mark_dirty(c, s);
+		ring_queue_zero(c, s, sig);
+	}
 	return GAS_OK;
 }
 
@@ -2279,6 +2431,10 @@ int gas_source_reset(gas_ctx *c, uint32_t slot) {
 		if (!c->h_mod_of.empty() && c->slots[slot].used) { // and its chorus lines and phaser banks
 			std::lock_guard<std::mutex> lk(c->params_mu);
 			mod_queue_zero(c, slot, c->slots[slot].chain_sig);
+		}
+		if (c->ring_cap > 0 && c->slots[slot].used) { // and its stereo-enhance rings
+			std::lock_guard<std::mutex> lk(c->params_mu);
+			ring_queue_zero(c, slot, c->slots[slot].chain_sig);
 		}
 	}
 	return GAS_OK;
@@ -2554,7 +2710,7 @@ int gas_fx_mod_settings_publish(gas_ctx *c, const uint32_t *slots, const gas_fx_
 }
 
 // [ENGINE] AudioEffectChorus's ring: 1 << bitlength((int)(0.24 sr)) frames
-uint32_t chorus_ring_frames(double sr) {
+static uint32_t chorus_ring_frames(double sr) {
 	const uint32_t n = (uint32_t)(int)(0.24 * sr);
 	uint32_t bits = 0;
 	while (bits < 31 && (n >> bits) != 0) {
@@ -2636,6 +2792,89 @@ int gas_ctx_reserve_fx_mod(gas_ctx *c, uint32_t chorus_lines, uint32_t phaser_ba
 	c->h_mod_of.assign(N, none);
 	c->h_mod = std::move(defaults);
 	c->mod_dirty_flag.assign(N, 0);
+	return GAS_OK;
+}
+
+int gas_fx_stereo_settings_publish(gas_ctx *c, const uint32_t *slots, const gas_fx_stereo_settings *settings, uint32_t n) {
+	if (!c || (n > 0 && (!slots || !settings))) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	for (uint32_t i = 0; i < n; i++) {
+		if (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used) {
+			return GAS_ERR_BAD_SLOT;
+		}
+		if (!gas_fx_stereo_settings_valid(settings[i])) {
+			return GAS_ERR_INVALID_ARGUMENT;
+		}
+	}
+	std::lock_guard<std::mutex> lk(c->params_mu);
+	for (uint32_t i = 0; i < n; i++) {
+		c->h_stereo[slots[i]] = settings[i];
+		stereo_mark_dirty(c, slots[i]);
+	}
+	return GAS_OK;
+}
+
+// [ENGINE] AudioEffectStereoEnhance's ring: 1 << bitlength((int)((50 + 2) / 1000 sr)) frames
+static uint32_t enhance_ring_frames(double sr) {
+	const uint32_t n = (uint32_t)(int)((50.0 + 2.0) / 1000.0 * sr);
+	uint32_t bits = 0;
+	while (bits < 31 && (n >> bits) != 0) {
+		bits++;
+	}
+	return 1u << bits;
+}
+
+int gas_ctx_reserve_fx_stereo(gas_ctx *c, uint32_t enhance_rings) {
+	if (!c) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	const uint32_t R = enhance_ring_frames((double)c->cfg.mix_rate);
+	if (enhance_rings > 0 && (R < c->cfg.frames || R < 4)) {
+		return GAS_ERR_INVALID_ARGUMENT; // two frames of one block would share a ring entry
+	}
+	std::lock_guard<std::mutex> alloc_lk(c->alloc_mu);
+	if (c->ring_free.size() != c->ring_cap) {
+		return GAS_ERR_INVALID_ARGUMENT; // rings are held
+	}
+	GAS_HIP(c, hipSetDevice(c->cfg.device));
+	GAS_HIP(c, hipStreamSynchronize(c->stream));
+	{
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		release_fx_stereo_pool(c);
+	}
+	const size_t ring_floats = GAS_ENHANCE_HEADER + (size_t)R;
+	hipError_t e = hipSuccess;
+	{
+		// (the staging buffer may hold queued settings rows only in the mirror: flush_fx_stereo fills it per flush)
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		e = alloc_stereo_upload(c, enhance_rings);
+	}
+	if (e == hipSuccess && enhance_rings) {
+		e = hipMalloc(&c->st.enhance_pool, ring_floats * sizeof(float) * enhance_rings);
+		e = e != hipSuccess ? e : hipMemsetAsync(c->st.enhance_pool, 0, ring_floats * sizeof(float) * enhance_rings, c->stream);
+		e = e != hipSuccess ? e : hipStreamSynchronize(c->stream);
+	}
+	if (e != hipSuccess) {
+		c->last_err = std::string("gas_ctx_reserve_fx_stereo: ") + hipGetErrorString(e);
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		release_fx_stereo_pool(c);
+		if (!c->h_stereo_upload || !c->d_stereo_upload) {
+			(void)alloc_stereo_upload(c, 0);
+		}
+		return e == hipErrorOutOfMemory ? GAS_ERR_OUT_OF_MEMORY : GAS_ERR_DEVICE;
+	}
+	if (enhance_rings == 0) {
+		return GAS_OK;
+	}
+	std::lock_guard<std::mutex> lk(c->params_mu);
+	c->st.enhance_mask = R - 1;
+	c->ring_cap = enhance_rings;
+	c->ring_zero_pending.assign(enhance_rings, 0);
+	c->ring_free.resize(enhance_rings);
+	for (uint32_t i = 0; i < enhance_rings; i++) { // handed out from ring 0 up
+		c->ring_free[i] = enhance_rings - 1 - i;
+	}
 	return GAS_OK;
 }
 

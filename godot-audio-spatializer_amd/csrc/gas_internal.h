@@ -16,6 +16,7 @@ static_assert(sizeof(gas_fx_dyn_settings) == 12 * 4 * GAS_MAX_EFFECTS, "gas_fx_d
 static_assert(sizeof(gas_fx_line_settings) == 21 * 4 * GAS_MAX_EFFECTS, "gas_fx_line_settings is 21 arrays by chain position");
 static_assert(sizeof(gas_fx_eq_settings) == 336, "gas_fx_eq_settings is [GAS_MAX_EFFECTS][21] f32");
 static_assert(sizeof(gas_fx_mod_settings) == 512, "gas_fx_mod_settings is 5 arrays by chain position, 6 by position and voice, 5 by position");
+static_assert(sizeof(gas_fx_stereo_settings) == 128, "gas_fx_stereo_settings is 8 arrays by chain position");
 
 // GAS_FX_EQ6 / _EQ10 / _EQ21 (k_fx_eq.hip): one bank of state per instance, [21 bands][a2, a3, b2, b3]
 // [2 ears] floats (the engine's BandProcess history per band and ear), and the per-band coefficients of one preset at
@@ -31,6 +32,10 @@ struct gas_eq_coefs {
 #define GAS_CHORUS_HEADER 64
 #define GAS_CHORUS_H 16
 #define GAS_PHASER_BANK_FLOATS 16
+
+// GAS_FX_STEREO_ENHANCE (k_fx_stereo.hip).  A ring is GAS_ENHANCE_HEADER floats of state {pos u32, -,
+// -, -}, then enhance_mask + 1 mono frames.
+#define GAS_ENHANCE_HEADER 4
 
 // GAS_FX_DELAY / GAS_FX_REVERB line geometry, fixed per context by the mix rate (gas_ctx_reserve_fx_lines).
 // Every line starts with GAS_LINE_HEADER floats of state; offsets below are in floats from the line's start.
@@ -92,6 +97,12 @@ struct gas_dev_state {
 	float *chorus_pool; // [chorus lines][GAS_CHORUS_HEADER + 2 (chorus_mask + 1)]
 	float *phaser_pool; // [phaser banks][GAS_PHASER_BANK_FLOATS]
 	uint32_t chorus_mask; // ring frames - 1
+	// GAS_FX_PANNER / GAS_FX_STEREO_ENHANCE / GAS_FX_LIMITER (k_fx_stereo.hip): settings and the slot -> ring table (from
+	// gas_ctx_create on), the ring pool (nullptr until gas_ctx_reserve_fx_stereo)
+	gas_fx_stereo_settings *stereo_settings; // [max_sources], by chain position
+	int32_t *stereo_of; // [GAS_MAX_EFFECTS][max_sources] ring of chain position j, -1: none
+	float *enhance_pool; // [rings][GAS_ENHANCE_HEADER + enhance_mask + 1]
+	uint32_t enhance_mask; // ring frames - 1
 };
 
 // Device-resident playback cursor: what SpatialPlaybackListNode + the engine's sampler hold.
@@ -254,6 +265,12 @@ int gas_eq_bands(int kind); // 6, 10, 21; 0 for any other kind
 hipError_t gas_launch_fx_mod(hipStream_t stream, int kind, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t chain_pos, float mix_rate, gas_audio_frame *rows_out);
 hipError_t gas_launch_scatter_mod(hipStream_t stream, const gas_dev_state &st, const gas_fx_mod_settings *upload, const uint32_t *slot_idx, uint32_t n);
 hipError_t gas_launch_zero_mod(hipStream_t stream, const gas_dev_state &st, const uint32_t *kind_idx, uint32_t n);
+// k_fx_stereo.hip: a GAS_FX_PANNER / GAS_FX_STEREO_ENHANCE / GAS_FX_LIMITER stage (rows in -> dense rows out); the
+// scatter of published settings records ([m] gas_fx_stereo_settings, then [m] {slot, ring[GAS_MAX_EFFECTS]}) and the
+// zeroing of [z] rings
+hipError_t gas_launch_fx_stereo(hipStream_t stream, int kind, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t chain_pos, float mix_rate, gas_audio_frame *rows_out);
+hipError_t gas_launch_scatter_stereo(hipStream_t stream, const gas_dev_state &st, const gas_fx_stereo_settings *upload, const uint32_t *slot_idx, uint32_t n);
+hipError_t gas_launch_zero_rings(hipStream_t stream, const gas_dev_state &st, const uint32_t *rings, uint32_t n);
 hipError_t gas_launch_zero_lines(hipStream_t stream, const gas_dev_state &st, const gas_line_geo &geo, const uint32_t *kind_line, uint32_t n);
 hipError_t gas_launch_scatter_dyn(hipStream_t stream, gas_fx_dyn_settings *table, const gas_fx_dyn_settings *upload, const uint32_t *slots, uint32_t n);
 hipError_t gas_launch_scatter_params(hipStream_t stream, gas_params *table, const gas_params *upload, const uint32_t *slots, uint32_t n);

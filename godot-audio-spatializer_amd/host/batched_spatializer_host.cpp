@@ -24,6 +24,7 @@
 #include "../csrc/gas_fx_eq_check.h"
 #include "../csrc/gas_fx_line_check.h"
 #include "../csrc/gas_fx_mod_check.h"
+#include "../csrc/gas_fx_stereo_check.h"
 
 // A weak reference: the host layer is also built for the CPU against a stand-in of the library's entries (the
 // ThreadSanitizer build) that does not define this one; in libgas_amd.so it is always there.
@@ -31,6 +32,7 @@
 #pragma weak gas_fx_line_settings_publish
 #pragma weak gas_fx_eq_settings_publish
 #pragma weak gas_fx_mod_settings_publish
+#pragma weak gas_fx_stereo_settings_publish
 
 namespace {
 
@@ -87,7 +89,7 @@ struct Playback {
 };
 
 struct Command {
-	enum Kind { START, PARAMS, FX_SETTINGS, FX_DYN_SETTINGS, FX_LINE_SETTINGS, FX_EQ_SETTINGS, FX_MOD_SETTINGS } kind = START;
+	enum Kind { START, PARAMS, FX_SETTINGS, FX_DYN_SETTINGS, FX_LINE_SETTINGS, FX_EQ_SETTINGS, FX_MOD_SETTINGS, FX_STEREO_SETTINGS } kind = START;
 	uint32_t id = 0;
 	std::unique_ptr<Playback> playback; // START
 	gas_params params{}; // PARAMS
@@ -96,6 +98,7 @@ struct Command {
 	gas_fx_line_settings fx_line_settings{}; // FX_LINE_SETTINGS
 	gas_fx_eq_settings fx_eq_settings{}; // FX_EQ_SETTINGS
 	gas_fx_mod_settings fx_mod_settings{}; // FX_MOD_SETTINGS
+	gas_fx_stereo_settings fx_stereo_settings{}; // FX_STEREO_SETTINGS
 };
 
 // [ENGINE] Math::db_to_linear
@@ -257,6 +260,11 @@ struct gas_host {
 				auto it = by_id.find(c.id);
 				if (it != by_id.end() && gas_fx_mod_settings_publish) {
 					gas_fx_mod_settings_publish(ctx, &it->second->slot, &c.fx_mod_settings, 1); // (validated when queued)
+				}
+			} else if (c.kind == Command::FX_STEREO_SETTINGS) {
+				auto it = by_id.find(c.id);
+				if (it != by_id.end() && gas_fx_stereo_settings_publish) {
+					gas_fx_stereo_settings_publish(ctx, &it->second->slot, &c.fx_stereo_settings, 1); // (validated when queued)
 				}
 			} else {
 				auto it = by_id.find(c.id);
@@ -634,6 +642,25 @@ int gas_host_set_effect_settings_mod(gas_host *h, uint32_t id, const gas_fx_mod_
 	c.kind = Command::FX_MOD_SETTINGS;
 	c.id = id;
 	c.fx_mod_settings = *settings;
+	std::lock_guard<std::mutex> lk(h->inbox_mu);
+	h->inbox.push_back(std::move(c));
+	return GAS_OK;
+}
+
+int gas_host_set_effect_settings_stereo(gas_host *h, uint32_t id, const gas_fx_stereo_settings *settings) {
+	if (!h || !h->lookup(id)) {
+		return GAS_ERR_BAD_SLOT;
+	}
+	if (!settings) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (!gas_fx_stereo_settings_valid(*settings)) { // gas_fx_stereo_settings_publish's rule, checked here: the audio thread cannot report it
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	Command c;
+	c.kind = Command::FX_STEREO_SETTINGS;
+	c.id = id;
+	c.fx_stereo_settings = *settings;
 	std::lock_guard<std::mutex> lk(h->inbox_mu);
 	h->inbox.push_back(std::move(c));
 	return GAS_OK;

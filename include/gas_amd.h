@@ -103,6 +103,11 @@ typedef enum gas_effect_kind {
 	 * playback and chain position: gas_fx_mod_settings. */
 	GAS_FX_CHORUS = 19, /* [ENGINE] AudioEffectChorus: up to 4 LFO-modulated taps of a stereo ring, each low-passed and panned */
 	GAS_FX_PHASER = 20, /* [ENGINE] AudioEffectPhaser: six first-order allpasses per ear with feedback, swept by one LFO */
+	/* The engine's stereo kinds: no recurrence over frames.  Panner and limiter hold no state; every stereo enhance holds
+	 * one mono delay "ring" (gas_ctx_reserve_fx_stereo).  Settings per playback and chain position: gas_fx_stereo_settings. */
+	GAS_FX_PANNER = 21, /* [ENGINE] AudioEffectPanner: each ear keeps its own share and takes the other's remainder */
+	GAS_FX_STEREO_ENHANCE = 22, /* [ENGINE] AudioEffectStereoEnhance: side gain, then a delayed right ear or a delayed mid as +/- surround */
+	GAS_FX_LIMITER = 23, /* [ENGINE] AudioEffectLimiter: make-up gain, soft clip above -soft_clip_db, hard ceiling */
 } gas_effect_kind;
 
 /* [ENGINE] AudioEffectDistortion::Mode */
@@ -303,6 +308,21 @@ typedef struct gas_fx_mod_settings {
 	float phaser_depth[GAS_MAX_EFFECTS]; /* 0.1 .. 4, default 1 */
 } gas_fx_mod_settings;
 
+/* Settings of the GAS_FX_PANNER / GAS_FX_STEREO_ENHANCE / GAS_FX_LIMITER effects of one playback, by chain position:
+ * position j is read only when effect j of the playback's chain is one of those kinds.  Read once per block (no ramp).
+ * A slot's settings start at the defaults below when it is allocated.  Ranges (the engine's property ranges;
+ * gas_fx_stereo_settings_publish refuses anything outside them or not finite, at any position, used or not): */
+typedef struct gas_fx_stereo_settings {
+	float panner_pan[GAS_MAX_EFFECTS]; /* -1 .. 1, default 0 */
+	float enhance_pan_pullout[GAS_MAX_EFFECTS]; /* 0 .. 4, default 1 */
+	float enhance_time_pullout_ms[GAS_MAX_EFFECTS]; /* 0 .. 50, default 0 */
+	float enhance_surround[GAS_MAX_EFFECTS]; /* 0 .. 1, default 0 (> 0: the surround mode) */
+	float limiter_ceiling_db[GAS_MAX_EFFECTS]; /* -20 .. -0.1, default -0.1 */
+	float limiter_threshold_db[GAS_MAX_EFFECTS]; /* -30 .. 0, default 0 */
+	float limiter_soft_clip_db[GAS_MAX_EFFECTS]; /* 0 .. 6, default 2 */
+	float limiter_soft_clip_ratio[GAS_MAX_EFFECTS]; /* 3 .. 20, default 10 (carried; the engine's process never reads it) */
+} gas_fx_stereo_settings;
+
 /* Per-kernel device timing collected with HIP events on the context stream. */
 typedef struct gas_profile {
 	uint64_t launches; /* timed launches of the dominant kernel since the last reset */
@@ -373,6 +393,14 @@ int gas_fx_eq_settings_publish(gas_ctx *ctx, const uint32_t *slots, const gas_fx
  * thread.  A value outside the ranges given at gas_fx_mod_settings or not finite (at any position and voice) is
  * GAS_ERR_INVALID_ARGUMENT, and nothing of the call is taken. */
 int gas_fx_mod_settings_publish(gas_ctx *ctx, const uint32_t *slots, const gas_fx_mod_settings *settings, uint32_t n);
+/* The same for gas_fx_stereo_settings: latest wins, snapshotted at the start of the next gas_process_block, physics
+ * thread.  A value outside the ranges given at gas_fx_stereo_settings or not finite (at any position) is
+ * GAS_ERR_INVALID_ARGUMENT, and nothing of the call is taken.  Needs no reservation: the device settings table, the
+ * slot -> ring table and the staging buffers are allocated by gas_ctx_create, where gas_fx_settings' table is, whether
+ * or not a chain ever holds one of the kinds.  Cost per context: 292 bytes of device memory (128 settings, 16 table,
+ * 148 staging) and 148 bytes of pinned host memory per slot of max_sources -- 2.4 MB and 1.2 MB at 8192 slots, 19 MB
+ * and 9.7 MB at 65 536, 2.4 GB and 1.2 GB at 8.1 M. */
+int gas_fx_stereo_settings_publish(gas_ctx *ctx, const uint32_t *slots, const gas_fx_stereo_settings *settings, uint32_t n);
 
 /* ---- delay memory of the GAS_FX_DELAY / GAS_FX_REVERB instances ("lines") ---------------------------------------
  * Every GAS_FX_DELAY of a chain holds one delay line, every GAS_FX_REVERB one reverb line, from two device pools the
@@ -421,6 +449,24 @@ int gas_ctx_reserve_fx_eq(gas_ctx *ctx, uint32_t eq_banks);
  * reservation is independent of gas_ctx_reserve_fx_lines and gas_ctx_reserve_fx_eq: no call touches another's pools.
  * A gas_multi caller reserves per shard (gas_multi_shard). */
 int gas_ctx_reserve_fx_mod(gas_ctx *ctx, uint32_t chorus_lines, uint32_t phaser_banks);
+
+/* ---- delay memory of the GAS_FX_STEREO_ENHANCE instances ("rings") ------------------------------------------------
+ * Every stereo enhance of a chain holds one ring from a device pool the caller sizes here, with the same contract as
+ * gas_ctx_reserve_fx_mod: main thread, never concurrently with gas_process_block; the pool and the room of the pinned
+ * upload buffer that names the rings to zero are allocated here and nothing on the audio thread (the slot -> ring
+ * table and the device settings table exist from gas_ctx_create on: GAS_FX_PANNER and GAS_FX_LIMITER hold no state,
+ * and chains of only those two and other stateless kinds need no reservation at all); 0 releases the pool; while any
+ * ring is held the call is GAS_ERR_INVALID_ARGUMENT.  Bytes per ring, with sr the mix rate: 16 + 4 R,
+ * R = 1 << bitlength((int)(0.052 sr)) mono frames (the engine's; 4096 at 44.1 and 48 kHz, 8192 at 96 kHz).  The kernel
+ * writes a block into the ring after every read of its launch, so it needs only R >= frames (no two frames of a block
+ * on one entry; R > (unsigned)(0.05 sr), the longest delay, always holds): enhance_rings > 0 with R < frames is
+ * GAS_ERR_INVALID_ARGUMENT.  gas_source_alloc takes one ring per stereo enhance of the chain: with no pool reserved it
+ * is GAS_ERR_UNSUPPORTED_CHAIN, with too few free entries in any pool the chain needs (these, the delay and reverb
+ * lines, the EQ banks, the chorus lines, the phaser banks) GAS_ERR_OUT_OF_SLOTS, and nothing is taken.  Rings go back
+ * with the slot at the next block boundary after gas_source_free; they are zeroed whenever they change hands and by
+ * gas_source_reset.  The reservation is independent of gas_ctx_reserve_fx_lines, gas_ctx_reserve_fx_eq and
+ * gas_ctx_reserve_fx_mod: no call touches another's pools.  A gas_multi caller reserves per shard (gas_multi_shard). */
+int gas_ctx_reserve_fx_stereo(gas_ctx *ctx, uint32_t enhance_rings);
 
 /* ---- NEW AudioSpatializerHRTF resource: hrir is [dirs][2 ears][taps] f32, taps <= 256 */
 int gas_hrtf_load(gas_ctx *ctx, const float *hrir, uint32_t dirs, uint32_t taps);

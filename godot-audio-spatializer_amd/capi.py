@@ -206,6 +206,51 @@ def fx_stereo_settings_defaults(n):
     return d
 
 
+# the engine's AudioEffectFilter at any slope and AudioEffectBandLimitFilter (one "bank" of state per instance,
+# gas_ctx_reserve_fx_filter); settings: gas_fx_filter_settings by chain position
+FX_FILTER = 24
+FILTER_LOWPASS, FILTER_HIGHPASS, FILTER_BANDPASS, FILTER_NOTCH, FILTER_LOWSHELF, FILTER_HIGHSHELF, FILTER_BANDLIMIT = range(7)
+FILTER_6DB, FILTER_12DB, FILTER_18DB, FILTER_24DB = range(4)
+FX_FILTER_SETTINGS_DTYPE = np.dtype(
+    [
+        ("type", np.int32, (MAX_EFFECTS,)),
+        ("db", np.int32, (MAX_EFFECTS,)),
+        ("cutoff_hz", np.float32, (MAX_EFFECTS,)),
+        ("resonance", np.float32, (MAX_EFFECTS,)),
+        ("gain", np.float32, (MAX_EFFECTS,)),
+        ("reserved", np.uint32, (12,)),
+    ]
+)
+assert FX_FILTER_SETTINGS_DTYPE.itemsize == 128
+
+
+class FxFilterSettings(C.Structure):
+    """gas_fx_filter_settings for callers that use ctypes directly."""
+
+    _fields_ = [
+        ("type", C.c_int32 * MAX_EFFECTS),
+        ("db", C.c_int32 * MAX_EFFECTS),
+        ("cutoff_hz", C.c_float * MAX_EFFECTS),
+        ("resonance", C.c_float * MAX_EFFECTS),
+        ("gain", C.c_float * MAX_EFFECTS),
+        ("reserved", C.c_uint32 * 12),
+    ]
+
+
+assert C.sizeof(FxFilterSettings) == 128
+
+
+def fx_filter_settings_defaults(n):
+    """The engine's AudioEffectFilter defaults at every position, n rows (what a slot starts with): low-pass, 6 dB."""
+    d = np.zeros(n, FX_FILTER_SETTINGS_DTYPE)
+    d["type"] = FILTER_LOWPASS
+    d["db"] = FILTER_6DB
+    d["cutoff_hz"] = 2000.0
+    d["resonance"] = 0.5
+    d["gain"] = 1.0
+    return d
+
+
 MEM_HOST = 0
 MEM_DEVICE = 1
 FLAG_PEAKS_DRAINING_ONLY = 1
@@ -355,6 +400,8 @@ EXPORTS = [
     "gas_ctx_reserve_fx_mod",
     "gas_fx_stereo_settings_publish",
     "gas_ctx_reserve_fx_stereo",
+    "gas_fx_filter_settings_publish",
+    "gas_ctx_reserve_fx_filter",
     "gas_params_publish_batch",
     "gas_hrtf_load",
     "gas_hrtf_load_positions",
@@ -445,6 +492,8 @@ def load_library():
     L.gas_ctx_reserve_fx_mod.argtypes = [vp, u32, u32]
     L.gas_fx_stereo_settings_publish.argtypes = [vp, vp, vp, u32]
     L.gas_ctx_reserve_fx_stereo.argtypes = [vp, u32]
+    L.gas_fx_filter_settings_publish.argtypes = [vp, vp, vp, u32]
+    L.gas_ctx_reserve_fx_filter.argtypes = [vp, u32]
     L.gas_params_publish_batch.argtypes = [vp, vp, vp, u32, i32]
     L.gas_hrtf_load.argtypes = [vp, vp, u32, u32]
     L.gas_hrtf_load_positions.argtypes = [vp, vp, vp, u32, u32, u32, u32, i32, vp]
@@ -619,6 +668,20 @@ class SpatializerContext:
     def reserve_fx_stereo(self, enhance_rings):
         """Size the GAS_FX_STEREO_ENHANCE ring pool (main thread, not during a callback); 0 releases it."""
         self._check(self.lib.gas_ctx_reserve_fx_stereo(self.h, int(enhance_rings)), "gas_ctx_reserve_fx_stereo")
+
+    @staticmethod
+    def fx_filter_settings_defaults(n):
+        return fx_filter_settings_defaults(n)
+
+    def fx_filter_settings_publish(self, slots, settings):
+        s = np.ascontiguousarray(slots, dtype=np.uint32)
+        f = np.ascontiguousarray(settings, dtype=FX_FILTER_SETTINGS_DTYPE)
+        assert s.shape == f.shape
+        self._check(self.lib.gas_fx_filter_settings_publish(self.h, _np_ptr(s), _np_ptr(f), len(s)), "gas_fx_filter_settings_publish")
+
+    def reserve_fx_filter(self, banks):
+        """Size the GAS_FX_FILTER bank pool (main thread, not during a callback); 0 releases it."""
+        self._check(self.lib.gas_ctx_reserve_fx_filter(self.h, int(banks)), "gas_ctx_reserve_fx_filter")
 
     def params_publish_batch(self, slots, params):
         s = np.ascontiguousarray(slots, dtype=np.uint32)
@@ -822,6 +885,7 @@ class BatchedSpatializerHost:
         L.gas_host_set_effect_settings_eq.argtypes = [vp, u32, vp]
         L.gas_host_set_effect_settings_mod.argtypes = [vp, u32, vp]
         L.gas_host_set_effect_settings_stereo.argtypes = [vp, u32, vp]
+        L.gas_host_set_effect_settings_filter.argtypes = [vp, u32, vp]
         L.gas_host_set_release_fn.argtypes = [vp, vp, vp]
         L.gas_host_collect_released.argtypes = [vp]
         L.gas_host_set_process_effects_fn.argtypes = [vp, vp, vp]
@@ -923,6 +987,10 @@ class BatchedSpatializerHost:
     def set_effect_settings_stereo(self, pid, settings):
         f = np.ascontiguousarray(settings, dtype=FX_STEREO_SETTINGS_DTYPE).reshape(1)
         return self.lib.gas_host_set_effect_settings_stereo(self.h, pid, _np_ptr(f))
+
+    def set_effect_settings_filter(self, pid, settings):
+        f = np.ascontiguousarray(settings, dtype=FX_FILTER_SETTINGS_DTYPE).reshape(1)
+        return self.lib.gas_host_set_effect_settings_filter(self.h, pid, _np_ptr(f))
 
     def is_playback_active(self, pid):
         return bool(self.lib.gas_host_is_playback_active(self.h, pid))

@@ -13,6 +13,7 @@
 #include <new>
 
 #include "gas_fx_eq_check.h"
+#include "gas_fx_filter_check.h"
 #include "gas_fx_line_check.h"
 #include "gas_fx_mod_check.h"
 #include "gas_fx_stereo_check.h"
@@ -160,6 +161,17 @@ struct gas_ctx {
 	std::vector<uint8_t> eq_zero_pending; // [bank]: queued in eq_zero_list
 	unsigned char *h_eq_upload = nullptr, *d_eq_upload = nullptr;
 	gas_eq_coefs eq_coefs[3] = {}; // EQ6, EQ10, EQ21 at the mix rate (make_eq_coefs)
+	// GAS_FX_FILTER banks (gas_ctx_reserve_fx_filter), kept exactly like the EQ banks: [m settings][m {slot, bank[4]}]
+	// [z bank] through one pinned staging buffer
+	uint32_t flt_cap = 0;
+	std::vector<uint32_t> flt_free;
+	std::vector<std::array<int32_t, GAS_MAX_EFFECTS>> h_flt_of;
+	std::vector<gas_fx_filter_settings> h_flt;
+	std::vector<uint8_t> flt_dirty_flag;
+	std::vector<uint32_t> flt_dirty_list;
+	std::vector<uint32_t> flt_zero_list; // banks, each at most once (flt_zero_pending)
+	std::vector<uint8_t> flt_zero_pending; // [bank]: queued in flt_zero_list
+	unsigned char *h_flt_upload = nullptr, *d_flt_upload = nullptr;
 	// GAS_FX_CHORUS lines and GAS_FX_PHASER banks (gas_ctx_reserve_fx_mod), kept like the delay and reverb lines: pool
 	// sizes and free entries (alloc_mu), each slot's entries by chain position (written under alloc_mu and params_mu),
 	// settings mirror and what the next flush uploads (params_mu): [m settings][m {slot, index[4]}][z {kind, index}]
@@ -337,7 +349,7 @@ int group_of(int kind, const int32_t *fx, uint32_t n_fx) {
 	// reflection ring and one HRTF history per playback
 	int n_er = 0, n_hrtf = 0;
 	for (uint32_t j = 0; j < n_fx; j++) {
-		if ((fx[j] < GAS_FX_HIGHSHELF || fx[j] > GAS_FX_AMPLIFY) && (fx[j] < GAS_FX_DISTORTION || fx[j] > GAS_FX_REVERB) && (fx[j] < GAS_FX_EQ6 || fx[j] > GAS_FX_EQ21) && (fx[j] < GAS_FX_CHORUS || fx[j] > GAS_FX_LIMITER)) {
+		if ((fx[j] < GAS_FX_HIGHSHELF || fx[j] > GAS_FX_AMPLIFY) && (fx[j] < GAS_FX_DISTORTION || fx[j] > GAS_FX_REVERB) && (fx[j] < GAS_FX_EQ6 || fx[j] > GAS_FX_EQ21) && (fx[j] < GAS_FX_CHORUS || fx[j] > GAS_FX_FILTER)) {
 			return -1;
 		}
 		n_er += fx[j] == GAS_FX_EARLY_REFLECTIONS;
@@ -979,6 +991,8 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 							e = gas_launch_fx_line(c->stream, kind, in, c->st, c->line_geo, F, (uint32_t)j, c->cfg.mix_rate, outb);
 						} else if (is_eq(kind)) { // k_fx_eq.hip, state in the slot's bank of chain position j
 							e = gas_launch_fx_eq(c->stream, kind, in, c->st, c->eq_coefs[kind - GAS_FX_EQ6], F, (uint32_t)j, outb);
+						} else if (kind == GAS_FX_FILTER) { // k_fx_filter.hip, state in the slot's bank of chain position j
+							e = gas_launch_fx_filter(c->stream, in, c->st, F, (uint32_t)j, c->cfg.mix_rate, outb);
 						} else if (mod_pool_of(kind) >= 0) { // k_fx_mod.hip, state in the slot's chorus line / phaser bank of chain position j
 							e = gas_launch_fx_mod(c->stream, kind, in, c->st, F, (uint32_t)j, c->cfg.mix_rate, outb);
 						} else if (is_stereo(kind)) { // k_fx_stereo.hip, settings by chain position; a stereo enhance's state in the slot's ring of chain position j
@@ -1439,6 +1453,86 @@ void release_fx_eq(gas_ctx *c) {
 	c->eq_zero_pending.clear();
 }
 
+// gas_fx_filter_settings_publish's rows, new slot -> bank entries and banks to zero: one copy of
+// [m settings][m {slot, bank[4]}][z bank], one scatter, one zeroing launch.
+int flush_fx_filter(gas_ctx *c) {
+	if (!c->h_flt_upload) {
+		return GAS_OK;
+	}
+	uint32_t m = 0, z = 0;
+	{
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		m = (uint32_t)c->flt_dirty_list.size();
+		z = (uint32_t)c->flt_zero_list.size();
+		if (m == 0 && z == 0) {
+			return GAS_OK;
+		}
+		gas_fx_filter_settings *hs = reinterpret_cast<gas_fx_filter_settings *>(c->h_flt_upload);
+		uint32_t *hsb = reinterpret_cast<uint32_t *>(c->h_flt_upload + (size_t)m * sizeof(gas_fx_filter_settings));
+		for (uint32_t i = 0; i < m; i++) {
+			const uint32_t s = c->flt_dirty_list[i];
+			hs[i] = c->h_flt[s];
+			hsb[i * (1 + GAS_MAX_EFFECTS)] = s;
+			for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
+				hsb[i * (1 + GAS_MAX_EFFECTS) + 1 + j] = (uint32_t)c->h_flt_of[s][j];
+			}
+			c->flt_dirty_flag[s] = 0;
+		}
+		std::memcpy(hsb + (size_t)m * (1 + GAS_MAX_EFFECTS), c->flt_zero_list.data(), (size_t)z * sizeof(uint32_t));
+		for (uint32_t i = 0; i < z; i++) {
+			c->flt_zero_pending[c->flt_zero_list[i]] = 0;
+		}
+		c->flt_dirty_list.clear();
+		c->flt_zero_list.clear();
+	}
+	const size_t zoff = (size_t)m * (sizeof(gas_fx_filter_settings) + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t));
+	GAS_HIP(c, hipMemcpyAsync(c->d_flt_upload, c->h_flt_upload, zoff + (size_t)z * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	GAS_HIP(c, gas_launch_scatter_filter(c->stream, c->st, reinterpret_cast<const gas_fx_filter_settings *>(c->d_flt_upload), reinterpret_cast<const uint32_t *>(c->d_flt_upload + (size_t)m * sizeof(gas_fx_filter_settings)), m));
+	GAS_HIP(c, gas_launch_zero_filter_banks(c->stream, c->st, reinterpret_cast<const uint32_t *>(c->d_flt_upload + zoff), z));
+	GAS_HIP(c, hipStreamSynchronize(c->stream)); // the pinned staging buffer is reused by the next flush
+	return GAS_OK;
+}
+
+// Marks slot s's GAS_FX_FILTER settings row (and its bank table row) for the next flush; params_mu held.
+void flt_mark_dirty(gas_ctx *c, uint32_t s) {
+	if (!c->flt_dirty_flag[s]) {
+		c->flt_dirty_flag[s] = 1;
+		c->flt_dirty_list.push_back(s);
+	}
+}
+
+// Queues the zeroing of slot s's banks (chain signature sig), each bank at most once until the next flush, so the queue
+// never holds more entries than the pool has banks (the upload buffer's zero section); params_mu held.
+void flt_queue_zero(gas_ctx *c, uint32_t s, uint32_t sig) {
+	for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
+		const int32_t bank = c->h_flt_of[s][j];
+		if (((sig >> (8 * j)) & 0xff) == GAS_FX_FILTER && bank >= 0 && !c->flt_zero_pending[bank]) {
+			c->flt_zero_pending[bank] = 1;
+			c->flt_zero_list.push_back((uint32_t)bank);
+		}
+	}
+}
+
+void release_fx_filter(gas_ctx *c) {
+	(void)hipFree(c->st.flt_pool);
+	(void)hipFree(c->st.flt_of);
+	(void)hipFree(c->st.flt_settings);
+	(void)hipFree(c->d_flt_upload);
+	(void)hipHostFree(c->h_flt_upload);
+	c->st.flt_pool = nullptr;
+	c->st.flt_of = nullptr;
+	c->st.flt_settings = nullptr;
+	c->d_flt_upload = c->h_flt_upload = nullptr;
+	c->flt_cap = 0;
+	c->flt_free.clear();
+	c->h_flt_of.clear();
+	c->h_flt.clear();
+	c->flt_dirty_flag.clear();
+	c->flt_dirty_list.clear();
+	c->flt_zero_list.clear();
+	c->flt_zero_pending.clear();
+}
+
 // gas_fx_mod_settings_publish's rows, new slot -> line / bank entries and entries to zero: one copy of
 // [m settings][m {slot, index[4]}][z {kind, index}], one scatter, one zeroing launch.
 int flush_fx_mod(gas_ctx *c) {
@@ -1633,6 +1727,7 @@ int flush_params(gas_ctx *c) {
 	rc = rc != GAS_OK ? rc : flush_fx_dyn_settings(c);
 	rc = rc != GAS_OK ? rc : flush_fx_lines(c);
 	rc = rc != GAS_OK ? rc : flush_fx_eq(c);
+	rc = rc != GAS_OK ? rc : flush_fx_filter(c);
 	rc = rc != GAS_OK ? rc : flush_fx_mod(c);
 	return rc != GAS_OK ? rc : flush_fx_stereo(c);
 }
@@ -1671,6 +1766,15 @@ int apply_pending_frees(gas_ctx *c) {
 				if (pool >= 0 && c->h_line_of[s][j] >= 0) {
 					c->line_free[pool].push_back((uint32_t)c->h_line_of[s][j]);
 					c->h_line_of[s][j] = -1;
+				}
+			}
+		}
+		if (!c->h_flt_of.empty()) { // its GAS_FX_FILTER banks likewise
+			std::lock_guard<std::mutex> lk(c->params_mu);
+			for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
+				if (((si.chain_sig >> (8 * j)) & 0xff) == GAS_FX_FILTER && c->h_flt_of[s][j] >= 0) {
+					c->flt_free.push_back((uint32_t)c->h_flt_of[s][j]);
+					c->h_flt_of[s][j] = -1;
 				}
 			}
 		}
@@ -1942,6 +2046,7 @@ void gas_ctx_destroy(gas_ctx *c) {
 	(void)hipHostFree(c->h_dyn_upload);
 	release_fx_lines(c);
 	release_fx_eq(c);
+	release_fx_filter(c);
 	release_fx_mod(c);
 	release_fx_stereo_pool(c);
 	(void)hipFree(c->st.stereo_settings);
@@ -2248,6 +2353,7 @@ int gas_source_alloc(gas_ctx *c, int kind, const int32_t *effects, uint32_t n_ef
 	uint32_t need_eq = 0; // EQ banks of the chain
 	uint32_t need_mod[2] = { 0, 0 }; // chorus lines / phaser banks of the chain
 	uint32_t need_rings = 0; // stereo-enhance rings of the chain
+	uint32_t need_flt = 0; // GAS_FX_FILTER banks of the chain
 	bool any_stereo = false;
 	for (uint32_t j = 0; j < n_effects; j++) {
 		const int pool = line_pool_of(effects[j]);
@@ -2260,6 +2366,7 @@ int gas_source_alloc(gas_ctx *c, int kind, const int32_t *effects, uint32_t n_ef
 			need_mod[mpool]++;
 		}
 		need_rings += effects[j] == GAS_FX_STEREO_ENHANCE;
+		need_flt += effects[j] == GAS_FX_FILTER;
 		any_stereo = any_stereo || is_stereo(effects[j]);
 	}
 	std::lock_guard<std::mutex> alloc_lk(c->alloc_mu); // any thread (instantiate_playback_data runs on the physics thread, audio_spatializer.cpp:69)
@@ -2275,7 +2382,10 @@ int gas_source_alloc(gas_ctx *c, int kind, const int32_t *effects, uint32_t n_ef
 	if (need_rings > 0 && c->ring_cap == 0) {
 		return GAS_ERR_UNSUPPORTED_CHAIN; // no ring pool reserved (gas_ctx_reserve_fx_stereo)
 	}
-	if (c->free_list.empty() || c->line_free[0].size() < need[0] || c->line_free[1].size() < need[1] || c->eq_free.size() < need_eq || c->mod_free[0].size() < need_mod[0] || c->mod_free[1].size() < need_mod[1] || c->ring_free.size() < need_rings) { // all or nothing
+	if (need_flt > 0 && c->flt_cap == 0) {
+		return GAS_ERR_UNSUPPORTED_CHAIN; // no bank pool reserved (gas_ctx_reserve_fx_filter)
+	}
+	if (c->free_list.empty() || c->line_free[0].size() < need[0] || c->line_free[1].size() < need[1] || c->eq_free.size() < need_eq || c->mod_free[0].size() < need_mod[0] || c->mod_free[1].size() < need_mod[1] || c->ring_free.size() < need_rings || c->flt_free.size() < need_flt) { // all or nothing
 		return GAS_ERR_OUT_OF_SLOTS;
 	}
 	const uint32_t s = c->free_list.back();
@@ -2371,6 +2481,20 @@ int gas_source_alloc(gas_ctx *c, int kind, const int32_t *effects, uint32_t n_ef
 		stereo_mark_dirty(c, s);
 		ring_queue_zero(c, s, sig);
 	}
+	if (need_flt > 0) { // one bank per GAS_FX_FILTER, zeroed and entered in the table at the next flush
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		for (uint32_t j = 0; j < GAS_MAX_EFFECTS; j++) {
+			if (j < n_effects && effects[j] == GAS_FX_FILTER) {
+				c->h_flt_of[s][j] = (int32_t)c->flt_free.back();
+				c->flt_free.pop_back();
+			} else {
+				c->h_flt_of[s][j] = -1;
+			}
+		}
+		c->h_flt[s] = gas_fx_filter_settings_defaults();
+		flt_mark_dirty(c, s);
+		flt_queue_zero(c, s, sig);
+	}
 	return GAS_OK;
 }
 
@@ -2431,6 +2555,10 @@ int gas_source_reset(gas_ctx *c, uint32_t slot) {
 		if (!c->h_mod_of.empty() && c->slots[slot].used) { // and its chorus lines and phaser banks
 			std::lock_guard<std::mutex> lk(c->params_mu);
 			mod_queue_zero(c, slot, c->slots[slot].chain_sig);
+		}
+		if (!c->h_flt_of.empty() && c->slots[slot].used) { // and its GAS_FX_FILTER banks
+			std::lock_guard<std::mutex> lk(c->params_mu);
+			flt_queue_zero(c, slot, c->slots[slot].chain_sig);
 		}
 		if (c->ring_cap > 0 && c->slots[slot].used) { // and its stereo-enhance rings
 			std::lock_guard<std::mutex> lk(c->params_mu);
@@ -2683,6 +2811,86 @@ int gas_ctx_reserve_fx_eq(gas_ctx *c, uint32_t eq_banks) {
 	c->h_eq_of.assign(N, none);
 	c->h_eq = std::move(defaults);
 	c->eq_dirty_flag.assign(N, 0);
+	return GAS_OK;
+}
+
+int gas_fx_filter_settings_publish(gas_ctx *c, const uint32_t *slots, const gas_fx_filter_settings *settings, uint32_t n) {
+	if (!c || (n > 0 && (!slots || !settings))) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	for (uint32_t i = 0; i < n; i++) {
+		if (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used) {
+			return GAS_ERR_BAD_SLOT;
+		}
+		if (!gas_fx_filter_settings_valid(settings[i])) {
+			return GAS_ERR_INVALID_ARGUMENT;
+		}
+	}
+	std::lock_guard<std::mutex> lk(c->params_mu);
+	if (c->h_flt.empty()) { // no pool reserved: no slot has a GAS_FX_FILTER the settings could reach
+		return GAS_OK;
+	}
+	for (uint32_t i = 0; i < n; i++) {
+		c->h_flt[slots[i]] = settings[i];
+		flt_mark_dirty(c, slots[i]);
+	}
+	return GAS_OK;
+}
+
+int gas_ctx_reserve_fx_filter(gas_ctx *c, uint32_t banks) {
+	if (!c) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	std::lock_guard<std::mutex> alloc_lk(c->alloc_mu);
+	if (c->flt_free.size() != c->flt_cap) {
+		return GAS_ERR_INVALID_ARGUMENT; // banks are held
+	}
+	GAS_HIP(c, hipSetDevice(c->cfg.device));
+	GAS_HIP(c, hipStreamSynchronize(c->stream));
+	{
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		release_fx_filter(c);
+	}
+	if (banks == 0) {
+		return GAS_OK;
+	}
+	const size_t N = c->cfg.max_sources;
+	// [<= N settings rows][<= N {slot, bank[4]}][<= every bank once] (flt_mark_dirty / flt_queue_zero)
+	const size_t upload = N * (sizeof(gas_fx_filter_settings) + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t)) + (size_t)banks * sizeof(uint32_t);
+	std::vector<gas_fx_filter_settings> defaults(N, gas_fx_filter_settings_defaults());
+	hipError_t e = hipSuccess;
+	auto step = [&e](hipError_t r) {
+		if (e == hipSuccess) {
+			e = r;
+		}
+	};
+	step(hipMalloc(&c->st.flt_pool, sizeof(float) * GAS_FILTER_BANK_FLOATS * banks));
+	step(e == hipSuccess ? hipMemsetAsync(c->st.flt_pool, 0, sizeof(float) * GAS_FILTER_BANK_FLOATS * banks, c->stream) : e);
+	step(hipMalloc(&c->st.flt_of, sizeof(int32_t) * GAS_MAX_EFFECTS * N));
+	step(e == hipSuccess ? hipMemsetAsync(c->st.flt_of, 0xff, sizeof(int32_t) * GAS_MAX_EFFECTS * N, c->stream) : e);
+	step(hipMalloc(&c->st.flt_settings, sizeof(gas_fx_filter_settings) * N));
+	step(e == hipSuccess ? hipMemcpyAsync(c->st.flt_settings, defaults.data(), sizeof(gas_fx_filter_settings) * N, hipMemcpyHostToDevice, c->stream) : e);
+	step(hipMalloc(&c->d_flt_upload, upload));
+	step(hipHostMalloc(&c->h_flt_upload, upload, hipHostMallocDefault));
+	step(e == hipSuccess ? hipStreamSynchronize(c->stream) : e);
+	if (e != hipSuccess) {
+		c->last_err = std::string("gas_ctx_reserve_fx_filter: ") + hipGetErrorString(e);
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		release_fx_filter(c);
+		return e == hipErrorOutOfMemory ? GAS_ERR_OUT_OF_MEMORY : GAS_ERR_DEVICE;
+	}
+	std::lock_guard<std::mutex> lk(c->params_mu);
+	c->flt_cap = banks;
+	c->flt_zero_pending.assign(banks, 0);
+	c->flt_free.resize(banks);
+	for (uint32_t i = 0; i < banks; i++) { // handed out from bank 0 up
+		c->flt_free[i] = banks - 1 - i;
+	}
+	std::array<int32_t, GAS_MAX_EFFECTS> none;
+	none.fill(-1);
+	c->h_flt_of.assign(N, none);
+	c->h_flt = std::move(defaults);
+	c->flt_dirty_flag.assign(N, 0);
 	return GAS_OK;
 }
 

@@ -17,6 +17,7 @@ static_assert(sizeof(gas_fx_line_settings) == 21 * 4 * GAS_MAX_EFFECTS, "gas_fx_
 static_assert(sizeof(gas_fx_eq_settings) == 336, "gas_fx_eq_settings is [GAS_MAX_EFFECTS][21] f32");
 static_assert(sizeof(gas_fx_mod_settings) == 512, "gas_fx_mod_settings is 5 arrays by chain position, 6 by position and voice, 5 by position");
 static_assert(sizeof(gas_fx_stereo_settings) == 128, "gas_fx_stereo_settings is 8 arrays by chain position");
+static_assert(sizeof(gas_fx_filter_settings) == 128, "gas_fx_filter_settings is 5 arrays by chain position and 12 reserved words");
 
 // GAS_FX_EQ6 / _EQ10 / _EQ21 (k_fx_eq.hip): one bank of state per instance, [21 bands][a2, a3, b2, b3]
 // [2 ears] floats (the engine's BandProcess history per band and ear), and the per-band coefficients of one preset at
@@ -25,6 +26,10 @@ static_assert(sizeof(gas_fx_stereo_settings) == 128, "gas_fx_stereo_settings is 
 struct gas_eq_coefs {
 	float c1[GAS_EQ_MAX_BANDS], c2[GAS_EQ_MAX_BANDS], c3[GAS_EQ_MAX_BANDS];
 };
+
+// GAS_FX_FILTER (k_fx_filter.hip): one bank of state per instance, [4 stages][a1, a2, b1, b2][2 ears]
+// floats (the history of the engine's four AudioFilterSW processors per ear)
+#define GAS_FILTER_BANK_FLOATS 32
 
 // GAS_FX_CHORUS / GAS_FX_PHASER (k_fx_mod.hip).  A chorus line is GAS_CHORUS_HEADER floats of state
 // {pos u32, -, cycles[4] u64, -, h[4 voices][2 ears] at GAS_CHORUS_H}, then a ring of chorus_mask + 1 stereo frames; a
@@ -103,6 +108,11 @@ struct gas_dev_state {
 	int32_t *stereo_of; // [GAS_MAX_EFFECTS][max_sources] ring of chain position j, -1: none
 	float *enhance_pool; // [rings][GAS_ENHANCE_HEADER + enhance_mask + 1]
 	uint32_t enhance_mask; // ring frames - 1
+	// GAS_FX_FILTER (k_fx_filter.hip): settings, slot -> bank table, the bank pool (nullptr until
+	// gas_ctx_reserve_fx_filter)
+	gas_fx_filter_settings *flt_settings; // [max_sources], by chain position
+	int32_t *flt_of; // [GAS_MAX_EFFECTS][max_sources] bank of chain position j
+	float *flt_pool; // [banks][GAS_FILTER_BANK_FLOATS]
 };
 
 // Device-resident playback cursor: what SpatialPlaybackListNode + the engine's sampler hold.
@@ -271,6 +281,11 @@ hipError_t gas_launch_zero_mod(hipStream_t stream, const gas_dev_state &st, cons
 hipError_t gas_launch_fx_stereo(hipStream_t stream, int kind, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t chain_pos, float mix_rate, gas_audio_frame *rows_out);
 hipError_t gas_launch_scatter_stereo(hipStream_t stream, const gas_dev_state &st, const gas_fx_stereo_settings *upload, const uint32_t *slot_idx, uint32_t n);
 hipError_t gas_launch_zero_rings(hipStream_t stream, const gas_dev_state &st, const uint32_t *rings, uint32_t n);
+// k_fx_filter.hip: a GAS_FX_FILTER stage (rows in -> dense rows out); the scatter of published settings records ([m]
+// gas_fx_filter_settings, then [m] {slot, bank[GAS_MAX_EFFECTS]}) and the zeroing of ([z] bank) banks
+hipError_t gas_launch_fx_filter(hipStream_t stream, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t chain_pos, float mix_rate, gas_audio_frame *rows_out);
+hipError_t gas_launch_scatter_filter(hipStream_t stream, const gas_dev_state &st, const gas_fx_filter_settings *upload, const uint32_t *slot_banks, uint32_t n);
+hipError_t gas_launch_zero_filter_banks(hipStream_t stream, const gas_dev_state &st, const uint32_t *banks, uint32_t n);
 hipError_t gas_launch_zero_lines(hipStream_t stream, const gas_dev_state &st, const gas_line_geo &geo, const uint32_t *kind_line, uint32_t n);
 hipError_t gas_launch_scatter_dyn(hipStream_t stream, gas_fx_dyn_settings *table, const gas_fx_dyn_settings *upload, const uint32_t *slots, uint32_t n);
 hipError_t gas_launch_scatter_params(hipStream_t stream, gas_params *table, const gas_params *upload, const uint32_t *slots, uint32_t n);

@@ -24,6 +24,7 @@
 #include "../csrc/gas_fx_eq_check.h"
 #include "../csrc/gas_fx_line_check.h"
 #include "../csrc/gas_fx_mod_check.h"
+#include "../csrc/gas_fx_filter_check.h"
 #include "../csrc/gas_fx_stereo_check.h"
 
 // A weak reference: the host layer is also built for the CPU against a stand-in of the library's entries (the
@@ -33,6 +34,7 @@
 #pragma weak gas_fx_eq_settings_publish
 #pragma weak gas_fx_mod_settings_publish
 #pragma weak gas_fx_stereo_settings_publish
+#pragma weak gas_fx_filter_settings_publish
 
 namespace {
 
@@ -89,7 +91,7 @@ struct Playback {
 };
 
 struct Command {
-	enum Kind { START, PARAMS, FX_SETTINGS, FX_DYN_SETTINGS, FX_LINE_SETTINGS, FX_EQ_SETTINGS, FX_MOD_SETTINGS, FX_STEREO_SETTINGS } kind = START;
+	enum Kind { START, PARAMS, FX_SETTINGS, FX_DYN_SETTINGS, FX_LINE_SETTINGS, FX_EQ_SETTINGS, FX_MOD_SETTINGS, FX_STEREO_SETTINGS, FX_FILTER_SETTINGS } kind = START;
 	uint32_t id = 0;
 	std::unique_ptr<Playback> playback; // START
 	gas_params params{}; // PARAMS
@@ -99,6 +101,7 @@ struct Command {
 	gas_fx_eq_settings fx_eq_settings{}; // FX_EQ_SETTINGS
 	gas_fx_mod_settings fx_mod_settings{}; // FX_MOD_SETTINGS
 	gas_fx_stereo_settings fx_stereo_settings{}; // FX_STEREO_SETTINGS
+	gas_fx_filter_settings fx_filter_settings{}; // FX_FILTER_SETTINGS
 };
 
 // [ENGINE] Math::db_to_linear
@@ -265,6 +268,11 @@ struct gas_host {
 				auto it = by_id.find(c.id);
 				if (it != by_id.end() && gas_fx_stereo_settings_publish) {
 					gas_fx_stereo_settings_publish(ctx, &it->second->slot, &c.fx_stereo_settings, 1); // (validated when queued)
+				}
+			} else if (c.kind == Command::FX_FILTER_SETTINGS) {
+				auto it = by_id.find(c.id);
+				if (it != by_id.end() && gas_fx_filter_settings_publish) {
+					gas_fx_filter_settings_publish(ctx, &it->second->slot, &c.fx_filter_settings, 1); // (validated when queued)
 				}
 			} else {
 				auto it = by_id.find(c.id);
@@ -661,6 +669,25 @@ int gas_host_set_effect_settings_stereo(gas_host *h, uint32_t id, const gas_fx_s
 	c.kind = Command::FX_STEREO_SETTINGS;
 	c.id = id;
 	c.fx_stereo_settings = *settings;
+	std::lock_guard<std::mutex> lk(h->inbox_mu);
+	h->inbox.push_back(std::move(c));
+	return GAS_OK;
+}
+
+int gas_host_set_effect_settings_filter(gas_host *h, uint32_t id, const gas_fx_filter_settings *settings) {
+	if (!h || !h->lookup(id)) {
+		return GAS_ERR_BAD_SLOT;
+	}
+	if (!settings) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (!gas_fx_filter_settings_valid(*settings)) { // gas_fx_filter_settings_publish's rule, checked here: the audio thread cannot report it
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	Command c;
+	c.kind = Command::FX_FILTER_SETTINGS;
+	c.id = id;
+	c.fx_filter_settings = *settings;
 	std::lock_guard<std::mutex> lk(h->inbox_mu);
 	h->inbox.push_back(std::move(c));
 	return GAS_OK;

@@ -108,7 +108,25 @@ typedef enum gas_effect_kind {
 	GAS_FX_PANNER = 21, /* [ENGINE] AudioEffectPanner: each ear keeps its own share and takes the other's remainder */
 	GAS_FX_STEREO_ENHANCE = 22, /* [ENGINE] AudioEffectStereoEnhance: side gain, then a delayed right ear or a delayed mid as +/- surround */
 	GAS_FX_LIMITER = 23, /* [ENGINE] AudioEffectLimiter: make-up gain, soft clip above -soft_clip_db, hard ceiling */
+	/* The engine's AudioEffectFilter of any subclass at any slope, and AudioEffectBandLimitFilter: 1 .. 4 cascaded
+	 * AudioFilterSW stages per ear (state in "banks", reserved with gas_ctx_reserve_fx_filter); settings per playback and
+	 * chain position: gas_fx_filter_settings.  Kinds 1 and 4 .. 8 stay the one-stage forms they are. */
+	GAS_FX_FILTER = 24, /* [ENGINE] AudioEffectFilter: `type` at FILTER_6DB .. FILTER_24DB */
 } gas_effect_kind;
+
+/* gas_fx_filter_settings.type: which AudioEffectFilter subclass (the AudioFilterSW mode it selects) */
+#define GAS_FILTER_LOWPASS 0
+#define GAS_FILTER_HIGHPASS 1
+#define GAS_FILTER_BANDPASS 2
+#define GAS_FILTER_NOTCH 3
+#define GAS_FILTER_LOWSHELF 4
+#define GAS_FILTER_HIGHSHELF 5
+#define GAS_FILTER_BANDLIMIT 6 /* [ENGINE] AudioEffectBandLimitFilter: `resonance` is the band's other edge (> 0) */
+/* gas_fx_filter_settings.db: [ENGINE] AudioEffectFilter::FilterDB, db + 1 cascaded stages */
+#define GAS_FILTER_6DB 0
+#define GAS_FILTER_12DB 1
+#define GAS_FILTER_18DB 2
+#define GAS_FILTER_24DB 3
 
 /* [ENGINE] AudioEffectDistortion::Mode */
 #define GAS_DISTORTION_CLIP 0
@@ -323,6 +341,22 @@ typedef struct gas_fx_stereo_settings {
 	float limiter_soft_clip_ratio[GAS_MAX_EFFECTS]; /* 3 .. 20, default 10 (carried; the engine's process never reads it) */
 } gas_fx_stereo_settings;
 
+/* Settings of the GAS_FX_FILTER effects of one playback, by chain position: position j is read only when effect j of the
+ * playback's chain is GAS_FX_FILTER.  Read once per block: the engine's set_cutoff, set_gain, set_resonance,
+ * set_stages(db + 1), then every processor snaps to the new coefficients (no ramp).  Stages at index db + 1 and above
+ * are not run and keep their history, so `db` may change between blocks.  A slot's settings start at the defaults
+ * below when it is allocated.  gas_fx_filter_settings_publish refuses, at any position, used or not: a `type` or `db`
+ * that is none of the constants above, anything not finite or outside the engine's property ranges, and -- a deviation
+ * from the engine, whose band-limit coefficients are NaN there -- GAS_FILTER_BANDLIMIT with resonance <= 0. */
+typedef struct gas_fx_filter_settings {
+	int32_t type[GAS_MAX_EFFECTS]; /* GAS_FILTER_*, default LOWPASS */
+	int32_t db[GAS_MAX_EFFECTS]; /* GAS_FILTER_6DB .. _24DB, default 6 dB */
+	float cutoff_hz[GAS_MAX_EFFECTS]; /* 1 .. 20500, default 2000 */
+	float resonance[GAS_MAX_EFFECTS]; /* 0 .. 1, default 0.5 */
+	float gain[GAS_MAX_EFFECTS]; /* 0 .. 4, default 1 (linear; the shelf types) */
+	uint32_t reserved[12];
+} gas_fx_filter_settings;
+
 /* Per-kernel device timing collected with HIP events on the context stream. */
 typedef struct gas_profile {
 	uint64_t launches; /* timed launches of the dominant kernel since the last reset */
@@ -401,6 +435,10 @@ int gas_fx_mod_settings_publish(gas_ctx *ctx, const uint32_t *slots, const gas_f
  * 148 staging) and 148 bytes of pinned host memory per slot of max_sources -- 2.4 MB and 1.2 MB at 8192 slots, 19 MB
  * and 9.7 MB at 65 536, 2.4 GB and 1.2 GB at 8.1 M. */
 int gas_fx_stereo_settings_publish(gas_ctx *ctx, const uint32_t *slots, const gas_fx_stereo_settings *settings, uint32_t n);
+/* The same for gas_fx_filter_settings: latest wins, snapshotted at the start of the next gas_process_block, physics
+ * thread.  Settings refused by the rules given at gas_fx_filter_settings (at any position) are
+ * GAS_ERR_INVALID_ARGUMENT, and nothing of the call is taken. */
+int gas_fx_filter_settings_publish(gas_ctx *ctx, const uint32_t *slots, const gas_fx_filter_settings *settings, uint32_t n);
 
 /* ---- delay memory of the GAS_FX_DELAY / GAS_FX_REVERB instances ("lines") ---------------------------------------
  * Every GAS_FX_DELAY of a chain holds one delay line, every GAS_FX_REVERB one reverb line, from two device pools the
@@ -467,6 +505,20 @@ int gas_ctx_reserve_fx_mod(gas_ctx *ctx, uint32_t chorus_lines, uint32_t phaser_
  * gas_source_reset.  The reservation is independent of gas_ctx_reserve_fx_lines, gas_ctx_reserve_fx_eq and
  * gas_ctx_reserve_fx_mod: no call touches another's pools.  A gas_multi caller reserves per shard (gas_multi_shard). */
 int gas_ctx_reserve_fx_stereo(gas_ctx *ctx, uint32_t enhance_rings);
+
+/* ---- state of the GAS_FX_FILTER instances ("banks") ----------------------------------------------------------------
+ * Every GAS_FX_FILTER of a chain holds one bank ([4 stages][a1, a2, b1, b2][2 ears] floats, 128 bytes: the history of
+ * the engine's four processors per ear) from a device pool the caller sizes here, with the same contract as
+ * gas_ctx_reserve_fx_eq: main thread, never concurrently with gas_process_block; the pool, the slot -> bank table, the
+ * device settings table and a pinned upload buffer are allocated here and nothing on the audio thread (a context that
+ * never reserves pays nothing); 0 releases everything; while any bank is held the call is GAS_ERR_INVALID_ARGUMENT.
+ * gas_source_alloc takes one bank per GAS_FX_FILTER of the chain: with no pool reserved it is
+ * GAS_ERR_UNSUPPORTED_CHAIN, with too few free entries in any pool the chain needs (these, the delay and reverb lines,
+ * the EQ banks, the chorus lines, the phaser banks, the rings) GAS_ERR_OUT_OF_SLOTS, and nothing is taken.  Banks go
+ * back with the slot at the next block boundary after gas_source_free; they are zeroed whenever they change hands and
+ * by gas_source_reset.  The reservation is independent of the other gas_ctx_reserve_fx_* calls: no call touches
+ * another's pools.  A gas_multi caller reserves per shard (gas_multi_shard). */
+int gas_ctx_reserve_fx_filter(gas_ctx *ctx, uint32_t banks);
 
 /* ---- NEW AudioSpatializerHRTF resource: hrir is [dirs][2 ears][taps] f32, taps <= 256 */
 int gas_hrtf_load(gas_ctx *ctx, const float *hrir, uint32_t dirs, uint32_t taps);

@@ -12,6 +12,7 @@
 #include <cstring>
 #include <new>
 
+#include "gas_fx_dyn_check.h"
 #include "gas_fx_eq_check.h"
 #include "gas_fx_filter_check.h"
 #include "gas_fx_line_check.h"
@@ -66,6 +67,24 @@ struct ChainRange {
 };
 
 constexpr uint32_t PROFILE_EVENTS = 4096;
+
+// The pooled effect families, in the order their uploads are flushed; k_fx_families describes them.
+enum { FX_LINES = 0, FX_EQ, FX_FILTER, FX_MOD, FX_STEREO, FX_FAMILIES };
+
+// Host side of one pooled family: pool sizes and free entries (alloc_mu), each slot's entries by chain position (written
+// under alloc_mu and params_mu), the settings mirror and what the next flush uploads (params_mu):
+// [m settings][m {slot, entry[4]}][z zero records] through one pinned staging buffer.
+struct FxFamily {
+	uint32_t cap[2] = { 0, 0 };
+	std::vector<uint32_t> free[2];
+	std::vector<std::array<int32_t, GAS_MAX_EFFECTS>> h_of;
+	std::vector<unsigned char> h_settings; // [max_sources] settings PODs, latest published value
+	std::vector<uint8_t> dirty_flag;
+	std::vector<uint32_t> dirty_list;
+	std::vector<uint32_t> zero_list; // zero records, each entry at most once (zero_pending)
+	std::vector<uint8_t> zero_pending[2]; // [pool][entry]: queued in zero_list
+	unsigned char *h_upload = nullptr, *d_upload = nullptr;
+};
 
 } // namespace
 
@@ -135,69 +154,10 @@ struct gas_ctx {
 	std::vector<uint32_t> dyn_dirty_list;
 	unsigned char *h_dyn_upload = nullptr; // pinned, [max_sources] settings then [max_sources] slots
 	unsigned char *d_dyn_upload = nullptr;
-	// GAS_FX_DELAY / GAS_FX_REVERB lines (gas_ctx_reserve_fx_lines): pool sizes and free lines (alloc_mu), each slot's
-	// lines by chain position (written under alloc_mu and params_mu), settings mirror and what the next flush uploads
-	// (params_mu): [m settings][m {slot, line[4]}][z {kind, line}] through one pinned staging buffer
+	// the pooled effect families (gas_ctx_reserve_fx_*), and what their reservations derive from the mix rate
+	FxFamily fx[FX_FAMILIES];
 	gas_line_geo line_geo{};
-	uint32_t line_cap[2] = { 0, 0 }; // delay, reverb
-	std::vector<uint32_t> line_free[2];
-	std::vector<std::array<int32_t, GAS_MAX_EFFECTS>> h_line_of;
-	std::vector<gas_fx_line_settings> h_line;
-	std::vector<uint8_t> line_dirty_flag;
-	std::vector<uint32_t> line_dirty_list;
-	std::vector<uint32_t> line_zero_list; // {kind, line} pairs, each line at most once (line_zero_pending)
-	std::vector<uint8_t> line_zero_pending[2]; // [pool][line]: queued in line_zero_list
-	unsigned char *h_line_upload = nullptr, *d_line_upload = nullptr;
-	// GAS_FX_EQ6 / _EQ10 / _EQ21 banks (gas_ctx_reserve_fx_eq), kept like the lines: pool size and free banks (alloc_mu),
-	// each slot's banks by chain position (written under alloc_mu and params_mu), settings mirror and what the next flush
-	// uploads (params_mu): [m settings][m {slot, bank[4]}][z bank] through one pinned staging buffer
-	uint32_t eq_cap = 0;
-	std::vector<uint32_t> eq_free;
-	std::vector<std::array<int32_t, GAS_MAX_EFFECTS>> h_eq_of;
-	std::vector<gas_fx_eq_settings> h_eq;
-	std::vector<uint8_t> eq_dirty_flag;
-	std::vector<uint32_t> eq_dirty_list;
-	std::vector<uint32_t> eq_zero_list; // banks, each at most once (eq_zero_pending)
-	std::vector<uint8_t> eq_zero_pending; // [bank]: queued in eq_zero_list
-	unsigned char *h_eq_upload = nullptr, *d_eq_upload = nullptr;
 	gas_eq_coefs eq_coefs[3] = {}; // EQ6, EQ10, EQ21 at the mix rate (make_eq_coefs)
-	// GAS_FX_FILTER banks (gas_ctx_reserve_fx_filter), kept exactly like the EQ banks: [m settings][m {slot, bank[4]}]
-	// [z bank] through one pinned staging buffer
-	uint32_t flt_cap = 0;
-	std::vector<uint32_t> flt_free;
-	std::vector<std::array<int32_t, GAS_MAX_EFFECTS>> h_flt_of;
-	std::vector<gas_fx_filter_settings> h_flt;
-	std::vector<uint8_t> flt_dirty_flag;
-	std::vector<uint32_t> flt_dirty_list;
-	std::vector<uint32_t> flt_zero_list; // banks, each at most once (flt_zero_pending)
-	std::vector<uint8_t> flt_zero_pending; // [bank]: queued in flt_zero_list
-	unsigned char *h_flt_upload = nullptr, *d_flt_upload = nullptr;
-	// GAS_FX_CHORUS lines and GAS_FX_PHASER banks (gas_ctx_reserve_fx_mod), kept like the delay and reverb lines: pool
-	// sizes and free entries (alloc_mu), each slot's entries by chain position (written under alloc_mu and params_mu),
-	// settings mirror and what the next flush uploads (params_mu): [m settings][m {slot, index[4]}][z {kind, index}]
-	// through one pinned staging buffer
-	uint32_t mod_cap[2] = { 0, 0 }; // chorus lines, phaser banks
-	std::vector<uint32_t> mod_free[2];
-	std::vector<std::array<int32_t, GAS_MAX_EFFECTS>> h_mod_of;
-	std::vector<gas_fx_mod_settings> h_mod;
-	std::vector<uint8_t> mod_dirty_flag;
-	std::vector<uint32_t> mod_dirty_list;
-	std::vector<uint32_t> mod_zero_list; // {kind, index} pairs, each entry at most once (mod_zero_pending)
-	std::vector<uint8_t> mod_zero_pending[2]; // [pool][index]: queued in mod_zero_list
-	unsigned char *h_mod_upload = nullptr, *d_mod_upload = nullptr;
-	// GAS_FX_PANNER / _STEREO_ENHANCE / _LIMITER settings and the stereo-enhance rings (gas_ctx_reserve_fx_stereo), kept
-	// like the chorus lines; the settings mirror, the slot -> ring table and the staging buffer exist from gas_ctx_create
-	// on (panner and limiter need no reservation), the pool and the staging buffer's [z ring] section from the
-	// reservation: [m settings][m {slot, ring[4]}][z ring]
-	uint32_t ring_cap = 0;
-	std::vector<uint32_t> ring_free;
-	std::vector<std::array<int32_t, GAS_MAX_EFFECTS>> h_stereo_of;
-	std::vector<gas_fx_stereo_settings> h_stereo;
-	std::vector<uint8_t> stereo_dirty_flag;
-	std::vector<uint32_t> stereo_dirty_list;
-	std::vector<uint32_t> ring_zero_list; // each ring at most once (ring_zero_pending)
-	std::vector<uint8_t> ring_zero_pending; // [ring]: queued in ring_zero_list
-	unsigned char *h_stereo_upload = nullptr, *d_stereo_upload = nullptr;
 
 	// plain [HRTF] group of the cached list (k_hrtf_uni): which entries need their exact peak
 	uint32_t *h_peak_bits = nullptr, *d_peak_bits = nullptr; // two halves of (max_sources + 31) / 32 words: bit k = entry k of the plain-[HRTF] group / of the staged group
@@ -403,15 +363,6 @@ gas_fx_dyn_settings fx_dyn_settings_defaults() {
 	return d;
 }
 
-bool fx_dyn_settings_valid(const gas_fx_dyn_settings &d) {
-	for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
-		if (d.distortion_mode[j] < GAS_DISTORTION_CLIP || d.distortion_mode[j] > GAS_DISTORTION_WAVESHAPE || !(d.compressor_ratio[j] > 0.0f) || !(d.compressor_attack_us[j] > 0.0f) || !(d.compressor_release_ms[j] > 0.0f)) {
-			return false;
-		}
-	}
-	return true;
-}
-
 // [ENGINE] AudioEffectDelay / AudioEffectReverb resource defaults
 gas_fx_line_settings fx_line_settings_defaults() {
 	gas_fx_line_settings d;
@@ -528,6 +479,10 @@ gas_eq_coefs make_eq_coefs(int kind, float mix_rate) {
 
 inline bool is_eq(int kind) {
 	return kind >= GAS_FX_EQ6 && kind <= GAS_FX_EQ21;
+}
+
+gas_fx_eq_settings fx_eq_settings_defaults() {
+	return gas_fx_eq_settings{}; // 0 dB everywhere
 }
 
 inline int mod_pool_of(int kind) { // 0 chorus line, 1 phaser bank, -1 neither
@@ -1220,6 +1175,14 @@ int run_hrtf_batch(gas_ctx *c, const std::vector<gas_ctx::Deferred> &blocks, uin
 	return GAS_OK;
 }
 
+// Marks row s of a slot-indexed host mirror for the next flush; params_mu held.
+inline void mark_dirty(std::vector<uint8_t> &flag, std::vector<uint32_t> &list, uint32_t s) {
+	if (!flag[s]) {
+		flag[s] = 1;
+		list.push_back(s);
+	}
+}
+
 // Scatter a deferred device-side publish into the table (list unchanged since it was recorded).
 int flush_pending_params(gas_ctx *c) {
 	if (!c->pending_params) {
@@ -1287,420 +1250,433 @@ int flush_fx_dyn_settings(gas_ctx *c) {
 	return GAS_OK;
 }
 
-// gas_fx_line_settings_publish's rows, new slot -> line entries and lines to zero: one copy of
-// [m settings][m {slot, line[4]}][z {kind, line}], one scatter, one zeroing launch.
-int flush_fx_lines(gas_ctx *c) {
-	if (!c->h_line_upload) {
+// ---------------------------------------------------------------------------------------------------------------
+// The pooled effect families: one life cycle -- reserve, hand out, publish, flush, reset, free,
+// release -- over a description of what differs between them.
+// ---------------------------------------------------------------------------------------------------------------
+
+// A family's members of gas_dev_state.
+struct FxDev {
+	void *settings = nullptr; // [max_sources] settings PODs, by chain position
+	int32_t *of = nullptr; // [GAS_MAX_EFFECTS][max_sources] pool entry of chain position j, -1: none
+	float *pool[2] = { nullptr, nullptr };
+};
+
+template <class S, S *gas_dev_state::*Settings, int32_t *gas_dev_state::*Of, float *gas_dev_state::*Pool0, float *gas_dev_state::*Pool1 = nullptr>
+struct FxDevOf {
+	static FxDev get(const gas_dev_state &st) {
+		FxDev d;
+		d.settings = st.*Settings;
+		d.of = st.*Of;
+		d.pool[0] = st.*Pool0;
+		if constexpr (Pool1 != nullptr) {
+			d.pool[1] = st.*Pool1;
+		}
+		return d;
+	}
+	static void set(gas_dev_state &st, const FxDev &d) {
+		st.*Settings = static_cast<S *>(d.settings);
+		st.*Of = d.of;
+		st.*Pool0 = d.pool[0];
+		if constexpr (Pool1 != nullptr) {
+			st.*Pool1 = d.pool[1];
+		}
+	}
+};
+
+template <class S, S (*Defaults)()>
+void fx_defaults_of(void *row) {
+	*static_cast<S *>(row) = Defaults();
+}
+
+template <class S, bool (*Valid)(const S &)>
+bool fx_valid_of(const void *row) {
+	return Valid(*static_cast<const S *>(row));
+}
+
+struct FxFamilyDesc {
+	const char *name; // gas_ctx_reserve_fx_<name>, for its error strings
+	uint32_t pod_bytes; // the settings POD
+	void (*defaults)(void *row); // the engine's resource defaults
+	bool (*valid)(const void *row); // gas_fx_*_check.h
+	int pools; // 1: a zero record is [entry]; 2: [kind, entry]
+	int (*pool_of)(int kind); // the pool an effect kind takes its entry from, -1: none
+	bool (*has_kind)(int kind); // the kinds whose settings the POD carries
+	bool resident; // settings, table and staging buffer exist from gas_ctx_create on, the reservation adds the pool
+	FxDev (*get)(const gas_dev_state &st);
+	void (*set)(gas_dev_state &st, const FxDev &d);
+	int (*check)(const gas_ctx *c, const uint32_t *counts); // what a reservation asks of the context (nullptr: nothing)
+	size_t (*entry_floats)(const gas_ctx *c, int pool);
+	void (*extras)(gas_ctx *c, bool reserved); // what the kernels need besides the pools: set by a reservation, dropped by a release (nullptr: nothing)
+	hipError_t (*zero)(const gas_ctx *c, const uint32_t *records, uint32_t z); // the zeroing launch of a flush
+};
+
+// [ENGINE] AudioEffectChorus's ring: 1 << bitlength((int)(0.24 sr)) frames; AudioEffectStereoEnhance's: of
+// (int)((50 + 2) / 1000 sr)
+uint32_t ring_frames(uint32_t n) {
+	uint32_t bits = 0;
+	while (bits < 31 && (n >> bits) != 0) {
+		bits++;
+	}
+	return 1u << bits;
+}
+
+uint32_t chorus_ring_frames(const gas_ctx *c) {
+	return ring_frames((uint32_t)(int)(0.24 * (double)c->cfg.mix_rate));
+}
+
+uint32_t enhance_ring_frames(const gas_ctx *c) {
+	return ring_frames((uint32_t)(int)((50.0 + 2.0) / 1000.0 * (double)c->cfg.mix_rate));
+}
+
+int lines_check(const gas_ctx *c, const uint32_t *counts) {
+	const double sr = (double)c->cfg.mix_rate;
+	const long F = (long)c->cfg.frames;
+	// the reverb kernel's predelay and comb reads must not reach the block's own writes
+	return counts[1] > 0 && (lrint(0.02 * sr) < F || lrint(0.025306122 * sr) < F) ? GAS_ERR_INVALID_ARGUMENT : GAS_OK;
+}
+
+int mod_check(const gas_ctx *c, const uint32_t *counts) {
+	const double sr = (double)c->cfg.mix_rate;
+	// one block's ring writes must not overtake its own oldest read
+	return counts[0] > 0 && (long)chorus_ring_frames(c) < lrint(0.05 * sr) + 2L * (int)(0.02 * sr) + 12 + (long)c->cfg.frames ? GAS_ERR_INVALID_ARGUMENT : GAS_OK;
+}
+
+int stereo_check(const gas_ctx *c, const uint32_t *counts) {
+	const uint32_t R = enhance_ring_frames(c);
+	return counts[0] > 0 && (R < c->cfg.frames || R < 4) ? GAS_ERR_INVALID_ARGUMENT : GAS_OK; // two frames of one block would share a ring entry
+}
+
+const FxFamilyDesc k_fx_families[FX_FAMILIES] = {
+	{ "lines", sizeof(gas_fx_line_settings), fx_defaults_of<gas_fx_line_settings, fx_line_settings_defaults>, fx_valid_of<gas_fx_line_settings, gas_fx_line_settings_valid>, 2, line_pool_of,
+			[](int kind) { return line_pool_of(kind) >= 0; }, false,
+			FxDevOf<gas_fx_line_settings, &gas_dev_state::line_settings, &gas_dev_state::line_of, &gas_dev_state::delay_pool, &gas_dev_state::reverb_pool>::get,
+			FxDevOf<gas_fx_line_settings, &gas_dev_state::line_settings, &gas_dev_state::line_of, &gas_dev_state::delay_pool, &gas_dev_state::reverb_pool>::set, lines_check,
+			[](const gas_ctx *c, int pool) { const gas_line_geo g = make_line_geo(c->cfg.mix_rate); return pool == 0 ? g.delay_floats : g.reverb_floats; },
+			[](gas_ctx *c, bool reserved) {
+				if (reserved) {
+					c->line_geo = make_line_geo(c->cfg.mix_rate);
+				}
+			},
+			[](const gas_ctx *c, const uint32_t *r, uint32_t z) { return gas_launch_zero_lines(c->stream, c->st, c->line_geo, r, z); } },
+	{ "eq", sizeof(gas_fx_eq_settings), fx_defaults_of<gas_fx_eq_settings, fx_eq_settings_defaults>, fx_valid_of<gas_fx_eq_settings, gas_fx_eq_settings_valid>, 1,
+			[](int kind) { return is_eq(kind) ? 0 : -1; }, is_eq, false,
+			FxDevOf<gas_fx_eq_settings, &gas_dev_state::eq_settings, &gas_dev_state::eq_of, &gas_dev_state::eq_pool>::get,
+			FxDevOf<gas_fx_eq_settings, &gas_dev_state::eq_settings, &gas_dev_state::eq_of, &gas_dev_state::eq_pool>::set, nullptr,
+			[](const gas_ctx *, int) { return (size_t)GAS_EQ_BANK_FLOATS; },
+			[](gas_ctx *c, bool reserved) {
+				for (int k = 0; k < 3 && reserved; k++) {
+					c->eq_coefs[k] = make_eq_coefs(GAS_FX_EQ6 + k, c->cfg.mix_rate);
+				}
+			},
+			[](const gas_ctx *c, const uint32_t *r, uint32_t z) { return gas_launch_zero_banks(c->stream, c->st, r, z); } },
+	{ "filter", sizeof(gas_fx_filter_settings), fx_defaults_of<gas_fx_filter_settings, gas_fx_filter_settings_defaults>, fx_valid_of<gas_fx_filter_settings, gas_fx_filter_settings_valid>, 1,
+			[](int kind) { return kind == GAS_FX_FILTER ? 0 : -1; }, [](int kind) { return kind == GAS_FX_FILTER; }, false,
+			FxDevOf<gas_fx_filter_settings, &gas_dev_state::flt_settings, &gas_dev_state::flt_of, &gas_dev_state::flt_pool>::get,
+			FxDevOf<gas_fx_filter_settings, &gas_dev_state::flt_settings, &gas_dev_state::flt_of, &gas_dev_state::flt_pool>::set, nullptr,
+			[](const gas_ctx *, int) { return (size_t)GAS_FILTER_BANK_FLOATS; }, nullptr,
+			[](const gas_ctx *c, const uint32_t *r, uint32_t z) { return gas_launch_zero_filter_banks(c->stream, c->st, r, z); } },
+	{ "mod", sizeof(gas_fx_mod_settings), fx_defaults_of<gas_fx_mod_settings, gas_fx_mod_settings_defaults>, fx_valid_of<gas_fx_mod_settings, gas_fx_mod_settings_valid>, 2, mod_pool_of,
+			[](int kind) { return mod_pool_of(kind) >= 0; }, false,
+			FxDevOf<gas_fx_mod_settings, &gas_dev_state::mod_settings, &gas_dev_state::mod_of, &gas_dev_state::chorus_pool, &gas_dev_state::phaser_pool>::get,
+			FxDevOf<gas_fx_mod_settings, &gas_dev_state::mod_settings, &gas_dev_state::mod_of, &gas_dev_state::chorus_pool, &gas_dev_state::phaser_pool>::set, mod_check,
+			[](const gas_ctx *c, int pool) { return pool == 0 ? GAS_CHORUS_HEADER + 2 * (size_t)chorus_ring_frames(c) : (size_t)GAS_PHASER_BANK_FLOATS; },
+			[](gas_ctx *c, bool reserved) { c->st.chorus_mask = reserved ? chorus_ring_frames(c) - 1 : 0; },
+			[](const gas_ctx *c, const uint32_t *r, uint32_t z) { return gas_launch_zero_mod(c->stream, c->st, r, z); } },
+	// panner and limiter need no reservation: only the stereo enhance takes a ring
+	{ "stereo", sizeof(gas_fx_stereo_settings), fx_defaults_of<gas_fx_stereo_settings, gas_fx_stereo_settings_defaults>, fx_valid_of<gas_fx_stereo_settings, gas_fx_stereo_settings_valid>, 1,
+			[](int kind) { return kind == GAS_FX_STEREO_ENHANCE ? 0 : -1; }, is_stereo, true,
+			FxDevOf<gas_fx_stereo_settings, &gas_dev_state::stereo_settings, &gas_dev_state::stereo_of, &gas_dev_state::enhance_pool>::get,
+			FxDevOf<gas_fx_stereo_settings, &gas_dev_state::stereo_settings, &gas_dev_state::stereo_of, &gas_dev_state::enhance_pool>::set, stereo_check,
+			[](const gas_ctx *c, int) { return GAS_ENHANCE_HEADER + (size_t)enhance_ring_frames(c); },
+			[](gas_ctx *c, bool reserved) { c->st.enhance_mask = reserved ? enhance_ring_frames(c) - 1 : 0; },
+			[](const gas_ctx *c, const uint32_t *r, uint32_t z) { return gas_launch_zero_rings(c->stream, c->st, r, z); } },
+};
+
+std::array<int32_t, GAS_MAX_EFFECTS> fx_no_entries() {
+	std::array<int32_t, GAS_MAX_EFFECTS> none;
+	none.fill(-1);
+	return none;
+}
+
+// What a flush uploads: one copy of [m settings][m {slot, entry[4]}][z zero records], one scatter, one zeroing launch.
+int fx_flush(gas_ctx *c, int f) {
+	FxFamily &p = c->fx[f];
+	const FxFamilyDesc &d = k_fx_families[f];
+	if (!d.resident && !p.h_upload) {
 		return GAS_OK;
 	}
+	const size_t pod = d.pod_bytes;
+	const uint32_t w = (uint32_t)d.pools; // words of a zero record
 	uint32_t m = 0, z = 0;
 	{
 		std::lock_guard<std::mutex> lk(c->params_mu);
-		m = (uint32_t)c->line_dirty_list.size();
-		z = (uint32_t)(c->line_zero_list.size() / 2);
+		m = (uint32_t)p.dirty_list.size();
+		z = (uint32_t)p.zero_list.size() / w;
 		if (m == 0 && z == 0) {
 			return GAS_OK;
 		}
-		gas_fx_line_settings *hs = reinterpret_cast<gas_fx_line_settings *>(c->h_line_upload);
-		uint32_t *hsl = reinterpret_cast<uint32_t *>(c->h_line_upload + (size_t)m * sizeof(gas_fx_line_settings));
-		for (uint32_t i = 0; i < m; i++) {
-			const uint32_t s = c->line_dirty_list[i];
-			hs[i] = c->h_line[s];
-			hsl[i * (1 + GAS_MAX_EFFECTS)] = s;
-			for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
-				hsl[i * (1 + GAS_MAX_EFFECTS) + 1 + j] = (uint32_t)c->h_line_of[s][j];
-			}
-			c->line_dirty_flag[s] = 0;
-		}
-		std::memcpy(hsl + (size_t)m * (1 + GAS_MAX_EFFECTS), c->line_zero_list.data(), (size_t)z * 2 * sizeof(uint32_t));
-		for (uint32_t i = 0; i < z; i++) {
-			c->line_zero_pending[line_pool_of((int)c->line_zero_list[2 * i])][c->line_zero_list[2 * i + 1]] = 0;
-		}
-		c->line_dirty_list.clear();
-		c->line_zero_list.clear();
-	}
-	const size_t zoff = (size_t)m * (sizeof(gas_fx_line_settings) + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t));
-	GAS_HIP(c, hipMemcpyAsync(c->d_line_upload, c->h_line_upload, zoff + (size_t)z * 2 * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-	GAS_HIP(c, gas_launch_scatter_line(c->stream, c->st, reinterpret_cast<const gas_fx_line_settings *>(c->d_line_upload), reinterpret_cast<const uint32_t *>(c->d_line_upload + (size_t)m * sizeof(gas_fx_line_settings)), m));
-	GAS_HIP(c, gas_launch_zero_lines(c->stream, c->st, c->line_geo, reinterpret_cast<const uint32_t *>(c->d_line_upload + zoff), z));
-	GAS_HIP(c, hipStreamSynchronize(c->stream)); // the pinned staging buffer is reused by the next flush
-	return GAS_OK;
-}
-
-// Marks slot s's settings row (and its line table row) for the next flush; params_mu held.
-void line_mark_dirty(gas_ctx *c, uint32_t s) {
-	if (!c->line_dirty_flag[s]) {
-		c->line_dirty_flag[s] = 1;
-		c->line_dirty_list.push_back(s);
-	}
-}
-
-// Queues the zeroing of slot s's lines (chain signature sig), each line at most once until the next flush, so the
-// queue never holds more pairs than the pools have lines (the upload buffer's zero section); params_mu held.
-void line_queue_zero(gas_ctx *c, uint32_t s, uint32_t sig) {
-	for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
-		const int kind = (sig >> (8 * j)) & 0xff;
-		const int pool = line_pool_of(kind);
-		const int32_t line = c->h_line_of[s][j];
-		if (pool >= 0 && line >= 0 && !c->line_zero_pending[pool][line]) {
-			c->line_zero_pending[pool][line] = 1;
-			c->line_zero_list.push_back((uint32_t)kind);
-			c->line_zero_list.push_back((uint32_t)line);
-		}
-	}
-}
-
-void release_fx_lines(gas_ctx *c) {
-	(void)hipFree(c->st.delay_pool);
-	(void)hipFree(c->st.reverb_pool);
-	(void)hipFree(c->st.line_of);
-	(void)hipFree(c->st.line_settings);
-	(void)hipFree(c->d_line_upload);
-	(void)hipHostFree(c->h_line_upload);
-	c->st.delay_pool = c->st.reverb_pool = nullptr;
-	c->st.line_of = nullptr;
-	c->st.line_settings = nullptr;
-	c->d_line_upload = c->h_line_upload = nullptr;
-	c->line_cap[0] = c->line_cap[1] = 0;
-	c->line_free[0].clear();
-	c->line_free[1].clear();
-	c->h_line_of.clear();
-	c->h_line.clear();
-	c->line_dirty_flag.clear();
-	c->line_dirty_list.clear();
-	c->line_zero_list.clear();
-	c->line_zero_pending[0].clear();
-	c->line_zero_pending[1].clear();
-}
-
-// gas_fx_eq_settings_publish's rows, new slot -> bank entries and banks to zero: one copy of
-// [m settings][m {slot, bank[4]}][z bank], one scatter, one zeroing launch.
-int flush_fx_eq(gas_ctx *c) {
-	if (!c->h_eq_upload) {
-		return GAS_OK;
-	}
-	uint32_t m = 0, z = 0;
-	{
-		std::lock_guard<std::mutex> lk(c->params_mu);
-		m = (uint32_t)c->eq_dirty_list.size();
-		z = (uint32_t)c->eq_zero_list.size();
-		if (m == 0 && z == 0) {
-			return GAS_OK;
-		}
-		gas_fx_eq_settings *hs = reinterpret_cast<gas_fx_eq_settings *>(c->h_eq_upload);
-		uint32_t *hsb = reinterpret_cast<uint32_t *>(c->h_eq_upload + (size_t)m * sizeof(gas_fx_eq_settings));
-		for (uint32_t i = 0; i < m; i++) {
-			const uint32_t s = c->eq_dirty_list[i];
-			hs[i] = c->h_eq[s];
-			hsb[i * (1 + GAS_MAX_EFFECTS)] = s;
-			for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
-				hsb[i * (1 + GAS_MAX_EFFECTS) + 1 + j] = (uint32_t)c->h_eq_of[s][j];
-			}
-			c->eq_dirty_flag[s] = 0;
-		}
-		std::memcpy(hsb + (size_t)m * (1 + GAS_MAX_EFFECTS), c->eq_zero_list.data(), (size_t)z * sizeof(uint32_t));
-		for (uint32_t i = 0; i < z; i++) {
-			c->eq_zero_pending[c->eq_zero_list[i]] = 0;
-		}
-		c->eq_dirty_list.clear();
-		c->eq_zero_list.clear();
-	}
-	const size_t zoff = (size_t)m * (sizeof(gas_fx_eq_settings) + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t));
-	GAS_HIP(c, hipMemcpyAsync(c->d_eq_upload, c->h_eq_upload, zoff + (size_t)z * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-	GAS_HIP(c, gas_launch_scatter_eq(c->stream, c->st, reinterpret_cast<const gas_fx_eq_settings *>(c->d_eq_upload), reinterpret_cast<const uint32_t *>(c->d_eq_upload + (size_t)m * sizeof(gas_fx_eq_settings)), m));
-	GAS_HIP(c, gas_launch_zero_banks(c->stream, c->st, reinterpret_cast<const uint32_t *>(c->d_eq_upload + zoff), z));
-	GAS_HIP(c, hipStreamSynchronize(c->stream)); // the pinned staging buffer is reused by the next flush
-	return GAS_OK;
-}
-
-// Marks slot s's EQ settings row (and its bank table row) for the next flush; params_mu held.
-void eq_mark_dirty(gas_ctx *c, uint32_t s) {
-	if (!c->eq_dirty_flag[s]) {
-		c->eq_dirty_flag[s] = 1;
-		c->eq_dirty_list.push_back(s);
-	}
-}
-
-// Queues the zeroing of slot s's banks (chain signature sig), each bank at most once until the next flush, so the queue
-// never holds more entries than the pool has banks (the upload buffer's zero section); params_mu held.
-void eq_queue_zero(gas_ctx *c, uint32_t s, uint32_t sig) {
-	for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
-		const int32_t bank = c->h_eq_of[s][j];
-		if (is_eq((sig >> (8 * j)) & 0xff) && bank >= 0 && !c->eq_zero_pending[bank]) {
-			c->eq_zero_pending[bank] = 1;
-			c->eq_zero_list.push_back((uint32_t)bank);
-		}
-	}
-}
-
-void release_fx_eq(gas_ctx *c) {
-	(void)hipFree(c->st.eq_pool);
-	(void)hipFree(c->st.eq_of);
-	(void)hipFree(c->st.eq_settings);
-	(void)hipFree(c->d_eq_upload);
-	(void)hipHostFree(c->h_eq_upload);
-	c->st.eq_pool = nullptr;
-	c->st.eq_of = nullptr;
-	c->st.eq_settings = nullptr;
-	c->d_eq_upload = c->h_eq_upload = nullptr;
-	c->eq_cap = 0;
-	c->eq_free.clear();
-	c->h_eq_of.clear();
-	c->h_eq.clear();
-	c->eq_dirty_flag.clear();
-	c->eq_dirty_list.clear();
-	c->eq_zero_list.clear();
-	c->eq_zero_pending.clear();
-}
-
-// gas_fx_filter_settings_publish's rows, new slot -> bank entries and banks to zero: one copy of
-// [m settings][m {slot, bank[4]}][z bank], one scatter, one zeroing launch.
-int flush_fx_filter(gas_ctx *c) {
-	if (!c->h_flt_upload) {
-		return GAS_OK;
-	}
-	uint32_t m = 0, z = 0;
-	{
-		std::lock_guard<std::mutex> lk(c->params_mu);
-		m = (uint32_t)c->flt_dirty_list.size();
-		z = (uint32_t)c->flt_zero_list.size();
-		if (m == 0 && z == 0) {
-			return GAS_OK;
-		}
-		gas_fx_filter_settings *hs = reinterpret_cast<gas_fx_filter_settings *>(c->h_flt_upload);
-		uint32_t *hsb = reinterpret_cast<uint32_t *>(c->h_flt_upload + (size_t)m * sizeof(gas_fx_filter_settings));
-		for (uint32_t i = 0; i < m; i++) {
-			const uint32_t s = c->flt_dirty_list[i];
-			hs[i] = c->h_flt[s];
-			hsb[i * (1 + GAS_MAX_EFFECTS)] = s;
-			for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
-				hsb[i * (1 + GAS_MAX_EFFECTS) + 1 + j] = (uint32_t)c->h_flt_of[s][j];
-			}
-			c->flt_dirty_flag[s] = 0;
-		}
-		std::memcpy(hsb + (size_t)m * (1 + GAS_MAX_EFFECTS), c->flt_zero_list.data(), (size_t)z * sizeof(uint32_t));
-		for (uint32_t i = 0; i < z; i++) {
-			c->flt_zero_pending[c->flt_zero_list[i]] = 0;
-		}
-		c->flt_dirty_list.clear();
-		c->flt_zero_list.clear();
-	}
-	const size_t zoff = (size_t)m * (sizeof(gas_fx_filter_settings) + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t));
-	GAS_HIP(c, hipMemcpyAsync(c->d_flt_upload, c->h_flt_upload, zoff + (size_t)z * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-	GAS_HIP(c, gas_launch_scatter_filter(c->stream, c->st, reinterpret_cast<const gas_fx_filter_settings *>(c->d_flt_upload), reinterpret_cast<const uint32_t *>(c->d_flt_upload + (size_t)m * sizeof(gas_fx_filter_settings)), m));
-	GAS_HIP(c, gas_launch_zero_filter_banks(c->stream, c->st, reinterpret_cast<const uint32_t *>(c->d_flt_upload + zoff), z));
-	GAS_HIP(c, hipStreamSynchronize(c->stream)); // the pinned staging buffer is reused by the next flush
-	return GAS_OK;
-}
-
-// Marks slot s's GAS_FX_FILTER settings row (and its bank table row) for the next flush; params_mu held.
-void flt_mark_dirty(gas_ctx *c, uint32_t s) {
-	if (!c->flt_dirty_flag[s]) {
-		c->flt_dirty_flag[s] = 1;
-		c->flt_dirty_list.push_back(s);
-	}
-}
-
-// Queues the zeroing of slot s's banks (chain signature sig), each bank at most once until the next flush, so the queue
-// never holds more entries than the pool has banks (the upload buffer's zero section); params_mu held.
-void flt_queue_zero(gas_ctx *c, uint32_t s, uint32_t sig) {
-	for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
-		const int32_t bank = c->h_flt_of[s][j];
-		if (((sig >> (8 * j)) & 0xff) == GAS_FX_FILTER && bank >= 0 && !c->flt_zero_pending[bank]) {
-			c->flt_zero_pending[bank] = 1;
-			c->flt_zero_list.push_back((uint32_t)bank);
-		}
-	}
-}
-
-void release_fx_filter(gas_ctx *c) {
-	(void)hipFree(c->st.flt_pool);
-	(void)hipFree(c->st.flt_of);
-	(void)hipFree(c->st.flt_settings);
-	(void)hipFree(c->d_flt_upload);
-	(void)hipHostFree(c->h_flt_upload);
-	c->st.flt_pool = nullptr;
-	c->st.flt_of = nullptr;
-	c->st.flt_settings = nullptr;
-	c->d_flt_upload = c->h_flt_upload = nullptr;
-	c->flt_cap = 0;
-	c->flt_free.clear();
-	c->h_flt_of.clear();
-	c->h_flt.clear();
-	c->flt_dirty_flag.clear();
-	c->flt_dirty_list.clear();
-	c->flt_zero_list.clear();
-	c->flt_zero_pending.clear();
-}
-
-// gas_fx_mod_settings_publish's rows, new slot -> line / bank entries and entries to zero: one copy of
-// [m settings][m {slot, index[4]}][z {kind, index}], one scatter, one zeroing launch.
-int flush_fx_mod(gas_ctx *c) {
-	if (!c->h_mod_upload) {
-		return GAS_OK;
-	}
-	uint32_t m = 0, z = 0;
-	{
-		std::lock_guard<std::mutex> lk(c->params_mu);
-		m = (uint32_t)c->mod_dirty_list.size();
-		z = (uint32_t)c->mod_zero_list.size() / 2;
-		if (m == 0 && z == 0) {
-			return GAS_OK;
-		}
-		gas_fx_mod_settings *hs = reinterpret_cast<gas_fx_mod_settings *>(c->h_mod_upload);
-		uint32_t *hsi = reinterpret_cast<uint32_t *>(c->h_mod_upload + (size_t)m * sizeof(gas_fx_mod_settings));
-		for (uint32_t i = 0; i < m; i++) {
-			const uint32_t s = c->mod_dirty_list[i];
-			hs[i] = c->h_mod[s];
-			hsi[i * (1 + GAS_MAX_EFFECTS)] = s;
-			for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
-				hsi[i * (1 + GAS_MAX_EFFECTS) + 1 + j] = (uint32_t)c->h_mod_of[s][j];
-			}
-			c->mod_dirty_flag[s] = 0;
-		}
-		std::memcpy(hsi + (size_t)m * (1 + GAS_MAX_EFFECTS), c->mod_zero_list.data(), (size_t)z * 2 * sizeof(uint32_t));
-		for (uint32_t i = 0; i < z; i++) {
-			c->mod_zero_pending[mod_pool_of((int)c->mod_zero_list[2 * i])][c->mod_zero_list[2 * i + 1]] = 0;
-		}
-		c->mod_dirty_list.clear();
-		c->mod_zero_list.clear();
-	}
-	const size_t zoff = (size_t)m * (sizeof(gas_fx_mod_settings) + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t));
-	GAS_HIP(c, hipMemcpyAsync(c->d_mod_upload, c->h_mod_upload, zoff + (size_t)z * 2 * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-	GAS_HIP(c, gas_launch_scatter_mod(c->stream, c->st, reinterpret_cast<const gas_fx_mod_settings *>(c->d_mod_upload), reinterpret_cast<const uint32_t *>(c->d_mod_upload + (size_t)m * sizeof(gas_fx_mod_settings)), m));
-	GAS_HIP(c, gas_launch_zero_mod(c->stream, c->st, reinterpret_cast<const uint32_t *>(c->d_mod_upload + zoff), z));
-	GAS_HIP(c, hipStreamSynchronize(c->stream)); // the pinned staging buffer is reused by the next flush
-	return GAS_OK;
-}
-
-// Marks slot s's chorus / phaser settings row (and its table row) for the next flush; params_mu held.
-void mod_mark_dirty(gas_ctx *c, uint32_t s) {
-	if (!c->mod_dirty_flag[s]) {
-		c->mod_dirty_flag[s] = 1;
-		c->mod_dirty_list.push_back(s);
-	}
-}
-
-// Queues the zeroing of slot s's chorus lines and phaser banks (chain signature sig), each at most once until the next
-// flush, so the queue never holds more pairs than the pools have entries (the upload buffer's zero section);
-// params_mu held.
-void mod_queue_zero(gas_ctx *c, uint32_t s, uint32_t sig) {
-	for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
-		const int kind = (sig >> (8 * j)) & 0xff;
-		const int pool = mod_pool_of(kind);
-		const int32_t idx = c->h_mod_of[s][j];
-		if (pool >= 0 && idx >= 0 && !c->mod_zero_pending[pool][idx]) {
-			c->mod_zero_pending[pool][idx] = 1;
-			c->mod_zero_list.push_back((uint32_t)kind);
-			c->mod_zero_list.push_back((uint32_t)idx);
-		}
-	}
-}
-
-void release_fx_mod(gas_ctx *c) {
-	(void)hipFree(c->st.chorus_pool);
-	(void)hipFree(c->st.phaser_pool);
-	(void)hipFree(c->st.mod_of);
-	(void)hipFree(c->st.mod_settings);
-	(void)hipFree(c->d_mod_upload);
-	(void)hipHostFree(c->h_mod_upload);
-	c->st.chorus_pool = c->st.phaser_pool = nullptr;
-	c->st.mod_of = nullptr;
-	c->st.mod_settings = nullptr;
-	c->st.chorus_mask = 0;
-	c->d_mod_upload = c->h_mod_upload = nullptr;
-	for (int p = 0; p < 2; p++) {
-		c->mod_cap[p] = 0;
-		c->mod_free[p].clear();
-		c->mod_zero_pending[p].clear();
-	}
-	c->h_mod_of.clear();
-	c->h_mod.clear();
-	c->mod_dirty_flag.clear();
-	c->mod_dirty_list.clear();
-	c->mod_zero_list.clear();
-}
-
-// gas_fx_stereo_settings_publish's rows, new slot -> ring entries and rings to zero: one copy of
-// [m settings][m {slot, ring[4]}][z ring], one scatter, one zeroing launch.
-int flush_fx_stereo(gas_ctx *c) {
-	uint32_t m = 0, z = 0;
-	{
-		std::lock_guard<std::mutex> lk(c->params_mu);
-		m = (uint32_t)c->stereo_dirty_list.size();
-		z = (uint32_t)c->ring_zero_list.size();
-		if (m == 0 && z == 0) {
-			return GAS_OK;
-		}
-		if (!c->h_stereo_upload || !c->d_stereo_upload) { // a failed gas_ctx_reserve_fx_stereo could not restore it
+		if (!p.h_upload || !p.d_upload) { // a resident family's failed reservation could not restore it
 			return GAS_ERR_OUT_OF_MEMORY;
 		}
-		gas_fx_stereo_settings *hs = reinterpret_cast<gas_fx_stereo_settings *>(c->h_stereo_upload);
-		uint32_t *hsi = reinterpret_cast<uint32_t *>(c->h_stereo_upload + (size_t)m * sizeof(gas_fx_stereo_settings));
+		uint32_t *hsi = reinterpret_cast<uint32_t *>(p.h_upload + (size_t)m * pod);
 		for (uint32_t i = 0; i < m; i++) {
-			const uint32_t s = c->stereo_dirty_list[i];
-			hs[i] = c->h_stereo[s];
+			const uint32_t s = p.dirty_list[i];
+			std::memcpy(p.h_upload + (size_t)i * pod, p.h_settings.data() + (size_t)s * pod, pod);
 			hsi[i * (1 + GAS_MAX_EFFECTS)] = s;
 			for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
-				hsi[i * (1 + GAS_MAX_EFFECTS) + 1 + j] = (uint32_t)c->h_stereo_of[s][j];
+				hsi[i * (1 + GAS_MAX_EFFECTS) + 1 + j] = (uint32_t)p.h_of[s][j];
 			}
-			c->stereo_dirty_flag[s] = 0;
+			p.dirty_flag[s] = 0;
 		}
-		std::memcpy(hsi + (size_t)m * (1 + GAS_MAX_EFFECTS), c->ring_zero_list.data(), (size_t)z * sizeof(uint32_t));
+		std::memcpy(hsi + (size_t)m * (1 + GAS_MAX_EFFECTS), p.zero_list.data(), (size_t)z * w * sizeof(uint32_t));
 		for (uint32_t i = 0; i < z; i++) {
-			c->ring_zero_pending[c->ring_zero_list[i]] = 0;
+			const uint32_t *r = &p.zero_list[(size_t)w * i];
+			p.zero_pending[w == 2 ? d.pool_of((int)r[0]) : 0][r[w - 1]] = 0;
 		}
-		c->stereo_dirty_list.clear();
-		c->ring_zero_list.clear();
+		p.dirty_list.clear();
+		p.zero_list.clear();
 	}
-	const size_t zoff = (size_t)m * (sizeof(gas_fx_stereo_settings) + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t));
-	GAS_HIP(c, hipMemcpyAsync(c->d_stereo_upload, c->h_stereo_upload, zoff + (size_t)z * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-	GAS_HIP(c, gas_launch_scatter_stereo(c->stream, c->st, reinterpret_cast<const gas_fx_stereo_settings *>(c->d_stereo_upload), reinterpret_cast<const uint32_t *>(c->d_stereo_upload + (size_t)m * sizeof(gas_fx_stereo_settings)), m));
-	GAS_HIP(c, gas_launch_zero_rings(c->stream, c->st, reinterpret_cast<const uint32_t *>(c->d_stereo_upload + zoff), z));
+	const size_t zoff = (size_t)m * (pod + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t));
+	const FxDev dev = d.get(c->st);
+	GAS_HIP(c, hipMemcpyAsync(p.d_upload, p.h_upload, zoff + (size_t)z * w * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	GAS_HIP(c, gas_launch_scatter_fx(c->stream, dev.settings, dev.of, c->st.dyn_stride, d.pod_bytes, p.d_upload, reinterpret_cast<const uint32_t *>(p.d_upload + (size_t)m * pod), m));
+	GAS_HIP(c, d.zero(c, reinterpret_cast<const uint32_t *>(p.d_upload + zoff), z));
 	GAS_HIP(c, hipStreamSynchronize(c->stream)); // the pinned staging buffer is reused by the next flush
 	return GAS_OK;
 }
 
-// Marks slot s's panner / stereo enhance / limiter settings row (and its table row) for the next flush; params_mu held.
-void stereo_mark_dirty(gas_ctx *c, uint32_t s) {
-	if (!c->stereo_dirty_flag[s]) {
-		c->stereo_dirty_flag[s] = 1;
-		c->stereo_dirty_list.push_back(s);
-	}
-}
-
-// Queues the zeroing of slot s's stereo-enhance rings (chain signature sig), each at most once until the next flush,
-// so the queue never holds more entries than the pool has rings (the upload buffer's zero section); params_mu held.
-void ring_queue_zero(gas_ctx *c, uint32_t s, uint32_t sig) {
+// Queues the zeroing of slot s's pool entries (chain signature sig), each entry at most once until the next flush, so
+// the queue never holds more records than the pools have entries (the upload buffer's zero section); params_mu held.
+void fx_queue_zero(gas_ctx *c, int f, uint32_t s, uint32_t sig) {
+	FxFamily &p = c->fx[f];
+	const FxFamilyDesc &d = k_fx_families[f];
 	for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
-		const int32_t idx = c->h_stereo_of[s][j];
-		if (((sig >> (8 * j)) & 0xff) == GAS_FX_STEREO_ENHANCE && idx >= 0 && !c->ring_zero_pending[idx]) {
-			c->ring_zero_pending[idx] = 1;
-			c->ring_zero_list.push_back((uint32_t)idx);
+		const int kind = (sig >> (8 * j)) & 0xff;
+		const int pool = d.pool_of(kind);
+		const int32_t idx = p.h_of[s][j];
+		if (pool >= 0 && idx >= 0 && !p.zero_pending[pool][idx]) {
+			p.zero_pending[pool][idx] = 1;
+			if (d.pools == 2) {
+				p.zero_list.push_back((uint32_t)kind);
+			}
+			p.zero_list.push_back((uint32_t)idx);
 		}
 	}
 }
 
-// The staging buffer of flush_fx_stereo with room for `rings` entries in its zero section; main thread, stream idle.
-hipError_t alloc_stereo_upload(gas_ctx *c, uint32_t rings) {
-	(void)hipFree(c->d_stereo_upload);
-	(void)hipHostFree(c->h_stereo_upload);
-	c->d_stereo_upload = c->h_stereo_upload = nullptr;
-	// [<= N settings rows][<= N {slot, ring[4]}][<= every ring once] (stereo_mark_dirty / ring_queue_zero)
-	const size_t upload = (size_t)c->cfg.max_sources * (sizeof(gas_fx_stereo_settings) + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t)) + (size_t)rings * sizeof(uint32_t);
-	hipError_t e = hipMalloc(&c->d_stereo_upload, upload);
-	return e != hipSuccess ? e : hipHostMalloc(&c->h_stereo_upload, upload, hipHostMallocDefault);
+// A new slot's entries, one per effect of its chain that takes one, and its settings at the resource defaults: entered
+// in the tables and zeroed at the next flush.  alloc_mu held, the entries are there (gas_source_alloc).
+void fx_hand_out(gas_ctx *c, int f, uint32_t s, const int32_t *effects, uint32_t n_effects, uint32_t sig) {
+	FxFamily &p = c->fx[f];
+	const FxFamilyDesc &d = k_fx_families[f];
+	std::lock_guard<std::mutex> lk(c->params_mu);
+	for (uint32_t j = 0; j < GAS_MAX_EFFECTS; j++) {
+		const int pool = j < n_effects ? d.pool_of(effects[j]) : -1;
+		if (pool >= 0) {
+			p.h_of[s][j] = (int32_t)p.free[pool].back();
+			p.free[pool].pop_back();
+		} else {
+			p.h_of[s][j] = -1;
+		}
+	}
+	d.defaults(p.h_settings.data() + (size_t)s * d.pod_bytes);
+	mark_dirty(p.dirty_flag, p.dirty_list, s);
+	fx_queue_zero(c, f, s, sig);
 }
 
-// The ring pool only: the settings, the table and the staging buffer stay (gas_ctx_destroy frees those).
-void release_fx_stereo_pool(gas_ctx *c) {
-	(void)hipFree(c->st.enhance_pool);
-	c->st.enhance_pool = nullptr;
-	c->st.enhance_mask = 0;
-	c->ring_cap = 0;
-	c->ring_free.clear();
-	c->ring_zero_pending.clear();
-	c->ring_zero_list.clear();
+// A freed slot's entries go back to the pools (zeroed when they are handed out again); alloc_mu held.
+void fx_return_entries(gas_ctx *c, int f, uint32_t s, uint32_t sig) {
+	FxFamily &p = c->fx[f];
+	if (p.cap[0] + p.cap[1] == 0) {
+		return;
+	}
+	std::lock_guard<std::mutex> lk(c->params_mu); // (h_of is read by the flush under params_mu)
+	for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
+		const int pool = k_fx_families[f].pool_of((sig >> (8 * j)) & 0xff);
+		if (pool >= 0 && p.h_of[s][j] >= 0) {
+			p.free[pool].push_back((uint32_t)p.h_of[s][j]);
+			p.h_of[s][j] = -1;
+		}
+	}
+}
+
+// The staging buffer of fx_flush with room for `entries` zero records; main thread, stream idle.
+hipError_t fx_alloc_upload(gas_ctx *c, int f, size_t entries) {
+	FxFamily &p = c->fx[f];
+	const FxFamilyDesc &d = k_fx_families[f];
+	(void)hipFree(p.d_upload);
+	(void)hipHostFree(p.h_upload);
+	p.d_upload = p.h_upload = nullptr;
+	// [<= N settings rows][<= N {slot, entry[4]}][<= every entry once] (mark_dirty / fx_queue_zero)
+	const size_t bytes = (size_t)c->cfg.max_sources * (d.pod_bytes + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t)) + entries * d.pools * sizeof(uint32_t);
+	const hipError_t e = hipMalloc(&p.d_upload, bytes);
+	return e != hipSuccess ? e : hipHostMalloc(&p.h_upload, bytes, hipHostMallocDefault);
+}
+
+// The settings table at the resource defaults (`rows`: the same for the host mirror) and the slot -> entry table at -1.
+hipError_t fx_alloc_tables(gas_ctx *c, int f, FxDev &dev, std::vector<unsigned char> &rows) {
+	const FxFamilyDesc &d = k_fx_families[f];
+	const size_t N = c->cfg.max_sources, pod = d.pod_bytes;
+	rows.resize(N * pod);
+	d.defaults(rows.data());
+	for (size_t s = 1; s < N; s++) {
+		std::memcpy(rows.data() + s * pod, rows.data(), pod);
+	}
+	hipError_t e = hipMalloc(&dev.of, sizeof(int32_t) * GAS_MAX_EFFECTS * N);
+	e = e != hipSuccess ? e : hipMemsetAsync(dev.of, 0xff, sizeof(int32_t) * GAS_MAX_EFFECTS * N, c->stream);
+	e = e != hipSuccess ? e : hipMalloc(&dev.settings, N * pod);
+	return e != hipSuccess ? e : hipMemcpy(dev.settings, rows.data(), N * pod, hipMemcpyHostToDevice);
+}
+
+// Frees the pools and, unless the family is resident and `all` is not set (only gas_ctx_destroy sets it), the settings,
+// the table and the staging buffer; params_mu held or no other thread left.
+void fx_release(gas_ctx *c, int f, bool all) {
+	FxFamily &p = c->fx[f];
+	const FxFamilyDesc &d = k_fx_families[f];
+	FxDev dev = d.get(c->st);
+	for (int pl = 0; pl < 2; pl++) {
+		(void)hipFree(dev.pool[pl]);
+		dev.pool[pl] = nullptr;
+		p.cap[pl] = 0;
+		p.free[pl].clear();
+		p.zero_pending[pl].clear();
+	}
+	p.zero_list.clear();
+	if (all || !d.resident) {
+		(void)hipFree(dev.of);
+		(void)hipFree(dev.settings);
+		(void)hipFree(p.d_upload);
+		(void)hipHostFree(p.h_upload);
+		dev.of = nullptr;
+		dev.settings = nullptr;
+		p.d_upload = p.h_upload = nullptr;
+		p.h_of.clear();
+		p.h_settings.clear();
+		p.dirty_flag.clear();
+		p.dirty_list.clear();
+	}
+	d.set(c->st, dev);
+	if (d.extras) {
+		d.extras(c, false);
+	}
+}
+
+// gas_fx_*_settings_publish: latest wins in the host mirror, uploaded by the next flush.
+int fx_publish(gas_ctx *c, int f, const uint32_t *slots, const void *settings, uint32_t n) {
+	if (!c || (n > 0 && (!slots || !settings))) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	FxFamily &p = c->fx[f];
+	const FxFamilyDesc &d = k_fx_families[f];
+	const size_t pod = d.pod_bytes;
+	const unsigned char *rows = static_cast<const unsigned char *>(settings);
+	for (uint32_t i = 0; i < n; i++) {
+		if (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used) {
+			return GAS_ERR_BAD_SLOT;
+		}
+		if (!d.valid(rows + (size_t)i * pod)) {
+			return GAS_ERR_INVALID_ARGUMENT;
+		}
+	}
+	std::lock_guard<std::mutex> lk(c->params_mu);
+	if (p.h_settings.empty()) { // nothing reserved: no slot has an effect the settings could reach (never so for a resident family)
+		return GAS_OK;
+	}
+	for (uint32_t i = 0; i < n; i++) {
+		std::memcpy(p.h_settings.data() + (size_t)slots[i] * pod, rows + (size_t)i * pod, pod);
+		mark_dirty(p.dirty_flag, p.dirty_list, slots[i]);
+	}
+	return GAS_OK;
+}
+
+// gas_ctx_reserve_fx_*: main thread, refused while any entry is held; counts of 0 release everything (a resident
+// family keeps its settings, table and a staging buffer without a zero section).
+int fx_reserve(gas_ctx *c, int f, uint32_t count0, uint32_t count1) {
+	if (!c) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	FxFamily &p = c->fx[f];
+	const FxFamilyDesc &d = k_fx_families[f];
+	const uint32_t counts[2] = { count0, count1 };
+	const size_t total = (size_t)count0 + count1;
+	const int rc = d.check ? d.check(c, counts) : GAS_OK;
+	if (rc != GAS_OK) {
+		return rc;
+	}
+	std::lock_guard<std::mutex> alloc_lk(c->alloc_mu);
+	for (int pl = 0; pl < 2; pl++) {
+		if (p.free[pl].size() != p.cap[pl]) {
+			return GAS_ERR_INVALID_ARGUMENT; // entries are held
+		}
+	}
+	GAS_HIP(c, hipSetDevice(c->cfg.device));
+	GAS_HIP(c, hipStreamSynchronize(c->stream));
+	{
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		fx_release(c, f, false);
+	}
+	if (total == 0 && !d.resident) {
+		return GAS_OK;
+	}
+	std::vector<unsigned char> defaults;
+	FxDev dev = d.get(c->st);
+	hipError_t e = hipSuccess;
+	auto step = [&e](hipError_t r) {
+		if (e == hipSuccess) {
+			e = r;
+		}
+	};
+	{
+		// (queued settings rows live in the mirror only: fx_flush fills the staging buffer per flush)
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		step(fx_alloc_upload(c, f, total));
+	}
+	for (int pl = 0; pl < 2; pl++) {
+		if (counts[pl]) {
+			const size_t bytes = d.entry_floats(c, pl) * sizeof(float) * counts[pl];
+			step(hipMalloc(&dev.pool[pl], bytes));
+			step(e == hipSuccess ? hipMemsetAsync(dev.pool[pl], 0, bytes, c->stream) : e);
+		}
+	}
+	if (!d.resident) {
+		step(fx_alloc_tables(c, f, dev, defaults));
+	}
+	if (total > 0) {
+		step(e == hipSuccess ? hipStreamSynchronize(c->stream) : e);
+	}
+	d.set(c->st, dev);
+	if (e != hipSuccess) {
+		c->last_err = std::string("gas_ctx_reserve_fx_") + d.name + ": " + hipGetErrorString(e);
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		fx_release(c, f, false);
+		if (d.resident && (!p.h_upload || !p.d_upload)) {
+			(void)fx_alloc_upload(c, f, 0);
+		}
+		return e == hipErrorOutOfMemory ? GAS_ERR_OUT_OF_MEMORY : GAS_ERR_DEVICE;
+	}
+	if (total == 0) {
+		return GAS_OK;
+	}
+	std::lock_guard<std::mutex> lk(c->params_mu);
+	if (d.extras) {
+		d.extras(c, true);
+	}
+	for (int pl = 0; pl < 2; pl++) { // handed out from entry 0 up
+		const uint32_t n = counts[pl];
+		p.cap[pl] = n;
+		p.zero_pending[pl].assign(n, 0);
+		p.free[pl].resize(n);
+		for (uint32_t i = 0; i < n; i++) {
+			p.free[pl][i] = n - 1 - i;
+		}
+	}
+	if (!d.resident) {
+		p.h_of.assign(c->cfg.max_sources, fx_no_entries());
+		p.h_settings = std::move(defaults);
+		p.dirty_flag.assign(c->cfg.max_sources, 0);
+	}
+	return GAS_OK;
 }
 
 int flush_params(gas_ctx *c) {
@@ -1725,11 +1701,10 @@ int flush_params(gas_ctx *c) {
 	}
 	int rc = flush_fx_settings(c);
 	rc = rc != GAS_OK ? rc : flush_fx_dyn_settings(c);
-	rc = rc != GAS_OK ? rc : flush_fx_lines(c);
-	rc = rc != GAS_OK ? rc : flush_fx_eq(c);
-	rc = rc != GAS_OK ? rc : flush_fx_filter(c);
-	rc = rc != GAS_OK ? rc : flush_fx_mod(c);
-	return rc != GAS_OK ? rc : flush_fx_stereo(c);
+	for (int f = 0; f < FX_FAMILIES && rc == GAS_OK; f++) {
+		rc = fx_flush(c, f);
+	}
+	return rc;
 }
 
 void stream_rows_sync_back(gas_ctx *c);
@@ -1759,52 +1734,8 @@ int apply_pending_frees(gas_ctx *c) {
 	std::lock_guard<std::mutex> alloc_lk(c->alloc_mu);
 	for (uint32_t s : c->pending_free) {
 		SlotInfo &si = c->slots[s];
-		if (!c->h_line_of.empty()) { // its lines go back to the pools (zeroed when they are handed out again)
-			std::lock_guard<std::mutex> lk(c->params_mu); // (h_line_of is read by the flush under params_mu)
-			for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
-				const int pool = line_pool_of((si.chain_sig >> (8 * j)) & 0xff);
-				if (pool >= 0 && c->h_line_of[s][j] >= 0) {
-					c->line_free[pool].push_back((uint32_t)c->h_line_of[s][j]);
-					c->h_line_of[s][j] = -1;
-				}
-			}
-		}
-		if (!c->h_flt_of.empty()) { // its GAS_FX_FILTER banks likewise
-			std::lock_guard<std::mutex> lk(c->params_mu);
-			for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
-				if (((si.chain_sig >> (8 * j)) & 0xff) == GAS_FX_FILTER && c->h_flt_of[s][j] >= 0) {
-					c->flt_free.push_back((uint32_t)c->h_flt_of[s][j]);
-					c->h_flt_of[s][j] = -1;
-				}
-			}
-		}
-		if (!c->h_eq_of.empty()) { // its banks go back to the pool (zeroed when they are handed out again)
-			std::lock_guard<std::mutex> lk(c->params_mu);
-			for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
-				if (is_eq((si.chain_sig >> (8 * j)) & 0xff) && c->h_eq_of[s][j] >= 0) {
-					c->eq_free.push_back((uint32_t)c->h_eq_of[s][j]);
-					c->h_eq_of[s][j] = -1;
-				}
-			}
-		}
-		if (!c->h_mod_of.empty()) { // its chorus lines and phaser banks go back to the pools (zeroed when handed out again)
-			std::lock_guard<std::mutex> lk(c->params_mu);
-			for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
-				const int pool = mod_pool_of((si.chain_sig >> (8 * j)) & 0xff);
-				if (pool >= 0 && c->h_mod_of[s][j] >= 0) {
-					c->mod_free[pool].push_back((uint32_t)c->h_mod_of[s][j]);
-					c->h_mod_of[s][j] = -1;
-				}
-			}
-		}
-		if (c->ring_cap > 0) { // its stereo-enhance rings go back to the pool (zeroed when handed out again)
-			std::lock_guard<std::mutex> lk(c->params_mu);
-			for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
-				if (((si.chain_sig >> (8 * j)) & 0xff) == GAS_FX_STEREO_ENHANCE && c->h_stereo_of[s][j] >= 0) {
-					c->ring_free.push_back((uint32_t)c->h_stereo_of[s][j]);
-					c->h_stereo_of[s][j] = -1;
-				}
-			}
+		for (int f = 0; f < FX_FAMILIES; f++) {
+			fx_return_entries(c, f, s, si.chain_sig);
 		}
 		si = SlotInfo{};
 		si.dirty_state = 1;
@@ -2044,15 +1975,9 @@ void gas_ctx_destroy(gas_ctx *c) {
 	(void)hipFree(c->st.comp_rundb);
 	(void)hipFree(c->d_dyn_upload);
 	(void)hipHostFree(c->h_dyn_upload);
-	release_fx_lines(c);
-	release_fx_eq(c);
-	release_fx_filter(c);
-	release_fx_mod(c);
-	release_fx_stereo_pool(c);
-	(void)hipFree(c->st.stereo_settings);
-	(void)hipFree(c->st.stereo_of);
-	(void)hipFree(c->d_stereo_upload);
-	(void)hipHostFree(c->h_stereo_upload);
+	for (int f = 0; f < FX_FAMILIES; f++) {
+		fx_release(c, f, true);
+	}
 	(void)hipFree(c->d_slots);
 	(void)hipFree(c->d_rows);
 	(void)hipFree(c->d_slots_rows);
@@ -2160,10 +2085,17 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 		GAS_HIP(c, hipMemsetAsync(c->st.comp_rundb, 0, sizeof(float) * GAS_MAX_EFFECTS * N, c->stream));
 		GAS_HIP(c, hipMalloc(&c->d_dyn_upload, (sizeof(gas_fx_dyn_settings) + sizeof(uint32_t)) * N));
 		GAS_HIP(c, hipHostMalloc(&c->h_dyn_upload, (sizeof(gas_fx_dyn_settings) + sizeof(uint32_t)) * N, hipHostMallocDefault));
-		GAS_HIP(c, hipMalloc(&c->st.stereo_settings, sizeof(gas_fx_stereo_settings) * N));
-		GAS_HIP(c, hipMalloc(&c->st.stereo_of, sizeof(int32_t) * GAS_MAX_EFFECTS * N));
-		GAS_HIP(c, hipMemsetAsync(c->st.stereo_of, 0xff, sizeof(int32_t) * GAS_MAX_EFFECTS * N, c->stream));
-		GAS_HIP(c, alloc_stereo_upload(c, 0));
+		for (int f = 0; f < FX_FAMILIES; f++) { // the families that need no reservation for their settings
+			if (k_fx_families[f].resident) {
+				FxDev dev;
+				const hipError_t e = fx_alloc_tables(c, f, dev, c->fx[f].h_settings);
+				k_fx_families[f].set(c->st, dev);
+				GAS_HIP(c, e);
+				GAS_HIP(c, fx_alloc_upload(c, f, 0));
+				c->fx[f].h_of.assign(N, fx_no_entries());
+				c->fx[f].dirty_flag.assign(N, 0);
+			}
+		}
 		GAS_HIP(c, hipMalloc(&c->d_upload, sizeof(gas_params) * N));
 		GAS_HIP(c, hipMalloc(&c->d_upload_slots, sizeof(uint32_t) * N));
 		GAS_HIP(c, hipMalloc(&c->d_slots, sizeof(uint32_t) * N));
@@ -2223,20 +2155,10 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 	c->fx_dirty_flag.assign(N, 0);
 	c->h_dyn.assign(N, fx_dyn_settings_defaults());
 	c->dyn_dirty_flag.assign(N, 0);
-	c->h_stereo.assign(N, gas_fx_stereo_settings_defaults());
-	c->stereo_dirty_flag.assign(N, 0);
-	{
-		std::array<int32_t, GAS_MAX_EFFECTS> none;
-		none.fill(-1);
-		c->h_stereo_of.assign(N, none);
-	}
 	{ // every slot starts from the engine's resource defaults
 		hipError_t e = hipMemcpy(c->st.fxs, c->h_fxs.data(), sizeof(gas_fx_settings) * N, hipMemcpyHostToDevice);
 		if (e == hipSuccess) {
 			e = hipMemcpy(c->st.dyn, c->h_dyn.data(), sizeof(gas_fx_dyn_settings) * N, hipMemcpyHostToDevice);
-		}
-		if (e == hipSuccess) {
-			e = hipMemcpy(c->st.stereo_settings, c->h_stereo.data(), sizeof(gas_fx_stereo_settings) * N, hipMemcpyHostToDevice);
 		}
 		if (e != hipSuccess) {
 			gas_ctx_destroy(c);
@@ -2349,43 +2271,27 @@ int gas_source_alloc(gas_ctx *c, int kind, const int32_t *effects, uint32_t n_ef
 	if ((g == G_FX_ER || g == G_FX_ER_HRTF || (g == G_FX_GENERIC && chain_has(sig, GAS_FX_EARLY_REFLECTIONS))) && c->cfg.er_ring_frames == 0) {
 		return GAS_ERR_UNSUPPORTED_CHAIN;
 	}
-	uint32_t need[2] = { 0, 0 }; // delay / reverb lines of the chain
-	uint32_t need_eq = 0; // EQ banks of the chain
-	uint32_t need_mod[2] = { 0, 0 }; // chorus lines / phaser banks of the chain
-	uint32_t need_rings = 0; // stereo-enhance rings of the chain
-	uint32_t need_flt = 0; // GAS_FX_FILTER banks of the chain
-	bool any_stereo = false;
-	for (uint32_t j = 0; j < n_effects; j++) {
-		const int pool = line_pool_of(effects[j]);
-		if (pool >= 0) {
-			need[pool]++;
+	uint32_t need[FX_FAMILIES][2] = {}; // pool entries of the chain, per pooled family and pool
+	bool in_family[FX_FAMILIES] = {}; // the chain has a kind whose settings the family carries
+	for (int f = 0; f < FX_FAMILIES; f++) {
+		for (uint32_t j = 0; j < n_effects; j++) {
+			const int pool = k_fx_families[f].pool_of(effects[j]);
+			if (pool >= 0) {
+				need[f][pool]++;
+			}
+			in_family[f] = in_family[f] || k_fx_families[f].has_kind(effects[j]);
 		}
-		need_eq += is_eq(effects[j]);
-		const int mpool = mod_pool_of(effects[j]);
-		if (mpool >= 0) {
-			need_mod[mpool]++;
-		}
-		need_rings += effects[j] == GAS_FX_STEREO_ENHANCE;
-		need_flt += effects[j] == GAS_FX_FILTER;
-		any_stereo = any_stereo || is_stereo(effects[j]);
 	}
 	std::lock_guard<std::mutex> alloc_lk(c->alloc_mu); // any thread (instantiate_playback_data runs on the physics thread, audio_spatializer.cpp:69)
-	if (need[0] + need[1] > 0 && c->line_cap[0] == 0 && c->line_cap[1] == 0) {
-		return GAS_ERR_UNSUPPORTED_CHAIN; // no pool reserved (gas_ctx_reserve_fx_lines)
+	bool room = !c->free_list.empty();
+	for (int f = 0; f < FX_FAMILIES; f++) {
+		const FxFamily &p = c->fx[f];
+		if (need[f][0] + need[f][1] > 0 && p.cap[0] == 0 && p.cap[1] == 0) {
+			return GAS_ERR_UNSUPPORTED_CHAIN; // no pool reserved (gas_ctx_reserve_fx_*)
+		}
+		room = room && p.free[0].size() >= need[f][0] && p.free[1].size() >= need[f][1];
 	}
-	if (need_eq > 0 && c->eq_cap == 0) {
-		return GAS_ERR_UNSUPPORTED_CHAIN; // no bank pool reserved (gas_ctx_reserve_fx_eq)
-	}
-	if (need_mod[0] + need_mod[1] > 0 && c->mod_cap[0] == 0 && c->mod_cap[1] == 0) {
-		return GAS_ERR_UNSUPPORTED_CHAIN; // no chorus / phaser pool reserved (gas_ctx_reserve_fx_mod)
-	}
-	if (need_rings > 0 && c->ring_cap == 0) {
-		return GAS_ERR_UNSUPPORTED_CHAIN; // no ring pool reserved (gas_ctx_reserve_fx_stereo)
-	}
-	if (need_flt > 0 && c->flt_cap == 0) {
-		return GAS_ERR_UNSUPPORTED_CHAIN; // no bank pool reserved (gas_ctx_reserve_fx_filter)
-	}
-	if (c->free_list.empty() || c->line_free[0].size() < need[0] || c->line_free[1].size() < need[1] || c->eq_free.size() < need_eq || c->mod_free[0].size() < need_mod[0] || c->mod_free[1].size() < need_mod[1] || c->ring_free.size() < need_rings || c->flt_free.size() < need_flt) { // all or nothing
+	if (!room) { // all or nothing
 		return GAS_ERR_OUT_OF_SLOTS;
 	}
 	const uint32_t s = c->free_list.back();
@@ -2405,10 +2311,7 @@ int gas_source_alloc(gas_ctx *c, int kind, const int32_t *effects, uint32_t n_ef
 		if (effects[j] >= GAS_FX_LOWPASS) { // a new playback's effect instances start from the resource defaults (audio_spatializer_effect.cpp:79-88)
 			std::lock_guard<std::mutex> lk(c->params_mu);
 			c->h_fxs[s] = fx_settings_defaults();
-			if (!c->fx_dirty_flag[s]) {
-				c->fx_dirty_flag[s] = 1;
-				c->fx_dirty_list.push_back(s);
-			}
+			mark_dirty(c->fx_dirty_flag, c->fx_dirty_list, s);
 			break;
 		}
 	}
@@ -2416,84 +2319,14 @@ int gas_source_alloc(gas_ctx *c, int kind, const int32_t *effects, uint32_t n_ef
 		if (effects[j] == GAS_FX_DISTORTION || effects[j] == GAS_FX_COMPRESSOR) { // likewise for gas_fx_dyn_settings
 			std::lock_guard<std::mutex> lk(c->params_mu);
 			c->h_dyn[s] = fx_dyn_settings_defaults();
-			if (!c->dyn_dirty_flag[s]) {
-				c->dyn_dirty_flag[s] = 1;
-				c->dyn_dirty_list.push_back(s);
-			}
+			mark_dirty(c->dyn_dirty_flag, c->dyn_dirty_list, s);
 			break;
 		}
 	}
-	if (need[0] + need[1] > 0) { // one line per delay / reverb, zeroed and entered in the table at the next flush
-		std::lock_guard<std::mutex> lk(c->params_mu);
-		for (uint32_t j = 0; j < GAS_MAX_EFFECTS; j++) {
-			const int pool = j < n_effects ? line_pool_of(effects[j]) : -1;
-			if (pool >= 0) {
-				c->h_line_of[s][j] = (int32_t)c->line_free[pool].back();
-				c->line_free[pool].pop_back();
-			} else {
-				c->h_line_of[s][j] = -1;
-			}
+	for (int f = 0; f < FX_FAMILIES; f++) {
+		if (in_family[f]) {
+			fx_hand_out(c, f, s, effects, n_effects, sig);
 		}
-		c->h_line[s] = fx_line_settings_defaults();
-		line_mark_dirty(c, s);
-		line_queue_zero(c, s, sig);
-	}
-	if (need_eq > 0) { // one bank per equaliser, zeroed and entered in the table at the next flush
-		std::lock_guard<std::mutex> lk(c->params_mu);
-		for (uint32_t j = 0; j < GAS_MAX_EFFECTS; j++) {
-			if (j < n_effects && is_eq(effects[j])) {
-				c->h_eq_of[s][j] = (int32_t)c->eq_free.back();
-				c->eq_free.pop_back();
-			} else {
-				c->h_eq_of[s][j] = -1;
-			}
-		}
-		c->h_eq[s] = gas_fx_eq_settings{}; // 0 dB everywhere
-		eq_mark_dirty(c, s);
-		eq_queue_zero(c, s, sig);
-	}
-	if (need_mod[0] + need_mod[1] > 0) { // one line or bank per chorus / phaser, zeroed and entered in the table at the next flush
-		std::lock_guard<std::mutex> lk(c->params_mu);
-		for (uint32_t j = 0; j < GAS_MAX_EFFECTS; j++) {
-			const int pool = j < n_effects ? mod_pool_of(effects[j]) : -1;
-			if (pool >= 0) {
-				c->h_mod_of[s][j] = (int32_t)c->mod_free[pool].back();
-				c->mod_free[pool].pop_back();
-			} else {
-				c->h_mod_of[s][j] = -1;
-			}
-		}
-		c->h_mod[s] = gas_fx_mod_settings_defaults();
-		mod_mark_dirty(c, s);
-		mod_queue_zero(c, s, sig);
-	}
-	if (any_stereo) { // settings from the resource defaults; one ring per stereo enhance, zeroed and entered in the table at the next flush
-		std::lock_guard<std::mutex> lk(c->params_mu);
-		for (uint32_t j = 0; j < GAS_MAX_EFFECTS; j++) {
-			if (j < n_effects && effects[j] == GAS_FX_STEREO_ENHANCE) {
-				c->h_stereo_of[s][j] = (int32_t)c->ring_free.back();
-				c->ring_free.pop_back();
-			} else {
-				c->h_stereo_of[s][j] = -1;
-			}
-		}
-		c->h_stereo[s] = gas_fx_stereo_settings_defaults();
-		stereo_mark_dirty(c, s);
-		ring_queue_zero(c, s, sig);
-	}
-	if (need_flt > 0) { // one bank per GAS_FX_FILTER, zeroed and entered in the table at the next flush
-		std::lock_guard<std::mutex> lk(c->params_mu);
-		for (uint32_t j = 0; j < GAS_MAX_EFFECTS; j++) {
-			if (j < n_effects && effects[j] == GAS_FX_FILTER) {
-				c->h_flt_of[s][j] = (int32_t)c->flt_free.back();
-				c->flt_free.pop_back();
-			} else {
-				c->h_flt_of[s][j] = -1;
-			}
-		}
-		c->h_flt[s] = gas_fx_filter_settings_defaults();
-		flt_mark_dirty(c, s);
-		flt_queue_zero(c, s, sig);
 	}
 	return GAS_OK;
 }
@@ -2541,28 +2374,14 @@ int gas_source_reset(gas_ctx *c, uint32_t slot) {
 	}
 	GAS_HIP(c, hipSetDevice(c->cfg.device));
 	GAS_HIP(c, gas_launch_zero_slot(c->stream, c->st, slot, c->hist_len, c->cfg.er_ring_frames));
-	{ // its delay / reverb lines: zeroed by the next flush, before the next block (alloc_mu: the audio thread may be
-	  // returning a freed slot's lines; the same lock order as gas_source_alloc)
+	{ // its pool entries: zeroed by the next flush, before the next block (alloc_mu: the audio thread may be returning a
+	  // freed slot's entries; the same lock order as gas_source_alloc)
 		std::lock_guard<std::mutex> alloc_lk(c->alloc_mu);
-		if (!c->h_line_of.empty() && c->slots[slot].used) {
-			std::lock_guard<std::mutex> lk(c->params_mu);
-			line_queue_zero(c, slot, c->slots[slot].chain_sig);
-		}
-		if (!c->h_eq_of.empty() && c->slots[slot].used) { // and its EQ banks
-			std::lock_guard<std::mutex> lk(c->params_mu);
-			eq_queue_zero(c, slot, c->slots[slot].chain_sig);
-		}
-		if (!c->h_mod_of.empty() && c->slots[slot].used) { // and its chorus lines and phaser banks
-			std::lock_guard<std::mutex> lk(c->params_mu);
-			mod_queue_zero(c, slot, c->slots[slot].chain_sig);
-		}
-		if (!c->h_flt_of.empty() && c->slots[slot].used) { // and its GAS_FX_FILTER banks
-			std::lock_guard<std::mutex> lk(c->params_mu);
-			flt_queue_zero(c, slot, c->slots[slot].chain_sig);
-		}
-		if (c->ring_cap > 0 && c->slots[slot].used) { // and its stereo-enhance rings
-			std::lock_guard<std::mutex> lk(c->params_mu);
-			ring_queue_zero(c, slot, c->slots[slot].chain_sig);
+		for (int f = 0; f < FX_FAMILIES; f++) {
+			if (c->fx[f].cap[0] + c->fx[f].cap[1] > 0 && c->slots[slot].used) {
+				std::lock_guard<std::mutex> lk(c->params_mu);
+				fx_queue_zero(c, f, slot, c->slots[slot].chain_sig);
+			}
 		}
 	}
 	return GAS_OK;
@@ -2579,10 +2398,7 @@ int gas_params_publish(gas_ctx *c, uint32_t slot, const gas_params *params) {
 	c->stream_params_touched = true;
 	c->params_gen++;
 	c->h_params[slot] = *params;
-	if (!c->dirty_flag[slot]) {
-		c->dirty_flag[slot] = 1;
-		c->dirty_list.push_back(slot);
-	}
+	mark_dirty(c->dirty_flag, c->dirty_list, slot);
 	c->slots[slot].has_params = 1;
 	return GAS_OK;
 }
@@ -2600,10 +2416,7 @@ int gas_fx_settings_publish(gas_ctx *c, const uint32_t *slots, const gas_fx_sett
 	for (uint32_t i = 0; i < n; i++) {
 		const uint32_t s = slots[i];
 		c->h_fxs[s] = settings[i];
-		if (!c->fx_dirty_flag[s]) {
-			c->fx_dirty_flag[s] = 1;
-			c->fx_dirty_list.push_back(s);
-		}
+		mark_dirty(c->fx_dirty_flag, c->fx_dirty_list, s);
 	}
 	return GAS_OK;
 }
@@ -2616,7 +2429,7 @@ int gas_fx_dyn_settings_publish(gas_ctx *c, const uint32_t *slots, const gas_fx_
 		if (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used) {
 			return GAS_ERR_BAD_SLOT;
 		}
-		if (!fx_dyn_settings_valid(settings[i])) {
+		if (!gas_fx_dyn_settings_valid(settings[i])) {
 			return GAS_ERR_INVALID_ARGUMENT;
 		}
 	}
@@ -2624,466 +2437,49 @@ int gas_fx_dyn_settings_publish(gas_ctx *c, const uint32_t *slots, const gas_fx_
 	for (uint32_t i = 0; i < n; i++) {
 		const uint32_t s = slots[i];
 		c->h_dyn[s] = settings[i];
-		if (!c->dyn_dirty_flag[s]) {
-			c->dyn_dirty_flag[s] = 1;
-			c->dyn_dirty_list.push_back(s);
-		}
+		mark_dirty(c->dyn_dirty_flag, c->dyn_dirty_list, s);
 	}
 	return GAS_OK;
 }
 
 int gas_fx_line_settings_publish(gas_ctx *c, const uint32_t *slots, const gas_fx_line_settings *settings, uint32_t n) {
-	if (!c || (n > 0 && (!slots || !settings))) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	for (uint32_t i = 0; i < n; i++) {
-		if (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used) {
-			return GAS_ERR_BAD_SLOT;
-		}
-		if (!gas_fx_line_settings_valid(settings[i])) {
-			return GAS_ERR_INVALID_ARGUMENT;
-		}
-	}
-	std::lock_guard<std::mutex> lk(c->params_mu);
-	if (c->h_line.empty()) { // no pool reserved: no slot has a delay or reverb the settings could reach
-		return GAS_OK;
-	}
-	for (uint32_t i = 0; i < n; i++) {
-		c->h_line[slots[i]] = settings[i];
-		line_mark_dirty(c, slots[i]);
-	}
-	return GAS_OK;
+	return fx_publish(c, FX_LINES, slots, settings, n);
 }
 
 int gas_ctx_reserve_fx_lines(gas_ctx *c, uint32_t delay_lines, uint32_t reverb_lines) {
-	if (!c) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	const uint32_t F = c->cfg.frames;
-	const double sr = (double)c->cfg.mix_rate;
-	if (reverb_lines > 0 && (lrint(0.02 * sr) < (long)F || lrint(0.025306122 * sr) < (long)F)) {
-		return GAS_ERR_INVALID_ARGUMENT; // the reverb kernel's predelay and comb reads must not reach the block's own writes
-	}
-	std::lock_guard<std::mutex> alloc_lk(c->alloc_mu);
-	for (int p = 0; p < 2; p++) {
-		if (c->line_free[p].size() != c->line_cap[p]) {
-			return GAS_ERR_INVALID_ARGUMENT; // lines are held
-		}
-	}
-	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	GAS_HIP(c, hipStreamSynchronize(c->stream));
-	{
-		std::lock_guard<std::mutex> lk(c->params_mu);
-		release_fx_lines(c);
-	}
-	if (delay_lines == 0 && reverb_lines == 0) {
-		return GAS_OK;
-	}
-	const size_t N = c->cfg.max_sources;
-	const gas_line_geo geo = make_line_geo(c->cfg.mix_rate);
-	// [<= N settings rows][<= N {slot, line[4]}][<= every line once {kind, line}] (line_mark_dirty / line_queue_zero)
-	const size_t upload = N * (sizeof(gas_fx_line_settings) + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t)) + ((size_t)delay_lines + reverb_lines) * 2 * sizeof(uint32_t);
-	std::vector<gas_fx_line_settings> defaults(N, fx_line_settings_defaults());
-	hipError_t e = hipSuccess;
-	auto step = [&e](hipError_t r) {
-		if (e == hipSuccess) {
-			e = r;
-		}
-	};
-	if (delay_lines) {
-		step(hipMalloc(&c->st.delay_pool, geo.delay_floats * sizeof(float) * delay_lines));
-		step(e == hipSuccess ? hipMemsetAsync(c->st.delay_pool, 0, geo.delay_floats * sizeof(float) * delay_lines, c->stream) : e);
-	}
-	if (reverb_lines) {
-		step(hipMalloc(&c->st.reverb_pool, geo.reverb_floats * sizeof(float) * reverb_lines));
-		step(e == hipSuccess ? hipMemsetAsync(c->st.reverb_pool, 0, geo.reverb_floats * sizeof(float) * reverb_lines, c->stream) : e);
-	}
-	step(hipMalloc(&c->st.line_of, sizeof(int32_t) * GAS_MAX_EFFECTS * N));
-	step(e == hipSuccess ? hipMemsetAsync(c->st.line_of, 0xff, sizeof(int32_t) * GAS_MAX_EFFECTS * N, c->stream) : e);
-	step(hipMalloc(&c->st.line_settings, sizeof(gas_fx_line_settings) * N));
-	step(e == hipSuccess ? hipMemcpy(c->st.line_settings, defaults.data(), sizeof(gas_fx_line_settings) * N, hipMemcpyHostToDevice) : e);
-	step(hipMalloc(&c->d_line_upload, upload));
-	step(hipHostMalloc(&c->h_line_upload, upload, hipHostMallocDefault));
-	step(e == hipSuccess ? hipStreamSynchronize(c->stream) : e);
-	if (e != hipSuccess) {
-		c->last_err = std::string("gas_ctx_reserve_fx_lines: ") + hipGetErrorString(e);
-		std::lock_guard<std::mutex> lk(c->params_mu);
-		release_fx_lines(c);
-		return e == hipErrorOutOfMemory ? GAS_ERR_OUT_OF_MEMORY : GAS_ERR_DEVICE;
-	}
-	std::lock_guard<std::mutex> lk(c->params_mu);
-	c->line_geo = geo;
-	c->line_cap[0] = delay_lines;
-	c->line_cap[1] = reverb_lines;
-	for (int p = 0; p < 2; p++) { // handed out from line 0 up
-		const uint32_t n = p == 0 ? delay_lines : reverb_lines;
-		c->line_zero_pending[p].assign(n, 0);
-		c->line_free[p].resize(n);
-		for (uint32_t i = 0; i < n; i++) {
-			c->line_free[p][i] = n - 1 - i;
-		}
-	}
-	std::array<int32_t, GAS_MAX_EFFECTS> none;
-	none.fill(-1);
-	c->h_line_of.assign(N, none);
-	c->h_line = std::move(defaults);
-	c->line_dirty_flag.assign(N, 0);
-	return GAS_OK;
+	return fx_reserve(c, FX_LINES, delay_lines, reverb_lines);
 }
 
 int gas_fx_eq_settings_publish(gas_ctx *c, const uint32_t *slots, const gas_fx_eq_settings *settings, uint32_t n) {
-	if (!c || (n > 0 && (!slots || !settings))) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	for (uint32_t i = 0; i < n; i++) {
-		if (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used) {
-			return GAS_ERR_BAD_SLOT;
-		}
-		if (!gas_fx_eq_settings_valid(settings[i])) {
-			return GAS_ERR_INVALID_ARGUMENT;
-		}
-	}
-	std::lock_guard<std::mutex> lk(c->params_mu);
-	if (c->h_eq.empty()) { // no pool reserved: no slot has an equaliser the settings could reach
-		return GAS_OK;
-	}
-	for (uint32_t i = 0; i < n; i++) {
-		c->h_eq[slots[i]] = settings[i];
-		eq_mark_dirty(c, slots[i]);
-	}
-	return GAS_OK;
+	return fx_publish(c, FX_EQ, slots, settings, n);
 }
 
 int gas_ctx_reserve_fx_eq(gas_ctx *c, uint32_t eq_banks) {
-	if (!c) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	std::lock_guard<std::mutex> alloc_lk(c->alloc_mu);
-	if (c->eq_free.size() != c->eq_cap) {
-		return GAS_ERR_INVALID_ARGUMENT; // banks are held
-	}
-	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	GAS_HIP(c, hipStreamSynchronize(c->stream));
-	{
-		std::lock_guard<std::mutex> lk(c->params_mu);
-		release_fx_eq(c);
-	}
-	if (eq_banks == 0) {
-		return GAS_OK;
-	}
-	const size_t N = c->cfg.max_sources;
-	// [<= N settings rows][<= N {slot, bank[4]}][<= every bank once] (eq_mark_dirty / eq_queue_zero)
-	const size_t upload = N * (sizeof(gas_fx_eq_settings) + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t)) + (size_t)eq_banks * sizeof(uint32_t);
-	std::vector<gas_fx_eq_settings> defaults(N, gas_fx_eq_settings{});
-	hipError_t e = hipSuccess;
-	auto step = [&e](hipError_t r) {
-		if (e == hipSuccess) {
-			e = r;
-		}
-	};
-	step(hipMalloc(&c->st.eq_pool, sizeof(float) * GAS_EQ_BANK_FLOATS * eq_banks));
-	step(e == hipSuccess ? hipMemsetAsync(c->st.eq_pool, 0, sizeof(float) * GAS_EQ_BANK_FLOATS * eq_banks, c->stream) : e);
-	step(hipMalloc(&c->st.eq_of, sizeof(int32_t) * GAS_MAX_EFFECTS * N));
-	step(e == hipSuccess ? hipMemsetAsync(c->st.eq_of, 0xff, sizeof(int32_t) * GAS_MAX_EFFECTS * N, c->stream) : e);
-	step(hipMalloc(&c->st.eq_settings, sizeof(gas_fx_eq_settings) * N));
-	step(e == hipSuccess ? hipMemsetAsync(c->st.eq_settings, 0, sizeof(gas_fx_eq_settings) * N, c->stream) : e);
-	step(hipMalloc(&c->d_eq_upload, upload));
-	step(hipHostMalloc(&c->h_eq_upload, upload, hipHostMallocDefault));
-	step(e == hipSuccess ? hipStreamSynchronize(c->stream) : e);
-	if (e != hipSuccess) {
-		c->last_err = std::string("gas_ctx_reserve_fx_eq: ") + hipGetErrorString(e);
-		std::lock_guard<std::mutex> lk(c->params_mu);
-		release_fx_eq(c);
-		return e == hipErrorOutOfMemory ? GAS_ERR_OUT_OF_MEMORY : GAS_ERR_DEVICE;
-	}
-	std::lock_guard<std::mutex> lk(c->params_mu);
-	for (int k = 0; k < 3; k++) {
-		c->eq_coefs[k] = make_eq_coefs(GAS_FX_EQ6 + k, c->cfg.mix_rate);
-	}
-	c->eq_cap = eq_banks;
-	c->eq_zero_pending.assign(eq_banks, 0);
-	c->eq_free.resize(eq_banks);
-	for (uint32_t i = 0; i < eq_banks; i++) { // handed out from bank 0 up
-		c->eq_free[i] = eq_banks - 1 - i;
-	}
-	std::array<int32_t, GAS_MAX_EFFECTS> none;
-	none.fill(-1);
-	c->h_eq_of.assign(N, none);
-	c->h_eq = std::move(defaults);
-	c->eq_dirty_flag.assign(N, 0);
-	return GAS_OK;
+	return fx_reserve(c, FX_EQ, eq_banks, 0);
 }
 
 int gas_fx_filter_settings_publish(gas_ctx *c, const uint32_t *slots, const gas_fx_filter_settings *settings, uint32_t n) {
-	if (!c || (n > 0 && (!slots || !settings))) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	for (uint32_t i = 0; i < n; i++) {
-		if (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used) {
-			return GAS_ERR_BAD_SLOT;
-		}
-		if (!gas_fx_filter_settings_valid(settings[i])) {
-			return GAS_ERR_INVALID_ARGUMENT;
-		}
-	}
-	std::lock_guard<std::mutex> lk(c->params_mu);
-	if (c->h_flt.empty()) { // no pool reserved: no slot has a GAS_FX_FILTER the settings could reach
-		return GAS_OK;
-	}
-	for (uint32_t i = 0; i < n; i++) {
-		c->h_flt[slots[i]] = settings[i];
-		flt_mark_dirty(c, slots[i]);
-	}
-	return GAS_OK;
+	return fx_publish(c, FX_FILTER, slots, settings, n);
 }
 
 int gas_ctx_reserve_fx_filter(gas_ctx *c, uint32_t banks) {
-	if (!c) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	std::lock_guard<std::mutex> alloc_lk(c->alloc_mu);
-	if (c->flt_free.size() != c->flt_cap) {
-		return GAS_ERR_INVALID_ARGUMENT; // banks are held
-	}
-	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	GAS_HIP(c, hipStreamSynchronize(c->stream));
-	{
-		std::lock_guard<std::mutex> lk(c->params_mu);
-		release_fx_filter(c);
-	}
-	if (banks == 0) {
-		return GAS_OK;
-	}
-	const size_t N = c->cfg.max_sources;
-	// [<= N settings rows][<= N {slot, bank[4]}][<= every bank once] (flt_mark_dirty / flt_queue_zero)
-	const size_t upload = N * (sizeof(gas_fx_filter_settings) + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t)) + (size_t)banks * sizeof(uint32_t);
-	std::vector<gas_fx_filter_settings> defaults(N, gas_fx_filter_settings_defaults());
-	hipError_t e = hipSuccess;
-	auto step = [&e](hipError_t r) {
-		if (e == hipSuccess) {
-			e = r;
-		}
-	};
-	step(hipMalloc(&c->st.flt_pool, sizeof(float) * GAS_FILTER_BANK_FLOATS * banks));
-	step(e == hipSuccess ? hipMemsetAsync(c->st.flt_pool, 0, sizeof(float) * GAS_FILTER_BANK_FLOATS * banks, c->stream) : e);
-	step(hipMalloc(&c->st.flt_of, sizeof(int32_t) * GAS_MAX_EFFECTS * N));
-	step(e == hipSuccess ? hipMemsetAsync(c->st.flt_of, 0xff, sizeof(int32_t) * GAS_MAX_EFFECTS * N, c->stream) : e);
-	step(hipMalloc(&c->st.flt_settings, sizeof(gas_fx_filter_settings) * N));
-	step(e == hipSuccess ? hipMemcpyAsync(c->st.flt_settings, defaults.data(), sizeof(gas_fx_filter_settings) * N, hipMemcpyHostToDevice, c->stream) : e);
-	step(hipMalloc(&c->d_flt_upload, upload));
-	step(hipHostMalloc(&c->h_flt_upload, upload, hipHostMallocDefault));
-	step(e == hipSuccess ? hipStreamSynchronize(c->stream) : e);
-	if (e != hipSuccess) {
-		c->last_err = std::string("gas_ctx_reserve_fx_filter: ") + hipGetErrorString(e);
-		std::lock_guard<std::mutex> lk(c->params_mu);
-		release_fx_filter(c);
-		return e == hipErrorOutOfMemory ? GAS_ERR_OUT_OF_MEMORY : GAS_ERR_DEVICE;
-	}
-	std::lock_guard<std::mutex> lk(c->params_mu);
-	c->flt_cap = banks;
-	c->flt_zero_pending.assign(banks, 0);
-	c->flt_free.resize(banks);
-	for (uint32_t i = 0; i < banks; i++) { // handed out from bank 0 up
-		c->flt_free[i] = banks - 1 - i;
-	}
-	std::array<int32_t, GAS_MAX_EFFECTS> none;
-	none.fill(-1);
-	c->h_flt_of.assign(N, none);
-	c->h_flt = std::move(defaults);
-	c->flt_dirty_flag.assign(N, 0);
-	return GAS_OK;
+	return fx_reserve(c, FX_FILTER, banks, 0);
 }
 
 int gas_fx_mod_settings_publish(gas_ctx *c, const uint32_t *slots, const gas_fx_mod_settings *settings, uint32_t n) {
-	if (!c || (n > 0 && (!slots || !settings))) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	for (uint32_t i = 0; i < n; i++) {
-		if (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used) {
-			return GAS_ERR_BAD_SLOT;
-		}
-		if (!gas_fx_mod_settings_valid(settings[i])) {
-			return GAS_ERR_INVALID_ARGUMENT;
-		}
-	}
-	std::lock_guard<std::mutex> lk(c->params_mu);
-	if (c->h_mod.empty()) { // no pool reserved: no slot has a chorus or phaser the settings could reach
-		return GAS_OK;
-	}
-	for (uint32_t i = 0; i < n; i++) {
-		c->h_mod[slots[i]] = settings[i];
-		mod_mark_dirty(c, slots[i]);
-	}
-	return GAS_OK;
-}
-
-// [ENGINE] AudioEffectChorus's ring: 1 << bitlength((int)(0.24 sr)) frames
-static uint32_t chorus_ring_frames(double sr) {
-	const uint32_t n = (uint32_t)(int)(0.24 * sr);
-	uint32_t bits = 0;
-	while (bits < 31 && (n >> bits) != 0) {
-		bits++;
-	}
-	return 1u << bits;
+	return fx_publish(c, FX_MOD, slots, settings, n);
 }
 
 int gas_ctx_reserve_fx_mod(gas_ctx *c, uint32_t chorus_lines, uint32_t phaser_banks) {
-	if (!c) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	const double sr = (double)c->cfg.mix_rate;
-	const uint32_t R = chorus_ring_frames(sr);
-	if (chorus_lines > 0 && (long)R < lrint(0.05 * sr) + 2L * (int)(0.02 * sr) + 12 + (long)c->cfg.frames) {
-		return GAS_ERR_INVALID_ARGUMENT; // one block's ring writes could overtake its own oldest read
-	}
-	std::lock_guard<std::mutex> alloc_lk(c->alloc_mu);
-	for (int p = 0; p < 2; p++) {
-		if (c->mod_free[p].size() != c->mod_cap[p]) {
-			return GAS_ERR_INVALID_ARGUMENT; // lines or banks are held
-		}
-	}
-	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	GAS_HIP(c, hipStreamSynchronize(c->stream));
-	{
-		std::lock_guard<std::mutex> lk(c->params_mu);
-		release_fx_mod(c);
-	}
-	if (chorus_lines == 0 && phaser_banks == 0) {
-		return GAS_OK;
-	}
-	const size_t N = c->cfg.max_sources;
-	const size_t line_floats = GAS_CHORUS_HEADER + 2 * (size_t)R;
-	// [<= N settings rows][<= N {slot, index[4]}][<= every line and bank once {kind, index}] (mod_mark_dirty / mod_queue_zero)
-	const size_t upload = N * (sizeof(gas_fx_mod_settings) + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t)) + ((size_t)chorus_lines + phaser_banks) * 2 * sizeof(uint32_t);
-	std::vector<gas_fx_mod_settings> defaults(N, gas_fx_mod_settings_defaults());
-	hipError_t e = hipSuccess;
-	auto step = [&e](hipError_t r) {
-		if (e == hipSuccess) {
-			e = r;
-		}
-	};
-	if (chorus_lines) {
-		step(hipMalloc(&c->st.chorus_pool, line_floats * sizeof(float) * chorus_lines));
-		step(e == hipSuccess ? hipMemsetAsync(c->st.chorus_pool, 0, line_floats * sizeof(float) * chorus_lines, c->stream) : e);
-	}
-	if (phaser_banks) {
-		step(hipMalloc(&c->st.phaser_pool, sizeof(float) * GAS_PHASER_BANK_FLOATS * phaser_banks));
-		step(e == hipSuccess ? hipMemsetAsync(c->st.phaser_pool, 0, sizeof(float) * GAS_PHASER_BANK_FLOATS * phaser_banks, c->stream) : e);
-	}
-	step(hipMalloc(&c->st.mod_of, sizeof(int32_t) * GAS_MAX_EFFECTS * N));
-	step(e == hipSuccess ? hipMemsetAsync(c->st.mod_of, 0xff, sizeof(int32_t) * GAS_MAX_EFFECTS * N, c->stream) : e);
-	step(hipMalloc(&c->st.mod_settings, sizeof(gas_fx_mod_settings) * N));
-	step(e == hipSuccess ? hipMemcpy(c->st.mod_settings, defaults.data(), sizeof(gas_fx_mod_settings) * N, hipMemcpyHostToDevice) : e);
-	step(hipMalloc(&c->d_mod_upload, upload));
-	step(hipHostMalloc(&c->h_mod_upload, upload, hipHostMallocDefault));
-	step(e == hipSuccess ? hipStreamSynchronize(c->stream) : e);
-	if (e != hipSuccess) {
-		c->last_err = std::string("gas_ctx_reserve_fx_mod: ") + hipGetErrorString(e);
-		std::lock_guard<std::mutex> lk(c->params_mu);
-		release_fx_mod(c);
-		return e == hipErrorOutOfMemory ? GAS_ERR_OUT_OF_MEMORY : GAS_ERR_DEVICE;
-	}
-	std::lock_guard<std::mutex> lk(c->params_mu);
-	c->st.chorus_mask = R - 1;
-	c->mod_cap[0] = chorus_lines;
-	c->mod_cap[1] = phaser_banks;
-	for (int p = 0; p < 2; p++) { // handed out from entry 0 up
-		const uint32_t n = p == 0 ? chorus_lines : phaser_banks;
-		c->mod_zero_pending[p].assign(n, 0);
-		c->mod_free[p].resize(n);
-		for (uint32_t i = 0; i < n; i++) {
-			c->mod_free[p][i] = n - 1 - i;
-		}
-	}
-	std::array<int32_t, GAS_MAX_EFFECTS> none;
-	none.fill(-1);
-	c->h_mod_of.assign(N, none);
-	c->h_mod = std::move(defaults);
-	c->mod_dirty_flag.assign(N, 0);
-	return GAS_OK;
+	return fx_reserve(c, FX_MOD, chorus_lines, phaser_banks);
 }
 
 int gas_fx_stereo_settings_publish(gas_ctx *c, const uint32_t *slots, const gas_fx_stereo_settings *settings, uint32_t n) {
-	if (!c || (n > 0 && (!slots || !settings))) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	for (uint32_t i = 0; i < n; i++) {
-		if (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used) {
-			return GAS_ERR_BAD_SLOT;
-		}
-		if (!gas_fx_stereo_settings_valid(settings[i])) {
-			return GAS_ERR_INVALID_ARGUMENT;
-		}
-	}
-	std::lock_guard<std::mutex> lk(c->params_mu);
-	for (uint32_t i = 0; i < n; i++) {
-		c->h_stereo[slots[i]] = settings[i];
-		stereo_mark_dirty(c, slots[i]);
-	}
-	return GAS_OK;
-}
-
-// [ENGINE] AudioEffectStereoEnhance's ring: 1 << bitlength((int)((50 + 2) / 1000 sr)) frames
-static uint32_t enhance_ring_frames(double sr) {
-	const uint32_t n = (uint32_t)(int)((50.0 + 2.0) / 1000.0 * sr);
-	uint32_t bits = 0;
-	while (bits < 31 && (n >> bits) != 0) {
-		bits++;
-	}
-	return 1u << bits;
+	return fx_publish(c, FX_STEREO, slots, settings, n);
 }
 
 int gas_ctx_reserve_fx_stereo(gas_ctx *c, uint32_t enhance_rings) {
-	if (!c) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	const uint32_t R = enhance_ring_frames((double)c->cfg.mix_rate);
-	if (enhance_rings > 0 && (R < c->cfg.frames || R < 4)) {
-		return GAS_ERR_INVALID_ARGUMENT; // two frames of one block would share a ring entry
-	}
-	std::lock_guard<std::mutex> alloc_lk(c->alloc_mu);
-	if (c->ring_free.size() != c->ring_cap) {
-		return GAS_ERR_INVALID_ARGUMENT; // rings are held
-	}
-	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	GAS_HIP(c, hipStreamSynchronize(c->stream));
-	{
-		std::lock_guard<std::mutex> lk(c->params_mu);
-		release_fx_stereo_pool(c);
-	}
-	const size_t ring_floats = GAS_ENHANCE_HEADER + (size_t)R;
-	hipError_t e = hipSuccess;
-	{
-		// (the staging buffer may hold queued settings rows only in the mirror: flush_fx_stereo fills it per flush)
-		std::lock_guard<std::mutex> lk(c->params_mu);
-		e = alloc_stereo_upload(c, enhance_rings);
-	}
-	if (e == hipSuccess && enhance_rings) {
-		e = hipMalloc(&c->st.enhance_pool, ring_floats * sizeof(float) * enhance_rings);
-		e = e != hipSuccess ? e : hipMemsetAsync(c->st.enhance_pool, 0, ring_floats * sizeof(float) * enhance_rings, c->stream);
-		e = e != hipSuccess ? e : hipStreamSynchronize(c->stream);
-	}
-	if (e != hipSuccess) {
-		c->last_err = std::string("gas_ctx_reserve_fx_stereo: ") + hipGetErrorString(e);
-		std::lock_guard<std::mutex> lk(c->params_mu);
-		release_fx_stereo_pool(c);
-		if (!c->h_stereo_upload || !c->d_stereo_upload) {
-			(void)alloc_stereo_upload(c, 0);
-		}
-		return e == hipErrorOutOfMemory ? GAS_ERR_OUT_OF_MEMORY : GAS_ERR_DEVICE;
-	}
-	if (enhance_rings == 0) {
-		return GAS_OK;
-	}
-	std::lock_guard<std::mutex> lk(c->params_mu);
-	c->st.enhance_mask = R - 1;
-	c->ring_cap = enhance_rings;
-	c->ring_zero_pending.assign(enhance_rings, 0);
-	c->ring_free.resize(enhance_rings);
-	for (uint32_t i = 0; i < enhance_rings; i++) { // handed out from ring 0 up
-		c->ring_free[i] = enhance_rings - 1 - i;
-	}
-	return GAS_OK;
+	return fx_reserve(c, FX_STEREO, enhance_rings, 0);
 }
 
 int gas_params_publish_batch(gas_ctx *c, const uint32_t *slots, const gas_params *params, uint32_t n, int params_mem) {
@@ -3105,10 +2501,7 @@ int gas_params_publish_batch(gas_ctx *c, const uint32_t *slots, const gas_params
 		for (uint32_t i = 0; i < n; i++) {
 			const uint32_t s = slots[i];
 			c->h_params[s] = params[i];
-			if (!c->dirty_flag[s]) {
-				c->dirty_flag[s] = 1;
-				c->dirty_list.push_back(s);
-			}
+			mark_dirty(c->dirty_flag, c->dirty_list, s);
 			c->slots[s].has_params = 1;
 		}
 		return GAS_OK;

@@ -183,25 +183,6 @@ __global__ __launch_bounds__(NT) void k_fx_eq(gas_group_args g, gas_dev_state st
 	}
 }
 
-constexpr uint32_t EPIECES = sizeof(gas_fx_eq_settings) / 16; // 21 lanes move one POD as 16-byte pieces
-
-__global__ void k_scatter_eq(gas_dev_state st, const gas_fx_eq_settings *__restrict__ upload, const uint32_t *__restrict__ slot_banks, uint32_t n) {
-	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-	const uint32_t e = t / (EPIECES + 1), part = t % (EPIECES + 1);
-	if (e >= n) {
-		return;
-	}
-	const uint32_t *sb = slot_banks + (size_t)e * (1 + GAS_MAX_EFFECTS);
-	const uint32_t slot = sb[0];
-	if (part < EPIECES) {
-		reinterpret_cast<float4 *>(st.eq_settings + slot)[part] = reinterpret_cast<const float4 *>(upload + e)[part];
-	} else {
-		for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
-			st.eq_of[(size_t)j * st.dyn_stride + slot] = (int32_t)sb[1 + j];
-		}
-	}
-}
-
 __global__ void k_zero_banks(gas_dev_state st, const uint32_t *__restrict__ banks, uint32_t n) {
 	constexpr uint32_t Q = GAS_EQ_BANK_FLOATS / 4; // float4 per bank
 	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -237,15 +218,6 @@ hipError_t gas_launch_fx_eq(hipStream_t stream, int kind, const gas_group_args &
 		default:
 			return hipErrorInvalidValue;
 	}
-	return hipGetLastError();
-}
-
-hipError_t gas_launch_scatter_eq(hipStream_t stream, const gas_dev_state &st, const gas_fx_eq_settings *upload, const uint32_t *slot_banks, uint32_t n) {
-	if (n == 0) {
-		return hipSuccess;
-	}
-	const uint32_t threads = n * (EPIECES + 1);
-	hipLaunchKernelGGL(k_scatter_eq, dim3((threads + 255) / 256), dim3(256), 0, stream, st, upload, slot_banks, n);
 	return hipGetLastError();
 }
 

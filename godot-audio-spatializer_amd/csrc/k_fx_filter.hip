@@ -271,25 +271,6 @@ __global__ __launch_bounds__(NT) void k_fx_filter(gas_group_args g, gas_dev_stat
 	}
 }
 
-constexpr uint32_t FPIECES = sizeof(gas_fx_filter_settings) / 16; // 8 lanes move one POD as 16-byte pieces
-
-__global__ void k_scatter_filter(gas_dev_state st, const gas_fx_filter_settings *__restrict__ upload, const uint32_t *__restrict__ slot_banks, uint32_t n) {
-	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-	const uint32_t e = t / (FPIECES + 1), part = t % (FPIECES + 1);
-	if (e >= n) {
-		return;
-	}
-	const uint32_t *sb = slot_banks + (size_t)e * (1 + GAS_MAX_EFFECTS);
-	const uint32_t slot = sb[0];
-	if (part < FPIECES) {
-		reinterpret_cast<float4 *>(st.flt_settings + slot)[part] = reinterpret_cast<const float4 *>(upload + e)[part];
-	} else {
-		for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
-			st.flt_of[(size_t)j * st.dyn_stride + slot] = (int32_t)sb[1 + j];
-		}
-	}
-}
-
 __global__ void k_zero_filter_banks(gas_dev_state st, const uint32_t *__restrict__ banks, uint32_t n) {
 	constexpr uint32_t Q = GAS_FILTER_BANK_FLOATS / 4; // float4 per bank
 	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -308,15 +289,6 @@ hipError_t gas_launch_fx_filter(hipStream_t stream, const gas_group_args &g, con
 		return hipErrorInvalidValue;
 	}
 	hipLaunchKernelGGL(k_fx_filter, dim3((g.n + S - 1) / S), dim3(NT), 0, stream, g, st, frames, chain_pos, mix_rate, reinterpret_cast<float *>(rows_out));
-	return hipGetLastError();
-}
-
-hipError_t gas_launch_scatter_filter(hipStream_t stream, const gas_dev_state &st, const gas_fx_filter_settings *upload, const uint32_t *slot_banks, uint32_t n) {
-	if (n == 0) {
-		return hipSuccess;
-	}
-	const uint32_t threads = n * (FPIECES + 1);
-	hipLaunchKernelGGL(k_scatter_filter, dim3((threads + 255) / 256), dim3(256), 0, stream, st, upload, slot_banks, n);
 	return hipGetLastError();
 }
 

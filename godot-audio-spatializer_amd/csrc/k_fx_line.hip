@@ -536,27 +536,8 @@ __global__ __launch_bounds__(RNT) void k_fx_reverb(gas_group_args g, gas_dev_sta
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// settings scatter and line zeroing
+// line zeroing (the settings scatter is k_misc.hip's k_scatter_fx)
 // ---------------------------------------------------------------------------------------------------------------
-constexpr uint32_t LPIECES = sizeof(gas_fx_line_settings) / 16;
-
-__global__ void k_scatter_line(gas_dev_state st, const gas_fx_line_settings *__restrict__ upload, const uint32_t *__restrict__ slot_lines, uint32_t n) {
-	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-	const uint32_t e = t / (LPIECES + 1), part = t % (LPIECES + 1);
-	if (e >= n) {
-		return;
-	}
-	const uint32_t *sl = slot_lines + (size_t)e * (1 + GAS_MAX_EFFECTS);
-	const uint32_t slot = sl[0];
-	if (part < LPIECES) {
-		reinterpret_cast<float4 *>(st.line_settings + slot)[part] = reinterpret_cast<const float4 *>(upload + e)[part];
-	} else {
-		for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
-			st.line_of[(size_t)j * st.dyn_stride + slot] = (int32_t)sl[1 + j];
-		}
-	}
-}
-
 __global__ void k_zero_lines(gas_dev_state st, gas_line_geo geo, const uint32_t *__restrict__ kind_line, uint32_t n) {
 	const uint32_t e = blockIdx.x; // line; blockIdx.y = chunk
 	if (e >= n) {
@@ -588,15 +569,6 @@ hipError_t gas_launch_fx_line(hipStream_t stream, int kind, const gas_group_args
 	} else {
 		return hipErrorInvalidValue;
 	}
-	return hipGetLastError();
-}
-
-hipError_t gas_launch_scatter_line(hipStream_t stream, const gas_dev_state &st, const gas_fx_line_settings *upload, const uint32_t *slot_lines, uint32_t n) {
-	if (n == 0) {
-		return hipSuccess;
-	}
-	const uint32_t threads = n * (LPIECES + 1);
-	hipLaunchKernelGGL(k_scatter_line, dim3((threads + 255) / 256), dim3(256), 0, stream, st, upload, slot_lines, n);
 	return hipGetLastError();
 }
 

@@ -408,27 +408,8 @@ __global__ __launch_bounds__(PNT) void k_fx_phaser(gas_group_args g, gas_dev_sta
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// settings scatter and zeroing
+// zeroing of pool entries (the settings scatter is k_misc.hip's k_scatter_fx)
 // ---------------------------------------------------------------------------------------------------------------
-constexpr uint32_t MPIECES = sizeof(gas_fx_mod_settings) / 16; // lanes move one POD as 16-byte pieces
-
-__global__ void k_scatter_mod(gas_dev_state st, const gas_fx_mod_settings *__restrict__ upload, const uint32_t *__restrict__ slot_idx, uint32_t n) {
-	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-	const uint32_t e = t / (MPIECES + 1), part = t % (MPIECES + 1);
-	if (e >= n) {
-		return;
-	}
-	const uint32_t *sb = slot_idx + (size_t)e * (1 + GAS_MAX_EFFECTS);
-	const uint32_t slot = sb[0];
-	if (part < MPIECES) {
-		reinterpret_cast<float4 *>(st.mod_settings + slot)[part] = reinterpret_cast<const float4 *>(upload + e)[part];
-	} else {
-		for (int q = 0; q < GAS_MAX_EFFECTS; q++) {
-			st.mod_of[(size_t)q * st.dyn_stride + slot] = (int32_t)sb[1 + q];
-		}
-	}
-}
-
 // one workgroup per {kind, index} pair
 __global__ void k_zero_mod(gas_dev_state st, const uint32_t *__restrict__ kind_idx) {
 	const uint32_t kind = kind_idx[2 * blockIdx.x], idx = kind_idx[2 * blockIdx.x + 1];
@@ -456,15 +437,6 @@ hipError_t gas_launch_fx_mod(hipStream_t stream, int kind, const gas_group_args 
 	} else {
 		return hipErrorInvalidValue;
 	}
-	return hipGetLastError();
-}
-
-hipError_t gas_launch_scatter_mod(hipStream_t stream, const gas_dev_state &st, const gas_fx_mod_settings *upload, const uint32_t *slot_idx, uint32_t n) {
-	if (n == 0) {
-		return hipSuccess;
-	}
-	const uint32_t threads = n * (MPIECES + 1);
-	hipLaunchKernelGGL(k_scatter_mod, dim3((threads + 255) / 256), dim3(256), 0, stream, st, upload, slot_idx, n);
 	return hipGetLastError();
 }
 

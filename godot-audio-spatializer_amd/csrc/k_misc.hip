@@ -4,6 +4,7 @@
 //                     also the zeroing of :335-343 when there is nothing to add)
 //   k_scatter_params  publish staged SpatializerParameters PODs into the slot-indexed table
 //                     (set_spatializer_parameters, audio_spatializer.cpp:558-564)
+//   k_scatter_fx      the same for a pooled effect family's settings PODs and slot -> pool entry rows
 //   k_zero_slot       fresh SpatializerPlaybackData for a (re)started playback (audio_spatializer.cpp:69)
 #include "gas_device.h"
 #include "gas_internal.h"
@@ -85,6 +86,25 @@ __global__ void k_scatter_params(gas_params *__restrict__ table, const gas_param
 		const float4 *s = reinterpret_cast<const float4 *>(upload + e);
 		float4 *d = reinterpret_cast<float4 *>(table + slots[e]);
 		d[part] = s[part];
+	}
+}
+
+// A pooled effect family's flush records into its two slot-indexed tables: pieces lanes move record e's settings POD as
+// 16-byte pieces, one more lane writes its GAS_MAX_EFFECTS pool entries ([GAS_MAX_EFFECTS][stride] table).
+__global__ void k_scatter_fx(float4 *__restrict__ settings_table, int32_t *__restrict__ of_table, uint32_t stride, uint32_t pieces, const float4 *__restrict__ upload, const uint32_t *__restrict__ slot_idx, uint32_t n) {
+	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+	const uint32_t e = t / (pieces + 1), part = t % (pieces + 1);
+	if (e >= n) {
+		return;
+	}
+	const uint32_t *si = slot_idx + (size_t)e * (1 + GAS_MAX_EFFECTS);
+	const uint32_t slot = si[0];
+	if (part < pieces) {
+		settings_table[(size_t)slot * pieces + part] = upload[(size_t)e * pieces + part];
+	} else {
+		for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
+			of_table[(size_t)j * stride + slot] = (int32_t)si[1 + j];
+		}
 	}
 }
 
@@ -506,6 +526,19 @@ hipError_t gas_launch_scatter_params(hipStream_t stream, gas_params *table, cons
 	}
 	const uint32_t threads = n * 8;
 	hipLaunchKernelGGL(k_scatter_params, dim3((threads + 255) / 256), dim3(256), 0, stream, table, upload, slots, n);
+	return hipGetLastError();
+}
+
+hipError_t gas_launch_scatter_fx(hipStream_t stream, void *settings_table, int32_t *of_table, uint32_t stride, uint32_t pod_bytes, const void *upload, const uint32_t *slot_idx, uint32_t n) {
+	if (n == 0) {
+		return hipSuccess;
+	}
+	if (pod_bytes == 0 || pod_bytes % 16 != 0 || !settings_table || !of_table) {
+		return hipErrorInvalidValue;
+	}
+	const uint32_t pieces = pod_bytes / 16;
+	const uint32_t threads = n * (pieces + 1);
+	hipLaunchKernelGGL(k_scatter_fx, dim3((threads + 255) / 256), dim3(256), 0, stream, static_cast<float4 *>(settings_table), of_table, stride, pieces, static_cast<const float4 *>(upload), slot_idx, n);
 	return hipGetLastError();
 }
 

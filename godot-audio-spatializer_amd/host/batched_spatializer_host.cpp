@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/gas_amd_host.h"
+#include "../csrc/gas_fx_dyn_check.h"
 #include "../csrc/gas_fx_eq_check.h"
 #include "../csrc/gas_fx_line_check.h"
 #include "../csrc/gas_fx_mod_check.h"
@@ -212,6 +213,35 @@ struct gas_host {
 		graveyard.push_back(std::move(pb));
 	}
 
+	// A queued settings row goes to its playback's slot, if the playback is still there (rows were validated when they
+	// were queued) and the library has the entry (see the weak references above).
+	template <class S>
+	void publish_settings(const Command &c, S Command::*row, int (*publish)(gas_ctx *, const uint32_t *, const S *, uint32_t)) {
+		auto it = by_id.find(c.id);
+		if (it != by_id.end() && publish) {
+			publish(ctx, &it->second->slot, &(c.*row), 1);
+		}
+	}
+
+	// What every gas_host_set_effect_settings* does: the library's own rule is checked here, on the control thread,
+	// because the audio thread that publishes the row cannot report it.
+	template <class S>
+	int queue_settings(uint32_t id, const S *settings, bool (*valid)(const S &), Command::Kind kind, S Command::*row) {
+		if (!lookup(id)) {
+			return GAS_ERR_BAD_SLOT;
+		}
+		if (!settings || (valid && !valid(*settings))) {
+			return GAS_ERR_INVALID_ARGUMENT;
+		}
+		Command c;
+		c.kind = kind;
+		c.id = id;
+		c.*row = *settings;
+		std::lock_guard<std::mutex> lk(inbox_mu);
+		inbox.push_back(std::move(c));
+		return GAS_OK;
+	}
+
 	// New playbacks and parameters queued since the last callback, in the order they were issued.
 	void adopt_inbox() {
 		batch.clear();
@@ -239,41 +269,20 @@ struct gas_host {
 				// request mixes; here a playback is only ever adopted inside the request that starts a new mix)
 				by_id[pb->id] = pb.get();
 				list.push_back(std::move(pb)); // newest = last (walked from the back)
-			} else if (c.kind == Command::FX_SETTINGS) {
-				auto it = by_id.find(c.id);
-				if (it != by_id.end()) {
-					gas_fx_settings_publish(ctx, &it->second->slot, &c.fx_settings, 1); // snapshotted with the parameters (:328)
-				}
+			} else if (c.kind == Command::FX_SETTINGS) { // snapshotted with the parameters (:328)
+				publish_settings(c, &Command::fx_settings, gas_fx_settings_publish);
 			} else if (c.kind == Command::FX_DYN_SETTINGS) {
-				auto it = by_id.find(c.id);
-				if (it != by_id.end() && gas_fx_dyn_settings_publish) {
-					gas_fx_dyn_settings_publish(ctx, &it->second->slot, &c.fx_dyn_settings, 1); // (validated when queued)
-				}
+				publish_settings(c, &Command::fx_dyn_settings, gas_fx_dyn_settings_publish);
 			} else if (c.kind == Command::FX_LINE_SETTINGS) {
-				auto it = by_id.find(c.id);
-				if (it != by_id.end() && gas_fx_line_settings_publish) {
-					gas_fx_line_settings_publish(ctx, &it->second->slot, &c.fx_line_settings, 1); // (validated when queued)
-				}
+				publish_settings(c, &Command::fx_line_settings, gas_fx_line_settings_publish);
 			} else if (c.kind == Command::FX_EQ_SETTINGS) {
-				auto it = by_id.find(c.id);
-				if (it != by_id.end() && gas_fx_eq_settings_publish) {
-					gas_fx_eq_settings_publish(ctx, &it->second->slot, &c.fx_eq_settings, 1); // (validated when queued)
-				}
+				publish_settings(c, &Command::fx_eq_settings, gas_fx_eq_settings_publish);
 			} else if (c.kind == Command::FX_MOD_SETTINGS) {
-				auto it = by_id.find(c.id);
-				if (it != by_id.end() && gas_fx_mod_settings_publish) {
-					gas_fx_mod_settings_publish(ctx, &it->second->slot, &c.fx_mod_settings, 1); // (validated when queued)
-				}
+				publish_settings(c, &Command::fx_mod_settings, gas_fx_mod_settings_publish);
 			} else if (c.kind == Command::FX_STEREO_SETTINGS) {
-				auto it = by_id.find(c.id);
-				if (it != by_id.end() && gas_fx_stereo_settings_publish) {
-					gas_fx_stereo_settings_publish(ctx, &it->second->slot, &c.fx_stereo_settings, 1); // (validated when queued)
-				}
+				publish_settings(c, &Command::fx_stereo_settings, gas_fx_stereo_settings_publish);
 			} else if (c.kind == Command::FX_FILTER_SETTINGS) {
-				auto it = by_id.find(c.id);
-				if (it != by_id.end() && gas_fx_filter_settings_publish) {
-					gas_fx_filter_settings_publish(ctx, &it->second->slot, &c.fx_filter_settings, 1); // (validated when queued)
-				}
+				publish_settings(c, &Command::fx_filter_settings, gas_fx_filter_settings_publish);
 			} else {
 				auto it = by_id.find(c.id);
 				if (it == by_id.end()) {
@@ -562,135 +571,31 @@ int gas_host_set_spatializer_parameters(gas_host *h, uint32_t id, const gas_para
 }
 
 int gas_host_set_effect_settings(gas_host *h, uint32_t id, const gas_fx_settings *settings) {
-	if (!h || !h->lookup(id)) {
-		return GAS_ERR_BAD_SLOT;
-	}
-	if (!settings) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	Command c;
-	c.kind = Command::FX_SETTINGS;
-	c.id = id;
-	c.fx_settings = *settings;
-	std::lock_guard<std::mutex> lk(h->inbox_mu);
-	h->inbox.push_back(std::move(c));
-	return GAS_OK;
+	return h ? h->queue_settings<gas_fx_settings>(id, settings, nullptr, Command::FX_SETTINGS, &Command::fx_settings) : GAS_ERR_BAD_SLOT;
 }
 
 int gas_host_set_effect_settings_dyn(gas_host *h, uint32_t id, const gas_fx_dyn_settings *settings) {
-	if (!h || !h->lookup(id)) {
-		return GAS_ERR_BAD_SLOT;
-	}
-	if (!settings) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	for (int j = 0; j < GAS_MAX_EFFECTS; j++) { // gas_fx_dyn_settings_publish's rule, checked here: the audio thread cannot report it
-		if (settings->distortion_mode[j] < GAS_DISTORTION_CLIP || settings->distortion_mode[j] > GAS_DISTORTION_WAVESHAPE || !(settings->compressor_ratio[j] > 0.0f) || !(settings->compressor_attack_us[j] > 0.0f) || !(settings->compressor_release_ms[j] > 0.0f)) {
-			return GAS_ERR_INVALID_ARGUMENT;
-		}
-	}
-	Command c;
-	c.kind = Command::FX_DYN_SETTINGS;
-	c.id = id;
-	c.fx_dyn_settings = *settings;
-	std::lock_guard<std::mutex> lk(h->inbox_mu);
-	h->inbox.push_back(std::move(c));
-	return GAS_OK;
+	return h ? h->queue_settings(id, settings, gas_fx_dyn_settings_valid, Command::FX_DYN_SETTINGS, &Command::fx_dyn_settings) : GAS_ERR_BAD_SLOT;
 }
 
 int gas_host_set_effect_settings_line(gas_host *h, uint32_t id, const gas_fx_line_settings *settings) {
-	if (!h || !h->lookup(id)) {
-		return GAS_ERR_BAD_SLOT;
-	}
-	if (!settings) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (!gas_fx_line_settings_valid(*settings)) { // gas_fx_line_settings_publish's rule, checked here: the audio thread cannot report it
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	Command c;
-	c.kind = Command::FX_LINE_SETTINGS;
-	c.id = id;
-	c.fx_line_settings = *settings;
-	std::lock_guard<std::mutex> lk(h->inbox_mu);
-	h->inbox.push_back(std::move(c));
-	return GAS_OK;
+	return h ? h->queue_settings(id, settings, gas_fx_line_settings_valid, Command::FX_LINE_SETTINGS, &Command::fx_line_settings) : GAS_ERR_BAD_SLOT;
 }
 
 int gas_host_set_effect_settings_eq(gas_host *h, uint32_t id, const gas_fx_eq_settings *settings) {
-	if (!h || !h->lookup(id)) {
-		return GAS_ERR_BAD_SLOT;
-	}
-	if (!settings) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (!gas_fx_eq_settings_valid(*settings)) { // gas_fx_eq_settings_publish's rule, checked here: the audio thread cannot report it
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	Command c;
-	c.kind = Command::FX_EQ_SETTINGS;
-	c.id = id;
-	c.fx_eq_settings = *settings;
-	std::lock_guard<std::mutex> lk(h->inbox_mu);
-	h->inbox.push_back(std::move(c));
-	return GAS_OK;
+	return h ? h->queue_settings(id, settings, gas_fx_eq_settings_valid, Command::FX_EQ_SETTINGS, &Command::fx_eq_settings) : GAS_ERR_BAD_SLOT;
 }
 
 int gas_host_set_effect_settings_mod(gas_host *h, uint32_t id, const gas_fx_mod_settings *settings) {
-	if (!h || !h->lookup(id)) {
-		return GAS_ERR_BAD_SLOT;
-	}
-	if (!settings) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (!gas_fx_mod_settings_valid(*settings)) { // gas_fx_mod_settings_publish's rule, checked here: the audio thread cannot report it
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	Command c;
-	c.kind = Command::FX_MOD_SETTINGS;
-	c.id = id;
-	c.fx_mod_settings = *settings;
-	std::lock_guard<std::mutex> lk(h->inbox_mu);
-	h->inbox.push_back(std::move(c));
-	return GAS_OK;
+	return h ? h->queue_settings(id, settings, gas_fx_mod_settings_valid, Command::FX_MOD_SETTINGS, &Command::fx_mod_settings) : GAS_ERR_BAD_SLOT;
 }
 
 int gas_host_set_effect_settings_stereo(gas_host *h, uint32_t id, const gas_fx_stereo_settings *settings) {
-	if (!h || !h->lookup(id)) {
-		return GAS_ERR_BAD_SLOT;
-	}
-	if (!settings) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (!gas_fx_stereo_settings_valid(*settings)) { // gas_fx_stereo_settings_publish's rule, checked here: the audio thread cannot report it
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	Command c;
-	c.kind = Command::FX_STEREO_SETTINGS;
-	c.id = id;
-	c.fx_stereo_settings = *settings;
-	std::lock_guard<std::mutex> lk(h->inbox_mu);
-	h->inbox.push_back(std::move(c));
-	return GAS_OK;
+	return h ? h->queue_settings(id, settings, gas_fx_stereo_settings_valid, Command::FX_STEREO_SETTINGS, &Command::fx_stereo_settings) : GAS_ERR_BAD_SLOT;
 }
 
 int gas_host_set_effect_settings_filter(gas_host *h, uint32_t id, const gas_fx_filter_settings *settings) {
-	if (!h || !h->lookup(id)) {
-		return GAS_ERR_BAD_SLOT;
-	}
-	if (!settings) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (!gas_fx_filter_settings_valid(*settings)) { // gas_fx_filter_settings_publish's rule, checked here: the audio thread cannot report it
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	Command c;
-	c.kind = Command::FX_FILTER_SETTINGS;
-	c.id = id;
-	c.fx_filter_settings = *settings;
-	std::lock_guard<std::mutex> lk(h->inbox_mu);
-	h->inbox.push_back(std::move(c));
-	return GAS_OK;
+	return h ? h->queue_settings(id, settings, gas_fx_filter_settings_valid, Command::FX_FILTER_SETTINGS, &Command::fx_filter_settings) : GAS_ERR_BAD_SLOT;
 }
 
 void gas_host_set_playback_disable_threshold_db(gas_host *h, float db) {

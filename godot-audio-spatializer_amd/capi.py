@@ -251,6 +251,19 @@ def fx_filter_settings_defaults(n):
     return d
 
 
+# gas_hrtf_blend (GAS_FLAG_HRTF_INTERPOLATE): the HRIR rows one playback's HRTF stage blends; all-zero = no blend
+HRTF_BLEND_DTYPE = np.dtype([("dir", np.uint32, (4,)), ("weight", np.float32, (4,))])
+assert HRTF_BLEND_DTYPE.itemsize == 32
+
+
+class HrtfBlend(C.Structure):
+    """gas_hrtf_blend for callers that use ctypes directly."""
+
+    _fields_ = [("dir", C.c_uint32 * 4), ("weight", C.c_float * 4)]
+
+
+assert C.sizeof(HrtfBlend) == 32
+
 MEM_HOST = 0
 MEM_DEVICE = 1
 FLAG_PEAKS_DRAINING_ONLY = 1
@@ -260,6 +273,7 @@ FLAG_PIPELINED_MIX = 8
 FLAG_DIRECTION_RUNS = 16
 FLAG_XCD_ORDER = 32
 FLAG_BATCHED_LAUNCH = 64
+FLAG_HRTF_INTERPOLATE = 128
 
 STATUS = {
     0: "GAS_OK",
@@ -404,6 +418,7 @@ EXPORTS = [
     "gas_ctx_reserve_fx_filter",
     "gas_params_publish_batch",
     "gas_hrtf_load",
+    "gas_hrtf_blend_publish",
     "gas_hrtf_load_positions",
     "gas_calc_spatialization",
     "gas_calc_spatialization_areas",
@@ -496,6 +511,7 @@ def load_library():
     L.gas_ctx_reserve_fx_filter.argtypes = [vp, u32]
     L.gas_params_publish_batch.argtypes = [vp, vp, vp, u32, i32]
     L.gas_hrtf_load.argtypes = [vp, vp, u32, u32]
+    L.gas_hrtf_blend_publish.argtypes = [vp, vp, vp, u32]
     L.gas_hrtf_load_positions.argtypes = [vp, vp, vp, u32, u32, u32, u32, i32, vp]
     L.gas_stream_create.argtypes = [vp, vp, i32, u32, C.c_uint64, C.POINTER(u32)]
     L.gas_stream_destroy.argtypes = [vp, u32]
@@ -682,6 +698,13 @@ class SpatializerContext:
     def reserve_fx_filter(self, banks):
         """Size the GAS_FX_FILTER bank pool (main thread, not during a callback); 0 releases it."""
         self._check(self.lib.gas_ctx_reserve_fx_filter(self.h, int(banks)), "gas_ctx_reserve_fx_filter")
+
+    def publish_hrtf_blend(self, slots, blends):
+        """FLAG_HRTF_INTERPOLATE: the HRIR rows (HRTF_BLEND_DTYPE) the slots' HRTF stages blend from the next callback on."""
+        s = np.ascontiguousarray(slots, dtype=np.uint32)
+        b = np.ascontiguousarray(blends, dtype=HRTF_BLEND_DTYPE)
+        assert s.shape == b.shape
+        self._check(self.lib.gas_hrtf_blend_publish(self.h, _np_ptr(s), _np_ptr(b), len(s)), "gas_hrtf_blend_publish")
 
     def params_publish_batch(self, slots, params):
         s = np.ascontiguousarray(slots, dtype=np.uint32)
@@ -886,6 +909,7 @@ class BatchedSpatializerHost:
         L.gas_host_set_effect_settings_mod.argtypes = [vp, u32, vp]
         L.gas_host_set_effect_settings_stereo.argtypes = [vp, u32, vp]
         L.gas_host_set_effect_settings_filter.argtypes = [vp, u32, vp]
+        L.gas_host_set_hrtf_blend.argtypes = [vp, u32, vp]
         L.gas_host_set_release_fn.argtypes = [vp, vp, vp]
         L.gas_host_collect_released.argtypes = [vp]
         L.gas_host_set_process_effects_fn.argtypes = [vp, vp, vp]
@@ -991,6 +1015,10 @@ class BatchedSpatializerHost:
     def set_effect_settings_filter(self, pid, settings):
         f = np.ascontiguousarray(settings, dtype=FX_FILTER_SETTINGS_DTYPE).reshape(1)
         return self.lib.gas_host_set_effect_settings_filter(self.h, pid, _np_ptr(f))
+
+    def set_hrtf_blend(self, pid, blend):
+        b = np.ascontiguousarray(blend, dtype=HRTF_BLEND_DTYPE).reshape(1)
+        return self.lib.gas_host_set_hrtf_blend(self.h, pid, _np_ptr(b))
 
     def is_playback_active(self, pid):
         return bool(self.lib.gas_host_is_playback_active(self.h, pid))

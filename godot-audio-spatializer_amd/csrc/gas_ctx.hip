@@ -147,6 +147,12 @@ struct gas_ctx {
 	std::vector<uint8_t> fx_dirty_flag;
 	std::vector<uint32_t> fx_dirty_list;
 	gas_fx_settings *h_fx_upload = nullptr; // pinned, [max_sources], allocated by the first flush that needs it
+	// gas_hrtf_blend rows (GAS_FLAG_HRTF_INTERPOLATE): host mirror, latest wins, uploaded with the parameters the way
+	// gas_fx_settings are (params_mu); empty without the flag
+	std::vector<gas_hrtf_blend> h_blend;
+	std::vector<uint8_t> blend_dirty_flag;
+	std::vector<uint32_t> blend_dirty_list;
+	gas_hrtf_blend *h_blend_upload = nullptr; // pinned, [max_sources], allocated by the first flush that needs it
 	// gas_fx_dyn_settings (GAS_FX_DISTORTION / GAS_FX_COMPRESSOR): host mirror, latest wins (params_mu); uploaded as ONE
 	// copy of [m settings][m slots] out of a pinned staging buffer, then scattered on the device (k_scatter_dyn)
 	std::vector<gas_fx_dyn_settings> h_dyn;
@@ -324,7 +330,11 @@ int group_of(int kind, const int32_t *fx, uint32_t n_fx) {
 // The plain [HRTF] chain runs in k_hrtf_uni (one uniform launch, exact peaks per source on request) unless a mode
 // only k_hrtf_ols implements is on.
 inline bool uni_ok(const gas_ctx *c) {
-	return (c->cfg.flags & (GAS_FLAG_HRTF_CROSSFADE | GAS_FLAG_DIRECTION_RUNS | GAS_FLAG_DIRECTION_ORDER)) == 0;
+	return (c->cfg.flags & (GAS_FLAG_HRTF_CROSSFADE | GAS_FLAG_DIRECTION_RUNS | GAS_FLAG_DIRECTION_ORDER | GAS_FLAG_HRTF_INTERPOLATE)) == 0;
+}
+
+inline bool blend_on(const gas_ctx *c) {
+	return (c->cfg.flags & GAS_FLAG_HRTF_INTERPOLATE) != 0;
 }
 
 inline bool wants_peak(const gas_ctx *c, const SlotInfo &si) {
@@ -578,7 +588,7 @@ uint64_t group_bytes(const gas_ctx *c, int gt, uint32_t n) {
 			break;
 		case G_FX_HRTF:
 		case G_FX_HRTF_PK:
-			S = 24; // gain + dir, previous gain r/w, peak
+			S = 24 + (blend_on(c) ? sizeof(gas_hrtf_blend) : 0); // gain + dir, previous gain r/w, peak; the blend row
 			H = 2ull * c->hist_len * 4; // history read + write
 			tab = (uint64_t)c->tab.dirs * 2 * GAS_HRTF_TAPS * 4;
 			break;
@@ -588,7 +598,7 @@ uint64_t group_bytes(const gas_ctx *c, int gt, uint32_t n) {
 			break;
 		case G_FX_ER_HRTF:
 		case G_FX_ER_HRTF_PK:
-			S = 24 + 64 + 8;
+			S = 24 + 64 + 8 + (blend_on(c) ? sizeof(gas_hrtf_blend) : 0);
 			H = (uint64_t)GAS_ER_TAPS * F * 8 + F * 8 + 2ull * c->hist_len * 4;
 			tab = (uint64_t)c->tab.dirs * 2 * GAS_HRTF_TAPS * 4;
 			break;
@@ -694,7 +704,7 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 	// The plain [HRTF] launch takes it when there is one, else the [ER, HRTF] launch.
 	bool carrier = false;
 	int carrier_gt = -1;
-	if (!c->fused_streams && (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) == 0) {
+	if (!c->fused_streams && (c->cfg.flags & (GAS_FLAG_HRTF_CROSSFADE | GAS_FLAG_HRTF_INTERPOLATE)) == 0) {
 		for (int gt : { (int)G_FX_HRTF, (int)G_FX_ER_HRTF }) {
 			if (carrier_gt < 0 && groups[gt].count + groups[gt + 1].count > 0) {
 				carrier_gt = gt;
@@ -870,7 +880,7 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 						g_fd.order = ord;
 					}
 				}
-				e = gas_launch_hrtf_ols(c->stream, fd_gt == G_FX_ER_HRTF, (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) != 0, (c->cfg.flags & (GAS_FLAG_DIRECTION_RUNS | GAS_FLAG_DIRECTION_ORDER)) != 0, g_fd, g_pk, c->st, c->tab, c->d_tw, F, c->hist_len, c->cfg.er_ring_frames, parts, p_off, fd_gt == G_FX_HRTF && c->fused_streams ? c->d_cursors : nullptr, c->d_fade_env, fresh, fd_gt == carrier_gt ? job : gas_deferred_reduce());
+				e = gas_launch_hrtf_ols(c->stream, fd_gt == G_FX_ER_HRTF, (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) != 0, (c->cfg.flags & (GAS_FLAG_DIRECTION_RUNS | GAS_FLAG_DIRECTION_ORDER)) != 0, g_fd, g_pk, c->st, c->tab, c->d_tw, F, c->hist_len, c->cfg.er_ring_frames, parts, p_off, fd_gt == G_FX_HRTF && c->fused_streams ? c->d_cursors : nullptr, c->d_fade_env, fresh, fd_gt == carrier_gt ? job : gas_deferred_reduce(), blend_on(c));
 				if (fd_gt == carrier_gt) {
 					carried_bytes = job.partials ? ((uint64_t)job.p_count + 1) * job.elems * sizeof(float) : 0;
 					job = gas_deferred_reduce();
@@ -953,7 +963,7 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 						} else if (is_stereo(kind)) { // k_fx_stereo.hip, settings by chain position; a stereo enhance's state in the slot's ring of chain position j
 							e = gas_launch_fx_stereo(c->stream, kind, in, c->st, F, (uint32_t)j, c->cfg.mix_rate, outb);
 						} else {
-							e = gas_launch_hrtf_rows(c->stream, (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) != 0, in, c->st, c->tab, c->d_tw, F, outb);
+							e = gas_launch_hrtf_rows(c->stream, (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) != 0, in, c->st, c->tab, c->d_tw, F, outb, blend_on(c));
 						}
 						in.src = outb; // dense rows from here on
 						in.rows = nullptr;
@@ -1219,6 +1229,39 @@ int flush_fx_settings(gas_ctx *c) {
 	}
 	for (uint32_t i = 0; i < m; i++) {
 		GAS_HIP(c, hipMemcpyAsync(c->st.fxs + c->h_upload_slots[i], c->h_fx_upload + i, sizeof(gas_fx_settings), hipMemcpyHostToDevice, c->stream));
+	}
+	GAS_HIP(c, hipStreamSynchronize(c->stream));
+	return GAS_OK;
+}
+
+// gas_hrtf_blend_publish's rows (and the all-zero rows of freed slots) -> the slot-indexed device table, the way
+// flush_fx_settings does it: one 32-byte copy per changed slot out of a pinned staging array, no kernel.
+int flush_hrtf_blend(gas_ctx *c) {
+	if (!blend_on(c)) {
+		return GAS_OK;
+	}
+	uint32_t m = 0;
+	{
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		m = (uint32_t)c->blend_dirty_list.size();
+		if (m == 0) {
+			return GAS_OK;
+		}
+		if (!c->h_blend_upload) {
+			if (hipHostMalloc(&c->h_blend_upload, sizeof(gas_hrtf_blend) * c->cfg.max_sources, hipHostMallocDefault) != hipSuccess) {
+				return GAS_ERR_OUT_OF_MEMORY;
+			}
+		}
+		for (uint32_t i = 0; i < m; i++) {
+			const uint32_t s = c->blend_dirty_list[i];
+			c->h_blend_upload[i] = c->h_blend[s];
+			c->h_upload_slots[i] = s; // (the uploads above have been waited for)
+			c->blend_dirty_flag[s] = 0;
+		}
+		c->blend_dirty_list.clear();
+	}
+	for (uint32_t i = 0; i < m; i++) {
+		GAS_HIP(c, hipMemcpyAsync(c->st.hrtf_blend + c->h_upload_slots[i], c->h_blend_upload + i, sizeof(gas_hrtf_blend), hipMemcpyHostToDevice, c->stream));
 	}
 	GAS_HIP(c, hipStreamSynchronize(c->stream));
 	return GAS_OK;
@@ -1700,6 +1743,7 @@ int flush_params(gas_ctx *c) {
 		GAS_HIP(c, hipStreamSynchronize(c->stream));
 	}
 	int rc = flush_fx_settings(c);
+	rc = rc != GAS_OK ? rc : flush_hrtf_blend(c);
 	rc = rc != GAS_OK ? rc : flush_fx_dyn_settings(c);
 	for (int f = 0; f < FX_FAMILIES && rc == GAS_OK; f++) {
 		rc = fx_flush(c, f);
@@ -1739,6 +1783,11 @@ int apply_pending_frees(gas_ctx *c) {
 		}
 		si = SlotInfo{};
 		si.dirty_state = 1;
+		if (blend_on(c)) { // the next playback in this slot starts without a blend: the all-zero row, uploaded by this block's flush
+			std::lock_guard<std::mutex> lk(c->params_mu);
+			c->h_blend[s] = gas_hrtf_blend{};
+			mark_dirty(c->blend_dirty_flag, c->blend_dirty_list, s);
+		}
 		c->free_list.push_back(s);
 		if (c->h_cursors[s].pcm) {
 			// a freed playback lets go of its stream (gas_stream_destroy must not see it as bound for ever, and a
@@ -1970,6 +2019,8 @@ void gas_ctx_destroy(gas_ctx *c) {
 	(void)hipFree(c->d_upload_slots);
 	(void)hipFree(c->st.fxs);
 	(void)hipHostFree(c->h_fx_upload);
+	(void)hipFree(c->st.hrtf_blend);
+	(void)hipHostFree(c->h_blend_upload);
 	(void)hipFree(c->st.dyn);
 	(void)hipFree(c->st.dist_h);
 	(void)hipFree(c->st.comp_rundb);
@@ -2040,6 +2091,9 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 	if (cfg->er_ring_frames != 0 && ((cfg->er_ring_frames & (cfg->er_ring_frames - 1)) != 0 || cfg->er_ring_frames < 2 * cfg->frames)) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
+	if ((cfg->flags & GAS_FLAG_HRTF_INTERPOLATE) != 0 && (cfg->flags & (GAS_FLAG_HRTF_CROSSFADE | GAS_FLAG_DIRECTION_RUNS | GAS_FLAG_DIRECTION_ORDER | GAS_FLAG_XCD_ORDER)) != 0) {
+		return GAS_ERR_INVALID_ARGUMENT; // those fade from, group by or order by a source's ONE direction
+	}
 	int n_dev = 0;
 	if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0 || cfg->device < 0 || cfg->device >= n_dev) {
 		return GAS_ERR_NO_DEVICE;
@@ -2077,6 +2131,10 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 		GAS_HIP(c, hipMalloc(&c->st.params, sizeof(gas_params) * N));
 		GAS_HIP(c, hipMemsetAsync(c->st.params, 0, sizeof(gas_params) * N, c->stream));
 		GAS_HIP(c, hipMalloc(&c->st.fxs, sizeof(gas_fx_settings) * N));
+		if ((cfg->flags & GAS_FLAG_HRTF_INTERPOLATE) != 0) { // every slot starts with the all-zero row: no blend
+			GAS_HIP(c, hipMalloc(&c->st.hrtf_blend, sizeof(gas_hrtf_blend) * N));
+			GAS_HIP(c, hipMemsetAsync(c->st.hrtf_blend, 0, sizeof(gas_hrtf_blend) * N, c->stream));
+		}
 		c->st.dyn_stride = (uint32_t)N;
 		GAS_HIP(c, hipMalloc(&c->st.dyn, sizeof(gas_fx_dyn_settings) * N));
 		GAS_HIP(c, hipMalloc(&c->st.dist_h, sizeof(float) * GAS_MAX_EFFECTS * 2 * N));
@@ -2153,6 +2211,10 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 	c->dirty_flag.assign(N, 0);
 	c->h_fxs.assign(N, fx_settings_defaults());
 	c->fx_dirty_flag.assign(N, 0);
+	if (blend_on(c)) {
+		c->h_blend.assign(N, gas_hrtf_blend{});
+		c->blend_dirty_flag.assign(N, 0);
+	}
 	c->h_dyn.assign(N, fx_dyn_settings_defaults());
 	c->dyn_dirty_flag.assign(N, 0);
 	{ // every slot starts from the engine's resource defaults
@@ -2421,6 +2483,31 @@ int gas_fx_settings_publish(gas_ctx *c, const uint32_t *slots, const gas_fx_sett
 	return GAS_OK;
 }
 
+int gas_hrtf_blend_publish(gas_ctx *c, const uint32_t *slots, const gas_hrtf_blend *blends, uint32_t n) {
+	if (!c || !blend_on(c) || (n > 0 && (!slots || !blends))) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	const uint32_t dirs = c->tab.spec ? c->tab.dirs : 0; // no set loaded: the kernel clamps, as it clamps hrtf_dir
+	for (uint32_t i = 0; i < n; i++) {
+		if (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used) {
+			return GAS_ERR_BAD_SLOT;
+		}
+		for (int k = 0; k < 4; k++) {
+			const float w = blends[i].weight[k];
+			if (!std::isfinite(w) || w < 0.0f || (w != 0.0f && dirs != 0 && blends[i].dir[k] >= dirs)) {
+				return GAS_ERR_INVALID_ARGUMENT;
+			}
+		}
+	}
+	std::lock_guard<std::mutex> lk(c->params_mu);
+	for (uint32_t i = 0; i < n; i++) {
+		const uint32_t s = slots[i];
+		c->h_blend[s] = blends[i];
+		mark_dirty(c->blend_dirty_flag, c->blend_dirty_list, s);
+	}
+	return GAS_OK;
+}
+
 int gas_fx_dyn_settings_publish(gas_ctx *c, const uint32_t *slots, const gas_fx_dyn_settings *settings, uint32_t n) {
 	if (!c || (n > 0 && (!slots || !settings))) {
 		return GAS_ERR_INVALID_ARGUMENT;
@@ -2597,6 +2684,12 @@ int gas_calc_spatialization_areas(gas_ctx *c, const gas_spatializer3d_config *cf
 			return rcp;
 		}
 	}
+	{ // GAS_FLAG_HRTF_INTERPOLATE: blend rows published before this call reach the table first, so the launch's rows win
+		int rcb = flush_hrtf_blend(c);
+		if (rcb != GAS_OK) {
+			return rcb;
+		}
+	}
 	GAS_HIP(c, hipMemcpyAsync(c->d_calc_cfgs, cfgs, sizeof(gas_spatializer3d_config) * n_cfgs, hipMemcpyHostToDevice, c->stream));
 	if (n_listeners) {
 		GAS_HIP(c, hipMemcpyAsync(c->d_calc_listeners, listeners, sizeof(gas_listener) * n_listeners, hipMemcpyHostToDevice, c->stream));
@@ -2641,7 +2734,7 @@ int gas_calc_spatialization_areas(gas_ctx *c, const gas_spatializer3d_config *cf
 			d_reverb = c->d_calc_reverb;
 		}
 	}
-	GAS_HIP(c, gas_launch_calc_spatialization(c->stream, c->d_calc_cfgs, cfg_index ? c->d_calc_cfgidx : nullptr, d_poses, c->d_calc_listeners, n_listeners, c->d_calc_slots, n, c->st.params, c->st.was_further, d_out, d_areas, d_lap, d_reverb));
+	GAS_HIP(c, gas_launch_calc_spatialization(c->stream, c->d_calc_cfgs, cfg_index ? c->d_calc_cfgidx : nullptr, d_poses, c->d_calc_listeners, n_listeners, c->d_calc_slots, n, c->st.params, c->st.was_further, d_out, d_areas, d_lap, d_reverb, c->st.hrtf_blend));
 	if (mem == GAS_MEM_HOST && out_params) {
 		GAS_HIP(c, hipMemcpyAsync(out_params, c->d_calc_out, sizeof(gas_params) * n, hipMemcpyDeviceToHost, c->stream));
 	}
@@ -3108,7 +3201,7 @@ int gas_process_block(gas_ctx *c, const gas_audio_frame *src, const uint32_t *sl
 		bool host_dirty = false;
 		{
 			std::lock_guard<std::mutex> lk(c->params_mu);
-			host_dirty = !c->dirty_list.empty() || !c->fx_dirty_list.empty();
+			host_dirty = !c->dirty_list.empty() || !c->fx_dirty_list.empty() || !c->blend_dirty_list.empty();
 		}
 		const bool keep = mem == GAS_MEM_DEVICE && !slots && n == c->deferred_n && c->pending_free.empty() && c->groups_gen == c->deferred_groups_gen && !host_dirty;
 		if (!keep) {

@@ -12,6 +12,7 @@
 
 static_assert(sizeof(gas_params) == 128, "gas_params is a 128-byte POD");
 static_assert(sizeof(gas_audio_frame) == 8, "AudioFrame is 2 x f32");
+static_assert(sizeof(gas_hrtf_blend) == 32, "gas_hrtf_blend is 4 directions and 4 weights: two 16-byte loads");
 static_assert(sizeof(gas_fx_dyn_settings) == 12 * 4 * GAS_MAX_EFFECTS, "gas_fx_dyn_settings is 12 arrays by chain position");
 static_assert(sizeof(gas_fx_line_settings) == 21 * 4 * GAS_MAX_EFFECTS, "gas_fx_line_settings is 21 arrays by chain position");
 static_assert(sizeof(gas_fx_eq_settings) == 336, "gas_fx_eq_settings is [GAS_MAX_EFFECTS][21] f32");
@@ -114,6 +115,9 @@ struct gas_dev_state {
 	gas_fx_filter_settings *flt_settings; // [max_sources], by chain position
 	int32_t *flt_of; // [GAS_MAX_EFFECTS][max_sources] bank of chain position j
 	float *flt_pool; // [banks][GAS_FILTER_BANK_FLOATS]
+	// GAS_FLAG_HRTF_INTERPOLATE: the HRIR rows each slot's HRTF stage blends (nullptr without the flag); read by
+	// k_hrtf_ols_blend / k_hrtf_rows_blend, written by uploads and k_calc_spatialization only
+	gas_hrtf_blend *hrtf_blend; // [max_sources], all-zero row = hrtf_dir at weight 1
 };
 
 // Device-resident playback cursor: what SpatialPlaybackListNode + the engine's sampler hold.
@@ -218,7 +222,7 @@ struct gas_hrtf_launch_plan {
 };
 void gas_hrtf_plan(uint32_t n_fd, uint32_t n_pk, gas_hrtf_launch_plan *plan);
 uint32_t gas_hrtf_partials(uint32_t n); // workgroups of a single-path launch (k_er_only, k_hrtf_rows, k_rows_accumulate)
-hipError_t gas_launch_hrtf_ols(hipStream_t stream, bool with_er, bool crossfade, bool runs /* sum runs of equal directions before the FFT */, const gas_group_args &g_fd, const gas_group_args &g_pk, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *twiddles, uint32_t frames, uint32_t hist_len, uint32_t er_ring_frames, float *partials, uint32_t p_offset, gas_cursor *cursors /* non-null: sample the bound streams in the kernel */, const float *fade_env, const gas_params *fresh /* non-null: unscattered parameter rows in row order */, const gas_deferred_reduce &job = gas_deferred_reduce());
+hipError_t gas_launch_hrtf_ols(hipStream_t stream, bool with_er, bool crossfade, bool runs /* sum runs of equal directions before the FFT */, const gas_group_args &g_fd, const gas_group_args &g_pk, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *twiddles, uint32_t frames, uint32_t hist_len, uint32_t er_ring_frames, float *partials, uint32_t p_offset, gas_cursor *cursors /* non-null: sample the bound streams in the kernel */, const float *fade_env, const gas_params *fresh /* non-null: unscattered parameter rows in row order */, const gas_deferred_reduce &job = gas_deferred_reduce(), bool blend = false /* GAS_FLAG_HRTF_INTERPOLATE: k_hrtf_ols_blend (no cross-fade, no runs, no carried sum) */);
 // k_hrtf_uni.hip: all plain [HRTF] sources of a callback in one uniform launch; peak_bits (bit per group entry, or
 // nullptr) / peak_all say which sources also get their exact output peak
 uint32_t gas_hrtf_uni_partials(uint32_t n); // workgroups (= partial mixes) of a k_hrtf_uni launch
@@ -247,7 +251,7 @@ hipError_t gas_launch_hrtf_multi(hipStream_t stream, const gas_group_args &g, co
 hipError_t gas_launch_hrtf_uni(hipStream_t stream, const gas_group_args &g, const uint32_t *peak_bits, bool peak_all, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *twiddles, uint32_t frames, uint32_t hist_len, float *partials, uint32_t p_offset, gas_cursor *cursors, const float *fade_env, const gas_params *fresh, const gas_deferred_reduce &job = gas_deferred_reduce(), const gas_bus_route *routes = nullptr /* non-null: the two-bus form */, uint32_t bus_rows = 0, uint32_t bus_base = 0 /* the launch's pair of buses: bus_base, bus_base + 1 */, bool commit = true /* false: leave history / previous gain / peaks to a later pass */, uint32_t er_ring_frames = 0 /* non-zero: the chain [EARLY_REFLECTIONS, HRTF] */, uint32_t peak_from = 0xffffffffu /* entries from here on report their exact peak */, uint32_t peak_bit_base = 0 /* entry e's bit in peak_bits is bit e + peak_bit_base */, uint32_t flt_kind = 0 /* non-zero: the chain [this one-biquad kind, HRTF] */, uint32_t flt_pos = 0 /* its chain position (processor state, effect settings) */, float mix_rate = 0.0f);
 hipError_t gas_launch_er_only(hipStream_t stream, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t er_ring_frames, float *partials, uint32_t p_offset, uint32_t p_stride, gas_audio_frame *rows_out = nullptr);
 // stages of a general effect chain (rows in -> rows out) and its final mix
-hipError_t gas_launch_hrtf_rows(hipStream_t stream, bool crossfade, const gas_group_args &g, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *twiddles, uint32_t frames, gas_audio_frame *rows_out);
+hipError_t gas_launch_hrtf_rows(hipStream_t stream, bool crossfade, const gas_group_args &g, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *twiddles, uint32_t frames, gas_audio_frame *rows_out, bool blend = false /* GAS_FLAG_HRTF_INTERPOLATE */);
 hipError_t gas_launch_rows_accumulate(hipStream_t stream, const gas_group_args &g, uint32_t frames, float *partials, uint32_t p_offset);
 hipError_t gas_launch_rows_accumulate_buses(hipStream_t stream, const gas_group_args &g, uint32_t frames, const gas_bus_route *routes, uint32_t n_buses, uint32_t bus_rows, float *partials, uint32_t p_offset); // bus b's partial rows: [b * bus_rows + p_offset + workgroup]
 
@@ -285,7 +289,7 @@ hipError_t gas_launch_fx_filter(hipStream_t stream, const gas_group_args &g, con
 hipError_t gas_launch_zero_filter_banks(hipStream_t stream, const gas_dev_state &st, const uint32_t *banks, uint32_t n);
 hipError_t gas_launch_scatter_dyn(hipStream_t stream, gas_fx_dyn_settings *table, const gas_fx_dyn_settings *upload, const uint32_t *slots, uint32_t n);
 hipError_t gas_launch_scatter_params(hipStream_t stream, gas_params *table, const gas_params *upload, const uint32_t *slots, uint32_t n);
-hipError_t gas_launch_calc_spatialization(hipStream_t stream, const gas_spatializer3d_config *cfgs, const uint32_t *cfg_index, const gas_source_pose *poses, const gas_listener *listeners, uint32_t n_listeners, const uint32_t *slots, uint32_t n, gas_params *table, uint8_t *was_further, gas_params *out_params, const gas_area_send *areas = nullptr, const float *listener_area_pos = nullptr, gas_audio_frame *out_reverb = nullptr);
+hipError_t gas_launch_calc_spatialization(hipStream_t stream, const gas_spatializer3d_config *cfgs, const uint32_t *cfg_index, const gas_source_pose *poses, const gas_listener *listeners, uint32_t n_listeners, const uint32_t *slots, uint32_t n, gas_params *table, uint8_t *was_further, gas_params *out_params, const gas_area_send *areas = nullptr, const float *listener_area_pos = nullptr, gas_audio_frame *out_reverb = nullptr, gas_hrtf_blend *blend_table = nullptr /* GAS_FLAG_HRTF_INTERPOLATE: the slots' bilinear blend rows are written too */);
 hipError_t gas_launch_sample_sources(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc /* 16.16 step per row for resampled playbacks, or nullptr */);
 hipError_t gas_launch_noop(hipStream_t stream); // event-timer calibration
 hipError_t gas_launch_stream_probe(hipStream_t stream, const void *rd, uint64_t rd_bytes, void *wr, uint64_t wr_bytes, uint32_t workgroups, uint32_t unroll, float *sink); // copy-bandwidth ceiling

@@ -169,7 +169,7 @@ __device__ void calc_reverb_vol(const gas_spatializer3d_config &cfg, const gas_s
 	}
 }
 
-__global__ __launch_bounds__(256) void k_calc_spatialization(const gas_spatializer3d_config *__restrict__ cfgs, const uint32_t *__restrict__ cfg_index, const gas_source_pose *__restrict__ poses, const gas_listener *__restrict__ listeners, uint32_t n_listeners, const uint32_t *__restrict__ slots, uint32_t n, gas_params *__restrict__ table, uint8_t *__restrict__ was_further_tab, gas_params *__restrict__ out_params, const gas_area_send *__restrict__ areas, const float *__restrict__ listener_area_pos, gas_audio_frame *__restrict__ out_reverb) {
+__global__ __launch_bounds__(256) void k_calc_spatialization(const gas_spatializer3d_config *__restrict__ cfgs, const uint32_t *__restrict__ cfg_index, const gas_source_pose *__restrict__ poses, const gas_listener *__restrict__ listeners, uint32_t n_listeners, const uint32_t *__restrict__ slots, uint32_t n, gas_params *__restrict__ table, uint8_t *__restrict__ was_further_tab, gas_params *__restrict__ out_params, const gas_area_send *__restrict__ areas, const float *__restrict__ listener_area_pos, gas_audio_frame *__restrict__ out_reverb, gas_hrtf_blend *__restrict__ blend_table) {
 	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (i >= n) {
 		return;
@@ -300,6 +300,34 @@ __global__ __launch_bounds__(256) void k_calc_spatialization(const gas_spatializ
 		long long ei = cfg.hrtf_n_el > 1 ? llround((el + two_pi / 4) / (two_pi / 2) * (cfg.hrtf_n_el - 1)) : 0;
 		ei = ei < 0 ? 0 : (ei > (long long)cfg.hrtf_n_el - 1 ? (long long)cfg.hrtf_n_el - 1 : ei);
 		P->hrtf_dir = (uint32_t)(ei * cfg.hrtf_n_az + ai);
+		if (blend_table) {
+			// GAS_FLAG_HRTF_INTERPOLATE: bilinear weights over the grid cell that contains (az, el), f64, stored as f32
+			const double n_az = (double)cfg.hrtf_n_az, top = (double)(cfg.hrtf_n_el - 1);
+			double u = az / two_pi * n_az;
+			u -= floor(u / n_az) * n_az; // wrapped into [0, n_az)
+			long long a0 = (long long)floor(u);
+			double fu = u - (double)a0;
+			if (a0 >= (long long)cfg.hrtf_n_az) { // u rounded up to n_az: the first column again
+				a0 = 0;
+				fu = 0.0;
+			}
+			const long long a1 = (a0 + 1) % (long long)cfg.hrtf_n_az;
+			double v = (el + two_pi / 4) / (two_pi / 2) * top;
+			v = v < 0.0 ? 0.0 : (v > top ? top : v);
+			const long long e0 = (long long)floor(v);
+			const double fv = v - (double)e0;
+			const long long e1 = e0 + 1 <= (long long)cfg.hrtf_n_el - 1 ? e0 + 1 : e0; // top row (or one row): weight 0 there
+			gas_hrtf_blend b;
+			b.dir[0] = (uint32_t)(e0 * cfg.hrtf_n_az + a0);
+			b.dir[1] = (uint32_t)(e0 * cfg.hrtf_n_az + a1);
+			b.dir[2] = (uint32_t)(e1 * cfg.hrtf_n_az + a0);
+			b.dir[3] = (uint32_t)(e1 * cfg.hrtf_n_az + a1);
+			b.weight[0] = (float)((1.0 - fu) * (1.0 - fv));
+			b.weight[1] = (float)(fu * (1.0 - fv));
+			b.weight[2] = (float)((1.0 - fu) * fv);
+			b.weight[3] = (float)(fu * fv);
+			blend_table[slot] = b;
+		}
 	}
 	if (out_reverb) { // what the reference sends to the area's reverb bus (:451-452)
 #pragma unroll
@@ -315,10 +343,10 @@ __global__ __launch_bounds__(256) void k_calc_spatialization(const gas_spatializ
 
 } // namespace
 
-hipError_t gas_launch_calc_spatialization(hipStream_t stream, const gas_spatializer3d_config *cfgs, const uint32_t *cfg_index, const gas_source_pose *poses, const gas_listener *listeners, uint32_t n_listeners, const uint32_t *slots, uint32_t n, gas_params *table, uint8_t *was_further, gas_params *out_params, const gas_area_send *areas, const float *listener_area_pos, gas_audio_frame *out_reverb) {
+hipError_t gas_launch_calc_spatialization(hipStream_t stream, const gas_spatializer3d_config *cfgs, const uint32_t *cfg_index, const gas_source_pose *poses, const gas_listener *listeners, uint32_t n_listeners, const uint32_t *slots, uint32_t n, gas_params *table, uint8_t *was_further, gas_params *out_params, const gas_area_send *areas, const float *listener_area_pos, gas_audio_frame *out_reverb, gas_hrtf_blend *blend_table) {
 	if (n == 0) {
 		return hipSuccess;
 	}
-	hipLaunchKernelGGL(k_calc_spatialization, dim3((n + 255) / 256), dim3(256), 0, stream, cfgs, cfg_index, poses, listeners, n_listeners, slots, n, table, was_further, out_params, areas, listener_area_pos, out_reverb);
+	hipLaunchKernelGGL(k_calc_spatialization, dim3((n + 255) / 256), dim3(256), 0, stream, cfgs, cfg_index, poses, listeners, n_listeners, slots, n, table, was_further, out_params, areas, listener_area_pos, out_reverb, blend_table);
 	return hipGetLastError();
 }

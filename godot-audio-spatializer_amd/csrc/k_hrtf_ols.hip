@@ -56,9 +56,47 @@ struct HrtfLds {
 	static constexpr int TOTAL_F2 = PEAKS ? WAVES * LDS_F2_PER_WAVE : (FD_F2 + 2 * LDS_F2_HALF + F > WAVES * LDS_F2_PER_WAVE ? FD_F2 + 2 * LDS_F2_HALF + F : WAVES * LDS_F2_PER_WAVE);
 };
 
-template <int SQ, bool WITH_ER, bool PEAKS, bool SRC_PCM, bool XFADE, bool RUNS = false>
+// GAS_FLAG_HRTF_INTERPOLATE (BLEND): H = w0 H[d0] + w1 H[d1] + ... over a source's blend row, on the registers as
+// issue_spectra filled them (finish_spectra's unpacking is linear, so it runs once, on the sum).  The first row is the
+// one already in `hs` (requested a transform ahead, like the single row of the other forms); rows 2 .. 4 are fetched
+// here, half a row (16 registers) at a time, and only for non-zero weights: a wave-uniform branch, so a source on a
+// grid point loads one row.  The row was compacted in the prologue (non-zero entries first, in index order).
+__device__ __forceinline__ void blend_spectra(const float4 *__restrict__ spec, int lane, float4 (&hs)[8], float w0, const uint32_t (&d)[3], const float (&w)[3]) {
+#pragma unroll
+	for (int j = 0; j < 8; j++) {
+		hs[j] = make_float4(w0 * hs[j].x, w0 * hs[j].y, w0 * hs[j].z, w0 * hs[j].w);
+	}
+#pragma unroll
+	for (int k = 0; k < 3; k++) {
+		if (w[k] != 0.0f) { // wave-uniform
+			const float4 *base = spec + (size_t)d[k] * 256;
+			float4 hb[4];
+#pragma unroll
+			for (int j = 0; j < 4; j++) {
+				hb[j] = base[j * 64 + lane];
+			}
+#pragma unroll
+			for (int j = 0; j < 4; j++) {
+				hs[j] = make_float4(hs[j].x + w[k] * hb[j].x, hs[j].y + w[k] * hb[j].y, hs[j].z + w[k] * hb[j].z, hs[j].w + w[k] * hb[j].w);
+			}
+#pragma unroll
+			for (int j = 4; j < 8; j++) { // the mirrored half, as issue_spectra addresses it
+				int p = 512 - (lane + 64 * j);
+				p = p == 256 ? 0 : p;
+				hb[j - 4] = base[p];
+			}
+#pragma unroll
+			for (int j = 4; j < 8; j++) {
+				hs[j] = make_float4(hs[j].x + w[k] * hb[j - 4].x, hs[j].y + w[k] * hb[j - 4].y, hs[j].z + w[k] * hb[j - 4].z, hs[j].w + w[k] * hb[j - 4].w);
+			}
+		}
+	}
+}
+
+template <int SQ, bool WITH_ER, bool PEAKS, bool SRC_PCM, bool XFADE, bool RUNS = false, bool BLEND = false>
 __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const uint32_t wg, const gas_group_args &g, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *__restrict__ tw, uint32_t n_wgs, uint32_t er_R, float *__restrict__ my_partial, gas_cursor *__restrict__ cursors, const float *__restrict__ fade_env, const gas_params *__restrict__ fresh, gas_audio_frame *__restrict__ rows_out = nullptr, const gas_deferred_reduce job = gas_deferred_reduce(), uint32_t job_col = 0) {
 	static_assert(!(WITH_ER && SRC_PCM), "the early-reflection prologue reads float rows");
+	static_assert(!(BLEND && (XFADE || RUNS)), "a blended source has no single direction to fade from or to group by");
 	constexpr int FQ = 2 * SQ; // F / 64
 	constexpr int HQ = 8 - SQ; // hist_len / 64
 	constexpr int NQ = 8 + SQ; // (hist_len + F) / 64
@@ -93,7 +131,7 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 
 	// GAS_FLAG_PIPELINED_MIX: one wave also sums the previous callback's partial mixes for one output column
 	// (waves 2 .. 5, idle while waves 0 and 1 run the frequency-domain epilogue's inverse FFTs, take one column each)
-	constexpr bool JOB_OK = !SRC_PCM && !XFADE; // register budget: not the stream-sampling and cross-fade forms
+	constexpr bool JOB_OK = !SRC_PCM && !XFADE && !BLEND; // register budget: not the stream-sampling, cross-fade and blend forms
 	constexpr bool JOB_LATE = WITH_ER; // early reflections: no 16 registers to park the rows across the loop -- they are requested where they are summed
 	float4 jr[JOB_ROWS];
 	bool job_mine = false;
@@ -169,6 +207,10 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 	//            source's history and frames
 	//   level 3  the first source's spectra (consumed after the forward FFT, so they arrive under it)
 	LaneMeta lm{};
+	// BLEND: the compacted blend row of this lane's source; entry 0's direction is lm.dir, so the table row every form
+	// keeps in flight is the blend's first row
+	uint32_t bl_d[3] = { 0, 0, 0 };
+	float bl_w0 = 1.0f, bl_w[3] = { 0.0f, 0.0f, 0.0f };
 	const bool have = first + lane < last; // <= 64 sources per wave (gas_hrtf_plan): one lane per source of this wave
 	if (have) {
 		const uint32_t e = g.order ? g.order[first + lane] : first + lane; // direction order (k_dir_order) or entry order
@@ -196,6 +238,37 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 		lm.g1 = gd.x;
 		const uint32_t d = __float_as_uint(gd.y);
 		lm.dir = d < tab.dirs ? d : 0;
+		if constexpr (BLEND) {
+			// the slot's 32-byte row, requested with the 8-byte load above.  Non-zero entries move to the front in index
+			// order (static indices only: selects, no scratch); directions are clamped as hrtf_dir is; the all-zero
+			// row becomes {hrtf_dir, 1}: one row at weight 1.0f, the same code as an explicit one-row blend.
+			const uint4 rd = reinterpret_cast<const uint4 *>(st.hrtf_blend + lm.slot)[0];
+			const float4 rw = reinterpret_cast<const float4 *>(st.hrtf_blend + lm.slot)[1];
+			const uint32_t in_d[4] = { rd.x, rd.y, rd.z, rd.w };
+			const float in_w[4] = { rw.x, rw.y, rw.z, rw.w };
+			uint32_t cd[4] = { lm.dir, 0, 0, 0 };
+			float cw[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
+			int k = 0;
+#pragma unroll
+			for (int i = 0; i < 4; i++) {
+				const bool nz = in_w[i] != 0.0f;
+#pragma unroll
+				for (int j = 0; j < 4; j++) {
+					if (nz && k == j) {
+						cd[j] = in_d[i] < tab.dirs ? in_d[i] : 0;
+						cw[j] = in_w[i];
+					}
+				}
+				k += nz ? 1 : 0;
+			}
+			lm.dir = cd[0];
+			bl_w0 = k == 0 ? 1.0f : cw[0];
+#pragma unroll
+			for (int j = 0; j < 3; j++) {
+				bl_d[j] = cd[j + 1];
+				bl_w[j] = cw[j + 1];
+			}
+		}
 		lm.pdir = lm.dir;
 		if constexpr (XFADE) {
 			const uint32_t pd = st.hrtf_prev_dir[lm.slot]; // previous direction + 1, 0 = none yet
@@ -254,6 +327,20 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 		}
 	}
 	GAS_STAMP(1);
+
+	// BLEND: the table row in `hs` belongs to the wave's source number i; add the other rows of its blend
+	auto blend_rows = [&](uint32_t i) {
+		if constexpr (BLEND) {
+			uint32_t d[3];
+			float w[3];
+#pragma unroll
+			for (int k = 0; k < 3; k++) {
+				d[k] = (uint32_t)__builtin_amdgcn_readlane((int)bl_d[k], (int)i);
+				w[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bl_w[k]), (int)i));
+			}
+			blend_spectra(tab.spec, lane, hs, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bl_w0), (int)i)), d, w);
+		}
+	};
 
 	// STAGES sources per trip, each with its own landing registers: while source e transforms, the frames and
 	// history of sources e+1 .. e+STAGES are in flight.
@@ -414,6 +501,7 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 				v[j] = make_float2(xq[j], xq[j + SQ]);
 			}
 			fft512<false>(v, t1, t2, lds, lane);
+			blend_rows(e - first);
 			finish_spectra(lane, hs);
 			float2 yl[8], yr[8];
 #pragma unroll
@@ -496,6 +584,7 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 				}
 				if constexpr (SKEW) {
 					if (have_prev) {
+						blend_rows(e - 1 - first); // (every source is its own run here)
 						finish_spectra(lane, hs);
 #pragma unroll
 						for (int j = 0; j < 8; j++) {
@@ -511,6 +600,7 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 					}
 					have_prev = true;
 				} else {
+				static_assert(SKEW || !BLEND || PEAKS, "the blend form takes its products in the skewed loop");
 				finish_spectra(lane, hs);
 #pragma unroll
 				for (int j = 0; j < 8; j++) {
@@ -562,6 +652,7 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 	}
 	if constexpr (SKEW) {
 		if (have_prev) { // the last run's products
+			blend_rows(last - 1 - first);
 			finish_spectra(lane, hs);
 #pragma unroll
 			for (int j = 0; j < 8; j++) {
@@ -709,6 +800,9 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 	(void)have_prev;
 	(void)jr;
 	(void)job_mine;
+	(void)bl_d;
+	(void)bl_w0;
+	(void)bl_w;
 }
 
 // One launch per callback for every HRTF source: workgroups [0, wgs_fd) run the frequency-domain body over
@@ -727,6 +821,28 @@ __global__ __launch_bounds__(WAVES * 64, GAS_HRTF_WAVES_PER_SIMD) void k_hrtf_ol
 	} else {
 		hrtf_body<SQ, WITH_ER, true, SRC_PCM, XFADE>(lds_all, tw_lds, blockIdx.x - wgs_fd, g_pk, st, tab, tw, gridDim.x - wgs_fd, er_R, my_partial, cursors, fade_env, fresh, nullptr, job, blockIdx.x);
 	}
+}
+
+// GAS_FLAG_HRTF_INTERPOLATE: the same launch with every source's HRIR blended from its gas_hrtf_blend row
+// (st.hrtf_blend).  A kernel of its own, so that the instantiations above stay what they were.
+template <int SQ, bool WITH_ER, bool SRC_PCM>
+__global__ __launch_bounds__(WAVES * 64, GAS_HRTF_WAVES_PER_SIMD) void k_hrtf_ols_blend(gas_group_args g_fd, gas_group_args g_pk, uint32_t wgs_fd, gas_dev_state st, gas_hrtf_table tab, const float2 *__restrict__ tw, uint32_t er_R, float *__restrict__ partials, uint32_t p_offset, gas_cursor *__restrict__ cursors, const float *__restrict__ fade_env, const gas_params *__restrict__ fresh) {
+	constexpr int LDS_F2 = HrtfLds<SQ, false>::TOTAL_F2 > HrtfLds<SQ, true>::TOTAL_F2 ? HrtfLds<SQ, false>::TOTAL_F2 : HrtfLds<SQ, true>::TOTAL_F2;
+	__shared__ float2 lds_all[LDS_F2];
+	__shared__ float2 tw_lds[GAS_TW_LDS ? 1024 : 1];
+	float *my_partial = partials + ((size_t)p_offset + blockIdx.x) * (size_t)(2 * SQ * 64 * 2);
+	if (blockIdx.x < wgs_fd) {
+		hrtf_body<SQ, WITH_ER, false, SRC_PCM, false, false, true>(lds_all, tw_lds, blockIdx.x, g_fd, st, tab, tw, wgs_fd, er_R, my_partial, cursors, fade_env, fresh);
+	} else {
+		hrtf_body<SQ, WITH_ER, true, SRC_PCM, false, false, true>(lds_all, tw_lds, blockIdx.x - wgs_fd, g_pk, st, tab, tw, gridDim.x - wgs_fd, er_R, my_partial, cursors, fade_env, fresh);
+	}
+}
+
+template <int SQ>
+__global__ __launch_bounds__(WAVES * 64, GAS_HRTF_WAVES_PER_SIMD) void k_hrtf_rows_blend(gas_group_args g, gas_dev_state st, gas_hrtf_table tab, const float2 *__restrict__ tw, gas_audio_frame *__restrict__ rows_out) {
+	__shared__ float2 lds_all[HrtfLds<SQ, true>::TOTAL_F2];
+	__shared__ float2 tw_lds[GAS_TW_LDS ? 1024 : 1];
+	hrtf_body<SQ, false, true, false, false, false, true>(lds_all, tw_lds, blockIdx.x, g, st, tab, tw, gridDim.x, 0, nullptr, nullptr, nullptr, nullptr, rows_out);
 }
 
 // One HRTF stage of a general effect chain: stereo rows in (mono downmix inside), per-source stereo rows out.
@@ -1031,17 +1147,45 @@ uint32_t gas_hrtf_partials(uint32_t n) {
 	return p.wgs_fd;
 }
 
-hipError_t gas_launch_hrtf_ols(hipStream_t stream, bool with_er, bool crossfade, bool runs, const gas_group_args &g_fd, const gas_group_args &g_pk, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *twiddles, uint32_t frames, uint32_t hist_len, uint32_t er_ring_frames, float *partials, uint32_t p_offset, gas_cursor *cursors, const float *fade_env, const gas_params *fresh, const gas_deferred_reduce &job) {
+hipError_t gas_launch_hrtf_ols(hipStream_t stream, bool with_er, bool crossfade, bool runs, const gas_group_args &g_fd, const gas_group_args &g_pk, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *twiddles, uint32_t frames, uint32_t hist_len, uint32_t er_ring_frames, float *partials, uint32_t p_offset, gas_cursor *cursors, const float *fade_env, const gas_params *fresh, const gas_deferred_reduce &job, bool blend) {
 	if (g_fd.n + g_pk.n == 0) {
 		return hipSuccess;
 	}
 	if (frames % 128 != 0 || frames > 512 || hist_len != 512 - frames / 2 || (with_er && cursors)) {
 		return hipErrorInvalidValue;
 	}
+	if (blend && (crossfade || runs || job.partials || !st.hrtf_blend)) {
+		return hipErrorInvalidValue;
+	}
 	gas_hrtf_launch_plan plan;
 	gas_hrtf_plan(g_fd.n, g_pk.n, &plan);
 	const uint32_t wgs_fd = plan.wgs_fd;
 	dim3 grid(plan.wgs_fd + plan.wgs_pk), block(WAVES * 64);
+	if (blend) {
+#define GAS_HRTF_BLEND_LAUNCH(SQv, ERv, PCMv) \
+	hipLaunchKernelGGL((k_hrtf_ols_blend<SQv, ERv, PCMv>), grid, block, 0, stream, g_fd, g_pk, wgs_fd, st, tab, twiddles, er_ring_frames, partials, p_offset, cursors, fade_env, fresh)
+#define GAS_HRTF_BLEND_CASE(SQv)                          \
+	case SQv:                                             \
+		if (with_er) {                                    \
+			GAS_HRTF_BLEND_LAUNCH(SQv, true, false);      \
+		} else if (cursors) {                             \
+			GAS_HRTF_BLEND_LAUNCH(SQv, false, true);      \
+		} else {                                          \
+			GAS_HRTF_BLEND_LAUNCH(SQv, false, false);     \
+		}                                                 \
+		break;
+		switch (frames / 128) {
+			GAS_HRTF_BLEND_CASE(1)
+			GAS_HRTF_BLEND_CASE(2)
+			GAS_HRTF_BLEND_CASE(3)
+			GAS_HRTF_BLEND_CASE(4)
+			default:
+				return hipErrorInvalidValue;
+		}
+#undef GAS_HRTF_BLEND_CASE
+#undef GAS_HRTF_BLEND_LAUNCH
+		return hipGetLastError();
+	}
 #define GAS_HRTF_LAUNCH2(SQv, ERv, PCMv, XFv, RNv) \
 	hipLaunchKernelGGL((k_hrtf_ols<SQv, ERv, PCMv, XFv, RNv>), grid, block, 0, stream, g_fd, g_pk, wgs_fd, st, tab, twiddles, er_ring_frames, partials, p_offset, cursors, fade_env, fresh, job)
 #define GAS_HRTF_LAUNCH(SQv, ERv, PCMv, XFv)          \
@@ -1107,12 +1251,34 @@ hipError_t gas_launch_er_only(hipStream_t stream, const gas_group_args &g, const
 	return hipGetLastError();
 }
 
-hipError_t gas_launch_hrtf_rows(hipStream_t stream, bool crossfade, const gas_group_args &g, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *twiddles, uint32_t frames, gas_audio_frame *rows_out) {
+hipError_t gas_launch_hrtf_rows(hipStream_t stream, bool crossfade, const gas_group_args &g, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *twiddles, uint32_t frames, gas_audio_frame *rows_out, bool blend) {
 	if (g.n == 0) {
 		return hipSuccess;
 	}
+	if (blend && (crossfade || !st.hrtf_blend)) {
+		return hipErrorInvalidValue;
+	}
 	const uint32_t wgs = gas_hrtf_partials(g.n);
 	dim3 grid(wgs), block(WAVES * 64);
+	if (blend) {
+		switch (frames / 128) {
+			case 1:
+				hipLaunchKernelGGL((k_hrtf_rows_blend<1>), grid, block, 0, stream, g, st, tab, twiddles, rows_out);
+				break;
+			case 2:
+				hipLaunchKernelGGL((k_hrtf_rows_blend<2>), grid, block, 0, stream, g, st, tab, twiddles, rows_out);
+				break;
+			case 3:
+				hipLaunchKernelGGL((k_hrtf_rows_blend<3>), grid, block, 0, stream, g, st, tab, twiddles, rows_out);
+				break;
+			case 4:
+				hipLaunchKernelGGL((k_hrtf_rows_blend<4>), grid, block, 0, stream, g, st, tab, twiddles, rows_out);
+				break;
+			default:
+				return hipErrorInvalidValue;
+		}
+		return hipGetLastError();
+	}
 #define GAS_ROWS_CASE(SQv)                                                                                              \
 	case SQv:                                                                                                           \
 		if (crossfade) {                                                                                                \

@@ -36,6 +36,7 @@
 #pragma weak gas_fx_mod_settings_publish
 #pragma weak gas_fx_stereo_settings_publish
 #pragma weak gas_fx_filter_settings_publish
+#pragma weak gas_hrtf_blend_publish
 
 namespace {
 
@@ -92,7 +93,7 @@ struct Playback {
 };
 
 struct Command {
-	enum Kind { START, PARAMS, FX_SETTINGS, FX_DYN_SETTINGS, FX_LINE_SETTINGS, FX_EQ_SETTINGS, FX_MOD_SETTINGS, FX_STEREO_SETTINGS, FX_FILTER_SETTINGS } kind = START;
+	enum Kind { START, PARAMS, FX_SETTINGS, FX_DYN_SETTINGS, FX_LINE_SETTINGS, FX_EQ_SETTINGS, FX_MOD_SETTINGS, FX_STEREO_SETTINGS, FX_FILTER_SETTINGS, HRTF_BLEND } kind = START;
 	uint32_t id = 0;
 	std::unique_ptr<Playback> playback; // START
 	gas_params params{}; // PARAMS
@@ -103,6 +104,7 @@ struct Command {
 	gas_fx_mod_settings fx_mod_settings{}; // FX_MOD_SETTINGS
 	gas_fx_stereo_settings fx_stereo_settings{}; // FX_STEREO_SETTINGS
 	gas_fx_filter_settings fx_filter_settings{}; // FX_FILTER_SETTINGS
+	gas_hrtf_blend hrtf_blend{}; // HRTF_BLEND
 };
 
 // [ENGINE] Math::db_to_linear
@@ -283,6 +285,8 @@ struct gas_host {
 				publish_settings(c, &Command::fx_stereo_settings, gas_fx_stereo_settings_publish);
 			} else if (c.kind == Command::FX_FILTER_SETTINGS) {
 				publish_settings(c, &Command::fx_filter_settings, gas_fx_filter_settings_publish);
+			} else if (c.kind == Command::HRTF_BLEND) {
+				publish_settings(c, &Command::hrtf_blend, gas_hrtf_blend_publish);
 			} else {
 				auto it = by_id.find(c.id);
 				if (it == by_id.end()) {
@@ -596,6 +600,26 @@ int gas_host_set_effect_settings_stereo(gas_host *h, uint32_t id, const gas_fx_s
 
 int gas_host_set_effect_settings_filter(gas_host *h, uint32_t id, const gas_fx_filter_settings *settings) {
 	return h ? h->queue_settings(id, settings, gas_fx_filter_settings_valid, Command::FX_FILTER_SETTINGS, &Command::fx_filter_settings) : GAS_ERR_BAD_SLOT;
+}
+
+static bool hrtf_blend_weights_valid(const gas_hrtf_blend &b) {
+	for (int k = 0; k < 4; k++) {
+		if (!std::isfinite(b.weight[k]) || b.weight[k] < 0.0f) {
+			return false;
+		}
+	}
+	return true;
+}
+
+int gas_host_set_hrtf_blend(gas_host *h, uint32_t id, const gas_hrtf_blend *blend) {
+	if (!h) {
+		return GAS_ERR_BAD_SLOT;
+	}
+	gas_config cfg{};
+	if (gas_ctx_get_config(h->ctx, &cfg) != GAS_OK || (cfg.flags & GAS_FLAG_HRTF_INTERPOLATE) == 0) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	return h->queue_settings(id, blend, hrtf_blend_weights_valid, Command::HRTF_BLEND, &Command::hrtf_blend);
 }
 
 void gas_host_set_playback_disable_threshold_db(gas_host *h, float db) {

@@ -3,7 +3,7 @@ reference's own pan / attenuation formulas, and a synthetic HRIR set.  Harness-s
 (tests and bench.py); nothing here is on the audio path."""
 import numpy as np
 
-from .capi import ER_TAPS, HRTF_TAPS, PARAMS_DTYPE
+from .capi import ER_TAPS, HRTF_BLEND_DTYPE, HRTF_TAPS, PARAMS_DTYPE
 
 
 def db_to_linear(db):
@@ -62,3 +62,16 @@ def synthetic_hrir(rng, dirs=1024):
         out[d, 0, :] = h[d, 0, :]
         out[d, 1, s:] = h[d, 1, : HRTF_TAPS - s]
     return (out * 0.25).astype(np.float32)
+
+
+def draw_blends(rng, n, dirs):
+    """n gas_hrtf_blend rows (FLAG_HRTF_INTERPOLATE): 1 .. 4 non-zero weights summing to 1, at random positions of the
+    row, each on a direction of its own; the other entries are zero (their directions are not read)."""
+    b = np.zeros(n, dtype=HRTF_BLEND_DTYPE)
+    for i in range(n):
+        k = int(rng.integers(1, 5))
+        pos = np.sort(rng.choice(4, size=k, replace=False))
+        w = rng.uniform(0.1, 1.0, k)
+        b["weight"][i, pos] = (w / w.sum()).astype(np.float32)
+        b["dir"][i, pos] = rng.choice(dirs, size=k, replace=dirs < k)
+    return b

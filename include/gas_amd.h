@@ -210,9 +210,24 @@ typedef struct gas_config {
  *  - every entry of the context must be called from ONE thread (the recorded calls are run by whoever comes next:
  *    anything that changes what they must see -- a new list, host-published parameters, frees, any other entry that
  *    enqueues work -- first runs them, exactly as the unbatched mode would have);
- *  - callbacks that do not qualify (other source kinds, < 2048 sources, 2 or more channel pairs, streams, cross-fade
- *    or direction flags) run as before. */
+ *  - callbacks that do not qualify (other source kinds, < 2048 sources, 2 or more channel pairs, streams, cross-fade,
+ *    direction or HRIR-interpolation flags) run as before. */
 #define GAS_FLAG_BATCHED_LAUNCH 64u
+/* NEW: every HRTF stage of the context convolves with a weighted sum of up to four rows of the HRIR
+ * set instead of the one row hrtf_dir names: H = sum_i weight[i] * H[dir[i]] over the slot's gas_hrtf_blend row (added
+ * in f32, in index order, before the spectral product; the HRTF stage is linear in the HRIR, so this is the weighted
+ * sum of the single-direction renders).  Rows come from gas_hrtf_blend_publish or from gas_calc_spatialization, which
+ * then writes the bilinear weights of the grid cell around the source next to hrtf_dir.  A slot whose row is all zero
+ * (every slot when it is allocated) has no blend: it renders hrtf_dir at weight 1, through the same code.  HRTF sources
+ * of such a context run in k_hrtf_ols (the kernel the cross-fade uses), never in k_hrtf_uni / k_hrtf_multi, so their
+ * mixes agree with an unflagged context's to rounding, not to the bit.  Without the flag nothing changes anywhere.
+ * Cost per context: 32 bytes of device memory per slot of max_sources for the blend table (0.26 MB at 8192 slots, 2 MB
+ * at 65 536, 260 MB at 8.1 M) plus, once a row has been published, 32 bytes of pinned host memory per slot for the
+ * upload; the host mirror is 32 bytes per slot of ordinary memory.  gas_ctx_create refuses the flag
+ * (GAS_ERR_INVALID_ARGUMENT) together with GAS_FLAG_HRTF_CROSSFADE (fading from an old blend to a new one is not
+ * implemented) and with GAS_FLAG_DIRECTION_RUNS, GAS_FLAG_DIRECTION_ORDER and GAS_FLAG_XCD_ORDER (they group or order
+ * sources by their ONE direction). */
+#define GAS_FLAG_HRTF_INTERPOLATE 128u
 
 /* SpatializerParameters (spatializer_parameters.h:39-67) + SpatializerParameters3D
  * (audio_spatializer_3d.h:61-83) as one 128-byte POD, plus the per-block effect
@@ -522,6 +537,22 @@ int gas_ctx_reserve_fx_filter(gas_ctx *ctx, uint32_t banks);
 
 /* ---- NEW AudioSpatializerHRTF resource: hrir is [dirs][2 ears][taps] f32, taps <= 256 */
 int gas_hrtf_load(gas_ctx *ctx, const float *hrir, uint32_t dirs, uint32_t taps);
+
+/* GAS_FLAG_HRTF_INTERPOLATE: the HRIR rows one playback's HRTF stage blends.  Entries with weight == 0 are ignored and
+ * their dir is not read.  Weights are used as given, not normalised: they scale the output like hrtf_gain does.  The
+ * all-zero row means "no blend": gas_params.hrtf_dir at weight 1. */
+typedef struct gas_hrtf_blend {
+	uint32_t dir[4];
+	float weight[4];
+} gas_hrtf_blend;
+/* Host arrays, physics thread, latest wins; snapshotted with the parameters at the start of the next
+ * gas_process_block* (like gas_fx_settings_publish).  GAS_ERR_INVALID_ARGUMENT, and nothing of the call is taken: a
+ * context without GAS_FLAG_HRTF_INTERPOLATE; a weight that is negative or not finite; a dir >= the loaded set's
+ * direction count on an entry with non-zero weight.  The direction check is made HERE, against the set loaded at the
+ * time of the call; with no set loaded yet (or after a smaller set is loaded later) the kernel clamps an out-of-range
+ * dir to direction 0, exactly as it clamps hrtf_dir.  gas_source_free returns the slot's row to all-zero at the next
+ * block boundary; gas_source_reset leaves it (settings, not DSP state). */
+int gas_hrtf_blend_publish(gas_ctx *ctx, const uint32_t *slots, const gas_hrtf_blend *blends, uint32_t n);
 /* The same resource from a MEASURED set (what a SOFA file holds: M source positions x 2 receivers x N samples; parsing
  * netCDF / HDF5 is the caller's business, the loader takes the arrays).  positions is [m][2] = (azimuth, elevation) in
  * radians, azimuth from straight ahead (-Z) towards the right (+X), elevation up from the horizontal plane -- SOFA's
@@ -596,7 +627,15 @@ int gas_mix_channel_1(gas_ctx *ctx, uint32_t slot, int channel, gas_audio_frame 
  * (:103-110), SPCAP surround (:56-98, :903-938), doppler pitch (:405-438), update_parameters latch
  * (:472-479).  Physics queries (Area3D override / reverb send) stay on the host.  Results are written
  * straight into the slots' device-resident parameters (as gas_params_publish would) and optionally
- * copied to out_params for the host's get_bus_map (audio_spatializer.cpp:274-324). */
+ * copied to out_params for the host's get_bus_map (audio_spatializer.cpp:274-324).
+ * On a GAS_FLAG_HRTF_INTERPOLATE context, with hrtf_n_az and hrtf_n_el non-zero, the launch also writes each slot's
+ * gas_hrtf_blend row: bilinear over the grid cell that contains (az, el).  u = az / 2pi * n_az wrapped into [0, n_az),
+ * v = (el + pi/2) / pi * (n_el - 1) clamped to [0, n_el - 1]; corners (floor u, floor v), (floor u + 1 mod n_az,
+ * floor v) and the same two at floor v + 1, as dir = elevation_index * n_az + azimuth_index; weights (1-fu)(1-fv),
+ * fu (1-fv), (1-fu) fv, fu fv with fu, fv the fractional parts, computed in f64 and stored as f32; at n_el == 1 or v on
+ * the top row the upper pair has weight 0 (and names the lower pair's cells).  hrtf_dir is written as without the flag
+ * (nearest cell).  The row overrides an earlier gas_hrtf_blend_publish for the slot and is overridden by a later one;
+ * it is not copied to out_params (there is no read-back of blend rows). */
 typedef struct gas_spatializer3d_config { /* AudioSpatializer3D properties, audio_spatializer_3d.h:171-187 */
 	int32_t attenuation_model; /* 0 inverse distance, 1 inverse square distance, 2 logarithmic, 3 disabled */
 	float unit_size, max_distance, panning_strength;

@@ -11,7 +11,7 @@
  *
  * Threading contract (the reference's split, audio_spatializer.h:135-138, with its SafeList / SafeFlag / Mutex roles):
  *   - control entries -- gas_host_start_playback*, gas_host_stop_playback, gas_host_set_spatializer_parameters,
- *     gas_host_set_effect_settings, gas_host_set_effect_settings_dyn, gas_host_set_effect_settings_line, gas_host_set_effect_settings_eq, gas_host_set_effect_settings_mod, gas_host_set_effect_settings_stereo, gas_host_set_effect_settings_filter, gas_host_set_playback_disable_threshold_db, gas_host_is_playback_active, gas_host_set_playback_paused,
+ *     gas_host_set_effect_settings, gas_host_set_effect_settings_dyn, gas_host_set_effect_settings_line, gas_host_set_effect_settings_eq, gas_host_set_effect_settings_mod, gas_host_set_effect_settings_stereo, gas_host_set_effect_settings_filter, gas_host_set_hrtf_blend, gas_host_set_playback_disable_threshold_db, gas_host_is_playback_active, gas_host_set_playback_paused,
  *     gas_host_is_playback_paused, gas_host_get_playback_position, gas_host_playback_count, gas_host_set_release_fn,
  *     gas_host_collect_released, gas_host_set_process_effects_fn -- may be
  *     called from any number of threads (main, physics) at any time, concurrently with the audio thread.  They only
@@ -77,6 +77,11 @@ int gas_host_set_effect_settings_stereo(gas_host *host, uint32_t id, const gas_f
 /* The same for the playback's GAS_FX_FILTER settings (gas_fx_filter_settings), through the same queue; settings
  * gas_fx_filter_settings_publish would refuse are GAS_ERR_INVALID_ARGUMENT here.  Control thread. */
 int gas_host_set_effect_settings_filter(gas_host *host, uint32_t id, const gas_fx_filter_settings *settings);
+/* The playback's HRIR blend row (gas_hrtf_blend, GAS_FLAG_HRTF_INTERPOLATE contexts), through the same queue.  A
+ * context without the flag, a negative weight or one that is not finite are GAS_ERR_INVALID_ARGUMENT here; a direction
+ * beyond the loaded set is only seen by gas_hrtf_blend_publish on the audio thread, which then drops the row (the
+ * playback keeps its previous one).  Control thread. */
+int gas_host_set_hrtf_blend(gas_host *host, uint32_t id, const gas_hrtf_blend *blend);
 void gas_host_set_playback_disable_threshold_db(gas_host *host, float db); /* audio_spatializer.h:87 */
 int gas_host_is_playback_active(gas_host *host, uint32_t id);
 /* set_playback_paused / is_playback_paused (audio_spatializer.cpp:115-122, :161-170), PER PLAYBACK: the reference

@@ -274,6 +274,7 @@ FLAG_DIRECTION_RUNS = 16
 FLAG_XCD_ORDER = 32
 FLAG_BATCHED_LAUNCH = 64
 FLAG_HRTF_INTERPOLATE = 128
+FLAG_HRTF_BLEND_FADE = 256  # with FLAG_HRTF_INTERPOLATE only: fade from the previous callback's blend to this one's
 
 STATUS = {
     0: "GAS_OK",

@@ -337,6 +337,10 @@ inline bool blend_on(const gas_ctx *c) {
 	return (c->cfg.flags & GAS_FLAG_HRTF_INTERPOLATE) != 0;
 }
 
+inline bool fade_on(const gas_ctx *c) {
+	return (c->cfg.flags & GAS_FLAG_HRTF_BLEND_FADE) != 0;
+}
+
 inline bool wants_peak(const gas_ctx *c, const SlotInfo &si) {
 	return si.draining || !(c->cfg.flags & GAS_FLAG_PEAKS_DRAINING_ONLY);
 }
@@ -588,7 +592,7 @@ uint64_t group_bytes(const gas_ctx *c, int gt, uint32_t n) {
 			break;
 		case G_FX_HRTF:
 		case G_FX_HRTF_PK:
-			S = 24 + (blend_on(c) ? sizeof(gas_hrtf_blend) : 0); // gain + dir, previous gain r/w, peak; the blend row
+			S = 24 + (blend_on(c) ? sizeof(gas_hrtf_blend) : 0) + (fade_on(c) ? 2 * sizeof(gas_hrtf_blend) : 0); // gain + dir, previous gain r/w, peak; the blend row; the previous effective row r/w
 			H = 2ull * c->hist_len * 4; // history read + write
 			tab = (uint64_t)c->tab.dirs * 2 * GAS_HRTF_TAPS * 4;
 			break;
@@ -598,7 +602,7 @@ uint64_t group_bytes(const gas_ctx *c, int gt, uint32_t n) {
 			break;
 		case G_FX_ER_HRTF:
 		case G_FX_ER_HRTF_PK:
-			S = 24 + 64 + 8 + (blend_on(c) ? sizeof(gas_hrtf_blend) : 0);
+			S = 24 + 64 + 8 + (blend_on(c) ? sizeof(gas_hrtf_blend) : 0) + (fade_on(c) ? 2 * sizeof(gas_hrtf_blend) : 0);
 			H = (uint64_t)GAS_ER_TAPS * F * 8 + F * 8 + 2ull * c->hist_len * 4;
 			tab = (uint64_t)c->tab.dirs * 2 * GAS_HRTF_TAPS * 4;
 			break;
@@ -880,7 +884,7 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 						g_fd.order = ord;
 					}
 				}
-				e = gas_launch_hrtf_ols(c->stream, fd_gt == G_FX_ER_HRTF, (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) != 0, (c->cfg.flags & (GAS_FLAG_DIRECTION_RUNS | GAS_FLAG_DIRECTION_ORDER)) != 0, g_fd, g_pk, c->st, c->tab, c->d_tw, F, c->hist_len, c->cfg.er_ring_frames, parts, p_off, fd_gt == G_FX_HRTF && c->fused_streams ? c->d_cursors : nullptr, c->d_fade_env, fresh, fd_gt == carrier_gt ? job : gas_deferred_reduce(), blend_on(c));
+				e = gas_launch_hrtf_ols(c->stream, fd_gt == G_FX_ER_HRTF, (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) != 0, (c->cfg.flags & (GAS_FLAG_DIRECTION_RUNS | GAS_FLAG_DIRECTION_ORDER)) != 0, g_fd, g_pk, c->st, c->tab, c->d_tw, F, c->hist_len, c->cfg.er_ring_frames, parts, p_off, fd_gt == G_FX_HRTF && c->fused_streams ? c->d_cursors : nullptr, c->d_fade_env, fresh, fd_gt == carrier_gt ? job : gas_deferred_reduce(), blend_on(c), fade_on(c));
 				if (fd_gt == carrier_gt) {
 					carried_bytes = job.partials ? ((uint64_t)job.p_count + 1) * job.elems * sizeof(float) : 0;
 					job = gas_deferred_reduce();
@@ -963,7 +967,7 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 						} else if (is_stereo(kind)) { // k_fx_stereo.hip, settings by chain position; a stereo enhance's state in the slot's ring of chain position j
 							e = gas_launch_fx_stereo(c->stream, kind, in, c->st, F, (uint32_t)j, c->cfg.mix_rate, outb);
 						} else {
-							e = gas_launch_hrtf_rows(c->stream, (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) != 0, in, c->st, c->tab, c->d_tw, F, outb, blend_on(c));
+							e = gas_launch_hrtf_rows(c->stream, (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) != 0, in, c->st, c->tab, c->d_tw, F, outb, blend_on(c), fade_on(c));
 						}
 						in.src = outb; // dense rows from here on
 						in.rows = nullptr;
@@ -2020,6 +2024,7 @@ void gas_ctx_destroy(gas_ctx *c) {
 	(void)hipFree(c->st.fxs);
 	(void)hipHostFree(c->h_fx_upload);
 	(void)hipFree(c->st.hrtf_blend);
+	(void)hipFree(c->st.hrtf_prev_blend);
 	(void)hipHostFree(c->h_blend_upload);
 	(void)hipFree(c->st.dyn);
 	(void)hipFree(c->st.dist_h);
@@ -2094,6 +2099,9 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 	if ((cfg->flags & GAS_FLAG_HRTF_INTERPOLATE) != 0 && (cfg->flags & (GAS_FLAG_HRTF_CROSSFADE | GAS_FLAG_DIRECTION_RUNS | GAS_FLAG_DIRECTION_ORDER | GAS_FLAG_XCD_ORDER)) != 0) {
 		return GAS_ERR_INVALID_ARGUMENT; // those fade from, group by or order by a source's ONE direction
 	}
+	if ((cfg->flags & GAS_FLAG_HRTF_BLEND_FADE) != 0 && ((cfg->flags & GAS_FLAG_HRTF_INTERPOLATE) == 0 || (cfg->flags & (GAS_FLAG_HRTF_CROSSFADE | GAS_FLAG_DIRECTION_RUNS | GAS_FLAG_DIRECTION_ORDER | GAS_FLAG_XCD_ORDER)) != 0)) {
+		return GAS_ERR_INVALID_ARGUMENT; // the fade is between blend rows: nothing to fade without them
+	}
 	int n_dev = 0;
 	if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0 || cfg->device < 0 || cfg->device >= n_dev) {
 		return GAS_ERR_NO_DEVICE;
@@ -2134,6 +2142,10 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 		if ((cfg->flags & GAS_FLAG_HRTF_INTERPOLATE) != 0) { // every slot starts with the all-zero row: no blend
 			GAS_HIP(c, hipMalloc(&c->st.hrtf_blend, sizeof(gas_hrtf_blend) * N));
 			GAS_HIP(c, hipMemsetAsync(c->st.hrtf_blend, 0, sizeof(gas_hrtf_blend) * N, c->stream));
+		}
+		if ((cfg->flags & GAS_FLAG_HRTF_BLEND_FADE) != 0) { // no slot has rendered yet: no old row to fade from
+			GAS_HIP(c, hipMalloc(&c->st.hrtf_prev_blend, sizeof(gas_hrtf_blend) * N));
+			GAS_HIP(c, hipMemsetAsync(c->st.hrtf_prev_blend, 0, sizeof(gas_hrtf_blend) * N, c->stream));
 		}
 		c->st.dyn_stride = (uint32_t)N;
 		GAS_HIP(c, hipMalloc(&c->st.dyn, sizeof(gas_fx_dyn_settings) * N));
@@ -3055,7 +3067,8 @@ int gas_process_block_streams(gas_ctx *c, const uint32_t *slots, uint32_t n, uin
 	}
 	// rows for this callback live in the library's staging buffer (not needed when k_hrtf_ols samples the
 	// streams itself: every playback a plain [HRTF] chain)
-	const bool all_hrtf = c->stream_all_hrtf && !c->stream_any_resampled; // the fused prologue samples plain playbacks only
+	// (GAS_FLAG_HRTF_BLEND_FADE: the stream-sampling form has no registers left for the fade, DESIGN.md 3.4 -- rows first)
+	const bool all_hrtf = c->stream_all_hrtf && !c->stream_any_resampled && !fade_on(c); // the fused prologue samples plain playbacks only
 	if (!all_hrtf) {
 		const size_t need = (size_t)n * F;
 		if (need > c->d_src_frames) {

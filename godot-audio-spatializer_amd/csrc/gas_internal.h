@@ -118,6 +118,10 @@ struct gas_dev_state {
 	// GAS_FLAG_HRTF_INTERPOLATE: the HRIR rows each slot's HRTF stage blends (nullptr without the flag); read by
 	// k_hrtf_ols_blend / k_hrtf_rows_blend, written by uploads and k_calc_spatialization only
 	gas_hrtf_blend *hrtf_blend; // [max_sources], all-zero row = hrtf_dir at weight 1
+	// GAS_FLAG_HRTF_BLEND_FADE: the effective row (compacted, clamped, {hrtf_dir, 1} for the all-zero row) each slot's HRTF
+	// stage last rendered with, all-zero = none yet (nullptr without the flag); read and replaced by
+	// k_hrtf_ols_blend_fade / k_hrtf_rows_blend_fade, zeroed with the slot's other DSP state (k_zero_slot)
+	gas_hrtf_blend *hrtf_prev_blend; // [max_sources]
 };
 
 // Device-resident playback cursor: what SpatialPlaybackListNode + the engine's sampler hold.
@@ -222,7 +226,7 @@ struct gas_hrtf_launch_plan {
 };
 void gas_hrtf_plan(uint32_t n_fd, uint32_t n_pk, gas_hrtf_launch_plan *plan);
 uint32_t gas_hrtf_partials(uint32_t n); // workgroups of a single-path launch (k_er_only, k_hrtf_rows, k_rows_accumulate)
-hipError_t gas_launch_hrtf_ols(hipStream_t stream, bool with_er, bool crossfade, bool runs /* sum runs of equal directions before the FFT */, const gas_group_args &g_fd, const gas_group_args &g_pk, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *twiddles, uint32_t frames, uint32_t hist_len, uint32_t er_ring_frames, float *partials, uint32_t p_offset, gas_cursor *cursors /* non-null: sample the bound streams in the kernel */, const float *fade_env, const gas_params *fresh /* non-null: unscattered parameter rows in row order */, const gas_deferred_reduce &job = gas_deferred_reduce(), bool blend = false /* GAS_FLAG_HRTF_INTERPOLATE: k_hrtf_ols_blend (no cross-fade, no runs, no carried sum) */);
+hipError_t gas_launch_hrtf_ols(hipStream_t stream, bool with_er, bool crossfade, bool runs /* sum runs of equal directions before the FFT */, const gas_group_args &g_fd, const gas_group_args &g_pk, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *twiddles, uint32_t frames, uint32_t hist_len, uint32_t er_ring_frames, float *partials, uint32_t p_offset, gas_cursor *cursors /* non-null: sample the bound streams in the kernel */, const float *fade_env, const gas_params *fresh /* non-null: unscattered parameter rows in row order */, const gas_deferred_reduce &job = gas_deferred_reduce(), bool blend = false /* GAS_FLAG_HRTF_INTERPOLATE: k_hrtf_ols_blend (no cross-fade, no runs, no carried sum) */, bool fade = false /* GAS_FLAG_HRTF_BLEND_FADE, with blend only: k_hrtf_ols_blend_fade */);
 // k_hrtf_uni.hip: all plain [HRTF] sources of a callback in one uniform launch; peak_bits (bit per group entry, or
 // nullptr) / peak_all say which sources also get their exact output peak
 uint32_t gas_hrtf_uni_partials(uint32_t n); // workgroups (= partial mixes) of a k_hrtf_uni launch
@@ -251,7 +255,7 @@ hipError_t gas_launch_hrtf_multi(hipStream_t stream, const gas_group_args &g, co
 hipError_t gas_launch_hrtf_uni(hipStream_t stream, const gas_group_args &g, const uint32_t *peak_bits, bool peak_all, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *twiddles, uint32_t frames, uint32_t hist_len, float *partials, uint32_t p_offset, gas_cursor *cursors, const float *fade_env, const gas_params *fresh, const gas_deferred_reduce &job = gas_deferred_reduce(), const gas_bus_route *routes = nullptr /* non-null: the two-bus form */, uint32_t bus_rows = 0, uint32_t bus_base = 0 /* the launch's pair of buses: bus_base, bus_base + 1 */, bool commit = true /* false: leave history / previous gain / peaks to a later pass */, uint32_t er_ring_frames = 0 /* non-zero: the chain [EARLY_REFLECTIONS, HRTF] */, uint32_t peak_from = 0xffffffffu /* entries from here on report their exact peak */, uint32_t peak_bit_base = 0 /* entry e's bit in peak_bits is bit e + peak_bit_base */, uint32_t flt_kind = 0 /* non-zero: the chain [this one-biquad kind, HRTF] */, uint32_t flt_pos = 0 /* its chain position (processor state, effect settings) */, float mix_rate = 0.0f);
 hipError_t gas_launch_er_only(hipStream_t stream, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t er_ring_frames, float *partials, uint32_t p_offset, uint32_t p_stride, gas_audio_frame *rows_out = nullptr);
 // stages of a general effect chain (rows in -> rows out) and its final mix
-hipError_t gas_launch_hrtf_rows(hipStream_t stream, bool crossfade, const gas_group_args &g, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *twiddles, uint32_t frames, gas_audio_frame *rows_out, bool blend = false /* GAS_FLAG_HRTF_INTERPOLATE */);
+hipError_t gas_launch_hrtf_rows(hipStream_t stream, bool crossfade, const gas_group_args &g, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *twiddles, uint32_t frames, gas_audio_frame *rows_out, bool blend = false /* GAS_FLAG_HRTF_INTERPOLATE */, bool fade = false /* GAS_FLAG_HRTF_BLEND_FADE, with blend only */);
 hipError_t gas_launch_rows_accumulate(hipStream_t stream, const gas_group_args &g, uint32_t frames, float *partials, uint32_t p_offset);
 hipError_t gas_launch_rows_accumulate_buses(hipStream_t stream, const gas_group_args &g, uint32_t frames, const gas_bus_route *routes, uint32_t n_buses, uint32_t bus_rows, float *partials, uint32_t p_offset); // bus b's partial rows: [b * bus_rows + p_offset + workgroup]
 

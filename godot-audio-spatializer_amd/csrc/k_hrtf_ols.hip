@@ -93,10 +93,13 @@ __device__ __forceinline__ void blend_spectra(const float4 *__restrict__ spec, i
 	}
 }
 
-template <int SQ, bool WITH_ER, bool PEAKS, bool SRC_PCM, bool XFADE, bool RUNS = false, bool BLEND = false>
-__device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const uint32_t wg, const gas_group_args &g, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *__restrict__ tw, uint32_t n_wgs, uint32_t er_R, float *__restrict__ my_partial, gas_cursor *__restrict__ cursors, const float *__restrict__ fade_env, const gas_params *__restrict__ fresh, gas_audio_frame *__restrict__ rows_out = nullptr, const gas_deferred_reduce job = gas_deferred_reduce(), uint32_t job_col = 0) {
+template <int SQ, bool WITH_ER, bool PEAKS, bool SRC_PCM, bool XFADE, bool RUNS = false, bool BLEND = false, bool FADE = false>
+__device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const uint32_t wg, const gas_group_args &g, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *__restrict__ tw, uint32_t n_wgs, uint32_t er_R, float *__restrict__ my_partial, gas_cursor *__restrict__ cursors, const float *__restrict__ fade_env, const gas_params *__restrict__ fresh, gas_audio_frame *__restrict__ rows_out = nullptr, const gas_deferred_reduce job = gas_deferred_reduce(), uint32_t job_col = 0, float2 *fade_lds = nullptr) {
 	static_assert(!(WITH_ER && SRC_PCM), "the early-reflection prologue reads float rows");
 	static_assert(!(BLEND && (XFADE || RUNS)), "a blended source has no single direction to fade from or to group by");
+	static_assert(!FADE || BLEND, "GAS_FLAG_HRTF_BLEND_FADE fades between blend rows");
+	// two renders per source lerped with t = f/F: the old direction's (XFADE) or the old blend row's (FADE)
+	constexpr bool TWO = XFADE || FADE;
 	constexpr int FQ = 2 * SQ; // F / 64
 	constexpr int HQ = 8 - SQ; // hist_len / 64
 	constexpr int NQ = 8 + SQ; // (hist_len + F) / 64
@@ -108,6 +111,22 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 	const int lane = threadIdx.x & 63;
 	const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 	float2 *lds = lds_all + wave * LDS_F2_PER_WAVE;
+	// FADE: where this wave keeps the old effective rows of its sources (32 bytes each, by source number) and, in the
+	// frequency-domain form, its difference sum fade_d[ear][j][lane] (below).  The exact-peak form's transform pairs
+	// use both exchange slices, so its rows sit in fade_lds; the frequency-domain loop transforms one spectrum at a
+	// time in the first slice, so its rows sit in the second and fade_lds holds the sums.
+	uint32_t *old_rows = nullptr;
+	float2 *fade_d = nullptr;
+	if constexpr (FADE) {
+		old_rows = PEAKS ? reinterpret_cast<uint32_t *>(fade_lds + wave * 256) : reinterpret_cast<uint32_t *>(lds + LDS_F2_HALF);
+		fade_d = fade_lds + wave * 1024;
+		if constexpr (!PEAKS) {
+#pragma unroll
+			for (int j = 0; j < 16; j++) {
+				fade_d[j * 64 + lane] = make_float2(0.0f, 0.0f); // lane-private from here to the epilogue: no barrier
+			}
+		}
+	}
 
 	GAS_STAMP(0);
 #ifdef GAS_STAMPS
@@ -181,7 +200,7 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 	// requested once its direction is known (parameter row -> direction -> table row: two dependent round trips,
 	// 2.7 us of a 16.7 us launch when the first product waited for them), whereas its frames need one; with the skew
 	// the table row of run r travels while run r+1 is loaded and transformed.
-	constexpr bool SKEW = !PEAKS && !XFADE;
+	constexpr bool SKEW = !PEAKS && !TWO;
 	float2 zp[8]; // spectrum of the previous run, its table row in flight
 	bool have_prev = false; // wave-uniform
 #pragma unroll
@@ -211,6 +230,7 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 	// keeps in flight is the blend's first row
 	uint32_t bl_d[3] = { 0, 0, 0 };
 	float bl_w0 = 1.0f, bl_w[3] = { 0.0f, 0.0f, 0.0f };
+	bool fade_changed = false; // FADE: this lane's source has an old row and it differs from the new one
 	const bool have = first + lane < last; // <= 64 sources per wave (gas_hrtf_plan): one lane per source of this wave
 	if (have) {
 		const uint32_t e = g.order ? g.order[first + lane] : first + lane; // direction order (k_dir_order) or entry order
@@ -268,6 +288,25 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 				bl_d[j] = cd[j + 1];
 				bl_w[j] = cw[j + 1];
 			}
+			if constexpr (FADE) {
+				// GAS_FLAG_HRTF_BLEND_FADE: the effective row of the last callback that processed this slot (all-zero =
+				// none yet, which an effective row never is: its first weight is not 0) is compared word by word with
+				// this callback's, replaced by it, and parked in the wave's LDS rows, where the loop finds it by source
+				// number: no lane registers are held for it across the loop.
+				const uint4 nd = make_uint4(cd[0], cd[1], cd[2], cd[3]);
+				const uint4 nw = make_uint4(__float_as_uint(bl_w0), __float_as_uint(cw[1]), __float_as_uint(cw[2]), __float_as_uint(cw[3]));
+				uint4 *prev = reinterpret_cast<uint4 *>(st.hrtf_prev_blend + lm.slot);
+				const uint4 od = prev[0], ow = prev[1];
+				const bool has_old = (od.x | od.y | od.z | od.w | ow.x | ow.y | ow.z | ow.w) != 0;
+				fade_changed = has_old && (((od.x ^ nd.x) | (od.y ^ nd.y) | (od.z ^ nd.z) | (od.w ^ nd.w) | (ow.x ^ nw.x) | (ow.y ^ nw.y) | (ow.z ^ nw.z) | (ow.w ^ nw.w)) != 0);
+				if (!(GAS_ABL & 64)) {
+					prev[0] = nd;
+					prev[1] = nw;
+				}
+				uint4 *mine = reinterpret_cast<uint4 *>(old_rows) + lane * 2;
+				mine[0] = od;
+				mine[1] = ow;
+			}
 		}
 		lm.pdir = lm.dir;
 		if constexpr (XFADE) {
@@ -288,6 +327,11 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 				*reinterpret_cast<float2 *>(g.peaks + (size_t)lm.row * 2) = make_float2(__builtin_inff(), __builtin_inff());
 			}
 		}
+	}
+	// FADE: bit i = the wave's source number i renders its old row too (wave-uniform in the loop, like `changed` of XFADE)
+	const unsigned long long fade_mask = FADE ? __ballot(fade_changed) : 0ull;
+	if constexpr (FADE) {
+		wave_lds_sync(); // the old rows are read back by source number, not by lane
 	}
 	if (first < last) {
 #pragma unroll
@@ -339,6 +383,30 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 				w[k] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bl_w[k]), (int)i));
 			}
 			blend_spectra(tab.spec, lane, hs, __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bl_w0), (int)i)), d, w);
+		}
+	};
+
+	// FADE, changed sources only: the old effective row of the wave's source number i, from its LDS row.  The first
+	// row is requested like any single row (issue_spectra); the others are added the way blend_spectra adds the new
+	// blend's, through the one landing buffer.  Directions are clamped again: the set may have been reloaded since.
+	auto fade_old_first = [&](uint32_t i) {
+		if constexpr (FADE) {
+			const uint32_t d0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)old_rows[i * 8]);
+			issue_spectra(tab.spec, d0 < tab.dirs ? d0 : 0, lane, hs);
+		}
+	};
+	auto fade_old_rows = [&](uint32_t i) {
+		if constexpr (FADE) {
+			const uint32_t *r = old_rows + i * 8;
+			uint32_t d[3];
+			float w[3];
+#pragma unroll
+			for (int k = 0; k < 3; k++) {
+				const uint32_t dk = (uint32_t)__builtin_amdgcn_readfirstlane((int)r[1 + k]);
+				d[k] = dk < tab.dirs ? dk : 0;
+				w[k] = __int_as_float(__builtin_amdgcn_readfirstlane((int)r[5 + k]));
+			}
+			blend_spectra(tab.spec, lane, hs, __int_as_float(__builtin_amdgcn_readfirstlane((int)r[4])), d, w);
 		}
 	};
 
@@ -493,7 +561,7 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 		}
 
 		// z = a + i b : a = x_full[0..512), b = x_full[S..S+512)
-		const bool changed = XFADE && m.pdir != m.dir; // wave-uniform
+		const bool changed = FADE ? ((fade_mask >> (e - first)) & 1ull) != 0 : (XFADE && m.pdir != m.dir); // wave-uniform
 		if constexpr (PEAKS) {
 			float2 v[8];
 #pragma unroll
@@ -511,7 +579,11 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 			}
 			// spectra registers are free again: the old direction's rows (cross-fade) or the next source's
 			if (changed) {
-				issue_spectra(tab.spec, m.pdir, lane, hs);
+				if constexpr (FADE) {
+					fade_old_first(e - first);
+				} else {
+					issue_spectra(tab.spec, m.pdir, lane, hs);
+				}
 			} else if (has_next) {
 				issue_spectra(tab.spec, mn.dir, lane, hs);
 			}
@@ -526,8 +598,9 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 				oR[t] = yr[HQ + t].x;
 				oR[SQ + t] = yr[HQ + t].y;
 			}
-			if constexpr (XFADE) {
-				if (changed) { // render the old direction too and blend, t = frame / F
+			if constexpr (TWO) {
+				if (changed) { // render the old direction (FADE: the old blend) too and blend, t = frame / F
+					fade_old_rows(e - first);
 					finish_spectra(lane, hs);
 #pragma unroll
 					for (int j = 0; j < 8; j++) {
@@ -600,7 +673,10 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 					}
 					have_prev = true;
 				} else {
-				static_assert(SKEW || !BLEND || PEAKS, "the blend form takes its products in the skewed loop");
+				static_assert(SKEW || !BLEND || PEAKS || FADE, "the blend form takes its products in the skewed loop, the blend fade like the cross-fade");
+				if constexpr (FADE) {
+					blend_rows(e - first);
+				}
 				finish_spectra(lane, hs);
 #pragma unroll
 				for (int j = 0; j < 8; j++) {
@@ -608,6 +684,12 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 					const float2 pr = cmul(zs[j], make_float2(hs[j].z, hs[j].w));
 					aYL[j] = cadd(aYL[j], pl);
 					aYR[j] = cadd(aYR[j], pr);
+					if constexpr (FADE) {
+						if (changed) { // bY = aY + fade_d: take the new products out again, the old ones go in below
+							fade_d[j * 64 + lane] = csub(fade_d[j * 64 + lane], pl);
+							fade_d[(8 + j) * 64 + lane] = csub(fade_d[(8 + j) * 64 + lane], pr);
+						}
+					}
 					if constexpr (XFADE) {
 						if (!changed) { // same HRIR on both sides of the fade
 							bYL[j] = cadd(bYL[j], pl);
@@ -623,6 +705,18 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 						for (int j = 0; j < 8; j++) {
 							bYL[j] = cadd(bYL[j], cmul(zs[j], make_float2(hs[j].x, hs[j].y)));
 							bYR[j] = cadd(bYR[j], cmul(zs[j], make_float2(hs[j].z, hs[j].w)));
+						}
+					}
+				}
+				if constexpr (FADE) {
+					if (changed) { // the old blended spectra, built in the registers the new products left free
+						fade_old_first(e - first);
+						fade_old_rows(e - first);
+						finish_spectra(lane, hs);
+#pragma unroll
+						for (int j = 0; j < 8; j++) {
+							fade_d[j * 64 + lane] = cadd(fade_d[j * 64 + lane], cmul(zs[j], make_float2(hs[j].x, hs[j].y)));
+							fade_d[(8 + j) * 64 + lane] = cadd(fade_d[(8 + j) * 64 + lane], cmul(zs[j], make_float2(hs[j].z, hs[j].w)));
 						}
 					}
 				}
@@ -705,14 +799,19 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 		}
 		float2 *fd = lds_all;
 		float *outp = reinterpret_cast<float *>(lds_all + FD_F2 + 2 * LDS_F2_HALF);
-		constexpr int ROUNDS = XFADE ? 2 : 1;
+		constexpr int ROUNDS = TWO ? 2 : 1;
 #pragma unroll
 		for (int round = 0; round < ROUNDS; round++) {
 			__syncthreads(); // every wave is done with its exchange slice / the previous round (fd aliases them)
 #pragma unroll
 			for (int j = 0; j < 8; j++) {
-				fd[(wave * 2 + 0) * 512 + j * 64 + lane] = round == 0 ? aYL[j] : bYL[j];
-				fd[(wave * 2 + 1) * 512 + j * 64 + lane] = round == 0 ? aYR[j] : bYR[j];
+				if constexpr (FADE) { // the old blends' sums: the new ones' plus the changed sources' differences
+					fd[(wave * 2 + 0) * 512 + j * 64 + lane] = round == 0 ? aYL[j] : cadd(aYL[j], fade_d[j * 64 + lane]);
+					fd[(wave * 2 + 1) * 512 + j * 64 + lane] = round == 0 ? aYR[j] : cadd(aYR[j], fade_d[(8 + j) * 64 + lane]);
+				} else {
+					fd[(wave * 2 + 0) * 512 + j * 64 + lane] = round == 0 ? aYL[j] : bYL[j];
+					fd[(wave * 2 + 1) * 512 + j * 64 + lane] = round == 0 ? aYR[j] : bYR[j];
+				}
 			}
 			__syncthreads();
 			if (round == 0) {
@@ -767,7 +866,7 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 #pragma unroll
 				for (int t = 0; t < SQ; t++) {
 					const int fa = lane + 64 * t, fb = lane + 64 * (SQ + t);
-					if constexpr (!XFADE) {
+					if constexpr (!TWO) {
 						outp[fa * 2 + wave] = y[HQ + t].x;
 						outp[fb * 2 + wave] = y[HQ + t].y;
 					} else {
@@ -803,6 +902,9 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 	(void)bl_d;
 	(void)bl_w0;
 	(void)bl_w;
+	(void)fade_changed;
+	(void)fade_mask;
+	(void)fade_d;
 }
 
 // One launch per callback for every HRTF source: workgroups [0, wgs_fd) run the frequency-domain body over
@@ -843,6 +945,31 @@ __global__ __launch_bounds__(WAVES * 64, GAS_HRTF_WAVES_PER_SIMD) void k_hrtf_ro
 	__shared__ float2 lds_all[HrtfLds<SQ, true>::TOTAL_F2];
 	__shared__ float2 tw_lds[GAS_TW_LDS ? 1024 : 1];
 	hrtf_body<SQ, false, true, false, false, false, true>(lds_all, tw_lds, blockIdx.x, g, st, tab, tw, gridDim.x, 0, nullptr, nullptr, nullptr, nullptr, rows_out);
+}
+
+// GAS_FLAG_HRTF_BLEND_FADE: the blend kernels with the fade from each source's previous effective row (st.hrtf_prev_blend);
+// again kernels of their own.  fade_lds: per wave 2 KiB of old rows (exact-peak form) or 8 KiB of difference sums
+// (frequency-domain form).  No stream-sampling form: a fade context samples its streams into rows first (k_sample_sources).
+template <int SQ, bool WITH_ER>
+__global__ __launch_bounds__(WAVES * 64, GAS_HRTF_WAVES_PER_SIMD) void k_hrtf_ols_blend_fade(gas_group_args g_fd, gas_group_args g_pk, uint32_t wgs_fd, gas_dev_state st, gas_hrtf_table tab, const float2 *__restrict__ tw, uint32_t er_R, float *__restrict__ partials, uint32_t p_offset, const float *__restrict__ fade_env, const gas_params *__restrict__ fresh) {
+	constexpr int LDS_F2 = HrtfLds<SQ, false>::TOTAL_F2 > HrtfLds<SQ, true>::TOTAL_F2 ? HrtfLds<SQ, false>::TOTAL_F2 : HrtfLds<SQ, true>::TOTAL_F2;
+	__shared__ __attribute__((aligned(16))) float2 lds_all[LDS_F2];
+	__shared__ float2 tw_lds[GAS_TW_LDS ? 1024 : 1];
+	__shared__ __attribute__((aligned(16))) float2 fade_lds[WAVES * 1024];
+	float *my_partial = partials + ((size_t)p_offset + blockIdx.x) * (size_t)(2 * SQ * 64 * 2);
+	if (blockIdx.x < wgs_fd) {
+		hrtf_body<SQ, WITH_ER, false, false, false, false, true, true>(lds_all, tw_lds, blockIdx.x, g_fd, st, tab, tw, wgs_fd, er_R, my_partial, nullptr, fade_env, fresh, nullptr, gas_deferred_reduce(), 0, fade_lds);
+	} else {
+		hrtf_body<SQ, WITH_ER, true, false, false, false, true, true>(lds_all, tw_lds, blockIdx.x - wgs_fd, g_pk, st, tab, tw, gridDim.x - wgs_fd, er_R, my_partial, nullptr, fade_env, fresh, nullptr, gas_deferred_reduce(), 0, fade_lds);
+	}
+}
+
+template <int SQ>
+__global__ __launch_bounds__(WAVES * 64, GAS_HRTF_WAVES_PER_SIMD) void k_hrtf_rows_blend_fade(gas_group_args g, gas_dev_state st, gas_hrtf_table tab, const float2 *__restrict__ tw, gas_audio_frame *__restrict__ rows_out) {
+	__shared__ float2 lds_all[HrtfLds<SQ, true>::TOTAL_F2];
+	__shared__ float2 tw_lds[GAS_TW_LDS ? 1024 : 1];
+	__shared__ __attribute__((aligned(16))) float2 fade_lds[WAVES * 256];
+	hrtf_body<SQ, false, true, false, false, false, true, true>(lds_all, tw_lds, blockIdx.x, g, st, tab, tw, gridDim.x, 0, nullptr, nullptr, nullptr, nullptr, rows_out, gas_deferred_reduce(), 0, fade_lds);
 }
 
 // One HRTF stage of a general effect chain: stereo rows in (mono downmix inside), per-source stereo rows out.
@@ -1147,7 +1274,7 @@ uint32_t gas_hrtf_partials(uint32_t n) {
 	return p.wgs_fd;
 }
 
-hipError_t gas_launch_hrtf_ols(hipStream_t stream, bool with_er, bool crossfade, bool runs, const gas_group_args &g_fd, const gas_group_args &g_pk, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *twiddles, uint32_t frames, uint32_t hist_len, uint32_t er_ring_frames, float *partials, uint32_t p_offset, gas_cursor *cursors, const float *fade_env, const gas_params *fresh, const gas_deferred_reduce &job, bool blend) {
+hipError_t gas_launch_hrtf_ols(hipStream_t stream, bool with_er, bool crossfade, bool runs, const gas_group_args &g_fd, const gas_group_args &g_pk, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *twiddles, uint32_t frames, uint32_t hist_len, uint32_t er_ring_frames, float *partials, uint32_t p_offset, gas_cursor *cursors, const float *fade_env, const gas_params *fresh, const gas_deferred_reduce &job, bool blend, bool fade) {
 	if (g_fd.n + g_pk.n == 0) {
 		return hipSuccess;
 	}
@@ -1157,13 +1284,20 @@ hipError_t gas_launch_hrtf_ols(hipStream_t stream, bool with_er, bool crossfade,
 	if (blend && (crossfade || runs || job.partials || !st.hrtf_blend)) {
 		return hipErrorInvalidValue;
 	}
+	if (fade && (!blend || !st.hrtf_prev_blend || cursors)) { // (a fade context samples its streams into rows first)
+		return hipErrorInvalidValue;
+	}
 	gas_hrtf_launch_plan plan;
 	gas_hrtf_plan(g_fd.n, g_pk.n, &plan);
 	const uint32_t wgs_fd = plan.wgs_fd;
 	dim3 grid(plan.wgs_fd + plan.wgs_pk), block(WAVES * 64);
 	if (blend) {
-#define GAS_HRTF_BLEND_LAUNCH(SQv, ERv, PCMv) \
-	hipLaunchKernelGGL((k_hrtf_ols_blend<SQv, ERv, PCMv>), grid, block, 0, stream, g_fd, g_pk, wgs_fd, st, tab, twiddles, er_ring_frames, partials, p_offset, cursors, fade_env, fresh)
+#define GAS_HRTF_BLEND_LAUNCH(SQv, ERv, PCMv)                                                                                                                                                         \
+	if (fade) {                                                                                                                                                                                        \
+		hipLaunchKernelGGL((k_hrtf_ols_blend_fade<SQv, ERv>), grid, block, 0, stream, g_fd, g_pk, wgs_fd, st, tab, twiddles, er_ring_frames, partials, p_offset, fade_env, fresh);                \
+	} else {                                                                                                                                                                                           \
+		hipLaunchKernelGGL((k_hrtf_ols_blend<SQv, ERv, PCMv>), grid, block, 0, stream, g_fd, g_pk, wgs_fd, st, tab, twiddles, er_ring_frames, partials, p_offset, cursors, fade_env, fresh);      \
+	}
 #define GAS_HRTF_BLEND_CASE(SQv)                          \
 	case SQv:                                             \
 		if (with_er) {                                    \
@@ -1251,11 +1385,14 @@ hipError_t gas_launch_er_only(hipStream_t stream, const gas_group_args &g, const
 	return hipGetLastError();
 }
 
-hipError_t gas_launch_hrtf_rows(hipStream_t stream, bool crossfade, const gas_group_args &g, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *twiddles, uint32_t frames, gas_audio_frame *rows_out, bool blend) {
+hipError_t gas_launch_hrtf_rows(hipStream_t stream, bool crossfade, const gas_group_args &g, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *twiddles, uint32_t frames, gas_audio_frame *rows_out, bool blend, bool fade) {
 	if (g.n == 0) {
 		return hipSuccess;
 	}
 	if (blend && (crossfade || !st.hrtf_blend)) {
+		return hipErrorInvalidValue;
+	}
+	if (fade && (!blend || !st.hrtf_prev_blend)) {
 		return hipErrorInvalidValue;
 	}
 	const uint32_t wgs = gas_hrtf_partials(g.n);
@@ -1263,16 +1400,32 @@ hipError_t gas_launch_hrtf_rows(hipStream_t stream, bool crossfade, const gas_gr
 	if (blend) {
 		switch (frames / 128) {
 			case 1:
-				hipLaunchKernelGGL((k_hrtf_rows_blend<1>), grid, block, 0, stream, g, st, tab, twiddles, rows_out);
+				if (fade) {
+					hipLaunchKernelGGL((k_hrtf_rows_blend_fade<1>), grid, block, 0, stream, g, st, tab, twiddles, rows_out);
+				} else {
+					hipLaunchKernelGGL((k_hrtf_rows_blend<1>), grid, block, 0, stream, g, st, tab, twiddles, rows_out);
+				}
 				break;
 			case 2:
-				hipLaunchKernelGGL((k_hrtf_rows_blend<2>), grid, block, 0, stream, g, st, tab, twiddles, rows_out);
+				if (fade) {
+					hipLaunchKernelGGL((k_hrtf_rows_blend_fade<2>), grid, block, 0, stream, g, st, tab, twiddles, rows_out);
+				} else {
+					hipLaunchKernelGGL((k_hrtf_rows_blend<2>), grid, block, 0, stream, g, st, tab, twiddles, rows_out);
+				}
 				break;
 			case 3:
-				hipLaunchKernelGGL((k_hrtf_rows_blend<3>), grid, block, 0, stream, g, st, tab, twiddles, rows_out);
+				if (fade) {
+					hipLaunchKernelGGL((k_hrtf_rows_blend_fade<3>), grid, block, 0, stream, g, st, tab, twiddles, rows_out);
+				} else {
+					hipLaunchKernelGGL((k_hrtf_rows_blend<3>), grid, block, 0, stream, g, st, tab, twiddles, rows_out);
+				}
 				break;
 			case 4:
-				hipLaunchKernelGGL((k_hrtf_rows_blend<4>), grid, block, 0, stream, g, st, tab, twiddles, rows_out);
+				if (fade) {
+					hipLaunchKernelGGL((k_hrtf_rows_blend_fade<4>), grid, block, 0, stream, g, st, tab, twiddles, rows_out);
+				} else {
+					hipLaunchKernelGGL((k_hrtf_rows_blend<4>), grid, block, 0, stream, g, st, tab, twiddles, rows_out);
+				}
 				break;
 			default:
 				return hipErrorInvalidValue;

@@ -122,6 +122,11 @@ __global__ void k_zero_slot(gas_dev_state st, uint32_t slot, uint32_t hist_len, 
 		st.was_further[slot] = 0;
 		st.hrtf_prev_gain[slot] = 0.0f;
 		st.hrtf_prev_dir[slot] = 0;
+		if (st.hrtf_prev_blend) { // GAS_FLAG_HRTF_BLEND_FADE: no old row, the next block renders its row alone
+			uint4 *pb = reinterpret_cast<uint4 *>(st.hrtf_prev_blend + slot);
+			pb[0] = make_uint4(0, 0, 0, 0);
+			pb[1] = make_uint4(0, 0, 0, 0);
+		}
 		if (st.er_pos) {
 			st.er_pos[slot] = 0;
 		}

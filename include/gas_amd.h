@@ -224,10 +224,34 @@ typedef struct gas_config {
  * Cost per context: 32 bytes of device memory per slot of max_sources for the blend table (0.26 MB at 8192 slots, 2 MB
  * at 65 536, 260 MB at 8.1 M) plus, once a row has been published, 32 bytes of pinned host memory per slot for the
  * upload; the host mirror is 32 bytes per slot of ordinary memory.  gas_ctx_create refuses the flag
- * (GAS_ERR_INVALID_ARGUMENT) together with GAS_FLAG_HRTF_CROSSFADE (fading from an old blend to a new one is not
- * implemented) and with GAS_FLAG_DIRECTION_RUNS, GAS_FLAG_DIRECTION_ORDER and GAS_FLAG_XCD_ORDER (they group or order
+ * (GAS_ERR_INVALID_ARGUMENT) together with GAS_FLAG_HRTF_CROSSFADE (that flag fades from ONE
+ * old direction; fading from an old blend to a new one is GAS_FLAG_HRTF_BLEND_FADE) and with GAS_FLAG_DIRECTION_RUNS, GAS_FLAG_DIRECTION_ORDER and GAS_FLAG_XCD_ORDER (they group or order
  * sources by their ONE direction). */
 #define GAS_FLAG_HRTF_INTERPOLATE 128u
+/* NEW: fade between successive blends, valid only together with GAS_FLAG_HRTF_INTERPOLATE.  The blend row is read once
+ * per callback, so without this flag the filter of a moving source switches at every block boundary where its row
+ * changed; with it the block is rendered with the old and the new blend and lerped across the block, the way
+ * GAS_FLAG_HRTF_CROSSFADE lerps between two single directions (mix_channel's volume lerp, audio_spatializer_3d.cpp:591-592).
+ *  - A playback's EFFECTIVE ROW for a callback is what the HRTF stage derives from its gas_hrtf_blend row: the entries
+ *    of non-zero weight moved to the front in index order, directions clamped as hrtf_dir is (>= the set's dirs -> 0),
+ *    the remaining entries zero; the all-zero row becomes { hrtf_dir, 1 }.
+ *  - The stage renders  y[i] = t * (sum_k w_new,k * x conv h[dir_new,k])[i] + (1 - t) * (sum_k w_old,k * x conv
+ *    h[dir_old,k])[i],  t = (float)i * (1 / F),  where `old` is the effective row of the LAST CALLBACK THAT PROCESSED
+ *    THIS SLOT and x is the stage's gained mono input; the hrtf_gain ramp is unchanged and independent of the fade.
+ *  - A slot with no old row renders the new row alone: the first callback after gas_source_alloc, after
+ *    gas_source_reset, and after a free plus re-alloc of the slot.  A playback left out of a callback's list keeps its
+ *    old row.
+ *  - "Changed" means that any of the eight 32-bit words of the effective row differs from the stored one.  A source
+ *    whose row did not change loads no table row beyond those of its blend.
+ *  - Rows written on the device by gas_calc_spatialization fade exactly like published ones: the comparison is made
+ *    in the HRTF kernel, nothing is read back.  Peaks are those of the faded output.
+ * Every road a GAS_FLAG_HRTF_INTERPOLATE context takes is covered (plain [HRTF] and [EARLY_REFLECTIONS, HRTF],
+ * frequency-domain and exact-peak, PCM streams, staged chains, bus callbacks); batched launches do not qualify and a
+ * pipelined callback is summed at once, as with the blend alone.  Cost per context: another 32 bytes of device memory
+ * per slot of max_sources (the stored effective rows).  gas_ctx_create refuses the flag (GAS_ERR_INVALID_ARGUMENT)
+ * without GAS_FLAG_HRTF_INTERPOLATE and with each flag GAS_FLAG_HRTF_INTERPOLATE is refused with.  Contexts without
+ * the flag behave exactly as before. */
+#define GAS_FLAG_HRTF_BLEND_FADE 256u
 
 /* SpatializerParameters (spatializer_parameters.h:39-67) + SpatializerParameters3D
  * (audio_spatializer_3d.h:61-83) as one 128-byte POD, plus the per-block effect

@@ -80,7 +80,8 @@ int gas_host_set_effect_settings_filter(gas_host *host, uint32_t id, const gas_f
 /* The playback's HRIR blend row (gas_hrtf_blend, GAS_FLAG_HRTF_INTERPOLATE contexts), through the same queue.  A
  * context without the flag, a negative weight or one that is not finite are GAS_ERR_INVALID_ARGUMENT here; a direction
  * beyond the loaded set is only seen by gas_hrtf_blend_publish on the audio thread, which then drops the row (the
- * playback keeps its previous one).  Control thread. */
+ * playback keeps its previous one).  Control thread.  GAS_FLAG_HRTF_BLEND_FADE needs nothing from this layer: it is a
+ * flag of the context the host was created on, and the fade happens in the HRTF kernels. */
 int gas_host_set_hrtf_blend(gas_host *host, uint32_t id, const gas_hrtf_blend *blend);
 void gas_host_set_playback_disable_threshold_db(gas_host *host, float db); /* audio_spatializer.h:87 */
 int gas_host_is_playback_active(gas_host *host, uint32_t id);

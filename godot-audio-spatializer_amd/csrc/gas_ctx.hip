@@ -68,12 +68,13 @@ struct ChainRange {
 
 constexpr uint32_t PROFILE_EVENTS = 4096;
 
-// The pooled effect families, in the order their uploads are flushed; k_fx_families describes them.
-enum { FX_LINES = 0, FX_EQ, FX_FILTER, FX_MOD, FX_STEREO, FX_FAMILIES };
+// The effect families, in the order their uploads are flushed; k_fx_families describes them.  The
+// first two have no pool: gas_fx_settings (GAS_FX_LOWPASS .. GAS_FX_AMPLIFY) and gas_fx_dyn_settings.
+enum { FX_BASIC = 0, FX_DYN, FX_LINES, FX_EQ, FX_FILTER, FX_MOD, FX_STEREO, FX_FAMILIES };
 
-// Host side of one pooled family: pool sizes and free entries (alloc_mu), each slot's entries by chain position (written
+// Host side of one family: pool sizes and free entries (alloc_mu), each slot's entries by chain position (written
 // under alloc_mu and params_mu), the settings mirror and what the next flush uploads (params_mu):
-// [m settings][m {slot, entry[4]}][z zero records] through one pinned staging buffer.
+// [m settings][m {slot, entry[4]}][z {pool, entry} zero records] through one pinned staging buffer.
 struct FxFamily {
 	uint32_t cap[2] = { 0, 0 };
 	std::vector<uint32_t> free[2];
@@ -81,7 +82,7 @@ struct FxFamily {
 	std::vector<unsigned char> h_settings; // [max_sources] settings PODs, latest published value
 	std::vector<uint8_t> dirty_flag;
 	std::vector<uint32_t> dirty_list;
-	std::vector<uint32_t> zero_list; // zero records, each entry at most once (zero_pending)
+	std::vector<uint32_t> zero_list; // {pool, entry} zero records, each entry at most once (zero_pending)
 	std::vector<uint8_t> zero_pending[2]; // [pool][entry]: queued in zero_list
 	unsigned char *h_upload = nullptr, *d_upload = nullptr;
 };
@@ -142,25 +143,13 @@ struct gas_ctx {
 	uint32_t *h_upload_slots = nullptr; // pinned
 	gas_params *d_upload = nullptr;
 	uint32_t *d_upload_slots = nullptr;
-	// gas_fx_settings (engine-effect kinds): host mirror, latest wins, uploaded with the parameters (params_mu)
-	std::vector<gas_fx_settings> h_fxs;
-	std::vector<uint8_t> fx_dirty_flag;
-	std::vector<uint32_t> fx_dirty_list;
-	gas_fx_settings *h_fx_upload = nullptr; // pinned, [max_sources], allocated by the first flush that needs it
-	// gas_hrtf_blend rows (GAS_FLAG_HRTF_INTERPOLATE): host mirror, latest wins, uploaded with the parameters the way
-	// gas_fx_settings are (params_mu); empty without the flag
+	// gas_hrtf_blend rows (GAS_FLAG_HRTF_INTERPOLATE): host mirror, latest wins, uploaded with the parameters
+	// (params_mu); empty without the flag
 	std::vector<gas_hrtf_blend> h_blend;
 	std::vector<uint8_t> blend_dirty_flag;
 	std::vector<uint32_t> blend_dirty_list;
 	gas_hrtf_blend *h_blend_upload = nullptr; // pinned, [max_sources], allocated by the first flush that needs it
-	// gas_fx_dyn_settings (GAS_FX_DISTORTION / GAS_FX_COMPRESSOR): host mirror, latest wins (params_mu); uploaded as ONE
-	// copy of [m settings][m slots] out of a pinned staging buffer, then scattered on the device (k_scatter_dyn)
-	std::vector<gas_fx_dyn_settings> h_dyn;
-	std::vector<uint8_t> dyn_dirty_flag;
-	std::vector<uint32_t> dyn_dirty_list;
-	unsigned char *h_dyn_upload = nullptr; // pinned, [max_sources] settings then [max_sources] slots
-	unsigned char *d_dyn_upload = nullptr;
-	// the pooled effect families (gas_ctx_reserve_fx_*), and what their reservations derive from the mix rate
+	// the effect families, and what the reservations (gas_ctx_reserve_fx_*) derive from the mix rate
 	FxFamily fx[FX_FAMILIES];
 	gas_line_geo line_geo{};
 	gas_eq_coefs eq_coefs[3] = {}; // EQ6, EQ10, EQ21 at the mix rate (make_eq_coefs)
@@ -286,6 +275,11 @@ namespace {
 		}                                                                                     \
 	} while (0)
 
+// The effect families (k_fx_families, below): which one carries an effect kind's settings (-1: none), and the stage of
+// a staged chain that runs the kind.
+int family_of(int kind);
+hipError_t fx_launch(const gas_ctx *c, int kind, const gas_group_args &in, uint32_t chain_pos, gas_audio_frame *rows_out);
+
 int group_of(int kind, const int32_t *fx, uint32_t n_fx) {
 	if (kind == GAS_KIND_3D_MIX) {
 		return n_fx == 0 ? G_3D_MIX : -1;
@@ -315,7 +309,7 @@ int group_of(int kind, const int32_t *fx, uint32_t n_fx) {
 	// reflection ring and one HRTF history per playback
 	int n_er = 0, n_hrtf = 0;
 	for (uint32_t j = 0; j < n_fx; j++) {
-		if ((fx[j] < GAS_FX_HIGHSHELF || fx[j] > GAS_FX_AMPLIFY) && (fx[j] < GAS_FX_DISTORTION || fx[j] > GAS_FX_REVERB) && (fx[j] < GAS_FX_EQ6 || fx[j] > GAS_FX_EQ21) && (fx[j] < GAS_FX_CHORUS || fx[j] > GAS_FX_FILTER)) {
+		if (fx[j] != GAS_FX_HIGHSHELF && fx[j] != GAS_FX_EARLY_REFLECTIONS && fx[j] != GAS_FX_HRTF && family_of(fx[j]) < 0) {
 			return -1;
 		}
 		n_er += fx[j] == GAS_FX_EARLY_REFLECTIONS;
@@ -445,7 +439,7 @@ gas_line_geo make_line_geo(float mix_rate) {
 	return g;
 }
 
-inline int line_pool_of(int kind) { // 0 delay, 1 reverb, -1 no line
+constexpr int line_pool_of(int kind) { // 0 delay, 1 reverb, -1 no line
 	return kind == GAS_FX_DELAY ? 0 : (kind == GAS_FX_REVERB ? 1 : -1);
 }
 
@@ -491,7 +485,7 @@ gas_eq_coefs make_eq_coefs(int kind, float mix_rate) {
 	return q;
 }
 
-inline bool is_eq(int kind) {
+constexpr bool is_eq(int kind) {
 	return kind >= GAS_FX_EQ6 && kind <= GAS_FX_EQ21;
 }
 
@@ -499,11 +493,11 @@ gas_fx_eq_settings fx_eq_settings_defaults() {
 	return gas_fx_eq_settings{}; // 0 dB everywhere
 }
 
-inline int mod_pool_of(int kind) { // 0 chorus line, 1 phaser bank, -1 neither
+constexpr int mod_pool_of(int kind) { // 0 chorus line, 1 phaser bank, -1 neither
 	return kind == GAS_FX_CHORUS ? 0 : (kind == GAS_FX_PHASER ? 1 : -1);
 }
 
-inline bool is_stereo(int kind) { // k_fx_stereo.hip's kinds
+constexpr bool is_stereo(int kind) { // k_fx_stereo.hip's kinds
 	return kind >= GAS_FX_PANNER && kind <= GAS_FX_LIMITER;
 }
 
@@ -950,24 +944,12 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 						gas_audio_frame *outb = c->d_chain[j & 1];
 						if (kind == GAS_FX_HIGHSHELF) {
 							e = gas_launch_biquad_mix(c->stream, GAS_MODE_FX_HIGHSHELF, in, c->st, F, (uint32_t)j, 1, c->cfg.mix_rate, parts, 0, c->partial_rows, reinterpret_cast<float *>(outb));
-						} else if (kind >= GAS_FX_LOWPASS && kind <= GAS_FX_AMPLIFY) { // the engine's other one-biquad filters and the amplifier: same kernel, settings by chain position
-							e = gas_launch_biquad_mix(c->stream, kind == GAS_FX_AMPLIFY ? GAS_MODE_FX_AMPLIFY : GAS_MODE_FX_FILTER, in, c->st, F, (uint32_t)j, 1, c->cfg.mix_rate, parts, 0, c->partial_rows, reinterpret_cast<float *>(outb), gas_bus_args(), kind);
 						} else if (kind == GAS_FX_EARLY_REFLECTIONS) {
 							e = gas_launch_er_only(c->stream, in, c->st, F, c->cfg.er_ring_frames, parts, 0, c->partial_rows, outb);
-						} else if (kind == GAS_FX_DISTORTION || kind == GAS_FX_COMPRESSOR) { // k_fx_dyn.hip, settings and state by chain position
-							e = gas_launch_fx_dyn(c->stream, kind, in, c->st, F, (uint32_t)j, c->cfg.mix_rate, outb);
-						} else if (kind == GAS_FX_DELAY || kind == GAS_FX_REVERB) { // k_fx_line.hip, state in the slot's line of chain position j
-							e = gas_launch_fx_line(c->stream, kind, in, c->st, c->line_geo, F, (uint32_t)j, c->cfg.mix_rate, outb);
-						} else if (is_eq(kind)) { // k_fx_eq.hip, state in the slot's bank of chain position j
-							e = gas_launch_fx_eq(c->stream, kind, in, c->st, c->eq_coefs[kind - GAS_FX_EQ6], F, (uint32_t)j, outb);
-						} else if (kind == GAS_FX_FILTER) { // k_fx_filter.hip, state in the slot's bank of chain position j
-							e = gas_launch_fx_filter(c->stream, in, c->st, F, (uint32_t)j, c->cfg.mix_rate, outb);
-						} else if (mod_pool_of(kind) >= 0) { // k_fx_mod.hip, state in the slot's chorus line / phaser bank of chain position j
-							e = gas_launch_fx_mod(c->stream, kind, in, c->st, F, (uint32_t)j, c->cfg.mix_rate, outb);
-						} else if (is_stereo(kind)) { // k_fx_stereo.hip, settings by chain position; a stereo enhance's state in the slot's ring of chain position j
-							e = gas_launch_fx_stereo(c->stream, kind, in, c->st, F, (uint32_t)j, c->cfg.mix_rate, outb);
-						} else {
+						} else if (kind == GAS_FX_HRTF) {
 							e = gas_launch_hrtf_rows(c->stream, (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) != 0, in, c->st, c->tab, c->d_tw, F, outb, blend_on(c), fade_on(c));
+						} else { // a family's kind: settings (and state, or the slot's pool entry) of chain position j
+							e = fx_launch(c, kind, in, (uint32_t)j, outb);
 						}
 						in.src = outb; // dense rows from here on
 						in.rows = nullptr;
@@ -1208,38 +1190,8 @@ int flush_pending_params(gas_ctx *c) {
 	return GAS_OK;
 }
 
-// gas_fx_settings_publish's rows -> the slot-indexed device table.  Control-rate data: one 64-byte copy per changed slot
-// out of a pinned staging array, no kernel.
-int flush_fx_settings(gas_ctx *c) {
-	uint32_t m = 0;
-	{
-		std::lock_guard<std::mutex> lk(c->params_mu);
-		m = (uint32_t)c->fx_dirty_list.size();
-		if (m == 0) {
-			return GAS_OK;
-		}
-		if (!c->h_fx_upload) {
-			if (hipHostMalloc(&c->h_fx_upload, sizeof(gas_fx_settings) * c->cfg.max_sources, hipHostMallocDefault) != hipSuccess) {
-				return GAS_ERR_OUT_OF_MEMORY;
-			}
-		}
-		for (uint32_t i = 0; i < m; i++) {
-			const uint32_t s = c->fx_dirty_list[i];
-			c->h_fx_upload[i] = c->h_fxs[s];
-			c->h_upload_slots[i] = s; // (the parameter upload above has been waited for)
-			c->fx_dirty_flag[s] = 0;
-		}
-		c->fx_dirty_list.clear();
-	}
-	for (uint32_t i = 0; i < m; i++) {
-		GAS_HIP(c, hipMemcpyAsync(c->st.fxs + c->h_upload_slots[i], c->h_fx_upload + i, sizeof(gas_fx_settings), hipMemcpyHostToDevice, c->stream));
-	}
-	GAS_HIP(c, hipStreamSynchronize(c->stream));
-	return GAS_OK;
-}
-
-// gas_hrtf_blend_publish's rows (and the all-zero rows of freed slots) -> the slot-indexed device table, the way
-// flush_fx_settings does it: one 32-byte copy per changed slot out of a pinned staging array, no kernel.
+// gas_hrtf_blend_publish's rows (and the all-zero rows of freed slots) -> the slot-indexed device table.  Control-rate
+// data: one 32-byte copy per changed slot out of a pinned staging array, no kernel.
 int flush_hrtf_blend(gas_ctx *c) {
 	if (!blend_on(c)) {
 		return GAS_OK;
@@ -1271,51 +1223,29 @@ int flush_hrtf_blend(gas_ctx *c) {
 	return GAS_OK;
 }
 
-// gas_fx_dyn_settings_publish's rows -> the slot-indexed device table: one copy of [m settings][m slots], one scatter.
-int flush_fx_dyn_settings(gas_ctx *c) {
-	uint32_t m = 0;
-	{
-		std::lock_guard<std::mutex> lk(c->params_mu);
-		m = (uint32_t)c->dyn_dirty_list.size();
-		if (m == 0) {
-			return GAS_OK;
-		}
-		gas_fx_dyn_settings *hs = reinterpret_cast<gas_fx_dyn_settings *>(c->h_dyn_upload);
-		uint32_t *hslots = reinterpret_cast<uint32_t *>(c->h_dyn_upload + (size_t)m * sizeof(gas_fx_dyn_settings));
-		for (uint32_t i = 0; i < m; i++) {
-			const uint32_t s = c->dyn_dirty_list[i];
-			hs[i] = c->h_dyn[s];
-			hslots[i] = s;
-			c->dyn_dirty_flag[s] = 0;
-		}
-		c->dyn_dirty_list.clear();
-	}
-	const size_t bytes = (size_t)m * (sizeof(gas_fx_dyn_settings) + sizeof(uint32_t));
-	GAS_HIP(c, hipMemcpyAsync(c->d_dyn_upload, c->h_dyn_upload, bytes, hipMemcpyHostToDevice, c->stream));
-	GAS_HIP(c, gas_launch_scatter_dyn(c->stream, c->st.dyn, reinterpret_cast<const gas_fx_dyn_settings *>(c->d_dyn_upload), reinterpret_cast<const uint32_t *>(c->d_dyn_upload + (size_t)m * sizeof(gas_fx_dyn_settings)), m));
-	GAS_HIP(c, hipStreamSynchronize(c->stream)); // the pinned staging buffer is reused by the next flush
-	return GAS_OK;
-}
-
 // ---------------------------------------------------------------------------------------------------------------
-// The pooled effect families: one life cycle -- reserve, hand out, publish, flush, reset, free,
-// release -- over a description of what differs between them.
+// The effect families: one life cycle -- reserve, hand out, publish, flush, reset, free, release --
+// and one stage launch over a description of what differs between them.
 // ---------------------------------------------------------------------------------------------------------------
 
 // A family's members of gas_dev_state.
 struct FxDev {
 	void *settings = nullptr; // [max_sources] settings PODs, by chain position
-	int32_t *of = nullptr; // [GAS_MAX_EFFECTS][max_sources] pool entry of chain position j, -1: none
+	int32_t *of = nullptr; // [GAS_MAX_EFFECTS][max_sources] pool entry of chain position j, -1: none (nullptr: a family without pools)
 	float *pool[2] = { nullptr, nullptr };
 };
 
-template <class S, S *gas_dev_state::*Settings, int32_t *gas_dev_state::*Of, float *gas_dev_state::*Pool0, float *gas_dev_state::*Pool1 = nullptr>
+template <class S, S *gas_dev_state::*Settings, int32_t *gas_dev_state::*Of = nullptr, float *gas_dev_state::*Pool0 = nullptr, float *gas_dev_state::*Pool1 = nullptr>
 struct FxDevOf {
 	static FxDev get(const gas_dev_state &st) {
 		FxDev d;
 		d.settings = st.*Settings;
-		d.of = st.*Of;
-		d.pool[0] = st.*Pool0;
+		if constexpr (Of != nullptr) {
+			d.of = st.*Of;
+		}
+		if constexpr (Pool0 != nullptr) {
+			d.pool[0] = st.*Pool0;
+		}
 		if constexpr (Pool1 != nullptr) {
 			d.pool[1] = st.*Pool1;
 		}
@@ -1323,13 +1253,24 @@ struct FxDevOf {
 	}
 	static void set(gas_dev_state &st, const FxDev &d) {
 		st.*Settings = static_cast<S *>(d.settings);
-		st.*Of = d.of;
-		st.*Pool0 = d.pool[0];
+		if constexpr (Of != nullptr) {
+			st.*Of = d.of;
+		}
+		if constexpr (Pool0 != nullptr) {
+			st.*Pool0 = d.pool[0];
+		}
 		if constexpr (Pool1 != nullptr) {
 			st.*Pool1 = d.pool[1];
 		}
 	}
 };
+using BasicDev = FxDevOf<gas_fx_settings, &gas_dev_state::fxs>;
+using DynDev = FxDevOf<gas_fx_dyn_settings, &gas_dev_state::dyn>;
+using LinesDev = FxDevOf<gas_fx_line_settings, &gas_dev_state::line_settings, &gas_dev_state::line_of, &gas_dev_state::delay_pool, &gas_dev_state::reverb_pool>;
+using EqDev = FxDevOf<gas_fx_eq_settings, &gas_dev_state::eq_settings, &gas_dev_state::eq_of, &gas_dev_state::eq_pool>;
+using FilterDev = FxDevOf<gas_fx_filter_settings, &gas_dev_state::flt_settings, &gas_dev_state::flt_of, &gas_dev_state::flt_pool>;
+using ModDev = FxDevOf<gas_fx_mod_settings, &gas_dev_state::mod_settings, &gas_dev_state::mod_of, &gas_dev_state::chorus_pool, &gas_dev_state::phaser_pool>;
+using StereoDev = FxDevOf<gas_fx_stereo_settings, &gas_dev_state::stereo_settings, &gas_dev_state::stereo_of, &gas_dev_state::enhance_pool>;
 
 template <class S, S (*Defaults)()>
 void fx_defaults_of(void *row) {
@@ -1345,17 +1286,16 @@ struct FxFamilyDesc {
 	const char *name; // gas_ctx_reserve_fx_<name>, for its error strings
 	uint32_t pod_bytes; // the settings POD
 	void (*defaults)(void *row); // the engine's resource defaults
-	bool (*valid)(const void *row); // gas_fx_*_check.h
-	int pools; // 1: a zero record is [entry]; 2: [kind, entry]
+	bool (*valid)(const void *row); // gas_fx_*_check.h (nullptr: every row is taken)
 	int (*pool_of)(int kind); // the pool an effect kind takes its entry from, -1: none
-	bool (*has_kind)(int kind); // the kinds whose settings the POD carries
-	bool resident; // settings, table and staging buffer exist from gas_ctx_create on, the reservation adds the pool
+	bool (*has_kind)(int kind); // the kinds whose settings the POD carries: no kind is in two families (k_fx_kinds)
+	bool resident; // settings, table and staging buffer exist from gas_ctx_create on, a reservation adds the pool
 	FxDev (*get)(const gas_dev_state &st);
 	void (*set)(gas_dev_state &st, const FxDev &d);
 	int (*check)(const gas_ctx *c, const uint32_t *counts); // what a reservation asks of the context (nullptr: nothing)
-	size_t (*entry_floats)(const gas_ctx *c, int pool);
+	size_t (*entry_floats)(const gas_ctx *c, int pool); // nullptr: a family without pools (no reservation, no slot -> entry table on the device)
 	void (*extras)(gas_ctx *c, bool reserved); // what the kernels need besides the pools: set by a reservation, dropped by a release (nullptr: nothing)
-	hipError_t (*zero)(const gas_ctx *c, const uint32_t *records, uint32_t z); // the zeroing launch of a flush
+	hipError_t (*launch)(const gas_ctx *c, int kind, const gas_group_args &in, uint32_t chain_pos, gas_audio_frame *rows_out); // a stage of a staged chain
 };
 
 // [ENGINE] AudioEffectChorus's ring: 1 << bitlength((int)(0.24 sr)) frames; AudioEffectStereoEnhance's: of
@@ -1394,51 +1334,88 @@ int stereo_check(const gas_ctx *c, const uint32_t *counts) {
 	return counts[0] > 0 && (R < c->cfg.frames || R < 4) ? GAS_ERR_INVALID_ARGUMENT : GAS_OK; // two frames of one block would share a ring entry
 }
 
-const FxFamilyDesc k_fx_families[FX_FAMILIES] = {
-	{ "lines", sizeof(gas_fx_line_settings), fx_defaults_of<gas_fx_line_settings, fx_line_settings_defaults>, fx_valid_of<gas_fx_line_settings, gas_fx_line_settings_valid>, 2, line_pool_of,
-			[](int kind) { return line_pool_of(kind) >= 0; }, false,
-			FxDevOf<gas_fx_line_settings, &gas_dev_state::line_settings, &gas_dev_state::line_of, &gas_dev_state::delay_pool, &gas_dev_state::reverb_pool>::get,
-			FxDevOf<gas_fx_line_settings, &gas_dev_state::line_settings, &gas_dev_state::line_of, &gas_dev_state::delay_pool, &gas_dev_state::reverb_pool>::set, lines_check,
+constexpr int no_pool(int) {
+	return -1;
+}
+
+constexpr FxFamilyDesc k_fx_families[FX_FAMILIES] = {
+	// the engine's other one-biquad filters and the amplifier: k_biquad_mix's rows-out form (its partial-mix arguments
+	// are not read then), state in the slot's processor stream of chain position j
+	{ "basic", sizeof(gas_fx_settings), fx_defaults_of<gas_fx_settings, fx_settings_defaults>, nullptr, no_pool,
+			[](int kind) { return kind >= GAS_FX_LOWPASS && kind <= GAS_FX_AMPLIFY; }, true, BasicDev::get, BasicDev::set, nullptr, nullptr, nullptr,
+			[](const gas_ctx *c, int kind, const gas_group_args &in, uint32_t j, gas_audio_frame *out) {
+				return gas_launch_biquad_mix(c->stream, kind == GAS_FX_AMPLIFY ? GAS_MODE_FX_AMPLIFY : GAS_MODE_FX_FILTER, in, c->st, c->cfg.frames, j, 1, c->cfg.mix_rate, c->d_partials, 0, c->partial_rows, reinterpret_cast<float *>(out), gas_bus_args(), kind);
+			} },
+	{ "dyn", sizeof(gas_fx_dyn_settings), fx_defaults_of<gas_fx_dyn_settings, fx_dyn_settings_defaults>, fx_valid_of<gas_fx_dyn_settings, gas_fx_dyn_settings_valid>, no_pool,
+			[](int kind) { return kind == GAS_FX_DISTORTION || kind == GAS_FX_COMPRESSOR; }, true, DynDev::get, DynDev::set, nullptr, nullptr, nullptr,
+			[](const gas_ctx *c, int kind, const gas_group_args &in, uint32_t j, gas_audio_frame *out) { return gas_launch_fx_dyn(c->stream, kind, in, c->st, c->cfg.frames, j, c->cfg.mix_rate, out); } },
+	{ "lines", sizeof(gas_fx_line_settings), fx_defaults_of<gas_fx_line_settings, fx_line_settings_defaults>, fx_valid_of<gas_fx_line_settings, gas_fx_line_settings_valid>, line_pool_of,
+			[](int kind) { return line_pool_of(kind) >= 0; }, false, LinesDev::get, LinesDev::set, lines_check,
 			[](const gas_ctx *c, int pool) { const gas_line_geo g = make_line_geo(c->cfg.mix_rate); return pool == 0 ? g.delay_floats : g.reverb_floats; },
 			[](gas_ctx *c, bool reserved) {
 				if (reserved) {
 					c->line_geo = make_line_geo(c->cfg.mix_rate);
 				}
 			},
-			[](const gas_ctx *c, const uint32_t *r, uint32_t z) { return gas_launch_zero_lines(c->stream, c->st, c->line_geo, r, z); } },
-	{ "eq", sizeof(gas_fx_eq_settings), fx_defaults_of<gas_fx_eq_settings, fx_eq_settings_defaults>, fx_valid_of<gas_fx_eq_settings, gas_fx_eq_settings_valid>, 1,
-			[](int kind) { return is_eq(kind) ? 0 : -1; }, is_eq, false,
-			FxDevOf<gas_fx_eq_settings, &gas_dev_state::eq_settings, &gas_dev_state::eq_of, &gas_dev_state::eq_pool>::get,
-			FxDevOf<gas_fx_eq_settings, &gas_dev_state::eq_settings, &gas_dev_state::eq_of, &gas_dev_state::eq_pool>::set, nullptr,
+			[](const gas_ctx *c, int kind, const gas_group_args &in, uint32_t j, gas_audio_frame *out) { return gas_launch_fx_line(c->stream, kind, in, c->st, c->line_geo, c->cfg.frames, j, c->cfg.mix_rate, out); } },
+	{ "eq", sizeof(gas_fx_eq_settings), fx_defaults_of<gas_fx_eq_settings, fx_eq_settings_defaults>, fx_valid_of<gas_fx_eq_settings, gas_fx_eq_settings_valid>,
+			[](int kind) { return is_eq(kind) ? 0 : -1; }, is_eq, false, EqDev::get, EqDev::set, nullptr,
 			[](const gas_ctx *, int) { return (size_t)GAS_EQ_BANK_FLOATS; },
 			[](gas_ctx *c, bool reserved) {
 				for (int k = 0; k < 3 && reserved; k++) {
 					c->eq_coefs[k] = make_eq_coefs(GAS_FX_EQ6 + k, c->cfg.mix_rate);
 				}
 			},
-			[](const gas_ctx *c, const uint32_t *r, uint32_t z) { return gas_launch_zero_banks(c->stream, c->st, r, z); } },
-	{ "filter", sizeof(gas_fx_filter_settings), fx_defaults_of<gas_fx_filter_settings, gas_fx_filter_settings_defaults>, fx_valid_of<gas_fx_filter_settings, gas_fx_filter_settings_valid>, 1,
-			[](int kind) { return kind == GAS_FX_FILTER ? 0 : -1; }, [](int kind) { return kind == GAS_FX_FILTER; }, false,
-			FxDevOf<gas_fx_filter_settings, &gas_dev_state::flt_settings, &gas_dev_state::flt_of, &gas_dev_state::flt_pool>::get,
-			FxDevOf<gas_fx_filter_settings, &gas_dev_state::flt_settings, &gas_dev_state::flt_of, &gas_dev_state::flt_pool>::set, nullptr,
+			[](const gas_ctx *c, int kind, const gas_group_args &in, uint32_t j, gas_audio_frame *out) { return gas_launch_fx_eq(c->stream, kind, in, c->st, c->eq_coefs[kind - GAS_FX_EQ6], c->cfg.frames, j, out); } },
+	{ "filter", sizeof(gas_fx_filter_settings), fx_defaults_of<gas_fx_filter_settings, gas_fx_filter_settings_defaults>, fx_valid_of<gas_fx_filter_settings, gas_fx_filter_settings_valid>,
+			[](int kind) { return kind == GAS_FX_FILTER ? 0 : -1; }, [](int kind) { return kind == GAS_FX_FILTER; }, false, FilterDev::get, FilterDev::set, nullptr,
 			[](const gas_ctx *, int) { return (size_t)GAS_FILTER_BANK_FLOATS; }, nullptr,
-			[](const gas_ctx *c, const uint32_t *r, uint32_t z) { return gas_launch_zero_filter_banks(c->stream, c->st, r, z); } },
-	{ "mod", sizeof(gas_fx_mod_settings), fx_defaults_of<gas_fx_mod_settings, gas_fx_mod_settings_defaults>, fx_valid_of<gas_fx_mod_settings, gas_fx_mod_settings_valid>, 2, mod_pool_of,
-			[](int kind) { return mod_pool_of(kind) >= 0; }, false,
-			FxDevOf<gas_fx_mod_settings, &gas_dev_state::mod_settings, &gas_dev_state::mod_of, &gas_dev_state::chorus_pool, &gas_dev_state::phaser_pool>::get,
-			FxDevOf<gas_fx_mod_settings, &gas_dev_state::mod_settings, &gas_dev_state::mod_of, &gas_dev_state::chorus_pool, &gas_dev_state::phaser_pool>::set, mod_check,
+			[](const gas_ctx *c, int, const gas_group_args &in, uint32_t j, gas_audio_frame *out) { return gas_launch_fx_filter(c->stream, in, c->st, c->cfg.frames, j, c->cfg.mix_rate, out); } },
+	{ "mod", sizeof(gas_fx_mod_settings), fx_defaults_of<gas_fx_mod_settings, gas_fx_mod_settings_defaults>, fx_valid_of<gas_fx_mod_settings, gas_fx_mod_settings_valid>, mod_pool_of,
+			[](int kind) { return mod_pool_of(kind) >= 0; }, false, ModDev::get, ModDev::set, mod_check,
 			[](const gas_ctx *c, int pool) { return pool == 0 ? GAS_CHORUS_HEADER + 2 * (size_t)chorus_ring_frames(c) : (size_t)GAS_PHASER_BANK_FLOATS; },
 			[](gas_ctx *c, bool reserved) { c->st.chorus_mask = reserved ? chorus_ring_frames(c) - 1 : 0; },
-			[](const gas_ctx *c, const uint32_t *r, uint32_t z) { return gas_launch_zero_mod(c->stream, c->st, r, z); } },
+			[](const gas_ctx *c, int kind, const gas_group_args &in, uint32_t j, gas_audio_frame *out) { return gas_launch_fx_mod(c->stream, kind, in, c->st, c->cfg.frames, j, c->cfg.mix_rate, out); } },
 	// panner and limiter need no reservation: only the stereo enhance takes a ring
-	{ "stereo", sizeof(gas_fx_stereo_settings), fx_defaults_of<gas_fx_stereo_settings, gas_fx_stereo_settings_defaults>, fx_valid_of<gas_fx_stereo_settings, gas_fx_stereo_settings_valid>, 1,
-			[](int kind) { return kind == GAS_FX_STEREO_ENHANCE ? 0 : -1; }, is_stereo, true,
-			FxDevOf<gas_fx_stereo_settings, &gas_dev_state::stereo_settings, &gas_dev_state::stereo_of, &gas_dev_state::enhance_pool>::get,
-			FxDevOf<gas_fx_stereo_settings, &gas_dev_state::stereo_settings, &gas_dev_state::stereo_of, &gas_dev_state::enhance_pool>::set, stereo_check,
+	{ "stereo", sizeof(gas_fx_stereo_settings), fx_defaults_of<gas_fx_stereo_settings, gas_fx_stereo_settings_defaults>, fx_valid_of<gas_fx_stereo_settings, gas_fx_stereo_settings_valid>,
+			[](int kind) { return kind == GAS_FX_STEREO_ENHANCE ? 0 : -1; }, is_stereo, true, StereoDev::get, StereoDev::set, stereo_check,
 			[](const gas_ctx *c, int) { return GAS_ENHANCE_HEADER + (size_t)enhance_ring_frames(c); },
 			[](gas_ctx *c, bool reserved) { c->st.enhance_mask = reserved ? enhance_ring_frames(c) - 1 : 0; },
-			[](const gas_ctx *c, const uint32_t *r, uint32_t z) { return gas_launch_zero_rings(c->stream, c->st, r, z); } },
+			[](const gas_ctx *c, int kind, const gas_group_args &in, uint32_t j, gas_audio_frame *out) { return gas_launch_fx_stereo(c->stream, kind, in, c->st, c->cfg.frames, j, c->cfg.mix_rate, out); } },
 };
+
+// kind -> family, filled once from has_kind, so that neither group_of nor a callback's stage loop walks the table
+struct FxKinds {
+	int8_t family[256];
+	bool unique;
+};
+
+constexpr FxKinds fx_kinds() {
+	FxKinds m{};
+	m.unique = true;
+	for (int kind = 0; kind < 256; kind++) {
+		m.family[kind] = -1;
+		for (int f = 0; f < FX_FAMILIES; f++) {
+			if (k_fx_families[f].has_kind(kind)) {
+				m.unique = m.unique && m.family[kind] < 0;
+				m.family[kind] = (int8_t)f;
+			}
+		}
+	}
+	return m;
+}
+
+constexpr FxKinds k_fx_kinds = fx_kinds();
+static_assert(k_fx_kinds.unique, "an effect kind belongs to at most one family");
+
+int family_of(int kind) {
+	return kind >= 0 && kind < 256 ? k_fx_kinds.family[kind] : -1;
+}
+
+hipError_t fx_launch(const gas_ctx *c, int kind, const gas_group_args &in, uint32_t chain_pos, gas_audio_frame *rows_out) {
+	const int f = family_of(kind);
+	return f < 0 ? hipErrorInvalidValue : k_fx_families[f].launch(c, kind, in, chain_pos, rows_out);
+}
 
 std::array<int32_t, GAS_MAX_EFFECTS> fx_no_entries() {
 	std::array<int32_t, GAS_MAX_EFFECTS> none;
@@ -1446,7 +1423,8 @@ std::array<int32_t, GAS_MAX_EFFECTS> fx_no_entries() {
 	return none;
 }
 
-// What a flush uploads: one copy of [m settings][m {slot, entry[4]}][z zero records], one scatter, one zeroing launch.
+// What a flush uploads: one copy of [m settings][m {slot, entry[4]}][z {pool, entry} zero records], one scatter, one
+// zeroing launch.
 int fx_flush(gas_ctx *c, int f) {
 	FxFamily &p = c->fx[f];
 	const FxFamilyDesc &d = k_fx_families[f];
@@ -1454,12 +1432,11 @@ int fx_flush(gas_ctx *c, int f) {
 		return GAS_OK;
 	}
 	const size_t pod = d.pod_bytes;
-	const uint32_t w = (uint32_t)d.pools; // words of a zero record
 	uint32_t m = 0, z = 0;
 	{
 		std::lock_guard<std::mutex> lk(c->params_mu);
 		m = (uint32_t)p.dirty_list.size();
-		z = (uint32_t)p.zero_list.size() / w;
+		z = (uint32_t)p.zero_list.size() / 2;
 		if (m == 0 && z == 0) {
 			return GAS_OK;
 		}
@@ -1476,19 +1453,21 @@ int fx_flush(gas_ctx *c, int f) {
 			}
 			p.dirty_flag[s] = 0;
 		}
-		std::memcpy(hsi + (size_t)m * (1 + GAS_MAX_EFFECTS), p.zero_list.data(), (size_t)z * w * sizeof(uint32_t));
+		std::memcpy(hsi + (size_t)m * (1 + GAS_MAX_EFFECTS), p.zero_list.data(), (size_t)z * 2 * sizeof(uint32_t));
 		for (uint32_t i = 0; i < z; i++) {
-			const uint32_t *r = &p.zero_list[(size_t)w * i];
-			p.zero_pending[w == 2 ? d.pool_of((int)r[0]) : 0][r[w - 1]] = 0;
+			p.zero_pending[p.zero_list[2 * i]][p.zero_list[2 * i + 1]] = 0;
 		}
 		p.dirty_list.clear();
 		p.zero_list.clear();
 	}
 	const size_t zoff = (size_t)m * (pod + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t));
 	const FxDev dev = d.get(c->st);
-	GAS_HIP(c, hipMemcpyAsync(p.d_upload, p.h_upload, zoff + (size_t)z * w * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	GAS_HIP(c, hipMemcpyAsync(p.d_upload, p.h_upload, zoff + (size_t)z * 2 * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
 	GAS_HIP(c, gas_launch_scatter_fx(c->stream, dev.settings, dev.of, c->st.dyn_stride, d.pod_bytes, p.d_upload, reinterpret_cast<const uint32_t *>(p.d_upload + (size_t)m * pod), m));
-	GAS_HIP(c, d.zero(c, reinterpret_cast<const uint32_t *>(p.d_upload + zoff), z));
+	if (z > 0) {
+		const size_t floats[2] = { d.entry_floats(c, 0), d.entry_floats(c, 1) };
+		GAS_HIP(c, gas_launch_zero_entries(c->stream, dev.pool, floats, reinterpret_cast<const uint32_t *>(p.d_upload + zoff), z));
+	}
 	GAS_HIP(c, hipStreamSynchronize(c->stream)); // the pinned staging buffer is reused by the next flush
 	return GAS_OK;
 }
@@ -1504,9 +1483,7 @@ void fx_queue_zero(gas_ctx *c, int f, uint32_t s, uint32_t sig) {
 		const int32_t idx = p.h_of[s][j];
 		if (pool >= 0 && idx >= 0 && !p.zero_pending[pool][idx]) {
 			p.zero_pending[pool][idx] = 1;
-			if (d.pools == 2) {
-				p.zero_list.push_back((uint32_t)kind);
-			}
+			p.zero_list.push_back((uint32_t)pool);
 			p.zero_list.push_back((uint32_t)idx);
 		}
 	}
@@ -1556,12 +1533,13 @@ hipError_t fx_alloc_upload(gas_ctx *c, int f, size_t entries) {
 	(void)hipHostFree(p.h_upload);
 	p.d_upload = p.h_upload = nullptr;
 	// [<= N settings rows][<= N {slot, entry[4]}][<= every entry once] (mark_dirty / fx_queue_zero)
-	const size_t bytes = (size_t)c->cfg.max_sources * (d.pod_bytes + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t)) + entries * d.pools * sizeof(uint32_t);
+	const size_t bytes = (size_t)c->cfg.max_sources * (d.pod_bytes + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t)) + entries * 2 * sizeof(uint32_t);
 	const hipError_t e = hipMalloc(&p.d_upload, bytes);
 	return e != hipSuccess ? e : hipHostMalloc(&p.h_upload, bytes, hipHostMallocDefault);
 }
 
-// The settings table at the resource defaults (`rows`: the same for the host mirror) and the slot -> entry table at -1.
+// The settings table at the resource defaults (`rows`: the same for the host mirror) and, for a family with pools, the
+// slot -> entry table at -1.
 hipError_t fx_alloc_tables(gas_ctx *c, int f, FxDev &dev, std::vector<unsigned char> &rows) {
 	const FxFamilyDesc &d = k_fx_families[f];
 	const size_t N = c->cfg.max_sources, pod = d.pod_bytes;
@@ -1570,8 +1548,11 @@ hipError_t fx_alloc_tables(gas_ctx *c, int f, FxDev &dev, std::vector<unsigned c
 	for (size_t s = 1; s < N; s++) {
 		std::memcpy(rows.data() + s * pod, rows.data(), pod);
 	}
-	hipError_t e = hipMalloc(&dev.of, sizeof(int32_t) * GAS_MAX_EFFECTS * N);
-	e = e != hipSuccess ? e : hipMemsetAsync(dev.of, 0xff, sizeof(int32_t) * GAS_MAX_EFFECTS * N, c->stream);
+	hipError_t e = hipSuccess;
+	if (d.entry_floats) {
+		e = hipMalloc(&dev.of, sizeof(int32_t) * GAS_MAX_EFFECTS * N);
+		e = e != hipSuccess ? e : hipMemsetAsync(dev.of, 0xff, sizeof(int32_t) * GAS_MAX_EFFECTS * N, c->stream);
+	}
 	e = e != hipSuccess ? e : hipMalloc(&dev.settings, N * pod);
 	return e != hipSuccess ? e : hipMemcpy(dev.settings, rows.data(), N * pod, hipMemcpyHostToDevice);
 }
@@ -1622,7 +1603,7 @@ int fx_publish(gas_ctx *c, int f, const uint32_t *slots, const void *settings, u
 		if (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used) {
 			return GAS_ERR_BAD_SLOT;
 		}
-		if (!d.valid(rows + (size_t)i * pod)) {
+		if (d.valid && !d.valid(rows + (size_t)i * pod)) {
 			return GAS_ERR_INVALID_ARGUMENT;
 		}
 	}
@@ -1650,6 +1631,11 @@ int fx_reserve(gas_ctx *c, int f, uint32_t count0, uint32_t count1) {
 	const int rc = d.check ? d.check(c, counts) : GAS_OK;
 	if (rc != GAS_OK) {
 		return rc;
+	}
+	for (int pl = 0; pl < 2; pl++) { // k_zero_entries writes float4: hipMalloc's base and every entry behind it 16-byte aligned
+		if (counts[pl] > 0 && d.entry_floats(c, pl) % 4 != 0) {
+			return GAS_ERR_INVALID_ARGUMENT; // (no mix rate the checks above accept gets here)
+		}
 	}
 	std::lock_guard<std::mutex> alloc_lk(c->alloc_mu);
 	for (int pl = 0; pl < 2; pl++) {
@@ -1746,10 +1732,9 @@ int flush_params(gas_ctx *c) {
 		GAS_HIP(c, gas_launch_scatter_params(c->stream, c->st.params, c->d_upload, c->d_upload_slots, m));
 		GAS_HIP(c, hipStreamSynchronize(c->stream));
 	}
-	int rc = flush_fx_settings(c);
+	int rc = fx_flush(c, FX_BASIC); // (the blend rows keep their place between the first two families)
 	rc = rc != GAS_OK ? rc : flush_hrtf_blend(c);
-	rc = rc != GAS_OK ? rc : flush_fx_dyn_settings(c);
-	for (int f = 0; f < FX_FAMILIES && rc == GAS_OK; f++) {
+	for (int f = FX_BASIC + 1; f < FX_FAMILIES && rc == GAS_OK; f++) {
 		rc = fx_flush(c, f);
 	}
 	return rc;
@@ -2021,16 +2006,11 @@ void gas_ctx_destroy(gas_ctx *c) {
 	(void)hipFree(c->d_tw);
 	(void)hipFree(c->d_upload);
 	(void)hipFree(c->d_upload_slots);
-	(void)hipFree(c->st.fxs);
-	(void)hipHostFree(c->h_fx_upload);
 	(void)hipFree(c->st.hrtf_blend);
 	(void)hipFree(c->st.hrtf_prev_blend);
 	(void)hipHostFree(c->h_blend_upload);
-	(void)hipFree(c->st.dyn);
 	(void)hipFree(c->st.dist_h);
 	(void)hipFree(c->st.comp_rundb);
-	(void)hipFree(c->d_dyn_upload);
-	(void)hipHostFree(c->h_dyn_upload);
 	for (int f = 0; f < FX_FAMILIES; f++) {
 		fx_release(c, f, true);
 	}
@@ -2138,7 +2118,6 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 		}
 		GAS_HIP(c, hipMalloc(&c->st.params, sizeof(gas_params) * N));
 		GAS_HIP(c, hipMemsetAsync(c->st.params, 0, sizeof(gas_params) * N, c->stream));
-		GAS_HIP(c, hipMalloc(&c->st.fxs, sizeof(gas_fx_settings) * N));
 		if ((cfg->flags & GAS_FLAG_HRTF_INTERPOLATE) != 0) { // every slot starts with the all-zero row: no blend
 			GAS_HIP(c, hipMalloc(&c->st.hrtf_blend, sizeof(gas_hrtf_blend) * N));
 			GAS_HIP(c, hipMemsetAsync(c->st.hrtf_blend, 0, sizeof(gas_hrtf_blend) * N, c->stream));
@@ -2148,14 +2127,11 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 			GAS_HIP(c, hipMemsetAsync(c->st.hrtf_prev_blend, 0, sizeof(gas_hrtf_blend) * N, c->stream));
 		}
 		c->st.dyn_stride = (uint32_t)N;
-		GAS_HIP(c, hipMalloc(&c->st.dyn, sizeof(gas_fx_dyn_settings) * N));
 		GAS_HIP(c, hipMalloc(&c->st.dist_h, sizeof(float) * GAS_MAX_EFFECTS * 2 * N));
 		GAS_HIP(c, hipMemsetAsync(c->st.dist_h, 0, sizeof(float) * GAS_MAX_EFFECTS * 2 * N, c->stream));
 		GAS_HIP(c, hipMalloc(&c->st.comp_rundb, sizeof(float) * GAS_MAX_EFFECTS * N));
 		GAS_HIP(c, hipMemsetAsync(c->st.comp_rundb, 0, sizeof(float) * GAS_MAX_EFFECTS * N, c->stream));
-		GAS_HIP(c, hipMalloc(&c->d_dyn_upload, (sizeof(gas_fx_dyn_settings) + sizeof(uint32_t)) * N));
-		GAS_HIP(c, hipHostMalloc(&c->h_dyn_upload, (sizeof(gas_fx_dyn_settings) + sizeof(uint32_t)) * N, hipHostMallocDefault));
-		for (int f = 0; f < FX_FAMILIES; f++) { // the families that need no reservation for their settings
+		for (int f = 0; f < FX_FAMILIES; f++) { // the families that need no reservation for their settings: every slot starts from the engine's resource defaults
 			if (k_fx_families[f].resident) {
 				FxDev dev;
 				const hipError_t e = fx_alloc_tables(c, f, dev, c->fx[f].h_settings);
@@ -2221,23 +2197,9 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 	c->h_cursors.assign(N, gas_cursor{});
 	c->stamp.assign(N, 0);
 	c->dirty_flag.assign(N, 0);
-	c->h_fxs.assign(N, fx_settings_defaults());
-	c->fx_dirty_flag.assign(N, 0);
 	if (blend_on(c)) {
 		c->h_blend.assign(N, gas_hrtf_blend{});
 		c->blend_dirty_flag.assign(N, 0);
-	}
-	c->h_dyn.assign(N, fx_dyn_settings_defaults());
-	c->dyn_dirty_flag.assign(N, 0);
-	{ // every slot starts from the engine's resource defaults
-		hipError_t e = hipMemcpy(c->st.fxs, c->h_fxs.data(), sizeof(gas_fx_settings) * N, hipMemcpyHostToDevice);
-		if (e == hipSuccess) {
-			e = hipMemcpy(c->st.dyn, c->h_dyn.data(), sizeof(gas_fx_dyn_settings) * N, hipMemcpyHostToDevice);
-		}
-		if (e != hipSuccess) {
-			gas_ctx_destroy(c);
-			return GAS_ERR_DEVICE;
-		}
 	}
 	c->free_list.reserve(N);
 	for (size_t s = N; s-- > 0;) {
@@ -2345,7 +2307,7 @@ int gas_source_alloc(gas_ctx *c, int kind, const int32_t *effects, uint32_t n_ef
 	if ((g == G_FX_ER || g == G_FX_ER_HRTF || (g == G_FX_GENERIC && chain_has(sig, GAS_FX_EARLY_REFLECTIONS))) && c->cfg.er_ring_frames == 0) {
 		return GAS_ERR_UNSUPPORTED_CHAIN;
 	}
-	uint32_t need[FX_FAMILIES][2] = {}; // pool entries of the chain, per pooled family and pool
+	uint32_t need[FX_FAMILIES][2] = {}; // pool entries of the chain, per family and pool
 	bool in_family[FX_FAMILIES] = {}; // the chain has a kind whose settings the family carries
 	for (int f = 0; f < FX_FAMILIES; f++) {
 		for (uint32_t j = 0; j < n_effects; j++) {
@@ -2381,24 +2343,8 @@ int gas_source_alloc(gas_ctx *c, int kind, const int32_t *effects, uint32_t n_ef
 	si.chain_sig = sig;
 	c->slots[s] = si;
 	*out_slot = s;
-	for (uint32_t j = 0; j < n_effects; j++) {
-		if (effects[j] >= GAS_FX_LOWPASS) { // a new playback's effect instances start from the resource defaults (audio_spatializer_effect.cpp:79-88)
-			std::lock_guard<std::mutex> lk(c->params_mu);
-			c->h_fxs[s] = fx_settings_defaults();
-			mark_dirty(c->fx_dirty_flag, c->fx_dirty_list, s);
-			break;
-		}
-	}
-	for (uint32_t j = 0; j < n_effects; j++) {
-		if (effects[j] == GAS_FX_DISTORTION || effects[j] == GAS_FX_COMPRESSOR) { // likewise for gas_fx_dyn_settings
-			std::lock_guard<std::mutex> lk(c->params_mu);
-			c->h_dyn[s] = fx_dyn_settings_defaults();
-			mark_dirty(c->dyn_dirty_flag, c->dyn_dirty_list, s);
-			break;
-		}
-	}
 	for (int f = 0; f < FX_FAMILIES; f++) {
-		if (in_family[f]) {
+		if (in_family[f]) { // a new playback's effect instances start from the resource defaults (audio_spatializer_effect.cpp:79-88)
 			fx_hand_out(c, f, s, effects, n_effects, sig);
 		}
 	}
@@ -2478,21 +2424,7 @@ int gas_params_publish(gas_ctx *c, uint32_t slot, const gas_params *params) {
 }
 
 int gas_fx_settings_publish(gas_ctx *c, const uint32_t *slots, const gas_fx_settings *settings, uint32_t n) {
-	if (!c || (n > 0 && (!slots || !settings))) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	for (uint32_t i = 0; i < n; i++) {
-		if (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used) {
-			return GAS_ERR_BAD_SLOT;
-		}
-	}
-	std::lock_guard<std::mutex> lk(c->params_mu);
-	for (uint32_t i = 0; i < n; i++) {
-		const uint32_t s = slots[i];
-		c->h_fxs[s] = settings[i];
-		mark_dirty(c->fx_dirty_flag, c->fx_dirty_list, s);
-	}
-	return GAS_OK;
+	return fx_publish(c, FX_BASIC, slots, settings, n);
 }
 
 int gas_hrtf_blend_publish(gas_ctx *c, const uint32_t *slots, const gas_hrtf_blend *blends, uint32_t n) {
@@ -2521,24 +2453,7 @@ int gas_hrtf_blend_publish(gas_ctx *c, const uint32_t *slots, const gas_hrtf_ble
 }
 
 int gas_fx_dyn_settings_publish(gas_ctx *c, const uint32_t *slots, const gas_fx_dyn_settings *settings, uint32_t n) {
-	if (!c || (n > 0 && (!slots || !settings))) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	for (uint32_t i = 0; i < n; i++) {
-		if (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used) {
-			return GAS_ERR_BAD_SLOT;
-		}
-		if (!gas_fx_dyn_settings_valid(settings[i])) {
-			return GAS_ERR_INVALID_ARGUMENT;
-		}
-	}
-	std::lock_guard<std::mutex> lk(c->params_mu);
-	for (uint32_t i = 0; i < n; i++) {
-		const uint32_t s = slots[i];
-		c->h_dyn[s] = settings[i];
-		mark_dirty(c->dyn_dirty_flag, c->dyn_dirty_list, s);
-	}
-	return GAS_OK;
+	return fx_publish(c, FX_DYN, slots, settings, n);
 }
 
 int gas_fx_line_settings_publish(gas_ctx *c, const uint32_t *slots, const gas_fx_line_settings *settings, uint32_t n) {
@@ -3214,7 +3129,7 @@ int gas_process_block(gas_ctx *c, const gas_audio_frame *src, const uint32_t *sl
 		bool host_dirty = false;
 		{
 			std::lock_guard<std::mutex> lk(c->params_mu);
-			host_dirty = !c->dirty_list.empty() || !c->fx_dirty_list.empty() || !c->blend_dirty_list.empty();
+			host_dirty = !c->dirty_list.empty() || !c->fx[FX_BASIC].dirty_list.empty() || !c->blend_dirty_list.empty();
 		}
 		const bool keep = mem == GAS_MEM_DEVICE && !slots && n == c->deferred_n && c->pending_free.empty() && c->groups_gen == c->deferred_groups_gen && !host_dirty;
 		if (!keep) {

@@ -19,7 +19,8 @@ static_assert(sizeof(gas_fx_eq_settings) == 336, "gas_fx_eq_settings is [GAS_MAX
 static_assert(sizeof(gas_fx_mod_settings) == 512, "gas_fx_mod_settings is 5 arrays by chain position, 6 by position and voice, 5 by position");
 static_assert(sizeof(gas_fx_stereo_settings) == 128, "gas_fx_stereo_settings is 8 arrays by chain position");
 static_assert(sizeof(gas_fx_filter_settings) == 128, "gas_fx_filter_settings is 5 arrays by chain position and 12 reserved words");
-static_assert(sizeof(gas_fx_line_settings) % 16 == 0 && sizeof(gas_fx_eq_settings) % 16 == 0 && sizeof(gas_fx_mod_settings) % 16 == 0 && sizeof(gas_fx_stereo_settings) % 16 == 0 && sizeof(gas_fx_filter_settings) % 16 == 0, "k_scatter_fx moves a pooled family's settings POD as 16-byte pieces");
+static_assert(sizeof(gas_fx_settings) == 4 * 4 * GAS_MAX_EFFECTS, "gas_fx_settings is 4 arrays by chain position");
+static_assert(sizeof(gas_fx_settings) % 16 == 0 && sizeof(gas_fx_dyn_settings) % 16 == 0 && sizeof(gas_fx_line_settings) % 16 == 0 && sizeof(gas_fx_eq_settings) % 16 == 0 && sizeof(gas_fx_mod_settings) % 16 == 0 && sizeof(gas_fx_stereo_settings) % 16 == 0 && sizeof(gas_fx_filter_settings) % 16 == 0, "k_scatter_fx moves a family's settings POD as 16-byte pieces");
 
 // GAS_FX_EQ6 / _EQ10 / _EQ21 (k_fx_eq.hip): one bank of state per instance, [21 bands][a2, a3, b2, b3]
 // [2 ears] floats (the engine's BandProcess history per band and ear), and the per-band coefficients of one preset at
@@ -43,6 +44,10 @@ struct gas_eq_coefs {
 // GAS_FX_STEREO_ENHANCE (k_fx_stereo.hip).  A ring is GAS_ENHANCE_HEADER floats of state {pos u32, -,
 // -, -}, then enhance_mask + 1 mono frames.
 #define GAS_ENHANCE_HEADER 4
+
+// k_zero_entries (k_misc.hip) writes a pool entry as float4: the entry sizes fixed at compile time are multiples of 4
+// floats (the rings behind the two headers are powers of two, the line sizes multiples of 64: fx_reserve checks those)
+static_assert(GAS_EQ_BANK_FLOATS % 4 == 0 && GAS_FILTER_BANK_FLOATS % 4 == 0 && GAS_CHORUS_HEADER % 4 == 0 && GAS_PHASER_BANK_FLOATS % 4 == 0 && GAS_ENHANCE_HEADER % 4 == 0, "pool entries are zeroed as float4");
 
 // GAS_FX_DELAY / GAS_FX_REVERB line geometry, fixed per context by the mix rate (gas_ctx_reserve_fx_lines).
 // Every line starts with GAS_LINE_HEADER floats of state; offsets below are in floats from the line's start.
@@ -265,33 +270,25 @@ void gas_make_twiddles(float2 *host_tw /* [64][16] */);
 
 hipError_t gas_launch_mix_reduce(hipStream_t stream, const float *partials, uint32_t p_count, uint32_t p_stride, uint32_t channels, uint32_t frames, gas_audio_frame *out);
 // k_fx_dyn.hip: a GAS_FX_DISTORTION / GAS_FX_COMPRESSOR stage of a staged chain (rows in -> dense rows out), settings
-// and state of chain position chain_pos; and the scatter of published gas_fx_dyn_settings rows into the slot table
+// and state of chain position chain_pos
 hipError_t gas_launch_fx_dyn(hipStream_t stream, int kind, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t chain_pos, float mix_rate, gas_audio_frame *rows_out);
-// The pooled effect families below share one settings scatter, k_misc.hip's k_scatter_fx: [n] settings
-// PODs of pod_bytes (a multiple of 16) go to settings_table[slot], [n] {slot, entry[GAS_MAX_EFFECTS]} rows to the
-// [GAS_MAX_EFFECTS][stride] table of_table.  Each family keeps the zeroing of its own pool entries.
+// The effect families share k_misc.hip's settings scatter and zeroing.  k_scatter_fx: [n] settings PODs
+// of pod_bytes (a multiple of 16) go to settings_table[slot], [n] {slot, entry[GAS_MAX_EFFECTS]} rows to the
+// [GAS_MAX_EFFECTS][stride] table of_table (nullptr: a family without pools, the entries are skipped).  k_zero_entries:
+// [z] {pool, entry} records, entry_floats[pool] floats (a multiple of 4) of pools[pool] each; z == 0 launches nothing.
 hipError_t gas_launch_scatter_fx(hipStream_t stream, void *settings_table, int32_t *of_table, uint32_t stride, uint32_t pod_bytes, const void *upload, const uint32_t *slot_idx, uint32_t n);
-// k_fx_line.hip: a GAS_FX_DELAY / GAS_FX_REVERB stage (rows in -> dense rows out) and the zeroing of ([z] {kind, line})
-// lines
+hipError_t gas_launch_zero_entries(hipStream_t stream, float *const pools[2], const size_t entry_floats[2], const uint32_t *records, uint32_t z);
+// k_fx_line.hip: a GAS_FX_DELAY / GAS_FX_REVERB stage (rows in -> dense rows out)
 hipError_t gas_launch_fx_line(hipStream_t stream, int kind, const gas_group_args &g, const gas_dev_state &st, const gas_line_geo &geo, uint32_t frames, uint32_t chain_pos, float mix_rate, gas_audio_frame *rows_out);
-hipError_t gas_launch_zero_lines(hipStream_t stream, const gas_dev_state &st, const gas_line_geo &geo, const uint32_t *kind_line, uint32_t n);
-// k_fx_eq.hip: a GAS_FX_EQ6 / _EQ10 / _EQ21 stage (rows in -> dense rows out) with the preset's coefficients and the
-// zeroing of ([z] bank) banks
+// k_fx_eq.hip: a GAS_FX_EQ6 / _EQ10 / _EQ21 stage (rows in -> dense rows out) with the preset's coefficients
 hipError_t gas_launch_fx_eq(hipStream_t stream, int kind, const gas_group_args &g, const gas_dev_state &st, const gas_eq_coefs &coefs, uint32_t frames, uint32_t chain_pos, gas_audio_frame *rows_out);
-hipError_t gas_launch_zero_banks(hipStream_t stream, const gas_dev_state &st, const uint32_t *banks, uint32_t n);
 int gas_eq_bands(int kind); // 6, 10, 21; 0 for any other kind
-// k_fx_mod.hip: a GAS_FX_CHORUS / GAS_FX_PHASER stage (rows in -> dense rows out) and the zeroing of ([z] {kind, index})
-// chorus lines and phaser banks
+// k_fx_mod.hip: a GAS_FX_CHORUS / GAS_FX_PHASER stage (rows in -> dense rows out)
 hipError_t gas_launch_fx_mod(hipStream_t stream, int kind, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t chain_pos, float mix_rate, gas_audio_frame *rows_out);
-hipError_t gas_launch_zero_mod(hipStream_t stream, const gas_dev_state &st, const uint32_t *kind_idx, uint32_t n);
-// k_fx_stereo.hip: a GAS_FX_PANNER / GAS_FX_STEREO_ENHANCE / GAS_FX_LIMITER stage (rows in -> dense rows out) and the
-// zeroing of [z] rings
+// k_fx_stereo.hip: a GAS_FX_PANNER / GAS_FX_STEREO_ENHANCE / GAS_FX_LIMITER stage (rows in -> dense rows out)
 hipError_t gas_launch_fx_stereo(hipStream_t stream, int kind, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t chain_pos, float mix_rate, gas_audio_frame *rows_out);
-hipError_t gas_launch_zero_rings(hipStream_t stream, const gas_dev_state &st, const uint32_t *rings, uint32_t n);
-// k_fx_filter.hip: a GAS_FX_FILTER stage (rows in -> dense rows out) and the zeroing of ([z] bank) banks
+// k_fx_filter.hip: a GAS_FX_FILTER stage (rows in -> dense rows out)
 hipError_t gas_launch_fx_filter(hipStream_t stream, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t chain_pos, float mix_rate, gas_audio_frame *rows_out);
-hipError_t gas_launch_zero_filter_banks(hipStream_t stream, const gas_dev_state &st, const uint32_t *banks, uint32_t n);
-hipError_t gas_launch_scatter_dyn(hipStream_t stream, gas_fx_dyn_settings *table, const gas_fx_dyn_settings *upload, const uint32_t *slots, uint32_t n);
 hipError_t gas_launch_scatter_params(hipStream_t stream, gas_params *table, const gas_params *upload, const uint32_t *slots, uint32_t n);
 hipError_t gas_launch_calc_spatialization(hipStream_t stream, const gas_spatializer3d_config *cfgs, const uint32_t *cfg_index, const gas_source_pose *poses, const gas_listener *listeners, uint32_t n_listeners, const uint32_t *slots, uint32_t n, gas_params *table, uint8_t *was_further, gas_params *out_params, const gas_area_send *areas = nullptr, const float *listener_area_pos = nullptr, gas_audio_frame *out_reverb = nullptr, gas_hrtf_blend *blend_table = nullptr /* GAS_FLAG_HRTF_INTERPOLATE: the slots' bilinear blend rows are written too */);
 hipError_t gas_launch_sample_sources(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc /* 16.16 step per row for resampled playbacks, or nullptr */);

@@ -280,17 +280,6 @@ __global__ __launch_bounds__(NT) void k_fx_dyn(gas_group_args g, gas_dev_state s
 	}
 }
 
-__global__ void k_scatter_dyn(gas_fx_dyn_settings *__restrict__ table, const gas_fx_dyn_settings *__restrict__ upload, const uint32_t *__restrict__ slots, uint32_t n) {
-	constexpr uint32_t PIECES = sizeof(gas_fx_dyn_settings) / 16; // 12 lanes move one POD as 16-byte pieces
-	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-	const uint32_t e = t / PIECES, part = t % PIECES;
-	if (e < n) {
-		const float4 *s = reinterpret_cast<const float4 *>(upload + e);
-		float4 *d = reinterpret_cast<float4 *>(table + slots[e]);
-		d[part] = s[part];
-	}
-}
-
 } // namespace
 
 hipError_t gas_launch_fx_dyn(hipStream_t stream, int kind, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t chain_pos, float mix_rate, gas_audio_frame *rows_out) {
@@ -308,14 +297,5 @@ hipError_t gas_launch_fx_dyn(hipStream_t stream, int kind, const gas_group_args 
 	} else {
 		return hipErrorInvalidValue;
 	}
-	return hipGetLastError();
-}
-
-hipError_t gas_launch_scatter_dyn(hipStream_t stream, gas_fx_dyn_settings *table, const gas_fx_dyn_settings *upload, const uint32_t *slots, uint32_t n) {
-	if (n == 0) {
-		return hipSuccess;
-	}
-	const uint32_t threads = n * (uint32_t)(sizeof(gas_fx_dyn_settings) / 16);
-	hipLaunchKernelGGL(k_scatter_dyn, dim3((threads + 255) / 256), dim3(256), 0, stream, table, upload, slots, n);
 	return hipGetLastError();
 }

@@ -183,14 +183,6 @@ __global__ __launch_bounds__(NT) void k_fx_eq(gas_group_args g, gas_dev_state st
 	}
 }
 
-__global__ void k_zero_banks(gas_dev_state st, const uint32_t *__restrict__ banks, uint32_t n) {
-	constexpr uint32_t Q = GAS_EQ_BANK_FLOATS / 4; // float4 per bank
-	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-	if (t < n * Q) {
-		reinterpret_cast<float4 *>(st.eq_pool + (size_t)banks[t / Q] * GAS_EQ_BANK_FLOATS)[t % Q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-	}
-}
-
 } // namespace
 
 int gas_eq_bands(int kind) {
@@ -218,14 +210,5 @@ hipError_t gas_launch_fx_eq(hipStream_t stream, int kind, const gas_group_args &
 		default:
 			return hipErrorInvalidValue;
 	}
-	return hipGetLastError();
-}
-
-hipError_t gas_launch_zero_banks(hipStream_t stream, const gas_dev_state &st, const uint32_t *banks, uint32_t n) {
-	if (n == 0) {
-		return hipSuccess;
-	}
-	const uint32_t threads = n * (GAS_EQ_BANK_FLOATS / 4);
-	hipLaunchKernelGGL(k_zero_banks, dim3((threads + 255) / 256), dim3(256), 0, stream, st, banks, n);
 	return hipGetLastError();
 }

@@ -271,14 +271,6 @@ __global__ __launch_bounds__(NT) void k_fx_filter(gas_group_args g, gas_dev_stat
 	}
 }
 
-__global__ void k_zero_filter_banks(gas_dev_state st, const uint32_t *__restrict__ banks, uint32_t n) {
-	constexpr uint32_t Q = GAS_FILTER_BANK_FLOATS / 4; // float4 per bank
-	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-	if (t < n * Q) {
-		reinterpret_cast<float4 *>(st.flt_pool + (size_t)banks[t / Q] * GAS_FILTER_BANK_FLOATS)[t % Q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-	}
-}
-
 } // namespace
 
 hipError_t gas_launch_fx_filter(hipStream_t stream, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t chain_pos, float mix_rate, gas_audio_frame *rows_out) {
@@ -289,14 +281,5 @@ hipError_t gas_launch_fx_filter(hipStream_t stream, const gas_group_args &g, con
 		return hipErrorInvalidValue;
 	}
 	hipLaunchKernelGGL(k_fx_filter, dim3((g.n + S - 1) / S), dim3(NT), 0, stream, g, st, frames, chain_pos, mix_rate, reinterpret_cast<float *>(rows_out));
-	return hipGetLastError();
-}
-
-hipError_t gas_launch_zero_filter_banks(hipStream_t stream, const gas_dev_state &st, const uint32_t *banks, uint32_t n) {
-	if (n == 0) {
-		return hipSuccess;
-	}
-	const uint32_t threads = n * (GAS_FILTER_BANK_FLOATS / 4);
-	hipLaunchKernelGGL(k_zero_filter_banks, dim3((threads + 255) / 256), dim3(256), 0, stream, st, banks, n);
 	return hipGetLastError();
 }

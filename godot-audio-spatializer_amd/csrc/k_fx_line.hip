@@ -535,23 +535,6 @@ __global__ __launch_bounds__(RNT) void k_fx_reverb(gas_group_args g, gas_dev_sta
 	}
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// line zeroing (the settings scatter is k_misc.hip's k_scatter_fx)
-// ---------------------------------------------------------------------------------------------------------------
-__global__ void k_zero_lines(gas_dev_state st, gas_line_geo geo, const uint32_t *__restrict__ kind_line, uint32_t n) {
-	const uint32_t e = blockIdx.x; // line; blockIdx.y = chunk
-	if (e >= n) {
-		return;
-	}
-	const bool delay = kind_line[2 * e] == GAS_FX_DELAY;
-	const size_t floats = delay ? geo.delay_floats : geo.reverb_floats;
-	float4 *p = reinterpret_cast<float4 *>((delay ? st.delay_pool : st.reverb_pool) + (size_t)kind_line[2 * e + 1] * floats);
-	const size_t n4 = floats / 4;
-	for (size_t i = (size_t)blockIdx.y * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.y * blockDim.x) {
-		p[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-	}
-}
-
 } // namespace
 
 hipError_t gas_launch_fx_line(hipStream_t stream, int kind, const gas_group_args &g, const gas_dev_state &st, const gas_line_geo &geo, uint32_t frames, uint32_t chain_pos, float mix_rate, gas_audio_frame *rows_out) {
@@ -569,13 +552,5 @@ hipError_t gas_launch_fx_line(hipStream_t stream, int kind, const gas_group_args
 	} else {
 		return hipErrorInvalidValue;
 	}
-	return hipGetLastError();
-}
-
-hipError_t gas_launch_zero_lines(hipStream_t stream, const gas_dev_state &st, const gas_line_geo &geo, const uint32_t *kind_line, uint32_t n) {
-	if (n == 0) {
-		return hipSuccess;
-	}
-	hipLaunchKernelGGL(k_zero_lines, dim3(n, 16), dim3(256), 0, stream, st, geo, kind_line, n);
 	return hipGetLastError();
 }

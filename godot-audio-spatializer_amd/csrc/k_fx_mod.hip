@@ -407,19 +407,6 @@ __global__ __launch_bounds__(PNT) void k_fx_phaser(gas_group_args g, gas_dev_sta
 	}
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// zeroing of pool entries (the settings scatter is k_misc.hip's k_scatter_fx)
-// ---------------------------------------------------------------------------------------------------------------
-// one workgroup per {kind, index} pair
-__global__ void k_zero_mod(gas_dev_state st, const uint32_t *__restrict__ kind_idx) {
-	const uint32_t kind = kind_idx[2 * blockIdx.x], idx = kind_idx[2 * blockIdx.x + 1];
-	const size_t floats = kind == GAS_FX_CHORUS ? GAS_CHORUS_HEADER + 2 * ((size_t)st.chorus_mask + 1) : GAS_PHASER_BANK_FLOATS;
-	float4 *p = reinterpret_cast<float4 *>((kind == GAS_FX_CHORUS ? st.chorus_pool : st.phaser_pool) + (size_t)idx * floats);
-	for (size_t q = threadIdx.x; q < floats / 4; q += blockDim.x) {
-		p[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-	}
-}
-
 } // namespace
 
 hipError_t gas_launch_fx_mod(hipStream_t stream, int kind, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t chain_pos, float mix_rate, gas_audio_frame *rows_out) {
@@ -437,13 +424,5 @@ hipError_t gas_launch_fx_mod(hipStream_t stream, int kind, const gas_group_args 
 	} else {
 		return hipErrorInvalidValue;
 	}
-	return hipGetLastError();
-}
-
-hipError_t gas_launch_zero_mod(hipStream_t stream, const gas_dev_state &st, const uint32_t *kind_idx, uint32_t n) {
-	if (n == 0) {
-		return hipSuccess;
-	}
-	hipLaunchKernelGGL(k_zero_mod, dim3(n), dim3(256), 0, stream, st, kind_idx);
 	return hipGetLastError();
 }

@@ -210,18 +210,6 @@ __global__ __launch_bounds__(SNT) void k_fx_stereo(gas_group_args g, gas_dev_sta
 	}
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// zeroing of pool entries (the settings scatter is k_misc.hip's k_scatter_fx)
-// ---------------------------------------------------------------------------------------------------------------
-// one workgroup per ring
-__global__ void k_zero_rings(gas_dev_state st, const uint32_t *__restrict__ rings) {
-	const size_t floats = GAS_ENHANCE_HEADER + (size_t)st.enhance_mask + 1;
-	float4 *p = reinterpret_cast<float4 *>(st.enhance_pool + (size_t)rings[blockIdx.x] * floats);
-	for (size_t q = threadIdx.x; q < floats / 4; q += blockDim.x) {
-		p[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-	}
-}
-
 } // namespace
 
 hipError_t gas_launch_fx_stereo(hipStream_t stream, int kind, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t chain_pos, float mix_rate, gas_audio_frame *rows_out) {
@@ -242,13 +230,5 @@ hipError_t gas_launch_fx_stereo(hipStream_t stream, int kind, const gas_group_ar
 	} else {
 		return hipErrorInvalidValue;
 	}
-	return hipGetLastError();
-}
-
-hipError_t gas_launch_zero_rings(hipStream_t stream, const gas_dev_state &st, const uint32_t *rings, uint32_t n) {
-	if (n == 0 || !st.enhance_pool) {
-		return hipSuccess;
-	}
-	hipLaunchKernelGGL(k_zero_rings, dim3(n), dim3(256), 0, stream, st, rings);
 	return hipGetLastError();
 }

@@ -4,7 +4,8 @@
 //                     also the zeroing of :335-343 when there is nothing to add)
 //   k_scatter_params  publish staged SpatializerParameters PODs into the slot-indexed table
 //                     (set_spatializer_parameters, audio_spatializer.cpp:558-564)
-//   k_scatter_fx      the same for a pooled effect family's settings PODs and slot -> pool entry rows
+//   k_scatter_fx      the same for an effect family's settings PODs and slot -> pool entry rows
+//   k_zero_entries    fresh state for the pool entries an effect family's flush names
 //   k_zero_slot       fresh SpatializerPlaybackData for a (re)started playback (audio_spatializer.cpp:69)
 #include "gas_device.h"
 #include "gas_internal.h"
@@ -89,8 +90,9 @@ __global__ void k_scatter_params(gas_params *__restrict__ table, const gas_param
 	}
 }
 
-// A pooled effect family's flush records into its two slot-indexed tables: pieces lanes move record e's settings POD as
-// 16-byte pieces, one more lane writes its GAS_MAX_EFFECTS pool entries ([GAS_MAX_EFFECTS][stride] table).
+// An effect family's flush records into its two slot-indexed tables: pieces lanes move record e's settings POD as
+// 16-byte pieces, one more lane writes its GAS_MAX_EFFECTS pool entries ([GAS_MAX_EFFECTS][stride] table; a family
+// without pools has none: of_table == nullptr).
 __global__ void k_scatter_fx(float4 *__restrict__ settings_table, int32_t *__restrict__ of_table, uint32_t stride, uint32_t pieces, const float4 *__restrict__ upload, const uint32_t *__restrict__ slot_idx, uint32_t n) {
 	const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
 	const uint32_t e = t / (pieces + 1), part = t % (pieces + 1);
@@ -101,10 +103,22 @@ __global__ void k_scatter_fx(float4 *__restrict__ settings_table, int32_t *__res
 	const uint32_t slot = si[0];
 	if (part < pieces) {
 		settings_table[(size_t)slot * pieces + part] = upload[(size_t)e * pieces + part];
-	} else {
+	} else if (of_table) {
 		for (int j = 0; j < GAS_MAX_EFFECTS; j++) {
 			of_table[(size_t)j * stride + slot] = (int32_t)si[1 + j];
 		}
+	}
+}
+
+// Zeroes the pool entries of an effect family's flush: record blockIdx.x = {pool, entry} names entry_floats[pool] floats
+// (a multiple of 4, every entry 16-byte aligned: fx_reserve checks both) of pool0 / pool1, written as float4 by the
+// gridDim.y workgroups of the record.
+__global__ void k_zero_entries(float *__restrict__ pool0, float *__restrict__ pool1, uint32_t floats0, uint32_t floats1, const uint32_t *__restrict__ records) {
+	const uint32_t pool = records[2 * blockIdx.x], entry = records[2 * blockIdx.x + 1];
+	const uint32_t floats = pool == 0 ? floats0 : floats1;
+	float4 *p = reinterpret_cast<float4 *>((pool == 0 ? pool0 : pool1) + (size_t)entry * floats);
+	for (uint32_t i = blockIdx.y * blockDim.x + threadIdx.x; i < floats / 4; i += gridDim.y * blockDim.x) {
+		p[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 	}
 }
 
@@ -538,12 +552,25 @@ hipError_t gas_launch_scatter_fx(hipStream_t stream, void *settings_table, int32
 	if (n == 0) {
 		return hipSuccess;
 	}
-	if (pod_bytes == 0 || pod_bytes % 16 != 0 || !settings_table || !of_table) {
+	if (pod_bytes == 0 || pod_bytes % 16 != 0 || !settings_table) {
 		return hipErrorInvalidValue;
 	}
 	const uint32_t pieces = pod_bytes / 16;
 	const uint32_t threads = n * (pieces + 1);
 	hipLaunchKernelGGL(k_scatter_fx, dim3((threads + 255) / 256), dim3(256), 0, stream, static_cast<float4 *>(settings_table), of_table, stride, pieces, static_cast<const float4 *>(upload), slot_idx, n);
+	return hipGetLastError();
+}
+
+hipError_t gas_launch_zero_entries(hipStream_t stream, float *const pools[2], const size_t entry_floats[2], const uint32_t *records, uint32_t z) {
+	if (z == 0) {
+		return hipSuccess;
+	}
+	const size_t big = entry_floats[0] > entry_floats[1] ? entry_floats[0] : entry_floats[1];
+	if (big == 0 || big > UINT32_MAX || (!pools[0] && !pools[1])) {
+		return hipErrorInvalidValue;
+	}
+	const size_t chunks = (big / 4 + 255) / 256; // workgroups that find a float4 of the larger entry to write
+	hipLaunchKernelGGL(k_zero_entries, dim3(z, (uint32_t)(chunks < 16 ? chunks : 16)), dim3(256), 0, stream, pools[0], pools[1], (uint32_t)entry_floats[0], (uint32_t)entry_floats[1], records);
 	return hipGetLastError();
 }
 

@@ -266,6 +266,10 @@ assert C.sizeof(HrtfBlend) == 32
 
 MEM_HOST = 0
 MEM_DEVICE = 1
+# gas_loop_mode (gas_stream_set_loop)
+LOOP_DISABLED = 0
+LOOP_FORWARD = 1
+LOOP_PINGPONG = 2
 FLAG_PEAKS_DRAINING_ONLY = 1
 FLAG_HRTF_CROSSFADE = 2
 FLAG_DIRECTION_ORDER = 4
@@ -428,6 +432,8 @@ EXPORTS = [
     "gas_stream_get_info",
     "gas_stream_positions",
     "gas_stream_set_resampled",
+    "gas_stream_set_loop",
+    "gas_stream_get_loop",
     "gas_source_bind_stream",
     "gas_process_block_streams",
     "gas_process_block",
@@ -519,6 +525,8 @@ def load_library():
     L.gas_stream_positions.argtypes = [vp, u32, vp]
     L.gas_stream_get_info.argtypes = [vp, u32, C.POINTER(C.c_uint64), C.POINTER(u32), C.POINTER(i32)]
     L.gas_stream_set_resampled.argtypes = [vp, u32, i32]
+    L.gas_stream_set_loop.argtypes = [vp, u32, i32, C.c_uint64, C.c_uint64]
+    L.gas_stream_get_loop.argtypes = [vp, u32, C.POINTER(i32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.gas_source_bind_stream.argtypes = [vp, u32, u32, C.c_uint64]
     L.gas_process_block_streams.argtypes = [vp, vp, u32, u32, vp, vp, vp, i32]
     L.gas_calc_spatialization.argtypes = [vp, vp, u32, vp, vp, vp, u32, vp, u32, vp, i32]
@@ -764,11 +772,27 @@ class SpatializerContext:
     def stream_set_resampled(self, sid, on=True):
         self._check(self.lib.gas_stream_set_resampled(self.h, sid, int(on)), "gas_stream_set_resampled")
 
+    def stream_set_loop(self, sid, mode, begin=0, end=0):
+        """Loop [begin, end) of the stream (end 0 = its length) for playbacks bound from now on; mode is a LOOP_* constant."""
+        self._check(self.lib.gas_stream_set_loop(self.h, int(sid), int(mode), int(begin), int(end)), "gas_stream_set_loop")
+
+    def stream_get_loop(self, sid):
+        """(mode, begin, end) as set; (LOOP_DISABLED, 0, 0) for a stream that plays once."""
+        mode, b, e = C.c_int32(), C.c_uint64(), C.c_uint64()
+        self._check(self.lib.gas_stream_get_loop(self.h, int(sid), C.byref(mode), C.byref(b), C.byref(e)), "gas_stream_get_loop")
+        return mode.value, b.value, e.value
+
     def stream_destroy(self, sid):
         self._check(self.lib.gas_stream_destroy(self.h, sid), "gas_stream_destroy")
 
     def source_bind_stream(self, slot, sid, start_frame=0):
         self._check(self.lib.gas_source_bind_stream(self.h, int(slot), int(sid), int(start_frame)), "gas_source_bind_stream")
+
+    def stream_positions(self, n):
+        """Stream frame each playback of the last process_block_streams list (n entries) takes next."""
+        out = np.zeros(max(n, 1), dtype=np.uint64)
+        self._check(self.lib.gas_stream_positions(self.h, n, _np_ptr(out)), "gas_stream_positions")
+        return out[:n]
 
     def process_block_streams(self, slots):
         s = np.ascontiguousarray(slots, dtype=np.uint32)

@@ -191,6 +191,8 @@ struct gas_ctx {
 		uint64_t frames = 0;
 		uint32_t format = 0, channels = 0;
 		bool resampled = false; // its playbacks are [ENGINE] AudioStreamPlaybackResampled (gas_stream_set_resampled)
+		uint32_t loop_mode = 0; // NEW gas_stream_set_loop: its playbacks repeat [loop_begin, loop_end)
+		uint64_t loop_begin = 0, loop_end = 0;
 	};
 	std::vector<StreamInfo> streams;
 	gas_cursor *d_cursors = nullptr; // [max_sources]
@@ -210,9 +212,13 @@ struct gas_ctx {
 		uint32_t has_frames = 0, draining_marked = 0;
 		uint32_t resampled = 0, inc = 65536; // resampled playbacks: 16.16 step of this callback (from the host-published pitch_scale)
 		uint64_t fp_pos = 0, end_fp = 0; // ... and the engine's mix_offset / the stream's end, 16.16
+		uint32_t looped = 0; // gas_stream_set_loop: never ends; a plain playback counts `pos` up instead of `remaining` down
+		uint64_t pos = 0;
 	};
 	std::vector<StreamRow> stream_rows;
 	bool stream_all_hrtf = false;
+	bool stream_rows_first = getenv("GAS_STREAM_ROWS_FIRST") != nullptr && atoi(getenv("GAS_STREAM_ROWS_FIRST")) != 0; // development aid: plain [HRTF] stream lists sample rows first too (tools/time_stream_loops.py compares the routes)
+	bool stream_any_looped = false;
 	bool stream_params_touched = false; // a parameter publish may have changed pitch_scale: re-validate
 
 	// gas_calc_spatialization staging (physics thread)
@@ -2762,9 +2768,12 @@ int gas_stream_positions(gas_ctx *c, uint32_t n, uint64_t *out_frames) {
 			out_frames[i] = 0;
 		} else if (rows_live) {
 			const gas_ctx::StreamRow &r = c->stream_rows[i];
-			out_frames[i] = r.resampled ? (r.fp_pos >> 16) : cur.frames - r.remaining;
+			out_frames[i] = r.resampled ? (r.fp_pos >> 16) : r.looped ? r.pos : cur.frames - r.remaining;
 		} else {
 			out_frames[i] = cur.resampled ? (cur.fp_pos >> 16) : cur.pos;
+		}
+		if (cur.pcm && cur.loop_mode) { // the stream frame taken next, m(frames consumed)
+			out_frames[i] = gas_loop_map(out_frames[i], cur.loop_begin, cur.loop_len, cur.loop_mode);
 		}
 	}
 	return GAS_OK;
@@ -2786,6 +2795,56 @@ int gas_stream_set_resampled(gas_ctx *c, uint32_t stream, int on) {
 	return GAS_OK;
 }
 
+int gas_stream_set_loop(gas_ctx *c, uint32_t stream, int mode, uint64_t loop_begin, uint64_t loop_end) {
+	if (!c) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (stream >= c->streams.size() || !c->streams[stream].d_pcm) {
+		return GAS_ERR_BAD_SLOT;
+	}
+	gas_ctx::StreamInfo &si = c->streams[stream];
+	for (const gas_cursor &cur : c->h_cursors) {
+		if (cur.pcm == si.d_pcm) {
+			return GAS_ERR_INVALID_ARGUMENT; // the loop is chosen before playbacks are bound
+		}
+	}
+	if (mode == GAS_LOOP_DISABLED) {
+		si.loop_mode = 0;
+		si.loop_begin = si.loop_end = 0;
+		return GAS_OK;
+	}
+	if (mode != GAS_LOOP_FORWARD && mode != GAS_LOOP_PINGPONG) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	const uint64_t end = loop_end == 0 ? si.frames : loop_end;
+	if (loop_begin >= end || end > si.frames || end - loop_begin >= (1ull << 31)) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	si.loop_mode = (uint32_t)mode;
+	si.loop_begin = loop_begin;
+	si.loop_end = end;
+	return GAS_OK;
+}
+
+int gas_stream_get_loop(gas_ctx *c, uint32_t stream, int *out_mode, uint64_t *out_begin, uint64_t *out_end) {
+	if (!c) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (stream >= c->streams.size() || !c->streams[stream].d_pcm) {
+		return GAS_ERR_BAD_SLOT;
+	}
+	if (out_mode) {
+		*out_mode = (int)c->streams[stream].loop_mode;
+	}
+	if (out_begin) {
+		*out_begin = c->streams[stream].loop_begin;
+	}
+	if (out_end) {
+		*out_end = c->streams[stream].loop_end;
+	}
+	return GAS_OK;
+}
+
 int gas_source_bind_stream(gas_ctx *c, uint32_t slot, uint32_t stream, uint64_t start_frame) {
 	if (!c) {
 		return GAS_ERR_INVALID_ARGUMENT;
@@ -2800,6 +2859,12 @@ int gas_source_bind_stream(gas_ctx *c, uint32_t slot, uint32_t stream, uint64_t 
 	cur.pcm = si.d_pcm;
 	cur.frames = si.frames;
 	cur.pos = start_frame < si.frames ? start_frame : si.frames;
+	if (si.loop_mode) { // a position on the unrolled timeline: not clamped
+		cur.pos = start_frame;
+		cur.loop_begin = si.loop_begin;
+		cur.loop_len = (uint32_t)(si.loop_end - si.loop_begin);
+		cur.loop_mode = si.loop_mode;
+	}
 	cur.start = cur.pos;
 	cur.format_channels = (si.format << 8) | si.channels;
 	cur.has_frames = 1;
@@ -2825,7 +2890,7 @@ void stream_rows_sync_back(gas_ctx *c) {
 		gas_cursor &cur = c->h_cursors[c->stream_slots_host[i]];
 		const gas_ctx::StreamRow &r = c->stream_rows[i];
 		if (cur.pcm) {
-			cur.pos = cur.frames - r.remaining;
+			cur.pos = r.looped ? r.pos : cur.frames - r.remaining;
 		}
 		if (r.resampled) {
 			cur.fp_pos = r.fp_pos;
@@ -2906,12 +2971,16 @@ int gas_process_block_streams(gas_ctx *c, const uint32_t *slots, uint32_t n, uin
 		c->stream_rows.resize(n);
 		c->stream_all_hrtf = n > 0;
 		c->stream_any_resampled = false;
+		c->stream_any_looped = false;
 		for (uint32_t i = 0; i < n; i++) {
 			const gas_cursor &cur = c->h_cursors[slots[i]];
 			gas_ctx::StreamRow &r = c->stream_rows[i];
 			r.remaining = cur.pcm && cur.frames > cur.pos ? cur.frames - cur.pos : 0;
 			r.has_frames = cur.pcm ? cur.has_frames : 0;
 			r.resampled = cur.pcm ? cur.resampled : 0;
+			r.looped = cur.pcm && cur.loop_mode ? 1 : 0;
+			r.pos = cur.pos;
+			c->stream_any_looped = c->stream_any_looped || r.looped;
 			r.inc = 65536;
 			if (r.resampled) {
 				// [ENGINE] mix_increment = uint64((stream_rate * rate_scale / mix_rate) * FP_LEN), stream at the mix rate
@@ -2948,7 +3017,9 @@ int gas_process_block_streams(gas_ctx *c, const uint32_t *slots, uint32_t n, uin
 		gas_ctx::StreamRow &r = c->stream_rows[i];
 		if (r.has_frames && r.resampled) { // same arithmetic as k_sample_sources' resampled branch
 			uint64_t mixed = F;
-			if (r.fp_pos >= r.end_fp) {
+			if (r.looped) {
+				// never runs out
+			} else if (r.fp_pos >= r.end_fp) {
 				mixed = 0;
 			} else if (r.inc > 0) {
 				const uint64_t need = (r.end_fp - r.fp_pos + r.inc - 1) / r.inc;
@@ -2958,6 +3029,8 @@ int gas_process_block_streams(gas_ctx *c, const uint32_t *slots, uint32_t n, uin
 			if (mixed != F) {
 				r.has_frames = 0;
 			}
+		} else if (r.has_frames && r.looped) {
+			r.pos += F;
 		} else if (r.has_frames) {
 			const uint32_t mixed = r.remaining < F ? (uint32_t)r.remaining : F;
 			r.remaining -= mixed;
@@ -2983,7 +3056,9 @@ int gas_process_block_streams(gas_ctx *c, const uint32_t *slots, uint32_t n, uin
 	// rows for this callback live in the library's staging buffer (not needed when k_hrtf_ols samples the
 	// streams itself: every playback a plain [HRTF] chain)
 	// (GAS_FLAG_HRTF_BLEND_FADE: the stream-sampling form has no registers left for the fade, DESIGN.md 3.4 -- rows first)
-	const bool all_hrtf = c->stream_all_hrtf && !c->stream_any_resampled && !fade_on(c); // the fused prologue samples plain playbacks only
+	// (gas_stream_set_loop: the cross-fade form has no registers left for the looped branch either, DESIGN.md 3.4 -- rows first)
+	const bool loops_fused = !c->stream_any_looped || (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) == 0;
+	const bool all_hrtf = c->stream_all_hrtf && !c->stream_any_resampled && !fade_on(c) && loops_fused && !c->stream_rows_first; // the fused prologue samples plain playbacks only
 	if (!all_hrtf) {
 		const size_t need = (size_t)n * F;
 		if (need > c->d_src_frames) {

@@ -417,6 +417,7 @@ struct SrcMeta {
 	const void *pcm;
 	uint64_t len, pos, start;
 	uint32_t fc, hf, mixed;
+	uint32_t lmode; // NEW gas_stream_set_loop (0: none); begin and length are read where the window's phase is taken (load_window)
 };
 
 // Metadata of a wave's sources lives one-source-per-lane in VGPRs: the dependent loads
@@ -430,13 +431,21 @@ struct LaneMeta {
 	gas_cursor cur;
 };
 
+// The cursor as LaneMeta keeps it: the loop mode rides in has_frames' upper bits, so looped streams cost the un-looped
+// path no lane register; loop_begin / loop_len are read in load_window's looped branch from a wave-uniform address.
+__device__ __forceinline__ gas_cursor lane_cursor(const gas_cursor *__restrict__ cursors, uint32_t slot) {
+	gas_cursor c = cursors[slot];
+	c.has_frames = (c.has_frames ? 1u : 0u) | (c.loop_mode << 8);
+	return c;
+}
+
 __device__ __forceinline__ uint64_t readlane64(uint64_t v, int i) {
 	const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, i);
 	const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), i);
 	return ((uint64_t)hi << 32) | lo;
 }
 
-template <bool SRC_PCM>
+template <bool SRC_PCM, bool LOOPS = true>
 __device__ __forceinline__ SrcMeta bcast_meta(const LaneMeta &lm, uint32_t i, uint32_t F) {
 	SrcMeta m{};
 	m.slot = (uint32_t)__builtin_amdgcn_readlane((int)lm.slot, (int)i);
@@ -452,9 +461,13 @@ __device__ __forceinline__ SrcMeta bcast_meta(const LaneMeta &lm, uint32_t i, ui
 		m.start = readlane64(lm.cur.start, (int)i);
 		m.fc = (uint32_t)__builtin_amdgcn_readlane((int)lm.cur.format_channels, (int)i);
 		m.hf = (uint32_t)__builtin_amdgcn_readlane((int)lm.cur.has_frames, (int)i);
-		m.hf = (m.hf && m.pcm) ? 1u : 0u;
+		m.lmode = LOOPS ? m.hf >> 8 : 0; // forms without the looped branch are never launched over looped cursors (and keep the plain cursor)
+		m.hf = ((LOOPS ? m.hf & 0xffu : m.hf) && m.pcm) ? 1u : 0u;
 		const uint64_t left = m.len > m.pos ? m.len - m.pos : 0;
 		m.mixed = m.hf ? (left < F ? (uint32_t)left : F) : 0; // [ENGINE] AudioStreamPlayback::mix return value
+		if (m.lmode) { // wave-uniform: a looped playback never runs out
+			m.mixed = m.hf ? F : 0;
+		}
 	}
 	return m;
 }
@@ -464,8 +477,8 @@ __device__ __forceinline__ SrcMeta bcast_meta(const LaneMeta &lm, uint32_t i, ui
 // logic, fused: 64-frame lookahead delay, silence in front of the playback's start, fade-out over the last 64
 // valid frames, zero feed afterwards.  The format switch sits outside the frame loop and every load is
 // unconditional (out-of-window lanes read index 0 and are masked afterwards), so the loads issue back to back.
-template <bool SRC_PCM, int FQ>
-__device__ __forceinline__ void load_window(const gas_group_args &g, const SrcMeta &m, int lane, const float *__restrict__ fade_env, gas_audio_frame (&raw)[FQ]) {
+template <bool SRC_PCM, int FQ, bool LOOPS = true>
+__device__ __forceinline__ void load_window(const gas_group_args &g, const SrcMeta &m, int lane, const float *__restrict__ fade_env, gas_audio_frame (&raw)[FQ], const gas_cursor *cursors = nullptr) {
 	constexpr uint32_t F = FQ * 64;
 	if constexpr (!SRC_PCM) {
 #pragma unroll
@@ -477,12 +490,29 @@ __device__ __forceinline__ void load_window(const gas_group_args &g, const SrcMe
 		const int64_t base = (int64_t)m.pos - GAS_LOOKAHEAD_BUFFER_SIZE;
 		bool ok[FQ];
 		int64_t idx[FQ];
+		if (LOOPS && m.lmode && m.hf) {
+			// wave-uniform branch: the window of the unrolled stream, idx = m(base + f).  The 64-bit remainder is taken once
+			// per source on wave-uniform values; a lane then steps its phase by 64 with one conditional subtract per frame.
+			const uint64_t lbegin = cursors[m.slot].loop_begin;
+			const gas_loop_win w = gas_loop_window(base, lbegin, cursors[m.slot].loop_len, m.lmode, F);
+			uint32_t t = gas_loop_first(w, (uint32_t)lane);
 #pragma unroll
-		for (int q = 0; q < FQ; q++) {
-			const uint32_t f = (uint32_t)(lane + 64 * q);
-			const int64_t si = base + f;
-			ok[q] = m.hf && (m.mixed == F || f < m.mixed + GAS_LOOKAHEAD_BUFFER_SIZE) && si >= (int64_t)m.start;
-			idx[q] = ok[q] ? si : 0;
+			for (int q = 0; q < FQ; q++) {
+				const uint32_t f = (uint32_t)(lane + 64 * q);
+				const int64_t si = base + f;
+				ok[q] = si >= (int64_t)m.start;
+				const int64_t li = f < w.skip ? si : (int64_t)(lbegin + gas_loop_fold(w, t));
+				idx[q] = ok[q] ? li : 0;
+				t = gas_loop_add(t, w.step, w.P);
+			}
+		} else {
+#pragma unroll
+			for (int q = 0; q < FQ; q++) {
+				const uint32_t f = (uint32_t)(lane + 64 * q);
+				const int64_t si = base + f;
+				ok[q] = m.hf && (m.mixed == F || f < m.mixed + GAS_LOOKAHEAD_BUFFER_SIZE) && si >= (int64_t)m.start;
+				idx[q] = ok[q] ? si : 0;
+			}
 		}
 		const uint32_t fmt = m.fc >> 8, ch = m.fc & 0xff;
 		if (fmt == GAS_PCM_S16 && ch == 1) {

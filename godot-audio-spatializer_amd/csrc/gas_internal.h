@@ -143,7 +143,60 @@ struct gas_cursor {
 	uint64_t fp_pos, fp_prev_pos;
 	uint32_t prev_inc;
 	uint32_t resampled; // 0 plain, 1 resampled and never mixed yet (zeroed lookahead, :61-63), 2 resampled
+	// NEW gas_stream_set_loop: pos / fp_pos / start count on the unrolled timeline U[k] = S[m(k)] and never wrap
+	uint64_t loop_begin;
+	uint32_t loop_len; // L = loop_end - loop_begin < 2^31
+	uint32_t loop_mode; // gas_loop_mode; 0 = the stream plays once
 };
+
+// The index map m of gas_stream_set_loop (gas_amd.h), and its incremental form for the frames of one window.
+__host__ __device__ inline uint64_t gas_loop_map(uint64_t k, uint64_t b, uint32_t L, uint32_t mode) {
+	if (mode == GAS_LOOP_DISABLED || k < b) {
+		return k;
+	}
+	const uint64_t P = mode == GAS_LOOP_PINGPONG ? 2 * (uint64_t)L : L;
+	const uint64_t t = (k - b) % P;
+	return b + (t < L ? t : P - 1 - t);
+}
+
+// t(i) = (base + i - loop_begin) mod P (floored) for the frames i = 0 .. F of a window that starts at unrolled index
+// `base`: the one 64-bit remainder of a source's callback.  The first `skip` frames lie in front of the loop (m = k).
+struct gas_loop_win {
+	uint32_t P, L, t0, skip, step;
+};
+
+__host__ __device__ inline gas_loop_win gas_loop_window(int64_t base, uint64_t b, uint32_t L, uint32_t mode, uint32_t F) {
+	gas_loop_win w;
+	w.L = L;
+	w.P = mode == GAS_LOOP_PINGPONG ? 2 * L : L; // <= 2^32 - 2
+	const int64_t d = base - (int64_t)b;
+	if (d >= 0) {
+		w.t0 = (uint32_t)((uint64_t)d % w.P);
+		w.skip = 0;
+	} else {
+		const uint64_t nd = (uint64_t)-d;
+		const uint32_t r = (uint32_t)(nd % w.P);
+		w.t0 = r ? w.P - r : 0;
+		w.skip = nd < F ? (uint32_t)nd : F;
+	}
+	w.step = w.P > 64 ? 64 : 64 % w.P; // a lane's frames are 64 apart
+	return w;
+}
+
+// (t + a) mod P for t, a < P; the sum may carry out of 32 bits (P up to 2^32 - 2), the difference never does
+__host__ __device__ inline uint32_t gas_loop_add(uint32_t t, uint32_t a, uint32_t P) {
+	const uint32_t s = t + a;
+	return (s < t || s >= P) ? s - P : s;
+}
+
+// t(lane), lane < 64: one conditional subtract when the period is longer than a wave, else a 32-bit remainder
+__host__ __device__ inline uint32_t gas_loop_first(const gas_loop_win &w, uint32_t lane) {
+	return w.P > 64 ? gas_loop_add(w.t0, lane, w.P) : (w.t0 + lane) % w.P;
+}
+
+__host__ __device__ inline uint32_t gas_loop_fold(const gas_loop_win &w, uint32_t t) {
+	return t < w.L ? t : w.P - 1 - t;
+}
 
 // What a launch group (one kind/chain) needs.
 struct gas_group_args {

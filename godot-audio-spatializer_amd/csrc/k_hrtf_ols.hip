@@ -96,6 +96,7 @@ __device__ __forceinline__ void blend_spectra(const float4 *__restrict__ spec, i
 template <int SQ, bool WITH_ER, bool PEAKS, bool SRC_PCM, bool XFADE, bool RUNS = false, bool BLEND = false, bool FADE = false>
 __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const uint32_t wg, const gas_group_args &g, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *__restrict__ tw, uint32_t n_wgs, uint32_t er_R, float *__restrict__ my_partial, gas_cursor *__restrict__ cursors, const float *__restrict__ fade_env, const gas_params *__restrict__ fresh, gas_audio_frame *__restrict__ rows_out = nullptr, const gas_deferred_reduce job = gas_deferred_reduce(), uint32_t job_col = 0, float2 *fade_lds = nullptr) {
 	static_assert(!(WITH_ER && SRC_PCM), "the early-reflection prologue reads float rows");
+	constexpr bool LOOPS = !XFADE; // register budget: the cross-fade form keeps the un-looped prologue; looped lists reach it as rows
 	static_assert(!(BLEND && (XFADE || RUNS)), "a blended source has no single direction to fade from or to group by");
 	static_assert(!FADE || BLEND, "GAS_FLAG_HRTF_BLEND_FADE fades between blend rows");
 	// two renders per source lerped with t = f/F: the old direction's (XFADE) or the old blend row's (FADE)
@@ -314,7 +315,11 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 			lm.pdir = pd == 0 ? lm.dir : (pd - 1 < tab.dirs ? pd - 1 : 0);
 		}
 		if constexpr (SRC_PCM) {
-			lm.cur = cursors[lm.slot];
+			if constexpr (LOOPS) {
+				lm.cur = lane_cursor(cursors, lm.slot);
+			} else {
+				lm.cur = cursors[lm.slot];
+			}
 		}
 		// per-source state that does not depend on the audio, written once for all of the wave's sources (one lane
 		// each) instead of by lane 0 inside the source loop
@@ -352,7 +357,7 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 #pragma unroll
 			for (int s = 0; s < STAGES; s++) {
 				if (first + s < last) {
-					load_window<true, FQ>(g, bcast_meta<SRC_PCM>(lm, s, F), lane, fade_env, raw[s]); // needs the cursor
+					load_window<true, FQ, LOOPS>(g, bcast_meta<SRC_PCM, LOOPS>(lm, s, F), lane, fade_env, raw[s], cursors); // needs the cursor
 				}
 			}
 		}
@@ -421,9 +426,9 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 		}
 		const bool has_next = e + 1 < last;
 		const bool has_ahead = e + STAGES < last;
-		const SrcMeta m = bcast_meta<SRC_PCM>(lm, e - first, F);
-		const SrcMeta mn = bcast_meta<SRC_PCM>(lm, has_next ? e + 1 - first : e - first, F);
-		const SrcMeta ma = bcast_meta<SRC_PCM>(lm, has_ahead ? e + STAGES - first : e - first, F);
+		const SrcMeta m = bcast_meta<SRC_PCM, LOOPS>(lm, e - first, F);
+		const SrcMeta mn = bcast_meta<SRC_PCM, LOOPS>(lm, has_next ? e + 1 - first : e - first, F);
+		const SrcMeta ma = bcast_meta<SRC_PCM, LOOPS>(lm, has_ahead ? e + STAGES - first : e - first, F);
 
 		// x_full[lane + 64 q]: q < HQ from the history, the rest from this callback's frames.
 		float xq[NQ];
@@ -556,7 +561,7 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 				load_history<HQ>(st.hrtf_hist + (size_t)ma.slot * HL, lane, rawh[s]);
 			}
 			if constexpr (!WITH_ER) {
-				load_window<SRC_PCM, FQ>(g, ma, lane, fade_env, raw[s]);
+				load_window<SRC_PCM, FQ, LOOPS>(g, ma, lane, fade_env, raw[s], cursors);
 			}
 		}
 

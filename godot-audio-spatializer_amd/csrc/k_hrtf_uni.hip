@@ -196,7 +196,7 @@ __global__ __launch_bounds__(UW * 64, UW > 8 ? 3 : GAS_HRTF_WAVES_PER_SIMD) void
 		lm.dir = d < tab.dirs ? d : 0;
 		lm.pdir = lm.dir;
 		if constexpr (SRC_PCM) {
-			lm.cur = cursors[lm.slot];
+			lm.cur = lane_cursor(cursors, lm.slot);
 		}
 		const uint32_t e = my_entry;
 		my_flag = (peak_all || e >= peak_from) ? 1u : (peak_bits ? (peak_bits[(e + peak_bit_base) >> 5] >> ((e + peak_bit_base) & 31)) & 1u : 0u);
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(UW * 64, UW > 8 ? 3 : GAS_HRTF_WAVES_PER_SIMD) void
 	}
 	if constexpr (SRC_PCM) {
 		if (first < last) {
-			load_window<true, FQ>(g, bcast_meta<true>(lm, 0, F), lane, fade_env, raw); // needs the cursor
+			load_window<true, FQ>(g, bcast_meta<true>(lm, 0, F), lane, fade_env, raw, cursors); // needs the cursor
 		}
 	}
 	float *flt_par = flt_all + (FLT ? wave * 64 * FLT_W : 0);
@@ -647,7 +647,7 @@ __global__ __launch_bounds__(UW * 64, UW > 8 ? 3 : GAS_HRTF_WAVES_PER_SIMD) void
 		}
 		if (has_next) {
 			load_history<HQ>(st.hrtf_hist + (size_t)mn.slot * HL, lane, rawh, nt_hist != 0);
-			load_window<SRC_PCM, FQ>(g, mn, lane, fade_env, raw);
+			load_window<SRC_PCM, FQ>(g, mn, lane, fade_env, raw, cursors);
 		}
 		// z = a + i b : a = x_full[0..512), b = x_full[S..S+512) -- one complex FFT serves both sub-blocks
 		float2 zs[8];

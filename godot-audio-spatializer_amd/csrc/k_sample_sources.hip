@@ -39,10 +39,23 @@ __device__ __forceinline__ gas_audio_frame cubic_frame(const gas_cursor &c, uint
 	const int64_t q = (int64_t)(off >> 16);
 	const float mu = (float)(uint32_t)(off & 0xFFFFu) / 65536.0f;
 	gas_audio_frame y[4];
+	if (c.loop_mode) { // taps U[q-3 .. q] of the unrolled stream: one 64-bit remainder per output frame, then steps of one
+		const gas_loop_win w = gas_loop_window(q - 3, c.loop_begin, c.loop_len, c.loop_mode, 4);
+		const uint32_t one = w.P > 1 ? 1u : 0u;
+		uint32_t t = w.t0;
 #pragma unroll
-	for (int k = 0; k < 4; k++) {
-		const int64_t j = q - 3 + k;
-		y[k] = (j >= (int64_t)c.start && j < (int64_t)c.frames) ? load_frame(c.pcm, fmt, ch, (uint64_t)j) : gas_audio_frame{ 0.0f, 0.0f };
+		for (int k = 0; k < 4; k++) {
+			const int64_t j = q - 3 + k;
+			const uint64_t idx = (uint32_t)k < w.skip ? (uint64_t)j : c.loop_begin + gas_loop_fold(w, t);
+			y[k] = j >= (int64_t)c.start ? load_frame(c.pcm, fmt, ch, idx) : gas_audio_frame{ 0.0f, 0.0f };
+			t = gas_loop_add(t, one, w.P);
+		}
+	} else {
+#pragma unroll
+		for (int k = 0; k < 4; k++) {
+			const int64_t j = q - 3 + k;
+			y[k] = (j >= (int64_t)c.start && j < (int64_t)c.frames) ? load_frame(c.pcm, fmt, ch, (uint64_t)j) : gas_audio_frame{ 0.0f, 0.0f };
+		}
 	}
 	const float mu2 = mu * mu;
 	const float h11 = mu2 * (mu - 1);
@@ -73,7 +86,9 @@ __global__ __launch_bounds__(256) void k_sample_sources(gas_cursor *__restrict__
 		const uint64_t inc = row_inc ? row_inc[e] : 65536u;
 		const uint64_t end_fp = c.frames << 16;
 		uint64_t mixed64 = F;
-		if (c.fp_pos >= end_fp) {
+		if (c.loop_mode) {
+			// a looped playback never runs out
+		} else if (c.fp_pos >= end_fp) {
 			mixed64 = 0;
 		} else if (inc > 0) {
 			const uint64_t need = (end_fp - c.fp_pos + inc - 1) / inc; // first i with fp_pos + i * inc >= end
@@ -104,6 +119,26 @@ __global__ __launch_bounds__(256) void k_sample_sources(gas_cursor *__restrict__
 			if (mixed != F) {
 				cp->has_frames = 0; // :398
 			}
+		}
+		return;
+	}
+	if (c.loop_mode && c.has_frames && c.pcm) {
+		// NEW gas_stream_set_loop: the same 64-frame delay over the unrolled stream, row[i] = S[m(pos - 64 + i)]; seams
+		// fall wherever they fall and nothing fades or ends.  One 64-bit remainder per row, 32-bit steps per frame.
+		const int64_t base = (int64_t)c.pos - GAS_LOOKAHEAD_BUFFER_SIZE;
+		const gas_loop_win w = gas_loop_window(base, c.loop_begin, c.loop_len, c.loop_mode, F);
+		uint32_t t = gas_loop_first(w, (uint32_t)lane);
+		for (uint32_t i = lane; i < F; i += 64) {
+			gas_audio_frame v{ 0.0f, 0.0f };
+			const int64_t si = base + (int64_t)i;
+			if (si >= (int64_t)c.start) {
+				v = load_frame(c.pcm, fmt, ch, i < w.skip ? (uint64_t)si : c.loop_begin + gas_loop_fold(w, t));
+			}
+			row[i] = v;
+			t = gas_loop_add(t, w.step, w.P);
+		}
+		if (lane == 0) {
+			cp->pos = c.pos + F;
 		}
 		return;
 	}

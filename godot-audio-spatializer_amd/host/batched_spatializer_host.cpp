@@ -37,6 +37,7 @@
 #pragma weak gas_fx_stereo_settings_publish
 #pragma weak gas_fx_filter_settings_publish
 #pragma weak gas_hrtf_blend_publish
+#pragma weak gas_stream_get_loop
 
 namespace {
 
@@ -68,6 +69,7 @@ struct Playback {
 	bool on_device = false;
 	uint32_t device_stream = 0;
 	uint64_t device_start = 0; // first frame of this playback in its stream
+	bool device_looped = false; // the stream loops (gas_stream_set_loop): it never runs dry, its position is the wrapped stream frame
 	uint64_t consumed = 0; // frames taken from the source so far
 	// audio-thread state
 	bool stream_live = true; // the source still has frames (has_frames, audio_spatializer.h:63)
@@ -259,6 +261,8 @@ struct gas_host {
 				pb->has_slot = rc == GAS_OK;
 				if (rc == GAS_OK && pb->on_device) {
 					rc = gas_source_bind_stream(ctx, pb->slot, pb->device_stream, pb->device_start);
+					int loop_mode = GAS_LOOP_DISABLED;
+					pb->device_looped = rc == GAS_OK && gas_stream_get_loop && gas_stream_get_loop(ctx, pb->device_stream, &loop_mode, nullptr, nullptr) == GAS_OK && loop_mode != GAS_LOOP_DISABLED;
 				}
 				if (rc != GAS_OK) { // out of slots / unknown stream: the playback never becomes audible
 					if (pb->has_slot) {
@@ -388,7 +392,9 @@ struct gas_host {
 				const bool have_pos = gas_stream_positions(ctx, count, positions.data()) == GAS_OK; // the library's mirror of the device cursors
 				for (uint32_t r = 0; r < count; r++) {
 					Playback *pb = row_owner[r];
-					if (have_pos && positions[r] >= pb->device_start) {
+					if (have_pos && pb->device_looped) {
+						pb->consumed = positions[r]; // m(k): the stream frame taken next
+					} else if (have_pos && positions[r] >= pb->device_start) {
 						pb->consumed = positions[r] - pb->device_start;
 					}
 					pb->stream_live = live_out[r] != 0; // audio_spatializer.cpp:398

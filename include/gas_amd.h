@@ -738,11 +738,32 @@ int gas_stream_create(gas_ctx *ctx, const void *pcm, int format, uint32_t channe
  *                  parity unpinned; the stream is taken to be at the context's mix rate.  pitch_scale is the value last
  *                  published from the host (gas_params_publish*); 0 <= pitch_scale < 32768. */
 int gas_stream_set_resampled(gas_ctx *ctx, uint32_t stream, int on);
+/* NEW (no counterpart in the reference; named after [ENGINE] AudioStreamWAV's loop modes, not a restatement of its
+ * mixer): the stream's playbacks repeat [loop_begin, loop_end).  A looped playback behaves exactly as a plain playback
+ * over the unrolled stream U[k] = S[m(k)], k = 0, 1, 2, ...; with b = loop_begin, e = loop_end, L = e - b:
+ *   k <  b: m(k) = k
+ *   k >= b: t = (k - b) mod P;  FORWARD: P = L, m = b + t;  PINGPONG: P = 2L, m = b + (t < L ? t : 2L - 1 - t)
+ * (both end frames of a ping-pong loop play twice; frames from e on never play).  Cursor, 64-frame lookahead, the
+ * resampler's taps and start_frame all count on the unrolled timeline; no fade at a seam; the playback never ends on
+ * its own (has_frames stays 1) and stops through gas_source_set_draining / gas_source_free like any other.
+ * loop_end == 0 means the stream's length.  Chosen before playbacks are bound, like gas_stream_set_resampled: a bound
+ * stream answers GAS_ERR_INVALID_ARGUMENT, an unknown one GAS_ERR_BAD_SLOT.  An unknown mode, loop_begin >= loop_end,
+ * loop_end > frames and L >= 2^31 answer GAS_ERR_INVALID_ARGUMENT and change nothing.  GAS_LOOP_DISABLED ignores
+ * loop_begin / loop_end. */
+typedef enum gas_loop_mode {
+	GAS_LOOP_DISABLED = 0,
+	GAS_LOOP_FORWARD = 1,
+	GAS_LOOP_PINGPONG = 2,
+} gas_loop_mode;
+int gas_stream_set_loop(gas_ctx *ctx, uint32_t stream, int mode, uint64_t loop_begin, uint64_t loop_end);
+/* The stream's loop as set (DISABLED: begin = end = 0; any of the outputs may be NULL). */
+int gas_stream_get_loop(gas_ctx *ctx, uint32_t stream, int *out_mode, uint64_t *out_begin, uint64_t *out_end);
 int gas_stream_destroy(gas_ctx *ctx, uint32_t stream);
 /* Length, channel count and sample format of a stream (any of the outputs may be NULL). */
 int gas_stream_get_info(gas_ctx *ctx, uint32_t stream, uint64_t *out_frames, uint32_t *out_channels, int *out_format);
 /* start_playback_stream (audio_spatializer.cpp:55-63): the slot's playback starts at start_frame of the stream
- * with a zeroed lookahead and has_frames set. */
+ * with a zeroed lookahead and has_frames set.  For a looped stream start_frame is a position on the unrolled
+ * timeline and is not clamped to the stream's length. */
 int gas_source_bind_stream(gas_ctx *ctx, uint32_t slot, uint32_t stream, uint64_t start_frame);
 /* Like gas_process_block, but the source windows are produced on the device from the bound streams (cursor
  * advance, lookahead delay, fade-out, zero feed after the end).  has_frames ([n] bytes, host, may be NULL)
@@ -751,7 +772,7 @@ int gas_source_bind_stream(gas_ctx *ctx, uint32_t slot, uint32_t stream, uint64_
 int gas_process_block_streams(gas_ctx *ctx, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, float *peaks, uint8_t *has_frames, int mem);
 /* Where the playbacks of the LAST gas_process_block_streams list stand in their streams after it, in its row order:
  * out_frames[i] = index of the next stream frame playback i will take ([ENGINE] get_playback_position x mix rate, plus
- * the playback's start frame).  From the host-side mirror of the cursor arithmetic: nothing is read back from the
+ * the playback's start frame; for a looped stream m(k) of the frames consumed).  From the host-side mirror of the cursor arithmetic: nothing is read back from the
  * device.  n must be that callback's n.  Audio thread. */
 int gas_stream_positions(gas_ctx *ctx, uint32_t n, uint64_t *out_frames);
 

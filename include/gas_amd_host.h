@@ -49,7 +49,9 @@ int gas_host_start_playback(gas_host *host, gas_host_stream_mix_fn mix, void *us
 int gas_host_start_playback_array(gas_host *host, const gas_audio_frame *stream, int64_t stream_frames, uint32_t *out_id);
 /* A playback over a device-resident stream (gas_stream_create): nothing crosses PCIe per callback, the source window
  * and fade-out are produced on the GPU (gas_process_block_streams).  A host serves either callback/array playbacks
- * or device-stream playbacks, not a mixture (GAS_ERR_KIND_MISMATCH). */
+ * or device-stream playbacks, not a mixture (GAS_ERR_KIND_MISMATCH).  A stream with a loop (gas_stream_set_loop) plays
+ * until gas_host_stop_playback; start_frame is then a position on the unrolled timeline and
+ * gas_host_get_playback_position reports the wrapped stream frame that is taken next. */
 int gas_host_start_playback_device_stream(gas_host *host, uint32_t stream, uint64_t start_frame, uint32_t *out_id);
 /* stop_playback_stream (audio_spatializer.cpp:98-113): active = false; the audio thread reaps it. */
 int gas_host_stop_playback(gas_host *host, uint32_t id);

@@ -2,6 +2,8 @@
 // coefficient preparation.  Anonymous namespace: each translation unit gets its own copy.
 #pragma once
 #include "gas_internal.h"
+#define GAS_GATE_FN __host__ __device__
+#include "gas_biquad_gate.h" // scan or serial: the one test both filter-stage kernels apply
 
 // No FMA contraction anywhere in the high-shelf path (the including files say why): the f64 coefficient preparation
 // below and the f32 recurrences must round exactly where the engine's C++ does.

@@ -103,7 +103,7 @@ struct UniLds {
 // 44 -> 31 us with every peak, 38 -> 23 with the draining ones; profiles/r03_notes.md).  The filter is k_shelf_scan's,
 // operation for operation (the same bits as the two-launch form): both ears, a lane owns F/64 consecutive frames (a
 // transpose through the wave's LDS slice on the way in and out), local response from rest, homogeneous solutions,
-// six-step affine scan over the lanes; a source whose poles lie outside r^2 <= 0.9 is walked serially by two lanes, one
+// six-step affine scan over the lanes; a source gas_biquad_gate.h refuses (all-pole peak gain above 40) is walked serially by two lanes, one
 // per ear (the engine's form, bitwise k_biquad_mix's).  Filtering the MEAN of the ears instead (the HRTF's input; the
 // filter is linear) would halve the work, and was measured and dropped for its numerics: next to the unit circle the
 // mean's one extra rounding, or a per-ear walk from a mean history, is amplified ~1 / (1 - r) -- 1e-4 on a source's peak
@@ -513,7 +513,8 @@ __global__ __launch_bounds__(UW * 64, UW > 8 ? 3 : GAS_HRTF_WAVES_PER_SIMD) void
 				xs[lane + 64 * q] = make_float2(raw[q].left, raw[q].right);
 			}
 			wave_lds_sync();
-			const bool serial = !(fabsf(__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(co.a2)))) <= 0.9f); // wave-uniform; NaN goes serial too
+			// k_shelf_scan's choice, on the same coefficient bits (gas_biquad_gate.h: the all-pole peak gain, not |a2|); wave-uniform, NaN goes serial too
+			const bool serial = !gas_biquad_scan_allowed(__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(co.a1))), __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(co.a2))));
 			if (serial) {
 				if (lane < 2) { // each ear on its own lane, [ENGINE] process_one's operation order, no contraction
 					float a1 = hp[5 + 4 * lane], a2 = hp[6 + 4 * lane], b1 = hp[7 + 4 * lane], b2 = hp[8 + 4 * lane];

@@ -18,11 +18,14 @@
 //   4. y[k] = w[k] + p[k] s_(l-1).x + q[k] s_(l-1).y
 // ~300 VALU instructions per source instead of a 512-step chain: the stage is bound by its 8 KiB of row traffic per
 // source.  Same filter, DIFFERENT rounding from the serial form: the scan's sums associate differently and the powers of
-// M carry their own error, which a pole radius near 1 amplifies like the recurrence itself does.  A source whose poles
-// lie outside r^2 <= 0.9 therefore takes the serial path (two lanes walk the row out of LDS, the engine's operation
-// order, no FMA contraction: bitwise k_biquad_mix) -- the wave-uniform choice below; inside it the scan tracks the
-// oracle to ~2e-6 relative (tests/test_gpu_chains.py).  NEW arrangement of [ENGINE] arithmetic: parity unpinned like
-// the rest of SURVEY.md Appendix B.
+// M carry their own error, which the filter's feedback part amplifies like the recurrence itself does -- by up to the
+// peak gain of 1 / |1 - a1 z^-1 - a2 z^-2| on the unit circle, the filter's conditioning.  A source whose all-pole peak
+// gain exceeds 40 (gas_biquad_gate.h: poles next to the unit circle, real or complex, and near-double poles next to
+// z = +-1 at any radius) therefore takes the serial path (two lanes walk the row out of LDS, the engine's operation
+// order, no FMA contraction: bitwise k_biquad_mix, pinned by tests/test_gpu_filter_scan_gate.py) -- the wave-uniform
+// choice below; inside the gate a source's peak stays within 2e-5 of a float64 recurrence (same test; DESIGN.md 3.5 (a)
+// has the measured figures).  NEW arrangement of [ENGINE] arithmetic: parity unpinned like the rest of SURVEY.md
+// Appendix B.
 #include <cstdlib>
 
 #include "gas_biquad.h"
@@ -81,7 +84,7 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void k_shelf_scan(gas_group_args g
 		x[1][2 * k + 1] = v.w;
 	}
 	float y[2][P];
-	const bool serial = !(fabsf(co.a2) <= 0.9f); // wave-uniform (coefficients are the source's); NaN coefficients go serial too
+	const bool serial = !gas_biquad_scan_allowed(co.a1, co.a2); // wave-uniform (coefficients are the source's); NaN coefficients go serial too
 
 	if (serial) {
 		// the engine's own loop, two lanes (one per ear) over the row staged in LDS: bitwise k_biquad_mix's FX modes

@@ -223,9 +223,12 @@ def test_filter_stage_as_a_scan_matches_oracle(gas, ob, chain, frames, monkeypat
     """From 512 sources on (and below 32768) a rows-out filter stage runs k_shelf_scan: one wave per source, the block's
     recurrence split over the lanes and stitched by an affine scan -- another rounding than the engine's serial loop, so
     this is the test that says how far apart they are: the mix to TOL, a single source's peak to 2e-5 where the poles
-    are well inside the unit circle (the default 5 kHz shelf: ~2e-6 measured).  Sources whose poles are close to it
-    (r^2 > 0.9) take the kernel's serial path; some are mixed in here.  The same callbacks with GAS_SHELF_SCAN=0 (the
-    serial stage kernel) are the control."""
+    are well inside the unit circle (the default 5 kHz shelf: ~2e-6 measured).  Ill-conditioned sources (all-pole peak
+    gain above 40, csrc/gas_biquad_gate.h) take the kernel's serial path; some are mixed in here.  The same callbacks
+    with GAS_SHELF_SCAN=0 (the serial stage kernel) are the control.  Peaks stay at rtol 1e-4: with that gate the worst
+    deviation measured here is 4.9e-5 ([HS, HRTF], 4500 sources, both scan forms; 2.0e-6 for [LP, HRTF], 6.3e-6 for
+    [NOTCH, HP], 1.5e-6 for the control), above the 1e-5 that would let it go to 2e-5.  A filter stage alone is held
+    to 2e-5 per source in test_gpu_filter_scan_gate.py."""
     from godot_audio_spatializer_amd import synth
 
     # [filter, HRTF] has a third form, the default: both effects in one launch (k_hrtf_uni<FLT>, the filter on the mean of
@@ -243,7 +246,7 @@ def test_filter_stage_as_a_scan_matches_oracle(gas, ob, chain, frames, monkeypat
                 ctx.hrtf_load(hrir)
             slots = ctx.source_alloc_many(n, gas.capi.KIND_EFFECT, chain)
             ora = ob.BatchOracle(ob.KIND_EFFECT, n, frames, chain=chain, hrir=hrir)
-            worst = 0.0
+            worst = worst_peak = 0.0
             for b in range(6):
                 if b % 2 == 0:
                     p = synth.draw_params(rng, n, dirs=32, frames=frames)
@@ -262,9 +265,11 @@ def test_filter_stage_as_a_scan_matches_oracle(gas, ob, chain, frames, monkeypat
                 mix, peaks = ctx.process_block(src, slots)
                 _, rpeaks, r64 = ora.block(p.astype(ob.PARAMS_DTYPE), src, want64=True)
                 worst = max(worst, rel_rms(mix[0], r64[0]))
+                worst_peak = max(worst_peak, float(((np.abs(peaks - rpeaks) - 1e-6) / np.abs(rpeaks)).max()))  # the rtol this block needs
                 assert rel_rms(mix[0], r64[0]) <= TOL, f"scan={scan} flt={flt} block {b}"
                 np.testing.assert_allclose(peaks, rpeaks, rtol=1e-4, atol=1e-6, err_msg=f"scan={scan} flt={flt} block {b}")
                 seen.setdefault((scan, flt), []).append((mix.copy(), peaks.copy()))
+            print(f"{chain} F={frames} scan={scan} flt={flt}: worst mix {worst:.2e}, worst peak deviation {worst_peak:.2e}")
     if HRTF in chain:  # the one-launch form runs k_shelf_scan's operations in k_shelf_scan's order: the two-launch form's bits
         for (m1, p1), (m0, p0) in zip(seen[("1", "1")], seen[("1", "0")]):
             np.testing.assert_array_equal(m1, m0)

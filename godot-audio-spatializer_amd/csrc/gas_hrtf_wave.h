@@ -42,6 +42,20 @@ __device__ __forceinline__ float2 cmul_fixed(float2 z, float hx, float hy) {
 #pragma clang fp contract(off)
 	return make_float2(__builtin_fmaf(z.x, hx, -(z.y * hy)), __builtin_fmaf(z.x, hy, z.y * hx));
 }
+// The window registers that enter the transform as zeros.  The outputs a sub-block keeps are window positions
+// [512 - S, 512), S = 64 SQ, and each reaches back GAS_HRTF_TAPS - 1 frames: window frames below 512 - S - (TAPS - 1) feed
+// only the aliased outputs nobody reads.  Transformed, they would still leave their rounding (1e-7 of full scale) on the
+// outputs that are kept -- at F = 128 up to three callbacks after a source fell silent, when its true output is an exact
+// zero and its peak decides the silence gate.  Whole 64-frame registers: 3, 2, 1, 0 for F = 128, 256, 384, 512.
+template <int SQ>
+constexpr int hrtf_dead_regs() {
+	return (512 - 64 * SQ - (GAS_HRTF_TAPS - 1)) / 64;
+}
+// z = a + i b of register j: a = x_full[0..512), b = x_full[S..S+512)
+template <int SQ>
+__device__ __forceinline__ float2 hrtf_window_z(const float *xq, int j) {
+	return j < hrtf_dead_regs<SQ>() ? make_float2(0.0f, 0.0f) : make_float2(xq[j], xq[j + SQ]);
+}
 // Once-touched streams (source rows, history) bypass the caches' retention so they do not evict the HRIR
 // spectra table, which is the only data re-read across sources (MI355X_MICROARCH.md nt-weights row).
 #ifndef GAS_ABL

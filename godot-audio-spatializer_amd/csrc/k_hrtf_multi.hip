@@ -242,7 +242,7 @@ __global__ __launch_bounds__(MW * 64, GAS_HRTF_WAVES_PER_SIMD) void k_hrtf_multi
 			float2 zs[8];
 #pragma unroll
 			for (int j = 0; j < 8; j++) {
-				zs[j] = make_float2(xq[j], xq[j + SQ]);
+				zs[j] = hrtf_window_z<SQ>(xq, j);
 			}
 			fft512<false>(zs, t1, t2, lds, lane);
 			products(true, dir);

@@ -571,7 +571,7 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 			float2 v[8];
 #pragma unroll
 			for (int j = 0; j < 8; j++) {
-				v[j] = make_float2(xq[j], xq[j + SQ]);
+				v[j] = hrtf_window_z<SQ>(xq, j);
 			}
 			fft512<false>(v, t1, t2, lds, lane);
 			blend_rows(e - first);
@@ -650,8 +650,9 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 		} else {
 #pragma unroll
 			for (int j = 0; j < 8; j++) {
-				zs[j].x += xq[j];
-				zs[j].y += xq[j + SQ];
+				const float2 z = hrtf_window_z<SQ>(xq, j);
+				zs[j].x += z.x;
+				zs[j].y += z.y;
 			}
 			// the run ends with the wave's sources or when the direction changes; the cross-fade pairs every source
 			// with its own previous direction, so it transforms source by source

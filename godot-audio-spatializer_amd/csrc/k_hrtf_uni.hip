@@ -654,7 +654,7 @@ __global__ __launch_bounds__(UW * 64, UW > 8 ? 3 : GAS_HRTF_WAVES_PER_SIMD) void
 		float2 zs[8];
 #pragma unroll
 		for (int j = 0; j < 8; j++) {
-			zs[j] = make_float2(xq[j], xq[j + SQ]);
+			zs[j] = hrtf_window_z<SQ>(xq, j);
 		}
 		if constexpr (LEAN) {
 			if constexpr (GAS_UNI12_DIRECT) {

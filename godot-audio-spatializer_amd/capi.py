@@ -22,6 +22,7 @@ FX_EARLY_REFLECTIONS = 2
 FX_HRTF = 3
 FX_LOWPASS, FX_HIGHPASS, FX_BANDPASS, FX_NOTCH, FX_LOWSHELF, FX_AMPLIFY = 4, 5, 6, 7, 8, 9
 MAX_EFFECTS = 4
+MAX_SIDECHAINS = 8  # GAS_MAX_SIDECHAINS: key blocks per context (SpatializerContext.sidechain_set)
 # gas_fx_settings: settings of the engine-effect kinds by chain position (64 bytes)
 FX_SETTINGS_DTYPE = np.dtype([("filter_cutoff_hz", np.float32, (MAX_EFFECTS,)), ("filter_resonance", np.float32, (MAX_EFFECTS,)), ("filter_gain", np.float32, (MAX_EFFECTS,)), ("amplify_volume_db", np.float32, (MAX_EFFECTS,))])
 # the engine's nonlinear / dynamics kinds (10 is not assigned); settings: gas_fx_dyn_settings by chain position
@@ -40,7 +41,7 @@ FX_DYN_SETTINGS_DTYPE = np.dtype(
         ("compressor_attack_us", np.float32, (MAX_EFFECTS,)),
         ("compressor_release_ms", np.float32, (MAX_EFFECTS,)),
         ("compressor_mix", np.float32, (MAX_EFFECTS,)),
-        ("reserved", np.uint32, (MAX_EFFECTS,)),
+        ("compressor_sidechain", np.uint32, (MAX_EFFECTS,)),  # 0: none, k: key k - 1 of the context
     ]
 )
 assert FX_DYN_SETTINGS_DTYPE.itemsize == 192
@@ -411,6 +412,7 @@ EXPORTS = [
     "gas_params_publish",
     "gas_fx_settings_publish",
     "gas_fx_dyn_settings_publish",
+    "gas_sidechain_set",
     "gas_fx_line_settings_publish",
     "gas_ctx_reserve_fx_lines",
     "gas_fx_eq_settings_publish",
@@ -506,6 +508,7 @@ def load_library():
     L.gas_params_publish.argtypes = [vp, u32, vp]
     L.gas_fx_settings_publish.argtypes = [vp, vp, vp, u32]
     L.gas_fx_dyn_settings_publish.argtypes = [vp, vp, vp, u32]
+    L.gas_sidechain_set.argtypes = [vp, u32, vp, u32, i32]
     L.gas_fx_line_settings_publish.argtypes = [vp, vp, vp, u32]
     L.gas_ctx_reserve_fx_lines.argtypes = [vp, u32, u32]
     L.gas_fx_eq_settings_publish.argtypes = [vp, vp, vp, u32]
@@ -637,6 +640,23 @@ class SpatializerContext:
         f = np.ascontiguousarray(settings, dtype=FX_DYN_SETTINGS_DTYPE)
         assert s.shape == f.shape
         self._check(self.lib.gas_fx_dyn_settings_publish(self.h, _np_ptr(s), _np_ptr(f), len(s)), "gas_fx_dyn_settings_publish")
+
+    def sidechain_set(self, key, frames):
+        """Replace sidechain key block `key` (0 .. MAX_SIDECHAINS - 1) from host memory: frames float32 [F][2], or None for
+        a silent key.  Compressors whose compressor_sidechain is key + 1 detect on it from the next callback on.  A block
+        of another length than the context's frames raises GAS_ERR_FRAME_COUNT, a key out of range
+        GAS_ERR_INVALID_ARGUMENT."""
+        if frames is None:
+            self._check(self.lib.gas_sidechain_set(self.h, int(key), None, self.frames, MEM_HOST), "gas_sidechain_set")
+            return
+        f = np.ascontiguousarray(frames, dtype=np.float32)
+        assert f.ndim == 2 and f.shape[1] == 2
+        self._check(self.lib.gas_sidechain_set(self.h, int(key), _np_ptr(f), f.shape[0], MEM_HOST), "gas_sidechain_set")
+
+    def sidechain_set_raw(self, key, ptr, mem, frames=None):
+        """Raw pointer (device or host, 0 / None: a silent key); returns the status.  With MEM_DEVICE the copy is only
+        enqueued on the context's stream.  `frames` (default: the context's) is the frame count handed to the library."""
+        return self.lib.gas_sidechain_set(self.h, int(key), C.c_void_p(ptr) if ptr else None, self.frames if frames is None else int(frames), mem)
 
     @staticmethod
     def fx_line_settings_defaults(n):
@@ -930,6 +950,7 @@ class BatchedSpatializerHost:
         L.gas_host_set_effect_settings.argtypes = [vp, u32, vp]
         L.gas_host_set_effect_settings_dyn.argtypes = [vp, u32, vp]
         L.gas_host_set_effect_settings_line.argtypes = [vp, u32, vp]
+        L.gas_host_set_sidechain.argtypes = [vp, u32, vp, i32]
         L.gas_host_set_effect_settings_eq.argtypes = [vp, u32, vp]
         L.gas_host_set_effect_settings_mod.argtypes = [vp, u32, vp]
         L.gas_host_set_effect_settings_stereo.argtypes = [vp, u32, vp]
@@ -1020,6 +1041,13 @@ class BatchedSpatializerHost:
     def set_effect_dyn_settings(self, pid, settings):
         f = np.ascontiguousarray(settings, dtype=FX_DYN_SETTINGS_DTYPE).reshape(1)
         return self.lib.gas_host_set_effect_settings_dyn(self.h, pid, _np_ptr(f))
+
+    def set_sidechain(self, key, frames):
+        """Audio thread, before get_mixed_frames: key block `key` of the host's context from float32 [F][2], or None."""
+        if frames is None:
+            return self.lib.gas_host_set_sidechain(self.h, int(key), None, self.ctx.frames)
+        f = np.ascontiguousarray(frames, dtype=np.float32)
+        return self.lib.gas_host_set_sidechain(self.h, int(key), _np_ptr(f), f.shape[0])
 
     def set_effect_line_settings(self, pid, settings):
         f = np.ascontiguousarray(settings, dtype=FX_LINE_SETTINGS_DTYPE).reshape(1)

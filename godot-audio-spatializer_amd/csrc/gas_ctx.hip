@@ -177,6 +177,9 @@ struct gas_ctx {
 
 	gas_audio_frame *d_src = nullptr; // staging for GAS_MEM_HOST, lazily sized
 	size_t d_src_frames = 0;
+	// gas_sidechain_set(GAS_MEM_HOST): pinned staging per key, and the event behind each key's last copy out of it
+	gas_audio_frame *h_sidechain = nullptr; // [GAS_MAX_SIDECHAINS][frames]
+	hipEvent_t sidechain_ev[GAS_MAX_SIDECHAINS] = {};
 	gas_audio_frame *d_out = nullptr; // [C][F]
 	float *d_peaks = nullptr; // [max_sources][2]
 	float *d_partials = nullptr;
@@ -372,7 +375,7 @@ gas_fx_dyn_settings fx_dyn_settings_defaults() {
 		d.compressor_attack_us[j] = 20.0f;
 		d.compressor_release_ms[j] = 250.0f;
 		d.compressor_mix[j] = 1.0f;
-		d.reserved[j] = 0;
+		d.compressor_sidechain[j] = 0;
 	}
 	return d;
 }
@@ -2017,6 +2020,13 @@ void gas_ctx_destroy(gas_ctx *c) {
 	(void)hipHostFree(c->h_blend_upload);
 	(void)hipFree(c->st.dist_h);
 	(void)hipFree(c->st.comp_rundb);
+	(void)hipFree(c->st.sidechain);
+	(void)hipHostFree(c->h_sidechain);
+	for (hipEvent_t e : c->sidechain_ev) {
+		if (e) {
+			(void)hipEventDestroy(e);
+		}
+	}
 	for (int f = 0; f < FX_FAMILIES; f++) {
 		fx_release(c, f, true);
 	}
@@ -2137,6 +2147,13 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 		GAS_HIP(c, hipMemsetAsync(c->st.dist_h, 0, sizeof(float) * GAS_MAX_EFFECTS * 2 * N, c->stream));
 		GAS_HIP(c, hipMalloc(&c->st.comp_rundb, sizeof(float) * GAS_MAX_EFFECTS * N));
 		GAS_HIP(c, hipMemsetAsync(c->st.comp_rundb, 0, sizeof(float) * GAS_MAX_EFFECTS * N, c->stream));
+		// the compressor's sidechain keys start silent
+		GAS_HIP(c, hipMalloc(&c->st.sidechain, sizeof(gas_audio_frame) * GAS_MAX_SIDECHAINS * cfg->frames));
+		GAS_HIP(c, hipMemsetAsync(c->st.sidechain, 0, sizeof(gas_audio_frame) * GAS_MAX_SIDECHAINS * cfg->frames, c->stream));
+		GAS_HIP(c, hipHostMalloc(&c->h_sidechain, sizeof(gas_audio_frame) * GAS_MAX_SIDECHAINS * cfg->frames, hipHostMallocDefault));
+		for (hipEvent_t &e : c->sidechain_ev) {
+			GAS_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+		}
 		for (int f = 0; f < FX_FAMILIES; f++) { // the families that need no reservation for their settings: every slot starts from the engine's resource defaults
 			if (k_fx_families[f].resident) {
 				FxDev dev;
@@ -2460,6 +2477,43 @@ int gas_hrtf_blend_publish(gas_ctx *c, const uint32_t *slots, const gas_hrtf_ble
 
 int gas_fx_dyn_settings_publish(gas_ctx *c, const uint32_t *slots, const gas_fx_dyn_settings *settings, uint32_t n) {
 	return fx_publish(c, FX_DYN, slots, settings, n);
+}
+
+int gas_sidechain_set(gas_ctx *c, uint32_t key, const gas_audio_frame *frames, uint32_t frame_count, int mem) {
+	if (!c || key >= GAS_MAX_SIDECHAINS || (mem != GAS_MEM_HOST && mem != GAS_MEM_DEVICE)) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	const uint32_t F = c->cfg.frames;
+	if (frame_count != F) {
+		return GAS_ERR_FRAME_COUNT;
+	}
+	{ // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch detect on the blocks they were recorded behind
+		const int rcd = flush_deferred(c);
+		if (rcd != GAS_OK) {
+			return rcd;
+		}
+	}
+	GAS_HIP(c, hipSetDevice(c->cfg.device));
+	const size_t bytes = (size_t)F * sizeof(gas_audio_frame);
+	gas_audio_frame *dst = c->st.sidechain + (size_t)key * F;
+	if (!frames) {
+		GAS_HIP(c, hipMemsetAsync(dst, 0, bytes, c->stream));
+		return GAS_OK;
+	}
+	if (mem == GAS_MEM_DEVICE) {
+		const int rcj = join_outputs(c); // GAS_FLAG_PIPELINED_MIX: `frames` may be an earlier callback's out, still a pending sum
+		if (rcj != GAS_OK) {
+			return rcj;
+		}
+		GAS_HIP(c, hipMemcpyAsync(dst, frames, bytes, hipMemcpyDeviceToDevice, c->stream));
+		return GAS_OK;
+	}
+	gas_audio_frame *stage = c->h_sidechain + (size_t)key * F;
+	GAS_HIP(c, hipEventSynchronize(c->sidechain_ev[key])); // this key's previous upload has left the staging: a wait only while that upload is still queued (gas_amd.h)
+	std::memcpy(stage, frames, bytes);
+	GAS_HIP(c, hipMemcpyAsync(dst, stage, bytes, hipMemcpyHostToDevice, c->stream));
+	GAS_HIP(c, hipEventRecord(c->sidechain_ev[key], c->stream));
+	return GAS_OK;
 }
 
 int gas_fx_line_settings_publish(gas_ctx *c, const uint32_t *slots, const gas_fx_line_settings *settings, uint32_t n) {

@@ -91,6 +91,7 @@ struct gas_dev_state {
 	float *dist_h; // [GAS_MAX_EFFECTS][2 ears][max_sources] the distortion's one-pole state h
 	float *comp_rundb; // [GAS_MAX_EFFECTS][max_sources] the compressor's smoothed over-threshold level
 	uint32_t dyn_stride; // max_sources
+	gas_audio_frame *sidechain; // [GAS_MAX_SIDECHAINS][frames] the compressor's key blocks (gas_sidechain_set)
 	// GAS_FX_DELAY / GAS_FX_REVERB (k_fx_line.hip): settings, slot -> line table, the two line pools (nullptr until
 	// gas_ctx_reserve_fx_lines)
 	gas_fx_line_settings *line_settings; // [max_sources], by chain position

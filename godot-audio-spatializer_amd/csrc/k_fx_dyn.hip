@@ -13,14 +13,18 @@
 //       OVERDRIVE  in f64: x' = a 0.686306, z = 1 + exp(-0.75 sqrt|x'|), a = (e^x' - e^(-x' z)) / (e^x' + e^-x')
 //       WAVESHAPE  k = 2 d / (1.00001 - d), in f64: a = (1 + k) a / (1 + k |a|)
 //       y = a post + hf
-//   GAS_FX_COMPRESSOR  [ENGINE] AudioEffectCompressorInstance::process without sidechain.  Stereo-linked; the only state
-//     that reaches the output is rundb per slot and chain position (the engine's averatio / runratio / runmax / maxover /
-//     gr_meter do not: its ratio is always `ratio`).  Block constants (f64, rounded to f32):
+//   GAS_FX_COMPRESSOR  [ENGINE] AudioEffectCompressorInstance::process.  Stereo-linked; the only state that reaches the
+//     output is rundb per slot and chain position (the engine's averatio / runratio / runmax / maxover / gr_meter do
+//     not: its ratio is always `ratio`).  Block constants (f64, rounded to f32):
 //       thr = db2lin(threshold_db), at = exp(-1 / (attack_us 1e-6 sr)), rel = exp(-1 / (release_ms 1e-3 sr)), mk = db2lin(gain_db)
-//     per frame (l, r):
-//       over = max(0, 2.08136898 lin2db(max(|l|, |r|) / thr))        (silence: lin2db = -inf -> 0)
+//     per frame i, with s = compressor_sidechain[j] and x the playback's own frame:
+//       d = s == 0 ? x[i] : key[s - 1][i]        (the engine's sidechain bus: a key block of the context, gas_sidechain_set)
+//       over = max(0, 2.08136898 lin2db(max(|d.l|, |d.r|) / thr))    (silence: lin2db = -inf -> 0)
 //       rundb = over + (over > rundb ? at : rel) (rundb - over)
 //       g = db2lin(-rundb (ratio - 1) / ratio),   y = ((x g) mk) mix + x (1 - mix) per ear
+//     The detector alone reads the key: the gain always lands on x, and rundb is the one state whatever s is (changing s
+//     between blocks keeps it).  The peak is divided by the source's own thr and goes through the one logf either way, so
+//     a key equal to the source's row gives the keyless result to the bit.
 //   db2lin(x) = exp(x 0.11512925464970228), lin2db(x) = log(x) 8.685889638065035.
 //
 // Geometry (wave64, NW = 8 waves per workgroup): S sources per workgroup -- 32 for the distortion (wave 0's lane =
@@ -28,16 +32,22 @@
 // with coalesced 16-byte loads by all waves (the next tile's loads in flight during the current one, as k_biquad_mix
 // does), and every tile runs in three phases:
 //   1. across all waves: what does not depend on the recurrence -- the distortion's input products x ic, the
-//      compressor's detector (peak, logf, scale, clamp);
+//      compressor's detector (peak of the source's frame or of its key's, logf, scale, clamp);
 //   2. wave 0, one serial lane per recurrence, in the engine's order (not scanned: keep_hf_hz puts c next to 1, where scans leave
 //      the parity band) -- per step only add / mul / select for the distortion, compare / select / sub / mul / add for
 //      the compressor;
 //   3. across all waves again: the waveshaper and output of the distortion (one source per wave and step of the loop, so
 //      the mode is wave-uniform), the compressor's gain (expf) and output.
+// Sidechain keys: the key frames of a tile are the same for every source of the workgroup, so they are staged once per
+// tile as kpk[key][frame] = max(|l|, |r|) (GAS_MAX_SIDECHAINS x KF floats, 1 KiB) by the first 256 threads, each with one
+// 8-byte load a tile ahead like the rows, instead of a global read per (source, frame).  Whether any source of the
+// workgroup names a key is a ballot every wave takes over the same 64 settings words: workgroup-uniform, and a launch
+// without keys does nothing of this beyond that branch.
 // MEASURED (profiles/r04_fx_dyn_notes.md): with one wave per workgroup the per-sample transcendentals of phases 1 and 3,
 // not the recurrence, bounded the stage (275 us at 256 and at 8192 sources); eight waves share them.
 // No FMA contraction: the recurrences and products round like the engine's separate f32 operations.
 #include <cmath>
+#include <type_traits>
 
 #include "gas_internal.h"
 
@@ -52,12 +62,17 @@ constexpr int PARTS = COLS / 4; // 16-byte pieces of one source's tile row
 constexpr int OW = KF + 1; // compressor detector row stride: serial lane s reads bank (s + k) % 32
 constexpr int NW = 8; // waves per workgroup
 constexpr int NT = 64 * NW;
+// compressor key peaks kpk[key][frame] (behind the detector rows in `work`), row stride KF: phase 1's thread = (source, frame) puts one source on each
+// 32-lane half of a wave, so a half reads ONE row at banks f % 32, all distinct (two halves never conflict; sources on
+// the same key read the same addresses); the staging thread (key, frame) = (tid / KF, tid % KF) writes the same way
+constexpr int KEYS = GAS_MAX_SIDECHAINS;
+static_assert(KEYS * KF <= NT, "one staging thread per (key, frame) of a tile");
 
 template <int KIND>
 struct Geo {
 	static constexpr int S = KIND == GAS_FX_DISTORTION ? 32 : 64;
 	static constexpr int LOADS = S * PARTS / NT; // staging loads per thread per tile
-	static constexpr int WORK = KIND == GAS_FX_DISTORTION ? S * ROW : S * OW;
+	static constexpr int WORK = KIND == GAS_FX_DISTORTION ? S * ROW : S * OW + GAS_MAX_SIDECHAINS * KF; // the compressor's: detector rows, then the key peaks
 };
 
 // constants per source in LDS (phases 1 and 3)
@@ -105,7 +120,7 @@ __global__ __launch_bounds__(NT) void k_fx_dyn(gas_group_args g, gas_dev_state s
 	__shared__ float tile[2][S * ROW];
 	__shared__ float work[Geo<KIND>::WORK];
 	__shared__ float cst[DIST ? DC_N : CC_N][S];
-	__shared__ int mode_s[S];
+	__shared__ int mode_s[S]; // the distortion's mode; the compressor's sidechain (0: none, k: key k - 1)
 
 	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 	const uint32_t e0 = blockIdx.x * S;
@@ -117,6 +132,11 @@ __global__ __launch_bounds__(NT) void k_fx_dyn(gas_group_args g, gas_dev_state s
 	const uint32_t slot = g.slots ? g.slots[ec] : g.slot_base + ec;
 	const gas_fx_dyn_settings *P = st.dyn + slot;
 	const size_t stride = st.dyn_stride;
+	// the compressor's sidechain word of this lane's source, in every wave: issued here, looked at behind the staging loads
+	[[maybe_unused]] uint32_t side = 0;
+	if constexpr (!DIST) {
+		side = valid ? P->compressor_sidechain[j] : 0u;
+	}
 
 	// block constants and state of this lane's recurrence (wave 0)
 	float c = 0.0f, at = 0.0f, rel = 0.0f, h = 0.0f;
@@ -177,6 +197,27 @@ __global__ __launch_bounds__(NT) void k_fx_dyn(gas_group_args g, gas_dev_state s
 	for (int q = 0; q < LOADS; q++) {
 		pre[q] = *reinterpret_cast<const float4 *>(ld[q]);
 	}
+	// sidechain keys: the compressor instantiation only
+	[[maybe_unused]] bool any_key = false, key_thread = false;
+	[[maybe_unused]] uint32_t koff = 0;
+	[[maybe_unused]] float2 kpre = make_float2(0.0f, 0.0f);
+	[[maybe_unused]] float *const kpk = work + S * OW;
+	[[maybe_unused]] const float2 *const keys = reinterpret_cast<const float2 *>(st.sidechain);
+	if constexpr (!DIST) {
+		// lane = source in every wave: all eight ballots see the same 64 words.  Behind the staging loads, so that no
+		// wave holds those back for the settings word
+		side = side > (uint32_t)KEYS ? 0u : side; // (a publish never lets such a value through)
+		any_key = __ballot(side != 0) != 0;
+		if (wave == 0) {
+			mode_s[me] = (int)side;
+		}
+		// key staging: thread (key, frame) of the tile, its frame loaded a tile ahead
+		key_thread = any_key && tid < KEYS * KF;
+		koff = (uint32_t)(tid / KF) * F + tid % KF; // < GAS_MAX_SIDECHAINS * F for a key thread
+		if (key_thread) {
+			kpre = keys[koff];
+		}
+	}
 
 	const uint32_t n_tiles = F / KF;
 	for (uint32_t tl = 0; tl < n_tiles; tl++) {
@@ -188,10 +229,21 @@ __global__ __launch_bounds__(NT) void k_fx_dyn(gas_group_args g, gas_dev_state s
 			*reinterpret_cast<float2 *>(d) = make_float2(pre[q].x, pre[q].y);
 			*reinterpret_cast<float2 *>(d + 2) = make_float2(pre[q].z, pre[q].w);
 		}
+		if constexpr (!DIST) {
+			if (key_thread) { // last read in phase 1 of the previous tile, three barriers ago
+				const float l = fabsf(kpre.x), r = fabsf(kpre.y);
+				kpk[tid] = l > r ? l : r; // [tid / KF][tid % KF]
+			}
+		}
 		if (tl + 1 < n_tiles) {
 #pragma unroll
 			for (int q = 0; q < LOADS; q++) {
 				pre[q] = *reinterpret_cast<const float4 *>(ld[q] + (size_t)(tl + 1) * COLS);
+			}
+			if constexpr (!DIST) {
+				if (key_thread) {
+					kpre = keys[koff + (tl + 1) * KF];
+				}
 			}
 		}
 		__syncthreads();
@@ -202,14 +254,26 @@ __global__ __launch_bounds__(NT) void k_fx_dyn(gas_group_args g, gas_dev_state s
 				work[s * ROW + lane] = tb[s * ROW + lane] * cst[DC_IC][s];
 			}
 		} else {
-			for (int it = 0; it < S * KF / NT; it++) { // thread = (source, frame)
-				const int idx = it * NT + tid;
-				const int s = idx / KF, f = idx % KF;
-				const float l = fabsf(tb[s * ROW + 2 * f]), r = fabsf(tb[s * ROW + 2 * f + 1]);
-				const float peak = l > r ? l : r;
-				float over = 2.08136898f * (logf(peak / cst[CC_THR][s]) * 8.685889638065035f);
-				over = over < 0.0f ? 0.0f : over; // (-inf for silence)
-				work[s * OW + f] = over;
+			auto detect = [&](auto keyed) { // the keyless loop is the one loop there was: the choice is made outside it
+				for (int it = 0; it < S * KF / NT; it++) { // thread = (source, frame)
+					const int idx = it * NT + tid;
+					const int s = idx / KF, f = idx % KF;
+					const float l = fabsf(tb[s * ROW + 2 * f]), r = fabsf(tb[s * ROW + 2 * f + 1]);
+					float peak = l > r ? l : r;
+					if constexpr (decltype(keyed)::value) {
+						const int k = mode_s[s];
+						const float key_peak = kpk[((k != 0 ? k : 1) - 1) * KF + f];
+						peak = k != 0 ? key_peak : peak;
+					}
+					float over = 2.08136898f * (logf(peak / cst[CC_THR][s]) * 8.685889638065035f);
+					over = over < 0.0f ? 0.0f : over; // (-inf for silence)
+					work[s * OW + f] = over;
+				}
+			};
+			if (any_key) {
+				detect(std::true_type());
+			} else {
+				detect(std::false_type());
 			}
 		}
 		__syncthreads();

@@ -38,6 +38,7 @@
 #pragma weak gas_fx_filter_settings_publish
 #pragma weak gas_hrtf_blend_publish
 #pragma weak gas_stream_get_loop
+#pragma weak gas_sidechain_set
 
 namespace {
 
@@ -586,6 +587,13 @@ int gas_host_set_effect_settings(gas_host *h, uint32_t id, const gas_fx_settings
 
 int gas_host_set_effect_settings_dyn(gas_host *h, uint32_t id, const gas_fx_dyn_settings *settings) {
 	return h ? h->queue_settings(id, settings, gas_fx_dyn_settings_valid, Command::FX_DYN_SETTINGS, &Command::fx_dyn_settings) : GAS_ERR_BAD_SLOT;
+}
+
+int gas_host_set_sidechain(gas_host *h, uint32_t key, const gas_audio_frame *frames, int frame_count) {
+	if (!h || !gas_sidechain_set || frame_count < 0) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	return gas_sidechain_set(h->ctx, key, frames, (uint32_t)frame_count, GAS_MEM_HOST);
 }
 
 int gas_host_set_effect_settings_line(gas_host *h, uint32_t id, const gas_fx_line_settings *settings) {

@@ -17,7 +17,7 @@
  *     The slot allocator takes a lock; a free takes effect at the audio thread's next block boundary; a slot is
  *     handed to the audio thread by the caller (the first callback whose list names it), never before alloc returned.
  *   - gas_process_block*, gas_process_frames_1, gas_mix_channel_1, gas_source_set_draining, gas_source_bind_stream,
- *     gas_stream_positions : audio thread only, one caller at a time, never re-entrant per context.
+ *     gas_stream_positions, gas_sidechain_set : audio thread only, one caller at a time, never re-entrant per context.
  *   - everything else      : one thread at a time and not concurrently with the audio-thread entries -- the main
  *     thread while audio is stopped, or the audio thread itself between callbacks.
  */
@@ -41,6 +41,7 @@ extern "C" {
 #define GAS_HRTF_TAPS 256
 #define GAS_ER_TAPS 8
 #define GAS_MAX_EFFECTS 4
+#define GAS_MAX_SIDECHAINS 8 /* key blocks a context holds for the compressor's sidechain (gas_sidechain_set) */
 
 typedef struct gas_ctx gas_ctx;
 
@@ -88,7 +89,7 @@ typedef enum gas_effect_kind {
 	/* The engine's first nonlinear and dynamics kinds; settings per playback and chain position: gas_fx_dyn_settings.
 	 * (10 is not assigned: an effect kind the library does not know is GAS_ERR_INVALID_ARGUMENT / _UNSUPPORTED_CHAIN.) */
 	GAS_FX_DISTORTION = 11, /* [ENGINE] AudioEffectDistortion: per-ear one-pole split, the low band shaped by `mode` */
-	GAS_FX_COMPRESSOR = 12, /* [ENGINE] AudioEffectCompressor without sidechain: stereo-linked detector, one gain per frame */
+	GAS_FX_COMPRESSOR = 12, /* [ENGINE] AudioEffectCompressor: stereo-linked detector on the playback's own frames or on a sidechain key (gas_sidechain_set), one gain per frame */
 	/* The engine's time-domain kinds with long per-instance memory ("lines", reserved with gas_ctx_reserve_fx_lines);
 	 * settings per playback and chain position: gas_fx_line_settings. */
 	GAS_FX_DELAY = 13, /* [ENGINE] AudioEffectDelay: two panned taps and a low-passed feedback echo, ears independent */
@@ -286,7 +287,9 @@ typedef struct gas_fx_settings {
 /* Settings of the GAS_FX_DISTORTION / GAS_FX_COMPRESSOR effects of one playback, by chain position like gas_fx_settings:
  * position j is read only when effect j of the playback's chain is one of those kinds.  Read once per block (no ramps).
  * A slot that never got settings has the engine's resource defaults, given per field.  The compressor's `sidechain`
- * bus is not supported: a playback whose compressor uses one stays on the engine's own path. */
+ * bus is compressor_sidechain[j]: 0 (the default) detects on the playback's own frames, k in 1 .. GAS_MAX_SIDECHAINS
+ * detects on key block k - 1 of the context (gas_sidechain_set); the gain is applied to the playback's own frames either
+ * way, and the state (rundb) is the same one whatever the value is. */
 typedef struct gas_fx_dyn_settings {
 	int32_t distortion_mode[GAS_MAX_EFFECTS]; /* GAS_DISTORTION_*, default CLIP */
 	float distortion_pre_gain_db[GAS_MAX_EFFECTS]; /* default 0 */
@@ -299,7 +302,7 @@ typedef struct gas_fx_dyn_settings {
 	float compressor_attack_us[GAS_MAX_EFFECTS]; /* > 0, default 20 */
 	float compressor_release_ms[GAS_MAX_EFFECTS]; /* > 0, default 250 */
 	float compressor_mix[GAS_MAX_EFFECTS]; /* default 1 */
-	uint32_t reserved[GAS_MAX_EFFECTS];
+	uint32_t compressor_sidechain[GAS_MAX_EFFECTS]; /* 0 .. GAS_MAX_SIDECHAINS, default 0: no sidechain */
 } gas_fx_dyn_settings;
 
 /* Settings of the GAS_FX_DELAY / GAS_FX_REVERB effects of one playback, by chain position like gas_fx_dyn_settings:
@@ -451,9 +454,27 @@ int gas_params_publish_batch(gas_ctx *ctx, const uint32_t *slots, const gas_para
  * next gas_process_block.  Physics thread, like gas_params_publish. */
 int gas_fx_settings_publish(gas_ctx *ctx, const uint32_t *slots, const gas_fx_settings *settings, uint32_t n);
 /* The same for gas_fx_dyn_settings: latest wins, snapshotted at the start of the next gas_process_block, physics thread.
- * A distortion_mode outside 0..4 or a compressor ratio, attack or release that is not > 0 (at any position) is
- * GAS_ERR_INVALID_ARGUMENT, and nothing of the call is taken. */
+ * A distortion_mode outside 0..4, a compressor ratio, attack or release that is not > 0, or a compressor_sidechain
+ * above GAS_MAX_SIDECHAINS (at any position, used or not) is GAS_ERR_INVALID_ARGUMENT, and nothing of the call is taken. */
 int gas_fx_dyn_settings_publish(gas_ctx *ctx, const uint32_t *slots, const gas_fx_dyn_settings *settings, uint32_t n);
+/* The compressor's sidechain keys.  The context owns GAS_MAX_SIDECHAINS key blocks of cfg.frames AudioFrames in device
+ * memory, allocated and zeroed by gas_ctx_create with the pinned staging the host form needs (nothing is allocated
+ * here).  The call replaces the block of `key`; frames == NULL zeroes it (a silent key: over = 0, the compressor
+ * releases).  With GAS_MEM_HOST `frames` has been consumed when the call returns: it is copied into the key's pinned
+ * staging block and uploaded in stream order.  The call does not wait for that upload, but it does wait for the SAME
+ * key's previous host upload if that one is still queued behind earlier work of the stream (device-memory callbacks
+ * not yet finished): up to the GPU time of what is queued, nothing when the stream has caught up, as it has after any
+ * GAS_MEM_HOST callback.  How often that happens in a running game has not been measured.  With GAS_MEM_DEVICE the call only
+ * enqueues a device copy in the context's stream order, so the buffer must stay valid until that point of the stream
+ * -- it may be the `out` of an earlier callback on the same stream, which is how one of the caller's own bus mixes
+ * becomes a key.  Audio thread, between callbacks.  A key keeps its block until it is replaced: a callback with no
+ * gas_sidechain_set in front of it detects on the same block again, and every compressor stage of every callback
+ * enqueued after the call reads the new block.  Callbacks recorded or deferred before the call (GAS_FLAG_BATCHED_LAUNCH)
+ * run first; their results are unchanged.  Keys are context state: gas_source_reset and gas_source_free do not touch
+ * them.  key >= GAS_MAX_SIDECHAINS, a bad `mem` or ctx == NULL is GAS_ERR_INVALID_ARGUMENT, frame_count != cfg.frames
+ * GAS_ERR_FRAME_COUNT, a HIP failure GAS_ERR_DEVICE; an error changes nothing.  A gas_multi caller sets keys per shard
+ * (gas_multi_shard). */
+int gas_sidechain_set(gas_ctx *ctx, uint32_t key, const gas_audio_frame *frames, uint32_t frame_count, int mem);
 /* The same for gas_fx_line_settings: latest wins, snapshotted at the start of the next gas_process_block, physics
  * thread.  A value outside the ranges given at gas_fx_line_settings (at any position) is GAS_ERR_INVALID_ARGUMENT, and
  * nothing of the call is taken. */

@@ -17,7 +17,7 @@
  *     called from any number of threads (main, physics) at any time, concurrently with the audio thread.  They only
  *     queue commands / flip per-playback atomics; a start or a parameter set takes effect at the top of the next
  *     callback, in the order issued (one parameter snapshot per callback, audio_spatializer.cpp:328).
- *   - gas_host_get_mixed_frames is the audio thread: one caller.  It is the only thread that uses the context's slot
+ *   - gas_host_get_mixed_frames and gas_host_set_sidechain are the audio thread: one caller.  It is the only thread that uses the context's slot
  *     API (gas_source_alloc / free / set_draining / bind_stream) and gas_process_block, as gas_amd.h requires; a start
  *     that cannot get a slot (or names an unknown device stream) simply never becomes active.
  *   - nodes are deleted on a control thread (deferred delete, audio_spatializer.cpp:538-547); the stream callback of a
@@ -63,6 +63,10 @@ int gas_host_set_effect_settings(gas_host *host, uint32_t id, const gas_fx_setti
 /* The same for the playback's GAS_FX_DISTORTION / GAS_FX_COMPRESSOR settings (gas_fx_dyn_settings), through the same
  * queue; settings gas_fx_dyn_settings_publish would refuse are GAS_ERR_INVALID_ARGUMENT here.  Control thread. */
 int gas_host_set_effect_settings_dyn(gas_host *host, uint32_t id, const gas_fx_dyn_settings *settings);
+/* The compressor's sidechain keys of the host's context: gas_sidechain_set(ctx, key, frames, frame_count, GAS_MEM_HOST),
+ * with its statuses (frames == NULL: a silent key).  AUDIO THREAD ONLY, before gas_host_get_mixed_frames: the callback's
+ * compressors whose compressor_sidechain is key + 1 detect on this block, and on it again until it is replaced. */
+int gas_host_set_sidechain(gas_host *host, uint32_t key, const gas_audio_frame *frames, int frame_count);
 /* The same for the playback's GAS_FX_DELAY / GAS_FX_REVERB settings (gas_fx_line_settings), through the same queue;
  * settings gas_fx_line_settings_publish would refuse are GAS_ERR_INVALID_ARGUMENT here.  Control thread. */
 int gas_host_set_effect_settings_line(gas_host *host, uint32_t id, const gas_fx_line_settings *settings);

@@ -267,6 +267,10 @@ assert C.sizeof(HrtfBlend) == 32
 
 MEM_HOST = 0
 MEM_DEVICE = 1
+# gas_pcm_format (gas_stream_create)
+PCM_S16 = 0
+PCM_F32 = 1
+PCM_IMA_ADPCM = 2
 # gas_loop_mode (gas_stream_set_loop)
 LOOP_DISABLED = 0
 LOOP_FORWARD = 1
@@ -778,14 +782,22 @@ class SpatializerContext:
         return out, reverb
 
     # ---- device-resident streams ----
-    def stream_create(self, pcm):
-        """pcm: int16 or float32 array [frames] (mono) or [frames][2] (stereo)."""
+    def stream_create(self, pcm, format=None, channels=None, frames=None):
+        """pcm: int16 or float32 array [frames] (mono) or [frames][2] (stereo); or, with format=PCM_IMA_ADPCM, channels
+        and frames, the uint8 codes as include/gas_amd.h lays them out (((frames + 1) // 2) * channels bytes)."""
         a = np.ascontiguousarray(pcm)
-        fmt = 0 if a.dtype == np.int16 else 1
-        if fmt == 1:
+        sid = C.c_uint32()
+        if format is not None or a.dtype == np.uint8:
+            if a.dtype != np.uint8 or format is None or channels is None or frames is None:
+                raise ValueError("encoded data are a uint8 array passed with format, channels and frames")
+            if int(channels) > 0 and a.size < ((int(frames) + 1) // 2) * int(channels):
+                raise ValueError("fewer bytes than ((frames + 1) // 2) * channels")
+            self._check(self.lib.gas_stream_create(self.h, _np_ptr(a), int(format), int(channels), int(frames), C.byref(sid)), "gas_stream_create")
+            return sid.value
+        fmt = PCM_S16 if a.dtype == np.int16 else PCM_F32
+        if fmt == PCM_F32:
             a = a.astype(np.float32)
         ch = 1 if a.ndim == 1 else a.shape[1]
-        sid = C.c_uint32()
         self._check(self.lib.gas_stream_create(self.h, _np_ptr(a), fmt, ch, a.shape[0], C.byref(sid)), "gas_stream_create")
         return sid.value
 
@@ -801,6 +813,12 @@ class SpatializerContext:
         mode, b, e = C.c_int32(), C.c_uint64(), C.c_uint64()
         self._check(self.lib.gas_stream_get_loop(self.h, int(sid), C.byref(mode), C.byref(b), C.byref(e)), "gas_stream_get_loop")
         return mode.value, b.value, e.value
+
+    def stream_get_info(self, sid):
+        """(frames, channels, format) of a stream; format is a PCM_* constant."""
+        n, ch, fmt = C.c_uint64(), C.c_uint32(), C.c_int32()
+        self._check(self.lib.gas_stream_get_info(self.h, int(sid), C.byref(n), C.byref(ch), C.byref(fmt)), "gas_stream_get_info")
+        return n.value, ch.value, fmt.value
 
     def stream_destroy(self, sid):
         self._check(self.lib.gas_stream_destroy(self.h, sid), "gas_stream_destroy")

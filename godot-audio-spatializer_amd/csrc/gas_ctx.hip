@@ -222,6 +222,8 @@ struct gas_ctx {
 	bool stream_all_hrtf = false;
 	bool stream_rows_first = getenv("GAS_STREAM_ROWS_FIRST") != nullptr && atoi(getenv("GAS_STREAM_ROWS_FIRST")) != 0; // development aid: plain [HRTF] stream lists sample rows first too (tools/time_stream_loops.py compares the routes)
 	bool stream_any_looped = false;
+	bool stream_any_adpcm = false; // the list holds a GAS_PCM_IMA_ADPCM playback: rows first, k_sample_adpcm behind k_sample_sources
+	bool adpcm_span = getenv("GAS_ADPCM_SPAN") == nullptr || atoi(getenv("GAS_ADPCM_SPAN")) != 0; // development aid: 0 = every load decodes from its checkpoint (k_sample_adpcm.hip; tools/time_stream_adpcm.py and the tests compare the paths)
 	bool stream_params_touched = false; // a parameter publish may have changed pitch_scale: re-validate
 
 	// gas_calc_spatialization staging (physics thread)
@@ -2740,11 +2742,33 @@ static inline void stream_rows_sync_back_fwd(gas_ctx *c) {
 }
 
 int gas_stream_create(gas_ctx *c, const void *pcm, int format, uint32_t channels, uint64_t frames, uint32_t *out_stream) {
-	if (!c || !pcm || !out_stream || (format != GAS_PCM_S16 && format != GAS_PCM_F32) || (channels != 1 && channels != 2) || frames == 0) {
+	if (!c || !pcm || !out_stream || (format != GAS_PCM_S16 && format != GAS_PCM_F32 && format != GAS_PCM_IMA_ADPCM) || (channels != 1 && channels != 2) || frames == 0) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
 	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	const size_t bytes = (size_t)frames * channels * (format == GAS_PCM_S16 ? 2 : 4);
+	size_t bytes = (size_t)frames * channels * (format == GAS_PCM_S16 ? 2 : 4);
+	std::vector<uint8_t> adpcm; // codes padded to whole chunks ++ checkpoint table (gas_internal.h)
+	if (format == GAS_PCM_IMA_ADPCM) {
+		bytes = (size_t)gas_adpcm_device_bytes(frames, channels);
+		try {
+			adpcm.assign(bytes, 0);
+		} catch (const std::exception &) { // a length no host can stage
+			return GAS_ERR_OUT_OF_MEMORY;
+		}
+		std::memcpy(adpcm.data(), pcm, (size_t)((frames + 1) / 2) * channels);
+		gas_adpcm_ckpt *table = reinterpret_cast<gas_adpcm_ckpt *>(adpcm.data() + gas_adpcm_table_offset(frames, channels));
+		for (uint32_t ch = 0; ch < channels; ch++) { // decode once, keeping the state in front of every chunk
+			int32_t predictor = 0, step_index = 0;
+			for (uint64_t i = 0; i < frames; i++) {
+				if (i % GAS_ADPCM_CHUNK == 0) {
+					table[(i / GAS_ADPCM_CHUNK) * channels + ch] = gas_adpcm_ckpt{ (int16_t)predictor, (uint8_t)step_index, 0 };
+				}
+				const uint32_t n = (adpcm[(i >> 1) * channels + ch] >> ((i & 1) * 4)) & 15u;
+				gas_adpcm_step(predictor, step_index, n, gas_adpcm_step_size((uint32_t)step_index));
+			}
+		}
+		pcm = adpcm.data();
+	}
 	gas_ctx::StreamInfo si;
 	GAS_HIP(c, hipMalloc(&si.d_pcm, bytes));
 	hipError_t e = hipMemcpy(si.d_pcm, pcm, bytes, hipMemcpyHostToDevice);
@@ -3026,8 +3050,10 @@ int gas_process_block_streams(gas_ctx *c, const uint32_t *slots, uint32_t n, uin
 		c->stream_all_hrtf = n > 0;
 		c->stream_any_resampled = false;
 		c->stream_any_looped = false;
+		c->stream_any_adpcm = false;
 		for (uint32_t i = 0; i < n; i++) {
 			const gas_cursor &cur = c->h_cursors[slots[i]];
+			c->stream_any_adpcm = c->stream_any_adpcm || (cur.pcm && (cur.format_channels >> 8) == GAS_PCM_IMA_ADPCM);
 			gas_ctx::StreamRow &r = c->stream_rows[i];
 			r.remaining = cur.pcm && cur.frames > cur.pos ? cur.frames - cur.pos : 0;
 			r.has_frames = cur.pcm ? cur.has_frames : 0;
@@ -3112,7 +3138,8 @@ int gas_process_block_streams(gas_ctx *c, const uint32_t *slots, uint32_t n, uin
 	// (GAS_FLAG_HRTF_BLEND_FADE: the stream-sampling form has no registers left for the fade, DESIGN.md 3.4 -- rows first)
 	// (gas_stream_set_loop: the cross-fade form has no registers left for the looped branch either, DESIGN.md 3.4 -- rows first)
 	const bool loops_fused = !c->stream_any_looped || (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) == 0;
-	const bool all_hrtf = c->stream_all_hrtf && !c->stream_any_resampled && !fade_on(c) && loops_fused && !c->stream_rows_first; // the fused prologue samples plain playbacks only
+	// (GAS_PCM_IMA_ADPCM: the fused prologues read uncompressed frames only -- rows first, like a resampled playback)
+	const bool all_hrtf = c->stream_all_hrtf && !c->stream_any_resampled && !c->stream_any_adpcm && !fade_on(c) && loops_fused && !c->stream_rows_first; // the fused prologue samples plain playbacks only
 	if (!all_hrtf) {
 		const size_t need = (size_t)n * F;
 		if (need > c->d_src_frames) {
@@ -3129,6 +3156,9 @@ int gas_process_block_streams(gas_ctx *c, const uint32_t *slots, uint32_t n, uin
 		}
 		if (n > 0) {
 			hipError_t e = gas_launch_sample_sources(c->stream, c->d_cursors, c->d_stream_slots, n, F, c->d_fade_env, c->d_src, c->stream_any_resampled ? c->d_stream_inc : nullptr);
+			if (e == hipSuccess && c->stream_any_adpcm) {
+				e = gas_launch_sample_adpcm(c->stream, c->d_cursors, c->d_stream_slots, n, F, c->d_fade_env, c->d_src, c->stream_any_resampled ? c->d_stream_inc : nullptr, c->adpcm_span);
+			}
 			if (e != hipSuccess) {
 				c->last_err = hipGetErrorString(e);
 				return fail(GAS_ERR_DEVICE);

@@ -199,6 +199,116 @@ __host__ __device__ inline uint32_t gas_loop_fold(const gas_loop_win &w, uint32_
 	return t < w.L ? t : w.P - 1 - t;
 }
 
+// GAS_PCM_IMA_ADPCM (gas_amd.h): IMA/DVI ADPCM, the public standard.  A stream's device allocation holds the 4-bit codes
+// padded with zeros to whole chunks of GAS_ADPCM_CHUNK frames (16 bytes per chunk and channel, so every chunk starts on
+// a 16-byte boundary), then one checkpoint per chunk and channel: the decoder state in front of the chunk's first frame.
+// Any frame is then at most GAS_ADPCM_CHUNK steps away from a known state, which is what lets the sampler read at
+// arbitrary indices (loops, ping-pong, resampler taps).  20 bytes per 32 samples: 5 bits per sample.
+#define GAS_ADPCM_CHUNK 32
+#define GAS_ADPCM_STEPS 89
+struct alignas(4) gas_adpcm_ckpt {
+	int16_t predictor;
+	uint8_t step_index;
+	uint8_t pad;
+};
+static_assert(sizeof(gas_adpcm_ckpt) == 4, "gas_adpcm_ckpt layout");
+
+__host__ __device__ inline uint64_t gas_adpcm_chunks(uint64_t frames) {
+	return (frames + GAS_ADPCM_CHUNK - 1) / GAS_ADPCM_CHUNK;
+}
+// byte offset of the checkpoint table [chunk][channel] behind the codes
+__host__ __device__ inline uint64_t gas_adpcm_table_offset(uint64_t frames, uint32_t channels) {
+	return gas_adpcm_chunks(frames) * (GAS_ADPCM_CHUNK / 2) * channels;
+}
+__host__ __device__ inline uint64_t gas_adpcm_device_bytes(uint64_t frames, uint32_t channels) {
+	return gas_adpcm_table_offset(frames, channels) + gas_adpcm_chunks(frames) * channels * sizeof(gas_adpcm_ckpt);
+}
+
+// The standard step-size table, 7 ... 32767.
+__host__ __device__ inline int32_t gas_adpcm_step_size(uint32_t step_index) {
+	static constexpr uint16_t STEP[GAS_ADPCM_STEPS] = { 7, 8, 9, 10, 11, 12, 13, 14, 16, 17, 19, 21, 23, 25, 28, 31, 34, 37, 41, 45, 50, 55, 60, 66, 73, 80, 88, 97, 107, 118, 130, 143, 157, 173, 190, 209, 230, 253, 279, 307, 337, 371, 408, 449, 494, 544, 598, 658, 724, 796, 876, 963, 1060, 1166, 1282, 1411, 1552, 1707, 1878, 2066, 2272, 2499, 2749, 3024, 3327, 3660, 4026, 4428, 4871, 5358, 5894, 6484, 7132, 7845, 8630, 9493, 10442, 11487, 12635, 13899, 15289, 16818, 18500, 20350, 22385, 24623, 27086, 29794, 32767 };
+	return STEP[step_index];
+}
+
+// One decoder step, the only definition of the arithmetic: code n moves (predictor, step_index); the sample is the new
+// predictor.  `step` is gas_adpcm_step_size(step_index), looked up by the caller (the kernel keeps the table in LDS).
+__host__ __device__ inline void gas_adpcm_step(int32_t &predictor, int32_t &step_index, uint32_t n, int32_t step) {
+	const int32_t m = (int32_t)(n & 7);
+	int32_t si = step_index + (m < 4 ? -1 : 2 * (m - 3)); // INDEX = {-1, -1, -1, -1, 2, 4, 6, 8}
+	si = si < 0 ? 0 : si;
+	step_index = si > GAS_ADPCM_STEPS - 1 ? GAS_ADPCM_STEPS - 1 : si;
+	int32_t diff = step >> 3;
+	diff += (n & 1) ? step >> 2 : 0;
+	diff += (n & 2) ? step >> 1 : 0;
+	diff += (n & 4) ? step : 0;
+	int32_t p = predictor + ((n & 8) ? -diff : diff);
+	p = p < -32768 ? -32768 : p;
+	predictor = p > 32767 ? 32767 : p;
+}
+
+// Stream indices [lo, hi] that contain m(k) for every unrolled index k in [k0, k1] (0 <= k0 <= k1) of a looped cursor:
+// the indices themselves in front of the loop; inside it the run they map to while no seam falls into it, else the
+// whole loop.
+__host__ __device__ inline void gas_adpcm_loop_bounds(const gas_cursor &c, uint64_t k0, uint64_t k1, uint64_t &lo, uint64_t &hi) {
+	const uint64_t b = c.loop_begin;
+	if (k1 < b) {
+		lo = k0;
+		hi = k1;
+		return;
+	}
+	const uint64_t L = c.loop_len, P = c.loop_mode == GAS_LOOP_PINGPONG ? 2 * L : L;
+	const uint64_t in0 = k0 > b ? k0 : b;
+	const uint64_t t0 = (in0 - b) % P, t1 = t0 + (k1 - in0); // t runs t0 .. t1 before it wraps
+	uint64_t mlo = b, mhi = b + L - 1;
+	if (t1 < L) { // forward run
+		mlo = b + t0;
+		mhi = b + t1;
+	} else if (t0 >= L && t1 < P) { // backward run of a ping-pong loop
+		mlo = b + (P - 1 - t1);
+		mhi = b + (P - 1 - t0);
+	}
+	lo = k0 < b ? k0 : mlo;
+	hi = mhi;
+}
+
+// Bounds of the stream indices gas_sample_row (gas_sample_row.h) can load for this cursor and callback, hi < frames;
+// false: it loads none.  What k_sample_adpcm.hip decodes ahead of a row.
+__host__ __device__ inline bool gas_adpcm_span_bounds(const gas_cursor &c, uint32_t F, uint64_t inc, uint64_t &lo, uint64_t &hi) {
+	if (!c.has_frames) {
+		return false;
+	}
+	int64_t k0, k1;
+	if (c.resampled) { // taps q - 3 .. q of the fresh outputs, and of the regenerated lookahead once there is one
+		const uint64_t fresh = F - GAS_LOOKAHEAD_BUFFER_SIZE;
+		k0 = (int64_t)(c.fp_pos >> 16) - 3;
+		k1 = (int64_t)((c.fp_pos + fresh * inc) >> 16);
+		if (c.resampled == 2) {
+			const int64_t p0 = (int64_t)((c.fp_prev_pos + fresh * c.prev_inc) >> 16) - 3, p1 = (int64_t)((c.fp_prev_pos + (uint64_t)F * c.prev_inc) >> 16);
+			k0 = p0 < k0 ? p0 : k0;
+			k1 = p1 > k1 ? p1 : k1;
+		}
+	} else { // the window
+		k0 = (int64_t)c.pos - GAS_LOOKAHEAD_BUFFER_SIZE;
+		k1 = k0 + (int64_t)F - 1;
+	}
+	if (k0 < (int64_t)c.start) {
+		k0 = (int64_t)c.start;
+	}
+	if (!c.loop_mode && k1 > (int64_t)c.frames - 1) {
+		k1 = (int64_t)c.frames - 1;
+	}
+	if (k1 < k0) {
+		return false;
+	}
+	if (c.loop_mode) {
+		gas_adpcm_loop_bounds(c, (uint64_t)k0, (uint64_t)k1, lo, hi);
+	} else {
+		lo = (uint64_t)k0;
+		hi = (uint64_t)k1;
+	}
+	return true;
+}
+
 // What a launch group (one kind/chain) needs.
 struct gas_group_args {
 	const gas_audio_frame *src; // [n_rows_total][F]
@@ -346,6 +456,7 @@ hipError_t gas_launch_fx_filter(hipStream_t stream, const gas_group_args &g, con
 hipError_t gas_launch_scatter_params(hipStream_t stream, gas_params *table, const gas_params *upload, const uint32_t *slots, uint32_t n);
 hipError_t gas_launch_calc_spatialization(hipStream_t stream, const gas_spatializer3d_config *cfgs, const uint32_t *cfg_index, const gas_source_pose *poses, const gas_listener *listeners, uint32_t n_listeners, const uint32_t *slots, uint32_t n, gas_params *table, uint8_t *was_further, gas_params *out_params, const gas_area_send *areas = nullptr, const float *listener_area_pos = nullptr, gas_audio_frame *out_reverb = nullptr, gas_hrtf_blend *blend_table = nullptr /* GAS_FLAG_HRTF_INTERPOLATE: the slots' bilinear blend rows are written too */);
 hipError_t gas_launch_sample_sources(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc /* 16.16 step per row for resampled playbacks, or nullptr */);
+hipError_t gas_launch_sample_adpcm(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc, bool span /* false: every load decodes from its checkpoint (GAS_ADPCM_SPAN=0) */); // the GAS_PCM_IMA_ADPCM rows of the same list, after gas_launch_sample_sources
 hipError_t gas_launch_noop(hipStream_t stream); // event-timer calibration
 hipError_t gas_launch_stream_probe(hipStream_t stream, const void *rd, uint64_t rd_bytes, void *wr, uint64_t wr_bytes, uint32_t workgroups, uint32_t unroll, float *sink); // copy-bandwidth ceiling
 #define GAS_DIR_ORDER_SEGMENT 8192

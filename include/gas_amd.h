@@ -746,7 +746,20 @@ int gas_calc_spatialization_areas(gas_ctx *ctx, const gas_spatializer3d_config *
 typedef enum gas_pcm_format {
 	GAS_PCM_S16 = 0, /* interleaved little-endian int16 */
 	GAS_PCM_F32 = 1, /* interleaved float32 (already decoded) */
+	GAS_PCM_IMA_ADPCM = 2, /* 4-bit IMA/DVI ADPCM codes, see below */
 } gas_pcm_format;
+/* GAS_PCM_IMA_ADPCM.  The data are [ENGINE] AudioStreamWAV's FORMAT_IMA_ADPCM data as stored (recollection of the engine
+ * source, parity unpinned): one 4-bit code per frame and channel, channel c's frame i in byte (i >> 1) * channels + c,
+ * low nibble for even i, high nibble for odd i; no block headers; the call reads ((frames + 1) / 2) * channels bytes.
+ * The decoder is the public IMA/DVI standard.  Per channel (predictor, step_index) = (0, 0) before frame 0; per code n:
+ *   step = STEP[step_index];  step_index = clamp(step_index + INDEX[n & 7], 0, 88)
+ *   diff = step >> 3, + step >> 2 if n & 1, + step >> 1 if n & 2, + step if n & 4; negated if n & 8
+ *   predictor = clamp(predictor + diff, -32768, 32767); the sample is predictor
+ * with the standard 89-entry STEP table (7 ... 32767) and INDEX = {-1, -1, -1, -1, 2, 4, 6, 8}.
+ * In every entry a stream of this format behaves exactly as the GAS_PCM_S16 stream of its decoded samples would
+ * (resampled, looped in both modes -- decoding is random-access here --, bound at any start_frame).
+ * Device memory: the codes plus the decoder state in front of every 32 frames (4 bytes per channel), 20 bytes per 32
+ * samples = 5 bits per sample, counted in whole 32-frame chunks. */
 
 int gas_stream_create(gas_ctx *ctx, const void *pcm, int format, uint32_t channels /* 1 or 2 */, uint64_t frames, uint32_t *out_stream);
 /* Which engine playback class stands behind the stream's playbacks (choose before binding them):

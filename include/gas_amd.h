@@ -270,7 +270,8 @@ typedef struct gas_params {
 	float fx_shelf_gain; /* GAS_FX_HIGHSHELF gain (linear) */
 	float fx_shelf_cutoff_hz; /* GAS_FX_HIGHSHELF cutoff */
 	float er_gain[GAS_ER_TAPS]; /* NEW */
-	uint32_t er_delay[GAS_ER_TAPS]; /* NEW: 1 .. er_ring_frames - frames */
+	uint32_t er_delay[GAS_ER_TAPS]; /* NEW: 1 .. er_ring_frames - frames.  A value above er_ring_frames - frames acts as
+	                                  * er_ring_frames - frames (the oldest frame the ring holds); 0 adds the frame itself */
 } gas_params;
 
 /* Settings of the GAS_FX_LOWPASS .. GAS_FX_AMPLIFY effects of one playback, by chain position (what a script sets on

@@ -1,0 +1,462 @@
+"""GAS_FX_EARLY_REFLECTIONS on the GPU at the ends of the delay range and of the ring.
+
+The tap loop -- clamp d = min(er_delay, R - F), row-or-ring select i >= 0, wrap & (R - 1), advance of er_pos -- is written
+out in k_er_only, in k_hrtf_uni<ER> and in hrtf_body's WITH_ER prologue (k_hrtf_ols, its cross-fade and direction-run
+forms, k_hrtf_ols_blend, k_hrtf_ols_blend_fade).  Every copy is run here over tests/er_ref.py's table: delays 1, 2, around
+63 .. 65, around F, around m - 64 and m - 1, m with m = R - F, and 0, m + 1, R, R + 1, 0xffffffff from outside the range;
+gains 0 and +-0.7^k; repeated delays; rings from 2F (every ring frame live) to 8192; 2R/F + 3 callbacks, so that the write
+position wraps twice and the m tap reads real frames.  Parameters are redrawn every third callback.
+
+References: the oracle fed min(d, R - F) (test_er_reference.py pins it to er_ref at < 3e-7), or er_ref directly where
+the output can be had without the oracle's HRTF.  Every case compares all sources and all frames: the mix at
+rel_rms <= TOL against float64, the per-source peaks at rtol 2e-5, atol 1e-7 (test_gpu_parity.py's bounds).
+
+What these tests cannot tell apart, by construction of the kernels: `i > 0` in place of `i >= 0`.  Every copy of the loop
+stores the callback's frames into the ring before it reads a tap, so at i == 0 the ring frame (er_pos + R) & (R - 1) =
+er_pos already holds srow[0]: both sides of the select are the same frame.  The select's other neighbours are pinned
+(i == -1 is the last frame of the previous callback, i == 1 the second of this one: delays F - 1, F, F + 1 and 1, 2)."""
+import numpy as np
+import pytest
+
+import er_ref
+import hrtf_blend_fade_ref
+import hrtf_blend_ref
+from helpers import TOL, rel_rms
+
+pytestmark = pytest.mark.gpu
+
+HS, ER, HRTF, AMPLIFY = 1, 2, 3, 9
+DIRS = 16
+PEAK_TOL = dict(rtol=2e-5, atol=1e-7)
+AMP_DB = -4.5
+SHAPES = er_ref.FRAMES_RINGS
+SMALL = [(128, 256), (512, 1024)]
+_ids = lambda fr: f"F{fr[0]}_R{fr[1]}"  # noqa: E731
+
+
+def _hrir(kind="synth"):
+    from godot_audio_spatializer_amd import synth
+
+    if kind == "impulse":  # both ears, every direction: out = the gained mono signal itself
+        h = np.zeros((DIRS, 2, 256), np.float32)
+        h[:, :, 0] = 1.0
+        return h
+    return synth.synthetic_hrir(np.random.default_rng(7), dirs=DIRS)
+
+
+_INPUTS = {}
+
+
+def inputs(F, R, n, seed, blocks=None, gain_one=False, sort_dirs=False, table=None):
+    """(params [T] of PARAMS_DTYPE [n] with the raw delays, src [T] of float32 [n][F][2]); one object per key, shared by
+    the tests that render the same case through different kernels.  Coverage of the table is asserted here: per draw
+    when the case has sources enough to hold it, else over the case."""
+    from godot_audio_spatializer_amd import synth
+
+    key = (F, R, n, seed, blocks, gain_one, sort_dirs, None if table is None else tuple(table))
+    if key not in _INPUTS:
+        T = blocks or er_ref.callbacks(F, R)
+        rng = np.random.default_rng(seed)
+        drawer = er_ref.TapDrawer(rng, F, R, table)
+        params, srcs = [], []
+        for b in range(T):
+            if b % 3 == 0:
+                p = synth.draw_params(rng, n, dirs=DIRS, ring_frames=R, frames=F)
+                p["er_delay"], p["er_gain"] = drawer.draw(n)
+                if gain_one:
+                    p["hrtf_gain"] = 1.0
+                if sort_dirs:
+                    p["hrtf_dir"] = np.sort(p["hrtf_dir"])
+            params.append(p)
+            srcs.append(synth.draw_sources(rng, n, F))
+        drawer.assert_covered(per_draw=n >= 4)
+        _INPUTS[key] = (params, srcs)
+    return _INPUTS[key]
+
+
+def clamped(p, F, R):
+    q = p.copy()
+    q["er_delay"] = er_ref.effective_delays(p["er_delay"], F, R)
+    return q
+
+
+_ORACLE = {}
+
+
+def oracle_blocks(ob, key, chain, F, R, params, srcs, hrir=None, crossfade=False):
+    """[(mix64 [F][2], peaks [n][2])] of one n-source oracle fed the clamped delays; computed once per key."""
+    key = (key, tuple(chain), crossfade)
+    if key not in _ORACLE:
+        n = len(params[0])
+        ora = ob.BatchOracle(ob.KIND_EFFECT, n, F, chain=list(chain), hrir=hrir, er_ring_frames=R, crossfade=crossfade)
+        if AMPLIFY in chain:
+            for s in range(n):
+                ora.set_fx_settings(s, list(chain).index(AMPLIFY), volume_db=AMP_DB)
+        out = []
+        for p, x in zip(params, srcs):
+            _, pk, m64 = ora.block(clamped(p, F, R).astype(ob.PARAMS_DTYPE), x, want64=True)
+            out.append((m64[0], pk))
+        _ORACLE[key] = out
+    return _ORACLE[key]
+
+
+def render(gas, chain, F, R, params, srcs, flags=0, draining=(), hrir=None, clamp=False, device_publish=False, active_of=None, blends=None):
+    """The case on one context.  Returns [(mix [F][2], peaks [m][2])] per callback.  device_publish: every publish after
+    the first goes through gas_params_publish_batch(GAS_MEM_DEVICE, slots = NULL).  active_of(b): the source numbers of
+    callback b's list (default: all).  blends: per callback HRTF_BLEND_DTYPE [n] (flagged contexts)."""
+    K = gas.capi
+    n = len(params[0])
+    out, keep = [], []
+    with gas.SpatializerContext(max_sources=n, frames=F, er_ring_frames=R, flags=flags) as ctx:
+        if hrir is not None:
+            ctx.hrtf_load(hrir)
+        slots = ctx.source_alloc_many(n, K.KIND_EFFECT, chain)
+        for s in draining:
+            ctx.source_set_draining(int(slots[s]), True)
+        if AMPLIFY in chain:
+            fx = ctx.fx_settings_defaults(n)
+            fx["amplify_volume_db"][:, list(chain).index(AMPLIFY)] = AMP_DB
+            ctx.fx_settings_publish(slots, fx)
+        for b, (p, x) in enumerate(zip(params, srcs)):
+            if b % 3 == 0:
+                q = clamped(p, F, R) if clamp else p
+                if device_publish and b > 0:
+                    import torch
+
+                    d = torch.from_numpy(q.view(np.uint8).reshape(n, 128).copy()).cuda()
+                    keep.append(d)  # must outlive the next callback
+                    torch.cuda.synchronize()
+                    ctx.params_publish_device(d.data_ptr(), n)
+                else:
+                    ctx.params_publish_batch(slots, q)
+            if blends is not None:
+                ctx.publish_hrtf_blend(slots, blends[b])
+            act = np.arange(n) if active_of is None else np.asarray(active_of(b))
+            mix, pk = ctx.process_block(x[act], slots[act])
+            assert mix.shape == (1, F, 2)
+            out.append((mix[0].copy(), pk.copy()))
+    return out
+
+
+def check(got, want, exact=None, what=""):
+    """Mix of every callback at rel_rms <= TOL against float64; peaks of the `exact` sources (default: all) at PEAK_TOL,
+    +inf for the others."""
+    worst = 0.0
+    for b, ((mix, pk), (m64, rpk)) in enumerate(zip(got, want)):
+        e = rel_rms(mix, m64)
+        worst = max(worst, e)
+        assert e <= TOL, f"{what} callback {b}: mix rel rms {e:.3e}"
+        ex = np.ones(len(rpk), bool) if exact is None else exact
+        np.testing.assert_allclose(pk[ex], rpk[ex], err_msg=f"{what} callback {b}", **PEAK_TOL)
+        assert np.all(np.isposinf(pk[~ex])), f"{what} callback {b}"
+    print(f"{what}: worst mix rel rms {worst:.3e} over {len(got)} callbacks")
+
+
+def closed_form_blocks(F, R, params, srcs, through_hrtf):
+    """[(mix64, peaks)] from er_ref alone.  through_hrtf: the chain [ER, HRTF] with a unit-impulse HRIR in both ears and
+    hrtf_gain = 1 in every callback: both ears carry (yl + yr) / 2, times the HRTF stage's gain ramp -- from 0 (a
+    playback's gain before its first callback) to 1 over the first callback, t = i / F, then 1 -> 1."""
+    n = len(params[0])
+    bank = er_ref.ErBank(n, F, R)
+    out = []
+    for b, (p, x) in enumerate(zip(params, srcs)):
+        rows = bank.block(p, x)
+        if through_hrtf:
+            mono = rows.mean(axis=2)
+            if b == 0:
+                mono = mono * (np.arange(F, dtype=np.float64) / F)[None, :]
+            rows = np.stack([mono, mono], axis=2)
+        out.append((rows.sum(axis=0), np.abs(rows).max(axis=1)))
+    return out
+
+
+def third(n):
+    ex = np.zeros(n, bool)
+    ex[::3] = True
+    return ex
+
+
+# kernel -> (GAS_UNI_ER, context flags, exact-peak sources of n)
+def _er_hrtf_kernel(K, name, n):
+    if name == "uni":  # k_hrtf_uni<ER>: frequency-domain entries first, the exact-peak ones behind them (peak_from)
+        return "2", K.FLAG_PEAKS_DRAINING_ONLY, third(n)
+    if name == "ols_fd":  # k_hrtf_ols<WITH_ER>, frequency-domain group only: nothing draining
+        return "0", K.FLAG_PEAKS_DRAINING_ONLY, np.zeros(n, bool)
+    assert name == "ols_pk"  # k_hrtf_ols<WITH_ER>, exact-peak group only: every playback draining
+    return "0", K.FLAG_PEAKS_DRAINING_ONLY, np.ones(n, bool)
+
+
+ER_HRTF_KERNELS = ["uni", "ols_fd", "ols_pk"]
+
+
+# ---- a. [ER] summed ----------------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("FR", SHAPES, ids=_ids)
+def test_er_only_against_the_oracle(gas, ob, FR):
+    """Chain [ER]: k_er_only, summed (G_FX_ER in run_groups), 24 sources."""
+    F, R = FR
+    params, srcs = inputs(F, R, 24, seed=R + F)
+    check(render(gas, (ER,), F, R, params, srcs), oracle_blocks(ob, (F, R, 24, R + F), (ER,), F, R, params, srcs), what=f"k_er_only F {F} R {R}")
+
+
+@pytest.mark.parametrize("FR", SHAPES, ids=_ids)
+def test_er_only_one_source_is_the_closed_form(gas, FR):
+    """Chain [ER], n = 1: k_er_only; the mix IS the source's output, so both ears are compared frame for frame with
+    er_ref, and the peaks with its maxima -- nothing of the oracle in between.  Eight taps cannot hold the table, so it
+    is covered over the case's three (or more) draws."""
+    F, R = FR
+    params, srcs = inputs(F, R, 1, seed=R - F)
+    check(render(gas, (ER,), F, R, params, srcs), closed_form_blocks(F, R, params, srcs, False), what=f"k_er_only n 1 F {F} R {R}")
+
+
+# ---- b. [ER, HRTF] -----------------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("kernel", ER_HRTF_KERNELS)
+@pytest.mark.parametrize("FR", SHAPES, ids=_ids)
+def test_er_hrtf_against_the_oracle(gas, ob, monkeypatch, FR, kernel):
+    """Chain [ER, HRTF].  uni: GAS_UNI_ER=2 -> k_hrtf_uni<ER>, every third playback draining (both of its sections).
+    ols_fd / ols_pk: GAS_UNI_ER=0 -> the split k_hrtf_ols<WITH_ER>, under GAS_FLAG_PEAKS_DRAINING_ONLY with nothing
+    draining (hrtf_body's frequency-domain form) and with everything draining (its exact-peak form)."""
+    F, R = FR
+    env, flags, exact = _er_hrtf_kernel(gas.capi, kernel, 24)
+    monkeypatch.setenv("GAS_UNI_ER", env)
+    params, srcs = inputs(F, R, 24, seed=R + F)
+    want = oracle_blocks(ob, (F, R, 24, R + F), (ER, HRTF), F, R, params, srcs, hrir=_hrir())
+    check(render(gas, (ER, HRTF), F, R, params, srcs, flags=flags, draining=np.flatnonzero(exact), hrir=_hrir()), want, exact, what=f"{kernel} F {F} R {R}")
+
+
+@pytest.mark.parametrize("kernel", ER_HRTF_KERNELS)
+def test_er_hrtf_unit_impulse_is_the_closed_form(gas, monkeypatch, kernel):
+    """Chain [ER, HRTF] with a unit-impulse HRIR in both ears and hrtf_gain = 1 throughout, through k_hrtf_uni<ER> and both
+    forms of k_hrtf_ols<WITH_ER>: both ears are (yl + yr) / 2 of er_ref times the HRTF stage's gain ramp (0 -> 1 over a
+    playback's first callback, 1 afterwards).  Owes nothing to the oracle's HRTF."""
+    F, R, n = 128, 256, 24
+    env, flags, exact = _er_hrtf_kernel(gas.capi, kernel, n)
+    monkeypatch.setenv("GAS_UNI_ER", env)
+    params, srcs = inputs(F, R, n, seed=5, gain_one=True)
+    got = render(gas, (ER, HRTF), F, R, params, srcs, flags=flags, draining=np.flatnonzero(exact), hrir=_hrir("impulse"))
+    check(got, closed_form_blocks(F, R, params, srcs, True), exact, what=f"impulse {kernel}")
+
+
+# ---- c. [ER, HRTF] under the flags that select hrtf_body's other instantiations ----------------------------------------
+
+
+@pytest.mark.parametrize("flag_name", ["crossfade", "direction_runs", "direction_order"])
+@pytest.mark.parametrize("FR", SMALL, ids=_ids)
+def test_er_hrtf_crossfade_and_direction_runs(gas, ob, FR, flag_name):
+    """Chain [ER, HRTF] on a context with GAS_FLAG_HRTF_CROSSFADE (k_hrtf_ols<WITH_ER, XFADE>; the oracle cross-fades
+    too), GAS_FLAG_DIRECTION_RUNS or GAS_FLAG_DIRECTION_ORDER (k_hrtf_ols<WITH_ER, RUNS>; directions sorted so that the
+    list has runs).  Under GAS_FLAG_PEAKS_DRAINING_ONLY with every third playback draining: the frequency-domain and the
+    exact-peak group in one launch."""
+    K = gas.capi
+    F, R = FR
+    flag = {"crossfade": K.FLAG_HRTF_CROSSFADE, "direction_runs": K.FLAG_DIRECTION_RUNS, "direction_order": K.FLAG_DIRECTION_ORDER}[flag_name]
+    xf = flag_name == "crossfade"
+    params, srcs = inputs(F, R, 24, seed=R + F, sort_dirs=not xf)
+    want = oracle_blocks(ob, (F, R, 24, R + F, not xf), (ER, HRTF), F, R, params, srcs, hrir=_hrir(), crossfade=xf)
+    exact = third(24)
+    got = render(gas, (ER, HRTF), F, R, params, srcs, flags=flag | K.FLAG_PEAKS_DRAINING_ONLY, draining=np.flatnonzero(exact), hrir=_hrir())
+    check(got, want, exact, what=f"{flag_name} F {F} R {R}")
+
+
+@pytest.mark.parametrize("fade", [False, True], ids=["blend", "blend_fade"])
+@pytest.mark.parametrize("FR", SMALL, ids=_ids)
+def test_er_hrtf_blend_kernels(gas, ob, FR, fade):
+    """Chain [ER, HRTF] under GAS_FLAG_HRTF_INTERPOLATE (k_hrtf_ols_blend<WITH_ER>) and with GAS_FLAG_HRTF_BLEND_FADE
+    (k_hrtf_ols_blend_fade<WITH_ER>), blends redrawn every callback, against hrtf_blend_ref / hrtf_blend_fade_ref -- the
+    weighted sums of single-direction oracle renders, each of those oracles fed the clamped delays."""
+    from godot_audio_spatializer_amd import synth
+
+    K = gas.capi
+    F, R = FR
+    n = 24
+    params, srcs = inputs(F, R, n, seed=R + F)
+    rng = np.random.default_rng(F)
+    blends = [synth.draw_blends(rng, n, DIRS) for _ in params]
+    exact = third(n)
+    flags = K.FLAG_HRTF_INTERPOLATE | (K.FLAG_HRTF_BLEND_FADE if fade else 0) | K.FLAG_PEAKS_DRAINING_ONLY
+    got = render(gas, (ER, HRTF), F, R, params, srcs, flags=flags, draining=np.flatnonzero(exact), hrir=_hrir(), blends=blends)
+    ref = (hrtf_blend_fade_ref.BlendFadeReference if fade else hrtf_blend_ref.BlendReference)(ob, n, F, (ER, HRTF), _hrir(), er_ring_frames=R)
+    want = []
+    for p, bl, x in zip(params, blends, srcs):
+        _, rpk, m64 = ref.block(clamped(p, F, R), bl, x)
+        want.append((m64, rpk))
+    check(got, want, exact, what=f"{'blend_fade' if fade else 'blend'} F {F} R {R}")
+
+
+# ---- d. staged chains --------------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("chain_name", ["er_amplify", "highshelf_er", "amplify_er_hrtf"])
+@pytest.mark.parametrize("FR", SHAPES, ids=_ids)
+def test_er_in_staged_chains(gas, ob, FR, chain_name):
+    """[ER, AMPLIFY]: k_er_only writing rows_out, the first stage, reading the caller's rows.  [HIGHSHELF, ER]: k_er_only
+    writing rows_out as the second stage, reading a ping-pong buffer's dense rows.  [AMPLIFY, ER, HRTF]: the staged tail
+    [ER, HRTF] in one launch of k_hrtf_uni<ER> over the amplifier's rows (the default GAS_UNI_ER)."""
+    F, R = FR
+    chain = {"er_amplify": (ER, AMPLIFY), "highshelf_er": (HS, ER), "amplify_er_hrtf": (AMPLIFY, ER, HRTF)}[chain_name]
+    hrir = _hrir() if HRTF in chain else None
+    params, srcs = inputs(F, R, 24, seed=R + F)
+    want = oracle_blocks(ob, (F, R, 24, R + F), chain, F, R, params, srcs, hrir=hrir)
+    check(render(gas, chain, F, R, params, srcs, hrir=hrir), want, what=f"{chain_name} F {F} R {R}")
+
+
+# ---- e. device-published parameters ------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("kernel", ["uni", "ols_fd"])
+def test_er_reads_device_published_rows(gas, ob, monkeypatch, kernel):
+    """gas_params_publish_batch(GAS_MEM_DEVICE, slots = NULL) on a list of [ER, HRTF] playbacks is consumed inside the
+    launch: k_hrtf_uni<ER> and k_hrtf_ols<WITH_ER> read er_delay / er_gain through the `fresh` pointer in that callback
+    and from the table, written through, in the two after it."""
+    F, R, n = 128, 256, 24
+    env, flags, exact = _er_hrtf_kernel(gas.capi, kernel, n)
+    monkeypatch.setenv("GAS_UNI_ER", env)
+    params, srcs = inputs(F, R, n, seed=R + F)
+    want = oracle_blocks(ob, (F, R, n, R + F), (ER, HRTF), F, R, params, srcs, hrir=_hrir())
+    got = render(gas, (ER, HRTF), F, R, params, srcs, flags=flags, draining=np.flatnonzero(exact), hrir=_hrir(), device_publish=True)
+    check(got, want, exact, what=f"device publish {kernel}")
+
+
+# ---- f. more than one source per wave ----------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("kernel", ["er_only", "uni", "ols_fd"])
+def test_two_sources_on_one_wave(gas, ob, monkeypatch, kernel):
+    """n = 2049, F = 128, R = 256, 5 callbacks: the smallest n at which wave_range() hands one wave two sources.
+    k_er_only and k_hrtf_ols with one group: gas_hrtf_plan's wgs_for(n, budget) = max(min(ceil(n / 8), budget),
+    ceil(n / 512)) workgroups of WAVES = 8, budget = 256 * 4 * GAS_HRTF_WAVES_PER_SIMD / WAVES = 256, so 2048 waves from
+    n = 2041 on and two sources on the first wave at n = 2049.  k_hrtf_uni: gas_hrtf_uni_partials(n) = max(min(ceil(n /
+    8), 256), ceil(n / 512)) workgroups of UNI_W = 8 waves: 2049 again.  The second source of a wave reads er_pos, the
+    ring and the parameters of ITS slot."""
+    K = gas.capi
+    F, R, n = 128, 256, 2049
+    params, srcs = inputs(F, R, n, seed=2049, blocks=5)
+    if kernel == "er_only":
+        chain, flags, exact, hrir = (ER,), 0, np.ones(n, bool), None
+    else:
+        env, flags, exact = _er_hrtf_kernel(K, kernel, n)
+        monkeypatch.setenv("GAS_UNI_ER", env)
+        chain, hrir = (ER, HRTF), _hrir()
+    want = oracle_blocks(ob, (F, R, n, 2049), chain, F, R, params, srcs, hrir=hrir)
+    check(render(gas, chain, F, R, params, srcs, flags=flags, draining=np.flatnonzero(exact) if flags else (), hrir=hrir), want, exact, what=f"2049 {kernel}")
+
+
+# ---- g. the clamp, bitwise ---------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("kernel", ["er_only", "uni", "ols_fd", "ols_pk"])
+@pytest.mark.parametrize("FR", [(128, 256), (384, 1024)], ids=_ids)
+def test_out_of_range_delays_are_the_clamped_ones_bitwise(gas, monkeypatch, FR, kernel):
+    """Two contexts, the same sources: one is given the raw delays (0, m + 1, R, R + 1, 0xffffffff among them), the other
+    min(d, R - F).  k_er_only, k_hrtf_uni<ER> and both forms of k_hrtf_ols<WITH_ER> must not tell them apart: mix and
+    peaks array_equal."""
+    K = gas.capi
+    F, R = FR
+    n = 24
+    params, srcs = inputs(F, R, n, seed=R + F)
+    assert any((p["er_delay"] > R - F).any() for p in params)
+    if kernel == "er_only":
+        chain, flags, exact, hrir = (ER,), 0, np.ones(n, bool), None
+    else:
+        env, flags, exact = _er_hrtf_kernel(K, kernel, n)
+        monkeypatch.setenv("GAS_UNI_ER", env)
+        chain, hrir = (ER, HRTF), _hrir()
+    dr = np.flatnonzero(exact) if flags else ()
+    raw = render(gas, chain, F, R, params, srcs, flags=flags, draining=dr, hrir=hrir)
+    twin = render(gas, chain, F, R, params, srcs, flags=flags, draining=dr, hrir=hrir, clamp=True)
+    for (ma, pa), (mb, pb) in zip(raw, twin):
+        assert np.isfinite(ma).all() and np.abs(ma).max() > 0
+        np.testing.assert_array_equal(ma, mb)
+        np.testing.assert_array_equal(pa, pb)
+
+
+# ---- h. a playback left out of a callback ------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("kernel", ["er_only", "uni", "ols_pk"])
+def test_a_playback_left_out_of_a_callback_keeps_ring_and_position(gas, ob, monkeypatch, kernel):
+    """24 playbacks in three interleaved subsets; each callback's list holds two of them, rotating, for 3R/F + 3
+    callbacks.  A playback's ring and er_pos move only in the callbacks it is listed in: each is compared through a
+    one-source oracle of its own that is advanced only then (as in test_gpu_buses.py).  k_er_only for [ER]; k_hrtf_uni<ER>
+    and k_hrtf_ols<WITH_ER> (exact peaks) for [ER, HRTF]."""
+    K = gas.capi
+    F, R, n = 128, 256, 24
+    T = 3 * R // F + 3
+    params, srcs = inputs(F, R, n, seed=77, blocks=T)
+    if kernel == "er_only":
+        chain, flags, hrir = (ER,), 0, None
+    else:
+        env, flags, _ = _er_hrtf_kernel(K, kernel, n)
+        monkeypatch.setenv("GAS_UNI_ER", env)
+        chain, hrir = (ER, HRTF), _hrir()
+    active_of = lambda b: [s for s in range(n) if s % 3 != b % 3]  # noqa: E731
+    got = render(gas, chain, F, R, params, srcs, flags=flags, draining=range(n) if flags else (), hrir=hrir, active_of=active_of)
+    oras = [ob.BatchOracle(ob.KIND_EFFECT, 1, F, chain=list(chain), hrir=hrir, er_ring_frames=R) for _ in range(n)]
+    want = []
+    for b, (p, x) in enumerate(zip(params, srcs)):
+        pc = clamped(p, F, R).astype(ob.PARAMS_DTYPE)
+        m64, pk = np.zeros((F, 2), np.float64), []
+        for s in active_of(b):
+            _, rp, y = oras[s].block(pc[s : s + 1], x[s : s + 1], want64=True)
+            m64 += y[0]
+            pk.append(rp[0])
+        want.append((m64, np.stack(pk)))
+    check(got, want, what=f"left out {kernel}")
+
+
+# ---- i. slot reuse and reset -------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("chain", [(ER,), (ER, HRTF)], ids=["er", "er_hrtf"])
+@pytest.mark.parametrize("FR", [(128, 256), (256, 8192)], ids=_ids)
+def test_reused_and_reset_slots_start_with_an_empty_ring(gas, ob, FR, chain):
+    """k_zero_slot's ring zeroing, seen through the taps: every tap at m or m - 1, non-zero gains.  A playback fills its
+    ring for R/F + 1 callbacks, is freed; after one callback gas_source_alloc hands the same slot out, and the new
+    playback's first R/F + 1 callbacks must be a fresh oracle's (for R/F - 1 of them the m taps read the zeros in front
+    of the stream -- or what the previous playback left).  Then gas_source_reset on the live slot: the same again.  A
+    second playback runs alongside throughout and keeps its own ring."""
+    from godot_audio_spatializer_amd import synth
+
+    K = gas.capi
+    F, R = FR
+    m, T = R - F, R // F + 1
+    rng = np.random.default_rng(R)
+    hrir = _hrir() if HRTF in chain else None
+    p = synth.draw_params(rng, 2, dirs=DIRS, ring_frames=R, frames=F)
+    p["er_delay"] = [[m, m - 1] * 4, [m - 1, m] * 4]
+    p["er_gain"] = (0.7 ** np.arange(1, 9)) * np.array([1, -1, -1, 1, 1, -1, 1, -1])
+    po = p.astype(ob.PARAMS_DTYPE)
+    mk = lambda: ob.BatchOracle(ob.KIND_EFFECT, 1, F, chain=list(chain), hrir=hrir, er_ring_frames=R)  # noqa: E731
+    with gas.SpatializerContext(max_sources=2, frames=F, er_ring_frames=R) as ctx:
+        if hrir is not None:
+            ctx.hrtf_load(hrir)
+        a, b = ctx.source_alloc(K.KIND_EFFECT, chain), ctx.source_alloc(K.KIND_EFFECT, chain)
+        ctx.params_publish_batch([a, b], p)
+        ora_a, ora_b = mk(), mk()
+
+        def both(tag):
+            for t in range(T):
+                x = synth.draw_sources(rng, 2, F)
+                mix, pk = ctx.process_block(x, [a, b])
+                _, pa, ya = ora_a.block(po[:1], x[:1], want64=True)
+                _, pb, yb = ora_b.block(po[1:], x[1:], want64=True)
+                e = rel_rms(mix[0], ya[0] + yb[0])
+                assert e <= TOL, f"{tag} callback {t}: {e:.3e}"
+                np.testing.assert_allclose(pk, np.concatenate([pa, pb]), err_msg=f"{tag} callback {t}", **PEAK_TOL)
+
+        both("first playback")  # the ring is full of non-zero frames
+        ctx.source_free(a)  # takes effect at the next callback
+        x = synth.draw_sources(rng, 1, F)
+        mix, _ = ctx.process_block(x, [b])
+        assert rel_rms(mix[0], ora_b.block(po[1:], x, want64=True)[2][0]) <= TOL
+        a2 = ctx.source_alloc(K.KIND_EFFECT, chain)
+        assert a2 == a
+        ctx.params_publish(a2, p[0])
+        ora_a = mk()
+        both("re-allocated slot")
+        ctx.source_reset(a)
+        ora_a = mk()
+        both("reset slot")

@@ -271,6 +271,17 @@ MEM_DEVICE = 1
 PCM_S16 = 0
 PCM_F32 = 1
 PCM_IMA_ADPCM = 2
+PCM_QOA = 3
+
+
+def qoa_file_bytes(frames, channels):
+    """Bytes of the QOA file of a stream (include/gas_amd.h): 8, and per 5120 frames 8 + 16 * channels + 8 * slices *
+    channels with slices = ceil(frames in it / 20)."""
+    full, rest = divmod(int(frames), 5120)
+    per = lambda n: 8 + 16 * channels + 8 * ((n + 19) // 20) * channels  # noqa: E731
+    return 8 + full * per(5120) + (per(rest) if rest else 0)
+
+
 # gas_loop_mode (gas_stream_set_loop)
 LOOP_DISABLED = 0
 LOOP_FORWARD = 1
@@ -783,14 +794,19 @@ class SpatializerContext:
 
     # ---- device-resident streams ----
     def stream_create(self, pcm, format=None, channels=None, frames=None):
-        """pcm: int16 or float32 array [frames] (mono) or [frames][2] (stereo); or, with format=PCM_IMA_ADPCM, channels
-        and frames, the uint8 codes as include/gas_amd.h lays them out (((frames + 1) // 2) * channels bytes)."""
+        """pcm: int16 or float32 array [frames] (mono) or [frames][2] (stereo); or, with format, channels and frames, uint8
+        data as include/gas_amd.h lays them out: PCM_IMA_ADPCM the codes (((frames + 1) // 2) * channels bytes), PCM_QOA
+        the whole QOA file (qoa_file_bytes(frames, channels) bytes).  ValueError only for fewer bytes than the library
+        would read; what the bytes hold is the library's to judge (GasError)."""
         a = np.ascontiguousarray(pcm)
         sid = C.c_uint32()
         if format is not None or a.dtype == np.uint8:
             if a.dtype != np.uint8 or format is None or channels is None or frames is None:
                 raise ValueError("encoded data are a uint8 array passed with format, channels and frames")
-            if int(channels) > 0 and a.size < ((int(frames) + 1) // 2) * int(channels):
+            if int(format) == PCM_QOA:
+                if a.size < 4 or (int(channels) in (1, 2) and int(frames) > 0 and bytes(a[:4]) == b"qoaf" and a.size < qoa_file_bytes(int(frames), int(channels))):
+                    raise ValueError("fewer bytes than the QOA file of these frames and channels")
+            elif int(channels) > 0 and a.size < ((int(frames) + 1) // 2) * int(channels):
                 raise ValueError("fewer bytes than ((frames + 1) // 2) * channels")
             self._check(self.lib.gas_stream_create(self.h, _np_ptr(a), int(format), int(channels), int(frames), C.byref(sid)), "gas_stream_create")
             return sid.value

@@ -19,6 +19,7 @@
 #include "gas_fx_mod_check.h"
 #include "gas_fx_stereo_check.h"
 #include "gas_internal.h"
+#include "gas_qoa.h"
 
 namespace {
 
@@ -224,6 +225,8 @@ struct gas_ctx {
 	bool stream_any_looped = false;
 	bool stream_any_adpcm = false; // the list holds a GAS_PCM_IMA_ADPCM playback: rows first, k_sample_adpcm behind k_sample_sources
 	bool adpcm_span = getenv("GAS_ADPCM_SPAN") == nullptr || atoi(getenv("GAS_ADPCM_SPAN")) != 0; // development aid: 0 = every load decodes from its checkpoint (k_sample_adpcm.hip; tools/time_stream_adpcm.py and the tests compare the paths)
+	bool stream_any_qoa = false; // the list holds a GAS_PCM_QOA playback: rows first, k_sample_qoa behind k_sample_sources
+	bool qoa_span = getenv("GAS_QOA_SPAN") == nullptr || atoi(getenv("GAS_QOA_SPAN")) != 0; // development aid: 0 = every load decodes from its record (k_sample_qoa.hip; tools/time_stream_qoa.py and the tests compare the paths)
 	bool stream_params_touched = false; // a parameter publish may have changed pitch_scale: re-validate
 
 	// gas_calc_spatialization staging (physics thread)
@@ -2742,8 +2745,11 @@ static inline void stream_rows_sync_back_fwd(gas_ctx *c) {
 }
 
 int gas_stream_create(gas_ctx *c, const void *pcm, int format, uint32_t channels, uint64_t frames, uint32_t *out_stream) {
-	if (!c || !pcm || !out_stream || (format != GAS_PCM_S16 && format != GAS_PCM_F32 && format != GAS_PCM_IMA_ADPCM) || (channels != 1 && channels != 2) || frames == 0) {
+	if (!c || !pcm || !out_stream || (format != GAS_PCM_S16 && format != GAS_PCM_F32 && format != GAS_PCM_IMA_ADPCM && format != GAS_PCM_QOA) || (channels != 1 && channels != 2) || frames == 0) {
 		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (format == GAS_PCM_QOA && !gas_qoa_validate(static_cast<const uint8_t *>(pcm), gas_qoa_file_bytes(frames, channels), channels, frames)) {
+		return GAS_ERR_INVALID_ARGUMENT; // the magic first: nothing else is read of data that are no QOA file
 	}
 	GAS_HIP(c, hipSetDevice(c->cfg.device));
 	size_t bytes = (size_t)frames * channels * (format == GAS_PCM_S16 ? 2 : 4);
@@ -2768,6 +2774,17 @@ int gas_stream_create(gas_ctx *c, const void *pcm, int format, uint32_t channels
 			}
 		}
 		pcm = adpcm.data();
+	}
+	std::vector<gas_qoa_record> qoa; // [chunk][channel] (gas_qoa.h)
+	if (format == GAS_PCM_QOA) {
+		bytes = (size_t)gas_qoa_device_bytes(frames, channels);
+		try {
+			qoa.assign(bytes / sizeof(gas_qoa_record), gas_qoa_record{});
+		} catch (const std::exception &) {
+			return GAS_ERR_OUT_OF_MEMORY;
+		}
+		gas_qoa_build_records(static_cast<const uint8_t *>(pcm), channels, frames, qoa.data()); // decodes once, keeping the state in front of every chunk
+		pcm = qoa.data();
 	}
 	gas_ctx::StreamInfo si;
 	GAS_HIP(c, hipMalloc(&si.d_pcm, bytes));
@@ -3051,9 +3068,11 @@ int gas_process_block_streams(gas_ctx *c, const uint32_t *slots, uint32_t n, uin
 		c->stream_any_resampled = false;
 		c->stream_any_looped = false;
 		c->stream_any_adpcm = false;
+		c->stream_any_qoa = false;
 		for (uint32_t i = 0; i < n; i++) {
 			const gas_cursor &cur = c->h_cursors[slots[i]];
 			c->stream_any_adpcm = c->stream_any_adpcm || (cur.pcm && (cur.format_channels >> 8) == GAS_PCM_IMA_ADPCM);
+			c->stream_any_qoa = c->stream_any_qoa || (cur.pcm && (cur.format_channels >> 8) == GAS_PCM_QOA);
 			gas_ctx::StreamRow &r = c->stream_rows[i];
 			r.remaining = cur.pcm && cur.frames > cur.pos ? cur.frames - cur.pos : 0;
 			r.has_frames = cur.pcm ? cur.has_frames : 0;
@@ -3138,8 +3157,8 @@ int gas_process_block_streams(gas_ctx *c, const uint32_t *slots, uint32_t n, uin
 	// (GAS_FLAG_HRTF_BLEND_FADE: the stream-sampling form has no registers left for the fade, DESIGN.md 3.4 -- rows first)
 	// (gas_stream_set_loop: the cross-fade form has no registers left for the looped branch either, DESIGN.md 3.4 -- rows first)
 	const bool loops_fused = !c->stream_any_looped || (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) == 0;
-	// (GAS_PCM_IMA_ADPCM: the fused prologues read uncompressed frames only -- rows first, like a resampled playback)
-	const bool all_hrtf = c->stream_all_hrtf && !c->stream_any_resampled && !c->stream_any_adpcm && !fade_on(c) && loops_fused && !c->stream_rows_first; // the fused prologue samples plain playbacks only
+	// (GAS_PCM_IMA_ADPCM, GAS_PCM_QOA: the fused prologues read uncompressed frames only -- rows first, like a resampled playback)
+	const bool all_hrtf = c->stream_all_hrtf && !c->stream_any_resampled && !c->stream_any_adpcm && !c->stream_any_qoa && !fade_on(c) && loops_fused && !c->stream_rows_first; // the fused prologue samples plain playbacks only
 	if (!all_hrtf) {
 		const size_t need = (size_t)n * F;
 		if (need > c->d_src_frames) {
@@ -3158,6 +3177,9 @@ int gas_process_block_streams(gas_ctx *c, const uint32_t *slots, uint32_t n, uin
 			hipError_t e = gas_launch_sample_sources(c->stream, c->d_cursors, c->d_stream_slots, n, F, c->d_fade_env, c->d_src, c->stream_any_resampled ? c->d_stream_inc : nullptr);
 			if (e == hipSuccess && c->stream_any_adpcm) {
 				e = gas_launch_sample_adpcm(c->stream, c->d_cursors, c->d_stream_slots, n, F, c->d_fade_env, c->d_src, c->stream_any_resampled ? c->d_stream_inc : nullptr, c->adpcm_span);
+			}
+			if (e == hipSuccess && c->stream_any_qoa) {
+				e = gas_launch_sample_qoa(c->stream, c->d_cursors, c->d_stream_slots, n, F, c->d_fade_env, c->d_src, c->stream_any_resampled ? c->d_stream_inc : nullptr, c->qoa_span);
 			}
 			if (e != hipSuccess) {
 				c->last_err = hipGetErrorString(e);

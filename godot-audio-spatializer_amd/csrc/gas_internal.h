@@ -249,7 +249,7 @@ __host__ __device__ inline void gas_adpcm_step(int32_t &predictor, int32_t &step
 // Stream indices [lo, hi] that contain m(k) for every unrolled index k in [k0, k1] (0 <= k0 <= k1) of a looped cursor:
 // the indices themselves in front of the loop; inside it the run they map to while no seam falls into it, else the
 // whole loop.
-__host__ __device__ inline void gas_adpcm_loop_bounds(const gas_cursor &c, uint64_t k0, uint64_t k1, uint64_t &lo, uint64_t &hi) {
+__host__ __device__ inline void gas_stream_loop_bounds(const gas_cursor &c, uint64_t k0, uint64_t k1, uint64_t &lo, uint64_t &hi) {
 	const uint64_t b = c.loop_begin;
 	if (k1 < b) {
 		lo = k0;
@@ -272,8 +272,8 @@ __host__ __device__ inline void gas_adpcm_loop_bounds(const gas_cursor &c, uint6
 }
 
 // Bounds of the stream indices gas_sample_row (gas_sample_row.h) can load for this cursor and callback, hi < frames;
-// false: it loads none.  What k_sample_adpcm.hip decodes ahead of a row.
-__host__ __device__ inline bool gas_adpcm_span_bounds(const gas_cursor &c, uint32_t F, uint64_t inc, uint64_t &lo, uint64_t &hi) {
+// false: it loads none.  What k_sample_adpcm.hip and k_sample_qoa.hip decode ahead of a row.
+__host__ __device__ inline bool gas_stream_span_bounds(const gas_cursor &c, uint32_t F, uint64_t inc, uint64_t &lo, uint64_t &hi) {
 	if (!c.has_frames) {
 		return false;
 	}
@@ -301,7 +301,7 @@ __host__ __device__ inline bool gas_adpcm_span_bounds(const gas_cursor &c, uint3
 		return false;
 	}
 	if (c.loop_mode) {
-		gas_adpcm_loop_bounds(c, (uint64_t)k0, (uint64_t)k1, lo, hi);
+		gas_stream_loop_bounds(c, (uint64_t)k0, (uint64_t)k1, lo, hi);
 	} else {
 		lo = (uint64_t)k0;
 		hi = (uint64_t)k1;
@@ -457,6 +457,7 @@ hipError_t gas_launch_scatter_params(hipStream_t stream, gas_params *table, cons
 hipError_t gas_launch_calc_spatialization(hipStream_t stream, const gas_spatializer3d_config *cfgs, const uint32_t *cfg_index, const gas_source_pose *poses, const gas_listener *listeners, uint32_t n_listeners, const uint32_t *slots, uint32_t n, gas_params *table, uint8_t *was_further, gas_params *out_params, const gas_area_send *areas = nullptr, const float *listener_area_pos = nullptr, gas_audio_frame *out_reverb = nullptr, gas_hrtf_blend *blend_table = nullptr /* GAS_FLAG_HRTF_INTERPOLATE: the slots' bilinear blend rows are written too */);
 hipError_t gas_launch_sample_sources(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc /* 16.16 step per row for resampled playbacks, or nullptr */);
 hipError_t gas_launch_sample_adpcm(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc, bool span /* false: every load decodes from its checkpoint (GAS_ADPCM_SPAN=0) */); // the GAS_PCM_IMA_ADPCM rows of the same list, after gas_launch_sample_sources
+hipError_t gas_launch_sample_qoa(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc, bool span /* false: every load decodes from its record (GAS_QOA_SPAN=0) */); // the GAS_PCM_QOA rows of the same list, after gas_launch_sample_sources
 hipError_t gas_launch_noop(hipStream_t stream); // event-timer calibration
 hipError_t gas_launch_stream_probe(hipStream_t stream, const void *rd, uint64_t rd_bytes, void *wr, uint64_t wr_bytes, uint32_t workgroups, uint32_t unroll, float *sink); // copy-bandwidth ceiling
 #define GAS_DIR_ORDER_SEGMENT 8192

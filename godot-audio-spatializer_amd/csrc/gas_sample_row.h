@@ -1,5 +1,5 @@
 // gas_sample_row.h -- the row logic of the stream sampler, shared by k_sample_sources.hip (GAS_PCM_S16 / GAS_PCM_F32)
-// and k_sample_adpcm.hip (GAS_PCM_IMA_ADPCM): plain, looped and resampled branches, the fade table, the cursor write-back
+// k_sample_adpcm.hip (GAS_PCM_IMA_ADPCM) and k_sample_qoa.hip (GAS_PCM_QOA): plain, looped and resampled branches, the fade table, the cursor write-back
 // by lane 0; one wave per row.  Only where a frame comes from differs: `src.load(idx)` returns stream frame idx.
 // What the rows are: k_sample_sources.hip's header.  Everything from here on is compiled with fp contract off, so a row
 // is comparable bit for bit (tests/stream_window_ref.py).

@@ -7,7 +7,7 @@
 // values:
 //
 // per-load  the definition, right for any index: read checkpoint idx / 32, decode idx % 32 + 1 codes.
-// span      the wave bounds the stream indices its row can load (gas_adpcm_span_bounds, gas_internal.h: any superset
+// span      the wave bounds the stream indices its row can load (gas_stream_span_bounds, gas_internal.h: any superset
 //           will do); if they cover at most 64 chunks (2048 frames), lane l decodes chunk lo / 32 + l once, all 32 steps,
 //           into wave-private LDS, one 32-bit word (left, right as int16; mono twice the same) per frame, and every
 //           load of the row reads LDS.
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256) void k_sample_adpcm(gas_cursor *__restrict__ c
 	adpcm_src src{ codes, reinterpret_cast<const gas_adpcm_ckpt *>(codes + gas_adpcm_table_offset(c.frames, ch)), ch, steps, span, 0, false };
 	uint64_t lo = 0, hi = 0;
 	if (span_on && c.pcm) {
-		const bool any = gas_adpcm_span_bounds(c, F, inc, lo, hi);
+		const bool any = gas_stream_span_bounds(c, F, inc, lo, hi);
 		const uint64_t chunk0 = lo / GAS_ADPCM_CHUNK;
 		const uint64_t n_chunks = any ? hi / GAS_ADPCM_CHUNK - chunk0 + 1 : 0;
 		if (__builtin_amdgcn_readfirstlane((int)(n_chunks <= SPAN_CHUNKS))) {

@@ -9,7 +9,7 @@
 // the reference's envelope 0.96^(j+1) * (64 - j) / 64 (:380-396; table computed on the host with the same f32
 // recurrence), everything after is zero, and has_frames clears (:398); afterwards the row is all zeros (:405-408).
 // One wave per playback row, lane-contiguous 8-byte stores; int16 -> float as s / 32768, mono feeds both ears.
-// The row logic itself is gas_sample_row.h's, shared with k_sample_adpcm.hip; this file reads the uncompressed formats.
+// The row logic itself is gas_sample_row.h's, shared with k_sample_adpcm.hip and k_sample_qoa.hip; this file reads the uncompressed formats.
 #include "gas_sample_row.h"
 
 namespace {
@@ -50,8 +50,8 @@ __global__ __launch_bounds__(256) void k_sample_sources(gas_cursor *__restrict__
 	gas_cursor *cp = cursors + slots[e];
 	const gas_cursor c = *cp;
 	const pcm_src src{ c.pcm, c.format_channels >> 8, c.format_channels & 0xff };
-	if (src.fmt == GAS_PCM_IMA_ADPCM) {
-		return; // k_sample_adpcm.hip's row, launched behind this kernel over the same list
+	if (src.fmt >= GAS_PCM_IMA_ADPCM) {
+		return; // k_sample_adpcm.hip's or k_sample_qoa.hip's row, launched behind this kernel over the same list
 	}
 	const uint64_t inc = (c.resampled && row_inc) ? row_inc[e] : 65536u;
 	gas_sample_row(cp, c, rows + (size_t)e * F, F, lane, inc, fade_env, src);

@@ -748,6 +748,7 @@ typedef enum gas_pcm_format {
 	GAS_PCM_S16 = 0, /* interleaved little-endian int16 */
 	GAS_PCM_F32 = 1, /* interleaved float32 (already decoded) */
 	GAS_PCM_IMA_ADPCM = 2, /* 4-bit IMA/DVI ADPCM codes, see below */
+	GAS_PCM_QOA = 3, /* a whole QOA ("Quite OK Audio") file, see below */
 } gas_pcm_format;
 /* GAS_PCM_IMA_ADPCM.  The data are [ENGINE] AudioStreamWAV's FORMAT_IMA_ADPCM data as stored (recollection of the engine
  * source, parity unpinned): one 4-bit code per frame and channel, channel c's frame i in byte (i >> 1) * channels + c,
@@ -761,6 +762,35 @@ typedef enum gas_pcm_format {
  * (resampled, looped in both modes -- decoding is random-access here --, bound at any start_frame).
  * Device memory: the codes plus the decoder state in front of every 32 frames (4 bytes per channel), 20 bytes per 32
  * samples = 5 bits per sample, counted in whole 32-frame chunks. */
+/* GAS_PCM_QOA.  The data are [ENGINE] AudioStreamWAV's FORMAT_QOA data as stored, taken to be the whole QOA file
+ * (recollection of the engine source, parity unpinned).  The format is the public QOA specification; all fields are
+ * big-endian:
+ *   file header   'qoaf', u32 samples per channel
+ *   frames        ceil(samples / 5120) of them, each
+ *     header      u8 channels, u24 sample rate, u16 fsamples (samples per channel in this frame), u16 fsize (bytes of the
+ *                 frame, header included)
+ *     state       per channel history[4] int16, then weights[4] int16 (16 bytes per channel)
+ *     slices      ceil(fsamples / 20) per channel, interleaved by channel (slice s of channel 0, slice s of channel 1,
+ *                 slice s + 1 of channel 0, ...);  fsize = 8 + 16 * channels + 8 * slices * channels
+ *   slice         a u64: bits 63..60 the scale factor sf, then 20 residual codes of 3 bits, the first in bits 59..57; a
+ *                 partial last slice is padded with zeros
+ * The call reads the bytes that `frames` and `channels` imply (8 + the sum of the fsize values) and validates before it
+ * uploads anything; GAS_ERR_INVALID_ARGUMENT, and no stream, if the magic is not 'qoaf' (checked before anything else is
+ * read), the header's sample count is not `frames`, a frame header's channel count is not `channels` (1 or 2 only), or
+ * a frame header's fsamples or fsize is not what the layout implies.  The sample-rate fields are ignored: streams are
+ * taken to be at the context's mix rate.
+ * The decoder is a 4-tap sign-LMS predictor.  Every frame header RELOADS (h, w) = (history, weights) of each channel --
+ * nothing carries across a frame edge -- and per sample, in 32-bit two's-complement arithmetic that wraps:
+ *   p = (w0 * h0 + w1 * h1 + w2 * h2 + w3 * h3) >> 13          (arithmetic shift)
+ *   d = DEQ[sf][code];  s = clamp(p + d, -32768, 32767);  delta = d >> 4
+ *   w[i] += (h[i] < 0 ? -delta : delta);  h = (h1, h2, h3, s);  the sample is s
+ * with DEQ[sf][k] = round-half-away-from-zero of round((sf + 1)^2.75) * {0.75, -0.75, 2.5, -2.5, 4.5, -4.5, 7, -7}[k]
+ * (scale factors 1, 7, 21, 45, 84, 138, 211, 304, 421, 562, 731, 928, 1157, 1419, 1715, 2048).
+ * In every entry a stream of this format behaves exactly as the GAS_PCM_S16 stream of its decoded samples would
+ * (resampled, looped in both modes, bound at any start_frame, positions, the host layer).
+ * Device memory: one 64-byte record per 80 frames (4 slices) and channel -- the slices as stored and the decoder state
+ * in front of them, filled by one decode on the host in this call -- 6.4 bits per sample, counted in whole 80-frame
+ * chunks. */
 
 int gas_stream_create(gas_ctx *ctx, const void *pcm, int format, uint32_t channels /* 1 or 2 */, uint64_t frames, uint32_t *out_stream);
 /* Which engine playback class stands behind the stream's playbacks (choose before binding them):

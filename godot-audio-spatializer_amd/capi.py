@@ -453,6 +453,7 @@ EXPORTS = [
     "gas_stream_get_loop",
     "gas_source_bind_stream",
     "gas_process_block_streams",
+    "gas_process_block_streams_buses",
     "gas_process_block",
     "gas_bus_routes_publish",
     "gas_process_block_buses",
@@ -547,6 +548,7 @@ def load_library():
     L.gas_stream_get_loop.argtypes = [vp, u32, C.POINTER(i32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.gas_source_bind_stream.argtypes = [vp, u32, u32, C.c_uint64]
     L.gas_process_block_streams.argtypes = [vp, vp, u32, u32, vp, vp, vp, i32]
+    L.gas_process_block_streams_buses.argtypes = [vp, vp, u32, u32, vp, u32, vp, vp, i32]
     L.gas_calc_spatialization.argtypes = [vp, vp, u32, vp, vp, vp, u32, vp, u32, vp, i32]
     L.gas_calc_spatialization_areas.argtypes = [vp, vp, u32, vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, i32]
     L.gas_process_block.argtypes = [vp, vp, vp, u32, u32, vp, vp, i32]
@@ -843,7 +845,7 @@ class SpatializerContext:
         self._check(self.lib.gas_source_bind_stream(self.h, int(slot), int(sid), int(start_frame)), "gas_source_bind_stream")
 
     def stream_positions(self, n):
-        """Stream frame each playback of the last process_block_streams list (n entries) takes next."""
+        """Stream frame each playback of the last process_block_streams / process_block_streams_buses list (n entries) takes next."""
         out = np.zeros(max(n, 1), dtype=np.uint64)
         self._check(self.lib.gas_stream_positions(self.h, n, _np_ptr(out)), "gas_stream_positions")
         return out[:n]
@@ -857,6 +859,17 @@ class SpatializerContext:
         rc = self.lib.gas_process_block_streams(self.h, _np_ptr(s) if n else None, n, self.frames, _np_ptr(out), _np_ptr(peaks), _np_ptr(hf), MEM_HOST)
         self._check(rc, "gas_process_block_streams")
         return out, peaks[:n], hf[:n].astype(bool)
+
+    def process_block_streams_buses(self, slots, n_buses):
+        """Stream callback over several buses: -> (mix [n_buses][C][F][2], peaks [n][2], has_frames [n])."""
+        s = np.ascontiguousarray(slots, dtype=np.uint32)
+        n = len(s)
+        out = np.full((max(n_buses, 1), self.channel_count, self.frames, 2), np.nan, dtype=np.float32)
+        peaks = np.zeros((max(n, 1), 2), dtype=np.float32)
+        hf = np.zeros(max(n, 1), dtype=np.uint8)
+        rc = self.lib.gas_process_block_streams_buses(self.h, _np_ptr(s) if n else None, n, self.frames, _np_ptr(out), n_buses, _np_ptr(peaks), _np_ptr(hf), MEM_HOST)
+        self._check(rc, "gas_process_block_streams_buses")
+        return out[:n_buses], peaks[:n], hf[:n].astype(bool)
 
     def hrtf_load(self, hrir):
         h = np.ascontiguousarray(hrir, dtype=np.float32)

@@ -221,6 +221,8 @@ struct gas_ctx {
 	};
 	std::vector<StreamRow> stream_rows;
 	bool stream_all_hrtf = false;
+	bool stream_last_buses = false; // the cached stream list was validated by gas_process_block_streams_buses (its checks differ from the mix entry's)
+	bool stream_bus_staged = false; // ... and ran the staged bus form, which regroups on every call (cached_n never names it)
 	bool stream_rows_first = getenv("GAS_STREAM_ROWS_FIRST") != nullptr && atoi(getenv("GAS_STREAM_ROWS_FIRST")) != 0; // development aid: plain [HRTF] stream lists sample rows first too (tools/time_stream_loops.py compares the routes)
 	bool stream_any_looped = false;
 	bool stream_any_adpcm = false; // the list holds a GAS_PCM_IMA_ADPCM playback: rows first, k_sample_adpcm behind k_sample_sources
@@ -2852,7 +2854,7 @@ int gas_stream_positions(gas_ctx *c, uint32_t n, uint64_t *out_frames) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
 	if (n != c->stream_slots_host.size()) {
-		return GAS_ERR_INVALID_ARGUMENT; // not the list of the last stream callback
+		return GAS_ERR_INVALID_ARGUMENT; // not the list of the last stream callback (gas_process_block_streams or gas_process_block_streams_buses)
 	}
 	// The compact row mirror holds the positions while the list is cached; a block boundary that applied deferred
 	// frees has folded it back into the per-slot cursors (stream_rows_sync_back) and emptied it.
@@ -2998,8 +3000,17 @@ void stream_rows_sync_back(gas_ctx *c) {
 
 extern "C" {
 
-int gas_process_block_streams(gas_ctx *c, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, float *peaks, uint8_t *has_frames, int mem) {
+// Both stream entries: validation, the host mirror of the cursor arithmetic, the same_list steady state, the sampler
+// launches and fused_streams.  !buses: gas_process_block_streams (one mix, out [C][frames], n_buses unused); buses:
+// gas_process_block_streams_buses (out [n_buses][C][frames], the device path of gas_process_block_buses over the windows).
+static int process_block_streams_common(gas_ctx *c, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, uint32_t n_buses, bool buses, float *peaks, uint8_t *has_frames, int mem) {
 	if (!c || !out || (n > 0 && !slots) || n > c->cfg.max_sources || (mem != GAS_MEM_HOST && mem != GAS_MEM_DEVICE)) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (buses && (n_buses < 1 || n_buses > GAS_MAX_BUSES)) {
+		if (mem == GAS_MEM_HOST) { // as much of `out` as a legal call could name
+			std::memset(out, 0, (size_t)(n_buses < GAS_MAX_BUSES ? n_buses : GAS_MAX_BUSES) * c->cfg.channel_count * c->cfg.frames * sizeof(gas_audio_frame));
+		}
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
 	{ // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
@@ -3009,9 +3020,10 @@ int gas_process_block_streams(gas_ctx *c, const uint32_t *slots, uint32_t n, uin
 		}
 	}
 	const uint32_t F = c->cfg.frames, C = c->cfg.channel_count;
+	const size_t out_bytes = (size_t)(buses ? n_buses : 1u) * C * F * sizeof(gas_audio_frame);
 	auto fail = [&](int code) {
 		if (mem == GAS_MEM_HOST) {
-			std::memset(out, 0, (size_t)C * F * sizeof(gas_audio_frame));
+			std::memset(out, 0, out_bytes);
 		}
 		return code;
 	};
@@ -3023,8 +3035,9 @@ int gas_process_block_streams(gas_ctx *c, const uint32_t *slots, uint32_t n, uin
 	}
 	// Steady state: same slot list as the previous stream callback, launch groups still cached, no parameter or
 	// binding change since -> skip validation and work on the compact row mirror.
+	// (The staged bus form regroups on every call and leaves no cached groups behind: its list stays "the same" without them.)
 	adopt_frees(c);
-	bool same_list = c->pending_free.empty() /* a deferred free re-sorts the groups */ && c->stream_rows.size() == n && c->cached_n == n && c->stream_groups_gen == c->groups_gen && !c->stream_params_touched && c->stream_slots_host.size() == n && (n == 0 || std::memcmp(c->stream_slots_host.data(), slots, (size_t)n * sizeof(uint32_t)) == 0);
+	bool same_list = c->pending_free.empty() /* a deferred free re-sorts the groups */ && c->stream_rows.size() == n && (c->cached_n == n || (buses && c->stream_bus_staged)) && c->stream_last_buses == buses && c->stream_groups_gen == c->groups_gen && !c->stream_params_touched && c->stream_slots_host.size() == n && (n == 0 || std::memcmp(c->stream_slots_host.data(), slots, (size_t)n * sizeof(uint32_t)) == 0);
 	if (!same_list) {
 		stream_rows_sync_back(c);
 		for (uint32_t i = 0; i < n; i++) {
@@ -3061,6 +3074,19 @@ int gas_process_block_streams(gas_ctx *c, const uint32_t *slots, uint32_t n, uin
 				return fail(GAS_ERR_NO_HRTF);
 			}
 		}
+		if (buses) { // what gas_process_block_buses rejects beyond that: neither of its two forms (every source 3D mix; every source a non-empty chain, one pair)
+			bool all_mix = true, all_fx = n > 0;
+			for (uint32_t i = 0; i < n; i++) {
+				const SlotInfo &si = c->slots[slots[i]];
+				all_mix = all_mix && si.kind == GAS_KIND_3D_MIX;
+				all_fx = all_fx && si.kind == GAS_KIND_EFFECT && si.chain_sig != 0;
+			}
+			if (!all_mix && !(all_fx && C == 1)) {
+				return fail(GAS_ERR_UNSUPPORTED_CHAIN);
+			}
+		}
+		c->stream_last_buses = buses;
+		c->stream_bus_staged = false;
 		c->stream_params_touched = false;
 		c->stream_slots_host.assign(slots, slots + n);
 		c->stream_rows.resize(n);
@@ -3158,7 +3184,9 @@ int gas_process_block_streams(gas_ctx *c, const uint32_t *slots, uint32_t n, uin
 	// (gas_stream_set_loop: the cross-fade form has no registers left for the looped branch either, DESIGN.md 3.4 -- rows first)
 	const bool loops_fused = !c->stream_any_looped || (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) == 0;
 	// (GAS_PCM_IMA_ADPCM, GAS_PCM_QOA: the fused prologues read uncompressed frames only -- rows first, like a resampled playback)
-	const bool all_hrtf = c->stream_all_hrtf && !c->stream_any_resampled && !c->stream_any_adpcm && !c->stream_any_qoa && !fade_on(c) && loops_fused && !c->stream_rows_first; // the fused prologue samples plain playbacks only
+	// (buses: the fused form is k_hrtf_uni<SRC_PCM, BUS2>, which gas_process_block_buses picks on a one-pair context without a k_hrtf_ols-only mode)
+	const bool bus_fusable = !buses || (C == 1 && uni_ok(c) && gas_hrtf_uni_waves() == 8);
+	const bool all_hrtf = c->stream_all_hrtf && !c->stream_any_resampled && !c->stream_any_adpcm && !c->stream_any_qoa && !fade_on(c) && loops_fused && !c->stream_rows_first && bus_fusable; // the fused prologue samples plain playbacks only
 	if (!all_hrtf) {
 		const size_t need = (size_t)n * F;
 		if (need > c->d_src_frames) {
@@ -3187,8 +3215,45 @@ int gas_process_block_streams(gas_ctx *c, const uint32_t *slots, uint32_t n, uin
 			}
 		}
 	}
-	const uint32_t *list = same_list ? nullptr : slots;
 	const gas_audio_frame *rows = all_hrtf ? reinterpret_cast<const gas_audio_frame *>(c->d_cursors) /* unused, non-null */ : c->d_src;
+	if (buses) {
+		// gas_process_block_buses reuses a list only for its 3D-mix and fused [HRTF] forms; the staged form needs it every time
+		const bool reuse = same_list && n > 0 && c->cached_n == n && c->bus_form_cached != 0 && c->bus_form_groups_gen == c->groups_gen;
+		const uint32_t *bus_list = reuse ? nullptr : slots;
+		gas_audio_frame *d_bus = out;
+		float *d_pk = peaks;
+		if (mem == GAS_MEM_HOST) { // host outputs: the device path into the library's buffers, one copy back
+			if (!c->d_bus_out && hipMalloc(&c->d_bus_out, (size_t)GAS_MAX_BUSES * C * F * sizeof(gas_audio_frame)) != hipSuccess) {
+				return fail(GAS_ERR_OUT_OF_MEMORY);
+			}
+			d_bus = c->d_bus_out;
+			d_pk = c->d_peaks;
+		}
+		c->fused_streams = all_hrtf;
+		const int rcb = gas_process_block_buses(c, rows, bus_list, n, F, d_bus, n_buses, d_pk, GAS_MEM_DEVICE);
+		c->fused_streams = false;
+		c->stream_groups_gen = rcb == GAS_OK ? c->groups_gen : UINT64_MAX;
+		c->stream_bus_staged = rcb == GAS_OK && n > 0 && c->cached_n != n; // ran staged: nothing cached to compare with next time
+		if (rcb != GAS_OK) {
+			return fail(rcb);
+		}
+		if (mem == GAS_MEM_DEVICE) {
+			return GAS_OK;
+		}
+		hipError_t e = hipMemcpyAsync(out, c->d_bus_out, out_bytes, hipMemcpyDeviceToHost, c->stream);
+		if (e == hipSuccess && peaks && n > 0) {
+			e = hipMemcpyAsync(peaks, c->d_peaks, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+		}
+		if (e == hipSuccess) {
+			e = hipStreamSynchronize(c->stream);
+		}
+		if (e != hipSuccess) {
+			c->last_err = hipGetErrorString(e);
+			return fail(GAS_ERR_DEVICE);
+		}
+		return GAS_OK;
+	}
+	const uint32_t *list = same_list ? nullptr : slots;
 	c->fused_streams = all_hrtf;
 	if (mem == GAS_MEM_DEVICE) {
 		const int rc_dev = gas_process_block(c, rows, list, n, F, out, peaks, GAS_MEM_DEVICE);
@@ -3218,6 +3283,14 @@ int gas_process_block_streams(gas_ctx *c, const uint32_t *slots, uint32_t n, uin
 		return fail(GAS_ERR_DEVICE);
 	}
 	return GAS_OK;
+}
+
+int gas_process_block_streams(gas_ctx *c, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, float *peaks, uint8_t *has_frames, int mem) {
+	return process_block_streams_common(c, slots, n, frames, out, 0, false, peaks, has_frames, mem);
+}
+
+int gas_process_block_streams_buses(gas_ctx *c, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, uint32_t n_buses, float *peaks, uint8_t *has_frames, int mem) {
+	return process_block_streams_common(c, slots, n, frames, out, n_buses, true, peaks, has_frames, mem);
 }
 
 int gas_hrtf_load(gas_ctx *c, const float *hrir, uint32_t dirs, uint32_t taps) {
@@ -3512,7 +3585,10 @@ int gas_process_block_buses(gas_ctx *c, const gas_audio_frame *src, const uint32
 		}
 	}
 	// (three to six buses: one fused launch per pair of buses, the state committed by the last)
-	const bool fused_hrtf = !all_mix && all_plain_hrtf && C == 1 && uni_ok(c) && !c->fused_streams && gas_hrtf_uni_waves() == 8;
+	const bool fused_hrtf = !all_mix && all_plain_hrtf && C == 1 && uni_ok(c) && gas_hrtf_uni_waves() == 8;
+	if (c->fused_streams && !(fused_hrtf && mem == GAS_MEM_DEVICE)) {
+		return fail(GAS_ERR_INVALID_ARGUMENT); // gas_process_block_streams_buses hands over no rows: only the fused form can sample
+	}
 	const bool staged = !all_mix && all_fx && C == 1 && !fused_hrtf;
 	if (reuse && staged) {
 		return fail(GAS_ERR_INVALID_ARGUMENT); // the staged form regroups: it needs the list
@@ -3612,7 +3688,7 @@ int gas_process_block_buses(gas_ctx *c, const gas_audio_frame *src, const uint32
 			// bus b's partial rows: [b * P, (b + 1) * P); one launch per pair of buses, the last one commits the state
 			const uint32_t passes = (n_buses + 1) / 2;
 			for (uint32_t pass = 0; pass < passes; pass++) {
-				GAS_HIP(c, gas_launch_hrtf_uni(c->stream, ga, c->uni_peak_any && !c->uni_peak_all ? c->d_peak_bits : nullptr, c->uni_peak_all, c->st, c->tab, c->d_tw, F, c->hist_len, c->d_bus_partials, 2 * pass * P, nullptr, c->d_fade_env, nullptr, gas_deferred_reduce(), c->d_routes, P, 2 * pass, pass + 1 == passes));
+				GAS_HIP(c, gas_launch_hrtf_uni(c->stream, ga, c->uni_peak_any && !c->uni_peak_all ? c->d_peak_bits : nullptr, c->uni_peak_all, c->st, c->tab, c->d_tw, F, c->hist_len, c->d_bus_partials, 2 * pass * P, c->fused_streams ? c->d_cursors : nullptr, c->d_fade_env, nullptr, gas_deferred_reduce(), c->d_routes, P, 2 * pass, pass + 1 == passes));
 			}
 		} else if (staged) {
 			// effect kinds: the stages of every chain with rows out, then k_rows_accumulate_buses and one reduce over the

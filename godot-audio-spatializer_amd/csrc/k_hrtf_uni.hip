@@ -57,7 +57,7 @@ namespace {
 #define GAS_UNI_STAMP(i) do { } while (0)
 #endif
 
-// UW = waves per workgroup (one workgroup per CU): 8 = two waves per SIMD, the general form (stream sampling, two buses);
+// UW = waves per workgroup (one workgroup per CU): 8 = two waves per SIMD, the general form (stream sampling, two buses, or both);
 // 12 = three waves per SIMD (<= 168 VGPRs), float rows on one bus.  What the third wave costs in registers is paid by
 // the HRIR row: the twelve-wave form never holds it in VGPRs.  Each wave owns two 4 KiB LDS slots; the stored half
 // of the next source's row (256 float4) is copied global -> LDS by four global_load_lds_dwordx4 at the top of a trip
@@ -89,7 +89,8 @@ struct UniLds {
 // epilogue runs once per bus.  Partial rows of bus b: [b * bus_rows + p_offset + workgroup].
 // More than two buses (a playback reaches up to six, audio_spatializer.cpp:283-287): one launch per PAIR of buses --
 // bus_base names the pair (buses bus_base, bus_base + 1) and only the last launch commits the per-source state (history
-// row, previous gain, peak), so every pass transforms the same windows.
+// row, previous gain, peak, and with SRC_PCM -- gas_process_block_streams_buses -- the playback cursor), so every pass
+// samples and transforms the same windows.
 // ER (round 3): the chain [EARLY_REFLECTIONS, HRTF] in this kernel's shape -- the eight-tap gather of oracle
 // fx_early_reflections (y[i] = x[i] + sum_k g_k x[i - d_k], per-source ring of er_R frames) in front of the window, the
 // rest unchanged.  k_hrtf_ols<ER> (split frequency-domain / exact-peak workgroups, 22.5 us for cfg5) stays for the
@@ -639,7 +640,7 @@ __global__ __launch_bounds__(UW * 64, UW > 8 ? 3 : GAS_HRTF_WAVES_PER_SIMD) void
 			store_history<HQ>(st.hrtf_hist + (size_t)m.slot * HL, lane, &xq[FQ], nt_hist != 0); // new history = x_full[F .. F + HL)
 		}
 		if constexpr (SRC_PCM) {
-			if (lane == 0 && m.hf) { // advance the playback cursor (audio_spatializer.cpp:378,398)
+			if (lane == 0 && m.hf && (!BUS2 || commit)) { // advance the playback cursor (audio_spatializer.cpp:378,398); every bus pass samples the same windows, the committing one moves on
 				cursors[m.slot].pos = m.pos + m.mixed;
 				if (m.mixed != F) {
 					cursors[m.slot].has_frames = 0;
@@ -857,7 +858,7 @@ hipError_t gas_launch_hrtf_uni(hipStream_t stream, const gas_group_args &g, cons
 	if (g.n == 0) {
 		return hipSuccess;
 	}
-	if (frames % 128 != 0 || frames > 512 || hist_len != 512 - frames / 2 || (routes && (cursors || g.order)) || ((er_ring_frames || flt_kind) && (routes || cursors || g.order)) || (er_ring_frames && flt_kind)) {
+	if (frames % 128 != 0 || frames > 512 || hist_len != 512 - frames / 2 || (routes && g.order) || ((er_ring_frames || flt_kind) && (routes || cursors || g.order)) || (er_ring_frames && flt_kind)) {
 		return hipErrorInvalidValue;
 	}
 	const uint32_t wgs = gas_hrtf_uni_partials(g.n);
@@ -872,6 +873,8 @@ hipError_t gas_launch_hrtf_uni(hipStream_t stream, const gas_group_args &g, cons
 			hipLaunchKernelGGL((k_hrtf_uni<SQv, false, false, 8, false, true>), grid, block, 0, stream, g, peak_bits, all, st, tab, twiddles, partials, p_offset, cursors, fade_env, fresh, job, routes, bus_rows, bus_base, commit ? 1u : 0u, nt_hist, er_ring_frames, peak_from, peak_bit_base, flt_kind, flt_pos, mix_rate); \
 		} else if (er_ring_frames) {           \
 			hipLaunchKernelGGL((k_hrtf_uni<SQv, false, false, 8, true>), grid, block, 0, stream, g, peak_bits, all, st, tab, twiddles, partials, p_offset, cursors, fade_env, fresh, job, routes, bus_rows, bus_base, commit ? 1u : 0u, nt_hist, er_ring_frames, peak_from, peak_bit_base, flt_kind, flt_pos, mix_rate); \
+		} else if (routes && cursors) {        \
+			GAS_UNI_GO(SQv, true, true, 8);    \
 		} else if (routes) {                   \
 			GAS_UNI_GO(SQv, false, true, 8);   \
 		} else if (cursors) {                  \

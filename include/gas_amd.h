@@ -835,7 +835,25 @@ int gas_source_bind_stream(gas_ctx *ctx, uint32_t slot, uint32_t stream, uint64_
  * receives each playback's has_frames flag after this callback (audio_spatializer.cpp:398); slots whose
  * stream ended are marked draining automatically.  out / peaks are host or device pointers per `mem`. */
 int gas_process_block_streams(gas_ctx *ctx, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, float *peaks, uint8_t *has_frames, int mem);
-/* Where the playbacks of the LAST gas_process_block_streams list stand in their streams after it, in its row order:
+/* gas_process_block_buses over the windows gas_process_block_streams would have produced for the same list: every
+ * playback mixes onto its dry bus and its sends (gas_bus_routes_publish) without a source frame crossing to the device.
+ *   From the streams entry: cursor advance and lookahead delay, the fade-out at a stream's end and zeros after it,
+ *     automatic draining, has_frames, the resampled-pitch rules (GAS_ERR_UNSUPPORTED_CHAIN for pitch != 1 on a
+ *     non-resampled stream), GAS_ERR_INVALID_ARGUMENT for one slot twice.
+ *   From the bus entry: 1 <= n_buses <= GAS_MAX_BUSES; the routes snapshot; either every source GAS_KIND_3D_MIX, or every
+ *     source a non-empty effect chain on a one-pair context (anything else: GAS_ERR_UNSUPPORTED_CHAIN); peaks are those
+ *     of y before any bus factor; out ([n_buses][C][frames]) is fully overwritten, with zeros when n == 0.
+ * `mem` governs out and peaks.  A failed callback moves no cursor: everything either entry can refuse for the list
+ * (n_buses, the kinds, an empty chain, a chain on C > 1, GAS_ERR_NO_HRTF, GAS_ERR_NO_PARAMS, a duplicate) is checked
+ * before the sampler runs, and a host `out` comes back zeroed (n_buses out of range: its first
+ * min(n_buses, GAS_MAX_BUSES) buses).
+ * Routes: plain [HRTF] lists of uncompressed, non-resampled streams on a one-pair context are sampled inside the HRTF
+ * kernel (k_hrtf_uni<SRC_PCM, BUS2>, one launch per pair of buses, the cursors committed by the last); every other
+ * list the bus entry accepts (3D mix on 1..4 pairs, staged chains, resampled / ADPCM / QOA / blend-fade playbacks) has
+ * its rows sampled first and runs the device path of gas_process_block_buses over them. */
+int gas_process_block_streams_buses(gas_ctx *ctx, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out /* [n_buses][C][frames] */, uint32_t n_buses, float *peaks, uint8_t *has_frames, int mem);
+/* Where the playbacks of the LAST stream callback's list (gas_process_block_streams or gas_process_block_streams_buses,
+ * whichever ran last) stand in their streams after it, in its row order:
  * out_frames[i] = index of the next stream frame playback i will take ([ENGINE] get_playback_position x mix rate, plus
  * the playback's start frame; for a looped stream m(k) of the frames consumed).  From the host-side mirror of the cursor arithmetic: nothing is read back from the
  * device.  n must be that callback's n.  Audio thread. */

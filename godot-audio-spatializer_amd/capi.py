@@ -454,6 +454,8 @@ EXPORTS = [
     "gas_source_bind_stream",
     "gas_process_block_streams",
     "gas_process_block_streams_buses",
+    "gas_source_feed_rows",
+    "gas_stream_last_fused",
     "gas_process_block",
     "gas_bus_routes_publish",
     "gas_process_block_buses",
@@ -549,6 +551,8 @@ def load_library():
     L.gas_source_bind_stream.argtypes = [vp, u32, u32, C.c_uint64]
     L.gas_process_block_streams.argtypes = [vp, vp, u32, u32, vp, vp, vp, i32]
     L.gas_process_block_streams_buses.argtypes = [vp, vp, u32, u32, vp, u32, vp, vp, i32]
+    L.gas_source_feed_rows.argtypes = [vp, vp, vp, i32, u32, u32, u32, i32]
+    L.gas_stream_last_fused.argtypes = [vp]
     L.gas_calc_spatialization.argtypes = [vp, vp, u32, vp, vp, vp, u32, vp, u32, vp, i32]
     L.gas_calc_spatialization_areas.argtypes = [vp, vp, u32, vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, i32]
     L.gas_process_block.argtypes = [vp, vp, vp, u32, u32, vp, vp, i32]
@@ -871,6 +875,22 @@ class SpatializerContext:
         self._check(rc, "gas_process_block_streams_buses")
         return out[:n_buses], peaks[:n], hf[:n].astype(bool)
 
+    def source_feed_rows(self, slots, rows):
+        """Window rows of playbacks that are not bound to a stream, for the next stream callback: rows int16 or float32,
+        [n][F] (mono) or [n][F][2] (stereo)."""
+        s = np.ascontiguousarray(slots, dtype=np.uint32)
+        r = np.ascontiguousarray(rows)
+        assert r.dtype in (np.int16, np.float32) and r.ndim in (2, 3) and r.shape[0] == len(s)
+        fmt = PCM_S16 if r.dtype == np.int16 else PCM_F32
+        ch = 1 if r.ndim == 2 else r.shape[2]
+        frames = r.shape[1]
+        rc = self.lib.gas_source_feed_rows(self.h, _np_ptr(s) if len(s) else None, _np_ptr(r) if len(s) else None, fmt, ch, len(s), frames, MEM_HOST)
+        self._check(rc, "gas_source_feed_rows")
+
+    def stream_last_fused(self):
+        """Whether the last stream callback sampled its windows inside the HRTF kernel (else: rows first)."""
+        return bool(self.lib.gas_stream_last_fused(self.h))
+
     def hrtf_load(self, hrir):
         h = np.ascontiguousarray(hrir, dtype=np.float32)
         assert h.ndim == 3 and h.shape[1] == 2
@@ -1007,6 +1027,7 @@ class BatchedSpatializerHost:
         L.gas_host_collect_released.argtypes = [vp]
         L.gas_host_set_process_effects_fn.argtypes = [vp, vp, vp]
         L.gas_host_start_playback.argtypes = [vp, vp, vp, C.POINTER(u32)]
+        L.gas_host_set_mixed.argtypes = [vp, i32]
         self._callbacks = []  # ctypes trampolines must outlive their registration
         fx = (C.c_int32 * max(1, len(effects)))(*effects)
         h = C.c_void_p()
@@ -1018,6 +1039,10 @@ class BatchedSpatializerHost:
         if self.h:
             self.lib.gas_host_destroy(self.h)
             self.h = None
+
+    def set_mixed(self, on=True):
+        """Opt in to array / callback playbacks next to device-stream playbacks (before the first playback starts)."""
+        return self.lib.gas_host_set_mixed(self.h, int(on))
 
     def start_playback_array(self, stream):
         s = np.ascontiguousarray(stream, dtype=np.float32)

@@ -221,6 +221,7 @@ struct gas_ctx {
 	};
 	std::vector<StreamRow> stream_rows;
 	bool stream_all_hrtf = false;
+	bool stream_last_fused = false; // the last stream callback that got as far as its launches sampled inside the HRTF kernel (gas_stream_last_fused)
 	bool stream_last_buses = false; // the cached stream list was validated by gas_process_block_streams_buses (its checks differ from the mix entry's)
 	bool stream_bus_staged = false; // ... and ran the staged bus form, which regroups on every call (cached_n never names it)
 	bool stream_rows_first = getenv("GAS_STREAM_ROWS_FIRST") != nullptr && atoi(getenv("GAS_STREAM_ROWS_FIRST")) != 0; // development aid: plain [HRTF] stream lists sample rows first too (tools/time_stream_loops.py compares the routes)
@@ -230,6 +231,22 @@ struct gas_ctx {
 	bool stream_any_qoa = false; // the list holds a GAS_PCM_QOA playback: rows first, k_sample_qoa behind k_sample_sources
 	bool qoa_span = getenv("GAS_QOA_SPAN") == nullptr || atoi(getenv("GAS_QOA_SPAN")) != 0; // development aid: 0 = every load decodes from its record (k_sample_qoa.hip; tools/time_stream_qoa.py and the tests compare the paths)
 	bool stream_params_touched = false; // a parameter publish may have changed pitch_scale: re-validate
+	// gas_source_feed_rows: window rows of playbacks that are not bound to a stream, pending for the next stream callback.
+	// d_feed is the feed table the kernels read (gas_internal.h, GAS_FEED_*): [max_sources] words in the callback's row
+	// order, then two halves of max_sources rows: the rows of every call since the last callback, appended as they came
+	// (feed_place).
+	uint8_t *d_feed = nullptr;
+	size_t feed_used = 0; // end of the rows taken, as an offset into d_feed (0: emptied)
+	uint32_t feed_side = 0; // the half of the table that rows are appended in
+	std::vector<uint32_t> feed_moved; // feed_place: (slot, new word) of the rows it moved to the other half
+	uint8_t *h_feed = nullptr; // pinned staging of one GAS_MEM_HOST call
+	size_t h_feed_cap = 0;
+	hipEvent_t feed_ev = nullptr; // the last upload out of h_feed
+	std::vector<uint32_t> feed_word; // [max_sources] by slot: GAS_FEED_NONE, or where and in which format its pending row lies
+	std::vector<uint32_t> feed_slots; // the slots with a pending row
+	std::vector<uint32_t> feed_entry, feed_entry_dev; // per list entry: this callback's words, and the words the table's header holds (empty: none written)
+	uint32_t *h_feed_entry = nullptr; // [max_sources] pinned: what the header upload reads
+	hipEvent_t feed_entry_ev = nullptr; // ... and the last upload out of it
 
 	// gas_calc_spatialization staging (physics thread)
 	std::mutex calc_mu;
@@ -1758,6 +1775,18 @@ int flush_params(gas_ctx *c) {
 
 void stream_rows_sync_back(gas_ctx *c);
 
+// gas_source_feed_rows: forget the slot's pending row.  Its bytes of the feed table stay taken until the next stream
+// callback empties the table (or feed_place moves on to the table's other half).
+void feed_drop(gas_ctx *c, uint32_t slot) {
+	if (c->feed_word[slot] == GAS_FEED_NONE) {
+		return;
+	}
+	c->feed_word[slot] = GAS_FEED_NONE;
+	auto it = std::find(c->feed_slots.begin(), c->feed_slots.end(), slot);
+	*it = c->feed_slots.back();
+	c->feed_slots.pop_back();
+}
+
 // Frees requested on other threads become the audio thread's pending frees (deferred like audio_spatializer.cpp:538-547).
 void adopt_frees(gas_ctx *c) {
 	std::lock_guard<std::mutex> lk(c->alloc_mu);
@@ -1794,6 +1823,7 @@ int apply_pending_frees(gas_ctx *c) {
 			mark_dirty(c->blend_dirty_flag, c->blend_dirty_list, s);
 		}
 		c->free_list.push_back(s);
+		feed_drop(c, s); // ... nor a window row fed to the playback that is gone
 		if (c->h_cursors[s].pcm) {
 			// a freed playback lets go of its stream (gas_stream_destroy must not see it as bound for ever, and a
 			// re-allocated slot must not inherit the cursor): host mirror and device cursor both
@@ -2054,6 +2084,15 @@ void gas_ctx_destroy(gas_ctx *c) {
 	(void)hipFree(c->d_stream_slots);
 	(void)hipFree(c->d_stream_inc);
 	(void)hipHostFree(c->h_stream_inc);
+	(void)hipFree(c->d_feed);
+	(void)hipHostFree(c->h_feed);
+	(void)hipHostFree(c->h_feed_entry);
+	if (c->feed_entry_ev) {
+		(void)hipEventDestroy(c->feed_entry_ev);
+	}
+	if (c->feed_ev) {
+		(void)hipEventDestroy(c->feed_ev);
+	}
 	for (auto &s : c->streams) {
 		(void)hipFree(s.d_pcm);
 	}
@@ -2186,6 +2225,7 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 		GAS_HIP(c, hipMalloc(&c->d_stream_slots, sizeof(uint32_t) * N));
 		GAS_HIP(c, hipMalloc(&c->d_stream_inc, sizeof(uint32_t) * N));
 		GAS_HIP(c, hipHostMalloc(&c->h_stream_inc, sizeof(uint32_t) * N, hipHostMallocDefault));
+		c->feed_word.assign(N, GAS_FEED_NONE);
 		{
 			// end-of-stream ramp the stream-sampling prologue multiplies the last 64 valid frames by: tap k =
 			// 0.96^(k+1) * (64 - k) / 64, the running f32 product and the f32 divide of audio_spatializer.cpp:382-392
@@ -2423,6 +2463,7 @@ int gas_source_reset(gas_ctx *c, uint32_t slot) {
 		return GAS_ERR_BAD_SLOT;
 	}
 	GAS_HIP(c, hipSetDevice(c->cfg.device));
+	feed_drop(c, slot); // gas_source_feed_rows: a reset playback starts from silence
 	GAS_HIP(c, gas_launch_zero_slot(c->stream, c->st, slot, c->hist_len, c->cfg.er_ring_frames));
 	{ // its pool entries: zeroed by the next flush, before the next block (alloc_mu: the audio thread may be returning a
 	  // freed slot's entries; the same lock order as gas_source_alloc)
@@ -2951,6 +2992,7 @@ int gas_source_bind_stream(gas_ctx *c, uint32_t slot, uint32_t stream, uint64_t 
 	}
 	stream_rows_sync_back_fwd(c);
 	c->stream_groups_gen = UINT64_MAX;
+	feed_drop(c, slot); // gas_source_feed_rows: the stream supplies the windows from here on
 	const gas_ctx::StreamInfo &si = c->streams[stream];
 	gas_cursor cur{};
 	cur.pcm = si.d_pcm;
@@ -2995,6 +3037,61 @@ void stream_rows_sync_back(gas_ctx *c) {
 		cur.has_frames = r.has_frames;
 	}
 	c->stream_rows.clear();
+}
+
+inline size_t feed_header_bytes(const gas_ctx *c) {
+	return ((size_t)c->cfg.max_sources * sizeof(uint32_t) + 15) & ~(size_t)15;
+}
+
+// Where the next `bytes` of rows go in the feed table.  The table is allocated once, at the first feed: the header and
+// two halves of max_sources float32 stereo rows each.  Rows are appended in the current half.  When it is full -- rows
+// that were replaced, or fed while no callback ran, leave holes -- the pending rows this call does not replace (those
+// without its stamp) move to the front of the other half and the new rows follow them: together at most max_sources
+// rows, so they fit.  Everything is a copy in the context's stream order from one half into the other: no allocation and
+// no wait on the audio thread.  Nothing is committed here: feed_moved holds the moved rows' new words, and the caller
+// switches halves once its own copy is enqueued.
+int feed_place(gas_ctx *c, size_t bytes, size_t &at, bool &switched) {
+	const size_t hdr = feed_header_bytes(c), half = (size_t)c->cfg.max_sources * c->cfg.frames * sizeof(gas_audio_frame);
+	if (!c->d_feed) {
+		if (!c->h_feed_entry && hipHostMalloc(&c->h_feed_entry, (size_t)c->cfg.max_sources * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) {
+			c->h_feed_entry = nullptr;
+			return GAS_ERR_OUT_OF_MEMORY;
+		}
+		if (!c->feed_entry_ev) {
+			GAS_HIP(c, hipEventCreateWithFlags(&c->feed_entry_ev, hipEventDisableTiming));
+		}
+		if (hipMalloc(&c->d_feed, hdr + 2 * half) != hipSuccess) {
+			c->d_feed = nullptr;
+			return GAS_ERR_OUT_OF_MEMORY;
+		}
+		c->feed_used = 0;
+	}
+	if (c->feed_used < hdr) { // emptied by a callback: start over
+		c->feed_used = hdr;
+		c->feed_side = 0;
+	}
+	c->feed_moved.clear();
+	switched = false;
+	if (c->feed_used + bytes <= hdr + (c->feed_side + 1) * half) {
+		at = c->feed_used;
+		return GAS_OK;
+	}
+	switched = true;
+	const uint32_t F = c->cfg.frames;
+	size_t off = hdr + (1 - c->feed_side) * half;
+	for (uint32_t s : c->feed_slots) {
+		if (c->stamp[s] == c->stamp_gen) {
+			continue; // this call replaces it
+		}
+		const uint32_t w = c->feed_word[s];
+		const size_t rb = gas_feed_row_bytes(w, F);
+		GAS_HIP(c, hipMemcpyAsync(c->d_feed + off, c->d_feed + gas_feed_offset(w), rb, hipMemcpyDeviceToDevice, c->stream));
+		c->feed_moved.push_back(s);
+		c->feed_moved.push_back(gas_feed_word(off, (w & 2u) ? GAS_PCM_F32 : GAS_PCM_S16, (w & 1u) + 1u));
+		off += rb;
+	}
+	at = off;
+	return GAS_OK;
 }
 } // namespace
 
@@ -3045,7 +3142,11 @@ static int process_block_streams_common(gas_ctx *c, const uint32_t *slots, uint3
 				return fail(GAS_ERR_BAD_SLOT);
 			}
 			const float pitch = c->slots[slots[i]].has_params ? c->h_params[slots[i]].pitch_scale : 1.0f;
-			if (c->h_cursors[slots[i]].resampled) {
+			if (!c->h_cursors[slots[i]].pcm) {
+				// bound to no stream: a fed row or silence.  pitch_scale is the sampler's input, and whoever decodes this
+				// playback has applied it already (the host layer hands it to the playback's mix callback), as for the
+				// rows of gas_process_block
+			} else if (c->h_cursors[slots[i]].resampled) {
 				if (!(pitch >= 0.0f && pitch < 32768.0f)) {
 					return fail(GAS_ERR_INVALID_ARGUMENT);
 				}
@@ -3138,8 +3239,24 @@ static int process_block_streams_common(gas_ctx *c, const uint32_t *slots, uint3
 	}
 	// host mirror of the cursor arithmetic: which playbacks end inside this callback (audio_spatializer.cpp:380,398)
 	bool draining_changed = false;
+	// gas_source_feed_rows: which entries take a fed row is this callback's matter alone, read from the pending rows and
+	// never from the cached list -- the steady state above holds whatever is fed, not fed, or fed again under it.
+	const bool feed_pending = !c->feed_slots.empty();
+	bool any_fed = false;
+	if (feed_pending) {
+		c->feed_entry.assign(n, GAS_FEED_NONE);
+	}
 	for (uint32_t i = 0; i < n; i++) {
 		gas_ctx::StreamRow &r = c->stream_rows[i];
+		if (feed_pending && c->feed_word[slots[i]] != GAS_FEED_NONE) { // a live playback without a cursor: nothing moves, nothing ends
+			c->feed_entry[i] = c->feed_word[slots[i]];
+			any_fed = true;
+			r.draining_marked = 0; // the next callback that finds it unfed marks it draining again
+			if (has_frames) {
+				has_frames[i] = 1;
+			}
+			continue;
+		}
 		if (r.has_frames && r.resampled) { // same arithmetic as k_sample_sources' resampled branch
 			uint64_t mixed = F;
 			if (r.looped) {
@@ -3178,6 +3295,30 @@ static int process_block_streams_common(gas_ctx *c, const uint32_t *slots, uint3
 		c->cached_n = UINT32_MAX;
 		same_list = false;
 	}
+	if (any_fed && c->feed_entry != c->feed_entry_dev) { // the list or the fed set changed: the table's header follows
+		hipError_t e = hipEventSynchronize(c->feed_entry_ev); // the previous header has left the pinned words: a wait only while that upload is still queued
+		if (e == hipSuccess) {
+			std::memcpy(c->h_feed_entry, c->feed_entry.data(), (size_t)n * sizeof(uint32_t));
+			e = hipMemcpyAsync(c->d_feed, c->h_feed_entry, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
+		}
+		if (e == hipSuccess) {
+			e = hipEventRecord(c->feed_entry_ev, c->stream);
+		}
+		if (e != hipSuccess) {
+			c->feed_entry_dev.clear();
+			c->last_err = hipGetErrorString(e);
+			return fail(GAS_ERR_DEVICE);
+		}
+		c->feed_entry_dev = c->feed_entry;
+	}
+	if (feed_pending) { // one feed serves one callback; rows of slots the list does not name go with it
+		for (uint32_t s : c->feed_slots) {
+			c->feed_word[s] = GAS_FEED_NONE;
+		}
+		c->feed_slots.clear();
+		c->feed_used = 0;
+	}
+	const uint8_t *feed = any_fed ? c->d_feed : nullptr;
 	// rows for this callback live in the library's staging buffer (not needed when k_hrtf_ols samples the
 	// streams itself: every playback a plain [HRTF] chain)
 	// (GAS_FLAG_HRTF_BLEND_FADE: the stream-sampling form has no registers left for the fade, DESIGN.md 3.4 -- rows first)
@@ -3186,7 +3327,10 @@ static int process_block_streams_common(gas_ctx *c, const uint32_t *slots, uint3
 	// (GAS_PCM_IMA_ADPCM, GAS_PCM_QOA: the fused prologues read uncompressed frames only -- rows first, like a resampled playback)
 	// (buses: the fused form is k_hrtf_uni<SRC_PCM, BUS2>, which gas_process_block_buses picks on a one-pair context without a k_hrtf_ols-only mode)
 	const bool bus_fusable = !buses || (C == 1 && uni_ok(c) && gas_hrtf_uni_waves() == 8);
-	const bool all_hrtf = c->stream_all_hrtf && !c->stream_any_resampled && !c->stream_any_adpcm && !c->stream_any_qoa && !fade_on(c) && loops_fused && !c->stream_rows_first && bus_fusable; // the fused prologue samples plain playbacks only
+	// (gas_source_feed_rows: k_hrtf_uni<SRC_PCM> and k_hrtf_uni<SRC_PCM, BUS2> take fed entries; the k_hrtf_ols stream-sampling forms -- cross-fade, direction runs / order, interpolation contexts -- have no registers left for them, DESIGN.md 3.4 -- rows first)
+	const bool fed_fusable = !any_fed || uni_ok(c);
+	const bool all_hrtf = c->stream_all_hrtf && !c->stream_any_resampled && !c->stream_any_adpcm && !c->stream_any_qoa && !fade_on(c) && loops_fused && !c->stream_rows_first && bus_fusable && fed_fusable; // the fused prologue samples plain playbacks only
+	c->stream_last_fused = all_hrtf;
 	if (!all_hrtf) {
 		const size_t need = (size_t)n * F;
 		if (need > c->d_src_frames) {
@@ -3202,7 +3346,7 @@ static int process_block_streams_common(gas_ctx *c, const uint32_t *slots, uint3
 			c->d_src_frames = need;
 		}
 		if (n > 0) {
-			hipError_t e = gas_launch_sample_sources(c->stream, c->d_cursors, c->d_stream_slots, n, F, c->d_fade_env, c->d_src, c->stream_any_resampled ? c->d_stream_inc : nullptr);
+			hipError_t e = gas_launch_sample_sources(c->stream, c->d_cursors, c->d_stream_slots, n, F, c->d_fade_env, c->d_src, c->stream_any_resampled ? c->d_stream_inc : nullptr, feed);
 			if (e == hipSuccess && c->stream_any_adpcm) {
 				e = gas_launch_sample_adpcm(c->stream, c->d_cursors, c->d_stream_slots, n, F, c->d_fade_env, c->d_src, c->stream_any_resampled ? c->d_stream_inc : nullptr, c->adpcm_span);
 			}
@@ -3215,7 +3359,8 @@ static int process_block_streams_common(gas_ctx *c, const uint32_t *slots, uint3
 			}
 		}
 	}
-	const gas_audio_frame *rows = all_hrtf ? reinterpret_cast<const gas_audio_frame *>(c->d_cursors) /* unused, non-null */ : c->d_src;
+	// (fused: no float rows; the launch finds the feed table in their place when an entry is fed, else the cursor array -- k_hrtf_uni.hip)
+	const gas_audio_frame *rows = all_hrtf ? (feed ? reinterpret_cast<const gas_audio_frame *>(feed) : reinterpret_cast<const gas_audio_frame *>(c->d_cursors)) : c->d_src;
 	if (buses) {
 		// gas_process_block_buses reuses a list only for its 3D-mix and fused [HRTF] forms; the staged form needs it every time
 		const bool reuse = same_list && n > 0 && c->cached_n == n && c->bus_form_cached != 0 && c->bus_form_groups_gen == c->groups_gen;
@@ -3291,6 +3436,107 @@ int gas_process_block_streams(gas_ctx *c, const uint32_t *slots, uint32_t n, uin
 
 int gas_process_block_streams_buses(gas_ctx *c, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, uint32_t n_buses, float *peaks, uint8_t *has_frames, int mem) {
 	return process_block_streams_common(c, slots, n, frames, out, n_buses, true, peaks, has_frames, mem);
+}
+
+int gas_stream_last_fused(gas_ctx *c) {
+	return c ? (c->stream_last_fused ? 1 : 0) : GAS_ERR_INVALID_ARGUMENT;
+}
+
+int gas_source_feed_rows(gas_ctx *c, const uint32_t *slots, const void *rows, int format, uint32_t channels, uint32_t n, uint32_t frames, int mem) {
+	if (!c || (n > 0 && (!slots || !rows)) || n > c->cfg.max_sources || (format != GAS_PCM_S16 && format != GAS_PCM_F32) || (channels != 1 && channels != 2) || (mem != GAS_MEM_HOST && mem != GAS_MEM_DEVICE)) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	const uint32_t F = c->cfg.frames;
+	if (frames != F) {
+		return GAS_ERR_FRAME_COUNT;
+	}
+	{ // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
+		const int rcd = flush_deferred(c);
+		if (rcd != GAS_OK) {
+			return rcd;
+		}
+	}
+	// everything is checked before anything is taken
+	if (++c->stamp_gen == 0) {
+		std::fill(c->stamp.begin(), c->stamp.end(), 0u);
+		c->stamp_gen = 1;
+	}
+	{
+		std::lock_guard<std::mutex> alloc_lk(c->alloc_mu); // pending_free is set by gas_source_free on any thread
+		for (uint32_t i = 0; i < n; i++) {
+			if (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used || c->slots[slots[i]].pending_free) {
+				return GAS_ERR_BAD_SLOT;
+			}
+		}
+	}
+	for (uint32_t i = 0; i < n; i++) {
+		if (c->h_cursors[slots[i]].pcm) {
+			return GAS_ERR_INVALID_ARGUMENT; // bound to a stream: the sampler supplies its windows
+		}
+		if (c->stamp[slots[i]] == c->stamp_gen) {
+			return GAS_ERR_INVALID_ARGUMENT; // one playback twice in a call
+		}
+		c->stamp[slots[i]] = c->stamp_gen;
+	}
+	if (n == 0) {
+		return GAS_OK;
+	}
+	GAS_HIP(c, hipSetDevice(c->cfg.device));
+	const size_t row_bytes = (size_t)F * (format == GAS_PCM_F32 ? 4u : 2u) * channels; // a multiple of 256: frames % 128 == 0
+	const size_t bytes = (size_t)n * row_bytes;
+	if (mem == GAS_MEM_HOST && bytes > c->h_feed_cap) { // grows to the largest call: not in the steady state
+		if (c->feed_ev) {
+			GAS_HIP(c, hipEventSynchronize(c->feed_ev));
+		} else {
+			GAS_HIP(c, hipEventCreateWithFlags(&c->feed_ev, hipEventDisableTiming));
+		}
+		(void)hipHostFree(c->h_feed);
+		c->h_feed = nullptr;
+		c->h_feed_cap = 0;
+		if (hipHostMalloc(&c->h_feed, bytes, hipHostMallocDefault) != hipSuccess) {
+			return GAS_ERR_OUT_OF_MEMORY;
+		}
+		c->h_feed_cap = bytes;
+	}
+	size_t at = 0;
+	bool switched = false;
+	const int rcp = feed_place(c, bytes, at, switched);
+	if (rcp != GAS_OK) {
+		return rcp;
+	}
+	uint8_t *dst = c->d_feed + at;
+	const int rcc = [&]() -> int {
+		if (mem == GAS_MEM_DEVICE) {
+			const int rcj = join_outputs(c); // GAS_FLAG_PIPELINED_MIX: `rows` may be an earlier callback's out, still a pending sum
+			if (rcj != GAS_OK) {
+				return rcj;
+			}
+			GAS_HIP(c, hipMemcpyAsync(dst, rows, bytes, hipMemcpyDeviceToDevice, c->stream));
+			return GAS_OK;
+		}
+		GAS_HIP(c, hipEventSynchronize(c->feed_ev)); // the previous upload has left the staging: a wait only while it is still queued
+		std::memcpy(c->h_feed, rows, bytes);
+		GAS_HIP(c, hipMemcpyAsync(dst, c->h_feed, bytes, hipMemcpyHostToDevice, c->stream));
+		GAS_HIP(c, hipEventRecord(c->feed_ev, c->stream));
+		return GAS_OK;
+	}();
+	if (rcc != GAS_OK) {
+		return rcc; // nothing committed: every pending row is still where its word says
+	}
+	if (switched) {
+		c->feed_side = 1 - c->feed_side;
+		for (size_t k = 0; k + 1 < c->feed_moved.size(); k += 2) {
+			c->feed_word[c->feed_moved[k]] = c->feed_moved[k + 1];
+		}
+	}
+	for (uint32_t i = 0; i < n; i++) {
+		if (c->feed_word[slots[i]] == GAS_FEED_NONE) {
+			c->feed_slots.push_back(slots[i]);
+		} // else: replaces the row fed before; its bytes lie idle until the table is emptied
+		c->feed_word[slots[i]] = gas_feed_word(at + (size_t)i * row_bytes, format, channels);
+	}
+	c->feed_used = at + bytes;
+	return GAS_OK;
 }
 
 int gas_hrtf_load(gas_ctx *c, const float *hrir, uint32_t dirs, uint32_t taps) {

@@ -453,6 +453,21 @@ __device__ __forceinline__ gas_cursor lane_cursor(const gas_cursor *__restrict__
 	return c;
 }
 
+// gas_source_feed_rows: a fed entry rides as a playback whose stream IS its row of the feed table -- 64 frames in (the
+// window starts at stream frame 0: idx = f), never short (mixed == F: no fade, nothing ends), in the row's own format, so
+// load_window's four format branches read it as they read a stream.  The length marks it: no stream is this long, and
+// the cursor write-back leaves such an entry's slot alone (its cursor is unbound and stays so).
+#define GAS_FED_FRAMES 0xffffffffffffffffull
+__device__ __forceinline__ gas_cursor fed_cursor(const uint8_t *__restrict__ feed, uint32_t word) {
+	gas_cursor c{};
+	c.pcm = feed + gas_feed_offset(word);
+	c.frames = GAS_FED_FRAMES;
+	c.pos = GAS_LOOKAHEAD_BUFFER_SIZE;
+	c.format_channels = gas_feed_format_channels(word);
+	c.has_frames = 1;
+	return c;
+}
+
 __device__ __forceinline__ uint64_t readlane64(uint64_t v, int i) {
 	const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, i);
 	const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), i);

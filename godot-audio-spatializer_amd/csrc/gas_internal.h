@@ -150,6 +150,24 @@ struct gas_cursor {
 	uint32_t loop_mode; // gas_loop_mode; 0 = the stream plays once
 };
 
+// gas_source_feed_rows: the feed table a stream callback's kernels read, one device buffer.  Its header holds one word
+// per list entry in the callback's row order: GAS_FEED_NONE, or where the entry's fed window row lies and how it is
+// stored -- (offset from the table's base in 16-byte units) << 2 | (float32 ? 2 : 0) | (stereo ? 1 : 0).  The rows follow
+// the header, [frames] each, every one 16-byte aligned.
+#define GAS_FEED_NONE 0xffffffffu
+__host__ __device__ inline uint32_t gas_feed_word(size_t byte_offset, int format, uint32_t channels) {
+	return (uint32_t)(byte_offset >> 4) << 2 | (format == GAS_PCM_F32 ? 2u : 0u) | (channels == 2 ? 1u : 0u);
+}
+__host__ __device__ inline size_t gas_feed_offset(uint32_t word) {
+	return (size_t)(word >> 2) << 4;
+}
+__host__ __device__ inline uint32_t gas_feed_format_channels(uint32_t word) { // gas_cursor::format_channels of the row
+	return ((word & 2u ? (uint32_t)GAS_PCM_F32 : (uint32_t)GAS_PCM_S16) << 8) | ((word & 1u) + 1u);
+}
+__host__ __device__ inline size_t gas_feed_row_bytes(uint32_t word, uint32_t F) {
+	return (size_t)F * (word & 2u ? 4u : 2u) * ((word & 1u) + 1u);
+}
+
 // The index map m of gas_stream_set_loop (gas_amd.h), and its incremental form for the frames of one window.
 __host__ __device__ inline uint64_t gas_loop_map(uint64_t k, uint64_t b, uint32_t L, uint32_t mode) {
 	if (mode == GAS_LOOP_DISABLED || k < b) {
@@ -455,7 +473,7 @@ hipError_t gas_launch_fx_stereo(hipStream_t stream, int kind, const gas_group_ar
 hipError_t gas_launch_fx_filter(hipStream_t stream, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t chain_pos, float mix_rate, gas_audio_frame *rows_out);
 hipError_t gas_launch_scatter_params(hipStream_t stream, gas_params *table, const gas_params *upload, const uint32_t *slots, uint32_t n);
 hipError_t gas_launch_calc_spatialization(hipStream_t stream, const gas_spatializer3d_config *cfgs, const uint32_t *cfg_index, const gas_source_pose *poses, const gas_listener *listeners, uint32_t n_listeners, const uint32_t *slots, uint32_t n, gas_params *table, uint8_t *was_further, gas_params *out_params, const gas_area_send *areas = nullptr, const float *listener_area_pos = nullptr, gas_audio_frame *out_reverb = nullptr, gas_hrtf_blend *blend_table = nullptr /* GAS_FLAG_HRTF_INTERPOLATE: the slots' bilinear blend rows are written too */);
-hipError_t gas_launch_sample_sources(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc /* 16.16 step per row for resampled playbacks, or nullptr */);
+hipError_t gas_launch_sample_sources(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc /* 16.16 step per row for resampled playbacks, or nullptr */, const uint8_t *feed = nullptr /* the feed table when an entry of the list is fed (GAS_FEED_NONE, above) */);
 hipError_t gas_launch_sample_adpcm(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc, bool span /* false: every load decodes from its checkpoint (GAS_ADPCM_SPAN=0) */); // the GAS_PCM_IMA_ADPCM rows of the same list, after gas_launch_sample_sources
 hipError_t gas_launch_sample_qoa(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc, bool span /* false: every load decodes from its record (GAS_QOA_SPAN=0) */); // the GAS_PCM_QOA rows of the same list, after gas_launch_sample_sources
 hipError_t gas_launch_noop(hipStream_t stream); // event-timer calibration

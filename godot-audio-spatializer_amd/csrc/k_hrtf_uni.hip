@@ -198,6 +198,15 @@ __global__ __launch_bounds__(UW * 64, UW > 8 ? 3 : GAS_HRTF_WAVES_PER_SIMD) void
 		lm.pdir = lm.dir;
 		if constexpr (SRC_PCM) {
 			lm.cur = lane_cursor(cursors, lm.slot);
+			// gas_source_feed_rows: this form reads no float rows, and g.src names the feed table when an entry of the list
+			// is fed (the cursor array itself when none is)
+			const uint8_t *feed = reinterpret_cast<const uint8_t *>(g.src);
+			if (feed != reinterpret_cast<const uint8_t *>(cursors)) {
+				const uint32_t word = reinterpret_cast<const uint32_t *>(feed)[lm.row];
+				if (word != GAS_FEED_NONE) {
+					lm.cur = fed_cursor(feed, word);
+				}
+			}
 		}
 		const uint32_t e = my_entry;
 		my_flag = (peak_all || e >= peak_from) ? 1u : (peak_bits ? (peak_bits[(e + peak_bit_base) >> 5] >> ((e + peak_bit_base) & 31)) & 1u : 0u);
@@ -640,7 +649,7 @@ __global__ __launch_bounds__(UW * 64, UW > 8 ? 3 : GAS_HRTF_WAVES_PER_SIMD) void
 			store_history<HQ>(st.hrtf_hist + (size_t)m.slot * HL, lane, &xq[FQ], nt_hist != 0); // new history = x_full[F .. F + HL)
 		}
 		if constexpr (SRC_PCM) {
-			if (lane == 0 && m.hf && (!BUS2 || commit)) { // advance the playback cursor (audio_spatializer.cpp:378,398); every bus pass samples the same windows, the committing one moves on
+			if (lane == 0 && m.hf && m.len != GAS_FED_FRAMES && (!BUS2 || commit)) { // advance the playback cursor (audio_spatializer.cpp:378,398); every bus pass samples the same windows, the committing one moves on; a fed entry has no cursor to move
 				cursors[m.slot].pos = m.pos + m.mixed;
 				if (m.mixed != F) {
 					cursors[m.slot].has_frames = 0;

@@ -144,7 +144,7 @@ __global__ __launch_bounds__(256) void k_sample_adpcm(gas_cursor *__restrict__ c
 	gas_cursor *cp = cursors + slots[e];
 	const gas_cursor c = *cp;
 	if ((c.format_channels >> 8) != GAS_PCM_IMA_ADPCM) {
-		return; // k_sample_sources' row
+		return; // k_sample_sources' row (a fed entry's too: its slot is unbound, the cursor all zero)
 	}
 	const uint32_t ch = c.format_channels & 0xff;
 	const uint64_t inc = (c.resampled && row_inc) ? row_inc[e] : 65536u;

@@ -137,7 +137,7 @@ __global__ __launch_bounds__(256) void k_sample_qoa(gas_cursor *__restrict__ cur
 	gas_cursor *cp = cursors + slots[e];
 	const gas_cursor c = *cp;
 	if ((c.format_channels >> 8) != GAS_PCM_QOA) {
-		return; // k_sample_sources' or k_sample_adpcm's row
+		return; // k_sample_sources' or k_sample_adpcm's row (a fed entry's too: its slot is unbound, the cursor all zero)
 	}
 	const uint32_t ch = c.format_channels & 0xff;
 	const uint64_t inc = (c.resampled && row_inc) ? row_inc[e] : 65536u;

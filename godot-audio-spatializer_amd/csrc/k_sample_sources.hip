@@ -9,6 +9,7 @@
 // the reference's envelope 0.96^(j+1) * (64 - j) / 64 (:380-396; table computed on the host with the same f32
 // recurrence), everything after is zero, and has_frames clears (:398); afterwards the row is all zeros (:405-408).
 // One wave per playback row, lane-contiguous 8-byte stores; int16 -> float as s / 32768, mono feeds both ears.
+// An entry with a row in the feed table (gas_source_feed_rows) takes that row instead, converted the same way: fed_row.
 // The row logic itself is gas_sample_row.h's, shared with k_sample_adpcm.hip and k_sample_qoa.hip; this file reads the uncompressed formats.
 #include "gas_sample_row.h"
 
@@ -41,11 +42,47 @@ struct pcm_src { // gas_sample_row's frame source
 	}
 };
 
-__global__ __launch_bounds__(256) void k_sample_sources(gas_cursor *__restrict__ cursors, const uint32_t *__restrict__ slots, uint32_t n, uint32_t F, const float *__restrict__ fade_env, gas_audio_frame *__restrict__ rows, const uint32_t *__restrict__ row_inc) {
+// gas_source_feed_rows: the window row of an entry that is not bound to a stream, converted from the feed table (the
+// streams' conversion; no cursor is read or written).  A lane takes two frames per trip -- F is a multiple of 128 -- so
+// every store is 16 bytes, and so is the load of a float32 stereo row.
+__device__ __forceinline__ void fed_row(const uint8_t *__restrict__ feed, uint32_t word, gas_audio_frame *__restrict__ row, uint32_t F, int lane) {
+	const uint8_t *p = feed + gas_feed_offset(word);
+	for (uint32_t i = 2 * (uint32_t)lane; i < F; i += 128) {
+		float4 v;
+		switch (word & 3u) {
+			case 0: { // int16 mono
+				const short2 s = *reinterpret_cast<const short2 *>(p + (size_t)i * 2);
+				const float a = (float)s.x / 32768.0f, b = (float)s.y / 32768.0f;
+				v = make_float4(a, a, b, b);
+			} break;
+			case 1: { // int16 stereo
+				const short4 s = *reinterpret_cast<const short4 *>(p + (size_t)i * 4);
+				v = make_float4((float)s.x / 32768.0f, (float)s.y / 32768.0f, (float)s.z / 32768.0f, (float)s.w / 32768.0f);
+			} break;
+			case 2: { // float32 mono
+				const float2 s = *reinterpret_cast<const float2 *>(p + (size_t)i * 4);
+				v = make_float4(s.x, s.x, s.y, s.y);
+			} break;
+			default: // float32 stereo
+				v = *reinterpret_cast<const float4 *>(p + (size_t)i * 8);
+				break;
+		}
+		*reinterpret_cast<float4 *>(row + i) = v;
+	}
+}
+
+__global__ __launch_bounds__(256) void k_sample_sources(gas_cursor *__restrict__ cursors, const uint32_t *__restrict__ slots, uint32_t n, uint32_t F, const float *__restrict__ fade_env, gas_audio_frame *__restrict__ rows, const uint32_t *__restrict__ row_inc, const uint8_t *__restrict__ feed) {
 	const int lane = threadIdx.x & 63;
 	const uint32_t e = blockIdx.x * 4 + (threadIdx.x >> 6);
 	if (e >= n) {
 		return;
+	}
+	if (feed) { // wave-uniform
+		const uint32_t word = reinterpret_cast<const uint32_t *>(feed)[e];
+		if (word != GAS_FEED_NONE) {
+			fed_row(feed, word, rows + (size_t)e * F, F, lane);
+			return;
+		}
 	}
 	gas_cursor *cp = cursors + slots[e];
 	const gas_cursor c = *cp;
@@ -59,10 +96,10 @@ __global__ __launch_bounds__(256) void k_sample_sources(gas_cursor *__restrict__
 
 } // namespace
 
-hipError_t gas_launch_sample_sources(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc) {
+hipError_t gas_launch_sample_sources(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc, const uint8_t *feed) {
 	if (n == 0) {
 		return hipSuccess;
 	}
-	hipLaunchKernelGGL(k_sample_sources, dim3((n + 3) / 4), dim3(256), 0, stream, cursors, slots, n, frames, fade_env, rows, row_inc);
+	hipLaunchKernelGGL(k_sample_sources, dim3((n + 3) / 4), dim3(256), 0, stream, cursors, slots, n, frames, fade_env, rows, row_inc, feed);
 	return hipGetLastError();
 }

@@ -39,6 +39,7 @@
 #pragma weak gas_hrtf_blend_publish
 #pragma weak gas_stream_get_loop
 #pragma weak gas_sidechain_set
+#pragma weak gas_source_feed_rows
 
 namespace {
 
@@ -128,7 +129,8 @@ struct gas_host {
 	// ---- shared between threads ----
 	std::atomic<uint32_t> next_id{ 1 };
 	std::atomic<int> node_count{ 0 }; // playbacks started and not yet reaped
-	std::atomic<int> mode{ 0 }; // 0 undecided, 1 callback/array playbacks, 2 device-stream playbacks
+	std::atomic<int> mode{ 0 }; // 0 undecided, 1 callback/array playbacks, 2 device-stream playbacks, 3 both (gas_host_set_mixed)
+	std::atomic<bool> mixed{ false }; // gas_host_set_mixed: the first start decides for mode 3
 	std::atomic<float> disable_threshold_db{ -80.0f }; // audio_spatializer.h:87
 	std::mutex reg_mu; // id -> shared state, for the control side's lookups
 	std::unordered_map<uint32_t, std::shared_ptr<Shared>> registry;
@@ -151,6 +153,7 @@ struct gas_host {
 	std::vector<gas_audio_frame> window; // [n + 64]
 	std::vector<gas_audio_frame> rows; // [playbacks][n]
 	std::vector<uint32_t> slots;
+	std::vector<uint32_t> fed_slots; // mixed host: the slots of `rows`, which then holds the callback / array playbacks' windows only
 	std::vector<Playback *> row_owner;
 	std::vector<float> peaks;
 	std::vector<uint8_t> live_out;
@@ -355,8 +358,11 @@ struct gas_host {
 		rows.clear();
 		slots.clear();
 		row_owner.clear();
-		const bool device_streams = mode.load() == 2;
-		if (!device_streams) {
+		const int mode_now = mode.load();
+		const bool device_streams = mode_now >= 2; // one stream callback over the whole list
+		const bool feeds = mode_now != 2; // some windows are built here
+		fed_slots.clear();
+		if (feeds) {
 			window.resize((size_t)n + TAIL);
 		}
 		gas_host_process_effects_fn fx_hook;
@@ -375,9 +381,10 @@ struct gas_host {
 				pb->pitch_scale = pb->params.pitch_scale;
 				gas_params_publish(ctx, pb->slot, &pb->params);
 			}
-			if (!device_streams) {
+			if (feeds && !pb->on_device) {
 				build_window(pb, window.data(), n);
 				rows.insert(rows.end(), window.begin(), window.begin() + n); // the DSP consumes [0, n)
+				fed_slots.push_back(pb->slot);
 			}
 			slots.push_back(pb->slot);
 			row_owner.push_back(pb);
@@ -387,12 +394,22 @@ struct gas_host {
 		int rc;
 		if (device_streams) { // the library samples the windows itself and reports has_frames per row
 			live_out.assign((size_t)count + 1, 0);
+			rc = GAS_OK;
+			if (!fed_slots.empty()) { // mixed host: the windows built above ride in the stream callback, in the list's one fixed order
+				rc = gas_source_feed_rows(ctx, fed_slots.data(), rows.data(), GAS_PCM_F32, 2, (uint32_t)fed_slots.size(), (uint32_t)n, GAS_MEM_HOST);
+			}
+			if (rc != GAS_OK) {
+				return rc; // `mix` is the zero fill from above
+			}
 			rc = gas_process_block_streams(ctx, slots.data(), count, (uint32_t)n, mix.data(), peaks.data(), live_out.data(), GAS_MEM_HOST);
 			if (rc == GAS_OK) {
 				positions.resize((size_t)count + 1);
 				const bool have_pos = gas_stream_positions(ctx, count, positions.data()) == GAS_OK; // the library's mirror of the device cursors
 				for (uint32_t r = 0; r < count; r++) {
 					Playback *pb = row_owner[r];
+					if (!pb->on_device) {
+						continue; // a fed playback: position and stream_live are build_window's, as in a host without device streams
+					}
 					if (have_pos && pb->device_looped) {
 						pb->consumed = positions[r]; // m(k): the stream frame taken next
 					} else if (have_pos && positions[r] >= pb->device_start) {
@@ -508,12 +525,23 @@ void gas_host_destroy(gas_host *h) { // no thread may be inside the host any mor
 }
 
 static int start_common(gas_host *h, std::unique_ptr<Playback> pb, int want_mode, uint32_t *out_id) {
+	if (h->mixed.load()) {
+		want_mode = 3; // every kind of start is welcome
+	}
 	int undecided = 0;
 	if (!h->mode.compare_exchange_strong(undecided, want_mode) && undecided != want_mode) {
-		return GAS_ERR_KIND_MISMATCH; // a host serves callback/array playbacks or device streams, not both
+		return GAS_ERR_KIND_MISMATCH; // without gas_host_set_mixed a host serves callback/array playbacks or device streams, not both
 	}
 	h->empty_graveyard();
 	return h->enqueue_start(std::move(pb), out_id);
+}
+
+int gas_host_set_mixed(gas_host *h, int on) {
+	if (!h || h->mode.load() != 0 || (on && !gas_source_feed_rows)) {
+		return GAS_ERR_INVALID_ARGUMENT; // a playback has started: the host's kind is decided
+	}
+	h->mixed.store(on != 0);
+	return GAS_OK;
 }
 
 int gas_host_start_playback(gas_host *h, gas_host_stream_mix_fn mix, void *user, uint32_t *out_id) {

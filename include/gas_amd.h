@@ -858,6 +858,40 @@ int gas_process_block_streams_buses(gas_ctx *ctx, const uint32_t *slots, uint32_
  * the playback's start frame; for a looped stream m(k) of the frames consumed).  From the host-side mirror of the cursor arithmetic: nothing is read back from the
  * device.  n must be that callback's n.  Audio thread. */
 int gas_stream_positions(gas_ctx *ctx, uint32_t n, uint64_t *out_frames);
+/* NEW.  The 64-frame-delayed window (what gas_process_block's src row holds) of playbacks that are NOT bound to a
+ * stream, for the next stream callback: a playback the host decodes (Ogg Vorbis, MP3, a generator, a microphone) next
+ * to device-resident ones, in one list and one fixed-order mix.
+ *   rows      [n][frames] frames of `format` (GAS_PCM_S16 or GAS_PCM_F32 only) and `channels` (1 or 2), row i for
+ *             slots[i].  Converted as streams are: s / 32768, mono feeds both ears.
+ *   mem       GAS_MEM_HOST: `rows` has been consumed when the call returns -- copied into pinned staging (which grows
+ *             to the largest call made so far, so not in the steady state) and uploaded from there; the call waits only
+ *             while the previous call's upload is still queued.  GAS_MEM_DEVICE: the call enqueues a device copy in the
+ *             context's stream order, as gas_sidechain_set does: `rows` need only be valid at that point of the stream.
+ *             Callbacks recorded or deferred under GAS_FLAG_BATCHED_LAUNCH run first.
+ * In the next gas_process_block_streams / gas_process_block_streams_buses that passes its validation, a list entry whose
+ * slot has a pending row takes that row as its window, reports has_frames = 1, is not auto-marked draining (a mark an
+ * earlier, unfed callback left stays until gas_source_set_draining clears it), moves no cursor and reports 0 in
+ * gas_stream_positions.  The callback's mix, peaks and bus outputs are those of gas_process_block[_buses] over the rows
+ * R, R[i] the sampler's window where entry i is a stream playback and the converted fed row where it is fed.
+ * A pending row: the callback that uses it consumes it (one feed serves one callback); a later feed of the same slot
+ * before that callback replaces it, and several calls accumulate; a callback that fails validation leaves it where it
+ * is, as it leaves the cursors; that callback drops the pending row of a slot its list does not name;
+ * gas_source_free, gas_source_reset and gas_source_bind_stream of the slot drop it.  An unbound slot without a pending
+ * row behaves as ever: a silent row, has_frames = 0, marked draining.
+ * Routes: a plain [HRTF] list keeps its one-launch forms with fed entries (k_hrtf_uni<SRC_PCM> and
+ * k_hrtf_uni<SRC_PCM, BUS2> read a fed row as a stream window); on a cross-fade, direction-run, direction-order or
+ * interpolation context -- the k_hrtf_ols stream-sampling forms -- a callback with a fed entry samples its rows first.
+ * Errors, each leaving nothing taken: GAS_ERR_INVALID_ARGUMENT for a bad format, channels or mem, a slot bound to a
+ * stream, a slot named twice in one call; GAS_ERR_BAD_SLOT for a slot that is not in use; GAS_ERR_FRAME_COUNT for
+ * frames != cfg.frames; GAS_ERR_DEVICE for a HIP failure (GAS_ERR_OUT_OF_MEMORY when the feed table -- header + 2 x max_sources float32 stereo rows of device
+ * memory, allocated by the first call -- or the pinned staging cannot be allocated).  pitch_scale of a playback that is
+ * bound to no stream is not looked at by the stream callbacks: whoever decodes it has applied it, as for the rows of
+ * gas_process_block.
+ * Audio thread. */
+int gas_source_feed_rows(gas_ctx *ctx, const uint32_t *slots, const void *rows /* [n][frames] */, int format, uint32_t channels, uint32_t n, uint32_t frames, int mem);
+/* Diagnostic: 1 if the last stream callback that reached its launches sampled its windows inside the HRTF kernel (the
+ * fused route), 0 if it sampled rows first; GAS_ERR_INVALID_ARGUMENT for ctx == NULL. */
+int gas_stream_last_fused(gas_ctx *ctx);
 
 /* ---- measurement ------------------------------------------------------- */
 /* on = 0 off, 1 = bracket the dominant launch of every callback with HIP events, N > 1 = of every Nth callback. */

@@ -10,7 +10,7 @@
  * engine's AudioStreamPlayback::mix is a plain callback.
  *
  * Threading contract (the reference's split, audio_spatializer.h:135-138, with its SafeList / SafeFlag / Mutex roles):
- *   - control entries -- gas_host_start_playback*, gas_host_stop_playback, gas_host_set_spatializer_parameters,
+ *   - control entries -- gas_host_set_mixed, gas_host_start_playback*, gas_host_stop_playback, gas_host_set_spatializer_parameters,
  *     gas_host_set_effect_settings, gas_host_set_effect_settings_dyn, gas_host_set_effect_settings_line, gas_host_set_effect_settings_eq, gas_host_set_effect_settings_mod, gas_host_set_effect_settings_stereo, gas_host_set_effect_settings_filter, gas_host_set_hrtf_blend, gas_host_set_playback_disable_threshold_db, gas_host_is_playback_active, gas_host_set_playback_paused,
  *     gas_host_is_playback_paused, gas_host_get_playback_position, gas_host_playback_count, gas_host_set_release_fn,
  *     gas_host_collect_released, gas_host_set_process_effects_fn -- may be
@@ -49,10 +49,18 @@ int gas_host_start_playback(gas_host *host, gas_host_stream_mix_fn mix, void *us
 int gas_host_start_playback_array(gas_host *host, const gas_audio_frame *stream, int64_t stream_frames, uint32_t *out_id);
 /* A playback over a device-resident stream (gas_stream_create): nothing crosses PCIe per callback, the source window
  * and fade-out are produced on the GPU (gas_process_block_streams).  A host serves either callback/array playbacks
- * or device-stream playbacks, not a mixture (GAS_ERR_KIND_MISMATCH).  A stream with a loop (gas_stream_set_loop) plays
+ * or device-stream playbacks, not a mixture (GAS_ERR_KIND_MISMATCH), unless gas_host_set_mixed opted in.  A stream with a loop (gas_stream_set_loop) plays
  * until gas_host_stop_playback; start_frame is then a position on the unrolled timeline and
  * gas_host_get_playback_position reports the wrapped stream frame that is taken next. */
 int gas_host_start_playback_device_stream(gas_host *host, uint32_t stream, uint64_t start_frame, uint32_t *out_id);
+/* Opt in (on != 0) to callback, array and device-stream playbacks in ONE host: an Ogg Vorbis or MP3 emitter, a generator
+ * or a microphone (decoded on the CPU) next to WAV emitters whose streams are device-resident, in one list and one
+ * fixed-order mix.  Per callback the host builds the windows of its callback / array playbacks as ever (lookahead,
+ * fade-out, gate), publishes them with one gas_source_feed_rows and runs one gas_process_block_streams over the whole
+ * list; has_frames, reaping and gas_host_get_playback_position keep their per-kind meaning.  Call it before the first
+ * playback starts: afterwards the host's kind is decided and the call is GAS_ERR_INVALID_ARGUMENT.  Off is the default.
+ * Control thread. */
+int gas_host_set_mixed(gas_host *host, int on);
 /* stop_playback_stream (audio_spatializer.cpp:98-113): active = false; the audio thread reaps it. */
 int gas_host_stop_playback(gas_host *host, uint32_t id);
 /* set_spatializer_parameters (audio_spatializer.cpp:558-564), per playback. */

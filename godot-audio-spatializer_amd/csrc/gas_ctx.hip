@@ -135,6 +135,8 @@ struct gas_ctx {
 	std::vector<uint32_t> free_inbox; // frees requested since the audio thread last looked (adopt_frees)
 	std::vector<uint32_t> stamp; // duplicate detection per block
 	uint32_t stamp_gen = 0;
+	std::vector<uint32_t> calc_stamp; // the same for gas_calc_spatialization's slot list (physics thread, under calc_mu)
+	uint32_t calc_stamp_gen = 0;
 
 	std::mutex params_mu;
 	gas_params *h_params = nullptr; // pinned [max_sources], latest published value
@@ -1745,7 +1747,8 @@ int fx_reserve(gas_ctx *c, int f, uint32_t count0, uint32_t count1) {
 	return GAS_OK;
 }
 
-int flush_params(gas_ctx *c) {
+// Host-published gas_params rows -> the slot-indexed device table.
+int flush_param_rows(gas_ctx *c) {
 	uint32_t m = 0;
 	{
 		std::lock_guard<std::mutex> lk(c->params_mu);
@@ -1765,7 +1768,12 @@ int flush_params(gas_ctx *c) {
 		GAS_HIP(c, gas_launch_scatter_params(c->stream, c->st.params, c->d_upload, c->d_upload_slots, m));
 		GAS_HIP(c, hipStreamSynchronize(c->stream));
 	}
-	int rc = fx_flush(c, FX_BASIC); // (the blend rows keep their place between the first two families)
+	return GAS_OK;
+}
+
+int flush_params(gas_ctx *c) {
+	int rc = flush_param_rows(c);
+	rc = rc != GAS_OK ? rc : fx_flush(c, FX_BASIC); // (the blend rows keep their place between the first two families)
 	rc = rc != GAS_OK ? rc : flush_hrtf_blend(c);
 	for (int f = FX_BASIC + 1; f < FX_FAMILIES && rc == GAS_OK; f++) {
 		rc = fx_flush(c, f);
@@ -2266,6 +2274,7 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 	c->h_routes.assign(N, gas_bus_route_default());
 	c->h_cursors.assign(N, gas_cursor{});
 	c->stamp.assign(N, 0);
+	c->calc_stamp.assign(N, 0);
 	c->dirty_flag.assign(N, 0);
 	if (blend_on(c)) {
 		c->h_blend.assign(N, gas_hrtf_blend{});
@@ -2712,11 +2721,28 @@ int gas_calc_spatialization_areas(gas_ctx *c, const gas_spatializer3d_config *cf
 		return GAS_OK;
 	}
 	std::lock_guard<std::mutex> lk(c->calc_mu);
+	if (++c->calc_stamp_gen == 0) {
+		std::fill(c->calc_stamp.begin(), c->calc_stamp.end(), 0u);
+		c->calc_stamp_gen = 1;
+	}
+	for (uint32_t i = 0; i < n; i++) {
+		if (c->calc_stamp[slots[i]] == c->calc_stamp_gen) {
+			return GAS_ERR_INVALID_ARGUMENT; // one playback twice: two lanes would race on its table row and its latch
+		}
+		c->calc_stamp[slots[i]] = c->calc_stamp_gen;
+	}
 	GAS_HIP(c, hipSetDevice(c->cfg.device));
 	{
 		int rcp = flush_pending_params(c);
 		if (rcp != GAS_OK) {
 			return rcp;
+		}
+	}
+	{ // rows published from the host before this call reach the table first: the launch keeps their fields it does not
+	  // write (early reflections, shelf, hrtf_* without a grid) and its own are not overwritten by them at the next callback
+		int rcr = flush_param_rows(c);
+		if (rcr != GAS_OK) {
+			return rcr;
 		}
 	}
 	{ // GAS_FLAG_HRTF_INTERPOLATE: blend rows published before this call reach the table first, so the launch's rows win

@@ -716,7 +716,13 @@ typedef struct gas_listener { /* orthonormalized global transform of the camera 
 #define GAS_MAX_SPATIALIZER_CONFIGS 64
 
 /* cfgs, cfg_index ([n] or NULL = config 0 for all), listeners and slots are host arrays; poses (and out_params,
- * [n] gas_params, may be NULL) are host or device pointers according to `mem`.  Physics thread. */
+ * [n] gas_params, may be NULL) are host or device pointers according to `mem`.  A slot named twice in `slots` is refused
+ * with GAS_ERR_INVALID_ARGUMENT before anything is uploaded, as gas_process_block refuses it (two lanes would race on
+ * the slot's row and latch).  Rows published from the host before the call (gas_params_publish[_batch]) are uploaded
+ * before the launch: the launch overwrites only the fields it generates (mix_volumes, pitch_scale, linear_attenuation,
+ * the cutoff, update_parameters, and hrtf_* when the config has a grid) and out_params returns the whole row, the
+ * published early-reflection and shelf fields included.  The update_parameters latch (:472-479) is per slot and starts clear for a newly allocated
+ * slot and after gas_source_reset.  Physics thread. */
 int gas_calc_spatialization(gas_ctx *ctx, const gas_spatializer3d_config *cfgs, uint32_t n_cfgs, const uint32_t *cfg_index, const gas_source_pose *poses, const gas_listener *listeners, uint32_t n_listeners, const uint32_t *slots, uint32_t n, gas_params *out_params, int mem);
 
 /* The same with the Area3D branches of calculate_spatialization.  The physics queries stay on the

@@ -3,6 +3,8 @@ calculate_spatialization's arithmetic (audio_spatializer_3d.cpp:103-151, 277-479
 import numpy as np
 import pytest
 
+import calc_spat_ref
+
 pytestmark = pytest.mark.gpu
 
 
@@ -77,7 +79,11 @@ def test_calc_spatialization_matches_oracle(gas, ob, n_listeners):
             np.testing.assert_array_equal(got["attenuation_filter_cutoff_hz"], want["attenuation_filter_cutoff_hz"])
             np.testing.assert_array_equal(got["update_parameters"], want["update_parameters"])
             np.testing.assert_allclose(got["hrtf_gain"], want["hrtf_gain"], rtol=3e-5, atol=1e-8)
-            assert (got["hrtf_dir"] != want["hrtf_dir"]).mean() < 1e-3  # grid-cell boundaries may round differently
+            differ = got["hrtf_dir"] != want["hrtf_dir"]
+            assert differ.mean() < 1e-3  # grid-cell boundaries may round differently ...
+            # ... and nowhere else: the float64 reference puts every such row within 1e-4 grid units of a rounding border
+            margins = calc_spat_ref.calc(cfgs, cfg_index, poses, listeners, np.zeros(n, np.int32))["margins"]  # (the direction does not depend on the latch)
+            assert calc_spat_ref.on_grid_border(margins)[differ].all()
             assert got["hrtf_dir"].max() < 32 * 9
 
 

@@ -119,8 +119,6 @@ struct gas_ctx {
 	uint32_t batch_depth = 2; // callbacks per launch (gas_ctx_set_batch_depth), <= GAS_HRTF_MULTI_MAX_BLOCKS
 	int bus_form_cached = 0; // form of the last gas_process_block_buses whose list can be reused: 1 3D mix, 2 fused [HRTF], 0 none
 	uint64_t bus_form_groups_gen = 0;
-	bool force_staged = false; // gas_process_block_buses over effect kinds: every chain runs staged (rows out), the rows are mixed per bus
-	const gas_bus_args *run_buses = nullptr; // set for the duration of that run_groups
 	uint32_t partial_planes = 1; // planes of d_partials (1 ordered, 2 pipelined, 2 x max batch depth batched)
 	bool prof_multi = false; // the timed launch was k_hrtf_multi
 	uint32_t hist_len = 0;
@@ -211,8 +209,6 @@ struct gas_ctx {
 	// parameter rows published from device memory for the cached slot list (row order), not yet in the table
 	const gas_params *pending_params = nullptr;
 	uint32_t pending_n = 0;
-	const gas_params *fresh_for_launch = nullptr; // set for the duration of one run_groups
-	bool fused_streams = false; // this callback's HRTF launch samples the bound streams itself (no materialised rows)
 	struct StreamRow { // compact mirror of the cached list's cursors: the per-callback host loop touches only this
 		uint64_t remaining = 0;
 		uint32_t has_frames = 0, draining_marked = 0;
@@ -712,17 +708,89 @@ int free_plane(const gas_ctx *c, const std::vector<int> &taken) {
 	return -1;
 }
 
+// Where a callback's rows come from: float rows, or "fused" -- none, the HRTF launch samples the bound streams itself.
+struct RowSource {
+	const gas_audio_frame *rows = nullptr; // [n][F]
+	gas_cursor *cursors = nullptr; // non-null: fused, the slot-indexed cursor array
+	const uint8_t *feed = nullptr; // fused only: the feed table when an entry of the list is fed (gas_source_feed_rows)
+	bool fused() const {
+		return cursors != nullptr;
+	}
+};
+
+// One callback over already-grouped entries: everything run_groups is told.
+struct RunArgs {
+	RowSource src;
+	const uint32_t *slots = nullptr; // [n_total] sorted by launch group
+	const uint32_t *rows = nullptr; // [n_total] row of src (and of peaks) per entry, or nullptr (= identity)
+	const Group *groups = nullptr; // [G_COUNT]
+	const std::vector<ChainRange> *ranges = nullptr; // sub-runs of groups[G_FX_GENERIC]
+	uint32_t n_total = 0;
+	gas_audio_frame *out = nullptr;
+	float *peaks = nullptr; // [n_total][2]
+	uint32_t channel_begin = 0, channel_count = 1;
+	int force_mode = -1; // >= 0: the 3D groups run this gas_biquad_mode
+	bool use_order = false; // the context's cached processing orders (d_order) apply
+	bool pipelined = false; // the sum may be left to the next callback (GAS_FLAG_PIPELINED_MIX)
+	const gas_bus_args *buses = nullptr; // gas_process_block_buses over effect kinds: the staged chains' rows are mixed per bus
+	const gas_params *fresh = nullptr; // device-published parameter rows in row order, not yet in the table: the HRTF launches read them and write them through
+};
+
+// A callback over the context's own cached list.
+RunArgs own_list(const gas_ctx *c, const RowSource &src, uint32_t n, gas_audio_frame *out, float *peaks) {
+	RunArgs a;
+	a.src = src;
+	a.slots = c->d_slots;
+	a.rows = c->cached_identity_rows ? nullptr : c->d_rows;
+	a.groups = c->groups;
+	a.ranges = &c->chain_ranges;
+	a.n_total = n;
+	a.out = out;
+	a.peaks = peaks;
+	return a;
+}
+
+// The plain-[HRTF] group of the context's own list, for a launch that covers exactly it.
+gas_group_args own_hrtf_group(const gas_ctx *c, const gas_audio_frame *src, uint32_t n, float *peaks) {
+	const Group &gr = c->groups[G_FX_HRTF];
+	gas_group_args ga;
+	ga.src = src;
+	ga.rows = c->cached_identity_rows ? nullptr : c->d_rows + gr.offset;
+	ga.slots = gr.contiguous ? nullptr : c->d_slots + gr.offset; // a contiguous slot range needs no list on the device
+	ga.slot_base = gr.contiguous ? gr.slot_base : 0;
+	ga.n = n;
+	ga.peaks = peaks;
+	return ga;
+}
+
+// The fields every HRTF launch of this context shares.
+gas_hrtf_launch_common hrtf_common(const gas_ctx *c) {
+	gas_hrtf_launch_common k;
+	k.stream = c->stream;
+	k.st = &c->st;
+	k.tab = &c->tab;
+	k.twiddles = c->d_tw;
+	k.frames = c->cfg.frames;
+	k.hist_len = c->hist_len;
+	k.fade_env = c->d_fade_env;
+	return k;
+}
+
 // Device work of one callback over already-grouped entries.
-int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots, const uint32_t *d_rows, const Group *groups, const std::vector<ChainRange> &ranges, uint32_t n_total, gas_audio_frame *d_out, float *d_peaks, uint32_t channel_begin, uint32_t channel_count, int force_mode, bool use_order = false, bool pipelined = false) {
+int run_groups(gas_ctx *c, const RunArgs &a) {
 	const uint32_t F = c->cfg.frames;
+	const Group *const groups = a.groups;
+	const std::vector<ChainRange> &ranges = *a.ranges;
+	const uint32_t *const d_slots = a.slots, *const d_rows = a.rows;
+	const gas_audio_frame *const d_src = a.src.rows; // nullptr when fused: only plain-[HRTF] launches run then, and they sample
 	uint32_t pcount[G_COUNT];
 	const bool uni_hrtf = groups == c->groups && uni_ok(c);
-	const bool staged_uni = uni_ok(c) && c->run_buses == nullptr && gas_hrtf_uni_waves() == 8; // staged chains ending in the HRTF: last stage = k_hrtf_uni
+	const bool staged_uni = uni_ok(c) && a.buses == nullptr && gas_hrtf_uni_waves() == 8; // staged chains ending in the HRTF: last stage = k_hrtf_uni
 	// [ER, HRTF] through k_hrtf_uni<ER> (22.5 -> see profiles/r03_notes.md): the exact-peak group's entries follow the
 	// frequency-domain group's in the callback's list, so one launch covers both
-	pipelined = pipelined && c->pipelined_mix && channel_count == 1 && c->cfg.channel_count == 1;
+	const bool pipelined = a.pipelined && c->pipelined_mix && a.channel_count == 1 && c->cfg.channel_count == 1;
 	const bool uni_er_pays = c->uni_er_mode == 2 || groups[G_FX_ER_HRTF_PK].count * 4 <= groups[G_FX_ER_HRTF].count + groups[G_FX_ER_HRTF_PK].count;
-	const bool uni_er = uni_ok(c) && c->run_buses == nullptr && gas_hrtf_uni_waves() == 8 && c->uni_er_enabled && uni_er_pays && (groups[G_FX_ER_HRTF].count == 0 || groups[G_FX_ER_HRTF_PK].count == 0 || groups[G_FX_ER_HRTF].offset + groups[G_FX_ER_HRTF].count == groups[G_FX_ER_HRTF_PK].offset);
+	const bool uni_er = uni_ok(c) && a.buses == nullptr && gas_hrtf_uni_waves() == 8 && c->uni_er_enabled && uni_er_pays && (groups[G_FX_ER_HRTF].count == 0 || groups[G_FX_ER_HRTF_PK].count == 0 || groups[G_FX_ER_HRTF].offset + groups[G_FX_ER_HRTF].count == groups[G_FX_ER_HRTF_PK].offset);
 	plan_partials(groups, ranges, pcount, uni_hrtf, staged_uni, uni_er);
 	uint32_t p_total = 0, p_mix = 0;
 	for (int gt = 0; gt < G_COUNT; gt++) {
@@ -737,7 +805,7 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 	// The plain [HRTF] launch takes it when there is one, else the [ER, HRTF] launch.
 	bool carrier = false;
 	int carrier_gt = -1;
-	if (!c->fused_streams && (c->cfg.flags & (GAS_FLAG_HRTF_CROSSFADE | GAS_FLAG_HRTF_INTERPOLATE)) == 0) {
+	if (!a.src.fused() && (c->cfg.flags & (GAS_FLAG_HRTF_CROSSFADE | GAS_FLAG_HRTF_INTERPOLATE)) == 0) {
 		for (int gt : { (int)G_FX_HRTF, (int)G_FX_ER_HRTF }) {
 			if (carrier_gt < 0 && groups[gt].count + groups[gt + 1].count > 0) {
 				carrier_gt = gt;
@@ -764,7 +832,7 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 			return rc;
 		}
 	}
-	rc = ensure_partials(c, (p_total > 0 ? p_total : 1) * (c->run_buses ? c->run_buses->n_buses : 1u)); // buses: p_total rows per bus, bus after bus
+	rc = ensure_partials(c, (p_total > 0 ? p_total : 1) * (a.buses ? a.buses->n_buses : 1u)); // buses: p_total rows per bus, bus after bus
 	if (rc != GAS_OK) {
 		return rc;
 	}
@@ -780,8 +848,8 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 	}
 	// only the mix_channel launch over several channel pairs accumulates peaks (atomicMax over the pairs, from zero);
 	// every other launch -- a single pair included -- stores them, so the zeroing pass (a 4 us dispatch) is skipped
-	if (groups[G_3D_MIX].count + groups[G_3D_PROCESS].count > 0 && channel_count > 1 && force_mode != GAS_MODE_PROCESS_FRAMES) {
-		GAS_HIP(c, hipMemsetAsync(d_peaks, 0, (size_t)n_total * 2 * sizeof(float), c->stream));
+	if (groups[G_3D_MIX].count + groups[G_3D_PROCESS].count > 0 && a.channel_count > 1 && a.force_mode != GAS_MODE_PROCESS_FRAMES) {
+		GAS_HIP(c, hipMemsetAsync(a.peaks, 0, (size_t)a.n_total * 2 * sizeof(float), c->stream));
 	}
 
 	// the dominant launch of this callback is the one timed by the profiler
@@ -807,7 +875,7 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 		ga.slots = d_slots + gr.offset;
 		ga.slot_base = 0;
 		ga.n = gr.count;
-		ga.peaks = d_peaks;
+		ga.peaks = a.peaks;
 		const bool timed = c->profiling && gt == dom && c->ev_used + 2 <= c->ev.size() && (c->prof_tick++ % c->prof_every) == 0;
 		if (timed) {
 			GAS_HIP(c, hipEventRecord(c->ev[c->ev_used], c->stream));
@@ -818,11 +886,11 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 			case G_3D_MIX:
 			case G_3D_PROCESS: {
 				int mode = gt == G_3D_MIX ? GAS_MODE_MIX_CHANNEL : GAS_MODE_PROCESS_FRAMES;
-				if (force_mode >= 0) {
-					mode = force_mode;
+				if (a.force_mode >= 0) {
+					mode = a.force_mode;
 				}
-				const uint32_t cb = mode == GAS_MODE_MIX_CHANNEL ? channel_begin : 0;
-				const uint32_t cc = mode == GAS_MODE_MIX_CHANNEL ? channel_count : 1;
+				const uint32_t cb = mode == GAS_MODE_MIX_CHANNEL ? a.channel_begin : 0;
+				const uint32_t cc = mode == GAS_MODE_MIX_CHANNEL ? a.channel_count : 1;
 				e = gas_launch_biquad_mix(c->stream, mode, ga, c->st, F, cb, cc, c->cfg.mix_rate, parts, p_off, c->partial_rows);
 			} break;
 			case G_FX_COPY:
@@ -861,13 +929,13 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 				}
 				// GAS_FLAG_DIRECTION_ORDER: direction order of the frequency-domain group, rebuilt when the
 				// callback's list or any parameter changed, else reused.  Only when directions repeat within a segment.
-				const gas_params *fresh = c->fresh_for_launch; // both HRTF forms read device-published rows themselves and write them through
+				const gas_params *fresh = a.fresh; // both HRTF forms read device-published rows themselves and write them through
 				if (gt == G_FX_HRTF && gp.count == 0 && uni_hrtf) {
 					// the whole plain-[HRTF] group in one uniform launch (k_hrtf_uni.hip)
 					// XCD-affine processing order (k_xcd_order): rebuilt when the list or any parameter changed, else reused
 					const uint32_t uni_wgs = gas_hrtf_uni_partials(g_fd.n);
 					c->last_uni_ordered = false;
-					if (use_order && ((c->cfg.flags & GAS_FLAG_XCD_ORDER) != 0 || g_fd.n >= c->xcd_order_auto_min) && uni_wgs % 8 == 0 && c->tab.dirs >= 8) {
+					if (a.use_order && ((c->cfg.flags & GAS_FLAG_XCD_ORDER) != 0 || g_fd.n >= c->xcd_order_auto_min) && uni_wgs % 8 == 0 && c->tab.dirs >= 8) {
 						if (!c->d_order) {
 							GAS_HIP(c, hipMalloc(&c->d_order, (size_t)c->cfg.max_sources * sizeof(uint32_t)));
 						}
@@ -879,7 +947,17 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 						g_fd.order = ord;
 						c->last_uni_ordered = true;
 					}
-					e = gas_launch_hrtf_uni(c->stream, g_fd, c->uni_peak_any && !c->uni_peak_all ? c->d_peak_bits : nullptr, c->uni_peak_all, c->st, c->tab, c->d_tw, F, c->hist_len, parts, p_off, c->fused_streams ? c->d_cursors : nullptr, c->d_fade_env, fresh, job);
+					gas_hrtf_uni_launch lu{ hrtf_common(c) };
+					lu.g = g_fd;
+					lu.peak_bits = c->uni_peak_any && !c->uni_peak_all ? c->d_peak_bits : nullptr;
+					lu.peak_all = c->uni_peak_all;
+					lu.partials = parts;
+					lu.p_offset = p_off;
+					lu.cursors = a.src.cursors;
+					lu.feed = a.src.feed;
+					lu.fresh = fresh;
+					lu.job = job;
+					e = gas_launch_hrtf_uni(lu);
 					carried_bytes = job.partials ? ((uint64_t)job.p_count + 1) * job.elems * sizeof(float) : 0;
 					job = gas_deferred_reduce();
 					break;
@@ -892,14 +970,23 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 						gu.slots = nullptr;
 						gu.slot_base = groups[gt].slot_base;
 					}
-					e = gas_launch_hrtf_uni(c->stream, gu, nullptr, is_pk, c->st, c->tab, c->d_tw, F, c->hist_len, parts, p_off, nullptr, c->d_fade_env, fresh, fd_gt == carrier_gt ? job : gas_deferred_reduce(), nullptr, 0, 0, true, c->cfg.er_ring_frames, is_pk ? 0u : gr.count);
+					gas_hrtf_uni_launch lu{ hrtf_common(c) };
+					lu.g = gu;
+					lu.peak_all = is_pk;
+					lu.partials = parts;
+					lu.p_offset = p_off;
+					lu.fresh = fresh;
+					lu.job = fd_gt == carrier_gt ? job : gas_deferred_reduce();
+					lu.er_ring_frames = c->cfg.er_ring_frames;
+					lu.peak_from = is_pk ? 0u : gr.count;
+					e = gas_launch_hrtf_uni(lu);
 					if (fd_gt == carrier_gt) {
 						carried_bytes = job.partials ? ((uint64_t)job.p_count + 1) * job.elems * sizeof(float) : 0;
 						job = gas_deferred_reduce();
 					}
 					break;
 				}
-				if (use_order && (c->cfg.flags & GAS_FLAG_DIRECTION_ORDER) != 0 && g_fd.n >= GAS_DIR_ORDER_MIN_SOURCES && (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) == 0 && gas_dir_order_supported(c->tab.dirs)) {
+				if (a.use_order && (c->cfg.flags & GAS_FLAG_DIRECTION_ORDER) != 0 && g_fd.n >= GAS_DIR_ORDER_MIN_SOURCES && (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) == 0 && gas_dir_order_supported(c->tab.dirs)) {
 					const uint32_t seg = g_fd.n < GAS_DIR_ORDER_SEGMENT ? g_fd.n : GAS_DIR_ORDER_SEGMENT;
 					if (seg >= 2 * c->tab.dirs) {
 						if (!c->d_order) {
@@ -913,7 +1000,21 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 						g_fd.order = ord;
 					}
 				}
-				e = gas_launch_hrtf_ols(c->stream, fd_gt == G_FX_ER_HRTF, (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) != 0, (c->cfg.flags & (GAS_FLAG_DIRECTION_RUNS | GAS_FLAG_DIRECTION_ORDER)) != 0, g_fd, g_pk, c->st, c->tab, c->d_tw, F, c->hist_len, c->cfg.er_ring_frames, parts, p_off, fd_gt == G_FX_HRTF && c->fused_streams ? c->d_cursors : nullptr, c->d_fade_env, fresh, fd_gt == carrier_gt ? job : gas_deferred_reduce(), blend_on(c), fade_on(c));
+				gas_hrtf_ols_launch lo{ hrtf_common(c) };
+				lo.with_er = fd_gt == G_FX_ER_HRTF;
+				lo.crossfade = (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) != 0;
+				lo.runs = (c->cfg.flags & (GAS_FLAG_DIRECTION_RUNS | GAS_FLAG_DIRECTION_ORDER)) != 0;
+				lo.g_fd = g_fd;
+				lo.g_pk = g_pk;
+				lo.er_ring_frames = c->cfg.er_ring_frames;
+				lo.partials = parts;
+				lo.p_offset = p_off;
+				lo.cursors = fd_gt == G_FX_HRTF ? a.src.cursors : nullptr;
+				lo.fresh = fresh;
+				lo.job = fd_gt == carrier_gt ? job : gas_deferred_reduce();
+				lo.blend = blend_on(c);
+				lo.fade = fade_on(c);
+				e = gas_launch_hrtf_ols(lo);
 				if (fd_gt == carrier_gt) {
 					carried_bytes = job.partials ? ((uint64_t)job.p_count + 1) * job.elems * sizeof(float) : 0;
 					job = gas_deferred_reduce();
@@ -944,16 +1045,27 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 					in.slots = d_slots + off;
 					in.rows = d_rows ? d_rows + off : nullptr;
 					in.src = d_rows ? d_src : d_src + (size_t)off * F; // identity rows: the run's first row is entry `off`
-					in.peaks = d_rows ? d_peaks : d_peaks + (size_t)off * 2;
+					in.peaks = d_rows ? a.peaks : a.peaks + (size_t)off * 2;
 					const uint32_t *peak_rows = in.rows;
 					const bool last_is_uni = range_ends_in_uni(r, staged_uni);
 					const bool own = groups == c->groups; // the context's own list: GAS_FLAG_PEAKS_DRAINING_ONLY's bits exist
 					const int k0 = r.sig & 0xff;
+					// a last stage that is k_hrtf_uni: exact peaks for every source of the chain, or (GAS_FLAG_PEAKS_DRAINING_ONLY,
+					// the context's own list) for the draining ones
+					gas_hrtf_uni_launch lu{ hrtf_common(c) };
+					lu.peak_bits = own && r.peak_any && !r.peak_all ? c->d_peak_bits + (c->cfg.max_sources + 31) / 32 : nullptr;
+					lu.peak_all = !own || r.peak_all;
+					lu.partials = parts;
+					lu.p_offset = pp;
+					lu.peak_bit_base = r.offset;
 					if (last_is_uni && c->uni_flt_enabled && (r.sig >> 8) == GAS_FX_HRTF && (k0 == GAS_FX_HIGHSHELF || (k0 >= GAS_FX_LOWPASS && k0 <= GAS_FX_LOWSHELF)) && gas_shelf_scan_applies(k0 == GAS_FX_HIGHSHELF ? GAS_MODE_FX_HIGHSHELF : GAS_MODE_FX_FILTER, r.count, F)) {
 						// [one-biquad filter, HRTF]: one launch (k_hrtf_uni<FLT>), no rows in between.  The filter there is the
 						// scan form, so it is taken exactly where the two-launch road would take k_shelf_scan (same bits either
 						// way; small callbacks and GAS_SHELF_SCAN=0 keep the engine's serial order)
-						e = gas_launch_hrtf_uni(c->stream, in, own && r.peak_any && !r.peak_all ? c->d_peak_bits + (c->cfg.max_sources + 31) / 32 : nullptr, !own || r.peak_all, c->st, c->tab, c->d_tw, F, c->hist_len, parts, pp, nullptr, c->d_fade_env, nullptr, gas_deferred_reduce(), nullptr, 0, 0, true, 0, 0xffffffffu, r.offset, (uint32_t)k0, 0, c->cfg.mix_rate);
+						lu.g = in;
+						lu.flt_kind = (uint32_t)k0;
+						lu.mix_rate = c->cfg.mix_rate;
+						e = gas_launch_hrtf_uni(lu);
 						pp += range_partials(r, staged_uni);
 						continue;
 					}
@@ -964,16 +1076,16 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 						}
 						if (last_is_uni && c->uni_er_enabled && kind == GAS_FX_EARLY_REFLECTIONS && j < 3 && ((r.sig >> (8 * (j + 1))) & 0xff) == GAS_FX_HRTF) {
 							// ... [ER, HRTF] at the end of a longer chain: both in the last launch (k_hrtf_uni<ER>), no rows in between
-							gas_group_args gu = in;
-							gu.peak_rows = peak_rows;
-							e = gas_launch_hrtf_uni(c->stream, gu, own && r.peak_any && !r.peak_all ? c->d_peak_bits + (c->cfg.max_sources + 31) / 32 : nullptr, !own || r.peak_all, c->st, c->tab, c->d_tw, F, c->hist_len, parts, pp, nullptr, c->d_fade_env, nullptr, gas_deferred_reduce(), nullptr, 0, 0, true, c->cfg.er_ring_frames, 0xffffffffu, r.offset);
+							lu.g = in;
+							lu.g.peak_rows = peak_rows;
+							lu.er_ring_frames = c->cfg.er_ring_frames;
+							e = gas_launch_hrtf_uni(lu);
 							break;
 						}
 						if (last_is_uni && kind == GAS_FX_HRTF) { // (the last effect: one HRTF per chain)
-							gas_group_args gu = in; // dense rows of the previous stage, peaks into the callback's rows
-							gu.peak_rows = peak_rows;
-							// exact peaks for every source of the chain, or (GAS_FLAG_PEAKS_DRAINING_ONLY, the context's own list) for the draining ones
-							e = gas_launch_hrtf_uni(c->stream, gu, own && r.peak_any && !r.peak_all ? c->d_peak_bits + (c->cfg.max_sources + 31) / 32 : nullptr, !own || r.peak_all, c->st, c->tab, c->d_tw, F, c->hist_len, parts, pp, nullptr, c->d_fade_env, nullptr, gas_deferred_reduce(), nullptr, 0, 0, true, 0, 0xffffffffu, r.offset);
+							lu.g = in; // dense rows of the previous stage, peaks into the callback's rows
+							lu.g.peak_rows = peak_rows;
+							e = gas_launch_hrtf_uni(lu);
 							break;
 						}
 						gas_audio_frame *outb = c->d_chain[j & 1];
@@ -992,8 +1104,8 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 					if (e == hipSuccess && !last_is_uni) {
 						gas_group_args fin = in;
 						fin.rows = peak_rows; // peaks go to the callback's row of each source
-						if (c->run_buses) {
-							e = gas_launch_rows_accumulate_buses(c->stream, fin, F, c->run_buses->routes, c->run_buses->n_buses, p_total, parts, pp);
+						if (a.buses) {
+							e = gas_launch_rows_accumulate_buses(c->stream, fin, F, a.buses->routes, a.buses->n_buses, p_total, parts, pp);
 						} else {
 							e = gas_launch_rows_accumulate(c->stream, fin, F, parts, pp);
 						}
@@ -1018,7 +1130,7 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 			c->prof_group = gt;
 			c->prof_uni = (gt == G_FX_HRTF && uni_hrtf && groups[G_FX_HRTF_PK].count == 0) || ((gt == G_FX_ER_HRTF || gt == G_FX_ER_HRTF_PK) && uni_er);
 			c->prof_multi = false;
-			c->prof_pipe = (gt == G_3D_MIX || gt == G_3D_PROCESS || gt == G_FX_SHELF) && gas_biquad_uses_pipe(gt == G_FX_SHELF ? GAS_MODE_FX_HIGHSHELF : (force_mode >= 0 ? force_mode : (gt == G_3D_MIX ? GAS_MODE_MIX_CHANNEL : GAS_MODE_PROCESS_FRAMES)), gr.count, gt == G_3D_MIX ? channel_count : 1, F, false);
+			c->prof_pipe = (gt == G_3D_MIX || gt == G_3D_PROCESS || gt == G_FX_SHELF) && gas_biquad_uses_pipe(gt == G_FX_SHELF ? GAS_MODE_FX_HIGHSHELF : (a.force_mode >= 0 ? a.force_mode : (gt == G_3D_MIX ? GAS_MODE_MIX_CHANNEL : GAS_MODE_PROCESS_FRAMES)), gr.count, gt == G_3D_MIX ? a.channel_count : 1, F, false);
 		}
 		p_off += pcount[gt];
 	}
@@ -1031,17 +1143,17 @@ int run_groups(gas_ctx *c, const gas_audio_frame *d_src, const uint32_t *d_slots
 		c->pending_mix.valid = true;
 		c->pending_mix.parity = parity;
 		c->pending_mix.p_total = p_total;
-		c->pending_mix.out = d_out;
+		c->pending_mix.out = a.out;
 		c->pipe_tick++;
 		return GAS_OK;
 	}
-	if (c->run_buses) { // out[b][F]: bus b's rows are [b * p_total, (b + 1) * p_total)
-		GAS_HIP(c, gas_launch_mix_reduce(c->stream, parts, p_total, p_total > 0 ? p_total : 1, c->run_buses->n_buses, F, d_out));
+	if (a.buses) { // out[b][F]: bus b's rows are [b * p_total, (b + 1) * p_total)
+		GAS_HIP(c, gas_launch_mix_reduce(c->stream, parts, p_total, p_total > 0 ? p_total : 1, a.buses->n_buses, F, a.out));
 		return GAS_OK;
 	}
-	GAS_HIP(c, gas_launch_mix_reduce(c->stream, parts, p_total, c->partial_rows, 1, F, d_out));
-	if (channel_count > 1) {
-		GAS_HIP(c, gas_launch_mix_reduce(c->stream, parts + (size_t)c->partial_rows * F * 2, p_mix, c->partial_rows, channel_count - 1, F, d_out + F));
+	GAS_HIP(c, gas_launch_mix_reduce(c->stream, parts, p_total, c->partial_rows, 1, F, a.out));
+	if (a.channel_count > 1) {
+		GAS_HIP(c, gas_launch_mix_reduce(c->stream, parts + (size_t)c->partial_rows * F * 2, p_mix, c->partial_rows, a.channel_count - 1, F, a.out + F));
 	}
 	return GAS_OK;
 }
@@ -1061,15 +1173,18 @@ int flush_deferred(gas_ctx *c) {
 		return run_hrtf_batch(c, blocks, c->deferred_n);
 	}
 	const gas_ctx::Deferred &d = blocks[0]; // a single one: k_hrtf_uni, exactly as the unbatched mode
-	c->fresh_for_launch = d.fresh;
-	const int rc = run_groups(c, d.src, c->d_slots, c->cached_identity_rows ? nullptr : c->d_rows, c->groups, c->chain_ranges, c->deferred_n, d.out, d.peaks, 0, c->cfg.channel_count, -1, true, true);
-	c->fresh_for_launch = nullptr;
-	return rc;
+	RowSource src;
+	src.rows = d.src;
+	RunArgs a = own_list(c, src, c->deferred_n, d.out, d.peaks);
+	a.channel_count = c->cfg.channel_count;
+	a.use_order = a.pipelined = true;
+	a.fresh = d.fresh;
+	return run_groups(c, a);
 }
 
 // Can this callback (already validated, groups built) wait for / run with its neighbours?
-bool batchable(const gas_ctx *c, uint32_t n) {
-	if ((c->cfg.flags & GAS_FLAG_BATCHED_LAUNCH) == 0 || c->batch_depth < 2 || !c->pipelined_mix || c->cfg.channel_count != 1 || !uni_ok(c) || c->fused_streams || (c->cfg.flags & GAS_FLAG_XCD_ORDER) != 0) {
+bool batchable(const gas_ctx *c, uint32_t n, bool fused) {
+	if ((c->cfg.flags & GAS_FLAG_BATCHED_LAUNCH) == 0 || c->batch_depth < 2 || !c->pipelined_mix || c->cfg.channel_count != 1 || !uni_ok(c) || fused || (c->cfg.flags & GAS_FLAG_XCD_ORDER) != 0) {
 		return false;
 	}
 	for (int gt = 0; gt < G_COUNT; gt++) {
@@ -1101,18 +1216,7 @@ int run_hrtf_batch(gas_ctx *c, const std::vector<gas_ctx::Deferred> &blocks, uin
 	if (rc != GAS_OK) {
 		return rc;
 	}
-	const Group &gr = c->groups[G_FX_HRTF];
-	gas_group_args ga;
-	ga.src = blocks[0].src;
-	ga.rows = c->cached_identity_rows ? nullptr : c->d_rows + gr.offset;
-	ga.slots = c->d_slots + gr.offset;
-	ga.slot_base = 0;
-	ga.n = n;
-	ga.peaks = blocks[0].peaks;
-	if (gr.contiguous) {
-		ga.slots = nullptr;
-		ga.slot_base = gr.slot_base;
-	}
+	const gas_group_args ga = own_hrtf_group(c, blocks[0].src, n, blocks[0].peaks);
 	gas_hrtf_blocks mb;
 	mb.k = K;
 	for (uint32_t b = 0; b < K; b++) {
@@ -1845,8 +1949,8 @@ int apply_pending_frees(gas_ctx *c) {
 }
 
 // HRTF sources take the frequency-domain path unless their peak is needed.
-inline int launch_group(const gas_ctx *c, const SlotInfo &si) {
-	if (c->force_staged && si.kind == GAS_KIND_EFFECT && si.chain_sig != 0) {
+inline int launch_group(const gas_ctx *c, const SlotInfo &si, bool all_staged) {
+	if (all_staged && si.kind == GAS_KIND_EFFECT && si.chain_sig != 0) {
 		return G_FX_GENERIC;
 	}
 	const bool want_peak = wants_peak(c, si);
@@ -1859,8 +1963,9 @@ inline int launch_group(const gas_ctx *c, const SlotInfo &si) {
 	return si.group;
 }
 
-// Validate + counting-sort the callback's slot list by launch group.
-int build_groups(gas_ctx *c, const uint32_t *slots, uint32_t n) {
+// Validate + counting-sort the callback's slot list by launch group.  all_staged (gas_process_block_buses over effect
+// kinds): every chain runs staged (rows out), the rows are mixed per bus.
+int build_groups(gas_ctx *c, const uint32_t *slots, uint32_t n, bool all_staged) {
 	uint32_t counts[G_COUNT] = { 0 };
 	if (++c->stamp_gen == 0) {
 		std::fill(c->stamp.begin(), c->stamp.end(), 0u);
@@ -1878,7 +1983,7 @@ int build_groups(gas_ctx *c, const uint32_t *slots, uint32_t n) {
 			return GAS_ERR_INVALID_ARGUMENT; // one playback twice in a callback would race on its state
 		}
 		c->stamp[s] = c->stamp_gen;
-		counts[launch_group(c, c->slots[s])]++;
+		counts[launch_group(c, c->slots[s], all_staged)]++;
 	}
 	uint32_t off = 0, cursor[G_COUNT];
 	int nonempty = 0;
@@ -1891,7 +1996,7 @@ int build_groups(gas_ctx *c, const uint32_t *slots, uint32_t n) {
 	}
 	uint32_t *hs = c->h_idx, *hr = c->h_idx + c->cfg.max_sources;
 	for (uint32_t i = 0; i < n; i++) {
-		const uint32_t p = cursor[launch_group(c, c->slots[slots[i]])]++;
+		const uint32_t p = cursor[launch_group(c, c->slots[slots[i]], all_staged)]++;
 		hs[p] = slots[i];
 		hr[p] = i;
 	}
@@ -3119,12 +3224,54 @@ int feed_place(gas_ctx *c, size_t bytes, size_t &at, bool &switched) {
 	at = off;
 	return GAS_OK;
 }
+
+// The staging of the callback entries.  d_src holds at least `frames` frames afterwards.
+// (hipFree synchronises the device by itself: waiting for the stream in front of it changes nothing observable.)
+hipError_t ensure_src(gas_ctx *c, size_t frames) {
+	if (frames <= c->d_src_frames) {
+		return hipSuccess;
+	}
+	if (c->d_src) {
+		(void)hipStreamSynchronize(c->stream);
+		(void)hipFree(c->d_src);
+		c->d_src = nullptr;
+		c->d_src_frames = 0;
+	}
+	const hipError_t e = hipMalloc(&c->d_src, (frames ? frames : 1) * sizeof(gas_audio_frame));
+	if (e == hipSuccess) {
+		c->d_src_frames = frames;
+	}
+	return e;
+}
+
+// Queues `out` and, when the caller wants them, the peaks of n sources back to the host, and waits for both.
+hipError_t copy_back(gas_ctx *c, gas_audio_frame *out, const gas_audio_frame *d_out, size_t out_bytes, float *peaks, uint32_t n) {
+	hipError_t e = hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream);
+	if (e == hipSuccess && peaks && n > 0) {
+		e = hipMemcpyAsync(peaks, c->d_peaks, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+	}
+	return e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
+}
+
+// A failed callback leaves a zeroed mix in host memory (the reference's ERR_FAIL paths, audio_spatializer.cpp:335-343);
+// device memory is left as it is.
+int fail_out(int code, int mem, gas_audio_frame *out, size_t out_bytes) {
+	if (mem == GAS_MEM_HOST) {
+		std::memset(out, 0, out_bytes);
+	}
+	return code;
+}
 } // namespace
 
 extern "C" {
 
+// The bodies of gas_process_block and gas_process_block_buses, behind their argument checks; the stream entries call
+// them with a fused source.
+static int process_block(gas_ctx *c, const RowSource &src, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, float *peaks, int mem);
+static int process_block_buses(gas_ctx *c, const RowSource &src, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, uint32_t n_buses, float *peaks, int mem);
+
 // Both stream entries: validation, the host mirror of the cursor arithmetic, the same_list steady state, the sampler
-// launches and fused_streams.  !buses: gas_process_block_streams (one mix, out [C][frames], n_buses unused); buses:
+// launches and the choice of the fused form.  !buses: gas_process_block_streams (one mix, out [C][frames], n_buses unused); buses:
 // gas_process_block_streams_buses (out [n_buses][C][frames], the device path of gas_process_block_buses over the windows).
 static int process_block_streams_common(gas_ctx *c, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, uint32_t n_buses, bool buses, float *peaks, uint8_t *has_frames, int mem) {
 	if (!c || !out || (n > 0 && !slots) || n > c->cfg.max_sources || (mem != GAS_MEM_HOST && mem != GAS_MEM_DEVICE)) {
@@ -3144,12 +3291,7 @@ static int process_block_streams_common(gas_ctx *c, const uint32_t *slots, uint3
 	}
 	const uint32_t F = c->cfg.frames, C = c->cfg.channel_count;
 	const size_t out_bytes = (size_t)(buses ? n_buses : 1u) * C * F * sizeof(gas_audio_frame);
-	auto fail = [&](int code) {
-		if (mem == GAS_MEM_HOST) {
-			std::memset(out, 0, out_bytes);
-		}
-		return code;
-	};
+	const auto fail = [&](int code) { return fail_out(code, mem, out, out_bytes); };
 	if (frames != F) {
 		return fail(GAS_ERR_FRAME_COUNT);
 	}
@@ -3358,18 +3500,8 @@ static int process_block_streams_common(gas_ctx *c, const uint32_t *slots, uint3
 	const bool all_hrtf = c->stream_all_hrtf && !c->stream_any_resampled && !c->stream_any_adpcm && !c->stream_any_qoa && !fade_on(c) && loops_fused && !c->stream_rows_first && bus_fusable && fed_fusable; // the fused prologue samples plain playbacks only
 	c->stream_last_fused = all_hrtf;
 	if (!all_hrtf) {
-		const size_t need = (size_t)n * F;
-		if (need > c->d_src_frames) {
-			if (c->d_src) {
-				(void)hipStreamSynchronize(c->stream);
-				(void)hipFree(c->d_src);
-				c->d_src = nullptr;
-				c->d_src_frames = 0;
-			}
-			if (hipMalloc(&c->d_src, (need ? need : 1) * sizeof(gas_audio_frame)) != hipSuccess) {
-				return fail(GAS_ERR_OUT_OF_MEMORY);
-			}
-			c->d_src_frames = need;
+		if (ensure_src(c, (size_t)n * F) != hipSuccess) {
+			return fail(GAS_ERR_OUT_OF_MEMORY);
 		}
 		if (n > 0) {
 			hipError_t e = gas_launch_sample_sources(c->stream, c->d_cursors, c->d_stream_slots, n, F, c->d_fade_env, c->d_src, c->stream_any_resampled ? c->d_stream_inc : nullptr, feed);
@@ -3385,70 +3517,43 @@ static int process_block_streams_common(gas_ctx *c, const uint32_t *slots, uint3
 			}
 		}
 	}
-	// (fused: no float rows; the launch finds the feed table in their place when an entry is fed, else the cursor array -- k_hrtf_uni.hip)
-	const gas_audio_frame *rows = all_hrtf ? (feed ? reinterpret_cast<const gas_audio_frame *>(feed) : reinterpret_cast<const gas_audio_frame *>(c->d_cursors)) : c->d_src;
+	RowSource rows; // fused: no float rows, the HRTF launch samples the bound streams (and the fed rows) itself
+	if (all_hrtf) {
+		rows.cursors = c->d_cursors;
+		rows.feed = feed;
+	} else {
+		rows.rows = c->d_src;
+	}
+	// host outputs: the device path into the library's buffers, one copy back
+	gas_audio_frame *d_out = out;
+	float *d_pk = peaks;
+	if (mem == GAS_MEM_HOST) {
+		if (buses && !c->d_bus_out && hipMalloc(&c->d_bus_out, (size_t)GAS_MAX_BUSES * C * F * sizeof(gas_audio_frame)) != hipSuccess) {
+			return fail(GAS_ERR_OUT_OF_MEMORY);
+		}
+		d_out = buses ? c->d_bus_out : c->d_out;
+		d_pk = c->d_peaks;
+	}
+	int rc = GAS_OK;
 	if (buses) {
 		// gas_process_block_buses reuses a list only for its 3D-mix and fused [HRTF] forms; the staged form needs it every time
 		const bool reuse = same_list && n > 0 && c->cached_n == n && c->bus_form_cached != 0 && c->bus_form_groups_gen == c->groups_gen;
-		const uint32_t *bus_list = reuse ? nullptr : slots;
-		gas_audio_frame *d_bus = out;
-		float *d_pk = peaks;
-		if (mem == GAS_MEM_HOST) { // host outputs: the device path into the library's buffers, one copy back
-			if (!c->d_bus_out && hipMalloc(&c->d_bus_out, (size_t)GAS_MAX_BUSES * C * F * sizeof(gas_audio_frame)) != hipSuccess) {
-				return fail(GAS_ERR_OUT_OF_MEMORY);
-			}
-			d_bus = c->d_bus_out;
-			d_pk = c->d_peaks;
-		}
-		c->fused_streams = all_hrtf;
-		const int rcb = gas_process_block_buses(c, rows, bus_list, n, F, d_bus, n_buses, d_pk, GAS_MEM_DEVICE);
-		c->fused_streams = false;
-		c->stream_groups_gen = rcb == GAS_OK ? c->groups_gen : UINT64_MAX;
-		c->stream_bus_staged = rcb == GAS_OK && n > 0 && c->cached_n != n; // ran staged: nothing cached to compare with next time
-		if (rcb != GAS_OK) {
-			return fail(rcb);
-		}
-		if (mem == GAS_MEM_DEVICE) {
-			return GAS_OK;
-		}
-		hipError_t e = hipMemcpyAsync(out, c->d_bus_out, out_bytes, hipMemcpyDeviceToHost, c->stream);
-		if (e == hipSuccess && peaks && n > 0) {
-			e = hipMemcpyAsync(peaks, c->d_peaks, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-		}
-		if (e == hipSuccess) {
-			e = hipStreamSynchronize(c->stream);
-		}
-		if (e != hipSuccess) {
-			c->last_err = hipGetErrorString(e);
-			return fail(GAS_ERR_DEVICE);
-		}
-		return GAS_OK;
+		rc = process_block_buses(c, rows, reuse ? nullptr : slots, n, F, d_out, n_buses, d_pk, GAS_MEM_DEVICE);
+		c->stream_bus_staged = rc == GAS_OK && n > 0 && c->cached_n != n; // ran staged: nothing cached to compare with next time
+	} else {
+		rc = process_block(c, rows, same_list ? nullptr : slots, n, F, d_out, d_pk, GAS_MEM_DEVICE);
 	}
-	const uint32_t *list = same_list ? nullptr : slots;
-	c->fused_streams = all_hrtf;
-	if (mem == GAS_MEM_DEVICE) {
-		const int rc_dev = gas_process_block(c, rows, list, n, F, out, peaks, GAS_MEM_DEVICE);
-		c->fused_streams = false;
-		c->stream_groups_gen = rc_dev == GAS_OK ? c->groups_gen : UINT64_MAX;
-		return rc_dev;
-	}
-	// host outputs: run the device path into the library's buffers, then copy back
-	int rc = gas_process_block(c, rows, list, n, F, c->d_out, c->d_peaks, GAS_MEM_DEVICE);
-	c->fused_streams = false;
 	c->stream_groups_gen = rc == GAS_OK ? c->groups_gen : UINT64_MAX;
-	if (rc == GAS_OK) {
+	if (rc == GAS_OK && !buses && mem == GAS_MEM_HOST) {
 		rc = join_outputs(c);
 	}
 	if (rc != GAS_OK) {
 		return fail(rc);
 	}
-	hipError_t e = hipMemcpyAsync(out, c->d_out, (size_t)C * F * sizeof(gas_audio_frame), hipMemcpyDeviceToHost, c->stream);
-	if (e == hipSuccess && peaks && n > 0) {
-		e = hipMemcpyAsync(peaks, c->d_peaks, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
+	if (mem == GAS_MEM_DEVICE) {
+		return GAS_OK;
 	}
-	if (e == hipSuccess) {
-		e = hipStreamSynchronize(c->stream);
-	}
+	const hipError_t e = copy_back(c, out, d_out, out_bytes, peaks, n);
 	if (e != hipSuccess) {
 		c->last_err = hipGetErrorString(e);
 		return fail(GAS_ERR_DEVICE);
@@ -3635,15 +3740,16 @@ int gas_process_block(gas_ctx *c, const gas_audio_frame *src, const uint32_t *sl
 	if (!c || !out || (mem != GAS_MEM_HOST && mem != GAS_MEM_DEVICE) || (n > 0 && !src) || n > c->cfg.max_sources) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
+	RowSource rows;
+	rows.rows = src;
+	return process_block(c, rows, slots, n, frames, out, peaks, mem);
+}
+
+static int process_block(gas_ctx *c, const RowSource &src, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, float *peaks, int mem) {
 	const uint32_t F = c->cfg.frames, C = c->cfg.channel_count;
 	const size_t out_bytes = (size_t)C * F * sizeof(gas_audio_frame);
 	int rc = GAS_OK;
-	auto fail = [&](int code) {
-		if (mem == GAS_MEM_HOST) {
-			std::memset(out, 0, out_bytes); // the reference's ERR_FAIL paths leave a zeroed mix (:335-343)
-		}
-		return code;
-	};
+	const auto fail = [&](int code) { return fail_out(code, mem, out, out_bytes); };
 	if (frames != F) {
 		return fail(GAS_ERR_FRAME_COUNT);
 	}
@@ -3673,7 +3779,7 @@ int gas_process_block(gas_ctx *c, const gas_audio_frame *src, const uint32_t *sl
 	}
 	apply_pending_frees(c);
 	if (slots || n == 0) { // an empty callback needs no list
-		rc = build_groups(c, slots, n);
+		rc = build_groups(c, slots, n, false);
 		if (rc != GAS_OK) {
 			c->cached_n = UINT32_MAX;
 			return fail(rc);
@@ -3695,40 +3801,33 @@ int gas_process_block(gas_ctx *c, const gas_audio_frame *src, const uint32_t *sl
 		c->order_params_gen = pgen;
 	}
 
-	const gas_audio_frame *d_src = src;
+	RowSource d_src = src;
 	gas_audio_frame *d_out = out;
 	float *d_peaks = peaks ? peaks : c->d_peaks;
 	if (mem == GAS_MEM_HOST) {
 		const size_t need = (size_t)n * F;
-		if (need > c->d_src_frames) {
-			if (c->d_src) {
-				(void)hipFree(c->d_src);
-				c->d_src = nullptr;
-				c->d_src_frames = 0;
-			}
-			if (hipMalloc(&c->d_src, need * sizeof(gas_audio_frame)) != hipSuccess) {
-				return fail(GAS_ERR_OUT_OF_MEMORY);
-			}
-			c->d_src_frames = need;
+		if (ensure_src(c, need) != hipSuccess) {
+			return fail(GAS_ERR_OUT_OF_MEMORY);
 		}
 		if (n > 0) {
-			hipError_t e = hipMemcpyAsync(c->d_src, src, need * sizeof(gas_audio_frame), hipMemcpyHostToDevice, c->stream);
+			hipError_t e = hipMemcpyAsync(c->d_src, src.rows, need * sizeof(gas_audio_frame), hipMemcpyHostToDevice, c->stream);
 			if (e != hipSuccess) {
 				c->last_err = hipGetErrorString(e);
 				return fail(GAS_ERR_DEVICE);
 			}
 		}
-		d_src = c->d_src;
+		d_src.rows = c->d_src;
 		d_out = c->d_out;
 		d_peaks = c->d_peaks;
 	}
+	const gas_params *fresh = nullptr; // device-published rows this callback's HRTF launch reads itself
 	if (c->pending_params) {
 		bool only_hrtf = true;
 		for (int gt = 0; gt < G_COUNT; gt++) {
 			only_hrtf = only_hrtf && (gt == G_FX_HRTF || gt == G_FX_HRTF_PK || gt == G_FX_ER_HRTF || gt == G_FX_ER_HRTF_PK || c->groups[gt].count == 0);
 		}
 		if (only_hrtf && c->pending_n == n) {
-			c->fresh_for_launch = c->pending_params; // k_hrtf_ols reads the rows and writes them through
+			fresh = c->pending_params; // k_hrtf_ols reads the rows and writes them through
 			c->pending_params = nullptr;
 		} else {
 			rc = flush_pending_params(c);
@@ -3737,13 +3836,12 @@ int gas_process_block(gas_ctx *c, const gas_audio_frame *src, const uint32_t *sl
 			}
 		}
 	}
-	if (mem == GAS_MEM_DEVICE && batchable(c, n)) {
+	if (mem == GAS_MEM_DEVICE && batchable(c, n, src.fused())) {
 		gas_ctx::Deferred cur;
-		cur.src = d_src;
+		cur.src = d_src.rows;
 		cur.out = d_out;
 		cur.peaks = d_peaks;
-		cur.fresh = c->fresh_for_launch;
-		c->fresh_for_launch = nullptr;
+		cur.fresh = fresh;
 		c->deferred.push_back(cur); // nothing is enqueued yet: this callback runs with its neighbours (or when flushed)
 		c->deferred_n = n;
 		c->deferred_groups_gen = c->groups_gen;
@@ -3755,27 +3853,22 @@ int gas_process_block(gas_ctx *c, const gas_audio_frame *src, const uint32_t *sl
 		return GAS_OK;
 	}
 	if (!c->deferred.empty()) {
-		const gas_params *fresh = c->fresh_for_launch;
 		rc = flush_deferred(c);
 		if (rc != GAS_OK) {
-			c->fresh_for_launch = nullptr;
 			return fail(rc);
 		}
-		c->fresh_for_launch = fresh;
 	}
-	rc = run_groups(c, d_src, c->d_slots, c->cached_identity_rows ? nullptr : c->d_rows, c->groups, c->chain_ranges, n, d_out, d_peaks, 0, C, -1, true, mem == GAS_MEM_DEVICE);
-	c->fresh_for_launch = nullptr;
+	RunArgs a = own_list(c, d_src, n, d_out, d_peaks);
+	a.channel_count = C;
+	a.use_order = true;
+	a.pipelined = mem == GAS_MEM_DEVICE;
+	a.fresh = fresh;
+	rc = run_groups(c, a);
 	if (rc != GAS_OK) {
 		return fail(rc);
 	}
 	if (mem == GAS_MEM_HOST) {
-		hipError_t e = hipMemcpyAsync(out, c->d_out, out_bytes, hipMemcpyDeviceToHost, c->stream);
-		if (e == hipSuccess && peaks && n > 0) {
-			e = hipMemcpyAsync(peaks, c->d_peaks, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream);
-		}
-		if (e == hipSuccess) {
-			e = hipStreamSynchronize(c->stream);
-		}
+		const hipError_t e = copy_back(c, out, c->d_out, out_bytes, peaks, n);
 		if (e != hipSuccess) {
 			c->last_err = hipGetErrorString(e);
 			return fail(GAS_ERR_DEVICE);
@@ -3809,6 +3902,12 @@ int gas_process_block_buses(gas_ctx *c, const gas_audio_frame *src, const uint32
 	if (!c || !out || (mem != GAS_MEM_HOST && mem != GAS_MEM_DEVICE) || (n > 0 && !src) || n > c->cfg.max_sources || n_buses < 1 || n_buses > GAS_MAX_BUSES) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
+	RowSource rows;
+	rows.rows = src;
+	return process_block_buses(c, rows, slots, n, frames, out, n_buses, peaks, mem);
+}
+
+static int process_block_buses(gas_ctx *c, const RowSource &src, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, uint32_t n_buses, float *peaks, int mem) {
 	adopt_frees(c);
 	if (n > 0 && !slots && (c->cached_n != n || c->bus_form_cached == 0 || c->bus_form_groups_gen != c->groups_gen || !c->pending_free.empty())) {
 		return GAS_ERR_INVALID_ARGUMENT;
@@ -3821,12 +3920,7 @@ int gas_process_block_buses(gas_ctx *c, const gas_audio_frame *src, const uint32
 	}
 	const uint32_t F = c->cfg.frames, C = c->cfg.channel_count;
 	const size_t out_bytes = (size_t)n_buses * C * F * sizeof(gas_audio_frame);
-	auto fail = [&](int code) {
-		if (mem == GAS_MEM_HOST) {
-			std::memset(out, 0, out_bytes);
-		}
-		return code;
-	};
+	const auto fail = [&](int code) { return fail_out(code, mem, out, out_bytes); };
 	if (frames != F) {
 		return fail(GAS_ERR_FRAME_COUNT);
 	}
@@ -3858,7 +3952,7 @@ int gas_process_block_buses(gas_ctx *c, const gas_audio_frame *src, const uint32
 	}
 	// (three to six buses: one fused launch per pair of buses, the state committed by the last)
 	const bool fused_hrtf = !all_mix && all_plain_hrtf && C == 1 && uni_ok(c) && gas_hrtf_uni_waves() == 8;
-	if (c->fused_streams && !(fused_hrtf && mem == GAS_MEM_DEVICE)) {
+	if (src.fused() && !(fused_hrtf && mem == GAS_MEM_DEVICE)) {
 		return fail(GAS_ERR_INVALID_ARGUMENT); // gas_process_block_streams_buses hands over no rows: only the fused form can sample
 	}
 	const bool staged = !all_mix && all_fx && C == 1 && !fused_hrtf;
@@ -3866,9 +3960,7 @@ int gas_process_block_buses(gas_ctx *c, const gas_audio_frame *src, const uint32
 		return fail(GAS_ERR_INVALID_ARGUMENT); // the staged form regroups: it needs the list
 	}
 	if (!reuse) {
-		c->force_staged = staged;
-		rc = build_groups(c, slots, n);
-		c->force_staged = false;
+		rc = build_groups(c, slots, n, staged);
 		c->cached_n = staged ? UINT32_MAX : c->cached_n; // the staged grouping is this call's only: a later list reuse must regroup
 		if (rc != GAS_OK) {
 			c->cached_n = UINT32_MAX;
@@ -3922,45 +4014,39 @@ int gas_process_block_buses(gas_ctx *c, const gas_audio_frame *src, const uint32
 			GAS_HIP(c, hipMalloc(&c->d_bus_partials, need * sizeof(float)));
 			c->bus_partial_floats = need;
 		}
-		const gas_audio_frame *d_src = src;
+		RowSource d_src = src;
 		gas_audio_frame *d_out = out;
 		float *d_peaks = peaks ? peaks : c->d_peaks;
 		if (mem == GAS_MEM_HOST) {
 			const size_t rows = (size_t)n * F;
-			if (rows > c->d_src_frames) {
-				(void)hipFree(c->d_src);
-				c->d_src = nullptr;
-				c->d_src_frames = 0;
-				GAS_HIP(c, hipMalloc(&c->d_src, rows * sizeof(gas_audio_frame)));
-				c->d_src_frames = rows;
-			}
+			GAS_HIP(c, ensure_src(c, rows));
 			if (n > 0) {
-				GAS_HIP(c, hipMemcpyAsync(c->d_src, src, rows * sizeof(gas_audio_frame), hipMemcpyHostToDevice, c->stream));
+				GAS_HIP(c, hipMemcpyAsync(c->d_src, src.rows, rows * sizeof(gas_audio_frame), hipMemcpyHostToDevice, c->stream));
 			}
 			if (!c->d_bus_out) {
 				GAS_HIP(c, hipMalloc(&c->d_bus_out, (size_t)GAS_MAX_BUSES * C * F * sizeof(gas_audio_frame)));
 			}
-			d_src = c->d_src;
+			d_src.rows = c->d_src;
 			d_out = c->d_bus_out;
 			d_peaks = c->d_peaks;
 		}
 		if (fused_hrtf && n > 0) {
-			const Group &gr = c->groups[G_FX_HRTF];
-			gas_group_args ga;
-			ga.src = d_src;
-			ga.rows = c->cached_identity_rows ? nullptr : c->d_rows + gr.offset;
-			ga.slots = c->d_slots + gr.offset;
-			ga.slot_base = 0;
-			ga.n = n;
-			ga.peaks = d_peaks;
-			if (gr.contiguous) {
-				ga.slots = nullptr;
-				ga.slot_base = gr.slot_base;
-			}
 			// bus b's partial rows: [b * P, (b + 1) * P); one launch per pair of buses, the last one commits the state
+			gas_hrtf_uni_launch lu{ hrtf_common(c) };
+			lu.g = own_hrtf_group(c, d_src.rows, n, d_peaks);
+			lu.peak_bits = c->uni_peak_any && !c->uni_peak_all ? c->d_peak_bits : nullptr;
+			lu.peak_all = c->uni_peak_all;
+			lu.partials = c->d_bus_partials;
+			lu.cursors = d_src.cursors;
+			lu.feed = d_src.feed;
+			lu.routes = c->d_routes;
+			lu.bus_rows = P;
 			const uint32_t passes = (n_buses + 1) / 2;
 			for (uint32_t pass = 0; pass < passes; pass++) {
-				GAS_HIP(c, gas_launch_hrtf_uni(c->stream, ga, c->uni_peak_any && !c->uni_peak_all ? c->d_peak_bits : nullptr, c->uni_peak_all, c->st, c->tab, c->d_tw, F, c->hist_len, c->d_bus_partials, 2 * pass * P, c->fused_streams ? c->d_cursors : nullptr, c->d_fade_env, nullptr, gas_deferred_reduce(), c->d_routes, P, 2 * pass, pass + 1 == passes));
+				lu.p_offset = 2 * pass * P;
+				lu.bus_base = 2 * pass;
+				lu.commit = pass + 1 == passes;
+				GAS_HIP(c, gas_launch_hrtf_uni(lu));
 			}
 		} else if (staged) {
 			// effect kinds: the stages of every chain with rows out, then k_rows_accumulate_buses and one reduce over the
@@ -3968,16 +4054,16 @@ int gas_process_block_buses(gas_ctx *c, const gas_audio_frame *src, const uint32
 			gas_bus_args ba;
 			ba.routes = c->d_routes;
 			ba.n_buses = n_buses;
-			c->run_buses = &ba;
-			const int rcg = run_groups(c, d_src, c->d_slots, c->cached_identity_rows ? nullptr : c->d_rows, c->groups, c->chain_ranges, n, d_out, d_peaks, 0, 1, -1, false, false);
-			c->run_buses = nullptr;
+			RunArgs a = own_list(c, d_src, n, d_out, d_peaks);
+			a.buses = &ba;
+			const int rcg = run_groups(c, a);
 			if (rcg != GAS_OK) {
 				return rcg;
 			}
 		} else if (n > 0) {
 			GAS_HIP(c, hipMemsetAsync(d_peaks, 0, (size_t)n * 2 * sizeof(float), c->stream)); // k_biquad_mix accumulates peaks over channel pairs
 			gas_group_args ga;
-			ga.src = d_src;
+			ga.src = d_src.rows;
 			ga.rows = c->cached_identity_rows ? nullptr : c->d_rows;
 			ga.slots = c->d_slots;
 			ga.slot_base = 0;
@@ -3993,11 +4079,7 @@ int gas_process_block_buses(gas_ctx *c, const gas_audio_frame *src, const uint32
 			GAS_HIP(c, gas_launch_mix_reduce(c->stream, c->d_bus_partials, P, P ? P : 1, n_buses * C, F, d_out));
 		}
 		if (mem == GAS_MEM_HOST) {
-			GAS_HIP(c, hipMemcpyAsync(out, c->d_bus_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
-			if (peaks && n > 0) {
-				GAS_HIP(c, hipMemcpyAsync(peaks, c->d_peaks, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-			}
-			GAS_HIP(c, hipStreamSynchronize(c->stream));
+			GAS_HIP(c, copy_back(c, out, c->d_bus_out, out_bytes, peaks, n));
 		}
 		return GAS_OK;
 	}();
@@ -4059,15 +4141,7 @@ static int process_one(gas_ctx *c, uint32_t slot, int channel, bool mix_channel,
 	if (rc != GAS_OK) {
 		return rc;
 	}
-	if (c->d_src_frames < F) {
-		if (c->d_src) {
-			(void)hipFree(c->d_src);
-			c->d_src = nullptr;
-			c->d_src_frames = 0;
-		}
-		GAS_HIP(c, hipMalloc(&c->d_src, (size_t)F * sizeof(gas_audio_frame)));
-		c->d_src_frames = F;
-	}
+	GAS_HIP(c, ensure_src(c, F));
 	GAS_HIP(c, hipMemcpyAsync(c->d_one_slot, &slot, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
 	GAS_HIP(c, hipMemcpyAsync(c->d_src, src, (size_t)F * sizeof(gas_audio_frame), hipMemcpyHostToDevice, c->stream));
 	std::vector<ChainRange> one_range;
@@ -4080,12 +4154,21 @@ static int process_one(gas_ctx *c, uint32_t slot, int channel, bool mix_channel,
 			return GAS_ERR_NO_HRTF;
 		}
 	}
-	rc = run_groups(c, c->d_src, c->d_one_slot, nullptr, groups, one_range, 1, c->d_out, c->d_peaks, mix_channel ? (uint32_t)channel : 0, 1, force_mode);
+	RunArgs a;
+	a.src.rows = c->d_src;
+	a.slots = c->d_one_slot;
+	a.groups = groups;
+	a.ranges = &one_range;
+	a.n_total = 1;
+	a.out = c->d_out;
+	a.peaks = c->d_peaks;
+	a.channel_begin = mix_channel ? (uint32_t)channel : 0;
+	a.force_mode = force_mode;
+	rc = run_groups(c, a);
 	if (rc != GAS_OK) {
 		return rc;
 	}
-	GAS_HIP(c, hipMemcpyAsync(out, c->d_out, (size_t)F * sizeof(gas_audio_frame), hipMemcpyDeviceToHost, c->stream));
-	GAS_HIP(c, hipStreamSynchronize(c->stream));
+	GAS_HIP(c, copy_back(c, out, c->d_out, (size_t)F * sizeof(gas_audio_frame), nullptr, 0));
 	return GAS_OK;
 }
 

@@ -413,7 +413,37 @@ struct gas_hrtf_launch_plan {
 };
 void gas_hrtf_plan(uint32_t n_fd, uint32_t n_pk, gas_hrtf_launch_plan *plan);
 uint32_t gas_hrtf_partials(uint32_t n); // workgroups of a single-path launch (k_er_only, k_hrtf_rows, k_rows_accumulate)
-hipError_t gas_launch_hrtf_ols(hipStream_t stream, bool with_er, bool crossfade, bool runs /* sum runs of equal directions before the FFT */, const gas_group_args &g_fd, const gas_group_args &g_pk, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *twiddles, uint32_t frames, uint32_t hist_len, uint32_t er_ring_frames, float *partials, uint32_t p_offset, gas_cursor *cursors /* non-null: sample the bound streams in the kernel */, const float *fade_env, const gas_params *fresh /* non-null: unscattered parameter rows in row order */, const gas_deferred_reduce &job = gas_deferred_reduce(), bool blend = false /* GAS_FLAG_HRTF_INTERPOLATE: k_hrtf_ols_blend (no cross-fade, no runs, no carried sum) */, bool fade = false /* GAS_FLAG_HRTF_BLEND_FADE, with blend only: k_hrtf_ols_blend_fade */);
+// A fused launch ("sample inside the HRTF launch") reads no float rows.  Its kernels find, in g.src, the feed table when an
+// entry of the list is fed, else the cursor array itself (k_hrtf_uni.hip: lane_cursor / fed_cursor).  The two launchers
+// below pack their typed fields through here, and nobody else does.
+inline const gas_audio_frame *gas_fused_src(const gas_cursor *cursors, const uint8_t *feed) {
+	return feed ? reinterpret_cast<const gas_audio_frame *>(feed) : reinterpret_cast<const gas_audio_frame *>(cursors);
+}
+// What is the same for every HRTF launch of a context
+struct gas_hrtf_launch_common {
+	hipStream_t stream = nullptr;
+	const gas_dev_state *st = nullptr;
+	const gas_hrtf_table *tab = nullptr;
+	const float2 *twiddles = nullptr;
+	uint32_t frames = 0;
+	uint32_t hist_len = 0;
+	const float *fade_env = nullptr;
+};
+struct gas_hrtf_ols_launch : gas_hrtf_launch_common {
+	bool with_er = false;
+	bool crossfade = false;
+	bool runs = false; // sum runs of equal directions before the FFT
+	gas_group_args g_fd{}, g_pk{};
+	uint32_t er_ring_frames = 0;
+	float *partials = nullptr;
+	uint32_t p_offset = 0;
+	gas_cursor *cursors = nullptr; // non-null: sample the bound streams in the kernel (g_fd.src / g_pk.src are then unused)
+	const gas_params *fresh = nullptr; // non-null: unscattered parameter rows in row order
+	gas_deferred_reduce job;
+	bool blend = false; // GAS_FLAG_HRTF_INTERPOLATE: k_hrtf_ols_blend (no cross-fade, no runs, no carried sum)
+	bool fade = false; // GAS_FLAG_HRTF_BLEND_FADE, with blend only: k_hrtf_ols_blend_fade
+};
+hipError_t gas_launch_hrtf_ols(const gas_hrtf_ols_launch &a);
 // k_hrtf_uni.hip: all plain [HRTF] sources of a callback in one uniform launch; peak_bits (bit per group entry, or
 // nullptr) / peak_all say which sources also get their exact output peak
 uint32_t gas_hrtf_uni_partials(uint32_t n); // workgroups (= partial mixes) of a k_hrtf_uni launch
@@ -439,7 +469,28 @@ struct gas_reduce_jobs {
 hipError_t gas_launch_mix_reduce_jobs(hipStream_t stream, const gas_reduce_jobs &jobs, uint32_t frames);
 bool gas_hrtf_multi_hist_in_lds(uint32_t n, uint32_t frames); // whether a launch over n sources keeps the history rows in LDS between its blocks
 hipError_t gas_launch_hrtf_multi(hipStream_t stream, const gas_group_args &g, const gas_hrtf_blocks &mb, const uint32_t *peak_bits, bool peak_all, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *twiddles, uint32_t frames, uint32_t hist_len, float *partials);
-hipError_t gas_launch_hrtf_uni(hipStream_t stream, const gas_group_args &g, const uint32_t *peak_bits, bool peak_all, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *twiddles, uint32_t frames, uint32_t hist_len, float *partials, uint32_t p_offset, gas_cursor *cursors, const float *fade_env, const gas_params *fresh, const gas_deferred_reduce &job = gas_deferred_reduce(), const gas_bus_route *routes = nullptr /* non-null: the two-bus form */, uint32_t bus_rows = 0, uint32_t bus_base = 0 /* the launch's pair of buses: bus_base, bus_base + 1 */, bool commit = true /* false: leave history / previous gain / peaks to a later pass */, uint32_t er_ring_frames = 0 /* non-zero: the chain [EARLY_REFLECTIONS, HRTF] */, uint32_t peak_from = 0xffffffffu /* entries from here on report their exact peak */, uint32_t peak_bit_base = 0 /* entry e's bit in peak_bits is bit e + peak_bit_base */, uint32_t flt_kind = 0 /* non-zero: the chain [this one-biquad kind, HRTF] */, uint32_t flt_pos = 0 /* its chain position (processor state, effect settings) */, float mix_rate = 0.0f);
+struct gas_hrtf_uni_launch : gas_hrtf_launch_common {
+	gas_group_args g{};
+	const uint32_t *peak_bits = nullptr;
+	bool peak_all = false;
+	float *partials = nullptr;
+	uint32_t p_offset = 0;
+	gas_cursor *cursors = nullptr; // non-null: sample the bound streams in the kernel (g.src is then unused)
+	const uint8_t *feed = nullptr; // with cursors only: the feed table when an entry of the list is fed (GAS_FEED_NONE, above)
+	const gas_params *fresh = nullptr; // non-null: unscattered parameter rows in row order
+	gas_deferred_reduce job;
+	const gas_bus_route *routes = nullptr; // non-null: the two-bus form
+	uint32_t bus_rows = 0;
+	uint32_t bus_base = 0; // the launch's pair of buses: bus_base, bus_base + 1
+	bool commit = true; // false: leave history / previous gain / peaks to a later pass
+	uint32_t er_ring_frames = 0; // non-zero: the chain [EARLY_REFLECTIONS, HRTF]
+	uint32_t peak_from = 0xffffffffu; // entries from here on report their exact peak
+	uint32_t peak_bit_base = 0; // entry e's bit in peak_bits is bit e + peak_bit_base
+	uint32_t flt_kind = 0; // non-zero: the chain [this one-biquad kind, HRTF]
+	uint32_t flt_pos = 0; // its chain position (processor state, effect settings)
+	float mix_rate = 0.0f;
+};
+hipError_t gas_launch_hrtf_uni(const gas_hrtf_uni_launch &a);
 hipError_t gas_launch_er_only(hipStream_t stream, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t er_ring_frames, float *partials, uint32_t p_offset, uint32_t p_stride, gas_audio_frame *rows_out = nullptr);
 // stages of a general effect chain (rows in -> rows out) and its final mix
 hipError_t gas_launch_hrtf_rows(hipStream_t stream, bool crossfade, const gas_group_args &g, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *twiddles, uint32_t frames, gas_audio_frame *rows_out, bool blend = false /* GAS_FLAG_HRTF_INTERPOLATE */, bool fade = false /* GAS_FLAG_HRTF_BLEND_FADE, with blend only */);

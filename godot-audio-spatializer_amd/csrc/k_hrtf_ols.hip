@@ -1280,19 +1280,35 @@ uint32_t gas_hrtf_partials(uint32_t n) {
 	return p.wgs_fd;
 }
 
-hipError_t gas_launch_hrtf_ols(hipStream_t stream, bool with_er, bool crossfade, bool runs, const gas_group_args &g_fd, const gas_group_args &g_pk, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *twiddles, uint32_t frames, uint32_t hist_len, uint32_t er_ring_frames, float *partials, uint32_t p_offset, gas_cursor *cursors, const float *fade_env, const gas_params *fresh, const gas_deferred_reduce &job, bool blend, bool fade) {
-	if (g_fd.n + g_pk.n == 0) {
+hipError_t gas_launch_hrtf_ols(const gas_hrtf_ols_launch &a) {
+	if (a.g_fd.n + a.g_pk.n == 0) {
 		return hipSuccess;
 	}
-	if (frames % 128 != 0 || frames > 512 || hist_len != 512 - frames / 2 || (with_er && cursors)) {
+	if (a.frames % 128 != 0 || a.frames > 512 || a.hist_len != 512 - a.frames / 2 || (a.with_er && a.cursors)) {
 		return hipErrorInvalidValue;
 	}
-	if (blend && (crossfade || runs || job.partials || !st.hrtf_blend)) {
+	if (a.blend && (a.crossfade || a.runs || a.job.partials || !a.st->hrtf_blend)) {
 		return hipErrorInvalidValue;
 	}
-	if (fade && (!blend || !st.hrtf_prev_blend || cursors)) { // (a fade context samples its streams into rows first)
+	if (a.fade && (!a.blend || !a.st->hrtf_prev_blend || a.cursors)) { // (a fade context samples its streams into rows first)
 		return hipErrorInvalidValue;
 	}
+	gas_group_args g_fd = a.g_fd, g_pk = a.g_pk;
+	if (a.cursors) {
+		g_fd.src = g_pk.src = gas_fused_src(a.cursors, nullptr);
+	}
+	// the kernels' arguments, under the names the launch macros below use
+	const hipStream_t stream = a.stream;
+	const gas_dev_state &st = *a.st;
+	const gas_hrtf_table &tab = *a.tab;
+	const float2 *const twiddles = a.twiddles;
+	const uint32_t frames = a.frames, er_ring_frames = a.er_ring_frames, p_offset = a.p_offset;
+	float *const partials = a.partials;
+	gas_cursor *const cursors = a.cursors;
+	const float *const fade_env = a.fade_env;
+	const gas_params *const fresh = a.fresh;
+	const gas_deferred_reduce &job = a.job;
+	const bool with_er = a.with_er, crossfade = a.crossfade, runs = a.runs, blend = a.blend, fade = a.fade;
 	gas_hrtf_launch_plan plan;
 	gas_hrtf_plan(g_fd.n, g_pk.n, &plan);
 	const uint32_t wgs_fd = plan.wgs_fd;

@@ -863,30 +863,35 @@ bool gas_hrtf_uni_twelve(uint32_t n, bool streams, bool buses) {
 	return !streams && !buses && mn != 0 && n >= mn && n >= wgs * UNI_W12 && n <= wgs * UNI_W12 * 64;
 }
 
-hipError_t gas_launch_hrtf_uni(hipStream_t stream, const gas_group_args &g, const uint32_t *peak_bits, bool peak_all, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *twiddles, uint32_t frames, uint32_t hist_len, float *partials, uint32_t p_offset, gas_cursor *cursors, const float *fade_env, const gas_params *fresh, const gas_deferred_reduce &job, const gas_bus_route *routes, uint32_t bus_rows, uint32_t bus_base, bool commit, uint32_t er_ring_frames, uint32_t peak_from, uint32_t peak_bit_base, uint32_t flt_kind, uint32_t flt_pos, float mix_rate) {
-	if (g.n == 0) {
+hipError_t gas_launch_hrtf_uni(const gas_hrtf_uni_launch &a) {
+	if (a.g.n == 0) {
 		return hipSuccess;
 	}
-	if (frames % 128 != 0 || frames > 512 || hist_len != 512 - frames / 2 || (routes && g.order) || ((er_ring_frames || flt_kind) && (routes || cursors || g.order)) || (er_ring_frames && flt_kind)) {
+	if (a.frames % 128 != 0 || a.frames > 512 || a.hist_len != 512 - a.frames / 2 || (a.routes && a.g.order) || ((a.er_ring_frames || a.flt_kind) && (a.routes || a.cursors || a.g.order)) || (a.er_ring_frames && a.flt_kind)) {
 		return hipErrorInvalidValue;
 	}
+	gas_group_args g = a.g;
+	if (a.cursors) {
+		g.src = gas_fused_src(a.cursors, a.feed);
+	}
 	const uint32_t wgs = gas_hrtf_uni_partials(g.n);
-	const uint32_t all = peak_all ? 1u : 0u;
-	const bool twelve = er_ring_frames == 0 && flt_kind == 0 && gas_hrtf_uni_twelve(g.n, cursors != nullptr, routes != nullptr);
+	const uint32_t all = a.peak_all ? 1u : 0u;
+	const bool twelve = a.er_ring_frames == 0 && a.flt_kind == 0 && gas_hrtf_uni_twelve(g.n, a.cursors != nullptr, a.routes != nullptr);
 	const uint32_t nt_hist = g.n >= nt_hist_min_sources() ? 1u : 0u; // history rows larger than what stays cached between callbacks
 	const dim3 grid(wgs), block((twelve ? UNI_W12 : UNI_W) * 64);
-#define GAS_UNI_GO(SQv, PCM, BUS, W) hipLaunchKernelGGL((k_hrtf_uni<SQv, PCM, BUS, W>), grid, block, 0, stream, g, peak_bits, all, st, tab, twiddles, partials, p_offset, cursors, fade_env, fresh, job, routes, bus_rows, bus_base, commit ? 1u : 0u, nt_hist, er_ring_frames, peak_from, peak_bit_base, flt_kind, flt_pos, mix_rate)
+#define GAS_UNI_ARGS g, a.peak_bits, all, *a.st, *a.tab, a.twiddles, a.partials, a.p_offset, a.cursors, a.fade_env, a.fresh, a.job, a.routes, a.bus_rows, a.bus_base, a.commit ? 1u : 0u, nt_hist, a.er_ring_frames, a.peak_from, a.peak_bit_base, a.flt_kind, a.flt_pos, a.mix_rate
+#define GAS_UNI_GO(SQv, PCM, BUS, W) hipLaunchKernelGGL((k_hrtf_uni<SQv, PCM, BUS, W>), grid, block, 0, a.stream, GAS_UNI_ARGS)
 #define GAS_UNI_CASE(SQv)                      \
 	case SQv:                                  \
-		if (flt_kind) {                        \
-			hipLaunchKernelGGL((k_hrtf_uni<SQv, false, false, 8, false, true>), grid, block, 0, stream, g, peak_bits, all, st, tab, twiddles, partials, p_offset, cursors, fade_env, fresh, job, routes, bus_rows, bus_base, commit ? 1u : 0u, nt_hist, er_ring_frames, peak_from, peak_bit_base, flt_kind, flt_pos, mix_rate); \
-		} else if (er_ring_frames) {           \
-			hipLaunchKernelGGL((k_hrtf_uni<SQv, false, false, 8, true>), grid, block, 0, stream, g, peak_bits, all, st, tab, twiddles, partials, p_offset, cursors, fade_env, fresh, job, routes, bus_rows, bus_base, commit ? 1u : 0u, nt_hist, er_ring_frames, peak_from, peak_bit_base, flt_kind, flt_pos, mix_rate); \
-		} else if (routes && cursors) {        \
+		if (a.flt_kind) {                      \
+			hipLaunchKernelGGL((k_hrtf_uni<SQv, false, false, 8, false, true>), grid, block, 0, a.stream, GAS_UNI_ARGS); \
+		} else if (a.er_ring_frames) {         \
+			hipLaunchKernelGGL((k_hrtf_uni<SQv, false, false, 8, true>), grid, block, 0, a.stream, GAS_UNI_ARGS); \
+		} else if (a.routes && a.cursors) {    \
 			GAS_UNI_GO(SQv, true, true, 8);    \
-		} else if (routes) {                   \
+		} else if (a.routes) {                 \
 			GAS_UNI_GO(SQv, false, true, 8);   \
-		} else if (cursors) {                  \
+		} else if (a.cursors) {                \
 			GAS_UNI_GO(SQv, true, false, 8);   \
 		} else if (twelve) {                   \
 			GAS_UNI_GO(SQv, false, false, 12); \
@@ -894,7 +899,7 @@ hipError_t gas_launch_hrtf_uni(hipStream_t stream, const gas_group_args &g, cons
 			GAS_UNI_GO(SQv, false, false, 8);  \
 		}                                      \
 		break;
-	switch (frames / 128) {
+	switch (a.frames / 128) {
 		GAS_UNI_CASE(1)
 		GAS_UNI_CASE(2)
 		GAS_UNI_CASE(3)
@@ -904,6 +909,7 @@ hipError_t gas_launch_hrtf_uni(hipStream_t stream, const gas_group_args &g, cons
 	}
 #undef GAS_UNI_CASE
 #undef GAS_UNI_GO
+#undef GAS_UNI_ARGS
 	return hipGetLastError();
 }
 

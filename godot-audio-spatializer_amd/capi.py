@@ -391,6 +391,26 @@ def bus_routes(n):
     return r
 LISTENER_DTYPE = np.dtype([("basis", np.float32, (3, 3)), ("origin", np.float32, (3,)), ("velocity", np.float32, (3,)), ("pad", np.float32)])
 assert SPAT3D_CONFIG_DTYPE.itemsize == 64 and POSE_DTYPE.itemsize == 48 and LISTENER_DTYPE.itemsize == 64
+# gas_room / gas_er_taps (gas_calc_early_reflections)
+MAX_ROOMS = 64
+ROOM_NONE = 0xFFFFFFFF
+ROOM_DTYPE = np.dtype([("basis", np.float32, (3, 3)), ("origin", np.float32, (3,)), ("half_extent", np.float32, (3,)), ("reflectance", np.float32, (6,)), ("speed_of_sound", np.float32), ("level", np.float32), ("max_order", np.uint32)])
+ER_TAPS_DTYPE = np.dtype([("gain", np.float32, (ER_TAPS,)), ("delay", np.uint32, (ER_TAPS,))])
+assert ROOM_DTYPE.itemsize == 96 and ER_TAPS_DTYPE.itemsize == 64
+
+
+def default_rooms(n=1, **kw):
+    """n box rooms: identity basis at the origin, 4 x 2.5 x 3 m half-extents, every wall 0.8, 343 m/s, level 1, second order."""
+    r = np.zeros(n, ROOM_DTYPE)
+    r["basis"] = np.eye(3, dtype=np.float32)
+    r["half_extent"] = (4.0, 2.5, 3.0)
+    r["reflectance"] = 0.8
+    r["speed_of_sound"] = 343.0
+    r["level"] = 1.0
+    r["max_order"] = 2
+    for k, v in kw.items():
+        r[k] = v
+    return r
 
 
 def default_spat3d_config(n=1, **kw):
@@ -444,6 +464,7 @@ EXPORTS = [
     "gas_hrtf_load_positions",
     "gas_calc_spatialization",
     "gas_calc_spatialization_areas",
+    "gas_calc_early_reflections",
     "gas_stream_create",
     "gas_stream_destroy",
     "gas_stream_get_info",
@@ -555,6 +576,7 @@ def load_library():
     L.gas_stream_last_fused.argtypes = [vp]
     L.gas_calc_spatialization.argtypes = [vp, vp, u32, vp, vp, vp, u32, vp, u32, vp, i32]
     L.gas_calc_spatialization_areas.argtypes = [vp, vp, u32, vp, vp, vp, u32, vp, u32, vp, vp, vp, vp, i32]
+    L.gas_calc_early_reflections.argtypes = [vp, vp, u32, vp, vp, vp, vp, u32, vp, i32]
     L.gas_process_block.argtypes = [vp, vp, vp, u32, u32, vp, vp, i32]
     L.gas_bus_routes_publish.argtypes = [vp, vp, vp, u32]
     L.gas_process_block_buses.argtypes = [vp, vp, vp, u32, u32, vp, u32, vp, i32]
@@ -797,6 +819,22 @@ class SpatializerContext:
         rc = self.lib.gas_calc_spatialization_areas(self.h, _np_ptr(cfgs), len(cfgs), _np_ptr(ci) if ci is not None else None, _np_ptr(poses), _np_ptr(listeners), len(listeners), _np_ptr(slots), n, _np_ptr(areas), _np_ptr(lap) if lap is not None else None, _np_ptr(out), _np_ptr(reverb), MEM_HOST)
         self._check(rc, "gas_calc_spatialization_areas")
         return out, reverb
+
+    def calc_early_reflections(self, rooms, poses, listener, slots=None, room_index=None):
+        """Host-array form of gas_calc_early_reflections; returns the generated taps (ER_TAPS_DTYPE [n]).  slots=None: the
+        pure generator (nothing in the context changes); else the taps also go into the slots' parameter rows."""
+        rooms = np.ascontiguousarray(rooms, dtype=ROOM_DTYPE).reshape(-1)
+        poses = np.ascontiguousarray(poses, dtype=POSE_DTYPE).reshape(-1)
+        listener = np.ascontiguousarray(listener, dtype=LISTENER_DTYPE).reshape(-1)
+        assert len(listener) == 1
+        n = len(poses)
+        sl = np.ascontiguousarray(slots, dtype=np.uint32) if slots is not None else None
+        ri = np.ascontiguousarray(room_index, dtype=np.uint32) if room_index is not None else None
+        assert (sl is None or len(sl) == n) and (ri is None or len(ri) == n)
+        out = np.zeros(n, ER_TAPS_DTYPE)
+        rc = self.lib.gas_calc_early_reflections(self.h, _np_ptr(rooms), len(rooms), _np_ptr(ri) if ri is not None else None, _np_ptr(poses), _np_ptr(listener), _np_ptr(sl) if sl is not None else None, n, _np_ptr(out), MEM_HOST)
+        self._check(rc, "gas_calc_early_reflections")
+        return out
 
     # ---- device-resident streams (SURVEY.md 8f#2) ----
     def stream_create(self, pcm, format=None, channels=None, frames=None):

@@ -256,6 +256,7 @@ struct gas_ctx {
 	gas_area_send *d_calc_areas = nullptr; // gas_calc_spatialization_areas staging (host-memory calls)
 	float *d_calc_lap = nullptr;
 	gas_audio_frame *d_calc_reverb = nullptr;
+	gas_room *d_calc_rooms = nullptr; // gas_calc_early_reflections: its rooms (everything else it stages lies in the buffers above)
 
 	// several output buses: slot-indexed routes, host mirror + device table, own partial planes
 	std::vector<gas_bus_route> h_routes; // guarded by params_mu
@@ -2225,6 +2226,7 @@ void gas_ctx_destroy(gas_ctx *c) {
 	(void)hipFree(c->d_calc_areas);
 	(void)hipFree(c->d_calc_lap);
 	(void)hipFree(c->d_calc_reverb);
+	(void)hipFree(c->d_calc_rooms);
 	(void)hipHostFree(c->h_params);
 	(void)hipHostFree(c->h_upload);
 	(void)hipHostFree(c->h_upload_slots);
@@ -2911,6 +2913,95 @@ int gas_calc_spatialization_areas(gas_ctx *c, const gas_spatializer3d_config *cf
 	for (uint32_t i = 0; i < n; i++) {
 		c->slots[slots[i]].has_params = 1;
 	}
+	return GAS_OK;
+}
+
+int gas_calc_early_reflections(gas_ctx *c, const gas_room *rooms, uint32_t n_rooms, const uint32_t *room_index, const gas_source_pose *poses, const gas_listener *listener, const uint32_t *slots, uint32_t n, gas_er_taps *out_taps, int mem) {
+	if (!c || !rooms || !poses || !listener || (!slots && !out_taps) || (mem != GAS_MEM_HOST && mem != GAS_MEM_DEVICE)) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (n_rooms == 0 || n_rooms > GAS_MAX_ROOMS || n > c->cfg.max_sources || c->cfg.er_ring_frames == 0) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	for (uint32_t r = 0; r < n_rooms; r++) {
+		const gas_room &R = rooms[r];
+		bool ok = R.speed_of_sound > 0.0f && std::isfinite(R.speed_of_sound) && R.level >= 0.0f && std::isfinite(R.level) && (R.max_order == 1 || R.max_order == 2);
+		for (int a = 0; a < 3; a++) {
+			ok = ok && R.half_extent[a] > 0.0f && std::isfinite(R.half_extent[a]);
+		}
+		for (int w = 0; w < 6; w++) {
+			ok = ok && R.reflectance[w] >= 0.0f && R.reflectance[w] <= 1.0f;
+		}
+		if (!ok) {
+			return GAS_ERR_INVALID_ARGUMENT;
+		}
+	}
+	for (uint32_t i = 0; i < n; i++) {
+		if (slots && (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used)) {
+			return GAS_ERR_BAD_SLOT;
+		}
+		if (room_index && room_index[i] >= n_rooms && room_index[i] != GAS_ROOM_NONE) {
+			return GAS_ERR_INVALID_ARGUMENT;
+		}
+	}
+	if (n == 0) {
+		return GAS_OK;
+	}
+	std::lock_guard<std::mutex> lk(c->calc_mu);
+	if (slots) {
+		if (++c->calc_stamp_gen == 0) {
+			std::fill(c->calc_stamp.begin(), c->calc_stamp.end(), 0u);
+			c->calc_stamp_gen = 1;
+		}
+		for (uint32_t i = 0; i < n; i++) {
+			if (c->calc_stamp[slots[i]] == c->calc_stamp_gen) {
+				return GAS_ERR_INVALID_ARGUMENT; // one playback twice: two lane groups would race on its row
+			}
+			c->calc_stamp[slots[i]] = c->calc_stamp_gen;
+		}
+	}
+	GAS_HIP(c, hipSetDevice(c->cfg.device));
+	if (slots) { // the launch writes table rows: whatever must still see or precede the old ones goes first.  Without
+		// slots the launch reads and writes nothing of the context's but the staging buffers
+		int rc = flush_deferred(c); // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch
+		rc = rc != GAS_OK ? rc : flush_pending_params(c);
+		rc = rc != GAS_OK ? rc : flush_param_rows(c); // host-published rows first: the launch's two fields land on top of them
+		if (rc != GAS_OK) {
+			return rc;
+		}
+	}
+	if (!c->d_calc_rooms) {
+		GAS_HIP(c, hipMalloc(&c->d_calc_rooms, sizeof(gas_room) * GAS_MAX_ROOMS));
+	}
+	GAS_HIP(c, hipMemcpyAsync(c->d_calc_rooms, rooms, sizeof(gas_room) * n_rooms, hipMemcpyHostToDevice, c->stream));
+	GAS_HIP(c, hipMemcpyAsync(c->d_calc_listeners, listener, sizeof(gas_listener), hipMemcpyHostToDevice, c->stream));
+	if (slots) {
+		GAS_HIP(c, hipMemcpyAsync(c->d_calc_slots, slots, sizeof(uint32_t) * n, hipMemcpyHostToDevice, c->stream));
+	}
+	if (room_index) { // config indices and room indices never travel in the same call
+		GAS_HIP(c, hipMemcpyAsync(c->d_calc_cfgidx, room_index, sizeof(uint32_t) * n, hipMemcpyHostToDevice, c->stream));
+	}
+	const gas_source_pose *d_poses = poses;
+	gas_er_taps *d_taps = out_taps;
+	if (mem == GAS_MEM_HOST) {
+		if (!c->d_calc_poses) {
+			GAS_HIP(c, hipMalloc(&c->d_calc_poses, sizeof(gas_source_pose) * c->cfg.max_sources));
+		}
+		GAS_HIP(c, hipMemcpyAsync(c->d_calc_poses, poses, sizeof(gas_source_pose) * n, hipMemcpyHostToDevice, c->stream));
+		d_poses = c->d_calc_poses;
+		if (out_taps) { // staged in the read-back buffer of gas_calc_spatialization's rows: a gas_er_taps is half a row
+			static_assert(sizeof(gas_er_taps) <= sizeof(gas_params), "gas_er_taps are staged in d_calc_out");
+			if (!c->d_calc_out) {
+				GAS_HIP(c, hipMalloc(&c->d_calc_out, sizeof(gas_params) * c->cfg.max_sources));
+			}
+			d_taps = reinterpret_cast<gas_er_taps *>(c->d_calc_out);
+		}
+	}
+	GAS_HIP(c, gas_launch_calc_er(c->stream, c->d_calc_rooms, room_index ? c->d_calc_cfgidx : nullptr, d_poses, c->d_calc_listeners, c->d_calc_slots, n, c->cfg.er_ring_frames - c->cfg.frames, c->cfg.mix_rate, slots ? c->st.params : nullptr, d_taps));
+	if (mem == GAS_MEM_HOST && out_taps) {
+		GAS_HIP(c, hipMemcpyAsync(out_taps, d_taps, sizeof(gas_er_taps) * n, hipMemcpyDeviceToHost, c->stream));
+	}
+	GAS_HIP(c, hipStreamSynchronize(c->stream)); // the host staging arrays are the caller's
 	return GAS_OK;
 }
 

@@ -75,3 +75,22 @@ def draw_blends(rng, n, dirs):
         b["weight"][i, pos] = (w / w.sum()).astype(np.float32)
         b["dir"][i, pos] = rng.choice(dirs, size=k, replace=dirs < k)
     return b
+
+
+def draw_room_scene(rng, n, n_rooms=4):
+    """A scene for gas_calc_early_reflections: (rooms ROOM_DTYPE [n_rooms], room_index uint32 [n], poses POSE_DTYPE [n],
+    listener LISTENER_DTYPE [1]).  Axis-aligned boxes around one listener at the origin, half-extents 2 .. 10 m, wall
+    reflectances 0.3 .. 0.95; every source uniform inside its room."""
+    from .capi import LISTENER_DTYPE, POSE_DTYPE, default_rooms
+
+    rooms = default_rooms(n_rooms)
+    rooms["half_extent"] = rng.uniform(2.0, 10.0, (n_rooms, 3))
+    rooms["origin"] = rng.uniform(-0.5, 0.5, (n_rooms, 3)) * rooms["half_extent"]
+    rooms["reflectance"] = rng.uniform(0.3, 0.95, (n_rooms, 6))
+    room_index = rng.integers(0, n_rooms, n).astype(np.uint32)
+    poses = np.zeros(n, POSE_DTYPE)
+    poses["position"] = rooms["origin"][room_index] + rng.uniform(-0.98, 0.98, (n, 3)) * rooms["half_extent"][room_index]
+    poses["pitch_scale"] = 1.0
+    listener = np.zeros(1, LISTENER_DTYPE)
+    listener["basis"] = np.eye(3, dtype=np.float32)
+    return rooms, room_index, poses, listener

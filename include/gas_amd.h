@@ -743,6 +743,64 @@ typedef struct gas_area_send {
  * gas_calc_spatialization. */
 int gas_calc_spatialization_areas(gas_ctx *ctx, const gas_spatializer3d_config *cfgs, uint32_t n_cfgs, const uint32_t *cfg_index, const gas_source_pose *poses, const gas_listener *listeners, uint32_t n_listeners, const uint32_t *slots, uint32_t n, const gas_area_send *areas, const float *listener_area_pos, gas_params *out_params, gas_audio_frame *out_reverb, int mem);
 
+/* ---- the producer of GAS_FX_EARLY_REFLECTIONS' parameters -------------------------------------------
+ * NEW (the effect has no counterpart in the engine, and neither has this).  n sources and one listener inside
+ * axis-aligned box rooms: the image sources up to second order, the eight strongest of them as er_gain / er_delay,
+ * in one launch per physics tick.
+ *
+ * The rule, in float32 in this order, no fused multiply-adds.  M = er_ring_frames - frames, rate = the context's
+ * mix_rate, h = half_extent, c = speed_of_sound.
+ *  1. s = basis^T (position - origin), l = basis^T (listener->origin - origin): both in the room's frame.
+ *  2. room_index[i] == GAS_ROOM_NONE, or any |s_a| > h_a, or any |l_a| > h_a: all eight taps are (gain 0, delay 1).
+ *  3. d0 = |s - l|: sqrtf of the sum of the squares in x, y, z order.
+ *  4. The candidates are the 24 integer triples m with 1 <= |m_x| + |m_y| + |m_z| <= 2, numbered in ascending order
+ *     of (|m|_1, m_x, m_y, m_z): (-1,0,0), (0,-1,0), (0,0,-1), (0,0,1), (0,1,0), (1,0,0), (-2,0,0), (-1,-1,0), ...
+ *  5. img_a = 2 m_a h_a + (m_a odd ? -s_a : s_a); dist = |img - l|.  R starts at 1 and, in axis order x, y, z, is
+ *     multiplied p_a times by the +a wall's reflectance, then q_a times by the -a wall's: p_a = ceil(m_a / 2),
+ *     q_a = floor(m_a / 2) for m_a > 0, swapped for m_a < 0.  g = ((level R) d0) / dist -- the reflection relative to
+ *     the direct sound under 1/r, so g <= level.  fr = ((dist - d0) / c) rate; delay_raw = rintf(fr), ties to even.
+ *  6. g becomes 0 when |m|_1 > max_order, when !(dist > 0), when g is not finite, or when delay_raw > M: the ring does
+ *     not reach that far, and the effect's own clamp would put the echo at the wrong time.  delay = max(delay_raw, 1).
+ *  7. Tap k takes the candidate of rank k, by g descending, ties to the lower candidate number.  A tap whose
+ *     candidate has g == 0 is written as (0, 1).
+ * Not modelled: a direction per reflection, smoothing of the taps between callbacks (the effect switches gains and
+ * delays at block boundaries), rooms that are no boxes, occlusion. */
+#define GAS_MAX_ROOMS 64
+#define GAS_ROOM_NONE 0xffffffffu
+typedef struct gas_room { /* NEW; 96 bytes */
+	float basis[3][3]; /* global = basis * local + origin, orthonormal (as gas_listener) */
+	float origin[3]; /* centre of the box */
+	float half_extent[3]; /* > 0 */
+	float reflectance[6]; /* amplitude factor per wall, 0 .. 1: -x, +x, -y, +y, -z, +z */
+	float speed_of_sound; /* > 0, metres per second */
+	float level; /* >= 0, linear, on every reflection */
+	uint32_t max_order; /* 1 or 2 */
+} gas_room;
+typedef struct gas_er_taps {
+	float gain[GAS_ER_TAPS];
+	uint32_t delay[GAS_ER_TAPS];
+} gas_er_taps;
+
+/* rooms [n_rooms], 1 <= n_rooms <= GAS_MAX_ROOMS, room_index ([n] or NULL = room 0 for all; GAS_ROOM_NONE = the source
+ * sits in no room), listener (one; only its origin is read) and slots ([n] or NULL) are host arrays; poses ([n]; only
+ * position is read) and out_taps ([n], may be NULL) are host or device pointers according to `mem`.
+ * slots != NULL: the taps go into the slots' rows of the parameter table, the rows gas_calc_spatialization writes.
+ * Recorded or deferred batched callbacks run first, and rows published from the host before the call are uploaded
+ * before the launch, which overwrites er_gain and er_delay and nothing else.  It does not make a slot "have
+ * parameters": a slot that never got a whole row is still refused by gas_process_block with GAS_ERR_NO_PARAMS.  A later
+ * gas_params_publish[_batch] of the slot replaces the whole row, these fields included, as it replaces
+ * gas_calc_spatialization's -- so within a tick: publish, then gas_calc_spatialization, then this call.
+ * slots == NULL: a pure generator.  Nothing in the context changes and out_taps is required.  (The road for gas_host_*
+ * users, whose rows are published whole on the audio thread: merge the taps into the POD and publish that.)
+ * out_taps, when given, holds exactly what was generated, in either mode.
+ * GAS_ERR_INVALID_ARGUMENT, with nothing written: a NULL ctx / rooms / poses / listener; slots and out_taps both NULL;
+ * a bad mem; n_rooms 0 or > GAS_MAX_ROOMS; n > max_sources; a context with er_ring_frames == 0; a room_index[i] that
+ * is neither < n_rooms nor GAS_ROOM_NONE; a slot named twice; a room whose half_extent or speed_of_sound is not
+ * positive and finite, whose level is negative or not finite, with a reflectance outside [0, 1] or a max_order other
+ * than 1 or 2.  GAS_ERR_BAD_SLOT: a slot that is not in use.  n == 0 is GAS_OK.
+ * Physics thread: it shares gas_calc_spatialization's lock and staging buffers. */
+int gas_calc_early_reflections(gas_ctx *ctx, const gas_room *rooms, uint32_t n_rooms, const uint32_t *room_index, const gas_source_pose *poses, const gas_listener *listener, const uint32_t *slots, uint32_t n, gas_er_taps *out_taps, int mem);
+
 
 /* ---- device-resident source sampling ------------------------------------------------
  * The step in front of the path: AudioStreamPlayback::mix into the 64-frame lookahead window with the

@@ -295,6 +295,7 @@ FLAG_XCD_ORDER = 32
 FLAG_BATCHED_LAUNCH = 64
 FLAG_HRTF_INTERPOLATE = 128
 FLAG_HRTF_BLEND_FADE = 256  # with FLAG_HRTF_INTERPOLATE only: fade from the previous callback's blend to this one's
+FLAG_ER_TAP_FADE = 512  # fade early-reflection taps from the row a slot last rendered with to this callback's (needs er_ring_frames)
 
 STATUS = {
     0: "GAS_OK",

@@ -367,6 +367,10 @@ inline bool fade_on(const gas_ctx *c) {
 	return (c->cfg.flags & GAS_FLAG_HRTF_BLEND_FADE) != 0;
 }
 
+inline bool er_fade_on(const gas_ctx *c) {
+	return (c->cfg.flags & GAS_FLAG_ER_TAP_FADE) != 0;
+}
+
 inline bool wants_peak(const gas_ctx *c, const SlotInfo &si) {
 	return si.draining || !(c->cfg.flags & GAS_FLAG_PEAKS_DRAINING_ONLY);
 }
@@ -623,8 +627,8 @@ uint64_t group_bytes(const gas_ctx *c, int gt, uint32_t n) {
 			tab = (uint64_t)c->tab.dirs * 2 * GAS_HRTF_TAPS * 4;
 			break;
 		case G_FX_ER:
-			S = 8 + 64 + 8;
-			H = (uint64_t)GAS_ER_TAPS * F * 8 + F * 8; // tap gathers + ring write
+			S = 8 + 64 + 8 + (er_fade_on(c) ? 2 * 64 : 0); // position r/w, taps, peak; GAS_FLAG_ER_TAP_FADE: the old tap row r/w
+			H = (uint64_t)GAS_ER_TAPS * F * 8 + F * 8; // tap gathers + ring write (a fading source's second set of gathers re-reads the same ring: not compulsory bytes)
 			break;
 		case G_FX_ER_HRTF:
 		case G_FX_ER_HRTF_PK:
@@ -1093,7 +1097,7 @@ int run_groups(gas_ctx *c, const RunArgs &a) {
 						if (kind == GAS_FX_HIGHSHELF) {
 							e = gas_launch_biquad_mix(c->stream, GAS_MODE_FX_HIGHSHELF, in, c->st, F, (uint32_t)j, 1, c->cfg.mix_rate, parts, 0, c->partial_rows, reinterpret_cast<float *>(outb));
 						} else if (kind == GAS_FX_EARLY_REFLECTIONS) {
-							e = gas_launch_er_only(c->stream, in, c->st, F, c->cfg.er_ring_frames, parts, 0, c->partial_rows, outb);
+							e = gas_launch_er_only(c->stream, in, c->st, F, c->cfg.er_ring_frames, parts, 0, c->partial_rows, outb, er_fade_on(c));
 						} else if (kind == GAS_FX_HRTF) {
 							e = gas_launch_hrtf_rows(c->stream, (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) != 0, in, c->st, c->tab, c->d_tw, F, outb, blend_on(c), fade_on(c));
 						} else { // a family's kind: settings (and state, or the slot's pool entry) of chain position j
@@ -1115,7 +1119,7 @@ int run_groups(gas_ctx *c, const RunArgs &a) {
 				}
 			} break;
 			case G_FX_ER:
-				e = gas_launch_er_only(c->stream, ga, c->st, F, c->cfg.er_ring_frames, parts, p_off, c->partial_rows);
+				e = gas_launch_er_only(c->stream, ga, c->st, F, c->cfg.er_ring_frames, parts, p_off, c->partial_rows, nullptr, er_fade_on(c));
 				break;
 		}
 		GAS_HIP(c, e);
@@ -2168,6 +2172,7 @@ void gas_ctx_destroy(gas_ctx *c) {
 	(void)hipFree(c->d_upload_slots);
 	(void)hipFree(c->st.hrtf_blend);
 	(void)hipFree(c->st.hrtf_prev_blend);
+	(void)hipFree(c->st.er_prev);
 	(void)hipHostFree(c->h_blend_upload);
 	(void)hipFree(c->st.dist_h);
 	(void)hipFree(c->st.comp_rundb);
@@ -2259,6 +2264,9 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 	if ((cfg->flags & GAS_FLAG_HRTF_BLEND_FADE) != 0 && ((cfg->flags & GAS_FLAG_HRTF_INTERPOLATE) == 0 || (cfg->flags & (GAS_FLAG_HRTF_CROSSFADE | GAS_FLAG_DIRECTION_RUNS | GAS_FLAG_DIRECTION_ORDER | GAS_FLAG_XCD_ORDER)) != 0)) {
 		return GAS_ERR_INVALID_ARGUMENT; // the fade is between blend rows: nothing to fade without them
 	}
+	if ((cfg->flags & GAS_FLAG_ER_TAP_FADE) != 0 && cfg->er_ring_frames == 0) {
+		return GAS_ERR_INVALID_ARGUMENT; // the fade is between tap rows: no early-reflection stage without a ring
+	}
 	int n_dev = 0;
 	if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0 || cfg->device < 0 || cfg->device >= n_dev) {
 		return GAS_ERR_NO_DEVICE;
@@ -2269,6 +2277,9 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 	}
 	c->cfg = *cfg;
 	c->hist_len = 512 - cfg->frames / 2;
+	if (er_fade_on(c)) { // the fused [ER, HRTF] kernels have no fading form: the tail of a staged chain stays two launches, whatever GAS_UNI_ER says
+		c->uni_er_enabled = false;
+	}
 	if (const char *v = std::getenv("GAS_XCD_ORDER_AUTO_MIN")) {
 		c->xcd_order_auto_min = (uint32_t)std::strtoul(v, nullptr, 10);
 	}
@@ -2302,6 +2313,10 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 		if ((cfg->flags & GAS_FLAG_HRTF_BLEND_FADE) != 0) { // no slot has rendered yet: no old row to fade from
 			GAS_HIP(c, hipMalloc(&c->st.hrtf_prev_blend, sizeof(gas_hrtf_blend) * N));
 			GAS_HIP(c, hipMemsetAsync(c->st.hrtf_prev_blend, 0, sizeof(gas_hrtf_blend) * N, c->stream));
+		}
+		if (er_fade_on(c)) { // no slot has rendered yet: rendered == 0 everywhere
+			GAS_HIP(c, hipMalloc(&c->st.er_prev, sizeof(gas_er_prev) * N));
+			GAS_HIP(c, hipMemsetAsync(c->st.er_prev, 0, sizeof(gas_er_prev) * N, c->stream));
 		}
 		c->st.dyn_stride = (uint32_t)N;
 		GAS_HIP(c, hipMalloc(&c->st.dist_h, sizeof(float) * GAS_MAX_EFFECTS * 2 * N));
@@ -2482,12 +2497,15 @@ int gas_source_alloc(gas_ctx *c, int kind, const int32_t *effects, uint32_t n_ef
 	if (!c || !out_slot || n_effects > GAS_MAX_EFFECTS || (n_effects > 0 && !effects)) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
-	const int g = group_of(kind, effects, n_effects);
+	int g = group_of(kind, effects, n_effects);
 	if (g == -1) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
 	if (g == -2) {
 		return GAS_ERR_UNSUPPORTED_CHAIN;
+	}
+	if (g == G_FX_ER_HRTF && er_fade_on(c)) {
+		g = G_FX_GENERIC; // GAS_FLAG_ER_TAP_FADE: the fused kernels do not fade; k_er_only<FADE> writes rows, the HRTF stage reads them
 	}
 	const uint32_t sig = (g == G_FX_GENERIC || (kind == GAS_KIND_EFFECT && n_effects > 0)) ? chain_signature(effects, n_effects) : 0; // fused chains keep theirs too: a bus callback runs them staged
 	if ((g == G_FX_ER || g == G_FX_ER_HRTF || (g == G_FX_GENERIC && chain_has(sig, GAS_FX_EARLY_REFLECTIONS))) && c->cfg.er_ring_frames == 0) {

@@ -75,6 +75,13 @@ struct gas_line_geo {
 enum { GAS_BQ_FIELDS = 10 }; // b0 b1 b2 a1 a2 ha1 ha2 hb1 hb2 prev_vol
 enum { BQ_B0 = 0, BQ_B1, BQ_B2, BQ_A1, BQ_A2, BQ_HA1, BQ_HA2, BQ_HB1, BQ_HB2, BQ_PREV };
 
+// GAS_FLAG_ER_TAP_FADE: er_gain[8] as bits, then min(er_delay[8], er_ring_frames - frames); rendered != 0 once the words hold
+// a row the stage rendered with.
+struct gas_er_prev {
+	uint32_t word[2 * GAS_ER_TAPS];
+	uint32_t rendered;
+};
+
 struct gas_dev_state {
 	float *bq; // [GAS_BQ_FIELDS][max_sources * 8]
 	size_t bq_stride; // max_sources * 8
@@ -128,6 +135,10 @@ struct gas_dev_state {
 	// stage last rendered with, all-zero = none yet (nullptr without the flag); read and replaced by
 	// k_hrtf_ols_blend_fade / k_hrtf_rows_blend_fade, zeroed with the slot's other DSP state (k_zero_slot)
 	gas_hrtf_blend *hrtf_prev_blend; // [max_sources]
+	// GAS_FLAG_ER_TAP_FADE: the effective tap row each slot's early-reflection stage last rendered with, and whether it has
+	// rendered at all (an all-zero row is a legal tap set); nullptr without the flag.  Read and replaced by k_er_only<FADE>;
+	// `rendered` is cleared with the slot's other DSP state (k_zero_slot)
+	gas_er_prev *er_prev; // [max_sources]
 };
 
 // Device-resident playback cursor: what SpatialPlaybackListNode + the engine's sampler hold.
@@ -491,7 +502,7 @@ struct gas_hrtf_uni_launch : gas_hrtf_launch_common {
 	float mix_rate = 0.0f;
 };
 hipError_t gas_launch_hrtf_uni(const gas_hrtf_uni_launch &a);
-hipError_t gas_launch_er_only(hipStream_t stream, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t er_ring_frames, float *partials, uint32_t p_offset, uint32_t p_stride, gas_audio_frame *rows_out = nullptr);
+hipError_t gas_launch_er_only(hipStream_t stream, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t er_ring_frames, float *partials, uint32_t p_offset, uint32_t p_stride, gas_audio_frame *rows_out = nullptr, bool fade = false /* GAS_FLAG_ER_TAP_FADE */);
 // stages of a general effect chain (rows in -> rows out) and its final mix
 hipError_t gas_launch_hrtf_rows(hipStream_t stream, bool crossfade, const gas_group_args &g, const gas_dev_state &st, const gas_hrtf_table &tab, const float2 *twiddles, uint32_t frames, gas_audio_frame *rows_out, bool blend = false /* GAS_FLAG_HRTF_INTERPOLATE */, bool fade = false /* GAS_FLAG_HRTF_BLEND_FADE, with blend only */);
 hipError_t gas_launch_rows_accumulate(hipStream_t stream, const gas_group_args &g, uint32_t frames, float *partials, uint32_t p_offset);

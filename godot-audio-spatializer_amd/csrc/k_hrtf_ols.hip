@@ -1149,7 +1149,13 @@ __global__ __launch_bounds__(64) void k_hrtf_table(const float *__restrict__ hri
 }
 
 // The chain [EARLY_REFLECTIONS] alone: stereo out, lane = frame, wave = source.
-template <int FQ>
+// FADE (GAS_FLAG_ER_TAP_FADE): lanes 0 .. 15 hold the source's new effective row (eight gains, eight clamped delays) and
+// the one st.er_prev keeps from the slot's last render.  A source that has rendered before and whose rows differ in any
+// word -- one ballot, so the decision is the wave's -- runs the tap loop a second time over the old row (its words handed
+// round by readlane: 16 gathers per frame, the same select and wrap) and stores t * Y_new + (1 - t) * Y_old; every other
+// source takes the loop below as the unflagged kernel does.  Ring store, er_pos advance and the sums are those of the
+// unflagged form; the old row is replaced once the source's frames are done.
+template <int FQ, bool FADE = false>
 __global__ __launch_bounds__(WAVES * 64) void k_er_only(gas_group_args g, gas_dev_state st, uint32_t er_R, float *__restrict__ partials, uint32_t p_offset, gas_audio_frame *__restrict__ rows_out) {
 	constexpr uint32_t F = FQ * 64;
 	__shared__ float red_all[WAVES * F * 2];
@@ -1171,6 +1177,17 @@ __global__ __launch_bounds__(WAVES * 64) void k_er_only(gas_group_args g, gas_de
 		const uint32_t er_pos = st.er_pos[slot];
 		gas_audio_frame *ring = st.er_ring + (size_t)slot * er_R;
 		float pkl = 0.0f, pkr = 0.0f;
+		uint32_t new_w = 0, old_w = 0; // FADE, lanes 0 .. 15: word `lane` of the new and of the stored effective row
+		bool changed = false; // wave-uniform
+		if constexpr (FADE) {
+			uint32_t *prev = st.er_prev[slot].word;
+			if (lane < 2 * GAS_ER_TAPS) {
+				const uint32_t raw = reinterpret_cast<const uint32_t *>(P->er_gain)[lane]; // er_gain[8], er_delay[8]: 16 words in a row
+				new_w = lane < GAS_ER_TAPS || raw < er_R - F ? raw : er_R - F;
+				old_w = prev[lane];
+			}
+			changed = st.er_prev[slot].rendered != 0 && __ballot(new_w != old_w) != 0;
+		}
 #pragma unroll
 		for (int q = 0; q < FQ; q++) {
 			const int f = lane + 64 * q;
@@ -1187,6 +1204,24 @@ __global__ __launch_bounds__(WAVES * 64) void k_er_only(gas_group_args g, gas_de
 				yl = yl + gk * xp.left;
 				yr = yr + gk * xp.right;
 			}
+			if constexpr (FADE) {
+				if (changed) { // the same sum over the old row (a shared helper for the two loops changes the unflagged kernels' code)
+					float ol = fr.left, orr = fr.right;
+#pragma unroll
+					for (int k = 0; k < GAS_ER_TAPS; k++) {
+						const uint32_t du = (uint32_t)__builtin_amdgcn_readlane((int)old_w, GAS_ER_TAPS + k);
+						const int d = (int)(du < er_R - F ? du : er_R - F); // stored clamped; kept so that no word of the table can index past the ring
+						const float gk = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)old_w, k));
+						const int i = f - d;
+						gas_audio_frame xp = i >= 0 ? srow[i] : ring[(er_pos + (uint32_t)(i + (int)er_R)) & (er_R - 1)];
+						ol = ol + gk * xp.left;
+						orr = orr + gk * xp.right;
+					}
+					const float t = (float)f * (1.0f / (float)F);
+					yl = t * yl + (1.0f - t) * ol;
+					yr = t * yr + (1.0f - t) * orr;
+				}
+			}
 			if (rows_out) { // a stage of a general effect chain: dense per-source rows, no sum, no peak
 				rows_out[(size_t)e * F + f] = gas_audio_frame{ yl, yr };
 			} else {
@@ -1198,6 +1233,14 @@ __global__ __launch_bounds__(WAVES * 64) void k_er_only(gas_group_args g, gas_de
 		}
 		pkl = wave_max(pkl);
 		pkr = wave_max(pkr);
+		if constexpr (FADE) { // the row this block rendered with is the next block's old row
+			if (lane < 2 * GAS_ER_TAPS) {
+				st.er_prev[slot].word[lane] = new_w;
+			}
+			if (lane == 0) {
+				st.er_prev[slot].rendered = 1;
+			}
+		}
 		if (lane == 0) {
 			st.er_pos[slot] = (er_pos + F) & (er_R - 1);
 			if (!rows_out) {
@@ -1381,25 +1424,44 @@ hipError_t gas_launch_hrtf_ols(const gas_hrtf_ols_launch &a) {
 	return hipGetLastError();
 }
 
-hipError_t gas_launch_er_only(hipStream_t stream, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t er_ring_frames, float *partials, uint32_t p_offset, uint32_t p_stride, gas_audio_frame *rows_out) {
+hipError_t gas_launch_er_only(hipStream_t stream, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t er_ring_frames, float *partials, uint32_t p_offset, uint32_t p_stride, gas_audio_frame *rows_out, bool fade) {
 	(void)p_stride;
 	if (g.n == 0) {
 		return hipSuccess;
+	}
+	if (fade && !st.er_prev) {
+		return hipErrorInvalidValue;
 	}
 	const uint32_t wgs = gas_hrtf_partials(g.n);
 	dim3 grid(wgs), block(WAVES * 64);
 	switch (frames / 64) {
 		case 2:
-			hipLaunchKernelGGL((k_er_only<2>), grid, block, 0, stream, g, st, er_ring_frames, partials, p_offset, rows_out);
+			if (fade) {
+				hipLaunchKernelGGL((k_er_only<2, true>), grid, block, 0, stream, g, st, er_ring_frames, partials, p_offset, rows_out);
+			} else {
+				hipLaunchKernelGGL((k_er_only<2>), grid, block, 0, stream, g, st, er_ring_frames, partials, p_offset, rows_out);
+			}
 			break;
 		case 4:
-			hipLaunchKernelGGL((k_er_only<4>), grid, block, 0, stream, g, st, er_ring_frames, partials, p_offset, rows_out);
+			if (fade) {
+				hipLaunchKernelGGL((k_er_only<4, true>), grid, block, 0, stream, g, st, er_ring_frames, partials, p_offset, rows_out);
+			} else {
+				hipLaunchKernelGGL((k_er_only<4>), grid, block, 0, stream, g, st, er_ring_frames, partials, p_offset, rows_out);
+			}
 			break;
 		case 6:
-			hipLaunchKernelGGL((k_er_only<6>), grid, block, 0, stream, g, st, er_ring_frames, partials, p_offset, rows_out);
+			if (fade) {
+				hipLaunchKernelGGL((k_er_only<6, true>), grid, block, 0, stream, g, st, er_ring_frames, partials, p_offset, rows_out);
+			} else {
+				hipLaunchKernelGGL((k_er_only<6>), grid, block, 0, stream, g, st, er_ring_frames, partials, p_offset, rows_out);
+			}
 			break;
 		case 8:
-			hipLaunchKernelGGL((k_er_only<8>), grid, block, 0, stream, g, st, er_ring_frames, partials, p_offset, rows_out);
+			if (fade) {
+				hipLaunchKernelGGL((k_er_only<8, true>), grid, block, 0, stream, g, st, er_ring_frames, partials, p_offset, rows_out);
+			} else {
+				hipLaunchKernelGGL((k_er_only<8>), grid, block, 0, stream, g, st, er_ring_frames, partials, p_offset, rows_out);
+			}
 			break;
 		default:
 			return hipErrorInvalidValue;

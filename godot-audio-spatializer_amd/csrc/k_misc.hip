@@ -144,6 +144,9 @@ __global__ void k_zero_slot(gas_dev_state st, uint32_t slot, uint32_t hist_len, 
 		if (st.er_pos) {
 			st.er_pos[slot] = 0;
 		}
+		if (st.er_prev) { // GAS_FLAG_ER_TAP_FADE: no old taps, the next block renders its row alone
+			st.er_prev[slot].rendered = 0;
+		}
 		for (int j = 0; j < GAS_MAX_EFFECTS; j++) { // GAS_FX_DISTORTION / GAS_FX_COMPRESSOR state of every chain position
 			st.dist_h[((size_t)j * 2 + 0) * st.dyn_stride + slot] = 0.0f;
 			st.dist_h[((size_t)j * 2 + 1) * st.dyn_stride + slot] = 0.0f;

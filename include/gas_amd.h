@@ -253,6 +253,18 @@ typedef struct gas_config {
  * without GAS_FLAG_HRTF_INTERPOLATE and with each flag GAS_FLAG_HRTF_INTERPOLATE is refused with.  Contexts without
  * the flag behave exactly as before. */
 #define GAS_FLAG_HRTF_BLEND_FADE 256u
+/* NEW: fade the early-reflection taps between callbacks.  The rule is stated at gas_params::er_delay.  The flag changes
+ * early-reflection stages and nothing else: the chain [EARLY_REFLECTIONS] and every staged chain's early-reflection
+ * stage fade; [EARLY_REFLECTIONS, HRTF] runs as a staged chain (the early-reflection stage writes rows, the HRTF stage
+ * reads them as it does behind any other stage: two launches and a row round trip in place of the fused kernel, whatever
+ * GAS_UNI_ER says), because the fused kernels have no fading form.  A staged chain with an early-reflection stage is
+ * refused by gas_source_alloc (GAS_ERR_UNSUPPORTED_CHAIN) on a context with er_ring_frames == 0; a flagged context
+ * always has a ring, so a flagged [EARLY_REFLECTIONS, HRTF] is accepted wherever the unflagged one is.  Bus, stream,
+ * host and multi-device entries run their early-reflection stages through the same launches.  gas_ctx_create refuses
+ * the flag (GAS_ERR_INVALID_ARGUMENT) with er_ring_frames == 0 and with no other flag.  Cost per context: 68 bytes of
+ * device memory per slot of max_sources (the stored rows and the "has rendered" word).  Contexts without the flag
+ * behave exactly as before. */
+#define GAS_FLAG_ER_TAP_FADE 512u
 
 /* SpatializerParameters (spatializer_parameters.h:39-67) + SpatializerParameters3D
  * (audio_spatializer_3d.h:61-83) as one 128-byte POD, plus the per-block effect
@@ -271,7 +283,22 @@ typedef struct gas_params {
 	float fx_shelf_cutoff_hz; /* GAS_FX_HIGHSHELF cutoff */
 	float er_gain[GAS_ER_TAPS]; /* NEW */
 	uint32_t er_delay[GAS_ER_TAPS]; /* NEW: 1 .. er_ring_frames - frames.  A value above er_ring_frames - frames acts as
-	                                  * er_ring_frames - frames (the oldest frame the ring holds); 0 adds the frame itself */
+	                                  * er_ring_frames - frames (the oldest frame the ring holds); 0 adds the frame itself.
+	                                  * NEW, GAS_FLAG_ER_TAP_FADE (no counterpart in the engine).  A playback's EFFECTIVE TAP ROW
+	                                  * for a callback is 16 words: er_gain[8] as stored, then min(er_delay[k], er_ring_frames -
+	                                  * frames) -- so a raw delay outside the range equals its clamped value.  The context keeps,
+	                                  * per slot, the row the early-reflection stage LAST RENDERED WITH and whether it has rendered
+	                                  * at all (an all-zero row is a legal tap set).  With Y_row[f] = x[f] + sum_k g[k] * x[f -
+	                                  * d[k]] (tap order, f32, the playback's one history):
+	                                  *  - no old row, or old and new row bitwise equal: y = Y_new, bit for bit what a context
+	                                  *    without the flag stores;
+	                                  *  - otherwise y[f] = t * Y_new[f] + (1 - t) * Y_old[f], t = (float)f * (1 / frames): frame 0
+	                                  *    is all old, the next callback starts all new (GAS_FLAG_HRTF_BLEND_FADE's ramp);
+	                                  *  - then the new row becomes the slot's old row.
+	                                  * A playback left out of a callback (not listed, paused) keeps ring, position and old row, and
+	                                  * fades from the taps it last rendered with when it returns.  gas_source_reset, and a free
+	                                  * plus re-alloc of the slot, forget the old row: the first block after them does not fade.
+	                                  * Peaks are those of the faded output. */
 } gas_params;
 
 /* Settings of the GAS_FX_LOWPASS .. GAS_FX_AMPLIFY effects of one playback, by chain position (what a script sets on

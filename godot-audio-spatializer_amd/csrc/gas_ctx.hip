@@ -19,6 +19,7 @@
 #include "gas_fx_mod_check.h"
 #include "gas_fx_stereo_check.h"
 #include "gas_internal.h"
+#include "gas_owned.h"
 #include "gas_qoa.h"
 
 namespace {
@@ -88,9 +89,36 @@ struct FxFamily {
 	unsigned char *h_upload = nullptr, *d_upload = nullptr;
 };
 
+// gas_owned.h's way to the runtime: the only place that allocates or frees device memory, pinned memory or events.
+struct HipMem {
+	using status = hipError_t;
+	using event = hipEvent_t;
+	static constexpr status misuse = hipErrorInvalidValue;
+	static status device_alloc(void **p, size_t bytes) {
+		return hipMalloc(p, bytes);
+	}
+	static status device_free(void *p) {
+		return hipFree(p);
+	}
+	static status pinned_alloc(void **p, size_t bytes) {
+		return hipHostMalloc(p, bytes, hipHostMallocDefault);
+	}
+	static status pinned_free(void *p) {
+		return hipHostFree(p);
+	}
+	static status event_create(event *e, unsigned flags) {
+		return hipEventCreateWithFlags(e, flags);
+	}
+	static status event_destroy(event e) {
+		return hipEventDestroy(e);
+	}
+};
+using Mem = gas_owned<HipMem>;
+
 } // namespace
 
 struct gas_ctx {
+	Mem mem; // owns every device buffer, pinned buffer and event below: they are allocated through it alone
 	gas_config cfg{};
 	hipStream_t stream = nullptr;
 	bool own_stream = false;
@@ -306,6 +334,19 @@ namespace {
 			return GAS_ERR_DEVICE;                                                            \
 		}                                                                                     \
 	} while (0)
+
+// A lazily allocated buffer: each pointer is guarded by its own null test.
+template <class T>
+hipError_t alloc_once(gas_ctx *c, T *&p, size_t count, Mem::Kind kind = Mem::DEVICE) {
+	return p ? hipSuccess : c->mem.alloc(p, count, kind);
+}
+
+// `count` zeroed elements: the fill runs on the context's stream.
+template <class T>
+hipError_t device_zeroed(gas_ctx *c, T *&p, size_t count) {
+	const hipError_t e = c->mem.alloc(p, count);
+	return e != hipSuccess ? e : hipMemsetAsync(p, 0, count * sizeof(T), c->stream);
+}
 
 // The effect families (k_fx_families, below): which one carries an effect kind's settings (-1: none), and the stage of
 // a staged chain that runs the kind.
@@ -646,16 +687,11 @@ int ensure_partials(gas_ctx *c, uint32_t rows) {
 	}
 	if (c->d_partials) {
 		GAS_HIP(c, hipStreamSynchronize(c->stream));
-		GAS_HIP(c, hipFree(c->d_partials));
-		c->d_partials = nullptr;
-		c->partial_rows = 0;
 	}
 	// two generations when the reduce is pipelined: callback t+1 fills one while callback t's is being summed; with
 	// batched launches one per block being filled and one per block being summed
 	c->partial_planes = c->pipelined_mix ? ((c->cfg.flags & GAS_FLAG_BATCHED_LAUNCH) != 0 ? 2u * GAS_HRTF_MULTI_MAX_BLOCKS : 2u) : 1u;
-	const size_t bytes = (size_t)c->partial_planes * rows * c->cfg.channel_count * c->cfg.frames * 2 * sizeof(float);
-	GAS_HIP(c, hipMalloc(&c->d_partials, bytes));
-	c->partial_rows = rows;
+	GAS_HIP(c, c->mem.grow(c->d_partials, c->partial_rows, rows, (size_t)c->partial_planes * c->cfg.channel_count * c->cfg.frames * 2));
 	return GAS_OK;
 }
 
@@ -941,9 +977,7 @@ int run_groups(gas_ctx *c, const RunArgs &a) {
 					const uint32_t uni_wgs = gas_hrtf_uni_partials(g_fd.n);
 					c->last_uni_ordered = false;
 					if (a.use_order && ((c->cfg.flags & GAS_FLAG_XCD_ORDER) != 0 || g_fd.n >= c->xcd_order_auto_min) && uni_wgs % 8 == 0 && c->tab.dirs >= 8) {
-						if (!c->d_order) {
-							GAS_HIP(c, hipMalloc(&c->d_order, (size_t)c->cfg.max_sources * sizeof(uint32_t)));
-						}
+						GAS_HIP(c, alloc_once(c, c->d_order, c->cfg.max_sources));
 						uint32_t *ord = c->d_order + groups[fd_gt].offset;
 						if (!c->order_ok[fd_gt]) {
 							GAS_HIP(c, gas_launch_xcd_order(c->stream, g_fd, c->st.params, fresh, c->tab.dirs, uni_wgs, gas_hrtf_uni_waves(), ord));
@@ -994,9 +1028,7 @@ int run_groups(gas_ctx *c, const RunArgs &a) {
 				if (a.use_order && (c->cfg.flags & GAS_FLAG_DIRECTION_ORDER) != 0 && g_fd.n >= GAS_DIR_ORDER_MIN_SOURCES && (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) == 0 && gas_dir_order_supported(c->tab.dirs)) {
 					const uint32_t seg = g_fd.n < GAS_DIR_ORDER_SEGMENT ? g_fd.n : GAS_DIR_ORDER_SEGMENT;
 					if (seg >= 2 * c->tab.dirs) {
-						if (!c->d_order) {
-							GAS_HIP(c, hipMalloc(&c->d_order, (size_t)c->cfg.max_sources * sizeof(uint32_t)));
-						}
+						GAS_HIP(c, alloc_once(c, c->d_order, c->cfg.max_sources));
 						uint32_t *ord = c->d_order + groups[fd_gt].offset;
 						if (!c->order_ok[fd_gt]) {
 							GAS_HIP(c, gas_launch_dir_order(c->stream, g_fd, c->st.params, fresh, c->tab.dirs, ord));
@@ -1034,12 +1066,10 @@ int run_groups(gas_ctx *c, const RunArgs &a) {
 				}
 				if (need > c->d_chain_frames) {
 					GAS_HIP(c, hipStreamSynchronize(c->stream));
-					(void)hipFree(c->d_chain[0]);
-					(void)hipFree(c->d_chain[1]);
-					c->d_chain[0] = c->d_chain[1] = nullptr;
-					c->d_chain_frames = 0;
-					GAS_HIP(c, hipMalloc(&c->d_chain[0], need * sizeof(gas_audio_frame)));
-					GAS_HIP(c, hipMalloc(&c->d_chain[1], need * sizeof(gas_audio_frame)));
+					size_t cap[2] = { c->d_chain_frames, c->d_chain_frames };
+					c->d_chain_frames = 0; // both rows or neither
+					GAS_HIP(c, c->mem.grow(c->d_chain[0], cap[0], need));
+					GAS_HIP(c, c->mem.grow(c->d_chain[1], cap[1], need));
 					c->d_chain_frames = need;
 				}
 				uint32_t pp = p_off;
@@ -1347,10 +1377,8 @@ int flush_hrtf_blend(gas_ctx *c) {
 		if (m == 0) {
 			return GAS_OK;
 		}
-		if (!c->h_blend_upload) {
-			if (hipHostMalloc(&c->h_blend_upload, sizeof(gas_hrtf_blend) * c->cfg.max_sources, hipHostMallocDefault) != hipSuccess) {
-				return GAS_ERR_OUT_OF_MEMORY;
-			}
+		if (alloc_once(c, c->h_blend_upload, c->cfg.max_sources, Mem::PINNED) != hipSuccess) {
+			return GAS_ERR_OUT_OF_MEMORY;
 		}
 		for (uint32_t i = 0; i < m; i++) {
 			const uint32_t s = c->blend_dirty_list[i];
@@ -1673,13 +1701,12 @@ void fx_return_entries(gas_ctx *c, int f, uint32_t s, uint32_t sig) {
 hipError_t fx_alloc_upload(gas_ctx *c, int f, size_t entries) {
 	FxFamily &p = c->fx[f];
 	const FxFamilyDesc &d = k_fx_families[f];
-	(void)hipFree(p.d_upload);
-	(void)hipHostFree(p.h_upload);
-	p.d_upload = p.h_upload = nullptr;
 	// [<= N settings rows][<= N {slot, entry[4]}][<= every entry once] (mark_dirty / fx_queue_zero)
 	const size_t bytes = (size_t)c->cfg.max_sources * (d.pod_bytes + (1 + GAS_MAX_EFFECTS) * sizeof(uint32_t)) + entries * 2 * sizeof(uint32_t);
-	const hipError_t e = hipMalloc(&p.d_upload, bytes);
-	return e != hipSuccess ? e : hipHostMalloc(&p.h_upload, bytes, hipHostMallocDefault);
+	size_t cap[2] = { 0, 0 }; // no capacity is kept: the buffers are as large as this reservation needs, never larger
+	const hipError_t e = c->mem.grow(p.d_upload, cap[0], bytes);
+	const hipError_t eh = c->mem.grow(p.h_upload, cap[1], bytes, 1, Mem::PINNED);
+	return e != hipSuccess ? e : eh;
 }
 
 // The settings table at the resource defaults (`rows`: the same for the host mirror) and, for a family with pools, the
@@ -1694,35 +1721,30 @@ hipError_t fx_alloc_tables(gas_ctx *c, int f, FxDev &dev, std::vector<unsigned c
 	}
 	hipError_t e = hipSuccess;
 	if (d.entry_floats) {
-		e = hipMalloc(&dev.of, sizeof(int32_t) * GAS_MAX_EFFECTS * N);
+		e = c->mem.alloc(dev.of, GAS_MAX_EFFECTS * N);
 		e = e != hipSuccess ? e : hipMemsetAsync(dev.of, 0xff, sizeof(int32_t) * GAS_MAX_EFFECTS * N, c->stream);
 	}
-	e = e != hipSuccess ? e : hipMalloc(&dev.settings, N * pod);
+	e = e != hipSuccess ? e : c->mem.alloc(dev.settings, N * pod);
 	return e != hipSuccess ? e : hipMemcpy(dev.settings, rows.data(), N * pod, hipMemcpyHostToDevice);
 }
 
-// Frees the pools and, unless the family is resident and `all` is not set (only gas_ctx_destroy sets it), the settings,
-// the table and the staging buffer; params_mu held or no other thread left.
-void fx_release(gas_ctx *c, int f, bool all) {
+// Frees the pools and, unless the family is resident, the settings, the table and the staging buffer; params_mu held.
+void fx_release(gas_ctx *c, int f) {
 	FxFamily &p = c->fx[f];
 	const FxFamilyDesc &d = k_fx_families[f];
 	FxDev dev = d.get(c->st);
 	for (int pl = 0; pl < 2; pl++) {
-		(void)hipFree(dev.pool[pl]);
-		dev.pool[pl] = nullptr;
+		c->mem.drop(dev.pool[pl]);
 		p.cap[pl] = 0;
 		p.free[pl].clear();
 		p.zero_pending[pl].clear();
 	}
 	p.zero_list.clear();
-	if (all || !d.resident) {
-		(void)hipFree(dev.of);
-		(void)hipFree(dev.settings);
-		(void)hipFree(p.d_upload);
-		(void)hipHostFree(p.h_upload);
-		dev.of = nullptr;
-		dev.settings = nullptr;
-		p.d_upload = p.h_upload = nullptr;
+	if (!d.resident) {
+		c->mem.drop(dev.of);
+		c->mem.drop(dev.settings);
+		c->mem.drop(p.d_upload);
+		c->mem.drop(p.h_upload);
 		p.h_of.clear();
 		p.h_settings.clear();
 		p.dirty_flag.clear();
@@ -1791,7 +1813,7 @@ int fx_reserve(gas_ctx *c, int f, uint32_t count0, uint32_t count1) {
 	GAS_HIP(c, hipStreamSynchronize(c->stream));
 	{
 		std::lock_guard<std::mutex> lk(c->params_mu);
-		fx_release(c, f, false);
+		fx_release(c, f);
 	}
 	if (total == 0 && !d.resident) {
 		return GAS_OK;
@@ -1811,9 +1833,7 @@ int fx_reserve(gas_ctx *c, int f, uint32_t count0, uint32_t count1) {
 	}
 	for (int pl = 0; pl < 2; pl++) {
 		if (counts[pl]) {
-			const size_t bytes = d.entry_floats(c, pl) * sizeof(float) * counts[pl];
-			step(hipMalloc(&dev.pool[pl], bytes));
-			step(e == hipSuccess ? hipMemsetAsync(dev.pool[pl], 0, bytes, c->stream) : e);
+			step(e == hipSuccess ? device_zeroed(c, dev.pool[pl], d.entry_floats(c, pl) * counts[pl]) : e);
 		}
 	}
 	if (!d.resident) {
@@ -1826,7 +1846,7 @@ int fx_reserve(gas_ctx *c, int f, uint32_t count0, uint32_t count1) {
 	if (e != hipSuccess) {
 		c->last_err = std::string("gas_ctx_reserve_fx_") + d.name + ": " + hipGetErrorString(e);
 		std::lock_guard<std::mutex> lk(c->params_mu);
-		fx_release(c, f, false);
+		fx_release(c, f);
 		if (d.resident && (!p.h_upload || !p.d_upload)) {
 			(void)fx_alloc_upload(c, f, 0);
 		}
@@ -2156,88 +2176,7 @@ void gas_ctx_destroy(gas_ctx *c) {
 	if (c->stream) {
 		(void)hipStreamSynchronize(c->stream);
 	}
-	for (hipEvent_t e : c->ev) {
-		(void)hipEventDestroy(e);
-	}
-	(void)hipFree(c->st.bq);
-	(void)hipFree(c->st.hrtf_hist);
-	(void)hipFree(c->st.hrtf_prev_gain);
-	(void)hipFree(c->st.hrtf_prev_dir);
-	(void)hipFree(c->st.er_ring);
-	(void)hipFree(c->st.er_pos);
-	(void)hipFree(c->st.params);
-	(void)hipFree(c->tab.spec);
-	(void)hipFree(c->d_tw);
-	(void)hipFree(c->d_upload);
-	(void)hipFree(c->d_upload_slots);
-	(void)hipFree(c->st.hrtf_blend);
-	(void)hipFree(c->st.hrtf_prev_blend);
-	(void)hipFree(c->st.er_prev);
-	(void)hipHostFree(c->h_blend_upload);
-	(void)hipFree(c->st.dist_h);
-	(void)hipFree(c->st.comp_rundb);
-	(void)hipFree(c->st.sidechain);
-	(void)hipHostFree(c->h_sidechain);
-	for (hipEvent_t e : c->sidechain_ev) {
-		if (e) {
-			(void)hipEventDestroy(e);
-		}
-	}
-	for (int f = 0; f < FX_FAMILIES; f++) {
-		fx_release(c, f, true);
-	}
-	(void)hipFree(c->d_slots);
-	(void)hipFree(c->d_rows);
-	(void)hipFree(c->d_slots_rows);
-	(void)hipFree(c->d_src);
-	(void)hipFree(c->d_chain[0]);
-	(void)hipFree(c->d_chain[1]);
-	(void)hipFree(c->d_order);
-	(void)hipFree(c->d_out);
-	(void)hipFree(c->d_peaks);
-	(void)hipFree(c->d_partials);
-	(void)hipFree(c->d_one_slot);
-	(void)hipFree(c->st.was_further);
-	(void)hipFree(c->d_cursors);
-	(void)hipFree(c->d_fade_env);
-	(void)hipFree(c->d_stream_slots);
-	(void)hipFree(c->d_stream_inc);
-	(void)hipHostFree(c->h_stream_inc);
-	(void)hipFree(c->d_feed);
-	(void)hipHostFree(c->h_feed);
-	(void)hipHostFree(c->h_feed_entry);
-	if (c->feed_entry_ev) {
-		(void)hipEventDestroy(c->feed_entry_ev);
-	}
-	if (c->feed_ev) {
-		(void)hipEventDestroy(c->feed_ev);
-	}
-	for (auto &s : c->streams) {
-		(void)hipFree(s.d_pcm);
-	}
-	(void)hipFree(c->d_routes);
-	(void)hipFree(c->d_bus_partials);
-	(void)hipFree(c->d_bus_out);
-	(void)hipHostFree(c->h_routes_pinned);
-	(void)hipFree(c->d_probe_rd);
-	(void)hipFree(c->d_probe_wr);
-	(void)hipFree(c->d_probe_sink);
-	(void)hipFree(c->d_calc_cfgs);
-	(void)hipFree(c->d_calc_listeners);
-	(void)hipFree(c->d_calc_slots);
-	(void)hipFree(c->d_calc_cfgidx);
-	(void)hipFree(c->d_calc_poses);
-	(void)hipFree(c->d_calc_out);
-	(void)hipFree(c->d_calc_areas);
-	(void)hipFree(c->d_calc_lap);
-	(void)hipFree(c->d_calc_reverb);
-	(void)hipFree(c->d_calc_rooms);
-	(void)hipHostFree(c->h_params);
-	(void)hipHostFree(c->h_upload);
-	(void)hipHostFree(c->h_upload_slots);
-	(void)hipHostFree(c->h_idx);
-	(void)hipHostFree(c->h_peak_bits);
-	(void)hipFree(c->d_peak_bits);
+	c->mem.release_all();
 	if (c->own_stream && c->stream) {
 		(void)hipStreamDestroy(c->stream);
 	}
@@ -2290,45 +2229,32 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 		c->own_stream = true;
 		c->pipelined_mix = (cfg->flags & GAS_FLAG_PIPELINED_MIX) != 0;
 		c->st.bq_stride = N * 8;
-		GAS_HIP(c, hipMalloc(&c->st.bq, sizeof(float) * GAS_BQ_FIELDS * c->st.bq_stride));
-		GAS_HIP(c, hipMemsetAsync(c->st.bq, 0, sizeof(float) * GAS_BQ_FIELDS * c->st.bq_stride, c->stream));
-		GAS_HIP(c, hipMalloc(&c->st.hrtf_hist, sizeof(float) * N * c->hist_len));
-		GAS_HIP(c, hipMemsetAsync(c->st.hrtf_hist, 0, sizeof(float) * N * c->hist_len, c->stream));
-		GAS_HIP(c, hipMalloc(&c->st.hrtf_prev_gain, sizeof(float) * N));
-		GAS_HIP(c, hipMemsetAsync(c->st.hrtf_prev_gain, 0, sizeof(float) * N, c->stream));
-		GAS_HIP(c, hipMalloc(&c->st.hrtf_prev_dir, sizeof(uint32_t) * N));
-		GAS_HIP(c, hipMemsetAsync(c->st.hrtf_prev_dir, 0, sizeof(uint32_t) * N, c->stream));
+		GAS_HIP(c, device_zeroed(c, c->st.bq, GAS_BQ_FIELDS * c->st.bq_stride));
+		GAS_HIP(c, device_zeroed(c, c->st.hrtf_hist, N * c->hist_len));
+		GAS_HIP(c, device_zeroed(c, c->st.hrtf_prev_gain, N));
+		GAS_HIP(c, device_zeroed(c, c->st.hrtf_prev_dir, N));
 		if (cfg->er_ring_frames) {
-			GAS_HIP(c, hipMalloc(&c->st.er_ring, sizeof(gas_audio_frame) * N * cfg->er_ring_frames));
-			GAS_HIP(c, hipMemsetAsync(c->st.er_ring, 0, sizeof(gas_audio_frame) * N * cfg->er_ring_frames, c->stream));
-			GAS_HIP(c, hipMalloc(&c->st.er_pos, sizeof(uint32_t) * N));
-			GAS_HIP(c, hipMemsetAsync(c->st.er_pos, 0, sizeof(uint32_t) * N, c->stream));
+			GAS_HIP(c, device_zeroed(c, c->st.er_ring, N * cfg->er_ring_frames));
+			GAS_HIP(c, device_zeroed(c, c->st.er_pos, N));
 		}
-		GAS_HIP(c, hipMalloc(&c->st.params, sizeof(gas_params) * N));
-		GAS_HIP(c, hipMemsetAsync(c->st.params, 0, sizeof(gas_params) * N, c->stream));
+		GAS_HIP(c, device_zeroed(c, c->st.params, N));
 		if ((cfg->flags & GAS_FLAG_HRTF_INTERPOLATE) != 0) { // every slot starts with the all-zero row: no blend
-			GAS_HIP(c, hipMalloc(&c->st.hrtf_blend, sizeof(gas_hrtf_blend) * N));
-			GAS_HIP(c, hipMemsetAsync(c->st.hrtf_blend, 0, sizeof(gas_hrtf_blend) * N, c->stream));
+			GAS_HIP(c, device_zeroed(c, c->st.hrtf_blend, N));
 		}
 		if ((cfg->flags & GAS_FLAG_HRTF_BLEND_FADE) != 0) { // no slot has rendered yet: no old row to fade from
-			GAS_HIP(c, hipMalloc(&c->st.hrtf_prev_blend, sizeof(gas_hrtf_blend) * N));
-			GAS_HIP(c, hipMemsetAsync(c->st.hrtf_prev_blend, 0, sizeof(gas_hrtf_blend) * N, c->stream));
+			GAS_HIP(c, device_zeroed(c, c->st.hrtf_prev_blend, N));
 		}
 		if (er_fade_on(c)) { // no slot has rendered yet: rendered == 0 everywhere
-			GAS_HIP(c, hipMalloc(&c->st.er_prev, sizeof(gas_er_prev) * N));
-			GAS_HIP(c, hipMemsetAsync(c->st.er_prev, 0, sizeof(gas_er_prev) * N, c->stream));
+			GAS_HIP(c, device_zeroed(c, c->st.er_prev, N));
 		}
 		c->st.dyn_stride = (uint32_t)N;
-		GAS_HIP(c, hipMalloc(&c->st.dist_h, sizeof(float) * GAS_MAX_EFFECTS * 2 * N));
-		GAS_HIP(c, hipMemsetAsync(c->st.dist_h, 0, sizeof(float) * GAS_MAX_EFFECTS * 2 * N, c->stream));
-		GAS_HIP(c, hipMalloc(&c->st.comp_rundb, sizeof(float) * GAS_MAX_EFFECTS * N));
-		GAS_HIP(c, hipMemsetAsync(c->st.comp_rundb, 0, sizeof(float) * GAS_MAX_EFFECTS * N, c->stream));
+		GAS_HIP(c, device_zeroed(c, c->st.dist_h, GAS_MAX_EFFECTS * 2 * N));
+		GAS_HIP(c, device_zeroed(c, c->st.comp_rundb, GAS_MAX_EFFECTS * N));
 		// the compressor's sidechain keys start silent
-		GAS_HIP(c, hipMalloc(&c->st.sidechain, sizeof(gas_audio_frame) * GAS_MAX_SIDECHAINS * cfg->frames));
-		GAS_HIP(c, hipMemsetAsync(c->st.sidechain, 0, sizeof(gas_audio_frame) * GAS_MAX_SIDECHAINS * cfg->frames, c->stream));
-		GAS_HIP(c, hipHostMalloc(&c->h_sidechain, sizeof(gas_audio_frame) * GAS_MAX_SIDECHAINS * cfg->frames, hipHostMallocDefault));
+		GAS_HIP(c, device_zeroed(c, c->st.sidechain, GAS_MAX_SIDECHAINS * cfg->frames));
+		GAS_HIP(c, c->mem.alloc(c->h_sidechain, GAS_MAX_SIDECHAINS * cfg->frames, Mem::PINNED));
 		for (hipEvent_t &e : c->sidechain_ev) {
-			GAS_HIP(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+			GAS_HIP(c, c->mem.make_event(e, hipEventDisableTiming));
 		}
 		for (int f = 0; f < FX_FAMILIES; f++) { // the families that need no reservation for their settings: every slot starts from the engine's resource defaults
 			if (k_fx_families[f].resident) {
@@ -2341,20 +2267,19 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 				c->fx[f].dirty_flag.assign(N, 0);
 			}
 		}
-		GAS_HIP(c, hipMalloc(&c->d_upload, sizeof(gas_params) * N));
-		GAS_HIP(c, hipMalloc(&c->d_upload_slots, sizeof(uint32_t) * N));
-		GAS_HIP(c, hipMalloc(&c->d_slots, sizeof(uint32_t) * N));
-		GAS_HIP(c, hipMalloc(&c->d_rows, sizeof(uint32_t) * N));
-		GAS_HIP(c, hipMalloc(&c->d_slots_rows, sizeof(uint32_t) * N));
-		GAS_HIP(c, hipMalloc(&c->d_out, sizeof(gas_audio_frame) * cfg->channel_count * cfg->frames));
-		GAS_HIP(c, hipMalloc(&c->d_peaks, sizeof(float) * 2 * N));
-		GAS_HIP(c, hipMalloc(&c->d_one_slot, sizeof(uint32_t)));
-		GAS_HIP(c, hipMalloc(&c->st.was_further, N));
-		GAS_HIP(c, hipMalloc(&c->d_cursors, sizeof(gas_cursor) * N));
-		GAS_HIP(c, hipMemsetAsync(c->d_cursors, 0, sizeof(gas_cursor) * N, c->stream));
-		GAS_HIP(c, hipMalloc(&c->d_stream_slots, sizeof(uint32_t) * N));
-		GAS_HIP(c, hipMalloc(&c->d_stream_inc, sizeof(uint32_t) * N));
-		GAS_HIP(c, hipHostMalloc(&c->h_stream_inc, sizeof(uint32_t) * N, hipHostMallocDefault));
+		GAS_HIP(c, c->mem.alloc(c->d_upload, N));
+		GAS_HIP(c, c->mem.alloc(c->d_upload_slots, N));
+		GAS_HIP(c, c->mem.alloc(c->d_slots, N));
+		GAS_HIP(c, c->mem.alloc(c->d_rows, N));
+		GAS_HIP(c, c->mem.alloc(c->d_slots_rows, N));
+		GAS_HIP(c, c->mem.alloc(c->d_out, cfg->channel_count * cfg->frames));
+		GAS_HIP(c, c->mem.alloc(c->d_peaks, 2 * N));
+		GAS_HIP(c, c->mem.alloc(c->d_one_slot, 1));
+		GAS_HIP(c, device_zeroed(c, c->st.was_further, N));
+		GAS_HIP(c, device_zeroed(c, c->d_cursors, N));
+		GAS_HIP(c, c->mem.alloc(c->d_stream_slots, N));
+		GAS_HIP(c, c->mem.alloc(c->d_stream_inc, N));
+		GAS_HIP(c, c->mem.alloc(c->h_stream_inc, N, Mem::PINNED));
 		c->feed_word.assign(N, GAS_FEED_NONE);
 		{
 			// end-of-stream ramp the stream-sampling prologue multiplies the last 64 valid frames by: tap k =
@@ -2367,23 +2292,22 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 				decay *= 0.96f;
 				env[k] = decay * ((float)TAIL - (float)k) / (float)TAIL;
 			}
-			GAS_HIP(c, hipMalloc(&c->d_fade_env, sizeof(env)));
+			GAS_HIP(c, c->mem.alloc(c->d_fade_env, TAIL));
 			GAS_HIP(c, hipMemcpy(c->d_fade_env, env, sizeof(env), hipMemcpyHostToDevice));
 		}
-		GAS_HIP(c, hipMemsetAsync(c->st.was_further, 0, N, c->stream));
-		GAS_HIP(c, hipMalloc(&c->d_calc_cfgs, sizeof(gas_spatializer3d_config) * GAS_MAX_SPATIALIZER_CONFIGS));
-		GAS_HIP(c, hipMalloc(&c->d_calc_listeners, sizeof(gas_listener) * GAS_MAX_LISTENERS));
-		GAS_HIP(c, hipMalloc(&c->d_calc_slots, sizeof(uint32_t) * N));
-		GAS_HIP(c, hipMalloc(&c->d_calc_cfgidx, sizeof(uint32_t) * N));
-		GAS_HIP(c, hipHostMalloc(&c->h_params, sizeof(gas_params) * N, hipHostMallocDefault));
-		GAS_HIP(c, hipHostMalloc(&c->h_upload, sizeof(gas_params) * N, hipHostMallocDefault));
-		GAS_HIP(c, hipHostMalloc(&c->h_upload_slots, sizeof(uint32_t) * N, hipHostMallocDefault));
-		GAS_HIP(c, hipHostMalloc(&c->h_idx, sizeof(uint32_t) * 2 * N, hipHostMallocDefault));
-		GAS_HIP(c, hipHostMalloc(&c->h_peak_bits, sizeof(uint32_t) * 2 * ((N + 31) / 32), hipHostMallocDefault));
-		GAS_HIP(c, hipMalloc(&c->d_peak_bits, sizeof(uint32_t) * 2 * ((N + 31) / 32)));
+		GAS_HIP(c, c->mem.alloc(c->d_calc_cfgs, GAS_MAX_SPATIALIZER_CONFIGS));
+		GAS_HIP(c, c->mem.alloc(c->d_calc_listeners, GAS_MAX_LISTENERS));
+		GAS_HIP(c, c->mem.alloc(c->d_calc_slots, N));
+		GAS_HIP(c, c->mem.alloc(c->d_calc_cfgidx, N));
+		GAS_HIP(c, c->mem.alloc(c->h_params, N, Mem::PINNED));
+		GAS_HIP(c, c->mem.alloc(c->h_upload, N, Mem::PINNED));
+		GAS_HIP(c, c->mem.alloc(c->h_upload_slots, N, Mem::PINNED));
+		GAS_HIP(c, c->mem.alloc(c->h_idx, 2 * N, Mem::PINNED));
+		GAS_HIP(c, c->mem.alloc(c->h_peak_bits, 2 * ((N + 31) / 32), Mem::PINNED));
+		GAS_HIP(c, c->mem.alloc(c->d_peak_bits, 2 * ((N + 31) / 32)));
 		float2 h_tw[64 * 16];
 		gas_make_twiddles(h_tw);
-		GAS_HIP(c, hipMalloc(&c->d_tw, sizeof(h_tw)));
+		GAS_HIP(c, c->mem.alloc(c->d_tw, 64 * 16));
 		GAS_HIP(c, hipMemcpyAsync(c->d_tw, h_tw, sizeof(h_tw), hipMemcpyHostToDevice, c->stream));
 		GAS_HIP(c, hipStreamSynchronize(c->stream));
 		return GAS_OK;
@@ -2887,15 +2811,11 @@ int gas_calc_spatialization_areas(gas_ctx *c, const gas_spatializer3d_config *cf
 	const gas_source_pose *d_poses = poses;
 	gas_params *d_out = out_params;
 	if (mem == GAS_MEM_HOST) {
-		if (!c->d_calc_poses) {
-			GAS_HIP(c, hipMalloc(&c->d_calc_poses, sizeof(gas_source_pose) * c->cfg.max_sources));
-		}
+		GAS_HIP(c, alloc_once(c, c->d_calc_poses, c->cfg.max_sources));
 		GAS_HIP(c, hipMemcpyAsync(c->d_calc_poses, poses, sizeof(gas_source_pose) * n, hipMemcpyHostToDevice, c->stream));
 		d_poses = c->d_calc_poses;
 		if (out_params) {
-			if (!c->d_calc_out) {
-				GAS_HIP(c, hipMalloc(&c->d_calc_out, sizeof(gas_params) * c->cfg.max_sources));
-			}
+			GAS_HIP(c, alloc_once(c, c->d_calc_out, c->cfg.max_sources));
 			d_out = c->d_calc_out;
 		}
 	}
@@ -2903,11 +2823,9 @@ int gas_calc_spatialization_areas(gas_ctx *c, const gas_spatializer3d_config *cf
 	const float *d_lap = listener_area_pos;
 	gas_audio_frame *d_reverb = out_reverb;
 	if (mem == GAS_MEM_HOST && (areas || out_reverb)) { // staged like the poses; sized for the worst case once
-		if (!c->d_calc_areas) {
-			GAS_HIP(c, hipMalloc(&c->d_calc_areas, sizeof(gas_area_send) * c->cfg.max_sources));
-			GAS_HIP(c, hipMalloc(&c->d_calc_lap, sizeof(float) * 3 * GAS_MAX_LISTENERS * c->cfg.max_sources));
-			GAS_HIP(c, hipMalloc(&c->d_calc_reverb, sizeof(gas_audio_frame) * 4 * c->cfg.max_sources));
-		}
+		GAS_HIP(c, alloc_once(c, c->d_calc_areas, c->cfg.max_sources));
+		GAS_HIP(c, alloc_once(c, c->d_calc_lap, (size_t)3 * GAS_MAX_LISTENERS * c->cfg.max_sources));
+		GAS_HIP(c, alloc_once(c, c->d_calc_reverb, (size_t)4 * c->cfg.max_sources));
 		if (areas) {
 			GAS_HIP(c, hipMemcpyAsync(c->d_calc_areas, areas, sizeof(gas_area_send) * n, hipMemcpyHostToDevice, c->stream));
 			d_areas = c->d_calc_areas;
@@ -2988,9 +2906,7 @@ int gas_calc_early_reflections(gas_ctx *c, const gas_room *rooms, uint32_t n_roo
 			return rc;
 		}
 	}
-	if (!c->d_calc_rooms) {
-		GAS_HIP(c, hipMalloc(&c->d_calc_rooms, sizeof(gas_room) * GAS_MAX_ROOMS));
-	}
+	GAS_HIP(c, alloc_once(c, c->d_calc_rooms, GAS_MAX_ROOMS));
 	GAS_HIP(c, hipMemcpyAsync(c->d_calc_rooms, rooms, sizeof(gas_room) * n_rooms, hipMemcpyHostToDevice, c->stream));
 	GAS_HIP(c, hipMemcpyAsync(c->d_calc_listeners, listener, sizeof(gas_listener), hipMemcpyHostToDevice, c->stream));
 	if (slots) {
@@ -3002,16 +2918,12 @@ int gas_calc_early_reflections(gas_ctx *c, const gas_room *rooms, uint32_t n_roo
 	const gas_source_pose *d_poses = poses;
 	gas_er_taps *d_taps = out_taps;
 	if (mem == GAS_MEM_HOST) {
-		if (!c->d_calc_poses) {
-			GAS_HIP(c, hipMalloc(&c->d_calc_poses, sizeof(gas_source_pose) * c->cfg.max_sources));
-		}
+		GAS_HIP(c, alloc_once(c, c->d_calc_poses, c->cfg.max_sources));
 		GAS_HIP(c, hipMemcpyAsync(c->d_calc_poses, poses, sizeof(gas_source_pose) * n, hipMemcpyHostToDevice, c->stream));
 		d_poses = c->d_calc_poses;
 		if (out_taps) { // staged in the read-back buffer of gas_calc_spatialization's rows: a gas_er_taps is half a row
 			static_assert(sizeof(gas_er_taps) <= sizeof(gas_params), "gas_er_taps are staged in d_calc_out");
-			if (!c->d_calc_out) {
-				GAS_HIP(c, hipMalloc(&c->d_calc_out, sizeof(gas_params) * c->cfg.max_sources));
-			}
+			GAS_HIP(c, alloc_once(c, c->d_calc_out, c->cfg.max_sources));
 			d_taps = reinterpret_cast<gas_er_taps *>(c->d_calc_out);
 		}
 	}
@@ -3070,10 +2982,10 @@ int gas_stream_create(gas_ctx *c, const void *pcm, int format, uint32_t channels
 		pcm = qoa.data();
 	}
 	gas_ctx::StreamInfo si;
-	GAS_HIP(c, hipMalloc(&si.d_pcm, bytes));
+	GAS_HIP(c, c->mem.alloc(si.d_pcm, bytes));
 	hipError_t e = hipMemcpy(si.d_pcm, pcm, bytes, hipMemcpyHostToDevice);
 	if (e != hipSuccess) {
-		(void)hipFree(si.d_pcm);
+		c->mem.drop(si.d_pcm);
 		c->last_err = hipGetErrorString(e);
 		return GAS_ERR_DEVICE;
 	}
@@ -3106,7 +3018,7 @@ int gas_stream_destroy(gas_ctx *c, uint32_t stream) {
 			return GAS_ERR_INVALID_ARGUMENT; // still bound to a playback
 		}
 	}
-	(void)hipFree(c->streams[stream].d_pcm);
+	c->mem.drop(c->streams[stream].d_pcm);
 	c->streams[stream] = gas_ctx::StreamInfo{};
 	return GAS_OK;
 }
@@ -3293,15 +3205,13 @@ inline size_t feed_header_bytes(const gas_ctx *c) {
 int feed_place(gas_ctx *c, size_t bytes, size_t &at, bool &switched) {
 	const size_t hdr = feed_header_bytes(c), half = (size_t)c->cfg.max_sources * c->cfg.frames * sizeof(gas_audio_frame);
 	if (!c->d_feed) {
-		if (!c->h_feed_entry && hipHostMalloc(&c->h_feed_entry, (size_t)c->cfg.max_sources * sizeof(uint32_t), hipHostMallocDefault) != hipSuccess) {
-			c->h_feed_entry = nullptr;
+		if (alloc_once(c, c->h_feed_entry, c->cfg.max_sources, Mem::PINNED) != hipSuccess) {
 			return GAS_ERR_OUT_OF_MEMORY;
 		}
 		if (!c->feed_entry_ev) {
-			GAS_HIP(c, hipEventCreateWithFlags(&c->feed_entry_ev, hipEventDisableTiming));
+			GAS_HIP(c, c->mem.make_event(c->feed_entry_ev, hipEventDisableTiming));
 		}
-		if (hipMalloc(&c->d_feed, hdr + 2 * half) != hipSuccess) {
-			c->d_feed = nullptr;
+		if (c->mem.alloc(c->d_feed, hdr + 2 * half) != hipSuccess) {
 			return GAS_ERR_OUT_OF_MEMORY;
 		}
 		c->feed_used = 0;
@@ -3342,15 +3252,8 @@ hipError_t ensure_src(gas_ctx *c, size_t frames) {
 	}
 	if (c->d_src) {
 		(void)hipStreamSynchronize(c->stream);
-		(void)hipFree(c->d_src);
-		c->d_src = nullptr;
-		c->d_src_frames = 0;
 	}
-	const hipError_t e = hipMalloc(&c->d_src, (frames ? frames : 1) * sizeof(gas_audio_frame));
-	if (e == hipSuccess) {
-		c->d_src_frames = frames;
-	}
-	return e;
+	return c->mem.grow(c->d_src, c->d_src_frames, frames ? frames : 1);
 }
 
 // Queues `out` and, when the caller wants them, the peaks of n sources back to the host, and waits for both.
@@ -3637,7 +3540,7 @@ static int process_block_streams_common(gas_ctx *c, const uint32_t *slots, uint3
 	gas_audio_frame *d_out = out;
 	float *d_pk = peaks;
 	if (mem == GAS_MEM_HOST) {
-		if (buses && !c->d_bus_out && hipMalloc(&c->d_bus_out, (size_t)GAS_MAX_BUSES * C * F * sizeof(gas_audio_frame)) != hipSuccess) {
+		if (buses && alloc_once(c, c->d_bus_out, (size_t)GAS_MAX_BUSES * C * F) != hipSuccess) {
 			return fail(GAS_ERR_OUT_OF_MEMORY);
 		}
 		d_out = buses ? c->d_bus_out : c->d_out;
@@ -3728,15 +3631,11 @@ int gas_source_feed_rows(gas_ctx *c, const uint32_t *slots, const void *rows, in
 		if (c->feed_ev) {
 			GAS_HIP(c, hipEventSynchronize(c->feed_ev));
 		} else {
-			GAS_HIP(c, hipEventCreateWithFlags(&c->feed_ev, hipEventDisableTiming));
+			GAS_HIP(c, c->mem.make_event(c->feed_ev, hipEventDisableTiming));
 		}
-		(void)hipHostFree(c->h_feed);
-		c->h_feed = nullptr;
-		c->h_feed_cap = 0;
-		if (hipHostMalloc(&c->h_feed, bytes, hipHostMallocDefault) != hipSuccess) {
+		if (c->mem.grow(c->h_feed, c->h_feed_cap, bytes, 1, Mem::PINNED) != hipSuccess) {
 			return GAS_ERR_OUT_OF_MEMORY;
 		}
-		c->h_feed_cap = bytes;
 	}
 	size_t at = 0;
 	bool switched = false;
@@ -3791,27 +3690,19 @@ int gas_hrtf_load(gas_ctx *c, const float *hrir, uint32_t dirs, uint32_t taps) {
 	}
 	GAS_HIP(c, hipSetDevice(c->cfg.device));
 	GAS_HIP(c, hipStreamSynchronize(c->stream));
-	if (c->tab.spec) {
-		GAS_HIP(c, hipFree(c->tab.spec));
-		c->tab.spec = nullptr;
-		c->tab.dirs = 0;
-	}
+	c->mem.drop(c->tab.spec);
+	c->tab.dirs = 0;
+	Mem tmp; // frees d_hrir on every way out
 	float *d_hrir = nullptr;
-	const size_t bytes = (size_t)dirs * 2 * taps * sizeof(float);
-	GAS_HIP(c, hipMalloc(&d_hrir, bytes));
-	int rc = [&]() -> int {
-		GAS_HIP(c, hipMemcpyAsync(d_hrir, hrir, bytes, hipMemcpyHostToDevice, c->stream));
-		GAS_HIP(c, hipMalloc(&c->tab.spec, (size_t)dirs * 4 * 64 * sizeof(float4))); // bins 0..255, Hermitian half
-		GAS_HIP(c, gas_launch_hrtf_table(c->stream, d_hrir, dirs, taps, c->d_tw, c->tab.spec));
-		GAS_HIP(c, hipStreamSynchronize(c->stream));
-		return GAS_OK;
-	}();
-	(void)hipFree(d_hrir);
-	if (rc == GAS_OK) {
-		c->tab.dirs = dirs;
-		c->params_gen++;
-	}
-	return rc;
+	const size_t floats = (size_t)dirs * 2 * taps;
+	GAS_HIP(c, tmp.alloc(d_hrir, floats));
+	GAS_HIP(c, hipMemcpyAsync(d_hrir, hrir, floats * sizeof(float), hipMemcpyHostToDevice, c->stream));
+	GAS_HIP(c, c->mem.alloc(c->tab.spec, (size_t)dirs * 4 * 64)); // bins 0..255, Hermitian half
+	GAS_HIP(c, gas_launch_hrtf_table(c->stream, d_hrir, dirs, taps, c->d_tw, c->tab.spec));
+	GAS_HIP(c, hipStreamSynchronize(c->stream));
+	c->tab.dirs = dirs;
+	c->params_gen++;
+	return GAS_OK;
 }
 
 int gas_hrtf_load_positions(gas_ctx *c, const float *positions, const float *hrir, uint32_t m, uint32_t taps, uint32_t az_steps, uint32_t el_steps, int interpolation, float *out_hrir) {
@@ -3820,24 +3711,18 @@ int gas_hrtf_load_positions(gas_ctx *c, const float *positions, const float *hri
 	}
 	GAS_HIP(c, hipSetDevice(c->cfg.device));
 	const uint32_t dirs = az_steps * el_steps;
-	float *d_pos = nullptr, *d_in = nullptr, *d_grid = nullptr;
 	std::vector<float> grid((size_t)dirs * 2 * GAS_HRTF_TAPS);
-	int rc = [&]() -> int {
-		GAS_HIP(c, hipMalloc(&d_pos, (size_t)m * 2 * sizeof(float)));
-		GAS_HIP(c, hipMalloc(&d_in, (size_t)m * 2 * taps * sizeof(float)));
-		GAS_HIP(c, hipMalloc(&d_grid, grid.size() * sizeof(float)));
+	{
+		Mem tmp; // frees the three on every way out of the block
+		float *d_pos = nullptr, *d_in = nullptr, *d_grid = nullptr;
+		GAS_HIP(c, tmp.alloc(d_pos, (size_t)m * 2));
+		GAS_HIP(c, tmp.alloc(d_in, (size_t)m * 2 * taps));
+		GAS_HIP(c, tmp.alloc(d_grid, grid.size()));
 		GAS_HIP(c, hipMemcpyAsync(d_pos, positions, (size_t)m * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
 		GAS_HIP(c, hipMemcpyAsync(d_in, hrir, (size_t)m * 2 * taps * sizeof(float), hipMemcpyHostToDevice, c->stream));
 		GAS_HIP(c, gas_launch_hrtf_regrid(c->stream, d_pos, d_in, m, taps, az_steps, el_steps, interpolation, d_grid));
 		GAS_HIP(c, hipMemcpyAsync(grid.data(), d_grid, grid.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
 		GAS_HIP(c, hipStreamSynchronize(c->stream));
-		return GAS_OK;
-	}();
-	(void)hipFree(d_pos);
-	(void)hipFree(d_in);
-	(void)hipFree(d_grid);
-	if (rc != GAS_OK) {
-		return rc;
 	}
 	if (out_hrir) {
 		std::memcpy(out_hrir, grid.data(), grid.size() * sizeof(float));
@@ -4100,10 +3985,8 @@ static int process_block_buses(gas_ctx *c, const RowSource &src, const uint32_t 
 		{
 			std::lock_guard<std::mutex> lk(c->params_mu);
 			if (c->routes_dirty || !c->d_routes) {
-				if (!c->h_routes_pinned) {
-					GAS_HIP(c, hipHostMalloc(&c->h_routes_pinned, sizeof(gas_bus_route) * c->cfg.max_sources, hipHostMallocDefault));
-					GAS_HIP(c, hipMalloc(&c->d_routes, sizeof(gas_bus_route) * c->cfg.max_sources));
-				}
+				GAS_HIP(c, alloc_once(c, c->h_routes_pinned, c->cfg.max_sources, Mem::PINNED));
+				GAS_HIP(c, alloc_once(c, c->d_routes, c->cfg.max_sources));
 				std::memcpy(c->h_routes_pinned, c->h_routes.data(), sizeof(gas_bus_route) * c->cfg.max_sources);
 				c->routes_dirty = false;
 				upload = true;
@@ -4117,11 +4000,7 @@ static int process_block_buses(gas_ctx *c, const RowSource &src, const uint32_t 
 		const size_t need = (size_t)(fused_hrtf ? 2 * ((n_buses + 1) / 2) : n_buses) * C * (P ? P : 1) * F * 2; // the fused [HRTF] form writes two planes per launch
 		if (need > c->bus_partial_floats) {
 			GAS_HIP(c, hipStreamSynchronize(c->stream));
-			(void)hipFree(c->d_bus_partials);
-			c->d_bus_partials = nullptr;
-			c->bus_partial_floats = 0;
-			GAS_HIP(c, hipMalloc(&c->d_bus_partials, need * sizeof(float)));
-			c->bus_partial_floats = need;
+			GAS_HIP(c, c->mem.grow(c->d_bus_partials, c->bus_partial_floats, need));
 		}
 		RowSource d_src = src;
 		gas_audio_frame *d_out = out;
@@ -4132,9 +4011,7 @@ static int process_block_buses(gas_ctx *c, const RowSource &src, const uint32_t 
 			if (n > 0) {
 				GAS_HIP(c, hipMemcpyAsync(c->d_src, src.rows, rows * sizeof(gas_audio_frame), hipMemcpyHostToDevice, c->stream));
 			}
-			if (!c->d_bus_out) {
-				GAS_HIP(c, hipMalloc(&c->d_bus_out, (size_t)GAS_MAX_BUSES * C * F * sizeof(gas_audio_frame)));
-			}
+			GAS_HIP(c, alloc_once(c, c->d_bus_out, (size_t)GAS_MAX_BUSES * C * F));
 			d_src.rows = c->d_src;
 			d_out = c->d_bus_out;
 			d_peaks = c->d_peaks;
@@ -4301,10 +4178,11 @@ int gas_profile_enable(gas_ctx *c, int on) {
 	}
 	GAS_HIP(c, hipSetDevice(c->cfg.device));
 	if (on && c->ev.empty()) {
-		c->ev.resize(PROFILE_EVENTS);
-		for (hipEvent_t &e : c->ev) {
-			GAS_HIP(c, hipEventCreate(&e));
+		std::vector<hipEvent_t> ev(PROFILE_EVENTS, nullptr);
+		for (hipEvent_t &e : ev) {
+			GAS_HIP(c, c->mem.make_event(e, hipEventDefault)); // a failure leaves c->ev empty and what exists to the owner
 		}
+		c->ev = std::move(ev);
 	}
 	if (on) {
 		// An event pair around a launch reads the launch's span on the GPU timeline plus the cost of the second
@@ -4363,64 +4241,48 @@ int gas_bandwidth_probe(gas_ctx *c, uint64_t read_bytes, uint64_t write_bytes, u
 	// the read arena is swept in rotation so that successive launches cannot be served by the 256 MiB Infinity Cache
 	const size_t want_rd = read_bytes ? ((size_t)(320u << 20) / read_bytes + 2) * read_bytes : 16;
 	if (want_rd > c->probe_rd_bytes) {
-		(void)hipFree(c->d_probe_rd);
-		c->d_probe_rd = nullptr;
-		c->probe_rd_bytes = 0;
-		GAS_HIP(c, hipMalloc(&c->d_probe_rd, want_rd));
+		GAS_HIP(c, c->mem.grow(c->d_probe_rd, c->probe_rd_bytes, want_rd));
 		GAS_HIP(c, hipMemsetAsync(c->d_probe_rd, 0, want_rd, c->stream));
-		c->probe_rd_bytes = want_rd;
 	}
 	const size_t want_wr = write_bytes ? write_bytes : 16;
-	if (want_wr > c->probe_wr_bytes) {
-		(void)hipFree(c->d_probe_wr);
-		c->d_probe_wr = nullptr;
-		c->probe_wr_bytes = 0;
-		GAS_HIP(c, hipMalloc(&c->d_probe_wr, want_wr));
-		c->probe_wr_bytes = want_wr;
-	}
-	if (!c->d_probe_sink) {
-		GAS_HIP(c, hipMalloc(&c->d_probe_sink, 256 * sizeof(float)));
-	}
+	GAS_HIP(c, c->mem.grow(c->d_probe_wr, c->probe_wr_bytes, want_wr));
+	GAS_HIP(c, alloc_once(c, c->d_probe_sink, 256));
+	Mem tmp; // destroys the two events on every way out
 	hipEvent_t e0 = nullptr, e1 = nullptr;
-	GAS_HIP(c, hipEventCreate(&e0));
-	GAS_HIP(c, hipEventCreate(&e1));
-	int rc = [&]() -> int {
-		// marker calibration as in gas_profile_enable: an empty bracket, minimum of 16 tries
-		double marker = 1e9;
-		for (int i = 0; i < 16; i++) {
-			GAS_HIP(c, hipEventRecord(e0, c->stream));
-			GAS_HIP(c, hipEventRecord(e1, c->stream));
-			GAS_HIP(c, hipEventSynchronize(e1));
-			float ms = 0.0f;
-			GAS_HIP(c, hipEventElapsedTime(&ms, e0, e1));
-			marker = ms < marker ? ms : marker;
-		}
-		const size_t slices = read_bytes ? c->probe_rd_bytes / read_bytes : 1;
-		size_t k = 0;
-		auto launch = [&]() {
-			const char *rd = static_cast<const char *>(c->d_probe_rd) + (k++ % slices) * read_bytes;
-			return gas_launch_stream_probe(c->stream, rd, read_bytes, c->d_probe_wr, write_bytes, workgroups, unroll, c->d_probe_sink);
-		};
-		for (int i = 0; i < 8; i++) { // warm-up, back to back
-			GAS_HIP(c, launch());
-		}
-		double sum_ms = 0.0;
-		for (uint32_t i = 0; i < iters; i++) {
-			GAS_HIP(c, launch()); // an unbracketed launch in front keeps the GPU busy, as the bench's callbacks do
-			GAS_HIP(c, hipEventRecord(e0, c->stream));
-			GAS_HIP(c, launch());
-			GAS_HIP(c, hipEventRecord(e1, c->stream));
-			GAS_HIP(c, hipEventSynchronize(e1));
-			float ms = 0.0f;
-			GAS_HIP(c, hipEventElapsedTime(&ms, e0, e1));
-			sum_ms += ms > marker ? ms - marker : 0.0;
-		}
-		*out_us = sum_ms / iters * 1e3;
-		return GAS_OK;
-	}();
-	(void)hipEventDestroy(e0);
-	(void)hipEventDestroy(e1);
-	return rc;
+	GAS_HIP(c, tmp.make_event(e0, hipEventDefault));
+	GAS_HIP(c, tmp.make_event(e1, hipEventDefault));
+	// marker calibration as in gas_profile_enable: an empty bracket, minimum of 16 tries
+	double marker = 1e9;
+	for (int i = 0; i < 16; i++) {
+		GAS_HIP(c, hipEventRecord(e0, c->stream));
+		GAS_HIP(c, hipEventRecord(e1, c->stream));
+		GAS_HIP(c, hipEventSynchronize(e1));
+		float ms = 0.0f;
+		GAS_HIP(c, hipEventElapsedTime(&ms, e0, e1));
+		marker = ms < marker ? ms : marker;
+	}
+	const size_t slices = read_bytes ? c->probe_rd_bytes / read_bytes : 1;
+	size_t k = 0;
+	auto launch = [&]() {
+		const char *rd = static_cast<const char *>(c->d_probe_rd) + (k++ % slices) * read_bytes;
+		return gas_launch_stream_probe(c->stream, rd, read_bytes, c->d_probe_wr, write_bytes, workgroups, unroll, c->d_probe_sink);
+	};
+	for (int i = 0; i < 8; i++) { // warm-up, back to back
+		GAS_HIP(c, launch());
+	}
+	double sum_ms = 0.0;
+	for (uint32_t i = 0; i < iters; i++) {
+		GAS_HIP(c, launch()); // an unbracketed launch in front keeps the GPU busy, as the bench's callbacks do
+		GAS_HIP(c, hipEventRecord(e0, c->stream));
+		GAS_HIP(c, launch());
+		GAS_HIP(c, hipEventRecord(e1, c->stream));
+		GAS_HIP(c, hipEventSynchronize(e1));
+		float ms = 0.0f;
+		GAS_HIP(c, hipEventElapsedTime(&ms, e0, e1));
+		sum_ms += ms > marker ? ms - marker : 0.0;
+	}
+	*out_us = sum_ms / iters * 1e3;
+	return GAS_OK;
 }
 
 int gas_profile_read(gas_ctx *c, gas_profile *out, int reset) {

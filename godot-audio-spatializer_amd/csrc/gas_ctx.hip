@@ -68,6 +68,28 @@ struct ChainRange {
 	bool peak_all = true, peak_any = true; // which of its sources report their exact peak (GAS_FLAG_PEAKS_DRAINING_ONLY; read by a last stage that is k_hrtf_uni)
 };
 
+// Which slots the current list has named so far, without a pass over every slot between two lists.
+struct SlotStamp {
+	std::vector<uint32_t> at; // [max_sources]: the list that named the slot last
+	uint32_t gen = 0;
+	void next() { // a new list begins
+		if (++gen == 0) {
+			std::fill(at.begin(), at.end(), 0u);
+			gen = 1;
+		}
+	}
+	bool has(uint32_t slot) const {
+		return at[slot] == gen;
+	}
+	bool seen(uint32_t slot) { // true: named before in this list; marks it otherwise
+		if (has(slot)) {
+			return true;
+		}
+		at[slot] = gen;
+		return false;
+	}
+};
+
 constexpr uint32_t PROFILE_EVENTS = 4096;
 
 // The effect families, in the order their uploads are flushed; k_fx_families describes them.  The
@@ -127,12 +149,11 @@ struct gas_ctx {
 	bool pipelined_mix = false;
 	uint32_t pipe_tick = 0;
 	struct PendingMix {
-		bool valid = false;
 		int parity = 0; // plane of d_partials holding the callback's partial mixes
 		uint32_t p_total = 0;
 		gas_audio_frame *out = nullptr;
-	} pending_mix; // what a single launch carries / the first sum left by a batched launch
-	std::vector<PendingMix> pending_more; // the other sums a batched launch left (one per block)
+	};
+	std::vector<PendingMix> pending; // the sums not launched yet, oldest first: one after a single launch, one per block after a batched one
 	// GAS_FLAG_BATCHED_LAUNCH: plain-[HRTF] device-memory callbacks wait here until batch_depth of them run as ONE
 	// k_hrtf_multi launch.  Anything that could change what the waiting callbacks must see runs them first.
 	struct Deferred {
@@ -159,10 +180,8 @@ struct gas_ctx {
 	std::vector<uint32_t> pending_free; // audio thread: frees taking effect at the next block boundary
 	std::mutex alloc_mu; // gas_source_alloc / gas_source_free may come from any thread: guards free_list and free_inbox
 	std::vector<uint32_t> free_inbox; // frees requested since the audio thread last looked (adopt_frees)
-	std::vector<uint32_t> stamp; // duplicate detection per block
-	uint32_t stamp_gen = 0;
-	std::vector<uint32_t> calc_stamp; // the same for gas_calc_spatialization's slot list (physics thread, under calc_mu)
-	uint32_t calc_stamp_gen = 0;
+	SlotStamp stamp; // duplicate detection per block
+	SlotStamp calc_stamp; // the same for gas_calc_spatialization's slot list (physics thread, under calc_mu)
 
 	std::mutex params_mu;
 	gas_params *h_params = nullptr; // pinned [max_sources], latest published value
@@ -334,6 +353,20 @@ namespace {
 			return GAS_ERR_DEVICE;                                                            \
 		}                                                                                     \
 	} while (0)
+
+// Returns the status of `expr` to the caller unless it is GAS_OK.
+#define GAS_TRY(expr)               \
+	do {                            \
+		const int _rc = (expr);     \
+		if (_rc != GAS_OK) {        \
+			return _rc;             \
+		}                           \
+	} while (0)
+
+// The slot names a playback of this context.
+inline bool live(const gas_ctx *c, uint32_t slot) {
+	return slot < c->cfg.max_sources && c->slots[slot].used;
+}
 
 // A lazily allocated buffer: each pointer is guarded by its own null test.
 template <class T>
@@ -695,39 +728,47 @@ int ensure_partials(gas_ctx *c, uint32_t rows) {
 	return GAS_OK;
 }
 
-// Launches the pending callback's k_mix_reduce on the context's stream (GAS_FLAG_PIPELINED_MIX).
+// The pending sums (GAS_FLAG_PIPELINED_MIX), c->pending: where one's partial mixes lie, what a launch that carries it
+// is handed, and what the carrying adds to that launch's bytes.
+inline float *partials_plane(const gas_ctx *c, int parity) {
+	return c->d_partials + (size_t)parity * c->partial_rows * c->cfg.channel_count * c->cfg.frames * 2;
+}
+
+gas_deferred_reduce carried_job(const gas_ctx *c, const gas_ctx::PendingMix &pm) {
+	gas_deferred_reduce job;
+	job.partials = partials_plane(c, pm.parity);
+	job.p_count = pm.p_total;
+	job.elems = c->cfg.frames * 2;
+	job.out = reinterpret_cast<float *>(pm.out);
+	return job;
+}
+
+inline uint64_t carried_bytes(const gas_deferred_reduce &job) {
+	return job.partials ? ((uint64_t)job.p_count + 1) * job.elems * sizeof(float) : 0;
+}
+
+// Launches the pending callback's k_mix_reduce on the context's stream.
 int reduce_now(gas_ctx *c, const gas_ctx::PendingMix &pm) {
-	const uint32_t F = c->cfg.frames;
-	const float *parts = c->d_partials + (size_t)pm.parity * c->partial_rows * c->cfg.channel_count * F * 2;
-	GAS_HIP(c, gas_launch_mix_reduce(c->stream, parts, pm.p_total, c->partial_rows, 1, F, pm.out));
+	GAS_HIP(c, gas_launch_mix_reduce(c->stream, partials_plane(c, pm.parity), pm.p_total, c->partial_rows, 1, c->cfg.frames, pm.out));
 	return GAS_OK;
 }
 
 int join_outputs(gas_ctx *c) {
-	std::vector<gas_ctx::PendingMix> all;
-	if (c->pending_mix.valid) {
-		all.push_back(c->pending_mix);
-		c->pending_mix.valid = false;
-	}
-	for (const gas_ctx::PendingMix &pm : c->pending_more) {
-		all.push_back(pm);
-	}
-	c->pending_more.clear();
+	const std::vector<gas_ctx::PendingMix> all = std::move(c->pending);
+	c->pending.clear();
 	if (all.size() == 1) {
 		return reduce_now(c, all[0]);
 	}
 	// the sums a batched launch left: one launch for all of them (eight k_mix_reduce launches cost 38 us)
-	const uint32_t F = c->cfg.frames;
-	const size_t plane_elems = (size_t)c->partial_rows * c->cfg.channel_count * F * 2;
 	for (size_t i = 0; i < all.size(); i += GAS_HRTF_MULTI_MAX_BLOCKS) {
 		gas_reduce_jobs jobs;
 		for (size_t j = i; j < all.size() && j < i + GAS_HRTF_MULTI_MAX_BLOCKS; j++) {
-			jobs.partials[jobs.count] = c->d_partials + (size_t)all[j].parity * plane_elems;
+			jobs.partials[jobs.count] = partials_plane(c, all[j].parity);
 			jobs.p_count[jobs.count] = all[j].p_total;
 			jobs.out[jobs.count] = reinterpret_cast<float *>(all[j].out);
 			jobs.count++;
 		}
-		GAS_HIP(c, gas_launch_mix_reduce_jobs(c->stream, jobs, F));
+		GAS_HIP(c, gas_launch_mix_reduce_jobs(c->stream, jobs, c->cfg.frames));
 	}
 	return GAS_OK;
 }
@@ -735,8 +776,8 @@ int join_outputs(gas_ctx *c) {
 // A plane of d_partials that no pending sum still reads and that is not in `taken`.
 int free_plane(const gas_ctx *c, const std::vector<int> &taken) {
 	for (int p = 0; p < (int)c->partial_planes; p++) {
-		bool busy = c->pending_mix.valid && c->pending_mix.parity == p;
-		for (const gas_ctx::PendingMix &pm : c->pending_more) {
+		bool busy = false;
+		for (const gas_ctx::PendingMix &pm : c->pending) {
 			busy = busy || pm.parity == p;
 		}
 		for (int t : taken) {
@@ -817,22 +858,256 @@ gas_hrtf_launch_common hrtf_common(const gas_ctx *c) {
 	return k;
 }
 
+// Which entries of the plain-[HRTF] group of the context's own list report their exact peak (build_groups): the bit
+// list, unless all of them or none do.
+inline const uint32_t *plain_peak_bits(const gas_ctx *c) {
+	return c->uni_peak_any && !c->uni_peak_all ? c->d_peak_bits : nullptr;
+}
+
+// k_hrtf_uni over the plain-[HRTF] group `g` of the context's own list.
+gas_hrtf_uni_launch plain_uni_launch(const gas_ctx *c, const gas_group_args &g, const RowSource &src, float *partials, uint32_t p_offset) {
+	gas_hrtf_uni_launch lu{ hrtf_common(c) };
+	lu.g = g;
+	lu.peak_bits = plain_peak_bits(c);
+	lu.peak_all = c->uni_peak_all;
+	lu.partials = partials;
+	lu.p_offset = p_offset;
+	lu.cursors = src.cursors;
+	lu.feed = src.feed;
+	return lu;
+}
+
+// What run_groups' loop over the groups shares with the launch families below.
+struct GroupRun {
+	float *parts = nullptr; // this callback's plane of d_partials
+	uint32_t p_off = 0; // its rows taken by the groups in front of the current one
+	uint32_t p_total = 0; // ... and by all groups
+	bool uni_hrtf = false, staged_uni = false, uni_er = false; // the launch forms plan_partials counted the rows of
+	gas_deferred_reduce job; // the previous callback's sum (GAS_FLAG_PIPELINED_MIX), until a launch takes it along
+	int carrier_gt = -1; // the frequency-domain group whose launch does
+	// The job if fd_gt's launch is the carrier (`bytes`: what summing it adds to the launch's traffic), else none.
+	gas_deferred_reduce take(int fd_gt, uint64_t &bytes) {
+		if (fd_gt != carrier_gt) {
+			return gas_deferred_reduce();
+		}
+		const gas_deferred_reduce taken = job;
+		job = gas_deferred_reduce();
+		bytes = carried_bytes(taken);
+		return taken;
+	}
+};
+
+// G_FX_HRTF / G_FX_ER_HRTF and the exact-peak group behind each: one launch covers both (`ga`: group gt's entries, the
+// exact-peak group's when the frequency-domain one is empty).  k_hrtf_uni where it applies, else k_hrtf_ols.
+int launch_hrtf_groups(gas_ctx *c, const RunArgs &a, int gt, const gas_group_args &ga, GroupRun &run, uint64_t &carried) {
+	const Group *const groups = a.groups;
+	const uint32_t *const d_slots = a.slots, *const d_rows = a.rows;
+	const bool is_pk = gt == G_FX_HRTF_PK || gt == G_FX_ER_HRTF_PK;
+	const int fd_gt = is_pk ? gt - 1 : gt;
+	const Group &gr = groups[gt], &gp = groups[fd_gt + 1];
+	gas_group_args g_fd = ga, g_pk = ga;
+	if (is_pk) {
+		g_fd.n = 0;
+	} else {
+		g_pk.rows = d_rows ? d_rows + gp.offset : nullptr;
+		g_pk.slots = d_slots + gp.offset;
+		g_pk.n = gp.count;
+	}
+	// contiguous slot ranges need no slot list on the device (one dependent load less in the prologue)
+	if (g_fd.n && groups[fd_gt].contiguous) {
+		g_fd.slots = nullptr;
+		g_fd.slot_base = groups[fd_gt].slot_base;
+	}
+	if (g_pk.n && groups[fd_gt + 1].contiguous) {
+		g_pk.slots = nullptr;
+		g_pk.slot_base = groups[fd_gt + 1].slot_base;
+	}
+	const gas_params *fresh = a.fresh; // both HRTF forms read device-published rows themselves and write them through
+	if (gt == G_FX_HRTF && gp.count == 0 && run.uni_hrtf) {
+		// the whole plain-[HRTF] group in one uniform launch (k_hrtf_uni.hip)
+		// XCD-affine processing order (k_xcd_order): rebuilt when the list or any parameter changed, else reused
+		const uint32_t uni_wgs = gas_hrtf_uni_partials(g_fd.n);
+		c->last_uni_ordered = false;
+		if (a.use_order && ((c->cfg.flags & GAS_FLAG_XCD_ORDER) != 0 || g_fd.n >= c->xcd_order_auto_min) && uni_wgs % 8 == 0 && c->tab.dirs >= 8) {
+			GAS_HIP(c, alloc_once(c, c->d_order, c->cfg.max_sources));
+			uint32_t *ord = c->d_order + groups[fd_gt].offset;
+			if (!c->order_ok[fd_gt]) {
+				GAS_HIP(c, gas_launch_xcd_order(c->stream, g_fd, c->st.params, fresh, c->tab.dirs, uni_wgs, gas_hrtf_uni_waves(), ord));
+				c->order_ok[fd_gt] = true;
+			}
+			g_fd.order = ord;
+			c->last_uni_ordered = true;
+		}
+		gas_hrtf_uni_launch lu = plain_uni_launch(c, g_fd, a.src, run.parts, run.p_off);
+		lu.fresh = fresh;
+		lu.job = run.take(fd_gt, carried); // (a pending sum makes this group the carrier: it is the first of the two)
+		GAS_HIP(c, gas_launch_hrtf_uni(lu));
+		return GAS_OK;
+	}
+	if (fd_gt == G_FX_ER_HRTF && run.uni_er) {
+		gas_group_args gu = ga; // this group's entries, then (frequency-domain group first) the exact-peak group's
+		gu.n = is_pk ? gr.count : gr.count + gp.count;
+		const bool whole = gr.contiguous && (is_pk || gp.count == 0 || (gp.contiguous && gp.slot_base == gr.slot_base + gr.count));
+		if (whole) {
+			gu.slots = nullptr;
+			gu.slot_base = gr.slot_base;
+		}
+		gas_hrtf_uni_launch lu{ hrtf_common(c) };
+		lu.g = gu;
+		lu.peak_all = is_pk;
+		lu.partials = run.parts;
+		lu.p_offset = run.p_off;
+		lu.fresh = fresh;
+		lu.job = run.take(fd_gt, carried);
+		lu.er_ring_frames = c->cfg.er_ring_frames;
+		lu.peak_from = is_pk ? 0u : gr.count;
+		GAS_HIP(c, gas_launch_hrtf_uni(lu));
+		return GAS_OK;
+	}
+	// GAS_FLAG_DIRECTION_ORDER: direction order of the frequency-domain group, rebuilt when the
+	// callback's list or any parameter changed, else reused.  Only when directions repeat within a segment.
+	if (a.use_order && (c->cfg.flags & GAS_FLAG_DIRECTION_ORDER) != 0 && g_fd.n >= GAS_DIR_ORDER_MIN_SOURCES && (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) == 0 && gas_dir_order_supported(c->tab.dirs)) {
+		const uint32_t seg = g_fd.n < GAS_DIR_ORDER_SEGMENT ? g_fd.n : GAS_DIR_ORDER_SEGMENT;
+		if (seg >= 2 * c->tab.dirs) {
+			GAS_HIP(c, alloc_once(c, c->d_order, c->cfg.max_sources));
+			uint32_t *ord = c->d_order + groups[fd_gt].offset;
+			if (!c->order_ok[fd_gt]) {
+				GAS_HIP(c, gas_launch_dir_order(c->stream, g_fd, c->st.params, fresh, c->tab.dirs, ord));
+				c->order_ok[fd_gt] = true;
+			}
+			g_fd.order = ord;
+		}
+	}
+	gas_hrtf_ols_launch lo{ hrtf_common(c) };
+	lo.with_er = fd_gt == G_FX_ER_HRTF;
+	lo.crossfade = (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) != 0;
+	lo.runs = (c->cfg.flags & (GAS_FLAG_DIRECTION_RUNS | GAS_FLAG_DIRECTION_ORDER)) != 0;
+	lo.g_fd = g_fd;
+	lo.g_pk = g_pk;
+	lo.er_ring_frames = c->cfg.er_ring_frames;
+	lo.partials = run.parts;
+	lo.p_offset = run.p_off;
+	lo.cursors = fd_gt == G_FX_HRTF ? a.src.cursors : nullptr;
+	lo.fresh = fresh;
+	lo.job = run.take(fd_gt, carried);
+	lo.blend = blend_on(c);
+	lo.fade = fade_on(c);
+	GAS_HIP(c, gas_launch_hrtf_ols(lo));
+	return GAS_OK;
+}
+
+// G_FX_GENERIC: audio_spatializer_effect.cpp:52-76 on the device, chain by chain (`ga`: the group's entries).  Effect j
+// reads the previous stage's rows and writes the other ping-pong buffer; the last stage's rows are mixed by
+// k_rows_accumulate, unless the chain ends in a k_hrtf_uni launch, which mixes by itself.
+int launch_staged_chains(gas_ctx *c, const RunArgs &a, const gas_group_args &ga, const GroupRun &run) {
+	const uint32_t F = c->cfg.frames;
+	const Group &gr = a.groups[G_FX_GENERIC];
+	const uint32_t *const d_slots = a.slots, *const d_rows = a.rows;
+	const gas_audio_frame *const d_src = a.src.rows;
+	size_t need = 0;
+	for (const ChainRange &r : *a.ranges) {
+		need = need > (size_t)r.count * F ? need : (size_t)r.count * F;
+	}
+	if (need > c->d_chain_frames) {
+		GAS_HIP(c, hipStreamSynchronize(c->stream));
+		size_t cap[2] = { c->d_chain_frames, c->d_chain_frames };
+		c->d_chain_frames = 0; // both rows or neither
+		GAS_HIP(c, c->mem.grow(c->d_chain[0], cap[0], need));
+		GAS_HIP(c, c->mem.grow(c->d_chain[1], cap[1], need));
+		c->d_chain_frames = need;
+	}
+	uint32_t pp = run.p_off;
+	for (const ChainRange &r : *a.ranges) {
+		const uint32_t off = gr.offset + r.offset, pp_r = pp;
+		pp += range_partials(r, run.staged_uni);
+		gas_group_args in = ga;
+		in.n = r.count;
+		in.slots = d_slots + off;
+		in.rows = d_rows ? d_rows + off : nullptr;
+		in.src = d_rows ? d_src : d_src + (size_t)off * F; // identity rows: the run's first row is entry `off`
+		in.peaks = d_rows ? a.peaks : a.peaks + (size_t)off * 2;
+		const uint32_t *peak_rows = in.rows;
+		const bool last_is_uni = range_ends_in_uni(r, run.staged_uni);
+		const bool own = a.groups == c->groups; // the context's own list: GAS_FLAG_PEAKS_DRAINING_ONLY's bits exist
+		const int k0 = r.sig & 0xff;
+		// a last stage that is k_hrtf_uni: exact peaks for every source of the chain, or (GAS_FLAG_PEAKS_DRAINING_ONLY,
+		// the context's own list) for the draining ones
+		gas_hrtf_uni_launch lu{ hrtf_common(c) };
+		lu.peak_bits = own && r.peak_any && !r.peak_all ? c->d_peak_bits + (c->cfg.max_sources + 31) / 32 : nullptr;
+		lu.peak_all = !own || r.peak_all;
+		lu.partials = run.parts;
+		lu.p_offset = pp_r;
+		lu.peak_bit_base = r.offset;
+		if (last_is_uni && c->uni_flt_enabled && (r.sig >> 8) == GAS_FX_HRTF && (k0 == GAS_FX_HIGHSHELF || (k0 >= GAS_FX_LOWPASS && k0 <= GAS_FX_LOWSHELF)) && gas_shelf_scan_applies(k0 == GAS_FX_HIGHSHELF ? GAS_MODE_FX_HIGHSHELF : GAS_MODE_FX_FILTER, r.count, F)) {
+			// [one-biquad filter, HRTF]: one launch (k_hrtf_uni<FLT>), no rows in between.  The filter there is the
+			// scan form, so it is taken exactly where the two-launch road would take k_shelf_scan (same bits either
+			// way; small callbacks and GAS_SHELF_SCAN=0 keep the engine's serial order)
+			lu.g = in;
+			lu.flt_kind = (uint32_t)k0;
+			lu.mix_rate = c->cfg.mix_rate;
+			GAS_HIP(c, gas_launch_hrtf_uni(lu));
+			continue;
+		}
+		for (int j = 0; j < 4; j++) {
+			const int kind = (r.sig >> (8 * j)) & 0xff;
+			if (!kind) {
+				break;
+			}
+			if (last_is_uni && c->uni_er_enabled && kind == GAS_FX_EARLY_REFLECTIONS && j < 3 && ((r.sig >> (8 * (j + 1))) & 0xff) == GAS_FX_HRTF) {
+				// ... [ER, HRTF] at the end of a longer chain: both in the last launch (k_hrtf_uni<ER>), no rows in between
+				lu.g = in;
+				lu.g.peak_rows = peak_rows;
+				lu.er_ring_frames = c->cfg.er_ring_frames;
+				GAS_HIP(c, gas_launch_hrtf_uni(lu));
+				break;
+			}
+			if (last_is_uni && kind == GAS_FX_HRTF) { // (the last effect: one HRTF per chain)
+				lu.g = in; // dense rows of the previous stage, peaks into the callback's rows
+				lu.g.peak_rows = peak_rows;
+				GAS_HIP(c, gas_launch_hrtf_uni(lu));
+				break;
+			}
+			gas_audio_frame *outb = c->d_chain[j & 1];
+			if (kind == GAS_FX_HIGHSHELF) {
+				GAS_HIP(c, gas_launch_biquad_mix(c->stream, GAS_MODE_FX_HIGHSHELF, in, c->st, F, (uint32_t)j, 1, c->cfg.mix_rate, run.parts, 0, c->partial_rows, reinterpret_cast<float *>(outb)));
+			} else if (kind == GAS_FX_EARLY_REFLECTIONS) {
+				GAS_HIP(c, gas_launch_er_only(c->stream, in, c->st, F, c->cfg.er_ring_frames, run.parts, 0, c->partial_rows, outb, er_fade_on(c)));
+			} else if (kind == GAS_FX_HRTF) {
+				GAS_HIP(c, gas_launch_hrtf_rows(c->stream, (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) != 0, in, c->st, c->tab, c->d_tw, F, outb, blend_on(c), fade_on(c)));
+			} else { // a family's kind: settings (and state, or the slot's pool entry) of chain position j
+				GAS_HIP(c, fx_launch(c, kind, in, (uint32_t)j, outb));
+			}
+			in.src = outb; // dense rows from here on
+			in.rows = nullptr;
+		}
+		if (last_is_uni) {
+			continue;
+		}
+		gas_group_args fin = in;
+		fin.rows = peak_rows; // peaks go to the callback's row of each source
+		if (a.buses) {
+			GAS_HIP(c, gas_launch_rows_accumulate_buses(c->stream, fin, F, a.buses->routes, a.buses->n_buses, run.p_total, run.parts, pp_r));
+		} else {
+			GAS_HIP(c, gas_launch_rows_accumulate(c->stream, fin, F, run.parts, pp_r));
+		}
+	}
+	return GAS_OK;
+}
+
 // Device work of one callback over already-grouped entries.
 int run_groups(gas_ctx *c, const RunArgs &a) {
 	const uint32_t F = c->cfg.frames;
 	const Group *const groups = a.groups;
-	const std::vector<ChainRange> &ranges = *a.ranges;
-	const uint32_t *const d_slots = a.slots, *const d_rows = a.rows;
-	const gas_audio_frame *const d_src = a.src.rows; // nullptr when fused: only plain-[HRTF] launches run then, and they sample
 	uint32_t pcount[G_COUNT];
-	const bool uni_hrtf = groups == c->groups && uni_ok(c);
-	const bool staged_uni = uni_ok(c) && a.buses == nullptr && gas_hrtf_uni_waves() == 8; // staged chains ending in the HRTF: last stage = k_hrtf_uni
+	GroupRun run;
+	run.uni_hrtf = groups == c->groups && uni_ok(c);
+	run.staged_uni = uni_ok(c) && a.buses == nullptr && gas_hrtf_uni_waves() == 8; // staged chains ending in the HRTF: last stage = k_hrtf_uni
 	// [ER, HRTF] through k_hrtf_uni<ER> (22.5 -> see profiles/r03_notes.md): the exact-peak group's entries follow the
 	// frequency-domain group's in the callback's list, so one launch covers both
 	const bool pipelined = a.pipelined && c->pipelined_mix && a.channel_count == 1 && c->cfg.channel_count == 1;
 	const bool uni_er_pays = c->uni_er_mode == 2 || groups[G_FX_ER_HRTF_PK].count * 4 <= groups[G_FX_ER_HRTF].count + groups[G_FX_ER_HRTF_PK].count;
-	const bool uni_er = uni_ok(c) && a.buses == nullptr && gas_hrtf_uni_waves() == 8 && c->uni_er_enabled && uni_er_pays && (groups[G_FX_ER_HRTF].count == 0 || groups[G_FX_ER_HRTF_PK].count == 0 || groups[G_FX_ER_HRTF].offset + groups[G_FX_ER_HRTF].count == groups[G_FX_ER_HRTF_PK].offset);
-	plan_partials(groups, ranges, pcount, uni_hrtf, staged_uni, uni_er);
+	run.uni_er = uni_ok(c) && a.buses == nullptr && gas_hrtf_uni_waves() == 8 && c->uni_er_enabled && uni_er_pays && (groups[G_FX_ER_HRTF].count == 0 || groups[G_FX_ER_HRTF_PK].count == 0 || groups[G_FX_ER_HRTF].offset + groups[G_FX_ER_HRTF].count == groups[G_FX_ER_HRTF_PK].offset);
+	plan_partials(groups, *a.ranges, pcount, run.uni_hrtf, run.staged_uni, run.uni_er);
 	uint32_t p_total = 0, p_mix = 0;
 	for (int gt = 0; gt < G_COUNT; gt++) {
 		p_total += pcount[gt];
@@ -840,52 +1115,41 @@ int run_groups(gas_ctx *c, const RunArgs &a) {
 			p_mix = p_total;
 		}
 	}
+	run.p_total = p_total;
 	// GAS_FLAG_PIPELINED_MIX: only callbacks that are one channel pair wide and carry an HRTF launch defer their sum
 	// A launch can carry the pending sum when it is the plain [HRTF] kernel (register budget), covers every output
 	// column with a workgroup and the pending callback left at most 256 partial rows (k_hrtf_ols: job_issue).
 	// The plain [HRTF] launch takes it when there is one, else the [ER, HRTF] launch.
 	bool carrier = false;
-	int carrier_gt = -1;
 	if (!a.src.fused() && (c->cfg.flags & (GAS_FLAG_HRTF_CROSSFADE | GAS_FLAG_HRTF_INTERPOLATE)) == 0) {
 		for (int gt : { (int)G_FX_HRTF, (int)G_FX_ER_HRTF }) {
-			if (carrier_gt < 0 && groups[gt].count + groups[gt + 1].count > 0) {
-				carrier_gt = gt;
+			if (run.carrier_gt < 0 && groups[gt].count + groups[gt + 1].count > 0) {
+				run.carrier_gt = gt;
 			}
 		}
 	}
-	if (carrier_gt >= 0) {
-		carrier = (pcount[carrier_gt] + pcount[carrier_gt + 1]) * GAS_HRTF_JOB_WAVES >= F * 2 / 4 && c->pending_mix.p_total <= 256;
+	if (run.carrier_gt >= 0) {
+		// the oldest pending sum is the one a single launch carries; with none pending the launch counts as fitting (the
+		// join below then has nothing to do either way)
+		const bool fits = c->pending.empty() || c->pending.front().p_total <= 256;
+		carrier = (pcount[run.carrier_gt] + pcount[run.carrier_gt + 1]) * GAS_HRTF_JOB_WAVES >= F * 2 / 4 && fits;
 	}
-	int rc = GAS_OK;
-	if (!c->pending_more.empty()) { // left by a batched launch: a single launch carries one sum only
-		const std::vector<gas_ctx::PendingMix> more = std::move(c->pending_more);
-		c->pending_more.clear();
+	if (c->pending.size() > 1) { // left by a batched launch: a single launch carries one sum only, the oldest
+		const std::vector<gas_ctx::PendingMix> more(c->pending.begin() + 1, c->pending.end());
+		c->pending.resize(1);
 		for (const gas_ctx::PendingMix &pm : more) {
-			rc = reduce_now(c, pm);
-			if (rc != GAS_OK) {
-				return rc;
-			}
+			GAS_TRY(reduce_now(c, pm));
 		}
 	}
 	if (!pipelined || !carrier || (p_total > 0 ? p_total : 1) > c->partial_rows) {
-		rc = join_outputs(c); // nobody to carry the pending sum (or the partials are about to move): do it now
-		if (rc != GAS_OK) {
-			return rc;
-		}
+		GAS_TRY(join_outputs(c)); // nobody to carry the pending sum (or the partials are about to move): do it now
 	}
-	rc = ensure_partials(c, (p_total > 0 ? p_total : 1) * (a.buses ? a.buses->n_buses : 1u)); // buses: p_total rows per bus, bus after bus
-	if (rc != GAS_OK) {
-		return rc;
-	}
+	GAS_TRY(ensure_partials(c, (p_total > 0 ? p_total : 1) * (a.buses ? a.buses->n_buses : 1u))); // buses: p_total rows per bus, bus after bus
 	const int parity = pipelined ? free_plane(c, {}) : 0;
-	float *const parts = c->d_partials + (size_t)parity * c->partial_rows * c->cfg.channel_count * F * 2;
-	gas_deferred_reduce job; // handed to the first HRTF launch of this callback
-	if (c->pending_mix.valid) {
-		job.partials = c->d_partials + (size_t)c->pending_mix.parity * c->partial_rows * c->cfg.channel_count * F * 2;
-		job.p_count = c->pending_mix.p_total;
-		job.elems = F * 2;
-		job.out = reinterpret_cast<float *>(c->pending_mix.out);
-		c->pending_mix.valid = false;
+	float *const parts = run.parts = partials_plane(c, parity);
+	if (!c->pending.empty()) { // handed to the carrier's launch
+		run.job = carried_job(c, c->pending.front());
+		c->pending.clear();
 	}
 	// only the mix_channel launch over several channel pairs accumulates peaks (atomicMax over the pairs, from zero);
 	// every other launch -- a single pair included -- stores them, so the zeroing pass (a 4 us dispatch) is skipped
@@ -904,16 +1168,15 @@ int run_groups(gas_ctx *c, const RunArgs &a) {
 		dom = dom - 1; // one launch covers both
 	}
 
-	uint32_t p_off = 0;
 	for (int gt = 0; gt < G_COUNT; gt++) {
 		const Group &gr = groups[gt];
 		if (gr.count == 0) {
 			continue;
 		}
 		gas_group_args ga;
-		ga.src = d_src;
-		ga.rows = d_rows ? d_rows + gr.offset : nullptr;
-		ga.slots = d_slots + gr.offset;
+		ga.src = a.src.rows; // nullptr when fused: only plain-[HRTF] launches run then, and they sample
+		ga.rows = a.rows ? a.rows + gr.offset : nullptr;
+		ga.slots = a.slots + gr.offset;
 		ga.slot_base = 0;
 		ga.n = gr.count;
 		ga.peaks = a.peaks;
@@ -921,8 +1184,7 @@ int run_groups(gas_ctx *c, const RunArgs &a) {
 		if (timed) {
 			GAS_HIP(c, hipEventRecord(c->ev[c->ev_used], c->stream));
 		}
-		hipError_t e = hipSuccess;
-		uint64_t carried_bytes = 0; // the previous callback's partial mixes summed inside this launch (GAS_FLAG_PIPELINED_MIX)
+		uint64_t carried = 0; // bytes of the previous callback's partial mixes summed inside this launch (GAS_FLAG_PIPELINED_MIX)
 		switch (gt) {
 			case G_3D_MIX:
 			case G_3D_PROCESS: {
@@ -932,13 +1194,16 @@ int run_groups(gas_ctx *c, const RunArgs &a) {
 				}
 				const uint32_t cb = mode == GAS_MODE_MIX_CHANNEL ? a.channel_begin : 0;
 				const uint32_t cc = mode == GAS_MODE_MIX_CHANNEL ? a.channel_count : 1;
-				e = gas_launch_biquad_mix(c->stream, mode, ga, c->st, F, cb, cc, c->cfg.mix_rate, parts, p_off, c->partial_rows);
+				GAS_HIP(c, gas_launch_biquad_mix(c->stream, mode, ga, c->st, F, cb, cc, c->cfg.mix_rate, parts, run.p_off, c->partial_rows));
 			} break;
 			case G_FX_COPY:
-				e = gas_launch_biquad_mix(c->stream, GAS_MODE_COPY, ga, c->st, F, 0, 1, c->cfg.mix_rate, parts, p_off, c->partial_rows);
+				GAS_HIP(c, gas_launch_biquad_mix(c->stream, GAS_MODE_COPY, ga, c->st, F, 0, 1, c->cfg.mix_rate, parts, run.p_off, c->partial_rows));
 				break;
 			case G_FX_SHELF:
-				e = gas_launch_biquad_mix(c->stream, GAS_MODE_FX_HIGHSHELF, ga, c->st, F, 0, 1, c->cfg.mix_rate, parts, p_off, c->partial_rows);
+				GAS_HIP(c, gas_launch_biquad_mix(c->stream, GAS_MODE_FX_HIGHSHELF, ga, c->st, F, 0, 1, c->cfg.mix_rate, parts, run.p_off, c->partial_rows));
+				break;
+			case G_FX_ER:
+				GAS_HIP(c, gas_launch_er_only(c->stream, ga, c->st, F, c->cfg.er_ring_frames, parts, run.p_off, c->partial_rows, nullptr, er_fade_on(c)));
 				break;
 			case G_FX_HRTF_PK:
 			case G_FX_ER_HRTF_PK:
@@ -947,238 +1212,40 @@ int run_groups(gas_ctx *c, const RunArgs &a) {
 				}
 				[[fallthrough]];
 			case G_FX_HRTF:
-			case G_FX_ER_HRTF: {
-				const bool is_pk = gt == G_FX_HRTF_PK || gt == G_FX_ER_HRTF_PK;
-				const int fd_gt = is_pk ? gt - 1 : gt;
-				const Group &gp = groups[fd_gt + 1];
-				gas_group_args g_fd = ga, g_pk = ga;
-				if (is_pk) {
-					g_fd.n = 0;
-				} else {
-					g_pk.rows = d_rows ? d_rows + gp.offset : nullptr;
-					g_pk.slots = d_slots + gp.offset;
-					g_pk.n = gp.count;
-				}
-				// contiguous slot ranges need no slot list on the device (one dependent load less in the prologue)
-				if (g_fd.n && groups[fd_gt].contiguous) {
-					g_fd.slots = nullptr;
-					g_fd.slot_base = groups[fd_gt].slot_base;
-				}
-				if (g_pk.n && groups[fd_gt + 1].contiguous) {
-					g_pk.slots = nullptr;
-					g_pk.slot_base = groups[fd_gt + 1].slot_base;
-				}
-				// GAS_FLAG_DIRECTION_ORDER: direction order of the frequency-domain group, rebuilt when the
-				// callback's list or any parameter changed, else reused.  Only when directions repeat within a segment.
-				const gas_params *fresh = a.fresh; // both HRTF forms read device-published rows themselves and write them through
-				if (gt == G_FX_HRTF && gp.count == 0 && uni_hrtf) {
-					// the whole plain-[HRTF] group in one uniform launch (k_hrtf_uni.hip)
-					// XCD-affine processing order (k_xcd_order): rebuilt when the list or any parameter changed, else reused
-					const uint32_t uni_wgs = gas_hrtf_uni_partials(g_fd.n);
-					c->last_uni_ordered = false;
-					if (a.use_order && ((c->cfg.flags & GAS_FLAG_XCD_ORDER) != 0 || g_fd.n >= c->xcd_order_auto_min) && uni_wgs % 8 == 0 && c->tab.dirs >= 8) {
-						GAS_HIP(c, alloc_once(c, c->d_order, c->cfg.max_sources));
-						uint32_t *ord = c->d_order + groups[fd_gt].offset;
-						if (!c->order_ok[fd_gt]) {
-							GAS_HIP(c, gas_launch_xcd_order(c->stream, g_fd, c->st.params, fresh, c->tab.dirs, uni_wgs, gas_hrtf_uni_waves(), ord));
-							c->order_ok[fd_gt] = true;
-						}
-						g_fd.order = ord;
-						c->last_uni_ordered = true;
-					}
-					gas_hrtf_uni_launch lu{ hrtf_common(c) };
-					lu.g = g_fd;
-					lu.peak_bits = c->uni_peak_any && !c->uni_peak_all ? c->d_peak_bits : nullptr;
-					lu.peak_all = c->uni_peak_all;
-					lu.partials = parts;
-					lu.p_offset = p_off;
-					lu.cursors = a.src.cursors;
-					lu.feed = a.src.feed;
-					lu.fresh = fresh;
-					lu.job = job;
-					e = gas_launch_hrtf_uni(lu);
-					carried_bytes = job.partials ? ((uint64_t)job.p_count + 1) * job.elems * sizeof(float) : 0;
-					job = gas_deferred_reduce();
-					break;
-				}
-				if (fd_gt == G_FX_ER_HRTF && uni_er) {
-					gas_group_args gu = ga; // this group's entries, then (frequency-domain group first) the exact-peak group's
-					gu.n = is_pk ? gr.count : gr.count + gp.count;
-					const bool whole = groups[gt].contiguous && (is_pk || gp.count == 0 || (gp.contiguous && gp.slot_base == gr.slot_base + gr.count));
-					if (whole) {
-						gu.slots = nullptr;
-						gu.slot_base = groups[gt].slot_base;
-					}
-					gas_hrtf_uni_launch lu{ hrtf_common(c) };
-					lu.g = gu;
-					lu.peak_all = is_pk;
-					lu.partials = parts;
-					lu.p_offset = p_off;
-					lu.fresh = fresh;
-					lu.job = fd_gt == carrier_gt ? job : gas_deferred_reduce();
-					lu.er_ring_frames = c->cfg.er_ring_frames;
-					lu.peak_from = is_pk ? 0u : gr.count;
-					e = gas_launch_hrtf_uni(lu);
-					if (fd_gt == carrier_gt) {
-						carried_bytes = job.partials ? ((uint64_t)job.p_count + 1) * job.elems * sizeof(float) : 0;
-						job = gas_deferred_reduce();
-					}
-					break;
-				}
-				if (a.use_order && (c->cfg.flags & GAS_FLAG_DIRECTION_ORDER) != 0 && g_fd.n >= GAS_DIR_ORDER_MIN_SOURCES && (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) == 0 && gas_dir_order_supported(c->tab.dirs)) {
-					const uint32_t seg = g_fd.n < GAS_DIR_ORDER_SEGMENT ? g_fd.n : GAS_DIR_ORDER_SEGMENT;
-					if (seg >= 2 * c->tab.dirs) {
-						GAS_HIP(c, alloc_once(c, c->d_order, c->cfg.max_sources));
-						uint32_t *ord = c->d_order + groups[fd_gt].offset;
-						if (!c->order_ok[fd_gt]) {
-							GAS_HIP(c, gas_launch_dir_order(c->stream, g_fd, c->st.params, fresh, c->tab.dirs, ord));
-							c->order_ok[fd_gt] = true;
-						}
-						g_fd.order = ord;
-					}
-				}
-				gas_hrtf_ols_launch lo{ hrtf_common(c) };
-				lo.with_er = fd_gt == G_FX_ER_HRTF;
-				lo.crossfade = (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) != 0;
-				lo.runs = (c->cfg.flags & (GAS_FLAG_DIRECTION_RUNS | GAS_FLAG_DIRECTION_ORDER)) != 0;
-				lo.g_fd = g_fd;
-				lo.g_pk = g_pk;
-				lo.er_ring_frames = c->cfg.er_ring_frames;
-				lo.partials = parts;
-				lo.p_offset = p_off;
-				lo.cursors = fd_gt == G_FX_HRTF ? a.src.cursors : nullptr;
-				lo.fresh = fresh;
-				lo.job = fd_gt == carrier_gt ? job : gas_deferred_reduce();
-				lo.blend = blend_on(c);
-				lo.fade = fade_on(c);
-				e = gas_launch_hrtf_ols(lo);
-				if (fd_gt == carrier_gt) {
-					carried_bytes = job.partials ? ((uint64_t)job.p_count + 1) * job.elems * sizeof(float) : 0;
-					job = gas_deferred_reduce();
-				}
-			} break;
-			case G_FX_GENERIC: {
-				// audio_spatializer_effect.cpp:52-76 on the device: effect j reads the previous stage's rows and writes
-				// the other ping-pong buffer; the last stage's rows are mixed by k_rows_accumulate
-				size_t need = 0;
-				for (const ChainRange &r : ranges) {
-					need = need > (size_t)r.count * F ? need : (size_t)r.count * F;
-				}
-				if (need > c->d_chain_frames) {
-					GAS_HIP(c, hipStreamSynchronize(c->stream));
-					size_t cap[2] = { c->d_chain_frames, c->d_chain_frames };
-					c->d_chain_frames = 0; // both rows or neither
-					GAS_HIP(c, c->mem.grow(c->d_chain[0], cap[0], need));
-					GAS_HIP(c, c->mem.grow(c->d_chain[1], cap[1], need));
-					c->d_chain_frames = need;
-				}
-				uint32_t pp = p_off;
-				for (const ChainRange &r : ranges) {
-					const uint32_t off = gr.offset + r.offset;
-					gas_group_args in = ga;
-					in.n = r.count;
-					in.slots = d_slots + off;
-					in.rows = d_rows ? d_rows + off : nullptr;
-					in.src = d_rows ? d_src : d_src + (size_t)off * F; // identity rows: the run's first row is entry `off`
-					in.peaks = d_rows ? a.peaks : a.peaks + (size_t)off * 2;
-					const uint32_t *peak_rows = in.rows;
-					const bool last_is_uni = range_ends_in_uni(r, staged_uni);
-					const bool own = groups == c->groups; // the context's own list: GAS_FLAG_PEAKS_DRAINING_ONLY's bits exist
-					const int k0 = r.sig & 0xff;
-					// a last stage that is k_hrtf_uni: exact peaks for every source of the chain, or (GAS_FLAG_PEAKS_DRAINING_ONLY,
-					// the context's own list) for the draining ones
-					gas_hrtf_uni_launch lu{ hrtf_common(c) };
-					lu.peak_bits = own && r.peak_any && !r.peak_all ? c->d_peak_bits + (c->cfg.max_sources + 31) / 32 : nullptr;
-					lu.peak_all = !own || r.peak_all;
-					lu.partials = parts;
-					lu.p_offset = pp;
-					lu.peak_bit_base = r.offset;
-					if (last_is_uni && c->uni_flt_enabled && (r.sig >> 8) == GAS_FX_HRTF && (k0 == GAS_FX_HIGHSHELF || (k0 >= GAS_FX_LOWPASS && k0 <= GAS_FX_LOWSHELF)) && gas_shelf_scan_applies(k0 == GAS_FX_HIGHSHELF ? GAS_MODE_FX_HIGHSHELF : GAS_MODE_FX_FILTER, r.count, F)) {
-						// [one-biquad filter, HRTF]: one launch (k_hrtf_uni<FLT>), no rows in between.  The filter there is the
-						// scan form, so it is taken exactly where the two-launch road would take k_shelf_scan (same bits either
-						// way; small callbacks and GAS_SHELF_SCAN=0 keep the engine's serial order)
-						lu.g = in;
-						lu.flt_kind = (uint32_t)k0;
-						lu.mix_rate = c->cfg.mix_rate;
-						e = gas_launch_hrtf_uni(lu);
-						pp += range_partials(r, staged_uni);
-						continue;
-					}
-					for (int j = 0; j < 4 && e == hipSuccess; j++) {
-						const int kind = (r.sig >> (8 * j)) & 0xff;
-						if (!kind) {
-							break;
-						}
-						if (last_is_uni && c->uni_er_enabled && kind == GAS_FX_EARLY_REFLECTIONS && j < 3 && ((r.sig >> (8 * (j + 1))) & 0xff) == GAS_FX_HRTF) {
-							// ... [ER, HRTF] at the end of a longer chain: both in the last launch (k_hrtf_uni<ER>), no rows in between
-							lu.g = in;
-							lu.g.peak_rows = peak_rows;
-							lu.er_ring_frames = c->cfg.er_ring_frames;
-							e = gas_launch_hrtf_uni(lu);
-							break;
-						}
-						if (last_is_uni && kind == GAS_FX_HRTF) { // (the last effect: one HRTF per chain)
-							lu.g = in; // dense rows of the previous stage, peaks into the callback's rows
-							lu.g.peak_rows = peak_rows;
-							e = gas_launch_hrtf_uni(lu);
-							break;
-						}
-						gas_audio_frame *outb = c->d_chain[j & 1];
-						if (kind == GAS_FX_HIGHSHELF) {
-							e = gas_launch_biquad_mix(c->stream, GAS_MODE_FX_HIGHSHELF, in, c->st, F, (uint32_t)j, 1, c->cfg.mix_rate, parts, 0, c->partial_rows, reinterpret_cast<float *>(outb));
-						} else if (kind == GAS_FX_EARLY_REFLECTIONS) {
-							e = gas_launch_er_only(c->stream, in, c->st, F, c->cfg.er_ring_frames, parts, 0, c->partial_rows, outb, er_fade_on(c));
-						} else if (kind == GAS_FX_HRTF) {
-							e = gas_launch_hrtf_rows(c->stream, (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) != 0, in, c->st, c->tab, c->d_tw, F, outb, blend_on(c), fade_on(c));
-						} else { // a family's kind: settings (and state, or the slot's pool entry) of chain position j
-							e = fx_launch(c, kind, in, (uint32_t)j, outb);
-						}
-						in.src = outb; // dense rows from here on
-						in.rows = nullptr;
-					}
-					if (e == hipSuccess && !last_is_uni) {
-						gas_group_args fin = in;
-						fin.rows = peak_rows; // peaks go to the callback's row of each source
-						if (a.buses) {
-							e = gas_launch_rows_accumulate_buses(c->stream, fin, F, a.buses->routes, a.buses->n_buses, p_total, parts, pp);
-						} else {
-							e = gas_launch_rows_accumulate(c->stream, fin, F, parts, pp);
-						}
-					}
-					pp += range_partials(r, staged_uni);
-				}
-			} break;
-			case G_FX_ER:
-				e = gas_launch_er_only(c->stream, ga, c->st, F, c->cfg.er_ring_frames, parts, p_off, c->partial_rows, nullptr, er_fade_on(c));
+			case G_FX_ER_HRTF:
+				GAS_TRY(launch_hrtf_groups(c, a, gt, ga, run, carried));
+				break;
+			case G_FX_GENERIC:
+				GAS_TRY(launch_staged_chains(c, a, ga, run));
 				break;
 		}
-		GAS_HIP(c, e);
 		if (timed) {
 			GAS_HIP(c, hipEventRecord(c->ev[c->ev_used + 1], c->stream));
 			c->ev_used += 2;
-			c->prof_bytes = group_bytes(c, gt, gr.count) + carried_bytes;
+			c->prof_bytes = group_bytes(c, gt, gr.count) + carried;
 			c->prof_k = 1;
 			if ((gt == G_FX_HRTF || gt == G_FX_ER_HRTF) && groups[gt + 1].count > 0) {
 				// the exact-peak sources ride in the same launch: add their per-source bytes (table/mix terms counted once)
 				c->prof_bytes += group_bytes(c, gt + 1, groups[gt + 1].count) - group_bytes(c, gt + 1, 0);
 			}
 			c->prof_group = gt;
-			c->prof_uni = (gt == G_FX_HRTF && uni_hrtf && groups[G_FX_HRTF_PK].count == 0) || ((gt == G_FX_ER_HRTF || gt == G_FX_ER_HRTF_PK) && uni_er);
+			c->prof_uni = (gt == G_FX_HRTF && run.uni_hrtf && groups[G_FX_HRTF_PK].count == 0) || ((gt == G_FX_ER_HRTF || gt == G_FX_ER_HRTF_PK) && run.uni_er);
 			c->prof_multi = false;
 			c->prof_pipe = (gt == G_3D_MIX || gt == G_3D_PROCESS || gt == G_FX_SHELF) && gas_biquad_uses_pipe(gt == G_FX_SHELF ? GAS_MODE_FX_HIGHSHELF : (a.force_mode >= 0 ? a.force_mode : (gt == G_3D_MIX ? GAS_MODE_MIX_CHANNEL : GAS_MODE_PROCESS_FRAMES)), gr.count, gt == G_3D_MIX ? a.channel_count : 1, F, false);
 		}
-		p_off += pcount[gt];
+		run.p_off += pcount[gt];
 	}
 
 	// channel pair 0 sums every group's partials; pairs > 0 only the mix_channel group's (which come first)
-	if (job.partials) { // no launch took the pending sum along (cannot happen with hrtf_launch set; kept for safety)
-		GAS_HIP(c, gas_launch_mix_reduce(c->stream, job.partials, job.p_count, c->partial_rows, 1, F, reinterpret_cast<gas_audio_frame *>(job.out)));
+	if (run.job.partials) { // no launch took the pending sum along (cannot happen with hrtf_launch set; kept for safety)
+		GAS_HIP(c, gas_launch_mix_reduce(c->stream, run.job.partials, run.job.p_count, c->partial_rows, 1, F, reinterpret_cast<gas_audio_frame *>(run.job.out)));
 	}
 	if (pipelined) { // summed by the next callback's HRTF launch, gas_ctx_join_outputs or the next ordered call
-		c->pending_mix.valid = true;
-		c->pending_mix.parity = parity;
-		c->pending_mix.p_total = p_total;
-		c->pending_mix.out = a.out;
+		gas_ctx::PendingMix pm;
+		pm.parity = parity;
+		pm.p_total = p_total;
+		pm.out = a.out;
+		c->pending.push_back(pm);
 		c->pipe_tick++;
 		return GAS_OK;
 	}
@@ -1236,21 +1303,14 @@ bool batchable(const gas_ctx *c, uint32_t n, bool fused) {
 int run_hrtf_batch(gas_ctx *c, const std::vector<gas_ctx::Deferred> &blocks, uint32_t n) {
 	const uint32_t F = c->cfg.frames, K = (uint32_t)blocks.size();
 	const uint32_t wgs = gas_hrtf_uni_partials(n);
-	int rc = GAS_OK;
-	bool tall = c->pending_mix.valid && c->pending_mix.p_total > 256;
-	for (const gas_ctx::PendingMix &pm : c->pending_more) {
+	bool tall = false;
+	for (const gas_ctx::PendingMix &pm : c->pending) {
 		tall = tall || pm.p_total > 256;
 	}
 	if (wgs > c->partial_rows || c->partial_planes < 2 * GAS_HRTF_MULTI_MAX_BLOCKS || tall) {
-		rc = join_outputs(c); // the partials are about to move, or a pending sum is too tall for a job wave
-		if (rc != GAS_OK) {
-			return rc;
-		}
+		GAS_TRY(join_outputs(c)); // the partials are about to move, or a pending sum is too tall for a job wave
 	}
-	rc = ensure_partials(c, wgs);
-	if (rc != GAS_OK) {
-		return rc;
-	}
+	GAS_TRY(ensure_partials(c, wgs));
 	const gas_group_args ga = own_hrtf_group(c, blocks[0].src, n, blocks[0].peaks);
 	gas_hrtf_blocks mb;
 	mb.k = K;
@@ -1263,28 +1323,13 @@ int run_hrtf_batch(gas_ctx *c, const std::vector<gas_ctx::Deferred> &blocks, uin
 		}
 	}
 	// the pending sums ride with the first blocks of this launch, one each; any beyond that are summed right away
-	const size_t plane_elems = (size_t)c->partial_rows * c->cfg.channel_count * F * 2;
-	std::vector<gas_ctx::PendingMix> carried;
-	if (c->pending_mix.valid) {
-		carried.push_back(c->pending_mix);
-	}
-	for (const gas_ctx::PendingMix &pm : c->pending_more) {
-		carried.push_back(pm);
-	}
-	uint64_t carried_bytes = 0;
-	for (size_t j = 0; j < carried.size(); j++) {
+	uint64_t carried = 0;
+	for (size_t j = 0; j < c->pending.size(); j++) {
 		if (j < K) {
-			gas_deferred_reduce &job = mb.job[j];
-			job.partials = c->d_partials + (size_t)carried[j].parity * plane_elems;
-			job.p_count = carried[j].p_total;
-			job.elems = F * 2;
-			job.out = reinterpret_cast<float *>(carried[j].out);
-			carried_bytes += ((uint64_t)job.p_count + 1) * job.elems * sizeof(float);
+			mb.job[j] = carried_job(c, c->pending[j]);
+			carried += carried_bytes(mb.job[j]);
 		} else {
-			rc = reduce_now(c, carried[j]);
-			if (rc != GAS_OK) {
-				return rc;
-			}
+			GAS_TRY(reduce_now(c, c->pending[j]));
 		}
 	}
 	// the planes this launch fills: none that a carried sum still reads (the pending records stay in place until the
@@ -1298,13 +1343,12 @@ int run_hrtf_batch(gas_ctx *c, const std::vector<gas_ctx::Deferred> &blocks, uin
 		planes.push_back(pl);
 		mb.p_offset[b] = (uint32_t)pl * c->partial_rows * c->cfg.channel_count;
 	}
-	c->pending_mix.valid = false;
-	c->pending_more.clear();
+	c->pending.clear();
 	const bool timed = c->profiling && c->ev_used + 2 <= c->ev.size() && (c->prof_tick++ % c->prof_every) == 0;
 	if (timed) {
 		GAS_HIP(c, hipEventRecord(c->ev[c->ev_used], c->stream));
 	}
-	GAS_HIP(c, gas_launch_hrtf_multi(c->stream, ga, mb, c->uni_peak_any && !c->uni_peak_all ? c->d_peak_bits : nullptr, c->uni_peak_all, c->st, c->tab, c->d_tw, F, c->hist_len, c->d_partials));
+	GAS_HIP(c, gas_launch_hrtf_multi(c->stream, ga, mb, plain_peak_bits(c), c->uni_peak_all, c->st, c->tab, c->d_tw, F, c->hist_len, c->d_partials));
 	if (timed) {
 		GAS_HIP(c, hipEventRecord(c->ev[c->ev_used + 1], c->stream));
 		c->ev_used += 2;
@@ -1320,9 +1364,9 @@ int run_hrtf_batch(gas_ctx *c, const std::vector<gas_ctx::Deferred> &blocks, uin
 			for (uint32_t b = 0; b < K; b++) {
 				fresh_blocks += blocks[b].fresh ? 1 : 0;
 			}
-			c->prof_bytes = (uint64_t)K * n * (F * 8 + 8) + fresh_blocks * n * 8 + (uint64_t)n * 8 + (hist_lds ? 1ull : (uint64_t)K) * n * hist_rw + (uint64_t)c->tab.dirs * 2 * GAS_HRTF_TAPS * 4 + (uint64_t)K * c->cfg.channel_count * F * 8 + carried_bytes;
+			c->prof_bytes = (uint64_t)K * n * (F * 8 + 8) + fresh_blocks * n * 8 + (uint64_t)n * 8 + (hist_lds ? 1ull : (uint64_t)K) * n * hist_rw + (uint64_t)c->tab.dirs * 2 * GAS_HRTF_TAPS * 4 + (uint64_t)K * c->cfg.channel_count * F * 8 + carried;
 		}
-		c->prof_bytes_formula = (uint64_t)K * group_bytes(c, G_FX_HRTF, n) + carried_bytes;
+		c->prof_bytes_formula = (uint64_t)K * group_bytes(c, G_FX_HRTF, n) + carried;
 		c->prof_k = K;
 		c->prof_group = G_FX_HRTF;
 		c->prof_uni = false;
@@ -1331,15 +1375,10 @@ int run_hrtf_batch(gas_ctx *c, const std::vector<gas_ctx::Deferred> &blocks, uin
 	}
 	for (uint32_t b = 0; b < K; b++) {
 		gas_ctx::PendingMix pm;
-		pm.valid = true;
 		pm.parity = planes[b];
 		pm.p_total = wgs;
 		pm.out = blocks[b].out;
-		if (b == 0) {
-			c->pending_mix = pm;
-		} else {
-			c->pending_more.push_back(pm);
-		}
+		c->pending.push_back(pm);
 	}
 	c->pipe_tick += K;
 	return GAS_OK;
@@ -1992,22 +2031,18 @@ inline int launch_group(const gas_ctx *c, const SlotInfo &si, bool all_staged) {
 // kinds): every chain runs staged (rows out), the rows are mixed per bus.
 int build_groups(gas_ctx *c, const uint32_t *slots, uint32_t n, bool all_staged) {
 	uint32_t counts[G_COUNT] = { 0 };
-	if (++c->stamp_gen == 0) {
-		std::fill(c->stamp.begin(), c->stamp.end(), 0u);
-		c->stamp_gen = 1;
-	}
+	c->stamp.next();
 	for (uint32_t i = 0; i < n; i++) {
 		const uint32_t s = slots[i];
-		if (s >= c->cfg.max_sources || !c->slots[s].used) {
+		if (!live(c, s)) {
 			return GAS_ERR_BAD_SLOT;
 		}
 		if (!c->slots[s].has_params) {
 			return GAS_ERR_NO_PARAMS;
 		}
-		if (c->stamp[s] == c->stamp_gen) {
+		if (c->stamp.seen(s)) {
 			return GAS_ERR_INVALID_ARGUMENT; // one playback twice in a callback would race on its state
 		}
-		c->stamp[s] = c->stamp_gen;
 		counts[launch_group(c, c->slots[s], all_staged)]++;
 	}
 	uint32_t off = 0, cursor[G_COUNT];
@@ -2319,8 +2354,8 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 	c->slots.resize(N);
 	c->h_routes.assign(N, gas_bus_route_default());
 	c->h_cursors.assign(N, gas_cursor{});
-	c->stamp.assign(N, 0);
-	c->calc_stamp.assign(N, 0);
+	c->stamp.at.assign(N, 0);
+	c->calc_stamp.at.assign(N, 0);
 	c->dirty_flag.assign(N, 0);
 	if (blend_on(c)) {
 		c->h_blend.assign(N, gas_hrtf_blend{});
@@ -2671,7 +2706,7 @@ int gas_params_publish_batch(gas_ctx *c, const uint32_t *slots, const gas_params
 			return GAS_ERR_INVALID_ARGUMENT;
 		}
 		for (uint32_t i = 0; i < n; i++) {
-			if (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used) {
+			if (!live(c, slots[i])) {
 				return GAS_ERR_BAD_SLOT;
 			}
 		}
@@ -2691,21 +2726,13 @@ int gas_params_publish_batch(gas_ctx *c, const uint32_t *slots, const gas_params
 	// slots == NULL addresses the slot list of the last gas_process_block, in its row order.
 	GAS_HIP(c, hipSetDevice(c->cfg.device));
 	if (slots) {
-		{ // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
-			const int rcd = flush_deferred(c);
-			if (rcd != GAS_OK) {
-				return rcd;
-			}
-		}
-		int rcp = flush_pending_params(c);
-		if (rcp != GAS_OK) {
-			return rcp;
-		}
+		GAS_TRY(flush_deferred(c)); // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
+		GAS_TRY(flush_pending_params(c));
 		if (n > c->cfg.max_sources) {
 			return GAS_ERR_INVALID_ARGUMENT;
 		}
 		for (uint32_t i = 0; i < n; i++) {
-			if (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used) {
+			if (!live(c, slots[i])) {
 				return GAS_ERR_BAD_SLOT;
 			}
 			c->slots[slots[i]].has_params = 1;
@@ -2721,15 +2748,9 @@ int gas_params_publish_batch(gas_ctx *c, const uint32_t *slots, const gas_params
 		// Deferred: the next gas_process_block over this same list consumes the rows in its own launch when it can
 		// (all sources [HRTF] or [ER, HRTF] chains), else scatters them first.  The buffer must stay untouched until then.
 		if (c->pending_params) { // an earlier publish nobody consumed is about to be scattered: recorded callbacks first
-			const int rcd = flush_deferred(c);
-			if (rcd != GAS_OK) {
-				return rcd;
-			}
+			GAS_TRY(flush_deferred(c));
 		}
-		int rcp = flush_pending_params(c);
-		if (rcp != GAS_OK) {
-			return rcp;
-		}
+		GAS_TRY(flush_pending_params(c));
 		c->pending_params = params;
 		c->pending_n = n;
 	}
@@ -2747,19 +2768,14 @@ int gas_calc_spatialization_areas(gas_ctx *c, const gas_spatializer3d_config *cf
 	if (n_cfgs == 0 || n_cfgs > GAS_MAX_SPATIALIZER_CONFIGS || n_listeners > GAS_MAX_LISTENERS || n > c->cfg.max_sources) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
-	{ // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
-		const int rcd = flush_deferred(c);
-		if (rcd != GAS_OK) {
-			return rcd;
-		}
-	}
+	GAS_TRY(flush_deferred(c)); // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
 	for (uint32_t i = 0; i < n_cfgs; i++) {
 		if (cfgs[i].speaker_mode < 0 || cfgs[i].speaker_mode > 3 || !(cfgs[i].unit_size > 0.0f)) {
 			return GAS_ERR_INVALID_ARGUMENT;
 		}
 	}
 	for (uint32_t i = 0; i < n; i++) {
-		if (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used) {
+		if (!live(c, slots[i])) {
 			return GAS_ERR_BAD_SLOT;
 		}
 		if (cfg_index && cfg_index[i] >= n_cfgs) {
@@ -2770,23 +2786,14 @@ int gas_calc_spatialization_areas(gas_ctx *c, const gas_spatializer3d_config *cf
 		return GAS_OK;
 	}
 	std::lock_guard<std::mutex> lk(c->calc_mu);
-	if (++c->calc_stamp_gen == 0) {
-		std::fill(c->calc_stamp.begin(), c->calc_stamp.end(), 0u);
-		c->calc_stamp_gen = 1;
-	}
+	c->calc_stamp.next();
 	for (uint32_t i = 0; i < n; i++) {
-		if (c->calc_stamp[slots[i]] == c->calc_stamp_gen) {
+		if (c->calc_stamp.seen(slots[i])) {
 			return GAS_ERR_INVALID_ARGUMENT; // one playback twice: two lanes would race on its table row and its latch
 		}
-		c->calc_stamp[slots[i]] = c->calc_stamp_gen;
 	}
 	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	{
-		int rcp = flush_pending_params(c);
-		if (rcp != GAS_OK) {
-			return rcp;
-		}
-	}
+	GAS_TRY(flush_pending_params(c));
 	{ // rows published from the host before this call reach the table first: the launch keeps their fields it does not
 	  // write (early reflections, shelf, hrtf_* without a grid) and its own are not overwritten by them at the next callback
 		int rcr = flush_param_rows(c);
@@ -2873,7 +2880,7 @@ int gas_calc_early_reflections(gas_ctx *c, const gas_room *rooms, uint32_t n_roo
 		}
 	}
 	for (uint32_t i = 0; i < n; i++) {
-		if (slots && (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used)) {
+		if (slots && !live(c, slots[i])) {
 			return GAS_ERR_BAD_SLOT;
 		}
 		if (room_index && room_index[i] >= n_rooms && room_index[i] != GAS_ROOM_NONE) {
@@ -2885,15 +2892,11 @@ int gas_calc_early_reflections(gas_ctx *c, const gas_room *rooms, uint32_t n_roo
 	}
 	std::lock_guard<std::mutex> lk(c->calc_mu);
 	if (slots) {
-		if (++c->calc_stamp_gen == 0) {
-			std::fill(c->calc_stamp.begin(), c->calc_stamp.end(), 0u);
-			c->calc_stamp_gen = 1;
-		}
+		c->calc_stamp.next();
 		for (uint32_t i = 0; i < n; i++) {
-			if (c->calc_stamp[slots[i]] == c->calc_stamp_gen) {
+			if (c->calc_stamp.seen(slots[i])) {
 				return GAS_ERR_INVALID_ARGUMENT; // one playback twice: two lane groups would race on its row
 			}
-			c->calc_stamp[slots[i]] = c->calc_stamp_gen;
 		}
 	}
 	GAS_HIP(c, hipSetDevice(c->cfg.device));
@@ -3230,7 +3233,7 @@ int feed_place(gas_ctx *c, size_t bytes, size_t &at, bool &switched) {
 	const uint32_t F = c->cfg.frames;
 	size_t off = hdr + (1 - c->feed_side) * half;
 	for (uint32_t s : c->feed_slots) {
-		if (c->stamp[s] == c->stamp_gen) {
+		if (c->stamp.has(s)) {
 			continue; // this call replaces it
 		}
 		const uint32_t w = c->feed_word[s];
@@ -3265,6 +3268,49 @@ hipError_t copy_back(gas_ctx *c, gas_audio_frame *out, const gas_audio_frame *d_
 	return e == hipSuccess ? hipStreamSynchronize(c->stream) : e;
 }
 
+// A GAS_MEM_HOST callback runs on the library's own buffers; copy_back is the way home.  Makes room in d_src for the n
+// rows and queues their upload (rows == nullptr: the rows are on the device already), and names what the launches
+// write: d_out -- a bus callback: d_bus_out, allocated by the first call that needs it -- and d_peaks.
+int stage_host(gas_ctx *c, const gas_audio_frame *rows, uint32_t n, bool buses, gas_audio_frame *&d_out, float *&d_peaks) {
+	const size_t frames = (size_t)n * c->cfg.frames;
+	if (rows) {
+		GAS_HIP(c, ensure_src(c, frames));
+		if (n > 0) {
+			GAS_HIP(c, hipMemcpyAsync(c->d_src, rows, frames * sizeof(gas_audio_frame), hipMemcpyHostToDevice, c->stream));
+		}
+	}
+	if (buses) {
+		GAS_HIP(c, alloc_once(c, c->d_bus_out, (size_t)GAS_MAX_BUSES * c->cfg.channel_count * c->cfg.frames));
+	}
+	d_out = buses ? c->d_bus_out : c->d_out;
+	d_peaks = c->d_peaks;
+	return GAS_OK;
+}
+
+// What a bus callback can run: a list whose sources are all 3D mix (the empty list too), or all non-empty effect chains
+// on a one-pair context -- plain [HRTF] every one of them, which has a fused form, or not.  Slots that are not live are
+// skipped: build_groups rejects them.
+enum BusList { BUS_LIST_NEITHER = 0, BUS_LIST_3D_MIX, BUS_LIST_CHAINS, BUS_LIST_PLAIN_HRTF };
+
+BusList bus_list_form(const gas_ctx *c, const uint32_t *slots, uint32_t n) {
+	bool all_mix = true, all_fx = n > 0, all_plain_hrtf = true;
+	for (uint32_t i = 0; i < n; i++) {
+		if (live(c, slots[i])) {
+			const SlotInfo &si = c->slots[slots[i]];
+			all_mix = all_mix && si.kind == GAS_KIND_3D_MIX;
+			all_fx = all_fx && si.kind == GAS_KIND_EFFECT && si.chain_sig != 0;
+			all_plain_hrtf = all_plain_hrtf && si.group == G_FX_HRTF;
+		}
+	}
+	if (all_mix) {
+		return BUS_LIST_3D_MIX;
+	}
+	if (!all_fx || c->cfg.channel_count != 1) {
+		return BUS_LIST_NEITHER;
+	}
+	return all_plain_hrtf ? BUS_LIST_PLAIN_HRTF : BUS_LIST_CHAINS;
+}
+
 // A failed callback leaves a zeroed mix in host memory (the reference's ERR_FAIL paths, audio_spatializer.cpp:335-343);
 // device memory is left as it is.
 int fail_out(int code, int mem, gas_audio_frame *out, size_t out_bytes) {
@@ -3295,12 +3341,7 @@ static int process_block_streams_common(gas_ctx *c, const uint32_t *slots, uint3
 		}
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
-	{ // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
-		const int rcd = flush_deferred(c);
-		if (rcd != GAS_OK) {
-			return rcd;
-		}
-	}
+	GAS_TRY(flush_deferred(c)); // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
 	const uint32_t F = c->cfg.frames, C = c->cfg.channel_count;
 	const size_t out_bytes = (size_t)(buses ? n_buses : 1u) * C * F * sizeof(gas_audio_frame);
 	const auto fail = [&](int code) { return fail_out(code, mem, out, out_bytes); };
@@ -3318,7 +3359,7 @@ static int process_block_streams_common(gas_ctx *c, const uint32_t *slots, uint3
 	if (!same_list) {
 		stream_rows_sync_back(c);
 		for (uint32_t i = 0; i < n; i++) {
-			if (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used) {
+			if (!live(c, slots[i])) {
 				return fail(GAS_ERR_BAD_SLOT);
 			}
 			const float pitch = c->slots[slots[i]].has_params ? c->h_params[slots[i]].pitch_scale : 1.0f;
@@ -3337,34 +3378,22 @@ static int process_block_streams_common(gas_ctx *c, const uint32_t *slots, uint3
 		// Everything gas_process_block could still reject is checked BEFORE a cursor moves: the reference consumes a
 		// playback's frames only when it mixes them (audio_spatializer.cpp:378), so a failed callback must leave
 		// the playback cursors (host mirror and device) where they were.
-		if (++c->stamp_gen == 0) {
-			std::fill(c->stamp.begin(), c->stamp.end(), 0u);
-			c->stamp_gen = 1;
-		}
+		c->stamp.next();
 		for (uint32_t i = 0; i < n; i++) {
 			const SlotInfo &si = c->slots[slots[i]];
 			if (!si.has_params) {
 				return fail(GAS_ERR_NO_PARAMS);
 			}
-			if (c->stamp[slots[i]] == c->stamp_gen) {
+			if (c->stamp.seen(slots[i])) {
 				return fail(GAS_ERR_INVALID_ARGUMENT); // one playback twice in a callback
 			}
-			c->stamp[slots[i]] = c->stamp_gen;
 			const bool wants_hrtf = si.group == G_FX_HRTF || si.group == G_FX_ER_HRTF || (si.group == G_FX_GENERIC && chain_has(si.chain_sig, GAS_FX_HRTF));
 			if (wants_hrtf && c->tab.spec == nullptr) {
 				return fail(GAS_ERR_NO_HRTF);
 			}
 		}
-		if (buses) { // what gas_process_block_buses rejects beyond that: neither of its two forms (every source 3D mix; every source a non-empty chain, one pair)
-			bool all_mix = true, all_fx = n > 0;
-			for (uint32_t i = 0; i < n; i++) {
-				const SlotInfo &si = c->slots[slots[i]];
-				all_mix = all_mix && si.kind == GAS_KIND_3D_MIX;
-				all_fx = all_fx && si.kind == GAS_KIND_EFFECT && si.chain_sig != 0;
-			}
-			if (!all_mix && !(all_fx && C == 1)) {
-				return fail(GAS_ERR_UNSUPPORTED_CHAIN);
-			}
+		if (buses && bus_list_form(c, slots, n) == BUS_LIST_NEITHER) {
+			return fail(GAS_ERR_UNSUPPORTED_CHAIN); // process_block_buses would, after the cursors have moved
 		}
 		c->stream_last_buses = buses;
 		c->stream_bus_staged = false;
@@ -3540,11 +3569,10 @@ static int process_block_streams_common(gas_ctx *c, const uint32_t *slots, uint3
 	gas_audio_frame *d_out = out;
 	float *d_pk = peaks;
 	if (mem == GAS_MEM_HOST) {
-		if (buses && alloc_once(c, c->d_bus_out, (size_t)GAS_MAX_BUSES * C * F) != hipSuccess) {
-			return fail(GAS_ERR_OUT_OF_MEMORY);
+		const int rcs = stage_host(c, nullptr, n, buses, d_out, d_pk);
+		if (rcs != GAS_OK) {
+			return fail(rcs);
 		}
-		d_out = buses ? c->d_bus_out : c->d_out;
-		d_pk = c->d_peaks;
 	}
 	int rc = GAS_OK;
 	if (buses) {
@@ -3593,21 +3621,13 @@ int gas_source_feed_rows(gas_ctx *c, const uint32_t *slots, const void *rows, in
 	if (frames != F) {
 		return GAS_ERR_FRAME_COUNT;
 	}
-	{ // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
-		const int rcd = flush_deferred(c);
-		if (rcd != GAS_OK) {
-			return rcd;
-		}
-	}
+	GAS_TRY(flush_deferred(c)); // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
 	// everything is checked before anything is taken
-	if (++c->stamp_gen == 0) {
-		std::fill(c->stamp.begin(), c->stamp.end(), 0u);
-		c->stamp_gen = 1;
-	}
+	c->stamp.next();
 	{
 		std::lock_guard<std::mutex> alloc_lk(c->alloc_mu); // pending_free is set by gas_source_free on any thread
 		for (uint32_t i = 0; i < n; i++) {
-			if (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used || c->slots[slots[i]].pending_free) {
+			if (!live(c, slots[i]) || c->slots[slots[i]].pending_free) {
 				return GAS_ERR_BAD_SLOT;
 			}
 		}
@@ -3616,10 +3636,9 @@ int gas_source_feed_rows(gas_ctx *c, const uint32_t *slots, const void *rows, in
 		if (c->h_cursors[slots[i]].pcm) {
 			return GAS_ERR_INVALID_ARGUMENT; // bound to a stream: the sampler supplies its windows
 		}
-		if (c->stamp[slots[i]] == c->stamp_gen) {
+		if (c->stamp.seen(slots[i])) {
 			return GAS_ERR_INVALID_ARGUMENT; // one playback twice in a call
 		}
-		c->stamp[slots[i]] = c->stamp_gen;
 	}
 	if (n == 0) {
 		return GAS_OK;
@@ -3799,20 +3818,11 @@ static int process_block(gas_ctx *c, const RowSource &src, const uint32_t *slots
 	gas_audio_frame *d_out = out;
 	float *d_peaks = peaks ? peaks : c->d_peaks;
 	if (mem == GAS_MEM_HOST) {
-		const size_t need = (size_t)n * F;
-		if (ensure_src(c, need) != hipSuccess) {
-			return fail(GAS_ERR_OUT_OF_MEMORY);
-		}
-		if (n > 0) {
-			hipError_t e = hipMemcpyAsync(c->d_src, src.rows, need * sizeof(gas_audio_frame), hipMemcpyHostToDevice, c->stream);
-			if (e != hipSuccess) {
-				c->last_err = hipGetErrorString(e);
-				return fail(GAS_ERR_DEVICE);
-			}
+		rc = stage_host(c, src.rows, n, false, d_out, d_peaks);
+		if (rc != GAS_OK) {
+			return fail(rc);
 		}
 		d_src.rows = c->d_src;
-		d_out = c->d_out;
-		d_peaks = c->d_peaks;
 	}
 	const gas_params *fresh = nullptr; // device-published rows this callback's HRTF launch reads itself
 	if (c->pending_params) {
@@ -3906,12 +3916,7 @@ static int process_block_buses(gas_ctx *c, const RowSource &src, const uint32_t 
 	if (n > 0 && !slots && (c->cached_n != n || c->bus_form_cached == 0 || c->bus_form_groups_gen != c->groups_gen || !c->pending_free.empty())) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
-	{ // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
-		const int rcd = flush_deferred(c);
-		if (rcd != GAS_OK) {
-			return rcd;
-		}
-	}
+	GAS_TRY(flush_deferred(c)); // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
 	const uint32_t F = c->cfg.frames, C = c->cfg.channel_count;
 	const size_t out_bytes = (size_t)n_buses * C * F * sizeof(gas_audio_frame);
 	const auto fail = [&](int code) { return fail_out(code, mem, out, out_bytes); };
@@ -3928,28 +3933,16 @@ static int process_block_buses(gas_ctx *c, const RowSource &src, const uint32_t 
 	apply_pending_frees(c);
 	// Two forms: every source GAS_KIND_3D_MIX (the mix-channel buses of AudioSpatializer3D, fused in the biquad
 	// kernels), or every source an effect chain (run staged: per-source rows, then mixed per bus) on a one-pair context.
-	const bool reuse = n > 0 && !slots;
-	bool all_mix = reuse ? c->bus_form_cached == 1 : true, all_fx = reuse ? c->bus_form_cached == 2 : n > 0;
-	for (uint32_t i = 0; i < n && slots; i++) {
-		if (slots[i] < c->cfg.max_sources && c->slots[slots[i]].used) {
-			const SlotInfo &si = c->slots[slots[i]];
-			all_mix = all_mix && si.kind == GAS_KIND_3D_MIX;
-			all_fx = all_fx && si.kind == GAS_KIND_EFFECT && si.chain_sig != 0;
-		}
-	}
+	const bool reuse = n > 0 && !slots; // the cached form is 1 (3D mix) or 2 (fused [HRTF]) then
+	const BusList form = reuse ? (c->bus_form_cached == 1 ? BUS_LIST_3D_MIX : BUS_LIST_PLAIN_HRTF) : bus_list_form(c, slots, n);
+	const bool all_mix = form == BUS_LIST_3D_MIX;
 	// [HRTF] sources onto one or two buses have a fused form (k_hrtf_uni<BUS2>: the second bus's spectra sums in LDS)
-	bool all_plain_hrtf = all_fx;
-	for (uint32_t i = 0; i < n && slots && all_plain_hrtf; i++) {
-		if (slots[i] < c->cfg.max_sources && c->slots[slots[i]].used) {
-			all_plain_hrtf = c->slots[slots[i]].group == G_FX_HRTF;
-		}
-	}
 	// (three to six buses: one fused launch per pair of buses, the state committed by the last)
-	const bool fused_hrtf = !all_mix && all_plain_hrtf && C == 1 && uni_ok(c) && gas_hrtf_uni_waves() == 8;
+	const bool fused_hrtf = form == BUS_LIST_PLAIN_HRTF && uni_ok(c) && gas_hrtf_uni_waves() == 8;
 	if (src.fused() && !(fused_hrtf && mem == GAS_MEM_DEVICE)) {
 		return fail(GAS_ERR_INVALID_ARGUMENT); // gas_process_block_streams_buses hands over no rows: only the fused form can sample
 	}
-	const bool staged = !all_mix && all_fx && C == 1 && !fused_hrtf;
+	const bool staged = (form == BUS_LIST_CHAINS || form == BUS_LIST_PLAIN_HRTF) && !fused_hrtf;
 	if (reuse && staged) {
 		return fail(GAS_ERR_INVALID_ARGUMENT); // the staged form regroups: it needs the list
 	}
@@ -4006,25 +3999,12 @@ static int process_block_buses(gas_ctx *c, const RowSource &src, const uint32_t 
 		gas_audio_frame *d_out = out;
 		float *d_peaks = peaks ? peaks : c->d_peaks;
 		if (mem == GAS_MEM_HOST) {
-			const size_t rows = (size_t)n * F;
-			GAS_HIP(c, ensure_src(c, rows));
-			if (n > 0) {
-				GAS_HIP(c, hipMemcpyAsync(c->d_src, src.rows, rows * sizeof(gas_audio_frame), hipMemcpyHostToDevice, c->stream));
-			}
-			GAS_HIP(c, alloc_once(c, c->d_bus_out, (size_t)GAS_MAX_BUSES * C * F));
+			GAS_TRY(stage_host(c, src.rows, n, true, d_out, d_peaks));
 			d_src.rows = c->d_src;
-			d_out = c->d_bus_out;
-			d_peaks = c->d_peaks;
 		}
 		if (fused_hrtf && n > 0) {
 			// bus b's partial rows: [b * P, (b + 1) * P); one launch per pair of buses, the last one commits the state
-			gas_hrtf_uni_launch lu{ hrtf_common(c) };
-			lu.g = own_hrtf_group(c, d_src.rows, n, d_peaks);
-			lu.peak_bits = c->uni_peak_any && !c->uni_peak_all ? c->d_peak_bits : nullptr;
-			lu.peak_all = c->uni_peak_all;
-			lu.partials = c->d_bus_partials;
-			lu.cursors = d_src.cursors;
-			lu.feed = d_src.feed;
+			gas_hrtf_uni_launch lu = plain_uni_launch(c, own_hrtf_group(c, d_src.rows, n, d_peaks), d_src, c->d_bus_partials, 0);
 			lu.routes = c->d_routes;
 			lu.bus_rows = P;
 			const uint32_t passes = (n_buses + 1) / 2;
@@ -4076,17 +4056,12 @@ static int process_one(gas_ctx *c, uint32_t slot, int channel, bool mix_channel,
 	if (!c || !out || !src) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
-	{ // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
-		const int rcd = flush_deferred(c);
-		if (rcd != GAS_OK) {
-			return rcd;
-		}
-	}
+	GAS_TRY(flush_deferred(c)); // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
 	const uint32_t F = c->cfg.frames;
 	if (frame_count < 0 || (uint32_t)frame_count != F) {
 		return GAS_ERR_FRAME_COUNT;
 	}
-	if (slot >= c->cfg.max_sources || !c->slots[slot].used) {
+	if (!live(c, slot)) {
 		return GAS_ERR_BAD_SLOT;
 	}
 	const SlotInfo &si = c->slots[slot];
@@ -4127,9 +4102,10 @@ static int process_one(gas_ctx *c, uint32_t slot, int channel, bool mix_channel,
 	if (rc != GAS_OK) {
 		return rc;
 	}
-	GAS_HIP(c, ensure_src(c, F));
+	gas_audio_frame *d_out = nullptr;
+	float *d_peaks = nullptr;
+	GAS_TRY(stage_host(c, src, 1, false, d_out, d_peaks));
 	GAS_HIP(c, hipMemcpyAsync(c->d_one_slot, &slot, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-	GAS_HIP(c, hipMemcpyAsync(c->d_src, src, (size_t)F * sizeof(gas_audio_frame), hipMemcpyHostToDevice, c->stream));
 	std::vector<ChainRange> one_range;
 	if (gt == G_FX_GENERIC) {
 		ChainRange r;
@@ -4146,15 +4122,12 @@ static int process_one(gas_ctx *c, uint32_t slot, int channel, bool mix_channel,
 	a.groups = groups;
 	a.ranges = &one_range;
 	a.n_total = 1;
-	a.out = c->d_out;
-	a.peaks = c->d_peaks;
+	a.out = d_out;
+	a.peaks = d_peaks;
 	a.channel_begin = mix_channel ? (uint32_t)channel : 0;
 	a.force_mode = force_mode;
-	rc = run_groups(c, a);
-	if (rc != GAS_OK) {
-		return rc;
-	}
-	GAS_HIP(c, copy_back(c, out, c->d_out, (size_t)F * sizeof(gas_audio_frame), nullptr, 0));
+	GAS_TRY(run_groups(c, a));
+	GAS_HIP(c, copy_back(c, out, d_out, (size_t)F * sizeof(gas_audio_frame), nullptr, 0));
 	return GAS_OK;
 }
 

@@ -10,7 +10,8 @@ pytestmark = pytest.mark.gpu
 
 
 def _render(gas, flags, n, F, T, events, dirs=48, depth=None):
-    """events: {t: [names]} applied before callback t: 'dev_publish', 'host_publish', 'host_call', 'relist', 'join'."""
+    """events: {t: [names]} applied before callback t: 'dev_publish', 'host_publish', 'host_call', 'relist', 'join',
+    'depth:N' (set_batch_depth(N))."""
     import torch
 
     from godot_audio_spatializer_amd import synth
@@ -34,6 +35,9 @@ def _render(gas, flags, n, F, T, events, dirs=48, depth=None):
     for t in range(T):
         ev = events.get(t, ())
         src = synth.draw_sources(rng, n, F)
+        for name in ev:
+            if name.startswith("depth:"):
+                ctx.set_batch_depth(int(name[len("depth:"):]))
         if "host_publish" in ev:
             ctx.params_publish_batch(slots[: n // 2], synth.draw_params(rng, n // 2, dirs=dirs, frames=F))
         if "dev_publish" in ev and t == 0:  # the device form addresses the previous callback's list: none yet
@@ -82,6 +86,8 @@ CASES = {
     "f256_hist_through_memory": dict(n=10000, F=256, T=5, events={1: ["dev_publish"]}),
     "two_device_publishes_in_a_row": dict(n=2048, F=512, T=7, events={2: ["dev_publish", "dev_publish"], 3: ["dev_publish"], 5: ["dev_publish", "dev_publish"]}),
     "long_run": dict(n=2048, F=512, T=21, events={t: ["dev_publish"] for t in range(0, 21, 2)}),
+    # fewer blocks in a launch than sums pending: the sums beyond its block count are reduced at once (depth 3: two blocks, three sums)
+    "depth_drops_with_sums_pending": dict(n=2048, F=128, T=22, events={**{t: ["dev_publish"] for t in range(0, 22, 2)}, 17: ["depth:2"]}),
     "long_run_with_breaks": dict(n=2200, F=512, T=23, events={3: ["dev_publish"], 5: ["host_publish"], 9: ["join"], 10: ["dev_publish"], 13: ["relist"], 14: ["dev_publish"], 19: ["host_call"]}),
 }
 

@@ -71,6 +71,27 @@ int main(void) {
 	rc |= gas_process_block(ctx, &src[0][0], slots, 2, F, out, &peaks[0][0], GAS_MEM_HOST);
 	printf("gas_process_block: %s; out[100] = (%f, %f); peaks pan (%f, %f) hrtf (%f, %f)\n", gas_strerror(rc), out[100].left, out[100].right, peaks[0][0], peaks[0][1], peaks[1][0], peaks[1][1]);
 
+	/* a convolution reverb on that mix: reserve the pool (main thread), load an impulse response, create an instance,
+	 * then one gas_conv_process per callback.  With GAS_MEM_DEVICE `in` would be a bus of a gas_process_block_buses `out`. */
+	{
+		static float ir[2][3 * F]; /* a direct tap and one echo per ear */
+		static gas_audio_frame wet[F];
+		uint32_t ir_id = 0, conv = 0;
+		ir[0][0] = 1.0f;
+		ir[0][F + 100] = 0.5f;
+		ir[1][0] = 1.0f;
+		ir[1][2 * F + 7] = 0.25f;
+		rc |= gas_ctx_reserve_conv(ctx, 1, 3 * F);
+		rc |= gas_conv_ir_load(ctx, &ir[0][0], 2, 3 * F, &ir_id);
+		rc |= gas_conv_create(ctx, ir_id, &conv);
+		rc |= gas_conv_set_levels(ctx, conv, 0.0f, 1.0f); /* the defaults: a send bus carries the wet signal alone */
+		rc |= gas_conv_process(ctx, &conv, 1, out, wet, F, GAS_MEM_HOST);
+		printf("gas_conv_process: %s; wet[100] = (%f, %f)\n", gas_strerror(rc), wet[100].left, wet[100].right);
+		rc |= gas_conv_destroy(ctx, conv);
+		rc |= gas_conv_ir_free(ctx, ir_id);
+		rc |= gas_ctx_reserve_conv(ctx, 0, 0);
+	}
+
 	gas_host *host = NULL;
 	rc |= gas_host_create(ctx, GAS_KIND_EFFECT, chain, 1, &host);
 	uint32_t id = 0;

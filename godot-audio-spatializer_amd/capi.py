@@ -481,6 +481,15 @@ EXPORTS = [
     "gas_process_block",
     "gas_bus_routes_publish",
     "gas_process_block_buses",
+    "gas_ctx_reserve_conv",
+    "gas_conv_ir_load",
+    "gas_conv_ir_free",
+    "gas_conv_create",
+    "gas_conv_destroy",
+    "gas_conv_reset",
+    "gas_conv_set_ir",
+    "gas_conv_set_levels",
+    "gas_conv_process",
     "gas_process_frames_1",
     "gas_mix_channel_1",
     "gas_profile_enable",
@@ -581,6 +590,15 @@ def load_library():
     L.gas_process_block.argtypes = [vp, vp, vp, u32, u32, vp, vp, i32]
     L.gas_bus_routes_publish.argtypes = [vp, vp, vp, u32]
     L.gas_process_block_buses.argtypes = [vp, vp, vp, u32, u32, vp, u32, vp, i32]
+    L.gas_ctx_reserve_conv.argtypes = [vp, u32, u32]
+    L.gas_conv_ir_load.argtypes = [vp, vp, u32, u32, C.POINTER(u32)]
+    L.gas_conv_ir_free.argtypes = [vp, u32]
+    L.gas_conv_create.argtypes = [vp, u32, C.POINTER(u32)]
+    L.gas_conv_destroy.argtypes = [vp, u32]
+    L.gas_conv_reset.argtypes = [vp, u32]
+    L.gas_conv_set_ir.argtypes = [vp, u32, u32]
+    L.gas_conv_set_levels.argtypes = [vp, u32, C.c_float, C.c_float]
+    L.gas_conv_process.argtypes = [vp, vp, u32, vp, vp, u32, i32]
     L.gas_process_frames_1.argtypes = [vp, u32, vp, vp, i32]
     L.gas_mix_channel_1.argtypes = [vp, u32, i32, vp, vp, i32]
     L.gas_profile_enable.argtypes = [vp, i32]
@@ -974,6 +992,64 @@ class SpatializerContext:
         rc = self.lib.gas_process_block_buses(self.h, _np_ptr(src) if n else None, _np_ptr(s) if n else None, n, self.frames, _np_ptr(out), n_buses, _np_ptr(peaks), MEM_HOST)
         self._check(rc, "gas_process_block_buses")
         return out, peaks[:n]
+
+    # ---- bus convolvers (gas_conv_*) ----
+    def reserve_conv(self, convolvers, max_ir_taps):
+        """Size the convolver pool (main thread): `convolvers` instances for IRs of up to max_ir_taps taps; (0, 0) releases."""
+        self._check(self.lib.gas_ctx_reserve_conv(self.h, int(convolvers), int(max_ir_taps)), "gas_ctx_reserve_conv")
+
+    def conv_ir_load(self, ir):
+        """ir float32 [taps] or [channels][taps], channels 1 or 2 -> IR id."""
+        h = np.ascontiguousarray(np.atleast_2d(np.asarray(ir, dtype=np.float32)))
+        assert h.ndim == 2
+        out = C.c_uint32()
+        self._check(self.lib.gas_conv_ir_load(self.h, _np_ptr(h), h.shape[0], h.shape[1], C.byref(out)), "gas_conv_ir_load")
+        return out.value
+
+    def conv_ir_free(self, ir):
+        self._check(self.lib.gas_conv_ir_free(self.h, int(ir)), "gas_conv_ir_free")
+
+    def conv_create(self, ir):
+        out = C.c_uint32()
+        self._check(self.lib.gas_conv_create(self.h, int(ir), C.byref(out)), "gas_conv_create")
+        return out.value
+
+    def conv_destroy(self, conv):
+        self._check(self.lib.gas_conv_destroy(self.h, int(conv)), "gas_conv_destroy")
+
+    def conv_reset(self, conv):
+        self._check(self.lib.gas_conv_reset(self.h, int(conv)), "gas_conv_reset")
+
+    def conv_set_ir(self, conv, ir):
+        self._check(self.lib.gas_conv_set_ir(self.h, int(conv), int(ir)), "gas_conv_set_ir")
+
+    def conv_set_levels(self, conv, dry, wet):
+        self._check(self.lib.gas_conv_set_levels(self.h, int(conv), float(dry), float(wet)), "gas_conv_set_levels")
+
+    def conv_process(self, convs, x, out=None):
+        """Instances convs [n] over x [n][F][2].  A host array gives a new host array (the call returns when it is
+        complete); a torch device tensor is only enqueued on the context's stream and gives `out` (a device tensor of
+        x's shape; default: x itself, in place)."""
+        s = np.ascontiguousarray(convs, dtype=np.uint32)
+        n = len(s)
+        if isinstance(x, np.ndarray) or not hasattr(x, "data_ptr"):
+            a = np.ascontiguousarray(x, dtype=np.float32)
+            assert a.ndim == 3 and a.shape[0] == n and a.shape[2] == 2
+            res = np.full_like(a, np.nan)
+            self._check(self.lib.gas_conv_process(self.h, _np_ptr(s), n, _np_ptr(a), _np_ptr(res), a.shape[1], MEM_HOST), "gas_conv_process")
+            return res
+        out = x if out is None else out
+        assert x.is_contiguous() and out.is_contiguous() and tuple(x.shape) == tuple(out.shape) and x.shape[0] == n and x.shape[2] == 2
+        self._check(self.lib.gas_conv_process(self.h, _np_ptr(s), n, C.c_void_p(x.data_ptr()), C.c_void_p(out.data_ptr()), x.shape[1], MEM_DEVICE), "gas_conv_process")
+        return out
+
+    def conv_process_raw(self, convs, n, in_ptr, out_ptr, frames, mem):
+        """Raw pointers (device or host); returns the status."""
+        sp = None
+        if convs is not None:
+            s = np.ascontiguousarray(convs, dtype=np.uint32)
+            sp = _np_ptr(s)
+        return self.lib.gas_conv_process(self.h, sp, int(n), C.c_void_p(in_ptr) if in_ptr else None, C.c_void_p(out_ptr) if out_ptr else None, int(frames), mem)
 
     def process_block_raw(self, src_ptr, slots, n, frames, out_ptr, peaks_ptr, mem):
         """Raw pointers (device or host). slots: numpy uint32 array or None (reuse the previous list)."""

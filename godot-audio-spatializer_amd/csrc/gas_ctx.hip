@@ -313,6 +313,29 @@ struct gas_ctx {
 	size_t bus_partial_floats = 0;
 	gas_audio_frame *d_bus_out = nullptr; // [GAS_MAX_BUSES][C][F] staging for host-memory calls
 
+	// bus convolvers (gas_conv_*, NEW): pools, tables and staging are gas_ctx_reserve_conv's, an IR's spectra
+	// gas_conv_ir_load's; the instance calls and gas_conv_process allocate nothing.  Audio-thread state, no lock: the
+	// reservation and the IR calls never run concurrently with a callback.
+	struct ConvIr {
+		float2 *H = nullptr; // [channels][k_ir][GAS_CONV_BINS]; null: a free id
+		uint32_t channels = 0, k_ir = 0;
+		uint32_t users = 0; // instances naming it
+	};
+	struct ConvInst {
+		bool used = false;
+		uint32_t ir = 0;
+		uint32_t pos = 0; // ring position of the newest spectrum
+		float dry = 0.0f, wet = 1.0f;
+	};
+	uint32_t conv_count = 0, conv_max_taps = 0; // the reservation; 0: none
+	gas_conv_pool conv_pool{};
+	float2 *conv_w1024 = nullptr;
+	std::vector<ConvInst> conv;
+	std::vector<uint32_t> conv_free; // pop_back hands out 0, 1, 2, ...
+	std::vector<ConvIr> conv_irs;
+	gas_audio_frame *conv_h_in = nullptr, *conv_h_out = nullptr; // pinned [GAS_MAX_CONVOLVERS][frames], host-memory calls
+	gas_audio_frame *conv_d_in = nullptr, *conv_d_out = nullptr;
+
 	// gas_bandwidth_probe: read arena (larger than the Infinity Cache, swept in rotation) and write target
 	void *d_probe_rd = nullptr, *d_probe_wr = nullptr;
 	size_t probe_rd_bytes = 0, probe_wr_bytes = 0;
@@ -4293,6 +4316,324 @@ int gas_profile_read(gas_ctx *c, gas_profile *out, int reset) {
 	if (reset) {
 		c->prof_launches = 0;
 		c->prof_ms = 0.0;
+	}
+	return GAS_OK;
+}
+
+// ---- bus convolvers (NEW; k_conv.hip) ---------------------------------------------------------------------------------
+
+#define GAS_CONV_MAX_IR_TAPS (1u << 20)
+
+static void conv_release(gas_ctx *c) {
+	c->mem.drop(c->conv_pool.ring);
+	c->mem.drop(c->conv_pool.prev);
+	c->mem.drop(c->conv_pool.ypart);
+	c->mem.drop(c->conv_w1024);
+	c->mem.drop(c->conv_h_in);
+	c->mem.drop(c->conv_h_out);
+	c->mem.drop(c->conv_d_in);
+	c->mem.drop(c->conv_d_out);
+	c->conv_pool = gas_conv_pool{};
+	c->conv_count = 0;
+	c->conv_max_taps = 0;
+	c->conv.clear();
+	c->conv_free.clear();
+	c->conv_irs.clear();
+}
+
+// The instance's ring and previous block become zeros in stream order: x[t] = 0 for every earlier t.
+static hipError_t conv_zero(gas_ctx *c, uint32_t conv) {
+	const size_t ring = (size_t)2 * c->conv_pool.K * GAS_CONV_BINS;
+	const hipError_t e = hipMemsetAsync(c->conv_pool.ring + conv * ring, 0, ring * sizeof(float2), c->stream);
+	return e != hipSuccess ? e : hipMemsetAsync(c->conv_pool.prev + (size_t)conv * 2 * 512, 0, 2 * 512 * sizeof(float), c->stream);
+}
+
+static bool conv_live(const gas_ctx *c, uint32_t conv) {
+	return conv < c->conv_count && c->conv[conv].used;
+}
+
+static bool conv_ir_live(const gas_ctx *c, uint32_t ir) {
+	return ir < c->conv_irs.size() && c->conv_irs[ir].H != nullptr;
+}
+
+int gas_ctx_reserve_conv(gas_ctx *c, uint32_t convolvers, uint32_t max_ir_taps) {
+	if (!c || convolvers > GAS_MAX_CONVOLVERS || max_ir_taps > GAS_CONV_MAX_IR_TAPS || (convolvers == 0) != (max_ir_taps == 0)) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	for (const auto &k : c->conv) {
+		if (k.used) {
+			return GAS_ERR_INVALID_ARGUMENT;
+		}
+	}
+	for (const auto &ir : c->conv_irs) {
+		if (ir.H) {
+			return GAS_ERR_INVALID_ARGUMENT;
+		}
+	}
+	GAS_TRY(flush_deferred(c));
+	GAS_HIP(c, hipSetDevice(c->cfg.device));
+	GAS_HIP(c, hipStreamSynchronize(c->stream));
+	conv_release(c);
+	if (convolvers == 0) {
+		return GAS_OK;
+	}
+	const uint32_t F = c->cfg.frames;
+	const uint32_t K = (max_ir_taps + F - 1) / F;
+	const int rc = [&]() -> int {
+		gas_conv_pool &p = c->conv_pool;
+		p.K = K;
+		p.max_chunks = gas_conv_max_chunks(K);
+		GAS_HIP(c, c->mem.alloc(p.ring, (size_t)convolvers * 2 * K * GAS_CONV_BINS));
+		GAS_HIP(c, c->mem.alloc(p.prev, (size_t)convolvers * 2 * 512));
+		GAS_HIP(c, c->mem.alloc(p.ypart, (size_t)GAS_MAX_CONVOLVERS * 2 * p.max_chunks * GAS_CONV_BINS));
+		GAS_HIP(c, c->mem.alloc(c->conv_w1024, 512));
+		const size_t stage = (size_t)GAS_MAX_CONVOLVERS * F;
+		GAS_HIP(c, c->mem.alloc(c->conv_h_in, stage, Mem::PINNED));
+		GAS_HIP(c, c->mem.alloc(c->conv_h_out, stage, Mem::PINNED));
+		GAS_HIP(c, c->mem.alloc(c->conv_d_in, stage));
+		GAS_HIP(c, c->mem.alloc(c->conv_d_out, stage));
+		float2 w[512];
+		gas_make_w1024(w);
+		GAS_HIP(c, hipMemcpyAsync(c->conv_w1024, w, sizeof(w), hipMemcpyHostToDevice, c->stream));
+		GAS_HIP(c, hipStreamSynchronize(c->stream));
+		p.w1024 = c->conv_w1024;
+		return GAS_OK;
+	}();
+	if (rc != GAS_OK) {
+		conv_release(c);
+		return rc;
+	}
+	c->conv_count = convolvers;
+	c->conv_max_taps = max_ir_taps;
+	c->conv.assign(convolvers, gas_ctx::ConvInst{});
+	c->conv_free.reserve(convolvers);
+	for (uint32_t s = convolvers; s-- > 0;) {
+		c->conv_free.push_back(s);
+	}
+	return GAS_OK;
+}
+
+int gas_conv_ir_load(gas_ctx *c, const float *ir, uint32_t channels, uint32_t taps, uint32_t *out_ir) {
+	if (!c || !ir || !out_ir || (channels != 1 && channels != 2) || taps == 0) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (c->conv_count == 0) {
+		return GAS_ERR_UNSUPPORTED_CHAIN;
+	}
+	if (taps > c->conv_max_taps) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	const size_t floats = (size_t)channels * taps;
+	for (size_t i = 0; i < floats; i++) {
+		if (!std::isfinite(ir[i])) {
+			return GAS_ERR_INVALID_ARGUMENT;
+		}
+	}
+	GAS_TRY(flush_deferred(c));
+	GAS_HIP(c, hipSetDevice(c->cfg.device));
+	const uint32_t F = c->cfg.frames;
+	gas_ctx::ConvIr rec;
+	rec.channels = channels;
+	rec.k_ir = (taps + F - 1) / F;
+	Mem tmp; // frees d_ir on every way out
+	float *d_ir = nullptr;
+	GAS_HIP(c, tmp.alloc(d_ir, floats));
+	GAS_HIP(c, hipMemcpyAsync(d_ir, ir, floats * sizeof(float), hipMemcpyHostToDevice, c->stream));
+	GAS_HIP(c, c->mem.alloc(rec.H, (size_t)channels * rec.k_ir * GAS_CONV_BINS));
+	hipError_t e = gas_launch_conv_ir(c->stream, d_ir, channels, taps, F, c->d_tw, c->conv_pool.w1024, rec.H);
+	e = e != hipSuccess ? e : hipStreamSynchronize(c->stream);
+	if (e != hipSuccess) {
+		c->mem.drop(rec.H);
+		GAS_HIP(c, e);
+	}
+	uint32_t id = 0;
+	while (id < c->conv_irs.size() && c->conv_irs[id].H) {
+		id++;
+	}
+	if (id == c->conv_irs.size()) {
+		c->conv_irs.push_back(rec);
+	} else {
+		c->conv_irs[id] = rec;
+	}
+	*out_ir = id;
+	return GAS_OK;
+}
+
+int gas_conv_ir_free(gas_ctx *c, uint32_t ir) {
+	if (!c) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (!conv_ir_live(c, ir)) {
+		return GAS_ERR_BAD_SLOT;
+	}
+	if (c->conv_irs[ir].users != 0) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	GAS_TRY(flush_deferred(c));
+	GAS_HIP(c, hipSetDevice(c->cfg.device));
+	GAS_HIP(c, hipStreamSynchronize(c->stream)); // calls still queued may read the spectra
+	c->mem.drop(c->conv_irs[ir].H);
+	c->conv_irs[ir] = gas_ctx::ConvIr{};
+	return GAS_OK;
+}
+
+int gas_conv_create(gas_ctx *c, uint32_t ir, uint32_t *out_conv) {
+	if (!c || !out_conv) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (c->conv_count == 0) {
+		return GAS_ERR_UNSUPPORTED_CHAIN;
+	}
+	if (!conv_ir_live(c, ir)) {
+		return GAS_ERR_BAD_SLOT;
+	}
+	if (c->conv_free.empty()) {
+		return GAS_ERR_OUT_OF_SLOTS;
+	}
+	const uint32_t id = c->conv_free.back();
+	GAS_HIP(c, hipSetDevice(c->cfg.device));
+	GAS_HIP(c, conv_zero(c, id)); // zeroed when it changes hands
+	c->conv_free.pop_back();
+	gas_ctx::ConvInst &k = c->conv[id];
+	k = gas_ctx::ConvInst{};
+	k.used = true;
+	k.ir = ir;
+	k.pos = c->conv_pool.K - 1;
+	c->conv_irs[ir].users++;
+	*out_conv = id;
+	return GAS_OK;
+}
+
+int gas_conv_destroy(gas_ctx *c, uint32_t conv) {
+	if (!c) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (!conv_live(c, conv)) {
+		return GAS_ERR_BAD_SLOT;
+	}
+	c->conv_irs[c->conv[conv].ir].users--;
+	c->conv[conv].used = false;
+	c->conv_free.push_back(conv);
+	return GAS_OK;
+}
+
+int gas_conv_reset(gas_ctx *c, uint32_t conv) {
+	if (!c) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (!conv_live(c, conv)) {
+		return GAS_ERR_BAD_SLOT;
+	}
+	GAS_HIP(c, hipSetDevice(c->cfg.device));
+	GAS_HIP(c, conv_zero(c, conv));
+	c->conv[conv].pos = c->conv_pool.K - 1;
+	return GAS_OK;
+}
+
+int gas_conv_set_ir(gas_ctx *c, uint32_t conv, uint32_t ir) {
+	if (!c) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (!conv_live(c, conv) || !conv_ir_live(c, ir)) {
+		return GAS_ERR_BAD_SLOT;
+	}
+	c->conv_irs[c->conv[conv].ir].users--;
+	c->conv[conv].ir = ir;
+	c->conv_irs[ir].users++;
+	return GAS_OK;
+}
+
+int gas_conv_set_levels(gas_ctx *c, uint32_t conv, float dry, float wet) {
+	if (!c || !std::isfinite(dry) || !std::isfinite(wet)) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (!conv_live(c, conv)) {
+		return GAS_ERR_BAD_SLOT;
+	}
+	c->conv[conv].dry = dry;
+	c->conv[conv].wet = wet;
+	return GAS_OK;
+}
+
+int gas_conv_process(gas_ctx *c, const uint32_t *convs, uint32_t n, const gas_audio_frame *in, gas_audio_frame *out, uint32_t frames, int mem) {
+	if (!c || (mem != GAS_MEM_HOST && mem != GAS_MEM_DEVICE) || (n > 0 && (!convs || !in || !out))) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	const uint32_t F = c->cfg.frames;
+	// a refused host-memory call leaves zeros in `out` ([n][frames] as the caller sized it, as far as that is legal)
+	const size_t zero_bytes = out ? (size_t)(n < GAS_MAX_CONVOLVERS ? n : GAS_MAX_CONVOLVERS) * (frames < 512 ? frames : 512) * sizeof(gas_audio_frame) : 0;
+	const auto fail = [&](int code) { return zero_bytes ? fail_out(code, mem, out, zero_bytes) : code; };
+	if (n > GAS_MAX_CONVOLVERS) {
+		return fail(GAS_ERR_INVALID_ARGUMENT);
+	}
+	if (frames != F) {
+		return fail(GAS_ERR_FRAME_COUNT);
+	}
+	if (n == 0) {
+		return GAS_OK;
+	}
+	uint32_t seen = 0;
+	for (uint32_t i = 0; i < n; i++) {
+		if (!conv_live(c, convs[i])) {
+			return fail(GAS_ERR_BAD_SLOT);
+		}
+		if (seen & (1u << convs[i])) {
+			return fail(GAS_ERR_INVALID_ARGUMENT); // an instance named twice
+		}
+		seen |= 1u << convs[i];
+	}
+	if (mem == GAS_MEM_DEVICE && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) != 0) {
+		return fail(GAS_ERR_INVALID_ARGUMENT); // rows are read and written sixteen bytes at a time
+	}
+	{ // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first (`in` may be one's out)
+		const int rcd = flush_deferred(c);
+		if (rcd != GAS_OK) {
+			return fail(rcd);
+		}
+	}
+	if (hipSetDevice(c->cfg.device) != hipSuccess) {
+		return fail(GAS_ERR_NO_DEVICE);
+	}
+	if (mem == GAS_MEM_DEVICE) {
+		const int rcj = join_outputs(c); // GAS_FLAG_PIPELINED_MIX: `in` may be an earlier callback's out, still a pending sum
+		if (rcj != GAS_OK) {
+			return rcj;
+		}
+	}
+	const uint32_t K = c->conv_pool.K;
+	gas_conv_call call{};
+	for (uint32_t i = 0; i < n; i++) {
+		const gas_ctx::ConvInst &k = c->conv[convs[i]];
+		const gas_ctx::ConvIr &ir = c->conv_irs[k.ir];
+		gas_conv_entry &e = call.e[i];
+		e.H = ir.H;
+		e.slot = convs[i];
+		e.pos = k.pos + 1 == K ? 0 : k.pos + 1;
+		e.k_ir = ir.k_ir;
+		e.stereo = ir.channels == 2 ? 1u : 0u;
+		e.dry = k.dry;
+		e.wet = k.wet;
+	}
+	const size_t bytes = (size_t)n * F * sizeof(gas_audio_frame);
+	const int rc = [&]() -> int {
+		if (mem == GAS_MEM_DEVICE) {
+			GAS_HIP(c, gas_launch_conv(c->stream, call, n, c->conv_pool, c->d_tw, in, out, F));
+			return GAS_OK;
+		}
+		// host memory: the previous host-memory call returned after its copies, so the staging is free
+		std::memcpy(c->conv_h_in, in, bytes);
+		GAS_HIP(c, hipMemcpyAsync(c->conv_d_in, c->conv_h_in, bytes, hipMemcpyHostToDevice, c->stream));
+		GAS_HIP(c, gas_launch_conv(c->stream, call, n, c->conv_pool, c->d_tw, c->conv_d_in, c->conv_d_out, F));
+		GAS_HIP(c, hipMemcpyAsync(c->conv_h_out, c->conv_d_out, bytes, hipMemcpyDeviceToHost, c->stream));
+		GAS_HIP(c, hipStreamSynchronize(c->stream));
+		std::memcpy(out, c->conv_h_out, bytes);
+		return GAS_OK;
+	}();
+	if (rc != GAS_OK) {
+		return fail(rc);
+	}
+	for (uint32_t i = 0; i < n; i++) {
+		c->conv[convs[i]].pos = call.e[i].pos; // only the named instances' time advances
 	}
 	return GAS_OK;
 }

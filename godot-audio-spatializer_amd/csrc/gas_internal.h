@@ -509,6 +509,47 @@ hipError_t gas_launch_rows_accumulate(hipStream_t stream, const gas_group_args &
 hipError_t gas_launch_rows_accumulate_buses(hipStream_t stream, const gas_group_args &g, uint32_t frames, const gas_bus_route *routes, uint32_t n_buses, uint32_t bus_rows, float *partials, uint32_t p_offset); // bus b's partial rows: [b * bus_rows + p_offset + workgroup]
 
 hipError_t gas_launch_hrtf_table(hipStream_t stream, const float *d_hrir, uint32_t dirs, uint32_t taps, const float2 *twiddles, float4 *spec);
+// k_conv.hip: the bus convolvers (gas_conv_*, NEW).  A spectrum is the Hermitian half of a 1024-point real
+// transform: 512 float2, bin k at [k], the real Nyquist bin parked in the (zero) imaginary part of DC.
+#define GAS_CONV_BINS 512
+#define GAS_CONV_MAX_CHUNKS 32
+struct gas_conv_entry { // one named instance of a gas_conv_process call
+	const float2 *H; // its IR's spectra [channels][k_ir][GAS_CONV_BINS], scaled by 1/512
+	uint32_t slot; // instance: ring [slot][ear][K][GAS_CONV_BINS], previous block [slot][ear][512]
+	uint32_t pos; // ring position this block's spectrum goes to
+	uint32_t k_ir; // partitions of the IR, 1 .. K
+	uint32_t stereo; // 1: ear e uses channel e; 0: both use channel 0
+	float dry, wet;
+};
+struct gas_conv_call { // passed by value: a device-memory call only enqueues, so nothing it reads may live in reused staging
+	gas_conv_entry e[GAS_MAX_CONVOLVERS];
+};
+struct gas_conv_pool {
+	float2 *ring = nullptr;
+	float *prev = nullptr;
+	float2 *ypart = nullptr; // [GAS_MAX_CONVOLVERS * 2][max_chunks][GAS_CONV_BINS] partial sums of one call
+	const float2 *w1024 = nullptr; // [512] exp(-2 pi i k / 1024)
+	uint32_t K = 0; // partitions per ring: ceil(max_ir_taps / frames)
+	uint32_t max_chunks = 0; // gas_conv_max_chunks(K)
+};
+// The multiply-accumulate walks an IR's partitions in chunks, one workgroup row per chunk, and the inverse stage adds the
+// chunks' sums in chunk order.  The split depends on the IR's length alone, so an instance's bits do not depend on what
+// else a call names.
+__host__ __device__ inline uint32_t gas_conv_chunk_len(uint32_t k_ir) {
+	const uint32_t per = (k_ir + GAS_CONV_MAX_CHUNKS - 1) / GAS_CONV_MAX_CHUNKS;
+	return per < 16 ? 16 : per;
+}
+__host__ __device__ inline uint32_t gas_conv_chunks(uint32_t k_ir) {
+	const uint32_t len = gas_conv_chunk_len(k_ir);
+	return (k_ir + len - 1) / len;
+}
+__host__ __device__ inline uint32_t gas_conv_max_chunks(uint32_t K) { // the most chunks any IR of at most K partitions has
+	const uint32_t c = (K + 15) / 16;
+	return c < GAS_CONV_MAX_CHUNKS ? c : GAS_CONV_MAX_CHUNKS;
+}
+hipError_t gas_launch_conv(hipStream_t stream, const gas_conv_call &call, uint32_t n, const gas_conv_pool &pool, const float2 *twiddles, const gas_audio_frame *in /* [n][frames] */, gas_audio_frame *out /* [n][frames] */, uint32_t frames);
+hipError_t gas_launch_conv_ir(hipStream_t stream, const float *d_ir /* [channels][taps] */, uint32_t channels, uint32_t taps, uint32_t frames, const float2 *twiddles, const float2 *w1024, float2 *H);
+void gas_make_w1024(float2 *host_w /* [512] */);
 hipError_t gas_launch_hrtf_regrid(hipStream_t stream, const float *d_positions, const float *d_hrir, uint32_t m, uint32_t taps, uint32_t az_steps, uint32_t el_steps, int interpolation, float *d_out /* [az_steps * el_steps][2][GAS_HRTF_TAPS] */);
 void gas_make_twiddles(float2 *host_tw /* [64][16] */);
 

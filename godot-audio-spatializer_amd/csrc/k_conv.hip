@@ -1,0 +1,285 @@
+// k_conv.hip -- the bus convolvers (gas_conv_*): a long impulse response convolved with a bus mix by uniformly
+// partitioned overlap-save, partition length = the callback's F frames.
+//
+// NEW, with no engine counterpart (the reference mixes buses on the CPU and has no convolution); the rule is the one of
+// include/gas_amd.h:   y_e[t] = dry x_e[t] + wet sum_j h_e[j] x_e[t - j].   Checked against tests/conv_ref.py.
+//
+// One 1024-point real transform serves every legal F (2 F <= 1024): the window of block b is
+// [zeros(1024 - 2 F), block b - 1, block b], partition k of the IR sits at the front of its own window, and of the
+// circular product the last F outputs are exact (they reach back F - 1 frames, never across the window's start).
+// A real 1024-point transform is one fft512 (gas_hrtf_wave.h) of z[n] = w[2 n] + i w[2 n + 1] and an untangling pass:
+//   E[k] = (Z[k] + conj Z[512 - k]) / 2,  O[k] = (Z[k] - conj Z[512 - k]) / 2i,  X[k] = E[k] + W1024^k O[k],  X[512] = Re Z[0] - Im Z[0]
+// and back:  Z[k] = E[k] + i O[k]  with  E[k] = (Y[k] + conj Y[512 - k]) / 2,  O[k] = W1024^-k (Y[k] - conj Y[512 - k]) / 2.
+// A spectrum is bins 0 .. 511 as float2 (4 KiB), the real bin 512 parked in bin 0's imaginary part.
+//
+// Three launches per call, all over the call's named instances (gas_conv_call, by value):
+//   k_conv_forward   one wave per (instance, ear): window -> spectrum -> the instance's ring at this block's position;
+//                    this block replaces the previous one (kept per instance and ear next to the ring)
+//   k_conv_mac       Y[bin] = sum_k X_{b-k}[bin] H_k[bin] over the partitions the IR has: 256 threads per (instance, ear,
+//                    chunk of partitions), a thread owning two bins (16-byte loads, sixteen in flight); the bytes that
+//                    matter -- k_ir x 8 KiB per ear -- spread over k_ir / chunk length workgroup rows
+//   k_conv_inverse   one workgroup of two waves per instance (wave = ear): chunk sums added in chunk order, back
+//                    transform, the last F samples, out = dry in + wet y as 16-byte stores (both ears of two frames)
+// Vector stores only, no atomics; every sum has a fixed order, so two runs give the same bits.
+#include "gas_hrtf_wave.h"
+
+#include <cmath>
+
+namespace {
+
+__device__ __forceinline__ void conv_twiddles(const float2 *__restrict__ tw, int lane, float2 (&t1)[8], float2 (&t2)[8]) {
+#pragma unroll
+	for (int k = 0; k < 8; k++) {
+		t1[k] = tw[k * 64 + lane];
+		t2[k] = tw[(8 + k) * 64 + lane];
+	}
+}
+
+// v[j] = z[lane + 64 j] of a packed real window -> dst[lane + 64 j] = scale * X[lane + 64 j]
+__device__ __forceinline__ void conv_spectrum(float2 (&v)[8], const float2 (&t1)[8], const float2 (&t2)[8], float2 *lds, int lane, const float2 *__restrict__ w1024, float scale, float2 *__restrict__ dst) {
+	fft512<false>(v, t1, t2, lds, lane);
+#pragma unroll
+	for (int j = 0; j < 8; j++) {
+		lds[lane + 64 * j] = v[j];
+	}
+	wave_lds_sync();
+#pragma unroll
+	for (int j = 0; j < 8; j++) {
+		const int k = lane + 64 * j;
+		const float2 m = lds[(512 - k) & 511];
+		const float2 w = w1024[k];
+		const float2 e = make_float2(0.5f * (v[j].x + m.x), 0.5f * (v[j].y - m.y));
+		const float2 o = make_float2(0.5f * (v[j].y + m.y), -0.5f * (v[j].x - m.x)); // (Z - conj Zm) / 2i
+		float2 x = cadd(e, cmul(w, o));
+		if (k == 0) {
+			x = make_float2(v[0].x + v[0].y, v[0].x - v[0].y); // bins 0 and 512, both real
+		}
+		dst[k] = make_float2(scale * x.x, scale * x.y);
+	}
+}
+
+__global__ __launch_bounds__(64) void k_conv_forward(gas_conv_call call, gas_conv_pool pool, const float2 *__restrict__ tw, const gas_audio_frame *__restrict__ in, uint32_t F) {
+	__shared__ float2 lds[LDS_F2_HALF];
+	const int lane = threadIdx.x;
+	const uint32_t i = blockIdx.x >> 1, ear = blockIdx.x & 1;
+	const gas_conv_entry en = call.e[i];
+	const int SQ = (int)(F / 128); // a block is SQ registers of 64 sample pairs
+	float2 t1[8], t2[8];
+	conv_twiddles(tw, lane, t1, t2);
+	// Pair q of the previous block and pair q of this one belong to the same lane (registers SQ apart), so the lane that
+	// reads a pair of `prev` is the one that replaces it, in program order.
+	float *prev = pool.prev + (size_t)(en.slot * 2 + ear) * 512;
+	const float4 *row = reinterpret_cast<const float4 *>(in + (size_t)i * F); // two frames: L0 R0 L1 R1
+	float2 v[8];
+#pragma unroll
+	for (int j = 0; j < 8; j++) {
+		const int jj = j - (8 - 2 * SQ);
+		if (jj < 0) {
+			v[j] = make_float2(0.0f, 0.0f);
+		} else if (jj < SQ) {
+			v[j] = *reinterpret_cast<const float2 *>(prev + 2 * (lane + 64 * jj));
+		} else {
+			const int q = lane + 64 * (jj - SQ);
+			const float4 f = row[q];
+			v[j] = ear ? make_float2(f.y, f.w) : make_float2(f.x, f.z);
+			*reinterpret_cast<float2 *>(prev + 2 * q) = v[j];
+		}
+	}
+	float2 *dst = pool.ring + ((size_t)(en.slot * 2 + ear) * pool.K + en.pos) * GAS_CONV_BINS;
+	conv_spectrum(v, t1, t2, lds, lane, pool.w1024, 1.0f, dst);
+}
+
+// IR [channels][taps] -> H[channel][partition][512]: partition k's F taps at the front of a zero window, scaled by
+// 1/512 so that the inverse stage needs no normalisation (k_hrtf_table does the same for the HRIRs).
+__global__ __launch_bounds__(64) void k_conv_ir(const float *__restrict__ ir, uint32_t taps, uint32_t k_ir, uint32_t F, const float2 *__restrict__ tw, const float2 *__restrict__ w1024, float2 *__restrict__ H) {
+	__shared__ float2 lds[LDS_F2_HALF];
+	const int lane = threadIdx.x;
+	const uint32_t ch = blockIdx.x / k_ir, k = blockIdx.x % k_ir;
+	float2 t1[8], t2[8];
+	conv_twiddles(tw, lane, t1, t2);
+	const float *h = ir + (size_t)ch * taps;
+	float2 v[8];
+#pragma unroll
+	for (int j = 0; j < 8; j++) {
+		const uint32_t s = 2u * (uint32_t)(lane + 64 * j); // window index of the pair
+		const uint32_t t = k * F + s; // tap index
+		v[j] = make_float2(s < F && t < taps ? h[t] : 0.0f, s + 1 < F && t + 1 < taps ? h[t + 1] : 0.0f);
+	}
+	conv_spectrum(v, t1, t2, lds, lane, w1024, 1.0f / 512.0f, H + (size_t)blockIdx.x * GAS_CONV_BINS);
+}
+
+// acc += x * h for the two bins of a float4; the first thread's first "bin" is the packed pair of real bins 0 and 512
+__device__ __forceinline__ void conv_mac(float4 &acc, const float4 x, const float4 h, bool packed) {
+	float2 a = make_float2(acc.x, acc.y), b = make_float2(acc.z, acc.w);
+	if (packed) {
+		a.x = __builtin_fmaf(x.x, h.x, a.x);
+		a.y = __builtin_fmaf(x.y, h.y, a.y);
+	} else {
+		cmac_fixed(a, make_float2(x.x, x.y), h.x, h.y);
+	}
+	cmac_fixed(b, make_float2(x.z, x.w), h.z, h.w);
+	acc = make_float4(a.x, a.y, b.x, b.y);
+}
+
+__global__ __launch_bounds__(256) void k_conv_mac(gas_conv_call call, gas_conv_pool pool) {
+	const uint32_t ie = blockIdx.y, ear = ie & 1;
+	const gas_conv_entry en = call.e[ie >> 1];
+	const uint32_t len = gas_conv_chunk_len(en.k_ir);
+	const uint32_t k0 = blockIdx.x * len;
+	if (k0 >= en.k_ir) { // this IR has fewer chunks than the call's longest
+		return;
+	}
+	const uint32_t k1 = k0 + len < en.k_ir ? k0 + len : en.k_ir;
+	const uint32_t K = pool.K;
+	const float4 *X = reinterpret_cast<const float4 *>(pool.ring + (size_t)(en.slot * 2 + ear) * K * GAS_CONV_BINS) + threadIdx.x;
+	const float4 *H = reinterpret_cast<const float4 *>(en.H + (size_t)(ear & en.stereo) * en.k_ir * GAS_CONV_BINS) + threadIdx.x;
+	constexpr uint32_t ROW = GAS_CONV_BINS / 2; // float4 per spectrum
+	const bool packed = threadIdx.x == 0;
+	float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+	uint32_t k = k0;
+	// partition k meets the spectrum of k blocks ago: ring position pos - k, modulo K
+	auto ring_row = [&](uint32_t kk) { return (size_t)(en.pos >= kk ? en.pos - kk : en.pos + K - kk) * ROW; };
+	constexpr int U = 8; // partitions per trip: sixteen 16-byte loads in flight per thread
+	for (; k + U <= k1; k += U) {
+		float4 x[U], h[U];
+#pragma unroll
+		for (int u = 0; u < U; u++) {
+			x[u] = X[ring_row(k + u)];
+			h[u] = H[(size_t)(k + u) * ROW];
+		}
+#pragma unroll
+		for (int u = 0; u < U; u++) {
+			conv_mac(acc, x[u], h[u], packed);
+		}
+	}
+	for (; k < k1; k++) {
+		conv_mac(acc, X[ring_row(k)], H[(size_t)k * ROW], packed);
+	}
+	reinterpret_cast<float4 *>(pool.ypart + ((size_t)ie * pool.max_chunks + blockIdx.x) * GAS_CONV_BINS)[threadIdx.x] = acc;
+}
+
+__global__ __launch_bounds__(128) void k_conv_inverse(gas_conv_call call, gas_conv_pool pool, const float2 *__restrict__ tw, const gas_audio_frame *in, gas_audio_frame *out, uint32_t F) {
+	__shared__ float2 lds_all[2 * LDS_F2_HALF];
+	__shared__ float y[2][512];
+	const int lane = threadIdx.x & 63;
+	const int ear = threadIdx.x >> 6;
+	const uint32_t i = blockIdx.x;
+	const gas_conv_entry en = call.e[i];
+	const int SQ = (int)(F / 128);
+	float2 t1[8], t2[8];
+	conv_twiddles(tw, lane, t1, t2);
+	const uint32_t chunks = gas_conv_chunks(en.k_ir);
+	const float2 *yp = pool.ypart + (size_t)(i * 2 + ear) * pool.max_chunks * GAS_CONV_BINS;
+	float2 *lds = lds_all + ear * LDS_F2_HALF;
+	float2 a[8], b[8]; // Y[k] and Y[512 - k], k = lane + 64 j
+#pragma unroll
+	for (int j = 0; j < 8; j++) {
+		a[j] = make_float2(0.0f, 0.0f);
+	}
+	// chunk order; four chunks' loads (32 of 8 bytes) in flight per trip
+	uint32_t c = 0;
+	for (; c + 4 <= chunks; c += 4) {
+		float2 t[4][8];
+#pragma unroll
+		for (int u = 0; u < 4; u++) {
+#pragma unroll
+			for (int j = 0; j < 8; j++) {
+				t[u][j] = yp[(size_t)(c + u) * GAS_CONV_BINS + lane + 64 * j];
+			}
+		}
+#pragma unroll
+		for (int u = 0; u < 4; u++) {
+#pragma unroll
+			for (int j = 0; j < 8; j++) {
+				a[j] = cadd(a[j], t[u][j]);
+			}
+		}
+	}
+	for (; c < chunks; c++) {
+#pragma unroll
+		for (int j = 0; j < 8; j++) {
+			a[j] = cadd(a[j], yp[(size_t)c * GAS_CONV_BINS + lane + 64 * j]);
+		}
+	}
+	// the mirrored bins come from the other lanes through the wave's LDS slice
+#pragma unroll
+	for (int j = 0; j < 8; j++) {
+		lds[lane + 64 * j] = a[j];
+	}
+	wave_lds_sync();
+#pragma unroll
+	for (int j = 0; j < 8; j++) {
+		b[j] = lds[(512 - (lane + 64 * j)) & 511];
+	}
+	wave_lds_sync();
+	float2 v[8];
+#pragma unroll
+	for (int j = 0; j < 8; j++) {
+		const int k = lane + 64 * j;
+		const float2 w = pool.w1024[k];
+		const float2 e = make_float2(0.5f * (a[j].x + b[j].x), 0.5f * (a[j].y - b[j].y));
+		const float2 d = make_float2(0.5f * (a[j].x - b[j].x), 0.5f * (a[j].y + b[j].y));
+		const float2 o = cmulc(d, w); // W1024^-k d
+		v[j] = make_float2(e.x - o.y, e.y + o.x);
+		if (k == 0) { // Y[0] and Y[512] are real, packed into one entry
+			v[j] = make_float2(0.5f * (a[0].x + a[0].y), 0.5f * (a[0].x - a[0].y));
+		}
+	}
+	fft512<true>(v, t1, t2, lds, lane);
+	// z[n] = y[2 n] + i y[2 n + 1]; the block is the window's last F samples: registers 8 - SQ .. 7
+#pragma unroll
+	for (int j = 0; j < 8; j++) {
+		const int jj = j - (8 - SQ);
+		if (jj >= 0) {
+			*reinterpret_cast<float2 *>(&y[ear][2 * (lane + 64 * jj)]) = v[j];
+		}
+	}
+	__syncthreads();
+	const float4 *irow = reinterpret_cast<const float4 *>(in + (size_t)i * F);
+	float4 *orow = reinterpret_cast<float4 *>(out + (size_t)i * F);
+	for (uint32_t q = threadIdx.x; q < F / 2; q += 128) { // frames 2 q and 2 q + 1; out may be in: a thread reads what it writes
+		const float4 x = irow[q];
+		const float2 yl = *reinterpret_cast<const float2 *>(&y[0][2 * q]);
+		const float2 yr = *reinterpret_cast<const float2 *>(&y[1][2 * q]);
+		orow[q] = make_float4(en.dry * x.x + en.wet * yl.x, en.dry * x.y + en.wet * yr.x, en.dry * x.z + en.wet * yl.y, en.dry * x.w + en.wet * yr.y);
+	}
+}
+
+} // namespace
+
+void gas_make_w1024(float2 *host_w) {
+	const double pi = 3.14159265358979323846264338328;
+	for (int k = 0; k < 512; k++) {
+		const double a = -pi * (double)k / 512.0;
+		host_w[k] = make_float2((float)cos(a), (float)sin(a));
+	}
+}
+
+hipError_t gas_launch_conv_ir(hipStream_t stream, const float *d_ir, uint32_t channels, uint32_t taps, uint32_t frames, const float2 *twiddles, const float2 *w1024, float2 *H) {
+	const uint32_t k_ir = (taps + frames - 1) / frames;
+	hipLaunchKernelGGL(k_conv_ir, dim3(channels * k_ir), dim3(64), 0, stream, d_ir, taps, k_ir, frames, twiddles, w1024, H);
+	return hipGetLastError();
+}
+
+hipError_t gas_launch_conv(hipStream_t stream, const gas_conv_call &call, uint32_t n, const gas_conv_pool &pool, const float2 *twiddles, const gas_audio_frame *in, gas_audio_frame *out, uint32_t frames) {
+	if (n == 0) {
+		return hipSuccess;
+	}
+	uint32_t chunks = 1;
+	for (uint32_t i = 0; i < n; i++) {
+		const uint32_t c = gas_conv_chunks(call.e[i].k_ir);
+		chunks = c > chunks ? c : chunks;
+	}
+	hipLaunchKernelGGL(k_conv_forward, dim3(n * 2), dim3(64), 0, stream, call, pool, twiddles, in, frames);
+	hipError_t e = hipGetLastError();
+	if (e != hipSuccess) {
+		return e;
+	}
+	hipLaunchKernelGGL(k_conv_mac, dim3(chunks, n * 2), dim3(256), 0, stream, call, pool);
+	e = hipGetLastError();
+	if (e != hipSuccess) {
+		return e;
+	}
+	hipLaunchKernelGGL(k_conv_inverse, dim3(n), dim3(128), 0, stream, call, pool, twiddles, in, out, frames);
+	return hipGetLastError();
+}

@@ -687,6 +687,68 @@ int gas_bus_routes_publish(gas_ctx *ctx, const uint32_t *slots, const gas_bus_ro
  * (audio_spatializer.cpp:436-443). */
 int gas_process_block_buses(gas_ctx *ctx, const gas_audio_frame *src, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, uint32_t n_buses, float *peaks, int mem);
 
+/* ---- convolution reverb for bus mixes ("convolvers") -------------------------------------------------------------
+ * NEW: the engine has no counterpart (its buses are mixed and their effects run on the CPU; nothing in it convolves).
+ * A convolver is one instance per bus and channel pair: it holds an impulse response h_e[0 .. T) per ear e and every
+ * frame it has been given.  From an IR of one channel both ears use channel 0, from an IR of two channels ear e uses
+ * channel e.  With x[t] the frames given to the instance, t counting on across its gas_conv_process calls and
+ * x[t] = 0 for t < 0 (before its first call and before the first call after gas_conv_reset):
+ *
+ *     y_e[t] = dry * x_e[t] + wet * sum_{j=0}^{T-1} h_e[j] * x_e[t - j]
+ *
+ * The ears are independent (no cross-feed).  dry and wet are read once per call, with no ramp, as the effect settings
+ * are; the defaults dry = 0, wet = 1 suit a send bus.  The IR is the one the instance names when the call is made,
+ * applied over the whole history the instance holds: gas_conv_set_ir between two calls is a hard switch at the block
+ * boundary, and the history stays, because it does not depend on the IR.  Sums are f32 in a fixed order: two runs of
+ * the same calls give the same bits, and an instance's output does not depend on what else a call names.
+ * Out of scope: fading between IRs, level ramps, four-channel ("true stereo") IRs, non-uniform partitioning, gas_multi
+ * (a bus reverb belongs on the root, after the gather), the host layer and godot_module/. */
+#define GAS_MAX_CONVOLVERS 24 /* GAS_MAX_BUSES x GAS_MAX_CHANNELS_PER_BUS */
+/* Sizes the instance pool: `convolvers` instances (<= GAS_MAX_CONVOLVERS) for IRs of up to max_ir_taps taps
+ * (<= 1 048 576 = 2^20, 21.8 s at 48 kHz).  Same contract as the gas_ctx_reserve_fx_* calls: main thread, never
+ * concurrently with a callback or another gas_conv_* call.  It allocates everything gas_conv_process will ever need
+ * (nothing is allocated on the audio thread).  With K = ceil(max_ir_taps / cfg.frames) the bytes are
+ *   per instance:  8192 K + 4096 of device memory (per ear a ring of K input spectra of 4 KiB, and the previous block);
+ *   per context:   4096 + 196 608 min(32, ceil(K / 16)) + 384 cfg.frames of device memory (a twiddle table, one call's
+ *                  partial sums, staging) and 384 cfg.frames of pinned host memory (staging of host-memory calls);
+ *   per IR (allocated by gas_conv_ir_load): 4096 channels ceil(taps / cfg.frames) of device memory.
+ * (0, 0) releases everything; one of the two zero and the other not, convolvers > GAS_MAX_CONVOLVERS or max_ir_taps >
+ * 2^20 is GAS_ERR_INVALID_ARGUMENT, and so is any call while an instance or an IR exists.  A HIP failure is
+ * GAS_ERR_DEVICE with nothing reserved.  A context that never reserves pays nothing. */
+int gas_ctx_reserve_conv(gas_ctx *ctx, uint32_t convolvers, uint32_t max_ir_taps);
+/* ir = [channels][taps] f32 in host memory.  Allocates the IR's partition spectra and transforms them on the device;
+ * returns when they are ready (`ir` has been consumed).  Main thread, like gas_hrtf_load.  Many instances may share
+ * one IR.  GAS_ERR_INVALID_ARGUMENT: taps == 0, taps > max_ir_taps, channels other than 1 or 2, a value that is not
+ * finite, a NULL pointer.  GAS_ERR_UNSUPPORTED_CHAIN: nothing is reserved.  GAS_ERR_DEVICE: a HIP failure (no IR). */
+int gas_conv_ir_load(gas_ctx *ctx, const float *ir /* [channels][taps] f32 */, uint32_t channels /* 1 or 2 */, uint32_t taps, uint32_t *out_ir);
+/* Main thread; waits for the stream.  GAS_ERR_BAD_SLOT: no such IR.  GAS_ERR_INVALID_ARGUMENT: an instance still names
+ * it (nothing is freed). */
+int gas_conv_ir_free(gas_ctx *ctx, uint32_t ir);
+/* Instances come from and go back to the reserved pool; these five calls allocate nothing.  Audio thread, between
+ * callbacks.  An instance's ring and previous block are zeroed, in the context's stream order, when it is created and
+ * by gas_conv_reset ("x[t] = 0 for all earlier t": the next call is bitwise what a fresh instance gives); levels and IR
+ * survive a reset.  gas_conv_create: dry = 0, wet = 1.  GAS_ERR_UNSUPPORTED_CHAIN: nothing reserved (create).
+ * GAS_ERR_OUT_OF_SLOTS: the pool is empty (create).  GAS_ERR_BAD_SLOT: an unknown instance or IR.
+ * GAS_ERR_INVALID_ARGUMENT: a level that is not finite, a NULL pointer.  An error changes nothing. */
+int gas_conv_create(gas_ctx *ctx, uint32_t ir, uint32_t *out_conv);
+int gas_conv_destroy(gas_ctx *ctx, uint32_t conv);
+int gas_conv_reset(gas_ctx *ctx, uint32_t conv); /* x[t] = 0 for all earlier t */
+int gas_conv_set_ir(gas_ctx *ctx, uint32_t conv, uint32_t ir);
+int gas_conv_set_levels(gas_ctx *ctx, uint32_t conv, float dry, float wet);
+/* out[i] = the rule over in[i] for instance convs[i], i < n; in and out are [n][frames] AudioFrames.  Audio thread.
+ * GAS_MEM_DEVICE: the call only enqueues on the context's stream; `in` may be one bus of the `out` of an earlier
+ * gas_process_block_buses or gas_process_block_streams_buses on the same stream (out + b * C * frames) -- the intended
+ * use, and the contract gas_sidechain_set gives -- so a bus mix is convolved with no synchronisation in between.
+ * Callbacks recorded or deferred before the call (GAS_FLAG_BATCHED_LAUNCH, GAS_FLAG_PIPELINED_MIX) run first.  Device
+ * rows are read and written sixteen bytes at a time: in and out must be 16-byte aligned.  GAS_MEM_HOST: copy in,
+ * compute, copy out; *out is complete when the call returns.  out == in (in place) is allowed; any other overlap of
+ * the two, or between rows, is the caller's error.  An instance that a call does not name keeps its history and its
+ * time does not advance.  n == 0 is GAS_OK.  Refusals, each with nothing changed and a host `out` zero-filled:
+ * frames != cfg.frames GAS_ERR_FRAME_COUNT; an instance named twice, n > GAS_MAX_CONVOLVERS, a misaligned device
+ * pointer, a bad `mem` or a NULL pointer GAS_ERR_INVALID_ARGUMENT; an unknown instance GAS_ERR_BAD_SLOT.  A HIP failure
+ * is GAS_ERR_DEVICE. */
+int gas_conv_process(gas_ctx *ctx, const uint32_t *convs, uint32_t n, const gas_audio_frame *in /* [n][frames] */, gas_audio_frame *out /* [n][frames] */, uint32_t frames, int mem);
+
 /* ---- compatibility / parity path: the exact _process_frames and _mix_channel
  * signatures for one source (audio_spatializer.h:146,148), host pointers, synchronous. */
 int gas_process_frames_1(gas_ctx *ctx, uint32_t slot, gas_audio_frame *out, const gas_audio_frame *src, int frame_count);

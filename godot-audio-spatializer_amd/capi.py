@@ -489,6 +489,8 @@ EXPORTS = [
     "gas_conv_reset",
     "gas_conv_set_ir",
     "gas_conv_set_levels",
+    "gas_conv_fade_to",
+    "gas_conv_fade_remaining",
     "gas_conv_process",
     "gas_process_frames_1",
     "gas_mix_channel_1",
@@ -598,6 +600,8 @@ def load_library():
     L.gas_conv_reset.argtypes = [vp, u32]
     L.gas_conv_set_ir.argtypes = [vp, u32, u32]
     L.gas_conv_set_levels.argtypes = [vp, u32, C.c_float, C.c_float]
+    L.gas_conv_fade_to.argtypes = [vp, u32, u32, C.c_float, C.c_float, u32]
+    L.gas_conv_fade_remaining.argtypes = [vp, u32, C.POINTER(u32)]
     L.gas_conv_process.argtypes = [vp, vp, u32, vp, vp, u32, i32]
     L.gas_process_frames_1.argtypes = [vp, u32, vp, vp, i32]
     L.gas_mix_channel_1.argtypes = [vp, u32, i32, vp, vp, i32]
@@ -1025,6 +1029,17 @@ class SpatializerContext:
 
     def conv_set_levels(self, conv, dry, wet):
         self._check(self.lib.gas_conv_set_levels(self.h, int(conv), float(dry), float(wet)), "gas_conv_set_levels")
+
+    def conv_fade_to(self, conv, ir, dry, wet, fade_blocks):
+        """Fade linearly to (ir, dry, wet) over the instance's next fade_blocks calls; 0 is a hard switch.  During a
+        fade the target is kept pending (the latest wins) and starts when the fade in progress has ended."""
+        self._check(self.lib.gas_conv_fade_to(self.h, int(conv), int(ir), float(dry), float(wet), int(fade_blocks)), "gas_conv_fade_to")
+
+    def conv_fade_remaining(self, conv):
+        """Calls left in the fade in progress plus a pending fade's; 0: settled, the old IR may be freed."""
+        out = C.c_uint32(0)
+        self._check(self.lib.gas_conv_fade_remaining(self.h, int(conv), C.byref(out)), "gas_conv_fade_remaining")
+        return out.value
 
     def conv_process(self, convs, x, out=None):
         """Instances convs [n] over x [n][F][2].  A host array gives a new host array (the call returns when it is

@@ -319,13 +319,22 @@ struct gas_ctx {
 	struct ConvIr {
 		float2 *H = nullptr; // [channels][k_ir][GAS_CONV_BINS]; null: a free id
 		uint32_t channels = 0, k_ir = 0;
-		uint32_t users = 0; // instances naming it
+		uint32_t users = 0; // references from instances: a state, a fade's target and a pending target each count
+	};
+	struct ConvTarget {
+		uint32_t ir = 0;
+		float dry = 0.0f, wet = 1.0f;
 	};
 	struct ConvInst {
 		bool used = false;
 		uint32_t ir = 0;
 		uint32_t pos = 0; // ring position of the newest spectrum
 		float dry = 0.0f, wet = 1.0f;
+		// gas_conv_fade_to: (ir, dry, wet) above is state A; fade_n > 0: fading to `to`, fade_pos of fade_n calls made
+		uint32_t fade_n = 0, fade_pos = 0;
+		ConvTarget to;
+		uint32_t pending_n = 0; // > 0: `pending` starts, over pending_n calls, when the fade in progress has ended
+		ConvTarget pending;
 	};
 	uint32_t conv_count = 0, conv_max_taps = 0; // the reservation; 0: none
 	gas_conv_pool conv_pool{};
@@ -4356,6 +4365,26 @@ static bool conv_ir_live(const gas_ctx *c, uint32_t ir) {
 	return ir < c->conv_irs.size() && c->conv_irs[ir].H != nullptr;
 }
 
+// The fade in progress ends in state B: A's IR is no longer named, B's reference becomes the state's.
+static void conv_fade_land(gas_ctx *c, gas_ctx::ConvInst &k) {
+	c->conv_irs[k.ir].users--;
+	k.ir = k.to.ir;
+	k.dry = k.to.dry;
+	k.wet = k.to.wet;
+	k.fade_n = k.fade_pos = 0;
+}
+
+// gas_conv_set_ir, gas_conv_set_levels: a fade in progress ends at once in state B and a pending target is dropped.
+static void conv_fade_end(gas_ctx *c, gas_ctx::ConvInst &k) {
+	if (k.fade_n) {
+		conv_fade_land(c, k);
+	}
+	if (k.pending_n) {
+		c->conv_irs[k.pending.ir].users--;
+		k.pending_n = 0;
+	}
+}
+
 int gas_ctx_reserve_conv(gas_ctx *c, uint32_t convolvers, uint32_t max_ir_taps) {
 	if (!c || convolvers > GAS_MAX_CONVOLVERS || max_ir_taps > GAS_CONV_MAX_IR_TAPS || (convolvers == 0) != (max_ir_taps == 0)) {
 		return GAS_ERR_INVALID_ARGUMENT;
@@ -4385,7 +4414,9 @@ int gas_ctx_reserve_conv(gas_ctx *c, uint32_t convolvers, uint32_t max_ir_taps) 
 		p.max_chunks = gas_conv_max_chunks(K);
 		GAS_HIP(c, c->mem.alloc(p.ring, (size_t)convolvers * 2 * K * GAS_CONV_BINS));
 		GAS_HIP(c, c->mem.alloc(p.prev, (size_t)convolvers * 2 * 512));
-		GAS_HIP(c, c->mem.alloc(p.ypart, (size_t)GAS_MAX_CONVOLVERS * 2 * p.max_chunks * GAS_CONV_BINS));
+		// two rows (ears) per named instance and two more per fading one: 96 rows of max_chunks spectra of 4 KiB,
+		// 393 216 max_chunks bytes
+		GAS_HIP(c, c->mem.alloc(p.ypart, (size_t)GAS_MAX_CONVOLVERS * 4 * p.max_chunks * GAS_CONV_BINS));
 		GAS_HIP(c, c->mem.alloc(c->conv_w1024, 512));
 		const size_t stage = (size_t)GAS_MAX_CONVOLVERS * F;
 		GAS_HIP(c, c->mem.alloc(c->conv_h_in, stage, Mem::PINNED));
@@ -4511,6 +4542,7 @@ int gas_conv_destroy(gas_ctx *c, uint32_t conv) {
 	if (!conv_live(c, conv)) {
 		return GAS_ERR_BAD_SLOT;
 	}
+	conv_fade_end(c, c->conv[conv]); // releases every IR the instance names
 	c->conv_irs[c->conv[conv].ir].users--;
 	c->conv[conv].used = false;
 	c->conv_free.push_back(conv);
@@ -4526,7 +4558,16 @@ int gas_conv_reset(gas_ctx *c, uint32_t conv) {
 	}
 	GAS_HIP(c, hipSetDevice(c->cfg.device));
 	GAS_HIP(c, conv_zero(c, conv));
-	c->conv[conv].pos = c->conv_pool.K - 1;
+	gas_ctx::ConvInst &k = c->conv[conv];
+	k.pos = c->conv_pool.K - 1;
+	if (k.fade_n) { // the fade ends in its final state: the pending target if there is one, else B
+		conv_fade_land(c, k);
+		if (k.pending_n) {
+			k.to = k.pending;
+			k.pending_n = 0;
+			conv_fade_land(c, k);
+		}
+	}
 	return GAS_OK;
 }
 
@@ -4537,6 +4578,7 @@ int gas_conv_set_ir(gas_ctx *c, uint32_t conv, uint32_t ir) {
 	if (!conv_live(c, conv) || !conv_ir_live(c, ir)) {
 		return GAS_ERR_BAD_SLOT;
 	}
+	conv_fade_end(c, c->conv[conv]);
 	c->conv_irs[c->conv[conv].ir].users--;
 	c->conv[conv].ir = ir;
 	c->conv_irs[ir].users++;
@@ -4550,8 +4592,52 @@ int gas_conv_set_levels(gas_ctx *c, uint32_t conv, float dry, float wet) {
 	if (!conv_live(c, conv)) {
 		return GAS_ERR_BAD_SLOT;
 	}
+	conv_fade_end(c, c->conv[conv]);
 	c->conv[conv].dry = dry;
 	c->conv[conv].wet = wet;
+	return GAS_OK;
+}
+
+int gas_conv_fade_to(gas_ctx *c, uint32_t conv, uint32_t ir, float dry, float wet, uint32_t fade_blocks) {
+	if (!c || !std::isfinite(dry) || !std::isfinite(wet) || fade_blocks > GAS_CONV_MAX_FADE_BLOCKS) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (!conv_live(c, conv) || !conv_ir_live(c, ir)) {
+		return GAS_ERR_BAD_SLOT;
+	}
+	if (fade_blocks == 0) { // nothing can refuse from here on
+		gas_conv_set_ir(c, conv, ir);
+		return gas_conv_set_levels(c, conv, dry, wet);
+	}
+	gas_ctx::ConvInst &k = c->conv[conv];
+	gas_ctx::ConvTarget t;
+	t.ir = ir;
+	t.dry = dry;
+	t.wet = wet;
+	c->conv_irs[ir].users++;
+	if (k.fade_n) { // waits for the fade in progress; the latest target wins
+		if (k.pending_n) {
+			c->conv_irs[k.pending.ir].users--;
+		}
+		k.pending = t;
+		k.pending_n = fade_blocks;
+	} else {
+		k.to = t;
+		k.fade_n = fade_blocks;
+		k.fade_pos = 0;
+	}
+	return GAS_OK;
+}
+
+int gas_conv_fade_remaining(gas_ctx *c, uint32_t conv, uint32_t *out_blocks) {
+	if (!c || !out_blocks) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (!conv_live(c, conv)) {
+		return GAS_ERR_BAD_SLOT;
+	}
+	const gas_ctx::ConvInst &k = c->conv[conv];
+	*out_blocks = k.fade_n - k.fade_pos + k.pending_n;
 	return GAS_OK;
 }
 
@@ -4613,6 +4699,16 @@ int gas_conv_process(gas_ctx *c, const uint32_t *convs, uint32_t n, const gas_au
 		e.stereo = ir.channels == 2 ? 1u : 0u;
 		e.dry = k.dry;
 		e.wet = k.wet;
+		if (k.fade_n) { // call fade_pos of fade_n: frame i has s = (float)(fade_pos F + i) * (1.0f / (float)(fade_n F))
+			const gas_ctx::ConvIr &irb = c->conv_irs[k.to.ir];
+			e.HB = k.to.ir == k.ir ? nullptr : irb.H; // a level-only fade: the wet sum is computed once
+			e.k_irB = irb.k_ir;
+			e.stereoB = irb.channels == 2 ? 1u : 0u;
+			e.dryB = k.to.dry;
+			e.wetB = k.to.wet;
+			e.fade_t0 = k.fade_pos * F;
+			e.fade_inv = 1.0f / (float)(k.fade_n * F);
+		}
 	}
 	const size_t bytes = (size_t)n * F * sizeof(gas_audio_frame);
 	const int rc = [&]() -> int {
@@ -4633,7 +4729,16 @@ int gas_conv_process(gas_ctx *c, const uint32_t *convs, uint32_t n, const gas_au
 		return fail(rc);
 	}
 	for (uint32_t i = 0; i < n; i++) {
-		c->conv[convs[i]].pos = call.e[i].pos; // only the named instances' time advances
+		gas_ctx::ConvInst &k = c->conv[convs[i]];
+		k.pos = call.e[i].pos; // only the named instances' time advances, and only their fades
+		if (k.fade_n && ++k.fade_pos == k.fade_n) { // that was the fade's last call: state B, A's IR may be freed
+			conv_fade_land(c, k);
+			if (k.pending_n) { // the pending fade starts at the next call, from B
+				k.to = k.pending;
+				k.fade_n = k.pending_n;
+				k.pending_n = 0;
+			}
+		}
 	}
 	return GAS_OK;
 }

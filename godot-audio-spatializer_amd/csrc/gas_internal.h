@@ -520,14 +520,23 @@ struct gas_conv_entry { // one named instance of a gas_conv_process call
 	uint32_t k_ir; // partitions of the IR, 1 .. K
 	uint32_t stereo; // 1: ear e uses channel e; 0: both use channel 0
 	float dry, wet;
+	// A fade in progress (gas_conv_fade_to): the fields above are state A, these state B; all zero where settled.
+	const float2 *HB; // B's spectra; null where B names A's IR (a level-only fade: one wet sum serves both states)
+	uint32_t k_irB, stereoB;
+	float dryB, wetB;
+	uint32_t fade_t0; // frames of the fade before this call's frame 0: b F
+	float fade_inv; // 1 / (N F), so that frame i has s = (float)(fade_t0 + i) * fade_inv; 0: settled
 };
 struct gas_conv_call { // passed by value: a device-memory call only enqueues, so nothing it reads may live in reused staging
 	gas_conv_entry e[GAS_MAX_CONVOLVERS];
+	uint8_t fading[GAS_MAX_CONVOLVERS]; // indices of the entries with a fade in progress, in call order (gas_launch_conv)
 };
 struct gas_conv_pool {
 	float2 *ring = nullptr;
 	float *prev = nullptr;
-	float2 *ypart = nullptr; // [GAS_MAX_CONVOLVERS * 2][max_chunks][GAS_CONV_BINS] partial sums of one call
+	// partial sums of one call, [GAS_MAX_CONVOLVERS * 4][max_chunks][GAS_CONV_BINS]: row 2 i + ear is entry i's sum over its
+	// IR (state A while it fades), row 2 GAS_MAX_CONVOLVERS + 2 i + ear its sum over state B's IR while it fades
+	float2 *ypart = nullptr;
 	const float2 *w1024 = nullptr; // [512] exp(-2 pi i k / 1024)
 	uint32_t K = 0; // partitions per ring: ceil(max_ir_taps / frames)
 	uint32_t max_chunks = 0; // gas_conv_max_chunks(K)
@@ -547,7 +556,8 @@ __host__ __device__ inline uint32_t gas_conv_max_chunks(uint32_t K) { // the mos
 	const uint32_t c = (K + 15) / 16;
 	return c < GAS_CONV_MAX_CHUNKS ? c : GAS_CONV_MAX_CHUNKS;
 }
-hipError_t gas_launch_conv(hipStream_t stream, const gas_conv_call &call, uint32_t n, const gas_conv_pool &pool, const float2 *twiddles, const gas_audio_frame *in /* [n][frames] */, gas_audio_frame *out /* [n][frames] */, uint32_t frames);
+// fills call.fading from the entries' fade_inv
+hipError_t gas_launch_conv(hipStream_t stream, gas_conv_call &call, uint32_t n, const gas_conv_pool &pool, const float2 *twiddles, const gas_audio_frame *in /* [n][frames] */, gas_audio_frame *out /* [n][frames] */, uint32_t frames);
 hipError_t gas_launch_conv_ir(hipStream_t stream, const float *d_ir /* [channels][taps] */, uint32_t channels, uint32_t taps, uint32_t frames, const float2 *twiddles, const float2 *w1024, float2 *H);
 void gas_make_w1024(float2 *host_w /* [512] */);
 hipError_t gas_launch_hrtf_regrid(hipStream_t stream, const float *d_positions, const float *d_hrir, uint32_t m, uint32_t taps, uint32_t az_steps, uint32_t el_steps, int interpolation, float *d_out /* [az_steps * el_steps][2][GAS_HRTF_TAPS] */);

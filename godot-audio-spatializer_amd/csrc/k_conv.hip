@@ -20,6 +20,12 @@
 //                    matter -- k_ir x 8 KiB per ear -- spread over k_ir / chunk length workgroup rows
 //   k_conv_inverse   one workgroup of two waves per instance (wave = ear): chunk sums added in chunk order, back
 //                    transform, the last F samples, out = dry in + wet y as 16-byte stores (both ears of two frames)
+// A fading instance (gas_conv_fade_to: state A -> state B over N calls) keeps its one input ring and adds
+//   k_conv_mac<true>       two more rows behind the call's own: the same walk over the same ring with B's spectra
+//                          (skipped where B names A's IR), split into chunks by B's length alone
+//   k_conv_inverse_fade    a second launch over the fading instances only, four waves (state x ear): both sums
+//                          transformed back side by side, out = (1 - s)(dry_A in + wet_A y^A) + s (dry_B in + wet_B y^B)
+// while the settled instances of the call stay on k_conv_inverse; a call without a fade launches what it always did.
 // Vector stores only, no atomics; every sum has a fixed order, so two runs give the same bits.
 #include "gas_hrtf_wave.h"
 
@@ -121,24 +127,24 @@ __device__ __forceinline__ void conv_mac(float4 &acc, const float4 x, const floa
 	acc = make_float4(a.x, a.y, b.x, b.y);
 }
 
-__global__ __launch_bounds__(256) void k_conv_mac(gas_conv_call call, gas_conv_pool pool) {
-	const uint32_t ie = blockIdx.y, ear = ie & 1;
-	const gas_conv_entry en = call.e[ie >> 1];
-	const uint32_t len = gas_conv_chunk_len(en.k_ir);
+// One workgroup's chunk of the sum over an IR (spectra Hs, k_ir partitions) for one ear of the instance in `slot`, into
+// row `row` of the call's partial sums.  The chunk split is a function of k_ir alone.
+__device__ __forceinline__ void conv_mac_chunk(const gas_conv_pool &pool, const float2 *__restrict__ Hs, uint32_t k_ir, uint32_t stereo, uint32_t slot, uint32_t pos, uint32_t ear, uint32_t row) {
+	const uint32_t len = gas_conv_chunk_len(k_ir);
 	const uint32_t k0 = blockIdx.x * len;
-	if (k0 >= en.k_ir) { // this IR has fewer chunks than the call's longest
+	if (k0 >= k_ir) { // this IR has fewer chunks than the call's longest
 		return;
 	}
-	const uint32_t k1 = k0 + len < en.k_ir ? k0 + len : en.k_ir;
+	const uint32_t k1 = k0 + len < k_ir ? k0 + len : k_ir;
 	const uint32_t K = pool.K;
-	const float4 *X = reinterpret_cast<const float4 *>(pool.ring + (size_t)(en.slot * 2 + ear) * K * GAS_CONV_BINS) + threadIdx.x;
-	const float4 *H = reinterpret_cast<const float4 *>(en.H + (size_t)(ear & en.stereo) * en.k_ir * GAS_CONV_BINS) + threadIdx.x;
+	const float4 *X = reinterpret_cast<const float4 *>(pool.ring + (size_t)(slot * 2 + ear) * K * GAS_CONV_BINS) + threadIdx.x;
+	const float4 *H = reinterpret_cast<const float4 *>(Hs + (size_t)(ear & stereo) * k_ir * GAS_CONV_BINS) + threadIdx.x;
 	constexpr uint32_t ROW = GAS_CONV_BINS / 2; // float4 per spectrum
 	const bool packed = threadIdx.x == 0;
 	float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 	uint32_t k = k0;
 	// partition k meets the spectrum of k blocks ago: ring position pos - k, modulo K
-	auto ring_row = [&](uint32_t kk) { return (size_t)(en.pos >= kk ? en.pos - kk : en.pos + K - kk) * ROW; };
+	auto ring_row = [&](uint32_t kk) { return (size_t)(pos >= kk ? pos - kk : pos + K - kk) * ROW; };
 	constexpr int U = 8; // partitions per trip: sixteen 16-byte loads in flight per thread
 	for (; k + U <= k1; k += U) {
 		float4 x[U], h[U];
@@ -155,22 +161,29 @@ __global__ __launch_bounds__(256) void k_conv_mac(gas_conv_call call, gas_conv_p
 	for (; k < k1; k++) {
 		conv_mac(acc, X[ring_row(k)], H[(size_t)k * ROW], packed);
 	}
-	reinterpret_cast<float4 *>(pool.ypart + ((size_t)ie * pool.max_chunks + blockIdx.x) * GAS_CONV_BINS)[threadIdx.x] = acc;
+	reinterpret_cast<float4 *>(pool.ypart + ((size_t)row * pool.max_chunks + blockIdx.x) * GAS_CONV_BINS)[threadIdx.x] = acc;
 }
 
-__global__ __launch_bounds__(128) void k_conv_inverse(gas_conv_call call, gas_conv_pool pool, const float2 *__restrict__ tw, const gas_audio_frame *in, gas_audio_frame *out, uint32_t F) {
-	__shared__ float2 lds_all[2 * LDS_F2_HALF];
-	__shared__ float y[2][512];
-	const int lane = threadIdx.x & 63;
-	const int ear = threadIdx.x >> 6;
-	const uint32_t i = blockIdx.x;
-	const gas_conv_entry en = call.e[i];
-	const int SQ = (int)(F / 128);
-	float2 t1[8], t2[8];
-	conv_twiddles(tw, lane, t1, t2);
-	const uint32_t chunks = gas_conv_chunks(en.k_ir);
-	const float2 *yp = pool.ypart + (size_t)(i * 2 + ear) * pool.max_chunks * GAS_CONV_BINS;
-	float2 *lds = lds_all + ear * LDS_F2_HALF;
+// FADE (a call that names a fading instance): behind the call's own `rows` rows come two per fading entry, the sum over
+// state B's IR -- the same walk over the same ring, so after the fade the bits are those of a hard switch to B.
+template <bool FADE>
+__global__ __launch_bounds__(256) void k_conv_mac(gas_conv_call call, gas_conv_pool pool, uint32_t rows) {
+	const uint32_t ie = blockIdx.y, ear = ie & 1;
+	if (FADE && ie >= rows) {
+		const uint32_t i = call.fading[(ie - rows) >> 1];
+		const gas_conv_entry en = call.e[i];
+		if (en.HB) { // a level-only fade has no second sum
+			conv_mac_chunk(pool, en.HB, en.k_irB, en.stereoB, en.slot, en.pos, ear, 2 * GAS_MAX_CONVOLVERS + i * 2 + ear);
+		}
+		return;
+	}
+	const gas_conv_entry en = call.e[ie >> 1];
+	conv_mac_chunk(pool, en.H, en.k_ir, en.stereo, en.slot, en.pos, ear, ie);
+}
+
+// One wave's share of the inverse stage: `chunks` partial sums from yp added in chunk order, untangled and transformed
+// back; the window's last F samples land in y[0 .. F).
+__device__ __forceinline__ void conv_back(const float2 *__restrict__ yp, uint32_t chunks, const float2 *__restrict__ w1024, const float2 (&t1)[8], const float2 (&t2)[8], float2 *lds, int lane, int SQ, float *y) {
 	float2 a[8], b[8]; // Y[k] and Y[512 - k], k = lane + 64 j
 #pragma unroll
 	for (int j = 0; j < 8; j++) {
@@ -216,7 +229,7 @@ __global__ __launch_bounds__(128) void k_conv_inverse(gas_conv_call call, gas_co
 #pragma unroll
 	for (int j = 0; j < 8; j++) {
 		const int k = lane + 64 * j;
-		const float2 w = pool.w1024[k];
+		const float2 w = w1024[k];
 		const float2 e = make_float2(0.5f * (a[j].x + b[j].x), 0.5f * (a[j].y - b[j].y));
 		const float2 d = make_float2(0.5f * (a[j].x - b[j].x), 0.5f * (a[j].y + b[j].y));
 		const float2 o = cmulc(d, w); // W1024^-k d
@@ -231,9 +244,27 @@ __global__ __launch_bounds__(128) void k_conv_inverse(gas_conv_call call, gas_co
 	for (int j = 0; j < 8; j++) {
 		const int jj = j - (8 - SQ);
 		if (jj >= 0) {
-			*reinterpret_cast<float2 *>(&y[ear][2 * (lane + 64 * jj)]) = v[j];
+			*reinterpret_cast<float2 *>(&y[2 * (lane + 64 * jj)]) = v[j];
 		}
 	}
+}
+
+// The settled instances of a call; a fading one is k_conv_inverse_fade's.
+__global__ __launch_bounds__(128) void k_conv_inverse(gas_conv_call call, gas_conv_pool pool, const float2 *__restrict__ tw, const gas_audio_frame *in, gas_audio_frame *out, uint32_t F) {
+	__shared__ float2 lds_all[2 * LDS_F2_HALF];
+	__shared__ float y[2][512];
+	const int lane = threadIdx.x & 63;
+	const int ear = threadIdx.x >> 6;
+	const uint32_t i = blockIdx.x;
+	const gas_conv_entry en = call.e[i];
+	if (en.fade_inv != 0.0f) {
+		return;
+	}
+	const int SQ = (int)(F / 128);
+	float2 t1[8], t2[8];
+	conv_twiddles(tw, lane, t1, t2);
+	const float2 *yp = pool.ypart + (size_t)(i * 2 + ear) * pool.max_chunks * GAS_CONV_BINS;
+	conv_back(yp, gas_conv_chunks(en.k_ir), pool.w1024, t1, t2, lds_all + ear * LDS_F2_HALF, lane, SQ, y[ear]);
 	__syncthreads();
 	const float4 *irow = reinterpret_cast<const float4 *>(in + (size_t)i * F);
 	float4 *orow = reinterpret_cast<float4 *>(out + (size_t)i * F);
@@ -242,6 +273,41 @@ __global__ __launch_bounds__(128) void k_conv_inverse(gas_conv_call call, gas_co
 		const float2 yl = *reinterpret_cast<const float2 *>(&y[0][2 * q]);
 		const float2 yr = *reinterpret_cast<const float2 *>(&y[1][2 * q]);
 		orow[q] = make_float4(en.dry * x.x + en.wet * yl.x, en.dry * x.y + en.wet * yr.x, en.dry * x.z + en.wet * yl.y, en.dry * x.w + en.wet * yr.y);
+	}
+}
+
+// The fading instances of a call, one workgroup of four waves each: waves 0 and 1 transform state A's sums back (one ear
+// each), waves 2 and 3 state B's, at the same time; then frame i is (1 - s) (dry_A x + wet_A y^A) + s (dry_B x + wet_B y^B)
+// with s = (float)(fade_t0 + i) * fade_inv.  In a level-only fade y^B is y^A and waves 2 and 3 only take part in the lerp.
+__global__ __launch_bounds__(256) void k_conv_inverse_fade(gas_conv_call call, gas_conv_pool pool, const float2 *__restrict__ tw, const gas_audio_frame *in, gas_audio_frame *out, uint32_t F) {
+	__shared__ float2 lds_all[4 * LDS_F2_HALF];
+	__shared__ float y[4][512]; // [state * 2 + ear]
+	const int lane = threadIdx.x & 63;
+	const int wave = threadIdx.x >> 6, ear = wave & 1, state = wave >> 1;
+	const uint32_t i = call.fading[blockIdx.x];
+	const gas_conv_entry en = call.e[i];
+	const bool own = en.HB != nullptr; // B has a wet sum of its own
+	if (state == 0 || own) { // uniform over a wave
+		float2 t1[8], t2[8];
+		conv_twiddles(tw, lane, t1, t2);
+		const uint32_t row = state * 2 * GAS_MAX_CONVOLVERS + i * 2 + ear;
+		const float2 *yp = pool.ypart + (size_t)row * pool.max_chunks * GAS_CONV_BINS;
+		conv_back(yp, gas_conv_chunks(state ? en.k_irB : en.k_ir), pool.w1024, t1, t2, lds_all + wave * LDS_F2_HALF, lane, (int)(F / 128), y[wave]);
+	}
+	__syncthreads();
+	const float *ybl = own ? y[2] : y[0], *ybr = own ? y[3] : y[1];
+	const float4 *irow = reinterpret_cast<const float4 *>(in + (size_t)i * F);
+	float4 *orow = reinterpret_cast<float4 *>(out + (size_t)i * F);
+	for (uint32_t q = threadIdx.x; q < F / 2; q += 256) { // frames 2 q and 2 q + 1; out may be in: a thread reads what it writes
+		const float4 x = irow[q];
+		const float2 al = *reinterpret_cast<const float2 *>(&y[0][2 * q]);
+		const float2 ar = *reinterpret_cast<const float2 *>(&y[1][2 * q]);
+		const float2 bl = *reinterpret_cast<const float2 *>(&ybl[2 * q]);
+		const float2 br = *reinterpret_cast<const float2 *>(&ybr[2 * q]);
+		const float s0 = (float)(en.fade_t0 + 2 * q) * en.fade_inv, s1 = (float)(en.fade_t0 + 2 * q + 1) * en.fade_inv;
+		const float r0 = 1.0f - s0, r1 = 1.0f - s1;
+		orow[q] = make_float4(r0 * (en.dry * x.x + en.wet * al.x) + s0 * (en.dryB * x.x + en.wetB * bl.x), r0 * (en.dry * x.y + en.wet * ar.x) + s0 * (en.dryB * x.y + en.wetB * br.x),
+				r1 * (en.dry * x.z + en.wet * al.y) + s1 * (en.dryB * x.z + en.wetB * bl.y), r1 * (en.dry * x.w + en.wet * ar.y) + s1 * (en.dryB * x.w + en.wetB * br.y));
 	}
 }
 
@@ -261,13 +327,19 @@ hipError_t gas_launch_conv_ir(hipStream_t stream, const float *d_ir, uint32_t ch
 	return hipGetLastError();
 }
 
-hipError_t gas_launch_conv(hipStream_t stream, const gas_conv_call &call, uint32_t n, const gas_conv_pool &pool, const float2 *twiddles, const gas_audio_frame *in, gas_audio_frame *out, uint32_t frames) {
+hipError_t gas_launch_conv(hipStream_t stream, gas_conv_call &call, uint32_t n, const gas_conv_pool &pool, const float2 *twiddles, const gas_audio_frame *in, gas_audio_frame *out, uint32_t frames) {
 	if (n == 0) {
 		return hipSuccess;
 	}
-	uint32_t chunks = 1;
+	uint32_t chunks = 1, fading = 0;
 	for (uint32_t i = 0; i < n; i++) {
-		const uint32_t c = gas_conv_chunks(call.e[i].k_ir);
+		const gas_conv_entry &en = call.e[i];
+		uint32_t c = gas_conv_chunks(en.k_ir);
+		if (en.fade_inv != 0.0f) {
+			call.fading[fading++] = (uint8_t)i;
+			const uint32_t cb = en.HB ? gas_conv_chunks(en.k_irB) : 0;
+			c = cb > c ? cb : c;
+		}
 		chunks = c > chunks ? c : chunks;
 	}
 	hipLaunchKernelGGL(k_conv_forward, dim3(n * 2), dim3(64), 0, stream, call, pool, twiddles, in, frames);
@@ -275,11 +347,25 @@ hipError_t gas_launch_conv(hipStream_t stream, const gas_conv_call &call, uint32
 	if (e != hipSuccess) {
 		return e;
 	}
-	hipLaunchKernelGGL(k_conv_mac, dim3(chunks, n * 2), dim3(256), 0, stream, call, pool);
+	if (fading == 0) {
+		hipLaunchKernelGGL(k_conv_mac<false>, dim3(chunks, n * 2), dim3(256), 0, stream, call, pool, n * 2);
+	} else {
+		hipLaunchKernelGGL(k_conv_mac<true>, dim3(chunks, (n + fading) * 2), dim3(256), 0, stream, call, pool, n * 2);
+	}
 	e = hipGetLastError();
 	if (e != hipSuccess) {
 		return e;
 	}
-	hipLaunchKernelGGL(k_conv_inverse, dim3(n), dim3(128), 0, stream, call, pool, twiddles, in, out, frames);
-	return hipGetLastError();
+	if (fading < n) {
+		hipLaunchKernelGGL(k_conv_inverse, dim3(n), dim3(128), 0, stream, call, pool, twiddles, in, out, frames);
+		e = hipGetLastError();
+		if (e != hipSuccess) {
+			return e;
+		}
+	}
+	if (fading > 0) {
+		hipLaunchKernelGGL(k_conv_inverse_fade, dim3(fading), dim3(256), 0, stream, call, pool, twiddles, in, out, frames);
+		e = hipGetLastError();
+	}
+	return e;
 }

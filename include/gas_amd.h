@@ -701,16 +701,17 @@ int gas_process_block_buses(gas_ctx *ctx, const gas_audio_frame *src, const uint
  * applied over the whole history the instance holds: gas_conv_set_ir between two calls is a hard switch at the block
  * boundary, and the history stays, because it does not depend on the IR.  Sums are f32 in a fixed order: two runs of
  * the same calls give the same bits, and an instance's output does not depend on what else a call names.
- * Out of scope: fading between IRs, level ramps, four-channel ("true stereo") IRs, non-uniform partitioning, gas_multi
- * (a bus reverb belongs on the root, after the gather), the host layer and godot_module/. */
+ * Out of scope: four-channel ("true stereo") IRs, non-uniform partitioning, gas_multi (a bus reverb belongs on the
+ * root, after the gather), the host layer and godot_module/. */
 #define GAS_MAX_CONVOLVERS 24 /* GAS_MAX_BUSES x GAS_MAX_CHANNELS_PER_BUS */
 /* Sizes the instance pool: `convolvers` instances (<= GAS_MAX_CONVOLVERS) for IRs of up to max_ir_taps taps
  * (<= 1 048 576 = 2^20, 21.8 s at 48 kHz).  Same contract as the gas_ctx_reserve_fx_* calls: main thread, never
  * concurrently with a callback or another gas_conv_* call.  It allocates everything gas_conv_process will ever need
  * (nothing is allocated on the audio thread).  With K = ceil(max_ir_taps / cfg.frames) the bytes are
  *   per instance:  8192 K + 4096 of device memory (per ear a ring of K input spectra of 4 KiB, and the previous block);
- *   per context:   4096 + 196 608 min(32, ceil(K / 16)) + 384 cfg.frames of device memory (a twiddle table, one call's
- *                  partial sums, staging) and 384 cfg.frames of pinned host memory (staging of host-memory calls);
+ *   per context:   4096 + 393 216 min(32, ceil(K / 16)) + 384 cfg.frames of device memory (a twiddle table, one call's
+ *                  partial sums -- two per instance and ear, for a call of 24 fading instances -- and staging) and
+ *                  384 cfg.frames of pinned host memory (staging of host-memory calls);
  *   per IR (allocated by gas_conv_ir_load): 4096 channels ceil(taps / cfg.frames) of device memory.
  * (0, 0) releases everything; one of the two zero and the other not, convolvers > GAS_MAX_CONVOLVERS or max_ir_taps >
  * 2^20 is GAS_ERR_INVALID_ARGUMENT, and so is any call while an instance or an IR exists.  A HIP failure is
@@ -735,6 +736,39 @@ int gas_conv_destroy(gas_ctx *ctx, uint32_t conv);
 int gas_conv_reset(gas_ctx *ctx, uint32_t conv); /* x[t] = 0 for all earlier t */
 int gas_conv_set_ir(gas_ctx *ctx, uint32_t conv, uint32_t ir);
 int gas_conv_set_levels(gas_ctx *ctx, uint32_t conv, float dry, float wet);
+/* NEW: a linear fade to another impulse response and other levels over N blocks, so that a listener who walks into the
+ * next room does not hear the whole reverb tail step inside one sample.  An instance has a state S = (ir, dry, wet);
+ * write y^S_e[t] = dry * x_e[t] + wet * sum_j h_e[j] * x_e[t - j] for the rule above evaluated with state S over the
+ * instance's one input history x (the history does not depend on the IR).  gas_conv_fade_to with N = fade_blocks >= 1
+ * on an instance in state A names a target B = (ir, dry, wet): for the instance's next N gas_conv_process calls that
+ * name it, frame i of the b-th such call (b = 0 .. N - 1) is
+ *
+ *     y[t] = (1 - s) * y^A[t] + s * y^B[t],   s = (float)(b * F + i) * (1.0f / (float)(N * F))
+ *
+ * with F = cfg.frames and s computed in float32 (exact for N F <= 2^21, hence the cap): the t = f * (1 / F) convention
+ * of GAS_FLAG_ER_TAP_FADE stretched over N blocks.  The first frame of the fade is all A, the first frame after it all
+ * B; from the (N + 1)-th call on the instance is in state B, bitwise what a hard switch to B gives over the same
+ * history.  A call that does not name the instance advances neither its time nor its fade.  fade_blocks == 0 is
+ * exactly gas_conv_set_ir followed by gas_conv_set_levels.  Ears and one- or two-channel IRs are handled as above for A
+ * and B independently.  A level-only fade (ir = the instance's current IR) is legal and computes the wet sum once.
+ *  - While a fade is in progress another gas_conv_fade_to stores a pending target (the latest wins); the pending fade
+ *    starts, with its own fade_blocks, at the first call after the fade in progress has ended, from state B.
+ *  - gas_conv_set_ir and gas_conv_set_levels end the fade at once: the state becomes B, a pending target is dropped,
+ *    then they apply as above.  gas_conv_reset zeroes the history as above and ends the fade in its final state: the
+ *    pending target if there is one, else B.  gas_conv_destroy releases every IR the instance names.
+ *  - A's IR, B's IR and a pending target's IR all count as named by the instance: gas_conv_ir_free on any of them is
+ *    GAS_ERR_INVALID_ARGUMENT with nothing freed.  A's IR can be freed once the fade's last call has been made.
+ *  - gas_conv_fade_remaining: the calls left in the fade in progress plus a pending fade's fade_blocks; 0 when the
+ *    instance is settled -- the moment the old IR may be freed.
+ * Both are audio-thread calls made between callbacks, like gas_conv_set_ir, and allocate nothing.  Refusals, each with
+ * everything unchanged: GAS_ERR_BAD_SLOT an unknown instance or IR; GAS_ERR_INVALID_ARGUMENT a level that is not
+ * finite, fade_blocks > GAS_CONV_MAX_FADE_BLOCKS, a NULL pointer.  Sums stay f32 in a fixed order: two runs of the same
+ * calls give the same bits, an instance's output, fading or not, does not depend on what else a call names, and a call
+ * that names no fading instance behaves as it did.  Out of scope: fades that are not linear, more than one fade
+ * overlapping in time (that is what pending is for). */
+#define GAS_CONV_MAX_FADE_BLOCKS 4096
+int gas_conv_fade_to(gas_ctx *ctx, uint32_t conv, uint32_t ir, float dry, float wet, uint32_t fade_blocks);
+int gas_conv_fade_remaining(gas_ctx *ctx, uint32_t conv, uint32_t *out_blocks);
 /* out[i] = the rule over in[i] for instance convs[i], i < n; in and out are [n][frames] AudioFrames.  Audio thread.
  * GAS_MEM_DEVICE: the call only enqueues on the context's stream; `in` may be one bus of the `out` of an earlier
  * gas_process_block_buses or gas_process_block_streams_buses on the same stream (out + b * C * frames) -- the intended

@@ -8,7 +8,13 @@ Prints the wall clock per device-memory call (enqueue, three launches, synchroni
 run, gas_bandwidth_probe's time for a pure streaming launch over the same byte counts (its reads come from an arena
 larger than the Infinity Cache: the HBM ceiling).  The kernels' own times (k_conv_forward, k_conv_mac, k_conv_inverse)
 come from running this under `rocprofv3 --kernel-trace --stats` in a run of its own, the program after `--`; pass
-`noprobe` as a fourth argument there to keep the probe's launches out of the trace's totals."""
+`noprobe` as a fourth argument there to keep the probe's launches out of the trace's totals.
+
+  python tools/time_conv.py 6 2.0 512 --fading
+
+Every instance is mid-fade (gas_conv_fade_to) between two IRs of the same length in every call of the run, the fill
+included: one 4096-call fade started before the first call.  The multiply-accumulate stage then walks the ring once per
+IR (k_conv_mac<true>: twice the reads and twice the partial sums) and the inverse stage is k_conv_inverse_fade."""
 import json
 import sys
 import time
@@ -32,13 +38,18 @@ def chunks(k_ir):  # gas_conv_chunks (gas_internal.h)
 def main(argv):
     n, seconds, F = int(argv[0]), float(argv[1]), int(argv[2])
     probe = "noprobe" not in argv[3:]
+    fading = "--fading" in argv[3:]
     taps = int(round(seconds * RATE))
     k_ir = -(-taps // F)
+    assert not fading or WARMUP + STEPS + k_ir <= 4096  # GAS_CONV_MAX_FADE_BLOCKS: the fade outlasts the run
     rng = np.random.default_rng(0)
     ctx = gas.SpatializerContext(max_sources=4, frames=F, mix_rate=float(RATE))
     ctx.reserve_conv(n, taps)
     env = np.exp(-6.0 * np.arange(taps) / taps)
     convs = [ctx.conv_create(ctx.conv_ir_load((rng.standard_normal((2, taps)) * env / np.sqrt(taps)).astype(np.float32))) for _ in range(n)]
+    if fading:
+        for k in convs:
+            ctx.conv_fade_to(k, ctx.conv_ir_load((rng.standard_normal((2, taps)) * env / np.sqrt(taps)).astype(np.float32)), 0.25, 0.75, 4096)
     x = torch.from_numpy(rng.uniform(-1, 1, (n, F, 2)).astype(np.float32)).cuda()
     y = torch.zeros_like(x)
     torch.cuda.synchronize()
@@ -52,9 +63,10 @@ def main(argv):
             ts.append((t1 - t0) * 1e6)
     out = y.cpu().numpy()
     assert np.isfinite(out).all() and np.abs(out).max() > 0
-    rd = n * 2 * k_ir * 2 * 4096
-    wr = n * 2 * chunks(k_ir) * 4096
-    res = {"instances": n, "ir_seconds": seconds, "frames": F, "taps": taps, "k_ir": k_ir, "steps": STEPS, "mac_read_bytes": rd, "mac_write_bytes": wr, "state_bytes": n * (8192 * k_ir + 4096) + n * 2 * k_ir * 4096, "call_us": {"median": round(float(np.median(ts)), 1), "min": round(min(ts), 1), "max": round(max(ts), 1)}}
+    sums = 2 if fading else 1  # walks over the ring: one per IR
+    rd = sums * n * 2 * k_ir * 2 * 4096
+    wr = sums * n * 2 * chunks(k_ir) * 4096
+    res = {"instances": n, "ir_seconds": seconds, "frames": F, "fading": fading, "taps": taps, "k_ir": k_ir, "steps": STEPS, "mac_read_bytes": rd, "mac_write_bytes": wr, "state_bytes": n * (8192 * k_ir + 4096) + sums * n * 2 * k_ir * 4096, "call_us": {"median": round(float(np.median(ts)), 1), "min": round(min(ts), 1), "max": round(max(ts), 1)}}
     if probe:
         us = ctx.bandwidth_probe(rd, wr)
         res["probe_us"] = round(us, 2)

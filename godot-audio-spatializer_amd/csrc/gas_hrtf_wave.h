@@ -42,6 +42,32 @@ __device__ __forceinline__ float2 cmul_fixed(float2 z, float hx, float hy) {
 #pragma clang fp contract(off)
 	return make_float2(__builtin_fmaf(z.x, hx, -(z.y * hy)), __builtin_fmaf(z.x, hy, z.y * hx));
 }
+// A window sample = the callback's mono frame times its gain-ramp weight.  KEPT (the sample is also part of the new
+// history row, x_full[F ..)): rounded on its own, as the stored value is, and that value enters the transform.  Not
+// kept: an ordinary product, which the compiler fuses into the transform's first additions (one rounding less).  Said
+// here and not left to the optimiser, which decides by what shares a basic block with the product: with a branch
+// between the history store and the transform it made exactly this choice in every HRTF kernel, and without that
+// branch it fused the kept samples as well, one ulp away from the other forms.  Same reason as cmac_fixed above.
+// (Two functions and, at the call sites, two loops with constant bounds: one function selecting between the two products
+// by a flag is merged into a single product before the unrolled loop makes the flag a constant.)
+__device__ __forceinline__ float window_sample_kept(float mono, float weight) {
+#pragma clang fp contract(off)
+	return mono * weight;
+}
+__device__ __forceinline__ float window_sample(float mono, float weight) {
+	return mono * weight;
+}
+// The ramp weight g1 t + (1 - t) g0 is a sum of two products, either of which the compiler may fuse; every HRTF kernel
+// got g1 t fused onto the rounded (1 - t) g0; k_hrtf_multi, whose source trip is one basic block, spells that out.
+__device__ __forceinline__ float ramp_weight(float g0, float g1, float t, float one_minus_t) {
+#pragma clang fp contract(off)
+	return __builtin_fmaf(g1, t, one_minus_t * g0);
+}
+// frame registers q < hrtf_unkept_regs of a callback are not part of the new history row (x_full[F ..) = registers FQ ..)
+template <int SQ>
+constexpr int hrtf_unkept_regs() {
+	return 2 * SQ > 8 - SQ ? 2 * SQ - (8 - SQ) : 0; // 0, 0, 1, 4 for F = 128, 256, 384, 512
+}
 // The window registers that enter the transform as zeros.  The outputs a sub-block keeps are window positions
 // [512 - S, 512), S = 64 SQ, and each reaches back GAS_HRTF_TAPS - 1 frames: window frames below 512 - S - (TAPS - 1) feed
 // only the aliased outputs nobody reads.  Transformed, they would still leave their rounding (1e-7 of full scale) on the

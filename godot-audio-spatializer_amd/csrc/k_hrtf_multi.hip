@@ -50,9 +50,20 @@ __device__ __forceinline__ void lds_wait_at_least(const uint32_t *flag, uint32_t
 }
 
 // HIST_LDS: every wave has at most MultiLds::HIST_ROWS sources, so their history rows stay in LDS from block to block --
-// read from HBM by the first block only, written back by the last one only.  Measured before (profiles/r02_notes.md):
-// the launch runs at the fabric's rate over its actual traffic, and a row stored by block b did NOT come back out of
-// the L2 for block b + 1 (FETCH_SIZE per block barely moved) -- 16.8 of a block's 74 MB were history.
+// copied from HBM into the wave's LDS rows by the prologue, read from LDS by every block (the first included: the source
+// loop holds no history load from memory at all), written back by the last block only.  Measured before
+// (profiles/r02_notes.md): the launch runs at the fabric's rate over its actual traffic, and a row stored by block b did
+// NOT come back out of the L2 for block b + 1 (FETCH_SIZE per block barely moved) -- 16.8 of a block's 74 MB were history.
+//
+// The load queue of a source trip.  A wave's vector-memory results return in order and one counter (vmcnt) covers them
+// all, so the compiler's wait for a register is "at most N operations still outstanding", N being the operations
+// issued behind that register's load -- on the path through the trip that issues the FEWEST.  A request that some
+// paths skip therefore turns the wait in front of the spectral products (which need the table row requested a trip
+// earlier) into a wait for the rows requested a transform ago as well: the prefetch is drained in the middle of every
+// trip.  So the loop issues the same operations in the same order whatever b and i are: the row request on every trip
+// (the last one of a launch asks for a row again and drops it), the history load with it (memory form) or never (LDS
+// form).  The listing then waits vmcnt(FQ + ...) in front of the products and the table request, and the rows stay
+// in flight until the next trip reads them (profiles/load_queue_notes.md; tools/isa_waits.py prints the waits).
 template <int SQ, bool HIST_LDS>
 __global__ __launch_bounds__(MW * 64, GAS_HRTF_WAVES_PER_SIMD) void k_hrtf_multi(gas_group_args g, gas_hrtf_blocks mb, const uint32_t *__restrict__ peak_bits, uint32_t peak_all, gas_dev_state st, gas_hrtf_table tab, const float2 *__restrict__ tw, float *__restrict__ partials) {
 	constexpr int FQ = 2 * SQ; // F / 64
@@ -92,7 +103,27 @@ __global__ __launch_bounds__(MW * 64, GAS_HRTF_WAVES_PER_SIMD) void k_hrtf_multi
 	float rawh[HQ];
 	if (cnt > 0) {
 		const uint32_t s0 = (uint32_t)__builtin_amdgcn_readlane((int)my_slot, 0), r0 = (uint32_t)__builtin_amdgcn_readlane((int)my_row, 0);
-		load_history<HQ>(st.hrtf_hist + (size_t)s0 * HL, lane, rawh);
+		if constexpr (HIST_LDS) {
+			// this wave's history rows, memory -> its LDS rows: every row requested before the first is parked (the rows
+			// are the wave's own, so its own program order is all the hand-over they need)
+			constexpr int HR = MultiLds<SQ>::HIST_ROWS;
+			float stage[HR][HQ];
+#pragma unroll
+			for (int r = 0; r < HR; r++) {
+				if ((uint32_t)r < cnt) {
+					const uint32_t sr = (uint32_t)__builtin_amdgcn_readlane((int)my_slot, r);
+					load_history<HQ>(st.hrtf_hist + (size_t)sr * HL, lane, stage[r]);
+				}
+			}
+#pragma unroll
+			for (int r = 0; r < HR; r++) {
+				if ((uint32_t)r < cnt) {
+					store_history<HQ>(my_hist + (size_t)r * HL, lane, stage[r]);
+				}
+			}
+		} else {
+			load_history<HQ>(st.hrtf_hist + (size_t)s0 * HL, lane, rawh);
+		}
 #pragma unroll
 		for (int q = 0; q < FQ; q++) {
 			raw[q] = (GAS_ABL & 8) ? gas_audio_frame{ (float)lane, (float)r0 } : nt_load_frame(mb.src[0] + (size_t)r0 * F + lane + 64 * q);
@@ -134,6 +165,10 @@ __global__ __launch_bounds__(MW * 64, GAS_HRTF_WAVES_PER_SIMD) void k_hrtf_multi
 
 	for (uint32_t b = 0; b < K; b++) {
 		float *peaks_b = mb.peaks[b];
+		// the row tables a trip of this block requests from, fetched from the by-value block table once per block and
+		// not once per trip: this block's, and where the wave's first source comes round again (the next block's)
+		const gas_audio_frame *src_b = mb.src[b];
+		const gas_audio_frame *src_wrap = mb.src[b + 1 < K ? b + 1 : b];
 		// this block's sums, the skewed spectrum and its table row: nothing of them lives across the block boundary
 		float2 aYL[8], aYR[8], zp[8];
 		float4 hs[8];
@@ -198,12 +233,22 @@ __global__ __launch_bounds__(MW * 64, GAS_HRTF_WAVES_PER_SIMD) void k_hrtf_multi
 			const float g1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(my_g1), (int)i));
 			const uint32_t flag = (uint32_t)__builtin_amdgcn_readlane((int)my_flag, (int)i);
 			float xq[NQ];
-			if (HIST_LDS && b > 0) { // wave-uniform: the row this wave parked in the previous block
+			if constexpr (HIST_LDS) { // the row this wave parked: in the prologue (block 0), else in the previous block
 				load_history<HQ>(my_hist + (size_t)i * HL, lane, rawh);
 			}
 #pragma unroll
 			for (int q = 0; q < HQ; q++) {
 				xq[q] = rawh[q];
+			}
+			if constexpr (!HIST_LDS) {
+				// Below F = 512 the first registers of a history row enter the transform as zeros (hrtf_dead_regs), yet they
+				// arrive in one wide load with the live ones.  Left unused, the compiler hands them out as temporaries while
+				// the load is in flight and then has to wait for that load -- the row request just issued -- before the
+				// first of them is written.  Naming them here keeps the whole landing set reserved until the row is read.
+#pragma unroll
+				for (int q = 0; q < hrtf_dead_regs<SQ>(); q++) {
+					asm volatile("" ::"v"(rawh[q]));
+				}
 			}
 			// gain ramp weights t = f / F and 1 - t of this lane's frames (k_hrtf_uni keeps the 2 FQ values in registers across
 			// the sources; this kernel has none to spare, so they are rebuilt -- the same exact integers, the same product --
@@ -211,10 +256,16 @@ __global__ __launch_bounds__(MW * 64, GAS_HRTF_WAVES_PER_SIMD) void k_hrtf_multi
 			float lf = lane_f;
 			asm volatile("" : "+v"(lf));
 #pragma unroll
-			for (int q = 0; q < FQ; q++) {
+			for (int q = 0; q < hrtf_unkept_regs<SQ>(); q++) {
 				const float mono = (raw[q].left + raw[q].right) * 0.5f;
 				const float t = (lf + (float)(64 * q)) * (1.0f / (float)F);
-				xq[HQ + q] = mono * (g1 * t + (1 - t) * g0);
+				xq[HQ + q] = window_sample(mono, ramp_weight(g0, g1, t, 1 - t));
+			}
+#pragma unroll
+			for (int q = hrtf_unkept_regs<SQ>(); q < FQ; q++) {
+				const float mono = (raw[q].left + raw[q].right) * 0.5f;
+				const float t = (lf + (float)(64 * q)) * (1.0f / (float)F);
+				xq[HQ + q] = window_sample_kept(mono, ramp_weight(g0, g1, t, 1 - t));
 			}
 			// new history = x_full[F .. F + HL): to the slot's row, or (HIST_LDS) parked for the next block and written
 			// back by the last one only
@@ -224,14 +275,18 @@ __global__ __launch_bounds__(MW * 64, GAS_HRTF_WAVES_PER_SIMD) void k_hrtf_multi
 				store_history<HQ>(my_hist + (size_t)i * HL, lane, &xq[FQ]);
 			}
 			// the landing registers are free again: the next source of this block, or the first one of the next block
-			// (whose history row this wave stored earlier in this block, or just above when it has a single source)
+			// (whose history row this wave stored earlier in this block, or just above when it has a single source).
+			// The request is issued on EVERY trip, so that the wave's vector-memory queue holds the same operations in the
+			// same order on every path through a trip ("The load queue of a source trip", above the kernel).  On the one
+			// trip nothing follows (last source of the last block) it asks once more for this wave's first row of this
+			// block, which nothing consumes: src_wrap is this block's table then, never one past the last.
 			const bool wrap = i + 1 == cnt;
-			if (!wrap || b + 1 < K) {
+			{
 				const uint32_t ni = wrap ? 0u : i + 1;
-				const uint32_t nslot = (uint32_t)__builtin_amdgcn_readlane((int)my_slot, (int)ni);
 				const uint32_t nrow = (uint32_t)__builtin_amdgcn_readlane((int)my_row, (int)ni);
-				const gas_audio_frame *nsrc = mb.src[wrap ? b + 1 : b] + (size_t)nrow * F;
-				if (!HIST_LDS || (b == 0 && !wrap)) { // HIST_LDS: only block 0 reads history rows from memory
+				const gas_audio_frame *nsrc = (wrap ? src_wrap : src_b) + (size_t)nrow * F;
+				if constexpr (!HIST_LDS) { // (HIST_LDS: no history row comes from memory inside the loop)
+					const uint32_t nslot = (uint32_t)__builtin_amdgcn_readlane((int)my_slot, (int)ni);
 					load_history<HQ>(st.hrtf_hist + (size_t)nslot * HL, lane, rawh);
 				}
 #pragma unroll
@@ -249,10 +304,11 @@ __global__ __launch_bounds__(MW * 64, GAS_HRTF_WAVES_PER_SIMD) void k_hrtf_multi
 #if GAS_MULTI_L2_PREFETCH
 			// The row of the source TWO trips ahead is pulled towards the L2 by one dword load per 128-byte line (no
 			// landing set: the loaded word is never looked at), issued behind this trip's requests AND behind the
-			// table row's (the wave's vector-memory results return in order, and the compiler's wait in front of the spectral
-			// products is vmcnt(0): anything requested before them would be waited for there).  A trip's own requests then find their lines a cache hit
-			// away instead of an HBM round trip under load (the trip is latency-bound with one source in flight per wave,
-			// profiles/r03_notes.md).  The word requested a trip ago is retired first (it has landed long since).
+			// table row's (the wave's vector-memory results return in order; when this was measured the compiler's wait in
+			// front of the spectral products was vmcnt(0), so anything requested before them was waited for there -- it now
+			// leaves the row request in flight, and this conditional touch would put a path-dependent operation back into
+			// the queue).  A trip's own requests then find their lines a cache hit away instead of an HBM round trip under
+			// load (profiles/r03_notes.md).  The word requested a trip ago is retired first (it has landed long since).
 			{
 				asm volatile("" ::"v"(pf_word));
 				const uint32_t i2 = i + 2, over = i2 / cnt, ni2 = i2 - over * cnt; // cnt >= 1; over <= 2

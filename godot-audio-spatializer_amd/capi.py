@@ -484,6 +484,7 @@ EXPORTS = [
     "gas_ctx_reserve_conv",
     "gas_conv_ir_load",
     "gas_conv_ir_free",
+    "gas_conv_ir_get_info",
     "gas_conv_create",
     "gas_conv_destroy",
     "gas_conv_reset",
@@ -595,6 +596,7 @@ def load_library():
     L.gas_ctx_reserve_conv.argtypes = [vp, u32, u32]
     L.gas_conv_ir_load.argtypes = [vp, vp, u32, u32, C.POINTER(u32)]
     L.gas_conv_ir_free.argtypes = [vp, u32]
+    L.gas_conv_ir_get_info.argtypes = [vp, u32, C.POINTER(u32), C.POINTER(u32)]
     L.gas_conv_create.argtypes = [vp, u32, C.POINTER(u32)]
     L.gas_conv_destroy.argtypes = [vp, u32]
     L.gas_conv_reset.argtypes = [vp, u32]
@@ -1003,7 +1005,7 @@ class SpatializerContext:
         self._check(self.lib.gas_ctx_reserve_conv(self.h, int(convolvers), int(max_ir_taps)), "gas_ctx_reserve_conv")
 
     def conv_ir_load(self, ir):
-        """ir float32 [taps] or [channels][taps], channels 1 or 2 -> IR id."""
+        """ir float32 [taps] or [channels][taps], channels 1, 2 or 4 (true stereo: LL, LR, RL, RR) -> IR id."""
         h = np.ascontiguousarray(np.atleast_2d(np.asarray(ir, dtype=np.float32)))
         assert h.ndim == 2
         out = C.c_uint32()
@@ -1012,6 +1014,12 @@ class SpatializerContext:
 
     def conv_ir_free(self, ir):
         self._check(self.lib.gas_conv_ir_free(self.h, int(ir)), "gas_conv_ir_free")
+
+    def conv_ir_get_info(self, ir):
+        """-> (channels, taps) as the IR was loaded."""
+        ch, taps = C.c_uint32(), C.c_uint32()
+        self._check(self.lib.gas_conv_ir_get_info(self.h, int(ir), C.byref(ch), C.byref(taps)), "gas_conv_ir_get_info")
+        return ch.value, taps.value
 
     def conv_create(self, ir):
         out = C.c_uint32()

@@ -318,7 +318,7 @@ struct gas_ctx {
 	// reservation and the IR calls never run concurrently with a callback.
 	struct ConvIr {
 		float2 *H = nullptr; // [channels][k_ir][GAS_CONV_BINS]; null: a free id
-		uint32_t channels = 0, k_ir = 0;
+		uint32_t channels = 0, taps = 0, k_ir = 0;
 		uint32_t users = 0; // references from instances: a state, a fade's target and a pending target each count
 	};
 	struct ConvTarget {
@@ -4445,7 +4445,7 @@ int gas_ctx_reserve_conv(gas_ctx *c, uint32_t convolvers, uint32_t max_ir_taps) 
 }
 
 int gas_conv_ir_load(gas_ctx *c, const float *ir, uint32_t channels, uint32_t taps, uint32_t *out_ir) {
-	if (!c || !ir || !out_ir || (channels != 1 && channels != 2) || taps == 0) {
+	if (!c || !ir || !out_ir || (channels != 1 && channels != 2 && channels != 4) || taps == 0) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
 	if (c->conv_count == 0) {
@@ -4465,6 +4465,7 @@ int gas_conv_ir_load(gas_ctx *c, const float *ir, uint32_t channels, uint32_t ta
 	const uint32_t F = c->cfg.frames;
 	gas_ctx::ConvIr rec;
 	rec.channels = channels;
+	rec.taps = taps;
 	rec.k_ir = (taps + F - 1) / F;
 	Mem tmp; // frees d_ir on every way out
 	float *d_ir = nullptr;
@@ -4505,6 +4506,22 @@ int gas_conv_ir_free(gas_ctx *c, uint32_t ir) {
 	GAS_HIP(c, hipStreamSynchronize(c->stream)); // calls still queued may read the spectra
 	c->mem.drop(c->conv_irs[ir].H);
 	c->conv_irs[ir] = gas_ctx::ConvIr{};
+	return GAS_OK;
+}
+
+int gas_conv_ir_get_info(gas_ctx *c, uint32_t ir, uint32_t *out_channels, uint32_t *out_taps) {
+	if (!c) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (!conv_ir_live(c, ir)) {
+		return GAS_ERR_BAD_SLOT;
+	}
+	if (out_channels) {
+		*out_channels = c->conv_irs[ir].channels;
+	}
+	if (out_taps) {
+		*out_taps = c->conv_irs[ir].taps;
+	}
 	return GAS_OK;
 }
 
@@ -4696,14 +4713,14 @@ int gas_conv_process(gas_ctx *c, const uint32_t *convs, uint32_t n, const gas_au
 		e.slot = convs[i];
 		e.pos = k.pos + 1 == K ? 0 : k.pos + 1;
 		e.k_ir = ir.k_ir;
-		e.stereo = ir.channels == 2 ? 1u : 0u;
+		e.mode = gas_conv_mode(ir.channels);
 		e.dry = k.dry;
 		e.wet = k.wet;
 		if (k.fade_n) { // call fade_pos of fade_n: frame i has s = (float)(fade_pos F + i) * (1.0f / (float)(fade_n F))
 			const gas_ctx::ConvIr &irb = c->conv_irs[k.to.ir];
 			e.HB = k.to.ir == k.ir ? nullptr : irb.H; // a level-only fade: the wet sum is computed once
 			e.k_irB = irb.k_ir;
-			e.stereoB = irb.channels == 2 ? 1u : 0u;
+			e.modeB = gas_conv_mode(irb.channels);
 			e.dryB = k.to.dry;
 			e.wetB = k.to.wet;
 			e.fade_t0 = k.fade_pos * F;

@@ -513,20 +513,25 @@ hipError_t gas_launch_hrtf_table(hipStream_t stream, const float *d_hrir, uint32
 // transform: 512 float2, bin k at [k], the real Nyquist bin parked in the (zero) imaginary part of DC.
 #define GAS_CONV_BINS 512
 #define GAS_CONV_MAX_CHUNKS 32
+enum : uint32_t { GAS_CONV_MONO = 0, GAS_CONV_STEREO = 1, GAS_CONV_TRUE_STEREO = 2 }; // an IR of 1, 2 or 4 channels
+__host__ __device__ inline uint32_t gas_conv_mode(uint32_t channels) {
+	return channels == 4 ? GAS_CONV_TRUE_STEREO : channels == 2 ? GAS_CONV_STEREO : GAS_CONV_MONO;
+}
 struct gas_conv_entry { // one named instance of a gas_conv_process call
 	const float2 *H; // its IR's spectra [channels][k_ir][GAS_CONV_BINS], scaled by 1/512
 	uint32_t slot; // instance: ring [slot][ear][K][GAS_CONV_BINS], previous block [slot][ear][512]
 	uint32_t pos; // ring position this block's spectrum goes to
 	uint32_t k_ir; // partitions of the IR, 1 .. K
-	uint32_t stereo; // 1: ear e uses channel e; 0: both use channel 0
+	uint32_t mode; // GAS_CONV_MONO: both ears use channel 0; _STEREO: ear e uses channel e; _TRUE_STEREO: 2 i + e, both inputs i
 	float dry, wet;
 	// A fade in progress (gas_conv_fade_to): the fields above are state A, these state B; all zero where settled.
 	const float2 *HB; // B's spectra; null where B names A's IR (a level-only fade: one wet sum serves both states)
-	uint32_t k_irB, stereoB;
+	uint32_t k_irB, modeB;
 	float dryB, wetB;
 	uint32_t fade_t0; // frames of the fade before this call's frame 0: b F
 	float fade_inv; // 1 / (N F), so that frame i has s = (float)(fade_t0 + i) * fade_inv; 0: settled
 };
+static_assert(sizeof(gas_conv_entry) == 64, "the call travels by value as a kernel argument (DESIGN.md 3.5k quotes its size)");
 struct gas_conv_call { // passed by value: a device-memory call only enqueues, so nothing it reads may live in reused staging
 	gas_conv_entry e[GAS_MAX_CONVOLVERS];
 	uint8_t fading[GAS_MAX_CONVOLVERS]; // indices of the entries with a fade in progress, in call order (gas_launch_conv)

@@ -26,6 +26,12 @@
 //   k_conv_inverse_fade    a second launch over the fading instances only, four waves (state x ear): both sums
 //                          transformed back side by side, out = (1 - s)(dry_A in + wet_A y^A) + s (dry_B in + wet_B y^B)
 // while the settled instances of the call stay on k_conv_inverse; a call without a fade launches what it always did.
+// A four-channel ("true stereo") IR, y_e = dry x_e + wet sum_j (h_0e[j] x_0[t - j] + h_1e[j] x_1[t - j]), changes the
+// middle launch only: a call that names one anywhere launches
+//   k_conv_mac_ts          in place of k_conv_mac<>: a true-stereo row reads both ears' rings and two channels' spectra
+//                          (a direct and a cross accumulator, added once per chunk); every other row, state B's included,
+//                          runs the walk above with the bits above
+// and a call that names none launches what it always did.  Rings, partial sums and the inverse stages are the same.
 // Vector stores only, no atomics; every sum has a fixed order, so two runs give the same bits.
 #include "gas_hrtf_wave.h"
 
@@ -129,7 +135,7 @@ __device__ __forceinline__ void conv_mac(float4 &acc, const float4 x, const floa
 
 // One workgroup's chunk of the sum over an IR (spectra Hs, k_ir partitions) for one ear of the instance in `slot`, into
 // row `row` of the call's partial sums.  The chunk split is a function of k_ir alone.
-__device__ __forceinline__ void conv_mac_chunk(const gas_conv_pool &pool, const float2 *__restrict__ Hs, uint32_t k_ir, uint32_t stereo, uint32_t slot, uint32_t pos, uint32_t ear, uint32_t row) {
+__device__ __forceinline__ void conv_mac_chunk(const gas_conv_pool &pool, const float2 *__restrict__ Hs, uint32_t k_ir, uint32_t mode, uint32_t slot, uint32_t pos, uint32_t ear, uint32_t row) {
 	const uint32_t len = gas_conv_chunk_len(k_ir);
 	const uint32_t k0 = blockIdx.x * len;
 	if (k0 >= k_ir) { // this IR has fewer chunks than the call's longest
@@ -138,7 +144,7 @@ __device__ __forceinline__ void conv_mac_chunk(const gas_conv_pool &pool, const 
 	const uint32_t k1 = k0 + len < k_ir ? k0 + len : k_ir;
 	const uint32_t K = pool.K;
 	const float4 *X = reinterpret_cast<const float4 *>(pool.ring + (size_t)(slot * 2 + ear) * K * GAS_CONV_BINS) + threadIdx.x;
-	const float4 *H = reinterpret_cast<const float4 *>(Hs + (size_t)(ear & stereo) * k_ir * GAS_CONV_BINS) + threadIdx.x;
+	const float4 *H = reinterpret_cast<const float4 *>(Hs + (size_t)(ear & mode) * k_ir * GAS_CONV_BINS) + threadIdx.x; // mono or stereo
 	constexpr uint32_t ROW = GAS_CONV_BINS / 2; // float4 per spectrum
 	const bool packed = threadIdx.x == 0;
 	float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -173,12 +179,80 @@ __global__ __launch_bounds__(256) void k_conv_mac(gas_conv_call call, gas_conv_p
 		const uint32_t i = call.fading[(ie - rows) >> 1];
 		const gas_conv_entry en = call.e[i];
 		if (en.HB) { // a level-only fade has no second sum
-			conv_mac_chunk(pool, en.HB, en.k_irB, en.stereoB, en.slot, en.pos, ear, 2 * GAS_MAX_CONVOLVERS + i * 2 + ear);
+			conv_mac_chunk(pool, en.HB, en.k_irB, en.modeB, en.slot, en.pos, ear, 2 * GAS_MAX_CONVOLVERS + i * 2 + ear);
 		}
 		return;
 	}
 	const gas_conv_entry en = call.e[ie >> 1];
-	conv_mac_chunk(pool, en.H, en.k_ir, en.stereo, en.slot, en.pos, ear, ie);
+	conv_mac_chunk(pool, en.H, en.k_ir, en.mode, en.slot, en.pos, ear, ie);
+}
+
+// TRUE STEREO (an IR of four channels, c = 2 i + e from input ear i to output ear e): the same row and the same chunk
+// split, but output ear `ear` walks both ears' rings.  The direct term (input ear `ear`) is conv_mac_chunk's sum, FMA for
+// FMA, in one accumulator; the cross term (the other input ear) goes ascending k into a second one; the chunk's sum is
+// direct + cross, one add per component.  Four loads per partition, so four partitions per trip keep conv_mac_chunk's
+// sixteen 16-byte loads in flight, and the two accumulators are two independent FMA chains.
+__device__ __forceinline__ void conv_mac_chunk_ts(const gas_conv_pool &pool, const float2 *__restrict__ Hs, uint32_t k_ir, uint32_t slot, uint32_t pos, uint32_t ear, uint32_t row) {
+	const uint32_t len = gas_conv_chunk_len(k_ir);
+	const uint32_t k0 = blockIdx.x * len;
+	if (k0 >= k_ir) {
+		return;
+	}
+	const uint32_t k1 = k0 + len < k_ir ? k0 + len : k_ir;
+	const uint32_t K = pool.K;
+	const size_t ring = (size_t)K * GAS_CONV_BINS, chan = (size_t)k_ir * GAS_CONV_BINS;
+	const float4 *Xd = reinterpret_cast<const float4 *>(pool.ring + (size_t)(slot * 2 + ear) * ring) + threadIdx.x;
+	const float4 *Xc = reinterpret_cast<const float4 *>(pool.ring + (size_t)(slot * 2 + (ear ^ 1)) * ring) + threadIdx.x;
+	const float4 *Hd = reinterpret_cast<const float4 *>(Hs + (size_t)(2 * ear + ear) * chan) + threadIdx.x;
+	const float4 *Hc = reinterpret_cast<const float4 *>(Hs + (size_t)(2 * (ear ^ 1) + ear) * chan) + threadIdx.x;
+	constexpr uint32_t ROW = GAS_CONV_BINS / 2;
+	const bool packed = threadIdx.x == 0;
+	float4 direct = make_float4(0.0f, 0.0f, 0.0f, 0.0f), cross = direct;
+	uint32_t k = k0;
+	auto ring_row = [&](uint32_t kk) { return (size_t)(pos >= kk ? pos - kk : pos + K - kk) * ROW; };
+	constexpr int U = 4;
+	for (; k + U <= k1; k += U) {
+		float4 xd[U], xc[U], hd[U], hc[U];
+#pragma unroll
+		for (int u = 0; u < U; u++) {
+			const size_t r = ring_row(k + u), p = (size_t)(k + u) * ROW;
+			xd[u] = Xd[r];
+			xc[u] = Xc[r];
+			hd[u] = Hd[p];
+			hc[u] = Hc[p];
+		}
+#pragma unroll
+		for (int u = 0; u < U; u++) {
+			conv_mac(direct, xd[u], hd[u], packed);
+			conv_mac(cross, xc[u], hc[u], packed);
+		}
+	}
+	for (; k < k1; k++) {
+		const size_t r = ring_row(k), p = (size_t)k * ROW;
+		conv_mac(direct, Xd[r], Hd[p], packed);
+		conv_mac(cross, Xc[r], Hc[p], packed);
+	}
+	reinterpret_cast<float4 *>(pool.ypart + ((size_t)row * pool.max_chunks + blockIdx.x) * GAS_CONV_BINS)[threadIdx.x] = make_float4(direct.x + cross.x, direct.y + cross.y, direct.z + cross.z, direct.w + cross.w);
+}
+
+// The form a call launches when one of its entries names a four-channel IR, as state A or B: rows of one- and
+// two-channel IRs run conv_mac_chunk, so their bits are k_conv_mac's.  Rows past `rows` are the fading entries' state B.
+__global__ __launch_bounds__(256) void k_conv_mac_ts(gas_conv_call call, gas_conv_pool pool, uint32_t rows) {
+	const uint32_t ie = blockIdx.y, ear = ie & 1;
+	const bool stateB = ie >= rows;
+	const uint32_t i = stateB ? call.fading[(ie - rows) >> 1] : ie >> 1;
+	const gas_conv_entry en = call.e[i];
+	if (stateB && !en.HB) { // a level-only fade has no second sum
+		return;
+	}
+	const float2 *Hs = stateB ? en.HB : en.H;
+	const uint32_t k_ir = stateB ? en.k_irB : en.k_ir, mode = stateB ? en.modeB : en.mode;
+	const uint32_t row = stateB ? 2 * GAS_MAX_CONVOLVERS + i * 2 + ear : ie;
+	if (mode == GAS_CONV_TRUE_STEREO) { // uniform over the workgroup
+		conv_mac_chunk_ts(pool, Hs, k_ir, en.slot, en.pos, ear, row);
+	} else {
+		conv_mac_chunk(pool, Hs, k_ir, mode, en.slot, en.pos, ear, row);
+	}
 }
 
 // One wave's share of the inverse stage: `chunks` partial sums from yp added in chunk order, untangled and transformed
@@ -332,13 +406,16 @@ hipError_t gas_launch_conv(hipStream_t stream, gas_conv_call &call, uint32_t n, 
 		return hipSuccess;
 	}
 	uint32_t chunks = 1, fading = 0;
+	bool true_stereo = false; // an entry names a four-channel IR, as state A or as a state B with a sum of its own
 	for (uint32_t i = 0; i < n; i++) {
 		const gas_conv_entry &en = call.e[i];
 		uint32_t c = gas_conv_chunks(en.k_ir);
+		true_stereo |= en.mode == GAS_CONV_TRUE_STEREO;
 		if (en.fade_inv != 0.0f) {
 			call.fading[fading++] = (uint8_t)i;
 			const uint32_t cb = en.HB ? gas_conv_chunks(en.k_irB) : 0;
 			c = cb > c ? cb : c;
+			true_stereo |= en.HB && en.modeB == GAS_CONV_TRUE_STEREO;
 		}
 		chunks = c > chunks ? c : chunks;
 	}
@@ -347,7 +424,9 @@ hipError_t gas_launch_conv(hipStream_t stream, gas_conv_call &call, uint32_t n, 
 	if (e != hipSuccess) {
 		return e;
 	}
-	if (fading == 0) {
+	if (true_stereo) {
+		hipLaunchKernelGGL(k_conv_mac_ts, dim3(chunks, (n + fading) * 2), dim3(256), 0, stream, call, pool, n * 2);
+	} else if (fading == 0) {
 		hipLaunchKernelGGL(k_conv_mac<false>, dim3(chunks, n * 2), dim3(256), 0, stream, call, pool, n * 2);
 	} else {
 		hipLaunchKernelGGL(k_conv_mac<true>, dim3(chunks, (n + fading) * 2), dim3(256), 0, stream, call, pool, n * 2);

@@ -696,13 +696,23 @@ int gas_process_block_buses(gas_ctx *ctx, const gas_audio_frame *src, const uint
  *
  *     y_e[t] = dry * x_e[t] + wet * sum_{j=0}^{T-1} h_e[j] * x_e[t - j]
  *
- * The ears are independent (no cross-feed).  dry and wet are read once per call, with no ramp, as the effect settings
+ * With such an IR the ears are independent (no cross-feed).  NEW: an IR of four channels ("true stereo", the form
+ * measured room responses are commonly shipped in) adds the cross-feed.  Its channel c = 2 * i + e is the response from
+ * input ear i to output ear e, so the order is LL, LR, RL, RR, and an instance that names it computes
+ *
+ *     y_e[t] = dry * x_e[t] + wet * sum_{j=0}^{T-1} ( h_{0e}[j] * x_0[t - j] + h_{1e}[j] * x_1[t - j] )
+ *
+ * with everything else as for one and two channels: a four-channel IR is legal wherever an IR is named
+ * (gas_conv_create, gas_conv_set_ir, gas_conv_fade_to as state A, state B or a pending target, in any combination with
+ * one- and two-channel IRs, and a level-only fade).  [h_L, 0, 0, h_R] gives the bits of the two-channel [h_L, h_R].
+ * dry and wet are read once per call, with no ramp, as the effect settings
  * are; the defaults dry = 0, wet = 1 suit a send bus.  The IR is the one the instance names when the call is made,
  * applied over the whole history the instance holds: gas_conv_set_ir between two calls is a hard switch at the block
  * boundary, and the history stays, because it does not depend on the IR.  Sums are f32 in a fixed order: two runs of
  * the same calls give the same bits, and an instance's output does not depend on what else a call names.
- * Out of scope: four-channel ("true stereo") IRs, non-uniform partitioning, gas_multi (a bus reverb belongs on the
- * root, after the gather), the host layer and godot_module/. */
+ * Out of scope: sharing one load of the two input ears between the two output ears of a true stereo instance (each
+ * output ear reads both rings itself), non-uniform partitioning, gas_multi (a bus reverb belongs on the root, after the
+ * gather), the host layer and godot_module/. */
 #define GAS_MAX_CONVOLVERS 24 /* GAS_MAX_BUSES x GAS_MAX_CHANNELS_PER_BUS */
 /* Sizes the instance pool: `convolvers` instances (<= GAS_MAX_CONVOLVERS) for IRs of up to max_ir_taps taps
  * (<= 1 048 576 = 2^20, 21.8 s at 48 kHz).  Same contract as the gas_ctx_reserve_fx_* calls: main thread, never
@@ -712,19 +722,24 @@ int gas_process_block_buses(gas_ctx *ctx, const gas_audio_frame *src, const uint
  *   per context:   4096 + 393 216 min(32, ceil(K / 16)) + 384 cfg.frames of device memory (a twiddle table, one call's
  *                  partial sums -- two per instance and ear, for a call of 24 fading instances -- and staging) and
  *                  384 cfg.frames of pinned host memory (staging of host-memory calls);
- *   per IR (allocated by gas_conv_ir_load): 4096 channels ceil(taps / cfg.frames) of device memory.
+ *   per IR (allocated by gas_conv_ir_load): 4096 channels ceil(taps / cfg.frames) of device memory, so a four-channel
+ *                  IR takes four times a mono IR's.
  * (0, 0) releases everything; one of the two zero and the other not, convolvers > GAS_MAX_CONVOLVERS or max_ir_taps >
  * 2^20 is GAS_ERR_INVALID_ARGUMENT, and so is any call while an instance or an IR exists.  A HIP failure is
  * GAS_ERR_DEVICE with nothing reserved.  A context that never reserves pays nothing. */
 int gas_ctx_reserve_conv(gas_ctx *ctx, uint32_t convolvers, uint32_t max_ir_taps);
 /* ir = [channels][taps] f32 in host memory.  Allocates the IR's partition spectra and transforms them on the device;
  * returns when they are ready (`ir` has been consumed).  Main thread, like gas_hrtf_load.  Many instances may share
- * one IR.  GAS_ERR_INVALID_ARGUMENT: taps == 0, taps > max_ir_taps, channels other than 1 or 2, a value that is not
- * finite, a NULL pointer.  GAS_ERR_UNSUPPORTED_CHAIN: nothing is reserved.  GAS_ERR_DEVICE: a HIP failure (no IR). */
-int gas_conv_ir_load(gas_ctx *ctx, const float *ir /* [channels][taps] f32 */, uint32_t channels /* 1 or 2 */, uint32_t taps, uint32_t *out_ir);
+ * one IR.  channels is 1, 2 or 4 (LL, LR, RL, RR; the rule above).  GAS_ERR_INVALID_ARGUMENT: taps == 0, taps >
+ * max_ir_taps, channels other than 1, 2 or 4, a value in any channel that is not finite, a NULL pointer, each with
+ * nothing loaded.  GAS_ERR_UNSUPPORTED_CHAIN: nothing is reserved.  GAS_ERR_DEVICE: a HIP failure (no IR). */
+int gas_conv_ir_load(gas_ctx *ctx, const float *ir /* [channels][taps] f32 */, uint32_t channels /* 1, 2 or 4 */, uint32_t taps, uint32_t *out_ir);
 /* Main thread; waits for the stream.  GAS_ERR_BAD_SLOT: no such IR.  GAS_ERR_INVALID_ARGUMENT: an instance still names
  * it (nothing is freed). */
 int gas_conv_ir_free(gas_ctx *ctx, uint32_t ir);
+/* NEW: what gas_conv_ir_load was given, in the manner of gas_stream_get_info.  Either output may be NULL.  Touches no
+ * device state.  GAS_ERR_BAD_SLOT: no such IR.  GAS_ERR_INVALID_ARGUMENT: a NULL ctx. */
+int gas_conv_ir_get_info(gas_ctx *ctx, uint32_t ir, uint32_t *out_channels, uint32_t *out_taps);
 /* Instances come from and go back to the reserved pool; these five calls allocate nothing.  Audio thread, between
  * callbacks.  An instance's ring and previous block are zeroed, in the context's stream order, when it is created and
  * by gas_conv_reset ("x[t] = 0 for all earlier t": the next call is bitwise what a fresh instance gives); levels and IR
@@ -749,8 +764,8 @@ int gas_conv_set_levels(gas_ctx *ctx, uint32_t conv, float dry, float wet);
  * of GAS_FLAG_ER_TAP_FADE stretched over N blocks.  The first frame of the fade is all A, the first frame after it all
  * B; from the (N + 1)-th call on the instance is in state B, bitwise what a hard switch to B gives over the same
  * history.  A call that does not name the instance advances neither its time nor its fade.  fade_blocks == 0 is
- * exactly gas_conv_set_ir followed by gas_conv_set_levels.  Ears and one- or two-channel IRs are handled as above for A
- * and B independently.  A level-only fade (ir = the instance's current IR) is legal and computes the wet sum once.
+ * exactly gas_conv_set_ir followed by gas_conv_set_levels.  Ears and one-, two- or four-channel IRs are handled as above for
+ * A and B independently.  A level-only fade (ir = the instance's current IR) is legal and computes the wet sum once.
  *  - While a fade is in progress another gas_conv_fade_to stores a pending target (the latest wins); the pending fade
  *    starts, with its own fade_blocks, at the first call after the fade in progress has ended, from state B.
  *  - gas_conv_set_ir and gas_conv_set_levels end the fade at once: the state becomes B, a pending target is dropped,

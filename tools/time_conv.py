@@ -14,7 +14,13 @@ come from running this under `rocprofv3 --kernel-trace --stats` in a run of its 
 
 Every instance is mid-fade (gas_conv_fade_to) between two IRs of the same length in every call of the run, the fill
 included: one 4096-call fade started before the first call.  The multiply-accumulate stage then walks the ring once per
-IR (k_conv_mac<true>: twice the reads and twice the partial sums) and the inverse stage is k_conv_inverse_fade."""
+IR (k_conv_mac<true>: twice the reads and twice the partial sums) and the inverse stage is k_conv_inverse_fade.
+
+  python tools/time_conv.py 6 2.0 512 --true-stereo        (combines with --fading)
+
+Every instance gets a four-channel IR of its own (LL, LR, RL, RR).  The multiply-accumulate stage is k_conv_mac_ts: per
+instance and output ear it reads 2 k_ir spectra of the rings (both input ears') and 2 k_ir of the IR, twice the
+two-channel bytes, and writes the same partial sums."""
 import json
 import sys
 import time
@@ -39,6 +45,7 @@ def main(argv):
     n, seconds, F = int(argv[0]), float(argv[1]), int(argv[2])
     probe = "noprobe" not in argv[3:]
     fading = "--fading" in argv[3:]
+    channels = 4 if "--true-stereo" in argv[3:] else 2
     taps = int(round(seconds * RATE))
     k_ir = -(-taps // F)
     assert not fading or WARMUP + STEPS + k_ir <= 4096  # GAS_CONV_MAX_FADE_BLOCKS: the fade outlasts the run
@@ -46,10 +53,10 @@ def main(argv):
     ctx = gas.SpatializerContext(max_sources=4, frames=F, mix_rate=float(RATE))
     ctx.reserve_conv(n, taps)
     env = np.exp(-6.0 * np.arange(taps) / taps)
-    convs = [ctx.conv_create(ctx.conv_ir_load((rng.standard_normal((2, taps)) * env / np.sqrt(taps)).astype(np.float32))) for _ in range(n)]
+    convs = [ctx.conv_create(ctx.conv_ir_load((rng.standard_normal((channels, taps)) * env / np.sqrt(taps)).astype(np.float32))) for _ in range(n)]
     if fading:
         for k in convs:
-            ctx.conv_fade_to(k, ctx.conv_ir_load((rng.standard_normal((2, taps)) * env / np.sqrt(taps)).astype(np.float32)), 0.25, 0.75, 4096)
+            ctx.conv_fade_to(k, ctx.conv_ir_load((rng.standard_normal((channels, taps)) * env / np.sqrt(taps)).astype(np.float32)), 0.25, 0.75, 4096)
     x = torch.from_numpy(rng.uniform(-1, 1, (n, F, 2)).astype(np.float32)).cuda()
     y = torch.zeros_like(x)
     torch.cuda.synchronize()
@@ -64,9 +71,9 @@ def main(argv):
     out = y.cpu().numpy()
     assert np.isfinite(out).all() and np.abs(out).max() > 0
     sums = 2 if fading else 1  # walks over the ring: one per IR
-    rd = sums * n * 2 * k_ir * 2 * 4096
+    rd = sums * n * 2 * (channels // 2) * k_ir * 2 * 4096  # per output ear: ring and IR spectra of every input ear it hears
     wr = sums * n * 2 * chunks(k_ir) * 4096
-    res = {"instances": n, "ir_seconds": seconds, "frames": F, "fading": fading, "taps": taps, "k_ir": k_ir, "steps": STEPS, "mac_read_bytes": rd, "mac_write_bytes": wr, "state_bytes": n * (8192 * k_ir + 4096) + sums * n * 2 * k_ir * 4096, "call_us": {"median": round(float(np.median(ts)), 1), "min": round(min(ts), 1), "max": round(max(ts), 1)}}
+    res = {"instances": n, "ir_seconds": seconds, "frames": F, "fading": fading, "true_stereo": channels == 4, "taps": taps, "k_ir": k_ir, "steps": STEPS, "mac_read_bytes": rd, "mac_write_bytes": wr, "state_bytes": n * (8192 * k_ir + 4096) + sums * n * channels * k_ir * 4096, "call_us": {"median": round(float(np.median(ts)), 1), "min": round(min(ts), 1), "max": round(max(ts), 1)}}
     if probe:
         us = ctx.bandwidth_probe(rd, wr)
         res["probe_us"] = round(us, 2)

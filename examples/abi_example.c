@@ -87,7 +87,38 @@ int main(void) {
 		rc |= gas_conv_set_levels(ctx, conv, 0.0f, 1.0f); /* the defaults: a send bus carries the wet signal alone */
 		rc |= gas_conv_process(ctx, &conv, 1, out, wet, F, GAS_MEM_HOST);
 		printf("gas_conv_process: %s; wet[100] = (%f, %f)\n", gas_strerror(rc), wet[100].left, wet[100].right);
-		rc |= gas_conv_destroy(ctx, conv);
+		/* no recording at hand: the tail of a box room, built on the device from the room itself.  min_order = 3 leaves
+		 * out what GAS_FX_EARLY_REFLECTIONS plays per source (orders 1 - 2) and the direct sound. */
+		{
+			static float tail[2][3 * F];
+			gas_room_ir d;
+			uint32_t room_ir = 0, channels = 0, taps = 0;
+			memset(&d, 0, sizeof d);
+			for (int a = 0; a < 3; a++) {
+				d.room.basis[a][a] = 1.0f;
+				d.listener.basis[a][a] = 1.0f;
+			}
+			d.room.half_extent[0] = 4.0f;
+			d.room.half_extent[1] = 2.5f;
+			d.room.half_extent[2] = 3.0f;
+			for (int w = 0; w < 6; w++) {
+				d.room.reflectance[w] = 0.8f;
+			}
+			d.room.speed_of_sound = 343.0f;
+			d.room.level = 1.0f;
+			d.source[0] = 1.0f;
+			d.listener.origin[0] = -1.0f;
+			d.ear_spacing = 0.18f;
+			d.min_order = 3;
+			rc |= gas_conv_ir_from_room(ctx, &d, 2, 3 * F, &tail[0][0], &room_ir);
+			rc |= gas_conv_ir_get_info(ctx, room_ir, &channels, &taps);
+			rc |= gas_conv_fade_to(ctx, conv, room_ir, 0.0f, 1.0f, 1); /* one block of fade, then the room's tail */
+			rc |= gas_conv_process(ctx, &conv, 1, out, wet, F, GAS_MEM_HOST);
+			rc |= gas_conv_process(ctx, &conv, 1, out, wet, F, GAS_MEM_HOST);
+			printf("gas_conv_ir_from_room: %s; %u channels, %u taps; tail[0][1000] = %g; wet[100] = (%f, %f)\n", gas_strerror(rc), channels, taps, tail[0][1000], wet[100].left, wet[100].right);
+			rc |= gas_conv_destroy(ctx, conv);
+			rc |= gas_conv_ir_free(ctx, room_ir);
+		}
 		rc |= gas_conv_ir_free(ctx, ir_id);
 		rc |= gas_ctx_reserve_conv(ctx, 0, 0);
 	}

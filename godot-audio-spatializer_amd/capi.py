@@ -398,6 +398,9 @@ ROOM_NONE = 0xFFFFFFFF
 ROOM_DTYPE = np.dtype([("basis", np.float32, (3, 3)), ("origin", np.float32, (3,)), ("half_extent", np.float32, (3,)), ("reflectance", np.float32, (6,)), ("speed_of_sound", np.float32), ("level", np.float32), ("max_order", np.uint32)])
 ER_TAPS_DTYPE = np.dtype([("gain", np.float32, (ER_TAPS,)), ("delay", np.uint32, (ER_TAPS,))])
 assert ROOM_DTYPE.itemsize == 96 and ER_TAPS_DTYPE.itemsize == 64
+# gas_room_ir (gas_conv_ir_from_room)
+ROOM_IR_DTYPE = np.dtype([("room", ROOM_DTYPE), ("source", np.float32, (3,)), ("listener", LISTENER_DTYPE), ("ear_spacing", np.float32), ("min_order", np.uint32), ("max_order", np.uint32)])
+assert ROOM_IR_DTYPE.itemsize == 184
 
 
 def default_rooms(n=1, **kw):
@@ -412,6 +415,19 @@ def default_rooms(n=1, **kw):
     for k, v in kw.items():
         r[k] = v
     return r
+
+
+def default_room_ir(room=None, source=(1.0, 0.5, 0.25), listener_origin=(-1.0, 0.0, 0.0), ear_spacing=0.18, min_order=0, max_order=0):
+    """One gas_room_ir ([1]): `room` (a ROOM_DTYPE entry; default default_rooms()) heard by a listener with the identity
+    basis at listener_origin from an emitter at `source`, ears 18 cm apart, every order the IR's length reaches."""
+    d = np.zeros(1, ROOM_IR_DTYPE)
+    d["room"] = (default_rooms() if room is None else np.asarray(room).reshape(-1))[0]
+    d["source"] = source
+    d["listener"]["basis"] = np.eye(3, dtype=np.float32)
+    d["listener"]["origin"] = listener_origin
+    d["ear_spacing"] = ear_spacing
+    d["min_order"], d["max_order"] = min_order, max_order
+    return d
 
 
 def default_spat3d_config(n=1, **kw):
@@ -485,6 +501,7 @@ EXPORTS = [
     "gas_conv_ir_load",
     "gas_conv_ir_free",
     "gas_conv_ir_get_info",
+    "gas_conv_ir_from_room",
     "gas_conv_create",
     "gas_conv_destroy",
     "gas_conv_reset",
@@ -597,6 +614,7 @@ def load_library():
     L.gas_conv_ir_load.argtypes = [vp, vp, u32, u32, C.POINTER(u32)]
     L.gas_conv_ir_free.argtypes = [vp, u32]
     L.gas_conv_ir_get_info.argtypes = [vp, u32, C.POINTER(u32), C.POINTER(u32)]
+    L.gas_conv_ir_from_room.argtypes = [vp, vp, u32, u32, vp, C.POINTER(u32)]
     L.gas_conv_create.argtypes = [vp, u32, C.POINTER(u32)]
     L.gas_conv_destroy.argtypes = [vp, u32]
     L.gas_conv_reset.argtypes = [vp, u32]
@@ -1020,6 +1038,20 @@ class SpatializerContext:
         ch, taps = C.c_uint32(), C.c_uint32()
         self._check(self.lib.gas_conv_ir_get_info(self.h, int(ir), C.byref(ch), C.byref(taps)), "gas_conv_ir_get_info")
         return ch.value, taps.value
+
+    def conv_ir_from_room(self, desc, channels, taps, want_taps=False, load=True):
+        """An impulse response built on the device from a box room (desc: one ROOM_IR_DTYPE entry).  load: it becomes an
+        IR of this context (a reserve is needed); want_taps: the float32 taps [channels][taps] are read back.  Returns
+        the IR id, the taps, or (id, taps) when both are asked for; load=False and want_taps=False is refused by the
+        library, like every other bad descriptor."""
+        d = np.ascontiguousarray(np.asarray(desc, dtype=ROOM_IR_DTYPE).reshape(-1)[:1])
+        taps_out = np.zeros((int(channels), int(taps)), dtype=np.float32) if want_taps else None
+        out = C.c_uint32()
+        rc = self.lib.gas_conv_ir_from_room(self.h, _np_ptr(d), int(channels), int(taps), _np_ptr(taps_out) if want_taps else None, C.byref(out) if load else None)
+        self._check(rc, "gas_conv_ir_from_room")
+        if load and want_taps:
+            return out.value, taps_out
+        return out.value if load else taps_out
 
     def conv_create(self, ir):
         out = C.c_uint32()

@@ -4444,6 +4444,35 @@ int gas_ctx_reserve_conv(gas_ctx *c, uint32_t convolvers, uint32_t max_ir_taps) 
 	return GAS_OK;
 }
 
+// The common end of gas_conv_ir_load and gas_conv_ir_from_room: d_ir [channels][taps] is on the device, in the context's
+// stream order.  Allocates the partition spectra, transforms, waits (the caller may free d_ir) and enters the IR in the
+// table at the lowest free id.  A failure leaves no IR.
+static int conv_ir_register(gas_ctx *c, const float *d_ir, uint32_t channels, uint32_t taps, uint32_t *out_ir) {
+	const uint32_t F = c->cfg.frames;
+	gas_ctx::ConvIr rec;
+	rec.channels = channels;
+	rec.taps = taps;
+	rec.k_ir = (taps + F - 1) / F;
+	GAS_HIP(c, c->mem.alloc(rec.H, (size_t)channels * rec.k_ir * GAS_CONV_BINS));
+	hipError_t e = gas_launch_conv_ir(c->stream, d_ir, channels, taps, F, c->d_tw, c->conv_pool.w1024, rec.H);
+	e = e != hipSuccess ? e : hipStreamSynchronize(c->stream);
+	if (e != hipSuccess) {
+		c->mem.drop(rec.H);
+		GAS_HIP(c, e);
+	}
+	uint32_t id = 0;
+	while (id < c->conv_irs.size() && c->conv_irs[id].H) {
+		id++;
+	}
+	if (id == c->conv_irs.size()) {
+		c->conv_irs.push_back(rec);
+	} else {
+		c->conv_irs[id] = rec;
+	}
+	*out_ir = id;
+	return GAS_OK;
+}
+
 int gas_conv_ir_load(gas_ctx *c, const float *ir, uint32_t channels, uint32_t taps, uint32_t *out_ir) {
 	if (!c || !ir || !out_ir || (channels != 1 && channels != 2 && channels != 4) || taps == 0) {
 		return GAS_ERR_INVALID_ARGUMENT;
@@ -4462,32 +4491,89 @@ int gas_conv_ir_load(gas_ctx *c, const float *ir, uint32_t channels, uint32_t ta
 	}
 	GAS_TRY(flush_deferred(c));
 	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	const uint32_t F = c->cfg.frames;
-	gas_ctx::ConvIr rec;
-	rec.channels = channels;
-	rec.taps = taps;
-	rec.k_ir = (taps + F - 1) / F;
 	Mem tmp; // frees d_ir on every way out
 	float *d_ir = nullptr;
 	GAS_HIP(c, tmp.alloc(d_ir, floats));
 	GAS_HIP(c, hipMemcpyAsync(d_ir, ir, floats * sizeof(float), hipMemcpyHostToDevice, c->stream));
-	GAS_HIP(c, c->mem.alloc(rec.H, (size_t)channels * rec.k_ir * GAS_CONV_BINS));
-	hipError_t e = gas_launch_conv_ir(c->stream, d_ir, channels, taps, F, c->d_tw, c->conv_pool.w1024, rec.H);
-	e = e != hipSuccess ? e : hipStreamSynchronize(c->stream);
-	if (e != hipSuccess) {
-		c->mem.drop(rec.H);
-		GAS_HIP(c, e);
+	return conv_ir_register(c, d_ir, channels, taps, out_ir);
+}
+
+int gas_conv_ir_from_room(gas_ctx *c, const gas_room_ir *desc, uint32_t channels, uint32_t taps, float *out_taps, uint32_t *out_ir) {
+	if (!c || !desc || (!out_taps && !out_ir) || (channels != 1 && channels != 2) || taps == 0) {
+		return GAS_ERR_INVALID_ARGUMENT;
 	}
-	uint32_t id = 0;
-	while (id < c->conv_irs.size() && c->conv_irs[id].H) {
-		id++;
+	if (out_ir && c->conv_count == 0) {
+		return GAS_ERR_UNSUPPORTED_CHAIN;
 	}
-	if (id == c->conv_irs.size()) {
-		c->conv_irs.push_back(rec);
-	} else {
-		c->conv_irs[id] = rec;
+	if (taps > (out_ir ? c->conv_max_taps : (uint32_t)GAS_CONV_MAX_IR_TAPS)) {
+		return GAS_ERR_INVALID_ARGUMENT;
 	}
-	*out_ir = id;
+	const gas_room &R = desc->room;
+	bool ok = R.speed_of_sound > 0.0f && std::isfinite(R.speed_of_sound) && R.level >= 0.0f && std::isfinite(R.level); // gas_calc_early_reflections' test but for max_order
+	for (int a = 0; a < 3; a++) {
+		ok = ok && R.half_extent[a] > 0.0f && std::isfinite(R.half_extent[a]);
+	}
+	for (int w = 0; w < 6; w++) {
+		ok = ok && R.reflectance[w] >= 0.0f && R.reflectance[w] <= 1.0f;
+	}
+	ok = ok && (desc->max_order == 0 || desc->min_order <= desc->max_order);
+	ok = ok && desc->ear_spacing >= 0.0f && std::isfinite(desc->ear_spacing);
+	for (int a = 0; a < 3; a++) {
+		ok = ok && std::isfinite(R.origin[a]) && std::isfinite(desc->source[a]) && std::isfinite(desc->listener.origin[a]);
+		for (int b = 0; b < 3; b++) {
+			ok = ok && std::isfinite(R.basis[a][b]) && std::isfinite(desc->listener.basis[a][b]);
+		}
+	}
+	gas_room_ir_plan plan;
+	if (!ok || !gas_room_ir_make_plan(*desc, channels, taps, c->cfg.mix_rate, plan)) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	std::vector<double> tables;
+	try {
+		tables.resize(gas_room_ir_table_doubles(plan));
+	} catch (const std::bad_alloc &) {
+		c->last_err = "gas_conv_ir_from_room: out of host memory for the reflectance tables";
+		return GAS_ERR_DEVICE;
+	}
+	gas_room_ir_fill_tables(*desc, plan, tables.data());
+	if (out_ir) { // the pure generator leaves queued callbacks where they are: it touches nothing of theirs
+		GAS_TRY(flush_deferred(c));
+	}
+	GAS_HIP(c, hipSetDevice(c->cfg.device));
+	const size_t n = (size_t)channels * taps;
+	Mem tmp; // frees the three buffers on every way out
+	double *d_tables = nullptr;
+	long long *d_acc = nullptr;
+	float *d_ir = nullptr;
+	GAS_HIP(c, tmp.alloc(d_tables, tables.size()));
+	GAS_HIP(c, tmp.alloc(d_acc, n));
+	GAS_HIP(c, tmp.alloc(d_ir, n));
+	GAS_HIP(c, hipMemcpy(d_tables, tables.data(), tables.size() * sizeof(double), hipMemcpyHostToDevice)); // complete on return
+	const bool timed = c->profiling && c->ev_used + 2 <= c->ev.size(); // gas_profile_enable: the generator's launches count as a dominant launch
+	if (timed) {
+		GAS_HIP(c, hipEventRecord(c->ev[c->ev_used], c->stream));
+	}
+	GAS_HIP(c, gas_launch_room_ir(c->stream, plan, d_tables, d_acc, d_ir));
+	if (timed) {
+		GAS_HIP(c, hipEventRecord(c->ev[c->ev_used + 1], c->stream));
+		c->ev_used += 2;
+	}
+	if (out_ir) { // waits for the stream
+		uint32_t id = 0;
+		GAS_TRY(conv_ir_register(c, d_ir, channels, taps, &id));
+		if (out_taps) {
+			const hipError_t e = hipMemcpy(out_taps, d_ir, n * sizeof(float), hipMemcpyDeviceToHost);
+			if (e != hipSuccess) { // no IR and nothing reported: the caller's out_ir keeps its value
+				c->mem.drop(c->conv_irs[id].H);
+				c->conv_irs[id] = gas_ctx::ConvIr{};
+				GAS_HIP(c, e);
+			}
+		}
+		*out_ir = id;
+		return GAS_OK;
+	}
+	GAS_HIP(c, hipStreamSynchronize(c->stream)); // before anything reaches out_taps: a failed kernel writes nothing there
+	GAS_HIP(c, hipMemcpy(out_taps, d_ir, n * sizeof(float), hipMemcpyDeviceToHost));
 	return GAS_OK;
 }
 

@@ -593,6 +593,23 @@ hipError_t gas_launch_scatter_params(hipStream_t stream, gas_params *table, cons
 hipError_t gas_launch_calc_spatialization(hipStream_t stream, const gas_spatializer3d_config *cfgs, const uint32_t *cfg_index, const gas_source_pose *poses, const gas_listener *listeners, uint32_t n_listeners, const uint32_t *slots, uint32_t n, gas_params *table, uint8_t *was_further, gas_params *out_params, const gas_area_send *areas = nullptr, const float *listener_area_pos = nullptr, gas_audio_frame *out_reverb = nullptr, gas_hrtf_blend *blend_table = nullptr /* GAS_FLAG_HRTF_INTERPOLATE: the slots' bilinear blend rows are written too */);
 // k_calc_er.hip: table == nullptr: nothing but out_taps is written (slots is not read); max_delay = er_ring_frames - frames
 hipError_t gas_launch_calc_er(hipStream_t stream, const gas_room *rooms, const uint32_t *room_index, const gas_source_pose *poses, const gas_listener *listener, const uint32_t *slots, uint32_t n, uint32_t max_delay, float rate, gas_params *table, gas_er_taps *out_taps);
+// k_room_ir.hip: gas_conv_ir_from_room.  The plan is steps 1 and 2 of the rule, made on the host in float64 and passed
+// to the kernel by value.  gas_room_ir_make_plan is false for what the geometry refuses: a point outside the box,
+// d0 < 1e-3, a candidate box of more than GAS_ROOM_IR_MAX_CELLS cells (the descriptor's plain fields are the caller's to
+// check first).  The tables are gas_room_ir_table_doubles(plan) doubles: per axis, index m + N_a, the walls' reflectances
+// an image with that m_a has met.  gas_launch_room_ir zeroes d_acc [channels][taps], accumulates, and writes d_out
+// [channels][taps] f32, all in stream order.
+#define GAS_ROOM_IR_MAX_CELLS (1u << 28)
+struct gas_room_ir_plan {
+	double h[3], s[3], e[2][3]; // half extents, source, receivers (both the listener for one channel), in the room's frame
+	double d0, c, rate, level;
+	uint32_t N[3], cells; // (2 N_x + 1)(2 N_y + 1)(2 N_z + 1) <= GAS_ROOM_IR_MAX_CELLS
+	uint32_t min_order, max_order, channels, taps;
+};
+bool gas_room_ir_make_plan(const gas_room_ir &desc, uint32_t channels, uint32_t taps, float rate, gas_room_ir_plan &plan);
+size_t gas_room_ir_table_doubles(const gas_room_ir_plan &plan);
+void gas_room_ir_fill_tables(const gas_room_ir &desc, const gas_room_ir_plan &plan, double *host_tables);
+hipError_t gas_launch_room_ir(hipStream_t stream, const gas_room_ir_plan &plan, const double *d_tables, long long *d_acc, float *d_out);
 hipError_t gas_launch_sample_sources(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc /* 16.16 step per row for resampled playbacks, or nullptr */, const uint8_t *feed = nullptr /* the feed table when an entry of the list is fed (GAS_FEED_NONE, above) */);
 hipError_t gas_launch_sample_adpcm(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc, bool span /* false: every load decodes from its checkpoint (GAS_ADPCM_SPAN=0) */); // the GAS_PCM_IMA_ADPCM rows of the same list, after gas_launch_sample_sources
 hipError_t gas_launch_sample_qoa(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc, bool span /* false: every load decodes from its record (GAS_QOA_SPAN=0) */); // the GAS_PCM_QOA rows of the same list, after gas_launch_sample_sources

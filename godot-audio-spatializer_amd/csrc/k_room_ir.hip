@@ -1,0 +1,181 @@
+// k_room_ir.hip -- gas_conv_ir_from_room: the impulse response of a box room by the image method, built on the device.
+// The rule is include/gas_amd.h's (gas_conv_ir_from_room), statement by statement in float64; tests/room_ir_ref.py
+// restates it in numpy.
+// Steps 1 and 2 (three points in the room's frame, d0, the candidate box) are a few dozen operations per call and run on
+// the host (gas_room_ir_make_plan); the plan travels to the kernel by value.  A wall's reflectance to the power an image
+// needs comes from per-axis tables of running products, 2 N_a + 1 doubles per axis, built on the host as well: pow() would
+// tie the bits to a library.
+// Shape: one lane per cell of the candidate box, m_z fastest, so a wave's lanes hold neighbouring images whose distances
+// differ by about a room height each and whose taps therefore seldom collide.  A lane masks by |m|_1, computes its image,
+// and per receiver one distance, two shares and two 64-bit integer adds without return on global memory.  No LDS: the two
+// table values that are uniform over most of a wave and the third, read along the lanes, stay in cache.
+// The sums are integers so that no order of arrival can change a bit; a second kernel scales them to float32
+// [channels][taps], the layout gas_launch_conv_ir reads.
+// Bound: 32 B of atomics per image and receiver against about sixty float64 operations; measured figures and the shell
+// variant that would replace the box walk: profiles/room_ir_notes.md.
+#include "gas_internal.h"
+
+#include <cmath>
+
+// No FMA contraction, on the host or on the device: the rule fixes the order of the float64 operations, and
+// `dist - d0` cancels for images close to the direct path.
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr double ROOM_IR_ONE = 4294967296.0; // 2^32: a share of 1 as an integer
+
+__global__ __launch_bounds__(256) void k_room_ir(gas_room_ir_plan p, const double *__restrict__ tables, unsigned long long *__restrict__ acc) {
+	const uint32_t id = blockIdx.x * 256u + threadIdx.x;
+	if (id >= p.cells) {
+		return;
+	}
+	const uint32_t wz = 2u * p.N[2] + 1u, wy = 2u * p.N[1] + 1u;
+	const uint32_t iz = id % wz, rest = id / wz;
+	const uint32_t iy = rest % wy, ix = rest / wy;
+	const int m[3] = {(int)ix - (int)p.N[0], (int)iy - (int)p.N[1], (int)iz - (int)p.N[2]};
+	const uint32_t order = (uint32_t)((m[0] < 0 ? -m[0] : m[0]) + (m[1] < 0 ? -m[1] : m[1]) + (m[2] < 0 ? -m[2] : m[2]));
+	if (order < p.min_order || (p.max_order != 0 && order > p.max_order)) {
+		return;
+	}
+	// step 3
+	const double *tx = tables, *ty = tx + (2u * p.N[0] + 1u), *tz = ty + wy;
+	const double R = (tx[ix] * ty[iy]) * tz[iz];
+	if (!(R > 0.0)) {
+		return; // every share would quantise to 0
+	}
+	double img[3];
+#pragma unroll
+	for (int a = 0; a < 3; a++) {
+		img[a] = (double)(2 * m[a]) * p.h[a] + ((m[a] & 1) ? -p.s[a] : p.s[a]);
+	}
+	// step 4
+	for (uint32_t e = 0; e < p.channels; e++) {
+		const double dx = img[0] - p.e[e][0], dy = img[1] - p.e[e][1], dz = img[2] - p.e[e][2];
+		const double dist = sqrt(dx * dx + dy * dy + dz * dz);
+		const double v = R * p.d0 / fmax(dist, p.d0);
+		const double pos = (dist - p.d0) / p.c * p.rate;
+		const double kf = floor(pos);
+		const double f = pos - kf;
+		// the box bounds pos by taps + a few frames; the comparison in double first keeps the conversion defined whatever comes
+		if (!(kf >= -1.0) || !(kf < (double)p.taps)) {
+			continue;
+		}
+		const long long k = (long long)kf; // -1 .. taps - 1
+		unsigned long long *row = acc + (size_t)e * p.taps;
+		// step 5: shares are in [0, 1], so the integers are in [0, 2^32]
+		const unsigned long long q0 = (unsigned long long)llrint(v * (1.0 - f) * ROOM_IR_ONE);
+		const unsigned long long q1 = (unsigned long long)llrint(v * f * ROOM_IR_ONE);
+		if (k >= 0 && q0 != 0) {
+			atomicAdd(row + k, q0); // result unused: the no-return form
+		}
+		if (k + 1 < (long long)p.taps && q1 != 0) {
+			atomicAdd(row + k + 1, q1);
+		}
+	}
+}
+
+// step 6
+__global__ __launch_bounds__(256) void k_room_ir_scale(const long long *__restrict__ acc, uint32_t n, double level, float *__restrict__ out) {
+	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+	if (i < n) {
+		out[i] = (float)(level * (double)acc[i] * (1.0 / ROOM_IR_ONE));
+	}
+}
+
+// basis^T v, each sum in row order
+void to_room_frame(const float basis[3][3], const double v[3], double out[3]) {
+	for (int a = 0; a < 3; a++) {
+		out[a] = (double)basis[0][a] * v[0] + (double)basis[1][a] * v[1] + (double)basis[2][a] * v[2];
+	}
+}
+
+} // namespace
+
+bool gas_room_ir_make_plan(const gas_room_ir &d, uint32_t channels, uint32_t taps, float rate, gas_room_ir_plan &p) {
+	const gas_room &room = d.room;
+	// step 1
+	double rs[3], rl[3], rr[3], l[3], r[3];
+	for (int a = 0; a < 3; a++) {
+		rs[a] = (double)d.source[a] - (double)room.origin[a];
+		rl[a] = (double)d.listener.origin[a] - (double)room.origin[a];
+		rr[a] = (double)d.listener.basis[a][0];
+		p.h[a] = (double)room.half_extent[a];
+	}
+	to_room_frame(room.basis, rs, p.s);
+	to_room_frame(room.basis, rl, l);
+	to_room_frame(room.basis, rr, r);
+	for (int a = 0; a < 3; a++) {
+		if (!(std::fabs(p.s[a]) <= p.h[a]) || !(std::fabs(l[a]) <= p.h[a])) {
+			return false;
+		}
+	}
+	const double dx = p.s[0] - l[0], dy = p.s[1] - l[1], dz = p.s[2] - l[2];
+	p.d0 = std::sqrt(dx * dx + dy * dy + dz * dz);
+	if (!(p.d0 >= 1e-3)) {
+		return false;
+	}
+	const double half = (double)d.ear_spacing / 2.0;
+	for (int a = 0; a < 3; a++) {
+		p.e[0][a] = channels == 1 ? l[a] : l[a] - half * r[a];
+		p.e[1][a] = channels == 1 ? l[a] : l[a] + half * r[a];
+	}
+	p.c = (double)room.speed_of_sound;
+	p.rate = (double)rate;
+	p.level = (double)room.level;
+	// step 2
+	const double reach = p.c * (double)taps / p.rate + p.d0 + (channels == 2 ? half : 0.0);
+	double cells = 1.0;
+	for (int a = 0; a < 3; a++) {
+		double n = std::floor(reach / (2.0 * p.h[a])) + 1.0;
+		if (d.max_order != 0 && n > (double)d.max_order) {
+			n = (double)d.max_order;
+		}
+		if (!(n <= 134217728.0)) { // 2^27: one axis alone is past the cap (and a float64 that is no uint32 is never converted)
+			return false;
+		}
+		p.N[a] = (uint32_t)n;
+		cells *= 2.0 * n + 1.0; // three factors below 2^29: exact enough to compare, and exact whenever it is below 2^53
+	}
+	if (cells > (double)GAS_ROOM_IR_MAX_CELLS) {
+		return false;
+	}
+	p.cells = (uint32_t)cells;
+	p.min_order = d.min_order;
+	p.max_order = d.max_order;
+	p.channels = channels;
+	p.taps = taps;
+	return true;
+}
+
+size_t gas_room_ir_table_doubles(const gas_room_ir_plan &p) {
+	return (size_t)(2u * p.N[0] + 1u) + (2u * p.N[1] + 1u) + (2u * p.N[2] + 1u);
+}
+
+void gas_room_ir_fill_tables(const gas_room_ir &d, const gas_room_ir_plan &p, double *t) {
+	for (int a = 0; a < 3; a++) {
+		const double neg = (double)d.room.reflectance[2 * a], pos = (double)d.room.reflectance[2 * a + 1];
+		const uint32_t n = p.N[a];
+		t[n] = 1.0; // index m + n; m = 0 meets no wall
+		for (uint32_t m = 1; m <= n; m++) { // step m of a path towards +a meets +a when m is odd, and the other way round
+			t[n + m] = t[n + m - 1] * ((m & 1) ? pos : neg);
+			t[n - m] = t[n - m + 1] * ((m & 1) ? neg : pos);
+		}
+		t += 2u * n + 1u;
+	}
+}
+
+hipError_t gas_launch_room_ir(hipStream_t stream, const gas_room_ir_plan &p, const double *d_tables, long long *d_acc, float *d_out) {
+	const uint32_t n = p.channels * p.taps;
+	hipError_t e = hipMemsetAsync(d_acc, 0, sizeof(long long) * n, stream);
+	if (e != hipSuccess) {
+		return e;
+	}
+	hipLaunchKernelGGL(k_room_ir, dim3((p.cells + 255u) / 256u), dim3(256), 0, stream, p, d_tables, reinterpret_cast<unsigned long long *>(d_acc));
+	e = hipGetLastError();
+	if (e != hipSuccess) {
+		return e;
+	}
+	hipLaunchKernelGGL(k_room_ir_scale, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_acc, n, p.level, d_out);
+	return hipGetLastError();
+}

@@ -740,6 +740,8 @@ int gas_conv_ir_free(gas_ctx *ctx, uint32_t ir);
 /* NEW: what gas_conv_ir_load was given, in the manner of gas_stream_get_info.  Either output may be NULL.  Touches no
  * device state.  GAS_ERR_BAD_SLOT: no such IR.  GAS_ERR_INVALID_ARGUMENT: a NULL ctx. */
 int gas_conv_ir_get_info(gas_ctx *ctx, uint32_t ir, uint32_t *out_channels, uint32_t *out_taps);
+/* NEW: gas_conv_ir_from_room makes an IR on the device from a box room instead of a recording.  It is declared below
+ * gas_calc_early_reflections, whose gas_room and conventions it shares. */
 /* Instances come from and go back to the reserved pool; these five calls allocate nothing.  Audio thread, between
  * callbacks.  An instance's ring and previous block are zeroed, in the context's stream order, when it is created and
  * by gas_conv_reset ("x[t] = 0 for all earlier t": the next call is bitwise what a fresh instance gives); levels and IR
@@ -938,6 +940,63 @@ typedef struct gas_er_taps {
  * than 1 or 2.  GAS_ERR_BAD_SLOT: a slot that is not in use.  n == 0 is GAS_OK.
  * Physics thread: it shares gas_calc_spatialization's lock and staging buffers. */
 int gas_calc_early_reflections(gas_ctx *ctx, const gas_room *rooms, uint32_t n_rooms, const uint32_t *room_index, const gas_source_pose *poses, const gas_listener *listener, const uint32_t *slots, uint32_t n, gas_er_taps *out_taps, int mem);
+
+/* ---- a convolver's impulse response from a box room (it belongs to the gas_conv_* calls above and stands here because
+ * it takes a gas_room and a gas_listener by value) ------------------------------------------------------------------
+ * NEW.  The image-source lattice of Allen & Berkley that gas_calc_early_reflections cuts off at order 2, summed into an
+ * impulse response of `taps` taps on the device and handed straight to the transform gas_conv_ir_load uses.  Levels and
+ * times are gas_calc_early_reflections': tap 0 is the arrival of the direct sound and a reflection's gain is relative to
+ * it, so the ER taps of the sources (orders 1 - 2) and a generated tail with min_order = 3 on the send bus add up to one
+ * room response with nothing counted twice.
+ *
+ * The rule.  Inputs are float32 and are widened to float64; everything up to the final conversion is float64 with no
+ * fused multiply-adds.  h = half_extent, c = speed_of_sound, rate = the context's mix_rate, B = room.basis.
+ *  1. s = B^T (source - origin), l = B^T (listener.origin - origin), r = B^T (listener.basis column 0); d0 = |s - l|.
+ *     Receivers: one channel e_0 = l; two channels e_0 = l - (ear_spacing / 2) r, e_1 = l + (ear_spacing / 2) r.
+ *  2. reach = c taps / rate + d0 + (channels == 2 ? ear_spacing / 2 : 0); N_a = floor(reach / (2 h_a)) + 1, clamped to
+ *     max_order when max_order != 0.  The candidates are the integer triples m with |m_a| <= N_a and min_order <= |m|_1
+ *     (and |m|_1 <= max_order when it is not 0).  No image outside this box can reach tap taps - 1.
+ *  3. Per image, steps 5 and 6 of gas_calc_early_reflections: img_a = 2 m_a h_a + (m_a odd ? -s_a : s_a); R is the
+ *     product over the axes of the +a wall's reflectance p_a times and the -a wall's q_a times, p_a = ceil(m_a / 2),
+ *     q_a = floor(m_a / 2) for m_a > 0, swapped for m_a < 0; each axis' factor is a running product over |m_a| = 1, 2, ...
+ *     and R = (R_x R_y) R_z.  m = 0 is the direct sound, R = 1.
+ *  4. Per receiver e: dist = |img - e_e|; v = R d0 / max(dist, d0), so v <= 1 (the clamp only ever bites for an ear that
+ *     is nearer than the head's centre); pos = ((dist - d0) / c) rate, which is gas_calc_early_reflections' fr;
+ *     k = floor(pos), f = pos - k; tap k receives v (1 - f) and tap k + 1 receives v f.  A tap index outside [0, taps) is
+ *     dropped on its own: an image with k = -1 still feeds tap 0, so the rule is continuous in every input.
+ *  5. Each of the two shares is quantised to q = llrint(share 2^32) and summed into one int64 per channel and tap.
+ *     Integer sums are associative: any order of arrival gives the same bits, and two runs of the same call do.  At most
+ *     2^28 candidates with v <= 1 keep a sum below 2^61.
+ *  6. h_e[k] = (float)((double)level (double)acc_e[k] 2^-32).
+ *
+ * out_ir != NULL: the result becomes an IR like any gas_conv_ir_load gives -- usable in gas_conv_create, gas_conv_set_ir
+ * and gas_conv_fade_to, freed by gas_conv_ir_free, reported by gas_conv_ir_get_info.  The taps never visit the host on
+ * this path.  out_taps != NULL: the float32 taps are copied back, [channels][taps].  With out_ir == NULL the call is a
+ * pure generator: it needs no reserved pool and touches no context state, like gas_calc_early_reflections with
+ * slots == NULL.  Main thread, the contract of gas_conv_ir_load: deferred and recorded callbacks are flushed first (when
+ * an IR is loaded) and the call returns when the IR is ready.  The temporaries (8 channels taps bytes of sums,
+ * 4 channels taps of taps, the reflectance tables) are freed on every way out.  While gas_profile_enable is on, the
+ * generator's launches (zeroing, sums, scaling; not the transform) are bracketed and counted by gas_profile_read as a
+ * callback's dominant launch is -- the one way in which a profiled pure generator touches the context.
+ * Refusals, each with nothing loaded and nothing written.  GAS_ERR_INVALID_ARGUMENT: a NULL ctx or desc; out_taps and
+ * out_ir both NULL; channels other than 1 or 2; taps == 0; taps > max_ir_taps of the reserve when out_ir != NULL, or
+ * taps > 2^20 for the pure generator; a room that gas_calc_early_reflections would refuse (room.max_order is not read);
+ * min_order > max_order when max_order != 0; an ear_spacing that is negative or not finite; a coordinate (room basis or
+ * origin, source, listener basis or origin) that is not finite; |s_a| > h_a or |l_a| > h_a on any axis; d0 < 1e-3;
+ * (2 N_x + 1)(2 N_y + 1)(2 N_z + 1) > 2^28 -- the remedy is a shorter IR or a max_order; the check is made from step 2
+ * before anything is launched.  GAS_ERR_UNSUPPORTED_CHAIN: out_ir != NULL with nothing reserved.  GAS_ERR_DEVICE: a HIP
+ * failure, with no IR loaded.
+ * Out of scope: frequency-dependent absorption, air absorption, jitter against flutter echoes, a direction-dependent
+ * (HRTF) receiver, four-channel results, rooms that are not boxes, the host layer, godot_module/ and gas_multi. */
+typedef struct gas_room_ir { /* NEW; 184 bytes */
+	gas_room room; /* as for gas_calc_early_reflections; room.max_order is NOT read here */
+	float source[3]; /* global position of the emitter that stands for the bus */
+	gas_listener listener; /* origin and basis are read (local +x = right ear side); velocity is not */
+	float ear_spacing; /* metres between the two receivers of a two-channel IR, >= 0; ignored for one channel */
+	uint32_t min_order; /* images with |m|_1 < min_order are left out: 3 = "behind ER at max_order 2", 1 = no direct sound */
+	uint32_t max_order; /* images with |m|_1 > max_order are left out; 0 = no limit but the IR's length */
+} gas_room_ir;
+int gas_conv_ir_from_room(gas_ctx *ctx, const gas_room_ir *desc, uint32_t channels /* 1 or 2 */, uint32_t taps, float *out_taps /* host [channels][taps], may be NULL */, uint32_t *out_ir /* may be NULL */);
 
 
 /* ---- device-resident source sampling ------------------------------------------------

@@ -502,6 +502,7 @@ EXPORTS = [
     "gas_conv_ir_free",
     "gas_conv_ir_get_info",
     "gas_conv_ir_from_room",
+    "gas_conv_ir_from_room_hrtf",
     "gas_conv_create",
     "gas_conv_destroy",
     "gas_conv_reset",
@@ -615,6 +616,7 @@ def load_library():
     L.gas_conv_ir_free.argtypes = [vp, u32]
     L.gas_conv_ir_get_info.argtypes = [vp, u32, C.POINTER(u32), C.POINTER(u32)]
     L.gas_conv_ir_from_room.argtypes = [vp, vp, u32, u32, vp, C.POINTER(u32)]
+    L.gas_conv_ir_from_room_hrtf.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, C.POINTER(u32)]
     L.gas_conv_create.argtypes = [vp, u32, C.POINTER(u32)]
     L.gas_conv_destroy.argtypes = [vp, u32]
     L.gas_conv_reset.argtypes = [vp, u32]
@@ -1049,6 +1051,21 @@ class SpatializerContext:
         out = C.c_uint32()
         rc = self.lib.gas_conv_ir_from_room(self.h, _np_ptr(d), int(channels), int(taps), _np_ptr(taps_out) if want_taps else None, C.byref(out) if load else None)
         self._check(rc, "gas_conv_ir_from_room")
+        if load and want_taps:
+            return out.value, taps_out
+        return out.value if load else taps_out
+
+    def conv_ir_from_room_hrtf(self, desc, hrir, n_az, n_el, taps, want_taps=False, load=True):
+        """conv_ir_from_room heard through an HRIR set: hrir float32 [n_az * n_el][2][hrir_taps] (what hrtf_load was
+        given), one direction per image, always two channels (left, right).  Returns as conv_ir_from_room does; the
+        taps are [2][taps]."""
+        d = np.ascontiguousarray(np.asarray(desc, dtype=ROOM_IR_DTYPE).reshape(-1)[:1])
+        h = np.ascontiguousarray(np.asarray(hrir, dtype=np.float32))
+        assert h.ndim == 3 and h.shape[0] == int(n_az) * int(n_el) and h.shape[1] == 2, h.shape
+        taps_out = np.zeros((2, int(taps)), dtype=np.float32) if want_taps else None
+        out = C.c_uint32()
+        rc = self.lib.gas_conv_ir_from_room_hrtf(self.h, _np_ptr(d), _np_ptr(h), int(n_az), int(n_el), h.shape[2], int(taps), _np_ptr(taps_out) if want_taps else None, C.byref(out) if load else None)
+        self._check(rc, "gas_conv_ir_from_room_hrtf")
         if load and want_taps:
             return out.value, taps_out
         return out.value if load else taps_out

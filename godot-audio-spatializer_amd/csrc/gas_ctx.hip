@@ -4498,17 +4498,9 @@ int gas_conv_ir_load(gas_ctx *c, const float *ir, uint32_t channels, uint32_t ta
 	return conv_ir_register(c, d_ir, channels, taps, out_ir);
 }
 
-int gas_conv_ir_from_room(gas_ctx *c, const gas_room_ir *desc, uint32_t channels, uint32_t taps, float *out_taps, uint32_t *out_ir) {
-	if (!c || !desc || (!out_taps && !out_ir) || (channels != 1 && channels != 2) || taps == 0) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (out_ir && c->conv_count == 0) {
-		return GAS_ERR_UNSUPPORTED_CHAIN;
-	}
-	if (taps > (out_ir ? c->conv_max_taps : (uint32_t)GAS_CONV_MAX_IR_TAPS)) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	const gas_room &R = desc->room;
+// What gas_conv_ir_from_room and gas_conv_ir_from_room_hrtf refuse in a descriptor's plain fields; `ears`: ear_spacing too.
+static bool room_ir_desc_ok(const gas_room_ir &d, bool ears) {
+	const gas_room &R = d.room;
 	bool ok = R.speed_of_sound > 0.0f && std::isfinite(R.speed_of_sound) && R.level >= 0.0f && std::isfinite(R.level); // gas_calc_early_reflections' test but for max_order
 	for (int a = 0; a < 3; a++) {
 		ok = ok && R.half_extent[a] > 0.0f && std::isfinite(R.half_extent[a]);
@@ -4516,18 +4508,28 @@ int gas_conv_ir_from_room(gas_ctx *c, const gas_room_ir *desc, uint32_t channels
 	for (int w = 0; w < 6; w++) {
 		ok = ok && R.reflectance[w] >= 0.0f && R.reflectance[w] <= 1.0f;
 	}
-	ok = ok && (desc->max_order == 0 || desc->min_order <= desc->max_order);
-	ok = ok && desc->ear_spacing >= 0.0f && std::isfinite(desc->ear_spacing);
+	ok = ok && (d.max_order == 0 || d.min_order <= d.max_order);
+	ok = ok && (!ears || (d.ear_spacing >= 0.0f && std::isfinite(d.ear_spacing)));
 	for (int a = 0; a < 3; a++) {
-		ok = ok && std::isfinite(R.origin[a]) && std::isfinite(desc->source[a]) && std::isfinite(desc->listener.origin[a]);
+		ok = ok && std::isfinite(R.origin[a]) && std::isfinite(d.source[a]) && std::isfinite(d.listener.origin[a]);
 		for (int b = 0; b < 3; b++) {
-			ok = ok && std::isfinite(R.basis[a][b]) && std::isfinite(desc->listener.basis[a][b]);
+			ok = ok && std::isfinite(R.basis[a][b]) && std::isfinite(d.listener.basis[a][b]);
 		}
 	}
-	gas_room_ir_plan plan;
-	if (!ok || !gas_room_ir_make_plan(*desc, channels, taps, c->cfg.mix_rate, plan)) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
+	return ok;
+}
+
+// The HRIR set of gas_conv_ir_from_room_hrtf, as the caller passed it.
+struct RoomIrSet {
+	const float *hrir;
+	uint32_t n_az, n_el, taps;
+};
+
+// The common body of the two box-room calls once everything is validated and the plan is made: tables, temporaries,
+// the generator's launches inside the profile bracket, registration and read-back.  set == nullptr: k_room_ir with
+// `channels` receivers; otherwise k_room_ir_hrtf, two ears.
+static int conv_ir_from_plan(gas_ctx *c, const gas_room_ir &desc, const gas_room_ir_plan &plan, uint32_t channels, const RoomIrSet *set, float *out_taps, uint32_t *out_ir) {
+	const uint32_t taps = plan.taps;
 	std::vector<double> tables;
 	try {
 		tables.resize(gas_room_ir_table_doubles(plan));
@@ -4535,25 +4537,34 @@ int gas_conv_ir_from_room(gas_ctx *c, const gas_room_ir *desc, uint32_t channels
 		c->last_err = "gas_conv_ir_from_room: out of host memory for the reflectance tables";
 		return GAS_ERR_DEVICE;
 	}
-	gas_room_ir_fill_tables(*desc, plan, tables.data());
+	gas_room_ir_fill_tables(desc, plan, tables.data());
 	if (out_ir) { // the pure generator leaves queued callbacks where they are: it touches nothing of theirs
 		GAS_TRY(flush_deferred(c));
 	}
 	GAS_HIP(c, hipSetDevice(c->cfg.device));
 	const size_t n = (size_t)channels * taps;
-	Mem tmp; // frees the three buffers on every way out
+	Mem tmp; // frees the buffers on every way out
 	double *d_tables = nullptr;
 	long long *d_acc = nullptr;
-	float *d_ir = nullptr;
+	float *d_ir = nullptr, *d_hrir = nullptr;
 	GAS_HIP(c, tmp.alloc(d_tables, tables.size()));
 	GAS_HIP(c, tmp.alloc(d_acc, n));
 	GAS_HIP(c, tmp.alloc(d_ir, n));
 	GAS_HIP(c, hipMemcpy(d_tables, tables.data(), tables.size() * sizeof(double), hipMemcpyHostToDevice)); // complete on return
+	if (set) {
+		const size_t floats = (size_t)set->n_az * set->n_el * 2 * set->taps;
+		GAS_HIP(c, tmp.alloc(d_hrir, floats));
+		GAS_HIP(c, hipMemcpy(d_hrir, set->hrir, floats * sizeof(float), hipMemcpyHostToDevice));
+	}
 	const bool timed = c->profiling && c->ev_used + 2 <= c->ev.size(); // gas_profile_enable: the generator's launches count as a dominant launch
 	if (timed) {
 		GAS_HIP(c, hipEventRecord(c->ev[c->ev_used], c->stream));
 	}
-	GAS_HIP(c, gas_launch_room_ir(c->stream, plan, d_tables, d_acc, d_ir));
+	if (set) {
+		GAS_HIP(c, gas_launch_room_ir_hrtf(c->stream, plan, desc, d_tables, d_hrir, set->n_az, set->n_el, set->taps, d_acc, d_ir));
+	} else {
+		GAS_HIP(c, gas_launch_room_ir(c->stream, plan, d_tables, d_acc, d_ir));
+	}
 	if (timed) {
 		GAS_HIP(c, hipEventRecord(c->ev[c->ev_used + 1], c->stream));
 		c->ev_used += 2;
@@ -4575,6 +4586,50 @@ int gas_conv_ir_from_room(gas_ctx *c, const gas_room_ir *desc, uint32_t channels
 	GAS_HIP(c, hipStreamSynchronize(c->stream)); // before anything reaches out_taps: a failed kernel writes nothing there
 	GAS_HIP(c, hipMemcpy(out_taps, d_ir, n * sizeof(float), hipMemcpyDeviceToHost));
 	return GAS_OK;
+}
+
+int gas_conv_ir_from_room(gas_ctx *c, const gas_room_ir *desc, uint32_t channels, uint32_t taps, float *out_taps, uint32_t *out_ir) {
+	if (!c || !desc || (!out_taps && !out_ir) || (channels != 1 && channels != 2) || taps == 0) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (out_ir && c->conv_count == 0) {
+		return GAS_ERR_UNSUPPORTED_CHAIN;
+	}
+	if (taps > (out_ir ? c->conv_max_taps : (uint32_t)GAS_CONV_MAX_IR_TAPS)) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	gas_room_ir_plan plan;
+	if (!room_ir_desc_ok(*desc, true) || !gas_room_ir_make_plan(*desc, channels, taps, c->cfg.mix_rate, plan)) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	return conv_ir_from_plan(c, *desc, plan, channels, nullptr, out_taps, out_ir);
+}
+
+int gas_conv_ir_from_room_hrtf(gas_ctx *c, const gas_room_ir *desc, const float *hrir, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps, uint32_t taps, float *out_taps, uint32_t *out_ir) {
+	if (!c || !desc || !hrir || (!out_taps && !out_ir) || taps == 0) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (n_az == 0 || n_el == 0 || (uint64_t)n_az * n_el > 65536u || hrir_taps == 0 || hrir_taps > GAS_HRTF_TAPS) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (out_ir && c->conv_count == 0) {
+		return GAS_ERR_UNSUPPORTED_CHAIN;
+	}
+	if (taps > (out_ir ? c->conv_max_taps : (uint32_t)GAS_CONV_MAX_IR_TAPS)) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	gas_room_ir_plan plan;
+	if (!room_ir_desc_ok(*desc, false) || !gas_room_ir_make_plan(*desc, 1, taps, c->cfg.mix_rate, plan)) { // one receiver: ear_spacing is not read
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	const size_t floats = (size_t)n_az * n_el * 2 * hrir_taps;
+	for (size_t i = 0; i < floats; i++) {
+		if (!(std::fabs(hrir[i]) <= 4.0f)) { // not finite, or a tap could pass 4 v per image: the int64 sums' bound
+			return GAS_ERR_INVALID_ARGUMENT;
+		}
+	}
+	const RoomIrSet set{hrir, n_az, n_el, hrir_taps};
+	return conv_ir_from_plan(c, *desc, plan, 2, &set, out_taps, out_ir);
 }
 
 int gas_conv_ir_free(gas_ctx *c, uint32_t ir) {

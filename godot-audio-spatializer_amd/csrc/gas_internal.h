@@ -610,6 +610,13 @@ bool gas_room_ir_make_plan(const gas_room_ir &desc, uint32_t channels, uint32_t 
 size_t gas_room_ir_table_doubles(const gas_room_ir_plan &plan);
 void gas_room_ir_fill_tables(const gas_room_ir &desc, const gas_room_ir_plan &plan, double *host_tables);
 hipError_t gas_launch_room_ir(hipStream_t stream, const gas_room_ir_plan &plan, const double *d_tables, long long *d_acc, float *d_out);
+// gas_conv_ir_from_room_hrtf: the plan is made with channels = 1 (one receiver, the listener); d_acc and d_out are
+// [2][taps] all the same, one row per ear.  d_hrir is the set as the caller passed it, f32 [n_az * n_el][2][hrir_taps];
+// the two bases of `desc` travel to the kernel widened, by value.
+struct gas_room_ir_frames {
+	double B[3][3], L[3][3]; // room.basis, listener.basis
+};
+hipError_t gas_launch_room_ir_hrtf(hipStream_t stream, const gas_room_ir_plan &plan, const gas_room_ir &desc, const double *d_tables, const float *d_hrir, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps, long long *d_acc, float *d_out);
 hipError_t gas_launch_sample_sources(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc /* 16.16 step per row for resampled playbacks, or nullptr */, const uint8_t *feed = nullptr /* the feed table when an entry of the list is fed (GAS_FEED_NONE, above) */);
 hipError_t gas_launch_sample_adpcm(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc, bool span /* false: every load decodes from its checkpoint (GAS_ADPCM_SPAN=0) */); // the GAS_PCM_IMA_ADPCM rows of the same list, after gas_launch_sample_sources
 hipError_t gas_launch_sample_qoa(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc, bool span /* false: every load decodes from its record (GAS_QOA_SPAN=0) */); // the GAS_PCM_QOA rows of the same list, after gas_launch_sample_sources

@@ -13,6 +13,15 @@
 // [channels][taps], the layout gas_launch_conv_ir reads.
 // Bound: 32 B of atomics per image and receiver against about sixty float64 operations; measured figures and the shell
 // variant that would replace the box walk: profiles/room_ir_notes.md.
+//
+// k_room_ir_hrtf -- gas_conv_ir_from_room_hrtf: the same lattice heard through an HRIR set.  A lane does for its cell what
+// k_room_ir does for one receiver and adds the direction of arrival in the listener's frame (the cell choice of
+// k_calc_spatialization's hrtf_dir).  An image that reaches a tap is then spread by its whole wave: the wave walks its
+// ballot of such lanes, takes each one's (k, a0, a1, dir) through lane reads, and per ear its 64 lanes stride over the
+// hrir_taps + 1 taps of the HRIR shifted by the fractional delay, so one wave instruction adds to 64 consecutive int64
+// (512 contiguous bytes) without return.  Nothing crosses a wave: no LDS, no barrier, and a lane that fails a mask stays
+// for the spreading instead of returning.  Bound: up to 2 (hrir_taps + 1) adds of 8 bytes per image, 514 at 256 taps
+// against 4 above; figures: profiles/room_brir_notes.md.  tests/room_brir_ref.py restates the rule in numpy.
 #include "gas_internal.h"
 
 #include <cmath>
@@ -80,6 +89,94 @@ __global__ __launch_bounds__(256) void k_room_ir_scale(const long long *__restri
 	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
 	if (i < n) {
 		out[i] = (float)(level * (double)acc[i] * (1.0 / ROOM_IR_ONE));
+	}
+}
+
+// One lane's value in every lane of the wave; src is the same in all of them and names a lane that is active.
+__device__ __forceinline__ double wave_read(double v, int src) {
+	return __shfl(v, src, 64);
+}
+
+__global__ __launch_bounds__(256) void k_room_ir_hrtf(gas_room_ir_plan p, gas_room_ir_frames fr, const double *__restrict__ tables, const float *__restrict__ hrir, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps, unsigned long long *__restrict__ acc) {
+	const uint32_t id = blockIdx.x * 256u + threadIdx.x;
+	const uint32_t lane = threadIdx.x & 63u;
+	// phase 1: this lane's image; `hit` when it reaches a tap.  No lane leaves before the wave has spread its hits.
+	bool hit = false;
+	double a0 = 0.0, a1 = 0.0;
+	int k = 0;
+	uint32_t dir = 0;
+	if (id < p.cells) {
+		const uint32_t wz = 2u * p.N[2] + 1u, wy = 2u * p.N[1] + 1u;
+		const uint32_t iz = id % wz, rest = id / wz;
+		const uint32_t iy = rest % wy, ix = rest / wy;
+		const int m[3] = {(int)ix - (int)p.N[0], (int)iy - (int)p.N[1], (int)iz - (int)p.N[2]};
+		const uint32_t order = (uint32_t)((m[0] < 0 ? -m[0] : m[0]) + (m[1] < 0 ? -m[1] : m[1]) + (m[2] < 0 ? -m[2] : m[2]));
+		if (order >= p.min_order && (p.max_order == 0 || order <= p.max_order)) {
+			// step 1 (steps 1 - 3 of gas_conv_ir_from_room)
+			const double *tx = tables, *ty = tx + (2u * p.N[0] + 1u), *tz = ty + wy;
+			const double R = (tx[ix] * ty[iy]) * tz[iz];
+			double w[3];
+#pragma unroll
+			for (int a = 0; a < 3; a++) {
+				w[a] = ((double)(2 * m[a]) * p.h[a] + ((m[a] & 1) ? -p.s[a] : p.s[a])) - p.e[0][a];
+			}
+			// step 2
+			const double dist = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+			const double v = R * p.d0 / fmax(dist, p.d0);
+			const double pos = (dist - p.d0) / p.c * p.rate;
+			const double kf = floor(pos);
+			const double f = pos - kf;
+			if (R > 0.0 && kf >= -1.0 && kf < (double)p.taps) { // taps <= 2^20: k fits an int
+				hit = true;
+				k = (int)kf;
+				a0 = v * (1.0 - f);
+				a1 = v * f;
+				// step 3: into the global frame, then into the listener's
+				double g[3], q[3];
+#pragma unroll
+				for (int a = 0; a < 3; a++) {
+					g[a] = fr.B[a][0] * w[0] + fr.B[a][1] * w[1] + fr.B[a][2] * w[2];
+				}
+#pragma unroll
+				for (int a = 0; a < 3; a++) {
+					q[a] = fr.L[0][a] * g[0] + fr.L[1][a] * g[1] + fr.L[2][a] * g[2];
+				}
+				const double two_pi = 6.2831853071795864769252867666;
+				const double az = atan2(q[0], -q[2]);
+				const double flat = sqrt(q[0] * q[0] + q[2] * q[2]);
+				const double el = atan2(q[1], flat);
+				long long ai = llround(az / two_pi * n_az);
+				ai = ((ai % (long long)n_az) + (long long)n_az) % (long long)n_az;
+				long long ei = n_el > 1 ? llround((el + two_pi / 4) / (two_pi / 2) * (n_el - 1)) : 0;
+				ei = ei < 0 ? 0 : (ei > (long long)n_el - 1 ? (long long)n_el - 1 : ei);
+				dir = (uint32_t)(ei * n_az + ai); // < n_az n_el
+			}
+		}
+	}
+	// phase 2 (step 4): every lane of the wave is here, so the ballot and the lane reads see all 64
+	unsigned long long live = __ballot(hit);
+	while (live != 0) {
+		const int src = __ffsll(live) - 1;
+		live &= live - 1;
+		const double b0 = wave_read(a0, src), b1 = wave_read(a1, src);
+		const long long kk = __shfl(k, src, 64); // -1 .. taps - 1
+		const size_t set = (size_t)__shfl((int)dir, src, 64) * 2u;
+		for (uint32_t e = 0; e < 2; e++) {
+			const float *H = hrir + (set + e) * hrir_taps;
+			unsigned long long *row = acc + (size_t)e * p.taps;
+			for (uint32_t j = lane; j <= hrir_taps; j += 64u) {
+				const long long t = kk + (long long)j;
+				if (t < 0 || t >= (long long)p.taps) {
+					continue;
+				}
+				const double hj = j < hrir_taps ? (double)H[j] : 0.0;
+				const double hp = j > 0 ? (double)H[j - 1] : 0.0;
+				const long long q = llrint((b0 * hj + b1 * hp) * ROOM_IR_ONE); // |.| <= 4 v 2^32 <= 2^34
+				if (q != 0) {
+					atomicAdd(row + t, (unsigned long long)q); // result unused: the no-return form; a negative q wraps as the sum of int64 does
+				}
+			}
+		}
 	}
 }
 
@@ -172,6 +269,28 @@ hipError_t gas_launch_room_ir(hipStream_t stream, const gas_room_ir_plan &p, con
 		return e;
 	}
 	hipLaunchKernelGGL(k_room_ir, dim3((p.cells + 255u) / 256u), dim3(256), 0, stream, p, d_tables, reinterpret_cast<unsigned long long *>(d_acc));
+	e = hipGetLastError();
+	if (e != hipSuccess) {
+		return e;
+	}
+	hipLaunchKernelGGL(k_room_ir_scale, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_acc, n, p.level, d_out);
+	return hipGetLastError();
+}
+
+hipError_t gas_launch_room_ir_hrtf(hipStream_t stream, const gas_room_ir_plan &p, const gas_room_ir &d, const double *d_tables, const float *d_hrir, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps, long long *d_acc, float *d_out) {
+	gas_room_ir_frames fr;
+	for (int a = 0; a < 3; a++) {
+		for (int b = 0; b < 3; b++) {
+			fr.B[a][b] = (double)d.room.basis[a][b];
+			fr.L[a][b] = (double)d.listener.basis[a][b];
+		}
+	}
+	const uint32_t n = 2u * p.taps;
+	hipError_t e = hipMemsetAsync(d_acc, 0, sizeof(long long) * n, stream);
+	if (e != hipSuccess) {
+		return e;
+	}
+	hipLaunchKernelGGL(k_room_ir_hrtf, dim3((p.cells + 255u) / 256u), dim3(256), 0, stream, p, fr, d_tables, d_hrir, n_az, n_el, hrir_taps, reinterpret_cast<unsigned long long *>(d_acc));
 	e = hipGetLastError();
 	if (e != hipSuccess) {
 		return e;

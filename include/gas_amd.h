@@ -987,7 +987,8 @@ int gas_calc_early_reflections(gas_ctx *ctx, const gas_room *rooms, uint32_t n_r
  * before anything is launched.  GAS_ERR_UNSUPPORTED_CHAIN: out_ir != NULL with nothing reserved.  GAS_ERR_DEVICE: a HIP
  * failure, with no IR loaded.
  * Out of scope: frequency-dependent absorption, air absorption, jitter against flutter echoes, a direction-dependent
- * (HRTF) receiver, four-channel results, rooms that are not boxes, the host layer, godot_module/ and gas_multi. */
+ * (HRTF) receiver, four-channel results, rooms that are not boxes, the host layer, godot_module/ and gas_multi.
+ * (The HRTF receiver is a call of its own, gas_conv_ir_from_room_hrtf, declared below this one.) */
 typedef struct gas_room_ir { /* NEW; 184 bytes */
 	gas_room room; /* as for gas_calc_early_reflections; room.max_order is NOT read here */
 	float source[3]; /* global position of the emitter that stands for the bus */
@@ -997,6 +998,51 @@ typedef struct gas_room_ir { /* NEW; 184 bytes */
 	uint32_t max_order; /* images with |m|_1 > max_order are left out; 0 = no limit but the IR's length */
 } gas_room_ir;
 int gas_conv_ir_from_room(gas_ctx *ctx, const gas_room_ir *desc, uint32_t channels /* 1 or 2 */, uint32_t taps, float *out_taps /* host [channels][taps], may be NULL */, uint32_t *out_ir /* may be NULL */);
+
+/* NEW: gas_conv_ir_from_room_hrtf -- the same box room heard binaurally: every image arrives through the HRIR pair of its
+ * direction, so the tail carries the pinna and head cues the dry GAS_FX_HRTF sources have, from the same HRIR set.  The
+ * result always has two channels: ear 0 is left, ear 1 is right.  `hrir` is the gridded set the caller gave gas_hrtf_load
+ * (or received as out_hrir from gas_hrtf_load_positions), float32 [n_az * n_el][2 ears][hrir_taps], with the direction
+ * convention of hrtf_dir = elevation_index * n_az + azimuth_index.  It is passed in because the context keeps only
+ * spectra, and so that the pure generator (out_ir == NULL) stays free of context state.  desc->ear_spacing is neither
+ * read nor validated.  ER taps on the sources (orders 1 - 2) plus this tail with min_order = 3 on the send bus form one
+ * room, heard through the HRIR set of the dry sound.
+ *
+ * The rule.  Inputs are float32 and are widened to float64; everything up to the final conversion is float64 with no
+ * fused multiply-adds.
+ *  1. Steps 1 - 3 of gas_conv_ir_from_room with channels = 1: one receiver e_0 = l, reach without the ear term; the
+ *     candidate box, the order masks, R from the running products and the refusal above 2^28 cells are the same.
+ *  2. Per image, step 4 with the receiver l: dist = |img - l|; v = R d0 / max(dist, d0); pos = ((dist - d0) / c) rate;
+ *     k = floor(pos), f = pos - k; a0 = v (1 - f), a1 = v f.  A reflected path is never shorter than the direct one, so
+ *     k >= 0; an image with k >= taps contributes nothing.
+ *  3. Direction of arrival in the listener's frame.  w = img - l (room's frame), B = room.basis, L = listener.basis:
+ *     g_a = B[a][0] w_0 + B[a][1] w_1 + B[a][2] w_2;  p_a = L[0][a] g_0 + L[1][a] g_1 + L[2][a] g_2, each sum in that
+ *     order.  The cell is chosen as gas_calc_spatialization chooses hrtf_dir: az = atan2(p_x, -p_z),
+ *     flat = sqrt(p_x p_x + p_z p_z), el = atan2(p_y, flat); ai = llround(az / 2pi n_az) wrapped into [0, n_az);
+ *     ei = n_el > 1 ? llround((el + pi/2) / pi (n_el - 1)) : 0, clamped to [0, n_el - 1]; dir = ei n_az + ai.  For m = 0
+ *     this is the cell gas_calc_spatialization writes as the source's hrtf_dir.
+ *  4. For ear e and j = 0 .. hrir_taps, with H = hrir widened and H[dir][e][-1] = H[dir][e][hrir_taps] = 0:
+ *     g_j = a0 H[dir][e][j] + a1 H[dir][e][j - 1] (two products, one sum); q = llrint(g_j 2^32), signed;
+ *     acc_e[k + j] += q when k + j < taps -- each tap is dropped on its own.  This is the HRIR shifted by the fractional
+ *     delay the one-channel rule uses.
+ *  5. h_e[t] = (float)((double)level (double)acc_e[t] 2^-32).
+ * Overflow: an hrir value above 4 in magnitude is refused, so a tap receives at most 4 v <= 4 per image and at most 2^28
+ * images keep the int64 sums below 2^62.
+ * Consequences.  With the set H[d][e][0] = 1 and everything else 0, both channels are bitwise the one-channel
+ * gas_conv_ir_from_room of the same descriptor (a0 1 + a1 0 is a0 exactly).  Orders [0, 2] plus [3, inf) equal [0, inf)
+ * exactly in the integer sums.  Two runs of one call give the same bits.
+ *
+ * out_ir, out_taps ([2][taps]), threading, the flushing of deferred callbacks, the gas_profile_enable bracket and the
+ * freeing of the temporaries (8 2 taps bytes of sums, 4 2 taps of taps, the reflectance tables, the set) on every way out
+ * are as for gas_conv_ir_from_room.
+ * Refusals, each with nothing loaded and nothing written.  GAS_ERR_INVALID_ARGUMENT: everything gas_conv_ir_from_room
+ * refuses with channels = 1, except the ear_spacing checks; a NULL hrir; n_az == 0, n_el == 0 or n_az n_el > 65 536;
+ * hrir_taps == 0 or hrir_taps > GAS_HRTF_TAPS; an hrir value that is not finite or above 4 in magnitude.
+ * GAS_ERR_UNSUPPORTED_CHAIN: out_ir != NULL with nothing reserved.  GAS_ERR_DEVICE: a HIP failure, with no IR loaded.
+ * Out of scope: bilinear blending of the four surrounding cells (nearest cell only, as hrtf_dir), four-channel results,
+ * a per-reflection direction for GAS_FX_EARLY_REFLECTIONS, frequency-dependent absorption and air absorption, the
+ * shell-per-workgroup shape, the host layer, godot_module/ and gas_multi. */
+int gas_conv_ir_from_room_hrtf(gas_ctx *ctx, const gas_room_ir *desc, const float *hrir /* host [n_az * n_el][2 ears][hrir_taps] f32 */, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps /* 1 .. GAS_HRTF_TAPS */, uint32_t taps, float *out_taps /* host [2][taps], may be NULL */, uint32_t *out_ir /* may be NULL */);
 
 
 /* ---- device-resident source sampling ------------------------------------------------

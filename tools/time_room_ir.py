@@ -1,13 +1,19 @@
-"""Dev aid: gas_conv_ir_from_room, one shape per run.
+"""Dev aid: gas_conv_ir_from_room and gas_conv_ir_from_room_hrtf, one shape per run.
 
   python tools/time_room_ir.py default      the room of capi.default_rooms, 48 000 taps, two channels
   python tools/time_room_ir.py long         the same room, 2^20 taps, two channels, max_order 256 (513^3 cells < 2^28)
   python tools/time_room_ir.py test         the largest shape of tests/test_gpu_room_ir.py (16 384 taps)
+  python tools/time_room_ir.py --hrtf SHAPE the same shape through gas_conv_ir_from_room_hrtf, with synth.synthetic_hrir's
+                                            1024 directions of 256 taps as a 64 x 16 grid
 
 Prints one JSON line: the wall clock of a whole loading call (tables, allocations, launches, transform, synchronise) as
 the median of STEPS calls, the span of the generator's launches from the library's HIP-event bracket
-(gas_profile_enable; zeroing, k_room_ir and the scaling kernel, not the transform), the numpy reference's time on the
-same inputs, and the parity of the read-back taps against it (relative RMS and max-abs over max|h|, worst channel)."""
+(gas_profile_enable; zeroing, k_room_ir or k_room_ir_hrtf and the scaling kernel, not the transform), the numpy
+reference's time on the same inputs, and the parity of the read-back taps against it (relative RMS and max-abs over
+max|h|, worst channel).  With --hrtf also the 8-byte adds the reference counts (non-zero products that land on a tap),
+their bytes and the rate over the generator's span, and near_edge: the images whose cell two atan2 may choose
+differently (tests/room_brir_ref.py); the long shape's reference takes minutes and is skipped unless --reference is
+given."""
 import json
 import os
 import sys
@@ -18,10 +24,13 @@ import numpy as np
 sys.path.insert(0, ".")
 sys.path.insert(0, os.path.join(".", "tests"))
 import godot_audio_spatializer_amd as gas  # noqa: E402
+from godot_audio_spatializer_amd import synth  # noqa: E402
+import room_brir_ref as BR  # noqa: E402
 import room_ir_ref as R  # noqa: E402
 
 K = gas.capi
 WARMUP, STEPS = 2, 7
+N_AZ, N_EL = 64, 16
 SHAPES = {
     "default": (dict(), 2, 48000),
     "long": (dict(max_order=256), 2, 1 << 20),
@@ -29,19 +38,53 @@ SHAPES = {
 }
 
 
-def main(shape):
+def parity(h, ref_h):
+    ch = range(h.shape[0])
+    rms = max(float(np.sqrt(np.mean((h[e].astype(np.float64) - ref_h[e]) ** 2)) / np.sqrt(np.mean(ref_h[e].astype(np.float64) ** 2))) for e in ch)
+    mx = max(float(np.abs(h[e].astype(np.float64) - ref_h[e]).max() / np.abs(ref_h[e]).max()) for e in ch)
+    return {"rel_rms": rms, "max_abs_over_max": mx, "bitwise": bool(np.array_equal(h, ref_h))}
+
+
+def count_adds(ref, hrir, taps):
+    """The adds k_room_ir_hrtf issues: per image, ear and j a non-zero quantised product whose tap is in range."""
+    v, pos = ref.mono.v[0], ref.mono.pos[0]
+    k = np.floor(pos)
+    f = pos - k
+    k = k.astype(np.int64)
+    a0, a1 = v * (1.0 - f), v * f
+    T = hrir.shape[2]
+    H = np.zeros((hrir.shape[0], 2, T + 2))
+    H[:, :, 1 : T + 1] = hrir
+    adds = 0
+    for e in range(2):
+        He = H[ref.dirs, e]
+        for j in range(T + 1):
+            t = k + j
+            q = np.rint((a0 * He[:, j + 1] + a1 * He[:, j]) * BR.ONE)
+            adds += int(np.count_nonzero((t >= 0) & (t < taps) & (q != 0)))
+    return adds
+
+
+def main(shape, hrtf, want_reference):
     kw, channels, taps = SHAPES[shape]
     d = K.default_room_ir(**kw)
+    hrir = synth.synthetic_hrir(np.random.default_rng(0), dirs=N_AZ * N_EL) if hrtf else None
     ctx = gas.SpatializerContext(max_sources=4, frames=512)
     ctx.reserve_conv(1, taps)
-    n, cells = R.box(d, channels, taps, 48000.0)
-    out = {"shape": shape, "channels": channels, "taps": taps, "N": n, "cells": cells}
+
+    def call(**how):
+        if hrtf:
+            return ctx.conv_ir_from_room_hrtf(d, hrir, N_AZ, N_EL, taps, **how)
+        return ctx.conv_ir_from_room(d, channels, taps, **how)
+
+    n, cells = R.box(d, 1 if hrtf else channels, taps, 48000.0)
+    out = {"shape": shape, "hrtf": hrtf, "channels": channels, "taps": taps, "N": n, "cells": cells}
     ts = []
     for i in range(WARMUP + STEPS):
         if i == WARMUP:
             ctx.profile_enable(1)
         t0 = time.perf_counter()
-        ir = ctx.conv_ir_from_room(d, channels, taps)
+        ir = call()
         t1 = time.perf_counter()
         ctx.conv_ir_free(ir)
         if i >= WARMUP:
@@ -52,18 +95,30 @@ def main(shape):
     out["bracketed_calls"] = p["launches"]
     ctx.profile_enable(0)
     t0 = time.perf_counter()
-    h = ctx.conv_ir_from_room(d, channels, taps, want_taps=True, load=False)
+    h = call(want_taps=True, load=False)
     out["pure_generator_with_read_back_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
     ctx.close()
+    if hrtf and shape == "long" and not want_reference:
+        out["reference"] = "skipped"
+        print(json.dumps(out))
+        return
     t0 = time.perf_counter()
-    ref = R.ir(d, channels, taps, 48000.0)
+    if hrtf:
+        ref = BR.brir(d, hrir, N_AZ, N_EL, taps, 48000.0)
+        mono = ref.mono
+    else:
+        ref = mono = R.ir(d, channels, taps, 48000.0)
     out["numpy_reference_s"] = round(time.perf_counter() - t0, 3)
-    out["candidates"], out["in_range_ch0"] = ref.candidates, ref.in_range
-    rms = max(float(np.sqrt(np.mean((h[e].astype(np.float64) - ref.h[e]) ** 2)) / np.sqrt(np.mean(ref.h[e].astype(np.float64) ** 2))) for e in range(channels))
-    mx = max(float(np.abs(h[e].astype(np.float64) - ref.h[e]).max() / np.abs(ref.h[e]).max()) for e in range(channels))
-    out["parity"] = {"rel_rms": rms, "max_abs_over_max": mx, "bitwise": bool(np.array_equal(h, ref.h))}
+    out["candidates"], out["in_range_ch0"] = mono.candidates, mono.in_range
+    if hrtf:
+        adds = count_adds(ref, hrir, taps)
+        out["near_edge"] = ref.near_edge
+        out["adds"], out["added_bytes"] = adds, 8 * adds
+        out["added_TB_per_s_over_generator_span"] = round(8 * adds / (out["generator_launches_ms"] * 1e-3) / 1e12, 3)
+    out["parity"] = parity(h, ref.h)
     print(json.dumps(out))
 
 
 if __name__ == "__main__":
-    main(sys.argv[1] if len(sys.argv) > 1 else "default")
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    main(args[0] if args else "default", "--hrtf" in sys.argv, "--reference" in sys.argv)

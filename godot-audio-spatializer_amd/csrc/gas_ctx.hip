@@ -1,417 +1,14 @@
 // gas_ctx.hip -- the C ABI of include/gas_amd.h: context, device-resident playback-data slots,
 // parameter publication, and the per-callback launch sequence that stands in for
 // AudioSpatializerInstance::_mix_from_playback_list (audio_spatializer.cpp:326-471).
+// Entries off the callback path live in their own units behind gas_ctx_priv.h: gas_ctx_conv.hip (bus convolvers),
+// gas_ctx_streams.hip (stream control, fed rows), gas_ctx_calc.hip (parameter generators), gas_ctx_hrtf_profile.hip.
 //
 // There is NO CPU fallback: every entry needs a HIP device and fails with GAS_ERR_NO_DEVICE /
 // GAS_ERR_DEVICE otherwise.
-#include <algorithm>
-#include <array>
-#include <cmath>
-#include <atomic>
-#include <cstdlib>
-#include <cstring>
-#include <new>
-
-#include "gas_fx_dyn_check.h"
-#include "gas_fx_eq_check.h"
-#include "gas_fx_filter_check.h"
-#include "gas_fx_line_check.h"
-#include "gas_fx_mod_check.h"
-#include "gas_fx_stereo_check.h"
-#include "gas_internal.h"
-#include "gas_owned.h"
-#include "gas_qoa.h"
+#include "gas_ctx_priv.h"
 
 namespace {
-
-// Launch groups: sources of one callback that run the same kernel instantiation.
-enum gas_group_type {
-	G_3D_MIX = 0, // must stay first: only these write channel pairs > 0
-	G_3D_PROCESS,
-	G_FX_COPY,
-	G_FX_SHELF,
-	G_FX_ER,
-	G_FX_HRTF, // frequency-domain accumulation, no per-source peak
-	G_FX_HRTF_PK, // per-source inverse FFTs: exact peaks (draining playbacks / peaks-for-all contexts); launched with G_FX_HRTF
-	G_FX_ER_HRTF,
-	G_FX_ER_HRTF_PK, // launched with G_FX_ER_HRTF
-	G_FX_GENERIC, // any other chain of the implemented effects: staged through ping-pong row buffers (audio_spatializer_effect.cpp:52-76)
-	G_COUNT
-};
-
-const char *const k_group_kernel[G_COUNT] = {
-	"k_biquad_mix<MIX_CHANNEL>", "k_biquad_mix<PROCESS_FRAMES>", "k_biquad_mix<COPY>", "k_biquad_mix<FX_HIGHSHELF>",
-	"k_er_only", "k_hrtf_ols", "k_hrtf_ols", "k_hrtf_ols<ER>", "k_hrtf_ols<ER>", "staged effect chain"
-};
-
-struct SlotInfo {
-	uint8_t used = 0;
-	uint8_t kind = 0;
-	uint8_t group = 0;
-	uint8_t has_params = 0;
-	uint8_t pending_free = 0;
-	uint8_t dirty_state = 0; // state must be zeroed before reuse
-	uint32_t chain_sig = 0; // G_FX_GENERIC: effect kinds, 8 bits each, first effect in the low byte
-	uint8_t draining = 0; // stream ended: the host's silence gate needs this source's peak (audio_spatializer.cpp:464)
-};
-
-struct Group {
-	uint32_t offset = 0, count = 0;
-	bool contiguous = false; // the group's slots are slot_base, slot_base + 1, ... in order
-	uint32_t slot_base = 0;
-};
-
-// One run of G_FX_GENERIC entries that share a chain.
-struct ChainRange {
-	uint32_t sig = 0;
-	uint32_t offset = 0, count = 0; // relative to the group's offset
-	bool peak_all = true, peak_any = true; // which of its sources report their exact peak (GAS_FLAG_PEAKS_DRAINING_ONLY; read by a last stage that is k_hrtf_uni)
-};
-
-// Which slots the current list has named so far, without a pass over every slot between two lists.
-struct SlotStamp {
-	std::vector<uint32_t> at; // [max_sources]: the list that named the slot last
-	uint32_t gen = 0;
-	void next() { // a new list begins
-		if (++gen == 0) {
-			std::fill(at.begin(), at.end(), 0u);
-			gen = 1;
-		}
-	}
-	bool has(uint32_t slot) const {
-		return at[slot] == gen;
-	}
-	bool seen(uint32_t slot) { // true: named before in this list; marks it otherwise
-		if (has(slot)) {
-			return true;
-		}
-		at[slot] = gen;
-		return false;
-	}
-};
-
-constexpr uint32_t PROFILE_EVENTS = 4096;
-
-// The effect families, in the order their uploads are flushed; k_fx_families describes them.  The
-// first two have no pool: gas_fx_settings (GAS_FX_LOWPASS .. GAS_FX_AMPLIFY) and gas_fx_dyn_settings.
-enum { FX_BASIC = 0, FX_DYN, FX_LINES, FX_EQ, FX_FILTER, FX_MOD, FX_STEREO, FX_FAMILIES };
-
-// Host side of one family: pool sizes and free entries (alloc_mu), each slot's entries by chain position (written
-// under alloc_mu and params_mu), the settings mirror and what the next flush uploads (params_mu):
-// [m settings][m {slot, entry[4]}][z {pool, entry} zero records] through one pinned staging buffer.
-struct FxFamily {
-	uint32_t cap[2] = { 0, 0 };
-	std::vector<uint32_t> free[2];
-	std::vector<std::array<int32_t, GAS_MAX_EFFECTS>> h_of;
-	std::vector<unsigned char> h_settings; // [max_sources] settings PODs, latest published value
-	std::vector<uint8_t> dirty_flag;
-	std::vector<uint32_t> dirty_list;
-	std::vector<uint32_t> zero_list; // {pool, entry} zero records, each entry at most once (zero_pending)
-	std::vector<uint8_t> zero_pending[2]; // [pool][entry]: queued in zero_list
-	unsigned char *h_upload = nullptr, *d_upload = nullptr;
-};
-
-// gas_owned.h's way to the runtime: the only place that allocates or frees device memory, pinned memory or events.
-struct HipMem {
-	using status = hipError_t;
-	using event = hipEvent_t;
-	static constexpr status misuse = hipErrorInvalidValue;
-	static status device_alloc(void **p, size_t bytes) {
-		return hipMalloc(p, bytes);
-	}
-	static status device_free(void *p) {
-		return hipFree(p);
-	}
-	static status pinned_alloc(void **p, size_t bytes) {
-		return hipHostMalloc(p, bytes, hipHostMallocDefault);
-	}
-	static status pinned_free(void *p) {
-		return hipHostFree(p);
-	}
-	static status event_create(event *e, unsigned flags) {
-		return hipEventCreateWithFlags(e, flags);
-	}
-	static status event_destroy(event e) {
-		return hipEventDestroy(e);
-	}
-};
-using Mem = gas_owned<HipMem>;
-
-} // namespace
-
-struct gas_ctx {
-	Mem mem; // owns every device buffer, pinned buffer and event below: they are allocated through it alone
-	gas_config cfg{};
-	hipStream_t stream = nullptr;
-	bool own_stream = false;
-	// GAS_FLAG_PIPELINED_MIX: the sum of callback t's partial mixes is carried out inside callback t+1's k_hrtf_ols
-	// launch (or by gas_ctx_join_outputs / the next ordered call); two generations of partials alternate
-	bool pipelined_mix = false;
-	uint32_t pipe_tick = 0;
-	struct PendingMix {
-		int parity = 0; // plane of d_partials holding the callback's partial mixes
-		uint32_t p_total = 0;
-		gas_audio_frame *out = nullptr;
-	};
-	std::vector<PendingMix> pending; // the sums not launched yet, oldest first: one after a single launch, one per block after a batched one
-	// GAS_FLAG_BATCHED_LAUNCH: plain-[HRTF] device-memory callbacks wait here until batch_depth of them run as ONE
-	// k_hrtf_multi launch.  Anything that could change what the waiting callbacks must see runs them first.
-	struct Deferred {
-		const gas_audio_frame *src = nullptr;
-		gas_audio_frame *out = nullptr;
-		float *peaks = nullptr;
-		const gas_params *fresh = nullptr;
-	};
-	std::vector<Deferred> deferred;
-	uint32_t deferred_n = 0;
-	uint64_t deferred_groups_gen = 0;
-	uint32_t batch_depth = 2; // callbacks per launch (gas_ctx_set_batch_depth), <= GAS_HRTF_MULTI_MAX_BLOCKS
-	int bus_form_cached = 0; // form of the last gas_process_block_buses whose list can be reused: 1 3D mix, 2 fused [HRTF], 0 none
-	uint64_t bus_form_groups_gen = 0;
-	uint32_t partial_planes = 1; // planes of d_partials (1 ordered, 2 pipelined, 2 x max batch depth batched)
-	bool prof_multi = false; // the timed launch was k_hrtf_multi
-	uint32_t hist_len = 0;
-	gas_dev_state st{};
-	gas_hrtf_table tab{};
-	float2 *d_tw = nullptr;
-
-	std::vector<SlotInfo> slots;
-	std::vector<uint32_t> free_list;
-	std::vector<uint32_t> pending_free; // audio thread: frees taking effect at the next block boundary
-	std::mutex alloc_mu; // gas_source_alloc / gas_source_free may come from any thread: guards free_list and free_inbox
-	std::vector<uint32_t> free_inbox; // frees requested since the audio thread last looked (adopt_frees)
-	SlotStamp stamp; // duplicate detection per block
-	SlotStamp calc_stamp; // the same for gas_calc_spatialization's slot list (physics thread, under calc_mu)
-
-	std::mutex params_mu;
-	gas_params *h_params = nullptr; // pinned [max_sources], latest published value
-	std::vector<uint8_t> dirty_flag;
-	std::vector<uint32_t> dirty_list;
-	gas_params *h_upload = nullptr; // pinned
-	uint32_t *h_upload_slots = nullptr; // pinned
-	gas_params *d_upload = nullptr;
-	uint32_t *d_upload_slots = nullptr;
-	// gas_hrtf_blend rows (GAS_FLAG_HRTF_INTERPOLATE): host mirror, latest wins, uploaded with the parameters
-	// (params_mu); empty without the flag
-	std::vector<gas_hrtf_blend> h_blend;
-	std::vector<uint8_t> blend_dirty_flag;
-	std::vector<uint32_t> blend_dirty_list;
-	gas_hrtf_blend *h_blend_upload = nullptr; // pinned, [max_sources], allocated by the first flush that needs it
-	// the effect families, and what the reservations (gas_ctx_reserve_fx_*) derive from the mix rate
-	FxFamily fx[FX_FAMILIES];
-	gas_line_geo line_geo{};
-	gas_eq_coefs eq_coefs[3] = {}; // EQ6, EQ10, EQ21 at the mix rate (make_eq_coefs)
-
-	// plain [HRTF] group of the cached list (k_hrtf_uni): which entries need their exact peak
-	uint32_t *h_peak_bits = nullptr, *d_peak_bits = nullptr; // two halves of (max_sources + 31) / 32 words: bit k = entry k of the plain-[HRTF] group / of the staged group
-	bool uni_peak_all = false, uni_peak_any = false;
-	uint32_t *h_idx = nullptr; // pinned [2 * max_sources]: slots then rows, sorted by group
-	uint32_t *d_slots = nullptr, *d_rows = nullptr; // sorted by launch group
-	uint32_t *d_slots_rows = nullptr; // the caller's list in row order (device-side parameter publication)
-	uint32_t cached_n = UINT32_MAX;
-	uint64_t groups_gen = 0; // bumped whenever build_groups re-sorts a slot list
-	std::atomic<uint64_t> params_gen{ 1 }; // bumped by every call that can change a source's HRIR direction
-	uint32_t *d_order = nullptr; // [max_sources] direction order of the frequency-domain HRTF groups (k_dir_order)
-	uint64_t order_groups_gen = UINT64_MAX, order_params_gen = 0; // what d_order was built from
-	bool order_ok[G_COUNT] = {}; // d_order holds this group's order
-	uint32_t xcd_order_auto_min = GAS_XCD_ORDER_AUTO_MIN; // GAS_XCD_ORDER_AUTO_MIN in the environment overrides (experiments)
-	bool last_uni_ordered = false; // the last k_hrtf_uni launch ran in k_xcd_order's order
-	uint64_t stream_groups_gen = UINT64_MAX; // groups_gen the stream path's cached list corresponds to
-	bool cached_identity_rows = true;
-	Group groups[G_COUNT];
-	std::vector<ChainRange> chain_ranges; // sub-runs of groups[G_FX_GENERIC], cached with the groups
-	gas_audio_frame *d_chain[2] = { nullptr, nullptr }; // ping-pong rows of the staged chains
-	size_t d_chain_frames = 0;
-
-	gas_audio_frame *d_src = nullptr; // staging for GAS_MEM_HOST, lazily sized
-	size_t d_src_frames = 0;
-	// gas_sidechain_set(GAS_MEM_HOST): pinned staging per key, and the event behind each key's last copy out of it
-	gas_audio_frame *h_sidechain = nullptr; // [GAS_MAX_SIDECHAINS][frames]
-	hipEvent_t sidechain_ev[GAS_MAX_SIDECHAINS] = {};
-	gas_audio_frame *d_out = nullptr; // [C][F]
-	float *d_peaks = nullptr; // [max_sources][2]
-	float *d_partials = nullptr;
-	uint32_t partial_rows = 0; // rows per channel pair
-
-	// one-source compatibility path
-	uint32_t *d_one_slot = nullptr;
-
-	// device-resident streams and playback cursors
-	struct StreamInfo {
-		void *d_pcm = nullptr;
-		uint64_t frames = 0;
-		uint32_t format = 0, channels = 0;
-		bool resampled = false; // its playbacks are [ENGINE] AudioStreamPlaybackResampled (gas_stream_set_resampled)
-		uint32_t loop_mode = 0; // NEW gas_stream_set_loop: its playbacks repeat [loop_begin, loop_end)
-		uint64_t loop_begin = 0, loop_end = 0;
-	};
-	std::vector<StreamInfo> streams;
-	gas_cursor *d_cursors = nullptr; // [max_sources]
-	std::vector<gas_cursor> h_cursors; // host mirror of the cursor arithmetic (deterministic, no read-back)
-	float *d_fade_env = nullptr; // [64]
-	uint32_t *d_stream_slots = nullptr; // callback slot list in row order
-	uint32_t *d_stream_inc = nullptr, *h_stream_inc = nullptr; // [max_sources] 16.16 step per row (resampled playbacks)
-	bool stream_any_resampled = false;
-	std::vector<uint32_t> stream_slots_host; // what d_stream_slots / the cached launch groups currently hold
-	// parameter rows published from device memory for the cached slot list (row order), not yet in the table
-	const gas_params *pending_params = nullptr;
-	uint32_t pending_n = 0;
-	struct StreamRow { // compact mirror of the cached list's cursors: the per-callback host loop touches only this
-		uint64_t remaining = 0;
-		uint32_t has_frames = 0, draining_marked = 0;
-		uint32_t resampled = 0, inc = 65536; // resampled playbacks: 16.16 step of this callback (from the host-published pitch_scale)
-		uint64_t fp_pos = 0, end_fp = 0; // ... and the engine's mix_offset / the stream's end, 16.16
-		uint32_t looped = 0; // gas_stream_set_loop: never ends; a plain playback counts `pos` up instead of `remaining` down
-		uint64_t pos = 0;
-	};
-	std::vector<StreamRow> stream_rows;
-	bool stream_all_hrtf = false;
-	bool stream_last_fused = false; // the last stream callback that got as far as its launches sampled inside the HRTF kernel (gas_stream_last_fused)
-	bool stream_last_buses = false; // the cached stream list was validated by gas_process_block_streams_buses (its checks differ from the mix entry's)
-	bool stream_bus_staged = false; // ... and ran the staged bus form, which regroups on every call (cached_n never names it)
-	bool stream_rows_first = getenv("GAS_STREAM_ROWS_FIRST") != nullptr && atoi(getenv("GAS_STREAM_ROWS_FIRST")) != 0; // development aid: plain [HRTF] stream lists sample rows first too (tools/time_stream_loops.py compares the routes)
-	bool stream_any_looped = false;
-	bool stream_any_adpcm = false; // the list holds a GAS_PCM_IMA_ADPCM playback: rows first, k_sample_adpcm behind k_sample_sources
-	bool adpcm_span = getenv("GAS_ADPCM_SPAN") == nullptr || atoi(getenv("GAS_ADPCM_SPAN")) != 0; // development aid: 0 = every load decodes from its checkpoint (k_sample_adpcm.hip; tools/time_stream_adpcm.py and the tests compare the paths)
-	bool stream_any_qoa = false; // the list holds a GAS_PCM_QOA playback: rows first, k_sample_qoa behind k_sample_sources
-	bool qoa_span = getenv("GAS_QOA_SPAN") == nullptr || atoi(getenv("GAS_QOA_SPAN")) != 0; // development aid: 0 = every load decodes from its record (k_sample_qoa.hip; tools/time_stream_qoa.py and the tests compare the paths)
-	bool stream_params_touched = false; // a parameter publish may have changed pitch_scale: re-validate
-	// gas_source_feed_rows: window rows of playbacks that are not bound to a stream, pending for the next stream callback.
-	// d_feed is the feed table the kernels read (gas_internal.h, GAS_FEED_*): [max_sources] words in the callback's row
-	// order, then two halves of max_sources rows: the rows of every call since the last callback, appended as they came
-	// (feed_place).
-	uint8_t *d_feed = nullptr;
-	size_t feed_used = 0; // end of the rows taken, as an offset into d_feed (0: emptied)
-	uint32_t feed_side = 0; // the half of the table that rows are appended in
-	std::vector<uint32_t> feed_moved; // feed_place: (slot, new word) of the rows it moved to the other half
-	uint8_t *h_feed = nullptr; // pinned staging of one GAS_MEM_HOST call
-	size_t h_feed_cap = 0;
-	hipEvent_t feed_ev = nullptr; // the last upload out of h_feed
-	std::vector<uint32_t> feed_word; // [max_sources] by slot: GAS_FEED_NONE, or where and in which format its pending row lies
-	std::vector<uint32_t> feed_slots; // the slots with a pending row
-	std::vector<uint32_t> feed_entry, feed_entry_dev; // per list entry: this callback's words, and the words the table's header holds (empty: none written)
-	uint32_t *h_feed_entry = nullptr; // [max_sources] pinned: what the header upload reads
-	hipEvent_t feed_entry_ev = nullptr; // ... and the last upload out of it
-
-	// gas_calc_spatialization staging (physics thread)
-	std::mutex calc_mu;
-	gas_spatializer3d_config *d_calc_cfgs = nullptr;
-	gas_listener *d_calc_listeners = nullptr;
-	uint32_t *d_calc_slots = nullptr, *d_calc_cfgidx = nullptr;
-	gas_source_pose *d_calc_poses = nullptr;
-	gas_params *d_calc_out = nullptr;
-	gas_area_send *d_calc_areas = nullptr; // gas_calc_spatialization_areas staging (host-memory calls)
-	float *d_calc_lap = nullptr;
-	gas_audio_frame *d_calc_reverb = nullptr;
-	gas_room *d_calc_rooms = nullptr; // gas_calc_early_reflections: its rooms (everything else it stages lies in the buffers above)
-
-	// several output buses: slot-indexed routes, host mirror + device table, own partial planes
-	std::vector<gas_bus_route> h_routes; // guarded by params_mu
-	bool routes_dirty = false;
-	gas_bus_route *h_routes_pinned = nullptr, *d_routes = nullptr;
-	float *d_bus_partials = nullptr;
-	size_t bus_partial_floats = 0;
-	gas_audio_frame *d_bus_out = nullptr; // [GAS_MAX_BUSES][C][F] staging for host-memory calls
-
-	// bus convolvers (gas_conv_*, NEW): pools, tables and staging are gas_ctx_reserve_conv's, an IR's spectra
-	// gas_conv_ir_load's; the instance calls and gas_conv_process allocate nothing.  Audio-thread state, no lock: the
-	// reservation and the IR calls never run concurrently with a callback.
-	struct ConvIr {
-		float2 *H = nullptr; // [channels][k_ir][GAS_CONV_BINS]; null: a free id
-		uint32_t channels = 0, taps = 0, k_ir = 0;
-		uint32_t users = 0; // references from instances: a state, a fade's target and a pending target each count
-	};
-	struct ConvTarget {
-		uint32_t ir = 0;
-		float dry = 0.0f, wet = 1.0f;
-	};
-	struct ConvInst {
-		bool used = false;
-		uint32_t ir = 0;
-		uint32_t pos = 0; // ring position of the newest spectrum
-		float dry = 0.0f, wet = 1.0f;
-		// gas_conv_fade_to: (ir, dry, wet) above is state A; fade_n > 0: fading to `to`, fade_pos of fade_n calls made
-		uint32_t fade_n = 0, fade_pos = 0;
-		ConvTarget to;
-		uint32_t pending_n = 0; // > 0: `pending` starts, over pending_n calls, when the fade in progress has ended
-		ConvTarget pending;
-	};
-	uint32_t conv_count = 0, conv_max_taps = 0; // the reservation; 0: none
-	gas_conv_pool conv_pool{};
-	float2 *conv_w1024 = nullptr;
-	std::vector<ConvInst> conv;
-	std::vector<uint32_t> conv_free; // pop_back hands out 0, 1, 2, ...
-	std::vector<ConvIr> conv_irs;
-	gas_audio_frame *conv_h_in = nullptr, *conv_h_out = nullptr; // pinned [GAS_MAX_CONVOLVERS][frames], host-memory calls
-	gas_audio_frame *conv_d_in = nullptr, *conv_d_out = nullptr;
-
-	// gas_bandwidth_probe: read arena (larger than the Infinity Cache, swept in rotation) and write target
-	void *d_probe_rd = nullptr, *d_probe_wr = nullptr;
-	size_t probe_rd_bytes = 0, probe_wr_bytes = 0;
-	float *d_probe_sink = nullptr;
-
-	bool profiling = false;
-	std::vector<hipEvent_t> ev;
-	uint32_t ev_used = 0;
-	uint64_t prof_launches = 0;
-	double prof_ms = 0.0;
-	uint64_t prof_bytes = 0, prof_bytes_formula = 0;
-	uint32_t prof_k = 1;
-	int prof_group = -1;
-	bool prof_uni = false; // the timed launch was k_hrtf_uni
-	bool uni_flt_enabled = getenv("GAS_UNI_FLT") == nullptr || atoi(getenv("GAS_UNI_FLT")) != 0; // [filter, HRTF] through k_hrtf_uni<FLT> (0: the filter stage and the HRTF stage as two launches, for comparison)
-	// [ER, HRTF] through k_hrtf_uni<ER>.  GAS_UNI_ER = 1 (default): when at most a quarter of the callback's playbacks want
-	// their exact peak.  In throughput mode it is the faster form (the launch carries the previous callback's sum, which
-	// k_hrtf_ols<ER> has no registers to park: 20.4 vs 22.4 us for cfg5), an ordered callback is a tie (22.7 / 22.4 us) --
-	// the choice does not look at the mode, so the two modes stay bit-identical -- and with every peak exact the split
-	// kernel's exact-peak workgroups win (23.6 vs 25.8 us).  0: never.  2: always (tests, A/B).  Staged chains that END in
-	// [ER, HRTF] take it whenever it is not 0 (one launch less, no rows in between).
-	int uni_er_mode = getenv("GAS_UNI_ER") ? atoi(getenv("GAS_UNI_ER")) : 1;
-	bool uni_er_enabled = uni_er_mode != 0;
-	bool prof_pipe = false; // the timed launch was k_biquad_pipe
-	double ev_overhead_ms = 0.0; // marker/dispatch overhead of an event pair around one launch (calibrated)
-	uint32_t prof_every = 1, prof_tick = 0; // bracket every Nth callback's dominant launch
-
-	std::string last_err;
-};
-
-namespace {
-
-#define GAS_HIP(ctx, call)                                                                    \
-	do {                                                                                      \
-		hipError_t _e = (call);                                                               \
-		if (_e != hipSuccess) {                                                               \
-			(ctx)->last_err = std::string(#call) + ": " + hipGetErrorString(_e);              \
-			return GAS_ERR_DEVICE;                                                            \
-		}                                                                                     \
-	} while (0)
-
-// Returns the status of `expr` to the caller unless it is GAS_OK.
-#define GAS_TRY(expr)               \
-	do {                            \
-		const int _rc = (expr);     \
-		if (_rc != GAS_OK) {        \
-			return _rc;             \
-		}                           \
-	} while (0)
-
-// The slot names a playback of this context.
-inline bool live(const gas_ctx *c, uint32_t slot) {
-	return slot < c->cfg.max_sources && c->slots[slot].used;
-}
-
-// A lazily allocated buffer: each pointer is guarded by its own null test.
-template <class T>
-hipError_t alloc_once(gas_ctx *c, T *&p, size_t count, Mem::Kind kind = Mem::DEVICE) {
-	return p ? hipSuccess : c->mem.alloc(p, count, kind);
-}
-
-// `count` zeroed elements: the fill runs on the context's stream.
-template <class T>
-hipError_t device_zeroed(gas_ctx *c, T *&p, size_t count) {
-	const hipError_t e = c->mem.alloc(p, count);
-	return e != hipSuccess ? e : hipMemsetAsync(p, 0, count * sizeof(T), c->stream);
-}
 
 // The effect families (k_fx_families, below): which one carries an effect kind's settings (-1: none), and the stage of
 // a staged chain that runs the kind.
@@ -785,6 +382,8 @@ int reduce_now(gas_ctx *c, const gas_ctx::PendingMix &pm) {
 	return GAS_OK;
 }
 
+} // namespace
+namespace gas_priv __attribute__((visibility("hidden"))) {
 int join_outputs(gas_ctx *c) {
 	const std::vector<gas_ctx::PendingMix> all = std::move(c->pending);
 	c->pending.clear();
@@ -804,6 +403,8 @@ int join_outputs(gas_ctx *c) {
 	}
 	return GAS_OK;
 }
+} // namespace gas_priv
+namespace {
 
 // A plane of d_partials that no pending sum still reads and that is not in `taken`.
 int free_plane(const gas_ctx *c, const std::vector<int> &taken) {
@@ -1294,6 +895,8 @@ int run_groups(gas_ctx *c, const RunArgs &a) {
 
 int run_hrtf_batch(gas_ctx *c, const std::vector<gas_ctx::Deferred> &blocks, uint32_t n);
 
+} // namespace
+namespace gas_priv __attribute__((visibility("hidden"))) {
 // GAS_FLAG_BATCHED_LAUNCH: the waiting callbacks run now -- something is about to change what they must see, or somebody
 // wants their outputs.  The list, the groups and the parameter table are still the ones they were recorded with.
 int flush_deferred(gas_ctx *c) {
@@ -1315,6 +918,8 @@ int flush_deferred(gas_ctx *c) {
 	a.fresh = d.fresh;
 	return run_groups(c, a);
 }
+} // namespace gas_priv
+namespace {
 
 // Can this callback (already validated, groups built) wait for / run with its neighbours?
 bool batchable(const gas_ctx *c, uint32_t n, bool fused) {
@@ -1424,6 +1029,8 @@ inline void mark_dirty(std::vector<uint8_t> &flag, std::vector<uint32_t> &list, 
 	}
 }
 
+} // namespace
+namespace gas_priv __attribute__((visibility("hidden"))) {
 // Scatter a deferred device-side publish into the table (list unchanged since it was recorded).
 int flush_pending_params(gas_ctx *c) {
 	if (!c->pending_params) {
@@ -1465,6 +1072,8 @@ int flush_hrtf_blend(gas_ctx *c) {
 	GAS_HIP(c, hipStreamSynchronize(c->stream));
 	return GAS_OK;
 }
+} // namespace gas_priv
+namespace {
 
 // ---------------------------------------------------------------------------------------------------------------
 // The effect families: one life cycle -- reserve, hand out, publish, flush, reset, free, release --
@@ -1947,6 +1556,8 @@ int fx_reserve(gas_ctx *c, int f, uint32_t count0, uint32_t count1) {
 	return GAS_OK;
 }
 
+} // namespace
+namespace gas_priv __attribute__((visibility("hidden"))) {
 // Host-published gas_params rows -> the slot-indexed device table.
 int flush_param_rows(gas_ctx *c) {
 	uint32_t m = 0;
@@ -1970,6 +1581,8 @@ int flush_param_rows(gas_ctx *c) {
 	}
 	return GAS_OK;
 }
+} // namespace gas_priv
+namespace {
 
 int flush_params(gas_ctx *c) {
 	int rc = flush_param_rows(c);
@@ -1981,8 +1594,8 @@ int flush_params(gas_ctx *c) {
 	return rc;
 }
 
-void stream_rows_sync_back(gas_ctx *c);
-
+} // namespace
+namespace gas_priv __attribute__((visibility("hidden"))) {
 // gas_source_feed_rows: forget the slot's pending row.  Its bytes of the feed table stay taken until the next stream
 // callback empties the table (or feed_place moves on to the table's other half).
 void feed_drop(gas_ctx *c, uint32_t slot) {
@@ -1994,6 +1607,8 @@ void feed_drop(gas_ctx *c, uint32_t slot) {
 	*it = c->feed_slots.back();
 	c->feed_slots.pop_back();
 }
+} // namespace gas_priv
+namespace {
 
 // Frees requested on other threads become the audio thread's pending frees (deferred like audio_spatializer.cpp:538-547).
 void adopt_frees(gas_ctx *c) {
@@ -2362,10 +1977,10 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 			GAS_HIP(c, c->mem.alloc(c->d_fade_env, TAIL));
 			GAS_HIP(c, hipMemcpy(c->d_fade_env, env, sizeof(env), hipMemcpyHostToDevice));
 		}
-		GAS_HIP(c, c->mem.alloc(c->d_calc_cfgs, GAS_MAX_SPATIALIZER_CONFIGS));
-		GAS_HIP(c, c->mem.alloc(c->d_calc_listeners, GAS_MAX_LISTENERS));
-		GAS_HIP(c, c->mem.alloc(c->d_calc_slots, N));
-		GAS_HIP(c, c->mem.alloc(c->d_calc_cfgidx, N));
+		GAS_HIP(c, c->mem.alloc(c->calc.d_cfgs, GAS_MAX_SPATIALIZER_CONFIGS));
+		GAS_HIP(c, c->mem.alloc(c->calc.d_listeners, GAS_MAX_LISTENERS));
+		GAS_HIP(c, c->mem.alloc(c->calc.d_slots, N));
+		GAS_HIP(c, c->mem.alloc(c->calc.d_cfgidx, N));
 		GAS_HIP(c, c->mem.alloc(c->h_params, N, Mem::PINNED));
 		GAS_HIP(c, c->mem.alloc(c->h_upload, N, Mem::PINNED));
 		GAS_HIP(c, c->mem.alloc(c->h_upload_slots, N, Mem::PINNED));
@@ -2387,7 +2002,7 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 	c->h_routes.assign(N, gas_bus_route_default());
 	c->h_cursors.assign(N, gas_cursor{});
 	c->stamp.at.assign(N, 0);
-	c->calc_stamp.at.assign(N, 0);
+	c->calc.stamp.at.assign(N, 0);
 	c->dirty_flag.assign(N, 0);
 	if (blend_on(c)) {
 		c->h_blend.assign(N, gas_hrtf_blend{});
@@ -2789,427 +2404,9 @@ int gas_params_publish_batch(gas_ctx *c, const uint32_t *slots, const gas_params
 	return GAS_OK;
 }
 
-int gas_calc_spatialization(gas_ctx *c, const gas_spatializer3d_config *cfgs, uint32_t n_cfgs, const uint32_t *cfg_index, const gas_source_pose *poses, const gas_listener *listeners, uint32_t n_listeners, const uint32_t *slots, uint32_t n, gas_params *out_params, int mem) {
-	return gas_calc_spatialization_areas(c, cfgs, n_cfgs, cfg_index, poses, listeners, n_listeners, slots, n, nullptr, nullptr, out_params, nullptr, mem);
-}
-
-int gas_calc_spatialization_areas(gas_ctx *c, const gas_spatializer3d_config *cfgs, uint32_t n_cfgs, const uint32_t *cfg_index, const gas_source_pose *poses, const gas_listener *listeners, uint32_t n_listeners, const uint32_t *slots, uint32_t n, const gas_area_send *areas, const float *listener_area_pos, gas_params *out_params, gas_audio_frame *out_reverb, int mem) {
-	if (!c || !cfgs || !poses || !slots || (n_listeners && !listeners) || (mem != GAS_MEM_HOST && mem != GAS_MEM_DEVICE)) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (n_cfgs == 0 || n_cfgs > GAS_MAX_SPATIALIZER_CONFIGS || n_listeners > GAS_MAX_LISTENERS || n > c->cfg.max_sources) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	GAS_TRY(flush_deferred(c)); // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
-	for (uint32_t i = 0; i < n_cfgs; i++) {
-		if (cfgs[i].speaker_mode < 0 || cfgs[i].speaker_mode > 3 || !(cfgs[i].unit_size > 0.0f)) {
-			return GAS_ERR_INVALID_ARGUMENT;
-		}
-	}
-	for (uint32_t i = 0; i < n; i++) {
-		if (!live(c, slots[i])) {
-			return GAS_ERR_BAD_SLOT;
-		}
-		if (cfg_index && cfg_index[i] >= n_cfgs) {
-			return GAS_ERR_INVALID_ARGUMENT;
-		}
-	}
-	if (n == 0) {
-		return GAS_OK;
-	}
-	std::lock_guard<std::mutex> lk(c->calc_mu);
-	c->calc_stamp.next();
-	for (uint32_t i = 0; i < n; i++) {
-		if (c->calc_stamp.seen(slots[i])) {
-			return GAS_ERR_INVALID_ARGUMENT; // one playback twice: two lanes would race on its table row and its latch
-		}
-	}
-	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	GAS_TRY(flush_pending_params(c));
-	{ // rows published from the host before this call reach the table first: the launch keeps their fields it does not
-	  // write (early reflections, shelf, hrtf_* without a grid) and its own are not overwritten by them at the next callback
-		int rcr = flush_param_rows(c);
-		if (rcr != GAS_OK) {
-			return rcr;
-		}
-	}
-	{ // GAS_FLAG_HRTF_INTERPOLATE: blend rows published before this call reach the table first, so the launch's rows win
-		int rcb = flush_hrtf_blend(c);
-		if (rcb != GAS_OK) {
-			return rcb;
-		}
-	}
-	GAS_HIP(c, hipMemcpyAsync(c->d_calc_cfgs, cfgs, sizeof(gas_spatializer3d_config) * n_cfgs, hipMemcpyHostToDevice, c->stream));
-	if (n_listeners) {
-		GAS_HIP(c, hipMemcpyAsync(c->d_calc_listeners, listeners, sizeof(gas_listener) * n_listeners, hipMemcpyHostToDevice, c->stream));
-	}
-	GAS_HIP(c, hipMemcpyAsync(c->d_calc_slots, slots, sizeof(uint32_t) * n, hipMemcpyHostToDevice, c->stream));
-	if (cfg_index) {
-		GAS_HIP(c, hipMemcpyAsync(c->d_calc_cfgidx, cfg_index, sizeof(uint32_t) * n, hipMemcpyHostToDevice, c->stream));
-	}
-	const gas_source_pose *d_poses = poses;
-	gas_params *d_out = out_params;
-	if (mem == GAS_MEM_HOST) {
-		GAS_HIP(c, alloc_once(c, c->d_calc_poses, c->cfg.max_sources));
-		GAS_HIP(c, hipMemcpyAsync(c->d_calc_poses, poses, sizeof(gas_source_pose) * n, hipMemcpyHostToDevice, c->stream));
-		d_poses = c->d_calc_poses;
-		if (out_params) {
-			GAS_HIP(c, alloc_once(c, c->d_calc_out, c->cfg.max_sources));
-			d_out = c->d_calc_out;
-		}
-	}
-	const gas_area_send *d_areas = areas;
-	const float *d_lap = listener_area_pos;
-	gas_audio_frame *d_reverb = out_reverb;
-	if (mem == GAS_MEM_HOST && (areas || out_reverb)) { // staged like the poses; sized for the worst case once
-		GAS_HIP(c, alloc_once(c, c->d_calc_areas, c->cfg.max_sources));
-		GAS_HIP(c, alloc_once(c, c->d_calc_lap, (size_t)3 * GAS_MAX_LISTENERS * c->cfg.max_sources));
-		GAS_HIP(c, alloc_once(c, c->d_calc_reverb, (size_t)4 * c->cfg.max_sources));
-		if (areas) {
-			GAS_HIP(c, hipMemcpyAsync(c->d_calc_areas, areas, sizeof(gas_area_send) * n, hipMemcpyHostToDevice, c->stream));
-			d_areas = c->d_calc_areas;
-		}
-		if (listener_area_pos) {
-			GAS_HIP(c, hipMemcpyAsync(c->d_calc_lap, listener_area_pos, sizeof(float) * 3 * n_listeners * n, hipMemcpyHostToDevice, c->stream));
-			d_lap = c->d_calc_lap;
-		}
-		if (out_reverb) {
-			d_reverb = c->d_calc_reverb;
-		}
-	}
-	GAS_HIP(c, gas_launch_calc_spatialization(c->stream, c->d_calc_cfgs, cfg_index ? c->d_calc_cfgidx : nullptr, d_poses, c->d_calc_listeners, n_listeners, c->d_calc_slots, n, c->st.params, c->st.was_further, d_out, d_areas, d_lap, d_reverb, c->st.hrtf_blend));
-	if (mem == GAS_MEM_HOST && out_params) {
-		GAS_HIP(c, hipMemcpyAsync(out_params, c->d_calc_out, sizeof(gas_params) * n, hipMemcpyDeviceToHost, c->stream));
-	}
-	if (mem == GAS_MEM_HOST && out_reverb) {
-		GAS_HIP(c, hipMemcpyAsync(out_reverb, c->d_calc_reverb, sizeof(gas_audio_frame) * 4 * n, hipMemcpyDeviceToHost, c->stream));
-	}
-	GAS_HIP(c, hipStreamSynchronize(c->stream)); // the host staging arrays are the caller's
-	for (uint32_t i = 0; i < n; i++) {
-		c->slots[slots[i]].has_params = 1;
-	}
-	return GAS_OK;
-}
-
-int gas_calc_early_reflections(gas_ctx *c, const gas_room *rooms, uint32_t n_rooms, const uint32_t *room_index, const gas_source_pose *poses, const gas_listener *listener, const uint32_t *slots, uint32_t n, gas_er_taps *out_taps, int mem) {
-	if (!c || !rooms || !poses || !listener || (!slots && !out_taps) || (mem != GAS_MEM_HOST && mem != GAS_MEM_DEVICE)) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (n_rooms == 0 || n_rooms > GAS_MAX_ROOMS || n > c->cfg.max_sources || c->cfg.er_ring_frames == 0) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	for (uint32_t r = 0; r < n_rooms; r++) {
-		const gas_room &R = rooms[r];
-		bool ok = R.speed_of_sound > 0.0f && std::isfinite(R.speed_of_sound) && R.level >= 0.0f && std::isfinite(R.level) && (R.max_order == 1 || R.max_order == 2);
-		for (int a = 0; a < 3; a++) {
-			ok = ok && R.half_extent[a] > 0.0f && std::isfinite(R.half_extent[a]);
-		}
-		for (int w = 0; w < 6; w++) {
-			ok = ok && R.reflectance[w] >= 0.0f && R.reflectance[w] <= 1.0f;
-		}
-		if (!ok) {
-			return GAS_ERR_INVALID_ARGUMENT;
-		}
-	}
-	for (uint32_t i = 0; i < n; i++) {
-		if (slots && !live(c, slots[i])) {
-			return GAS_ERR_BAD_SLOT;
-		}
-		if (room_index && room_index[i] >= n_rooms && room_index[i] != GAS_ROOM_NONE) {
-			return GAS_ERR_INVALID_ARGUMENT;
-		}
-	}
-	if (n == 0) {
-		return GAS_OK;
-	}
-	std::lock_guard<std::mutex> lk(c->calc_mu);
-	if (slots) {
-		c->calc_stamp.next();
-		for (uint32_t i = 0; i < n; i++) {
-			if (c->calc_stamp.seen(slots[i])) {
-				return GAS_ERR_INVALID_ARGUMENT; // one playback twice: two lane groups would race on its row
-			}
-		}
-	}
-	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	if (slots) { // the launch writes table rows: whatever must still see or precede the old ones goes first.  Without
-		// slots the launch reads and writes nothing of the context's but the staging buffers
-		int rc = flush_deferred(c); // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch
-		rc = rc != GAS_OK ? rc : flush_pending_params(c);
-		rc = rc != GAS_OK ? rc : flush_param_rows(c); // host-published rows first: the launch's two fields land on top of them
-		if (rc != GAS_OK) {
-			return rc;
-		}
-	}
-	GAS_HIP(c, alloc_once(c, c->d_calc_rooms, GAS_MAX_ROOMS));
-	GAS_HIP(c, hipMemcpyAsync(c->d_calc_rooms, rooms, sizeof(gas_room) * n_rooms, hipMemcpyHostToDevice, c->stream));
-	GAS_HIP(c, hipMemcpyAsync(c->d_calc_listeners, listener, sizeof(gas_listener), hipMemcpyHostToDevice, c->stream));
-	if (slots) {
-		GAS_HIP(c, hipMemcpyAsync(c->d_calc_slots, slots, sizeof(uint32_t) * n, hipMemcpyHostToDevice, c->stream));
-	}
-	if (room_index) { // config indices and room indices never travel in the same call
-		GAS_HIP(c, hipMemcpyAsync(c->d_calc_cfgidx, room_index, sizeof(uint32_t) * n, hipMemcpyHostToDevice, c->stream));
-	}
-	const gas_source_pose *d_poses = poses;
-	gas_er_taps *d_taps = out_taps;
-	if (mem == GAS_MEM_HOST) {
-		GAS_HIP(c, alloc_once(c, c->d_calc_poses, c->cfg.max_sources));
-		GAS_HIP(c, hipMemcpyAsync(c->d_calc_poses, poses, sizeof(gas_source_pose) * n, hipMemcpyHostToDevice, c->stream));
-		d_poses = c->d_calc_poses;
-		if (out_taps) { // staged in the read-back buffer of gas_calc_spatialization's rows: a gas_er_taps is half a row
-			static_assert(sizeof(gas_er_taps) <= sizeof(gas_params), "gas_er_taps are staged in d_calc_out");
-			GAS_HIP(c, alloc_once(c, c->d_calc_out, c->cfg.max_sources));
-			d_taps = reinterpret_cast<gas_er_taps *>(c->d_calc_out);
-		}
-	}
-	GAS_HIP(c, gas_launch_calc_er(c->stream, c->d_calc_rooms, room_index ? c->d_calc_cfgidx : nullptr, d_poses, c->d_calc_listeners, c->d_calc_slots, n, c->cfg.er_ring_frames - c->cfg.frames, c->cfg.mix_rate, slots ? c->st.params : nullptr, d_taps));
-	if (mem == GAS_MEM_HOST && out_taps) {
-		GAS_HIP(c, hipMemcpyAsync(out_taps, d_taps, sizeof(gas_er_taps) * n, hipMemcpyDeviceToHost, c->stream));
-	}
-	GAS_HIP(c, hipStreamSynchronize(c->stream)); // the host staging arrays are the caller's
-	return GAS_OK;
-}
-
-static inline void stream_rows_sync_back_fwd(gas_ctx *c) {
-	stream_rows_sync_back(c);
-}
-
-int gas_stream_create(gas_ctx *c, const void *pcm, int format, uint32_t channels, uint64_t frames, uint32_t *out_stream) {
-	if (!c || !pcm || !out_stream || (format != GAS_PCM_S16 && format != GAS_PCM_F32 && format != GAS_PCM_IMA_ADPCM && format != GAS_PCM_QOA) || (channels != 1 && channels != 2) || frames == 0) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (format == GAS_PCM_QOA && !gas_qoa_validate(static_cast<const uint8_t *>(pcm), gas_qoa_file_bytes(frames, channels), channels, frames)) {
-		return GAS_ERR_INVALID_ARGUMENT; // the magic first: nothing else is read of data that are no QOA file
-	}
-	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	size_t bytes = (size_t)frames * channels * (format == GAS_PCM_S16 ? 2 : 4);
-	std::vector<uint8_t> adpcm; // codes padded to whole chunks ++ checkpoint table (gas_internal.h)
-	if (format == GAS_PCM_IMA_ADPCM) {
-		bytes = (size_t)gas_adpcm_device_bytes(frames, channels);
-		try {
-			adpcm.assign(bytes, 0);
-		} catch (const std::exception &) { // a length no host can stage
-			return GAS_ERR_OUT_OF_MEMORY;
-		}
-		std::memcpy(adpcm.data(), pcm, (size_t)((frames + 1) / 2) * channels);
-		gas_adpcm_ckpt *table = reinterpret_cast<gas_adpcm_ckpt *>(adpcm.data() + gas_adpcm_table_offset(frames, channels));
-		for (uint32_t ch = 0; ch < channels; ch++) { // decode once, keeping the state in front of every chunk
-			int32_t predictor = 0, step_index = 0;
-			for (uint64_t i = 0; i < frames; i++) {
-				if (i % GAS_ADPCM_CHUNK == 0) {
-					table[(i / GAS_ADPCM_CHUNK) * channels + ch] = gas_adpcm_ckpt{ (int16_t)predictor, (uint8_t)step_index, 0 };
-				}
-				const uint32_t n = (adpcm[(i >> 1) * channels + ch] >> ((i & 1) * 4)) & 15u;
-				gas_adpcm_step(predictor, step_index, n, gas_adpcm_step_size((uint32_t)step_index));
-			}
-		}
-		pcm = adpcm.data();
-	}
-	std::vector<gas_qoa_record> qoa; // [chunk][channel] (gas_qoa.h)
-	if (format == GAS_PCM_QOA) {
-		bytes = (size_t)gas_qoa_device_bytes(frames, channels);
-		try {
-			qoa.assign(bytes / sizeof(gas_qoa_record), gas_qoa_record{});
-		} catch (const std::exception &) {
-			return GAS_ERR_OUT_OF_MEMORY;
-		}
-		gas_qoa_build_records(static_cast<const uint8_t *>(pcm), channels, frames, qoa.data()); // decodes once, keeping the state in front of every chunk
-		pcm = qoa.data();
-	}
-	gas_ctx::StreamInfo si;
-	GAS_HIP(c, c->mem.alloc(si.d_pcm, bytes));
-	hipError_t e = hipMemcpy(si.d_pcm, pcm, bytes, hipMemcpyHostToDevice);
-	if (e != hipSuccess) {
-		c->mem.drop(si.d_pcm);
-		c->last_err = hipGetErrorString(e);
-		return GAS_ERR_DEVICE;
-	}
-	si.frames = frames;
-	si.format = (uint32_t)format;
-	si.channels = channels;
-	for (size_t i = 0; i < c->streams.size(); i++) {
-		if (!c->streams[i].d_pcm) {
-			c->streams[i] = si;
-			*out_stream = (uint32_t)i;
-			return GAS_OK;
-		}
-	}
-	c->streams.push_back(si);
-	*out_stream = (uint32_t)c->streams.size() - 1;
-	return GAS_OK;
-}
-
-int gas_stream_destroy(gas_ctx *c, uint32_t stream) {
-	if (!c) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (stream >= c->streams.size() || !c->streams[stream].d_pcm) {
-		return GAS_ERR_BAD_SLOT;
-	}
-	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	GAS_HIP(c, hipStreamSynchronize(c->stream));
-	for (gas_cursor &cur : c->h_cursors) {
-		if (cur.pcm == c->streams[stream].d_pcm) {
-			return GAS_ERR_INVALID_ARGUMENT; // still bound to a playback
-		}
-	}
-	c->mem.drop(c->streams[stream].d_pcm);
-	c->streams[stream] = gas_ctx::StreamInfo{};
-	return GAS_OK;
-}
-
-int gas_stream_get_info(gas_ctx *c, uint32_t stream, uint64_t *out_frames, uint32_t *out_channels, int *out_format) {
-	if (!c) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (stream >= c->streams.size() || !c->streams[stream].d_pcm) {
-		return GAS_ERR_BAD_SLOT;
-	}
-	if (out_frames) {
-		*out_frames = c->streams[stream].frames;
-	}
-	if (out_channels) {
-		*out_channels = c->streams[stream].channels;
-	}
-	if (out_format) {
-		*out_format = (int)c->streams[stream].format;
-	}
-	return GAS_OK;
-}
-
-int gas_stream_positions(gas_ctx *c, uint32_t n, uint64_t *out_frames) {
-	if (!c || (n > 0 && !out_frames)) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (n != c->stream_slots_host.size()) {
-		return GAS_ERR_INVALID_ARGUMENT; // not the list of the last stream callback (gas_process_block_streams or gas_process_block_streams_buses)
-	}
-	// The compact row mirror holds the positions while the list is cached; a block boundary that applied deferred
-	// frees has folded it back into the per-slot cursors (stream_rows_sync_back) and emptied it.
-	const bool rows_live = c->stream_rows.size() == n;
-	for (uint32_t i = 0; i < n; i++) {
-		const gas_cursor &cur = c->h_cursors[c->stream_slots_host[i]];
-		if (!cur.pcm) {
-			out_frames[i] = 0;
-		} else if (rows_live) {
-			const gas_ctx::StreamRow &r = c->stream_rows[i];
-			out_frames[i] = r.resampled ? (r.fp_pos >> 16) : r.looped ? r.pos : cur.frames - r.remaining;
-		} else {
-			out_frames[i] = cur.resampled ? (cur.fp_pos >> 16) : cur.pos;
-		}
-		if (cur.pcm && cur.loop_mode) { // the stream frame taken next, m(frames consumed)
-			out_frames[i] = gas_loop_map(out_frames[i], cur.loop_begin, cur.loop_len, cur.loop_mode);
-		}
-	}
-	return GAS_OK;
-}
-
-int gas_stream_set_resampled(gas_ctx *c, uint32_t stream, int on) {
-	if (!c) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (stream >= c->streams.size() || !c->streams[stream].d_pcm) {
-		return GAS_ERR_BAD_SLOT;
-	}
-	for (const gas_cursor &cur : c->h_cursors) {
-		if (cur.pcm == c->streams[stream].d_pcm) {
-			return GAS_ERR_INVALID_ARGUMENT; // the playback class is chosen before playbacks are bound
-		}
-	}
-	c->streams[stream].resampled = on != 0;
-	return GAS_OK;
-}
-
-int gas_stream_set_loop(gas_ctx *c, uint32_t stream, int mode, uint64_t loop_begin, uint64_t loop_end) {
-	if (!c) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (stream >= c->streams.size() || !c->streams[stream].d_pcm) {
-		return GAS_ERR_BAD_SLOT;
-	}
-	gas_ctx::StreamInfo &si = c->streams[stream];
-	for (const gas_cursor &cur : c->h_cursors) {
-		if (cur.pcm == si.d_pcm) {
-			return GAS_ERR_INVALID_ARGUMENT; // the loop is chosen before playbacks are bound
-		}
-	}
-	if (mode == GAS_LOOP_DISABLED) {
-		si.loop_mode = 0;
-		si.loop_begin = si.loop_end = 0;
-		return GAS_OK;
-	}
-	if (mode != GAS_LOOP_FORWARD && mode != GAS_LOOP_PINGPONG) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	const uint64_t end = loop_end == 0 ? si.frames : loop_end;
-	if (loop_begin >= end || end > si.frames || end - loop_begin >= (1ull << 31)) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	si.loop_mode = (uint32_t)mode;
-	si.loop_begin = loop_begin;
-	si.loop_end = end;
-	return GAS_OK;
-}
-
-int gas_stream_get_loop(gas_ctx *c, uint32_t stream, int *out_mode, uint64_t *out_begin, uint64_t *out_end) {
-	if (!c) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (stream >= c->streams.size() || !c->streams[stream].d_pcm) {
-		return GAS_ERR_BAD_SLOT;
-	}
-	if (out_mode) {
-		*out_mode = (int)c->streams[stream].loop_mode;
-	}
-	if (out_begin) {
-		*out_begin = c->streams[stream].loop_begin;
-	}
-	if (out_end) {
-		*out_end = c->streams[stream].loop_end;
-	}
-	return GAS_OK;
-}
-
-int gas_source_bind_stream(gas_ctx *c, uint32_t slot, uint32_t stream, uint64_t start_frame) {
-	if (!c) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (slot >= c->cfg.max_sources || !c->slots[slot].used || stream >= c->streams.size() || !c->streams[stream].d_pcm) {
-		return GAS_ERR_BAD_SLOT;
-	}
-	stream_rows_sync_back_fwd(c);
-	c->stream_groups_gen = UINT64_MAX;
-	feed_drop(c, slot); // gas_source_feed_rows: the stream supplies the windows from here on
-	const gas_ctx::StreamInfo &si = c->streams[stream];
-	gas_cursor cur{};
-	cur.pcm = si.d_pcm;
-	cur.frames = si.frames;
-	cur.pos = start_frame < si.frames ? start_frame : si.frames;
-	if (si.loop_mode) { // a position on the unrolled timeline: not clamped
-		cur.pos = start_frame;
-		cur.loop_begin = si.loop_begin;
-		cur.loop_len = (uint32_t)(si.loop_end - si.loop_begin);
-		cur.loop_mode = si.loop_mode;
-	}
-	cur.start = cur.pos;
-	cur.format_channels = (si.format << 8) | si.channels;
-	cur.has_frames = 1;
-	cur.resampled = si.resampled ? 1 : 0;
-	cur.fp_pos = cur.pos << 16; // [ENGINE] begin_resample: mix_offset = 0, zeroed interpolation history
-	c->h_cursors[slot] = cur;
-	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	GAS_HIP(c, hipMemcpyAsync(c->d_cursors + slot, &c->h_cursors[slot], sizeof(gas_cursor), hipMemcpyHostToDevice, c->stream));
-	GAS_HIP(c, hipStreamSynchronize(c->stream));
-	if (c->slots[slot].draining) {
-		c->slots[slot].draining = 0;
-		c->cached_n = UINT32_MAX;
-	}
-	return GAS_OK;
-}
-
 } // extern "C"
 
-namespace {
+namespace gas_priv __attribute__((visibility("hidden"))) {
 // Write the compact per-row mirror of the cached stream list back into the per-slot cursors.
 void stream_rows_sync_back(gas_ctx *c) {
 	for (size_t i = 0; i < c->stream_rows.size(); i++) {
@@ -3225,60 +2422,9 @@ void stream_rows_sync_back(gas_ctx *c) {
 	}
 	c->stream_rows.clear();
 }
+} // namespace gas_priv
 
-inline size_t feed_header_bytes(const gas_ctx *c) {
-	return ((size_t)c->cfg.max_sources * sizeof(uint32_t) + 15) & ~(size_t)15;
-}
-
-// Where the next `bytes` of rows go in the feed table.  The table is allocated once, at the first feed: the header and
-// two halves of max_sources float32 stereo rows each.  Rows are appended in the current half.  When it is full -- rows
-// that were replaced, or fed while no callback ran, leave holes -- the pending rows this call does not replace (those
-// without its stamp) move to the front of the other half and the new rows follow them: together at most max_sources
-// rows, so they fit.  Everything is a copy in the context's stream order from one half into the other: no allocation and
-// no wait on the audio thread.  Nothing is committed here: feed_moved holds the moved rows' new words, and the caller
-// switches halves once its own copy is enqueued.
-int feed_place(gas_ctx *c, size_t bytes, size_t &at, bool &switched) {
-	const size_t hdr = feed_header_bytes(c), half = (size_t)c->cfg.max_sources * c->cfg.frames * sizeof(gas_audio_frame);
-	if (!c->d_feed) {
-		if (alloc_once(c, c->h_feed_entry, c->cfg.max_sources, Mem::PINNED) != hipSuccess) {
-			return GAS_ERR_OUT_OF_MEMORY;
-		}
-		if (!c->feed_entry_ev) {
-			GAS_HIP(c, c->mem.make_event(c->feed_entry_ev, hipEventDisableTiming));
-		}
-		if (c->mem.alloc(c->d_feed, hdr + 2 * half) != hipSuccess) {
-			return GAS_ERR_OUT_OF_MEMORY;
-		}
-		c->feed_used = 0;
-	}
-	if (c->feed_used < hdr) { // emptied by a callback: start over
-		c->feed_used = hdr;
-		c->feed_side = 0;
-	}
-	c->feed_moved.clear();
-	switched = false;
-	if (c->feed_used + bytes <= hdr + (c->feed_side + 1) * half) {
-		at = c->feed_used;
-		return GAS_OK;
-	}
-	switched = true;
-	const uint32_t F = c->cfg.frames;
-	size_t off = hdr + (1 - c->feed_side) * half;
-	for (uint32_t s : c->feed_slots) {
-		if (c->stamp.has(s)) {
-			continue; // this call replaces it
-		}
-		const uint32_t w = c->feed_word[s];
-		const size_t rb = gas_feed_row_bytes(w, F);
-		GAS_HIP(c, hipMemcpyAsync(c->d_feed + off, c->d_feed + gas_feed_offset(w), rb, hipMemcpyDeviceToDevice, c->stream));
-		c->feed_moved.push_back(s);
-		c->feed_moved.push_back(gas_feed_word(off, (w & 2u) ? GAS_PCM_F32 : GAS_PCM_S16, (w & 1u) + 1u));
-		off += rb;
-	}
-	at = off;
-	return GAS_OK;
-}
-
+namespace {
 // The staging of the callback entries.  d_src holds at least `frames` frames afterwards.
 // (hipFree synchronises the device by itself: waiting for the stream in front of it changes nothing observable.)
 hipError_t ensure_src(gas_ctx *c, size_t frames) {
@@ -3342,7 +2488,9 @@ BusList bus_list_form(const gas_ctx *c, const uint32_t *slots, uint32_t n) {
 	}
 	return all_plain_hrtf ? BUS_LIST_PLAIN_HRTF : BUS_LIST_CHAINS;
 }
+} // namespace
 
+namespace gas_priv __attribute__((visibility("hidden"))) {
 // A failed callback leaves a zeroed mix in host memory (the reference's ERR_FAIL paths, audio_spatializer.cpp:335-343);
 // device memory is left as it is.
 int fail_out(int code, int mem, gas_audio_frame *out, size_t out_bytes) {
@@ -3351,7 +2499,7 @@ int fail_out(int code, int mem, gas_audio_frame *out, size_t out_bytes) {
 	}
 	return code;
 }
-} // namespace
+} // namespace gas_priv
 
 extern "C" {
 
@@ -3643,142 +2791,6 @@ int gas_process_block_streams_buses(gas_ctx *c, const uint32_t *slots, uint32_t 
 
 int gas_stream_last_fused(gas_ctx *c) {
 	return c ? (c->stream_last_fused ? 1 : 0) : GAS_ERR_INVALID_ARGUMENT;
-}
-
-int gas_source_feed_rows(gas_ctx *c, const uint32_t *slots, const void *rows, int format, uint32_t channels, uint32_t n, uint32_t frames, int mem) {
-	if (!c || (n > 0 && (!slots || !rows)) || n > c->cfg.max_sources || (format != GAS_PCM_S16 && format != GAS_PCM_F32) || (channels != 1 && channels != 2) || (mem != GAS_MEM_HOST && mem != GAS_MEM_DEVICE)) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	const uint32_t F = c->cfg.frames;
-	if (frames != F) {
-		return GAS_ERR_FRAME_COUNT;
-	}
-	GAS_TRY(flush_deferred(c)); // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
-	// everything is checked before anything is taken
-	c->stamp.next();
-	{
-		std::lock_guard<std::mutex> alloc_lk(c->alloc_mu); // pending_free is set by gas_source_free on any thread
-		for (uint32_t i = 0; i < n; i++) {
-			if (!live(c, slots[i]) || c->slots[slots[i]].pending_free) {
-				return GAS_ERR_BAD_SLOT;
-			}
-		}
-	}
-	for (uint32_t i = 0; i < n; i++) {
-		if (c->h_cursors[slots[i]].pcm) {
-			return GAS_ERR_INVALID_ARGUMENT; // bound to a stream: the sampler supplies its windows
-		}
-		if (c->stamp.seen(slots[i])) {
-			return GAS_ERR_INVALID_ARGUMENT; // one playback twice in a call
-		}
-	}
-	if (n == 0) {
-		return GAS_OK;
-	}
-	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	const size_t row_bytes = (size_t)F * (format == GAS_PCM_F32 ? 4u : 2u) * channels; // a multiple of 256: frames % 128 == 0
-	const size_t bytes = (size_t)n * row_bytes;
-	if (mem == GAS_MEM_HOST && bytes > c->h_feed_cap) { // grows to the largest call: not in the steady state
-		if (c->feed_ev) {
-			GAS_HIP(c, hipEventSynchronize(c->feed_ev));
-		} else {
-			GAS_HIP(c, c->mem.make_event(c->feed_ev, hipEventDisableTiming));
-		}
-		if (c->mem.grow(c->h_feed, c->h_feed_cap, bytes, 1, Mem::PINNED) != hipSuccess) {
-			return GAS_ERR_OUT_OF_MEMORY;
-		}
-	}
-	size_t at = 0;
-	bool switched = false;
-	const int rcp = feed_place(c, bytes, at, switched);
-	if (rcp != GAS_OK) {
-		return rcp;
-	}
-	uint8_t *dst = c->d_feed + at;
-	const int rcc = [&]() -> int {
-		if (mem == GAS_MEM_DEVICE) {
-			const int rcj = join_outputs(c); // GAS_FLAG_PIPELINED_MIX: `rows` may be an earlier callback's out, still a pending sum
-			if (rcj != GAS_OK) {
-				return rcj;
-			}
-			GAS_HIP(c, hipMemcpyAsync(dst, rows, bytes, hipMemcpyDeviceToDevice, c->stream));
-			return GAS_OK;
-		}
-		GAS_HIP(c, hipEventSynchronize(c->feed_ev)); // the previous upload has left the staging: a wait only while it is still queued
-		std::memcpy(c->h_feed, rows, bytes);
-		GAS_HIP(c, hipMemcpyAsync(dst, c->h_feed, bytes, hipMemcpyHostToDevice, c->stream));
-		GAS_HIP(c, hipEventRecord(c->feed_ev, c->stream));
-		return GAS_OK;
-	}();
-	if (rcc != GAS_OK) {
-		return rcc; // nothing committed: every pending row is still where its word says
-	}
-	if (switched) {
-		c->feed_side = 1 - c->feed_side;
-		for (size_t k = 0; k + 1 < c->feed_moved.size(); k += 2) {
-			c->feed_word[c->feed_moved[k]] = c->feed_moved[k + 1];
-		}
-	}
-	for (uint32_t i = 0; i < n; i++) {
-		if (c->feed_word[slots[i]] == GAS_FEED_NONE) {
-			c->feed_slots.push_back(slots[i]);
-		} // else: replaces the row fed before; its bytes lie idle until the table is emptied
-		c->feed_word[slots[i]] = gas_feed_word(at + (size_t)i * row_bytes, format, channels);
-	}
-	c->feed_used = at + bytes;
-	return GAS_OK;
-}
-
-int gas_hrtf_load(gas_ctx *c, const float *hrir, uint32_t dirs, uint32_t taps) {
-	if (!c || !hrir || dirs == 0 || taps == 0 || taps > GAS_HRTF_TAPS) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	{ // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
-		const int rcd = flush_deferred(c);
-		if (rcd != GAS_OK) {
-			return rcd;
-		}
-	}
-	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	GAS_HIP(c, hipStreamSynchronize(c->stream));
-	c->mem.drop(c->tab.spec);
-	c->tab.dirs = 0;
-	Mem tmp; // frees d_hrir on every way out
-	float *d_hrir = nullptr;
-	const size_t floats = (size_t)dirs * 2 * taps;
-	GAS_HIP(c, tmp.alloc(d_hrir, floats));
-	GAS_HIP(c, hipMemcpyAsync(d_hrir, hrir, floats * sizeof(float), hipMemcpyHostToDevice, c->stream));
-	GAS_HIP(c, c->mem.alloc(c->tab.spec, (size_t)dirs * 4 * 64)); // bins 0..255, Hermitian half
-	GAS_HIP(c, gas_launch_hrtf_table(c->stream, d_hrir, dirs, taps, c->d_tw, c->tab.spec));
-	GAS_HIP(c, hipStreamSynchronize(c->stream));
-	c->tab.dirs = dirs;
-	c->params_gen++;
-	return GAS_OK;
-}
-
-int gas_hrtf_load_positions(gas_ctx *c, const float *positions, const float *hrir, uint32_t m, uint32_t taps, uint32_t az_steps, uint32_t el_steps, int interpolation, float *out_hrir) {
-	if (!c || !positions || !hrir || m == 0 || taps == 0 || taps > GAS_HRTF_TAPS || az_steps == 0 || el_steps == 0 || (uint64_t)az_steps * el_steps > (1u << 20) || (interpolation != 0 && interpolation != 1)) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	const uint32_t dirs = az_steps * el_steps;
-	std::vector<float> grid((size_t)dirs * 2 * GAS_HRTF_TAPS);
-	{
-		Mem tmp; // frees the three on every way out of the block
-		float *d_pos = nullptr, *d_in = nullptr, *d_grid = nullptr;
-		GAS_HIP(c, tmp.alloc(d_pos, (size_t)m * 2));
-		GAS_HIP(c, tmp.alloc(d_in, (size_t)m * 2 * taps));
-		GAS_HIP(c, tmp.alloc(d_grid, grid.size()));
-		GAS_HIP(c, hipMemcpyAsync(d_pos, positions, (size_t)m * 2 * sizeof(float), hipMemcpyHostToDevice, c->stream));
-		GAS_HIP(c, hipMemcpyAsync(d_in, hrir, (size_t)m * 2 * taps * sizeof(float), hipMemcpyHostToDevice, c->stream));
-		GAS_HIP(c, gas_launch_hrtf_regrid(c->stream, d_pos, d_in, m, taps, az_steps, el_steps, interpolation, d_grid));
-		GAS_HIP(c, hipMemcpyAsync(grid.data(), d_grid, grid.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-		GAS_HIP(c, hipStreamSynchronize(c->stream));
-	}
-	if (out_hrir) {
-		std::memcpy(out_hrir, grid.data(), grid.size() * sizeof(float));
-	}
-	return gas_hrtf_load(c, grid.data(), dirs, GAS_HRTF_TAPS);
 }
 
 int gas_process_block(gas_ctx *c, const gas_audio_frame *src, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, float *peaks, int mem) {
@@ -4169,736 +3181,6 @@ int gas_process_frames_1(gas_ctx *c, uint32_t slot, gas_audio_frame *out, const 
 
 int gas_mix_channel_1(gas_ctx *c, uint32_t slot, int channel, gas_audio_frame *out, const gas_audio_frame *src, int frame_count) {
 	return process_one(c, slot, channel, true, out, src, frame_count);
-}
-
-int gas_profile_enable(gas_ctx *c, int on) {
-	if (!c) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	{ // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
-		const int rcd = flush_deferred(c);
-		if (rcd != GAS_OK) {
-			return rcd;
-		}
-	}
-	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	if (on && c->ev.empty()) {
-		std::vector<hipEvent_t> ev(PROFILE_EVENTS, nullptr);
-		for (hipEvent_t &e : ev) {
-			GAS_HIP(c, c->mem.make_event(e, hipEventDefault)); // a failure leaves c->ev empty and what exists to the owner
-		}
-		c->ev = std::move(ev);
-	}
-	if (on) {
-		// An event pair around a launch reads the launch's span on the GPU timeline plus the cost of the second
-		// marker.  Only the marker is calibrated away (an empty bracket, minimum of 16 tries): the dispatch ramp of
-		// the kernel itself stays in, exactly as rocprofv3's kernel trace counts it (an empty kernel reads 3-4 us
-		// there), so the two figures of one run agree and neither flatters the kernel.
-		GAS_HIP(c, hipStreamSynchronize(c->stream));
-		double best = 1e9;
-		for (int i = 0; i < 16; i++) {
-			GAS_HIP(c, hipEventRecord(c->ev[0], c->stream));
-			GAS_HIP(c, hipEventRecord(c->ev[1], c->stream));
-			GAS_HIP(c, hipEventSynchronize(c->ev[1]));
-			float ms = 0.0f;
-			GAS_HIP(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
-			best = ms < best ? ms : best;
-		}
-		c->ev_overhead_ms = best;
-	}
-	c->profiling = on != 0;
-	c->prof_every = on > 1 ? (uint32_t)on : 1; // on = N > 1: bracket every Nth callback only (the markers cost throughput)
-	c->prof_tick = 0;
-	return GAS_OK;
-}
-
-int gas_ctx_read_hrtf_order(gas_ctx *c, uint32_t *out, uint32_t n) {
-	if (!c || !out) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	{ // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
-		const int rcd = flush_deferred(c);
-		if (rcd != GAS_OK) {
-			return rcd;
-		}
-	}
-	if (!c->d_order || !c->order_ok[G_FX_HRTF] || !c->last_uni_ordered || n > c->groups[G_FX_HRTF].count) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	GAS_HIP(c, hipStreamSynchronize(c->stream));
-	GAS_HIP(c, hipMemcpy(out, c->d_order + c->groups[G_FX_HRTF].offset, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-	return GAS_OK;
-}
-
-int gas_bandwidth_probe(gas_ctx *c, uint64_t read_bytes, uint64_t write_bytes, uint32_t workgroups, uint32_t unroll, uint32_t iters, double *out_us) {
-	if (!c || !out_us || iters == 0 || workgroups == 0 || read_bytes % 16 != 0 || write_bytes % 16 != 0 || read_bytes + write_bytes == 0) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	{ // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
-		const int rcd = flush_deferred(c);
-		if (rcd != GAS_OK) {
-			return rcd;
-		}
-	}
-	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	GAS_HIP(c, hipStreamSynchronize(c->stream));
-	// the read arena is swept in rotation so that successive launches cannot be served by the 256 MiB Infinity Cache
-	const size_t want_rd = read_bytes ? ((size_t)(320u << 20) / read_bytes + 2) * read_bytes : 16;
-	if (want_rd > c->probe_rd_bytes) {
-		GAS_HIP(c, c->mem.grow(c->d_probe_rd, c->probe_rd_bytes, want_rd));
-		GAS_HIP(c, hipMemsetAsync(c->d_probe_rd, 0, want_rd, c->stream));
-	}
-	const size_t want_wr = write_bytes ? write_bytes : 16;
-	GAS_HIP(c, c->mem.grow(c->d_probe_wr, c->probe_wr_bytes, want_wr));
-	GAS_HIP(c, alloc_once(c, c->d_probe_sink, 256));
-	Mem tmp; // destroys the two events on every way out
-	hipEvent_t e0 = nullptr, e1 = nullptr;
-	GAS_HIP(c, tmp.make_event(e0, hipEventDefault));
-	GAS_HIP(c, tmp.make_event(e1, hipEventDefault));
-	// marker calibration as in gas_profile_enable: an empty bracket, minimum of 16 tries
-	double marker = 1e9;
-	for (int i = 0; i < 16; i++) {
-		GAS_HIP(c, hipEventRecord(e0, c->stream));
-		GAS_HIP(c, hipEventRecord(e1, c->stream));
-		GAS_HIP(c, hipEventSynchronize(e1));
-		float ms = 0.0f;
-		GAS_HIP(c, hipEventElapsedTime(&ms, e0, e1));
-		marker = ms < marker ? ms : marker;
-	}
-	const size_t slices = read_bytes ? c->probe_rd_bytes / read_bytes : 1;
-	size_t k = 0;
-	auto launch = [&]() {
-		const char *rd = static_cast<const char *>(c->d_probe_rd) + (k++ % slices) * read_bytes;
-		return gas_launch_stream_probe(c->stream, rd, read_bytes, c->d_probe_wr, write_bytes, workgroups, unroll, c->d_probe_sink);
-	};
-	for (int i = 0; i < 8; i++) { // warm-up, back to back
-		GAS_HIP(c, launch());
-	}
-	double sum_ms = 0.0;
-	for (uint32_t i = 0; i < iters; i++) {
-		GAS_HIP(c, launch()); // an unbracketed launch in front keeps the GPU busy, as the bench's callbacks do
-		GAS_HIP(c, hipEventRecord(e0, c->stream));
-		GAS_HIP(c, launch());
-		GAS_HIP(c, hipEventRecord(e1, c->stream));
-		GAS_HIP(c, hipEventSynchronize(e1));
-		float ms = 0.0f;
-		GAS_HIP(c, hipEventElapsedTime(&ms, e0, e1));
-		sum_ms += ms > marker ? ms - marker : 0.0;
-	}
-	*out_us = sum_ms / iters * 1e3;
-	return GAS_OK;
-}
-
-int gas_profile_read(gas_ctx *c, gas_profile *out, int reset) {
-	if (!c || !out) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	{ // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
-		const int rcd = flush_deferred(c);
-		if (rcd != GAS_OK) {
-			return rcd;
-		}
-	}
-	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	GAS_HIP(c, hipStreamSynchronize(c->stream));
-	for (uint32_t i = 0; i + 1 < c->ev_used; i += 2) {
-		float ms = 0.0f;
-		GAS_HIP(c, hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]));
-		c->prof_ms += ms > c->ev_overhead_ms ? ms - c->ev_overhead_ms : 0.0;
-		c->prof_launches++;
-	}
-	c->ev_used = 0;
-	std::memset(out, 0, sizeof(*out));
-	out->launches = c->prof_launches;
-	out->kernel_ms = c->prof_ms;
-	out->bytes_per_launch = c->prof_bytes;
-	out->callbacks_per_launch = c->prof_k;
-	out->bytes_per_callback_formula = c->prof_k > 1 ? c->prof_bytes_formula : c->prof_bytes;
-	if (c->prof_group >= 0) {
-		std::string name = c->prof_multi ? "k_hrtf_multi" : (c->prof_uni ? "k_hrtf_uni" : k_group_kernel[c->prof_group]);
-		if (c->prof_pipe && name.rfind("k_biquad_mix", 0) == 0) {
-			name = "k_biquad_pipe" + name.substr(12);
-		}
-		std::strncpy(out->kernel_name, name.c_str(), sizeof(out->kernel_name) - 1);
-	}
-	if (reset) {
-		c->prof_launches = 0;
-		c->prof_ms = 0.0;
-	}
-	return GAS_OK;
-}
-
-// ---- bus convolvers (NEW; k_conv.hip) ---------------------------------------------------------------------------------
-
-#define GAS_CONV_MAX_IR_TAPS (1u << 20)
-
-static void conv_release(gas_ctx *c) {
-	c->mem.drop(c->conv_pool.ring);
-	c->mem.drop(c->conv_pool.prev);
-	c->mem.drop(c->conv_pool.ypart);
-	c->mem.drop(c->conv_w1024);
-	c->mem.drop(c->conv_h_in);
-	c->mem.drop(c->conv_h_out);
-	c->mem.drop(c->conv_d_in);
-	c->mem.drop(c->conv_d_out);
-	c->conv_pool = gas_conv_pool{};
-	c->conv_count = 0;
-	c->conv_max_taps = 0;
-	c->conv.clear();
-	c->conv_free.clear();
-	c->conv_irs.clear();
-}
-
-// The instance's ring and previous block become zeros in stream order: x[t] = 0 for every earlier t.
-static hipError_t conv_zero(gas_ctx *c, uint32_t conv) {
-	const size_t ring = (size_t)2 * c->conv_pool.K * GAS_CONV_BINS;
-	const hipError_t e = hipMemsetAsync(c->conv_pool.ring + conv * ring, 0, ring * sizeof(float2), c->stream);
-	return e != hipSuccess ? e : hipMemsetAsync(c->conv_pool.prev + (size_t)conv * 2 * 512, 0, 2 * 512 * sizeof(float), c->stream);
-}
-
-static bool conv_live(const gas_ctx *c, uint32_t conv) {
-	return conv < c->conv_count && c->conv[conv].used;
-}
-
-static bool conv_ir_live(const gas_ctx *c, uint32_t ir) {
-	return ir < c->conv_irs.size() && c->conv_irs[ir].H != nullptr;
-}
-
-// The fade in progress ends in state B: A's IR is no longer named, B's reference becomes the state's.
-static void conv_fade_land(gas_ctx *c, gas_ctx::ConvInst &k) {
-	c->conv_irs[k.ir].users--;
-	k.ir = k.to.ir;
-	k.dry = k.to.dry;
-	k.wet = k.to.wet;
-	k.fade_n = k.fade_pos = 0;
-}
-
-// gas_conv_set_ir, gas_conv_set_levels: a fade in progress ends at once in state B and a pending target is dropped.
-static void conv_fade_end(gas_ctx *c, gas_ctx::ConvInst &k) {
-	if (k.fade_n) {
-		conv_fade_land(c, k);
-	}
-	if (k.pending_n) {
-		c->conv_irs[k.pending.ir].users--;
-		k.pending_n = 0;
-	}
-}
-
-int gas_ctx_reserve_conv(gas_ctx *c, uint32_t convolvers, uint32_t max_ir_taps) {
-	if (!c || convolvers > GAS_MAX_CONVOLVERS || max_ir_taps > GAS_CONV_MAX_IR_TAPS || (convolvers == 0) != (max_ir_taps == 0)) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	for (const auto &k : c->conv) {
-		if (k.used) {
-			return GAS_ERR_INVALID_ARGUMENT;
-		}
-	}
-	for (const auto &ir : c->conv_irs) {
-		if (ir.H) {
-			return GAS_ERR_INVALID_ARGUMENT;
-		}
-	}
-	GAS_TRY(flush_deferred(c));
-	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	GAS_HIP(c, hipStreamSynchronize(c->stream));
-	conv_release(c);
-	if (convolvers == 0) {
-		return GAS_OK;
-	}
-	const uint32_t F = c->cfg.frames;
-	const uint32_t K = (max_ir_taps + F - 1) / F;
-	const int rc = [&]() -> int {
-		gas_conv_pool &p = c->conv_pool;
-		p.K = K;
-		p.max_chunks = gas_conv_max_chunks(K);
-		GAS_HIP(c, c->mem.alloc(p.ring, (size_t)convolvers * 2 * K * GAS_CONV_BINS));
-		GAS_HIP(c, c->mem.alloc(p.prev, (size_t)convolvers * 2 * 512));
-		// two rows (ears) per named instance and two more per fading one: 96 rows of max_chunks spectra of 4 KiB,
-		// 393 216 max_chunks bytes
-		GAS_HIP(c, c->mem.alloc(p.ypart, (size_t)GAS_MAX_CONVOLVERS * 4 * p.max_chunks * GAS_CONV_BINS));
-		GAS_HIP(c, c->mem.alloc(c->conv_w1024, 512));
-		const size_t stage = (size_t)GAS_MAX_CONVOLVERS * F;
-		GAS_HIP(c, c->mem.alloc(c->conv_h_in, stage, Mem::PINNED));
-		GAS_HIP(c, c->mem.alloc(c->conv_h_out, stage, Mem::PINNED));
-		GAS_HIP(c, c->mem.alloc(c->conv_d_in, stage));
-		GAS_HIP(c, c->mem.alloc(c->conv_d_out, stage));
-		float2 w[512];
-		gas_make_w1024(w);
-		GAS_HIP(c, hipMemcpyAsync(c->conv_w1024, w, sizeof(w), hipMemcpyHostToDevice, c->stream));
-		GAS_HIP(c, hipStreamSynchronize(c->stream));
-		p.w1024 = c->conv_w1024;
-		return GAS_OK;
-	}();
-	if (rc != GAS_OK) {
-		conv_release(c);
-		return rc;
-	}
-	c->conv_count = convolvers;
-	c->conv_max_taps = max_ir_taps;
-	c->conv.assign(convolvers, gas_ctx::ConvInst{});
-	c->conv_free.reserve(convolvers);
-	for (uint32_t s = convolvers; s-- > 0;) {
-		c->conv_free.push_back(s);
-	}
-	return GAS_OK;
-}
-
-// The common end of gas_conv_ir_load and gas_conv_ir_from_room: d_ir [channels][taps] is on the device, in the context's
-// stream order.  Allocates the partition spectra, transforms, waits (the caller may free d_ir) and enters the IR in the
-// table at the lowest free id.  A failure leaves no IR.
-static int conv_ir_register(gas_ctx *c, const float *d_ir, uint32_t channels, uint32_t taps, uint32_t *out_ir) {
-	const uint32_t F = c->cfg.frames;
-	gas_ctx::ConvIr rec;
-	rec.channels = channels;
-	rec.taps = taps;
-	rec.k_ir = (taps + F - 1) / F;
-	GAS_HIP(c, c->mem.alloc(rec.H, (size_t)channels * rec.k_ir * GAS_CONV_BINS));
-	hipError_t e = gas_launch_conv_ir(c->stream, d_ir, channels, taps, F, c->d_tw, c->conv_pool.w1024, rec.H);
-	e = e != hipSuccess ? e : hipStreamSynchronize(c->stream);
-	if (e != hipSuccess) {
-		c->mem.drop(rec.H);
-		GAS_HIP(c, e);
-	}
-	uint32_t id = 0;
-	while (id < c->conv_irs.size() && c->conv_irs[id].H) {
-		id++;
-	}
-	if (id == c->conv_irs.size()) {
-		c->conv_irs.push_back(rec);
-	} else {
-		c->conv_irs[id] = rec;
-	}
-	*out_ir = id;
-	return GAS_OK;
-}
-
-int gas_conv_ir_load(gas_ctx *c, const float *ir, uint32_t channels, uint32_t taps, uint32_t *out_ir) {
-	if (!c || !ir || !out_ir || (channels != 1 && channels != 2 && channels != 4) || taps == 0) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (c->conv_count == 0) {
-		return GAS_ERR_UNSUPPORTED_CHAIN;
-	}
-	if (taps > c->conv_max_taps) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	const size_t floats = (size_t)channels * taps;
-	for (size_t i = 0; i < floats; i++) {
-		if (!std::isfinite(ir[i])) {
-			return GAS_ERR_INVALID_ARGUMENT;
-		}
-	}
-	GAS_TRY(flush_deferred(c));
-	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	Mem tmp; // frees d_ir on every way out
-	float *d_ir = nullptr;
-	GAS_HIP(c, tmp.alloc(d_ir, floats));
-	GAS_HIP(c, hipMemcpyAsync(d_ir, ir, floats * sizeof(float), hipMemcpyHostToDevice, c->stream));
-	return conv_ir_register(c, d_ir, channels, taps, out_ir);
-}
-
-// What gas_conv_ir_from_room and gas_conv_ir_from_room_hrtf refuse in a descriptor's plain fields; `ears`: ear_spacing too.
-static bool room_ir_desc_ok(const gas_room_ir &d, bool ears) {
-	const gas_room &R = d.room;
-	bool ok = R.speed_of_sound > 0.0f && std::isfinite(R.speed_of_sound) && R.level >= 0.0f && std::isfinite(R.level); // gas_calc_early_reflections' test but for max_order
-	for (int a = 0; a < 3; a++) {
-		ok = ok && R.half_extent[a] > 0.0f && std::isfinite(R.half_extent[a]);
-	}
-	for (int w = 0; w < 6; w++) {
-		ok = ok && R.reflectance[w] >= 0.0f && R.reflectance[w] <= 1.0f;
-	}
-	ok = ok && (d.max_order == 0 || d.min_order <= d.max_order);
-	ok = ok && (!ears || (d.ear_spacing >= 0.0f && std::isfinite(d.ear_spacing)));
-	for (int a = 0; a < 3; a++) {
-		ok = ok && std::isfinite(R.origin[a]) && std::isfinite(d.source[a]) && std::isfinite(d.listener.origin[a]);
-		for (int b = 0; b < 3; b++) {
-			ok = ok && std::isfinite(R.basis[a][b]) && std::isfinite(d.listener.basis[a][b]);
-		}
-	}
-	return ok;
-}
-
-// The HRIR set of gas_conv_ir_from_room_hrtf, as the caller passed it.
-struct RoomIrSet {
-	const float *hrir;
-	uint32_t n_az, n_el, taps;
-};
-
-// The common body of the two box-room calls once everything is validated and the plan is made: tables, temporaries,
-// the generator's launches inside the profile bracket, registration and read-back.  set == nullptr: k_room_ir with
-// `channels` receivers; otherwise k_room_ir_hrtf, two ears.
-static int conv_ir_from_plan(gas_ctx *c, const gas_room_ir &desc, const gas_room_ir_plan &plan, uint32_t channels, const RoomIrSet *set, float *out_taps, uint32_t *out_ir) {
-	const uint32_t taps = plan.taps;
-	std::vector<double> tables;
-	try {
-		tables.resize(gas_room_ir_table_doubles(plan));
-	} catch (const std::bad_alloc &) {
-		c->last_err = "gas_conv_ir_from_room: out of host memory for the reflectance tables";
-		return GAS_ERR_DEVICE;
-	}
-	gas_room_ir_fill_tables(desc, plan, tables.data());
-	if (out_ir) { // the pure generator leaves queued callbacks where they are: it touches nothing of theirs
-		GAS_TRY(flush_deferred(c));
-	}
-	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	const size_t n = (size_t)channels * taps;
-	Mem tmp; // frees the buffers on every way out
-	double *d_tables = nullptr;
-	long long *d_acc = nullptr;
-	float *d_ir = nullptr, *d_hrir = nullptr;
-	GAS_HIP(c, tmp.alloc(d_tables, tables.size()));
-	GAS_HIP(c, tmp.alloc(d_acc, n));
-	GAS_HIP(c, tmp.alloc(d_ir, n));
-	GAS_HIP(c, hipMemcpy(d_tables, tables.data(), tables.size() * sizeof(double), hipMemcpyHostToDevice)); // complete on return
-	if (set) {
-		const size_t floats = (size_t)set->n_az * set->n_el * 2 * set->taps;
-		GAS_HIP(c, tmp.alloc(d_hrir, floats));
-		GAS_HIP(c, hipMemcpy(d_hrir, set->hrir, floats * sizeof(float), hipMemcpyHostToDevice));
-	}
-	const bool timed = c->profiling && c->ev_used + 2 <= c->ev.size(); // gas_profile_enable: the generator's launches count as a dominant launch
-	if (timed) {
-		GAS_HIP(c, hipEventRecord(c->ev[c->ev_used], c->stream));
-	}
-	if (set) {
-		GAS_HIP(c, gas_launch_room_ir_hrtf(c->stream, plan, desc, d_tables, d_hrir, set->n_az, set->n_el, set->taps, d_acc, d_ir));
-	} else {
-		GAS_HIP(c, gas_launch_room_ir(c->stream, plan, d_tables, d_acc, d_ir));
-	}
-	if (timed) {
-		GAS_HIP(c, hipEventRecord(c->ev[c->ev_used + 1], c->stream));
-		c->ev_used += 2;
-	}
-	if (out_ir) { // waits for the stream
-		uint32_t id = 0;
-		GAS_TRY(conv_ir_register(c, d_ir, channels, taps, &id));
-		if (out_taps) {
-			const hipError_t e = hipMemcpy(out_taps, d_ir, n * sizeof(float), hipMemcpyDeviceToHost);
-			if (e != hipSuccess) { // no IR and nothing reported: the caller's out_ir keeps its value
-				c->mem.drop(c->conv_irs[id].H);
-				c->conv_irs[id] = gas_ctx::ConvIr{};
-				GAS_HIP(c, e);
-			}
-		}
-		*out_ir = id;
-		return GAS_OK;
-	}
-	GAS_HIP(c, hipStreamSynchronize(c->stream)); // before anything reaches out_taps: a failed kernel writes nothing there
-	GAS_HIP(c, hipMemcpy(out_taps, d_ir, n * sizeof(float), hipMemcpyDeviceToHost));
-	return GAS_OK;
-}
-
-int gas_conv_ir_from_room(gas_ctx *c, const gas_room_ir *desc, uint32_t channels, uint32_t taps, float *out_taps, uint32_t *out_ir) {
-	if (!c || !desc || (!out_taps && !out_ir) || (channels != 1 && channels != 2) || taps == 0) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (out_ir && c->conv_count == 0) {
-		return GAS_ERR_UNSUPPORTED_CHAIN;
-	}
-	if (taps > (out_ir ? c->conv_max_taps : (uint32_t)GAS_CONV_MAX_IR_TAPS)) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	gas_room_ir_plan plan;
-	if (!room_ir_desc_ok(*desc, true) || !gas_room_ir_make_plan(*desc, channels, taps, c->cfg.mix_rate, plan)) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	return conv_ir_from_plan(c, *desc, plan, channels, nullptr, out_taps, out_ir);
-}
-
-int gas_conv_ir_from_room_hrtf(gas_ctx *c, const gas_room_ir *desc, const float *hrir, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps, uint32_t taps, float *out_taps, uint32_t *out_ir) {
-	if (!c || !desc || !hrir || (!out_taps && !out_ir) || taps == 0) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (n_az == 0 || n_el == 0 || (uint64_t)n_az * n_el > 65536u || hrir_taps == 0 || hrir_taps > GAS_HRTF_TAPS) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (out_ir && c->conv_count == 0) {
-		return GAS_ERR_UNSUPPORTED_CHAIN;
-	}
-	if (taps > (out_ir ? c->conv_max_taps : (uint32_t)GAS_CONV_MAX_IR_TAPS)) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	gas_room_ir_plan plan;
-	if (!room_ir_desc_ok(*desc, false) || !gas_room_ir_make_plan(*desc, 1, taps, c->cfg.mix_rate, plan)) { // one receiver: ear_spacing is not read
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	const size_t floats = (size_t)n_az * n_el * 2 * hrir_taps;
-	for (size_t i = 0; i < floats; i++) {
-		if (!(std::fabs(hrir[i]) <= 4.0f)) { // not finite, or a tap could pass 4 v per image: the int64 sums' bound
-			return GAS_ERR_INVALID_ARGUMENT;
-		}
-	}
-	const RoomIrSet set{hrir, n_az, n_el, hrir_taps};
-	return conv_ir_from_plan(c, *desc, plan, 2, &set, out_taps, out_ir);
-}
-
-int gas_conv_ir_free(gas_ctx *c, uint32_t ir) {
-	if (!c) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (!conv_ir_live(c, ir)) {
-		return GAS_ERR_BAD_SLOT;
-	}
-	if (c->conv_irs[ir].users != 0) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	GAS_TRY(flush_deferred(c));
-	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	GAS_HIP(c, hipStreamSynchronize(c->stream)); // calls still queued may read the spectra
-	c->mem.drop(c->conv_irs[ir].H);
-	c->conv_irs[ir] = gas_ctx::ConvIr{};
-	return GAS_OK;
-}
-
-int gas_conv_ir_get_info(gas_ctx *c, uint32_t ir, uint32_t *out_channels, uint32_t *out_taps) {
-	if (!c) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (!conv_ir_live(c, ir)) {
-		return GAS_ERR_BAD_SLOT;
-	}
-	if (out_channels) {
-		*out_channels = c->conv_irs[ir].channels;
-	}
-	if (out_taps) {
-		*out_taps = c->conv_irs[ir].taps;
-	}
-	return GAS_OK;
-}
-
-int gas_conv_create(gas_ctx *c, uint32_t ir, uint32_t *out_conv) {
-	if (!c || !out_conv) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (c->conv_count == 0) {
-		return GAS_ERR_UNSUPPORTED_CHAIN;
-	}
-	if (!conv_ir_live(c, ir)) {
-		return GAS_ERR_BAD_SLOT;
-	}
-	if (c->conv_free.empty()) {
-		return GAS_ERR_OUT_OF_SLOTS;
-	}
-	const uint32_t id = c->conv_free.back();
-	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	GAS_HIP(c, conv_zero(c, id)); // zeroed when it changes hands
-	c->conv_free.pop_back();
-	gas_ctx::ConvInst &k = c->conv[id];
-	k = gas_ctx::ConvInst{};
-	k.used = true;
-	k.ir = ir;
-	k.pos = c->conv_pool.K - 1;
-	c->conv_irs[ir].users++;
-	*out_conv = id;
-	return GAS_OK;
-}
-
-int gas_conv_destroy(gas_ctx *c, uint32_t conv) {
-	if (!c) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (!conv_live(c, conv)) {
-		return GAS_ERR_BAD_SLOT;
-	}
-	conv_fade_end(c, c->conv[conv]); // releases every IR the instance names
-	c->conv_irs[c->conv[conv].ir].users--;
-	c->conv[conv].used = false;
-	c->conv_free.push_back(conv);
-	return GAS_OK;
-}
-
-int gas_conv_reset(gas_ctx *c, uint32_t conv) {
-	if (!c) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (!conv_live(c, conv)) {
-		return GAS_ERR_BAD_SLOT;
-	}
-	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	GAS_HIP(c, conv_zero(c, conv));
-	gas_ctx::ConvInst &k = c->conv[conv];
-	k.pos = c->conv_pool.K - 1;
-	if (k.fade_n) { // the fade ends in its final state: the pending target if there is one, else B
-		conv_fade_land(c, k);
-		if (k.pending_n) {
-			k.to = k.pending;
-			k.pending_n = 0;
-			conv_fade_land(c, k);
-		}
-	}
-	return GAS_OK;
-}
-
-int gas_conv_set_ir(gas_ctx *c, uint32_t conv, uint32_t ir) {
-	if (!c) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (!conv_live(c, conv) || !conv_ir_live(c, ir)) {
-		return GAS_ERR_BAD_SLOT;
-	}
-	conv_fade_end(c, c->conv[conv]);
-	c->conv_irs[c->conv[conv].ir].users--;
-	c->conv[conv].ir = ir;
-	c->conv_irs[ir].users++;
-	return GAS_OK;
-}
-
-int gas_conv_set_levels(gas_ctx *c, uint32_t conv, float dry, float wet) {
-	if (!c || !std::isfinite(dry) || !std::isfinite(wet)) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (!conv_live(c, conv)) {
-		return GAS_ERR_BAD_SLOT;
-	}
-	conv_fade_end(c, c->conv[conv]);
-	c->conv[conv].dry = dry;
-	c->conv[conv].wet = wet;
-	return GAS_OK;
-}
-
-int gas_conv_fade_to(gas_ctx *c, uint32_t conv, uint32_t ir, float dry, float wet, uint32_t fade_blocks) {
-	if (!c || !std::isfinite(dry) || !std::isfinite(wet) || fade_blocks > GAS_CONV_MAX_FADE_BLOCKS) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (!conv_live(c, conv) || !conv_ir_live(c, ir)) {
-		return GAS_ERR_BAD_SLOT;
-	}
-	if (fade_blocks == 0) { // nothing can refuse from here on
-		gas_conv_set_ir(c, conv, ir);
-		return gas_conv_set_levels(c, conv, dry, wet);
-	}
-	gas_ctx::ConvInst &k = c->conv[conv];
-	gas_ctx::ConvTarget t;
-	t.ir = ir;
-	t.dry = dry;
-	t.wet = wet;
-	c->conv_irs[ir].users++;
-	if (k.fade_n) { // waits for the fade in progress; the latest target wins
-		if (k.pending_n) {
-			c->conv_irs[k.pending.ir].users--;
-		}
-		k.pending = t;
-		k.pending_n = fade_blocks;
-	} else {
-		k.to = t;
-		k.fade_n = fade_blocks;
-		k.fade_pos = 0;
-	}
-	return GAS_OK;
-}
-
-int gas_conv_fade_remaining(gas_ctx *c, uint32_t conv, uint32_t *out_blocks) {
-	if (!c || !out_blocks) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (!conv_live(c, conv)) {
-		return GAS_ERR_BAD_SLOT;
-	}
-	const gas_ctx::ConvInst &k = c->conv[conv];
-	*out_blocks = k.fade_n - k.fade_pos + k.pending_n;
-	return GAS_OK;
-}
-
-int gas_conv_process(gas_ctx *c, const uint32_t *convs, uint32_t n, const gas_audio_frame *in, gas_audio_frame *out, uint32_t frames, int mem) {
-	if (!c || (mem != GAS_MEM_HOST && mem != GAS_MEM_DEVICE) || (n > 0 && (!convs || !in || !out))) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	const uint32_t F = c->cfg.frames;
-	// a refused host-memory call leaves zeros in `out` ([n][frames] as the caller sized it, as far as that is legal)
-	const size_t zero_bytes = out ? (size_t)(n < GAS_MAX_CONVOLVERS ? n : GAS_MAX_CONVOLVERS) * (frames < 512 ? frames : 512) * sizeof(gas_audio_frame) : 0;
-	const auto fail = [&](int code) { return zero_bytes ? fail_out(code, mem, out, zero_bytes) : code; };
-	if (n > GAS_MAX_CONVOLVERS) {
-		return fail(GAS_ERR_INVALID_ARGUMENT);
-	}
-	if (frames != F) {
-		return fail(GAS_ERR_FRAME_COUNT);
-	}
-	if (n == 0) {
-		return GAS_OK;
-	}
-	uint32_t seen = 0;
-	for (uint32_t i = 0; i < n; i++) {
-		if (!conv_live(c, convs[i])) {
-			return fail(GAS_ERR_BAD_SLOT);
-		}
-		if (seen & (1u << convs[i])) {
-			return fail(GAS_ERR_INVALID_ARGUMENT); // an instance named twice
-		}
-		seen |= 1u << convs[i];
-	}
-	if (mem == GAS_MEM_DEVICE && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) != 0) {
-		return fail(GAS_ERR_INVALID_ARGUMENT); // rows are read and written sixteen bytes at a time
-	}
-	{ // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first (`in` may be one's out)
-		const int rcd = flush_deferred(c);
-		if (rcd != GAS_OK) {
-			return fail(rcd);
-		}
-	}
-	if (hipSetDevice(c->cfg.device) != hipSuccess) {
-		return fail(GAS_ERR_NO_DEVICE);
-	}
-	if (mem == GAS_MEM_DEVICE) {
-		const int rcj = join_outputs(c); // GAS_FLAG_PIPELINED_MIX: `in` may be an earlier callback's out, still a pending sum
-		if (rcj != GAS_OK) {
-			return rcj;
-		}
-	}
-	const uint32_t K = c->conv_pool.K;
-	gas_conv_call call{};
-	for (uint32_t i = 0; i < n; i++) {
-		const gas_ctx::ConvInst &k = c->conv[convs[i]];
-		const gas_ctx::ConvIr &ir = c->conv_irs[k.ir];
-		gas_conv_entry &e = call.e[i];
-		e.H = ir.H;
-		e.slot = convs[i];
-		e.pos = k.pos + 1 == K ? 0 : k.pos + 1;
-		e.k_ir = ir.k_ir;
-		e.mode = gas_conv_mode(ir.channels);
-		e.dry = k.dry;
-		e.wet = k.wet;
-		if (k.fade_n) { // call fade_pos of fade_n: frame i has s = (float)(fade_pos F + i) * (1.0f / (float)(fade_n F))
-			const gas_ctx::ConvIr &irb = c->conv_irs[k.to.ir];
-			e.HB = k.to.ir == k.ir ? nullptr : irb.H; // a level-only fade: the wet sum is computed once
-			e.k_irB = irb.k_ir;
-			e.modeB = gas_conv_mode(irb.channels);
-			e.dryB = k.to.dry;
-			e.wetB = k.to.wet;
-			e.fade_t0 = k.fade_pos * F;
-			e.fade_inv = 1.0f / (float)(k.fade_n * F);
-		}
-	}
-	const size_t bytes = (size_t)n * F * sizeof(gas_audio_frame);
-	const int rc = [&]() -> int {
-		if (mem == GAS_MEM_DEVICE) {
-			GAS_HIP(c, gas_launch_conv(c->stream, call, n, c->conv_pool, c->d_tw, in, out, F));
-			return GAS_OK;
-		}
-		// host memory: the previous host-memory call returned after its copies, so the staging is free
-		std::memcpy(c->conv_h_in, in, bytes);
-		GAS_HIP(c, hipMemcpyAsync(c->conv_d_in, c->conv_h_in, bytes, hipMemcpyHostToDevice, c->stream));
-		GAS_HIP(c, gas_launch_conv(c->stream, call, n, c->conv_pool, c->d_tw, c->conv_d_in, c->conv_d_out, F));
-		GAS_HIP(c, hipMemcpyAsync(c->conv_h_out, c->conv_d_out, bytes, hipMemcpyDeviceToHost, c->stream));
-		GAS_HIP(c, hipStreamSynchronize(c->stream));
-		std::memcpy(out, c->conv_h_out, bytes);
-		return GAS_OK;
-	}();
-	if (rc != GAS_OK) {
-		return fail(rc);
-	}
-	for (uint32_t i = 0; i < n; i++) {
-		gas_ctx::ConvInst &k = c->conv[convs[i]];
-		k.pos = call.e[i].pos; // only the named instances' time advances, and only their fades
-		if (k.fade_n && ++k.fade_pos == k.fade_n) { // that was the fade's last call: state B, A's IR may be freed
-			conv_fade_land(c, k);
-			if (k.pending_n) { // the pending fade starts at the next call, from B
-				k.to = k.pending;
-				k.fade_n = k.pending_n;
-				k.pending_n = 0;
-			}
-		}
-	}
-	return GAS_OK;
 }
 
 } // extern "C"

@@ -1,0 +1,577 @@
+// gas_ctx_conv.hip -- the bus convolvers of include/gas_amd.h (gas_ctx_reserve_conv, gas_conv_*; k_conv.hip) and the
+// impulse responses built on the device from box rooms (gas_conv_ir_from_room*; k_room_ir.hip).
+#include "gas_ctx_priv.h"
+
+extern "C" {
+
+#define GAS_CONV_MAX_IR_TAPS (1u << 20)
+
+static void conv_release(gas_ctx *c) {
+	c->mem.drop(c->conv.pool.ring);
+	c->mem.drop(c->conv.pool.prev);
+	c->mem.drop(c->conv.pool.ypart);
+	c->mem.drop(c->conv.w1024);
+	c->mem.drop(c->conv.h_in);
+	c->mem.drop(c->conv.h_out);
+	c->mem.drop(c->conv.d_in);
+	c->mem.drop(c->conv.d_out);
+	c->conv.pool = gas_conv_pool{};
+	c->conv.count = 0;
+	c->conv.max_taps = 0;
+	c->conv.inst.clear();
+	c->conv.free.clear();
+	c->conv.irs.clear();
+}
+
+// The instance's ring and previous block become zeros in stream order: x[t] = 0 for every earlier t.
+static hipError_t conv_zero(gas_ctx *c, uint32_t conv) {
+	const size_t ring = (size_t)2 * c->conv.pool.K * GAS_CONV_BINS;
+	const hipError_t e = hipMemsetAsync(c->conv.pool.ring + conv * ring, 0, ring * sizeof(float2), c->stream);
+	return e != hipSuccess ? e : hipMemsetAsync(c->conv.pool.prev + (size_t)conv * 2 * 512, 0, 2 * 512 * sizeof(float), c->stream);
+}
+
+static bool conv_live(const gas_ctx *c, uint32_t conv) {
+	return conv < c->conv.count && c->conv.inst[conv].used;
+}
+
+static bool conv_ir_live(const gas_ctx *c, uint32_t ir) {
+	return ir < c->conv.irs.size() && c->conv.irs[ir].H != nullptr;
+}
+
+// The fade in progress ends in state B: A's IR is no longer named, B's reference becomes the state's.
+static void conv_fade_land(gas_ctx *c, ConvInst &k) {
+	c->conv.irs[k.ir].users--;
+	k.ir = k.to.ir;
+	k.dry = k.to.dry;
+	k.wet = k.to.wet;
+	k.fade_n = k.fade_pos = 0;
+}
+
+// gas_conv_set_ir, gas_conv_set_levels: a fade in progress ends at once in state B and a pending target is dropped.
+static void conv_fade_end(gas_ctx *c, ConvInst &k) {
+	if (k.fade_n) {
+		conv_fade_land(c, k);
+	}
+	if (k.pending_n) {
+		c->conv.irs[k.pending.ir].users--;
+		k.pending_n = 0;
+	}
+}
+
+int gas_ctx_reserve_conv(gas_ctx *c, uint32_t convolvers, uint32_t max_ir_taps) {
+	if (!c || convolvers > GAS_MAX_CONVOLVERS || max_ir_taps > GAS_CONV_MAX_IR_TAPS || (convolvers == 0) != (max_ir_taps == 0)) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	for (const auto &k : c->conv.inst) {
+		if (k.used) {
+			return GAS_ERR_INVALID_ARGUMENT;
+		}
+	}
+	for (const auto &ir : c->conv.irs) {
+		if (ir.H) {
+			return GAS_ERR_INVALID_ARGUMENT;
+		}
+	}
+	GAS_TRY(flush_deferred(c));
+	GAS_HIP(c, hipSetDevice(c->cfg.device));
+	GAS_HIP(c, hipStreamSynchronize(c->stream));
+	conv_release(c);
+	if (convolvers == 0) {
+		return GAS_OK;
+	}
+	const uint32_t F = c->cfg.frames;
+	const uint32_t K = (max_ir_taps + F - 1) / F;
+	const int rc = [&]() -> int {
+		gas_conv_pool &p = c->conv.pool;
+		p.K = K;
+		p.max_chunks = gas_conv_max_chunks(K);
+		GAS_HIP(c, c->mem.alloc(p.ring, (size_t)convolvers * 2 * K * GAS_CONV_BINS));
+		GAS_HIP(c, c->mem.alloc(p.prev, (size_t)convolvers * 2 * 512));
+		// two rows (ears) per named instance and two more per fading one: 96 rows of max_chunks spectra of 4 KiB,
+		// 393 216 max_chunks bytes
+		GAS_HIP(c, c->mem.alloc(p.ypart, (size_t)GAS_MAX_CONVOLVERS * 4 * p.max_chunks * GAS_CONV_BINS));
+		GAS_HIP(c, c->mem.alloc(c->conv.w1024, 512));
+		const size_t stage = (size_t)GAS_MAX_CONVOLVERS * F;
+		GAS_HIP(c, c->mem.alloc(c->conv.h_in, stage, Mem::PINNED));
+		GAS_HIP(c, c->mem.alloc(c->conv.h_out, stage, Mem::PINNED));
+		GAS_HIP(c, c->mem.alloc(c->conv.d_in, stage));
+		GAS_HIP(c, c->mem.alloc(c->conv.d_out, stage));
+		float2 w[512];
+		gas_make_w1024(w);
+		GAS_HIP(c, hipMemcpyAsync(c->conv.w1024, w, sizeof(w), hipMemcpyHostToDevice, c->stream));
+		GAS_HIP(c, hipStreamSynchronize(c->stream));
+		p.w1024 = c->conv.w1024;
+		return GAS_OK;
+	}();
+	if (rc != GAS_OK) {
+		conv_release(c);
+		return rc;
+	}
+	c->conv.count = convolvers;
+	c->conv.max_taps = max_ir_taps;
+	c->conv.inst.assign(convolvers, ConvInst{});
+	c->conv.free.reserve(convolvers);
+	for (uint32_t s = convolvers; s-- > 0;) {
+		c->conv.free.push_back(s);
+	}
+	return GAS_OK;
+}
+
+// The common end of gas_conv_ir_load and gas_conv_ir_from_room: d_ir [channels][taps] is on the device, in the context's
+// stream order.  Allocates the partition spectra, transforms, waits (the caller may free d_ir) and enters the IR in the
+// table at the lowest free id.  A failure leaves no IR.
+static int conv_ir_register(gas_ctx *c, const float *d_ir, uint32_t channels, uint32_t taps, uint32_t *out_ir) {
+	const uint32_t F = c->cfg.frames;
+	ConvIr rec;
+	rec.channels = channels;
+	rec.taps = taps;
+	rec.k_ir = (taps + F - 1) / F;
+	GAS_HIP(c, c->mem.alloc(rec.H, (size_t)channels * rec.k_ir * GAS_CONV_BINS));
+	hipError_t e = gas_launch_conv_ir(c->stream, d_ir, channels, taps, F, c->d_tw, c->conv.pool.w1024, rec.H);
+	e = e != hipSuccess ? e : hipStreamSynchronize(c->stream);
+	if (e != hipSuccess) {
+		c->mem.drop(rec.H);
+		GAS_HIP(c, e);
+	}
+	uint32_t id = 0;
+	while (id < c->conv.irs.size() && c->conv.irs[id].H) {
+		id++;
+	}
+	if (id == c->conv.irs.size()) {
+		c->conv.irs.push_back(rec);
+	} else {
+		c->conv.irs[id] = rec;
+	}
+	*out_ir = id;
+	return GAS_OK;
+}
+
+int gas_conv_ir_load(gas_ctx *c, const float *ir, uint32_t channels, uint32_t taps, uint32_t *out_ir) {
+	if (!c || !ir || !out_ir || (channels != 1 && channels != 2 && channels != 4) || taps == 0) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (c->conv.count == 0) {
+		return GAS_ERR_UNSUPPORTED_CHAIN;
+	}
+	if (taps > c->conv.max_taps) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	const size_t floats = (size_t)channels * taps;
+	for (size_t i = 0; i < floats; i++) {
+		if (!std::isfinite(ir[i])) {
+			return GAS_ERR_INVALID_ARGUMENT;
+		}
+	}
+	GAS_TRY(flush_deferred(c));
+	GAS_HIP(c, hipSetDevice(c->cfg.device));
+	Mem tmp; // frees d_ir on every way out
+	float *d_ir = nullptr;
+	GAS_HIP(c, tmp.alloc(d_ir, floats));
+	GAS_HIP(c, hipMemcpyAsync(d_ir, ir, floats * sizeof(float), hipMemcpyHostToDevice, c->stream));
+	return conv_ir_register(c, d_ir, channels, taps, out_ir);
+}
+
+int gas_conv_ir_free(gas_ctx *c, uint32_t ir) {
+	if (!c) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (!conv_ir_live(c, ir)) {
+		return GAS_ERR_BAD_SLOT;
+	}
+	if (c->conv.irs[ir].users != 0) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	GAS_TRY(flush_deferred(c));
+	GAS_HIP(c, hipSetDevice(c->cfg.device));
+	GAS_HIP(c, hipStreamSynchronize(c->stream)); // calls still queued may read the spectra
+	c->mem.drop(c->conv.irs[ir].H);
+	c->conv.irs[ir] = ConvIr{};
+	return GAS_OK;
+}
+
+int gas_conv_ir_get_info(gas_ctx *c, uint32_t ir, uint32_t *out_channels, uint32_t *out_taps) {
+	if (!c) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (!conv_ir_live(c, ir)) {
+		return GAS_ERR_BAD_SLOT;
+	}
+	if (out_channels) {
+		*out_channels = c->conv.irs[ir].channels;
+	}
+	if (out_taps) {
+		*out_taps = c->conv.irs[ir].taps;
+	}
+	return GAS_OK;
+}
+
+int gas_conv_create(gas_ctx *c, uint32_t ir, uint32_t *out_conv) {
+	if (!c || !out_conv) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (c->conv.count == 0) {
+		return GAS_ERR_UNSUPPORTED_CHAIN;
+	}
+	if (!conv_ir_live(c, ir)) {
+		return GAS_ERR_BAD_SLOT;
+	}
+	if (c->conv.free.empty()) {
+		return GAS_ERR_OUT_OF_SLOTS;
+	}
+	const uint32_t id = c->conv.free.back();
+	GAS_HIP(c, hipSetDevice(c->cfg.device));
+	GAS_HIP(c, conv_zero(c, id)); // zeroed when it changes hands
+	c->conv.free.pop_back();
+	ConvInst &k = c->conv.inst[id];
+	k = ConvInst{};
+	k.used = true;
+	k.ir = ir;
+	k.pos = c->conv.pool.K - 1;
+	c->conv.irs[ir].users++;
+	*out_conv = id;
+	return GAS_OK;
+}
+
+int gas_conv_destroy(gas_ctx *c, uint32_t conv) {
+	if (!c) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (!conv_live(c, conv)) {
+		return GAS_ERR_BAD_SLOT;
+	}
+	conv_fade_end(c, c->conv.inst[conv]); // releases every IR the instance names
+	c->conv.irs[c->conv.inst[conv].ir].users--;
+	c->conv.inst[conv].used = false;
+	c->conv.free.push_back(conv);
+	return GAS_OK;
+}
+
+int gas_conv_reset(gas_ctx *c, uint32_t conv) {
+	if (!c) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (!conv_live(c, conv)) {
+		return GAS_ERR_BAD_SLOT;
+	}
+	GAS_HIP(c, hipSetDevice(c->cfg.device));
+	GAS_HIP(c, conv_zero(c, conv));
+	ConvInst &k = c->conv.inst[conv];
+	k.pos = c->conv.pool.K - 1;
+	if (k.fade_n) { // the fade ends in its final state: the pending target if there is one, else B
+		conv_fade_land(c, k);
+		if (k.pending_n) {
+			k.to = k.pending;
+			k.pending_n = 0;
+			conv_fade_land(c, k);
+		}
+	}
+	return GAS_OK;
+}
+
+int gas_conv_set_ir(gas_ctx *c, uint32_t conv, uint32_t ir) {
+	if (!c) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (!conv_live(c, conv) || !conv_ir_live(c, ir)) {
+		return GAS_ERR_BAD_SLOT;
+	}
+	conv_fade_end(c, c->conv.inst[conv]);
+	c->conv.irs[c->conv.inst[conv].ir].users--;
+	c->conv.inst[conv].ir = ir;
+	c->conv.irs[ir].users++;
+	return GAS_OK;
+}
+
+int gas_conv_set_levels(gas_ctx *c, uint32_t conv, float dry, float wet) {
+	if (!c || !std::isfinite(dry) || !std::isfinite(wet)) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (!conv_live(c, conv)) {
+		return GAS_ERR_BAD_SLOT;
+	}
+	conv_fade_end(c, c->conv.inst[conv]);
+	c->conv.inst[conv].dry = dry;
+	c->conv.inst[conv].wet = wet;
+	return GAS_OK;
+}
+
+int gas_conv_fade_to(gas_ctx *c, uint32_t conv, uint32_t ir, float dry, float wet, uint32_t fade_blocks) {
+	if (!c || !std::isfinite(dry) || !std::isfinite(wet) || fade_blocks > GAS_CONV_MAX_FADE_BLOCKS) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (!conv_live(c, conv) || !conv_ir_live(c, ir)) {
+		return GAS_ERR_BAD_SLOT;
+	}
+	if (fade_blocks == 0) { // nothing can refuse from here on
+		gas_conv_set_ir(c, conv, ir);
+		return gas_conv_set_levels(c, conv, dry, wet);
+	}
+	ConvInst &k = c->conv.inst[conv];
+	ConvTarget t;
+	t.ir = ir;
+	t.dry = dry;
+	t.wet = wet;
+	c->conv.irs[ir].users++;
+	if (k.fade_n) { // waits for the fade in progress; the latest target wins
+		if (k.pending_n) {
+			c->conv.irs[k.pending.ir].users--;
+		}
+		k.pending = t;
+		k.pending_n = fade_blocks;
+	} else {
+		k.to = t;
+		k.fade_n = fade_blocks;
+		k.fade_pos = 0;
+	}
+	return GAS_OK;
+}
+
+int gas_conv_fade_remaining(gas_ctx *c, uint32_t conv, uint32_t *out_blocks) {
+	if (!c || !out_blocks) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (!conv_live(c, conv)) {
+		return GAS_ERR_BAD_SLOT;
+	}
+	const ConvInst &k = c->conv.inst[conv];
+	*out_blocks = k.fade_n - k.fade_pos + k.pending_n;
+	return GAS_OK;
+}
+
+int gas_conv_process(gas_ctx *c, const uint32_t *convs, uint32_t n, const gas_audio_frame *in, gas_audio_frame *out, uint32_t frames, int mem) {
+	if (!c || (mem != GAS_MEM_HOST && mem != GAS_MEM_DEVICE) || (n > 0 && (!convs || !in || !out))) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	const uint32_t F = c->cfg.frames;
+	// a refused host-memory call leaves zeros in `out` ([n][frames] as the caller sized it, as far as that is legal)
+	const size_t zero_bytes = out ? (size_t)(n < GAS_MAX_CONVOLVERS ? n : GAS_MAX_CONVOLVERS) * (frames < 512 ? frames : 512) * sizeof(gas_audio_frame) : 0;
+	const auto fail = [&](int code) { return zero_bytes ? fail_out(code, mem, out, zero_bytes) : code; };
+	if (n > GAS_MAX_CONVOLVERS) {
+		return fail(GAS_ERR_INVALID_ARGUMENT);
+	}
+	if (frames != F) {
+		return fail(GAS_ERR_FRAME_COUNT);
+	}
+	if (n == 0) {
+		return GAS_OK;
+	}
+	uint32_t seen = 0;
+	for (uint32_t i = 0; i < n; i++) {
+		if (!conv_live(c, convs[i])) {
+			return fail(GAS_ERR_BAD_SLOT);
+		}
+		if (seen & (1u << convs[i])) {
+			return fail(GAS_ERR_INVALID_ARGUMENT); // an instance named twice
+		}
+		seen |= 1u << convs[i];
+	}
+	if (mem == GAS_MEM_DEVICE && ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) != 0) {
+		return fail(GAS_ERR_INVALID_ARGUMENT); // rows are read and written sixteen bytes at a time
+	}
+	{ // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first (`in` may be one's out)
+		const int rcd = flush_deferred(c);
+		if (rcd != GAS_OK) {
+			return fail(rcd);
+		}
+	}
+	if (hipSetDevice(c->cfg.device) != hipSuccess) {
+		return fail(GAS_ERR_NO_DEVICE);
+	}
+	if (mem == GAS_MEM_DEVICE) {
+		const int rcj = join_outputs(c); // GAS_FLAG_PIPELINED_MIX: `in` may be an earlier callback's out, still a pending sum
+		if (rcj != GAS_OK) {
+			return rcj;
+		}
+	}
+	const uint32_t K = c->conv.pool.K;
+	gas_conv_call call{};
+	for (uint32_t i = 0; i < n; i++) {
+		const ConvInst &k = c->conv.inst[convs[i]];
+		const ConvIr &ir = c->conv.irs[k.ir];
+		gas_conv_entry &e = call.e[i];
+		e.H = ir.H;
+		e.slot = convs[i];
+		e.pos = k.pos + 1 == K ? 0 : k.pos + 1;
+		e.k_ir = ir.k_ir;
+		e.mode = gas_conv_mode(ir.channels);
+		e.dry = k.dry;
+		e.wet = k.wet;
+		if (k.fade_n) { // call fade_pos of fade_n: frame i has s = (float)(fade_pos F + i) * (1.0f / (float)(fade_n F))
+			const ConvIr &irb = c->conv.irs[k.to.ir];
+			e.HB = k.to.ir == k.ir ? nullptr : irb.H; // a level-only fade: the wet sum is computed once
+			e.k_irB = irb.k_ir;
+			e.modeB = gas_conv_mode(irb.channels);
+			e.dryB = k.to.dry;
+			e.wetB = k.to.wet;
+			e.fade_t0 = k.fade_pos * F;
+			e.fade_inv = 1.0f / (float)(k.fade_n * F);
+		}
+	}
+	const size_t bytes = (size_t)n * F * sizeof(gas_audio_frame);
+	const int rc = [&]() -> int {
+		if (mem == GAS_MEM_DEVICE) {
+			GAS_HIP(c, gas_launch_conv(c->stream, call, n, c->conv.pool, c->d_tw, in, out, F));
+			return GAS_OK;
+		}
+		// host memory: the previous host-memory call returned after its copies, so the staging is free
+		std::memcpy(c->conv.h_in, in, bytes);
+		GAS_HIP(c, hipMemcpyAsync(c->conv.d_in, c->conv.h_in, bytes, hipMemcpyHostToDevice, c->stream));
+		GAS_HIP(c, gas_launch_conv(c->stream, call, n, c->conv.pool, c->d_tw, c->conv.d_in, c->conv.d_out, F));
+		GAS_HIP(c, hipMemcpyAsync(c->conv.h_out, c->conv.d_out, bytes, hipMemcpyDeviceToHost, c->stream));
+		GAS_HIP(c, hipStreamSynchronize(c->stream));
+		std::memcpy(out, c->conv.h_out, bytes);
+		return GAS_OK;
+	}();
+	if (rc != GAS_OK) {
+		return fail(rc);
+	}
+	for (uint32_t i = 0; i < n; i++) {
+		ConvInst &k = c->conv.inst[convs[i]];
+		k.pos = call.e[i].pos; // only the named instances' time advances, and only their fades
+		if (k.fade_n && ++k.fade_pos == k.fade_n) { // that was the fade's last call: state B, A's IR may be freed
+			conv_fade_land(c, k);
+			if (k.pending_n) { // the pending fade starts at the next call, from B
+				k.to = k.pending;
+				k.fade_n = k.pending_n;
+				k.pending_n = 0;
+			}
+		}
+	}
+	return GAS_OK;
+}
+
+// What gas_conv_ir_from_room and gas_conv_ir_from_room_hrtf refuse in a descriptor's plain fields; `ears`: ear_spacing too.
+static bool room_ir_desc_ok(const gas_room_ir &d, bool ears) {
+	const gas_room &R = d.room;
+	bool ok = R.speed_of_sound > 0.0f && std::isfinite(R.speed_of_sound) && R.level >= 0.0f && std::isfinite(R.level); // gas_calc_early_reflections' test but for max_order
+	for (int a = 0; a < 3; a++) {
+		ok = ok && R.half_extent[a] > 0.0f && std::isfinite(R.half_extent[a]);
+	}
+	for (int w = 0; w < 6; w++) {
+		ok = ok && R.reflectance[w] >= 0.0f && R.reflectance[w] <= 1.0f;
+	}
+	ok = ok && (d.max_order == 0 || d.min_order <= d.max_order);
+	ok = ok && (!ears || (d.ear_spacing >= 0.0f && std::isfinite(d.ear_spacing)));
+	for (int a = 0; a < 3; a++) {
+		ok = ok && std::isfinite(R.origin[a]) && std::isfinite(d.source[a]) && std::isfinite(d.listener.origin[a]);
+		for (int b = 0; b < 3; b++) {
+			ok = ok && std::isfinite(R.basis[a][b]) && std::isfinite(d.listener.basis[a][b]);
+		}
+	}
+	return ok;
+}
+
+// The HRIR set of gas_conv_ir_from_room_hrtf, as the caller passed it.
+struct RoomIrSet {
+	const float *hrir;
+	uint32_t n_az, n_el, taps;
+};
+
+// The common body of the two box-room calls once everything is validated and the plan is made: tables, temporaries,
+// the generator's launches inside the profile bracket, registration and read-back.  set == nullptr: k_room_ir with
+// `channels` receivers; otherwise k_room_ir_hrtf, two ears.
+static int conv_ir_from_plan(gas_ctx *c, const gas_room_ir &desc, const gas_room_ir_plan &plan, uint32_t channels, const RoomIrSet *set, float *out_taps, uint32_t *out_ir) {
+	const uint32_t taps = plan.taps;
+	std::vector<double> tables;
+	try {
+		tables.resize(gas_room_ir_table_doubles(plan));
+	} catch (const std::bad_alloc &) {
+		c->last_err = "gas_conv_ir_from_room: out of host memory for the reflectance tables";
+		return GAS_ERR_DEVICE;
+	}
+	gas_room_ir_fill_tables(desc, plan, tables.data());
+	if (out_ir) { // the pure generator leaves queued callbacks where they are: it touches nothing of theirs
+		GAS_TRY(flush_deferred(c));
+	}
+	GAS_HIP(c, hipSetDevice(c->cfg.device));
+	const size_t n = (size_t)channels * taps;
+	Mem tmp; // frees the buffers on every way out
+	double *d_tables = nullptr;
+	long long *d_acc = nullptr;
+	float *d_ir = nullptr, *d_hrir = nullptr;
+	GAS_HIP(c, tmp.alloc(d_tables, tables.size()));
+	GAS_HIP(c, tmp.alloc(d_acc, n));
+	GAS_HIP(c, tmp.alloc(d_ir, n));
+	GAS_HIP(c, hipMemcpy(d_tables, tables.data(), tables.size() * sizeof(double), hipMemcpyHostToDevice)); // complete on return
+	if (set) {
+		const size_t floats = (size_t)set->n_az * set->n_el * 2 * set->taps;
+		GAS_HIP(c, tmp.alloc(d_hrir, floats));
+		GAS_HIP(c, hipMemcpy(d_hrir, set->hrir, floats * sizeof(float), hipMemcpyHostToDevice));
+	}
+	const bool timed = c->profiling && c->ev_used + 2 <= c->ev.size(); // gas_profile_enable: the generator's launches count as a dominant launch
+	if (timed) {
+		GAS_HIP(c, hipEventRecord(c->ev[c->ev_used], c->stream));
+	}
+	if (set) {
+		GAS_HIP(c, gas_launch_room_ir_hrtf(c->stream, plan, desc, d_tables, d_hrir, set->n_az, set->n_el, set->taps, d_acc, d_ir));
+	} else {
+		GAS_HIP(c, gas_launch_room_ir(c->stream, plan, d_tables, d_acc, d_ir));
+	}
+	if (timed) {
+		GAS_HIP(c, hipEventRecord(c->ev[c->ev_used + 1], c->stream));
+		c->ev_used += 2;
+	}
+	if (out_ir) { // waits for the stream
+		uint32_t id = 0;
+		GAS_TRY(conv_ir_register(c, d_ir, channels, taps, &id));
+		if (out_taps) {
+			const hipError_t e = hipMemcpy(out_taps, d_ir, n * sizeof(float), hipMemcpyDeviceToHost);
+			if (e != hipSuccess) { // no IR and nothing reported: the caller's out_ir keeps its value
+				c->mem.drop(c->conv.irs[id].H);
+				c->conv.irs[id] = ConvIr{};
+				GAS_HIP(c, e);
+			}
+		}
+		*out_ir = id;
+		return GAS_OK;
+	}
+	GAS_HIP(c, hipStreamSynchronize(c->stream)); // before anything reaches out_taps: a failed kernel writes nothing there
+	GAS_HIP(c, hipMemcpy(out_taps, d_ir, n * sizeof(float), hipMemcpyDeviceToHost));
+	return GAS_OK;
+}
+
+int gas_conv_ir_from_room(gas_ctx *c, const gas_room_ir *desc, uint32_t channels, uint32_t taps, float *out_taps, uint32_t *out_ir) {
+	if (!c || !desc || (!out_taps && !out_ir) || (channels != 1 && channels != 2) || taps == 0) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (out_ir && c->conv.count == 0) {
+		return GAS_ERR_UNSUPPORTED_CHAIN;
+	}
+	if (taps > (out_ir ? c->conv.max_taps : (uint32_t)GAS_CONV_MAX_IR_TAPS)) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	gas_room_ir_plan plan;
+	if (!room_ir_desc_ok(*desc, true) || !gas_room_ir_make_plan(*desc, channels, taps, c->cfg.mix_rate, plan)) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	return conv_ir_from_plan(c, *desc, plan, channels, nullptr, out_taps, out_ir);
+}
+
+int gas_conv_ir_from_room_hrtf(gas_ctx *c, const gas_room_ir *desc, const float *hrir, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps, uint32_t taps, float *out_taps, uint32_t *out_ir) {
+	if (!c || !desc || !hrir || (!out_taps && !out_ir) || taps == 0) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (n_az == 0 || n_el == 0 || (uint64_t)n_az * n_el > 65536u || hrir_taps == 0 || hrir_taps > GAS_HRTF_TAPS) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (out_ir && c->conv.count == 0) {
+		return GAS_ERR_UNSUPPORTED_CHAIN;
+	}
+	if (taps > (out_ir ? c->conv.max_taps : (uint32_t)GAS_CONV_MAX_IR_TAPS)) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	gas_room_ir_plan plan;
+	if (!room_ir_desc_ok(*desc, false) || !gas_room_ir_make_plan(*desc, 1, taps, c->cfg.mix_rate, plan)) { // one receiver: ear_spacing is not read
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	const size_t floats = (size_t)n_az * n_el * 2 * hrir_taps;
+	for (size_t i = 0; i < floats; i++) {
+		if (!(std::fabs(hrir[i]) <= 4.0f)) { // not finite, or a tap could pass 4 v per image: the int64 sums' bound
+			return GAS_ERR_INVALID_ARGUMENT;
+		}
+	}
+	const RoomIrSet set{hrir, n_az, n_el, hrir_taps};
+	return conv_ir_from_plan(c, *desc, plan, 2, &set, out_taps, out_ir);
+}
+
+} // extern "C"

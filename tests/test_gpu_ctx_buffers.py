@@ -1,5 +1,5 @@
 """One context whose buffers are allocated, grown, dropped and re-allocated while it runs (csrc/gas_owned.h behind
-gas_ctx.hip), at the smallest shapes that cross the sites twice, all through host-memory calls:
+gas_ctx.hip and gas_ctx_*.hip), at the smallest shapes that cross the sites twice, all through host-memory calls:
 
   - an effect family reserved, released with a count of 0 and reserved larger, one callback of an [EQ6] chain against
     fx_eq_ref after each reservation (pool, settings, slot -> entry table and staging buffer dropped and re-made);

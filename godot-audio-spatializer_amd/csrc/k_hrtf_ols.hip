@@ -232,7 +232,7 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 	uint32_t bl_d[3] = { 0, 0, 0 };
 	float bl_w0 = 1.0f, bl_w[3] = { 0.0f, 0.0f, 0.0f };
 	bool fade_changed = false; // FADE: this lane's source has an old row and it differs from the new one
-	const bool have = first + lane < last; // <= 64 sources per wave (gas_hrtf_plan): one lane per source of this wave
+	const bool have = first + lane < last; // <= 64 sources per wave (gas_hrtf_plan's `need`, per group): one lane per source of this wave; all 64 lanes: tests/test_gpu_hrtf_large_callbacks.py
 	if (have) {
 		const uint32_t e = g.order ? g.order[first + lane] : first + lane; // direction order (k_dir_order) or entry order
 		lm.slot = g.slots ? g.slots[e] : g.slot_base + e;

@@ -149,7 +149,7 @@ __global__ __launch_bounds__(UW * 64, UW > 8 ? 3 : GAS_HRTF_WAVES_PER_SIMD) void
 	}
 	uint32_t first, last;
 	wave_range(g.n, blockIdx.x * UW + wave, gridDim.x * UW, first, last);
-	const bool have = first + lane < last; // <= 64 sources per wave (gas_hrtf_plan): one metadata lane per source
+	const bool have = first + lane < last; // <= 64 sources per wave (gas_hrtf_uni_partials, below): one metadata lane per source; all 64 lanes: tests/test_gpu_hrtf_large_callbacks.py
 	LaneMeta lm{};
 	uint32_t my_entry = first + lane; // list entry this lane's source is (g.order: XCD-affine processing order, k_xcd_order)
 	if (have) {

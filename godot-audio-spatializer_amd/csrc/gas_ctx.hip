@@ -813,9 +813,9 @@ int run_groups(gas_ctx *c, const RunArgs &a) {
 		ga.slot_base = 0;
 		ga.n = gr.count;
 		ga.peaks = a.peaks;
-		const bool timed = c->profiling && gt == dom && c->ev_used + 2 <= c->ev.size() && (c->prof_tick++ % c->prof_every) == 0;
+		const bool timed = gt == dom && c->prof.room() && c->prof.due();
 		if (timed) {
-			GAS_HIP(c, hipEventRecord(c->ev[c->ev_used], c->stream));
+			GAS_HIP(c, c->prof.begin(c->stream));
 		}
 		uint64_t carried = 0; // bytes of the previous callback's partial mixes summed inside this launch (GAS_FLAG_PIPELINED_MIX)
 		switch (gt) {
@@ -853,18 +853,17 @@ int run_groups(gas_ctx *c, const RunArgs &a) {
 				break;
 		}
 		if (timed) {
-			GAS_HIP(c, hipEventRecord(c->ev[c->ev_used + 1], c->stream));
-			c->ev_used += 2;
-			c->prof_bytes = group_bytes(c, gt, gr.count) + carried;
-			c->prof_k = 1;
+			GAS_HIP(c, c->prof.end(c->stream));
+			c->prof.bytes = group_bytes(c, gt, gr.count) + carried;
+			c->prof.k = 1;
 			if ((gt == G_FX_HRTF || gt == G_FX_ER_HRTF) && groups[gt + 1].count > 0) {
 				// the exact-peak sources ride in the same launch: add their per-source bytes (table/mix terms counted once)
-				c->prof_bytes += group_bytes(c, gt + 1, groups[gt + 1].count) - group_bytes(c, gt + 1, 0);
+				c->prof.bytes += group_bytes(c, gt + 1, groups[gt + 1].count) - group_bytes(c, gt + 1, 0);
 			}
-			c->prof_group = gt;
-			c->prof_uni = (gt == G_FX_HRTF && run.uni_hrtf && groups[G_FX_HRTF_PK].count == 0) || ((gt == G_FX_ER_HRTF || gt == G_FX_ER_HRTF_PK) && run.uni_er);
-			c->prof_multi = false;
-			c->prof_pipe = (gt == G_3D_MIX || gt == G_3D_PROCESS || gt == G_FX_SHELF) && gas_biquad_uses_pipe(gt == G_FX_SHELF ? GAS_MODE_FX_HIGHSHELF : (a.force_mode >= 0 ? a.force_mode : (gt == G_3D_MIX ? GAS_MODE_MIX_CHANNEL : GAS_MODE_PROCESS_FRAMES)), gr.count, gt == G_3D_MIX ? a.channel_count : 1, F, false);
+			c->prof.group = gt;
+			c->prof.uni = (gt == G_FX_HRTF && run.uni_hrtf && groups[G_FX_HRTF_PK].count == 0) || ((gt == G_FX_ER_HRTF || gt == G_FX_ER_HRTF_PK) && run.uni_er);
+			c->prof.multi = false;
+			c->prof.pipe = (gt == G_3D_MIX || gt == G_3D_PROCESS || gt == G_FX_SHELF) && gas_biquad_uses_pipe(gt == G_FX_SHELF ? GAS_MODE_FX_HIGHSHELF : (a.force_mode >= 0 ? a.force_mode : (gt == G_3D_MIX ? GAS_MODE_MIX_CHANNEL : GAS_MODE_PROCESS_FRAMES)), gr.count, gt == G_3D_MIX ? a.channel_count : 1, F, false);
 		}
 		run.p_off += pcount[gt];
 	}
@@ -981,14 +980,13 @@ int run_hrtf_batch(gas_ctx *c, const std::vector<gas_ctx::Deferred> &blocks, uin
 		mb.p_offset[b] = (uint32_t)pl * c->partial_rows * c->cfg.channel_count;
 	}
 	c->pending.clear();
-	const bool timed = c->profiling && c->ev_used + 2 <= c->ev.size() && (c->prof_tick++ % c->prof_every) == 0;
+	const bool timed = c->prof.room() && c->prof.due();
 	if (timed) {
-		GAS_HIP(c, hipEventRecord(c->ev[c->ev_used], c->stream));
+		GAS_HIP(c, c->prof.begin(c->stream));
 	}
 	GAS_HIP(c, gas_launch_hrtf_multi(c->stream, ga, mb, plain_peak_bits(c), c->uni_peak_all, c->st, c->tab, c->d_tw, F, c->hist_len, c->d_partials));
 	if (timed) {
-		GAS_HIP(c, hipEventRecord(c->ev[c->ev_used + 1], c->stream));
-		c->ev_used += 2;
+		GAS_HIP(c, c->prof.end(c->stream));
 		// What this launch has to move (not K times the single-callback formula: k_hrtf_multi<., true> reads a history
 		// row in its first block and writes it back in its last one, and meets the HRIR table once): per block the
 		// frames, 8 B of peak per source, 8 B of (gain, direction) where the block has device-published rows, and the
@@ -1001,14 +999,14 @@ int run_hrtf_batch(gas_ctx *c, const std::vector<gas_ctx::Deferred> &blocks, uin
 			for (uint32_t b = 0; b < K; b++) {
 				fresh_blocks += blocks[b].fresh ? 1 : 0;
 			}
-			c->prof_bytes = (uint64_t)K * n * (F * 8 + 8) + fresh_blocks * n * 8 + (uint64_t)n * 8 + (hist_lds ? 1ull : (uint64_t)K) * n * hist_rw + (uint64_t)c->tab.dirs * 2 * GAS_HRTF_TAPS * 4 + (uint64_t)K * c->cfg.channel_count * F * 8 + carried;
+			c->prof.bytes = (uint64_t)K * n * (F * 8 + 8) + fresh_blocks * n * 8 + (uint64_t)n * 8 + (hist_lds ? 1ull : (uint64_t)K) * n * hist_rw + (uint64_t)c->tab.dirs * 2 * GAS_HRTF_TAPS * 4 + (uint64_t)K * c->cfg.channel_count * F * 8 + carried;
 		}
-		c->prof_bytes_formula = (uint64_t)K * group_bytes(c, G_FX_HRTF, n) + carried;
-		c->prof_k = K;
-		c->prof_group = G_FX_HRTF;
-		c->prof_uni = false;
-		c->prof_pipe = false;
-		c->prof_multi = true;
+		c->prof.bytes_formula = (uint64_t)K * group_bytes(c, G_FX_HRTF, n) + carried;
+		c->prof.k = K;
+		c->prof.group = G_FX_HRTF;
+		c->prof.uni = false;
+		c->prof.pipe = false;
+		c->prof.multi = true;
 	}
 	for (uint32_t b = 0; b < K; b++) {
 		gas_ctx::PendingMix pm;
@@ -1599,13 +1597,13 @@ namespace gas_priv __attribute__((visibility("hidden"))) {
 // gas_source_feed_rows: forget the slot's pending row.  Its bytes of the feed table stay taken until the next stream
 // callback empties the table (or feed_place moves on to the table's other half).
 void feed_drop(gas_ctx *c, uint32_t slot) {
-	if (c->feed_word[slot] == GAS_FEED_NONE) {
+	if (c->feed.word[slot] == GAS_FEED_NONE) {
 		return;
 	}
-	c->feed_word[slot] = GAS_FEED_NONE;
-	auto it = std::find(c->feed_slots.begin(), c->feed_slots.end(), slot);
-	*it = c->feed_slots.back();
-	c->feed_slots.pop_back();
+	c->feed.word[slot] = GAS_FEED_NONE;
+	auto it = std::find(c->feed.slots.begin(), c->feed.slots.end(), slot);
+	*it = c->feed.slots.back();
+	c->feed.slots.pop_back();
 }
 } // namespace gas_priv
 namespace {
@@ -1626,11 +1624,11 @@ int apply_pending_frees(gas_ctx *c) {
 	}
 	bool had_stream = false;
 	for (uint32_t s : c->pending_free) {
-		had_stream = had_stream || c->h_cursors[s].pcm != nullptr;
+		had_stream = had_stream || c->streams.h_cursors[s].pcm != nullptr;
 	}
 	if (had_stream) {
 		stream_rows_sync_back(c); // the compact mirror may still name these slots: fold it back before they are cleared
-		c->stream_groups_gen = UINT64_MAX;
+		c->streams.groups_gen = UINT64_MAX;
 	}
 	std::lock_guard<std::mutex> alloc_lk(c->alloc_mu);
 	for (uint32_t s : c->pending_free) {
@@ -1647,11 +1645,11 @@ int apply_pending_frees(gas_ctx *c) {
 		}
 		c->free_list.push_back(s);
 		feed_drop(c, s); // ... nor a window row fed to the playback that is gone
-		if (c->h_cursors[s].pcm) {
+		if (c->streams.h_cursors[s].pcm) {
 			// a freed playback lets go of its stream (gas_stream_destroy must not see it as bound for ever, and a
 			// re-allocated slot must not inherit the cursor): host mirror and device cursor both
-			c->h_cursors[s] = gas_cursor{};
-			GAS_HIP(c, hipMemsetAsync(c->d_cursors + s, 0, sizeof(gas_cursor), c->stream));
+			c->streams.h_cursors[s] = gas_cursor{};
+			GAS_HIP(c, hipMemsetAsync(c->streams.d_cursors + s, 0, sizeof(gas_cursor), c->stream));
 		}
 	}
 	c->pending_free.clear();
@@ -1958,11 +1956,11 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 		GAS_HIP(c, c->mem.alloc(c->d_peaks, 2 * N));
 		GAS_HIP(c, c->mem.alloc(c->d_one_slot, 1));
 		GAS_HIP(c, device_zeroed(c, c->st.was_further, N));
-		GAS_HIP(c, device_zeroed(c, c->d_cursors, N));
-		GAS_HIP(c, c->mem.alloc(c->d_stream_slots, N));
-		GAS_HIP(c, c->mem.alloc(c->d_stream_inc, N));
-		GAS_HIP(c, c->mem.alloc(c->h_stream_inc, N, Mem::PINNED));
-		c->feed_word.assign(N, GAS_FEED_NONE);
+		GAS_HIP(c, device_zeroed(c, c->streams.d_cursors, N));
+		GAS_HIP(c, c->mem.alloc(c->streams.d_slots, N));
+		GAS_HIP(c, c->mem.alloc(c->streams.d_inc, N));
+		GAS_HIP(c, c->mem.alloc(c->streams.h_inc, N, Mem::PINNED));
+		c->feed.word.assign(N, GAS_FEED_NONE);
 		{
 			// end-of-stream ramp the stream-sampling prologue multiplies the last 64 valid frames by: tap k =
 			// 0.96^(k+1) * (64 - k) / 64, the running f32 product and the f32 divide of audio_spatializer.cpp:382-392
@@ -2000,7 +1998,7 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 	}
 	c->slots.resize(N);
 	c->h_routes.assign(N, gas_bus_route_default());
-	c->h_cursors.assign(N, gas_cursor{});
+	c->streams.h_cursors.assign(N, gas_cursor{});
 	c->stamp.at.assign(N, 0);
 	c->calc.stamp.at.assign(N, 0);
 	c->dirty_flag.assign(N, 0);
@@ -2226,7 +2224,7 @@ int gas_params_publish(gas_ctx *c, uint32_t slot, const gas_params *params) {
 		return GAS_ERR_BAD_SLOT;
 	}
 	std::lock_guard<std::mutex> lk(c->params_mu);
-	c->stream_params_touched = true;
+	c->streams.params_touched = true;
 	c->params_gen++;
 	c->h_params[slot] = *params;
 	mark_dirty(c->dirty_flag, c->dirty_list, slot);
@@ -2358,7 +2356,7 @@ int gas_params_publish_batch(gas_ctx *c, const uint32_t *slots, const gas_params
 			}
 		}
 		std::lock_guard<std::mutex> lk(c->params_mu);
-		c->stream_params_touched = true;
+		c->streams.params_touched = true;
 		c->params_gen++;
 		for (uint32_t i = 0; i < n; i++) {
 			const uint32_t s = slots[i];
@@ -2409,9 +2407,9 @@ int gas_params_publish_batch(gas_ctx *c, const uint32_t *slots, const gas_params
 namespace gas_priv __attribute__((visibility("hidden"))) {
 // Write the compact per-row mirror of the cached stream list back into the per-slot cursors.
 void stream_rows_sync_back(gas_ctx *c) {
-	for (size_t i = 0; i < c->stream_rows.size(); i++) {
-		gas_cursor &cur = c->h_cursors[c->stream_slots_host[i]];
-		const gas_ctx::StreamRow &r = c->stream_rows[i];
+	for (size_t i = 0; i < c->streams.rows.size(); i++) {
+		gas_cursor &cur = c->streams.h_cursors[c->streams.slots_host[i]];
+		const StreamRow &r = c->streams.rows[i];
 		if (cur.pcm) {
 			cur.pos = r.looped ? r.pos : cur.frames - r.remaining;
 		}
@@ -2420,7 +2418,7 @@ void stream_rows_sync_back(gas_ctx *c) {
 		}
 		cur.has_frames = r.has_frames;
 	}
-	c->stream_rows.clear();
+	c->streams.rows.clear();
 }
 } // namespace gas_priv
 
@@ -2491,328 +2489,35 @@ BusList bus_list_form(const gas_ctx *c, const uint32_t *slots, uint32_t n) {
 } // namespace
 
 namespace gas_priv __attribute__((visibility("hidden"))) {
-// A failed callback leaves a zeroed mix in host memory (the reference's ERR_FAIL paths, audio_spatializer.cpp:335-343);
-// device memory is left as it is.
+// The error exit of the callback entries.  Each entry's body returns its status, and the entry passes it through here
+// once: a failed callback leaves a zeroed mix in host memory (the reference's ERR_FAIL paths,
+// audio_spatializer.cpp:335-343); device memory is left as it is.  What an entry returns in FRONT of its body leaves
+// `out` alone in both: the argument checks of every entry; in gas_process_block_buses the list reuse it cannot serve
+// and the flush_deferred behind it; in the stream entries their flush_deferred -- and a bad n_buses there zeroes as
+// much of a host `out` as a legal call could name.  gas_process_frames_1 / gas_mix_channel_1 never zero.
 int fail_out(int code, int mem, gas_audio_frame *out, size_t out_bytes) {
-	if (mem == GAS_MEM_HOST) {
+	if (code != GAS_OK && mem == GAS_MEM_HOST) {
 		std::memset(out, 0, out_bytes);
 	}
 	return code;
 }
 } // namespace gas_priv
 
-extern "C" {
+namespace {
 
-// The bodies of gas_process_block and gas_process_block_buses, behind their argument checks; the stream entries call
-// them with a fused source.
-static int process_block(gas_ctx *c, const RowSource &src, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, float *peaks, int mem);
-static int process_block_buses(gas_ctx *c, const RowSource &src, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, uint32_t n_buses, float *peaks, int mem);
+// What every callback body begins with: the caller's frame count is the context's, and the context's device is current.
+int callback_begin(const gas_ctx *c, uint32_t frames) {
+	if (frames != c->cfg.frames) {
+		return GAS_ERR_FRAME_COUNT;
+	}
+	return hipSetDevice(c->cfg.device) == hipSuccess ? GAS_OK : GAS_ERR_NO_DEVICE;
+}
 
-// Both stream entries: validation, the host mirror of the cursor arithmetic, the same_list steady state, the sampler
-// launches and the choice of the fused form.  !buses: gas_process_block_streams (one mix, out [C][frames], n_buses unused); buses:
-// gas_process_block_streams_buses (out [n_buses][C][frames], the device path of gas_process_block_buses over the windows).
-static int process_block_streams_common(gas_ctx *c, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, uint32_t n_buses, bool buses, float *peaks, uint8_t *has_frames, int mem) {
-	if (!c || !out || (n > 0 && !slots) || n > c->cfg.max_sources || (mem != GAS_MEM_HOST && mem != GAS_MEM_DEVICE)) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (buses && (n_buses < 1 || n_buses > GAS_MAX_BUSES)) {
-		if (mem == GAS_MEM_HOST) { // as much of `out` as a legal call could name
-			std::memset(out, 0, (size_t)(n_buses < GAS_MAX_BUSES ? n_buses : GAS_MAX_BUSES) * c->cfg.channel_count * c->cfg.frames * sizeof(gas_audio_frame));
-		}
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	GAS_TRY(flush_deferred(c)); // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
+// The body of gas_process_block behind its argument checks; a stream callback runs it with a fused source or with the
+// rows it sampled (GAS_MEM_DEVICE).
+int process_block(gas_ctx *c, const RowSource &src, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, float *peaks, int mem) {
 	const uint32_t F = c->cfg.frames, C = c->cfg.channel_count;
-	const size_t out_bytes = (size_t)(buses ? n_buses : 1u) * C * F * sizeof(gas_audio_frame);
-	const auto fail = [&](int code) { return fail_out(code, mem, out, out_bytes); };
-	if (frames != F) {
-		return fail(GAS_ERR_FRAME_COUNT);
-	}
-	if (hipSetDevice(c->cfg.device) != hipSuccess) {
-		return fail(GAS_ERR_NO_DEVICE);
-	}
-	// Steady state: same slot list as the previous stream callback, launch groups still cached, no parameter or
-	// binding change since -> skip validation and work on the compact row mirror.
-	// (The staged bus form regroups on every call and leaves no cached groups behind: its list stays "the same" without them.)
-	adopt_frees(c);
-	bool same_list = c->pending_free.empty() /* a deferred free re-sorts the groups */ && c->stream_rows.size() == n && (c->cached_n == n || (buses && c->stream_bus_staged)) && c->stream_last_buses == buses && c->stream_groups_gen == c->groups_gen && !c->stream_params_touched && c->stream_slots_host.size() == n && (n == 0 || std::memcmp(c->stream_slots_host.data(), slots, (size_t)n * sizeof(uint32_t)) == 0);
-	if (!same_list) {
-		stream_rows_sync_back(c);
-		for (uint32_t i = 0; i < n; i++) {
-			if (!live(c, slots[i])) {
-				return fail(GAS_ERR_BAD_SLOT);
-			}
-			const float pitch = c->slots[slots[i]].has_params ? c->h_params[slots[i]].pitch_scale : 1.0f;
-			if (!c->h_cursors[slots[i]].pcm) {
-				// bound to no stream: a fed row or silence.  pitch_scale is the sampler's input, and whoever decodes this
-				// playback has applied it already (the host layer hands it to the playback's mix callback), as for the
-				// rows of gas_process_block
-			} else if (c->h_cursors[slots[i]].resampled) {
-				if (!(pitch >= 0.0f && pitch < 32768.0f)) {
-					return fail(GAS_ERR_INVALID_ARGUMENT);
-				}
-			} else if (pitch != 1.0f && pitch != 0.0f) {
-				return fail(GAS_ERR_UNSUPPORTED_CHAIN); // a non-resampled playback class (gas_stream_set_resampled is off)
-			}
-		}
-		// Everything gas_process_block could still reject is checked BEFORE a cursor moves: the reference consumes a
-		// playback's frames only when it mixes them (audio_spatializer.cpp:378), so a failed callback must leave
-		// the playback cursors (host mirror and device) where they were.
-		c->stamp.next();
-		for (uint32_t i = 0; i < n; i++) {
-			const SlotInfo &si = c->slots[slots[i]];
-			if (!si.has_params) {
-				return fail(GAS_ERR_NO_PARAMS);
-			}
-			if (c->stamp.seen(slots[i])) {
-				return fail(GAS_ERR_INVALID_ARGUMENT); // one playback twice in a callback
-			}
-			const bool wants_hrtf = si.group == G_FX_HRTF || si.group == G_FX_ER_HRTF || (si.group == G_FX_GENERIC && chain_has(si.chain_sig, GAS_FX_HRTF));
-			if (wants_hrtf && c->tab.spec == nullptr) {
-				return fail(GAS_ERR_NO_HRTF);
-			}
-		}
-		if (buses && bus_list_form(c, slots, n) == BUS_LIST_NEITHER) {
-			return fail(GAS_ERR_UNSUPPORTED_CHAIN); // process_block_buses would, after the cursors have moved
-		}
-		c->stream_last_buses = buses;
-		c->stream_bus_staged = false;
-		c->stream_params_touched = false;
-		c->stream_slots_host.assign(slots, slots + n);
-		c->stream_rows.resize(n);
-		c->stream_all_hrtf = n > 0;
-		c->stream_any_resampled = false;
-		c->stream_any_looped = false;
-		c->stream_any_adpcm = false;
-		c->stream_any_qoa = false;
-		for (uint32_t i = 0; i < n; i++) {
-			const gas_cursor &cur = c->h_cursors[slots[i]];
-			c->stream_any_adpcm = c->stream_any_adpcm || (cur.pcm && (cur.format_channels >> 8) == GAS_PCM_IMA_ADPCM);
-			c->stream_any_qoa = c->stream_any_qoa || (cur.pcm && (cur.format_channels >> 8) == GAS_PCM_QOA);
-			gas_ctx::StreamRow &r = c->stream_rows[i];
-			r.remaining = cur.pcm && cur.frames > cur.pos ? cur.frames - cur.pos : 0;
-			r.has_frames = cur.pcm ? cur.has_frames : 0;
-			r.resampled = cur.pcm ? cur.resampled : 0;
-			r.looped = cur.pcm && cur.loop_mode ? 1 : 0;
-			r.pos = cur.pos;
-			c->stream_any_looped = c->stream_any_looped || r.looped;
-			r.inc = 65536;
-			if (r.resampled) {
-				// [ENGINE] mix_increment = uint64((stream_rate * rate_scale / mix_rate) * FP_LEN), stream at the mix rate
-				const float pitch = c->slots[slots[i]].has_params ? c->h_params[slots[i]].pitch_scale : 1.0f;
-				r.inc = (uint32_t)(uint64_t)(((double)(c->cfg.mix_rate * pitch) / (double)c->cfg.mix_rate) * 65536.0);
-				r.fp_pos = cur.fp_pos;
-				r.end_fp = cur.frames << 16;
-				c->stream_any_resampled = true;
-			}
-			c->h_stream_inc[i] = r.inc;
-			c->stream_all_hrtf = c->stream_all_hrtf && c->slots[slots[i]].group == G_FX_HRTF;
-		}
-		if (c->stream_any_resampled) {
-			hipError_t e = hipMemcpyAsync(c->d_stream_inc, c->h_stream_inc, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-			if (e == hipSuccess) {
-				e = hipStreamSynchronize(c->stream); // the pinned staging array is rewritten by the next list
-			}
-			if (e != hipSuccess) {
-				c->last_err = hipGetErrorString(e);
-				return fail(GAS_ERR_DEVICE);
-			}
-		}
-		if (n > 0) {
-			hipError_t e = hipMemcpyAsync(c->d_stream_slots, c->stream_slots_host.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-			if (e != hipSuccess) {
-				c->last_err = hipGetErrorString(e);
-				return fail(GAS_ERR_DEVICE);
-			}
-		}
-	}
-	// host mirror of the cursor arithmetic: which playbacks end inside this callback (audio_spatializer.cpp:380,398)
-	bool draining_changed = false;
-	// gas_source_feed_rows: which entries take a fed row is this callback's matter alone, read from the pending rows and
-	// never from the cached list -- the steady state above holds whatever is fed, not fed, or fed again under it.
-	const bool feed_pending = !c->feed_slots.empty();
-	bool any_fed = false;
-	if (feed_pending) {
-		c->feed_entry.assign(n, GAS_FEED_NONE);
-	}
-	for (uint32_t i = 0; i < n; i++) {
-		gas_ctx::StreamRow &r = c->stream_rows[i];
-		if (feed_pending && c->feed_word[slots[i]] != GAS_FEED_NONE) { // a live playback without a cursor: nothing moves, nothing ends
-			c->feed_entry[i] = c->feed_word[slots[i]];
-			any_fed = true;
-			r.draining_marked = 0; // the next callback that finds it unfed marks it draining again
-			if (has_frames) {
-				has_frames[i] = 1;
-			}
-			continue;
-		}
-		if (r.has_frames && r.resampled) { // same arithmetic as k_sample_sources' resampled branch
-			uint64_t mixed = F;
-			if (r.looped) {
-				// never runs out
-			} else if (r.fp_pos >= r.end_fp) {
-				mixed = 0;
-			} else if (r.inc > 0) {
-				const uint64_t need = (r.end_fp - r.fp_pos + r.inc - 1) / r.inc;
-				mixed = need < F ? need : F;
-			}
-			r.fp_pos += (uint64_t)F * r.inc;
-			if (mixed != F) {
-				r.has_frames = 0;
-			}
-		} else if (r.has_frames && r.looped) {
-			r.pos += F;
-		} else if (r.has_frames) {
-			const uint32_t mixed = r.remaining < F ? (uint32_t)r.remaining : F;
-			r.remaining -= mixed;
-			if (mixed != F) {
-				r.has_frames = 0;
-			}
-		}
-		if (!r.has_frames && !r.draining_marked) {
-			r.draining_marked = 1;
-			if (!c->slots[slots[i]].draining) {
-				c->slots[slots[i]].draining = 1; // from now on the gate reads its peak (:464)
-				draining_changed = true;
-			}
-		}
-		if (has_frames) {
-			has_frames[i] = (uint8_t)r.has_frames;
-		}
-	}
-	if (draining_changed) {
-		c->cached_n = UINT32_MAX;
-		same_list = false;
-	}
-	if (any_fed && c->feed_entry != c->feed_entry_dev) { // the list or the fed set changed: the table's header follows
-		hipError_t e = hipEventSynchronize(c->feed_entry_ev); // the previous header has left the pinned words: a wait only while that upload is still queued
-		if (e == hipSuccess) {
-			std::memcpy(c->h_feed_entry, c->feed_entry.data(), (size_t)n * sizeof(uint32_t));
-			e = hipMemcpyAsync(c->d_feed, c->h_feed_entry, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream);
-		}
-		if (e == hipSuccess) {
-			e = hipEventRecord(c->feed_entry_ev, c->stream);
-		}
-		if (e != hipSuccess) {
-			c->feed_entry_dev.clear();
-			c->last_err = hipGetErrorString(e);
-			return fail(GAS_ERR_DEVICE);
-		}
-		c->feed_entry_dev = c->feed_entry;
-	}
-	if (feed_pending) { // one feed serves one callback; rows of slots the list does not name go with it
-		for (uint32_t s : c->feed_slots) {
-			c->feed_word[s] = GAS_FEED_NONE;
-		}
-		c->feed_slots.clear();
-		c->feed_used = 0;
-	}
-	const uint8_t *feed = any_fed ? c->d_feed : nullptr;
-	// rows for this callback live in the library's staging buffer (not needed when k_hrtf_ols samples the
-	// streams itself: every playback a plain [HRTF] chain)
-	// (GAS_FLAG_HRTF_BLEND_FADE: the stream-sampling form has no registers left for the fade, DESIGN.md 3.4 -- rows first)
-	// (gas_stream_set_loop: the cross-fade form has no registers left for the looped branch either, DESIGN.md 3.4 -- rows first)
-	const bool loops_fused = !c->stream_any_looped || (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) == 0;
-	// (GAS_PCM_IMA_ADPCM, GAS_PCM_QOA: the fused prologues read uncompressed frames only -- rows first, like a resampled playback)
-	// (buses: the fused form is k_hrtf_uni<SRC_PCM, BUS2>, which gas_process_block_buses picks on a one-pair context without a k_hrtf_ols-only mode)
-	const bool bus_fusable = !buses || (C == 1 && uni_ok(c) && gas_hrtf_uni_waves() == 8);
-	// (gas_source_feed_rows: k_hrtf_uni<SRC_PCM> and k_hrtf_uni<SRC_PCM, BUS2> take fed entries; the k_hrtf_ols stream-sampling forms -- cross-fade, direction runs / order, interpolation contexts -- have no registers left for them, DESIGN.md 3.4 -- rows first)
-	const bool fed_fusable = !any_fed || uni_ok(c);
-	const bool all_hrtf = c->stream_all_hrtf && !c->stream_any_resampled && !c->stream_any_adpcm && !c->stream_any_qoa && !fade_on(c) && loops_fused && !c->stream_rows_first && bus_fusable && fed_fusable; // the fused prologue samples plain playbacks only
-	c->stream_last_fused = all_hrtf;
-	if (!all_hrtf) {
-		if (ensure_src(c, (size_t)n * F) != hipSuccess) {
-			return fail(GAS_ERR_OUT_OF_MEMORY);
-		}
-		if (n > 0) {
-			hipError_t e = gas_launch_sample_sources(c->stream, c->d_cursors, c->d_stream_slots, n, F, c->d_fade_env, c->d_src, c->stream_any_resampled ? c->d_stream_inc : nullptr, feed);
-			if (e == hipSuccess && c->stream_any_adpcm) {
-				e = gas_launch_sample_adpcm(c->stream, c->d_cursors, c->d_stream_slots, n, F, c->d_fade_env, c->d_src, c->stream_any_resampled ? c->d_stream_inc : nullptr, c->adpcm_span);
-			}
-			if (e == hipSuccess && c->stream_any_qoa) {
-				e = gas_launch_sample_qoa(c->stream, c->d_cursors, c->d_stream_slots, n, F, c->d_fade_env, c->d_src, c->stream_any_resampled ? c->d_stream_inc : nullptr, c->qoa_span);
-			}
-			if (e != hipSuccess) {
-				c->last_err = hipGetErrorString(e);
-				return fail(GAS_ERR_DEVICE);
-			}
-		}
-	}
-	RowSource rows; // fused: no float rows, the HRTF launch samples the bound streams (and the fed rows) itself
-	if (all_hrtf) {
-		rows.cursors = c->d_cursors;
-		rows.feed = feed;
-	} else {
-		rows.rows = c->d_src;
-	}
-	// host outputs: the device path into the library's buffers, one copy back
-	gas_audio_frame *d_out = out;
-	float *d_pk = peaks;
-	if (mem == GAS_MEM_HOST) {
-		const int rcs = stage_host(c, nullptr, n, buses, d_out, d_pk);
-		if (rcs != GAS_OK) {
-			return fail(rcs);
-		}
-	}
-	int rc = GAS_OK;
-	if (buses) {
-		// gas_process_block_buses reuses a list only for its 3D-mix and fused [HRTF] forms; the staged form needs it every time
-		const bool reuse = same_list && n > 0 && c->cached_n == n && c->bus_form_cached != 0 && c->bus_form_groups_gen == c->groups_gen;
-		rc = process_block_buses(c, rows, reuse ? nullptr : slots, n, F, d_out, n_buses, d_pk, GAS_MEM_DEVICE);
-		c->stream_bus_staged = rc == GAS_OK && n > 0 && c->cached_n != n; // ran staged: nothing cached to compare with next time
-	} else {
-		rc = process_block(c, rows, same_list ? nullptr : slots, n, F, d_out, d_pk, GAS_MEM_DEVICE);
-	}
-	c->stream_groups_gen = rc == GAS_OK ? c->groups_gen : UINT64_MAX;
-	if (rc == GAS_OK && !buses && mem == GAS_MEM_HOST) {
-		rc = join_outputs(c);
-	}
-	if (rc != GAS_OK) {
-		return fail(rc);
-	}
-	if (mem == GAS_MEM_DEVICE) {
-		return GAS_OK;
-	}
-	const hipError_t e = copy_back(c, out, d_out, out_bytes, peaks, n);
-	if (e != hipSuccess) {
-		c->last_err = hipGetErrorString(e);
-		return fail(GAS_ERR_DEVICE);
-	}
-	return GAS_OK;
-}
-
-int gas_process_block_streams(gas_ctx *c, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, float *peaks, uint8_t *has_frames, int mem) {
-	return process_block_streams_common(c, slots, n, frames, out, 0, false, peaks, has_frames, mem);
-}
-
-int gas_process_block_streams_buses(gas_ctx *c, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, uint32_t n_buses, float *peaks, uint8_t *has_frames, int mem) {
-	return process_block_streams_common(c, slots, n, frames, out, n_buses, true, peaks, has_frames, mem);
-}
-
-int gas_stream_last_fused(gas_ctx *c) {
-	return c ? (c->stream_last_fused ? 1 : 0) : GAS_ERR_INVALID_ARGUMENT;
-}
-
-int gas_process_block(gas_ctx *c, const gas_audio_frame *src, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, float *peaks, int mem) {
-	if (!c || !out || (mem != GAS_MEM_HOST && mem != GAS_MEM_DEVICE) || (n > 0 && !src) || n > c->cfg.max_sources) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	RowSource rows;
-	rows.rows = src;
-	return process_block(c, rows, slots, n, frames, out, peaks, mem);
-}
-
-static int process_block(gas_ctx *c, const RowSource &src, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, float *peaks, int mem) {
-	const uint32_t F = c->cfg.frames, C = c->cfg.channel_count;
-	const size_t out_bytes = (size_t)C * F * sizeof(gas_audio_frame);
-	int rc = GAS_OK;
-	const auto fail = [&](int code) { return fail_out(code, mem, out, out_bytes); };
-	if (frames != F) {
-		return fail(GAS_ERR_FRAME_COUNT);
-	}
-	if (hipSetDevice(c->cfg.device) != hipSuccess) {
-		return fail(GAS_ERR_NO_DEVICE);
-	}
+	GAS_TRY(callback_begin(c, frames));
 	adopt_frees(c);
 	if (!c->deferred.empty()) { // GAS_FLAG_BATCHED_LAUNCH: do the waiting callbacks still see what they were recorded with?
 		bool host_dirty = false;
@@ -2822,36 +2527,24 @@ static int process_block(gas_ctx *c, const RowSource &src, const uint32_t *slots
 		}
 		const bool keep = mem == GAS_MEM_DEVICE && !slots && n == c->deferred_n && c->pending_free.empty() && c->groups_gen == c->deferred_groups_gen && !host_dirty;
 		if (!keep) {
-			rc = flush_deferred(c);
-			if (rc != GAS_OK) {
-				return fail(rc);
-			}
+			GAS_TRY(flush_deferred(c));
 		}
 	}
 	if (c->pending_params && (slots || n == 0 || c->cached_n != n || !c->pending_free.empty())) {
-		rc = flush_pending_params(c); // the list may change: scatter with the mapping it was published for
-		if (rc != GAS_OK) {
-			return fail(rc);
-		}
+		GAS_TRY(flush_pending_params(c)); // the list may change: scatter with the mapping it was published for
 	}
 	apply_pending_frees(c);
 	if (slots || n == 0) { // an empty callback needs no list
-		rc = build_groups(c, slots, n, false);
-		if (rc != GAS_OK) {
-			c->cached_n = UINT32_MAX;
-			return fail(rc);
-		}
+		c->cached_n = UINT32_MAX; // what a list that build_groups rejects leaves behind
+		GAS_TRY(build_groups(c, slots, n, false));
 	} else if (c->cached_n != n) {
-		return fail(GAS_ERR_INVALID_ARGUMENT);
+		return GAS_ERR_INVALID_ARGUMENT;
 	}
 	if (needs_hrtf(c)) {
-		return fail(GAS_ERR_NO_HRTF);
+		return GAS_ERR_NO_HRTF;
 	}
 	const uint64_t pgen = c->params_gen.load(); // read before the snapshot: a publish racing with it re-sorts next time
-	rc = flush_params(c); // one snapshot per callback (audio_spatializer.cpp:328)
-	if (rc != GAS_OK) {
-		return fail(rc);
-	}
+	GAS_TRY(flush_params(c)); // one snapshot per callback (audio_spatializer.cpp:328)
 	if (c->order_groups_gen != c->groups_gen || c->order_params_gen != pgen) {
 		std::memset(c->order_ok, 0, sizeof(c->order_ok));
 		c->order_groups_gen = c->groups_gen;
@@ -2862,10 +2555,7 @@ static int process_block(gas_ctx *c, const RowSource &src, const uint32_t *slots
 	gas_audio_frame *d_out = out;
 	float *d_peaks = peaks ? peaks : c->d_peaks;
 	if (mem == GAS_MEM_HOST) {
-		rc = stage_host(c, src.rows, n, false, d_out, d_peaks);
-		if (rc != GAS_OK) {
-			return fail(rc);
-		}
+		GAS_TRY(stage_host(c, src.rows, n, false, d_out, d_peaks));
 		d_src.rows = c->d_src;
 	}
 	const gas_params *fresh = nullptr; // device-published rows this callback's HRTF launch reads itself
@@ -2878,10 +2568,7 @@ static int process_block(gas_ctx *c, const RowSource &src, const uint32_t *slots
 			fresh = c->pending_params; // k_hrtf_ols reads the rows and writes them through
 			c->pending_params = nullptr;
 		} else {
-			rc = flush_pending_params(c);
-			if (rc != GAS_OK) {
-				return fail(rc);
-			}
+			GAS_TRY(flush_pending_params(c));
 		}
 	}
 	if (mem == GAS_MEM_DEVICE && batchable(c, n, src.fused())) {
@@ -2894,209 +2581,155 @@ static int process_block(gas_ctx *c, const RowSource &src, const uint32_t *slots
 		c->deferred_n = n;
 		c->deferred_groups_gen = c->groups_gen;
 		const uint32_t depth = c->batch_depth < GAS_HRTF_MULTI_MAX_BLOCKS ? c->batch_depth : GAS_HRTF_MULTI_MAX_BLOCKS;
-		if (c->deferred.size() >= depth) {
-			rc = flush_deferred(c);
-			return rc == GAS_OK ? GAS_OK : fail(rc);
-		}
-		return GAS_OK;
+		return c->deferred.size() >= depth ? flush_deferred(c) : GAS_OK;
 	}
-	if (!c->deferred.empty()) {
-		rc = flush_deferred(c);
-		if (rc != GAS_OK) {
-			return fail(rc);
-		}
-	}
+	GAS_TRY(flush_deferred(c));
 	RunArgs a = own_list(c, d_src, n, d_out, d_peaks);
 	a.channel_count = C;
 	a.use_order = true;
 	a.pipelined = mem == GAS_MEM_DEVICE;
 	a.fresh = fresh;
-	rc = run_groups(c, a);
-	if (rc != GAS_OK) {
-		return fail(rc);
-	}
+	GAS_TRY(run_groups(c, a));
 	if (mem == GAS_MEM_HOST) {
-		const hipError_t e = copy_back(c, out, c->d_out, out_bytes, peaks, n);
-		if (e != hipSuccess) {
-			c->last_err = hipGetErrorString(e);
-			return fail(GAS_ERR_DEVICE);
-		}
+		GAS_HIP(c, copy_back(c, out, c->d_out, (size_t)C * F * sizeof(gas_audio_frame), peaks, n));
 	}
 	return GAS_OK;
 }
 
-int gas_bus_routes_publish(gas_ctx *c, const uint32_t *slots, const gas_bus_route *routes, uint32_t n) {
-	if (!c || (n > 0 && (!slots || !routes))) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	for (uint32_t i = 0; i < n; i++) {
-		if (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used) {
-			return GAS_ERR_BAD_SLOT;
+// The routes snapshot of a bus callback (latest wins), like the parameters.
+int flush_routes(gas_ctx *c) {
+	bool upload = false;
+	{
+		std::lock_guard<std::mutex> lk(c->params_mu);
+		if (c->routes_dirty || !c->d_routes) {
+			GAS_HIP(c, alloc_once(c, c->h_routes_pinned, c->cfg.max_sources, Mem::PINNED));
+			GAS_HIP(c, alloc_once(c, c->d_routes, c->cfg.max_sources));
+			std::memcpy(c->h_routes_pinned, c->h_routes.data(), sizeof(gas_bus_route) * c->cfg.max_sources);
+			c->routes_dirty = false;
+			upload = true;
 		}
 	}
-	std::lock_guard<std::mutex> lk(c->params_mu);
-	for (uint32_t i = 0; i < n; i++) {
-		c->h_routes[slots[i]] = routes[i];
+	if (upload) {
+		GAS_HIP(c, hipMemcpyAsync(c->d_routes, c->h_routes_pinned, sizeof(gas_bus_route) * c->cfg.max_sources, hipMemcpyHostToDevice, c->stream));
+		GAS_HIP(c, hipStreamSynchronize(c->stream)); // the pinned mirror is rewritten by the next snapshot
 	}
-	c->routes_dirty = true;
 	return GAS_OK;
 }
 
-// AudioSpatializer3D's buses in one launch: the mix_channel kernel with per-source weights per bus, its partial
-// planes summed by the ordinary deterministic reduce (bus-major: plane b * C + c).
-int gas_process_block_buses(gas_ctx *c, const gas_audio_frame *src, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, uint32_t n_buses, float *peaks, int mem) {
-	// slots == NULL: the list (and grouping) of the previous call, like gas_process_block -- for the two forms whose
-	// grouping is the ordinary one (3D mix, fused [HRTF])
-	if (!c || !out || (mem != GAS_MEM_HOST && mem != GAS_MEM_DEVICE) || (n > 0 && !src) || n > c->cfg.max_sources || n_buses < 1 || n_buses > GAS_MAX_BUSES) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	RowSource rows;
-	rows.rows = src;
-	return process_block_buses(c, rows, slots, n, frames, out, n_buses, peaks, mem);
-}
-
-static int process_block_buses(gas_ctx *c, const RowSource &src, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, uint32_t n_buses, float *peaks, int mem) {
-	adopt_frees(c);
-	if (n > 0 && !slots && (c->cached_n != n || c->bus_form_cached == 0 || c->bus_form_groups_gen != c->groups_gen || !c->pending_free.empty())) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	GAS_TRY(flush_deferred(c)); // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
+// The body of process_block_buses.  AudioSpatializer3D's buses in one launch: the mix_channel kernel with per-source
+// weights per bus, its partial planes summed by the ordinary deterministic reduce (bus-major: plane b * C + c).
+int bus_body(gas_ctx *c, const RowSource &src, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, uint32_t n_buses, float *peaks, int mem) {
 	const uint32_t F = c->cfg.frames, C = c->cfg.channel_count;
-	const size_t out_bytes = (size_t)n_buses * C * F * sizeof(gas_audio_frame);
-	const auto fail = [&](int code) { return fail_out(code, mem, out, out_bytes); };
-	if (frames != F) {
-		return fail(GAS_ERR_FRAME_COUNT);
-	}
-	if (hipSetDevice(c->cfg.device) != hipSuccess) {
-		return fail(GAS_ERR_NO_DEVICE);
-	}
-	int rc = flush_pending_params(c);
-	if (rc != GAS_OK) {
-		return fail(rc);
-	}
+	GAS_TRY(callback_begin(c, frames));
+	GAS_TRY(flush_pending_params(c));
 	apply_pending_frees(c);
 	// Two forms: every source GAS_KIND_3D_MIX (the mix-channel buses of AudioSpatializer3D, fused in the biquad
 	// kernels), or every source an effect chain (run staged: per-source rows, then mixed per bus) on a one-pair context.
 	const bool reuse = n > 0 && !slots; // the cached form is 1 (3D mix) or 2 (fused [HRTF]) then
 	const BusList form = reuse ? (c->bus_form_cached == 1 ? BUS_LIST_3D_MIX : BUS_LIST_PLAIN_HRTF) : bus_list_form(c, slots, n);
-	const bool all_mix = form == BUS_LIST_3D_MIX;
 	// [HRTF] sources onto one or two buses have a fused form (k_hrtf_uni<BUS2>: the second bus's spectra sums in LDS)
 	// (three to six buses: one fused launch per pair of buses, the state committed by the last)
 	const bool fused_hrtf = form == BUS_LIST_PLAIN_HRTF && uni_ok(c) && gas_hrtf_uni_waves() == 8;
 	if (src.fused() && !(fused_hrtf && mem == GAS_MEM_DEVICE)) {
-		return fail(GAS_ERR_INVALID_ARGUMENT); // gas_process_block_streams_buses hands over no rows: only the fused form can sample
+		return GAS_ERR_INVALID_ARGUMENT; // gas_process_block_streams_buses hands over no rows: only the fused form can sample
 	}
 	const bool staged = (form == BUS_LIST_CHAINS || form == BUS_LIST_PLAIN_HRTF) && !fused_hrtf;
 	if (reuse && staged) {
-		return fail(GAS_ERR_INVALID_ARGUMENT); // the staged form regroups: it needs the list
+		return GAS_ERR_INVALID_ARGUMENT; // the staged form regroups: it needs the list
 	}
 	if (!reuse) {
-		rc = build_groups(c, slots, n, staged);
-		c->cached_n = staged ? UINT32_MAX : c->cached_n; // the staged grouping is this call's only: a later list reuse must regroup
-		if (rc != GAS_OK) {
-			c->cached_n = UINT32_MAX;
-			return fail(rc);
+		c->cached_n = UINT32_MAX; // what a list that build_groups rejects leaves behind
+		GAS_TRY(build_groups(c, slots, n, staged));
+		if (staged) {
+			c->cached_n = UINT32_MAX; // the staged grouping is this call's only: a later list reuse must regroup
 		}
 	}
-	c->bus_form_cached = staged ? 0 : (fused_hrtf ? 2 : (all_mix ? 1 : 0));
+	c->bus_form_cached = staged ? 0 : (fused_hrtf ? 2 : (form == BUS_LIST_3D_MIX ? 1 : 0));
 	c->bus_form_groups_gen = c->groups_gen;
 	for (int gt = 0; gt < G_COUNT; gt++) {
 		if (gt != (staged ? G_FX_GENERIC : (fused_hrtf ? G_FX_HRTF : G_3D_MIX)) && c->groups[gt].count > 0) {
 			c->cached_n = UINT32_MAX;
-			return fail(GAS_ERR_UNSUPPORTED_CHAIN);
+			return GAS_ERR_UNSUPPORTED_CHAIN;
 		}
 	}
 	if ((staged || fused_hrtf) && needs_hrtf(c)) {
-		return fail(GAS_ERR_NO_HRTF);
+		return GAS_ERR_NO_HRTF;
 	}
-	rc = join_outputs(c);
-	if (rc == GAS_OK) {
-		rc = flush_params(c);
+	GAS_TRY(join_outputs(c));
+	GAS_TRY(flush_params(c));
+	GAS_TRY(flush_routes(c));
+	const uint32_t P = n ? (fused_hrtf ? gas_hrtf_uni_partials(n) : gas_biquad_partials(n)) : 0;
+	const size_t need = (size_t)(fused_hrtf ? 2 * ((n_buses + 1) / 2) : n_buses) * C * (P ? P : 1) * F * 2; // the fused [HRTF] form writes two planes per launch
+	if (need > c->bus_partial_floats) {
+		GAS_HIP(c, hipStreamSynchronize(c->stream));
+		GAS_HIP(c, c->mem.grow(c->d_bus_partials, c->bus_partial_floats, need));
 	}
-	if (rc != GAS_OK) {
-		return fail(rc);
+	RowSource d_src = src;
+	gas_audio_frame *d_out = out;
+	float *d_peaks = peaks ? peaks : c->d_peaks;
+	if (mem == GAS_MEM_HOST) {
+		GAS_TRY(stage_host(c, src.rows, n, true, d_out, d_peaks));
+		d_src.rows = c->d_src;
 	}
-	rc = [&]() -> int {
-		// routes snapshot (latest wins), like the parameters
-		bool upload = false;
-		{
-			std::lock_guard<std::mutex> lk(c->params_mu);
-			if (c->routes_dirty || !c->d_routes) {
-				GAS_HIP(c, alloc_once(c, c->h_routes_pinned, c->cfg.max_sources, Mem::PINNED));
-				GAS_HIP(c, alloc_once(c, c->d_routes, c->cfg.max_sources));
-				std::memcpy(c->h_routes_pinned, c->h_routes.data(), sizeof(gas_bus_route) * c->cfg.max_sources);
-				c->routes_dirty = false;
-				upload = true;
-			}
+	if (fused_hrtf && n > 0) {
+		// bus b's partial rows: [b * P, (b + 1) * P); one launch per pair of buses, the last one commits the state
+		gas_hrtf_uni_launch lu = plain_uni_launch(c, own_hrtf_group(c, d_src.rows, n, d_peaks), d_src, c->d_bus_partials, 0);
+		lu.routes = c->d_routes;
+		lu.bus_rows = P;
+		const uint32_t passes = (n_buses + 1) / 2;
+		for (uint32_t pass = 0; pass < passes; pass++) {
+			lu.p_offset = 2 * pass * P;
+			lu.bus_base = 2 * pass;
+			lu.commit = pass + 1 == passes;
+			GAS_HIP(c, gas_launch_hrtf_uni(lu));
 		}
-		if (upload) {
-			GAS_HIP(c, hipMemcpyAsync(c->d_routes, c->h_routes_pinned, sizeof(gas_bus_route) * c->cfg.max_sources, hipMemcpyHostToDevice, c->stream));
-			GAS_HIP(c, hipStreamSynchronize(c->stream)); // the pinned mirror is rewritten by the next snapshot
-		}
-		const uint32_t P = n ? (fused_hrtf ? gas_hrtf_uni_partials(n) : gas_biquad_partials(n)) : 0;
-		const size_t need = (size_t)(fused_hrtf ? 2 * ((n_buses + 1) / 2) : n_buses) * C * (P ? P : 1) * F * 2; // the fused [HRTF] form writes two planes per launch
-		if (need > c->bus_partial_floats) {
-			GAS_HIP(c, hipStreamSynchronize(c->stream));
-			GAS_HIP(c, c->mem.grow(c->d_bus_partials, c->bus_partial_floats, need));
-		}
-		RowSource d_src = src;
-		gas_audio_frame *d_out = out;
-		float *d_peaks = peaks ? peaks : c->d_peaks;
-		if (mem == GAS_MEM_HOST) {
-			GAS_TRY(stage_host(c, src.rows, n, true, d_out, d_peaks));
-			d_src.rows = c->d_src;
-		}
-		if (fused_hrtf && n > 0) {
-			// bus b's partial rows: [b * P, (b + 1) * P); one launch per pair of buses, the last one commits the state
-			gas_hrtf_uni_launch lu = plain_uni_launch(c, own_hrtf_group(c, d_src.rows, n, d_peaks), d_src, c->d_bus_partials, 0);
-			lu.routes = c->d_routes;
-			lu.bus_rows = P;
-			const uint32_t passes = (n_buses + 1) / 2;
-			for (uint32_t pass = 0; pass < passes; pass++) {
-				lu.p_offset = 2 * pass * P;
-				lu.bus_base = 2 * pass;
-				lu.commit = pass + 1 == passes;
-				GAS_HIP(c, gas_launch_hrtf_uni(lu));
-			}
-		} else if (staged) {
-			// effect kinds: the stages of every chain with rows out, then k_rows_accumulate_buses and one reduce over the
-			// buses (run_groups' staged-chain path, told about the buses)
-			gas_bus_args ba;
-			ba.routes = c->d_routes;
-			ba.n_buses = n_buses;
-			RunArgs a = own_list(c, d_src, n, d_out, d_peaks);
-			a.buses = &ba;
-			const int rcg = run_groups(c, a);
-			if (rcg != GAS_OK) {
-				return rcg;
-			}
-		} else if (n > 0) {
-			GAS_HIP(c, hipMemsetAsync(d_peaks, 0, (size_t)n * 2 * sizeof(float), c->stream)); // k_biquad_mix accumulates peaks over channel pairs
-			gas_group_args ga;
-			ga.src = d_src.rows;
-			ga.rows = c->cached_identity_rows ? nullptr : c->d_rows;
-			ga.slots = c->d_slots;
-			ga.slot_base = 0;
-			ga.n = n;
-			ga.peaks = d_peaks;
-			gas_bus_args ba;
-			ba.routes = c->d_routes;
-			ba.n_buses = n_buses;
-			// force the multi-bus code even for one bus when the caller routes (a lone bus other than 0 is legal)
-			GAS_HIP(c, gas_launch_biquad_mix(c->stream, GAS_MODE_MIX_CHANNEL, ga, c->st, F, 0, C, c->cfg.mix_rate, c->d_bus_partials, 0, P, nullptr, ba));
-		}
-		if (!staged) {
-			GAS_HIP(c, gas_launch_mix_reduce(c->stream, c->d_bus_partials, P, P ? P : 1, n_buses * C, F, d_out));
-		}
-		if (mem == GAS_MEM_HOST) {
-			GAS_HIP(c, copy_back(c, out, c->d_bus_out, out_bytes, peaks, n));
-		}
-		return GAS_OK;
-	}();
-	return rc == GAS_OK ? GAS_OK : fail(rc);
+	} else if (staged) {
+		// effect kinds: the stages of every chain with rows out, then k_rows_accumulate_buses and one reduce over the
+		// buses (run_groups' staged-chain path, told about the buses)
+		gas_bus_args ba;
+		ba.routes = c->d_routes;
+		ba.n_buses = n_buses;
+		RunArgs a = own_list(c, d_src, n, d_out, d_peaks);
+		a.buses = &ba;
+		GAS_TRY(run_groups(c, a));
+	} else if (n > 0) {
+		GAS_HIP(c, hipMemsetAsync(d_peaks, 0, (size_t)n * 2 * sizeof(float), c->stream)); // k_biquad_mix accumulates peaks over channel pairs
+		gas_group_args ga;
+		ga.src = d_src.rows;
+		ga.rows = c->cached_identity_rows ? nullptr : c->d_rows;
+		ga.slots = c->d_slots;
+		ga.slot_base = 0;
+		ga.n = n;
+		ga.peaks = d_peaks;
+		gas_bus_args ba;
+		ba.routes = c->d_routes;
+		ba.n_buses = n_buses;
+		// force the multi-bus code even for one bus when the caller routes (a lone bus other than 0 is legal)
+		GAS_HIP(c, gas_launch_biquad_mix(c->stream, GAS_MODE_MIX_CHANNEL, ga, c->st, F, 0, C, c->cfg.mix_rate, c->d_bus_partials, 0, P, nullptr, ba));
+	}
+	if (!staged) {
+		GAS_HIP(c, gas_launch_mix_reduce(c->stream, c->d_bus_partials, P, P ? P : 1, n_buses * C, F, d_out));
+	}
+	if (mem == GAS_MEM_HOST) {
+		GAS_HIP(c, copy_back(c, out, c->d_bus_out, (size_t)n_buses * C * F * sizeof(gas_audio_frame), peaks, n));
+	}
+	return GAS_OK;
 }
 
-static int process_one(gas_ctx *c, uint32_t slot, int channel, bool mix_channel, gas_audio_frame *out, const gas_audio_frame *src, int frame_count) {
+// gas_process_block_buses behind its argument checks; a stream callback runs it with a fused source or with the rows
+// it sampled (GAS_MEM_DEVICE).  slots == NULL: the list (and grouping) of the previous call, like gas_process_block --
+// for the two forms whose grouping is the ordinary one (3D mix, fused [HRTF]).
+int process_block_buses(gas_ctx *c, const RowSource &src, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, uint32_t n_buses, float *peaks, int mem) {
+	adopt_frees(c);
+	if (n > 0 && !slots && (c->cached_n != n || c->bus_form_cached == 0 || c->bus_form_groups_gen != c->groups_gen || !c->pending_free.empty())) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	GAS_TRY(flush_deferred(c)); // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
+	return fail_out(bus_body(c, src, slots, n, frames, out, n_buses, peaks, mem), mem, out, (size_t)n_buses * c->cfg.channel_count * c->cfg.frames * sizeof(gas_audio_frame));
+}
+
+// The body of gas_process_frames_1 and gas_mix_channel_1 (host memory).  No exit of it touches `out`.
+int process_one(gas_ctx *c, uint32_t slot, int channel, bool mix_channel, gas_audio_frame *out, const gas_audio_frame *src, int frame_count) {
 	if (!c || !out || !src) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
@@ -3139,13 +2772,8 @@ static int process_one(gas_ctx *c, uint32_t slot, int channel, bool mix_channel,
 	if ((gt == G_FX_HRTF_PK || gt == G_FX_ER_HRTF_PK) && c->tab.spec == nullptr) {
 		return GAS_ERR_NO_HRTF;
 	}
-	int rc = flush_pending_params(c);
-	if (rc == GAS_OK) {
-		rc = flush_params(c);
-	}
-	if (rc != GAS_OK) {
-		return rc;
-	}
+	GAS_TRY(flush_pending_params(c));
+	GAS_TRY(flush_params(c));
 	gas_audio_frame *d_out = nullptr;
 	float *d_peaks = nullptr;
 	GAS_TRY(stage_host(c, src, 1, false, d_out, d_peaks));
@@ -3173,6 +2801,346 @@ static int process_one(gas_ctx *c, uint32_t slot, int channel, bool mix_channel,
 	GAS_TRY(run_groups(c, a));
 	GAS_HIP(c, copy_back(c, out, d_out, (size_t)F * sizeof(gas_audio_frame), nullptr, 0));
 	return GAS_OK;
+}
+
+// The stream callback, step by step.  Is this the list of the previous stream callback, its launch groups still cached, and no parameter or binding
+// change since?  Then the callback skips validation and works on the compact row mirror.
+bool stream_list_unchanged(const gas_ctx *c, const uint32_t *slots, uint32_t n, bool buses) {
+	const StreamState &s = c->streams;
+	return c->pending_free.empty() // a deferred free re-sorts the groups
+			&& s.rows.size() == n
+			&& (c->cached_n == n || (buses && s.bus_staged)) // the staged bus form regroups on every call and leaves no cached groups behind: its list stays "the same" without them
+			&& s.last_buses == buses
+			&& s.groups_gen == c->groups_gen
+			&& !s.params_touched
+			&& s.slots_host.size() == n
+			&& (n == 0 || std::memcmp(s.slots_host.data(), slots, (size_t)n * sizeof(uint32_t)) == 0);
+}
+
+// A new list: folds the old row mirror back into the cursors, checks the list, rebuilds the mirror and the list's
+// traits from the cursors, and uploads the slots and the resampled playbacks' steps.  Everything the callback can
+// reject its list for is checked BEFORE a cursor moves: the reference consumes a playback's frames only when it mixes
+// them (audio_spatializer.cpp:378), so a failed callback must leave the playback cursors (host mirror and device)
+// where they were.
+int stream_list_adopt(gas_ctx *c, const uint32_t *slots, uint32_t n, bool buses) {
+	StreamState &s = c->streams;
+	stream_rows_sync_back(c);
+	for (uint32_t i = 0; i < n; i++) {
+		if (!live(c, slots[i])) {
+			return GAS_ERR_BAD_SLOT;
+		}
+		const float pitch = c->slots[slots[i]].has_params ? c->h_params[slots[i]].pitch_scale : 1.0f;
+		if (!s.h_cursors[slots[i]].pcm) {
+			// bound to no stream: a fed row or silence.  pitch_scale is the sampler's input, and whoever decodes this
+			// playback has applied it already (the host layer hands it to the playback's mix callback), as for the
+			// rows of gas_process_block
+		} else if (s.h_cursors[slots[i]].resampled) {
+			if (!(pitch >= 0.0f && pitch < 32768.0f)) {
+				return GAS_ERR_INVALID_ARGUMENT;
+			}
+		} else if (pitch != 1.0f && pitch != 0.0f) {
+			return GAS_ERR_UNSUPPORTED_CHAIN; // a non-resampled playback class (gas_stream_set_resampled is off)
+		}
+	}
+	// what gas_process_block could still reject
+	c->stamp.next();
+	for (uint32_t i = 0; i < n; i++) {
+		const SlotInfo &si = c->slots[slots[i]];
+		if (!si.has_params) {
+			return GAS_ERR_NO_PARAMS;
+		}
+		if (c->stamp.seen(slots[i])) {
+			return GAS_ERR_INVALID_ARGUMENT; // one playback twice in a callback
+		}
+		const bool wants_hrtf = si.group == G_FX_HRTF || si.group == G_FX_ER_HRTF || (si.group == G_FX_GENERIC && chain_has(si.chain_sig, GAS_FX_HRTF));
+		if (wants_hrtf && c->tab.spec == nullptr) {
+			return GAS_ERR_NO_HRTF;
+		}
+	}
+	if (buses && bus_list_form(c, slots, n) == BUS_LIST_NEITHER) {
+		return GAS_ERR_UNSUPPORTED_CHAIN; // process_block_buses would, after the cursors have moved
+	}
+	s.last_buses = buses;
+	s.bus_staged = false;
+	s.params_touched = false;
+	s.slots_host.assign(slots, slots + n);
+	s.rows.resize(n);
+	s.list = StreamListTraits{};
+	s.list.all_hrtf = n > 0;
+	for (uint32_t i = 0; i < n; i++) {
+		const gas_cursor &cur = s.h_cursors[slots[i]];
+		s.list.any_adpcm = s.list.any_adpcm || (cur.pcm && (cur.format_channels >> 8) == GAS_PCM_IMA_ADPCM);
+		s.list.any_qoa = s.list.any_qoa || (cur.pcm && (cur.format_channels >> 8) == GAS_PCM_QOA);
+		StreamRow &r = s.rows[i];
+		r.remaining = cur.pcm && cur.frames > cur.pos ? cur.frames - cur.pos : 0;
+		r.has_frames = cur.pcm ? cur.has_frames : 0;
+		r.resampled = cur.pcm ? cur.resampled : 0;
+		r.looped = cur.pcm && cur.loop_mode ? 1 : 0;
+		r.pos = cur.pos;
+		s.list.any_looped = s.list.any_looped || r.looped;
+		r.inc = 65536;
+		if (r.resampled) {
+			// [ENGINE] mix_increment = uint64((stream_rate * rate_scale / mix_rate) * FP_LEN), stream at the mix rate
+			const float pitch = c->slots[slots[i]].has_params ? c->h_params[slots[i]].pitch_scale : 1.0f;
+			r.inc = (uint32_t)(uint64_t)(((double)(c->cfg.mix_rate * pitch) / (double)c->cfg.mix_rate) * 65536.0);
+			r.fp_pos = cur.fp_pos;
+			r.end_fp = cur.frames << 16;
+			s.list.any_resampled = true;
+		}
+		s.h_inc[i] = r.inc;
+		s.list.all_hrtf = s.list.all_hrtf && c->slots[slots[i]].group == G_FX_HRTF;
+	}
+	if (s.list.any_resampled) {
+		GAS_HIP(c, hipMemcpyAsync(s.d_inc, s.h_inc, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+		GAS_HIP(c, hipStreamSynchronize(c->stream)); // the pinned staging array is rewritten by the next list
+	}
+	if (n > 0) {
+		GAS_HIP(c, hipMemcpyAsync(s.d_slots, s.slots_host.data(), (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+	}
+	return GAS_OK;
+}
+
+// One row's share of a callback of F frames: the same arithmetic as k_sample_sources.  (Inlined into stream_advance's
+// loop: no call per row.)
+inline void stream_row_advance(StreamRow &r, uint32_t F) {
+	if (r.has_frames && r.resampled) { // k_sample_sources' resampled branch
+		uint64_t mixed = F;
+		if (r.looped) {
+			// never runs out
+		} else if (r.fp_pos >= r.end_fp) {
+			mixed = 0;
+		} else if (r.inc > 0) {
+			const uint64_t need = (r.end_fp - r.fp_pos + r.inc - 1) / r.inc;
+			mixed = need < F ? need : F;
+		}
+		r.fp_pos += (uint64_t)F * r.inc;
+		if (mixed != F) {
+			r.has_frames = 0;
+		}
+	} else if (r.has_frames && r.looped) {
+		r.pos += F;
+	} else if (r.has_frames) {
+		const uint32_t mixed = r.remaining < F ? (uint32_t)r.remaining : F;
+		r.remaining -= mixed;
+		if (mixed != F) {
+			r.has_frames = 0;
+		}
+	}
+}
+
+// The host mirror of one callback's cursor arithmetic: which playbacks end inside this callback
+// (audio_spatializer.cpp:380,398), the caller's has_frames, the draining marks, and the feed words.  Which entries take
+// a fed row is this callback's matter alone, read from the pending rows and never from the cached list -- the steady
+// state holds whatever is fed, not fed, or fed again under it.  Sets draining_changed when a playback that ended makes
+// its slot draining (the launch groups must be rebuilt), any_fed when an entry takes a fed row (feed.entry holds this
+// callback's words).  One loop over the rows: in the steady state it is the host cost of a stream callback.
+void stream_advance(gas_ctx *c, const uint32_t *slots, uint32_t n, uint8_t *has_frames, bool &draining_changed, bool &any_fed) {
+	FeedState &f = c->feed;
+	const uint32_t F = c->cfg.frames;
+	const bool feed_pending = !f.slots.empty();
+	if (feed_pending) {
+		f.entry.assign(n, GAS_FEED_NONE);
+	}
+	for (uint32_t i = 0; i < n; i++) {
+		StreamRow &r = c->streams.rows[i];
+		if (feed_pending && f.word[slots[i]] != GAS_FEED_NONE) { // a live playback without a cursor: nothing moves, nothing ends
+			f.entry[i] = f.word[slots[i]];
+			any_fed = true;
+			r.draining_marked = 0; // the next callback that finds it unfed marks it draining again
+			if (has_frames) {
+				has_frames[i] = 1;
+			}
+			continue;
+		}
+		stream_row_advance(r, F);
+		if (!r.has_frames && !r.draining_marked) {
+			r.draining_marked = 1;
+			if (!c->slots[slots[i]].draining) {
+				c->slots[slots[i]].draining = 1; // from now on the gate reads its peak (:464)
+				draining_changed = true;
+			}
+		}
+		if (has_frames) {
+			has_frames[i] = (uint8_t)r.has_frames;
+		}
+	}
+}
+
+// The feed table's header follows the list and the fed set: uploads this callback's words when they differ from the
+// words it holds.  Then the pending rows are spent -- one feed serves one callback; rows of slots the list does not
+// name go with it.  (A failed upload spends nothing.)
+int feed_serve(gas_ctx *c, uint32_t n, bool any_fed) {
+	FeedState &f = c->feed;
+	if (any_fed && f.entry != f.entry_dev) {
+		f.entry_dev.clear(); // until the upload is queued the header counts as unknown
+		GAS_HIP(c, hipEventSynchronize(f.entry_ev)); // the previous header has left the pinned words: a wait only while that upload is still queued
+		std::memcpy(f.h_entry, f.entry.data(), (size_t)n * sizeof(uint32_t));
+		GAS_HIP(c, hipMemcpyAsync(f.d_table, f.h_entry, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+		GAS_HIP(c, hipEventRecord(f.entry_ev, c->stream));
+		f.entry_dev = f.entry;
+	}
+	if (!f.slots.empty()) {
+		for (uint32_t s : f.slots) {
+			f.word[s] = GAS_FEED_NONE;
+		}
+		f.slots.clear();
+		f.used = 0;
+	}
+	return GAS_OK;
+}
+
+// May the HRTF launch sample the list's windows itself (k_hrtf_ols / k_hrtf_uni<SRC_PCM>), so that no rows are staged?
+bool stream_fuses(const gas_ctx *c, bool buses, bool any_fed) {
+	const StreamListTraits &l = c->streams.list;
+	// the fused prologues sample plain playbacks only: every chain a plain [HRTF], every stream uncompressed and at the
+	// mix rate (a resampled, GAS_PCM_IMA_ADPCM or GAS_PCM_QOA playback samples rows first)
+	const bool plain = l.all_hrtf && !l.any_resampled && !l.any_adpcm && !l.any_qoa;
+	// GAS_FLAG_HRTF_BLEND_FADE: the stream-sampling form has no registers left for the fade
+	const bool fade_free = !fade_on(c);
+	// gas_stream_set_loop: the cross-fade form has no registers left for the looped branch either
+	const bool loops_fused = !l.any_looped || (c->cfg.flags & GAS_FLAG_HRTF_CROSSFADE) == 0;
+	// buses: the fused form is k_hrtf_uni<SRC_PCM, BUS2>, which gas_process_block_buses picks on a one-pair context without a k_hrtf_ols-only mode
+	const bool bus_fusable = !buses || (c->cfg.channel_count == 1 && uni_ok(c) && gas_hrtf_uni_waves() == 8);
+	// gas_source_feed_rows: k_hrtf_uni<SRC_PCM> and k_hrtf_uni<SRC_PCM, BUS2> take fed entries; the k_hrtf_ols stream-sampling forms -- cross-fade, direction runs / order, interpolation contexts -- have no registers left for them
+	const bool fed_fusable = !any_fed || uni_ok(c);
+	return plain && fade_free && loops_fused && !c->streams.rows_first && bus_fusable && fed_fusable;
+}
+
+// Rows first: the windows of the list's n playbacks into d_src -- k_sample_sources, then the decoders of the compressed
+// streams the list holds.
+int stream_sample_rows(gas_ctx *c, uint32_t n, const uint8_t *feed) {
+	const StreamState &s = c->streams;
+	const uint32_t F = c->cfg.frames;
+	if (ensure_src(c, (size_t)n * F) != hipSuccess) {
+		return GAS_ERR_OUT_OF_MEMORY;
+	}
+	if (n == 0) {
+		return GAS_OK;
+	}
+	const uint32_t *inc = s.list.any_resampled ? s.d_inc : nullptr;
+	GAS_HIP(c, gas_launch_sample_sources(c->stream, s.d_cursors, s.d_slots, n, F, c->d_fade_env, c->d_src, inc, feed));
+	if (s.list.any_adpcm) {
+		GAS_HIP(c, gas_launch_sample_adpcm(c->stream, s.d_cursors, s.d_slots, n, F, c->d_fade_env, c->d_src, inc, s.adpcm_span));
+	}
+	if (s.list.any_qoa) {
+		GAS_HIP(c, gas_launch_sample_qoa(c->stream, s.d_cursors, s.d_slots, n, F, c->d_fade_env, c->d_src, inc, s.qoa_span));
+	}
+	return GAS_OK;
+}
+
+// The body of both stream entries: the steps above, then gas_process_block[_buses]' device path over the windows (a
+// host `out`: into the library's buffers, one copy back).
+int stream_body(gas_ctx *c, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, size_t out_bytes, uint32_t n_buses, bool buses, float *peaks, uint8_t *has_frames, int mem) {
+	const uint32_t F = c->cfg.frames;
+	GAS_TRY(callback_begin(c, frames));
+	adopt_frees(c);
+	bool same_list = stream_list_unchanged(c, slots, n, buses);
+	if (!same_list) {
+		GAS_TRY(stream_list_adopt(c, slots, n, buses));
+	}
+	bool draining_changed = false, any_fed = false;
+	stream_advance(c, slots, n, has_frames, draining_changed, any_fed);
+	if (draining_changed) {
+		c->cached_n = UINT32_MAX;
+		same_list = false;
+	}
+	GAS_TRY(feed_serve(c, n, any_fed));
+	const uint8_t *feed = any_fed ? c->feed.d_table : nullptr;
+	const bool fused = c->streams.last_fused = stream_fuses(c, buses, any_fed);
+	RowSource rows;
+	if (fused) { // no float rows: the HRTF launch samples the bound streams (and the fed rows) itself
+		rows.cursors = c->streams.d_cursors;
+		rows.feed = feed;
+	} else {
+		GAS_TRY(stream_sample_rows(c, n, feed));
+		rows.rows = c->d_src;
+	}
+	gas_audio_frame *d_out = out;
+	float *d_pk = peaks;
+	if (mem == GAS_MEM_HOST) {
+		GAS_TRY(stage_host(c, nullptr, n, buses, d_out, d_pk));
+	}
+	int rc = GAS_OK;
+	if (buses) {
+		// gas_process_block_buses reuses a list only for its 3D-mix and fused [HRTF] forms; the staged form needs it every time
+		const bool reuse = same_list && n > 0 && c->cached_n == n && c->bus_form_cached != 0 && c->bus_form_groups_gen == c->groups_gen;
+		rc = process_block_buses(c, rows, reuse ? nullptr : slots, n, F, d_out, n_buses, d_pk, GAS_MEM_DEVICE);
+		c->streams.bus_staged = rc == GAS_OK && n > 0 && c->cached_n != n; // ran staged: nothing cached to compare with next time
+	} else {
+		rc = process_block(c, rows, same_list ? nullptr : slots, n, F, d_out, d_pk, GAS_MEM_DEVICE);
+	}
+	c->streams.groups_gen = rc == GAS_OK ? c->groups_gen : UINT64_MAX;
+	GAS_TRY(rc);
+	if (mem == GAS_MEM_DEVICE) {
+		return GAS_OK;
+	}
+	if (!buses) {
+		GAS_TRY(join_outputs(c));
+	}
+	GAS_HIP(c, copy_back(c, out, d_out, out_bytes, peaks, n));
+	return GAS_OK;
+}
+
+// Both stream entries.  !buses: gas_process_block_streams (one mix, out [C][frames], n_buses unused); buses:
+// gas_process_block_streams_buses (out [n_buses][C][frames]).
+int process_block_streams(gas_ctx *c, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, uint32_t n_buses, bool buses, float *peaks, uint8_t *has_frames, int mem) {
+	if (!c || !out || (n > 0 && !slots) || n > c->cfg.max_sources || (mem != GAS_MEM_HOST && mem != GAS_MEM_DEVICE)) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	const size_t bus_bytes = (size_t)c->cfg.channel_count * c->cfg.frames * sizeof(gas_audio_frame);
+	if (buses && (n_buses < 1 || n_buses > GAS_MAX_BUSES)) { // zeroes as much of `out` as a legal call could name
+		return fail_out(GAS_ERR_INVALID_ARGUMENT, mem, out, (n_buses < GAS_MAX_BUSES ? n_buses : GAS_MAX_BUSES) * bus_bytes);
+	}
+	GAS_TRY(flush_deferred(c)); // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
+	const size_t out_bytes = (buses ? n_buses : 1u) * bus_bytes;
+	return fail_out(stream_body(c, slots, n, frames, out, out_bytes, n_buses, buses, peaks, has_frames, mem), mem, out, out_bytes);
+}
+
+} // namespace
+
+extern "C" {
+
+int gas_process_block(gas_ctx *c, const gas_audio_frame *src, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, float *peaks, int mem) {
+	if (!c || !out || (mem != GAS_MEM_HOST && mem != GAS_MEM_DEVICE) || (n > 0 && !src) || n > c->cfg.max_sources) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	return fail_out(process_block(c, RowSource{ src }, slots, n, frames, out, peaks, mem), mem, out, (size_t)c->cfg.channel_count * c->cfg.frames * sizeof(gas_audio_frame));
+}
+
+int gas_bus_routes_publish(gas_ctx *c, const uint32_t *slots, const gas_bus_route *routes, uint32_t n) {
+	if (!c || (n > 0 && (!slots || !routes))) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	for (uint32_t i = 0; i < n; i++) {
+		if (slots[i] >= c->cfg.max_sources || !c->slots[slots[i]].used) {
+			return GAS_ERR_BAD_SLOT;
+		}
+	}
+	std::lock_guard<std::mutex> lk(c->params_mu);
+	for (uint32_t i = 0; i < n; i++) {
+		c->h_routes[slots[i]] = routes[i];
+	}
+	c->routes_dirty = true;
+	return GAS_OK;
+}
+
+int gas_process_block_buses(gas_ctx *c, const gas_audio_frame *src, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, uint32_t n_buses, float *peaks, int mem) {
+	if (!c || !out || (mem != GAS_MEM_HOST && mem != GAS_MEM_DEVICE) || (n > 0 && !src) || n > c->cfg.max_sources || n_buses < 1 || n_buses > GAS_MAX_BUSES) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	return process_block_buses(c, RowSource{ src }, slots, n, frames, out, n_buses, peaks, mem);
+}
+
+int gas_process_block_streams(gas_ctx *c, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, float *peaks, uint8_t *has_frames, int mem) {
+	return process_block_streams(c, slots, n, frames, out, 0, false, peaks, has_frames, mem);
+}
+
+int gas_process_block_streams_buses(gas_ctx *c, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, uint32_t n_buses, float *peaks, uint8_t *has_frames, int mem) {
+	return process_block_streams(c, slots, n, frames, out, n_buses, true, peaks, has_frames, mem);
+}
+
+int gas_stream_last_fused(gas_ctx *c) {
+	return c ? (c->streams.last_fused ? 1 : 0) : GAS_ERR_INVALID_ARGUMENT;
 }
 
 int gas_process_frames_1(gas_ctx *c, uint32_t slot, gas_audio_frame *out, const gas_audio_frame *src, int frame_count) {

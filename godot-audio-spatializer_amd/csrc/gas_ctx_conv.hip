@@ -498,9 +498,9 @@ static int conv_ir_from_plan(gas_ctx *c, const gas_room_ir &desc, const gas_room
 		GAS_HIP(c, tmp.alloc(d_hrir, floats));
 		GAS_HIP(c, hipMemcpy(d_hrir, set->hrir, floats * sizeof(float), hipMemcpyHostToDevice));
 	}
-	const bool timed = c->profiling && c->ev_used + 2 <= c->ev.size(); // gas_profile_enable: the generator's launches count as a dominant launch
+	const bool timed = c->prof.room(); // gas_profile_enable: the generator's launches count as a dominant launch
 	if (timed) {
-		GAS_HIP(c, hipEventRecord(c->ev[c->ev_used], c->stream));
+		GAS_HIP(c, c->prof.begin(c->stream));
 	}
 	if (set) {
 		GAS_HIP(c, gas_launch_room_ir_hrtf(c->stream, plan, desc, d_tables, d_hrir, set->n_az, set->n_el, set->taps, d_acc, d_ir));
@@ -508,8 +508,7 @@ static int conv_ir_from_plan(gas_ctx *c, const gas_room_ir &desc, const gas_room
 		GAS_HIP(c, gas_launch_room_ir(c->stream, plan, d_tables, d_acc, d_ir));
 	}
 	if (timed) {
-		GAS_HIP(c, hipEventRecord(c->ev[c->ev_used + 1], c->stream));
-		c->ev_used += 2;
+		GAS_HIP(c, c->prof.end(c->stream));
 	}
 	if (out_ir) { // waits for the stream
 		uint32_t id = 0;

@@ -67,12 +67,12 @@ int gas_profile_enable(gas_ctx *c, int on) {
 		}
 	}
 	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	if (on && c->ev.empty()) {
+	if (on && c->prof.ev.empty()) {
 		std::vector<hipEvent_t> ev(PROFILE_EVENTS, nullptr);
 		for (hipEvent_t &e : ev) {
-			GAS_HIP(c, c->mem.make_event(e, hipEventDefault)); // a failure leaves c->ev empty and what exists to the owner
+			GAS_HIP(c, c->mem.make_event(e, hipEventDefault)); // a failure leaves c->prof.ev empty and what exists to the owner
 		}
-		c->ev = std::move(ev);
+		c->prof.ev = std::move(ev);
 	}
 	if (on) {
 		// An event pair around a launch reads the launch's span on the GPU timeline plus the cost of the second
@@ -82,18 +82,18 @@ int gas_profile_enable(gas_ctx *c, int on) {
 		GAS_HIP(c, hipStreamSynchronize(c->stream));
 		double best = 1e9;
 		for (int i = 0; i < 16; i++) {
-			GAS_HIP(c, hipEventRecord(c->ev[0], c->stream));
-			GAS_HIP(c, hipEventRecord(c->ev[1], c->stream));
-			GAS_HIP(c, hipEventSynchronize(c->ev[1]));
+			GAS_HIP(c, hipEventRecord(c->prof.ev[0], c->stream));
+			GAS_HIP(c, hipEventRecord(c->prof.ev[1], c->stream));
+			GAS_HIP(c, hipEventSynchronize(c->prof.ev[1]));
 			float ms = 0.0f;
-			GAS_HIP(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+			GAS_HIP(c, hipEventElapsedTime(&ms, c->prof.ev[0], c->prof.ev[1]));
 			best = ms < best ? ms : best;
 		}
-		c->ev_overhead_ms = best;
+		c->prof.ev_overhead_ms = best;
 	}
-	c->profiling = on != 0;
-	c->prof_every = on > 1 ? (uint32_t)on : 1; // on = N > 1: bracket every Nth callback only (the markers cost throughput)
-	c->prof_tick = 0;
+	c->prof.on = on != 0;
+	c->prof.every = on > 1 ? (uint32_t)on : 1; // on = N > 1: bracket every Nth callback only (the markers cost throughput)
+	c->prof.tick = 0;
 	return GAS_OK;
 }
 
@@ -109,29 +109,29 @@ int gas_profile_read(gas_ctx *c, gas_profile *out, int reset) {
 	}
 	GAS_HIP(c, hipSetDevice(c->cfg.device));
 	GAS_HIP(c, hipStreamSynchronize(c->stream));
-	for (uint32_t i = 0; i + 1 < c->ev_used; i += 2) {
+	for (uint32_t i = 0; i + 1 < c->prof.ev_used; i += 2) {
 		float ms = 0.0f;
-		GAS_HIP(c, hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]));
-		c->prof_ms += ms > c->ev_overhead_ms ? ms - c->ev_overhead_ms : 0.0;
-		c->prof_launches++;
+		GAS_HIP(c, hipEventElapsedTime(&ms, c->prof.ev[i], c->prof.ev[i + 1]));
+		c->prof.ms += ms > c->prof.ev_overhead_ms ? ms - c->prof.ev_overhead_ms : 0.0;
+		c->prof.launches++;
 	}
-	c->ev_used = 0;
+	c->prof.ev_used = 0;
 	std::memset(out, 0, sizeof(*out));
-	out->launches = c->prof_launches;
-	out->kernel_ms = c->prof_ms;
-	out->bytes_per_launch = c->prof_bytes;
-	out->callbacks_per_launch = c->prof_k;
-	out->bytes_per_callback_formula = c->prof_k > 1 ? c->prof_bytes_formula : c->prof_bytes;
-	if (c->prof_group >= 0) {
-		std::string name = c->prof_multi ? "k_hrtf_multi" : (c->prof_uni ? "k_hrtf_uni" : k_group_kernel[c->prof_group]);
-		if (c->prof_pipe && name.rfind("k_biquad_mix", 0) == 0) {
+	out->launches = c->prof.launches;
+	out->kernel_ms = c->prof.ms;
+	out->bytes_per_launch = c->prof.bytes;
+	out->callbacks_per_launch = c->prof.k;
+	out->bytes_per_callback_formula = c->prof.k > 1 ? c->prof.bytes_formula : c->prof.bytes;
+	if (c->prof.group >= 0) {
+		std::string name = c->prof.multi ? "k_hrtf_multi" : (c->prof.uni ? "k_hrtf_uni" : k_group_kernel[c->prof.group]);
+		if (c->prof.pipe && name.rfind("k_biquad_mix", 0) == 0) {
 			name = "k_biquad_pipe" + name.substr(12);
 		}
 		std::strncpy(out->kernel_name, name.c_str(), sizeof(out->kernel_name) - 1);
 	}
 	if (reset) {
-		c->prof_launches = 0;
-		c->prof_ms = 0.0;
+		c->prof.launches = 0;
+		c->prof.ms = 0.0;
 	}
 	return GAS_OK;
 }

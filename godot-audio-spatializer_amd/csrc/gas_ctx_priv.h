@@ -191,6 +191,100 @@ struct ProbeState {
 	float *d_sink = nullptr;
 };
 
+// device-resident streams and playback cursors: the streams, each playback's cursor, and what the
+// stream callbacks (gas_ctx.hip) keep of their last list.  Audio-thread state.
+struct StreamInfo {
+	void *d_pcm = nullptr;
+	uint64_t frames = 0;
+	uint32_t format = 0, channels = 0;
+	bool resampled = false; // its playbacks are [ENGINE] AudioStreamPlaybackResampled (gas_stream_set_resampled)
+	uint32_t loop_mode = 0; // NEW gas_stream_set_loop: its playbacks repeat [loop_begin, loop_end)
+	uint64_t loop_begin = 0, loop_end = 0;
+};
+struct StreamRow { // compact mirror of the cached list's cursors: the per-callback host loop touches only this
+	uint64_t remaining = 0;
+	uint32_t has_frames = 0, draining_marked = 0;
+	uint32_t resampled = 0, inc = 65536; // resampled playbacks: 16.16 step of this callback (from the host-published pitch_scale)
+	uint64_t fp_pos = 0, end_fp = 0; // ... and the engine's mix_offset / the stream's end, 16.16
+	uint32_t looped = 0; // gas_stream_set_loop: never ends; a plain playback counts `pos` up instead of `remaining` down
+	uint64_t pos = 0;
+};
+struct StreamListTraits { // of the cached list, rebuilt with it (stream_list_adopt)
+	bool all_hrtf = false; // every playback a plain [HRTF] chain
+	bool any_resampled = false;
+	bool any_looped = false;
+	bool any_adpcm = false; // a GAS_PCM_IMA_ADPCM playback: rows first, k_sample_adpcm behind k_sample_sources
+	bool any_qoa = false; // a GAS_PCM_QOA playback: rows first, k_sample_qoa behind k_sample_sources
+};
+struct StreamState {
+	std::vector<StreamInfo> info; // by stream id; d_pcm null: a free id
+	gas_cursor *d_cursors = nullptr; // [max_sources]
+	std::vector<gas_cursor> h_cursors; // host mirror of the cursor arithmetic (deterministic, no read-back)
+	uint32_t *d_slots = nullptr; // callback slot list in row order
+	uint32_t *d_inc = nullptr, *h_inc = nullptr; // [max_sources] 16.16 step per row (resampled playbacks)
+	std::vector<uint32_t> slots_host; // what d_slots / the cached launch groups currently hold
+	std::vector<StreamRow> rows;
+	StreamListTraits list;
+	uint64_t groups_gen = UINT64_MAX; // groups_gen the stream path's cached list corresponds to
+	bool last_fused = false; // the last stream callback that got as far as its launches sampled inside the HRTF kernel (gas_stream_last_fused)
+	bool last_buses = false; // the cached stream list was validated by gas_process_block_streams_buses (its checks differ from the mix entry's)
+	bool bus_staged = false; // ... and ran the staged bus form, which regroups on every call (cached_n never names it)
+	bool params_touched = false; // a parameter publish may have changed pitch_scale: re-validate
+	// development aids, read at context creation
+	bool rows_first = getenv("GAS_STREAM_ROWS_FIRST") != nullptr && atoi(getenv("GAS_STREAM_ROWS_FIRST")) != 0; // plain [HRTF] stream lists sample rows first too (tools/time_stream_loops.py compares the routes)
+	bool adpcm_span = getenv("GAS_ADPCM_SPAN") == nullptr || atoi(getenv("GAS_ADPCM_SPAN")) != 0; // 0 = every load decodes from its checkpoint (k_sample_adpcm.hip; tools/time_stream_adpcm.py and the tests compare the paths)
+	bool qoa_span = getenv("GAS_QOA_SPAN") == nullptr || atoi(getenv("GAS_QOA_SPAN")) != 0; // 0 = every load decodes from its record (k_sample_qoa.hip; tools/time_stream_qoa.py and the tests compare the paths)
+};
+
+// gas_source_feed_rows: window rows of playbacks that are not bound to a stream, pending for the next stream callback.
+// d_table is the feed table the kernels read (gas_internal.h, GAS_FEED_*): [max_sources] words in the callback's row
+// order, then two halves of max_sources rows: the rows of every call since the last callback, appended as they came
+// (feed_place).
+struct FeedState {
+	uint8_t *d_table = nullptr;
+	size_t used = 0; // end of the rows taken, as an offset into d_table (0: emptied)
+	uint32_t side = 0; // the half of the table that rows are appended in
+	std::vector<uint32_t> moved; // feed_place: (slot, new word) of the rows it moved to the other half
+	uint8_t *h_rows = nullptr; // pinned staging of one GAS_MEM_HOST call
+	size_t h_cap = 0;
+	hipEvent_t ev = nullptr; // the last upload out of h_rows
+	std::vector<uint32_t> word; // [max_sources] by slot: GAS_FEED_NONE, or where and in which format its pending row lies
+	std::vector<uint32_t> slots; // the slots with a pending row
+	std::vector<uint32_t> entry, entry_dev; // per list entry: this callback's words, and the words the table's header holds (empty: none written)
+	uint32_t *h_entry = nullptr; // [max_sources] pinned: what the header upload reads
+	hipEvent_t entry_ev = nullptr; // ... and the last upload out of it
+};
+
+// gas_profile_enable: event pairs around launches, and what the last timed launch was.
+struct ProfState {
+	bool on = false;
+	std::vector<hipEvent_t> ev;
+	uint32_t ev_used = 0;
+	double ev_overhead_ms = 0.0; // marker/dispatch overhead of an event pair around one launch (calibrated)
+	uint32_t every = 1, tick = 0; // bracket every Nth launch that asks
+	uint64_t launches = 0;
+	double ms = 0.0;
+	uint64_t bytes = 0, bytes_formula = 0;
+	uint32_t k = 1;
+	int group = -1;
+	bool uni = false, multi = false, pipe = false; // the timed launch was k_hrtf_uni / k_hrtf_multi / k_biquad_pipe
+	// The bracket of one launch: `timed = room() [&& due()]`, begin() in front of the launch, end() behind it.
+	bool room() const { // profiling, and two events are free
+		return on && ev_used + 2 <= ev.size();
+	}
+	bool due() { // this asker's turn; call it only where room() holds, it counts the askers
+		return (tick++ % every) == 0;
+	}
+	hipError_t begin(hipStream_t s) const {
+		return hipEventRecord(ev[ev_used], s);
+	}
+	hipError_t end(hipStream_t s) {
+		const hipError_t e = hipEventRecord(ev[ev_used + 1], s);
+		ev_used += e == hipSuccess ? 2 : 0;
+		return e;
+	}
+};
+
 } // namespace gas_priv
 using namespace gas_priv; // the units name these types and helpers as gas_ctx.hip always did
 
@@ -224,7 +318,6 @@ struct gas_ctx {
 	int bus_form_cached = 0; // form of the last gas_process_block_buses whose list can be reused: 1 3D mix, 2 fused [HRTF], 0 none
 	uint64_t bus_form_groups_gen = 0;
 	uint32_t partial_planes = 1; // planes of d_partials (1 ordered, 2 pipelined, 2 x max batch depth batched)
-	bool prof_multi = false; // the timed launch was k_hrtf_multi
 	uint32_t hist_len = 0;
 	gas_dev_state st{};
 	gas_hrtf_table tab{};
@@ -270,7 +363,6 @@ struct gas_ctx {
 	bool order_ok[G_COUNT] = {}; // d_order holds this group's order
 	uint32_t xcd_order_auto_min = GAS_XCD_ORDER_AUTO_MIN; // GAS_XCD_ORDER_AUTO_MIN in the environment overrides (experiments)
 	bool last_uni_ordered = false; // the last k_hrtf_uni launch ran in k_xcd_order's order
-	uint64_t stream_groups_gen = UINT64_MAX; // groups_gen the stream path's cached list corresponds to
 	bool cached_identity_rows = true;
 	Group groups[G_COUNT];
 	std::vector<ChainRange> chain_ranges; // sub-runs of groups[G_FX_GENERIC], cached with the groups
@@ -290,62 +382,12 @@ struct gas_ctx {
 	// one-source compatibility path
 	uint32_t *d_one_slot = nullptr;
 
-	// device-resident streams and playback cursors
-	struct StreamInfo {
-		void *d_pcm = nullptr;
-		uint64_t frames = 0;
-		uint32_t format = 0, channels = 0;
-		bool resampled = false; // its playbacks are [ENGINE] AudioStreamPlaybackResampled (gas_stream_set_resampled)
-		uint32_t loop_mode = 0; // NEW gas_stream_set_loop: its playbacks repeat [loop_begin, loop_end)
-		uint64_t loop_begin = 0, loop_end = 0;
-	};
-	std::vector<StreamInfo> streams;
-	gas_cursor *d_cursors = nullptr; // [max_sources]
-	std::vector<gas_cursor> h_cursors; // host mirror of the cursor arithmetic (deterministic, no read-back)
+	StreamState streams;
 	float *d_fade_env = nullptr; // [64]
-	uint32_t *d_stream_slots = nullptr; // callback slot list in row order
-	uint32_t *d_stream_inc = nullptr, *h_stream_inc = nullptr; // [max_sources] 16.16 step per row (resampled playbacks)
-	bool stream_any_resampled = false;
-	std::vector<uint32_t> stream_slots_host; // what d_stream_slots / the cached launch groups currently hold
 	// parameter rows published from device memory for the cached slot list (row order), not yet in the table
 	const gas_params *pending_params = nullptr;
 	uint32_t pending_n = 0;
-	struct StreamRow { // compact mirror of the cached list's cursors: the per-callback host loop touches only this
-		uint64_t remaining = 0;
-		uint32_t has_frames = 0, draining_marked = 0;
-		uint32_t resampled = 0, inc = 65536; // resampled playbacks: 16.16 step of this callback (from the host-published pitch_scale)
-		uint64_t fp_pos = 0, end_fp = 0; // ... and the engine's mix_offset / the stream's end, 16.16
-		uint32_t looped = 0; // gas_stream_set_loop: never ends; a plain playback counts `pos` up instead of `remaining` down
-		uint64_t pos = 0;
-	};
-	std::vector<StreamRow> stream_rows;
-	bool stream_all_hrtf = false;
-	bool stream_last_fused = false; // the last stream callback that got as far as its launches sampled inside the HRTF kernel (gas_stream_last_fused)
-	bool stream_last_buses = false; // the cached stream list was validated by gas_process_block_streams_buses (its checks differ from the mix entry's)
-	bool stream_bus_staged = false; // ... and ran the staged bus form, which regroups on every call (cached_n never names it)
-	bool stream_rows_first = getenv("GAS_STREAM_ROWS_FIRST") != nullptr && atoi(getenv("GAS_STREAM_ROWS_FIRST")) != 0; // development aid: plain [HRTF] stream lists sample rows first too (tools/time_stream_loops.py compares the routes)
-	bool stream_any_looped = false;
-	bool stream_any_adpcm = false; // the list holds a GAS_PCM_IMA_ADPCM playback: rows first, k_sample_adpcm behind k_sample_sources
-	bool adpcm_span = getenv("GAS_ADPCM_SPAN") == nullptr || atoi(getenv("GAS_ADPCM_SPAN")) != 0; // development aid: 0 = every load decodes from its checkpoint (k_sample_adpcm.hip; tools/time_stream_adpcm.py and the tests compare the paths)
-	bool stream_any_qoa = false; // the list holds a GAS_PCM_QOA playback: rows first, k_sample_qoa behind k_sample_sources
-	bool qoa_span = getenv("GAS_QOA_SPAN") == nullptr || atoi(getenv("GAS_QOA_SPAN")) != 0; // development aid: 0 = every load decodes from its record (k_sample_qoa.hip; tools/time_stream_qoa.py and the tests compare the paths)
-	bool stream_params_touched = false; // a parameter publish may have changed pitch_scale: re-validate
-	// gas_source_feed_rows: window rows of playbacks that are not bound to a stream, pending for the next stream callback.
-	// d_feed is the feed table the kernels read (gas_internal.h, GAS_FEED_*): [max_sources] words in the callback's row
-	// order, then two halves of max_sources rows: the rows of every call since the last callback, appended as they came
-	// (feed_place).
-	uint8_t *d_feed = nullptr;
-	size_t feed_used = 0; // end of the rows taken, as an offset into d_feed (0: emptied)
-	uint32_t feed_side = 0; // the half of the table that rows are appended in
-	std::vector<uint32_t> feed_moved; // feed_place: (slot, new word) of the rows it moved to the other half
-	uint8_t *h_feed = nullptr; // pinned staging of one GAS_MEM_HOST call
-	size_t h_feed_cap = 0;
-	hipEvent_t feed_ev = nullptr; // the last upload out of h_feed
-	std::vector<uint32_t> feed_word; // [max_sources] by slot: GAS_FEED_NONE, or where and in which format its pending row lies
-	std::vector<uint32_t> feed_slots; // the slots with a pending row
-	std::vector<uint32_t> feed_entry, feed_entry_dev; // per list entry: this callback's words, and the words the table's header holds (empty: none written)
-	uint32_t *h_feed_entry = nullptr; // [max_sources] pinned: what the header upload reads
-	hipEvent_t feed_entry_ev = nullptr; // ... and the last upload out of it
+	FeedState feed;
 
 	CalcState calc;
 
@@ -360,15 +402,7 @@ struct gas_ctx {
 	ConvState conv;
 	ProbeState probe;
 
-	bool profiling = false;
-	std::vector<hipEvent_t> ev;
-	uint32_t ev_used = 0;
-	uint64_t prof_launches = 0;
-	double prof_ms = 0.0;
-	uint64_t prof_bytes = 0, prof_bytes_formula = 0;
-	uint32_t prof_k = 1;
-	int prof_group = -1;
-	bool prof_uni = false; // the timed launch was k_hrtf_uni
+	ProfState prof;
 	bool uni_flt_enabled = getenv("GAS_UNI_FLT") == nullptr || atoi(getenv("GAS_UNI_FLT")) != 0; // [filter, HRTF] through k_hrtf_uni<FLT> (0: the filter stage and the HRTF stage as two launches, for comparison)
 	// [ER, HRTF] through k_hrtf_uni<ER>.  GAS_UNI_ER = 1 (default): when at most a quarter of the callback's playbacks want
 	// their exact peak.  In throughput mode it is the faster form (the launch carries the previous callback's sum, which
@@ -378,9 +412,6 @@ struct gas_ctx {
 	// [ER, HRTF] take it whenever it is not 0 (one launch less, no rows in between).
 	int uni_er_mode = getenv("GAS_UNI_ER") ? atoi(getenv("GAS_UNI_ER")) : 1;
 	bool uni_er_enabled = uni_er_mode != 0;
-	bool prof_pipe = false; // the timed launch was k_biquad_pipe
-	double ev_overhead_ms = 0.0; // marker/dispatch overhead of an event pair around one launch (calibrated)
-	uint32_t prof_every = 1, prof_tick = 0; // bracket every Nth callback's dominant launch
 
 	std::string last_err;
 };

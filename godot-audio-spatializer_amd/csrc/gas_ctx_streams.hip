@@ -17,40 +17,40 @@ inline size_t feed_header_bytes(const gas_ctx *c) {
 // switches halves once its own copy is enqueued.
 int feed_place(gas_ctx *c, size_t bytes, size_t &at, bool &switched) {
 	const size_t hdr = feed_header_bytes(c), half = (size_t)c->cfg.max_sources * c->cfg.frames * sizeof(gas_audio_frame);
-	if (!c->d_feed) {
-		if (alloc_once(c, c->h_feed_entry, c->cfg.max_sources, Mem::PINNED) != hipSuccess) {
+	if (!c->feed.d_table) {
+		if (alloc_once(c, c->feed.h_entry, c->cfg.max_sources, Mem::PINNED) != hipSuccess) {
 			return GAS_ERR_OUT_OF_MEMORY;
 		}
-		if (!c->feed_entry_ev) {
-			GAS_HIP(c, c->mem.make_event(c->feed_entry_ev, hipEventDisableTiming));
+		if (!c->feed.entry_ev) {
+			GAS_HIP(c, c->mem.make_event(c->feed.entry_ev, hipEventDisableTiming));
 		}
-		if (c->mem.alloc(c->d_feed, hdr + 2 * half) != hipSuccess) {
+		if (c->mem.alloc(c->feed.d_table, hdr + 2 * half) != hipSuccess) {
 			return GAS_ERR_OUT_OF_MEMORY;
 		}
-		c->feed_used = 0;
+		c->feed.used = 0;
 	}
-	if (c->feed_used < hdr) { // emptied by a callback: start over
-		c->feed_used = hdr;
-		c->feed_side = 0;
+	if (c->feed.used < hdr) { // emptied by a callback: start over
+		c->feed.used = hdr;
+		c->feed.side = 0;
 	}
-	c->feed_moved.clear();
+	c->feed.moved.clear();
 	switched = false;
-	if (c->feed_used + bytes <= hdr + (c->feed_side + 1) * half) {
-		at = c->feed_used;
+	if (c->feed.used + bytes <= hdr + (c->feed.side + 1) * half) {
+		at = c->feed.used;
 		return GAS_OK;
 	}
 	switched = true;
 	const uint32_t F = c->cfg.frames;
-	size_t off = hdr + (1 - c->feed_side) * half;
-	for (uint32_t s : c->feed_slots) {
+	size_t off = hdr + (1 - c->feed.side) * half;
+	for (uint32_t s : c->feed.slots) {
 		if (c->stamp.has(s)) {
 			continue; // this call replaces it
 		}
-		const uint32_t w = c->feed_word[s];
+		const uint32_t w = c->feed.word[s];
 		const size_t rb = gas_feed_row_bytes(w, F);
-		GAS_HIP(c, hipMemcpyAsync(c->d_feed + off, c->d_feed + gas_feed_offset(w), rb, hipMemcpyDeviceToDevice, c->stream));
-		c->feed_moved.push_back(s);
-		c->feed_moved.push_back(gas_feed_word(off, (w & 2u) ? GAS_PCM_F32 : GAS_PCM_S16, (w & 1u) + 1u));
+		GAS_HIP(c, hipMemcpyAsync(c->feed.d_table + off, c->feed.d_table + gas_feed_offset(w), rb, hipMemcpyDeviceToDevice, c->stream));
+		c->feed.moved.push_back(s);
+		c->feed.moved.push_back(gas_feed_word(off, (w & 2u) ? GAS_PCM_F32 : GAS_PCM_S16, (w & 1u) + 1u));
 		off += rb;
 	}
 	at = off;
@@ -103,7 +103,7 @@ int gas_stream_create(gas_ctx *c, const void *pcm, int format, uint32_t channels
 		gas_qoa_build_records(static_cast<const uint8_t *>(pcm), channels, frames, qoa.data()); // decodes once, keeping the state in front of every chunk
 		pcm = qoa.data();
 	}
-	gas_ctx::StreamInfo si;
+	StreamInfo si;
 	GAS_HIP(c, c->mem.alloc(si.d_pcm, bytes));
 	hipError_t e = hipMemcpy(si.d_pcm, pcm, bytes, hipMemcpyHostToDevice);
 	if (e != hipSuccess) {
@@ -114,15 +114,15 @@ int gas_stream_create(gas_ctx *c, const void *pcm, int format, uint32_t channels
 	si.frames = frames;
 	si.format = (uint32_t)format;
 	si.channels = channels;
-	for (size_t i = 0; i < c->streams.size(); i++) {
-		if (!c->streams[i].d_pcm) {
-			c->streams[i] = si;
+	for (size_t i = 0; i < c->streams.info.size(); i++) {
+		if (!c->streams.info[i].d_pcm) {
+			c->streams.info[i] = si;
 			*out_stream = (uint32_t)i;
 			return GAS_OK;
 		}
 	}
-	c->streams.push_back(si);
-	*out_stream = (uint32_t)c->streams.size() - 1;
+	c->streams.info.push_back(si);
+	*out_stream = (uint32_t)c->streams.info.size() - 1;
 	return GAS_OK;
 }
 
@@ -130,15 +130,15 @@ int gas_stream_set_resampled(gas_ctx *c, uint32_t stream, int on) {
 	if (!c) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
-	if (stream >= c->streams.size() || !c->streams[stream].d_pcm) {
+	if (stream >= c->streams.info.size() || !c->streams.info[stream].d_pcm) {
 		return GAS_ERR_BAD_SLOT;
 	}
-	for (const gas_cursor &cur : c->h_cursors) {
-		if (cur.pcm == c->streams[stream].d_pcm) {
+	for (const gas_cursor &cur : c->streams.h_cursors) {
+		if (cur.pcm == c->streams.info[stream].d_pcm) {
 			return GAS_ERR_INVALID_ARGUMENT; // the playback class is chosen before playbacks are bound
 		}
 	}
-	c->streams[stream].resampled = on != 0;
+	c->streams.info[stream].resampled = on != 0;
 	return GAS_OK;
 }
 
@@ -146,11 +146,11 @@ int gas_stream_set_loop(gas_ctx *c, uint32_t stream, int mode, uint64_t loop_beg
 	if (!c) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
-	if (stream >= c->streams.size() || !c->streams[stream].d_pcm) {
+	if (stream >= c->streams.info.size() || !c->streams.info[stream].d_pcm) {
 		return GAS_ERR_BAD_SLOT;
 	}
-	gas_ctx::StreamInfo &si = c->streams[stream];
-	for (const gas_cursor &cur : c->h_cursors) {
+	StreamInfo &si = c->streams.info[stream];
+	for (const gas_cursor &cur : c->streams.h_cursors) {
 		if (cur.pcm == si.d_pcm) {
 			return GAS_ERR_INVALID_ARGUMENT; // the loop is chosen before playbacks are bound
 		}
@@ -177,17 +177,17 @@ int gas_stream_get_loop(gas_ctx *c, uint32_t stream, int *out_mode, uint64_t *ou
 	if (!c) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
-	if (stream >= c->streams.size() || !c->streams[stream].d_pcm) {
+	if (stream >= c->streams.info.size() || !c->streams.info[stream].d_pcm) {
 		return GAS_ERR_BAD_SLOT;
 	}
 	if (out_mode) {
-		*out_mode = (int)c->streams[stream].loop_mode;
+		*out_mode = (int)c->streams.info[stream].loop_mode;
 	}
 	if (out_begin) {
-		*out_begin = c->streams[stream].loop_begin;
+		*out_begin = c->streams.info[stream].loop_begin;
 	}
 	if (out_end) {
-		*out_end = c->streams[stream].loop_end;
+		*out_end = c->streams.info[stream].loop_end;
 	}
 	return GAS_OK;
 }
@@ -196,18 +196,18 @@ int gas_stream_destroy(gas_ctx *c, uint32_t stream) {
 	if (!c) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
-	if (stream >= c->streams.size() || !c->streams[stream].d_pcm) {
+	if (stream >= c->streams.info.size() || !c->streams.info[stream].d_pcm) {
 		return GAS_ERR_BAD_SLOT;
 	}
 	GAS_HIP(c, hipSetDevice(c->cfg.device));
 	GAS_HIP(c, hipStreamSynchronize(c->stream));
-	for (gas_cursor &cur : c->h_cursors) {
-		if (cur.pcm == c->streams[stream].d_pcm) {
+	for (gas_cursor &cur : c->streams.h_cursors) {
+		if (cur.pcm == c->streams.info[stream].d_pcm) {
 			return GAS_ERR_INVALID_ARGUMENT; // still bound to a playback
 		}
 	}
-	c->mem.drop(c->streams[stream].d_pcm);
-	c->streams[stream] = gas_ctx::StreamInfo{};
+	c->mem.drop(c->streams.info[stream].d_pcm);
+	c->streams.info[stream] = StreamInfo{};
 	return GAS_OK;
 }
 
@@ -215,17 +215,17 @@ int gas_stream_get_info(gas_ctx *c, uint32_t stream, uint64_t *out_frames, uint3
 	if (!c) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
-	if (stream >= c->streams.size() || !c->streams[stream].d_pcm) {
+	if (stream >= c->streams.info.size() || !c->streams.info[stream].d_pcm) {
 		return GAS_ERR_BAD_SLOT;
 	}
 	if (out_frames) {
-		*out_frames = c->streams[stream].frames;
+		*out_frames = c->streams.info[stream].frames;
 	}
 	if (out_channels) {
-		*out_channels = c->streams[stream].channels;
+		*out_channels = c->streams.info[stream].channels;
 	}
 	if (out_format) {
-		*out_format = (int)c->streams[stream].format;
+		*out_format = (int)c->streams.info[stream].format;
 	}
 	return GAS_OK;
 }
@@ -234,13 +234,13 @@ int gas_source_bind_stream(gas_ctx *c, uint32_t slot, uint32_t stream, uint64_t 
 	if (!c) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
-	if (slot >= c->cfg.max_sources || !c->slots[slot].used || stream >= c->streams.size() || !c->streams[stream].d_pcm) {
+	if (slot >= c->cfg.max_sources || !c->slots[slot].used || stream >= c->streams.info.size() || !c->streams.info[stream].d_pcm) {
 		return GAS_ERR_BAD_SLOT;
 	}
 	stream_rows_sync_back(c);
-	c->stream_groups_gen = UINT64_MAX;
+	c->streams.groups_gen = UINT64_MAX;
 	feed_drop(c, slot); // gas_source_feed_rows: the stream supplies the windows from here on
-	const gas_ctx::StreamInfo &si = c->streams[stream];
+	const StreamInfo &si = c->streams.info[stream];
 	gas_cursor cur{};
 	cur.pcm = si.d_pcm;
 	cur.frames = si.frames;
@@ -256,9 +256,9 @@ int gas_source_bind_stream(gas_ctx *c, uint32_t slot, uint32_t stream, uint64_t 
 	cur.has_frames = 1;
 	cur.resampled = si.resampled ? 1 : 0;
 	cur.fp_pos = cur.pos << 16; // [ENGINE] begin_resample: mix_offset = 0, zeroed interpolation history
-	c->h_cursors[slot] = cur;
+	c->streams.h_cursors[slot] = cur;
 	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	GAS_HIP(c, hipMemcpyAsync(c->d_cursors + slot, &c->h_cursors[slot], sizeof(gas_cursor), hipMemcpyHostToDevice, c->stream));
+	GAS_HIP(c, hipMemcpyAsync(c->streams.d_cursors + slot, &c->streams.h_cursors[slot], sizeof(gas_cursor), hipMemcpyHostToDevice, c->stream));
 	GAS_HIP(c, hipStreamSynchronize(c->stream));
 	if (c->slots[slot].draining) {
 		c->slots[slot].draining = 0;
@@ -271,18 +271,18 @@ int gas_stream_positions(gas_ctx *c, uint32_t n, uint64_t *out_frames) {
 	if (!c || (n > 0 && !out_frames)) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
-	if (n != c->stream_slots_host.size()) {
+	if (n != c->streams.slots_host.size()) {
 		return GAS_ERR_INVALID_ARGUMENT; // not the list of the last stream callback (gas_process_block_streams or gas_process_block_streams_buses)
 	}
 	// The compact row mirror holds the positions while the list is cached; a block boundary that applied deferred
 	// frees has folded it back into the per-slot cursors (stream_rows_sync_back) and emptied it.
-	const bool rows_live = c->stream_rows.size() == n;
+	const bool rows_live = c->streams.rows.size() == n;
 	for (uint32_t i = 0; i < n; i++) {
-		const gas_cursor &cur = c->h_cursors[c->stream_slots_host[i]];
+		const gas_cursor &cur = c->streams.h_cursors[c->streams.slots_host[i]];
 		if (!cur.pcm) {
 			out_frames[i] = 0;
 		} else if (rows_live) {
-			const gas_ctx::StreamRow &r = c->stream_rows[i];
+			const StreamRow &r = c->streams.rows[i];
 			out_frames[i] = r.resampled ? (r.fp_pos >> 16) : r.looped ? r.pos : cur.frames - r.remaining;
 		} else {
 			out_frames[i] = cur.resampled ? (cur.fp_pos >> 16) : cur.pos;
@@ -314,7 +314,7 @@ int gas_source_feed_rows(gas_ctx *c, const uint32_t *slots, const void *rows, in
 		}
 	}
 	for (uint32_t i = 0; i < n; i++) {
-		if (c->h_cursors[slots[i]].pcm) {
+		if (c->streams.h_cursors[slots[i]].pcm) {
 			return GAS_ERR_INVALID_ARGUMENT; // bound to a stream: the sampler supplies its windows
 		}
 		if (c->stamp.seen(slots[i])) {
@@ -327,13 +327,13 @@ int gas_source_feed_rows(gas_ctx *c, const uint32_t *slots, const void *rows, in
 	GAS_HIP(c, hipSetDevice(c->cfg.device));
 	const size_t row_bytes = (size_t)F * (format == GAS_PCM_F32 ? 4u : 2u) * channels; // a multiple of 256: frames % 128 == 0
 	const size_t bytes = (size_t)n * row_bytes;
-	if (mem == GAS_MEM_HOST && bytes > c->h_feed_cap) { // grows to the largest call: not in the steady state
-		if (c->feed_ev) {
-			GAS_HIP(c, hipEventSynchronize(c->feed_ev));
+	if (mem == GAS_MEM_HOST && bytes > c->feed.h_cap) { // grows to the largest call: not in the steady state
+		if (c->feed.ev) {
+			GAS_HIP(c, hipEventSynchronize(c->feed.ev));
 		} else {
-			GAS_HIP(c, c->mem.make_event(c->feed_ev, hipEventDisableTiming));
+			GAS_HIP(c, c->mem.make_event(c->feed.ev, hipEventDisableTiming));
 		}
-		if (c->mem.grow(c->h_feed, c->h_feed_cap, bytes, 1, Mem::PINNED) != hipSuccess) {
+		if (c->mem.grow(c->feed.h_rows, c->feed.h_cap, bytes, 1, Mem::PINNED) != hipSuccess) {
 			return GAS_ERR_OUT_OF_MEMORY;
 		}
 	}
@@ -343,7 +343,7 @@ int gas_source_feed_rows(gas_ctx *c, const uint32_t *slots, const void *rows, in
 	if (rcp != GAS_OK) {
 		return rcp;
 	}
-	uint8_t *dst = c->d_feed + at;
+	uint8_t *dst = c->feed.d_table + at;
 	const int rcc = [&]() -> int {
 		if (mem == GAS_MEM_DEVICE) {
 			const int rcj = join_outputs(c); // GAS_FLAG_PIPELINED_MIX: `rows` may be an earlier callback's out, still a pending sum
@@ -353,28 +353,28 @@ int gas_source_feed_rows(gas_ctx *c, const uint32_t *slots, const void *rows, in
 			GAS_HIP(c, hipMemcpyAsync(dst, rows, bytes, hipMemcpyDeviceToDevice, c->stream));
 			return GAS_OK;
 		}
-		GAS_HIP(c, hipEventSynchronize(c->feed_ev)); // the previous upload has left the staging: a wait only while it is still queued
-		std::memcpy(c->h_feed, rows, bytes);
-		GAS_HIP(c, hipMemcpyAsync(dst, c->h_feed, bytes, hipMemcpyHostToDevice, c->stream));
-		GAS_HIP(c, hipEventRecord(c->feed_ev, c->stream));
+		GAS_HIP(c, hipEventSynchronize(c->feed.ev)); // the previous upload has left the staging: a wait only while it is still queued
+		std::memcpy(c->feed.h_rows, rows, bytes);
+		GAS_HIP(c, hipMemcpyAsync(dst, c->feed.h_rows, bytes, hipMemcpyHostToDevice, c->stream));
+		GAS_HIP(c, hipEventRecord(c->feed.ev, c->stream));
 		return GAS_OK;
 	}();
 	if (rcc != GAS_OK) {
 		return rcc; // nothing committed: every pending row is still where its word says
 	}
 	if (switched) {
-		c->feed_side = 1 - c->feed_side;
-		for (size_t k = 0; k + 1 < c->feed_moved.size(); k += 2) {
-			c->feed_word[c->feed_moved[k]] = c->feed_moved[k + 1];
+		c->feed.side = 1 - c->feed.side;
+		for (size_t k = 0; k + 1 < c->feed.moved.size(); k += 2) {
+			c->feed.word[c->feed.moved[k]] = c->feed.moved[k + 1];
 		}
 	}
 	for (uint32_t i = 0; i < n; i++) {
-		if (c->feed_word[slots[i]] == GAS_FEED_NONE) {
-			c->feed_slots.push_back(slots[i]);
+		if (c->feed.word[slots[i]] == GAS_FEED_NONE) {
+			c->feed.slots.push_back(slots[i]);
 		} // else: replaces the row fed before; its bytes lie idle until the table is emptied
-		c->feed_word[slots[i]] = gas_feed_word(at + (size_t)i * row_bytes, format, channels);
+		c->feed.word[slots[i]] = gas_feed_word(at + (size_t)i * row_bytes, format, channels);
 	}
-	c->feed_used = at + bytes;
+	c->feed.used = at + bytes;
 	return GAS_OK;
 }
 

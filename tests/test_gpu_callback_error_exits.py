@@ -1,0 +1,206 @@
+"""The error exits of the four callback entries (gas_process_block, gas_process_block_buses, gas_process_block_streams,
+gas_process_block_streams_buses), for host and device memory: what each failure that API misuse alone can cause
+returns, what it does to `out`, and that it moves no playback cursor and leaves nothing behind that a later callback
+could see.
+
+The contract (csrc/gas_ctx.hip, at fail_out): a failed callback leaves a zeroed mix in host memory and device memory
+as it is; exits in front of an entry's body -- its argument checks, a list reuse that gas_process_block_buses cannot
+serve -- touch `out` in neither; a bad n_buses at gas_process_block_streams_buses zeroes
+as many buses of a host `out` as a legal call could name (min(n_buses, GAS_MAX_BUSES)).  None of these failures reaches
+a kernel.
+
+`out` is prefilled with a pattern that is nowhere zero and is seven buses long, one more than a legal call can name.
+The follow-on test runs every failure of every entry on one context and then four valid stream callbacks -- a fed row,
+the same list again (its unfed entry starts to drain, a playback ends), another list, that list again -- whose mix,
+peaks and has_frames are compared bit for bit with a context that never saw a failure."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import stream_window_ref as wref
+
+pytestmark = pytest.mark.gpu
+
+INVALID_ARGUMENT, BAD_SLOT, FRAME_COUNT, NO_HRTF, UNSUPPORTED_CHAIN, NO_PARAMS = -1, -3, -4, -5, -6, -12
+F, MAX_SOURCES, MAX_BUSES, N_BUSES = 512, 4, 6, 2
+ENTRIES = ("block", "buses", "streams", "streams_buses")
+PATTERN = (1.0 + np.arange((MAX_BUSES + 1) * F * 2, dtype=np.float32) / 1024.0).reshape(MAX_BUSES + 1, 1, F, 2)
+PATTERN.setflags(write=False)
+
+
+class Scene:
+    """Three [HRTF] playbacks -- two bound to streams (the first ends in its third callback), one bound to none, which
+    takes fed rows -- and a 3D-mix playback, which has no parameters until publish_mix().  hrtf=False: no HRIR set is
+    loaded, and the 3D-mix playback (with parameters, bound to the second stream) is what a valid callback can run."""
+
+    def __init__(self, gas, hrtf=True):
+        from godot_audio_spatializer_amd import synth
+
+        self.K = K = gas.capi
+        self.ctx = ctx = gas.SpatializerContext(max_sources=MAX_SOURCES, frames=F)
+        if hrtf:
+            ctx.hrtf_load(synth.synthetic_hrir(np.random.default_rng(1), dirs=8))
+        self.fx = ctx.source_alloc_many(3, K.KIND_EFFECT, (K.FX_HRTF,))
+        self.mix = ctx.source_alloc(K.KIND_3D_MIX)
+        self.params = synth.draw_params(np.random.default_rng(2), MAX_SOURCES, dirs=8, frames=F)
+        ctx.params_publish_batch(self.fx, self.params[:3])
+        routes = K.bus_routes(3)
+        routes["dry_bus"] = [0, 1, 0]
+        routes["send_bus"][1] = 0
+        routes["send"][1, 0] = [0.5, 0.75]
+        ctx.bus_routes_publish(self.fx, routes)
+        rng = np.random.default_rng(3)
+        sids = [ctx.stream_create(wref.make_pcm(rng, 1300, "s16_mono")), ctx.stream_create(wref.make_pcm(rng, 4000, "f32_stereo"))]
+        ctx.source_bind_stream(self.fx[0], sids[0])
+        ctx.source_bind_stream(self.fx[1], sids[1], start_frame=17)
+        self.rows = synth.draw_sources(np.random.default_rng(4), MAX_SOURCES, F)
+        self.fed = wref.make_pcm(np.random.default_rng(5), F, "s16_mono")
+        self.listed = 0  # entries of the last valid stream list: what gas_stream_positions answers for
+        self.valid = self.fx
+        if not hrtf:
+            self.publish_mix()
+            ctx.source_bind_stream(self.mix, sids[1])
+            self.valid = np.array([self.mix], np.uint32)
+
+    def publish_mix(self):
+        self.ctx.params_publish(int(self.mix), self.params[3])
+
+    def prime(self):
+        """One valid stream callback: from here on the context has a list, cursors that have moved and cached groups."""
+        self.ctx.process_block_streams(self.valid)
+        self.listed = len(self.valid)
+
+    def close(self):
+        self.ctx.close()
+
+
+def call(sc, entry, mem, slots, n=None, frames=F, n_buses=N_BUSES):
+    """The entry through the C ABI with `out` prefilled; -> (status, out, peaks, has_frames) as host arrays."""
+    K, lib, h = sc.K, sc.ctx.lib, sc.ctx.h
+    s = None if slots is None else np.ascontiguousarray(slots, dtype=np.uint32)
+    n = len(s) if n is None else n
+    sp = None if s is None or len(s) == 0 else s.ctypes.data_as(C.c_void_p)
+    hf = np.full(MAX_SOURCES, 7, np.uint8)
+    hfp = hf.ctypes.data_as(C.c_void_p)
+    if mem == K.MEM_HOST:
+        src, out, peaks = sc.rows, PATTERN.copy(), np.zeros((MAX_SOURCES, 2), np.float32)
+
+        def ptr(a):
+            return a.ctypes.data_as(C.c_void_p)
+    else:
+        import torch
+
+        src, out, peaks = torch.from_numpy(sc.rows).cuda(), torch.from_numpy(PATTERN.copy()).cuda(), torch.zeros(MAX_SOURCES, 2, device="cuda")
+        torch.cuda.synchronize()
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr())
+    if entry == "block":
+        rc = lib.gas_process_block(h, ptr(src), sp, n, frames, ptr(out), ptr(peaks), mem)
+    elif entry == "buses":
+        rc = lib.gas_process_block_buses(h, ptr(src), sp, n, frames, ptr(out), n_buses, ptr(peaks), mem)
+    elif entry == "streams":
+        rc = lib.gas_process_block_streams(h, sp, n, frames, ptr(out), ptr(peaks), hfp, mem)
+    else:
+        rc = lib.gas_process_block_streams_buses(h, sp, n, frames, ptr(out), n_buses, ptr(peaks), hfp, mem)
+    if mem != K.MEM_HOST:
+        sc.ctx.synchronize()
+        out, peaks = out.cpu().numpy(), peaks.cpu().numpy()
+    return rc, out, peaks, hf
+
+
+def fails(sc, entry, mem, what, status, zeroed, **kw):
+    """The call fails with `status`; a host `out` has its first `zeroed` buses zeroed and nothing else written, a device
+    `out` is untouched; no playback cursor has moved."""
+    where = f"{entry}, {'host' if mem == sc.K.MEM_HOST else 'device'} memory: {what}"
+    before = sc.ctx.stream_positions(sc.listed)
+    rc, out, _, _ = call(sc, entry, mem, **kw)
+    assert rc == status, where
+    want = PATTERN.copy()
+    if mem == sc.K.MEM_HOST:
+        want[:zeroed] = 0.0
+    assert np.array_equal(out, want), where
+    assert np.array_equal(sc.ctx.stream_positions(sc.listed), before), where
+
+
+def failure_sequence(sc, entries, mem):
+    """Every failure below, for each of `entries`; in between the context is primed and the 3D-mix playback gets its
+    parameters.  `mix`: the buses of `out` that the entry's failed host call zeroes, one mix or N_BUSES bus mixes."""
+    fx, mixed = sc.fx, np.array([sc.fx[0], sc.mix], np.uint32)
+    for e in entries:  # slots == NULL with nothing cached; only gas_process_block gets as far as its body with it
+        fails(sc, e, mem, "no list, nothing cached", INVALID_ARGUMENT, 1 if e == "block" else 0, slots=None, n=2)
+    sc.prime()
+    for e in entries:
+        mix = N_BUSES if e.endswith("buses") else 1
+        fails(sc, e, mem, "a playback without parameters", NO_PARAMS, mix, slots=mixed)
+    sc.publish_mix()
+    for e in entries:
+        bus, stream = e.endswith("buses"), e.startswith("streams")
+        mix = N_BUSES if bus else 1
+        fails(sc, e, mem, "wrong frames", FRAME_COUNT, mix, slots=fx, frames=F // 2)
+        fails(sc, e, mem, "a slot that is not live", BAD_SLOT, mix, slots=[fx[0], MAX_SOURCES + 95])
+        fails(sc, e, mem, "a slot twice", INVALID_ARGUMENT, mix, slots=[fx[1], fx[0], fx[1]])
+        fails(sc, e, mem, "no list, another list's groups cached", INVALID_ARGUMENT, 1 if e == "block" else 0, slots=None, n=2)
+        if bus:
+            fails(sc, e, mem, "3D-mix and effect sources in a bus list", UNSUPPORTED_CHAIN, mix, slots=mixed)
+            fails(sc, e, mem, "n_buses 0", INVALID_ARGUMENT, 0, slots=fx, n_buses=0)
+            fails(sc, e, mem, "n_buses GAS_MAX_BUSES + 1", INVALID_ARGUMENT, MAX_BUSES if stream else 0, slots=fx, n_buses=MAX_BUSES + 1)
+        if stream:
+            fast = sc.params[:1].copy()
+            fast["pitch_scale"] = 1.5
+            sc.ctx.params_publish_batch(fx[:1], fast)
+            fails(sc, e, mem, "pitch_scale 1.5 on a playback that is not resampled", UNSUPPORTED_CHAIN, mix, slots=fx)
+            sc.ctx.params_publish_batch(fx[:1], sc.params[:1])
+
+
+@pytest.mark.parametrize("mem", ["host", "device"])
+@pytest.mark.parametrize("entry", ENTRIES)
+def test_error_exits(gas, entry, mem):
+    mem = gas.capi.MEM_HOST if mem == "host" else gas.capi.MEM_DEVICE
+    sc = Scene(gas)
+    try:
+        failure_sequence(sc, [entry], mem)
+    finally:
+        sc.close()
+    sc = Scene(gas, hrtf=False)
+    try:
+        sc.prime()
+        fails(sc, entry, mem, "HRTF chains before gas_hrtf_load", NO_HRTF, N_BUSES if entry.endswith("buses") else 1, slots=sc.fx[:2])
+    finally:
+        sc.close()
+
+
+def valid_callbacks(sc, entry, mem):
+    """Four stream callbacks; -> per callback the bits of mix and peaks, and has_frames."""
+    lists = [sc.fx, sc.fx, sc.fx[[1, 0]], sc.fx[[1, 0]]]
+    got = []
+    for cb, slots in enumerate(lists):
+        if cb == 0:
+            sc.ctx.source_feed_rows(sc.fx[2:], sc.fed[None])
+        rc, out, peaks, hf = call(sc, entry, mem, slots)
+        assert rc == 0, f"callback {cb}"
+        buses = N_BUSES if entry.endswith("buses") else 1
+        got.append((out[:buses].view(np.uint32), peaks[: len(slots)].view(np.uint32), hf[: len(slots)].copy()))
+        assert np.array_equal(out[buses:], PATTERN[buses:]), f"callback {cb}: wrote past its mix"
+    return got
+
+
+@pytest.mark.parametrize("mem", ["host", "device"])
+@pytest.mark.parametrize("entry", ["streams", "streams_buses"])
+def test_valid_callbacks_after_failures(gas, entry, mem):
+    mem = gas.capi.MEM_HOST if mem == "host" else gas.capi.MEM_DEVICE
+    failed, clean = Scene(gas), Scene(gas)
+    try:
+        failure_sequence(failed, ENTRIES, mem)
+        clean.prime()
+        clean.publish_mix()
+        got, want = valid_callbacks(failed, entry, mem), valid_callbacks(clean, entry, mem)
+        for cb, (g, w) in enumerate(zip(got, want)):
+            for a, b, what in zip(g, w, ("mix", "peaks", "has_frames")):
+                assert np.array_equal(a, b), f"{what}, callback {cb}"
+        ends = [hf.tolist() for _, _, hf in want]
+        assert ends == [[1, 1, 1], [0, 1, 0], [1, 0], [1, 0]]  # the scene is what the docstring says it is
+    finally:
+        failed.close()
+        clean.close()

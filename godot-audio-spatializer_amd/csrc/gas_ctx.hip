@@ -491,6 +491,24 @@ gas_hrtf_launch_common hrtf_common(const gas_ctx *c) {
 	return k;
 }
 
+// A biquad launch (gas_launch_biquad_mix: k_biquad_mix, or the form its launcher picks) over `g`, with the fields every
+// such launch of this context shares: one channel pair from channel 0, partial rows in the context's stride.
+gas_biquad_launch biquad_launch(const gas_ctx *c, int mode, const gas_group_args &g, float *partials, uint32_t p_offset) {
+	gas_biquad_launch lb;
+	lb.stream = c->stream;
+	lb.mode = mode;
+	lb.g = g;
+	lb.st = &c->st;
+	lb.frames = c->cfg.frames;
+	lb.mix_rate = c->cfg.mix_rate;
+	lb.partials = partials;
+	lb.p_offset = p_offset;
+	lb.p_stride = c->partial_rows;
+	lb.scan_ok = c->sw.shelf_scan;
+	lb.pipe_ok = c->sw.biquad_pipe;
+	return lb;
+}
+
 // Which entries of the plain-[HRTF] group of the context's own list report their exact peak (build_groups): the bit
 // list, unless all of them or none do.
 inline const uint32_t *plain_peak_bits(const gas_ctx *c) {
@@ -561,7 +579,7 @@ int launch_hrtf_groups(gas_ctx *c, const RunArgs &a, int gt, const gas_group_arg
 		// XCD-affine processing order (k_xcd_order): rebuilt when the list or any parameter changed, else reused
 		const uint32_t uni_wgs = gas_hrtf_uni_partials(g_fd.n);
 		c->last_uni_ordered = false;
-		if (a.use_order && ((c->cfg.flags & GAS_FLAG_XCD_ORDER) != 0 || g_fd.n >= c->xcd_order_auto_min) && uni_wgs % 8 == 0 && c->tab.dirs >= 8) {
+		if (a.use_order && ((c->cfg.flags & GAS_FLAG_XCD_ORDER) != 0 || g_fd.n >= c->sw.xcd_order_auto_min) && uni_wgs % 8 == 0 && c->tab.dirs >= 8) {
 			GAS_HIP(c, alloc_once(c, c->d_order, c->cfg.max_sources));
 			uint32_t *ord = c->d_order + groups[fd_gt].offset;
 			if (!c->order_ok[fd_gt]) {
@@ -671,7 +689,7 @@ int launch_staged_chains(gas_ctx *c, const RunArgs &a, const gas_group_args &ga,
 		lu.partials = run.parts;
 		lu.p_offset = pp_r;
 		lu.peak_bit_base = r.offset;
-		if (last_is_uni && c->uni_flt_enabled && (r.sig >> 8) == GAS_FX_HRTF && (k0 == GAS_FX_HIGHSHELF || (k0 >= GAS_FX_LOWPASS && k0 <= GAS_FX_LOWSHELF)) && gas_shelf_scan_applies(k0 == GAS_FX_HIGHSHELF ? GAS_MODE_FX_HIGHSHELF : GAS_MODE_FX_FILTER, r.count, F)) {
+		if (last_is_uni && c->sw.uni_flt && (r.sig >> 8) == GAS_FX_HRTF && (k0 == GAS_FX_HIGHSHELF || (k0 >= GAS_FX_LOWPASS && k0 <= GAS_FX_LOWSHELF)) && gas_shelf_scan_applies(c->sw.shelf_scan, k0 == GAS_FX_HIGHSHELF ? GAS_MODE_FX_HIGHSHELF : GAS_MODE_FX_FILTER, r.count, F)) {
 			// [one-biquad filter, HRTF]: one launch (k_hrtf_uni<FLT>), no rows in between.  The filter there is the
 			// scan form, so it is taken exactly where the two-launch road would take k_shelf_scan (same bits either
 			// way; small callbacks and GAS_SHELF_SCAN=0 keep the engine's serial order)
@@ -702,7 +720,10 @@ int launch_staged_chains(gas_ctx *c, const RunArgs &a, const gas_group_args &ga,
 			}
 			gas_audio_frame *outb = c->d_chain[j & 1];
 			if (kind == GAS_FX_HIGHSHELF) {
-				GAS_HIP(c, gas_launch_biquad_mix(c->stream, GAS_MODE_FX_HIGHSHELF, in, c->st, F, (uint32_t)j, 1, c->cfg.mix_rate, run.parts, 0, c->partial_rows, reinterpret_cast<float *>(outb)));
+				gas_biquad_launch lb = biquad_launch(c, GAS_MODE_FX_HIGHSHELF, in, run.parts, 0);
+				lb.channel_begin = (uint32_t)j;
+				lb.rows_out = reinterpret_cast<float *>(outb);
+				GAS_HIP(c, gas_launch_biquad_mix(lb));
 			} else if (kind == GAS_FX_EARLY_REFLECTIONS) {
 				GAS_HIP(c, gas_launch_er_only(c->stream, in, c->st, F, c->cfg.er_ring_frames, run.parts, 0, c->partial_rows, outb, er_fade_on(c)));
 			} else if (kind == GAS_FX_HRTF) {
@@ -738,7 +759,7 @@ int run_groups(gas_ctx *c, const RunArgs &a) {
 	// [ER, HRTF] through k_hrtf_uni<ER> (22.5 -> see profiles/r03_notes.md): the exact-peak group's entries follow the
 	// frequency-domain group's in the callback's list, so one launch covers both
 	const bool pipelined = a.pipelined && c->pipelined_mix && a.channel_count == 1 && c->cfg.channel_count == 1;
-	const bool uni_er_pays = c->uni_er_mode == 2 || groups[G_FX_ER_HRTF_PK].count * 4 <= groups[G_FX_ER_HRTF].count + groups[G_FX_ER_HRTF_PK].count;
+	const bool uni_er_pays = c->sw.uni_er_mode == 2 || groups[G_FX_ER_HRTF_PK].count * 4 <= groups[G_FX_ER_HRTF].count + groups[G_FX_ER_HRTF_PK].count;
 	run.uni_er = uni_ok(c) && a.buses == nullptr && gas_hrtf_uni_waves() == 8 && c->uni_er_enabled && uni_er_pays && (groups[G_FX_ER_HRTF].count == 0 || groups[G_FX_ER_HRTF_PK].count == 0 || groups[G_FX_ER_HRTF].offset + groups[G_FX_ER_HRTF].count == groups[G_FX_ER_HRTF_PK].offset);
 	plan_partials(groups, *a.ranges, pcount, run.uni_hrtf, run.staged_uni, run.uni_er);
 	uint32_t p_total = 0, p_mix = 0;
@@ -825,15 +846,18 @@ int run_groups(gas_ctx *c, const RunArgs &a) {
 				if (a.force_mode >= 0) {
 					mode = a.force_mode;
 				}
-				const uint32_t cb = mode == GAS_MODE_MIX_CHANNEL ? a.channel_begin : 0;
-				const uint32_t cc = mode == GAS_MODE_MIX_CHANNEL ? a.channel_count : 1;
-				GAS_HIP(c, gas_launch_biquad_mix(c->stream, mode, ga, c->st, F, cb, cc, c->cfg.mix_rate, parts, run.p_off, c->partial_rows));
+				gas_biquad_launch lb = biquad_launch(c, mode, ga, parts, run.p_off);
+				if (mode == GAS_MODE_MIX_CHANNEL) {
+					lb.channel_begin = a.channel_begin;
+					lb.channel_count = a.channel_count;
+				}
+				GAS_HIP(c, gas_launch_biquad_mix(lb));
 			} break;
 			case G_FX_COPY:
-				GAS_HIP(c, gas_launch_biquad_mix(c->stream, GAS_MODE_COPY, ga, c->st, F, 0, 1, c->cfg.mix_rate, parts, run.p_off, c->partial_rows));
+				GAS_HIP(c, gas_launch_biquad_mix(biquad_launch(c, GAS_MODE_COPY, ga, parts, run.p_off)));
 				break;
 			case G_FX_SHELF:
-				GAS_HIP(c, gas_launch_biquad_mix(c->stream, GAS_MODE_FX_HIGHSHELF, ga, c->st, F, 0, 1, c->cfg.mix_rate, parts, run.p_off, c->partial_rows));
+				GAS_HIP(c, gas_launch_biquad_mix(biquad_launch(c, GAS_MODE_FX_HIGHSHELF, ga, parts, run.p_off)));
 				break;
 			case G_FX_ER:
 				GAS_HIP(c, gas_launch_er_only(c->stream, ga, c->st, F, c->cfg.er_ring_frames, parts, run.p_off, c->partial_rows, nullptr, er_fade_on(c)));
@@ -863,7 +887,7 @@ int run_groups(gas_ctx *c, const RunArgs &a) {
 			c->prof.group = gt;
 			c->prof.uni = (gt == G_FX_HRTF && run.uni_hrtf && groups[G_FX_HRTF_PK].count == 0) || ((gt == G_FX_ER_HRTF || gt == G_FX_ER_HRTF_PK) && run.uni_er);
 			c->prof.multi = false;
-			c->prof.pipe = (gt == G_3D_MIX || gt == G_3D_PROCESS || gt == G_FX_SHELF) && gas_biquad_uses_pipe(gt == G_FX_SHELF ? GAS_MODE_FX_HIGHSHELF : (a.force_mode >= 0 ? a.force_mode : (gt == G_3D_MIX ? GAS_MODE_MIX_CHANNEL : GAS_MODE_PROCESS_FRAMES)), gr.count, gt == G_3D_MIX ? a.channel_count : 1, F, false);
+			c->prof.pipe = (gt == G_3D_MIX || gt == G_3D_PROCESS || gt == G_FX_SHELF) && gas_biquad_uses_pipe(c->sw.biquad_pipe, gt == G_FX_SHELF ? GAS_MODE_FX_HIGHSHELF : (a.force_mode >= 0 ? a.force_mode : (gt == G_3D_MIX ? GAS_MODE_MIX_CHANNEL : GAS_MODE_PROCESS_FRAMES)), gr.count, gt == G_3D_MIX ? a.channel_count : 1, F, false);
 		}
 		run.p_off += pcount[gt];
 	}
@@ -1194,7 +1218,11 @@ constexpr FxFamilyDesc k_fx_families[FX_FAMILIES] = {
 	{ "basic", sizeof(gas_fx_settings), fx_defaults_of<gas_fx_settings, fx_settings_defaults>, nullptr, no_pool,
 			[](int kind) { return kind >= GAS_FX_LOWPASS && kind <= GAS_FX_AMPLIFY; }, true, BasicDev::get, BasicDev::set, nullptr, nullptr, nullptr,
 			[](const gas_ctx *c, int kind, const gas_group_args &in, uint32_t j, gas_audio_frame *out) {
-				return gas_launch_biquad_mix(c->stream, kind == GAS_FX_AMPLIFY ? GAS_MODE_FX_AMPLIFY : GAS_MODE_FX_FILTER, in, c->st, c->cfg.frames, j, 1, c->cfg.mix_rate, c->d_partials, 0, c->partial_rows, reinterpret_cast<float *>(out), gas_bus_args(), kind);
+				gas_biquad_launch lb = biquad_launch(c, kind == GAS_FX_AMPLIFY ? GAS_MODE_FX_AMPLIFY : GAS_MODE_FX_FILTER, in, c->d_partials, 0);
+				lb.channel_begin = j;
+				lb.rows_out = reinterpret_cast<float *>(out);
+				lb.fx_kind = kind;
+				return gas_launch_biquad_mix(lb);
 			} },
 	{ "dyn", sizeof(gas_fx_dyn_settings), fx_defaults_of<gas_fx_dyn_settings, fx_dyn_settings_defaults>, fx_valid_of<gas_fx_dyn_settings, gas_fx_dyn_settings_valid>, no_pool,
 			[](int kind) { return kind == GAS_FX_DISTORTION || kind == GAS_FX_COMPRESSOR; }, true, DynDev::get, DynDev::set, nullptr, nullptr, nullptr,
@@ -1896,12 +1924,8 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 	}
 	c->cfg = *cfg;
 	c->hist_len = 512 - cfg->frames / 2;
-	if (er_fade_on(c)) { // the fused [ER, HRTF] kernels have no fading form: the tail of a staged chain stays two launches, whatever GAS_UNI_ER says
-		c->uni_er_enabled = false;
-	}
-	if (const char *v = std::getenv("GAS_XCD_ORDER_AUTO_MIN")) {
-		c->xcd_order_auto_min = (uint32_t)std::strtoul(v, nullptr, 10);
-	}
+	c->sw = gas_switches_from_env();
+	c->uni_er_enabled = c->sw.uni_er_mode != 0 && !er_fade_on(c); // the fused [ER, HRTF] kernels have no fading form: the tail of a staged chain stays two launches, whatever GAS_UNI_ER says
 	const size_t N = cfg->max_sources;
 	int rc = [&]() -> int {
 		GAS_HIP(c, hipSetDevice(cfg->device));
@@ -2705,7 +2729,11 @@ int bus_body(gas_ctx *c, const RowSource &src, const uint32_t *slots, uint32_t n
 		ba.routes = c->d_routes;
 		ba.n_buses = n_buses;
 		// force the multi-bus code even for one bus when the caller routes (a lone bus other than 0 is legal)
-		GAS_HIP(c, gas_launch_biquad_mix(c->stream, GAS_MODE_MIX_CHANNEL, ga, c->st, F, 0, C, c->cfg.mix_rate, c->d_bus_partials, 0, P, nullptr, ba));
+		gas_biquad_launch lb = biquad_launch(c, GAS_MODE_MIX_CHANNEL, ga, c->d_bus_partials, 0);
+		lb.channel_count = C;
+		lb.p_stride = P;
+		lb.buses = ba;
+		GAS_HIP(c, gas_launch_biquad_mix(lb));
 	}
 	if (!staged) {
 		GAS_HIP(c, gas_launch_mix_reduce(c->stream, c->d_bus_partials, P, P ? P : 1, n_buses * C, F, d_out));
@@ -3003,7 +3031,7 @@ bool stream_fuses(const gas_ctx *c, bool buses, bool any_fed) {
 	const bool bus_fusable = !buses || (c->cfg.channel_count == 1 && uni_ok(c) && gas_hrtf_uni_waves() == 8);
 	// gas_source_feed_rows: k_hrtf_uni<SRC_PCM> and k_hrtf_uni<SRC_PCM, BUS2> take fed entries; the k_hrtf_ols stream-sampling forms -- cross-fade, direction runs / order, interpolation contexts -- have no registers left for them
 	const bool fed_fusable = !any_fed || uni_ok(c);
-	return plain && fade_free && loops_fused && !c->streams.rows_first && bus_fusable && fed_fusable;
+	return plain && fade_free && loops_fused && !c->sw.rows_first && bus_fusable && fed_fusable;
 }
 
 // Rows first: the windows of the list's n playbacks into d_src -- k_sample_sources, then the decoders of the compressed
@@ -3020,10 +3048,10 @@ int stream_sample_rows(gas_ctx *c, uint32_t n, const uint8_t *feed) {
 	const uint32_t *inc = s.list.any_resampled ? s.d_inc : nullptr;
 	GAS_HIP(c, gas_launch_sample_sources(c->stream, s.d_cursors, s.d_slots, n, F, c->d_fade_env, c->d_src, inc, feed));
 	if (s.list.any_adpcm) {
-		GAS_HIP(c, gas_launch_sample_adpcm(c->stream, s.d_cursors, s.d_slots, n, F, c->d_fade_env, c->d_src, inc, s.adpcm_span));
+		GAS_HIP(c, gas_launch_sample_adpcm(c->stream, s.d_cursors, s.d_slots, n, F, c->d_fade_env, c->d_src, inc, c->sw.adpcm_span));
 	}
 	if (s.list.any_qoa) {
-		GAS_HIP(c, gas_launch_sample_qoa(c->stream, s.d_cursors, s.d_slots, n, F, c->d_fade_env, c->d_src, inc, s.qoa_span));
+		GAS_HIP(c, gas_launch_sample_qoa(c->stream, s.d_cursors, s.d_slots, n, F, c->d_fade_env, c->d_src, inc, c->sw.qoa_span));
 	}
 	return GAS_OK;
 }

@@ -18,6 +18,7 @@
 #include "gas_internal.h"
 #include "gas_owned.h"
 #include "gas_qoa.h"
+#include "gas_switches.h"
 
 // Hidden: the library is built without -fvisibility, and none of these names belongs in its dynamic symbol table.
 namespace gas_priv __attribute__((visibility("hidden"))) {
@@ -230,10 +231,6 @@ struct StreamState {
 	bool last_buses = false; // the cached stream list was validated by gas_process_block_streams_buses (its checks differ from the mix entry's)
 	bool bus_staged = false; // ... and ran the staged bus form, which regroups on every call (cached_n never names it)
 	bool params_touched = false; // a parameter publish may have changed pitch_scale: re-validate
-	// development aids, read at context creation
-	bool rows_first = getenv("GAS_STREAM_ROWS_FIRST") != nullptr && atoi(getenv("GAS_STREAM_ROWS_FIRST")) != 0; // plain [HRTF] stream lists sample rows first too (tools/time_stream_loops.py compares the routes)
-	bool adpcm_span = getenv("GAS_ADPCM_SPAN") == nullptr || atoi(getenv("GAS_ADPCM_SPAN")) != 0; // 0 = every load decodes from its checkpoint (k_sample_adpcm.hip; tools/time_stream_adpcm.py and the tests compare the paths)
-	bool qoa_span = getenv("GAS_QOA_SPAN") == nullptr || atoi(getenv("GAS_QOA_SPAN")) != 0; // 0 = every load decodes from its record (k_sample_qoa.hip; tools/time_stream_qoa.py and the tests compare the paths)
 };
 
 // gas_source_feed_rows: window rows of playbacks that are not bound to a stream, pending for the next stream callback.
@@ -361,7 +358,6 @@ struct gas_ctx {
 	uint32_t *d_order = nullptr; // [max_sources] direction order of the frequency-domain HRTF groups (k_dir_order)
 	uint64_t order_groups_gen = UINT64_MAX, order_params_gen = 0; // what d_order was built from
 	bool order_ok[G_COUNT] = {}; // d_order holds this group's order
-	uint32_t xcd_order_auto_min = GAS_XCD_ORDER_AUTO_MIN; // GAS_XCD_ORDER_AUTO_MIN in the environment overrides (experiments)
 	bool last_uni_ordered = false; // the last k_hrtf_uni launch ran in k_xcd_order's order
 	bool cached_identity_rows = true;
 	Group groups[G_COUNT];
@@ -403,15 +399,8 @@ struct gas_ctx {
 	ProbeState probe;
 
 	ProfState prof;
-	bool uni_flt_enabled = getenv("GAS_UNI_FLT") == nullptr || atoi(getenv("GAS_UNI_FLT")) != 0; // [filter, HRTF] through k_hrtf_uni<FLT> (0: the filter stage and the HRTF stage as two launches, for comparison)
-	// [ER, HRTF] through k_hrtf_uni<ER>.  GAS_UNI_ER = 1 (default): when at most a quarter of the callback's playbacks want
-	// their exact peak.  In throughput mode it is the faster form (the launch carries the previous callback's sum, which
-	// k_hrtf_ols<ER> has no registers to park: 20.4 vs 22.4 us for cfg5), an ordered callback is a tie (22.7 / 22.4 us) --
-	// the choice does not look at the mode, so the two modes stay bit-identical -- and with every peak exact the split
-	// kernel's exact-peak workgroups win (23.6 vs 25.8 us).  0: never.  2: always (tests, A/B).  Staged chains that END in
-	// [ER, HRTF] take it whenever it is not 0 (one launch less, no rows in between).
-	int uni_er_mode = getenv("GAS_UNI_ER") ? atoi(getenv("GAS_UNI_ER")) : 1;
-	bool uni_er_enabled = uni_er_mode != 0;
+	gas_switches sw; // the environment's run-time switches, filled once by gas_ctx_create (gas_switches.h)
+	bool uni_er_enabled = true; // sw.uni_er_mode != 0, and no GAS_FLAG_ER_TAP_FADE (gas_ctx_create)
 
 	std::string last_err;
 };

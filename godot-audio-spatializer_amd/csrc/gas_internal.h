@@ -407,17 +407,32 @@ struct gas_bus_args {
 // Returns the number of partial mixes (per channel) it writes into `partials`
 // ([C][P][F*2] floats, row stride P_stride).
 uint32_t gas_biquad_partials(uint32_t n); // P for n sources
-hipError_t gas_launch_biquad_mix(hipStream_t stream, int mode, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t channel_begin, uint32_t channel_count, float mix_rate, float *partials, uint32_t p_offset, uint32_t p_stride, float *rows_out = nullptr /* non-null: per-source rows instead of the partial mix */, const gas_bus_args &buses = gas_bus_args(), int fx_kind = 0 /* GAS_MODE_FX_FILTER: which GAS_FX_* filter */);
+struct gas_biquad_launch {
+	hipStream_t stream = nullptr;
+	int mode = GAS_MODE_COPY;
+	gas_group_args g{};
+	const gas_dev_state *st = nullptr;
+	uint32_t frames = 0;
+	uint32_t channel_begin = 0, channel_count = 1; // a staged chain's stage passes its chain position as channel_begin
+	float mix_rate = 0.0f;
+	float *partials = nullptr;
+	uint32_t p_offset = 0, p_stride = 0;
+	float *rows_out = nullptr; // non-null: per-source rows instead of the partial mix
+	gas_bus_args buses;
+	int fx_kind = 0; // GAS_MODE_FX_FILTER: which GAS_FX_* filter
+	bool scan_ok = true, pipe_ok = true; // the context's GAS_SHELF_SCAN / GAS_BIQUAD_PIPE (gas_switches.h): may the launcher choose k_shelf_scan / k_biquad_pipe
+};
+hipError_t gas_launch_biquad_mix(const gas_biquad_launch &a);
 
 // k_shelf_scan.hip: a rows-out filter stage of a staged chain as a parallel scan over the frames (one wave per source),
 // for callbacks too small to hide the serial recurrence (chosen inside gas_launch_biquad_mix)
-bool gas_shelf_scan_applies(int mode, uint32_t n, uint32_t frames);
-hipError_t gas_launch_shelf_scan(hipStream_t stream, int mode, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t chain_pos, float mix_rate, float *rows_out, int fx_kind);
+bool gas_shelf_scan_applies(bool scan_ok, int mode, uint32_t n, uint32_t frames);
+hipError_t gas_launch_shelf_scan(const gas_biquad_launch &a);
 
 // k_biquad_pipe.hip: the same arithmetic as an eight-wave software pipeline per 32 sources, for callbacks with fewer
 // workgroups than CUs (chosen inside gas_launch_biquad_mix)
-bool gas_biquad_uses_pipe(int mode, uint32_t n, uint32_t channel_count, uint32_t frames, bool rows_out); // the launcher's choice
-hipError_t gas_launch_biquad_pipe(hipStream_t stream, int mode, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t channel_begin, uint32_t channel_count, float mix_rate, float *partials, uint32_t p_offset, uint32_t p_stride, const gas_bus_args &buses = gas_bus_args());
+bool gas_biquad_uses_pipe(bool pipe_ok, int mode, uint32_t n, uint32_t channel_count, uint32_t frames, bool rows_out); // the launcher's choice
+hipError_t gas_launch_biquad_pipe(const gas_biquad_launch &a);
 
 struct gas_hrtf_launch_plan {
 	uint32_t wgs_fd, wgs_pk; // workgroups = partial mixes written
@@ -626,7 +641,6 @@ hipError_t gas_launch_stream_probe(hipStream_t stream, const void *rd, uint64_t 
 #define GAS_DIR_ORDER_MIN_SOURCES 512
 bool gas_dir_order_supported(uint32_t dirs);
 // k_xcd_order (k_misc.hip): XCD-affine processing order for a k_hrtf_uni launch of hrtf_wgs workgroups (multiple of 8)
-#define GAS_XCD_ORDER_AUTO_MIN 0xFFFFFFFFu // callbacks of at least this many sources are ordered without the flag: never (measured: no net gain at any size); the environment variable of the same name overrides for experiments
 hipError_t gas_launch_xcd_order(hipStream_t stream, const gas_group_args &g, const gas_params *params, const gas_params *fresh, uint32_t dirs, uint32_t hrtf_wgs, uint32_t waves_per_wg, uint32_t *order);
 uint32_t gas_hrtf_uni_waves();
 bool gas_hrtf_uni_twelve(uint32_t n, bool streams, bool buses); // whether a callback of n plain-[HRTF] sources runs k_hrtf_uni's twelve-wave form (its sums differ from the eight-wave form's in the last bits)

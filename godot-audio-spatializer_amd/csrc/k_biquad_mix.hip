@@ -19,8 +19,6 @@
 //
 // Bound: HBM once N is large (algorithmic bytes/source = F*8 source + 80 state r/w + 128 params + 8 peak);
 // at N = 256 it is latency-bound on the F-step recurrence (8 waves on a 256-CU part) -- DESIGN.md.
-#include <cstdlib>
-
 #include "gas_biquad.h"
 
 // No FMA contraction in this file.  The recurrence is f32 with poles that approach the unit circle at low cutoffs /
@@ -32,17 +30,12 @@
 
 namespace {
 
-#ifndef GAS_BQ_NT
-#define GAS_BQ_NT 1 // the staging loads of the (once-touched) source rows are non-temporal: 65 536 sources 79.8 -> 73.2 us per launch (round 3, profiles/r03_notes.md); no effect at 256 sources
-#endif
+// the staging loads of the (once-touched) source rows are non-temporal: 65 536 sources 79.8 -> 73.2 us per launch
+// (round 3, profiles/r03_notes.md); no effect at 256 sources
 typedef float bq_v4f __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ float4 bq_row_load(const float *p) {
-#if GAS_BQ_NT
 	const bq_v4f v = __builtin_nontemporal_load(reinterpret_cast<const bq_v4f *>(p));
 	return make_float4(v.x, v.y, v.z, v.w);
-#else
-	return *reinterpret_cast<const float4 *>(p);
-#endif
 }
 
 constexpr int SRC_PER_WG = 32;
@@ -424,47 +417,46 @@ uint32_t gas_biquad_partials(uint32_t n) {
 }
 
 // Few workgroups (no more than CUs): the launch is bound by one lane's dependent chain, not by memory -> the
-// eight-wave software pipeline of k_biquad_pipe.hip (bitwise the same results).  GAS_BIQUAD_PIPE=0 keeps the
-// single-wave kernel (development A/B; read per launch so that a test can switch inside one process).
-bool gas_biquad_uses_pipe(int mode, uint32_t n, uint32_t channel_count, uint32_t frames, bool rows_out) {
-	const char *pipe_env = std::getenv("GAS_BIQUAD_PIPE");
-	const bool pipe_on = !(pipe_env && pipe_env[0] == '0');
-	return pipe_on && !rows_out && mode != GAS_MODE_COPY && mode != GAS_MODE_FX_FILTER && mode != GAS_MODE_FX_AMPLIFY && gas_biquad_partials(n) * channel_count <= 256 && frames % 32 == 0;
+// eight-wave software pipeline of k_biquad_pipe.hip (bitwise the same results).  pipe_ok: the context's GAS_BIQUAD_PIPE,
+// read when the context was created (0 keeps the single-wave kernel, development A/B); a later change of the variable
+// does not reach that context.
+bool gas_biquad_uses_pipe(bool pipe_ok, int mode, uint32_t n, uint32_t channel_count, uint32_t frames, bool rows_out) {
+	return pipe_ok && !rows_out && mode != GAS_MODE_COPY && mode != GAS_MODE_FX_FILTER && mode != GAS_MODE_FX_AMPLIFY && gas_biquad_partials(n) * channel_count <= 256 && frames % 32 == 0;
 }
 
-hipError_t gas_launch_biquad_mix(hipStream_t stream, int mode, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t channel_begin, uint32_t channel_count, float mix_rate, float *partials, uint32_t p_offset, uint32_t p_stride, float *rows_out, const gas_bus_args &buses, int fx_kind) {
-	if (g.n == 0) {
+hipError_t gas_launch_biquad_mix(const gas_biquad_launch &a) {
+	if (a.g.n == 0) {
 		return hipSuccess;
 	}
-	if (rows_out && channel_count == 1 && g.slots && gas_shelf_scan_applies(mode, g.n, frames)) {
-		return gas_launch_shelf_scan(stream, mode, g, st, frames, channel_begin, mix_rate, rows_out, fx_kind);
+	if (a.rows_out && a.channel_count == 1 && a.g.slots && gas_shelf_scan_applies(a.scan_ok, a.mode, a.g.n, a.frames)) {
+		return gas_launch_shelf_scan(a);
 	}
-	dim3 grid(gas_biquad_partials(g.n), channel_count);
-	dim3 block(64);
-	if (gas_biquad_uses_pipe(mode, g.n, channel_count, frames, rows_out != nullptr)) {
-		return gas_launch_biquad_pipe(stream, mode, g, st, frames, channel_begin, channel_count, mix_rate, partials, p_offset, p_stride, buses);
+	if (gas_biquad_uses_pipe(a.pipe_ok, a.mode, a.g.n, a.channel_count, a.frames, a.rows_out != nullptr)) {
+		return gas_launch_biquad_pipe(a);
 	}
-	switch (mode) {
+	decltype(&k_biquad_mix<GAS_MODE_COPY>) k = nullptr;
+	switch (a.mode) {
 		case GAS_MODE_MIX_CHANNEL:
-			hipLaunchKernelGGL(k_biquad_mix<GAS_MODE_MIX_CHANNEL>, grid, block, 0, stream, g, st, frames, channel_begin, mix_rate, partials, p_offset, p_stride, rows_out, buses, fx_kind);
+			k = k_biquad_mix<GAS_MODE_MIX_CHANNEL>;
 			break;
 		case GAS_MODE_PROCESS_FRAMES:
-			hipLaunchKernelGGL(k_biquad_mix<GAS_MODE_PROCESS_FRAMES>, grid, block, 0, stream, g, st, frames, channel_begin, mix_rate, partials, p_offset, p_stride, rows_out, buses, fx_kind);
+			k = k_biquad_mix<GAS_MODE_PROCESS_FRAMES>;
 			break;
 		case GAS_MODE_FX_HIGHSHELF:
-			hipLaunchKernelGGL(k_biquad_mix<GAS_MODE_FX_HIGHSHELF>, grid, block, 0, stream, g, st, frames, channel_begin, mix_rate, partials, p_offset, p_stride, rows_out, buses, fx_kind);
+			k = k_biquad_mix<GAS_MODE_FX_HIGHSHELF>;
 			break;
 		case GAS_MODE_FX_FILTER:
-			hipLaunchKernelGGL(k_biquad_mix<GAS_MODE_FX_FILTER>, grid, block, 0, stream, g, st, frames, channel_begin, mix_rate, partials, p_offset, p_stride, rows_out, buses, fx_kind);
+			k = k_biquad_mix<GAS_MODE_FX_FILTER>;
 			break;
 		case GAS_MODE_FX_AMPLIFY:
-			hipLaunchKernelGGL(k_biquad_mix<GAS_MODE_FX_AMPLIFY>, grid, block, 0, stream, g, st, frames, channel_begin, mix_rate, partials, p_offset, p_stride, rows_out, buses, fx_kind);
+			k = k_biquad_mix<GAS_MODE_FX_AMPLIFY>;
 			break;
 		case GAS_MODE_COPY:
-			hipLaunchKernelGGL(k_biquad_mix<GAS_MODE_COPY>, grid, block, 0, stream, g, st, frames, channel_begin, mix_rate, partials, p_offset, p_stride, rows_out, buses, fx_kind);
+			k = k_biquad_mix<GAS_MODE_COPY>;
 			break;
 		default:
 			return hipErrorInvalidValue;
 	}
+	hipLaunchKernelGGL(k, dim3(gas_biquad_partials(a.g.n), a.channel_count), dim3(64), 0, a.stream, a.g, *a.st, a.frames, a.channel_begin, a.mix_rate, a.partials, a.p_offset, a.p_stride, a.rows_out, a.buses, a.fx_kind);
 	return hipGetLastError();
 }

@@ -465,46 +465,33 @@ __global__ __launch_bounds__(N_WAVES * 64) void k_biquad_pipe(gas_group_args g, 
 	}
 }
 
+// all_filt: the caller knows that every source of the launch takes the filter branch (FX_HIGHSHELF always does); the
+// general variant selects per lane.
 template <int MODE>
-void launch_pipe(hipStream_t stream, dim3 grid, bool f_pow2, bool all_filt, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t channel_begin, float mix_rate, float *partials, uint32_t p_offset, uint32_t p_stride, const gas_bus_args &buses) {
-	dim3 block(N_WAVES * 64);
-	if (f_pow2) {
-		if (all_filt) {
-			hipLaunchKernelGGL((k_biquad_pipe<MODE, true, true>), grid, block, 0, stream, g, st, frames, channel_begin, mix_rate, partials, p_offset, p_stride, buses);
-		} else {
-			hipLaunchKernelGGL((k_biquad_pipe<MODE, true, false>), grid, block, 0, stream, g, st, frames, channel_begin, mix_rate, partials, p_offset, p_stride, buses);
-		}
-	} else {
-		if (all_filt) {
-			hipLaunchKernelGGL((k_biquad_pipe<MODE, false, true>), grid, block, 0, stream, g, st, frames, channel_begin, mix_rate, partials, p_offset, p_stride, buses);
-		} else {
-			hipLaunchKernelGGL((k_biquad_pipe<MODE, false, false>), grid, block, 0, stream, g, st, frames, channel_begin, mix_rate, partials, p_offset, p_stride, buses);
-		}
-	}
+void launch_pipe(const gas_biquad_launch &a, bool all_filt) {
+	const bool f_pow2 = (a.frames & (a.frames - 1)) == 0;
+	const auto k = f_pow2 ? (all_filt ? k_biquad_pipe<MODE, true, true> : k_biquad_pipe<MODE, true, false>) : (all_filt ? k_biquad_pipe<MODE, false, true> : k_biquad_pipe<MODE, false, false>);
+	hipLaunchKernelGGL(k, dim3(gas_biquad_partials(a.g.n), a.channel_count), dim3(N_WAVES * 64), 0, a.stream, a.g, *a.st, a.frames, a.channel_begin, a.mix_rate, a.partials, a.p_offset, a.p_stride, a.buses);
 }
 
 } // namespace
 
-// all_filt: the caller knows that every source of the launch takes the filter branch (FX_HIGHSHELF always does); the
-// general variant selects per lane.
-hipError_t gas_launch_biquad_pipe(hipStream_t stream, int mode, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t channel_begin, uint32_t channel_count, float mix_rate, float *partials, uint32_t p_offset, uint32_t p_stride, const gas_bus_args &buses) {
-	if (g.n == 0) {
+hipError_t gas_launch_biquad_pipe(const gas_biquad_launch &a) {
+	if (a.g.n == 0) {
 		return hipSuccess;
 	}
-	if (frames % KF != 0) {
+	if (a.frames % KF != 0) {
 		return hipErrorInvalidValue;
 	}
-	dim3 grid(gas_biquad_partials(g.n), channel_count);
-	const bool f_pow2 = (frames & (frames - 1)) == 0;
-	switch (mode) {
+	switch (a.mode) {
 		case GAS_MODE_MIX_CHANNEL:
-			launch_pipe<GAS_MODE_MIX_CHANNEL>(stream, grid, f_pow2, false, g, st, frames, channel_begin, mix_rate, partials, p_offset, p_stride, buses);
+			launch_pipe<GAS_MODE_MIX_CHANNEL>(a, false);
 			break;
 		case GAS_MODE_PROCESS_FRAMES:
-			launch_pipe<GAS_MODE_PROCESS_FRAMES>(stream, grid, f_pow2, false, g, st, frames, channel_begin, mix_rate, partials, p_offset, p_stride, buses);
+			launch_pipe<GAS_MODE_PROCESS_FRAMES>(a, false);
 			break;
 		case GAS_MODE_FX_HIGHSHELF:
-			launch_pipe<GAS_MODE_FX_HIGHSHELF>(stream, grid, f_pow2, true, g, st, frames, channel_begin, mix_rate, partials, p_offset, p_stride, buses);
+			launch_pipe<GAS_MODE_FX_HIGHSHELF>(a, true);
 			break;
 		default:
 			return hipErrorInvalidValue;

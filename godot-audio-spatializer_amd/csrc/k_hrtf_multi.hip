@@ -20,10 +20,6 @@
 // Source rows are loaded non-temporal here: in a batched launch the HRIR rows ARE reused (the next block of an unchanged
 // direction meets them again), and once-touched frames that do not displace them from the L2 are worth 4.5 % of the
 // launch (10.65 vs 11.15 us per block, profiles/r02_notes.md).  The single-block kernels show no difference.
-#define GAS_USE_NT 1
-#ifndef GAS_MULTI_L2_PREFETCH
-#define GAS_MULTI_L2_PREFETCH 0 // EXPERIMENT (off): touch the rows of the source two trips ahead, one dword per 128-byte line.  Measured SLOWER (8192 sources: 12.0 vs 11.2 us per block; 65536: 87.7 vs 75.1): the launch is bound by what the fabric moves, not by one wave's load latency, and the touches add L2 -> L1 traffic (profiles/r03_notes.md)
-#endif
 #include "gas_hrtf_wave.h"
 
 namespace {
@@ -159,9 +155,6 @@ __global__ __launch_bounds__(MW * 64, GAS_HRTF_WAVES_PER_SIMD) void k_hrtf_multi
 		t2[k] = tw_lds[(8 + k) * 64 + lane];
 	}
 	const float lane_f = (float)lane;
-#if GAS_MULTI_L2_PREFETCH
-	uint32_t pf_word = 0; // the word of the line touch in flight
-#endif
 
 	for (uint32_t b = 0; b < K; b++) {
 		float *peaks_b = mb.peaks[b];
@@ -301,24 +294,6 @@ __global__ __launch_bounds__(MW * 64, GAS_HRTF_WAVES_PER_SIMD) void k_hrtf_multi
 			}
 			fft512<false>(zs, t1, t2, lds, lane);
 			products(true, dir);
-#if GAS_MULTI_L2_PREFETCH
-			// The row of the source TWO trips ahead is pulled towards the L2 by one dword load per 128-byte line (no
-			// landing set: the loaded word is never looked at), issued behind this trip's requests AND behind the
-			// table row's (the wave's vector-memory results return in order; when this was measured the compiler's wait in
-			// front of the spectral products was vmcnt(0), so anything requested before them was waited for there -- it now
-			// leaves the row request in flight, and this conditional touch would put a path-dependent operation back into
-			// the queue).  A trip's own requests then find their lines a cache hit away instead of an HBM round trip under
-			// load (profiles/r03_notes.md).  The word requested a trip ago is retired first (it has landed long since).
-			{
-				asm volatile("" ::"v"(pf_word));
-				const uint32_t i2 = i + 2, over = i2 / cnt, ni2 = i2 - over * cnt; // cnt >= 1; over <= 2
-				if (b + over < K) {
-					const uint32_t row2 = (uint32_t)__builtin_amdgcn_readlane((int)my_row, (int)ni2);
-					const char *p2 = reinterpret_cast<const char *>(mb.src[b + over] + (size_t)row2 * F);
-					pf_word = *reinterpret_cast<const uint32_t *>(p2 + ((uint32_t)lane * 128u) % (F * 8u));
-				}
-			}
-#endif
 #pragma unroll
 			for (int j = 0; j < 8; j++) {
 				zp[j] = zs[j];

@@ -30,7 +30,6 @@
 // part of the figure: the kernel reads its two HRTF fields, one 8-byte load.)  This file keeps the forms with
 // crossfade / direction runs / early reflections / per-source rows; the plain [HRTF] callback runs k_hrtf_uni.hip.
 // source rows non-temporal, like k_hrtf_uni (round 3): the cross-fade form gains 3 %, [ER, HRTF] nothing
-#define GAS_USE_NT 1
 #include "gas_hrtf_wave.h"
 
 namespace {
@@ -137,15 +136,15 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 	// twiddles: the workgroup's 512 threads fetch the 8 KiB table once (16 bytes each) and park it in LDS; the
 	// per-wave register copies are filled from there after the first barrier (below, behind the metadata loads)
 	float4 tw_in = make_float4(0.f, 0.f, 0.f, 0.f);
-	if (GAS_TW_LDS && !(GAS_ABL & 16)) {
+	if (!(GAS_ABL & 16)) {
 		tw_in = reinterpret_cast<const float4 *>(tw)[threadIdx.x];
 	}
 	float2 t1[8], t2[8];
-	if (!GAS_TW_LDS || (GAS_ABL & 16)) {
+	if (GAS_ABL & 16) {
 #pragma unroll
 		for (int k = 0; k < 8; k++) {
-			t1[k] = (GAS_ABL & 16) ? make_float2(0.001f * (float)(lane + k), 1.0f) : tw[k * 64 + lane];
-			t2[k] = (GAS_ABL & 16) ? make_float2(1.0f, 0.002f * (float)(lane - k)) : tw[(8 + k) * 64 + lane];
+			t1[k] = make_float2(0.001f * (float)(lane + k), 1.0f);
+			t2[k] = make_float2(1.0f, 0.002f * (float)(lane - k));
 		}
 	}
 
@@ -214,12 +213,11 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 
 	// in-flight buffers of the software pipeline
 	float4 hs[8]; // spectra (HL.re, HL.im, HR.re, HR.im) of bins lane + 64 j
-#ifndef GAS_HRTF_STAGES
-#define GAS_HRTF_STAGES 1 // 2 was measured no faster (17.7 vs 16.6 us at 8192 sources): the loop is not latency-bound per wave
-#endif
-	constexpr int STAGES = (WITH_ER || SRC_PCM || XFADE) ? 1 : GAS_HRTF_STAGES;
-	gas_audio_frame raw[STAGES][FQ]; // frames lane + 64 q of the source row
-	float rawh[STAGES][HQ]; // history samples lane + 64 q
+	gas_audio_frame raw[FQ]; // frames lane + 64 q of the source row
+	float rawh[HQ]; // history samples lane + 64 q
+	// Shape kept from a two-sources-per-trip form that was no faster: the single-trip `s` loops here and
+	// around the source loop's body, and `ma`, a second broadcast of `mn`.  They compute nothing of their own, but the
+	// compiler's code for every kernel of this file changes when one of them goes (profiles/switches_notes.md).
 	// Prologue, ordered so that no load waits behind one it does not depend on:
 	//   level 1  slot / row of each of this wave's sources (one lane per source; no load at all when the
 	//            callback's slots are a contiguous range and the rows are in order)
@@ -246,14 +244,6 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 		// `fresh`: parameter rows published from device memory for exactly this callback's list (row order) and not
 		// yet scattered: consume them here and write them through to the slot table (saves the scatter launch).
 		const gas_params *P = fresh ? fresh + lm.row : st.params + lm.slot;
-		if (fresh && !GAS_DEFER_WT && !(GAS_ABL & 128)) {
-			const float4 *src4 = reinterpret_cast<const float4 *>(P);
-			float4 *dst4 = reinterpret_cast<float4 *>(st.params + lm.slot);
-#pragma unroll
-			for (int k = 0; k < 8; k++) {
-				dst4[k] = src4[k];
-			}
-		}
 		const float2 gd = (GAS_ABL & 128) ? make_float2(1.0f, __uint_as_float(lm.slot & 1023u)) : *reinterpret_cast<const float2 *>(&P->hrtf_gain); // hrtf_gain, hrtf_dir: one 8-byte load
 		lm.g0 = (GAS_ABL & 128) ? 0.5f : st.hrtf_prev_gain[lm.slot];
 		lm.g1 = gd.x;
@@ -340,25 +330,21 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 	}
 	if (first < last) {
 #pragma unroll
-		for (int s = 0; s < STAGES; s++) {
-			if (first + s < last) { // wave-uniform
-				SrcMeta ms{};
-				ms.slot = (uint32_t)__builtin_amdgcn_readlane((int)lm.slot, s);
-				ms.row = (uint32_t)__builtin_amdgcn_readlane((int)lm.row, s);
-				if (!(GAS_ABL & 2)) {
-					load_history<HQ>(st.hrtf_hist + (size_t)ms.slot * HL, lane, rawh[s]);
-				}
-				if constexpr (!WITH_ER && !SRC_PCM) {
-					load_window<false, FQ>(g, ms, lane, fade_env, raw[s]); // needs the row only
-				}
+		for (int s = 0; s < 1; s++) {
+			SrcMeta ms{};
+			ms.slot = (uint32_t)__builtin_amdgcn_readlane((int)lm.slot, s);
+			ms.row = (uint32_t)__builtin_amdgcn_readlane((int)lm.row, s);
+			if (!(GAS_ABL & 2)) {
+				load_history<HQ>(st.hrtf_hist + (size_t)ms.slot * HL, lane, rawh);
+			}
+			if constexpr (!WITH_ER && !SRC_PCM) {
+				load_window<false, FQ>(g, ms, lane, fade_env, raw); // needs the row only
 			}
 		}
 		if constexpr (!WITH_ER && SRC_PCM) {
 #pragma unroll
-			for (int s = 0; s < STAGES; s++) {
-				if (first + s < last) {
-					load_window<true, FQ, LOOPS>(g, bcast_meta<SRC_PCM, LOOPS>(lm, s, F), lane, fade_env, raw[s], cursors); // needs the cursor
-				}
+			for (int s = 0; s < 1; s++) {
+				load_window<true, FQ, LOOPS>(g, bcast_meta<SRC_PCM, LOOPS>(lm, s, F), lane, fade_env, raw, cursors); // needs the cursor
 			}
 		}
 		if constexpr (!SKEW) {
@@ -366,7 +352,7 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 		}
 	}
 
-	if (GAS_TW_LDS && !(GAS_ABL & 16)) {
+	if (!(GAS_ABL & 16)) {
 		reinterpret_cast<float4 *>(tw_lds)[threadIdx.x] = tw_in;
 		__syncthreads();
 #pragma unroll
@@ -415,26 +401,21 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 		}
 	};
 
-	// STAGES sources per trip, each with its own landing registers: while source e transforms, the frames and
-	// history of sources e+1 .. e+STAGES are in flight.
-	for (uint32_t e0 = first; e0 < last; e0 += STAGES) {
+	// One source per trip: while source e transforms, the frames and history of source e + 1 are in flight.
+	for (uint32_t e0 = first; e0 < last; e0 += 1) {
 #pragma unroll
-		for (int s = 0; s < STAGES; s++) {
+		for (int s = 0; s < 1; s++) {
 		const uint32_t e = e0 + s;
-		if (e >= last) { // wave-uniform
-			continue;
-		}
 		const bool has_next = e + 1 < last;
-		const bool has_ahead = e + STAGES < last;
 		const SrcMeta m = bcast_meta<SRC_PCM, LOOPS>(lm, e - first, F);
 		const SrcMeta mn = bcast_meta<SRC_PCM, LOOPS>(lm, has_next ? e + 1 - first : e - first, F);
-		const SrcMeta ma = bcast_meta<SRC_PCM, LOOPS>(lm, has_ahead ? e + STAGES - first : e - first, F);
+		const SrcMeta ma = bcast_meta<SRC_PCM, LOOPS>(lm, has_next ? e + 1 - first : e - first, F);
 
 		// x_full[lane + 64 q]: q < HQ from the history, the rest from this callback's frames.
 		float xq[NQ];
 #pragma unroll
 		for (int q = 0; q < HQ; q++) {
-			xq[q] = rawh[s][q];
+			xq[q] = rawh[q];
 		}
 		if constexpr (WITH_ER) {
 			// early reflections (oracle fx_early_reflections): taps in order, f32.  The 64 gathers per
@@ -444,7 +425,7 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 			const uint32_t er_pos = st.er_pos[m.slot];
 			gas_audio_frame *ring = st.er_ring + (size_t)m.slot * er_R;
 			float *xs = reinterpret_cast<float *>(lds);
-#ifndef GAS_ER_PAIRS // the product form: a lane owns frames lane + 64 q, 8-byte accesses, 16 tap loads in flight (two round trips per source at F = 256)
+			// a lane owns frames lane + 64 q, 8-byte accesses, 16 tap loads in flight (two round trips per source at F = 256)
 #pragma unroll 2 // 16 tap loads in flight per trip (4 spills, 1 serialises four round trips per source)
 			for (int q = 0; q < FQ; q++) {
 				const int f = lane + 64 * q;
@@ -464,58 +445,6 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 				}
 				xs[f] = (yl + yr) * 0.5f;
 			}
-#else
-			// EXPERIMENT (round 3, -DGAS_ER_PAIRS, measured SLOWER: cfg5 27.2 vs 22.6 us per launch): a lane owns frame PAIRS
-			// (2 lane, 2 lane + 1) + 128 qq, so the row, the ring store and every tap are 16-byte accesses and the 8 tap
-			// loads of a pass are all in flight at once.  The gathers are 6.6 of the launch's 22.6 us (with them removed the
-			// launch takes 16.0), but halving their instruction count does not pay: odd delays make the 16-byte loads
-			// 8-byte-aligned only, the per-lane pointer selects and the straddle fix-ups add VALU work in front of them.
-			// The results pass through xs[] by frame index, and each frame adds its taps in tap order: the same bits.  A pair straddles the row / ring boundary (first frame still in the ring, second already in
-			// the row: i == -1) or the ring's wrap (ring index er_R - 1) only for odd delays, in one lane per tap: those lanes
-			// fetch their second frame separately.
-			typedef float er_v4f __attribute__((ext_vector_type(4)));
-#pragma unroll
-			for (int qq = 0; qq < FQ / 2; qq++) {
-				const int f0 = 2 * lane + 128 * qq;
-				const er_v4f fr2 = *reinterpret_cast<const er_v4f *>(&srow[f0]);
-				*reinterpret_cast<er_v4f *>(&ring[(er_pos + (uint32_t)f0) & (er_R - 1)]) = fr2; // this block into the ring (er_pos, f0 even: no wrap inside a pair)
-				er_v4f xp2[GAS_ER_TAPS];
-				bool fix[GAS_ER_TAPS];
-				const gas_audio_frame *second[GAS_ER_TAPS];
-#pragma unroll
-				for (int k = 0; k < GAS_ER_TAPS; k++) {
-					const uint32_t du = P->er_delay[k];
-					const int d = (int)(du < er_R - F ? du : er_R - F); // keeps every tap inside row/ring
-					const int i = f0 - d; // first frame of the pair, relative to this callback's row
-					const uint32_t j = (er_pos + (uint32_t)(i + (int)er_R)) & (er_R - 1); // its ring index when i < 0
-					const gas_audio_frame *p0 = i >= 0 ? &srow[i] : &ring[j];
-					// the pair is contiguous unless it straddles row / ring (i == -1) or the ring's end (j == er_R - 1, i < -1)
-					fix[k] = i == -1 || (i < -1 && j == er_R - 1);
-					second[k] = i + 1 >= 0 ? &srow[i + 1] : &ring[(j + 1) & (er_R - 1)];
-					xp2[k] = *reinterpret_cast<const er_v4f *>(fix[k] ? reinterpret_cast<const gas_audio_frame *>(&srow[f0]) : p0); // (a straddling lane loads something harmless here)
-				}
-				float yl0 = fr2.x, yr0 = fr2.y, yl1 = fr2.z, yr1 = fr2.w;
-#pragma unroll
-				for (int k = 0; k < GAS_ER_TAPS; k++) {
-					const float gk = P->er_gain[k];
-					er_v4f x2 = xp2[k];
-					if (fix[k]) { // one lane per tap at most (odd delays): both frames by 8-byte loads
-						const uint32_t du = P->er_delay[k];
-						const int d = (int)(du < er_R - F ? du : er_R - F);
-						const int i = f0 - d;
-						const uint32_t j = (er_pos + (uint32_t)(i + (int)er_R)) & (er_R - 1);
-						const gas_audio_frame a = i >= 0 ? srow[i] : ring[j];
-						const gas_audio_frame b2 = *second[k];
-						x2 = er_v4f{ a.left, a.right, b2.left, b2.right };
-					}
-					yl0 = yl0 + gk * x2.x;
-					yr0 = yr0 + gk * x2.y;
-					yl1 = yl1 + gk * x2.z;
-					yr1 = yr1 + gk * x2.w;
-				}
-				*reinterpret_cast<float2 *>(&xs[f0]) = make_float2((yl0 + yr0) * 0.5f, (yl1 + yr1) * 0.5f);
-			}
-#endif
 			if (lane == 0) {
 				st.er_pos[m.slot] = (er_pos + F) & (er_R - 1);
 			}
@@ -531,7 +460,7 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 #pragma unroll
 			for (int q = 0; q < FQ; q++) {
 				const int f = lane + 64 * q;
-				const float mono = (raw[s][q].left + raw[s][q].right) * 0.5f;
+				const float mono = (raw[q].left + raw[q].right) * 0.5f;
 				const float t = (float)f * (1.0f / (float)F); // exact for F = 128/256/512
 				xq[HQ + q] = mono * (m.g1 * t + (1 - t) * m.g0);
 			}
@@ -555,13 +484,13 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 				}
 			}
 		}
-		// this stage's landing registers are free again: start the frames and history of source e + STAGES
-		if (has_ahead) {
+		// the landing registers are free again: start the frames and history of source e + 1
+		if (has_next) {
 			if (!(GAS_ABL & 2)) {
-				load_history<HQ>(st.hrtf_hist + (size_t)ma.slot * HL, lane, rawh[s]);
+				load_history<HQ>(st.hrtf_hist + (size_t)ma.slot * HL, lane, rawh);
 			}
 			if constexpr (!WITH_ER) {
-				load_window<SRC_PCM, FQ, LOOPS>(g, ma, lane, fade_env, raw[s], cursors);
+				load_window<SRC_PCM, FQ, LOOPS>(g, ma, lane, fade_env, raw, cursors);
 			}
 		}
 
@@ -740,7 +669,7 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 	}
 
 	GAS_STAMP(3);
-	if (GAS_DEFER_WT && have && fresh && !(GAS_ABL & 128)) {
+	if (have && fresh && !(GAS_ABL & 128)) {
 		// the device-published rows this launch consumed go through to the slot table here, off the path to the first
 		// transform (128 bytes per source, one lane each: 64 different cache lines per instruction)
 		const float4 *src4 = reinterpret_cast<const float4 *>(fresh + lm.row);
@@ -823,21 +752,6 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 			if (round == 0) {
 				GAS_STAMP(4);
 			}
-			if (!GAS_EPI_DIRECT) {
-				// every wave folds one eighth of the bins over the WAVES spectra (fixed order), into slot 0
-				constexpr int PER_THREAD = 2 * 512 / (WAVES * 64); // 2 ears x 512 bins over the workgroup
-#pragma unroll
-				for (int r = 0; r < PER_THREAD; r++) {
-					const int idx = threadIdx.x + r * WAVES * 64; // ear * 512 + bin
-					float2 sacc = fd[idx];
-#pragma unroll
-					for (int w = 1; w < WAVES; w++) {
-						sacc = cadd(sacc, fd[w * 2 * 512 + idx]);
-					}
-					fd[idx] = sacc; // only this thread touches column idx: no hazard
-				}
-				__syncthreads();
-			}
 			if constexpr (JOB_OK) {
 				if (job_mine && round == 0) { // waves 2.. idle while 0 and 1 transform: the previous callback's sum
 					if (JOB_LATE) {
@@ -848,24 +762,17 @@ __device__ __forceinline__ void hrtf_body(float2 *lds_all, float2 *tw_lds, const
 			}
 			if (wave < 2) {
 				float2 y[8];
-				if (GAS_EPI_DIRECT) {
-					// wave `ear` adds the WAVES spectra of its ear itself, in wave order (the same association as the
-					// fold above: ((w0 + w1) + w2) + ...), 64 conflict-free 8-byte reads per lane
+				// wave `ear` adds the WAVES spectra of its ear itself, in wave order (((w0 + w1) + w2) + ...), 64
+				// conflict-free 8-byte reads per lane: no fold pass over the workgroup, one barrier and one LDS round trip less
+#pragma unroll
+				for (int j = 0; j < 8; j++) {
+					y[j] = fd[wave * 512 + j * 64 + lane];
+				}
+#pragma unroll
+				for (int w = 1; w < WAVES; w++) {
 #pragma unroll
 					for (int j = 0; j < 8; j++) {
-						y[j] = fd[wave * 512 + j * 64 + lane];
-					}
-#pragma unroll
-					for (int w = 1; w < WAVES; w++) {
-#pragma unroll
-						for (int j = 0; j < 8; j++) {
-							y[j] = cadd(y[j], fd[(w * 2 + wave) * 512 + j * 64 + lane]);
-						}
-					}
-				} else {
-#pragma unroll
-					for (int j = 0; j < 8; j++) {
-						y[j] = fd[wave * 512 + j * 64 + lane];
+						y[j] = cadd(y[j], fd[(w * 2 + wave) * 512 + j * 64 + lane]);
 					}
 				}
 				fft512<true>(y, t1, t2, lds_all + FD_F2 + wave * LDS_F2_HALF, lane);
@@ -919,7 +826,7 @@ template <int SQ, bool WITH_ER, bool SRC_PCM, bool XFADE, bool RUNS>
 __global__ __launch_bounds__(WAVES * 64, GAS_HRTF_WAVES_PER_SIMD) void k_hrtf_ols(gas_group_args g_fd, gas_group_args g_pk, uint32_t wgs_fd, gas_dev_state st, gas_hrtf_table tab, const float2 *__restrict__ tw, uint32_t er_R, float *__restrict__ partials, uint32_t p_offset, gas_cursor *__restrict__ cursors, const float *__restrict__ fade_env, const gas_params *__restrict__ fresh, gas_deferred_reduce job) {
 	constexpr int LDS_F2 = HrtfLds<SQ, false>::TOTAL_F2 > HrtfLds<SQ, true>::TOTAL_F2 ? HrtfLds<SQ, false>::TOTAL_F2 : HrtfLds<SQ, true>::TOTAL_F2;
 	__shared__ float2 lds_all[LDS_F2];
-	__shared__ float2 tw_lds[GAS_TW_LDS ? 1024 : 1];
+	__shared__ float2 tw_lds[1024];
 	if ((GAS_ABL & 256) && wgs_fd != 0xffffffffu) {
 		return;
 	}
@@ -937,7 +844,7 @@ template <int SQ, bool WITH_ER, bool SRC_PCM>
 __global__ __launch_bounds__(WAVES * 64, GAS_HRTF_WAVES_PER_SIMD) void k_hrtf_ols_blend(gas_group_args g_fd, gas_group_args g_pk, uint32_t wgs_fd, gas_dev_state st, gas_hrtf_table tab, const float2 *__restrict__ tw, uint32_t er_R, float *__restrict__ partials, uint32_t p_offset, gas_cursor *__restrict__ cursors, const float *__restrict__ fade_env, const gas_params *__restrict__ fresh) {
 	constexpr int LDS_F2 = HrtfLds<SQ, false>::TOTAL_F2 > HrtfLds<SQ, true>::TOTAL_F2 ? HrtfLds<SQ, false>::TOTAL_F2 : HrtfLds<SQ, true>::TOTAL_F2;
 	__shared__ float2 lds_all[LDS_F2];
-	__shared__ float2 tw_lds[GAS_TW_LDS ? 1024 : 1];
+	__shared__ float2 tw_lds[1024];
 	float *my_partial = partials + ((size_t)p_offset + blockIdx.x) * (size_t)(2 * SQ * 64 * 2);
 	if (blockIdx.x < wgs_fd) {
 		hrtf_body<SQ, WITH_ER, false, SRC_PCM, false, false, true>(lds_all, tw_lds, blockIdx.x, g_fd, st, tab, tw, wgs_fd, er_R, my_partial, cursors, fade_env, fresh);
@@ -949,7 +856,7 @@ __global__ __launch_bounds__(WAVES * 64, GAS_HRTF_WAVES_PER_SIMD) void k_hrtf_ol
 template <int SQ>
 __global__ __launch_bounds__(WAVES * 64, GAS_HRTF_WAVES_PER_SIMD) void k_hrtf_rows_blend(gas_group_args g, gas_dev_state st, gas_hrtf_table tab, const float2 *__restrict__ tw, gas_audio_frame *__restrict__ rows_out) {
 	__shared__ float2 lds_all[HrtfLds<SQ, true>::TOTAL_F2];
-	__shared__ float2 tw_lds[GAS_TW_LDS ? 1024 : 1];
+	__shared__ float2 tw_lds[1024];
 	hrtf_body<SQ, false, true, false, false, false, true>(lds_all, tw_lds, blockIdx.x, g, st, tab, tw, gridDim.x, 0, nullptr, nullptr, nullptr, nullptr, rows_out);
 }
 
@@ -960,7 +867,7 @@ template <int SQ, bool WITH_ER>
 __global__ __launch_bounds__(WAVES * 64, GAS_HRTF_WAVES_PER_SIMD) void k_hrtf_ols_blend_fade(gas_group_args g_fd, gas_group_args g_pk, uint32_t wgs_fd, gas_dev_state st, gas_hrtf_table tab, const float2 *__restrict__ tw, uint32_t er_R, float *__restrict__ partials, uint32_t p_offset, const float *__restrict__ fade_env, const gas_params *__restrict__ fresh) {
 	constexpr int LDS_F2 = HrtfLds<SQ, false>::TOTAL_F2 > HrtfLds<SQ, true>::TOTAL_F2 ? HrtfLds<SQ, false>::TOTAL_F2 : HrtfLds<SQ, true>::TOTAL_F2;
 	__shared__ __attribute__((aligned(16))) float2 lds_all[LDS_F2];
-	__shared__ float2 tw_lds[GAS_TW_LDS ? 1024 : 1];
+	__shared__ float2 tw_lds[1024];
 	__shared__ __attribute__((aligned(16))) float2 fade_lds[WAVES * 1024];
 	float *my_partial = partials + ((size_t)p_offset + blockIdx.x) * (size_t)(2 * SQ * 64 * 2);
 	if (blockIdx.x < wgs_fd) {
@@ -973,7 +880,7 @@ __global__ __launch_bounds__(WAVES * 64, GAS_HRTF_WAVES_PER_SIMD) void k_hrtf_ol
 template <int SQ>
 __global__ __launch_bounds__(WAVES * 64, GAS_HRTF_WAVES_PER_SIMD) void k_hrtf_rows_blend_fade(gas_group_args g, gas_dev_state st, gas_hrtf_table tab, const float2 *__restrict__ tw, gas_audio_frame *__restrict__ rows_out) {
 	__shared__ float2 lds_all[HrtfLds<SQ, true>::TOTAL_F2];
-	__shared__ float2 tw_lds[GAS_TW_LDS ? 1024 : 1];
+	__shared__ float2 tw_lds[1024];
 	__shared__ __attribute__((aligned(16))) float2 fade_lds[WAVES * 256];
 	hrtf_body<SQ, false, true, false, false, false, true, true>(lds_all, tw_lds, blockIdx.x, g, st, tab, tw, gridDim.x, 0, nullptr, nullptr, nullptr, nullptr, rows_out, gas_deferred_reduce(), 0, fade_lds);
 }
@@ -982,7 +889,7 @@ __global__ __launch_bounds__(WAVES * 64, GAS_HRTF_WAVES_PER_SIMD) void k_hrtf_ro
 template <int SQ, bool XFADE>
 __global__ __launch_bounds__(WAVES * 64, GAS_HRTF_WAVES_PER_SIMD) void k_hrtf_rows(gas_group_args g, gas_dev_state st, gas_hrtf_table tab, const float2 *__restrict__ tw, gas_audio_frame *__restrict__ rows_out) {
 	__shared__ float2 lds_all[HrtfLds<SQ, true>::TOTAL_F2];
-	__shared__ float2 tw_lds[GAS_TW_LDS ? 1024 : 1];
+	__shared__ float2 tw_lds[1024];
 	hrtf_body<SQ, false, true, false, XFADE>(lds_all, tw_lds, blockIdx.x, g, st, tab, tw, gridDim.x, 0, nullptr, nullptr, nullptr, nullptr, rows_out);
 }
 

@@ -26,8 +26,6 @@
 // choice below; inside the gate a source's peak stays within 2e-5 of a float64 recurrence (same test; DESIGN.md 3.5 (a)
 // has the measured figures).  NEW arrangement of [ENGINE] arithmetic: parity unpinned like the rest of SURVEY.md
 // Appendix B.
-#include <cstdlib>
-
 #include "gas_biquad.h"
 
 #pragma clang fp contract(off)
@@ -218,36 +216,34 @@ __global__ __launch_bounds__(SCAN_WAVES * 64) void k_shelf_scan(gas_group_args g
 
 // Whether a rows-out filter stage over n sources runs the scan form: callbacks small enough that k_biquad_mix's one
 // wave per 32 sources leaves SIMDs empty (below 32768 sources there are fewer than two of its waves per SIMD), frames a
-// multiple of 128 (a lane owns an even number of frames).  GAS_SHELF_SCAN=0 keeps the serial stage (A/B).
-bool gas_shelf_scan_applies(int mode, uint32_t n, uint32_t frames) {
-	const char *e = std::getenv("GAS_SHELF_SCAN");
-	if (e && e[0] == '0') {
-		return false;
-	}
-	return (mode == GAS_MODE_FX_HIGHSHELF || mode == GAS_MODE_FX_FILTER) && n >= 512 && n < 32768 && frames % 128 == 0 && frames <= 512;
+// multiple of 128 (a lane owns an even number of frames).  scan_ok: the context's GAS_SHELF_SCAN, read when the context
+// was created (0 keeps the serial stage, A/B); a later change of the variable does not reach that context.
+bool gas_shelf_scan_applies(bool scan_ok, int mode, uint32_t n, uint32_t frames) {
+	return scan_ok && (mode == GAS_MODE_FX_HIGHSHELF || mode == GAS_MODE_FX_FILTER) && n >= 512 && n < 32768 && frames % 128 == 0 && frames <= 512;
 }
 
-hipError_t gas_launch_shelf_scan(hipStream_t stream, int mode, const gas_group_args &g, const gas_dev_state &st, uint32_t frames, uint32_t chain_pos, float mix_rate, float *rows_out, int fx_kind) {
-	if (g.n == 0) {
+hipError_t gas_launch_shelf_scan(const gas_biquad_launch &a) {
+	if (a.g.n == 0) {
 		return hipSuccess;
 	}
-	const dim3 grid((g.n + SCAN_WAVES - 1) / SCAN_WAVES), block(SCAN_WAVES * 64);
-	const int hs = mode == GAS_MODE_FX_HIGHSHELF ? 1 : 0;
-	switch (frames / 64) {
+	decltype(&k_shelf_scan<2>) k = nullptr;
+	switch (a.frames / 64) {
 		case 2:
-			hipLaunchKernelGGL(k_shelf_scan<2>, grid, block, 0, stream, g, st, chain_pos, mix_rate, rows_out, hs, fx_kind);
+			k = k_shelf_scan<2>;
 			break;
 		case 4:
-			hipLaunchKernelGGL(k_shelf_scan<4>, grid, block, 0, stream, g, st, chain_pos, mix_rate, rows_out, hs, fx_kind);
+			k = k_shelf_scan<4>;
 			break;
 		case 6:
-			hipLaunchKernelGGL(k_shelf_scan<6>, grid, block, 0, stream, g, st, chain_pos, mix_rate, rows_out, hs, fx_kind);
+			k = k_shelf_scan<6>;
 			break;
 		case 8:
-			hipLaunchKernelGGL(k_shelf_scan<8>, grid, block, 0, stream, g, st, chain_pos, mix_rate, rows_out, hs, fx_kind);
+			k = k_shelf_scan<8>;
 			break;
 		default:
 			return hipErrorInvalidValue;
 	}
+	const dim3 grid((a.g.n + SCAN_WAVES - 1) / SCAN_WAVES), block(SCAN_WAVES * 64);
+	hipLaunchKernelGGL(k, grid, block, 0, a.stream, a.g, *a.st, a.channel_begin, a.mix_rate, a.rows_out, a.mode == GAS_MODE_FX_HIGHSHELF ? 1 : 0, a.fx_kind);
 	return hipGetLastError();
 }

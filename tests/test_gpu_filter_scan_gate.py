@@ -184,3 +184,38 @@ def test_one_launch_form_is_the_two_launch_forms_bits(gas, ob, kind, pop, n, fra
     for b, ((m1, p1), (m0, p0)) in enumerate(zip(got["1"], got["0"])):
         np.testing.assert_array_equal(m1, m0, err_msg=f"block {b}")
         np.testing.assert_array_equal(p1, p0, err_msg=f"block {b}")
+
+
+# ------------------------------------------------------------------------- e. the switch belongs to the context
+def test_shelf_scan_switch_is_read_when_the_context_is_created(gas, monkeypatch):
+    """GAS_SHELF_SCAN is part of a context from its creation on (csrc/gas_switches.h): a context created under
+    GAS_SHELF_SCAN=0 keeps the serial stage after the variable is gone.  [LOWPASS], 512 playbacks, 128 frames -- the
+    smallest callback that scans -- three callbacks, settings republished before each (mid low-passes, which scan:
+    CONTROL).  `frozen` must be `control`'s bits; `default` must differ somewhere, or the case could not tell."""
+
+    def setenv(value):
+        if value is None:
+            monkeypatch.delenv("GAS_SHELF_SCAN", raising=False)
+        else:
+            monkeypatch.setenv("GAS_SHELF_SCAN", value)
+
+    def run(env_at_create, env_at_run):
+        setenv(env_at_create)
+        ctx = gas.SpatializerContext(max_sources=N, frames=128)
+        setenv(env_at_run)  # before the first callback
+        rng, out = np.random.default_rng(9), []
+        with ctx:
+            slots = ctx.source_alloc_many(N, gas.capi.KIND_EFFECT, (S.LP,))
+            for b in range(3):
+                cutoff = (np.linspace(1500.0, 4000.0, N) * (1.0 + 0.1 * b)).astype(np.float32)
+                res = np.linspace(0.5, 0.7, N).astype(np.float32)
+                _publish(gas, ctx, slots, S.LP, cutoff, res, np.ones(N, np.float32), 128)
+                mix, peaks = ctx.process_block(rng.uniform(-0.5, 0.5, (N, 128, 2)).astype(np.float32), slots)
+                out.append((mix.copy(), peaks.copy()))
+        return out
+
+    control, frozen, default = run("0", "0"), run("0", None), run(None, None)
+    for b in range(3):
+        np.testing.assert_array_equal(frozen[b][0], control[b][0], err_msg=f"block {b}: mix")
+        np.testing.assert_array_equal(frozen[b][1], control[b][1], err_msg=f"block {b}: peaks")
+    assert any((d[0] != c[0]).any() or (d[1] != c[1]).any() for d, c in zip(default, control)), "the scan form and the serial stage gave the same bits: the case cannot tell them apart"

@@ -1,5 +1,6 @@
 // gas_ctx_priv.h -- what the units of the C ABI (gas_ctx.hip and gas_ctx_*.hip) share: the context, its types, the
-// error macros and the few helpers of gas_ctx.hip that entries in other units call.  Declarations only.
+// error macros, and what the units call of each other: the launch plan (gas_ctx_run.hip), the effect families
+// (gas_ctx_fx.hip) and the few helpers of gas_ctx.hip that entries in other units call.  Declarations and inlines only.
 #pragma once
 #include <algorithm>
 #include <array>
@@ -91,7 +92,7 @@ struct SlotStamp {
 
 constexpr uint32_t PROFILE_EVENTS = 4096;
 
-// The effect families, in the order their uploads are flushed; k_fx_families describes them.  The
+// The effect families, in the order their uploads are flushed; gas_ctx_fx.hip's table describes them.  The
 // first two have no pool: gas_fx_settings (GAS_FX_LOWPASS .. GAS_FX_AMPLIFY) and gas_fx_dyn_settings.
 enum { FX_BASIC = 0, FX_DYN, FX_LINES, FX_EQ, FX_FILTER, FX_MOD, FX_STEREO, FX_FAMILIES };
 
@@ -443,9 +444,84 @@ hipError_t device_zeroed(gas_ctx *c, T *&p, size_t count) {
 	return e != hipSuccess ? e : hipMemsetAsync(p, 0, count * sizeof(T), c->stream);
 }
 
-// gas_ctx.hip's, called by entries in the other units
+// The plain [HRTF] chain runs in k_hrtf_uni (one uniform launch, exact peaks per source on request) unless a mode
+// only k_hrtf_ols implements is on.
+inline bool uni_ok(const gas_ctx *c) {
+	return (c->cfg.flags & (GAS_FLAG_HRTF_CROSSFADE | GAS_FLAG_DIRECTION_RUNS | GAS_FLAG_DIRECTION_ORDER | GAS_FLAG_HRTF_INTERPOLATE)) == 0;
+}
+
+inline bool blend_on(const gas_ctx *c) {
+	return (c->cfg.flags & GAS_FLAG_HRTF_INTERPOLATE) != 0;
+}
+
+inline bool fade_on(const gas_ctx *c) {
+	return (c->cfg.flags & GAS_FLAG_HRTF_BLEND_FADE) != 0;
+}
+
+inline bool er_fade_on(const gas_ctx *c) {
+	return (c->cfg.flags & GAS_FLAG_ER_TAP_FADE) != 0;
+}
+
+// Marks row s of a slot-indexed host mirror for the next flush; params_mu held.
+inline void mark_dirty(std::vector<uint8_t> &flag, std::vector<uint32_t> &list, uint32_t s) {
+	if (!flag[s]) {
+		flag[s] = 1;
+		list.push_back(s);
+	}
+}
+
+// Where a callback's rows come from: float rows, or "fused" -- none, the HRTF launch samples the bound streams itself.
+struct RowSource {
+	const gas_audio_frame *rows = nullptr; // [n][F]
+	gas_cursor *cursors = nullptr; // non-null: fused, the slot-indexed cursor array
+	const uint8_t *feed = nullptr; // fused only: the feed table when an entry of the list is fed (gas_source_feed_rows)
+	bool fused() const {
+		return cursors != nullptr;
+	}
+};
+
+// One callback over already-grouped entries: everything run_groups is told.
+struct RunArgs {
+	RowSource src;
+	const uint32_t *slots = nullptr; // [n_total] sorted by launch group
+	const uint32_t *rows = nullptr; // [n_total] row of src (and of peaks) per entry, or nullptr (= identity)
+	const Group *groups = nullptr; // [G_COUNT]
+	const std::vector<ChainRange> *ranges = nullptr; // sub-runs of groups[G_FX_GENERIC]
+	uint32_t n_total = 0;
+	gas_audio_frame *out = nullptr;
+	float *peaks = nullptr; // [n_total][2]
+	uint32_t channel_begin = 0, channel_count = 1;
+	int force_mode = -1; // >= 0: the 3D groups run this gas_biquad_mode
+	bool use_order = false; // the context's cached processing orders (d_order) apply
+	bool pipelined = false; // the sum may be left to the next callback (GAS_FLAG_PIPELINED_MIX)
+	const gas_bus_args *buses = nullptr; // gas_process_block_buses over effect kinds: the staged chains' rows are mixed per bus
+	const gas_params *fresh = nullptr; // device-published parameter rows in row order, not yet in the table: the HRTF launches read them and write them through
+};
+
+// gas_ctx_run.hip: what a callback launches
+uint32_t chain_signature(const int32_t *fx, uint32_t n_fx);
+bool chain_has(uint32_t sig, int kind);
+RunArgs own_list(const gas_ctx *c, const RowSource &src, uint32_t n, gas_audio_frame *out, float *peaks);
+gas_group_args own_hrtf_group(const gas_ctx *c, const gas_audio_frame *src, uint32_t n, float *peaks);
+gas_biquad_launch biquad_launch(const gas_ctx *c, int mode, const gas_group_args &g, float *partials, uint32_t p_offset);
+gas_hrtf_uni_launch plain_uni_launch(const gas_ctx *c, const gas_group_args &g, const RowSource &src, float *partials, uint32_t p_offset);
+int run_groups(gas_ctx *c, const RunArgs &a);
+bool batchable(const gas_ctx *c, uint32_t n, bool fused);
 int flush_deferred(gas_ctx *c);
 int join_outputs(gas_ctx *c);
+
+// gas_ctx_fx.hip: the effect families.  Nothing else names their table or a member of FxFamily.
+int family_of(int kind);
+hipError_t fx_launch(const gas_ctx *c, int kind, const gas_group_args &in, uint32_t chain_pos, gas_audio_frame *rows_out);
+int fx_create(gas_ctx *c); // gas_ctx_create: the resident families' tables, staging and mirrors
+int fx_room(const gas_ctx *c, const int32_t *effects, uint32_t n_effects); // gas_source_alloc, alloc_mu held: GAS_OK, GAS_ERR_UNSUPPORTED_CHAIN or GAS_ERR_OUT_OF_SLOTS
+void fx_slot_new(gas_ctx *c, uint32_t s, const int32_t *effects, uint32_t n_effects, uint32_t sig); // ... then the new slot's entries and defaults
+void fx_slot_freed(gas_ctx *c, uint32_t s, uint32_t sig); // apply_pending_frees, alloc_mu held
+void fx_slot_reset(gas_ctx *c, uint32_t s); // gas_source_reset: takes alloc_mu, then params_mu
+int fx_flush(gas_ctx *c, int f);
+bool fx_basic_dirty(const gas_ctx *c); // params_mu held
+
+// gas_ctx.hip's, called by entries in the other units
 int fail_out(int code, int mem, gas_audio_frame *out, size_t out_bytes);
 void feed_drop(gas_ctx *c, uint32_t slot);
 void stream_rows_sync_back(gas_ctx *c);

@@ -1,5 +1,5 @@
 // gas_fx_dyn_check.h -- the rule of gas_fx_dyn_settings (a known distortion mode; compressor ratio, attack and release
-// above zero; a compressor sidechain of 0 .. GAS_MAX_SIDECHAINS), shared by gas_fx_dyn_settings_publish (gas_ctx.hip) and gas_host_set_effect_settings_dyn (the host
+// above zero; a compressor sidechain of 0 .. GAS_MAX_SIDECHAINS), shared by gas_fx_dyn_settings_publish (gas_ctx_fx.hip) and gas_host_set_effect_settings_dyn (the host
 // layer).  Plain C++, no HIP: the host layer is also built for the CPU.  Not part of the ABI.
 #pragma once
 

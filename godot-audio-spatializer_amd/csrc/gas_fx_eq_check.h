@@ -1,5 +1,5 @@
 // gas_fx_eq_check.h -- the range of gas_fx_eq_settings (the engine's band gain range, -60 .. 24 dB), shared by
-// gas_fx_eq_settings_publish (gas_ctx.hip) and gas_host_set_effect_settings_eq (the host layer).  Plain C++, no HIP: the
+// gas_fx_eq_settings_publish (gas_ctx_fx.hip) and gas_host_set_effect_settings_eq (the host layer).  Plain C++, no HIP: the
 // host layer is also built for the CPU.  Not part of the ABI.
 #pragma once
 

@@ -1,5 +1,5 @@
 // gas_fx_filter_check.h -- what gas_fx_filter_settings may hold (the engine's enums and property ranges), shared by
-// gas_fx_filter_settings_publish (gas_ctx.hip) and gas_host_set_effect_settings_filter (the host layer).  Plain C++,
+// gas_fx_filter_settings_publish (gas_ctx_fx.hip) and gas_host_set_effect_settings_filter (the host layer).  Plain C++,
 // no HIP: the host layer is also built for the CPU.  Not part of the ABI.
 #pragma once
 

@@ -1,5 +1,5 @@
 // gas_fx_stereo_check.h -- the ranges of gas_fx_stereo_settings (the engine's property ranges), shared by
-// gas_fx_stereo_settings_publish (gas_ctx.hip) and gas_host_set_effect_settings_stereo (the host layer).  Plain C++,
+// gas_fx_stereo_settings_publish (gas_ctx_fx.hip) and gas_host_set_effect_settings_stereo (the host layer).  Plain C++,
 // no HIP: the host layer is also built for the CPU.  Not part of the ABI.
 #pragma once
 

@@ -180,6 +180,8 @@ def third(n):
 def _er_hrtf_kernel(K, name, n):
     if name == "uni":  # k_hrtf_uni<ER>: frequency-domain entries first, the exact-peak ones behind them (peak_from)
         return "2", K.FLAG_PEAKS_DRAINING_ONLY, third(n)
+    if name == "uni_tail":  # ... the exact-peak entries' slots right behind the others': one slot range, no slot list on the device
+        return "2", K.FLAG_PEAKS_DRAINING_ONLY, np.arange(n) >= n - n // 4
     if name == "ols_fd":  # k_hrtf_ols<WITH_ER>, frequency-domain group only: nothing draining
         return "0", K.FLAG_PEAKS_DRAINING_ONLY, np.zeros(n, bool)
     assert name == "ols_pk"  # k_hrtf_ols<WITH_ER>, exact-peak group only: every playback draining
@@ -227,11 +229,12 @@ def test_er_hrtf_against_the_oracle(gas, ob, monkeypatch, FR, kernel):
     check(render(gas, (ER, HRTF), F, R, params, srcs, flags=flags, draining=np.flatnonzero(exact), hrir=_hrir()), want, exact, what=f"{kernel} F {F} R {R}")
 
 
-@pytest.mark.parametrize("kernel", ER_HRTF_KERNELS)
+@pytest.mark.parametrize("kernel", ER_HRTF_KERNELS + ["uni_tail"])
 def test_er_hrtf_unit_impulse_is_the_closed_form(gas, monkeypatch, kernel):
     """Chain [ER, HRTF] with a unit-impulse HRIR in both ears and hrtf_gain = 1 throughout, through k_hrtf_uni<ER> and both
     forms of k_hrtf_ols<WITH_ER>: both ears are (yl + yr) / 2 of er_ref times the HRTF stage's gain ramp (0 -> 1 over a
-    playback's first callback, 1 afterwards).  Owes nothing to the oracle's HRTF."""
+    playback's first callback, 1 afterwards).  Owes nothing to the oracle's HRTF.  uni_tail: the last quarter of the
+    slots draining, so that both groups' slots form one range (the launch covers it by its base)."""
     F, R, n = 128, 256, 24
     env, flags, exact = _er_hrtf_kernel(gas.capi, kernel, n)
     monkeypatch.setenv("GAS_UNI_ER", env)

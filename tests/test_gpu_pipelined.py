@@ -7,7 +7,9 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 
-def _render(gas, flags, kind, chain, n, F, T, channel_count=1, host_call_at=None, ring=0):
+def _render(gas, flags, kind, chain, n, F, T, channel_count=1, host_call_at=None, ring=0, grow=None):
+    """grow = (t0, n0): the callbacks in front of t0 run the first n0 playbacks, the others all n; the list is passed
+    when it changes and reused in between."""
     import torch
 
     from godot_audio_spatializer_amd import synth
@@ -24,6 +26,7 @@ def _render(gas, flags, kind, chain, n, F, T, channel_count=1, host_call_at=None
     outs = torch.full((T, channel_count, F, 2), float("nan"), device="cuda")
     peaks = torch.zeros(T, n, 2, device="cuda")
     host_mix = None
+    keep = []  # a batched launch reads its callbacks' sources when it runs
     for t in range(T):
         if t % 3 == 0:
             ctx.params_publish_batch(slots, synth.draw_params(rng, n, dirs=48, channel_count=channel_count, frames=F, ring_frames=max(ring, 2 * F)))
@@ -32,8 +35,11 @@ def _render(gas, flags, kind, chain, n, F, T, channel_count=1, host_call_at=None
             host_mix, _ = ctx.process_block(src, slots)
             outs[t] = torch.from_numpy(host_mix).cuda()
             continue
-        d_src = torch.from_numpy(src).cuda()
-        rc = ctx.process_block_raw(d_src.data_ptr(), slots, n, F, outs[t].data_ptr(), peaks[t].data_ptr(), K.MEM_DEVICE)
+        m = grow[1] if grow and t < grow[0] else n
+        d_src = torch.from_numpy(src[:m]).cuda()
+        keep.append(d_src)
+        relist = grow is None or t in (0, grow[0])
+        rc = ctx.process_block_raw(d_src.data_ptr(), slots[:m] if relist else None, m, F, outs[t].data_ptr(), peaks[t].data_ptr(), K.MEM_DEVICE)
         assert rc == 0
     ctx.join_outputs()
     res = outs.clone()  # enqueued on the context's stream: must see every mix
@@ -62,6 +68,22 @@ def test_pipelined_mix_is_bitwise_identical(gas, case):
     pipe, pk1 = _render(gas, K.FLAG_PEAKS_DRAINING_ONLY | K.FLAG_PIPELINED_MIX, **args)
     assert not np.isnan(base).any() and np.abs(base).max() > 0
     assert np.array_equal(base, pipe)
+    assert np.array_equal(pk0, pk1)
+
+
+@pytest.mark.parametrize("mode", ["pipelined", "batched"])
+def test_a_growing_list_joins_before_the_partials_move(gas, mode):
+    """128 plain-[HRTF] playbacks at F = 128 write 16 partial rows, just enough workgroups to carry a pending sum and to
+    batch; from callback 4 on the list has 136 playbacks, 17 rows.  The launch that would carry callback 3's sum needs
+    larger planes first, so the sum is joined in front of the reallocation (run_groups; at batch depth 2
+    run_hrtf_batch, when callbacks 4 and 5 run).  Bitwise the ordered mode."""
+    K = gas.capi
+    args = dict(kind=K.KIND_EFFECT, chain=(K.FX_HRTF,), n=136, F=128, T=8, grow=(4, 128))
+    base, pk0 = _render(gas, K.FLAG_PEAKS_DRAINING_ONLY, **args)
+    extra = K.FLAG_PIPELINED_MIX | (K.FLAG_BATCHED_LAUNCH if mode == "batched" else 0)
+    got, pk1 = _render(gas, K.FLAG_PEAKS_DRAINING_ONLY | extra, **args)
+    assert not np.isnan(base).any() and np.abs(base).max() > 0
+    assert np.array_equal(base, got)
     assert np.array_equal(pk0, pk1)
 
 

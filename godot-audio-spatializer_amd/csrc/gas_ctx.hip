@@ -20,7 +20,7 @@ int flush_pending_params(gas_ctx *c) {
 	}
 	const gas_params *p = c->pending_params;
 	c->pending_params = nullptr;
-	GAS_HIP(c, gas_launch_scatter_params(c->stream, c->st.params, p, c->cached_identity_rows ? c->d_slots : c->d_slots_rows, c->pending_n));
+	GAS_HIP(c, gas_launch_scatter_params(c->stream, c->st.params, p, c->list.identity_rows ? c->list.d_slots : c->list.d_slots_rows, c->pending_n));
 	return GAS_OK;
 }
 
@@ -193,7 +193,7 @@ int apply_pending_frees(gas_ctx *c) {
 		}
 	}
 	c->pending_free.clear();
-	c->cached_n = UINT32_MAX;
+	list_invalidate(c);
 	return GAS_OK;
 }
 
@@ -212,10 +212,9 @@ inline int launch_group(const gas_ctx *c, const SlotInfo &si, bool all_staged) {
 	return si.group;
 }
 
-// Validate + counting-sort the callback's slot list by launch group.  all_staged (gas_process_block_buses over effect
-// kinds): every chain runs staged (rows out), the rows are mixed per bus.
-int build_groups(gas_ctx *c, const uint32_t *slots, uint32_t n, bool all_staged) {
-	uint32_t counts[G_COUNT] = { 0 };
+// build_groups, step 1: may the list run?  Fills counts[] with its entries per launch group.  Writes nothing but the
+// duplicate stamp and makes no HIP call: a rejected list leaves the cached one's arrays as they were.
+int check_list(gas_ctx *c, const uint32_t *slots, uint32_t n, bool all_staged, uint32_t *counts) {
 	c->stamp.next();
 	for (uint32_t i = 0; i < n; i++) {
 		const uint32_t s = slots[i];
@@ -230,24 +229,40 @@ int build_groups(gas_ctx *c, const uint32_t *slots, uint32_t n, bool all_staged)
 		}
 		counts[launch_group(c, c->slots[s], all_staged)]++;
 	}
+	return GAS_OK;
+}
+
+// build_groups, step 2: the counting sort.  Writes each group's offset and count, and h_idx: the slots, then each one's
+// row in the caller's list, in group order (input order kept inside a group).  Returns the number of non-empty groups.
+int sort_by_group(gas_ctx *c, const uint32_t *slots, uint32_t n, bool all_staged, const uint32_t *counts) {
+	SlotList &l = c->list;
 	uint32_t off = 0, cursor[G_COUNT];
 	int nonempty = 0;
 	for (int gt = 0; gt < G_COUNT; gt++) {
-		c->groups[gt].offset = off;
-		c->groups[gt].count = counts[gt];
+		l.groups[gt].offset = off;
+		l.groups[gt].count = counts[gt];
 		cursor[gt] = off;
 		off += counts[gt];
 		nonempty += counts[gt] > 0;
 	}
-	uint32_t *hs = c->h_idx, *hr = c->h_idx + c->cfg.max_sources;
+	uint32_t *hs = l.h_idx, *hr = l.h_idx + c->cfg.max_sources;
 	for (uint32_t i = 0; i < n; i++) {
 		const uint32_t p = cursor[launch_group(c, c->slots[slots[i]], all_staged)]++;
 		hs[p] = slots[i];
 		hr[p] = i;
 	}
-	c->chain_ranges.clear();
-	if (c->groups[G_FX_GENERIC].count) { // runs of equal chains inside the staged group (stable: input order kept within a run)
-		const Group &gg = c->groups[G_FX_GENERIC];
+	return nonempty;
+}
+
+// build_groups, step 3: runs of equal chains inside the staged group (stable: input order kept within a run), as
+// chain_ranges.  h_idx is final behind it, so what is read off the final order is settled here too: which groups are
+// one slot range, and whether the sorted order is the caller's (`nonempty`: sort_by_group's count).
+void chain_runs(gas_ctx *c, int nonempty) {
+	SlotList &l = c->list;
+	uint32_t *hs = l.h_idx, *hr = l.h_idx + c->cfg.max_sources;
+	l.chain_ranges.clear();
+	if (l.groups[G_FX_GENERIC].count) {
+		const Group &gg = l.groups[G_FX_GENERIC];
 		std::vector<uint32_t> order(gg.count);
 		for (uint32_t k = 0; k < gg.count; k++) {
 			order[k] = k;
@@ -262,50 +277,57 @@ int build_groups(gas_ctx *c, const uint32_t *slots, uint32_t n, bool all_staged)
 			hs[gg.offset + k] = ts[k];
 			hr[gg.offset + k] = tr[k];
 			const uint32_t sig = c->slots[ts[k]].chain_sig;
-			if (c->chain_ranges.empty() || c->chain_ranges.back().sig != sig) {
+			if (l.chain_ranges.empty() || l.chain_ranges.back().sig != sig) {
 				ChainRange r;
 				r.sig = sig;
 				r.offset = k;
-				c->chain_ranges.push_back(r);
+				l.chain_ranges.push_back(r);
 			}
-			c->chain_ranges.back().count++;
+			l.chain_ranges.back().count++;
 		}
 	}
 	for (int gt = 0; gt < G_COUNT; gt++) {
-		Group &gr = c->groups[gt];
+		Group &gr = l.groups[gt];
 		gr.contiguous = gr.count > 0;
 		gr.slot_base = gr.count ? hs[gr.offset] : 0;
 		for (uint32_t k = 1; k < gr.count && gr.contiguous; k++) {
 			gr.contiguous = hs[gr.offset + k] == gr.slot_base + k;
 		}
 	}
-	c->cached_identity_rows = nonempty <= 1 && c->chain_ranges.size() <= 1;
-	c->uni_peak_all = c->uni_peak_any = false;
-	if (uni_ok(c) && c->groups[G_FX_HRTF].count > 0) {
-		const Group &gh = c->groups[G_FX_HRTF];
+	l.identity_rows = nonempty <= 1 && l.chain_ranges.size() <= 1;
+}
+
+// build_groups, step 4: which entries report their exact peak -- the plain-[HRTF] group's summary and bits (k_hrtf_uni),
+// then each staged run's.  A table goes to the device only where some entries do and some do not: at most two copies.
+int peak_bits(gas_ctx *c) {
+	SlotList &l = c->list;
+	const uint32_t *hs = l.h_idx;
+	l.uni_peak_all = l.uni_peak_any = false;
+	if (uni_ok(c) && l.groups[G_FX_HRTF].count > 0) {
+		const Group &gh = l.groups[G_FX_HRTF];
 		const uint32_t words = (gh.count + 31) / 32;
-		std::memset(c->h_peak_bits, 0, (size_t)words * sizeof(uint32_t));
+		std::memset(l.h_peak_bits, 0, (size_t)words * sizeof(uint32_t));
 		uint32_t n_peak = 0;
 		for (uint32_t k = 0; k < gh.count; k++) {
 			if (wants_peak(c, c->slots[hs[gh.offset + k]])) {
-				c->h_peak_bits[k >> 5] |= 1u << (k & 31);
+				l.h_peak_bits[k >> 5] |= 1u << (k & 31);
 				n_peak++;
 			}
 		}
-		c->uni_peak_any = n_peak > 0;
-		c->uni_peak_all = n_peak == gh.count;
-		if (c->uni_peak_any && !c->uni_peak_all) {
-			GAS_HIP(c, hipMemcpyAsync(c->d_peak_bits, c->h_peak_bits, (size_t)words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+		l.uni_peak_any = n_peak > 0;
+		l.uni_peak_all = n_peak == gh.count;
+		if (l.uni_peak_any && !l.uni_peak_all) {
+			GAS_HIP(c, hipMemcpyAsync(l.d_peak_bits, l.h_peak_bits, (size_t)words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
 		}
 	}
 	// staged chains whose last stage is k_hrtf_uni: the same rule (an HRTF source that is not draining reports +inf)
-	if (uni_ok(c) && (c->cfg.flags & GAS_FLAG_PEAKS_DRAINING_ONLY) != 0 && c->groups[G_FX_GENERIC].count > 0) {
-		const Group &gg = c->groups[G_FX_GENERIC];
+	if (uni_ok(c) && (c->cfg.flags & GAS_FLAG_PEAKS_DRAINING_ONLY) != 0 && l.groups[G_FX_GENERIC].count > 0) {
+		const Group &gg = l.groups[G_FX_GENERIC];
 		const uint32_t half = (c->cfg.max_sources + 31) / 32, words = (gg.count + 31) / 32;
-		uint32_t *bits = c->h_peak_bits + half;
+		uint32_t *bits = l.h_peak_bits + half;
 		std::memset(bits, 0, (size_t)words * sizeof(uint32_t));
 		bool partial = false;
-		for (ChainRange &r : c->chain_ranges) {
+		for (ChainRange &r : l.chain_ranges) {
 			uint32_t n_peak = 0;
 			for (uint32_t k = r.offset; k < r.offset + r.count; k++) {
 				if (wants_peak(c, c->slots[hs[gg.offset + k]])) {
@@ -318,25 +340,47 @@ int build_groups(gas_ctx *c, const uint32_t *slots, uint32_t n, bool all_staged)
 			partial = partial || (r.peak_any && !r.peak_all);
 		}
 		if (partial) {
-			GAS_HIP(c, hipMemcpyAsync(c->d_peak_bits + half, bits, (size_t)words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+			GAS_HIP(c, hipMemcpyAsync(l.d_peak_bits + half, bits, (size_t)words * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
 		}
 	}
-	if (n > 0) {
-		GAS_HIP(c, hipMemcpyAsync(c->d_slots, hs, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-		if (!c->cached_identity_rows) {
-			GAS_HIP(c, hipMemcpyAsync(c->d_rows, hr, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-			GAS_HIP(c, hipMemcpyAsync(c->d_slots_rows, slots, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-		}
-		GAS_HIP(c, hipStreamSynchronize(c->stream)); // h_idx is reused by the next list
-	}
-	c->cached_n = n;
-	c->groups_gen++;
 	return GAS_OK;
 }
 
+// build_groups, step 5: the sorted slots -- with the rows and the caller's order where the order is not the caller's
+// -- to the device, and the commit: the only step that sets `valid` and `n` and starts a generation.
+int upload_commit(gas_ctx *c, const uint32_t *slots, uint32_t n) {
+	SlotList &l = c->list;
+	const uint32_t *hs = l.h_idx, *hr = l.h_idx + c->cfg.max_sources;
+	if (n > 0) {
+		GAS_HIP(c, hipMemcpyAsync(l.d_slots, hs, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+		if (!l.identity_rows) {
+			GAS_HIP(c, hipMemcpyAsync(l.d_rows, hr, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+			GAS_HIP(c, hipMemcpyAsync(l.d_slots_rows, slots, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+		}
+		GAS_HIP(c, hipStreamSynchronize(c->stream)); // h_idx is reused by the next list
+	}
+	l.valid = true;
+	l.n = n;
+	l.gen++;
+	return GAS_OK;
+}
+
+// The callback's slot list becomes c->list: validated and counting-sorted by launch group.  The cached list is given
+// up first, so a list that is rejected, or whose upload fails, leaves none to reuse.  all_staged
+// (gas_process_block_buses over effect kinds): every chain runs staged (rows out), the rows are mixed per bus.
+int build_groups(gas_ctx *c, const uint32_t *slots, uint32_t n, bool all_staged) {
+	list_invalidate(c);
+	uint32_t counts[G_COUNT] = { 0 };
+	GAS_TRY(check_list(c, slots, n, all_staged, counts));
+	const int nonempty = sort_by_group(c, slots, n, all_staged, counts);
+	chain_runs(c, nonempty);
+	GAS_TRY(peak_bits(c));
+	return upload_commit(c, slots, n);
+}
+
 int needs_hrtf(const gas_ctx *c) {
-	bool any = c->groups[G_FX_HRTF].count > 0 || c->groups[G_FX_ER_HRTF].count > 0 || c->groups[G_FX_HRTF_PK].count > 0 || c->groups[G_FX_ER_HRTF_PK].count > 0;
-	for (const ChainRange &r : c->chain_ranges) {
+	bool any = c->list.groups[G_FX_HRTF].count > 0 || c->list.groups[G_FX_ER_HRTF].count > 0 || c->list.groups[G_FX_HRTF_PK].count > 0 || c->list.groups[G_FX_ER_HRTF_PK].count > 0;
+	for (const ChainRange &r : c->list.chain_ranges) {
 		any = any || chain_has(r.sig, GAS_FX_HRTF);
 	}
 	return any && c->tab.spec == nullptr;
@@ -475,9 +519,9 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 		GAS_TRY(fx_create(c)); // the effect families that need no reservation for their settings
 		GAS_HIP(c, c->mem.alloc(c->d_upload, N));
 		GAS_HIP(c, c->mem.alloc(c->d_upload_slots, N));
-		GAS_HIP(c, c->mem.alloc(c->d_slots, N));
-		GAS_HIP(c, c->mem.alloc(c->d_rows, N));
-		GAS_HIP(c, c->mem.alloc(c->d_slots_rows, N));
+		GAS_HIP(c, c->mem.alloc(c->list.d_slots, N));
+		GAS_HIP(c, c->mem.alloc(c->list.d_rows, N));
+		GAS_HIP(c, c->mem.alloc(c->list.d_slots_rows, N));
 		GAS_HIP(c, c->mem.alloc(c->d_out, cfg->channel_count * cfg->frames));
 		GAS_HIP(c, c->mem.alloc(c->d_peaks, 2 * N));
 		GAS_HIP(c, c->mem.alloc(c->d_one_slot, 1));
@@ -508,9 +552,9 @@ int gas_ctx_create(const gas_config *cfg, gas_ctx **out_ctx) {
 		GAS_HIP(c, c->mem.alloc(c->h_params, N, Mem::PINNED));
 		GAS_HIP(c, c->mem.alloc(c->h_upload, N, Mem::PINNED));
 		GAS_HIP(c, c->mem.alloc(c->h_upload_slots, N, Mem::PINNED));
-		GAS_HIP(c, c->mem.alloc(c->h_idx, 2 * N, Mem::PINNED));
-		GAS_HIP(c, c->mem.alloc(c->h_peak_bits, 2 * ((N + 31) / 32), Mem::PINNED));
-		GAS_HIP(c, c->mem.alloc(c->d_peak_bits, 2 * ((N + 31) / 32)));
+		GAS_HIP(c, c->mem.alloc(c->list.h_idx, 2 * N, Mem::PINNED));
+		GAS_HIP(c, c->mem.alloc(c->list.h_peak_bits, 2 * ((N + 31) / 32), Mem::PINNED));
+		GAS_HIP(c, c->mem.alloc(c->list.d_peak_bits, 2 * ((N + 31) / 32)));
 		float2 h_tw[64 * 16];
 		gas_make_twiddles(h_tw);
 		GAS_HIP(c, c->mem.alloc(c->d_tw, 64 * 16));
@@ -686,7 +730,7 @@ int gas_source_set_draining(gas_ctx *c, uint32_t slot, int draining) {
 	}
 	if (c->slots[slot].draining != (draining != 0)) {
 		c->slots[slot].draining = draining != 0;
-		c->cached_n = UINT32_MAX; // launch groups change: the next callback must pass its slot list again
+		list_invalidate(c); // launch groups change: the next callback must pass its slot list again
 	}
 	return GAS_OK;
 }
@@ -834,7 +878,7 @@ int gas_params_publish_batch(gas_ctx *c, const uint32_t *slots, const gas_params
 		GAS_HIP(c, gas_launch_scatter_params(c->stream, c->st.params, params, c->d_upload_slots, n));
 		GAS_HIP(c, hipStreamSynchronize(c->stream));
 	} else {
-		if (c->cached_n != n) {
+		if (!list_serves(c, n)) {
 			return GAS_ERR_INVALID_ARGUMENT;
 		}
 		// Deferred: the next gas_process_block over this same list consumes the rows in its own launch when it can
@@ -955,6 +999,18 @@ int callback_begin(const gas_ctx *c, uint32_t frames) {
 	return hipSetDevice(c->cfg.device) == hipSuccess ? GAS_OK : GAS_ERR_NO_DEVICE;
 }
 
+// GAS_FLAG_BATCHED_LAUNCH: may the callbacks that wait for their batch go on waiting while this one joins them?  Only
+// a device-memory callback over the very list, grouping and parameters they were recorded with.
+bool deferred_still_valid(const gas_ctx *c, const uint32_t *slots, uint32_t n, int mem, bool host_dirty) {
+	return mem == GAS_MEM_DEVICE && !slots && n == c->deferred_n && c->pending_free.empty() && c->list.gen == c->deferred_groups_gen && !host_dirty;
+}
+
+// May a bus callback run n entries without being handed the list?  On the cached list, where the last bus callback ran
+// it in a form whose grouping is the ordinary one, and no free waits to regroup it.
+bool bus_list_reusable(const gas_ctx *c, uint32_t n) {
+	return list_serves(c, n) && c->list.bus_form != BUS_FORM_NONE && c->pending_free.empty();
+}
+
 // The body of gas_process_block behind its argument checks; a stream callback runs it with a fused source or with the
 // rows it sampled (GAS_MEM_DEVICE).
 int process_block(gas_ctx *c, const RowSource &src, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, float *peaks, int mem) {
@@ -967,19 +1023,19 @@ int process_block(gas_ctx *c, const RowSource &src, const uint32_t *slots, uint3
 			std::lock_guard<std::mutex> lk(c->params_mu);
 			host_dirty = !c->dirty_list.empty() || fx_basic_dirty(c) || !c->blend_dirty_list.empty();
 		}
-		const bool keep = mem == GAS_MEM_DEVICE && !slots && n == c->deferred_n && c->pending_free.empty() && c->groups_gen == c->deferred_groups_gen && !host_dirty;
-		if (!keep) {
+		if (!deferred_still_valid(c, slots, n, mem, host_dirty)) {
 			GAS_TRY(flush_deferred(c));
 		}
 	}
-	if (c->pending_params && (slots || n == 0 || c->cached_n != n || !c->pending_free.empty())) {
-		GAS_TRY(flush_pending_params(c)); // the list may change: scatter with the mapping it was published for
+	// Device-published rows are scattered with the mapping they were published for -- c->list's device arrays, which
+	// outlive an invalidation -- so in front of anything below that may rebuild them.
+	if (c->pending_params && (slots || n == 0 || !list_serves(c, n) || !c->pending_free.empty())) {
+		GAS_TRY(flush_pending_params(c));
 	}
 	apply_pending_frees(c);
 	if (slots || n == 0) { // an empty callback needs no list
-		c->cached_n = UINT32_MAX; // what a list that build_groups rejects leaves behind
 		GAS_TRY(build_groups(c, slots, n, false));
-	} else if (c->cached_n != n) {
+	} else if (!list_serves(c, n)) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
 	if (needs_hrtf(c)) {
@@ -987,9 +1043,9 @@ int process_block(gas_ctx *c, const RowSource &src, const uint32_t *slots, uint3
 	}
 	const uint64_t pgen = c->params_gen.load(); // read before the snapshot: a publish racing with it re-sorts next time
 	GAS_TRY(flush_params(c)); // one snapshot per callback (audio_spatializer.cpp:328)
-	if (c->order_groups_gen != c->groups_gen || c->order_params_gen != pgen) {
+	if (c->order_groups_gen != c->list.gen || c->order_params_gen != pgen) {
 		std::memset(c->order_ok, 0, sizeof(c->order_ok));
-		c->order_groups_gen = c->groups_gen;
+		c->order_groups_gen = c->list.gen;
 		c->order_params_gen = pgen;
 	}
 
@@ -1004,7 +1060,7 @@ int process_block(gas_ctx *c, const RowSource &src, const uint32_t *slots, uint3
 	if (c->pending_params) {
 		bool only_hrtf = true;
 		for (int gt = 0; gt < G_COUNT; gt++) {
-			only_hrtf = only_hrtf && (gt == G_FX_HRTF || gt == G_FX_HRTF_PK || gt == G_FX_ER_HRTF || gt == G_FX_ER_HRTF_PK || c->groups[gt].count == 0);
+			only_hrtf = only_hrtf && (gt == G_FX_HRTF || gt == G_FX_HRTF_PK || gt == G_FX_ER_HRTF || gt == G_FX_ER_HRTF_PK || c->list.groups[gt].count == 0);
 		}
 		if (only_hrtf && c->pending_n == n) {
 			fresh = c->pending_params; // k_hrtf_ols reads the rows and writes them through
@@ -1021,7 +1077,7 @@ int process_block(gas_ctx *c, const RowSource &src, const uint32_t *slots, uint3
 		cur.fresh = fresh;
 		c->deferred.push_back(cur); // nothing is enqueued yet: this callback runs with its neighbours (or when flushed)
 		c->deferred_n = n;
-		c->deferred_groups_gen = c->groups_gen;
+		c->deferred_groups_gen = c->list.gen;
 		const uint32_t depth = c->batch_depth < GAS_HRTF_MULTI_MAX_BLOCKS ? c->batch_depth : GAS_HRTF_MULTI_MAX_BLOCKS;
 		return c->deferred.size() >= depth ? flush_deferred(c) : GAS_OK;
 	}
@@ -1063,12 +1119,13 @@ int flush_routes(gas_ctx *c) {
 int bus_body(gas_ctx *c, const RowSource &src, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, uint32_t n_buses, float *peaks, int mem) {
 	const uint32_t F = c->cfg.frames, C = c->cfg.channel_count;
 	GAS_TRY(callback_begin(c, frames));
+	const BusForm cached_form = c->list.bus_form; // read in front of apply_pending_frees: frees adopted only now take the list away
 	GAS_TRY(flush_pending_params(c));
 	apply_pending_frees(c);
 	// Two forms: every source GAS_KIND_3D_MIX (the mix-channel buses of AudioSpatializer3D, fused in the biquad
 	// kernels), or every source an effect chain (run staged: per-source rows, then mixed per bus) on a one-pair context.
-	const bool reuse = n > 0 && !slots; // the cached form is 1 (3D mix) or 2 (fused [HRTF]) then
-	const BusList form = reuse ? (c->bus_form_cached == 1 ? BUS_LIST_3D_MIX : BUS_LIST_PLAIN_HRTF) : bus_list_form(c, slots, n);
+	const bool reuse = n > 0 && !slots; // bus_list_reusable held: the list ran as 3D mix or as fused [HRTF]
+	const BusList form = reuse ? (cached_form == BUS_FORM_3D_MIX ? BUS_LIST_3D_MIX : BUS_LIST_PLAIN_HRTF) : bus_list_form(c, slots, n);
 	// [HRTF] sources onto one or two buses have a fused form (k_hrtf_uni<BUS2>: the second bus's spectra sums in LDS)
 	// (three to six buses: one fused launch per pair of buses, the state committed by the last)
 	const bool fused_hrtf = form == BUS_LIST_PLAIN_HRTF && uni_ok(c) && gas_hrtf_uni_waves() == 8;
@@ -1080,17 +1137,17 @@ int bus_body(gas_ctx *c, const RowSource &src, const uint32_t *slots, uint32_t n
 		return GAS_ERR_INVALID_ARGUMENT; // the staged form regroups: it needs the list
 	}
 	if (!reuse) {
-		c->cached_n = UINT32_MAX; // what a list that build_groups rejects leaves behind
 		GAS_TRY(build_groups(c, slots, n, staged));
 		if (staged) {
-			c->cached_n = UINT32_MAX; // the staged grouping is this call's only: a later list reuse must regroup
+			list_invalidate(c); // the staged grouping is this call's only: a later list reuse must regroup
 		}
 	}
-	c->bus_form_cached = staged ? 0 : (fused_hrtf ? 2 : (form == BUS_LIST_3D_MIX ? 1 : 0));
-	c->bus_form_groups_gen = c->groups_gen;
+	if (c->list.valid) { // the form a later bus callback may run it in again
+		c->list.bus_form = fused_hrtf ? BUS_FORM_FUSED_HRTF : (form == BUS_LIST_3D_MIX ? BUS_FORM_3D_MIX : BUS_FORM_NONE);
+	}
 	for (int gt = 0; gt < G_COUNT; gt++) {
-		if (gt != (staged ? G_FX_GENERIC : (fused_hrtf ? G_FX_HRTF : G_3D_MIX)) && c->groups[gt].count > 0) {
-			c->cached_n = UINT32_MAX;
+		if (gt != (staged ? G_FX_GENERIC : (fused_hrtf ? G_FX_HRTF : G_3D_MIX)) && c->list.groups[gt].count > 0) {
+			list_invalidate(c);
 			return GAS_ERR_UNSUPPORTED_CHAIN;
 		}
 	}
@@ -1138,8 +1195,8 @@ int bus_body(gas_ctx *c, const RowSource &src, const uint32_t *slots, uint32_t n
 		GAS_HIP(c, hipMemsetAsync(d_peaks, 0, (size_t)n * 2 * sizeof(float), c->stream)); // k_biquad_mix accumulates peaks over channel pairs
 		gas_group_args ga;
 		ga.src = d_src.rows;
-		ga.rows = c->cached_identity_rows ? nullptr : c->d_rows;
-		ga.slots = c->d_slots;
+		ga.rows = c->list.identity_rows ? nullptr : c->list.d_rows;
+		ga.slots = c->list.d_slots;
 		ga.slot_base = 0;
 		ga.n = n;
 		ga.peaks = d_peaks;
@@ -1167,7 +1224,7 @@ int bus_body(gas_ctx *c, const RowSource &src, const uint32_t *slots, uint32_t n
 // for the two forms whose grouping is the ordinary one (3D mix, fused [HRTF]).
 int process_block_buses(gas_ctx *c, const RowSource &src, const uint32_t *slots, uint32_t n, uint32_t frames, gas_audio_frame *out, uint32_t n_buses, float *peaks, int mem) {
 	adopt_frees(c);
-	if (n > 0 && !slots && (c->cached_n != n || c->bus_form_cached == 0 || c->bus_form_groups_gen != c->groups_gen || !c->pending_free.empty())) {
+	if (n > 0 && !slots && !bus_list_reusable(c, n)) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
 	GAS_TRY(flush_deferred(c)); // GAS_FLAG_BATCHED_LAUNCH: callbacks waiting for their batch run first
@@ -1255,9 +1312,9 @@ bool stream_list_unchanged(const gas_ctx *c, const uint32_t *slots, uint32_t n, 
 	const StreamState &s = c->streams;
 	return c->pending_free.empty() // a deferred free re-sorts the groups
 			&& s.rows.size() == n
-			&& (c->cached_n == n || (buses && s.bus_staged)) // the staged bus form regroups on every call and leaves no cached groups behind: its list stays "the same" without them
+			&& (list_serves(c, n) || (buses && s.bus_staged)) // the staged bus form regroups on every call and leaves no cached groups behind: its list stays "the same" without them
 			&& s.last_buses == buses
-			&& s.groups_gen == c->groups_gen
+			&& s.groups_gen == c->list.gen
 			&& !s.params_touched
 			&& s.slots_host.size() == n
 			&& (n == 0 || std::memcmp(s.slots_host.data(), slots, (size_t)n * sizeof(uint32_t)) == 0);
@@ -1487,7 +1544,7 @@ int stream_body(gas_ctx *c, const uint32_t *slots, uint32_t n, uint32_t frames, 
 	bool draining_changed = false, any_fed = false;
 	stream_advance(c, slots, n, has_frames, draining_changed, any_fed);
 	if (draining_changed) {
-		c->cached_n = UINT32_MAX;
+		list_invalidate(c);
 		same_list = false;
 	}
 	GAS_TRY(feed_serve(c, n, any_fed));
@@ -1509,13 +1566,13 @@ int stream_body(gas_ctx *c, const uint32_t *slots, uint32_t n, uint32_t frames, 
 	int rc = GAS_OK;
 	if (buses) {
 		// gas_process_block_buses reuses a list only for its 3D-mix and fused [HRTF] forms; the staged form needs it every time
-		const bool reuse = same_list && n > 0 && c->cached_n == n && c->bus_form_cached != 0 && c->bus_form_groups_gen == c->groups_gen;
+		const bool reuse = same_list && n > 0 && bus_list_reusable(c, n);
 		rc = process_block_buses(c, rows, reuse ? nullptr : slots, n, F, d_out, n_buses, d_pk, GAS_MEM_DEVICE);
-		c->streams.bus_staged = rc == GAS_OK && n > 0 && c->cached_n != n; // ran staged: nothing cached to compare with next time
+		c->streams.bus_staged = rc == GAS_OK && n > 0 && c->list.bus_form == BUS_FORM_NONE; // it ran staged: nothing cached to compare with next time
 	} else {
 		rc = process_block(c, rows, same_list ? nullptr : slots, n, F, d_out, d_pk, GAS_MEM_DEVICE);
 	}
-	c->streams.groups_gen = rc == GAS_OK ? c->groups_gen : UINT64_MAX;
+	c->streams.groups_gen = rc == GAS_OK ? c->list.gen : UINT64_MAX;
 	GAS_TRY(rc);
 	if (mem == GAS_MEM_DEVICE) {
 		return GAS_OK;

@@ -205,12 +205,12 @@ int gas_ctx_read_hrtf_order(gas_ctx *c, uint32_t *out, uint32_t n) {
 			return rcd;
 		}
 	}
-	if (!c->d_order || !c->order_ok[G_FX_HRTF] || !c->last_uni_ordered || n > c->groups[G_FX_HRTF].count) {
+	if (!c->d_order || !c->order_ok[G_FX_HRTF] || !c->last_uni_ordered || n > c->list.groups[G_FX_HRTF].count) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
 	GAS_HIP(c, hipSetDevice(c->cfg.device));
 	GAS_HIP(c, hipStreamSynchronize(c->stream));
-	GAS_HIP(c, hipMemcpy(out, c->d_order + c->groups[G_FX_HRTF].offset, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+	GAS_HIP(c, hipMemcpy(out, c->d_order + c->list.groups[G_FX_HRTF].offset, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
 	return GAS_OK;
 }
 

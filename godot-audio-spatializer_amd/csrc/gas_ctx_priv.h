@@ -90,6 +90,36 @@ struct SlotStamp {
 	}
 };
 
+// The form a gas_process_block_buses ran the list in, where a later bus callback may run it again without being handed
+// the list.  NONE: no bus callback ran it, or it ran staged -- a grouping of that call alone.
+enum BusForm { BUS_FORM_NONE = 0, BUS_FORM_3D_MIX, BUS_FORM_FUSED_HRTF };
+
+// The slot list a callback leaves behind for the next one (slots == NULL, the stream entries' "same list again", the
+// batched launch, the direction order), as c->list: what build_groups writes, and build_groups alone -- its last step
+// commits `valid`, `n` and a new `gen`; list_invalidate takes `valid` away; bus_body notes the form it ran.
+// !valid: no caller may reuse the list (list_serves).  Its device arrays stay where they are all the same: they are the
+// mapping of device-published rows not scattered yet (pending_params, recorded while the list was valid), so
+// flush_pending_params runs before the next build_groups overwrites them -- every callback body flushes, or has seen
+// that nothing is pending, in front of its rebuild.
+// Whoever caches something derived from the list keeps the `gen` it was derived from (deferred_groups_gen,
+// order_groups_gen, streams.groups_gen).
+struct SlotList {
+	uint32_t n = 0;
+	bool valid = false;
+	uint64_t gen = 0; // one per committed rebuild
+	BusForm bus_form = BUS_FORM_NONE; // reset by every rebuild and every invalidation: it needs no generation of its own
+	bool identity_rows = true; // the sorted order is the caller's row order
+	Group groups[G_COUNT];
+	std::vector<ChainRange> chain_ranges; // sub-runs of groups[G_FX_GENERIC]
+	// plain [HRTF] group (k_hrtf_uni): which entries need their exact peak
+	bool uni_peak_all = false, uni_peak_any = false;
+	// host and device mirrors (the context's Mem owns them)
+	uint32_t *h_idx = nullptr; // pinned [2 * max_sources]: slots then rows, sorted by group
+	uint32_t *d_slots = nullptr, *d_rows = nullptr; // sorted by launch group
+	uint32_t *d_slots_rows = nullptr; // the caller's list in row order (device-side parameter publication)
+	uint32_t *h_peak_bits = nullptr, *d_peak_bits = nullptr; // two halves of (max_sources + 31) / 32 words: bit k = entry k of the plain-[HRTF] group / of the staged group
+};
+
 constexpr uint32_t PROFILE_EVENTS = 4096;
 
 // The effect families, in the order their uploads are flushed; gas_ctx_fx.hip's table describes them.  The
@@ -227,10 +257,10 @@ struct StreamState {
 	std::vector<uint32_t> slots_host; // what d_slots / the cached launch groups currently hold
 	std::vector<StreamRow> rows;
 	StreamListTraits list;
-	uint64_t groups_gen = UINT64_MAX; // groups_gen the stream path's cached list corresponds to
+	uint64_t groups_gen = UINT64_MAX; // list.gen the stream path's cached list corresponds to
 	bool last_fused = false; // the last stream callback that got as far as its launches sampled inside the HRTF kernel (gas_stream_last_fused)
 	bool last_buses = false; // the cached stream list was validated by gas_process_block_streams_buses (its checks differ from the mix entry's)
-	bool bus_staged = false; // ... and ran the staged bus form, which regroups on every call (cached_n never names it)
+	bool bus_staged = false; // ... and ran the staged bus form, which regroups on every call (c->list never serves it)
 	bool params_touched = false; // a parameter publish may have changed pitch_scale: re-validate
 };
 
@@ -313,8 +343,6 @@ struct gas_ctx {
 	uint32_t deferred_n = 0;
 	uint64_t deferred_groups_gen = 0;
 	uint32_t batch_depth = 2; // callbacks per launch (gas_ctx_set_batch_depth), <= GAS_HRTF_MULTI_MAX_BLOCKS
-	int bus_form_cached = 0; // form of the last gas_process_block_buses whose list can be reused: 1 3D mix, 2 fused [HRTF], 0 none
-	uint64_t bus_form_groups_gen = 0;
 	uint32_t partial_planes = 1; // planes of d_partials (1 ordered, 2 pipelined, 2 x max batch depth batched)
 	uint32_t hist_len = 0;
 	gas_dev_state st{};
@@ -347,22 +375,15 @@ struct gas_ctx {
 	gas_line_geo line_geo{};
 	gas_eq_coefs eq_coefs[3] = {}; // EQ6, EQ10, EQ21 at the mix rate (make_eq_coefs)
 
-	// plain [HRTF] group of the cached list (k_hrtf_uni): which entries need their exact peak
-	uint32_t *h_peak_bits = nullptr, *d_peak_bits = nullptr; // two halves of (max_sources + 31) / 32 words: bit k = entry k of the plain-[HRTF] group / of the staged group
-	bool uni_peak_all = false, uni_peak_any = false;
-	uint32_t *h_idx = nullptr; // pinned [2 * max_sources]: slots then rows, sorted by group
-	uint32_t *d_slots = nullptr, *d_rows = nullptr; // sorted by launch group
-	uint32_t *d_slots_rows = nullptr; // the caller's list in row order (device-side parameter publication)
-	uint32_t cached_n = UINT32_MAX;
-	uint64_t groups_gen = 0; // bumped whenever build_groups re-sorts a slot list
+	SlotList list; // the cached slot list
+	// parameter rows published from device memory for it (row order), not yet in the table
+	const gas_params *pending_params = nullptr;
+	uint32_t pending_n = 0;
 	std::atomic<uint64_t> params_gen{ 1 }; // bumped by every call that can change a source's HRIR direction
 	uint32_t *d_order = nullptr; // [max_sources] direction order of the frequency-domain HRTF groups (k_dir_order)
 	uint64_t order_groups_gen = UINT64_MAX, order_params_gen = 0; // what d_order was built from
 	bool order_ok[G_COUNT] = {}; // d_order holds this group's order
 	bool last_uni_ordered = false; // the last k_hrtf_uni launch ran in k_xcd_order's order
-	bool cached_identity_rows = true;
-	Group groups[G_COUNT];
-	std::vector<ChainRange> chain_ranges; // sub-runs of groups[G_FX_GENERIC], cached with the groups
 	gas_audio_frame *d_chain[2] = { nullptr, nullptr }; // ping-pong rows of the staged chains
 	size_t d_chain_frames = 0;
 
@@ -381,9 +402,6 @@ struct gas_ctx {
 
 	StreamState streams;
 	float *d_fade_env = nullptr; // [64]
-	// parameter rows published from device memory for the cached slot list (row order), not yet in the table
-	const gas_params *pending_params = nullptr;
-	uint32_t pending_n = 0;
 	FeedState feed;
 
 	CalcState calc;
@@ -429,6 +447,17 @@ namespace gas_priv __attribute__((visibility("hidden"))) {
 // The slot names a playback of this context.
 inline bool live(const gas_ctx *c, uint32_t slot) {
 	return slot < c->cfg.max_sources && c->slots[slot].used;
+}
+
+// The one place that says "no list": launch groups changed, a list was rejected, or the grouping was one call's only.
+inline void list_invalidate(gas_ctx *c) {
+	c->list.valid = false;
+	c->list.bus_form = BUS_FORM_NONE;
+}
+
+// May a caller that names no list (slots == NULL, "the same list again") run n entries on the cached one?
+inline bool list_serves(const gas_ctx *c, uint32_t n) {
+	return c->list.valid && c->list.n == n;
 }
 
 // A lazily allocated buffer: each pointer is guarded by its own null test.

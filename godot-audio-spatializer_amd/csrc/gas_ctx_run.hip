@@ -164,7 +164,7 @@ gas_hrtf_launch_common hrtf_common(const gas_ctx *c) {
 // Which entries of the plain-[HRTF] group of the context's own list report their exact peak (build_groups): the bit
 // list, unless all of them or none do.
 inline const uint32_t *plain_peak_bits(const gas_ctx *c) {
-	return c->uni_peak_any && !c->uni_peak_all ? c->d_peak_bits : nullptr;
+	return c->list.uni_peak_any && !c->list.uni_peak_all ? c->list.d_peak_bits : nullptr;
 }
 
 // What run_groups decides before it enqueues anything (plan_run).
@@ -327,12 +327,12 @@ int launch_staged_chains(gas_ctx *c, const RunArgs &a, const gas_group_args &ga,
 		in.peaks = d_rows ? a.peaks : a.peaks + (size_t)off * 2;
 		const uint32_t *peak_rows = in.rows;
 		const bool last_is_uni = range_ends_in_uni(r, run.plan.staged_uni);
-		const bool own = a.groups == c->groups; // the context's own list: GAS_FLAG_PEAKS_DRAINING_ONLY's bits exist
+		const bool own = a.groups == c->list.groups; // the context's own list: GAS_FLAG_PEAKS_DRAINING_ONLY's bits exist
 		const int k0 = r.sig & 0xff;
 		// a last stage that is k_hrtf_uni: exact peaks for every source of the chain, or (GAS_FLAG_PEAKS_DRAINING_ONLY,
 		// the context's own list) for the draining ones
 		gas_hrtf_uni_launch lu{ hrtf_common(c) };
-		lu.peak_bits = own && r.peak_any && !r.peak_all ? c->d_peak_bits + (c->cfg.max_sources + 31) / 32 : nullptr;
+		lu.peak_bits = own && r.peak_any && !r.peak_all ? c->list.d_peak_bits + (c->cfg.max_sources + 31) / 32 : nullptr;
 		lu.peak_all = !own || r.peak_all;
 		lu.partials = run.parts;
 		lu.p_offset = pp_r;
@@ -401,7 +401,7 @@ RunPlan plan_run(const gas_ctx *c, const RunArgs &a) {
 	const uint32_t F = c->cfg.frames;
 	const Group *const groups = a.groups;
 	RunPlan p;
-	p.uni_hrtf = groups == c->groups && uni_ok(c);
+	p.uni_hrtf = groups == c->list.groups && uni_ok(c);
 	p.staged_uni = uni_ok(c) && a.buses == nullptr && gas_hrtf_uni_waves() == 8; // staged chains ending in the HRTF: last stage = k_hrtf_uni
 	// [ER, HRTF] through k_hrtf_uni<ER> (22.5 -> see profiles/r03_notes.md): the exact-peak group's entries follow the
 	// frequency-domain group's in the callback's list, so one launch covers both
@@ -611,7 +611,7 @@ int run_hrtf_batch(gas_ctx *c, const std::vector<gas_ctx::Deferred> &blocks, uin
 	if (timed) {
 		GAS_HIP(c, c->prof.begin(c->stream));
 	}
-	GAS_HIP(c, gas_launch_hrtf_multi(c->stream, ga, mb, plain_peak_bits(c), c->uni_peak_all, c->st, c->tab, c->d_tw, F, c->hist_len, c->d_partials));
+	GAS_HIP(c, gas_launch_hrtf_multi(c->stream, ga, mb, plain_peak_bits(c), c->list.uni_peak_all, c->st, c->tab, c->d_tw, F, c->hist_len, c->d_partials));
 	if (timed) {
 		GAS_HIP(c, c->prof.end(c->stream));
 		// What this launch has to move (not K times the single-callback formula: k_hrtf_multi<., true> reads a history
@@ -694,10 +694,10 @@ int join_outputs(gas_ctx *c) {
 RunArgs own_list(const gas_ctx *c, const RowSource &src, uint32_t n, gas_audio_frame *out, float *peaks) {
 	RunArgs a;
 	a.src = src;
-	a.slots = c->d_slots;
-	a.rows = c->cached_identity_rows ? nullptr : c->d_rows;
-	a.groups = c->groups;
-	a.ranges = &c->chain_ranges;
+	a.slots = c->list.d_slots;
+	a.rows = c->list.identity_rows ? nullptr : c->list.d_rows;
+	a.groups = c->list.groups;
+	a.ranges = &c->list.chain_ranges;
 	a.n_total = n;
 	a.out = out;
 	a.peaks = peaks;
@@ -706,11 +706,11 @@ RunArgs own_list(const gas_ctx *c, const RowSource &src, uint32_t n, gas_audio_f
 
 // The plain-[HRTF] group of the context's own list, for a launch that covers exactly it.
 gas_group_args own_hrtf_group(const gas_ctx *c, const gas_audio_frame *src, uint32_t n, float *peaks) {
-	const Group &gr = c->groups[G_FX_HRTF];
+	const Group &gr = c->list.groups[G_FX_HRTF];
 	gas_group_args ga;
 	ga.src = src;
-	ga.rows = c->cached_identity_rows ? nullptr : c->d_rows + gr.offset;
-	ga.slots = gr.contiguous ? nullptr : c->d_slots + gr.offset; // a contiguous slot range needs no list on the device
+	ga.rows = c->list.identity_rows ? nullptr : c->list.d_rows + gr.offset;
+	ga.slots = gr.contiguous ? nullptr : c->list.d_slots + gr.offset; // a contiguous slot range needs no list on the device
 	ga.slot_base = gr.contiguous ? gr.slot_base : 0;
 	ga.n = n;
 	ga.peaks = peaks;
@@ -740,7 +740,7 @@ gas_hrtf_uni_launch plain_uni_launch(const gas_ctx *c, const gas_group_args &g, 
 	gas_hrtf_uni_launch lu{ hrtf_common(c) };
 	lu.g = g;
 	lu.peak_bits = plain_peak_bits(c);
-	lu.peak_all = c->uni_peak_all;
+	lu.peak_all = c->list.uni_peak_all;
 	lu.partials = partials;
 	lu.p_offset = p_offset;
 	lu.cursors = src.cursors;
@@ -803,13 +803,13 @@ bool batchable(const gas_ctx *c, uint32_t n, bool fused) {
 		return false;
 	}
 	for (int gt = 0; gt < G_COUNT; gt++) {
-		if (gt != G_FX_HRTF && c->groups[gt].count != 0) {
+		if (gt != G_FX_HRTF && c->list.groups[gt].count != 0) {
 			return false;
 		}
 	}
 	const uint32_t wgs = gas_hrtf_uni_partials(n);
 	// every wave of the launch has a source; every output column of a carried sum finds a job wave
-	return c->groups[G_FX_HRTF].count == n && n >= wgs * gas_hrtf_uni_waves() && wgs * GAS_HRTF_JOB_WAVES >= c->cfg.frames * 2 / 4 && wgs <= 256;
+	return c->list.groups[G_FX_HRTF].count == n && n >= wgs * gas_hrtf_uni_waves() && wgs * GAS_HRTF_JOB_WAVES >= c->cfg.frames * 2 / 4 && wgs <= 256;
 }
 
 } // namespace gas_priv

@@ -262,7 +262,7 @@ int gas_source_bind_stream(gas_ctx *c, uint32_t slot, uint32_t stream, uint64_t 
 	GAS_HIP(c, hipStreamSynchronize(c->stream));
 	if (c->slots[slot].draining) {
 		c->slots[slot].draining = 0;
-		c->cached_n = UINT32_MAX;
+		list_invalidate(c);
 	}
 	return GAS_OK;
 }

@@ -430,6 +430,28 @@ def default_room_ir(room=None, source=(1.0, 0.5, 0.25), listener_origin=(-1.0, 0
     return d
 
 
+# gas_room_bands (gas_conv_ir_from_room_bands, gas_conv_ir_from_room_hrtf_bands)
+ROOM_MAX_BANDS = 8
+ROOM_BAND_FILTER_MAX_TAPS = 4095
+ROOM_BANDS_DTYPE = np.dtype([("n_bands", np.uint32), ("filter_taps", np.uint32), ("crossover_hz", np.float32, (ROOM_MAX_BANDS - 1,)), ("reflectance", np.float32, (ROOM_MAX_BANDS, 6)), ("air_db_per_m", np.float32, (ROOM_MAX_BANDS,)), ("reserved", np.uint32)])
+assert ROOM_BANDS_DTYPE.itemsize == 264
+
+
+def default_room_bands(crossover_hz=(500.0, 4000.0), reflectance=((0.9,) * 6, (0.8,) * 6, (0.6,) * 6), air_db_per_m=(0.0, 0.005, 0.05), filter_taps=255):
+    """One gas_room_bands ([1]) of len(reflectance) bands: by default low / mid / high split at 500 Hz and 4 kHz, walls
+    that absorb more towards the highs, air that takes 0.05 dB per metre from the high band, 255-tap band filters.
+    reflectance: one value or six (gas_room's wall order) per band."""
+    n = len(reflectance)
+    assert 1 <= n <= ROOM_MAX_BANDS and len(crossover_hz) == n - 1 and len(air_db_per_m) == n
+    b = np.zeros(1, ROOM_BANDS_DTYPE)
+    b["n_bands"], b["filter_taps"] = n, filter_taps
+    b["crossover_hz"][0, : n - 1] = crossover_hz
+    for i in range(n):
+        b["reflectance"][0, i] = reflectance[i]
+    b["air_db_per_m"][0, :n] = air_db_per_m
+    return b
+
+
 def default_spat3d_config(n=1, **kw):
     """AudioSpatializer3D defaults (audio_spatializer_3d.h:171-187), stereo, global panning strength 0.5."""
     c = np.zeros(n, SPAT3D_CONFIG_DTYPE)
@@ -503,6 +525,8 @@ EXPORTS = [
     "gas_conv_ir_get_info",
     "gas_conv_ir_from_room",
     "gas_conv_ir_from_room_hrtf",
+    "gas_conv_ir_from_room_bands",
+    "gas_conv_ir_from_room_hrtf_bands",
     "gas_conv_create",
     "gas_conv_destroy",
     "gas_conv_reset",
@@ -617,6 +641,8 @@ def load_library():
     L.gas_conv_ir_get_info.argtypes = [vp, u32, C.POINTER(u32), C.POINTER(u32)]
     L.gas_conv_ir_from_room.argtypes = [vp, vp, u32, u32, vp, C.POINTER(u32)]
     L.gas_conv_ir_from_room_hrtf.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, C.POINTER(u32)]
+    L.gas_conv_ir_from_room_bands.argtypes = [vp, vp, vp, u32, u32, vp, C.POINTER(u32)]
+    L.gas_conv_ir_from_room_hrtf_bands.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, vp, C.POINTER(u32)]
     L.gas_conv_create.argtypes = [vp, u32, C.POINTER(u32)]
     L.gas_conv_destroy.argtypes = [vp, u32]
     L.gas_conv_reset.argtypes = [vp, u32]
@@ -1066,6 +1092,34 @@ class SpatializerContext:
         out = C.c_uint32()
         rc = self.lib.gas_conv_ir_from_room_hrtf(self.h, _np_ptr(d), _np_ptr(h), int(n_az), int(n_el), h.shape[2], int(taps), _np_ptr(taps_out) if want_taps else None, C.byref(out) if load else None)
         self._check(rc, "gas_conv_ir_from_room_hrtf")
+        if load and want_taps:
+            return out.value, taps_out
+        return out.value if load else taps_out
+
+    def conv_ir_from_room_bands(self, desc, bands, channels, taps, want_taps=False, load=True):
+        """conv_ir_from_room with per-band wall reflectances and air absorption (bands: one ROOM_BANDS_DTYPE entry, see
+        default_room_bands); desc's own room.reflectance is validated but not used.  Returns as conv_ir_from_room does."""
+        d = np.ascontiguousarray(np.asarray(desc, dtype=ROOM_IR_DTYPE).reshape(-1)[:1])
+        b = np.ascontiguousarray(np.asarray(bands, dtype=ROOM_BANDS_DTYPE).reshape(-1)[:1])
+        taps_out = np.zeros((int(channels), int(taps)), dtype=np.float32) if want_taps else None
+        out = C.c_uint32()
+        rc = self.lib.gas_conv_ir_from_room_bands(self.h, _np_ptr(d), _np_ptr(b), int(channels), int(taps), _np_ptr(taps_out) if want_taps else None, C.byref(out) if load else None)
+        self._check(rc, "gas_conv_ir_from_room_bands")
+        if load and want_taps:
+            return out.value, taps_out
+        return out.value if load else taps_out
+
+    def conv_ir_from_room_hrtf_bands(self, desc, bands, hrir, n_az, n_el, taps, want_taps=False, load=True):
+        """conv_ir_from_room_hrtf with per-band wall reflectances and air absorption; arguments as conv_ir_from_room_bands
+        and conv_ir_from_room_hrtf, the taps are [2][taps]."""
+        d = np.ascontiguousarray(np.asarray(desc, dtype=ROOM_IR_DTYPE).reshape(-1)[:1])
+        b = np.ascontiguousarray(np.asarray(bands, dtype=ROOM_BANDS_DTYPE).reshape(-1)[:1])
+        h = np.ascontiguousarray(np.asarray(hrir, dtype=np.float32))
+        assert h.ndim == 3 and h.shape[0] == int(n_az) * int(n_el) and h.shape[1] == 2, h.shape
+        taps_out = np.zeros((2, int(taps)), dtype=np.float32) if want_taps else None
+        out = C.c_uint32()
+        rc = self.lib.gas_conv_ir_from_room_hrtf_bands(self.h, _np_ptr(d), _np_ptr(b), _np_ptr(h), int(n_az), int(n_el), h.shape[2], int(taps), _np_ptr(taps_out) if want_taps else None, C.byref(out) if load else None)
+        self._check(rc, "gas_conv_ir_from_room_hrtf_bands")
         if load and want_taps:
             return out.value, taps_out
         return out.value if load else taps_out

@@ -1,5 +1,5 @@
 // gas_ctx_conv.hip -- the bus convolvers of include/gas_amd.h (gas_ctx_reserve_conv, gas_conv_*; k_conv.hip) and the
-// impulse responses built on the device from box rooms (gas_conv_ir_from_room*; k_room_ir.hip).
+// impulse responses built on the device from box rooms (gas_conv_ir_from_room*; k_room_ir.hip, k_room_bands.hip).
 #include "gas_ctx_priv.h"
 
 extern "C" {
@@ -467,32 +467,83 @@ struct RoomIrSet {
 	uint32_t n_az, n_el, taps;
 };
 
-// The common body of the two box-room calls once everything is validated and the plan is made: tables, temporaries,
+// What the two *_bands calls refuse in a gas_room_bands; entries beyond n_bands (n_bands - 1 crossovers) are not read.
+static bool room_bands_ok(const gas_room_bands &b, float rate) {
+	if (b.n_bands == 0 || b.n_bands > GAS_ROOM_MAX_BANDS || b.reserved != 0) {
+		return false;
+	}
+	bool ok = b.n_bands == 1 || ((b.filter_taps & 1u) && b.filter_taps >= 3 && b.filter_taps <= GAS_ROOM_BAND_FILTER_MAX_TAPS);
+	float below = 0.0f;
+	for (uint32_t i = 0; i + 1 < b.n_bands; i++) { // the comparisons are false for a NaN
+		ok = ok && b.crossover_hz[i] > below && (double)b.crossover_hz[i] < (double)rate / 2.0;
+		below = b.crossover_hz[i];
+	}
+	for (uint32_t i = 0; i < b.n_bands; i++) {
+		for (int w = 0; w < 6; w++) {
+			ok = ok && b.reflectance[i][w] >= 0.0f && b.reflectance[i][w] <= 1.0f;
+		}
+		ok = ok && b.air_db_per_m[i] >= 0.0f && std::isfinite(b.air_db_per_m[i]);
+	}
+	return ok;
+}
+
+// The common body of the box-room calls once everything is validated and the plan is made: tables, temporaries,
 // the generator's launches inside the profile bracket, registration and read-back.  set == nullptr: k_room_ir with
-// `channels` receivers; otherwise k_room_ir_hrtf, two ears.
-static int conv_ir_from_plan(gas_ctx *c, const gas_room_ir &desc, const gas_room_ir_plan &plan, uint32_t channels, const RoomIrSet *set, float *out_taps, uint32_t *out_ir) {
+// `channels` receivers; otherwise k_room_ir_hrtf, two ears.  bands == nullptr: the plain calls, one pass whose scaled
+// taps are the result; otherwise one such pass per band with that band's reflectances, each into its own sums, and
+// k_room_bands_combine over them writes the result.
+static int conv_ir_from_plan(gas_ctx *c, const gas_room_ir &desc, const gas_room_ir_plan &plan, uint32_t channels, const RoomIrSet *set, const gas_room_bands *bands, float *out_taps, uint32_t *out_ir) {
 	const uint32_t taps = plan.taps;
-	std::vector<double> tables;
+	const uint32_t passes = bands ? bands->n_bands : 1u;
+	const size_t per_pass = gas_room_ir_table_doubles(plan);
+	gas_room_bands_plan bp{};
+	std::vector<double> tables, filt;
 	try {
-		tables.resize(gas_room_ir_table_doubles(plan));
+		tables.resize(per_pass * passes);
+		if (bands) {
+			bp.bands = passes;
+			bp.channels = channels;
+			bp.taps = taps;
+			bp.level = plan.level;
+			bp.L = passes == 1 ? 1u : bands->filter_taps;
+			bp.D = (bp.L - 1u) / 2u;
+			bp.Lp = (bp.L + GAS_ROOM_BANDS_FILTER_STEP - 1u) / GAS_ROOM_BANDS_FILTER_STEP * GAS_ROOM_BANDS_FILTER_STEP;
+			for (uint32_t b = 0; b < passes; b++) {
+				bp.lambda[b] = 2.302585092994046 / 20.0 * (double)bands->air_db_per_m[b] * plan.c / plan.rate;
+			}
+			filt.resize((size_t)passes * bp.Lp);
+			gas_room_bands_fill_filters(*bands, plan.rate, bp, filt.data());
+		}
 	} catch (const std::bad_alloc &) {
 		c->last_err = "gas_conv_ir_from_room: out of host memory for the reflectance tables";
 		return GAS_ERR_DEVICE;
 	}
-	gas_room_ir_fill_tables(desc, plan, tables.data());
+	if (bands) {
+		gas_room_ir d = desc;
+		for (uint32_t b = 0; b < passes; b++) {
+			std::memcpy(d.room.reflectance, bands->reflectance[b], sizeof(d.room.reflectance));
+			gas_room_ir_fill_tables(d, plan, tables.data() + per_pass * b);
+		}
+	} else {
+		gas_room_ir_fill_tables(desc, plan, tables.data());
+	}
 	if (out_ir) { // the pure generator leaves queued callbacks where they are: it touches nothing of theirs
 		GAS_TRY(flush_deferred(c));
 	}
 	GAS_HIP(c, hipSetDevice(c->cfg.device));
 	const size_t n = (size_t)channels * taps;
 	Mem tmp; // frees the buffers on every way out
-	double *d_tables = nullptr;
+	double *d_tables = nullptr, *d_filt = nullptr;
 	long long *d_acc = nullptr;
 	float *d_ir = nullptr, *d_hrir = nullptr;
 	GAS_HIP(c, tmp.alloc(d_tables, tables.size()));
-	GAS_HIP(c, tmp.alloc(d_acc, n));
+	GAS_HIP(c, tmp.alloc(d_acc, n * passes));
 	GAS_HIP(c, tmp.alloc(d_ir, n));
 	GAS_HIP(c, hipMemcpy(d_tables, tables.data(), tables.size() * sizeof(double), hipMemcpyHostToDevice)); // complete on return
+	if (bands) {
+		GAS_HIP(c, tmp.alloc(d_filt, filt.size()));
+		GAS_HIP(c, hipMemcpy(d_filt, filt.data(), filt.size() * sizeof(double), hipMemcpyHostToDevice));
+	}
 	if (set) {
 		const size_t floats = (size_t)set->n_az * set->n_el * 2 * set->taps;
 		GAS_HIP(c, tmp.alloc(d_hrir, floats));
@@ -502,10 +553,15 @@ static int conv_ir_from_plan(gas_ctx *c, const gas_room_ir &desc, const gas_room
 	if (timed) {
 		GAS_HIP(c, c->prof.begin(c->stream));
 	}
-	if (set) {
-		GAS_HIP(c, gas_launch_room_ir_hrtf(c->stream, plan, desc, d_tables, d_hrir, set->n_az, set->n_el, set->taps, d_acc, d_ir));
-	} else {
-		GAS_HIP(c, gas_launch_room_ir(c->stream, plan, d_tables, d_acc, d_ir));
+	for (uint32_t b = 0; b < passes; b++) { // in stream order: a band's scaled taps in d_ir are overwritten by the next writer
+		if (set) {
+			GAS_HIP(c, gas_launch_room_ir_hrtf(c->stream, plan, desc, d_tables + per_pass * b, d_hrir, set->n_az, set->n_el, set->taps, d_acc + n * b, d_ir));
+		} else {
+			GAS_HIP(c, gas_launch_room_ir(c->stream, plan, d_tables + per_pass * b, d_acc + n * b, d_ir));
+		}
+	}
+	if (bands) {
+		GAS_HIP(c, gas_launch_room_bands_combine(c->stream, bp, d_acc, d_filt, d_ir));
 	}
 	if (timed) {
 		GAS_HIP(c, c->prof.end(c->stream));
@@ -529,8 +585,9 @@ static int conv_ir_from_plan(gas_ctx *c, const gas_room_ir &desc, const gas_room
 	return GAS_OK;
 }
 
-int gas_conv_ir_from_room(gas_ctx *c, const gas_room_ir *desc, uint32_t channels, uint32_t taps, float *out_taps, uint32_t *out_ir) {
-	if (!c || !desc || (!out_taps && !out_ir) || (channels != 1 && channels != 2) || taps == 0) {
+// gas_conv_ir_from_room and gas_conv_ir_from_room_bands: `banded` says which, so that a NULL bands is refused by the second.
+static int conv_ir_from_room_any(gas_ctx *c, const gas_room_ir *desc, bool banded, const gas_room_bands *bands, uint32_t channels, uint32_t taps, float *out_taps, uint32_t *out_ir) {
+	if (!c || !desc || (banded && !bands) || (!out_taps && !out_ir) || (channels != 1 && channels != 2) || taps == 0) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
 	if (out_ir && c->conv.count == 0) {
@@ -540,14 +597,14 @@ int gas_conv_ir_from_room(gas_ctx *c, const gas_room_ir *desc, uint32_t channels
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
 	gas_room_ir_plan plan;
-	if (!room_ir_desc_ok(*desc, true) || !gas_room_ir_make_plan(*desc, channels, taps, c->cfg.mix_rate, plan)) {
+	if (!room_ir_desc_ok(*desc, true) || (banded && !room_bands_ok(*bands, c->cfg.mix_rate)) || !gas_room_ir_make_plan(*desc, channels, taps, c->cfg.mix_rate, plan)) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
-	return conv_ir_from_plan(c, *desc, plan, channels, nullptr, out_taps, out_ir);
+	return conv_ir_from_plan(c, *desc, plan, channels, nullptr, bands, out_taps, out_ir);
 }
 
-int gas_conv_ir_from_room_hrtf(gas_ctx *c, const gas_room_ir *desc, const float *hrir, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps, uint32_t taps, float *out_taps, uint32_t *out_ir) {
-	if (!c || !desc || !hrir || (!out_taps && !out_ir) || taps == 0) {
+static int conv_ir_from_room_hrtf_any(gas_ctx *c, const gas_room_ir *desc, bool banded, const gas_room_bands *bands, const float *hrir, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps, uint32_t taps, float *out_taps, uint32_t *out_ir) {
+	if (!c || !desc || (banded && !bands) || !hrir || (!out_taps && !out_ir) || taps == 0) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
 	if (n_az == 0 || n_el == 0 || (uint64_t)n_az * n_el > 65536u || hrir_taps == 0 || hrir_taps > GAS_HRTF_TAPS) {
@@ -560,7 +617,7 @@ int gas_conv_ir_from_room_hrtf(gas_ctx *c, const gas_room_ir *desc, const float 
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
 	gas_room_ir_plan plan;
-	if (!room_ir_desc_ok(*desc, false) || !gas_room_ir_make_plan(*desc, 1, taps, c->cfg.mix_rate, plan)) { // one receiver: ear_spacing is not read
+	if (!room_ir_desc_ok(*desc, false) || (banded && !room_bands_ok(*bands, c->cfg.mix_rate)) || !gas_room_ir_make_plan(*desc, 1, taps, c->cfg.mix_rate, plan)) { // one receiver: ear_spacing is not read
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
 	const size_t floats = (size_t)n_az * n_el * 2 * hrir_taps;
@@ -570,7 +627,23 @@ int gas_conv_ir_from_room_hrtf(gas_ctx *c, const gas_room_ir *desc, const float 
 		}
 	}
 	const RoomIrSet set{hrir, n_az, n_el, hrir_taps};
-	return conv_ir_from_plan(c, *desc, plan, 2, &set, out_taps, out_ir);
+	return conv_ir_from_plan(c, *desc, plan, 2, &set, bands, out_taps, out_ir);
+}
+
+int gas_conv_ir_from_room(gas_ctx *c, const gas_room_ir *desc, uint32_t channels, uint32_t taps, float *out_taps, uint32_t *out_ir) {
+	return conv_ir_from_room_any(c, desc, false, nullptr, channels, taps, out_taps, out_ir);
+}
+
+int gas_conv_ir_from_room_hrtf(gas_ctx *c, const gas_room_ir *desc, const float *hrir, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps, uint32_t taps, float *out_taps, uint32_t *out_ir) {
+	return conv_ir_from_room_hrtf_any(c, desc, false, nullptr, hrir, n_az, n_el, hrir_taps, taps, out_taps, out_ir);
+}
+
+int gas_conv_ir_from_room_bands(gas_ctx *c, const gas_room_ir *desc, const gas_room_bands *bands, uint32_t channels, uint32_t taps, float *out_taps, uint32_t *out_ir) {
+	return conv_ir_from_room_any(c, desc, true, bands, channels, taps, out_taps, out_ir);
+}
+
+int gas_conv_ir_from_room_hrtf_bands(gas_ctx *c, const gas_room_ir *desc, const gas_room_bands *bands, const float *hrir, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps, uint32_t taps, float *out_taps, uint32_t *out_ir) {
+	return conv_ir_from_room_hrtf_any(c, desc, true, bands, hrir, n_az, n_el, hrir_taps, taps, out_taps, out_ir);
 }
 
 } // extern "C"

@@ -632,6 +632,22 @@ struct gas_room_ir_frames {
 	double B[3][3], L[3][3]; // room.basis, listener.basis
 };
 hipError_t gas_launch_room_ir_hrtf(hipStream_t stream, const gas_room_ir_plan &plan, const gas_room_ir &desc, const double *d_tables, const float *d_hrir, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps, long long *d_acc, float *d_out);
+// k_room_bands.hip: gas_conv_ir_from_room_bands and gas_conv_ir_from_room_hrtf_bands.  d_acc is [bands][channels][taps],
+// band b's sums as gas_launch_room_ir[_hrtf] left them; d_filt is [bands][Lp] as gas_room_bands_fill_filters wrote it on
+// the host (step 3: row b reversed and padded with zeros to Lp).  B == 1 has L = 1, D = 0 whatever filter_taps says.
+// gas_launch_room_bands_combine writes d_out [channels][taps] f32 (steps 2, 4 and 5), in stream order.
+#define GAS_ROOM_BANDS_TILE 1792u // output taps per workgroup of the combine kernel from GAS_ROOM_BANDS_WIDE_FROM outputs on
+#define GAS_ROOM_BANDS_SMALL_TILE 256u // and below that
+#define GAS_ROOM_BANDS_WIDE_FROM (1u << 19) // channels * taps
+#define GAS_ROOM_BANDS_FILTER_STEP 16u
+struct gas_room_bands_plan {
+	double lambda[GAS_ROOM_MAX_BANDS]; // step 2's lambda_b
+	double level;
+	uint32_t bands, channels, taps;
+	uint32_t L, D, Lp; // Lp = L rounded up to GAS_ROOM_BANDS_FILTER_STEP
+};
+void gas_room_bands_fill_filters(const gas_room_bands &bands, double rate, const gas_room_bands_plan &plan, double *host_filt);
+hipError_t gas_launch_room_bands_combine(hipStream_t stream, const gas_room_bands_plan &plan, const long long *d_acc, const double *d_filt, float *d_out);
 hipError_t gas_launch_sample_sources(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc /* 16.16 step per row for resampled playbacks, or nullptr */, const uint8_t *feed = nullptr /* the feed table when an entry of the list is fed (GAS_FEED_NONE, above) */);
 hipError_t gas_launch_sample_adpcm(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc, bool span /* false: every load decodes from its checkpoint (GAS_ADPCM_SPAN=0) */); // the GAS_PCM_IMA_ADPCM rows of the same list, after gas_launch_sample_sources
 hipError_t gas_launch_sample_qoa(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc, bool span /* false: every load decodes from its record (GAS_QOA_SPAN=0) */); // the GAS_PCM_QOA rows of the same list, after gas_launch_sample_sources

@@ -1044,6 +1044,65 @@ int gas_conv_ir_from_room(gas_ctx *ctx, const gas_room_ir *desc, uint32_t channe
  * shell-per-workgroup shape, the host layer, godot_module/ and gas_multi. */
 int gas_conv_ir_from_room_hrtf(gas_ctx *ctx, const gas_room_ir *desc, const float *hrir /* host [n_az * n_el][2 ears][hrir_taps] f32 */, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps /* 1 .. GAS_HRTF_TAPS */, uint32_t taps, float *out_taps /* host [2][taps], may be NULL */, uint32_t *out_ir /* may be NULL */);
 
+/* NEW: gas_conv_ir_from_room_bands and gas_conv_ir_from_room_hrtf_bands -- the two calls above with walls that absorb
+ * differently per frequency band and with air that absorbs over distance.  With one broadband reflectance per wall every
+ * image arrives with a flat spectrum and all frequencies decay at one rate; here the spectrum is split into B bands by
+ * linear-phase filters, each band has its own six reflectances and its own loss per metre, and the bands are summed.
+ * desc->room.reflectance is validated as before but not used: bands->reflectance[b] takes its place.
+ *
+ * The rule.  Inputs are float32 and are widened to float64; everything up to the final conversion is float64.
+ *  1. Band sums.  For each band b < B = n_bands, acc_b[e][k] are the int64 sums of steps 1 - 5 of gas_conv_ir_from_room
+ *     with room.reflectance := bands.reflectance[b] (for the _hrtf call: steps 1 - 4 of gas_conv_ir_from_room_hrtf).  The
+ *     candidate box, the order masks and the refusal above 2^28 cells do not depend on a reflectance and are the same for
+ *     every band.
+ *  2. Air.  c = speed_of_sound, rate = mix_rate:  lambda_b = (ln 10 / 20) air_db_per_m[b] c / rate, left to right;
+ *     g_b[k] = exp(-(lambda_b k));  u_b[e][k] = ((double)acc_b[e][k] 2^-32) g_b[k].  Tap k lies k c / rate metres beyond
+ *     the direct path, so this is attenuation over distance written as a function of time.  At air_db_per_m[b] == 0,
+ *     g is exactly 1.
+ *  3. Band filters, L = filter_taps, D = (L - 1) / 2, built on the host:
+ *     w[j] = 0.42 - 0.5 cos(2 pi j / (L - 1)) + 0.08 cos(4 pi j / (L - 1));  for crossover i, nu = crossover_hz[i] / rate,
+ *     s_i[j] = w[j] (j == D ? 2 nu : sin(2 pi nu (j - D)) / (pi (j - D)));  lp_i = s_i / sum_j s_i[j], the sum taken in
+ *     ascending j.  F_0 = lp_0;  F_b = lp_b - lp_(b-1) for 0 < b < B - 1;  F_(B-1) = delta_D - lp_(B-2).  For B == 1,
+ *     F_0 = delta_D with L = 1, D = 0 (filter_taps is not read).  The filters sum to delta_D by construction.
+ *  4. Combine.  y[e][t] = sum_b sum_(j<L) F_b[j] u_b[e][t + D - j]; a term whose index t + D - j falls outside [0, taps)
+ *     is dropped.  The D samples of delay of the linear-phase filters are taken back out: tap 0 stays the arrival of the
+ *     direct sound.  The order of summation is fixed (bands ascending, within a band j descending, one running sum per
+ *     tap, each product fused into the sum) and nothing in this step is atomic.
+ *  5. Scale.  h[e][t] = (float)((double)level y[e][t]).
+ * Consequences.  B == 1 with air_db_per_m[0] == 0 is bitwise gas_conv_ir_from_room of a descriptor whose room.reflectance
+ * is reflectance[0] (a product with 1 and a power of two are exact); the _hrtf call likewise.  With every band's
+ * reflectances equal and no air the result equals the plain call's within float32's last rounding (4e-9 to 7e-9 relative
+ * RMS in the float64 reference).  The direct sound of a min_order = 0 result arrives at tap 0 as exactly `level`, whatever
+ * the bands and the air: it has R = 1 in every band, g_b[0] = 1, and the filters sum to delta_D (with every wall dead
+ * tap 0 is `level` to the bit and the other taps hold what the float64 sum of the filters leaves, below 1e-15; with
+ * live walls whose bands differ, reflections within D taps of tap 0 reach it through the band filters as they reach
+ * every tap near them).  Two runs of one call give the same bits.
+ *
+ * out_ir, out_taps, threading, the flushing of deferred callbacks, the gas_profile_enable bracket (B zeroings, B sums,
+ * B scalings and the combine) and the freeing of the temporaries (B times the plain call's sums and tables, the filter
+ * table of B L float64) on every way out are as for the plain call of the same name.
+ * Refusals, each with nothing loaded and nothing written.  GAS_ERR_INVALID_ARGUMENT: everything the plain call of the
+ * same name refuses; a NULL bands; n_bands == 0 or n_bands > GAS_ROOM_MAX_BANDS; for B > 1 a filter_taps that is even,
+ * below 3 or above GAS_ROOM_BAND_FILTER_MAX_TAPS; a crossover among the B - 1 read that is not finite, not positive,
+ * not below rate / 2 or not strictly above its predecessor; a reflectance in the B rows read that is outside [0, 1] (a
+ * NaN is); an air_db_per_m among the B read that is negative or not finite; reserved != 0.  Entries beyond B (beyond
+ * B - 1 for crossovers) are neither read nor checked.  GAS_ERR_UNSUPPORTED_CHAIN and GAS_ERR_DEVICE: as for the plain
+ * calls.
+ * Out of scope: jitter against flutter echoes, minimum-phase band filters, a level per band, rooms that are not boxes,
+ * bands for gas_calc_early_reflections' taps, the host layer, godot_module/ and gas_multi. */
+#define GAS_ROOM_MAX_BANDS 8
+#define GAS_ROOM_BAND_FILTER_MAX_TAPS 4095
+typedef struct gas_room_bands { /* NEW; 264 bytes */
+	uint32_t n_bands; /* B: 1 .. GAS_ROOM_MAX_BANDS */
+	uint32_t filter_taps; /* L: odd, 3 .. GAS_ROOM_BAND_FILTER_MAX_TAPS; not read when B == 1 */
+	float crossover_hz[GAS_ROOM_MAX_BANDS - 1]; /* B - 1 read: strictly ascending, 0 < c < mix_rate / 2 */
+	float reflectance[GAS_ROOM_MAX_BANDS][6]; /* per band, wall order of gas_room; 0 .. 1; B rows read */
+	float air_db_per_m[GAS_ROOM_MAX_BANDS]; /* per band, >= 0, finite: dB lost per metre of path beyond the direct path */
+	uint32_t reserved; /* 0 */
+} gas_room_bands;
+int gas_conv_ir_from_room_bands(gas_ctx *ctx, const gas_room_ir *desc, const gas_room_bands *bands, uint32_t channels /* 1 or 2 */, uint32_t taps, float *out_taps /* host [channels][taps], may be NULL */, uint32_t *out_ir /* may be NULL */);
+int gas_conv_ir_from_room_hrtf_bands(gas_ctx *ctx, const gas_room_ir *desc, const gas_room_bands *bands, const float *hrir /* host [n_az * n_el][2 ears][hrir_taps] f32 */, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps /* 1 .. GAS_HRTF_TAPS */, uint32_t taps, float *out_taps /* host [2][taps], may be NULL */, uint32_t *out_ir /* may be NULL */);
+
 
 /* ---- device-resident source sampling ------------------------------------------------
  * The step in front of the path: AudioStreamPlayback::mix into the 64-frame lookahead window with the

@@ -5,6 +5,10 @@
   python tools/time_room_ir.py test         the largest shape of tests/test_gpu_room_ir.py (16 384 taps)
   python tools/time_room_ir.py --hrtf SHAPE the same shape through gas_conv_ir_from_room_hrtf, with synth.synthetic_hrir's
                                             1024 directions of 256 taps as a 64 x 16 grid
+  python tools/time_room_ir.py --bands B --filter-taps L [--hrtf] SHAPE
+                                            the same shape through gas_conv_ir_from_room_bands (or _hrtf_bands): B bands
+                                            split at 500 Hz and 4 kHz (B = 3) or at B - 1 points from 125 Hz to 8 kHz,
+                                            walls that absorb more per band, air on all bands but the lowest
 
 Prints one JSON line: the wall clock of a whole loading call (tables, allocations, launches, transform, synchronise) as
 the median of STEPS calls, the span of the generator's launches from the library's HIP-event bracket
@@ -13,7 +17,9 @@ reference's time on the same inputs, and the parity of the read-back taps agains
 max|h|, worst channel).  With --hrtf also the 8-byte adds the reference counts (non-zero products that land on a tap),
 their bytes and the rate over the generator's span, and near_edge: the images whose cell two atan2 may choose
 differently (tests/room_brir_ref.py); the long shape's reference takes minutes and is skipped unless --reference is
-given."""
+given.  With --bands the reference is tests/room_bands_ref.py (B passes of the one above plus the float64 combine), and
+the line also holds the float64 multiply-adds of the combine, channels taps B L, and the plain call timed in the same
+process, so that "B lattice passes plus the combine" can be read off one line."""
 import json
 import os
 import sys
@@ -25,6 +31,7 @@ sys.path.insert(0, ".")
 sys.path.insert(0, os.path.join(".", "tests"))
 import godot_audio_spatializer_amd as gas  # noqa: E402
 from godot_audio_spatializer_amd import synth  # noqa: E402
+import room_bands_ref as BD  # noqa: E402
 import room_brir_ref as BR  # noqa: E402
 import room_ir_ref as R  # noqa: E402
 
@@ -65,20 +72,15 @@ def count_adds(ref, hrir, taps):
     return adds
 
 
-def main(shape, hrtf, want_reference):
-    kw, channels, taps = SHAPES[shape]
-    d = K.default_room_ir(**kw)
-    hrir = synth.synthetic_hrir(np.random.default_rng(0), dirs=N_AZ * N_EL) if hrtf else None
-    ctx = gas.SpatializerContext(max_sources=4, frames=512)
-    ctx.reserve_conv(1, taps)
+def make_bands(d, n_bands, filter_taps):
+    """B bands over the descriptor's own walls: band b reflects 1 - 0.05 b of what they do and loses 0.01 b dB a metre."""
+    xo = {1: (), 2: (1000.0,), 3: (500.0, 4000.0)}.get(n_bands) or tuple(float(v) for v in np.geomspace(125.0, 8000.0, n_bands - 1))
+    walls = d["room"]["reflectance"][0].astype(np.float64)
+    return K.default_room_bands(xo, [walls * (1.0 - 0.05 * b) for b in range(n_bands)], [0.01 * b for b in range(n_bands)], filter_taps)
 
-    def call(**how):
-        if hrtf:
-            return ctx.conv_ir_from_room_hrtf(d, hrir, N_AZ, N_EL, taps, **how)
-        return ctx.conv_ir_from_room(d, channels, taps, **how)
 
-    n, cells = R.box(d, 1 if hrtf else channels, taps, 48000.0)
-    out = {"shape": shape, "hrtf": hrtf, "channels": channels, "taps": taps, "N": n, "cells": cells}
+def timed_calls(ctx, call):
+    """-> (call_ms dict, generator's launches ms, bracketed calls): WARMUP + STEPS loading calls, the last STEPS profiled."""
     ts = []
     for i in range(WARMUP + STEPS):
         if i == WARMUP:
@@ -90,10 +92,39 @@ def main(shape, hrtf, want_reference):
         if i >= WARMUP:
             ts.append((t1 - t0) * 1e3)
     p = ctx.profile_read()
-    out["call_ms"] = {"median": round(float(np.median(ts)), 3), "min": round(min(ts), 3), "max": round(max(ts), 3)}
-    out["generator_launches_ms"] = round(p["kernel_ms"] / max(p["launches"], 1), 3)
-    out["bracketed_calls"] = p["launches"]
     ctx.profile_enable(0)
+    return {"median": round(float(np.median(ts)), 3), "min": round(min(ts), 3), "max": round(max(ts), 3)}, round(p["kernel_ms"] / max(p["launches"], 1), 3), p["launches"]
+
+
+def main(shape, hrtf, want_reference, n_bands=0, filter_taps=0):
+    kw, channels, taps = SHAPES[shape]
+    d = K.default_room_ir(**kw)
+    bands = make_bands(d, n_bands, filter_taps) if n_bands else None
+    hrir = synth.synthetic_hrir(np.random.default_rng(0), dirs=N_AZ * N_EL) if hrtf else None
+    ctx = gas.SpatializerContext(max_sources=4, frames=512)
+    ctx.reserve_conv(1, taps)
+
+    def plain_call(**how):
+        if hrtf:
+            return ctx.conv_ir_from_room_hrtf(d, hrir, N_AZ, N_EL, taps, **how)
+        return ctx.conv_ir_from_room(d, channels, taps, **how)
+
+    def call(**how):
+        if bands is None:
+            return plain_call(**how)
+        if hrtf:
+            return ctx.conv_ir_from_room_hrtf_bands(d, bands, hrir, N_AZ, N_EL, taps, **how)
+        return ctx.conv_ir_from_room_bands(d, bands, channels, taps, **how)
+
+    n, cells = R.box(d, 1 if hrtf else channels, taps, 48000.0)
+    out = {"shape": shape, "hrtf": hrtf, "channels": channels, "taps": taps, "N": n, "cells": cells}
+    if bands is not None:
+        L = 1 if n_bands == 1 else filter_taps
+        out["bands"], out["filter_taps"], out["combine_fma"] = n_bands, L, (2 if hrtf else channels) * taps * n_bands * L
+        out["plain_call_ms"], out["plain_generator_launches_ms"], _ = timed_calls(ctx, plain_call)
+    out["call_ms"], out["generator_launches_ms"], out["bracketed_calls"] = timed_calls(ctx, call)
+    if bands is not None:
+        out["generator_minus_B_plain_ms"] = round(out["generator_launches_ms"] - n_bands * out["plain_generator_launches_ms"], 3)
     t0 = time.perf_counter()
     h = call(want_taps=True, load=False)
     out["pure_generator_with_read_back_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
@@ -102,7 +133,17 @@ def main(shape, hrtf, want_reference):
         out["reference"] = "skipped"
         print(json.dumps(out))
         return
+    if shape == "long" and bands is not None and not want_reference:
+        out["reference"] = "skipped"
+        print(json.dumps(out))
+        return
     t0 = time.perf_counter()
+    if bands is not None:
+        ref = BD.brir(d, bands, hrir, N_AZ, N_EL, taps, 48000.0) if hrtf else BD.ir(d, bands, channels, taps, 48000.0)
+        out["numpy_reference_s"] = round(time.perf_counter() - t0, 3)
+        out["parity"] = parity(h, ref.h)
+        print(json.dumps(out))
+        return
     if hrtf:
         ref = BR.brir(d, hrir, N_AZ, N_EL, taps, 48000.0)
         mono = ref.mono
@@ -120,5 +161,12 @@ def main(shape, hrtf, want_reference):
 
 
 if __name__ == "__main__":
-    args = [a for a in sys.argv[1:] if not a.startswith("--")]
-    main(args[0] if args else "default", "--hrtf" in sys.argv, "--reference" in sys.argv)
+    argv = sys.argv[1:]
+    valued = {}
+    for flag in ("--bands", "--filter-taps"):
+        if flag in argv:
+            i = argv.index(flag)
+            valued[flag] = int(argv[i + 1])
+            del argv[i : i + 2]
+    args = [a for a in argv if not a.startswith("--")]
+    main(args[0] if args else "default", "--hrtf" in argv, "--reference" in argv, valued.get("--bands", 0), valued.get("--filter-taps", 255))

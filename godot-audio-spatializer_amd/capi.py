@@ -452,6 +452,19 @@ def default_room_bands(crossover_hz=(500.0, 4000.0), reflectance=((0.9,) * 6, (0
     return b
 
 
+# gas_room_tail (gas_conv_ir_from_room_diffuse, gas_conv_ir_from_room_hrtf_diffuse)
+ROOM_TAIL_DTYPE = np.dtype([("seed", np.uint32), ("mix_time_s", np.float32), ("fade_s", np.float32), ("gain", np.float32), ("reserved", np.uint32, (4,))])
+assert ROOM_TAIL_DTYPE.itemsize == 32
+
+
+def default_room_tail(seed=0, mix_time_s=0.08, fade_s=0.02, gain=1.0):
+    """One gas_room_tail ([1]): image sources for the first 80 ms after the direct sound, then 20 ms of cross-fade into
+    the diffuse tail at the rule's level."""
+    t = np.zeros(1, ROOM_TAIL_DTYPE)
+    t["seed"], t["mix_time_s"], t["fade_s"], t["gain"] = seed, mix_time_s, fade_s, gain
+    return t
+
+
 def default_spat3d_config(n=1, **kw):
     """AudioSpatializer3D defaults (audio_spatializer_3d.h:171-187), stereo, global panning strength 0.5."""
     c = np.zeros(n, SPAT3D_CONFIG_DTYPE)
@@ -527,6 +540,8 @@ EXPORTS = [
     "gas_conv_ir_from_room_hrtf",
     "gas_conv_ir_from_room_bands",
     "gas_conv_ir_from_room_hrtf_bands",
+    "gas_conv_ir_from_room_diffuse",
+    "gas_conv_ir_from_room_hrtf_diffuse",
     "gas_conv_create",
     "gas_conv_destroy",
     "gas_conv_reset",
@@ -643,6 +658,8 @@ def load_library():
     L.gas_conv_ir_from_room_hrtf.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, C.POINTER(u32)]
     L.gas_conv_ir_from_room_bands.argtypes = [vp, vp, vp, u32, u32, vp, C.POINTER(u32)]
     L.gas_conv_ir_from_room_hrtf_bands.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, vp, C.POINTER(u32)]
+    L.gas_conv_ir_from_room_diffuse.argtypes = [vp, vp, vp, vp, u32, u32, vp, C.POINTER(u32)]
+    L.gas_conv_ir_from_room_hrtf_diffuse.argtypes = [vp, vp, vp, vp, vp, u32, u32, u32, u32, vp, C.POINTER(u32)]
     L.gas_conv_create.argtypes = [vp, u32, C.POINTER(u32)]
     L.gas_conv_destroy.argtypes = [vp, u32]
     L.gas_conv_reset.argtypes = [vp, u32]
@@ -1120,6 +1137,37 @@ class SpatializerContext:
         out = C.c_uint32()
         rc = self.lib.gas_conv_ir_from_room_hrtf_bands(self.h, _np_ptr(d), _np_ptr(b), _np_ptr(h), int(n_az), int(n_el), h.shape[2], int(taps), _np_ptr(taps_out) if want_taps else None, C.byref(out) if load else None)
         self._check(rc, "gas_conv_ir_from_room_hrtf_bands")
+        if load and want_taps:
+            return out.value, taps_out
+        return out.value if load else taps_out
+
+    def conv_ir_from_room_diffuse(self, desc, bands, tail, channels, taps, want_taps=False, load=True):
+        """conv_ir_from_room_bands with a diffuse late tail: image sources up to tail's mixing time, then a cross-fade into
+        noise that decays per band as the room's mean absorption says (tail: one ROOM_TAIL_DTYPE entry, see
+        default_room_tail).  Returns as conv_ir_from_room does."""
+        d = np.ascontiguousarray(np.asarray(desc, dtype=ROOM_IR_DTYPE).reshape(-1)[:1])
+        b = np.ascontiguousarray(np.asarray(bands, dtype=ROOM_BANDS_DTYPE).reshape(-1)[:1])
+        t = np.ascontiguousarray(np.asarray(tail, dtype=ROOM_TAIL_DTYPE).reshape(-1)[:1])
+        taps_out = np.zeros((int(channels), int(taps)), dtype=np.float32) if want_taps else None
+        out = C.c_uint32()
+        rc = self.lib.gas_conv_ir_from_room_diffuse(self.h, _np_ptr(d), _np_ptr(b), _np_ptr(t), int(channels), int(taps), _np_ptr(taps_out) if want_taps else None, C.byref(out) if load else None)
+        self._check(rc, "gas_conv_ir_from_room_diffuse")
+        if load and want_taps:
+            return out.value, taps_out
+        return out.value if load else taps_out
+
+    def conv_ir_from_room_hrtf_diffuse(self, desc, bands, tail, hrir, n_az, n_el, taps, want_taps=False, load=True):
+        """conv_ir_from_room_hrtf_bands with a diffuse late tail; arguments as conv_ir_from_room_diffuse and
+        conv_ir_from_room_hrtf, the taps are [2][taps]."""
+        d = np.ascontiguousarray(np.asarray(desc, dtype=ROOM_IR_DTYPE).reshape(-1)[:1])
+        b = np.ascontiguousarray(np.asarray(bands, dtype=ROOM_BANDS_DTYPE).reshape(-1)[:1])
+        t = np.ascontiguousarray(np.asarray(tail, dtype=ROOM_TAIL_DTYPE).reshape(-1)[:1])
+        h = np.ascontiguousarray(np.asarray(hrir, dtype=np.float32))
+        assert h.ndim == 3 and h.shape[0] == int(n_az) * int(n_el) and h.shape[1] == 2, h.shape
+        taps_out = np.zeros((2, int(taps)), dtype=np.float32) if want_taps else None
+        out = C.c_uint32()
+        rc = self.lib.gas_conv_ir_from_room_hrtf_diffuse(self.h, _np_ptr(d), _np_ptr(b), _np_ptr(t), _np_ptr(h), int(n_az), int(n_el), h.shape[2], int(taps), _np_ptr(taps_out) if want_taps else None, C.byref(out) if load else None)
+        self._check(rc, "gas_conv_ir_from_room_hrtf_diffuse")
         if load and want_taps:
             return out.value, taps_out
         return out.value if load else taps_out

@@ -1,5 +1,6 @@
 // gas_ctx_conv.hip -- the bus convolvers of include/gas_amd.h (gas_ctx_reserve_conv, gas_conv_*; k_conv.hip) and the
-// impulse responses built on the device from box rooms (gas_conv_ir_from_room*; k_room_ir.hip, k_room_bands.hip).
+// impulse responses built on the device from box rooms (gas_conv_ir_from_room*; k_room_ir.hip, k_room_bands.hip,
+// k_room_tail.hip).
 #include "gas_ctx_priv.h"
 
 extern "C" {
@@ -491,9 +492,11 @@ static bool room_bands_ok(const gas_room_bands &b, float rate) {
 // the generator's launches inside the profile bracket, registration and read-back.  set == nullptr: k_room_ir with
 // `channels` receivers; otherwise k_room_ir_hrtf, two ears.  bands == nullptr: the plain calls, one pass whose scaled
 // taps are the result; otherwise one such pass per band with that band's reflectances, each into its own sums, and
-// k_room_bands_combine over them writes the result.
-static int conv_ir_from_plan(gas_ctx *c, const gas_room_ir &desc, const gas_room_ir_plan &plan, uint32_t channels, const RoomIrSet *set, const gas_room_bands *bands, float *out_taps, uint32_t *out_ir) {
-	const uint32_t taps = plan.taps;
+// k_room_bands_combine over them writes the result.  tail != nullptr (with bands): the *_diffuse calls -- `plan` is
+// the lattice's, made for K1 taps (0: no lattice pass), its passes go into sums of their own, [passes][channels][K1],
+// and k_room_tail mixes them into the sums of tail->taps taps that the combine reads.
+static int conv_ir_from_plan(gas_ctx *c, const gas_room_ir &desc, const gas_room_ir_plan &plan, uint32_t channels, const RoomIrSet *set, const gas_room_bands *bands, const gas_room_tail_plan *tail, float *out_taps, uint32_t *out_ir) {
+	const uint32_t taps = tail ? tail->taps : plan.taps;
 	const uint32_t passes = bands ? bands->n_bands : 1u;
 	const size_t per_pass = gas_room_ir_table_doubles(plan);
 	gas_room_bands_plan bp{};
@@ -531,13 +534,18 @@ static int conv_ir_from_plan(gas_ctx *c, const gas_room_ir &desc, const gas_room
 		GAS_TRY(flush_deferred(c));
 	}
 	GAS_HIP(c, hipSetDevice(c->cfg.device));
-	const size_t n = (size_t)channels * taps;
+	const size_t n = (size_t)channels * taps, n_lat = (size_t)channels * plan.taps;
 	Mem tmp; // frees the buffers on every way out
 	double *d_tables = nullptr, *d_filt = nullptr;
-	long long *d_acc = nullptr;
+	long long *d_acc = nullptr, *d_lat = nullptr; // what the combine reads; what the lattice passes write
 	float *d_ir = nullptr, *d_hrir = nullptr;
 	GAS_HIP(c, tmp.alloc(d_tables, tables.size()));
 	GAS_HIP(c, tmp.alloc(d_acc, n * passes));
+	if (!tail) {
+		d_lat = d_acc;
+	} else if (n_lat != 0) {
+		GAS_HIP(c, tmp.alloc(d_lat, n_lat * passes));
+	}
 	GAS_HIP(c, tmp.alloc(d_ir, n));
 	GAS_HIP(c, hipMemcpy(d_tables, tables.data(), tables.size() * sizeof(double), hipMemcpyHostToDevice)); // complete on return
 	if (bands) {
@@ -553,12 +561,15 @@ static int conv_ir_from_plan(gas_ctx *c, const gas_room_ir &desc, const gas_room
 	if (timed) {
 		GAS_HIP(c, c->prof.begin(c->stream));
 	}
-	for (uint32_t b = 0; b < passes; b++) { // in stream order: a band's scaled taps in d_ir are overwritten by the next writer
+	for (uint32_t b = 0; b < passes && n_lat != 0; b++) { // in stream order: a band's scaled taps in d_ir (n_lat <= n of them) are overwritten by the next writer
 		if (set) {
-			GAS_HIP(c, gas_launch_room_ir_hrtf(c->stream, plan, desc, d_tables + per_pass * b, d_hrir, set->n_az, set->n_el, set->taps, d_acc + n * b, d_ir));
+			GAS_HIP(c, gas_launch_room_ir_hrtf(c->stream, plan, desc, d_tables + per_pass * b, d_hrir, set->n_az, set->n_el, set->taps, d_lat + n_lat * b, d_ir));
 		} else {
-			GAS_HIP(c, gas_launch_room_ir(c->stream, plan, d_tables + per_pass * b, d_acc + n * b, d_ir));
+			GAS_HIP(c, gas_launch_room_ir(c->stream, plan, d_tables + per_pass * b, d_lat + n_lat * b, d_ir));
 		}
+	}
+	if (tail) {
+		GAS_HIP(c, gas_launch_room_tail(c->stream, *tail, d_lat, d_acc));
 	}
 	if (bands) {
 		GAS_HIP(c, gas_launch_room_bands_combine(c->stream, bp, d_acc, d_filt, d_ir));
@@ -585,9 +596,32 @@ static int conv_ir_from_plan(gas_ctx *c, const gas_room_ir &desc, const gas_room
 	return GAS_OK;
 }
 
-// gas_conv_ir_from_room and gas_conv_ir_from_room_bands: `banded` says which, so that a NULL bands is refused by the second.
-static int conv_ir_from_room_any(gas_ctx *c, const gas_room_ir *desc, bool banded, const gas_room_bands *bands, uint32_t channels, uint32_t taps, float *out_taps, uint32_t *out_ir) {
-	if (!c || !desc || (banded && !bands) || (!out_taps && !out_ir) || (channels != 1 && channels != 2) || taps == 0) {
+// Which of the box-room calls of one name this is: it decides which of `bands` and `tail` must be there.
+enum RoomCall { ROOM_PLAIN, ROOM_BANDS, ROOM_DIFFUSE };
+
+// The *_diffuse calls' two plans once the descriptor's plain fields and the bands have passed: steps 1 - 3 of
+// gas_conv_ir_from_room_diffuse.  `receivers` is the lattice's (1 for the HRTF call), `channels` the result's.  `lattice`
+// is made for K1 taps, so its cell check is; with K1 == 0 only its geometry (the points inside the box, d0) is wanted, and
+// it is made from a descriptor whose box cannot be refused for its size.  False for what either plan refuses.
+static bool room_tail_plans(const gas_room_ir &desc, const gas_room_bands &bands, const gas_room_tail &tail, uint32_t receivers, uint32_t channels, uint32_t taps, float rate, gas_room_ir_plan &lattice, gas_room_tail_plan &tp) {
+	uint32_t K0 = 0, K1 = 0;
+	if (!gas_room_tail_marks(tail, (double)rate, taps, K0, K1)) {
+		return false;
+	}
+	gas_room_ir d = desc;
+	if (K1 == 0) {
+		d.ear_spacing = 0.0f;
+		d.min_order = 0;
+		d.max_order = 1;
+	}
+	return gas_room_ir_make_plan(d, receivers, K1, rate, lattice) && gas_room_tail_make_plan(lattice, bands, tail, channels, taps, K0, K1, tp);
+}
+
+// gas_conv_ir_from_room, gas_conv_ir_from_room_bands and gas_conv_ir_from_room_diffuse: `call` says which, so that a NULL
+// bands or tail is refused by the calls that need it.
+static int conv_ir_from_room_any(gas_ctx *c, const gas_room_ir *desc, RoomCall call, const gas_room_bands *bands, const gas_room_tail *tail, uint32_t channels, uint32_t taps, float *out_taps, uint32_t *out_ir) {
+	const bool banded = call != ROOM_PLAIN;
+	if (!c || !desc || (banded && !bands) || (call == ROOM_DIFFUSE && !tail) || (!out_taps && !out_ir) || (channels != 1 && channels != 2) || taps == 0) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
 	if (out_ir && c->conv.count == 0) {
@@ -597,14 +631,19 @@ static int conv_ir_from_room_any(gas_ctx *c, const gas_room_ir *desc, bool bande
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
 	gas_room_ir_plan plan;
-	if (!room_ir_desc_ok(*desc, true) || (banded && !room_bands_ok(*bands, c->cfg.mix_rate)) || !gas_room_ir_make_plan(*desc, channels, taps, c->cfg.mix_rate, plan)) {
+	gas_room_tail_plan tp;
+	if (!room_ir_desc_ok(*desc, true) || (banded && !room_bands_ok(*bands, c->cfg.mix_rate))) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
-	return conv_ir_from_plan(c, *desc, plan, channels, nullptr, bands, out_taps, out_ir);
+	if (call == ROOM_DIFFUSE ? !room_tail_plans(*desc, *bands, *tail, channels, channels, taps, c->cfg.mix_rate, plan, tp) : !gas_room_ir_make_plan(*desc, channels, taps, c->cfg.mix_rate, plan)) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	return conv_ir_from_plan(c, *desc, plan, channels, nullptr, bands, call == ROOM_DIFFUSE ? &tp : nullptr, out_taps, out_ir);
 }
 
-static int conv_ir_from_room_hrtf_any(gas_ctx *c, const gas_room_ir *desc, bool banded, const gas_room_bands *bands, const float *hrir, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps, uint32_t taps, float *out_taps, uint32_t *out_ir) {
-	if (!c || !desc || (banded && !bands) || !hrir || (!out_taps && !out_ir) || taps == 0) {
+static int conv_ir_from_room_hrtf_any(gas_ctx *c, const gas_room_ir *desc, RoomCall call, const gas_room_bands *bands, const gas_room_tail *tail, const float *hrir, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps, uint32_t taps, float *out_taps, uint32_t *out_ir) {
+	const bool banded = call != ROOM_PLAIN;
+	if (!c || !desc || (banded && !bands) || (call == ROOM_DIFFUSE && !tail) || !hrir || (!out_taps && !out_ir) || taps == 0) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
 	if (n_az == 0 || n_el == 0 || (uint64_t)n_az * n_el > 65536u || hrir_taps == 0 || hrir_taps > GAS_HRTF_TAPS) {
@@ -617,7 +656,11 @@ static int conv_ir_from_room_hrtf_any(gas_ctx *c, const gas_room_ir *desc, bool 
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
 	gas_room_ir_plan plan;
-	if (!room_ir_desc_ok(*desc, false) || (banded && !room_bands_ok(*bands, c->cfg.mix_rate)) || !gas_room_ir_make_plan(*desc, 1, taps, c->cfg.mix_rate, plan)) { // one receiver: ear_spacing is not read
+	gas_room_tail_plan tp;
+	if (!room_ir_desc_ok(*desc, false) || (banded && !room_bands_ok(*bands, c->cfg.mix_rate))) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (call == ROOM_DIFFUSE ? !room_tail_plans(*desc, *bands, *tail, 1, 2, taps, c->cfg.mix_rate, plan, tp) : !gas_room_ir_make_plan(*desc, 1, taps, c->cfg.mix_rate, plan)) { // one receiver: ear_spacing is not read
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
 	const size_t floats = (size_t)n_az * n_el * 2 * hrir_taps;
@@ -627,23 +670,31 @@ static int conv_ir_from_room_hrtf_any(gas_ctx *c, const gas_room_ir *desc, bool 
 		}
 	}
 	const RoomIrSet set{hrir, n_az, n_el, hrir_taps};
-	return conv_ir_from_plan(c, *desc, plan, 2, &set, bands, out_taps, out_ir);
+	return conv_ir_from_plan(c, *desc, plan, 2, &set, bands, call == ROOM_DIFFUSE ? &tp : nullptr, out_taps, out_ir);
 }
 
 int gas_conv_ir_from_room(gas_ctx *c, const gas_room_ir *desc, uint32_t channels, uint32_t taps, float *out_taps, uint32_t *out_ir) {
-	return conv_ir_from_room_any(c, desc, false, nullptr, channels, taps, out_taps, out_ir);
+	return conv_ir_from_room_any(c, desc, ROOM_PLAIN, nullptr, nullptr, channels, taps, out_taps, out_ir);
 }
 
 int gas_conv_ir_from_room_hrtf(gas_ctx *c, const gas_room_ir *desc, const float *hrir, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps, uint32_t taps, float *out_taps, uint32_t *out_ir) {
-	return conv_ir_from_room_hrtf_any(c, desc, false, nullptr, hrir, n_az, n_el, hrir_taps, taps, out_taps, out_ir);
+	return conv_ir_from_room_hrtf_any(c, desc, ROOM_PLAIN, nullptr, nullptr, hrir, n_az, n_el, hrir_taps, taps, out_taps, out_ir);
 }
 
 int gas_conv_ir_from_room_bands(gas_ctx *c, const gas_room_ir *desc, const gas_room_bands *bands, uint32_t channels, uint32_t taps, float *out_taps, uint32_t *out_ir) {
-	return conv_ir_from_room_any(c, desc, true, bands, channels, taps, out_taps, out_ir);
+	return conv_ir_from_room_any(c, desc, ROOM_BANDS, bands, nullptr, channels, taps, out_taps, out_ir);
 }
 
 int gas_conv_ir_from_room_hrtf_bands(gas_ctx *c, const gas_room_ir *desc, const gas_room_bands *bands, const float *hrir, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps, uint32_t taps, float *out_taps, uint32_t *out_ir) {
-	return conv_ir_from_room_hrtf_any(c, desc, true, bands, hrir, n_az, n_el, hrir_taps, taps, out_taps, out_ir);
+	return conv_ir_from_room_hrtf_any(c, desc, ROOM_BANDS, bands, nullptr, hrir, n_az, n_el, hrir_taps, taps, out_taps, out_ir);
+}
+
+int gas_conv_ir_from_room_diffuse(gas_ctx *c, const gas_room_ir *desc, const gas_room_bands *bands, const gas_room_tail *tail, uint32_t channels, uint32_t taps, float *out_taps, uint32_t *out_ir) {
+	return conv_ir_from_room_any(c, desc, ROOM_DIFFUSE, bands, tail, channels, taps, out_taps, out_ir);
+}
+
+int gas_conv_ir_from_room_hrtf_diffuse(gas_ctx *c, const gas_room_ir *desc, const gas_room_bands *bands, const gas_room_tail *tail, const float *hrir, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps, uint32_t taps, float *out_taps, uint32_t *out_ir) {
+	return conv_ir_from_room_hrtf_any(c, desc, ROOM_DIFFUSE, bands, tail, hrir, n_az, n_el, hrir_taps, taps, out_taps, out_ir);
 }
 
 } // extern "C"

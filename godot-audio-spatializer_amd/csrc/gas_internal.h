@@ -648,6 +648,25 @@ struct gas_room_bands_plan {
 };
 void gas_room_bands_fill_filters(const gas_room_bands &bands, double rate, const gas_room_bands_plan &plan, double *host_filt);
 hipError_t gas_launch_room_bands_combine(hipStream_t stream, const gas_room_bands_plan &plan, const long long *d_acc, const double *d_filt, float *d_out);
+// k_room_tail.hip: gas_conv_ir_from_room_diffuse and gas_conv_ir_from_room_hrtf_diffuse.  gas_room_tail_marks is step 1's
+// K0 and K1; false for what a gas_room_tail is refused for on its own: a field that is negative or not finite,
+// reserved != 0 (a NULL tail is the caller's to refuse first).  gas_room_tail_make_plan is step 3 on the host in float64
+// from the lattice plan's geometry (h, d0, c, rate; its taps are not read); false for s0 not finite or above
+// GAS_ROOM_TAIL_S0_MAX.
+// gas_launch_room_tail reads d_spec [bands][channels][K1], band b's sums as gas_launch_room_ir[_hrtf] left them for a plan
+// of K1 taps (not read when K1 == 0), and writes every element of d_acc [bands][channels][taps] (steps 4 - 6), in stream
+// order; gas_launch_room_bands_combine takes it from there.
+#define GAS_ROOM_TAIL_S0_MAX 1024.0
+struct gas_room_tail_plan {
+	double mu[GAS_ROOM_MAX_BANDS]; // step 3's mu_b; not read for a band of `dead`
+	double s0, d0, c, rate;
+	uint32_t seed, K0, K1;
+	uint32_t bands, channels, taps;
+	uint32_t dead; // bit b: rho_b == 0, the band's diffuse part is 0
+};
+bool gas_room_tail_marks(const gas_room_tail &tail, double rate, uint32_t taps, uint32_t &K0, uint32_t &K1);
+bool gas_room_tail_make_plan(const gas_room_ir_plan &geometry, const gas_room_bands &bands, const gas_room_tail &tail, uint32_t channels, uint32_t taps, uint32_t K0, uint32_t K1, gas_room_tail_plan &plan);
+hipError_t gas_launch_room_tail(hipStream_t stream, const gas_room_tail_plan &plan, const long long *d_spec, long long *d_acc);
 hipError_t gas_launch_sample_sources(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc /* 16.16 step per row for resampled playbacks, or nullptr */, const uint8_t *feed = nullptr /* the feed table when an entry of the list is fed (GAS_FEED_NONE, above) */);
 hipError_t gas_launch_sample_adpcm(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc, bool span /* false: every load decodes from its checkpoint (GAS_ADPCM_SPAN=0) */); // the GAS_PCM_IMA_ADPCM rows of the same list, after gas_launch_sample_sources
 hipError_t gas_launch_sample_qoa(hipStream_t stream, gas_cursor *cursors, const uint32_t *slots, uint32_t n, uint32_t frames, const float *fade_env, gas_audio_frame *rows, const uint32_t *row_inc, bool span /* false: every load decodes from its record (GAS_QOA_SPAN=0) */); // the GAS_PCM_QOA rows of the same list, after gas_launch_sample_sources

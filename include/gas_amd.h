@@ -1088,8 +1088,9 @@ int gas_conv_ir_from_room_hrtf(gas_ctx *ctx, const gas_room_ir *desc, const floa
  * NaN is); an air_db_per_m among the B read that is negative or not finite; reserved != 0.  Entries beyond B (beyond
  * B - 1 for crossovers) are neither read nor checked.  GAS_ERR_UNSUPPORTED_CHAIN and GAS_ERR_DEVICE: as for the plain
  * calls.
- * Out of scope: jitter against flutter echoes, minimum-phase band filters, a level per band, rooms that are not boxes,
- * bands for gas_calc_early_reflections' taps, the host layer, godot_module/ and gas_multi. */
+ * Out of scope: jitter against flutter echoes (a diffuse late tail is a call of its own, gas_conv_ir_from_room_diffuse,
+ * declared below), minimum-phase band filters, a level per band, rooms that are not boxes, bands for
+ * gas_calc_early_reflections' taps, the host layer, godot_module/ and gas_multi. */
 #define GAS_ROOM_MAX_BANDS 8
 #define GAS_ROOM_BAND_FILTER_MAX_TAPS 4095
 typedef struct gas_room_bands { /* NEW; 264 bytes */
@@ -1102,6 +1103,77 @@ typedef struct gas_room_bands { /* NEW; 264 bytes */
 } gas_room_bands;
 int gas_conv_ir_from_room_bands(gas_ctx *ctx, const gas_room_ir *desc, const gas_room_bands *bands, uint32_t channels /* 1 or 2 */, uint32_t taps, float *out_taps /* host [channels][taps], may be NULL */, uint32_t *out_ir /* may be NULL */);
 int gas_conv_ir_from_room_hrtf_bands(gas_ctx *ctx, const gas_room_ir *desc, const gas_room_bands *bands, const float *hrir /* host [n_az * n_el][2 ears][hrir_taps] f32 */, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps /* 1 .. GAS_HRTF_TAPS */, uint32_t taps, float *out_taps /* host [2][taps], may be NULL */, uint32_t *out_ir /* may be NULL */);
+
+/* NEW: gas_conv_ir_from_room_diffuse and gas_conv_ir_from_room_hrtf_diffuse -- the two *_bands calls above with a diffuse
+ * late tail behind the image sources.  A box with mirror walls is not a diffuse room: out to the last tap the image
+ * lattice keeps the flutter and the sweeping echoes the method is known for, its late energy decays more slowly than a
+ * room's (paths along the least absorbing axis survive), and its cost grows with the cube of the response's length.
+ * Here the images are kept up to a mixing time; from there the response cross-fades into shaped noise whose decay per
+ * band follows the room's mean absorption by Eyring's formula, and the lattice is walked for the specular part alone.
+ * `bands` is required; a broadband room is n_bands = 1.  This is NEW behaviour with no engine counterpart.
+ *
+ * The rule.  Inputs are float32 and are widened to float64; everything up to the final conversion is float64, left to
+ * right, with no fused multiply-adds except where the *_bands rule allows them.  rate = mix_rate, c = speed_of_sound,
+ * h = half_extent, d0 as in step 1 of gas_conv_ir_from_room, B = n_bands.
+ *  1. Fade marks.  K0 = min(taps, llrint(min(mix_time_s rate, 2^31)));  K1 = min(taps, K0 + llrint(min(fade_s rate,
+ *     2^31)));  Kf = K1 - K0.  For tap k: x = k < K0 ? 0 : (k >= K1 ? 1 : (k - K0) / Kf);  ws[k] = sqrt(1 - x),
+ *     wd[k] = sqrt(x).  The two are power-complementary, and sqrt is correctly rounded on every side.
+ *  2. Specular sums.  acc_b[e][k] for k < K1 are the int64 band sums of step 1 of the *_bands rule (for the _hrtf call:
+ *     those of gas_conv_ir_from_room_hrtf_bands); order masks, min_order and max_order apply as there.  Taps k >= K1 take
+ *     nothing specular.  By step 2 of gas_conv_ir_from_room no image outside the candidate box for K1 taps reaches a tap
+ *     below K1, so the lattice passes run as for an IR of K1 taps, and the refusal above 2^28 cells is evaluated for K1
+ *     taps, not for `taps`.  With K1 == 0 there is no lattice pass and no cell check.
+ *  3. Decay per band.  V = 8 h_x h_y h_z;  A_x = 4 h_y h_z, A_y = 4 h_x h_z, A_z = 4 h_x h_y;  S = 2 (A_x + A_y + A_z).
+ *     With R = bands.reflectance[b]:  rho_b = (A_x (R[0] R[0] + R[1] R[1]) + A_y (R[2] R[2] + R[3] R[3]) +
+ *     A_z (R[4] R[4] + R[5] R[5])) / S, the walls' mean energy reflectance;  mu_b = -ln(rho_b) S / (4 V), the energy lost
+ *     per metre (Eyring).  rho_b == 0 makes the band's diffuse part 0.
+ *     s0 = gain sqrt(((4 pi c) (d0 d0)) / (V rate)): the echo density 4 pi r^2 (c / rate) / V times (d0 / r)^2, so the
+ *     level is relative to the direct sound as every image's v is.  r_k = d0 + c k / rate.  Air is not applied here:
+ *     step 2 of the *_bands rule applies g_b[k] to whatever the sums hold, the diffuse part included.
+ *  4. Noise, one stream per ear, shared by all bands, so that the band filters still sum to a delta over it.  In 64-bit
+ *     unsigned arithmetic mod 2^64:  z = (seed << 32) | (e << 24) | k;  z += 0x9E3779B97F4A7C15;
+ *     z = (z ^ (z >> 30)) 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) 0x94D049BB133111EB;  z ^= z >> 31;
+ *     u_i = (z >> 16 i) & 0xffff.  xi[e][k] = (2 (u_0 + u_1 + u_2) - 196605) / sqrt(65536^2 - 1): unit variance, odd
+ *     integer numerators.  f[e][k] = (u_3 + 0.5) / 65536.
+ *     Check vectors (seed, e, k) -> z, numerator:  (1, 0, 0) -> 0xc42c5a1aa3820138, -66133;
+ *     (1, 0, 1) -> 0x204391a6fd59956f, 84191;  (0, 1, 5) -> 0x554b78b0c52407ed, -29819;
+ *     (0xffffffff, 1, 2^20 - 1) -> 0x5e823beaa35dc300, 17553.
+ *  5. Arrivals, split as images are.  a_b[e][k] = (s0 exp(-(mu_b r_k) / 2)) xi[e][k];
+ *     d_b[e][k] = a_b[e][k] (1 - f[e][k]) + a_b[e][k - 1] f[e][k - 1], the second term absent at k = 0.  The diffuse part
+ *     so has the two-tap interpolation spectrum of the image taps and the same 2/3 of an arrival's energy per tap.
+ *  6. Mix.  acc'_b[e][k] = llrint(ws[k] (double)acc_b[e][k]) + llrint((wd[k] d_b[e][k]) 2^32); the first term is 0 for
+ *     k >= K1, and for k < K0 the result is acc_b[e][k] exactly.
+ *  7. Finish.  Steps 2 - 5 of the *_bands rule (air, band filters, combine, scale by level) over acc' at the full `taps`.
+ * Overflow: s0 <= 1024 is required, so |llrint((wd d) 2^32)| < 2^44 and the int64 sums stay below 2^62.
+ * Consequences (D = the band filters' delay, 0 for B == 1).  With K0 == taps the result is bitwise the *_bands call of the
+ * same name.  With gain == 0 every tap t >= K1 + D is exactly 0.  Taps t < K0 - D are bitwise the *_bands call's whatever
+ * the tail.  Two runs give the same bits; another seed gives other taps from K0 on.  Through unit-impulse HRIRs the
+ * specular part of the _hrtf call is the one-channel sums in both ears, as for the calls above; its diffuse parts differ
+ * per ear.  ER taps on the sources plus a min_order = 3 tail keep working: the diffuse part starts at K0 whatever the
+ * orders are.
+ * Known limits.  The level at the hand-over is theory, not a fit: `gain` is the trim.  The coherent low-frequency
+ * build-up of an image part whose reflectances are all positive is not reproduced by zero-mean noise.  The diffuse parts
+ * of the two ears are uncorrelated at all frequencies, and the _hrtf call's diffuse part is not coloured by the set.
+ *
+ * out_ir, out_taps, the pure generator, threading, the flushing of deferred callbacks, the gas_profile_enable bracket
+ * (the *_bands call's launches for K1 taps, the tail kernel and the combine) and the freeing of the temporaries (those
+ * of the *_bands call, its sums once for K1 taps and once for `taps`) on every way out are as for the *_bands call of the
+ * same name.  gas_abi_version() is unchanged.
+ * Refusals, each with nothing loaded and nothing written.  GAS_ERR_INVALID_ARGUMENT: everything the *_bands call of the
+ * same name refuses, its cell check made for K1 taps; a NULL tail; a mix_time_s, fade_s or gain that is negative or not
+ * finite; reserved != 0; s0 not finite or above 1024.  GAS_ERR_UNSUPPORTED_CHAIN and GAS_ERR_DEVICE: as for the *_bands
+ * calls.
+ * Out of scope: jitter of individual images, a diffuse-field-equalised colouring of the tail, interaural coherence of
+ * the diffuse part, a fitted hand-over level, the host layer, godot_module/ and gas_multi. */
+typedef struct gas_room_tail { /* NEW; 32 bytes */
+	uint32_t seed; /* any value; selects the noise */
+	float mix_time_s; /* >= 0, finite: the cross-fade begins this long after the direct sound */
+	float fade_s; /* >= 0, finite: its length; 0 = a hard switch */
+	float gain; /* >= 0, finite: linear trim of the diffuse part; 1 = the rule's level */
+	uint32_t reserved[4]; /* 0 */
+} gas_room_tail;
+int gas_conv_ir_from_room_diffuse(gas_ctx *ctx, const gas_room_ir *desc, const gas_room_bands *bands, const gas_room_tail *tail, uint32_t channels /* 1 or 2 */, uint32_t taps, float *out_taps /* host [channels][taps], may be NULL */, uint32_t *out_ir /* may be NULL */);
+int gas_conv_ir_from_room_hrtf_diffuse(gas_ctx *ctx, const gas_room_ir *desc, const gas_room_bands *bands, const gas_room_tail *tail, const float *hrir /* host [n_az * n_el][2 ears][hrir_taps] f32 */, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps /* 1 .. GAS_HRTF_TAPS */, uint32_t taps, float *out_taps /* host [2][taps], may be NULL */, uint32_t *out_ir /* may be NULL */);
 
 
 /* ---- device-resident source sampling ------------------------------------------------

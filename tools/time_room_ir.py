@@ -9,6 +9,10 @@
                                             the same shape through gas_conv_ir_from_room_bands (or _hrtf_bands): B bands
                                             split at 500 Hz and 4 kHz (B = 3) or at B - 1 points from 125 Hz to 8 kHz,
                                             walls that absorb more per band, air on all bands but the lowest
+  python tools/time_room_ir.py --diffuse MIX_MS FADE_MS [--bands B --filter-taps L] [--hrtf] SHAPE
+                                            the same shape through gas_conv_ir_from_room_diffuse (or _hrtf_diffuse):
+                                            image sources for MIX_MS after the direct sound, FADE_MS of cross-fade, the
+                                            diffuse tail behind them; without --bands one broadband band
 
 Prints one JSON line: the wall clock of a whole loading call (tables, allocations, launches, transform, synchronise) as
 the median of STEPS calls, the span of the generator's launches from the library's HIP-event bracket
@@ -19,7 +23,10 @@ their bytes and the rate over the generator's span, and near_edge: the images wh
 differently (tests/room_brir_ref.py); the long shape's reference takes minutes and is skipped unless --reference is
 given.  With --bands the reference is tests/room_bands_ref.py (B passes of the one above plus the float64 combine), and
 the line also holds the float64 multiply-adds of the combine, channels taps B L, and the plain call timed in the same
-process, so that "B lattice passes plus the combine" can be read off one line."""
+process, so that "B lattice passes plus the combine" can be read off one line.  With --diffuse the reference is
+tests/room_tail_ref.py, the line holds the marks K0 and K1 and the cells of the lattice for K1 taps, and the *_bands call
+of the same shape is timed in the same process (bands_call_ms, bands_generator_launches_ms), so that what the tail saves
+can be read off one line."""
 import json
 import os
 import sys
@@ -34,6 +41,7 @@ from godot_audio_spatializer_amd import synth  # noqa: E402
 import room_bands_ref as BD  # noqa: E402
 import room_brir_ref as BR  # noqa: E402
 import room_ir_ref as R  # noqa: E402
+import room_tail_ref as T  # noqa: E402
 
 K = gas.capi
 WARMUP, STEPS = 2, 7
@@ -96,10 +104,13 @@ def timed_calls(ctx, call):
     return {"median": round(float(np.median(ts)), 3), "min": round(min(ts), 3), "max": round(max(ts), 3)}, round(p["kernel_ms"] / max(p["launches"], 1), 3), p["launches"]
 
 
-def main(shape, hrtf, want_reference, n_bands=0, filter_taps=0):
+def main(shape, hrtf, want_reference, n_bands=0, filter_taps=0, diffuse=None):
     kw, channels, taps = SHAPES[shape]
     d = K.default_room_ir(**kw)
+    if diffuse and not n_bands:
+        n_bands = 1
     bands = make_bands(d, n_bands, filter_taps) if n_bands else None
+    tail = K.default_room_tail(seed=1, mix_time_s=diffuse[0] * 1e-3, fade_s=diffuse[1] * 1e-3) if diffuse else None
     hrir = synth.synthetic_hrir(np.random.default_rng(0), dirs=N_AZ * N_EL) if hrtf else None
     ctx = gas.SpatializerContext(max_sources=4, frames=512)
     ctx.reserve_conv(1, taps)
@@ -109,12 +120,19 @@ def main(shape, hrtf, want_reference, n_bands=0, filter_taps=0):
             return ctx.conv_ir_from_room_hrtf(d, hrir, N_AZ, N_EL, taps, **how)
         return ctx.conv_ir_from_room(d, channels, taps, **how)
 
-    def call(**how):
-        if bands is None:
-            return plain_call(**how)
+    def bands_call(**how):
         if hrtf:
             return ctx.conv_ir_from_room_hrtf_bands(d, bands, hrir, N_AZ, N_EL, taps, **how)
         return ctx.conv_ir_from_room_bands(d, bands, channels, taps, **how)
+
+    def call(**how):
+        if bands is None:
+            return plain_call(**how)
+        if tail is None:
+            return bands_call(**how)
+        if hrtf:
+            return ctx.conv_ir_from_room_hrtf_diffuse(d, bands, tail, hrir, N_AZ, N_EL, taps, **how)
+        return ctx.conv_ir_from_room_diffuse(d, bands, tail, channels, taps, **how)
 
     n, cells = R.box(d, 1 if hrtf else channels, taps, 48000.0)
     out = {"shape": shape, "hrtf": hrtf, "channels": channels, "taps": taps, "N": n, "cells": cells}
@@ -122,8 +140,12 @@ def main(shape, hrtf, want_reference, n_bands=0, filter_taps=0):
         L = 1 if n_bands == 1 else filter_taps
         out["bands"], out["filter_taps"], out["combine_fma"] = n_bands, L, (2 if hrtf else channels) * taps * n_bands * L
         out["plain_call_ms"], out["plain_generator_launches_ms"], _ = timed_calls(ctx, plain_call)
+    if tail is not None:
+        k0, k1 = T.marks(tail, taps, 48000.0)
+        out["diffuse"] = {"mix_ms": diffuse[0], "fade_ms": diffuse[1], "K0": k0, "K1": k1, "cells_for_K1": R.box(d, 1 if hrtf else channels, k1, 48000.0)[1] if k1 else 0}
+        out["bands_call_ms"], out["bands_generator_launches_ms"], _ = timed_calls(ctx, bands_call)
     out["call_ms"], out["generator_launches_ms"], out["bracketed_calls"] = timed_calls(ctx, call)
-    if bands is not None:
+    if bands is not None and tail is None:
         out["generator_minus_B_plain_ms"] = round(out["generator_launches_ms"] - n_bands * out["plain_generator_launches_ms"], 3)
     t0 = time.perf_counter()
     h = call(want_taps=True, load=False)
@@ -138,6 +160,12 @@ def main(shape, hrtf, want_reference, n_bands=0, filter_taps=0):
         print(json.dumps(out))
         return
     t0 = time.perf_counter()
+    if tail is not None:
+        ref = T.brir(d, bands, tail, hrir, N_AZ, N_EL, taps, 48000.0) if hrtf else T.ir(d, bands, tail, channels, taps, 48000.0)
+        out["numpy_reference_s"] = round(time.perf_counter() - t0, 3)
+        out["parity"] = parity(h, ref.h)
+        print(json.dumps(out))
+        return
     if bands is not None:
         ref = BD.brir(d, bands, hrir, N_AZ, N_EL, taps, 48000.0) if hrtf else BD.ir(d, bands, channels, taps, 48000.0)
         out["numpy_reference_s"] = round(time.perf_counter() - t0, 3)
@@ -168,5 +196,10 @@ if __name__ == "__main__":
             i = argv.index(flag)
             valued[flag] = int(argv[i + 1])
             del argv[i : i + 2]
+    diffuse = None
+    if "--diffuse" in argv:
+        i = argv.index("--diffuse")
+        diffuse = (float(argv[i + 1]), float(argv[i + 2]))
+        del argv[i : i + 3]
     args = [a for a in argv if not a.startswith("--")]
-    main(args[0] if args else "default", "--hrtf" in argv, "--reference" in argv, valued.get("--bands", 0), valued.get("--filter-taps", 255))
+    main(args[0] if args else "default", "--hrtf" in argv, "--reference" in argv, valued.get("--bands", 0), valued.get("--filter-taps", 255), diffuse)

@@ -430,6 +430,49 @@ def default_room_ir(room=None, source=(1.0, 0.5, 0.25), listener_origin=(-1.0, 0
     return d
 
 
+# gas_room_plane / gas_room_planes (gas_conv_ir_from_planes)
+ROOM_MAX_PLANES = 16
+ROOM_PLANES_MAX_ORDER = 8
+ROOM_PLANE_DTYPE = np.dtype([("normal", np.float32, (3,)), ("offset", np.float32), ("reflectance", np.float32)])
+ROOM_PLANES_DTYPE = np.dtype([("planes", ROOM_PLANE_DTYPE, (ROOM_MAX_PLANES,)), ("n_planes", np.uint32), ("speed_of_sound", np.float32), ("level", np.float32), ("source", np.float32, (3,)), ("listener", LISTENER_DTYPE), ("ear_spacing", np.float32), ("min_order", np.uint32), ("max_order", np.uint32)])
+assert ROOM_PLANE_DTYPE.itemsize == 20 and ROOM_PLANES_DTYPE.itemsize == 420
+
+
+def planes_from_box(room):
+    """The six walls of a gas_room (one ROOM_DTYPE entry) as ROOM_PLANE_DTYPE [6], in gas_room's wall order -x, +x, -y,
+    +y, -z, +z: inward normals are the basis' columns and their negatives, offsets are worked out in float64 and stored
+    as float32 (exact for an axis-aligned box whose origin and half-extents are short binary fractions)."""
+    r = np.asarray(room, dtype=ROOM_DTYPE).reshape(-1)[0]
+    B, o, h = r["basis"].astype(np.float64), r["origin"].astype(np.float64), r["half_extent"].astype(np.float64)
+    p = np.zeros(6, ROOM_PLANE_DTYPE)
+    for a in range(3):
+        for side, sign in ((0, 1.0), (1, -1.0)):  # the -a wall looks along +a
+            n = sign * B[:, a]
+            p[2 * a + side] = (n, float(n @ o) - h[a], r["reflectance"][2 * a + side])
+    return p
+
+
+def default_room_planes(planes=None, source=(1.0, 1.2, 0.5), listener_origin=(-1.0, 1.5, -0.75), ear_spacing=0.18, min_order=0, max_order=3, speed_of_sound=343.0, level=1.0):
+    """One gas_room_planes ([1]).  planes: ROOM_PLANE_DTYPE [P] (or rows of (normal, offset, reflectance)); by default an
+    attic of seven planes, every one 0.8: a floor at y = 0, walls at x = -+3 and z = -+4, and two roof slopes from the
+    eaves at y = 1.5 to a ridge at y = 3.5 above x = 0.  Identity listener basis, ears 18 cm apart, orders 0 .. 3."""
+    if planes is None:
+        k = 13.0**-0.5
+        planes = [((0, 1, 0), 0.0, 0.8), ((1, 0, 0), -3.0, 0.8), ((-1, 0, 0), -3.0, 0.8), ((0, 0, 1), -4.0, 0.8), ((0, 0, -1), -4.0, 0.8), ((-2 * k, -3 * k, 0), -10.5 * k, 0.8), ((2 * k, -3 * k, 0), -10.5 * k, 0.8)]
+    planes = np.asarray(planes, dtype=ROOM_PLANE_DTYPE).reshape(-1)
+    assert 1 <= len(planes) <= ROOM_MAX_PLANES
+    d = np.zeros(1, ROOM_PLANES_DTYPE)
+    d["planes"][0, : len(planes)] = planes
+    d["n_planes"] = len(planes)
+    d["speed_of_sound"], d["level"] = speed_of_sound, level
+    d["source"] = source
+    d["listener"]["basis"] = np.eye(3, dtype=np.float32)
+    d["listener"]["origin"] = listener_origin
+    d["ear_spacing"] = ear_spacing
+    d["min_order"], d["max_order"] = min_order, max_order
+    return d
+
+
 # gas_room_bands (gas_conv_ir_from_room_bands, gas_conv_ir_from_room_hrtf_bands)
 ROOM_MAX_BANDS = 8
 ROOM_BAND_FILTER_MAX_TAPS = 4095
@@ -537,6 +580,7 @@ EXPORTS = [
     "gas_conv_ir_free",
     "gas_conv_ir_get_info",
     "gas_conv_ir_from_room",
+    "gas_conv_ir_from_planes",
     "gas_conv_ir_from_room_hrtf",
     "gas_conv_ir_from_room_bands",
     "gas_conv_ir_from_room_hrtf_bands",
@@ -655,6 +699,7 @@ def load_library():
     L.gas_conv_ir_free.argtypes = [vp, u32]
     L.gas_conv_ir_get_info.argtypes = [vp, u32, C.POINTER(u32), C.POINTER(u32)]
     L.gas_conv_ir_from_room.argtypes = [vp, vp, u32, u32, vp, C.POINTER(u32)]
+    L.gas_conv_ir_from_planes.argtypes = [vp, vp, u32, u32, vp, C.POINTER(u32)]
     L.gas_conv_ir_from_room_hrtf.argtypes = [vp, vp, vp, u32, u32, u32, u32, vp, C.POINTER(u32)]
     L.gas_conv_ir_from_room_bands.argtypes = [vp, vp, vp, u32, u32, vp, C.POINTER(u32)]
     L.gas_conv_ir_from_room_hrtf_bands.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, vp, C.POINTER(u32)]
@@ -1094,6 +1139,18 @@ class SpatializerContext:
         out = C.c_uint32()
         rc = self.lib.gas_conv_ir_from_room(self.h, _np_ptr(d), int(channels), int(taps), _np_ptr(taps_out) if want_taps else None, C.byref(out) if load else None)
         self._check(rc, "gas_conv_ir_from_room")
+        if load and want_taps:
+            return out.value, taps_out
+        return out.value if load else taps_out
+
+    def conv_ir_from_planes(self, desc, channels, taps, want_taps=False, load=True):
+        """conv_ir_from_room for a room bounded by planes (desc: one ROOM_PLANES_DTYPE entry, see default_room_planes and
+        planes_from_box): image sources over plane sequences up to desc's max_order.  Returns as conv_ir_from_room does."""
+        d = np.ascontiguousarray(np.asarray(desc, dtype=ROOM_PLANES_DTYPE).reshape(-1)[:1])
+        taps_out = np.zeros((int(channels), int(taps)), dtype=np.float32) if want_taps else None
+        out = C.c_uint32()
+        rc = self.lib.gas_conv_ir_from_planes(self.h, _np_ptr(d), int(channels), int(taps), _np_ptr(taps_out) if want_taps else None, C.byref(out) if load else None)
+        self._check(rc, "gas_conv_ir_from_planes")
         if load and want_taps:
             return out.value, taps_out
         return out.value if load else taps_out

@@ -1,6 +1,6 @@
 // gas_ctx_conv.hip -- the bus convolvers of include/gas_amd.h (gas_ctx_reserve_conv, gas_conv_*; k_conv.hip) and the
 // impulse responses built on the device from box rooms (gas_conv_ir_from_room*; k_room_ir.hip, k_room_bands.hip,
-// k_room_tail.hip).
+// k_room_tail.hip) and from rooms bounded by planes (gas_conv_ir_from_planes; k_room_planes.hip).
 #include "gas_ctx_priv.h"
 
 extern "C" {
@@ -462,6 +462,23 @@ static bool room_ir_desc_ok(const gas_room_ir &d, bool ears) {
 	return ok;
 }
 
+// What gas_conv_ir_from_planes refuses in a descriptor's plain fields; a normal's length and where the points lie are the
+// plan's to refuse.  Planes beyond n_planes and the listener's fields other than origin and basis column 0 are not read.
+static bool room_planes_desc_ok(const gas_room_planes &d) {
+	if (d.n_planes == 0 || d.n_planes > GAS_ROOM_MAX_PLANES || d.max_order == 0 || d.max_order > GAS_ROOM_PLANES_MAX_ORDER || d.min_order > d.max_order) {
+		return false;
+	}
+	bool ok = d.speed_of_sound > 0.0f && std::isfinite(d.speed_of_sound) && d.level >= 0.0f && std::isfinite(d.level) && d.ear_spacing >= 0.0f && std::isfinite(d.ear_spacing);
+	for (uint32_t j = 0; j < d.n_planes; j++) {
+		const gas_room_plane &w = d.planes[j];
+		ok = ok && std::isfinite(w.normal[0]) && std::isfinite(w.normal[1]) && std::isfinite(w.normal[2]) && std::isfinite(w.offset) && w.reflectance >= 0.0f && w.reflectance <= 1.0f;
+	}
+	for (int a = 0; a < 3; a++) {
+		ok = ok && std::isfinite(d.source[a]) && std::isfinite(d.listener.origin[a]) && std::isfinite(d.listener.basis[a][0]);
+	}
+	return ok;
+}
+
 // The HRIR set of gas_conv_ir_from_room_hrtf, as the caller passed it.
 struct RoomIrSet {
 	const float *hrir;
@@ -486,6 +503,46 @@ static bool room_bands_ok(const gas_room_bands &b, float rate) {
 		ok = ok && b.air_db_per_m[i] >= 0.0f && std::isfinite(b.air_db_per_m[i]);
 	}
 	return ok;
+}
+
+// The common end of every generated IR: d_ir [channels][taps] is being written in the context's stream order.  out_ir:
+// it is registered (which waits for the stream); out_taps: it is copied back.  At least one of the two is given.
+static int conv_ir_deliver(gas_ctx *c, const float *d_ir, uint32_t channels, uint32_t taps, float *out_taps, uint32_t *out_ir) {
+	const size_t n = (size_t)channels * taps;
+	if (out_ir) { // waits for the stream
+		uint32_t id = 0;
+		GAS_TRY(conv_ir_register(c, d_ir, channels, taps, &id));
+		if (out_taps) {
+			const hipError_t e = hipMemcpy(out_taps, d_ir, n * sizeof(float), hipMemcpyDeviceToHost);
+			if (e != hipSuccess) { // no IR and nothing reported: the caller's out_ir keeps its value
+				c->mem.drop(c->conv.irs[id].H);
+				c->conv.irs[id] = ConvIr{};
+				GAS_HIP(c, e);
+			}
+		}
+		*out_ir = id;
+		return GAS_OK;
+	}
+	GAS_HIP(c, hipStreamSynchronize(c->stream)); // before anything reaches out_taps: a failed kernel writes nothing there
+	GAS_HIP(c, hipMemcpy(out_taps, d_ir, n * sizeof(float), hipMemcpyDeviceToHost));
+	return GAS_OK;
+}
+
+// A generator's launches inside the bracket of gas_profile_enable, where they count as a callback's dominant launch.
+// (A template has C++ linkage, whatever surrounds it.)
+extern "C++" {
+template <class Launches>
+static int conv_ir_bracketed(gas_ctx *c, Launches launches) {
+	const bool timed = c->prof.room();
+	if (timed) {
+		GAS_HIP(c, c->prof.begin(c->stream));
+	}
+	GAS_TRY(launches());
+	if (timed) {
+		GAS_HIP(c, c->prof.end(c->stream));
+	}
+	return GAS_OK;
+}
 }
 
 // The common body of the box-room calls once everything is validated and the plan is made: tables, temporaries,
@@ -557,43 +614,23 @@ static int conv_ir_from_plan(gas_ctx *c, const gas_room_ir &desc, const gas_room
 		GAS_HIP(c, tmp.alloc(d_hrir, floats));
 		GAS_HIP(c, hipMemcpy(d_hrir, set->hrir, floats * sizeof(float), hipMemcpyHostToDevice));
 	}
-	const bool timed = c->prof.room(); // gas_profile_enable: the generator's launches count as a dominant launch
-	if (timed) {
-		GAS_HIP(c, c->prof.begin(c->stream));
-	}
-	for (uint32_t b = 0; b < passes && n_lat != 0; b++) { // in stream order: a band's scaled taps in d_ir (n_lat <= n of them) are overwritten by the next writer
-		if (set) {
-			GAS_HIP(c, gas_launch_room_ir_hrtf(c->stream, plan, desc, d_tables + per_pass * b, d_hrir, set->n_az, set->n_el, set->taps, d_lat + n_lat * b, d_ir));
-		} else {
-			GAS_HIP(c, gas_launch_room_ir(c->stream, plan, d_tables + per_pass * b, d_lat + n_lat * b, d_ir));
-		}
-	}
-	if (tail) {
-		GAS_HIP(c, gas_launch_room_tail(c->stream, *tail, d_lat, d_acc));
-	}
-	if (bands) {
-		GAS_HIP(c, gas_launch_room_bands_combine(c->stream, bp, d_acc, d_filt, d_ir));
-	}
-	if (timed) {
-		GAS_HIP(c, c->prof.end(c->stream));
-	}
-	if (out_ir) { // waits for the stream
-		uint32_t id = 0;
-		GAS_TRY(conv_ir_register(c, d_ir, channels, taps, &id));
-		if (out_taps) {
-			const hipError_t e = hipMemcpy(out_taps, d_ir, n * sizeof(float), hipMemcpyDeviceToHost);
-			if (e != hipSuccess) { // no IR and nothing reported: the caller's out_ir keeps its value
-				c->mem.drop(c->conv.irs[id].H);
-				c->conv.irs[id] = ConvIr{};
-				GAS_HIP(c, e);
+	GAS_TRY(conv_ir_bracketed(c, [&]() -> int {
+		for (uint32_t b = 0; b < passes && n_lat != 0; b++) { // in stream order: a band's scaled taps in d_ir (n_lat <= n of them) are overwritten by the next writer
+			if (set) {
+				GAS_HIP(c, gas_launch_room_ir_hrtf(c->stream, plan, desc, d_tables + per_pass * b, d_hrir, set->n_az, set->n_el, set->taps, d_lat + n_lat * b, d_ir));
+			} else {
+				GAS_HIP(c, gas_launch_room_ir(c->stream, plan, d_tables + per_pass * b, d_lat + n_lat * b, d_ir));
 			}
 		}
-		*out_ir = id;
+		if (tail) {
+			GAS_HIP(c, gas_launch_room_tail(c->stream, *tail, d_lat, d_acc));
+		}
+		if (bands) {
+			GAS_HIP(c, gas_launch_room_bands_combine(c->stream, bp, d_acc, d_filt, d_ir));
+		}
 		return GAS_OK;
-	}
-	GAS_HIP(c, hipStreamSynchronize(c->stream)); // before anything reaches out_taps: a failed kernel writes nothing there
-	GAS_HIP(c, hipMemcpy(out_taps, d_ir, n * sizeof(float), hipMemcpyDeviceToHost));
-	return GAS_OK;
+	}));
+	return conv_ir_deliver(c, d_ir, channels, taps, out_taps, out_ir);
 }
 
 // Which of the box-room calls of one name this is: it decides which of `bands` and `tail` must be there.
@@ -695,6 +732,39 @@ int gas_conv_ir_from_room_diffuse(gas_ctx *c, const gas_room_ir *desc, const gas
 
 int gas_conv_ir_from_room_hrtf_diffuse(gas_ctx *c, const gas_room_ir *desc, const gas_room_bands *bands, const gas_room_tail *tail, const float *hrir, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps, uint32_t taps, float *out_taps, uint32_t *out_ir) {
 	return conv_ir_from_room_hrtf_any(c, desc, ROOM_DIFFUSE, bands, tail, hrir, n_az, n_el, hrir_taps, taps, out_taps, out_ir);
+}
+
+// The planes road has no tables: the plan carries the planes, so its temporaries are the sums and the taps.  The
+// bracket and the end are the box road's.
+int gas_conv_ir_from_planes(gas_ctx *c, const gas_room_planes *desc, uint32_t channels, uint32_t taps, float *out_taps, uint32_t *out_ir) {
+	if (!c || !desc || (!out_taps && !out_ir) || (channels != 1 && channels != 2) || taps == 0) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (out_ir && c->conv.count == 0) {
+		return GAS_ERR_UNSUPPORTED_CHAIN;
+	}
+	if (taps > (out_ir ? c->conv.max_taps : (uint32_t)GAS_CONV_MAX_IR_TAPS)) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	gas_room_planes_plan plan;
+	if (!room_planes_desc_ok(*desc) || !gas_room_planes_make_plan(*desc, channels, taps, c->cfg.mix_rate, plan)) {
+		return GAS_ERR_INVALID_ARGUMENT;
+	}
+	if (out_ir) { // the pure generator leaves queued callbacks where they are: it touches nothing of theirs
+		GAS_TRY(flush_deferred(c));
+	}
+	GAS_HIP(c, hipSetDevice(c->cfg.device));
+	const size_t n = (size_t)channels * taps;
+	Mem tmp; // frees the buffers on every way out
+	long long *d_acc = nullptr;
+	float *d_ir = nullptr;
+	GAS_HIP(c, tmp.alloc(d_acc, n));
+	GAS_HIP(c, tmp.alloc(d_ir, n));
+	GAS_TRY(conv_ir_bracketed(c, [&]() -> int {
+		GAS_HIP(c, gas_launch_room_planes(c->stream, plan, d_acc, d_ir));
+		return GAS_OK;
+	}));
+	return conv_ir_deliver(c, d_ir, channels, taps, out_taps, out_ir);
 }
 
 } // extern "C"

@@ -625,6 +625,30 @@ bool gas_room_ir_make_plan(const gas_room_ir &desc, uint32_t channels, uint32_t 
 size_t gas_room_ir_table_doubles(const gas_room_ir_plan &plan);
 void gas_room_ir_fill_tables(const gas_room_ir &desc, const gas_room_ir_plan &plan, double *host_tables);
 hipError_t gas_launch_room_ir(hipStream_t stream, const gas_room_ir_plan &plan, const double *d_tables, long long *d_acc, float *d_out);
+// step 6 alone, for every generator that leaves int64 sums of shares: d_out[i] = (float)(level d_acc[i] 2^-32), i < n
+hipError_t gas_launch_room_ir_scale(hipStream_t stream, const long long *d_acc, uint32_t n, double level, float *d_out);
+// k_room_planes.hip: gas_conv_ir_from_planes.  The plan is step 1 of the rule (normalised planes, source, receivers, d0)
+// and the layout of the candidates, made on the host in float64 and passed to the kernel by value.  A candidate's flat
+// index is first[K] + r, K its order and r its digits, most significant first: the first base P, the later ones base
+// P - 1 and mapped past the plane before them.  gas_room_planes_make_plan is false for what the geometry refuses: a
+// normal's length outside [0.999, 1.001], the source or a receiver not strictly inside every half-space, d0 < 1e-3, more
+// than GAS_ROOM_PLANES_MAX_CANDIDATES sequences (the descriptor's plain fields are the caller's to check first).
+// gas_launch_room_planes zeroes d_acc [channels][taps], accumulates, and writes d_out [channels][taps] f32, all in
+// stream order.
+#define GAS_ROOM_PLANES_MAX_CANDIDATES (1u << 28)
+struct gas_room_planes_plan {
+	double n[GAS_ROOM_MAX_PLANES][3], d[GAS_ROOM_MAX_PLANES], refl[GAS_ROOM_MAX_PLANES];
+	double s[3], e[2][3]; // source, receivers (both the listener for one channel)
+	double d0, c, rate, level;
+	double far2; // (c (taps + 1) / rate + d0)^2: an image further than this from every receiver reaches no tap, nor does one made from it
+	uint32_t first[GAS_ROOM_PLANES_MAX_ORDER + 2]; // [K], lo <= K <= hi + 1: first[lo] = 0, first[hi + 1] = candidates
+	uint32_t pw[GAS_ROOM_PLANES_MAX_ORDER]; // (P - 1)^k
+	uint32_t P, lo, hi, candidates; // orders lo .. hi, lo = max(min_order, 1)
+	uint32_t direct; // min_order == 0: candidate 0's lane adds the direct sound as well
+	uint32_t channels, taps;
+};
+bool gas_room_planes_make_plan(const gas_room_planes &desc, uint32_t channels, uint32_t taps, float rate, gas_room_planes_plan &plan);
+hipError_t gas_launch_room_planes(hipStream_t stream, const gas_room_planes_plan &plan, long long *d_acc, float *d_out);
 // gas_conv_ir_from_room_hrtf: the plan is made with channels = 1 (one receiver, the listener); d_acc and d_out are
 // [2][taps] all the same, one row per ear.  d_hrir is the set as the caller passed it, f32 [n_az * n_el][2][hrir_taps];
 // the two bases of `desc` travel to the kernel widened, by value.

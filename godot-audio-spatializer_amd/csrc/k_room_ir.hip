@@ -245,6 +245,11 @@ bool gas_room_ir_make_plan(const gas_room_ir &d, uint32_t channels, uint32_t tap
 	return true;
 }
 
+hipError_t gas_launch_room_ir_scale(hipStream_t stream, const long long *d_acc, uint32_t n, double level, float *d_out) {
+	hipLaunchKernelGGL(k_room_ir_scale, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_acc, n, level, d_out);
+	return hipGetLastError();
+}
+
 size_t gas_room_ir_table_doubles(const gas_room_ir_plan &p) {
 	return (size_t)(2u * p.N[0] + 1u) + (2u * p.N[1] + 1u) + (2u * p.N[2] + 1u);
 }
@@ -273,8 +278,7 @@ hipError_t gas_launch_room_ir(hipStream_t stream, const gas_room_ir_plan &p, con
 	if (e != hipSuccess) {
 		return e;
 	}
-	hipLaunchKernelGGL(k_room_ir_scale, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_acc, n, p.level, d_out);
-	return hipGetLastError();
+	return gas_launch_room_ir_scale(stream, d_acc, n, p.level, d_out);
 }
 
 hipError_t gas_launch_room_ir_hrtf(hipStream_t stream, const gas_room_ir_plan &p, const gas_room_ir &d, const double *d_tables, const float *d_hrir, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps, long long *d_acc, float *d_out) {
@@ -295,6 +299,5 @@ hipError_t gas_launch_room_ir_hrtf(hipStream_t stream, const gas_room_ir_plan &p
 	if (e != hipSuccess) {
 		return e;
 	}
-	hipLaunchKernelGGL(k_room_ir_scale, dim3((n + 255u) / 256u), dim3(256), 0, stream, d_acc, n, p.level, d_out);
-	return hipGetLastError();
+	return gas_launch_room_ir_scale(stream, d_acc, n, p.level, d_out);
 }

@@ -988,7 +988,8 @@ int gas_calc_early_reflections(gas_ctx *ctx, const gas_room *rooms, uint32_t n_r
  * failure, with no IR loaded.
  * Out of scope: frequency-dependent absorption, air absorption, jitter against flutter echoes, a direction-dependent
  * (HRTF) receiver, four-channel results, rooms that are not boxes, the host layer, godot_module/ and gas_multi.
- * (The HRTF receiver is a call of its own, gas_conv_ir_from_room_hrtf, declared below this one.) */
+ * (The HRTF receiver is a call of its own, gas_conv_ir_from_room_hrtf, and so are rooms that are not boxes,
+ * gas_conv_ir_from_planes; both are declared below this one.) */
 typedef struct gas_room_ir { /* NEW; 184 bytes */
 	gas_room room; /* as for gas_calc_early_reflections; room.max_order is NOT read here */
 	float source[3]; /* global position of the emitter that stands for the bus */
@@ -998,6 +999,78 @@ typedef struct gas_room_ir { /* NEW; 184 bytes */
 	uint32_t max_order; /* images with |m|_1 > max_order are left out; 0 = no limit but the IR's length */
 } gas_room_ir;
 int gas_conv_ir_from_room(gas_ctx *ctx, const gas_room_ir *desc, uint32_t channels /* 1 or 2 */, uint32_t taps, float *out_taps /* host [channels][taps], may be NULL */, uint32_t *out_ir /* may be NULL */);
+
+/* NEW: gas_conv_ir_from_planes -- the image-source method for a room that is no box: up to GAS_ROOM_MAX_PLANES
+ * half-spaces, each with a reflectance.  An attic, a corridor with a slanted wall, a hexagonal hall; the planes need not
+ * close a room, so a lone ground plane or two facing walls are rooms as well.  Levels and times are
+ * gas_conv_ir_from_room's: tap 0 is the arrival of the direct sound and a reflection's gain is relative to it.  The method
+ * walks plane sequences, P (P - 1)^(K - 1) of them at order K, so it is one for low orders -- the image part in front of
+ * a diffuse tail -- and max_order is required.
+ *
+ * The rule.  Inputs are float32 and are widened to float64; everything up to the final conversion is float64 with no
+ * fused multiply-adds.  dot(n, x) = (n_x x_x + n_y x_y) + n_z x_z.  P = n_planes, c = speed_of_sound, rate = the context's
+ * mix_rate.
+ *  1. Geometry.  n_j = the widened normal divided, per component, by its length sqrt((x x + y y) + z z); d_j = offset.
+ *     s = source, l = listener.origin, r = listener.basis column 0.  d0 = |s - l| = sqrt((dx dx + dy dy) + dz dz).
+ *     Receivers: one channel e_0 = l; two channels e_0 = l - (ear_spacing / 2) r, e_1 = l + (ear_spacing / 2) r.
+ *  2. Candidates.  The plane sequences q_1 .. q_K with q_i != q_{i+1}, for max(min_order, 1) <= K <= max_order:
+ *     P (P - 1)^(K - 1) per order (for P = 1 only K = 1).  For min_order == 0 there is also the direct sound: image = s,
+ *     R = 1, nothing to validate.
+ *  3. Images.  I_0 = s.  For i = 1 .. K: t = dot(n_{q_i}, I_{i-1}) - d_{q_i}; the sequence is void unless t > 0;
+ *     I_i = I_{i-1} - (2 t) n_{q_i}, per component.  R is the running product of the planes' reflectances in sequence
+ *     order.
+ *  4. Validity, per receiver e.  p = e.  For i = K down to 1: a = dot(n_{q_i}, p) - d_{q_i} and
+ *     b = dot(n_{q_i}, I_i) - d_{q_i}; the path is invalid unless a > 0; u = a / (a - b); hit = p + u (I_i - p), per
+ *     component; the path is invalid unless dot(n_j, hit) - d_j >= 0 for every j != q_i; then p = hit.  The test is
+ *     closed: a path through an exact edge of the room may pass for both orders of the two planes and count twice.
+ *  5. Taps, for a valid path: dist = |I_K - e|, as d0 is computed.  Then steps 4 to 6 of gas_conv_ir_from_room, unchanged:
+ *     v = R d0 / max(dist, d0); pos = ((dist - d0) / c) rate; k = floor(pos), f = pos - k; tap k receives v (1 - f) and
+ *     tap k + 1 receives v f, a tap index outside [0, taps) dropped on its own; each share is quantised to
+ *     llrint(share 2^32) and summed into one int64 per channel and tap, so no order of arrival changes a bit; and
+ *     h_e[k] = (float)((double)level (double)acc_e[k] 2^-32).
+ *
+ * Consequences.  A box given as its six planes has the images of gas_conv_ir_from_room with that max_order (same points,
+ * reached by another road of float64 operations: the two agree within the last float32 bit, not by contract to the bit).
+ * Swapping source and listener gives the same one-channel taps within that.  Two calls give the same bits.
+ *
+ * out_ir, out_taps, the pure generator (out_ir == NULL: no reserve needed, no context state touched), the main thread,
+ * the flush of deferred and recorded callbacks when an IR is loaded, the temporaries (8 channels taps bytes of sums,
+ * 4 channels taps of taps; the planes travel as a kernel argument) freed on every way out, and the profiling bracket
+ * (zeroing, sums, scaling; not the transform) are as for gas_conv_ir_from_room.
+ * Refusals, each with nothing loaded and nothing written.  GAS_ERR_INVALID_ARGUMENT: a NULL ctx or desc; out_taps and
+ * out_ir both NULL; channels other than 1 or 2; taps == 0; taps > max_ir_taps of the reserve when out_ir != NULL, or
+ * taps > 2^20 for the pure generator; n_planes 0 or above GAS_ROOM_MAX_PLANES; max_order 0 or above
+ * GAS_ROOM_PLANES_MAX_ORDER; min_order > max_order; a value that is read and is not finite (planes beyond n_planes and
+ * listener fields other than origin and basis column 0 are not read); a normal whose length is outside [0.999, 1.001]; a
+ * reflectance outside [0, 1]; a speed_of_sound that is not positive; a negative level or ear_spacing (ear_spacing is
+ * checked for one channel too); the source or a receiver with dot(n_j, x) - d_j <= 0 for some j; d0 < 1e-3; more than
+ * 2^28 candidate sequences over all orders (the direct sound is not counted) -- computed from P and the orders before
+ * anything is launched.  GAS_ERR_UNSUPPORTED_CHAIN: out_ir != NULL with nothing reserved.  GAS_ERR_DEVICE: a HIP failure,
+ * with no IR loaded.
+ * Out of scope: non-convex rooms and occlusion (every plane bounds the whole room); per-band reflectances and air
+ * absorption for planes; an HRTF receiver (the spreading phase of gas_conv_ir_from_room_hrtf's kernel would serve it); a
+ * diffuse tail, which needs the room's volume and face areas from the planes -- until it exists a caller adds the
+ * out_taps of a box's gas_conv_ir_from_room_diffuse on the host; early-reflection taps from planes; a per-order frontier
+ * with compaction in place of the enumeration of every sequence; the host layer, godot_module/ and gas_multi. */
+#define GAS_ROOM_MAX_PLANES 16
+#define GAS_ROOM_PLANES_MAX_ORDER 8
+typedef struct gas_room_plane { /* NEW; 20 bytes */
+	float normal[3]; /* unit length, pointing into the room */
+	float offset; /* inside: dot(normal, x) - offset > 0 */
+	float reflectance; /* amplitude factor, 0 .. 1 */
+} gas_room_plane;
+typedef struct gas_room_planes { /* NEW; 420 bytes */
+	gas_room_plane planes[GAS_ROOM_MAX_PLANES]; /* inside: dot(normal, x) - offset > 0, global coordinates, inward unit normals */
+	uint32_t n_planes; /* 1 .. GAS_ROOM_MAX_PLANES; the planes need not bound a closed room */
+	float speed_of_sound; /* > 0 */
+	float level; /* >= 0, as gas_room.level */
+	float source[3]; /* global position of the emitter that stands for the bus */
+	gas_listener listener; /* origin and basis column 0 are read, as in gas_room_ir */
+	float ear_spacing; /* as in gas_room_ir */
+	uint32_t min_order; /* 0 includes the direct sound */
+	uint32_t max_order; /* 1 .. GAS_ROOM_PLANES_MAX_ORDER, required */
+} gas_room_planes;
+int gas_conv_ir_from_planes(gas_ctx *ctx, const gas_room_planes *desc, uint32_t channels /* 1 or 2 */, uint32_t taps, float *out_taps /* host [channels][taps], may be NULL */, uint32_t *out_ir /* may be NULL */);
 
 /* NEW: gas_conv_ir_from_room_hrtf -- the same box room heard binaurally: every image arrives through the HRIR pair of its
  * direction, so the tail carries the pinna and head cues the dry GAS_FX_HRTF sources have, from the same HRIR set.  The
@@ -1089,8 +1162,8 @@ int gas_conv_ir_from_room_hrtf(gas_ctx *ctx, const gas_room_ir *desc, const floa
  * B - 1 for crossovers) are neither read nor checked.  GAS_ERR_UNSUPPORTED_CHAIN and GAS_ERR_DEVICE: as for the plain
  * calls.
  * Out of scope: jitter against flutter echoes (a diffuse late tail is a call of its own, gas_conv_ir_from_room_diffuse,
- * declared below), minimum-phase band filters, a level per band, rooms that are not boxes, bands for
- * gas_calc_early_reflections' taps, the host layer, godot_module/ and gas_multi. */
+ * declared below), minimum-phase band filters, a level per band, rooms that are not boxes
+ * (gas_conv_ir_from_planes, above, makes their image part, broadband), bands for gas_calc_early_reflections' taps, the host layer, godot_module/ and gas_multi. */
 #define GAS_ROOM_MAX_BANDS 8
 #define GAS_ROOM_BAND_FILTER_MAX_TAPS 4095
 typedef struct gas_room_bands { /* NEW; 264 bytes */

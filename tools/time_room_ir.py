@@ -14,6 +14,12 @@
                                             image sources for MIX_MS after the direct sound, FADE_MS of cross-fade, the
                                             diffuse tail behind them; without --bands one broadband band
 
+  python tools/time_room_ir.py --planes     gas_conv_ir_from_planes for four rooms, 8192 taps, two channels: a box as six
+                                            planes at max_order 4 and 8 next to gas_conv_ir_from_room of the same box and
+                                            orders, an attic of 7 planes at order 6, a room of 12 planes at order 5; one
+                                            JSON line per room with the times as below, the reference's candidate, void
+                                            and valid counts, the share of sequences a lane may leave early, and parity
+
 Prints one JSON line: the wall clock of a whole loading call (tables, allocations, launches, transform, synchronise) as
 the median of STEPS calls, the span of the generator's launches from the library's HIP-event bracket
 (gas_profile_enable; zeroing, k_room_ir or k_room_ir_hrtf and the scaling kernel, not the transform), the numpy
@@ -41,6 +47,7 @@ from godot_audio_spatializer_amd import synth  # noqa: E402
 import room_bands_ref as BD  # noqa: E402
 import room_brir_ref as BR  # noqa: E402
 import room_ir_ref as R  # noqa: E402
+import room_planes_ref as PL  # noqa: E402
 import room_tail_ref as T  # noqa: E402
 
 K = gas.capi
@@ -102,6 +109,47 @@ def timed_calls(ctx, call):
     p = ctx.profile_read()
     ctx.profile_enable(0)
     return {"median": round(float(np.median(ts)), 3), "min": round(min(ts), 3), "max": round(max(ts), 3)}, round(p["kernel_ms"] / max(p["launches"], 1), 3), p["launches"]
+
+
+def twelve_planes():
+    """A floor, a ceiling at 3.2 m and ten walls at uneven angles and distances of 3.5 to 4.5 m."""
+    rng = np.random.default_rng(1)
+    rows = [((0, 1, 0), 0.0, 0.8), ((0, -1, 0), -3.2, 0.8)]
+    for i in range(10):
+        th = 2 * np.pi * (i + rng.uniform(-0.2, 0.2)) / 10
+        rows.append(((-np.cos(th), 0.0, -np.sin(th)), -rng.uniform(3.5, 4.5), 0.7 + 0.02 * i))
+    return rows
+
+
+def planes_main():
+    channels, taps = 2, 8192
+    box = K.default_rooms(half_extent=(2.5, 2.0, 1.5), reflectance=(0.9, 0.85, 0.8, 0.75, 0.7, 0.95))
+    src, lis = (1.0, 0.5, 0.25), (-1.0, 0.25, -0.5)
+    attic_src, attic_lis = (1.1, 1.2, 0.5), (-0.9, 1.45, -0.8)
+    rooms = [
+        ("box as 6 planes, max_order 4", K.default_room_planes(K.planes_from_box(box), src, lis, max_order=4), K.default_room_ir(box, src, lis, max_order=4)),
+        ("box as 6 planes, max_order 8", K.default_room_planes(K.planes_from_box(box), src, lis, max_order=8), K.default_room_ir(box, src, lis, max_order=8)),
+        ("attic of 7 planes, max_order 6", K.default_room_planes(None, attic_src, attic_lis, max_order=6), None),
+        ("12 planes, max_order 5", PL.describe(twelve_planes(), attic_src, attic_lis, ear_spacing=0.18, max_order=5), None),
+    ]
+    ctx = gas.SpatializerContext(max_sources=4, frames=512)
+    ctx.reserve_conv(1, taps)
+    for name, d, box_desc in rooms:
+        out = {"room": name, "channels": channels, "taps": taps}
+        out["call_ms"], out["generator_launches_ms"], out["bracketed_calls"] = timed_calls(ctx, lambda: ctx.conv_ir_from_planes(d, channels, taps))
+        h = ctx.conv_ir_from_planes(d, channels, taps, want_taps=True, load=False)
+        if box_desc is not None:
+            out["box_call_ms"], out["box_generator_launches_ms"], _ = timed_calls(ctx, lambda: ctx.conv_ir_from_room(box_desc, channels, taps))
+            out["parity_with_the_box_call"] = parity(h, ctx.conv_ir_from_room(box_desc, channels, taps, want_taps=True, load=False))
+        t0 = time.perf_counter()
+        ref = PL.ir(d, channels, taps, 48000.0)
+        out["numpy_reference_s"] = round(time.perf_counter() - t0, 3)
+        out["candidates"], out["void"], out["valid"] = ref.candidates, ref.void, ref.valid
+        out["left_early"], out["left_early_share"] = ref.left_early, round(ref.left_early / max(ref.candidates, 1), 4)
+        out["margin_m"], out["smallest_v"] = ref.margin, ref.v_min
+        out["parity"] = parity(h, ref.h)
+        print(json.dumps(out), flush=True)
+    ctx.close()
 
 
 def main(shape, hrtf, want_reference, n_bands=0, filter_taps=0, diffuse=None):
@@ -190,6 +238,9 @@ def main(shape, hrtf, want_reference, n_bands=0, filter_taps=0, diffuse=None):
 
 if __name__ == "__main__":
     argv = sys.argv[1:]
+    if "--planes" in argv:
+        planes_main()
+        sys.exit(0)
     valued = {}
     for flag in ("--bands", "--filter-taps"):
         if flag in argv:

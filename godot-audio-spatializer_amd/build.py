@@ -10,7 +10,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libgas_amd.so")
 SOURCES = ["gas_ctx.hip", "gas_ctx_run.hip", "gas_ctx_fx.hip", "gas_ctx_conv.hip", "gas_ctx_streams.hip", "gas_ctx_calc.hip", "gas_ctx_hrtf_profile.hip", "k_biquad_mix.hip", "k_biquad_pipe.hip", "k_shelf_scan.hip", "k_hrtf_ols.hip", "k_hrtf_uni.hip", "k_hrtf_multi.hip", "k_misc.hip", "k_calc_spatialization.hip", "k_calc_er.hip", "k_conv.hip", "k_room_ir.hip", "k_room_bands.hip", "k_room_tail.hip", "k_room_planes.hip","k_sample_sources.hip", "k_sample_adpcm.hip", "k_sample_qoa.hip", "k_fx_dyn.hip", "k_fx_line.hip", "k_fx_eq.hip", "k_fx_mod.hip", "k_fx_stereo.hip", "k_fx_filter.hip", "gas_multi.hip", "../host/batched_spatializer_host.cpp"]
-HEADERS = [os.path.join(CSRC, "gas_internal.h"), os.path.join(CSRC, "gas_device.h"), os.path.join(CSRC, "gas_hrtf_wave.h"), os.path.join(CSRC, "gas_sample_row.h"), os.path.join(CSRC, "gas_qoa.h"), os.path.join(CSRC, "gas_owned.h"), os.path.join(CSRC, "gas_ctx_priv.h"), os.path.join(CSRC, "gas_switches.h"), os.path.join(CSRC, "gas_biquad.h"), os.path.join(CSRC, "gas_biquad_gate.h"), os.path.join(CSRC, "gas_fx_dyn_check.h"), os.path.join(CSRC, "gas_fx_line_check.h"), os.path.join(CSRC, "gas_fx_eq_check.h"), os.path.join(CSRC, "gas_fx_mod_check.h"), os.path.join(CSRC, "gas_fx_stereo_check.h"), os.path.join(CSRC, "gas_fx_filter_check.h"), os.path.join(HERE, "..", "include", "gas_amd.h"), os.path.join(HERE, "..", "include", "gas_amd_host.h")]
+HEADERS = [os.path.join(CSRC, "gas_internal.h"), os.path.join(CSRC, "gas_device.h"), os.path.join(CSRC, "gas_hrtf_wave.h"), os.path.join(CSRC, "gas_sample_row.h"), os.path.join(CSRC, "gas_qoa.h"), os.path.join(CSRC, "gas_owned.h"), os.path.join(CSRC, "gas_ctx_priv.h"), os.path.join(CSRC, "gas_switches.h"), os.path.join(CSRC, "gas_biquad.h"), os.path.join(CSRC, "gas_biquad_gate.h"), os.path.join(CSRC, "gas_fx_dyn_check.h"), os.path.join(CSRC, "gas_fx_line_check.h"), os.path.join(CSRC, "gas_fx_eq_check.h"), os.path.join(CSRC, "gas_fx_mod_check.h"), os.path.join(CSRC, "gas_fx_stereo_check.h"), os.path.join(CSRC, "gas_fx_filter_check.h"), os.path.join(CSRC, "gas_room_taps.h"), os.path.join(HERE, "..", "include", "gas_amd.h"), os.path.join(HERE, "..", "include", "gas_amd_host.h")]
 # -fno-slp-vectorize: hipcc's SLP pass packs the FFT butterflies into v_pk_{add,mul,fma}_f32; on gfx950 that
 # costs VGPRs (236 vs 188) and 15 % of k_hrtf_ols' time (measured, profiles/r01 notes), so it stays off.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-fno-slp-vectorize"]

@@ -1129,105 +1129,63 @@ class SpatializerContext:
         self._check(self.lib.gas_conv_ir_get_info(self.h, int(ir), C.byref(ch), C.byref(taps)), "gas_conv_ir_get_info")
         return ch.value, taps.value
 
+    def _conv_ir_generate(self, fn_name, structs, hrir, n_az, n_el, channels, taps, want_taps, load):
+        """The common body of the conv_ir_from_* methods.  structs: (value, dtype) pairs in call order, each narrowed to
+        one entry.  hrir None: the library's function takes `channels`; otherwise it takes the HRIR set in their place,
+        writes two channels, and `channels` is not read."""
+        args = [_np_ptr(np.ascontiguousarray(np.asarray(v, dtype=dt).reshape(-1)[:1])) for v, dt in structs]
+        if hrir is None:
+            args.append(int(channels))
+        else:
+            h = np.ascontiguousarray(np.asarray(hrir, dtype=np.float32))
+            assert h.ndim == 3 and h.shape[0] == int(n_az) * int(n_el) and h.shape[1] == 2, h.shape
+            args += [_np_ptr(h), int(n_az), int(n_el), h.shape[2]]
+        taps_out = np.zeros((int(channels) if hrir is None else 2, int(taps)), dtype=np.float32) if want_taps else None
+        out = C.c_uint32()
+        rc = getattr(self.lib, fn_name)(self.h, *args, int(taps), _np_ptr(taps_out) if want_taps else None, C.byref(out) if load else None)
+        self._check(rc, fn_name)
+        if load and want_taps:
+            return out.value, taps_out
+        return out.value if load else taps_out
+
     def conv_ir_from_room(self, desc, channels, taps, want_taps=False, load=True):
         """An impulse response built on the device from a box room (desc: one ROOM_IR_DTYPE entry).  load: it becomes an
         IR of this context (a reserve is needed); want_taps: the float32 taps [channels][taps] are read back.  Returns
         the IR id, the taps, or (id, taps) when both are asked for; load=False and want_taps=False is refused by the
         library, like every other bad descriptor."""
-        d = np.ascontiguousarray(np.asarray(desc, dtype=ROOM_IR_DTYPE).reshape(-1)[:1])
-        taps_out = np.zeros((int(channels), int(taps)), dtype=np.float32) if want_taps else None
-        out = C.c_uint32()
-        rc = self.lib.gas_conv_ir_from_room(self.h, _np_ptr(d), int(channels), int(taps), _np_ptr(taps_out) if want_taps else None, C.byref(out) if load else None)
-        self._check(rc, "gas_conv_ir_from_room")
-        if load and want_taps:
-            return out.value, taps_out
-        return out.value if load else taps_out
+        return self._conv_ir_generate("gas_conv_ir_from_room", [(desc, ROOM_IR_DTYPE)], None, 0, 0, channels, taps, want_taps, load)
 
     def conv_ir_from_planes(self, desc, channels, taps, want_taps=False, load=True):
         """conv_ir_from_room for a room bounded by planes (desc: one ROOM_PLANES_DTYPE entry, see default_room_planes and
         planes_from_box): image sources over plane sequences up to desc's max_order.  Returns as conv_ir_from_room does."""
-        d = np.ascontiguousarray(np.asarray(desc, dtype=ROOM_PLANES_DTYPE).reshape(-1)[:1])
-        taps_out = np.zeros((int(channels), int(taps)), dtype=np.float32) if want_taps else None
-        out = C.c_uint32()
-        rc = self.lib.gas_conv_ir_from_planes(self.h, _np_ptr(d), int(channels), int(taps), _np_ptr(taps_out) if want_taps else None, C.byref(out) if load else None)
-        self._check(rc, "gas_conv_ir_from_planes")
-        if load and want_taps:
-            return out.value, taps_out
-        return out.value if load else taps_out
+        return self._conv_ir_generate("gas_conv_ir_from_planes", [(desc, ROOM_PLANES_DTYPE)], None, 0, 0, channels, taps, want_taps, load)
 
     def conv_ir_from_room_hrtf(self, desc, hrir, n_az, n_el, taps, want_taps=False, load=True):
         """conv_ir_from_room heard through an HRIR set: hrir float32 [n_az * n_el][2][hrir_taps] (what hrtf_load was
         given), one direction per image, always two channels (left, right).  Returns as conv_ir_from_room does; the
         taps are [2][taps]."""
-        d = np.ascontiguousarray(np.asarray(desc, dtype=ROOM_IR_DTYPE).reshape(-1)[:1])
-        h = np.ascontiguousarray(np.asarray(hrir, dtype=np.float32))
-        assert h.ndim == 3 and h.shape[0] == int(n_az) * int(n_el) and h.shape[1] == 2, h.shape
-        taps_out = np.zeros((2, int(taps)), dtype=np.float32) if want_taps else None
-        out = C.c_uint32()
-        rc = self.lib.gas_conv_ir_from_room_hrtf(self.h, _np_ptr(d), _np_ptr(h), int(n_az), int(n_el), h.shape[2], int(taps), _np_ptr(taps_out) if want_taps else None, C.byref(out) if load else None)
-        self._check(rc, "gas_conv_ir_from_room_hrtf")
-        if load and want_taps:
-            return out.value, taps_out
-        return out.value if load else taps_out
+        return self._conv_ir_generate("gas_conv_ir_from_room_hrtf", [(desc, ROOM_IR_DTYPE)], hrir, n_az, n_el, None, taps, want_taps, load)
 
     def conv_ir_from_room_bands(self, desc, bands, channels, taps, want_taps=False, load=True):
         """conv_ir_from_room with per-band wall reflectances and air absorption (bands: one ROOM_BANDS_DTYPE entry, see
         default_room_bands); desc's own room.reflectance is validated but not used.  Returns as conv_ir_from_room does."""
-        d = np.ascontiguousarray(np.asarray(desc, dtype=ROOM_IR_DTYPE).reshape(-1)[:1])
-        b = np.ascontiguousarray(np.asarray(bands, dtype=ROOM_BANDS_DTYPE).reshape(-1)[:1])
-        taps_out = np.zeros((int(channels), int(taps)), dtype=np.float32) if want_taps else None
-        out = C.c_uint32()
-        rc = self.lib.gas_conv_ir_from_room_bands(self.h, _np_ptr(d), _np_ptr(b), int(channels), int(taps), _np_ptr(taps_out) if want_taps else None, C.byref(out) if load else None)
-        self._check(rc, "gas_conv_ir_from_room_bands")
-        if load and want_taps:
-            return out.value, taps_out
-        return out.value if load else taps_out
+        return self._conv_ir_generate("gas_conv_ir_from_room_bands", [(desc, ROOM_IR_DTYPE), (bands, ROOM_BANDS_DTYPE)], None, 0, 0, channels, taps, want_taps, load)
 
     def conv_ir_from_room_hrtf_bands(self, desc, bands, hrir, n_az, n_el, taps, want_taps=False, load=True):
         """conv_ir_from_room_hrtf with per-band wall reflectances and air absorption; arguments as conv_ir_from_room_bands
         and conv_ir_from_room_hrtf, the taps are [2][taps]."""
-        d = np.ascontiguousarray(np.asarray(desc, dtype=ROOM_IR_DTYPE).reshape(-1)[:1])
-        b = np.ascontiguousarray(np.asarray(bands, dtype=ROOM_BANDS_DTYPE).reshape(-1)[:1])
-        h = np.ascontiguousarray(np.asarray(hrir, dtype=np.float32))
-        assert h.ndim == 3 and h.shape[0] == int(n_az) * int(n_el) and h.shape[1] == 2, h.shape
-        taps_out = np.zeros((2, int(taps)), dtype=np.float32) if want_taps else None
-        out = C.c_uint32()
-        rc = self.lib.gas_conv_ir_from_room_hrtf_bands(self.h, _np_ptr(d), _np_ptr(b), _np_ptr(h), int(n_az), int(n_el), h.shape[2], int(taps), _np_ptr(taps_out) if want_taps else None, C.byref(out) if load else None)
-        self._check(rc, "gas_conv_ir_from_room_hrtf_bands")
-        if load and want_taps:
-            return out.value, taps_out
-        return out.value if load else taps_out
+        return self._conv_ir_generate("gas_conv_ir_from_room_hrtf_bands", [(desc, ROOM_IR_DTYPE), (bands, ROOM_BANDS_DTYPE)], hrir, n_az, n_el, None, taps, want_taps, load)
 
     def conv_ir_from_room_diffuse(self, desc, bands, tail, channels, taps, want_taps=False, load=True):
         """conv_ir_from_room_bands with a diffuse late tail: image sources up to tail's mixing time, then a cross-fade into
         noise that decays per band as the room's mean absorption says (tail: one ROOM_TAIL_DTYPE entry, see
         default_room_tail).  Returns as conv_ir_from_room does."""
-        d = np.ascontiguousarray(np.asarray(desc, dtype=ROOM_IR_DTYPE).reshape(-1)[:1])
-        b = np.ascontiguousarray(np.asarray(bands, dtype=ROOM_BANDS_DTYPE).reshape(-1)[:1])
-        t = np.ascontiguousarray(np.asarray(tail, dtype=ROOM_TAIL_DTYPE).reshape(-1)[:1])
-        taps_out = np.zeros((int(channels), int(taps)), dtype=np.float32) if want_taps else None
-        out = C.c_uint32()
-        rc = self.lib.gas_conv_ir_from_room_diffuse(self.h, _np_ptr(d), _np_ptr(b), _np_ptr(t), int(channels), int(taps), _np_ptr(taps_out) if want_taps else None, C.byref(out) if load else None)
-        self._check(rc, "gas_conv_ir_from_room_diffuse")
-        if load and want_taps:
-            return out.value, taps_out
-        return out.value if load else taps_out
+        return self._conv_ir_generate("gas_conv_ir_from_room_diffuse", [(desc, ROOM_IR_DTYPE), (bands, ROOM_BANDS_DTYPE), (tail, ROOM_TAIL_DTYPE)], None, 0, 0, channels, taps, want_taps, load)
 
     def conv_ir_from_room_hrtf_diffuse(self, desc, bands, tail, hrir, n_az, n_el, taps, want_taps=False, load=True):
         """conv_ir_from_room_hrtf_bands with a diffuse late tail; arguments as conv_ir_from_room_diffuse and
         conv_ir_from_room_hrtf, the taps are [2][taps]."""
-        d = np.ascontiguousarray(np.asarray(desc, dtype=ROOM_IR_DTYPE).reshape(-1)[:1])
-        b = np.ascontiguousarray(np.asarray(bands, dtype=ROOM_BANDS_DTYPE).reshape(-1)[:1])
-        t = np.ascontiguousarray(np.asarray(tail, dtype=ROOM_TAIL_DTYPE).reshape(-1)[:1])
-        h = np.ascontiguousarray(np.asarray(hrir, dtype=np.float32))
-        assert h.ndim == 3 and h.shape[0] == int(n_az) * int(n_el) and h.shape[1] == 2, h.shape
-        taps_out = np.zeros((2, int(taps)), dtype=np.float32) if want_taps else None
-        out = C.c_uint32()
-        rc = self.lib.gas_conv_ir_from_room_hrtf_diffuse(self.h, _np_ptr(d), _np_ptr(b), _np_ptr(t), _np_ptr(h), int(n_az), int(n_el), h.shape[2], int(taps), _np_ptr(taps_out) if want_taps else None, C.byref(out) if load else None)
-        self._check(rc, "gas_conv_ir_from_room_hrtf_diffuse")
-        if load and want_taps:
-            return out.value, taps_out
-        return out.value if load else taps_out
+        return self._conv_ir_generate("gas_conv_ir_from_room_hrtf_diffuse", [(desc, ROOM_IR_DTYPE), (bands, ROOM_BANDS_DTYPE), (tail, ROOM_TAIL_DTYPE)], hrir, n_az, n_el, None, taps, want_taps, load)
 
     def conv_create(self, ir):
         out = C.c_uint32()

@@ -654,84 +654,76 @@ static bool room_tail_plans(const gas_room_ir &desc, const gas_room_bands &bands
 	return gas_room_ir_make_plan(d, receivers, K1, rate, lattice) && gas_room_tail_make_plan(lattice, bands, tail, channels, taps, K0, K1, tp);
 }
 
-// gas_conv_ir_from_room, gas_conv_ir_from_room_bands and gas_conv_ir_from_room_diffuse: `call` says which, so that a NULL
-// bands or tail is refused by the calls that need it.
-static int conv_ir_from_room_any(gas_ctx *c, const gas_room_ir *desc, RoomCall call, const gas_room_bands *bands, const gas_room_tail *tail, uint32_t channels, uint32_t taps, float *out_taps, uint32_t *out_ir) {
-	const bool banded = call != ROOM_PLAIN;
-	if (!c || !desc || (banded && !bands) || (call == ROOM_DIFFUSE && !tail) || (!out_taps && !out_ir) || (channels != 1 && channels != 2) || taps == 0) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
+// What every generator checks once its arguments are there: registering (out_ir) needs a reserve, and `taps` must fit
+// that reserve, or GAS_CONV_MAX_IR_TAPS for the pure generator.
+static int conv_ir_room_for(const gas_ctx *c, uint32_t taps, const uint32_t *out_ir) {
 	if (out_ir && c->conv.count == 0) {
 		return GAS_ERR_UNSUPPORTED_CHAIN;
 	}
 	if (taps > (out_ir ? c->conv.max_taps : (uint32_t)GAS_CONV_MAX_IR_TAPS)) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
-	gas_room_ir_plan plan;
-	gas_room_tail_plan tp;
-	if (!room_ir_desc_ok(*desc, true) || (banded && !room_bands_ok(*bands, c->cfg.mix_rate))) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	if (call == ROOM_DIFFUSE ? !room_tail_plans(*desc, *bands, *tail, channels, channels, taps, c->cfg.mix_rate, plan, tp) : !gas_room_ir_make_plan(*desc, channels, taps, c->cfg.mix_rate, plan)) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
-	return conv_ir_from_plan(c, *desc, plan, channels, nullptr, bands, call == ROOM_DIFFUSE ? &tp : nullptr, out_taps, out_ir);
+	return GAS_OK;
 }
 
-static int conv_ir_from_room_hrtf_any(gas_ctx *c, const gas_room_ir *desc, RoomCall call, const gas_room_bands *bands, const gas_room_tail *tail, const float *hrir, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps, uint32_t taps, float *out_taps, uint32_t *out_ir) {
+// The six box-room calls: `call` says which of the three names, so that a NULL bands or tail is refused by the calls
+// that need it.  set == nullptr: the plain calls, `channels` receivers.  Otherwise the *_hrtf calls: one receiver (the
+// listener; ear_spacing is not read) heard through the set, and two channels whatever `channels` says.
+static int conv_ir_from_room_any(gas_ctx *c, const gas_room_ir *desc, RoomCall call, const gas_room_bands *bands, const gas_room_tail *tail, const RoomIrSet *set, uint32_t channels, uint32_t taps, float *out_taps, uint32_t *out_ir) {
 	const bool banded = call != ROOM_PLAIN;
-	if (!c || !desc || (banded && !bands) || (call == ROOM_DIFFUSE && !tail) || !hrir || (!out_taps && !out_ir) || taps == 0) {
+	if (!c || !desc || (banded && !bands) || (call == ROOM_DIFFUSE && !tail) || (!out_taps && !out_ir) || (set ? !set->hrir : channels != 1 && channels != 2) || taps == 0) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
-	if (n_az == 0 || n_el == 0 || (uint64_t)n_az * n_el > 65536u || hrir_taps == 0 || hrir_taps > GAS_HRTF_TAPS) {
+	if (set && (set->n_az == 0 || set->n_el == 0 || (uint64_t)set->n_az * set->n_el > 65536u || set->taps == 0 || set->taps > GAS_HRTF_TAPS)) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
-	if (out_ir && c->conv.count == 0) {
-		return GAS_ERR_UNSUPPORTED_CHAIN;
-	}
-	if (taps > (out_ir ? c->conv.max_taps : (uint32_t)GAS_CONV_MAX_IR_TAPS)) {
-		return GAS_ERR_INVALID_ARGUMENT;
+	GAS_TRY(conv_ir_room_for(c, taps, out_ir));
+	const uint32_t receivers = set ? 1u : channels;
+	if (set) {
+		channels = 2;
 	}
 	gas_room_ir_plan plan;
 	gas_room_tail_plan tp;
-	if (!room_ir_desc_ok(*desc, false) || (banded && !room_bands_ok(*bands, c->cfg.mix_rate))) {
+	if (!room_ir_desc_ok(*desc, !set) || (banded && !room_bands_ok(*bands, c->cfg.mix_rate))) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
-	if (call == ROOM_DIFFUSE ? !room_tail_plans(*desc, *bands, *tail, 1, 2, taps, c->cfg.mix_rate, plan, tp) : !gas_room_ir_make_plan(*desc, 1, taps, c->cfg.mix_rate, plan)) { // one receiver: ear_spacing is not read
+	if (call == ROOM_DIFFUSE ? !room_tail_plans(*desc, *bands, *tail, receivers, channels, taps, c->cfg.mix_rate, plan, tp) : !gas_room_ir_make_plan(*desc, receivers, taps, c->cfg.mix_rate, plan)) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
-	const size_t floats = (size_t)n_az * n_el * 2 * hrir_taps;
+	const size_t floats = set ? (size_t)set->n_az * set->n_el * 2 * set->taps : 0;
 	for (size_t i = 0; i < floats; i++) {
-		if (!(std::fabs(hrir[i]) <= 4.0f)) { // not finite, or a tap could pass 4 v per image: the int64 sums' bound
+		if (!(std::fabs(set->hrir[i]) <= 4.0f)) { // not finite, or a tap could pass 4 v per image: the int64 sums' bound
 			return GAS_ERR_INVALID_ARGUMENT;
 		}
 	}
-	const RoomIrSet set{hrir, n_az, n_el, hrir_taps};
-	return conv_ir_from_plan(c, *desc, plan, 2, &set, bands, call == ROOM_DIFFUSE ? &tp : nullptr, out_taps, out_ir);
+	return conv_ir_from_plan(c, *desc, plan, channels, set, bands, call == ROOM_DIFFUSE ? &tp : nullptr, out_taps, out_ir);
 }
 
 int gas_conv_ir_from_room(gas_ctx *c, const gas_room_ir *desc, uint32_t channels, uint32_t taps, float *out_taps, uint32_t *out_ir) {
-	return conv_ir_from_room_any(c, desc, ROOM_PLAIN, nullptr, nullptr, channels, taps, out_taps, out_ir);
+	return conv_ir_from_room_any(c, desc, ROOM_PLAIN, nullptr, nullptr, nullptr, channels, taps, out_taps, out_ir);
 }
 
 int gas_conv_ir_from_room_hrtf(gas_ctx *c, const gas_room_ir *desc, const float *hrir, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps, uint32_t taps, float *out_taps, uint32_t *out_ir) {
-	return conv_ir_from_room_hrtf_any(c, desc, ROOM_PLAIN, nullptr, nullptr, hrir, n_az, n_el, hrir_taps, taps, out_taps, out_ir);
+	const RoomIrSet set{hrir, n_az, n_el, hrir_taps};
+	return conv_ir_from_room_any(c, desc, ROOM_PLAIN, nullptr, nullptr, &set, 2, taps, out_taps, out_ir);
 }
 
 int gas_conv_ir_from_room_bands(gas_ctx *c, const gas_room_ir *desc, const gas_room_bands *bands, uint32_t channels, uint32_t taps, float *out_taps, uint32_t *out_ir) {
-	return conv_ir_from_room_any(c, desc, ROOM_BANDS, bands, nullptr, channels, taps, out_taps, out_ir);
+	return conv_ir_from_room_any(c, desc, ROOM_BANDS, bands, nullptr, nullptr, channels, taps, out_taps, out_ir);
 }
 
 int gas_conv_ir_from_room_hrtf_bands(gas_ctx *c, const gas_room_ir *desc, const gas_room_bands *bands, const float *hrir, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps, uint32_t taps, float *out_taps, uint32_t *out_ir) {
-	return conv_ir_from_room_hrtf_any(c, desc, ROOM_BANDS, bands, nullptr, hrir, n_az, n_el, hrir_taps, taps, out_taps, out_ir);
+	const RoomIrSet set{hrir, n_az, n_el, hrir_taps};
+	return conv_ir_from_room_any(c, desc, ROOM_BANDS, bands, nullptr, &set, 2, taps, out_taps, out_ir);
 }
 
 int gas_conv_ir_from_room_diffuse(gas_ctx *c, const gas_room_ir *desc, const gas_room_bands *bands, const gas_room_tail *tail, uint32_t channels, uint32_t taps, float *out_taps, uint32_t *out_ir) {
-	return conv_ir_from_room_any(c, desc, ROOM_DIFFUSE, bands, tail, channels, taps, out_taps, out_ir);
+	return conv_ir_from_room_any(c, desc, ROOM_DIFFUSE, bands, tail, nullptr, channels, taps, out_taps, out_ir);
 }
 
 int gas_conv_ir_from_room_hrtf_diffuse(gas_ctx *c, const gas_room_ir *desc, const gas_room_bands *bands, const gas_room_tail *tail, const float *hrir, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps, uint32_t taps, float *out_taps, uint32_t *out_ir) {
-	return conv_ir_from_room_hrtf_any(c, desc, ROOM_DIFFUSE, bands, tail, hrir, n_az, n_el, hrir_taps, taps, out_taps, out_ir);
+	const RoomIrSet set{hrir, n_az, n_el, hrir_taps};
+	return conv_ir_from_room_any(c, desc, ROOM_DIFFUSE, bands, tail, &set, 2, taps, out_taps, out_ir);
 }
 
 // The planes road has no tables: the plan carries the planes, so its temporaries are the sums and the taps.  The
@@ -740,12 +732,7 @@ int gas_conv_ir_from_planes(gas_ctx *c, const gas_room_planes *desc, uint32_t ch
 	if (!c || !desc || (!out_taps && !out_ir) || (channels != 1 && channels != 2) || taps == 0) {
 		return GAS_ERR_INVALID_ARGUMENT;
 	}
-	if (out_ir && c->conv.count == 0) {
-		return GAS_ERR_UNSUPPORTED_CHAIN;
-	}
-	if (taps > (out_ir ? c->conv.max_taps : (uint32_t)GAS_CONV_MAX_IR_TAPS)) {
-		return GAS_ERR_INVALID_ARGUMENT;
-	}
+	GAS_TRY(conv_ir_room_for(c, taps, out_ir));
 	gas_room_planes_plan plan;
 	if (!room_planes_desc_ok(*desc) || !gas_room_planes_make_plan(*desc, channels, taps, c->cfg.mix_rate, plan)) {
 		return GAS_ERR_INVALID_ARGUMENT;

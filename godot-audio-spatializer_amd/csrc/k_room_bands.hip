@@ -26,7 +26,7 @@
 // outputs, B = 8, L = 1023: 0.32 ms -> 0.19 ms; a trip's loads, not its 16 FMAs, then set the time.  Both forms add the
 // same terms in the same order, so which one ran cannot be read from the bits.
 // Figures: profiles/room_bands_notes.md.
-#include "gas_internal.h"
+#include "gas_room_taps.h"
 
 #include <cmath>
 
@@ -58,7 +58,7 @@ __global__ __launch_bounds__(256) void k_room_bands_combine(gas_room_bands_plan 
 			const long long k = t0 - (long long)p.D + (long long)i;
 			double u = 0.0;
 			if (k >= 0 && k < (long long)p.taps) {
-				u = (double)row[k] * (1.0 / 4294967296.0);
+				u = (double)row[k] * (1.0 / GAS_ROOM_ONE);
 				if (lam != 0.0) { // uniform; at 0 g is exactly 1
 					u = u * exp(-(lam * (double)k));
 				}

@@ -6,81 +6,49 @@
 // needs comes from per-axis tables of running products, 2 N_a + 1 doubles per axis, built on the host as well: pow() would
 // tie the bits to a library.
 // Shape: one lane per cell of the candidate box, m_z fastest, so a wave's lanes hold neighbouring images whose distances
-// differ by about a room height each and whose taps therefore seldom collide.  A lane masks by |m|_1, computes its image,
-// and per receiver one distance, two shares and two 64-bit integer adds without return on global memory.  No LDS: the two
-// table values that are uniform over most of a wave and the third, read along the lanes, stay in cache.
+// differ by about a room height each and whose taps therefore seldom collide.  A lane takes its cell (gas_room_cell with
+// gas_room_cell_reflectance and gas_room_cell_image: the mask by |m|_1, R, the image) and per receiver deposits it
+// (gas_room_deposit: one distance, two shares and two 64-bit integer adds without return on global memory); all are
+// gas_room_taps.h's, shared with k_room_ir_hrtf below and with k_room_planes.hip.  No LDS: the two table values that
+// are uniform over most of a wave and the third, read along the lanes, stay in cache.
 // The sums are integers so that no order of arrival can change a bit; a second kernel scales them to float32
 // [channels][taps], the layout gas_launch_conv_ir reads.
 // Bound: 32 B of atomics per image and receiver against about sixty float64 operations; measured figures and the shell
 // variant that would replace the box walk: profiles/room_ir_notes.md.
 //
-// k_room_ir_hrtf -- gas_conv_ir_from_room_hrtf: the same lattice heard through an HRIR set.  A lane does for its cell what
-// k_room_ir does for one receiver and adds the direction of arrival in the listener's frame (the cell choice of
-// k_calc_spatialization's hrtf_dir).  An image that reaches a tap is then spread by its whole wave: the wave walks its
-// ballot of such lanes, takes each one's (k, a0, a1, dir) through lane reads, and per ear its 64 lanes stride over the
-// hrir_taps + 1 taps of the HRIR shifted by the fractional delay, so one wave instruction adds to 64 consecutive int64
-// (512 contiguous bytes) without return.  Nothing crosses a wave: no LDS, no barrier, and a lane that fails a mask stays
-// for the spreading instead of returning.  Bound: up to 2 (hrir_taps + 1) adds of 8 bytes per image, 514 at 256 taps
-// against 4 above; figures: profiles/room_brir_notes.md.  tests/room_brir_ref.py restates the rule in numpy.
-#include "gas_internal.h"
-
-#include <cmath>
-
-// No FMA contraction, on the host or on the device: the rule fixes the order of the float64 operations, and
-// `dist - d0` cancels for images close to the direct path.
-#pragma clang fp contract(off)
+// k_room_ir_hrtf -- gas_conv_ir_from_room_hrtf: the same lattice heard through an HRIR set.  A lane takes its cell and its
+// arrival at the one receiver (gas_room_cell, gas_room_arrival) and adds the direction of arrival in the listener's frame
+// (the cell choice of k_calc_spatialization's hrtf_dir).  An image that reaches a tap is then spread by its whole wave:
+// the wave walks its ballot of such lanes, takes each one's (k, a0, a1, dir) through lane reads, and per ear its 64 lanes
+// stride over the hrir_taps + 1 taps of the HRIR shifted by the fractional delay, so one wave instruction adds to 64
+// consecutive int64 (512 contiguous bytes) without return.  Nothing crosses a wave: no LDS, no barrier, and a lane that
+// fails a mask stays for the spreading instead of returning.  Bound: up to 2 (hrir_taps + 1) adds of 8 bytes per image,
+// 514 at 256 taps against 4 above; figures: profiles/room_brir_notes.md.  tests/room_brir_ref.py restates the rule in numpy.
+// FMA contraction is off for the whole unit, host plan included: gas_room_taps.h sets it.
+#include "gas_room_taps.h"
 
 namespace {
-
-constexpr double ROOM_IR_ONE = 4294967296.0; // 2^32: a share of 1 as an integer
 
 __global__ __launch_bounds__(256) void k_room_ir(gas_room_ir_plan p, const double *__restrict__ tables, unsigned long long *__restrict__ acc) {
 	const uint32_t id = blockIdx.x * 256u + threadIdx.x;
 	if (id >= p.cells) {
 		return;
 	}
-	const uint32_t wz = 2u * p.N[2] + 1u, wy = 2u * p.N[1] + 1u;
-	const uint32_t iz = id % wz, rest = id / wz;
-	const uint32_t iy = rest % wy, ix = rest / wy;
-	const int m[3] = {(int)ix - (int)p.N[0], (int)iy - (int)p.N[1], (int)iz - (int)p.N[2]};
-	const uint32_t order = (uint32_t)((m[0] < 0 ? -m[0] : m[0]) + (m[1] < 0 ? -m[1] : m[1]) + (m[2] < 0 ? -m[2] : m[2]));
-	if (order < p.min_order || (p.max_order != 0 && order > p.max_order)) {
+	// step 3
+	int m[3];
+	uint32_t at[3];
+	if (!gas_room_cell(p, id, m, at)) {
 		return;
 	}
-	// step 3
-	const double *tx = tables, *ty = tx + (2u * p.N[0] + 1u), *tz = ty + wy;
-	const double R = (tx[ix] * ty[iy]) * tz[iz];
+	const double R = gas_room_cell_reflectance(p, at, tables);
 	if (!(R > 0.0)) {
 		return; // every share would quantise to 0
 	}
 	double img[3];
-#pragma unroll
-	for (int a = 0; a < 3; a++) {
-		img[a] = (double)(2 * m[a]) * p.h[a] + ((m[a] & 1) ? -p.s[a] : p.s[a]);
-	}
-	// step 4
+	gas_room_cell_image(p, m, img);
+	// steps 4 and 5
 	for (uint32_t e = 0; e < p.channels; e++) {
-		const double dx = img[0] - p.e[e][0], dy = img[1] - p.e[e][1], dz = img[2] - p.e[e][2];
-		const double dist = sqrt(dx * dx + dy * dy + dz * dz);
-		const double v = R * p.d0 / fmax(dist, p.d0);
-		const double pos = (dist - p.d0) / p.c * p.rate;
-		const double kf = floor(pos);
-		const double f = pos - kf;
-		// the box bounds pos by taps + a few frames; the comparison in double first keeps the conversion defined whatever comes
-		if (!(kf >= -1.0) || !(kf < (double)p.taps)) {
-			continue;
-		}
-		const long long k = (long long)kf; // -1 .. taps - 1
-		unsigned long long *row = acc + (size_t)e * p.taps;
-		// step 5: shares are in [0, 1], so the integers are in [0, 2^32]
-		const unsigned long long q0 = (unsigned long long)llrint(v * (1.0 - f) * ROOM_IR_ONE);
-		const unsigned long long q1 = (unsigned long long)llrint(v * f * ROOM_IR_ONE);
-		if (k >= 0 && q0 != 0) {
-			atomicAdd(row + k, q0); // result unused: the no-return form
-		}
-		if (k + 1 < (long long)p.taps && q1 != 0) {
-			atomicAdd(row + k + 1, q1);
-		}
+		gas_room_deposit(img, p.e[e], R, p.d0, p.c, p.rate, p.taps, acc + (size_t)e * p.taps);
 	}
 }
 
@@ -88,7 +56,7 @@ __global__ __launch_bounds__(256) void k_room_ir(gas_room_ir_plan p, const doubl
 __global__ __launch_bounds__(256) void k_room_ir_scale(const long long *__restrict__ acc, uint32_t n, double level, float *__restrict__ out) {
 	const uint32_t i = blockIdx.x * 256u + threadIdx.x;
 	if (i < n) {
-		out[i] = (float)(level * (double)acc[i] * (1.0 / ROOM_IR_ONE));
+		out[i] = (float)(level * (double)acc[i] * (1.0 / GAS_ROOM_ONE));
 	}
 }
 
@@ -106,31 +74,20 @@ __global__ __launch_bounds__(256) void k_room_ir_hrtf(gas_room_ir_plan p, gas_ro
 	int k = 0;
 	uint32_t dir = 0;
 	if (id < p.cells) {
-		const uint32_t wz = 2u * p.N[2] + 1u, wy = 2u * p.N[1] + 1u;
-		const uint32_t iz = id % wz, rest = id / wz;
-		const uint32_t iy = rest % wy, ix = rest / wy;
-		const int m[3] = {(int)ix - (int)p.N[0], (int)iy - (int)p.N[1], (int)iz - (int)p.N[2]};
-		const uint32_t order = (uint32_t)((m[0] < 0 ? -m[0] : m[0]) + (m[1] < 0 ? -m[1] : m[1]) + (m[2] < 0 ? -m[2] : m[2]));
-		if (order >= p.min_order && (p.max_order == 0 || order <= p.max_order)) {
-			// step 1 (steps 1 - 3 of gas_conv_ir_from_room)
-			const double *tx = tables, *ty = tx + (2u * p.N[0] + 1u), *tz = ty + wy;
-			const double R = (tx[ix] * ty[iy]) * tz[iz];
+		// step 1 (steps 1 - 3 of gas_conv_ir_from_room)
+		int m[3];
+		uint32_t at[3];
+		if (gas_room_cell(p, id, m, at)) {
+			const double R = gas_room_cell_reflectance(p, at, tables);
 			double w[3];
+			gas_room_cell_image(p, m, w);
 #pragma unroll
 			for (int a = 0; a < 3; a++) {
-				w[a] = ((double)(2 * m[a]) * p.h[a] + ((m[a] & 1) ? -p.s[a] : p.s[a])) - p.e[0][a];
+				w[a] = w[a] - p.e[0][a];
 			}
-			// step 2
-			const double dist = sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-			const double v = R * p.d0 / fmax(dist, p.d0);
-			const double pos = (dist - p.d0) / p.c * p.rate;
-			const double kf = floor(pos);
-			const double f = pos - kf;
-			if (R > 0.0 && kf >= -1.0 && kf < (double)p.taps) { // taps <= 2^20: k fits an int
+			// step 2; an image with R == 0 stays out (every share would quantise to 0)
+			if (gas_room_arrival(sqrt(gas_room_len2(w[0], w[1], w[2])), R, p.d0, p.c, p.rate, p.taps, k, a0, a1) && R > 0.0) { // taps <= 2^20: k fits an int
 				hit = true;
-				k = (int)kf;
-				a0 = v * (1.0 - f);
-				a1 = v * f;
 				// step 3: into the global frame, then into the listener's
 				double g[3], q[3];
 #pragma unroll
@@ -171,7 +128,7 @@ __global__ __launch_bounds__(256) void k_room_ir_hrtf(gas_room_ir_plan p, gas_ro
 				}
 				const double hj = j < hrir_taps ? (double)H[j] : 0.0;
 				const double hp = j > 0 ? (double)H[j - 1] : 0.0;
-				const long long q = llrint((b0 * hj + b1 * hp) * ROOM_IR_ONE); // |.| <= 4 v 2^32 <= 2^34
+				const long long q = llrint((b0 * hj + b1 * hp) * GAS_ROOM_ONE); // |.| <= 4 v 2^32 <= 2^34
 				if (q != 0) {
 					atomicAdd(row + t, (unsigned long long)q); // result unused: the no-return form; a negative q wraps as the sum of int64 does
 				}
@@ -207,15 +164,9 @@ bool gas_room_ir_make_plan(const gas_room_ir &d, uint32_t channels, uint32_t tap
 			return false;
 		}
 	}
-	const double dx = p.s[0] - l[0], dy = p.s[1] - l[1], dz = p.s[2] - l[2];
-	p.d0 = std::sqrt(dx * dx + dy * dy + dz * dz);
-	if (!(p.d0 >= 1e-3)) {
-		return false;
-	}
 	const double half = (double)d.ear_spacing / 2.0;
-	for (int a = 0; a < 3; a++) {
-		p.e[0][a] = channels == 1 ? l[a] : l[a] - half * r[a];
-		p.e[1][a] = channels == 1 ? l[a] : l[a] + half * r[a];
+	if (!gas_room_receivers(p.s, l, r, half, channels, p.d0, p.e)) {
+		return false;
 	}
 	p.c = (double)room.speed_of_sound;
 	p.rate = (double)rate;
@@ -268,17 +219,10 @@ void gas_room_ir_fill_tables(const gas_room_ir &d, const gas_room_ir_plan &p, do
 }
 
 hipError_t gas_launch_room_ir(hipStream_t stream, const gas_room_ir_plan &p, const double *d_tables, long long *d_acc, float *d_out) {
-	const uint32_t n = p.channels * p.taps;
-	hipError_t e = hipMemsetAsync(d_acc, 0, sizeof(long long) * n, stream);
-	if (e != hipSuccess) {
-		return e;
-	}
-	hipLaunchKernelGGL(k_room_ir, dim3((p.cells + 255u) / 256u), dim3(256), 0, stream, p, d_tables, reinterpret_cast<unsigned long long *>(d_acc));
-	e = hipGetLastError();
-	if (e != hipSuccess) {
-		return e;
-	}
-	return gas_launch_room_ir_scale(stream, d_acc, n, p.level, d_out);
+	return gas_room_launch_sums(stream, d_acc, p.channels * p.taps, p.level, d_out, [&](unsigned long long *acc) {
+		hipLaunchKernelGGL(k_room_ir, dim3((p.cells + 255u) / 256u), dim3(256), 0, stream, p, d_tables, acc);
+		return hipGetLastError();
+	});
 }
 
 hipError_t gas_launch_room_ir_hrtf(hipStream_t stream, const gas_room_ir_plan &p, const gas_room_ir &d, const double *d_tables, const float *d_hrir, uint32_t n_az, uint32_t n_el, uint32_t hrir_taps, long long *d_acc, float *d_out) {
@@ -289,15 +233,8 @@ hipError_t gas_launch_room_ir_hrtf(hipStream_t stream, const gas_room_ir_plan &p
 			fr.L[a][b] = (double)d.listener.basis[a][b];
 		}
 	}
-	const uint32_t n = 2u * p.taps;
-	hipError_t e = hipMemsetAsync(d_acc, 0, sizeof(long long) * n, stream);
-	if (e != hipSuccess) {
-		return e;
-	}
-	hipLaunchKernelGGL(k_room_ir_hrtf, dim3((p.cells + 255u) / 256u), dim3(256), 0, stream, p, fr, d_tables, d_hrir, n_az, n_el, hrir_taps, reinterpret_cast<unsigned long long *>(d_acc));
-	e = hipGetLastError();
-	if (e != hipSuccess) {
-		return e;
-	}
-	return gas_launch_room_ir_scale(stream, d_acc, n, p.level, d_out);
+	return gas_room_launch_sums(stream, d_acc, 2u * p.taps, p.level, d_out, [&](unsigned long long *acc) {
+		hipLaunchKernelGGL(k_room_ir_hrtf, dim3((p.cells + 255u) / 256u), dim3(256), 0, stream, p, fr, d_tables, d_hrir, n_az, n_el, hrir_taps, acc);
+		return hipGetLastError();
+	});
 }

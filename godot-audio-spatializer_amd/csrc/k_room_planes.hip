@@ -7,9 +7,10 @@
 // Shape: one lane per candidate sequence.  The flat index decodes to an order and then to digits, most significant
 // first, so neighbouring lanes share a prefix: they reflect the same images, fail the same `t > 0` and leave the image
 // loop together.  A lane builds its up to eight images (step 3), then per receiver walks the path back from the receiver
-// (step 4: one intersection and P - 1 face tests per reflection) and, for a valid path, does what k_room_ir does for an
-// image: one distance, two shares, two 64-bit integer adds without return on global memory.  The sums are integers, so
-// no order of arrival can change a bit; k_room_ir's scaling kernel turns them into float32 [channels][taps].
+// (step 4: one intersection and P - 1 face tests per reflection) and, for a valid path, deposits the last image as
+// k_room_ir deposits a cell's (gas_room_taps.h's gas_room_deposit, step 5; the direct sound goes the same way).  The
+// sums are integers, so no order of arrival can change a bit; k_room_ir's scaling kernel turns them into float32
+// [channels][taps].
 // No LDS, no barrier, no wave operation: a lane may return wherever its sequence is settled -- a void sequence, R == 0
 // (every share would quantise to 0), or a prefix image further from every receiver than any tap reaches: reflecting a
 // point that is inside a half-space moves it away from every point inside the room, so the images after it are further
@@ -17,44 +18,15 @@
 // The images and digits live in registers: every loop over the order has a compile-time bound and a guard, so nothing
 // is indexed by a run-time value but the plan itself.  Bound: float64 VALU -- per sequence and receiver about
 // K (12 + 6 (P - 1)) operations against at most 32 B of atomics; measured figures: profiles/room_planes_notes.md.
-#include "gas_internal.h"
-
-#include <cmath>
-
-// No FMA contraction, on the host or on the device: the rule fixes the order of the float64 operations.
-#pragma clang fp contract(off)
+// FMA contraction is off for the whole unit, host plan included: gas_room_taps.h sets it.
+#include "gas_room_taps.h"
 
 namespace {
 
-constexpr double ROOM_PLANES_ONE = 4294967296.0; // 2^32: a share of 1 as an integer
 constexpr int MAX_K = GAS_ROOM_PLANES_MAX_ORDER;
 
 __host__ __device__ __forceinline__ double dot3(const double n[3], const double x[3]) {
 	return (n[0] * x[0] + n[1] * x[1]) + n[2] * x[2];
-}
-
-// step 5 for one image and one receiver: steps 4 and 5 of gas_conv_ir_from_room
-__device__ __forceinline__ void add_taps(const gas_room_planes_plan &p, const double img[3], const double ear[3], double R, unsigned long long *__restrict__ row) {
-	const double dx = img[0] - ear[0], dy = img[1] - ear[1], dz = img[2] - ear[2];
-	const double dist = sqrt(dx * dx + dy * dy + dz * dz);
-	const double v = R * p.d0 / fmax(dist, p.d0);
-	const double pos = (dist - p.d0) / p.c * p.rate;
-	const double kf = floor(pos);
-	const double f = pos - kf;
-	// the comparison in double first keeps the conversion defined whatever comes (a NaN is dropped here)
-	if (!(kf >= -1.0) || !(kf < (double)p.taps)) {
-		return;
-	}
-	const long long k = (long long)kf; // -1 .. taps - 1
-	// shares are in [0, 1], so the integers are in [0, 2^32]
-	const unsigned long long q0 = (unsigned long long)llrint(v * (1.0 - f) * ROOM_PLANES_ONE);
-	const unsigned long long q1 = (unsigned long long)llrint(v * f * ROOM_PLANES_ONE);
-	if (k >= 0 && q0 != 0) {
-		atomicAdd(row + k, q0); // result unused: the no-return form
-	}
-	if (k + 1 < (long long)p.taps && q1 != 0) {
-		atomicAdd(row + k + 1, q1);
-	}
 }
 
 __global__ __launch_bounds__(256) void k_room_planes(gas_room_planes_plan p, unsigned long long *__restrict__ acc) {
@@ -64,7 +36,7 @@ __global__ __launch_bounds__(256) void k_room_planes(gas_room_planes_plan p, uns
 	}
 	if (id == 0 && p.direct) { // step 2's direct sound: nothing to reflect and nothing to validate
 		for (uint32_t e = 0; e < p.channels; e++) {
-			add_taps(p, p.s, p.e[e], 1.0, acc + (size_t)e * p.taps);
+			gas_room_deposit(p.s, p.e[e], 1.0, p.d0, p.c, p.rate, p.taps, acc + (size_t)e * p.taps);
 		}
 	}
 	// the order, then the digits' value within it
@@ -108,8 +80,7 @@ __global__ __launch_bounds__(256) void k_room_planes(gas_room_planes_plan p, uns
 			}
 			bool far = true;
 			for (uint32_t e = 0; e < p.channels; e++) {
-				const double dx = at[0] - p.e[e][0], dy = at[1] - p.e[e][1], dz = at[2] - p.e[e][2];
-				far = far && (dx * dx + dy * dy + dz * dz > p.far2);
+				far = far && (gas_room_len2(at[0] - p.e[e][0], at[1] - p.e[e][1], at[2] - p.e[e][2]) > p.far2);
 			}
 			if (far) {
 				return; // no image made from this one reaches a tap
@@ -147,7 +118,7 @@ __global__ __launch_bounds__(256) void k_room_planes(gas_room_planes_plan p, uns
 			}
 		}
 		if (valid) {
-			add_taps(p, at, ear, R, acc + (size_t)e * p.taps);
+			gas_room_deposit(at, ear, R, p.d0, p.c, p.rate, p.taps, acc + (size_t)e * p.taps);
 		}
 	}
 }
@@ -159,7 +130,7 @@ bool gas_room_planes_make_plan(const gas_room_planes &d, uint32_t channels, uint
 	p.P = d.n_planes;
 	for (uint32_t j = 0; j < p.P; j++) {
 		const double x = (double)d.planes[j].normal[0], y = (double)d.planes[j].normal[1], z = (double)d.planes[j].normal[2];
-		const double len = std::sqrt((x * x + y * y) + z * z);
+		const double len = std::sqrt(gas_room_len2(x, y, z));
 		if (!(len >= 0.999) || !(len <= 1.001)) {
 			return false;
 		}
@@ -175,15 +146,9 @@ bool gas_room_planes_make_plan(const gas_room_planes &d, uint32_t channels, uint
 		l[a] = (double)d.listener.origin[a];
 		r[a] = (double)d.listener.basis[a][0];
 	}
-	const double dx = p.s[0] - l[0], dy = p.s[1] - l[1], dz = p.s[2] - l[2];
-	p.d0 = std::sqrt((dx * dx + dy * dy) + dz * dz);
-	if (!(p.d0 >= 1e-3)) {
-		return false;
-	}
 	const double half = (double)d.ear_spacing / 2.0;
-	for (int a = 0; a < 3; a++) {
-		p.e[0][a] = channels == 1 ? l[a] : l[a] - half * r[a];
-		p.e[1][a] = channels == 1 ? l[a] : l[a] + half * r[a];
+	if (!gas_room_receivers(p.s, l, r, half, channels, p.d0, p.e)) {
+		return false;
 	}
 	for (uint32_t j = 0; j < p.P; j++) {
 		if (!(dot3(p.n[j], p.s) - p.d[j] > 0.0) || !(dot3(p.n[j], p.e[0]) - p.d[j] > 0.0) || !(dot3(p.n[j], p.e[1]) - p.d[j] > 0.0)) {
@@ -222,17 +187,11 @@ bool gas_room_planes_make_plan(const gas_room_planes &d, uint32_t channels, uint
 }
 
 hipError_t gas_launch_room_planes(hipStream_t stream, const gas_room_planes_plan &p, long long *d_acc, float *d_out) {
-	const uint32_t n = p.channels * p.taps;
-	hipError_t e = hipMemsetAsync(d_acc, 0, sizeof(long long) * n, stream);
-	if (e != hipSuccess) {
-		return e;
-	}
-	if (p.candidates != 0) { // P == 1 with min_order > 1 has none: a lone plane reflects once
-		hipLaunchKernelGGL(k_room_planes, dim3((p.candidates + 255u) / 256u), dim3(256), 0, stream, p, reinterpret_cast<unsigned long long *>(d_acc));
-		e = hipGetLastError();
-		if (e != hipSuccess) {
-			return e;
+	return gas_room_launch_sums(stream, d_acc, p.channels * p.taps, p.level, d_out, [&](unsigned long long *acc) {
+		if (p.candidates == 0) { // P == 1 with min_order > 1 has none: a lone plane reflects once
+			return hipSuccess;
 		}
-	}
-	return gas_launch_room_ir_scale(stream, d_acc, n, p.level, d_out);
+		hipLaunchKernelGGL(k_room_planes, dim3((p.candidates + 255u) / 256u), dim3(256), 0, stream, p, acc);
+		return hipGetLastError();
+	});
 }

@@ -17,7 +17,7 @@
 // Bound: float64 issue, not memory -- 55 us for B = 8 at 2^20 taps and two ears is 2.4 TB/s of stores where plain stores
 // reach 6, and about 130 float64 wave instructions per wave and band, the two trips through exp among them.
 // Figures: profiles/room_tail_notes.md.
-#include "gas_internal.h"
+#include "gas_room_taps.h"
 
 #include <algorithm>
 #include <cmath>
@@ -26,8 +26,6 @@
 #pragma clang fp contract(off)
 
 namespace {
-
-constexpr double ROOM_TAIL_ONE = 4294967296.0; // 2^32, as k_room_ir.hip's shares
 
 // Step 4: xi and f of tap k of ear e.
 __device__ __forceinline__ void tail_noise(uint32_t seed, uint32_t e, uint32_t k, double &xi, double &f) {
@@ -84,7 +82,7 @@ __global__ __launch_bounds__(256) void k_room_tail(gas_room_tail_plan p, const l
 			if (!mixes) {
 				q = spec[row * p.K1 + k]; // K0 <= K1
 			} else {
-				q = llrint((wd * d) * ROOM_TAIL_ONE);
+				q = llrint((wd * d) * GAS_ROOM_ONE);
 				if (k < p.K1) {
 					q += llrint(ws * (double)spec[row * p.K1 + k]);
 				}
